@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- AA coverage + composite throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth4096|synth8192|tiger2048]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth4096|synth8192|tiger2048] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+Everything else this file measures or checks -- the CPU baseline, parity against the CPU oracle, the cold / re-planned frames,
+the other BASELINE configurations, the roofline block, the multi-GPU companions and the all_gather of the strips -- runs only
+with `--full` (described below).
+
+`--dump-outputs DIR`: after the clock has stopped, what the last timed step computed is written to DIR as float32 / float64
+.npy files (inputs are the same from run to run, so two builds can be compared output for output).  An image small enough
+is written whole (`<name>.npy`); a larger one as a fixed, seeded sample of its pixels (`<name>_sample.npy`, the flat pixel
+indices in `<name>_sample_pixels.npy`) plus the float64 sum of every row (`<name>_row_sums.npy`).  At most 64 MB in all.
 
 One step = one full pass of the hot path over the scene, inputs resident in HBM when the clock
 starts: transform + flatten + bbox + band binning + cell classification + tile kernel (LDS delta scatter,
@@ -14,11 +24,13 @@ synthetic 10 000-path drawing @ 8192 x 8192, sharded over the N GPUs by strips o
 (`svgr_batch_set_bands`; every rank culls the geometry to what reaches its strips; edges that cross a strip border are
 simply kept by both owners: duplicated geometry is the halo, no pixel crosses a GPU, no data-path collective).  Total work is
 fixed; `value` = the drawing's path-pixels / the slowest rank's time.  RCCL carries the barrier / max-over-ranks clock and
-the optional all_gather of the strips (`all_gather_ms`, reported beside the step, never inside it).  The same line carries
-`single_gpu_same_scene` (rank 0 alone renders the whole drawing while the others wait: the denominator of the
+the optional all_gather of the strips (`all_gather_ms`, --full: reported beside the step, never inside it).  With --full the
+same line carries `single_gpu_same_scene` (rank 0 alone renders the whole drawing while the others wait: the denominator of the
 tile-parallel speed-up, measured in the same run) and `weak_scaling` (N stacked 4096-row blocks, one per GPU).
 
-Rank 0 prints ONE JSON line (contract in the task statement + `roofline` and `cpu_baseline`).
+Rank 0 prints ONE JSON line (the contract fields; with `--full` also `roofline`, `cpu_baseline`, `parity`, ...).
+With `--full` every `--time-every`-th timed step also brackets its stages with HIP events for the roofline block; a plain
+run's timed steps carry no events.
 
 `roofline`: the dominant kernel is k_tile_render, timed live by HIP events on the library's stream.  It keeps the delta
 tile and the canvas tile on chip, so what has to cross HBM per launch is the finished canvas once plus the geometry it reads:
@@ -118,32 +130,34 @@ def bench_scene(args):
 
     def step():
         layer, _hull = scene.render(tr, viewport=[0, 0, h, w], linear_rgb=False)
-        return layer._device()
+        layer._device()
+        return layer
 
-    # the FIRST render of the document in this process (leaf analysis, batch building, plans: what Scene.render retains for the
-    # renders that follow), then the same with the retained state dropped each time: what a caller who renders a document once pays
-    S.clear_render_cache()
-    ctx.sync()
-    c0 = time.perf_counter()
-    step()
-    ctx.sync()
-    first_ms = (time.perf_counter() - c0) * 1e3
-    cold, cold_listing = [], []
-    for _ in range(3):   # (with the opt-in cache on: the render also lists the document's paint arrays for the cache's guard)
+    if args.full:
+        # the FIRST render of the document in this process (leaf analysis, batch building, plans: what Scene.render retains for the
+        # renders that follow), then the same with the retained state dropped each time: what a caller who renders a document once pays
         S.clear_render_cache()
         ctx.sync()
         c0 = time.perf_counter()
         step()
         ctx.sync()
-        cold_listing.append((time.perf_counter() - c0) * 1e3)
-    S.set_render_cache(0)   # (the default: nothing kept between renders)
-    for _ in range(3):
-        ctx.sync()
-        c0 = time.perf_counter()
-        step()
-        ctx.sync()
-        cold.append((time.perf_counter() - c0) * 1e3)
-    S.set_render_cache(4)
+        first_ms = (time.perf_counter() - c0) * 1e3
+        cold, cold_listing = [], []
+        for _ in range(3):   # (with the opt-in cache on: the render also lists the document's paint arrays for the cache's guard)
+            S.clear_render_cache()
+            ctx.sync()
+            c0 = time.perf_counter()
+            step()
+            ctx.sync()
+            cold_listing.append((time.perf_counter() - c0) * 1e3)
+        S.set_render_cache(0)   # (the default: nothing kept between renders)
+        for _ in range(3):
+            ctx.sync()
+            c0 = time.perf_counter()
+            step()
+            ctx.sync()
+            cold.append((time.perf_counter() - c0) * 1e3)
+        S.set_render_cache(4)
     for _ in range(args.warmup):
         step()
     ctx.sync()
@@ -152,7 +166,21 @@ def bench_scene(args):
         keep = step()
     ctx.sync()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:   # the layer of the last timed render (its pixels as `.image` gives them, and its offset)
+        arrays = image_outputs("layer", keep._device().download(keep._shape, np.float64))
+        arrays["layer_offset"] = np.asarray(keep.offset, dtype=np.float64)
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays
     del keep
+    head = {
+        "metric": "canvas Mpixels/s through Scene.render (host walk + per-node launches; result resident in HBM)",
+        "value": round(h * w / dt / 1e6, 1), "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+    }
+    if not args.full:
+        print(json.dumps({**head, "dtype": "f64 arithmetic and f64 layers", "data": "real asset (scene dump)",
+                          "config": {"workload": desc, "canvas": [h, w]}}))
+        return
     # the picture of a warm render against the reference's own (sparse pins of its full-size float32 canvas, made by
     # oracle/gen_golden.py --full from the imported reference): after the clock has stopped
     parity = None
@@ -180,9 +208,7 @@ def bench_scene(args):
                 stream[k] = {"avg_us": round(v["counter_pass_avg_ns"] / 1e3, 1), "launches_per_step": v.get("kernel_trace_calls"),
                              "hbm_gbs": round(gbs, 1), "frac_of_8000": round(gbs / HBM_PEAK_GBS, 4)}
     print(json.dumps({
-        "metric": "canvas Mpixels/s through Scene.render (host walk + per-node launches; result resident in HBM)",
-        "value": round(h * w / dt / 1e6, 1), "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        **head,
         "first_render_ms": round(first_ms, 3), "cold_ms": round(min(cold), 3), "cold_with_cache_listing_ms": round(min(cold_listing), 3),
         "warm_what": "ms_per_step re-renders an unchanged document: Scene.render retains the leaf analysis and the built + planned batches "
                      "of a (scene, transform, viewport) between renders; cold_ms is a render with the cache off -- the default: nothing kept -- (best of 3), "
@@ -558,6 +584,42 @@ def contract_counts(got32, ref64):
             "what": "canvas of the last timed step, downloaded after the clock stopped"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: everything written, all ranks together
+DUMP_WHOLE_BYTES = 32 << 20      # an image up to this size is written whole
+DUMP_SAMPLE_PIXELS = 1 << 20     # ... a larger one as this many seeded pixels (split over the ranks) + its row sums
+DUMP_SEED = 0x5EED5
+
+
+def image_outputs(name, img, world=1):
+    """{file name: array} of one (rows, cols, channels) float image for --dump-outputs: whole, or a fixed seeded sample of its
+    pixels + the float64 sum of every row (which sees every value).  The sample depends only on the shape, never on the data."""
+    import numpy as np
+
+    img = np.ascontiguousarray(img)
+    assert img.dtype in (np.float32, np.float64), img.dtype
+    if img.nbytes <= DUMP_WHOLE_BYTES // max(world, 1):
+        return {name: img}
+    rows, cols = img.shape[:2]
+    flat = img.reshape(rows * cols, -1)
+    rng = np.random.default_rng(DUMP_SEED)
+    pix = np.unique(rng.integers(0, rows * cols, size=DUMP_SAMPLE_PIXELS // max(world, 1), dtype=np.int64))
+    return {f"{name}_sample": flat[pix], f"{name}_sample_pixels": pix.astype(np.float64),
+            f"{name}_row_sums": img.reshape(rows, -1).sum(axis=1, dtype=np.float64)}
+
+
+def dump_outputs(out_dir, arrays, world=1):
+    """Write {name: float32 / float64 array} as out_dir/<name>.npy; refuses to go past this rank's share of 64 MB."""
+    import numpy as np
+
+    total = sum(int(a.nbytes) for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES // max(world, 1):
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` started WITHOUT a launcher (no WORLD_SIZE in the environment): this process -- which has made no GPU
     kernel launch, allocation or context (counting the devices is the one runtime call it makes) and never re-execs -- starts the N ranks itself, one fresh child per GPU with RANK / LOCAL_RANK / WORLD_SIZE /
@@ -633,9 +695,14 @@ def launch_ranks(n, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200; 20 for the scene workloads)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=None, help="default: synth4096 on one GPU, synth8192 (config 4) on several")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR as .npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, parity, cold / re-planned frames, the other configurations, the roofline "
+                         "block and (N > 1) the companions; the --no-* / --cpu-paths / --time-every options below refine it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the `configs` array (the other BASELINE configurations)")
     ap.add_argument("--no-companions", action="store_true", help="N > 1: skip the single-GPU reference and the weak-scaling run")
@@ -644,6 +711,8 @@ def main():
                     help="bracket the stages of every n-th timed step with HIP events (each event drains the queue for ~8 us, "
                          "so timing every step would slow the thing being measured)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -675,9 +744,11 @@ def main():
     if args.workload in SCENE_WORKLOADS:
         if world > 1:
             raise SystemExit("the scene workloads run on one GPU")
-        if args.steps == 200:
+        if args.steps is None:
             args.steps = 20  # (tens of milliseconds per step)
         return bench_scene(args)
+    if args.steps is None:
+        args.steps = 200
 
     import numpy as np
 
@@ -721,8 +792,8 @@ def main():
         t0 = time.perf_counter()
         if active:
             try:
-                for i in range(steps):
-                    batch.render(out, _abi.OUT_CANVAS_F32, flags | (_abi.RENDER_TIMED if i % every == 0 else 0))
+                for i in range(steps):   # (stage timings feed the roofline block: --full only)
+                    batch.render(out, _abi.OUT_CANVAS_F32, flags | (_abi.RENDER_TIMED if args.full and i % every == 0 else 0))
                 ctx.sync()
             except Exception as exc:  # noqa: BLE001
                 err, active = exc, False
@@ -765,6 +836,10 @@ def main():
         out_t = None
         out = ctx.alloc(own_rows * cols * 16)
     t_max, tm = measure(batch, out)
+    if args.dump_outputs:   # the canvas (rows) of the last timed step, after the clock has stopped
+        got = out.download((own_rows, cols, 4), np.float32) if world == 1 else out_t.cpu().numpy()
+        dump_outputs(args.dump_outputs, image_outputs("canvas" if world == 1 else f"canvas_rank{rank}", got, world), world)
+        del got
     config = {
         "workload": desc, "canvas": [rows, cols], "paths": n_scene_paths, "edges": E, "path_pixels": P,
         "sharding": (f"{world} ranks x strips of {strip} bands ({strip * _abi.tile_rows()} rows); no data-path collective"
@@ -773,7 +848,7 @@ def main():
     scaling = "strong" if world > 1 else "weak"  # (N = 1 is the first point of either series)
     canvas_px = rows * cols
     extras = {}
-    if world > 1:
+    if world > 1 and args.full:
         try:  # optional assembly of the full canvas on every rank (svgrasterize.py_amd/dist.py): beside the step, not in it
             from svgrasterize_amd import dist as sdist
 
@@ -790,7 +865,7 @@ def main():
     # render (S:3854-3864 times the whole of scene.render, every Path.mask flattens from scratch, S:948-957), the headline above
     # replays a plan made during warm-up
     replan_canvas = replan_m6 = None
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         try:
             # (three cold frames one after the other, each batch destroyed before the next is made -- a caller drawing frame after
             #  frame: the first asks the driver for fresh device memory, which is cleared before its first use; the later ones get
@@ -869,15 +944,15 @@ def main():
             extras["cold_ms"] = {"error": repr(exc)}
     got_canvas = None
     got_strips = None
-    if world > 1 and rank == 0 and not args.no_cpu_baseline:
+    if world > 1 and rank == 0 and args.full and not args.no_cpu_baseline:
         got_strips = out_t.cpu().numpy()   # (rank 0's strips, packed in strip order; the clock has stopped)
-    if world == 1 and not args.no_cpu_baseline and not args.cpu_paths:
+    if world == 1 and args.full and not args.no_cpu_baseline and not args.cpu_paths:
         got_canvas = out.download((own_rows, cols, 4), np.float32)  # (the last timed step's canvas; the clock has stopped)
     del out
     out_t = None
 
     # ---- companions for N > 1 ---------------------------------------------------------------------------------------------
-    if world > 1 and not args.no_companions:
+    if world > 1 and args.full and not args.no_companions:
         # (a) the same drawing on ONE GPU (rank 0 alone, the others wait at the barriers): the speed-up's denominator
         try:
             out1, prep_err = None, None
@@ -934,11 +1009,6 @@ def main():
     batch.destroy()
 
     if rank == 0:
-        n_timed = max(tm["n"], 1)
-        tile_ms = tm["ms_tile"] / n_timed
-        geo_ms = tm["ms_geometry"] / n_timed
-        # (N > 1: the counters of rank 0 of an N-way sharding of the same drawing, collected on one GPU by profiles/collect_rank.sh)
-        counters, counters_file = load_counters(args.workload if world == 1 else f"{args.workload}_w{world}")
         line = {
             "metric": "Mpixels/sec AA coverage+composite (path-pixels/s; whole step: flatten+binning+coverage+composite; planned replay -- a frame with new geometry: value_replan)",
             "value": round(P / (t_max / args.steps) / 1e6, 1),
@@ -956,7 +1026,7 @@ def main():
             "canvas_mpixels_per_s": round(canvas_px / (t_max / args.steps) / 1e6, 1),
         }
         visible = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             ref_canvas, visible, line["cpu_baseline"] = cpu_baseline(sc, args.cpu_paths)
             if got_canvas is not None and ref_canvas is not None:
                 line["parity"] = contract_counts(got_canvas, ref_canvas)
@@ -970,7 +1040,7 @@ def main():
                     line["parity_replan"] = pr
                 except Exception as exc:  # noqa: BLE001
                     line["parity_replan"] = {"error": repr(exc)}
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and args.full and not args.no_cpu_baseline:
             # the first hardware record checks its own pixels (VERDICT r3 #4c): rank 0's strips against the oracle's render of
             # exactly those rows (the reference's own viewport cropping, S:968-971), and the CPU baseline on a bounded sample
             try:
@@ -1000,15 +1070,21 @@ def main():
                 _rc, _vis, line["cpu_baseline"] = cpu_baseline(sc, args.cpu_paths or n_sample)
             except Exception as exc:  # noqa: BLE001
                 line["cpu_baseline"] = {"error": repr(exc)}
-        if world == 1 and args.workload == "synth4096" and not args.no_configs:
+        if world == 1 and args.full and args.workload == "synth4096" and not args.no_configs:
             c0 = time.perf_counter()
             try:
                 line["configs"] = baseline_configs(ctx)
             except Exception as exc:  # noqa: BLE001
                 line["configs"] = {"error": repr(exc)}
             line["configs_seconds"] = round(time.perf_counter() - c0, 1)
-        line["roofline"] = roofline_block(tile_ms, geo_ms, tm["n"], every, P_rank, E_rank, own_rows * cols * 16, counters, counters_file,
-                                          visible=visible)
+        if args.full:
+            n_timed = max(tm["n"], 1)
+            tile_ms = tm["ms_tile"] / n_timed
+            geo_ms = tm["ms_geometry"] / n_timed
+            # (N > 1: the counters of rank 0 of an N-way sharding of the same drawing, collected on one GPU by profiles/collect_rank.sh)
+            counters, counters_file = load_counters(args.workload if world == 1 else f"{args.workload}_w{world}")
+            line["roofline"] = roofline_block(tile_ms, geo_ms, tm["n"], every, P_rank, E_rank, own_rows * cols * 16, counters,
+                                              counters_file, visible=visible)
         line.update(extras)
         print(json.dumps(line))
     if dist is not None:

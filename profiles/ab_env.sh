@@ -10,7 +10,7 @@ for v in "$@"; do
   echo "== $name  ($envs)" >> $out
   if [[ "$name" == T_* ]]; then
     env $envs timeout -k 10 600 python -m pytest tests -m gpu -x -q > gpurun_out/ab_pytest_$name.log 2>&1; echo "   pytest: $(tail -1 gpurun_out/ab_pytest_$name.log)" >> $out
-    env $envs timeout -k 10 300 python3 bench.py --steps 40 2> gpurun_out/ab_bench_$name.err | tail -1 > gpurun_out/ab_bench_$name.json
+    env $envs timeout -k 10 300 python3 bench.py --full --steps 40 2> "${out%/*}/ab_bench_$name.err" | tail -1 > "${out%/*}/ab_bench_$name.json"
     python3 -c "import json,sys; d=json.loads(open('gpurun_out/ab_bench_$name.json').read()); r=d['roofline']; print('   bench: step', d['ms_per_step'], 'tile', r['avg_launch_ms'], 'geo', r['geometry_ms'], 'parity', d.get('parity'))" >> $out 2>&1
   fi
   rm -rf gpurun_out/ab_$name

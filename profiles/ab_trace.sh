@@ -12,7 +12,7 @@ fi
 for v in "$@"; do
   name="${v%%:*}"; envs="${v#*:}"
   echo "== $name  ($envs)" >> $out
-  ( [ -n "$envs" ] && export $envs; timeout -k 10 300 python3 bench.py --steps 40 2> gpurun_out/ab_bench_$name.err | tail -1 > gpurun_out/ab_bench_$name.json )
+  ( [ -n "$envs" ] && export $envs; timeout -k 10 300 python3 bench.py --full --steps 40 2> "${out%/*}/ab_bench_$name.err" | tail -1 > "${out%/*}/ab_bench_$name.json" )
   python3 -c "import json,sys; d=json.loads(open('gpurun_out/ab_bench_$name.json').read()); r=d['roofline']; print('   bench: step', d['ms_per_step'], 'tile', r['avg_launch_ms'], 'geo', r['geometry_ms'], 'cold', d.get('cold_ms'), 'replan', d.get('replan_ms'), 'plan', d.get('plan_ms'), 'parity', d.get('parity'))" >> $out 2>&1
   rm -rf gpurun_out/ab_$name
   ( [ -n "$envs" ] && export $envs; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ab_$name -o t -- python3 bench.py --no-cpu-baseline --steps 40 > gpurun_out/ab_$name.log 2>&1 ) || { echo "$name RUN FAILED" >> $out; tail -3 gpurun_out/ab_$name.log >> $out; continue; }

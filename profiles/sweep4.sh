@@ -15,7 +15,7 @@ for v in "$@"; do
   echo "== $name  ($flags)" >> $out
   if [[ "$name" == T_* ]]; then
     env $envs timeout -k 10 600 python -m pytest tests -m gpu -x -q > gpurun_out/sweep4_pytest_$name.log 2>&1; echo "   pytest: $(tail -1 gpurun_out/sweep4_pytest_$name.log)" >> $out
-    env $envs timeout -k 10 300 python3 bench.py --steps 40 2> gpurun_out/sweep4_bench_$name.err | tail -1 > gpurun_out/sweep4_bench_$name.json
+    env $envs timeout -k 10 300 python3 bench.py --full --steps 40 2> "${out%/*}/sweep4_bench_$name.err" | tail -1 > "${out%/*}/sweep4_bench_$name.json"
     python3 -c "import json,sys; d=json.loads(open('gpurun_out/sweep4_bench_$name.json').read()); r=d['roofline']; print('   bench: step', d['ms_per_step'], 'tile', r['avg_launch_ms'], 'geo', r['geometry_ms'], 'parity', d.get('parity'))" >> $out 2>&1
   fi
   ( [ -n "$envs" ] && export $envs; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/s4_$name -o t -- python3 bench.py --no-cpu-baseline --steps 40 > gpurun_out/s4_$name.log 2>&1 ) || { echo "$name RUN FAILED" >> $out; tail -3 gpurun_out/s4_$name.log >> $out; continue; }

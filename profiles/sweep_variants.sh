@@ -9,7 +9,7 @@ for v in "$@"; do
   name="${v%%:*}"; flags="${v#*:}"
   make -s -C svgrasterize.py_amd/csrc clean
   if ! make -s -C svgrasterize.py_amd/csrc EXTRA="$flags" 2> gpurun_out/sweep_build_$name.err; then echo "$name BUILD FAILED" >> $out; continue; fi
-  timeout -k 10 120 python bench.py --no-cpu-baseline --steps 30 > gpurun_out/sweep_$name.json 2> gpurun_out/sweep_$name.err || { echo "$name RUN FAILED" >> $out; continue; }
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 30 > "${out%/*}/sweep_$name.json" 2> "${out%/*}/sweep_$name.err" || { echo "$name RUN FAILED" >> $out; continue; }
   python - "$name" gpurun_out/sweep_$name.json >> $out <<'P'
 import json,sys
 d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

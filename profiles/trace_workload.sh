@@ -4,6 +4,7 @@ set -u
 wl="${1:-tiger2048}"; shift || true
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/tw
+set -- --full "$@"   # (the step line read below carries the roofline block only with --full)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/tw -o t -- python3 bench.py --workload $wl --no-cpu-baseline --steps 100 "$@" > gpurun_out/tw.log 2>&1 || { tail -5 gpurun_out/tw.log; exit 1; }
 python3 - $(find gpurun_out/tw -name "*kernel_stats.csv" | head -1) > gpurun_out/trace_$wl.txt <<'P'
 import csv, sys

@@ -91,7 +91,7 @@ def test_launcher_refuses_more_gpus_than_the_box_has(tmp_path):
 def test_bench_gpus_2_launches_itself_on_one_gpu(tmp_path):
     """The real worker: two gloo ranks on GPU 0 (the rehearsal switches of bench.py), started by `bench.py --gpus 2` alone.
     The line says n_gpus 2, strong scaling of the 8192^2 drawing, and checks rank 0's strips against the oracle."""
-    r = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--no-companions", "--cpu-paths", "200"],
+    r = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-companions", "--cpu-paths", "200"],
              {"SVGR_BENCH_BACKEND": "gloo", "SVGR_BENCH_DEVICE": "0"}, tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -1,7 +1,7 @@
 """SVG front-end (svgrasterize.py_amd/svg.py): the Scene it builds against the Scene the reference's
-own loader built from the same document -- as scene dumps (tests/golden/scene_*.npz for the reference's demo files, read
-from /root/reference/demo when that exists: the build container only; tests/golden/svg_kat.npz for the hand-written
-documents of tests/svg_cases.py, everywhere)."""
+own loader built from the same document -- as scene dumps (tests/golden/scene_*.npz for the reference's demo files, whose
+documents are kept beside them in tests/golden/demo; tests/golden/svg_kat.npz for the hand-written documents of
+tests/svg_cases.py)."""
 import json
 import os
 import warnings
@@ -12,7 +12,7 @@ import pytest
 from tests import svg_cases
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEMO = "/root/reference/demo"
+DEMO = os.path.join(GOLD, "demo")
 
 
 def _compare(scene, tree_ref, arrays_ref, tol=1e-12):
@@ -44,9 +44,7 @@ def test_handwritten_documents_match_reference_loader():
 @pytest.mark.parametrize("name,svg_file,width", [("tiger", "icons/tiger.svg", 2048), ("material", "material-design.svg", 4096),
                                                   ("icons", "icons.svg", None), ("prompt", "prompt.svg", 256)])
 def test_demo_documents_match_reference_dumps(name, svg_file, width):
-    path = os.path.join(DEMO, svg_file)
-    if not os.path.exists(path):
-        pytest.skip("the reference's demo files exist only in the build container")
+    path = os.path.join(DEMO, svg_file + "z")   # (kept gzip-compressed)
     from svgrasterize_amd import svg
 
     z = np.load(os.path.join(GOLD, f"scene_{name}.npz"))
@@ -54,7 +52,7 @@ def test_demo_documents_match_reference_dumps(name, svg_file, width):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         fonts = svg.FontsDB()
-        fonts.register_file(os.path.join(os.path.dirname(DEMO), "fonts.svgz"))  # prompt.svg is all text
+        fonts.register_file(os.path.join(DEMO, "fonts.svgz"))  # prompt.svg is all text
         scene, _ids, size = svg.svg_scene_from_filepath(path, width=width, fonts=fonts)
     w, h = size
     assert [int(h), int(w)] == info["size"]
