@@ -63,33 +63,18 @@ static std::atomic<unsigned long long> g_n_launches{0};
 // ======================================================================================
 // tile geometry
 // ======================================================================================
-#ifndef SVGR_TR
-#define SVGR_TR 16
-#endif
-constexpr int TR = SVGR_TR;                // rows per band / tile
-#ifndef SVGR_PX
-#define SVGR_PX 8
-#endif
-constexpr int PX = SVGR_PX;                // pixels per lane (consecutive columns)
-#ifndef SVGR_CH
-#define SVGR_CH 8
-#endif
-constexpr int CH = SVGR_CH;                // lanes per tile row: 8 (half a DPP row), 16 (one) or 32 (two)
+constexpr int TR = 16;                     // rows per band / tile
+constexpr int PX = 8;                      // pixels per lane (consecutive columns)
+constexpr int CH = 8;                      // lanes per tile row: half a 16-lane DPP row
 constexpr int TC = CH * PX;                // columns per tile
 constexpr int NT = TR * CH;                // threads per workgroup (128 = 2 waves); a wave covers 64 / CH tile rows
 constexpr int CHUNK_STRIDE = PX + 2;       // doubles; +16 B makes the b128 lane groups conflict free
 constexpr int ROW_STRIDE = CH * CHUNK_STRIDE;
 constexpr int DELTA_BYTES = TR * ROW_STRIDE * 8;   // one delta tile in LDS
-static_assert(CH == 4 || CH == 8 || CH == 16 || CH == 32, "row scan: a quarter / half of a 16-lane DPP row, one, or two per tile row");
 static_assert(DELTA_BYTES < (1 << 16), "a TileAdd carries its byte offset in 16 bits");
 static_assert(TC <= 64, "a TileAdd carries its run length in 6 bits");
 constexpr int NW = NT / 64;                // waves per workgroup
-#ifndef SVGR_ORDER
-#define SVGR_ORDER 1                    // whole-canvas launches take their tiles heaviest first (k_tile_lists); 0: in raster order
-#endif
-#ifndef SVGR_WAVES_PER_EU
-#define SVGR_WAVES_PER_EU 4             // register budget of the tile kernel: 512 / 4 = 128 VGPRs
-#endif
+constexpr int WAVES_PER_EU = 4;            // register budget of the tile kernel: 512 / 4 = 128 VGPRs
 static_assert(NT % 64 == 0 && NT <= 1024, "tile kernel: whole waves, at most 1024 threads");
 
 // One addition into a tile's LDS delta tile: everything the scatter phase of the tile kernel does for it is
@@ -123,14 +108,14 @@ struct CellHdr {
     int n_add, add0;          // class 2: its add list
     int p;                    // path id
     int group, pad[3];        // isolated group the path belongs to (-1: none)
-    double carry[SVGR_TR];    // class 1 reads them; for class 2 they are in the add list
+    double carry[TR];        // class 1 reads them; for class 2 they are in the add list
 };
 constexpr int HDR_DWORDS = 20;    // everything in front of `carry`
-constexpr int HDR_LOAD_DWORDS = HDR_DWORDS + 2 * SVGR_TR;   // what the tile kernel loads per item: all of it, a dword per lane
+constexpr int HDR_LOAD_DWORDS = HDR_DWORDS + 2 * TR;   // what the tile kernel loads per item: all of it, a dword per lane
 static_assert(HDR_LOAD_DWORDS <= 64, "a CellHdr is one dword per lane of one load instruction");
-static_assert(sizeof(CellHdr) == 4 * HDR_DWORDS + 8 * SVGR_TR && offsetof(CellHdr, carry) == 4 * HDR_DWORDS, "CellHdr layout");
+static_assert(sizeof(CellHdr) == 4 * HDR_DWORDS + 8 * TR && offsetof(CellHdr, carry) == 4 * HDR_DWORDS, "CellHdr layout");
 constexpr unsigned SPAN_MAX = (1u << 26) - 1;
-static_assert(SVGR_TR <= 64, "row-in-band is stored in 6 bits");
+static_assert(TR <= 64, "row-in-band is stored in 6 bits");
 
 // ======================================================================================
 // errors
@@ -547,10 +532,7 @@ __global__ __launch_bounds__(256) void k_seg_select(const int* __restrict__ seg_
 // 32 lanes per segment.  Lane j owns the depth-5 node whose path bits are j (if the five ancestors
 // above it are not flat; an ancestor that is flat is emitted by the lane whose remaining bits are 0).
 // Per-path keys: {~key(min_r), ~key(min_c), key(max_r), key(max_c)}, all folded with atomicMax.
-#ifndef SVGR_FL_SUB
-#define SVGR_FL_SUB 5
-#endif
-constexpr int FL_SUB = SVGR_FL_SUB;       // 32 lanes per segment: the longest lane bounds the kernel, so cut subtrees small
+constexpr int FL_SUB = 5;                 // 32 lanes per segment: the longest lane bounds the kernel, so cut subtrees small
 constexpr int FL_BLOCK = 256;     // (the waves are independent up to the last step: the segments of a workgroup fold their extents per path)
 // PLACED (with EMIT): the pass stores the edges at the places the plan's counting pass left PER LANE (`lane_off`: a lane's first
 // edge inside its segment's slots) -- one traversal that stores as it goes: no remembered end points, no prefix sum over the
@@ -567,11 +549,9 @@ constexpr int FL_BLOCK = 256;     // (the waves are independent up to the last s
 // renders that follow.  Workgroups are dispatched in index order, so the lowest unfinished one is always resident and finds every
 // predecessor finished: the chain cannot stall.  (A dead-man count ends a look-back that does not return all the same: error bit
 // 2, the staged plan takes over.)
-template <bool EMIT, bool PLACED = false, int SUB = SVGR_FL_SUB, bool SCAN = false>
-#ifndef SVGR_FL_WAVES
-#define SVGR_FL_WAVES 1
-#endif
-__global__ __launch_bounds__(FL_BLOCK, SVGR_FL_WAVES) void k_flatten(const double* __restrict__ segs, const uint8_t* __restrict__ kind,
+constexpr int FL_WAVES = 1;
+template <bool EMIT, bool PLACED = false, int SUB = FL_SUB, bool SCAN = false>
+__global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __restrict__ segs, const uint8_t* __restrict__ kind,
                                                  const int* __restrict__ seg_path, const double* __restrict__ path_m6,
                                                  int n_segs, double thr, double* __restrict__ edges,
                                                  int* __restrict__ edge_path, const EdgeShards sh,
@@ -655,10 +635,7 @@ __global__ __launch_bounds__(FL_BLOCK, SVGR_FL_WAVES) void k_flatten(const doubl
     };
     int cnt = 0;
     bool ovf = false;
-#ifndef SVGR_FL_ENDS
-#define SVGR_FL_ENDS 4
-#endif
-    constexpr int FL_ENDS = SVGR_FL_ENDS;  // pieces a lane remembers from its counting traversal (a wave skips the second one when all its lanes fit)
+    constexpr int FL_ENDS = 4;  // pieces a lane remembers from its counting traversal (a wave skips the second one when all its lanes fit)
     double qe[2 * FL_ENDS];
     for (int k = 0; k < 2 * FL_ENDS; ++k) qe[k] = 0.0;
     // (the plan's counting pass also adds up the rows and columns the kept pieces cross: what the first guess of the add lists'
@@ -943,19 +920,10 @@ static_assert(sizeof(PathBin) == 16, "PathBin is one dwordx4");
 // (k relative to the path's first column tile).  A slab's counters and per-row sums live in LDS, so it holds at most
 // PB_CELLS cells: a path of up to PB_CELLS column tiles is cut into runs of bands, a wider one band by band into runs of
 // column tiles.
-#ifndef SVGR_PB_CELLS
-#define SVGR_PB_CELLS 80
-#endif
-#ifndef SVGR_PB_BANDS
-#define SVGR_PB_BANDS 16
-#endif
-#ifndef SVGR_PB_THREADS
-#define SVGR_PB_THREADS 256
-#endif
-constexpr int PB_THREADS = SVGR_PB_THREADS;
-constexpr int PB_CELLS = SVGR_PB_CELLS;
-constexpr int PB_BANDS = SVGR_PB_BANDS;   // bands per slab at most: one TR-lane group of the workgroup scans each
-static_assert(PB_BANDS * SVGR_TR <= PB_THREADS && PB_BANDS <= PB_CELLS, "k_path_build: one lane group per band of the slab");
+constexpr int PB_THREADS = 256;
+constexpr int PB_CELLS = 80;
+constexpr int PB_BANDS = 16;   // bands per slab at most: one TR-lane group of the workgroup scans each
+static_assert(PB_BANDS * TR <= PB_THREADS && PB_BANDS <= PB_CELLS, "k_path_build: one lane group per band of the slab");
 // It carries everything the workgroup needs of its path (bbox, bins, edge range): one load, then the edges -- looked up by
 // the workgroup itself they were three dependent round trips in front of the first edge.
 struct Slab {
@@ -1245,10 +1213,7 @@ static_assert(sizeof(TileEntry) == 32, "TileEntry is 32 bytes");
 // One workgroup per owned band, after k_path_bbox: the ascending (= paint order) list of the paths whose bbox reaches the
 // band (TileEntry), and the band's first tile-list slot (one slot per cell of a listed pair: k_tile_lists fills them).
 // A pair's place in its band's list is the bit that stands for it in the tiles' entry bitmasks.
-#ifndef SVGR_BE_BLOCK
-#define SVGR_BE_BLOCK 1024
-#endif
-constexpr int BE_BLOCK = SVGR_BE_BLOCK;
+constexpr int BE_BLOCK = 1024;
 constexpr int BE_KEEP = 4;   // 64-path groups per wave whose bins stay in registers between the two passes
 __global__ __launch_bounds__(BE_BLOCK) void k_band_entries(const PathBin* __restrict__ bins, int n_paths,
                                                               const int* __restrict__ plist,  // multi-GPU: the n_paths paths of this rank, ascending (else nullptr: all)
@@ -1514,16 +1479,11 @@ __device__ __forceinline__ double replay_rows(double x, int y, int n, double p0y
     return xn;
 }
 static_assert(sizeof(EdgeLds) == 32, "EdgeLds is two 16-byte LDS reads (its first row and direction ride in an int array beside it)");
-#ifndef SVGR_PB_BATCH
-#define SVGR_PB_BATCH 256
-#endif
-constexpr int PB_BATCH = SVGR_PB_BATCH;            // edges staged together
+constexpr int PB_BATCH = 256;            // edges staged together
 constexpr int PB_EPL = (PB_BATCH + PB_THREADS - 1) / PB_THREADS;   // edges per lane and batch
 static_assert(PB_BATCH % 64 == 0 && PB_BATCH / 16 <= 32, "two-level search: at most 32 coarse entries, read four at a time");
-static_assert(PB_BANDS * SVGR_TR * PB_BATCH < (1 << 20) && PB_BATCH < (1 << 11), "stage() scans row counts and live flags in one packed word");
-#ifndef SVGR_PB_WAVES
-#define SVGR_PB_WAVES 6
-#endif
+static_assert(PB_BANDS * TR * PB_BATCH < (1 << 20) && PB_BATCH < (1 << 11), "stage() scans row counts and live flags in one packed word");
+constexpr int PB_WAVES = 6;
 // The barriers of k_path_build order LDS traffic only -- nothing one wave writes to global memory is read by another inside the
 // kernel --, so they wait for the wave's LDS operations and not, as __syncthreads() does, for its global stores as well: behind
 // pass A those are the add lists on their way out, and a wave that waits for their acknowledgement stands still for a microsecond.
@@ -1537,7 +1497,7 @@ __device__ __forceinline__ void pb_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // lists keep the slack between them (memory, not traffic: only what is written is read).  A bound that did not hold is caught like
 // a plan that does not fit: the pieces are not stored, error bit 32, the staged plan (MODE 0, exact) takes over.
 template <int MODE>
-__global__ __launch_bounds__(PB_THREADS, SVGR_PB_WAVES) void k_path_build(const Slab* __restrict__ slabs, const double* __restrict__ edges,
+__global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab* __restrict__ slabs, const double* __restrict__ edges,
                                                            const int* __restrict__ pair_idx, const double* __restrict__ path_paint,
                                                            const uint8_t* __restrict__ path_rule, const int* __restrict__ path_group,
                                                            const int* __restrict__ path_grad, int vr0, int vc0, int n_ct, int mask_words,
@@ -2110,10 +2070,7 @@ struct TileSlot {
 // instruction fetches (a lane each).  Tile and items used to be two dependent round trips in front of the first header.
 constexpr int PAGE_ITEMS = 24, PAGE_STRIDE = PAGE_ITEMS + 1;
 static_assert(PAGE_STRIDE + 1 <= 64, "a page is one load per lane (and one more lane for the last word of the tile's entry)");
-#ifndef SVGR_TL_BLOCK
-#define SVGR_TL_BLOCK 1024
-#endif
-constexpr int TL_BLOCK = SVGR_TL_BLOCK;
+constexpr int TL_BLOCK = 1024;
 __device__ __forceinline__ int select_bit(unsigned long long m, int r) {  // position of the r-th (0-based) set bit of m
     unsigned x = (unsigned)m;
     int pos = 0;
@@ -2161,7 +2118,7 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
             int n, n2;
             count_tile(ct, n, n2);
             n_keep = n; n2_keep = n2;
-            atomicAdd(&s_hist[SVGR_ORDER ? weight_of(n, n2) : 0], 1);
+            atomicAdd(&s_hist[weight_of(n, n2)], 1);
         }
     }
     __syncthreads();
@@ -2197,7 +2154,7 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
             const bool fits = (long long)item0 + n <= (long long)item_cap;
             if (!fits) atomicOr(&bd->err, 64);
             tile_info[(size_t)band * n_ct + ct] = make_int2(item0, fits ? n : 0);
-            const int rank = SVGR_ORDER ? atomicAdd(&s_cur[weight_of(n, n2)], 1) : ct;
+            const int rank = atomicAdd(&s_cur[weight_of(n, n2)], 1);
             s_rank[tid] = rank;
             // (band: its ordinal among the owned ones)
             pages[((size_t)rank * n_owned + blockIdx.x) * PAGE_STRIDE + PAGE_ITEMS] = make_uint4(blockIdx.x, (unsigned)ct, (unsigned)item0, (unsigned)(fits ? n : 0));
@@ -2402,16 +2359,8 @@ __device__ __forceinline__ double dpp_row_shr(double v) {  // lane i <- lane i-N
     return __hiloint2double(hi, lo);
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_ctrl(double v) {  // generic DPP move of a double; lanes without a source / masked rows read 0
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // the lane's pixels, one macro call each (asm blocks with named operands cannot be written in a loop over a constexpr index)
-static_assert(SVGR_PX == 8, "the blend statements name a lane's eight pixels (16 px per lane / one wave per tile was built and measured slower: DESIGN section 4)");
+static_assert(PX == 8, "the blend statements name a lane's eight pixels (16 px per lane / one wave per tile was built and measured slower: DESIGN section 4)");
 #define SVGR_ACC_PX(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
 #define SVGR_ACC_PX2(F) F(0) F(2) F(4) F(6)
 
@@ -2487,7 +2436,6 @@ struct WinTable {
 // with a load in flight cannot be copied, spilled or recoloured by a compiler that does not have it.  The persistent tile loop
 // needs that: with several statements defining one target variable the allocator joins them with copies -- of registers
 // whose load has not landed.  (The other variants take one tile per workgroup and keep the targets as ordinary variables.)
-#if SVGR_WAVES_PER_EU == 4
 #define SVGR_FIX0 116
 #define SVGR_FR(k) SVGR_FR_##k
 #define SVGR_FR_0 "v116"
@@ -2506,9 +2454,6 @@ struct WinTable {
 #define SVGR_FP_67 "v[122:123]"
 #define SVGR_FP_89 "v[124:125]"
 #define SVGR_FP_1011 "v[126:127]"
-#else
-#error "the tile kernel's fixed load targets are named for 4 waves per SIMD (128 VGPRs)"
-#endif
 // The launch's arguments read AGAIN from the kernel-argument segment: scalar loads that hit the scalar cache, in the place of two
 // dozen SGPRs held across the item loops (the persistent loop ran out of them).  The pointer passes through an empty asm so that
 // the loads stay where they are written; it keeps its address space (constant): through a generic pointer they would be
@@ -2543,10 +2488,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a, const int win = 0, 
     constexpr bool FIXED = OUT == 0 && !CLIP;   // the production variant: fixed load targets, persistent tile loop
     static_assert(!GRAD || GROUPS, "gradient entries live in the variant with the large register budget");
     constexpr int OFF_CLIP = 2 * DELTA_BYTES;                                // canvas modes: coverage tile of a clip path
-#ifndef SVGR_DBG_TILE_PADLDS
-#define SVGR_DBG_TILE_PADLDS 0          // diagnostic: extra LDS per workgroup (occupancy experiment)
-#endif
-    constexpr int LDS_BYTES = OFF_CLIP + (CLIP ? DELTA_BYTES : 0) + SVGR_DBG_TILE_PADLDS;
+    constexpr int LDS_BYTES = OFF_CLIP + (CLIP ? DELTA_BYTES : 0);
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[LDS_BYTES];
     int clip_tag = -1;  // path whose coverage the clip tile holds (canvas modes)
 
@@ -2694,7 +2636,7 @@ __device__ __forceinline__ void tile_body(const TileArgs& a, const int win = 0, 
 #define vq0_C SVGR_FR(6), SVGR_FR(7)
 #define vq_R SVGR_FP_1011
 #define vq_C SVGR_FR(10), SVGR_FR(11)
-    static_assert(SVGR_FIX0 == 512 / SVGR_WAVES_PER_EU - 12, "the register names above: the top twelve of the budget");
+    static_assert(SVGR_FIX0 == 512 / WAVES_PER_EU - 12, "the register names above: the top twelve of the budget");
 #define SVGR_ADD_NT ""
 #define SVGR_HDR_LOAD(tgt, ptr)                                                                                        \
     do {                                                                                                               \
@@ -2777,13 +2719,15 @@ __device__ __forceinline__ void tile_body(const TileArgs& a, const int win = 0, 
     // the pair again in front of every use (their halves are equal)
     unsigned long long sm1_, sm2_, sm4_;
     {
-        constexpr unsigned long long rep = CH == 8 ? 0x0101010101010101ull : 0x1111111111111111ull;
-        sm1_ = rep * (CH == 8 ? 0xfeull : 0xeull); sm2_ = rep * (CH == 8 ? 0xfcull : 0xcull); sm4_ = rep * 0xf0ull;
+        constexpr unsigned long long rep = 0x0101010101010101ull;   // one byte per tile row of CH = 8 lanes
+        sm1_ = rep * 0xfeull; sm2_ = rep * 0xfcull; sm4_ = rep * 0xf0ull;
         asm volatile("" : "+s"(sm1_), "+s"(sm2_), "+s"(sm4_));
     }
     // (the uniform part of an item's header comes out of the vector load `h` by v_readlane; a scalar load issued an item ahead was
     //  built twice and measured equal: DESIGN section 4)
     auto process = [&](int h, int buf) {
+        (void)lane;   // (kept in the closure: without it the header loads' lane clamp compiles to v_min_u32 for v_min_i32 --
+                      //  the same values, but no longer the instructions that were measured)
         auto hw = [&](int j) { return __builtin_amdgcn_readlane(h, j); };
         const int bits = hw(12);
         const int cls = (bits >> 3) & 3;
@@ -2866,54 +2810,21 @@ __device__ __forceinline__ void tile_body(const TileArgs& a, const int win = 0, 
 #pragma unroll
             for (int i = 1; i < PX; ++i) tot += t[i];
             double inc = tot;  // inclusive scan of the CH chunk totals of this tile row
-            double run;
-            if (CH <= 8) {
-                // a 16-lane DPP row holds 16 / CH tile rows: a shift must not carry a value across their borders.  The shifted
-                // value is added under an EXEC mask (a scalar move on either side of the add) instead of being selected to zero
-                // first (two VOP3 v_cndmask per step: a fifth of the scan's vector instructions).  The DPP moves themselves run
-                // with every lane enabled: a disabled lane would read as zero on the source side as well.
-                constexpr unsigned long long rep = CH == 8 ? 0x0101010101010101ull : 0x1111111111111111ull;
-                (void)rep;
-                double v;
-                const unsigned long long exec_all = __builtin_amdgcn_read_exec();   // (all ones: every branch above is wave-uniform)
-                const unsigned long long m1 = sm1_, m2 = sm2_, m4 = sm4_;   // (whole scalar pairs made once: see their definition)
+            // a 16-lane DPP row holds two tile rows: a shift must not carry a value across their border.  The shifted value is
+            // added under an EXEC mask (a scalar move on either side of the add) instead of being selected to zero first (two
+            // VOP3 v_cndmask per step: a fifth of the scan's vector instructions).  The DPP moves themselves run with every lane
+            // enabled: a disabled lane would read as zero on the source side as well.
+            double v;
+            const unsigned long long exec_all = __builtin_amdgcn_read_exec();   // (all ones: every branch above is wave-uniform)
+            const unsigned long long m1 = sm1_, m2 = sm2_, m4 = sm4_;   // (whole scalar pairs made once: see their definition)
 #define SVGR_MASKED_ADD(acc_, v_, m_) asm volatile("s_mov_b64 exec, %2\n\tv_add_f64 %0, %0, %1\n\ts_mov_b64 exec, %3" : "+v"(acc_) : "v"(v_), "s"(m_), "s"(exec_all))
-                v = dpp_row_shr<1>(inc); SVGR_MASKED_ADD(inc, v, m1);
-                v = dpp_row_shr<2>(inc); SVGR_MASKED_ADD(inc, v, m2);
-                if (CH == 8) { v = dpp_row_shr<4>(inc); SVGR_MASKED_ADD(inc, v, m4); }
-                v = dpp_row_shr<1>(inc);  // exclusive: everything left of this chunk (lanes that start a tile row: nothing)
-                SVGR_MASKED_ADD(t[0], v, m1);
+            v = dpp_row_shr<1>(inc); SVGR_MASKED_ADD(inc, v, m1);
+            v = dpp_row_shr<2>(inc); SVGR_MASKED_ADD(inc, v, m2);
+            v = dpp_row_shr<4>(inc); SVGR_MASKED_ADD(inc, v, m4);
+            v = dpp_row_shr<1>(inc);  // exclusive: everything left of this chunk (lanes that start a tile row: nothing)
+            SVGR_MASKED_ADD(t[0], v, m1);
 #pragma unroll
-                for (int i = 1; i < PX; ++i) t[i] += t[i - 1];
-                run = 0.0;
-            } else if (CH <= 8) {
-                // a 16-lane DPP row holds 16 / CH tile rows: a shift must not carry a value across their borders
-                const int lc = lane & (CH - 1);
-                double v;
-                v = dpp_row_shr<1>(inc); inc += lc >= 1 ? v : 0.0;
-                v = dpp_row_shr<2>(inc); inc += lc >= 2 ? v : 0.0;
-                if (CH == 8) { v = dpp_row_shr<4>(inc); inc += lc >= 4 ? v : 0.0; }
-                v = dpp_row_shr<1>(inc);
-                run = lc >= 1 ? v : 0.0;  // exclusive: everything left of this chunk
-            } else {
-                inc += dpp_row_shr<1>(inc);
-                inc += dpp_row_shr<2>(inc);
-                inc += dpp_row_shr<4>(inc);
-                inc += dpp_row_shr<8>(inc);
-                if (CH == 16) {
-                    run = dpp_row_shr<1>(inc);  // exclusive: everything left of this chunk
-                } else {
-                    // a tile row is two DPP rows: add the lower row's total (its lane 15) to the upper row,
-                    // then shift by one lane across the pair; the first lane of a tile row starts at 0
-                    inc += dpp_ctrl<0x142, 0xA>(inc);   // row_bcast:15 into DPP rows 1 and 3
-                    run = dpp_ctrl<0x138, 0xF>(inc);    // wave_shr:1
-                    if ((lane & 31) == 0) run = 0.0;
-                }
-            }
-            if (!(CH <= 8)) {
-#pragma unroll
-                for (int i = 0; i < PX; ++i) { run += t[i]; t[i] = run; }
-            }
+            for (int i = 1; i < PX; ++i) t[i] += t[i - 1];
         }
 
         if (OUT <= 1) {
@@ -3458,17 +3369,17 @@ __device__ __forceinline__ void tile_body(const TileArgs& a, const int win = 0, 
 }
 
 template <int OUT, bool CLIP = false, bool GROUPS = false, bool GRAD = false>
-__global__ __launch_bounds__(NT, GROUPS ? 2 : (CLIP ? SVGR_WAVES_PER_EU - 1 : SVGR_WAVES_PER_EU)) void k_tile_render(const TileArgs a) {
+__global__ __launch_bounds__(NT, GROUPS ? 2 : (CLIP ? WAVES_PER_EU - 1 : WAVES_PER_EU)) void k_tile_render(const TileArgs a) {
     tile_body<OUT, CLIP, GROUPS, GRAD>(a);
 }
 template <>
-__global__ __launch_bounds__(NT, SVGR_WAVES_PER_EU) __attribute__((amdgpu_num_vgpr(SVGR_FIX0 / 2))) void k_tile_render<0, false, false, false>(const TileArgs a) {
+__global__ __launch_bounds__(NT, WAVES_PER_EU) __attribute__((amdgpu_num_vgpr(SVGR_FIX0 / 2))) void k_tile_render<0, false, false, false>(const TileArgs a) {
     tile_body<0, false, false, false>(a);
 }
 // the canvas variants drawing several windows (WinTable): the variants a document's runs use -- every one but the production kernel,
 // whose launch is persistent and whole-canvas
 template <int OUT, bool CLIP = false, bool GROUPS = false, bool GRAD = false>
-__global__ __launch_bounds__(NT, GROUPS ? 2 : (CLIP ? SVGR_WAVES_PER_EU - 1 : SVGR_WAVES_PER_EU)) void k_tile_render_windows(const TileArgs a, const WinTable wt) {
+__global__ __launch_bounds__(NT, GROUPS ? 2 : (CLIP ? WAVES_PER_EU - 1 : WAVES_PER_EU)) void k_tile_render_windows(const TileArgs a, const WinTable wt) {
     static_assert(OUT <= 1, "windows exist in the canvas outputs");
     int w = 0;
 #pragma unroll
@@ -3963,13 +3874,8 @@ __global__ __launch_bounds__(256) void k_convolve_cols(double* __restrict__ out,
 // source rows is a chain of loads, one per row, in a launch of a few hundred waves: CONV_U of them are asked for together
 // (round 5), and the weights are read from an LDS copy padded with CONV_RB zeros on either
 // side, so that a tap outside the kernel is a multiplication by zero instead of a branch.
-#ifndef SVGR_CONV_RB
-#define SVGR_CONV_RB 12        // (25-tap blur of a 2048x2048 layer: 8 -> 0.180 ms, 12 -> 0.171, 16 -> 0.176, 24 -> 0.203)
-#endif
-#ifndef SVGR_CONV_U
-#define SVGR_CONV_U 6
-#endif
-constexpr int CONV_RB = SVGR_CONV_RB, CONV_U = SVGR_CONV_U;
+constexpr int CONV_RB = 12;   // (25-tap blur of a 2048x2048 layer: 8 -> 0.180 ms, 12 -> 0.171, 16 -> 0.176, 24 -> 0.203)
+constexpr int CONV_U = 6;
 __global__ __launch_bounds__(64) void k_convolve_rows(double* __restrict__ out, const double* __restrict__ src, int rows, int cols,
                                                       const ConvW cw) {
     __shared__ double s_w[CONV_TAPS + 2 * CONV_RB + CONV_U];   // (+ CONV_U: the rows asked for beyond the span's first are multiplied too)
@@ -4128,7 +4034,7 @@ struct svgr_batch {
     std::vector<int> slab_at_host;
     int64_t n_slabs = 0;                    // ... the plan's count = the launch's grid
     DevArr<int> seg_cnt, seg_off;           // per segment: edges it flattens into (the plan's counting pass), their prefix sums
-    int fl_sub = SVGR_FL_SUB;               // log2 of the lanes k_flatten cuts a segment over (5, or 6 when the launch does not fill the chip: run_geometry)
+    int fl_sub = FL_SUB;                    // log2 of the lanes k_flatten cuts a segment over (5, or 6 when the launch does not fill the chip: run_geometry)
     DevArr<int> lane_off;                   // per (segment, lane of its 2^fl_sub): the lane's first edge inside the segment's slots (same pass)
     DevArr<int> path_seg0;                  // per path its first segment (view of the input blob)
     DevArr<int> seg_list;                   // multi-GPU: the segments this rank flattens (k_seg_select, at plan time)
@@ -4284,9 +4190,8 @@ static inline int cap_i32(size_t n) { return (int)std::min<size_t>(n, 0x7fffffff
 // sums), 2 = flatten + emit + bbox, 3 = + band lists, 4 = everything.  `use_vp` = clip bboxes to b->vp and bin relative to it.
 // log2 of the lanes k_flatten cuts a segment over: 5, or 6 when a launch over `n_items` segments would not fill the chip
 static int choose_fl_sub(const svgr_batch* b, int n_items) {
-    static const int sub_env = getenv("SVGR_FL_SUB") ? atoi(getenv("SVGR_FL_SUB")) : 0;
     const size_t waves32 = ((size_t)std::max(n_items, 1) << 5) / 64, slots = (size_t)b->ctx->n_cu * 4 * 6;   // (six waves per SIMD)
-    return sub_env == 5 || sub_env == 6 ? sub_env : (waves32 * 2 <= slots ? 6 : 5);
+    return waves32 * 2 <= slots ? 6 : 5;
 }
 static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     hipStream_t st = b->ctx->stream;
@@ -4548,6 +4453,34 @@ static int check_gradient(const svgr_gradient* g) {
     if (g->n_stops < 1 || g->n_stops > (1 << 20) || !g->stop_off || !g->stop_rgba)
         return fail(SVGR_E_INVALID, "gradient needs at least one stop");
     return 0;
+}
+
+// The production variant: a float32 canvas without gradients, groups or clips -- the tile kernel with fixed load registers and the
+// persistent tile loop (k_tile_render<0, false>).
+static bool production_variant(const svgr_batch* b, int out_kind) {
+    return out_kind == SVGR_OUT_CANVAS_F32 && b->n_grads == 0 && b->n_groups == 0 && !b->has_clips;
+}
+// The tile kernel's variant for a render, chosen here for both kernel families: `launch(TileVariant<OUT, CLIP, GROUPS, GRAD>{})`.
+template <int OUT_, bool CLIP_ = false, bool GROUPS_ = false, bool GRAD_ = false>
+struct TileVariant {
+    static constexpr int OUT = OUT_;
+    static constexpr bool CLIP = CLIP_, GROUPS = GROUPS_, GRAD = GRAD_;
+};
+template <int OUT, class F>
+static void with_canvas_variant(const svgr_batch* b, F& launch) {
+    if (b->n_grads > 0) launch(TileVariant<OUT, true, true, true>{});
+    else if (b->n_groups > 0) launch(TileVariant<OUT, true, true>{});
+    else if (b->has_clips) launch(TileVariant<OUT, true>{});
+    else launch(TileVariant<OUT, false>{});
+}
+template <class F>
+static void with_tile_variant(const svgr_batch* b, int out_kind, F&& launch) {
+    switch (out_kind) {
+        case 0: with_canvas_variant<0>(b, launch); break;
+        case 1: with_canvas_variant<1>(b, launch); break;
+        case 2: launch(TileVariant<2>{}); break;
+        default: launch(TileVariant<3>{}); break;
+    }
 }
 
 // ======================================================================================
@@ -5292,6 +5225,19 @@ int svgr_batch_plan(svgr_batch* b) {
     return abi_guard("svgr_batch_plan", [&]() { return batch_plan_impl(b); });
 }
 
+// page-locked staging of at least `bytes` for this context's read-backs (the stream is drained before a smaller one is replaced)
+static int ensure_pinned(svgr_ctx* c, size_t bytes) {
+    if (c->pinned_bytes >= bytes) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->pinned) (void)hipHostFree(c->pinned);
+    c->pinned = nullptr;
+    c->pinned_bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 20);
+    HIPCHK(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
+    c->pinned_bytes = want;
+    return 0;
+}
+
 // The plans of many batches behind one wait: a document's per-node route plans dozens of small batches (one per run of
 // fills between two filter nodes), and each plan alone is a device round trip of ~0.15 ms of which the kernels are a
 // fraction.  Every batch that qualifies for the single-pass plan has its pass enqueued first; then one wait per stream;
@@ -5312,16 +5258,8 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
             need += (sizeof(BatchDev) + 16 * (size_t)batches[i]->n_paths + 255) & ~(size_t)255;
         }
         for (auto& kv : stage_need) {
-            svgr_ctx* c = kv.first;
-            if (c->pinned_bytes >= kv.second) continue;
-            HIPCHK(enter_ctx(c));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (c->pinned) (void)hipHostFree(c->pinned);
-            c->pinned = nullptr;
-            c->pinned_bytes = 0;
-            const size_t want = std::max<size_t>(kv.second + kv.second / 2, 1u << 20);
-            HIPCHK(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-            c->pinned_bytes = want;
+            HIPCHK(enter_ctx(kv.first));
+            if (int rc = ensure_pinned(kv.first, kv.second)) return rc;
         }
         for (int64_t i = 0; i < n; ++i) {
             svgr_batch* b = batches[i];
@@ -5854,11 +5792,9 @@ int svgr_batch_render_windows(svgr_batch* b, int64_t n, svgr_buf* const* outs, i
         HIPCHK(enter_ctx(c));
         // Every variant but the production kernel (whose launch is whole-canvas and persistent) draws the windows in ONE launch per
         // MAX_WINS of them: a window is a few dozen workgroups that live as long as its deepest tile, and a document's runs are dozens
-        // of windows (icons.svg: 30 launches, 1.6 ms one after the other).  SVGR_WINDOWS_ON_STREAMS: the round-4 form, a launch per
-        // window on eight streams.
-        static const bool on_streams = getenv("SVGR_WINDOWS_ON_STREAMS") != nullptr;
-        const bool production = out_kind == SVGR_OUT_CANVAS_F32 && b->n_grads == 0 && b->n_groups == 0 && !b->has_clips;
-        if (!on_streams && !production && (out_kind == SVGR_OUT_CANVAS_F32 || out_kind == SVGR_OUT_CANVAS_F64) && b->own.world <= 1) {
+        // of windows (icons.svg: 30 launches, 1.6 ms one after the other).  The production kernel, and a rank of a sharded canvas,
+        // take a launch per window on eight streams.
+        if (!production_variant(b, out_kind) && (out_kind == SVGR_OUT_CANVAS_F32 || out_kind == SVGR_OUT_CANVAS_F64) && b->own.world <= 1) {
             if (int rc = batch_render_impl(b, outs[0], out_kind, flags, windows, 1)) return rc;
             WinTable local;   // (3 KiB on the stack, copied into the launch's argument)
             for (int64_t at = 0; at < n; at += MAX_WINS) {
@@ -6036,7 +5972,7 @@ static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigne
         // the whole canvas: the tiles in k_tile_lists' order (heaviest first); a window: its tiles in raster order
         a.use_order = a.win_ct == n_ctiles && a.n_bands == owned_bands ? 1 : 0;
         // A whole-canvas launch is persistent: as many workgroups as the chip holds at once walk the tiles (k_tile_render);
-        // how many a CU holds is the variant's register / LDS budget.  SVGR_TILE_WGS_PER_CU overrides it (0: a workgroup per tile).
+        // how many a CU holds is the variant's register / LDS budget.
         const unsigned n_tiles = (unsigned)a.win_ct * (unsigned)a.n_bands;
         if (phase == 3) {
             if (wt->n >= MAX_WINS) return fail(SVGR_E_INVALID, "window table full");
@@ -6048,14 +5984,12 @@ static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigne
             r.win_r = a.win_r; r.win_c = a.win_c; r.win_rows = a.win_rows; r.win_cols = a.win_cols; r.pad = 0;
             return 0;
         }
-        static const int wgs_env = getenv("SVGR_TILE_WGS_PER_CU") ? atoi(getenv("SVGR_TILE_WGS_PER_CU")) : -1;
-        const int wgs_variant = std::min((SVGR_WAVES_PER_EU * 4) / NW, (160 * 1024) / (2 * DELTA_BYTES));   // (registers, LDS)
-        const int wgs_per_cu = wgs_env >= 0 ? wgs_env : wgs_variant;
-        const bool production = out_kind == 0 && b->n_grads == 0 && b->n_groups == 0 && !b->has_clips;   // (the variant with the tile loop)
+        constexpr int wgs_per_cu = std::min((WAVES_PER_EU * 4) / NW, (160 * 1024) / (2 * DELTA_BYTES));   // (registers, LDS)
+        const bool production = production_variant(b, out_kind);   // (the variant with the tile loop)
         unsigned n_wgs = n_tiles;
         // (windows launched side by side on streams of their own take a workgroup per tile: the persistent launch's two sets of tile
         //  counters alternate per launch, which is only sound for launches that follow each other on ONE stream)
-        if (a.use_order && production && wgs_per_cu > 0 && tile_st == nullptr) n_wgs = std::min(n_tiles, (unsigned)wgs_per_cu * (unsigned)b->ctx->n_cu);
+        if (a.use_order && production && tile_st == nullptr) n_wgs = std::min(n_tiles, (unsigned)wgs_per_cu * (unsigned)b->ctx->n_cu);
         a.tile_ctr = a.tile_ctr_clear = b->ctx->tile_ctr;
         if (n_wgs < n_tiles) {   // (a persistent launch: this set of counters, and the other one zeroed for the next such launch)
             a.tile_ctr = b->ctx->tile_ctr + 256 * b->ctx->tile_ctr_set;
@@ -6070,37 +6004,19 @@ static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigne
             const WinRec& last = wt->w[wt->n - 1];
             const dim3 wgrid((unsigned)last.tile0 + (unsigned)last.win_ct * (unsigned)last.n_bands);
             a.use_order = 0;
-            if (out_kind == 0) {
-                if (b->n_grads > 0) SVGR_LAUNCH((k_tile_render_windows<0, true, true, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-                else if (b->n_groups > 0) SVGR_LAUNCH((k_tile_render_windows<0, true, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-                else SVGR_LAUNCH((k_tile_render_windows<0, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-            } else {
-                if (b->n_grads > 0) SVGR_LAUNCH((k_tile_render_windows<1, true, true, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-                else if (b->n_groups > 0) SVGR_LAUNCH((k_tile_render_windows<1, true, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-                else if (b->has_clips) SVGR_LAUNCH((k_tile_render_windows<1, true>), wgrid, dim3(NT), 0, lst, a, *wt);
-                else SVGR_LAUNCH((k_tile_render_windows<1, false>), wgrid, dim3(NT), 0, lst, a, *wt);
-            }
+            with_tile_variant(b, out_kind, [&](auto v) {
+                using V = decltype(v);
+                if constexpr (V::OUT <= 1 && (V::OUT == 1 || V::CLIP))   // (not the production variant: turned away above)
+                    SVGR_LAUNCH((k_tile_render_windows<V::OUT, V::CLIP, V::GROUPS, V::GRAD>), wgrid, dim3(NT), 0, lst, a, *wt);
+            });
             b->arena_zeroed = true;
             HIPCHK(hipGetLastError());
             return 0;
         }
-        static const int dyn_lds = getenv("SVGR_DBG_DYNLDS") ? atoi(getenv("SVGR_DBG_DYNLDS")) : 0;  // occupancy experiments
-        switch (out_kind) {
-            case 0:
-                if (b->n_grads > 0) SVGR_LAUNCH((k_tile_render<0, true, true, true>), grid, dim3(NT), 0, lst, a);
-                else if (b->n_groups > 0) SVGR_LAUNCH((k_tile_render<0, true, true>), grid, dim3(NT), 0, lst, a);
-                else if (b->has_clips) SVGR_LAUNCH((k_tile_render<0, true>), grid, dim3(NT), 0, lst, a);
-                else SVGR_LAUNCH((k_tile_render<0, false>), grid, dim3(NT), dyn_lds, lst, a);
-                break;
-            case 1:
-                if (b->n_grads > 0) SVGR_LAUNCH((k_tile_render<1, true, true, true>), grid, dim3(NT), 0, lst, a);
-                else if (b->n_groups > 0) SVGR_LAUNCH((k_tile_render<1, true, true>), grid, dim3(NT), 0, lst, a);
-                else if (b->has_clips) SVGR_LAUNCH((k_tile_render<1, true>), grid, dim3(NT), 0, lst, a);
-                else SVGR_LAUNCH((k_tile_render<1, false>), grid, dim3(NT), 0, lst, a);
-                break;
-            case 2: SVGR_LAUNCH(k_tile_render<2>, grid, dim3(NT), 0, lst, a); break;
-            default: SVGR_LAUNCH(k_tile_render<3>, grid, dim3(NT), 0, lst, a); break;
-        }
+        with_tile_variant(b, out_kind, [&](auto v) {
+            using V = decltype(v);
+            SVGR_LAUNCH((k_tile_render<V::OUT, V::CLIP, V::GROUPS, V::GRAD>), grid, dim3(NT), 0, lst, a);
+        });
         b->arena_zeroed = true;  // (done by that kernel, see TileArgs::arena)
     }
     if (timed) {
@@ -6108,19 +6024,6 @@ static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigne
         b->events.push_back(ev);
     }
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// page-locked staging of at least `bytes` for this context's read-backs (the stream is drained before a smaller one is replaced)
-static int ensure_pinned(svgr_ctx* c, size_t bytes) {
-    if (c->pinned_bytes >= bytes) return 0;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    c->pinned = nullptr;
-    c->pinned_bytes = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 20);
-    HIPCHK(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-    c->pinned_bytes = want;
     return 0;
 }
 

@@ -20,7 +20,6 @@ type here as in the reference (`Path.packed` has kept its packed segments since 
 """
 from __future__ import annotations
 
-import os
 import threading
 
 import numpy as np
@@ -29,7 +28,7 @@ from . import _abi
 from .geometry import ConvexHull, FLATNESS, Transform, _RULES, solid_paint
 from .layer import Layer
 
-ENABLED = os.environ.get("SVGR_NO_DISPLAY_LISTS") is None
+ENABLED = True   # (tests turn the display lists off to compare with the scene walk)
 _MAX_ENTRIES = 32
 _CACHE: "dict[int, tuple]" = {}     # id(scene) -> (scene, {linear_rgb: DisplayList or None})   (insertion-ordered: oldest first)
 _LOCK = threading.Lock()

@@ -645,7 +645,7 @@ def fill_plan_key(path, transform, fill_rule, paint4, viewport):
 
 
 # (STATE.serial numbers the top-level Scene.render calls (scene.py): the shared fills are drawn once per render)
-_SHARE_FILLS = __import__("os").environ.get("SVGR_NO_SHARED_FILLS") is None
+_SHARE_FILLS = True   # (off: every node-by-node fill in a batch of its own -- the route the tests compare the shared batch with)
 
 
 class _FillSet:

@@ -513,7 +513,7 @@ def _collect_mask_jobs(scene: Scene, transform: Transform, mask_only: bool, line
 # tall canvas to itself -- its leaves' matrices are moved down by a whole number of bands --, the geometry kernels run once
 # for all of them, and a run's layer is a render window of its range (svgr_batch_render_window, SVGR_RENDER_SAME_GEOMETRY).
 # A run whose geometry reaches far beyond the viewport's rows keeps a batch of its own (the range would be mostly air).
-_MERGE_RUNS = __import__("os").environ.get("SVGR_NO_MERGED_RUNS") is None
+_MERGE_RUNS = True   # (off: every run of fills in a batch of its own)
 _MERGE_MAX_TILES = 1 << 19     # tiles of the tall canvas (its per-tile tables grow with them); what does not fit starts another one
 _ROW_PAD = 4                   # rows kept free around a run's geometry (the anti-aliasing reaches one pixel)
 MERGE_STATS = {"shared_batches": 0, "runs_sharing": 0, "runs_alone": 0}   # counted since import (tests, profiles)
@@ -829,8 +829,8 @@ def _stroked(scene: Scene) -> Path:
     return out
 
 
-_BATCH_GROUPS = __import__("os").environ.get("SVGR_NO_BATCH_GROUPS") is None  # (off: isolated groups take the per-node route)
-_BATCH_GRADS = __import__("os").environ.get("SVGR_NO_BATCH_GRADIENTS") is None  # (off: gradient fills take the per-node route)
+_BATCH_GROUPS = True  # (off: isolated groups take the per-node route)
+_BATCH_GRADS = True  # (off: gradient fills take the per-node route)
 _ONES = np.ones(4)
 _ZERO4 = np.zeros(4)
 _ZERO4.flags.writeable = False   # (the paint of every clip source)
@@ -879,8 +879,8 @@ def _gradient_leaf(path, paint, rule, transform: Transform, linear_rgb: bool, op
     return _leaf(path, transform.m6(), _RULES[rule], mult, grad=(g, keep, paint, transform, bool(linear_rgb)))
 
 
-_NODE_RUNS = __import__("os").environ.get("SVGR_NO_NODE_RUNS") is None  # (off: a batchable node outside a GROUP's children goes node by node)
-_BATCH_BBOX_GRADS = __import__("os").environ.get("SVGR_NO_BATCH_BBOX_GRADIENTS") is None  # (off: objectBoundingBox gradients go node by node)
+_NODE_RUNS = True  # (off: a batchable node outside a GROUP's children goes node by node)
+_BATCH_BBOX_GRADS = True  # (off: objectBoundingBox gradients go node by node)
 _AXES_MEMO: dict = {}
 
 
@@ -1280,8 +1280,8 @@ def _run_window(leaves, batch):
 
 # (round 4 drew the windows a launch each on eight streams: 1.59 -> 0.73 ms of GPU time for icons.svg's 30, off by default because the
 #  host was the bound and the up-front launches cost it 0.1-0.2 ms.  Round 5: ONE launch for up to 64 windows -- a window table in
-#  the kernel argument --, on by default; SVGR_NO_WINDOW_PREFETCH draws a run's window when the walk meets it)
-_PREFETCH_WINDOWS = __import__("os").environ.get("SVGR_NO_WINDOW_PREFETCH") is None
+#  the kernel argument --, on by default; off, a run's window is drawn when the walk meets it)
+_PREFETCH_WINDOWS = True
 _PREFETCH_MAX_BYTES = 4 << 30   # of run layers drawn ahead of the walk; beyond it the runs are drawn when the walk meets them
 
 

@@ -74,7 +74,7 @@ def test_display_list_refuses_what_is_not_flat_and_rereads_paints():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["tiger", "material"])
 def test_display_list_render_is_the_walks_render(name, monkeypatch):
-    """The layer drawn from the display list against the layer the general route draws (SVGR_NO_DISPLAY_LISTS): same offset and
+    """The layer drawn from the display list against the layer the general route draws (`displaylist.ENABLED` off): same offset and
     shape, same pixels (1e-12: the order of the LDS atomics), same hull."""
     import svgrasterize_amd as S
     from svgrasterize_amd import displaylist, scenedump
