@@ -36,7 +36,9 @@ extern "C" {
  * 4: svgr_hash_buffers added (nothing changed or removed)
  * 6: svgr_batch_draw, svgr_measure_begin / _end / _launches added (nothing changed or removed)
  * 5: svgr_layer_compose_over / _in, svgr_layer_convert_scale_to, svgr_layer_convolve_ops, svgr_batch_get_extents added (nothing changed
- *    or removed) */
+ *    or removed)
+ * 6 (later, nothing changed or removed): svgr_layer_turbulence, svgr_layer_component_transfer, svgr_layer_convolve_matrix,
+ *    svgr_layer_displacement_map added (filter primitives beyond the reference) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -309,6 +311,38 @@ int svgr_layer_color_matrix(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const do
  * no padding: out is (rows - ky + 1, cols - kx + 1, 4).                                                          */
 int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, int64_t ky, int64_t kx,
                           int is_max);
+/* Filter primitives the reference does not implement (filters.py; DESIGN.md "Filter primitives beyond the reference").  All images
+ * are (rows, cols, 4) double, linear RGB; the arithmetic is svgr_core.h's (turb_point, transfer_fn) or written out below, in the
+ * order given, without contractions.                                                                                             */
+/* feTurbulence (Filter Effects 1): out (bbox[2] x bbox[3] x 4, straight alpha) at device offset (bbox[0], bbox[1]).  Pixel [R, C]
+ * is the device point (bbox[0] + R + 0.5, bbox[1] + C + 0.5); inv_m6 (rows 0-1 of the inverse transform) takes it to the user
+ * point (x, y) the noise is evaluated at.  tile = {x, y, width, height} of the stitch tile in user space; the lattice is set up
+ * on the host from `seed` (svgr::turb_init).  octaves 0..SVGR_TURBULENCE_MAX_OCTAVES, base frequencies >= 0, fractal: 0 turbulence,
+ * 1 fractalNoise; stitch: 0 noStitch, 1 stitch.                                                                                 */
+#define SVGR_TURBULENCE_MAX_OCTAVES 32
+int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, const double* inv_m6, double base_fx, double base_fy,
+                          const double* tile, int64_t seed, int octaves, int fractal, int stitch);
+/* feComponentTransfer in place on a straight-alpha image of n_px pixels.  types[4] (R, G, B, A): 0 identity, 1 table, 2 discrete,
+ * 3 linear, 4 gamma; params = 4 x 5 {slope, intercept, amplitude, exponent, offset}; n_values[4] table lengths, `values` the
+ * four tables back to back (at most SVGR_TRANSFER_MAX_VALUES in all).                                                          */
+#define SVGR_TRANSFER_MAX_VALUES 4096
+int svgr_layer_component_transfer(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const int* types, const double* params,
+                                  const int64_t* n_values, const double* values);
+/* feConvolveMatrix: out (rows, cols, 4) from src (rows, cols, 4); kernel = order_y x order_x row-major; X = column, Y = row:
+ * out[Y][X] = (sum_{I < order_y} sum_{J < order_x} src[Y - target_y + I][X - target_x + J] * kernel[order_y-1-I][order_x-1-J])
+ *             / divisor + bias, I outer, J inner.  edge_mode: 0 duplicate, 1 wrap, 2 none (zero).  preserve_alpha 0: all four
+ * channels of a premultiplied src, alpha clamped to [0, 1], colour to [0, alpha]; 1: colour of a straight src clamped to [0, 1],
+ * alpha copied.  out must not be src.                                                                                          */
+#define SVGR_CONVOLVE_MATRIX_MAX_ORDER 32
+int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, const double* kernel,
+                               int64_t order_x, int64_t order_y, int64_t target_x, int64_t target_y, double divisor, double bias,
+                               int edge_mode, int preserve_alpha);
+/* feDisplacementMap: out (premultiplied, bbox out_bbox) from the straight-alpha map (same bbox) and the premultiplied src (bbox
+ * src_bbox).  d = scale * (map[x_channel] - 0.5, map[y_channel] - 0.5) in user space, lin4 = {m00, m01, m10, m11} the linear
+ * part of the transform: out[R, C] = the src pixel containing (out_bbox[0] + R + 0.5 + (m00 d0 + m01 d1),
+ * out_bbox[1] + C + 0.5 + (m10 d0 + m11 d1)), transparent outside src.  Channels 0..3 = R, G, B, A.                            */
+int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* map, const svgr_buf* src,
+                                const int64_t* src_bbox, const double* lin4, double scale, int x_channel, int y_channel);
 /* Luminance of a straight-alpha RGBA image for RENDER_MASK (S:735): out(n_px doubles) = (rgb . {0.2125, 0.7154, 0.072}) * a */
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out_1ch, const svgr_buf* src_rgba, int64_t n_px);
 

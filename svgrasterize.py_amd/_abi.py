@@ -126,6 +126,11 @@ _PROTOS = {
     "svgr_layer_color_matrix": (C.c_int, [_P, _P, C.c_int64, _P]),
     "svgr_layer_morphology": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "svgr_layer_luminance": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "svgr_layer_turbulence": (C.c_int, [_P, _P, _P, _P, C.c_double, C.c_double, _P, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "svgr_layer_component_transfer": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P]),
+    "svgr_layer_convolve_matrix": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                              C.c_double, C.c_double, C.c_int, C.c_int]),
+    "svgr_layer_displacement_map": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int]),
     "svgr_gradient_fill": (C.c_int, [_P, C.POINTER(Gradient), _P, _P, _P]),
     "svgr_gradient_eval": (C.c_int, [_P, C.POINTER(Gradient), _P, C.c_int64, _P]),
     "svgr_pattern_fill": (C.c_int, [_P, C.POINTER(PatternArgs), _P, _P, _P, _P]),

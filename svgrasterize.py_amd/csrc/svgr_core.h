@@ -439,4 +439,177 @@ SVGR_HD void over_px_fma(double* dst, double s0, double s1, double s2, double s3
     dst[3] = fma(dst[3], k, s3);
 }
 
+// ------------------------------------------------------------------------------------
+// feTurbulence (SVG 1.1 / Filter Effects 1, the spec's C reference code).  The lattice depends on the seed only and is
+// set up on the host once per primitive (turb_init); turb_point evaluates the four channels of one user-space point.
+// Gradients are stored lattice-major: grad[(i * 4 + k) * 2 + axis] = the spec's gradient[k][i][axis], so the eight
+// numbers one lattice point contributes to the four channels sit side by side.  Indices and stitch state are int64:
+// the spec's ints overflow once `wrap` has doubled for twenty octaves.
+// ------------------------------------------------------------------------------------
+constexpr int kTurbBSize = 0x100, kTurbBM = 0xff, kTurbN = 0x1000;
+constexpr int kTurbLattice = kTurbBSize + kTurbBSize + 2;   // 514
+constexpr int kTurbMaxOctaves = 32;
+constexpr int64_t kTurbM = 2147483647, kTurbA = 16807, kTurbQ = 127773, kTurbR = 2836;
+
+SVGR_HD int64_t turb_setup_seed(int64_t s) {
+    if (s <= 0) s = -(s % (kTurbM - 1)) + 1;
+    if (s > kTurbM - 1) s = kTurbM - 1;
+    return s;
+}
+
+SVGR_HD int64_t turb_random(int64_t s) {
+    int64_t r = kTurbA * (s % kTurbQ) - kTurbR * (s / kTurbQ);
+    if (r <= 0) r += kTurbM;
+    return r;
+}
+
+// sel: 514 ints, grad: 514 * 4 * 2 doubles.  A zero gradient (both draws 256) stays zero instead of 0 / 0.
+SVGR_HD void turb_init(int64_t seed, int* sel, double* grad) {
+    int64_t s = turb_setup_seed(seed);
+    for (int k = 0; k < 4; ++k) {
+        for (int i = 0; i < kTurbBSize; ++i) {
+            sel[i] = i;
+            for (int j = 0; j < 2; ++j) {
+                s = turb_random(s);
+                grad[(i * 4 + k) * 2 + j] = (double)(s % (2 * kTurbBSize) - kTurbBSize) / kTurbBSize;
+            }
+            double* g = grad + (i * 4 + k) * 2;
+            const double len = sqrt(g[0] * g[0] + g[1] * g[1]);
+            if (len > 0.0) {
+                g[0] = g[0] / len;
+                g[1] = g[1] / len;
+            }
+        }
+    }
+    for (int i = kTurbBSize - 1; i > 0; --i) {
+        const int t = sel[i];
+        s = turb_random(s);
+        const int j = (int)(s % kTurbBSize);
+        sel[i] = sel[j];
+        sel[j] = t;
+    }
+    for (int i = 0; i < kTurbBSize + 2; ++i) {
+        sel[kTurbBSize + i] = sel[i];
+        for (int q = 0; q < 8; ++q) grad[(kTurbBSize + i) * 8 + q] = grad[i * 8 + q];
+    }
+}
+
+// Everything of a primitive that is the same for every pixel: the (stitch-adjusted) base frequencies and the stitch state
+// of the first octave.  tile = {x, y, width, height} in user space.
+struct TurbParams {
+    double fx, fy;
+    int64_t width, height, wrap_x, wrap_y;
+    int octaves, fractal, stitch;
+};
+
+SVGR_HD double turb_stitch_freq(double f, double w) {
+    const double lo = floor(w * f) / w, hi = ceil(w * f) / w;
+    return f / lo < hi / f ? lo : hi;
+}
+
+SVGR_HD TurbParams turb_params(double fx, double fy, const double* tile, int octaves, int fractal, int stitch) {
+    TurbParams p;
+    p.octaves = octaves;
+    p.fractal = fractal;
+    p.stitch = stitch;
+    p.width = p.height = p.wrap_x = p.wrap_y = 0;
+    if (stitch) {
+        if (fx != 0.0) fx = turb_stitch_freq(fx, tile[2]);
+        if (fy != 0.0) fy = turb_stitch_freq(fy, tile[3]);
+        p.width = (int64_t)(tile[2] * fx + 0.5);
+        p.wrap_x = (int64_t)(tile[0] * fx + kTurbN + (double)p.width);
+        p.height = (int64_t)(tile[3] * fy + 0.5);
+        p.wrap_y = (int64_t)(tile[1] * fy + kTurbN + (double)p.height);
+    }
+    p.fx = fx;
+    p.fy = fy;
+    return p;
+}
+
+SVGR_HD double turb_s_curve(double t) { return t * t * (3.0 - 2.0 * t); }
+
+// The four channels of feTurbulence at user-space point (px, py), clamped to [0, 1] (straight alpha, RGBA).  The lattice
+// indices, the s-curves and the stitch state of an octave are shared by the channels; each channel then runs the spec's
+// noise2 arithmetic in the spec's order.
+SVGR_HD void turb_point(const int* sel, const double* grad, const TurbParams& p, double px, double py, double* out) {
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    double vx = px * p.fx, vy = py * p.fy, ratio = 1.0;
+    int64_t width = p.width, height = p.height, wrap_x = p.wrap_x, wrap_y = p.wrap_y;
+    for (int o = 0; o < p.octaves; ++o) {
+        const double tx = vx + kTurbN, ty = vy + kTurbN;
+        int64_t bx0 = (int64_t)tx, by0 = (int64_t)ty;
+        int64_t bx1 = bx0 + 1, by1 = by0 + 1;
+        const double rx0 = tx - (double)(int64_t)tx, ry0 = ty - (double)(int64_t)ty;
+        const double rx1 = rx0 - 1.0, ry1 = ry0 - 1.0;
+        if (p.stitch) {
+            if (bx0 >= wrap_x) bx0 -= width;
+            if (bx1 >= wrap_x) bx1 -= width;
+            if (by0 >= wrap_y) by0 -= height;
+            if (by1 >= wrap_y) by1 -= height;
+        }
+        bx0 &= kTurbBM; bx1 &= kTurbBM; by0 &= kTurbBM; by1 &= kTurbBM;
+        const int i = sel[bx0], j = sel[bx1];
+        const int b00 = sel[i + by0], b10 = sel[j + by0], b01 = sel[i + by1], b11 = sel[j + by1];
+        const double sx = turb_s_curve(rx0), sy = turb_s_curve(ry0);
+        for (int k = 0; k < 4; ++k) {
+            const double* q00 = grad + (b00 * 4 + k) * 2;
+            const double* q10 = grad + (b10 * 4 + k) * 2;
+            const double* q01 = grad + (b01 * 4 + k) * 2;
+            const double* q11 = grad + (b11 * 4 + k) * 2;
+            double u = rx0 * q00[0] + ry0 * q00[1];
+            double v = rx1 * q10[0] + ry0 * q10[1];
+            const double a = u + sx * (v - u);
+            u = rx0 * q01[0] + ry1 * q01[1];
+            v = rx1 * q11[0] + ry1 * q11[1];
+            const double b = u + sx * (v - u);
+            const double n = a + sy * (b - a);
+            sum[k] = sum[k] + (p.fractal ? n : fabs(n)) / ratio;
+        }
+        vx = vx * 2.0;
+        vy = vy * 2.0;
+        ratio = ratio * 2.0;
+        if (p.stitch) {
+            width = width + width;
+            height = height + height;
+            wrap_x = 2 * wrap_x - kTurbN;
+            wrap_y = 2 * wrap_y - kTurbN;
+        }
+    }
+    for (int k = 0; k < 4; ++k) {
+        double c = p.fractal ? (sum[k] + 1.0) * 0.5 : sum[k];
+        out[k] = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// feComponentTransfer: one transfer function on one channel value (straight alpha).  type: 0 identity, 1 table,
+// 2 discrete, 3 linear, 4 gamma; prm = {slope, intercept, amplitude, exponent, offset}; v = the n table values.
+// ------------------------------------------------------------------------------------
+enum { kXferIdentity = 0, kXferTable = 1, kXferDiscrete = 2, kXferLinear = 3, kXferGamma = 4 };
+
+SVGR_HD double transfer_fn(double c, int type, const double* prm, const double* v, int n) {
+    c = c > 0.0 ? (c < 1.0 ? c : 1.0) : 0.0;   // (NaN -> 0: it must not reach a table index)
+    double r = c;
+    if (type == kXferTable && n > 0) {
+        if (n == 1) {
+            r = v[0];
+        } else {
+            const int m = n - 1;
+            const double t = c * m;
+            int k = (int)floor(t);
+            k = k < m - 1 ? k : m - 1;
+            r = v[k] + (t - k) * (v[k + 1] - v[k]);
+        }
+    } else if (type == kXferDiscrete && n > 0) {
+        int k = (int)floor(c * n);
+        k = k < n - 1 ? k : n - 1;
+        r = v[k];
+    } else if (type == kXferLinear) {
+        r = prm[0] * c + prm[1];
+    } else if (type == kXferGamma) {
+        r = prm[2] * pow(c, prm[3]) + prm[4];
+    }
+    return r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
+}
+
 }  // namespace svgr

@@ -3483,6 +3483,154 @@ __global__ void k_layer_morphology(double* __restrict__ out, const double* __res
     o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
 }
 
+// ---- filter primitives the reference does not implement (feTurbulence, feComponentTransfer, feConvolveMatrix,
+//      feDisplacementMap; DESIGN.md "Filter primitives beyond the reference") ----
+
+// feTurbulence over a layer at (o0, o1): pixel [R, C] is the device point (o0 + R + 0.5, o1 + C + 0.5), taken to user space
+// by inv (plain products and sums, left to right) and evaluated by svgr::turb_point.  The lattice (35 KB) is staged in LDS
+// once per workgroup and the workgroup strides over many pixels; one double4 store per pixel.
+struct TurbLaunch {
+    double inv[6];
+    svgr::TurbParams p;
+    int o0, o1, rows, cols;
+};
+__global__ __launch_bounds__(256) void k_layer_turbulence(double* __restrict__ out, const int* __restrict__ sel_g,
+                                                          const double* __restrict__ grad_g, TurbLaunch a) {
+    __shared__ double grad[svgr::kTurbLattice * 8];
+    __shared__ int sel[svgr::kTurbLattice];
+    for (int q = threadIdx.x; q < svgr::kTurbLattice * 8; q += blockDim.x) grad[q] = grad_g[q];
+    for (int q = threadIdx.x; q < svgr::kTurbLattice; q += blockDim.x) sel[q] = sel_g[q];
+    __syncthreads();
+    const size_t n = (size_t)a.rows * a.cols;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int R = (int)(i / a.cols), C = (int)(i % a.cols);
+        const double d0 = (double)(a.o0 + R) + 0.5, d1 = (double)(a.o1 + C) + 0.5;
+        const double px = a.inv[0] * d0 + a.inv[1] * d1 + a.inv[2];
+        const double py = a.inv[3] * d0 + a.inv[4] * d1 + a.inv[5];
+        double c[4];
+        svgr::turb_point(sel, grad, a.p, px, py, c);
+        reinterpret_cast<double4*>(out)[i] = make_double4(c[0], c[1], c[2], c[3]);
+    }
+}
+
+// feComponentTransfer in place on straight-alpha RGBA: channel k through svgr::transfer_fn.  blob (staged in LDS) =
+// 4 x 5 parameters {slope, intercept, amplitude, exponent, offset}, then the four tables back to back.
+struct XferLaunch {
+    int type0, type1, type2, type3;
+    int n0, n1, n2, n3;
+    int off0, off1, off2, off3;
+    int n_blob;
+};
+__global__ __launch_bounds__(256) void k_layer_component_transfer(double* __restrict__ img, size_t n_px, const double* __restrict__ blob_g,
+                                                                  XferLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* blob = (double*)smem;
+    for (int q = threadIdx.x; q < a.n_blob; q += blockDim.x) blob[q] = blob_g[q];
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_px; i += (size_t)gridDim.x * blockDim.x) {
+        double4 v = reinterpret_cast<const double4*>(img)[i];
+        v.x = svgr::transfer_fn(v.x, a.type0, blob + 0, blob + a.off0, a.n0);
+        v.y = svgr::transfer_fn(v.y, a.type1, blob + 5, blob + a.off1, a.n1);
+        v.z = svgr::transfer_fn(v.z, a.type2, blob + 10, blob + a.off2, a.n2);
+        v.w = svgr::transfer_fn(v.w, a.type3, blob + 15, blob + a.off3, a.n3);
+        reinterpret_cast<double4*>(img)[i] = v;
+    }
+}
+
+// feConvolveMatrix: a T x T workgroup computes a T x T output tile from a (T + oy - 1) x (T + ox - 1) input tile in LDS
+// (edge mode applied as it is loaded) and the weights in LDS.  out[R, C] = sum over I (rows, outer), J (cols, inner) of
+// src[R - ty + I, C - tx + J] * K[oy - 1 - I][ox - 1 - J], then / divisor + bias.  preserve = 0: all four channels of a
+// premultiplied source, alpha clamped to [0, 1] and colour to [0, alpha]; 1: the colours of a straight source clamped to
+// [0, 1], alpha copied.
+struct CmLaunch {
+    int rows, cols, ox, oy, tx, ty, edge, preserve, tiles_x;
+    double divisor, bias;
+};
+__global__ __launch_bounds__(256) void k_layer_convolve_matrix(double* __restrict__ out, const double* __restrict__ src,
+                                                               const double* __restrict__ w_g, CmLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int T = blockDim.x;
+    const int hr = T + a.oy - 1, hc = T + a.ox - 1;
+    double4* tile = (double4*)smem;
+    double* w = (double*)(smem + (size_t)hr * hc * sizeof(double4));
+    const int tid = threadIdx.y * T + threadIdx.x, nt = T * T;
+    for (int q = tid; q < a.ox * a.oy; q += nt) w[q] = w_g[q];
+    const int tile_r = (int)blockIdx.x / a.tiles_x, tile_c = (int)blockIdx.x % a.tiles_x;
+    const int r0 = tile_r * T - a.ty, c0 = tile_c * T - a.tx;
+    const double4* s4 = (const double4*)src;
+    for (int q = tid; q < hr * hc; q += nt) {
+        int r = r0 + q / hc, c = c0 + q % hc;
+        bool inside = true;
+        if (a.edge == 0) {          // duplicate
+            r = r < 0 ? 0 : (r >= a.rows ? a.rows - 1 : r);
+            c = c < 0 ? 0 : (c >= a.cols ? a.cols - 1 : c);
+        } else if (a.edge == 1) {   // wrap
+            r = ((r % a.rows) + a.rows) % a.rows;
+            c = ((c % a.cols) + a.cols) % a.cols;
+        } else {                    // none
+            inside = r >= 0 && r < a.rows && c >= 0 && c < a.cols;
+        }
+        tile[q] = inside ? s4[(size_t)r * a.cols + c] : make_double4(0.0, 0.0, 0.0, 0.0);
+    }
+    __syncthreads();
+    const int R = tile_r * T + (int)threadIdx.y, C = tile_c * T + (int)threadIdx.x;
+    if (R >= a.rows || C >= a.cols) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int I = 0; I < a.oy; ++I) {
+        const double4* row = tile + (size_t)(threadIdx.y + I) * hc + threadIdx.x;
+        const double* wr = w + (size_t)(a.oy - 1 - I) * a.ox + (a.ox - 1);
+        for (int J = 0; J < a.ox; ++J) {
+            const double4 v = row[J];
+            const double k = wr[-J];
+            s0 = s0 + v.x * k;
+            s1 = s1 + v.y * k;
+            s2 = s2 + v.z * k;
+            s3 = s3 + v.w * k;
+        }
+    }
+    s0 = s0 / a.divisor + a.bias;
+    s1 = s1 / a.divisor + a.bias;
+    s2 = s2 / a.divisor + a.bias;
+    double al;
+    if (a.preserve) {
+        al = s4[(size_t)R * a.cols + C].w;
+        s0 = s0 < 0.0 ? 0.0 : (s0 > 1.0 ? 1.0 : s0);
+        s1 = s1 < 0.0 ? 0.0 : (s1 > 1.0 ? 1.0 : s1);
+        s2 = s2 < 0.0 ? 0.0 : (s2 > 1.0 ? 1.0 : s2);
+    } else {
+        al = s3 / a.divisor + a.bias;
+        al = al < 0.0 ? 0.0 : (al > 1.0 ? 1.0 : al);
+        s0 = s0 < 0.0 ? 0.0 : (s0 > al ? al : s0);
+        s1 = s1 < 0.0 ? 0.0 : (s1 > al ? al : s1);
+        s2 = s2 < 0.0 ? 0.0 : (s2 > al ? al : s2);
+    }
+    reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(s0, s1, s2, al);
+}
+
+// feDisplacementMap: out has the map's extent (o0, o1, rows, cols).  d_user = scale * (map[XC] - 0.5, map[YC] - 0.5) of the
+// straight-alpha map, d_dev = L d_user, and the output pixel is the premultiplied source pixel containing the device point
+// (o0 + R + 0.5 + d_dev0, o1 + C + 0.5 + d_dev1); transparent outside the source.
+struct DmLaunch {
+    int o0, o1, rows, cols, s0, s1, srows, scols, xc, yc;
+    double l00, l01, l10, l11, scale;
+};
+__device__ __forceinline__ double dm_channel(const double4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
+__global__ __launch_bounds__(256) void k_layer_displacement_map(double* __restrict__ out, const double* __restrict__ map,
+                                                                const double* __restrict__ src, DmLaunch a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)a.rows * a.cols) return;
+    const int R = (int)(i / a.cols), C = (int)(i % a.cols);
+    const double4 m = reinterpret_cast<const double4*>(map)[i];
+    const double du0 = a.scale * (dm_channel(m, a.xc) - 0.5), du1 = a.scale * (dm_channel(m, a.yc) - 0.5);
+    const double dd0 = a.l00 * du0 + a.l01 * du1, dd1 = a.l10 * du0 + a.l11 * du1;
+    const double p0 = (double)(a.o0 + R) + 0.5 + dd0, p1 = (double)(a.o1 + C) + 0.5 + dd1;
+    const double r = floor(p0) - a.s0, c = floor(p1) - a.s1;   // (compared as doubles: a far displacement overflows no int)
+    double4 v = make_double4(0.0, 0.0, 0.0, 0.0);
+    if (r >= 0.0 && r < (double)a.srows && c >= 0.0 && c < (double)a.scols)
+        v = reinterpret_cast<const double4*>(src)[(size_t)r * a.scols + (size_t)c];
+    reinterpret_cast<double4*>(out)[i] = v;
+}
+
 // luminance mask (S:735): out(1 channel) = (rgb @ [0.2125, 0.7154, 0.072]) * alpha of a straight-alpha layer
 __global__ void k_layer_luminance(double* __restrict__ out, const double* __restrict__ src, size_t n_px) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -6177,6 +6325,149 @@ int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int
     HIPCHK(enter_ctx(ctx));
     SVGR_LAUNCH(k_layer_morphology, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)src->ptr, (int)rows, (int)cols,
                        (int)ky, (int)kx, is_max);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Host array -> a pool block on the context's stream; the caller synchronises the stream before it returns (the host array is
+// the caller's) and gives the block back.
+static hipError_t upload_tmp(svgr_ctx* ctx, void** dev, const void* host, size_t bytes) {
+    *dev = nullptr;
+    hipError_t e = g_pool.alloc(dev, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    return e;
+}
+
+static_assert(svgr::kTurbMaxOctaves == SVGR_TURBULENCE_MAX_OCTAVES, "one octave limit");
+static inline unsigned stride_blocks(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 1024)); }
+
+int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, const double* inv_m6, double base_fx, double base_fy,
+                          const double* tile, int64_t seed, int octaves, int fractal, int stitch) {
+    if (!ctx || !out || !inv_m6 || !tile || !bbox_ok(bbox) || octaves < 0 || octaves > svgr::kTurbMaxOctaves || !(base_fx >= 0.0) ||
+        !(base_fy >= 0.0) || (fractal != 0 && fractal != 1) || (stitch != 0 && stitch != 1))
+        return fail(SVGR_E_INVALID, "svgr_layer_turbulence: bad arguments (octaves 0..%d, base frequencies >= 0)", svgr::kTurbMaxOctaves);
+    const size_t n = (size_t)bbox[2] * (size_t)bbox[3];
+    if (out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_turbulence: buffer too small");
+    if (n == 0) return 0;
+    return abi_guard("svgr_layer_turbulence", [&]() -> int {
+        std::vector<char> host(sizeof(double) * svgr::kTurbLattice * 8 + sizeof(int) * svgr::kTurbLattice);
+        double* grad = (double*)host.data();
+        int* sel = (int*)(grad + svgr::kTurbLattice * 8);
+        svgr::turb_init(seed, sel, grad);
+        TurbLaunch a;
+        memcpy(a.inv, inv_m6, sizeof a.inv);
+        a.p = svgr::turb_params(base_fx, base_fy, tile, octaves, fractal, stitch);
+        a.o0 = (int)bbox[0]; a.o1 = (int)bbox[1]; a.rows = (int)bbox[2]; a.cols = (int)bbox[3];
+        HIPCHK(enter_ctx(ctx));
+        void* dev = nullptr;
+        hipError_t e = upload_tmp(ctx, &dev, host.data(), host.size());
+        if (e == hipSuccess) {
+            SVGR_LAUNCH(k_layer_turbulence, dim3(stride_blocks(n)), dim3(256), 0, ctx->stream, (double*)out->ptr,
+                        (const int*)((const double*)dev + svgr::kTurbLattice * 8), (const double*)dev, a);
+            e = hipGetLastError();
+            hipError_t e2 = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = e2;
+        }
+        if (dev) g_pool.release(dev);
+        if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_turbulence: %s", hipGetErrorString(e));
+        return 0;
+    });
+}
+
+int svgr_layer_component_transfer(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const int* types, const double* params,
+                                  const int64_t* n_values, const double* values) {
+    if (!ctx || !img || !types || !params || !n_values || n_px < 0 || img->bytes < (size_t)n_px * 32)
+        return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: bad arguments");
+    int64_t total = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (types[k] < svgr::kXferIdentity || types[k] > svgr::kXferGamma || n_values[k] < 0)
+            return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: channel %d: bad type %d or table length", k, types[k]);
+        total += n_values[k];
+    }
+    if (total > SVGR_TRANSFER_MAX_VALUES)
+        return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: %lld table values (at most %d)", (long long)total, SVGR_TRANSFER_MAX_VALUES);
+    if (total > 0 && !values) return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: values is NULL");
+    if (n_px == 0) return 0;
+    return abi_guard("svgr_layer_component_transfer", [&]() -> int {
+        std::vector<double> blob(20 + (size_t)total);
+        memcpy(blob.data(), params, sizeof(double) * 20);
+        if (total) memcpy(blob.data() + 20, values, sizeof(double) * (size_t)total);
+        XferLaunch a;
+        int off[4], cnt[4];
+        int64_t at = 20;
+        for (int k = 0; k < 4; ++k) { off[k] = (int)at; cnt[k] = (int)n_values[k]; at += n_values[k]; }
+        a.type0 = types[0]; a.type1 = types[1]; a.type2 = types[2]; a.type3 = types[3];
+        a.n0 = cnt[0]; a.n1 = cnt[1]; a.n2 = cnt[2]; a.n3 = cnt[3];
+        a.off0 = off[0]; a.off1 = off[1]; a.off2 = off[2]; a.off3 = off[3];
+        a.n_blob = (int)blob.size();
+        HIPCHK(enter_ctx(ctx));
+        void* dev = nullptr;
+        hipError_t e = upload_tmp(ctx, &dev, blob.data(), sizeof(double) * blob.size());
+        if (e == hipSuccess) {
+            SVGR_LAUNCH(k_layer_component_transfer, dim3(stride_blocks((size_t)n_px)), dim3(256), (unsigned)(sizeof(double) * blob.size()),
+                        ctx->stream, (double*)img->ptr, (size_t)n_px, (const double*)dev, a);
+            e = hipGetLastError();
+            hipError_t e2 = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = e2;
+        }
+        if (dev) g_pool.release(dev);
+        if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_component_transfer: %s", hipGetErrorString(e));
+        return 0;
+    });
+}
+
+int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, const double* kernel,
+                               int64_t order_x, int64_t order_y, int64_t target_x, int64_t target_y, double divisor, double bias,
+                               int edge_mode, int preserve_alpha) {
+    if (!ctx || !out || !src || !kernel || rows <= 0 || cols <= 0 || rows > (1 << 24) || cols > (1 << 24) || order_x < 1 || order_y < 1 ||
+        order_x > SVGR_CONVOLVE_MATRIX_MAX_ORDER || order_y > SVGR_CONVOLVE_MATRIX_MAX_ORDER || target_x < 0 || target_x >= order_x ||
+        target_y < 0 || target_y >= order_y || divisor == 0.0 || edge_mode < 0 || edge_mode > 2 || (preserve_alpha != 0 && preserve_alpha != 1))
+        return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: bad arguments (order 1..%d, target inside the kernel, divisor != 0, "
+                                    "edge mode 0..2)", SVGR_CONVOLVE_MATRIX_MAX_ORDER);
+    const size_t n = (size_t)rows * (size_t)cols;
+    if (src->bytes < n * 32 || out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: buffer too small");
+    if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: out must not be src");
+    // 16 x 16 tiles while the input tile and the weights fit in 64 KiB of LDS, 8 x 8 beyond (order 32: 56 KiB)
+    auto lds = [&](int T) { return (size_t)(T + order_y - 1) * (size_t)(T + order_x - 1) * 32 + (size_t)order_x * order_y * 8; };
+    const int T = lds(16) <= (64u << 10) ? 16 : 8;
+    CmLaunch a;
+    a.rows = (int)rows; a.cols = (int)cols; a.ox = (int)order_x; a.oy = (int)order_y; a.tx = (int)target_x; a.ty = (int)target_y;
+    a.edge = edge_mode; a.preserve = preserve_alpha; a.divisor = divisor; a.bias = bias;
+    a.tiles_x = (int)((cols + T - 1) / T);
+    const size_t tiles = (size_t)a.tiles_x * (size_t)((rows + T - 1) / T);
+    HIPCHK(enter_ctx(ctx));
+    void* dev = nullptr;
+    hipError_t e = upload_tmp(ctx, &dev, kernel, sizeof(double) * (size_t)(order_x * order_y));
+    if (e == hipSuccess) {
+        SVGR_LAUNCH(k_layer_convolve_matrix, dim3((unsigned)tiles), dim3(T, T), (unsigned)lds(T), ctx->stream, (double*)out->ptr,
+                    (const double*)src->ptr, (const double*)dev, a);
+        e = hipGetLastError();
+        hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = e2;
+    }
+    if (dev) g_pool.release(dev);
+    if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_convolve_matrix: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* map, const svgr_buf* src,
+                                const int64_t* src_bbox, const double* lin4, double scale, int x_channel, int y_channel) {
+    if (!ctx || !out || !map || !src || !lin4 || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || x_channel < 0 || x_channel > 3 ||
+        y_channel < 0 || y_channel > 3)
+        return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: bad arguments (channels 0..3)");
+    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
+    if (out->bytes < n * 32 || map->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+        return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: buffer too small");
+    if (out->ptr == src->ptr || out->ptr == map->ptr) return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: out must not be an input");
+    if (n == 0) return 0;
+    DmLaunch a;
+    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
+    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
+    a.xc = x_channel; a.yc = y_channel;
+    a.l00 = lin4[0]; a.l01 = lin4[1]; a.l10 = lin4[2]; a.l11 = lin4[3]; a.scale = scale;
+    HIPCHK(enter_ctx(ctx));
+    SVGR_LAUNCH(k_layer_displacement_map, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)map->ptr,
+                (const double*)src->ptr, a);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,9 +1,19 @@
 """Filter effects (reference S:1716-1944): feGaussianBlur (the one on the hot path) and the other
-primitives the reference implements -- feOffset, feMerge, feBlend, feComposite, feColorMatrix, feMorphology (8f-4).
+primitives the reference implements -- feOffset, feMerge, feBlend, feComposite, feColorMatrix, feMorphology (8f-4) --,
+plus primitives the reference does not have: feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix,
+feDisplacementMap and feDropShadow (expanded into the others by ``Filter.drop_shadow``).
 
 ``Filter`` keeps the reference's (names, filters) structure so scene dumps replay unchanged.  The blur weights are
 built on the host exactly like ``blur_kernel`` does (a few thousand numbers); every per-pixel operation runs on the
-GPU (``svgr_layer_convolve``, ``svgr_layer_blend``, ``svgr_layer_color_matrix``, ``svgr_layer_morphology``)."""
+GPU (``svgr_layer_convolve``, ``svgr_layer_blend``, ``svgr_layer_color_matrix``, ``svgr_layer_morphology``,
+``svgr_layer_turbulence``, ``svgr_layer_component_transfer``, ``svgr_layer_convolve_matrix``, ``svgr_layer_displacement_map``).
+
+The chain runs in linearRGB (``color-interpolation-filters`` is ignored, as in the reference).  The generators (feFlood,
+feTurbulence) cover the filter region: the ``<filter>``'s x / y / width / height in ``filterUnits`` (default
+objectBoundingBox, -10% / -10% / 120% / 120%), resolved at call time against the hull's bounding box in user space (or the
+source layer's extent when there is no hull) and rounded out to whole device pixels.  The other primitives keep the extent
+of their input; in particular feComponentTransfer leaves the pixels outside its input transparent even where feFuncA maps
+0 to something else.  Primitive subregions and ``primitiveUnits`` are not supported."""
 from __future__ import annotations
 
 import math
@@ -12,7 +22,7 @@ from typing import NamedTuple
 import numpy as np
 
 from .geometry import Transform
-from .layer import Layer
+from .layer import COMPOSE_IN, Layer
 
 import warnings
 
@@ -41,6 +51,43 @@ def color_matrix_hue_rotate(angle: float) -> np.ndarray:
 def color_matrix_saturate(value: float) -> np.ndarray:
     """4x5 colour matrix of feColorMatrix ``saturate`` (S:1954-1957)."""
     return _hue_matrix(value, 0)
+
+
+# feDropShadow's first step: the input's alpha, colour zero (a colour matrix on straight alpha)
+COLOR_MATRIX_ALPHA = np.array([[0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0, 0, 0, 1, 0]], dtype=np.float64)
+# limits of the C ABI (include/svgr.h): SVGR_TURBULENCE_MAX_OCTAVES, SVGR_TRANSFER_MAX_VALUES, SVGR_CONVOLVE_MATRIX_MAX_ORDER
+TURBULENCE_MAX_OCTAVES, TRANSFER_MAX_VALUES, CONVOLVE_MATRIX_MAX_ORDER = 32, 4096, 32
+# the filter region of a generator: (objectBoundingBox units?, x, y, width, height); None entries take the defaults below
+FILTER_REGION_DEFAULT = (True, -0.1, -0.1, 1.2, 1.2)
+
+
+def _user_bbox(transform: Transform, source: Layer, hull=None):
+    """[x, y, width, height] in user space of the hull (ConvexHull.bbox), or of the source layer's extent without one."""
+    if hull is not None and len(hull.points) > 0:
+        return hull.bbox(transform)
+    r0, c0 = source.offset
+    r1, c1 = r0 + source.height, c0 + source.width
+    pts = transform.invert(np.array([[r0, c0], [r0, c1], [r1, c0], [r1, c1]], dtype=np.float64))
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    return [lo[0], lo[1], hi[0] - lo[0], hi[1] - lo[1]]
+
+
+def filter_region(region, transform: Transform, source: Layer, hull=None):
+    """(offset, shape, (x, y, width, height)): the device pixels of the filter region `region` (see FILTER_REGION_DEFAULT)
+    -- the integer box (floor / ceil) around its four transformed corners, at least one pixel -- and the region in user
+    space.  objectBoundingBox values are fractions of the hull's bounding box (`_user_bbox`)."""
+    bbox_units, *vals = FILTER_REGION_DEFAULT if region is None else region
+    if bbox_units or any(v is None for v in vals):
+        bx, by, bw, bh = _user_bbox(transform, source, hull)
+        fx, fy, fw, fh = (d if v is None else v for v, d in zip(vals, FILTER_REGION_DEFAULT[1:]))
+        rel = (bx + fx * bw, by + fy * bh, fw * bw, fh * bh)
+        # (userSpaceOnUse without a value: the objectBoundingBox default for it; the viewport is not known here)
+        vals = rel if bbox_units else [r if v is None else v for v, r in zip(vals, rel)]
+    x, y, w, h = (float(v) for v in vals)
+    corners = transform(np.array([[x, y], [x + w, y], [x, y + h], [x + w, y + h]], dtype=np.float64))
+    lo, hi = np.floor(corners.min(axis=0)), np.ceil(corners.max(axis=0))
+    shape = (max(int(hi[0] - lo[0]), 1), max(int(hi[1] - lo[1]), 1))
+    return (int(lo[0]), int(lo[1])), shape, (x, y, w, h)
 
 
 FE_SOURCE_ALPHA = "SourceAlpha"
@@ -135,8 +182,47 @@ class Filter(NamedTuple):
     def morphology(self, rx, ry, method, input, result=None) -> "Filter":
         return self.add_filter(FE_MORPHOLOGY, (rx, ry, method), [input], result)
 
-    def __call__(self, transform: Transform, source: Layer) -> Layer:
-        """Execute the filter chain on `source` (S:1801-1831)."""
+    def flood(self, color, region=None, result=None) -> "Filter":
+        """feFlood: `color` = straight-alpha linear RGBA (flood-opacity already in the alpha) over the filter region."""
+        return self.add_filter(FE_FLOOD, (tuple(float(c) for c in color), region), [], result)
+
+    def turbulence(self, base_frequency, num_octaves=1, seed=0, stitch=False, fractal_noise=False, region=None,
+                   result=None) -> "Filter":
+        fx, fy = base_frequency
+        return self.add_filter(FE_TURBULENCE, ((fx, fy), num_octaves, seed, stitch, fractal_noise, region), [], result)
+
+    def component_transfer(self, input, funcs, result=None) -> "Filter":
+        """`funcs`: (R, G, B, A) transfer functions in ``Layer.component_transfer``'s form."""
+        return self.add_filter(FE_COMPONENT_TRANSFER, (tuple(funcs),), [input], result)
+
+    def convolve_matrix(self, input, kernel, divisor=None, bias=0.0, target=None, edge_mode="duplicate", preserve_alpha=False,
+                        result=None) -> "Filter":
+        return self.add_filter(FE_CONVOLVE_MATRIX, (kernel, divisor, bias, target, edge_mode, preserve_alpha), [input], result)
+
+    def displacement_map(self, in1, in2, scale=0.0, x_channel="A", y_channel="A", result=None) -> "Filter":
+        return self.add_filter(FE_DISPLACEMENT_MAP, (scale, x_channel, y_channel), [in1, in2], result)
+
+    def drop_shadow(self, dx=2.0, dy=2.0, std_x=2.0, std_y=None, color=(0.0, 0.0, 0.0, 1.0), region=None, input=None,
+                    result=None) -> "Filter":
+        """feDropShadow as the six entries it stands for: the alpha of `input`, blurred, offset, a flood of `color` IN that
+        shadow, and the merge of [shadow, `input`].  Only the merge can be named (`result`)."""
+        names, filters = dict(self.names), list(self.filters)
+        src = names.get(input) if input is not None else None
+        src = len(filters) + 1 if src is None else src   # (the default input: add_filter's rule)
+        at = len(filters) + 2                            # (stack index of the first new entry)
+        filters.append((FE_COLOR_MATRIX, (COLOR_MATRIX_ALPHA,), [src]))
+        filters.append((FE_GAUSSIAN_BLUR, (std_x, std_y), [at]))
+        filters.append((FE_OFFSET, (dx, dy), [at + 1]))
+        filters.append((FE_FLOOD, (tuple(float(c) for c in color), region), []))
+        filters.append((FE_COMPOSITE, (COMPOSE_IN,), [at + 3, at + 2]))
+        filters.append((FE_MERGE, tuple(), [at + 4, src]))
+        if result is not None:
+            names[result] = at + 5
+        return Filter(names, filters)
+
+    def __call__(self, transform: Transform, source: Layer, hull=None) -> Layer:
+        """Execute the filter chain on `source` (S:1801-1831).  `hull`: the filtered node's ConvexHull, the frame of an
+        objectBoundingBox filter region (only the generators use the region)."""
         stack: list = [None, source.convert(pre_alpha=False, linear_rgb=True)]
 
         def get(i):
@@ -175,6 +261,22 @@ class Filter(NamedTuple):
                 ux, uy = transform([[rx, 0], [0, ry]]) - transform([[0, 0], [0, 0]])
                 x, y = int(np.linalg.norm(ux) * 2), int(np.linalg.norm(uy) * 2)
                 res = args[0] if x < 1 or y < 1 else args[0].morphology(x, y, method)
+            elif ftype == FE_FLOOD:
+                color, region = attrs
+                offset, shape, _ = filter_region(region, transform, source, hull)
+                res = Layer.flood(color, offset, shape)
+            elif ftype == FE_TURBULENCE:
+                freq, octaves, seed, stitch, fractal, region = attrs
+                offset, shape, rect = filter_region(region, transform, source, hull)
+                res = Layer.turbulence(transform, offset, shape, freq, octaves, seed, rect if stitch else None, fractal)
+            elif ftype == FE_COMPONENT_TRANSFER:
+                res = args[0].component_transfer(attrs[0])
+            elif ftype == FE_CONVOLVE_MATRIX:
+                kernel, divisor, bias, target, edge_mode, preserve_alpha = attrs
+                res = args[0].convolve_matrix(kernel, divisor, bias, target, edge_mode, preserve_alpha)
+            elif ftype == FE_DISPLACEMENT_MAP:
+                scale, x_channel, y_channel = attrs
+                res = args[0].displacement_map(args[1], transform, scale, x_channel, y_channel)
             else:
                 raise ValueError(f"unsupported filter type: {ftype}")
             stack.append(res)

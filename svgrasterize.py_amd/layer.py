@@ -24,6 +24,22 @@ from . import _abi
 COMPOSE_OVER, COMPOSE_OUT, COMPOSE_IN, COMPOSE_ATOP, COMPOSE_XOR = 0, 1, 2, 3, 4
 COMPOSE_PRE_ALPHA = {COMPOSE_OVER, COMPOSE_OUT, COMPOSE_IN, COMPOSE_ATOP, COMPOSE_XOR}
 FLOAT = np.float64
+# feComponentTransfer / feConvolveMatrix / feDisplacementMap codes of the C ABI (include/svgr.h)
+TRANSFER_TYPES = {"identity": 0, "table": 1, "discrete": 2, "linear": 3, "gamma": 4}
+EDGE_MODES = {"duplicate": 0, "wrap": 1, "none": 2}
+CHANNELS = {"R": 0, "G": 1, "B": 2, "A": 3}
+_TURB_M = 2147483647
+
+
+def turbulence_seed(seed) -> int:
+    """feTurbulence ``seed``, truncated toward zero and brought into int64 without changing the lattice it selects: the set-up
+    clamps seeds above 2^31 - 2 and folds seeds <= 0 by their C remainder modulo 2^31 - 2."""
+    s = int(float(seed))
+    if s > _TURB_M - 1:
+        return _TURB_M - 1
+    if s <= 0:
+        return -((-s) % (_TURB_M - 1))   # (C's `s % (m - 1)` of a negative s)
+    return s
 
 
 def _bbox_arr(offset, shape):
@@ -285,6 +301,121 @@ class Layer:
             _abi._check(ctx.lib.svgr_layer_convolve(ctx.handle, out.handle, src.handle, rows, cols, _abi.ptr(kernel), kw, kh))
         offset = (int(layer.x - kw / 2), int(layer.y - kh / 2))
         return Layer._from_device(out, out_shape, offset, pre_alpha=False, linear_rgb=True)
+
+    # -- filter primitives beyond the reference (filters.py; DESIGN.md "Filter primitives beyond the reference") ------
+    # Pixel [i, j] of a layer at offset (o0, o1) is the device point (o0 + i + 0.5, o1 + j + 0.5); user space is
+    # `transform.invert` of that.  Every result is linear RGB.
+    @classmethod
+    def flood(cls, color, offset, shape) -> "Layer":
+        """feFlood: a (rows, cols) layer at `offset` filled with `color`, straight-alpha linear RGBA."""
+        rows, cols = int(shape[0]), int(shape[1])
+        rgba = np.ascontiguousarray(color, dtype=FLOAT).reshape(4)
+        ctx = _abi.Context.get()
+        buf = ctx.alloc(max(rows * cols, 1) * 32)
+        buf.zero()   # (then the background kernel's `0 + colour * (1 - 0)` is the colour itself)
+        _abi._check(ctx.lib.svgr_layer_background(ctx.handle, buf.handle, rows * cols, _abi.ptr(rgba)))
+        return Layer._from_device(buf, (rows, cols, 4), (int(offset[0]), int(offset[1])), pre_alpha=False, linear_rgb=True)
+
+    @classmethod
+    def turbulence(cls, transform, offset, shape, base_frequency, num_octaves: int = 1, seed=0, stitch_tile=None,
+                   fractal_noise: bool = False) -> "Layer":
+        """feTurbulence over a (rows, cols) layer at `offset`: the Filter Effects noise of the user-space point of every pixel
+        centre.  `base_frequency` = (fx, fy) >= 0; `seed` is truncated toward zero; `stitch_tile` = (x, y, width, height) in
+        user space stitches the noise to that tile, None does not.  Straight-alpha linear RGBA."""
+        rows, cols = int(shape[0]), int(shape[1])
+        fx, fy = (float(f) for f in base_frequency)
+        seed = turbulence_seed(seed)
+        tile = np.ascontiguousarray((0, 0, 0, 0) if stitch_tile is None else stitch_tile, dtype=FLOAT).reshape(4)
+        inv = np.ascontiguousarray(transform.invert.m6(), dtype=FLOAT)
+        ctx = _abi.Context.get()
+        buf = ctx.alloc(max(rows * cols, 1) * 32)
+        offset = (int(offset[0]), int(offset[1]))
+        _abi._check(ctx.lib.svgr_layer_turbulence(ctx.handle, buf.handle, _bbox_arr(offset, (rows, cols)), _abi.ptr(inv), fx, fy,
+                                                  _abi.ptr(tile), seed, int(num_octaves), int(bool(fractal_noise)),
+                                                  int(stitch_tile is not None)))
+        return Layer._from_device(buf, (rows, cols, 4), offset, pre_alpha=False, linear_rgb=True)
+
+    def component_transfer(self, funcs) -> "Layer":
+        """feComponentTransfer on straight-alpha linear RGBA: `funcs` = four transfer functions (R, G, B, A), each None
+        (identity) or one of ("identity",), ("table", values), ("discrete", values), ("linear", slope, intercept),
+        ("gamma", amplitude, exponent, offset).  The extent stays this layer's: pixels outside it stay transparent."""
+        if self.channels != 4:
+            raise ValueError("component_transfer expects an RGBA layer")
+        if len(funcs) != 4:
+            raise ValueError("component_transfer expects four transfer functions (R, G, B, A)")
+        types = np.zeros(4, dtype=np.int32)
+        params = np.tile(np.array([1.0, 0.0, 1.0, 1.0, 0.0]), (4, 1))   # slope, intercept, amplitude, exponent, offset
+        counts = np.zeros(4, dtype=np.int64)
+        tables = []
+        for k, fn in enumerate(funcs):
+            kind = "identity" if fn is None else fn[0]
+            if kind not in TRANSFER_TYPES:
+                raise ValueError(f"unknown transfer function type: {kind}")
+            types[k] = TRANSFER_TYPES[kind]
+            if kind in ("table", "discrete"):
+                values = np.asarray(fn[1], dtype=FLOAT).reshape(-1)
+                if values.size == 0:
+                    types[k] = TRANSFER_TYPES["identity"]
+                counts[k] = values.size
+                tables.append(values)
+            elif kind == "linear":
+                params[k, 0:2] = fn[1:3]
+            elif kind == "gamma":
+                params[k, 2:5] = fn[1:4]
+        values = np.ascontiguousarray(np.concatenate(tables) if tables else np.zeros(1), dtype=FLOAT)
+        params = np.ascontiguousarray(params, dtype=FLOAT)
+        layer = self.convert(pre_alpha=False, linear_rgb=True)
+        ctx = _abi.Context.get()
+        buf = layer._copy_device() if layer is self else layer._device()  # (a converted layer owns a fresh buffer)
+        _abi._check(ctx.lib.svgr_layer_component_transfer(ctx.handle, buf.handle, layer.height * layer.width, _abi.ptr(types),
+                                                          _abi.ptr(params), _abi.ptr(counts), _abi.ptr(values)))
+        return Layer._from_device(buf, layer._shape, layer.offset, pre_alpha=False, linear_rgb=True)
+
+    def convolve_matrix(self, kernel, divisor=None, bias: float = 0.0, target=None, edge_mode: str = "duplicate",
+                        preserve_alpha: bool = False) -> "Layer":
+        """feConvolveMatrix in device pixels: `kernel` = (orderY, orderX) (rows = vertical = this layer's first axis),
+        `target` = (targetX, targetY) (default: order // 2), `divisor` None or 0 = the kernel's sum (1 if that is 0),
+        `edge_mode` duplicate / wrap / none at this layer's edges.  Without `preserve_alpha` all four premultiplied
+        channels are convolved (result premultiplied); with it the straight colour is convolved and alpha kept."""
+        if self.channels != 4:
+            raise ValueError("convolve_matrix expects an RGBA layer")
+        kernel = np.ascontiguousarray(kernel, dtype=FLOAT)
+        if kernel.ndim != 2:
+            raise ValueError("convolve_matrix expects a 2-D kernel (orderY, orderX)")
+        order_y, order_x = kernel.shape
+        tx, ty = (order_x // 2, order_y // 2) if target is None else (int(target[0]), int(target[1]))
+        if divisor is None or divisor == 0:
+            divisor = float(kernel.sum()) or 1.0
+        if edge_mode not in EDGE_MODES:
+            raise ValueError(f"invalid edge mode: {edge_mode}")
+        layer = self.convert(pre_alpha=not preserve_alpha, linear_rgb=True)
+        ctx = _abi.Context.get()
+        rows, cols = layer.height, layer.width
+        out = ctx.alloc(max(rows * cols, 1) * 32)
+        src = layer._device()
+        _abi._check(ctx.lib.svgr_layer_convolve_matrix(ctx.handle, out.handle, src.handle, rows, cols, _abi.ptr(kernel), order_x, order_y,
+                                                       tx, ty, float(divisor), float(bias), EDGE_MODES[edge_mode],
+                                                       int(bool(preserve_alpha))))
+        return Layer._from_device(out, layer._shape, layer.offset, pre_alpha=not preserve_alpha, linear_rgb=True)
+
+    def displacement_map(self, map: "Layer", transform, scale: float, x_channel: str = "A", y_channel: str = "A") -> "Layer":
+        """feDisplacementMap of this layer (`in`) by `map` (`in2`): the result has the map's extent, and pixel [i, j] is the
+        pixel of this layer that contains the map pixel's centre moved by L @ (scale * (map[X] - 0.5), scale * (map[Y] - 0.5)),
+        L the linear part of `transform`; X / Y are the selected channels of the straight-alpha map.  Premultiplied."""
+        if self.channels != 4 or map.channels != 4:
+            raise ValueError("displacement_map expects RGBA layers")
+        if x_channel not in CHANNELS or y_channel not in CHANNELS:
+            raise ValueError(f"invalid channel selector: {x_channel}, {y_channel}")
+        src = self.convert(pre_alpha=True, linear_rgb=True)
+        disp = map.convert(pre_alpha=False, linear_rgb=True)
+        lin = np.ascontiguousarray(np.asarray(transform.m, dtype=FLOAT)[:2, :2]).reshape(4)
+        ctx = _abi.Context.get()
+        out = ctx.alloc(max(disp.height * disp.width, 1) * 32)
+        s_buf, d_buf = src._device(), disp._device()
+        _abi._check(ctx.lib.svgr_layer_displacement_map(ctx.handle, out.handle, _bbox_arr(disp.offset, disp._shape), d_buf.handle,
+                                                        s_buf.handle, _bbox_arr(src.offset, src._shape), _abi.ptr(lin), float(scale),
+                                                        CHANNELS[x_channel], CHANNELS[y_channel]))
+        return Layer._from_device(out, disp._shape, disp.offset, pre_alpha=True, linear_rgb=True)
 
     # -- Layer.compose  S:177-207 ----------------------------------------------------------
     @staticmethod

@@ -447,7 +447,7 @@ class Scene(tuple):
             if res is None:
                 return None
             image, hull = res
-            return flt(transform, image), hull
+            return flt(transform, image, hull), hull
         raise ValueError(f"unhandled scene type: {kind}")
 
     # -- whole-scene batched render: the bench / production entry -----------------------------

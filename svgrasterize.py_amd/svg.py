@@ -8,8 +8,9 @@ exactly like the scene dumps extracted from the reference (``tests/test_svg_load
 
 Supported: svg (nested, viewBox), g, defs, path, rect, circle, ellipse, line, polyline, polygon, use,
 linearGradient / radialGradient / stop, pattern, clipPath, mask, filter (feOffset, feGaussianBlur, feMerge, feBlend, feComposite,
-feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology), text / tspan set in SVG fonts (font, font-face, glyph,
-missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``.
+feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, and beyond the reference feFlood, feTurbulence,
+feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow; the <filter>'s region for the generators), text / tspan set in
+SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``.
 Not supported (a warning, the element is skipped): textPath, image, foreignObject, switch, marker, ...
 """
 from __future__ import annotations
@@ -24,7 +25,10 @@ import xml.etree.ElementTree as etree
 
 import numpy as np
 
-from .filters import COLOR_MATRIX_LUM, Filter, color_matrix_hue_rotate, color_matrix_saturate
+from .filters import (
+    COLOR_MATRIX_LUM, CONVOLVE_MATRIX_MAX_ORDER, TRANSFER_MAX_VALUES, TURBULENCE_MAX_OCTAVES, Filter, color_matrix_hue_rotate,
+    color_matrix_saturate,
+)
 from .fonts import FONT_STYLE_NORMAL, Font, FontsDB, Glyph
 from .geometry import (
     PATH_CLOSED, PATH_FILL_NONZERO, PATH_LINE, STROKE_CAP_BUTT, STROKE_JOIN_MITER, Path, Transform,
@@ -347,14 +351,136 @@ def _gradient(element, linear: bool):
 _COMPOSITE_OPERATORS = {"over": COMPOSE_OVER, "in": COMPOSE_IN, "out": COMPOSE_OUT, "atop": COMPOSE_ATOP, "xor": COMPOSE_XOR}
 
 
+def _filter_region(attrs):
+    """The <filter>'s region (x, y, width, height in filterUnits) in the form of ``filters.FILTER_REGION_DEFAULT``."""
+    units = attrs.get("filterUnits", UNITS_BBOX)
+    if units not in (UNITS_BBOX, UNITS_USER):
+        warnings.warn(f"invalid filter units: {units}")
+        units = UNITS_BBOX
+    return (units == UNITS_BBOX, *(parse_float(attrs.get(k)) for k in ("x", "y", "width", "height")))
+
+
+def _flood_color(attrs):
+    """flood-color x flood-opacity (attributes or style) as straight-alpha linear RGBA; None (+ warning) if invalid."""
+    color = parse_color(attrs.get("flood-color", "black").strip())
+    if color is None:
+        return None
+    opacity = min(max(parse_float(attrs.get("flood-opacity", "1")), 0.0), 1.0)
+    alpha = color[3]
+    rgb = color[:3] / alpha if alpha > 0 else np.zeros(3)   # (parse_color's colour is premultiplied)
+    return (*rgb, alpha * opacity)
+
+
+_TRANSFER_FUNCS = {"feFuncR": 0, "feFuncG": 1, "feFuncB": 2, "feFuncA": 3}
+
+
+def _transfer_funcs(element):
+    """feFuncR/G/B/A children -> the four transfer functions of ``Layer.component_transfer`` (None = identity)."""
+    funcs = [None] * 4
+    for child in element:
+        k = _TRANSFER_FUNCS.get(child.tag.split("}")[-1])
+        if k is None:
+            continue
+        attrs = child.attrib
+        kind = attrs.get("type", "identity")
+        if kind in ("table", "discrete"):
+            values = parse_floats(attrs.get("tableValues", "")) or []
+            funcs[k] = (kind, tuple(values)) if values else None
+        elif kind == "linear":
+            funcs[k] = ("linear", parse_float(attrs.get("slope", "1")), parse_float(attrs.get("intercept", "0")))
+        elif kind == "gamma":
+            funcs[k] = ("gamma", parse_float(attrs.get("amplitude", "1")), parse_float(attrs.get("exponent", "1")),
+                        parse_float(attrs.get("offset", "0")))
+        elif kind != "identity":
+            warnings.warn(f"invalid transfer function type: {kind}")
+    return funcs
+
+
+def _convolve_matrix_args(attrs):
+    """feConvolveMatrix attributes -> (kernel (orderY, orderX), divisor, bias, (targetX, targetY), edge mode, preserve alpha);
+    None (+ warning) when they do not describe a kernel."""
+    order = parse_floats(attrs.get("order", "3"), 1, 2)
+    ox, oy = (order[0], order[0]) if len(order) == 1 else order
+    if ox != int(ox) or oy != int(oy) or ox < 1 or oy < 1:
+        warnings.warn(f"invalid convolve matrix order: {attrs.get('order')}")
+        return None
+    ox, oy = int(ox), int(oy)
+    if ox > CONVOLVE_MATRIX_MAX_ORDER or oy > CONVOLVE_MATRIX_MAX_ORDER:
+        warnings.warn(f"convolve matrix order above {CONVOLVE_MATRIX_MAX_ORDER}: {attrs.get('order')}")
+        return None
+    values = parse_floats(attrs.get("kernelMatrix"))
+    if values is None or len(values) != ox * oy:
+        warnings.warn(f"kernelMatrix needs orderX * orderY = {ox * oy} values: {attrs.get('kernelMatrix')}")
+        return None
+    kernel = np.array(values, dtype=np.float64).reshape(oy, ox)
+    divisor = parse_float(attrs.get("divisor"))
+    if divisor == 0:
+        warnings.warn("convolve matrix divisor 0: the default divisor is used")
+        divisor = None
+    tx, ty = (int(parse_float(attrs.get(k, str(o // 2)))) for k, o in (("targetX", ox), ("targetY", oy)))
+    if not (0 <= tx < ox and 0 <= ty < oy):
+        warnings.warn(f"convolve matrix target outside the kernel: {tx}, {ty}")
+        return None
+    edge_mode = attrs.get("edgeMode", "duplicate")
+    if edge_mode not in ("duplicate", "wrap", "none"):
+        warnings.warn(f"invalid edge mode: {edge_mode}")
+        return None
+    if attrs.get("kernelUnitLength") is not None:
+        warnings.warn("kernelUnitLength is not supported: one kernel cell is one device pixel")
+    return kernel, divisor, parse_float(attrs.get("bias", "0")), (tx, ty), edge_mode, attrs.get("preserveAlpha") == "true"
+
+
 def _filter(element) -> Filter:
-    """<filter> -> Filter chain (S:3271-3362)."""
+    """<filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap
+    and feDropShadow beyond the reference)."""
     flt = Filter.empty()
+    region = _filter_region(element.attrib)
     for child in element:
         tag = child.tag.split("}")[-1]
         attrs = child.attrib
         result, src = attrs.get("result"), attrs.get("in")
-        if tag == "feOffset":
+        if tag == "feFlood":
+            color = _flood_color(_expand_style(attrs))
+            if color is not None:
+                flt = flt.flood(color, region, result)
+        elif tag == "feTurbulence":
+            freq = parse_floats(attrs.get("baseFrequency", "0"), 1, 2)
+            fx, fy = (freq[0], freq[0]) if len(freq) == 1 else freq
+            kind = attrs.get("type", "turbulence")
+            octaves = int(parse_float(attrs.get("numOctaves", "1")))
+            if fx < 0 or fy < 0:
+                warnings.warn(f"negative baseFrequency: {attrs.get('baseFrequency')}")
+            elif kind not in ("turbulence", "fractalNoise"):
+                warnings.warn(f"invalid turbulence type: {kind}")
+            else:
+                flt = flt.turbulence((fx, fy), min(max(octaves, 0), TURBULENCE_MAX_OCTAVES), parse_float(attrs.get("seed", "0")),
+                                     attrs.get("stitchTiles") == "stitch", kind == "fractalNoise", region, result)
+        elif tag == "feComponentTransfer":
+            funcs = _transfer_funcs(child)
+            n_values = sum(len(f[1]) for f in funcs if f is not None and f[0] in ("table", "discrete"))
+            if n_values > TRANSFER_MAX_VALUES:
+                warnings.warn(f"feComponentTransfer: {n_values} table values (at most {TRANSFER_MAX_VALUES})")
+            else:
+                flt = flt.component_transfer(src, funcs, result)
+        elif tag == "feConvolveMatrix":
+            args = _convolve_matrix_args(attrs)
+            if args is not None:
+                flt = flt.convolve_matrix(src, *args, result=result)
+        elif tag == "feDisplacementMap":
+            xc, yc = attrs.get("xChannelSelector", "A"), attrs.get("yChannelSelector", "A")
+            if xc not in ("R", "G", "B", "A") or yc not in ("R", "G", "B", "A"):
+                warnings.warn(f"invalid channel selector: {xc}, {yc}")
+            else:
+                flt = flt.displacement_map(src, attrs.get("in2"), parse_float(attrs.get("scale", "0")), xc, yc, result)
+        elif tag == "feDropShadow":
+            style = _expand_style(attrs)
+            color = _flood_color(style)
+            stds = parse_floats(attrs.get("stdDeviation", "2"), 1, 2)
+            std_x, std_y = stds * 2 if len(stds) == 1 else stds
+            if color is not None:
+                flt = flt.drop_shadow(parse_float(attrs.get("dx", "2")), parse_float(attrs.get("dy", "2")), std_x, std_y, color,
+                                      region, src, result)
+        elif tag == "feOffset":
             flt = flt.offset(parse_float(attrs.get("dx", "0")), parse_float(attrs.get("dy", "0")), src, result)
         elif tag == "feGaussianBlur":
             stds = parse_floats(attrs.get("stdDeviation"), 1, 2)

@@ -1,0 +1,260 @@
+"""numpy restatement of the filter primitives beyond the reference (feTurbulence, feComponentTransfer, feConvolveMatrix,
+feDisplacementMap), written from the Filter Effects text in the operation order the kernels use, plus the loader for the host
+build of their arithmetic (tests/filter_harness.cpp over csrc/svgr_core.h).  Test infrastructure only."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+
+from tests.util import ROOT
+
+BSIZE, BM, PERLIN_N = 0x100, 0xFF, 0x1000
+RAND_M, RAND_A, RAND_Q, RAND_R = 2147483647, 16807, 127773, 2836
+
+
+def _c_rem(a: int, b: int) -> int:
+    """C's a % b (the sign of the dividend)."""
+    r = abs(a) % abs(b)
+    return -r if a < 0 else r
+
+
+def setup_seed(s: int) -> int:
+    if s <= 0:
+        s = -_c_rem(s, RAND_M - 1) + 1
+    if s > RAND_M - 1:
+        s = RAND_M - 1
+    return s
+
+
+def random(s: int) -> int:
+    r = RAND_A * (s % RAND_Q) - RAND_R * (s // RAND_Q)   # (s > 0 here: Python's // and % are C's)
+    return r + RAND_M if r <= 0 else r
+
+
+def lattice(seed):
+    """(sel (514,), grad (4, 514, 2)) of the spec's init() for a seed (truncated toward zero first)."""
+    s = setup_seed(int(float(seed)) if not isinstance(seed, int) else seed)
+    sel = np.zeros(2 * BSIZE + 2, dtype=np.int64)
+    grad = np.zeros((4, 2 * BSIZE + 2, 2), dtype=np.float64)
+    for k in range(4):
+        for i in range(BSIZE):
+            sel[i] = i
+            for j in range(2):
+                s = random(s)
+                grad[k, i, j] = float(s % (2 * BSIZE) - BSIZE) / BSIZE
+            x, y = float(grad[k, i, 0]), float(grad[k, i, 1])
+            length = math.sqrt(x * x + y * y)
+            if length > 0.0:
+                grad[k, i] = (x / length, y / length)
+    for i in range(BSIZE - 1, 0, -1):
+        t = sel[i]
+        s = random(s)
+        j = s % BSIZE
+        sel[i] = sel[j]
+        sel[j] = t
+    for i in range(BSIZE + 2):   # (one by one, as in the spec: entries 512 and 513 read the copies of 0 and 1 made just before)
+        sel[BSIZE + i] = sel[i]
+        grad[:, BSIZE + i] = grad[:, i]
+    return sel, grad
+
+
+def turbulence_params(fx, fy, tile, stitch):
+    """(fx, fy, width, height, wrap_x, wrap_y) of the first octave: the base frequencies adjusted to the tile and the stitch
+    state when stitching."""
+    fx, fy = float(fx), float(fy)
+    if not stitch:
+        return fx, fy, 0, 0, 0, 0
+
+    def adjust(f, w):
+        lo, hi = math.floor(w * f) / w, math.ceil(w * f) / w
+        return lo if f / lo < hi / f else hi
+
+    tx, ty, tw, th = (float(v) for v in tile)
+    if fx != 0.0:
+        fx = adjust(fx, tw)
+    if fy != 0.0:
+        fy = adjust(fy, th)
+    width = int(tw * fx + 0.5)
+    height = int(th * fy + 0.5)
+    return fx, fy, width, height, int(tx * fx + PERLIN_N + width), int(ty * fy + PERLIN_N + height)
+
+
+def turbulence(seed, base_frequency, octaves, fractal, stitch_tile, px, py):
+    """(n, 4) RGBA in [0, 1] at the user-space points (px[i], py[i]); stitch_tile None = noStitch."""
+    sel, grad = lattice(seed)
+    fx, fy, width, height, wrap_x, wrap_y = turbulence_params(*base_frequency, stitch_tile, stitch_tile is not None)
+    px, py = np.asarray(px, dtype=np.float64), np.asarray(py, dtype=np.float64)
+    vx, vy, ratio = px * fx, py * fy, 1.0
+    total = np.zeros((4,) + px.shape)
+    for _ in range(octaves):
+        tx, ty = vx + PERLIN_N, vy + PERLIN_N
+        bx0, by0 = np.trunc(tx).astype(np.int64), np.trunc(ty).astype(np.int64)
+        bx1, by1 = bx0 + 1, by0 + 1
+        rx0, ry0 = tx - np.trunc(tx), ty - np.trunc(ty)
+        rx1, ry1 = rx0 - 1.0, ry0 - 1.0
+        if stitch_tile is not None:
+            bx0 = np.where(bx0 >= wrap_x, bx0 - width, bx0)
+            bx1 = np.where(bx1 >= wrap_x, bx1 - width, bx1)
+            by0 = np.where(by0 >= wrap_y, by0 - height, by0)
+            by1 = np.where(by1 >= wrap_y, by1 - height, by1)
+        bx0, bx1, by0, by1 = bx0 & BM, bx1 & BM, by0 & BM, by1 & BM
+        i, j = sel[bx0], sel[bx1]
+        b00, b10, b01, b11 = sel[i + by0], sel[j + by0], sel[i + by1], sel[j + by1]
+        sx = rx0 * rx0 * (3.0 - 2.0 * rx0)
+        sy = ry0 * ry0 * (3.0 - 2.0 * ry0)
+        for k in range(4):
+            g = grad[k]
+            u = rx0 * g[b00, 0] + ry0 * g[b00, 1]
+            v = rx1 * g[b10, 0] + ry0 * g[b10, 1]
+            a = u + sx * (v - u)
+            u = rx0 * g[b01, 0] + ry1 * g[b01, 1]
+            v = rx1 * g[b11, 0] + ry1 * g[b11, 1]
+            b = u + sx * (v - u)
+            n = a + sy * (b - a)
+            total[k] = total[k] + (n if fractal else np.abs(n)) / ratio
+        vx, vy, ratio = vx * 2.0, vy * 2.0, ratio * 2.0
+        if stitch_tile is not None:
+            width, height = width + width, height + height
+            wrap_x, wrap_y = 2 * wrap_x - PERLIN_N, 2 * wrap_y - PERLIN_N
+    out = (total + 1.0) * 0.5 if fractal else total
+    return np.clip(out, 0.0, 1.0).T.copy()
+
+
+def pixel_user_points(inv_m6, offset, shape):
+    """User-space points of the pixel centres of a (rows, cols) layer at `offset`: (o + i) + 0.5, then the inverse
+    transform as plain products and sums, left to right (the kernel's form)."""
+    rows, cols = shape
+    d0 = (offset[0] + np.arange(rows, dtype=np.int64)[:, None] + np.zeros((1, cols), dtype=np.int64)).astype(np.float64) + 0.5
+    d1 = (offset[1] + np.zeros((rows, 1), dtype=np.int64) + np.arange(cols, dtype=np.int64)[None, :]).astype(np.float64) + 0.5
+    m = inv_m6
+    return m[0] * d0 + m[1] * d1 + m[2], m[3] * d0 + m[4] * d1 + m[5]
+
+
+def turbulence_layer(transform, offset, shape, base_frequency, octaves, seed, stitch_tile, fractal):
+    px, py = pixel_user_points(transform.invert.m6(), offset, shape)
+    return turbulence(seed, base_frequency, octaves, fractal, stitch_tile, px.ravel(), py.ravel()).reshape(*shape, 4)
+
+
+def transfer(c, fn):
+    """One feComponentTransfer function on a channel array (fn in Layer.component_transfer's form)."""
+    c = np.clip(c, 0.0, 1.0)
+    kind = "identity" if fn is None else fn[0]
+    r = c
+    if kind == "table" and len(fn[1]):
+        v = np.asarray(fn[1], dtype=np.float64)
+        if len(v) == 1:
+            r = np.full_like(c, v[0])
+        else:
+            m = len(v) - 1
+            t = c * m
+            k = np.minimum(np.floor(t), m - 1).astype(np.int64)
+            r = v[k] + (t - k) * (v[k + 1] - v[k])
+    elif kind == "discrete" and len(fn[1]):
+        v = np.asarray(fn[1], dtype=np.float64)
+        k = np.minimum(np.floor(c * len(v)), len(v) - 1).astype(np.int64)
+        r = v[k]
+    elif kind == "linear":
+        r = fn[1] * c + fn[2]
+    elif kind == "gamma":
+        r = fn[1] * np.power(c, fn[2]) + fn[3]
+    return np.clip(r, 0.0, 1.0)
+
+
+def component_transfer(image, funcs):
+    return np.stack([transfer(image[..., k], funcs[k]) for k in range(4)], axis=-1)
+
+
+def convolve_matrix(image, kernel, divisor, bias, target, edge_mode, preserve_alpha):
+    """feConvolveMatrix of a (rows, cols, 4) image (premultiplied, or straight with preserve_alpha)."""
+    rows, cols = image.shape[:2]
+    oy, ox = kernel.shape
+    tx, ty = target
+    r = np.arange(rows)[:, None]
+    c = np.arange(cols)[None, :]
+    acc = np.zeros((rows, cols, 4))
+    for I in range(oy):
+        for J in range(ox):
+            rr, cc = r - ty + I, c - tx + J
+            if edge_mode == "duplicate":
+                v = image[np.clip(rr, 0, rows - 1), np.clip(cc, 0, cols - 1)]
+            elif edge_mode == "wrap":
+                v = image[rr % rows, cc % cols]
+            else:
+                inside = (rr >= 0) & (rr < rows) & (cc >= 0) & (cc < cols)
+                v = np.where(inside[..., None], image[np.clip(rr, 0, rows - 1), np.clip(cc, 0, cols - 1)], 0.0)
+            acc = acc + v * kernel[oy - 1 - I, ox - 1 - J]
+    res = acc / divisor + bias
+    if preserve_alpha:
+        res[..., :3] = np.clip(res[..., :3], 0.0, 1.0)
+        res[..., 3] = image[..., 3]
+    else:
+        res[..., 3] = np.clip(res[..., 3], 0.0, 1.0)
+        res[..., :3] = np.minimum(np.maximum(res[..., :3], 0.0), res[..., 3:])
+    return res
+
+
+def displacement_map(src, src_offset, disp, disp_offset, lin, scale, xc, yc):
+    """feDisplacementMap: src premultiplied (rows_s, cols_s, 4) at src_offset, disp straight (rows, cols, 4) at disp_offset,
+    lin = the 2 x 2 linear part of the transform; channels 0..3."""
+    rows, cols = disp.shape[:2]
+    du0 = scale * (disp[..., xc] - 0.5)
+    du1 = scale * (disp[..., yc] - 0.5)
+    dd0 = lin[0, 0] * du0 + lin[0, 1] * du1
+    dd1 = lin[1, 0] * du0 + lin[1, 1] * du1
+    p0 = (disp_offset[0] + np.arange(rows)[:, None]).astype(np.float64) + 0.5 + dd0
+    p1 = (disp_offset[1] + np.arange(cols)[None, :]).astype(np.float64) + 0.5 + dd1
+    r = np.floor(p0) - src_offset[0]
+    c = np.floor(p1) - src_offset[1]
+    inside = (r >= 0) & (r < src.shape[0]) & (c >= 0) & (c < src.shape[1])
+    ri = np.where(inside, r, 0).astype(np.int64)
+    ci = np.where(inside, c, 0).astype(np.int64)
+    return np.where(inside[..., None], src[ri, ci], 0.0)
+
+
+# -- the host build of svgr_core.h's filter arithmetic ---------------------------------------------------------------------
+HARNESS = os.path.join(ROOT, "tests", "_filter_harness.so")
+
+
+def harness():
+    src = os.path.join(ROOT, "tests", "filter_harness.cpp")
+    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
+    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        tmp = f"{HARNESS}.{os.getpid()}"
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, HARNESS)
+    L = C.CDLL(HARNESS)
+    f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
+    i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+    L.fh_lattice.argtypes = [C.c_int64, i32p, f64p]
+    L.fh_turbulence.argtypes = [C.c_int64, C.c_double, C.c_double, f64p, C.c_int, C.c_int, C.c_int, f64p, C.c_long, f64p]
+    L.fh_turbulence_layer.argtypes = [C.c_int64, C.c_double, C.c_double, f64p, C.c_int, C.c_int, C.c_int, f64p, C.c_long, C.c_long,
+                                      C.c_long, C.c_long, f64p]
+    return L
+
+
+def harness_lattice(L, seed):
+    """(sel (514,), grad (4, 514, 2)) from the host build (its lattice-major layout turned into the spec's)."""
+    sel = np.zeros(2 * BSIZE + 2, dtype=np.int32)
+    grad = np.zeros((2 * BSIZE + 2) * 8)
+    L.fh_lattice(seed, sel, grad)
+    return sel.astype(np.int64), grad.reshape(2 * BSIZE + 2, 4, 2).transpose(1, 0, 2)
+
+
+def harness_turbulence(L, seed, base_frequency, octaves, fractal, stitch_tile, px, py):
+    pts = np.ascontiguousarray(np.stack([np.asarray(px, np.float64).ravel(), np.asarray(py, np.float64).ravel()], axis=1)).reshape(-1)
+    out = np.zeros((len(pts) // 2, 4))
+    tile = np.ascontiguousarray((0, 0, 0, 0) if stitch_tile is None else stitch_tile, dtype=np.float64)
+    L.fh_turbulence(seed, base_frequency[0], base_frequency[1], tile, octaves, int(fractal), int(stitch_tile is not None), pts,
+                    len(pts) // 2, out.reshape(-1))
+    return out
+
+
+def harness_turbulence_layer(L, transform, offset, shape, base_frequency, octaves, seed, stitch_tile, fractal):
+    out = np.zeros((shape[0], shape[1], 4))
+    tile = np.ascontiguousarray((0, 0, 0, 0) if stitch_tile is None else stitch_tile, dtype=np.float64)
+    inv = np.ascontiguousarray(transform.invert.m6(), dtype=np.float64)
+    L.fh_turbulence_layer(seed, base_frequency[0], base_frequency[1], tile, octaves, int(fractal), int(stitch_tile is not None), inv,
+                          offset[0], offset[1], shape[0], shape[1], out.reshape(-1))
+    return out
