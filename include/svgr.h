@@ -38,7 +38,8 @@ extern "C" {
  * 5: svgr_layer_compose_over / _in, svgr_layer_convert_scale_to, svgr_layer_convolve_ops, svgr_batch_get_extents added (nothing changed
  *    or removed)
  * 6 (later, nothing changed or removed): svgr_layer_turbulence, svgr_layer_component_transfer, svgr_layer_convolve_matrix,
- *    svgr_layer_displacement_map added (filter primitives beyond the reference) */
+ *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
+ *    svgr_png_unfilter added (SVG <image>, beyond the reference) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -398,6 +399,28 @@ typedef struct svgr_pattern {
 int svgr_pattern_fill(svgr_ctx* ctx, const svgr_pattern* pattern, const svgr_buf* tile, const svgr_buf* mask,
                       const int64_t* bbox, svgr_buf* out_rgba);
 
+/* SVG <image> (beyond the reference): a raster image as a paint.
+ * svgr_image_upload: `rgba` is the caller's (h, w, 4) uint8 image, straight alpha, sRGB as stored.  `levels` receives
+ * every mip level as float32x4 premultiplied texels, level 0 first, each level right behind the previous one.  Level 0
+ * is byte / 255, sRGB -> linear if linear_rgb (the formula of svgr_layer_convert), times alpha.  Level k + 1 is
+ * (ceil(h_k / 2), ceil(w_k / 2)): each texel the mean (summed in double) of its 2 x 2 parents, the last row / column
+ * reused on odd sizes; the chain ends at 1 x 1.  The sizes are a function of (h, w) alone: the caller allocates for the
+ * sum of the levels' texels (16 bytes each). */
+int svgr_image_upload(svgr_ctx* ctx, const uint8_t* rgba, int64_t h, int64_t w, int linear_rgb, svgr_buf* levels);
+/* svgr_image_fill: out_rgba = image sampled per pixel * mask, over the pixel grid of bbox (as svgr_pattern_fill).  The
+ * pixel centre (row + 0.5, col + 0.5) goes through inv_m6 to image space (u along the image's columns, v along its rows;
+ * texel (r, c) covers [c, c + 1) x [r, r + 1)).  smooth: trilinear between levels floor(lod) and floor(lod) + 1 (bilinear,
+ * texel centres at + 0.5, clamp to edge; level k at (u, v) * 2^-k; level 0 alone if lod == 0); else the level-0 texel
+ * (floor v, floor u), clamped.  The result is double, premultiplied.                                                  */
+typedef struct svgr_image {
+    double inv_m6[6];      /* presentation pixels -> image space: rows 0-1 of (transform @ paint transform).invert      */
+    int64_t height, width; /* level 0 of `levels`                                                                        */
+    double lod;            /* 0 <= lod <= n_levels - 1: log2 of the larger image-space step of one pixel                */
+    int smooth;            /* 1 trilinear, 0 nearest                                                                    */
+} svgr_image;
+int svgr_image_fill(svgr_ctx* ctx, const svgr_image* image, const svgr_buf* levels, const svgr_buf* mask, const int64_t* bbox,
+                    svgr_buf* out_rgba);
+
 /* Layer.convolve (S:106-118): full 2-D convolution of a (rows, cols, 4) double image with a host (kw, kh)
  * kernel (blur_kernel, S:1903-1944, is built on the host); out is (rows + kw - 1, cols + kh - 1, 4).     */
 int svgr_layer_convolve(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, const double* kernel,
@@ -434,6 +457,13 @@ int svgr_path_stroke(const int32_t* seg_types, const double* seg_params, const i
 int svgr_stroke_out_counts(const svgr_stroke_out* s, int64_t* n_segs, int64_t* n_subpaths);
 int svgr_stroke_out_copy(const svgr_stroke_out* s, int32_t* seg_types, double* seg_params, int32_t* subpath_sizes);
 void svgr_stroke_out_free(svgr_stroke_out* s);
+
+/* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
+ * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
+ * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never
+ * read past src_bytes. */
+int svgr_png_unfilter(const uint8_t* src, int64_t src_bytes, int64_t rows, int64_t row_bytes, int64_t bytes_per_pixel,
+                      uint8_t* dst);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ from .layer import (  # noqa: F401
     Layer, canvas_to_png, canvas_create, canvas_compose, canvas_merge_at, canvas_merge_union, canvas_merge_intersect,
     CANVAS_COMPOSE_OVER, COMPOSE_OVER, COMPOSE_OUT, COMPOSE_IN, COMPOSE_ATOP, COMPOSE_XOR,
 )
-from .paint import GradLinear, GradRadial, Pattern  # noqa: F401
+from .paint import GradLinear, GradRadial, ImagePaint, Pattern  # noqa: F401
+from .png import read_png  # noqa: F401
 from .filters import (  # noqa: F401
     Filter, blur_kernel, COLOR_MATRIX_LUM, FE_SOURCE_ALPHA, FE_SOURCE_GRAPHIC, FE_BLEND, FE_COLOR_MATRIX, FE_COMPOSITE,
     FE_GAUSSIAN_BLUR, FE_MERGE, FE_MORPHOLOGY, FE_OFFSET,
@@ -28,4 +29,4 @@ from .fonts import Font, FontsDB, Glyph  # noqa: F401
 from .svg import render_svg, svg_scene, svg_scene_from_filepath, svg_scene_from_str  # noqa: F401
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
-           "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache"]
+           "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png"]

@@ -63,6 +63,12 @@ class PatternArgs(C.Structure):  # svgr_pattern
     ]
 
 
+class ImageArgs(C.Structure):  # svgr_image
+    _fields_ = [
+        ("inv_m6", C.c_double * 6), ("height", C.c_int64), ("width", C.c_int64), ("lod", C.c_double), ("smooth", C.c_int),
+    ]
+
+
 _P = C.c_void_p
 _PROTOS = {
     "svgr_abi_version": (C.c_int, []),
@@ -134,12 +140,15 @@ _PROTOS = {
     "svgr_gradient_fill": (C.c_int, [_P, C.POINTER(Gradient), _P, _P, _P]),
     "svgr_gradient_eval": (C.c_int, [_P, C.POINTER(Gradient), _P, C.c_int64, _P]),
     "svgr_pattern_fill": (C.c_int, [_P, C.POINTER(PatternArgs), _P, _P, _P, _P]),
+    "svgr_image_upload": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
+    "svgr_image_fill": (C.c_int, [_P, C.POINTER(ImageArgs), _P, _P, _P, _P]),
     "svgr_layer_convolve": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64]),
     "svgr_layer_convolve_ops": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_uint]),
     "svgr_path_stroke": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_int, C.POINTER(_P)]),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
+    "svgr_png_unfilter": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -526,3 +535,39 @@ def path_stroke(seg_types, seg_params, subpath_sizes, width: float, linecap: int
     finally:
         lib.svgr_stroke_out_free(out)
     return types, params, sizes
+
+
+def image_levels(h: int, w: int):
+    """[(offset, rows, cols)] in texels of every mip level of an (h, w) image, level 0 first, down to 1 x 1 (the layout
+    svgr_image_upload writes): a function of the size alone."""
+    out, off = [], 0
+    while True:
+        out.append((off, h, w))
+        off += h * w
+        if h == 1 and w == 1:
+            return out
+        h, w = (h + 1) // 2, (w + 1) // 2
+
+
+def image_upload(ctx: Context, pixels: np.ndarray, linear_rgb: bool) -> DeviceBuffer:
+    """svgr_image_upload: an (h, w, 4) uint8 straight-alpha sRGB image -> a device buffer holding its premultiplied float32x4
+    mip chain (levels as `image_levels` lays them out)."""
+    px = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if px.ndim != 3 or px.shape[2] != 4:
+        raise ValueError("an image is an (h, w, 4) uint8 array")
+    h, w = px.shape[:2]
+    off, lh, lw = image_levels(h, w)[-1]
+    buf = ctx.alloc((off + lh * lw) * 16)
+    _check(ctx.lib.svgr_image_upload(ctx.handle, ptr(px), h, w, int(bool(linear_rgb)), buf.handle))
+    return buf
+
+
+def png_unfilter(data, rows: int, row_bytes: int, bytes_per_pixel: int) -> np.ndarray:
+    """svgr_png_unfilter (host only): `rows` filtered PNG scanlines of 1 + row_bytes bytes -> (rows, row_bytes) uint8.
+    ValueError on a filter type above 4 or a short input."""
+    src = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    dst = np.empty((rows, row_bytes), dtype=np.uint8)
+    rc = load_library().svgr_png_unfilter(src.ctypes.data_as(_P), src.size, rows, row_bytes, bytes_per_pixel, dst.ctypes.data_as(_P))
+    if rc != 0:
+        raise ValueError("PNG scanlines: unknown filter type or truncated data")
+    return dst

@@ -3916,6 +3916,99 @@ __global__ void k_pattern_fill(const svgr_pattern pt, const double* __restrict__
 }
 
 // --------------------------------------------------------------------------------------
+// SVG <image> (beyond the reference): the mip chain of an uploaded raster and its per-pixel sampling
+// --------------------------------------------------------------------------------------
+// level 0: byte / 255, sRGB -> linear (convert_px's formula) if asked, premultiplied, rounded to float32.  The colour of a
+// byte takes one of 256 values: each workgroup puts them in LDS once (a pow per entry instead of three per texel) and strides
+// over the texels.  256-lane blocks only.
+__global__ void __launch_bounds__(256) k_image_prepare(const uchar4* __restrict__ src, size_t n, int linear_rgb,
+                                                       float4* __restrict__ dst) {
+    __shared__ double lut[256];
+    {
+        const double t = threadIdx.x / 255.0;
+        double v[4] = {t, t, t, 1.0};
+        convert_px(v, linear_rgb ? 2u : 0u);
+        lut[threadIdx.x] = v[0];
+    }
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uchar4 b = src[i];
+        const double a = b.w / 255.0;
+        dst[i] = make_float4((float)(lut[b.x] * a), (float)(lut[b.y] * a), (float)(lut[b.z] * a), (float)a);
+    }
+}
+
+// level k + 1 from level k: the mean of the 2 x 2 parents (the last row / column reused on odd sizes), summed in double
+__global__ void k_image_downsample(const float4* __restrict__ src, int h, int w, float4* __restrict__ dst, int dh, int dw) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)dh * dw) return;
+    const int r = (int)(i / dw), c = (int)(i % dw);
+    const int r0 = 2 * r, c0 = 2 * c, r1 = min(r0 + 1, h - 1), c1 = min(c0 + 1, w - 1);
+    const float4 a = src[(size_t)r0 * w + c0], b = src[(size_t)r0 * w + c1];
+    const float4 d = src[(size_t)r1 * w + c0], e = src[(size_t)r1 * w + c1];
+    dst[i] = make_float4((float)((((double)a.x + b.x) + ((double)d.x + e.x)) * 0.25),
+                         (float)((((double)a.y + b.y) + ((double)d.y + e.y)) * 0.25),
+                         (float)((((double)a.z + b.z) + ((double)d.z + e.z)) * 0.25),
+                         (float)((((double)a.w + b.w) + ((double)d.w + e.w)) * 0.25));
+}
+
+struct ImageLevel {
+    const float4* tex;
+    int h, w;
+    double scale;  // 2^-k
+};
+
+// bilinear at image-space (u, v) of one level: texel centres at + 0.5, clamp to edge.  The corner is clamped in double
+// before it becomes an index, so a NaN or huge coordinate lands on the edge, never outside the level.  Interpolation in the
+// form a + f (b - a): a uniform image gives back its texel exactly.
+__device__ __forceinline__ double lerp_d(double a, double b, double f) { return a + f * (b - a); }
+__device__ __forceinline__ double4 image_bilinear(const ImageLevel& L, double u, double v) {
+    const double x = u * L.scale - 0.5, y = v * L.scale - 0.5;
+    const double xf = fmin(fmax(floor(x), -1.0), (double)L.w), yf = fmin(fmax(floor(y), -1.0), (double)L.h);
+    const double fx = fmin(fmax(x - xf, 0.0), 1.0), fy = fmin(fmax(y - yf, 0.0), 1.0);
+    const int xi = (int)xf, yi = (int)yf;
+    const int c0 = min(max(xi, 0), L.w - 1), c1 = min(xi + 1, L.w - 1), r0 = min(max(yi, 0), L.h - 1), r1 = min(yi + 1, L.h - 1);
+    const float4 t00 = L.tex[(size_t)r0 * L.w + c0], t01 = L.tex[(size_t)r0 * L.w + c1];
+    const float4 t10 = L.tex[(size_t)r1 * L.w + c0], t11 = L.tex[(size_t)r1 * L.w + c1];
+    return make_double4(lerp_d(lerp_d(t00.x, t01.x, fx), lerp_d(t10.x, t11.x, fx), fy),
+                        lerp_d(lerp_d(t00.y, t01.y, fx), lerp_d(t10.y, t11.y, fx), fy),
+                        lerp_d(lerp_d(t00.z, t01.z, fx), lerp_d(t10.z, t11.z, fx), fy),
+                        lerp_d(lerp_d(t00.w, t01.w, fx), lerp_d(t10.w, t11.w, fx), fy));
+}
+
+// One lane per output pixel; a 256-lane block covers a 32-column x 8-row tile (a wave: 32 x 2), so that under rotation or
+// minification a wave's gathers stay on neighbouring texels.  Row tiles past the grid's height are strided over.  `blend`
+// (frac(lod)) > 0: trilinear between `lo` and `hi`; else `lo` alone.  Nearest: the level-0 texel (floor v, floor u).
+constexpr int IMG_TW = 32, IMG_TH = 8;
+template <bool SMOOTH>
+__global__ void __launch_bounds__(256) k_image_fill(const svgr_image im, ImageLevel lo, ImageLevel hi, double blend,
+                                                    const double* __restrict__ mask, int r0, int c0, int rows, int cols,
+                                                    double* __restrict__ out) {
+    const int j = blockIdx.x * IMG_TW + (threadIdx.x % IMG_TW);
+    for (int ti = blockIdx.y; ti * IMG_TH < rows; ti += gridDim.y) {
+        const int i = ti * IMG_TH + (int)(threadIdx.x / IMG_TW);
+        if (i >= rows || j >= cols) continue;
+        const size_t idx = (size_t)i * cols + j;
+        double u, v;
+        xform_point(im.inv_m6, (double)i + ((double)r0 + 0.5), (double)j + ((double)c0 + 0.5), u, v);
+        double4 s;
+        if (SMOOTH) {
+            s = image_bilinear(lo, u, v);
+            if (blend > 0.0) {
+                const double4 t = image_bilinear(hi, u, v);
+                s = make_double4(lerp_d(s.x, t.x, blend), lerp_d(s.y, t.y, blend), lerp_d(s.z, t.z, blend), lerp_d(s.w, t.w, blend));
+            }
+        } else {
+            const double xf = fmin(fmax(floor(u), 0.0), (double)(lo.w - 1)), yf = fmin(fmax(floor(v), 0.0), (double)(lo.h - 1));
+            const float4 t = lo.tex[(size_t)(int)yf * lo.w + (int)xf];
+            s = make_double4(t.x, t.y, t.z, t.w);
+        }
+        const double m = mask[idx];  // image * coverage, as every paint of Path.fill
+        *reinterpret_cast<double4*>(out + 4 * idx) = make_double4(s.x * m, s.y * m, s.z * m, s.w * m);
+    }
+}
+
+// --------------------------------------------------------------------------------------
 // full 2-D convolution of a (rows, cols, 4) image with a (kw, kh) kernel (Layer.convolve, S:106-118)
 // --------------------------------------------------------------------------------------
 template <typename KernPtr>
@@ -6711,6 +6804,90 @@ int svgr_pattern_fill(svgr_ctx* ctx, const svgr_pattern* pt, const svgr_buf* til
     g_pool.release(flag);
     if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_pattern_fill: %s", hipGetErrorString(e));
     if (oob) return fail(SVGR_E_INVALID, "svgr_pattern_fill: a tile offset falls outside the pattern canvas");
+    return 0;
+}
+
+// the mip chain of an (h, w) image: level k's size and its first texel in the one buffer that holds them all
+static int64_t image_level(int64_t h, int64_t w, int64_t k, int64_t* lh, int64_t* lw) {
+    int64_t off = 0;
+    for (int64_t i = 0; i < k; ++i) {
+        off += h * w;
+        h = (h + 1) / 2;
+        w = (w + 1) / 2;
+    }
+    *lh = h;
+    *lw = w;
+    return off;
+}
+static int64_t image_n_levels(int64_t h, int64_t w) {
+    int64_t n = 1;
+    for (; h > 1 || w > 1; ++n) { h = (h + 1) / 2; w = (w + 1) / 2; }
+    return n;
+}
+static bool image_size_ok(int64_t h, int64_t w) { return h > 0 && w > 0 && h <= (1 << 16) && w <= (1 << 16) && h * w <= ((int64_t)1 << 30); }
+
+int svgr_image_upload(svgr_ctx* ctx, const uint8_t* rgba, int64_t h, int64_t w, int linear_rgb, svgr_buf* levels) {
+    if (!ctx || !rgba || !levels || !image_size_ok(h, w)) return fail(SVGR_E_INVALID, "svgr_image_upload: bad arguments");
+    const int64_t nl = image_n_levels(h, w);
+    int64_t lh, lw;
+    const int64_t total = image_level(h, w, nl, &lh, &lw);
+    if (levels->bytes < (size_t)total * 16) return fail(SVGR_E_INVALID, "svgr_image_upload: buffer too small");
+    HIPCHK(enter_ctx(ctx));
+    const size_t n0 = (size_t)h * w;
+    uchar4* staging = nullptr;
+    HIPCHK(g_pool.alloc((void**)&staging, n0 * 4, ctx->device));
+    float4* tex = (float4*)levels->ptr;
+    hipError_t e = hipMemcpyAsync(staging, rgba, n0 * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        const dim3 pgrid((unsigned)std::min<size_t>((n0 + 255) / 256, 2048));
+        SVGR_LAUNCH(k_image_prepare, pgrid, dim3(256), 0, ctx->stream, (const uchar4*)staging, n0, linear_rgb ? 1 : 0, tex);
+        int64_t ph = h, pw = w, off = 0;
+        for (int64_t k = 1; k < nl; ++k) {
+            const int64_t dh = (ph + 1) / 2, dw = (pw + 1) / 2;
+            SVGR_LAUNCH(k_image_downsample, grid1((size_t)(dh * dw)), dim3(256), 0, ctx->stream, (const float4*)(tex + off), (int)ph,
+                        (int)pw, tex + off + ph * pw, (int)dh, (int)dw);
+            off += ph * pw;
+            ph = dh;
+            pw = dw;
+        }
+        e = hipGetLastError();
+        // (the caller's array must have been read before the call returns)
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    g_pool.release(staging);
+    if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_image_upload: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int svgr_image_fill(svgr_ctx* ctx, const svgr_image* im, const svgr_buf* levels, const svgr_buf* mask, const int64_t* bbox,
+                    svgr_buf* out) {
+    if (!ctx || !im || !levels || !mask || !out || !bbox_ok(bbox) || !image_size_ok(im->height, im->width))
+        return fail(SVGR_E_INVALID, "svgr_image_fill: bad arguments");
+    const int64_t nl = image_n_levels(im->height, im->width);
+    if (!(im->lod >= 0.0 && im->lod <= (double)(nl - 1)) || (im->smooth != 0 && im->smooth != 1))
+        return fail(SVGR_E_INVALID, "svgr_image_fill: bad level of detail or mode");
+    int64_t th, tw;
+    const size_t n = (size_t)bbox[2] * bbox[3];
+    if (mask->bytes < n * 8 || out->bytes < n * 32 || levels->bytes < (size_t)image_level(im->height, im->width, nl, &th, &tw) * 16)
+        return fail(SVGR_E_INVALID, "svgr_image_fill: buffer too small");
+    if (n == 0) return 0;
+    // the two levels the fill reads (the level of detail is constant over an affine map): floor(lod) and the one above
+    const int64_t k = im->smooth ? (int64_t)std::floor(im->lod) : 0;
+    const double blend = im->smooth ? im->lod - (double)k : 0.0;
+    const int64_t k1 = std::min<int64_t>(k + 1, nl - 1);
+    int64_t h0, w0, h1, w1;
+    const int64_t o0 = image_level(im->height, im->width, k, &h0, &w0), o1 = image_level(im->height, im->width, k1, &h1, &w1);
+    const float4* tex = (const float4*)levels->ptr;
+    const ImageLevel lo{tex + o0, (int)h0, (int)w0, std::ldexp(1.0, -(int)k)}, hi{tex + o1, (int)h1, (int)w1, std::ldexp(1.0, -(int)k1)};
+    HIPCHK(enter_ctx(ctx));
+    const dim3 grid((unsigned)((bbox[3] + IMG_TW - 1) / IMG_TW), (unsigned)std::min<int64_t>((bbox[2] + IMG_TH - 1) / IMG_TH, 32768));
+    if (im->smooth)
+        SVGR_LAUNCH(k_image_fill<true>, grid, dim3(256), 0, ctx->stream, *im, lo, hi, blend, (const double*)mask->ptr, (int)bbox[0],
+                    (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
+    else
+        SVGR_LAUNCH(k_image_fill<false>, grid, dim3(256), 0, ctx->stream, *im, lo, hi, 0.0, (const double*)mask->ptr, (int)bbox[0],
+                    (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -458,7 +458,7 @@ class Path:
         return layer, ConvexHull(_source=lambda: batch.all_edges()[0])
 
     def fill(self, transform: Transform, paint, fill_rule: str | None = None, viewport=None, linear_rgb: bool = True):
-        """Render path by fill-ing it, S:995-1103: solid colours, gradients, patterns."""
+        """Render path by fill-ing it, S:995-1103: solid colours, gradients, patterns; and raster images (ImagePaint)."""
         if paint is None:
             return None
         if isinstance(paint, np.ndarray) and paint.shape == (4,):
@@ -499,6 +499,14 @@ class Path:
             mask, hull = res
             layer = pattern_fill(paint, mask, hull, transform, linear_rgb)
             return None if layer is None else (layer, hull)
+        from .paint import ImagePaint, image_fill  # noqa: PLC0415
+
+        if isinstance(paint, ImagePaint):
+            res = self.mask(transform, fill_rule, viewport)
+            if res is None:
+                return None
+            mask, hull = res
+            return image_fill(paint, mask, hull, transform, linear_rgb), hull
         warnings.warn(f"fill method is not implemented: {paint}")
         return None
 

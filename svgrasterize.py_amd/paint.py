@@ -135,7 +135,7 @@ def is_gradient(paint) -> bool:
 
 def needs_mask(paint) -> bool:
     """Paints that are applied to the path's coverage mask (``Path.mask`` first), i.e. everything but a solid colour."""
-    return isinstance(paint, (GradLinear, GradRadial, Pattern))
+    return isinstance(paint, (GradLinear, GradRadial, Pattern, ImagePaint))
 
 
 def gradient_fill(paint, mask_layer, hull, transform, linear_rgb: bool):
@@ -229,3 +229,76 @@ def pattern_fill(paint: Pattern, mask_layer, hull, transform, linear_rgb: bool):
     tile_buf, mask_buf = tile._device(), mask_layer._device()
     _abi._check(ctx.lib.svgr_pattern_fill(ctx.handle, C.byref(pat), tile_buf.handle, mask_buf.handle, bbox, out.handle))
     return Layer._from_device(out, (rows, cols, 4), mask_layer.offset, pre_alpha=tile.pre_alpha, linear_rgb=tile.linear_rgb)
+
+
+class ImagePaint(tuple):
+    """A raster image as a paint (SVG <image>, beyond the reference): ``pixels`` (h, w, 4) uint8, straight alpha, sRGB as
+    stored; ``transform`` from image space (x along the columns, y along the rows; texel (r, c) covers [c, c + 1) x
+    [r, r + 1)) to user space; ``smooth`` trilinear over a mip chain, else nearest texel (image-rendering: pixelated).
+
+    The pixels are kept as a read-only copy, so that the device image made from them can never go stale; it is made once
+    per colour space on first use and lives (and goes) with this object."""
+
+    def __new__(cls, pixels, transform, smooth: bool = True):
+        px = np.array(pixels, dtype=np.uint8, copy=True, order="C")
+        if px.ndim != 3 or px.shape[2] != 4 or px.shape[0] == 0 or px.shape[1] == 0:
+            raise ValueError(f"an image is a non-empty (h, w, 4) uint8 array, not {px.shape}")
+        px.flags.writeable = False
+        return tuple.__new__(cls, (px, transform, bool(smooth)))
+
+    pixels = property(lambda self: self[0])
+    transform = property(lambda self: self[1])
+    smooth = property(lambda self: self[2])
+    __hash__ = object.__hash__          # (identity: the fields hold an array)
+
+    def __eq__(self, other):
+        return self is other
+
+    def __ne__(self, other):
+        return self is not other
+
+    def __reduce__(self):   # (the device image stays behind)
+        return (ImagePaint, tuple(self))
+
+    def __repr__(self):
+        h, w = self[0].shape[:2]
+        return f"ImagePaint({w}x{h}, {'smooth' if self[2] else 'nearest'})"
+
+    def levels(self, linear_rgb: bool) -> "_abi.DeviceBuffer":
+        """The device image (premultiplied float32x4 mip chain, svgr_image_upload) for one colour space, uploaded once."""
+        cache = self.__dict__.setdefault("_levels", {})
+        buf = cache.get(bool(linear_rgb))
+        if buf is None:
+            buf = cache[bool(linear_rgb)] = _abi.image_upload(_abi.Context.get(), self[0], linear_rgb)
+        return buf
+
+
+def image_lod(inv_m, n_levels: int) -> float:
+    """Level of detail of an affine pixel -> image map: log2 of the longer image-space step of one pixel along the rows or
+    the columns, clamped to [0, n_levels - 1] (constant over the fill)."""
+    a = np.asarray(inv_m, dtype=np.float64)[:2, :2]
+    rho = max(float(np.hypot(a[0, 0], a[1, 0])), float(np.hypot(a[0, 1], a[1, 1])))
+    if not rho > 1.0:       # (also NaN)
+        return 0.0
+    return float(min(np.log2(rho), n_levels - 1))
+
+
+def image_fill(paint: ImagePaint, mask_layer, hull, transform, linear_rgb: bool):
+    """Path.fill, image branch: the RGBA Layer = image sampled at every pixel centre * mask (``k_image_fill``)."""
+    from .layer import Layer
+
+    h, w = paint.pixels.shape[:2]
+    inv = (transform @ paint.transform).invert.m
+    im = _abi.ImageArgs()
+    im.inv_m6 = (C.c_double * 6)(*np.asarray(inv, dtype=np.float64)[:2].ravel())
+    im.height, im.width = h, w
+    im.smooth = int(paint.smooth)
+    im.lod = image_lod(inv, len(_abi.image_levels(h, w))) if paint.smooth else 0.0
+    levels = paint.levels(linear_rgb)
+    ctx = _abi.Context.get()
+    rows, cols = mask_layer.height, mask_layer.width
+    out = ctx.alloc(rows * cols * 32)
+    bbox = (C.c_int64 * 4)(int(mask_layer.x), int(mask_layer.y), rows, cols)
+    mask_buf = mask_layer._device()   # (bound to a name: a host-resident layer's buffer must outlive the call)
+    _abi._check(ctx.lib.svgr_image_fill(ctx.handle, C.byref(im), levels.handle, mask_buf.handle, bbox, out.handle))
+    return Layer._from_device(out, (rows, cols, 4), mask_layer.offset, pre_alpha=True, linear_rgb=linear_rgb)

@@ -1,0 +1,155 @@
+"""PNG reader for SVG <image> (beyond the reference): bytes in, an (h, w, 4) uint8 array out, straight alpha, sRGB as stored.
+
+Chunks are read here (signature, CRC of every chunk, IHDR / PLTE / tRNS / IDAT; ancillary chunks are skipped) and the
+image data is inflated with the standard library's zlib.  Reversing the scanline filters is a sequential walk over the
+bytes and runs in native host code (``svgr_png_unfilter``, csrc/svgr_png.cpp); unpacking samples below 8 bits, the palette
+lookup, 16 -> 8 bit reduction and the Adam7 scatter are numpy.  Every colour type and bit depth of the specification is
+read.  Malformed input raises ValueError with the reason."""
+from __future__ import annotations
+
+import struct
+import zlib
+
+import numpy as np
+
+from . import _abi
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}   # colour type -> bit depths
+_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+# Adam7 passes: (first row, first column, row step, column step)
+_ADAM7 = ((0, 0, 8, 8), (0, 4, 8, 8), (4, 0, 8, 4), (0, 2, 4, 4), (2, 0, 4, 2), (0, 1, 2, 2), (1, 0, 2, 1))
+_MAX_PIXELS = 1 << 30
+
+
+def _chunks(data: bytes):
+    if data[:8] != SIGNATURE:
+        raise ValueError("not a PNG image: bad signature")
+    pos, n = 8, len(data)
+    while True:
+        if pos + 8 > n:
+            raise ValueError("truncated PNG: no IEND chunk")
+        length, ctype = struct.unpack(">I4s", data[pos:pos + 8])
+        if length > 0x7FFFFFFF:
+            raise ValueError(f"bad PNG chunk length {length}")
+        end = pos + 12 + length
+        if end > n:
+            raise ValueError(f"truncated PNG: the {ctype!r} chunk runs past the end of the data")
+        body = data[pos + 8:pos + 8 + length]
+        (crc,) = struct.unpack(">I", data[pos + 8 + length:end])
+        if zlib.crc32(body, zlib.crc32(ctype)) & 0xFFFFFFFF != crc:
+            raise ValueError(f"bad CRC in the {ctype!r} chunk")
+        yield ctype, body
+        if ctype == b"IEND":
+            return
+        pos = end
+
+
+def _samples(rows: np.ndarray, width: int, channels: int, depth: int) -> np.ndarray:
+    """Unfiltered scanlines (h, row_bytes) -> samples (h, width, channels): uint8, or uint16 at depth 16."""
+    h = rows.shape[0]
+    if depth == 8:
+        return rows[:, :width * channels].reshape(h, width, channels)
+    if depth == 16:
+        return rows[:, :width * channels * 2].copy().view(">u2").astype(np.uint16).reshape(h, width, channels)
+    per_byte = 8 // depth   # (depths below 8 occur with one channel only)
+    shifts = np.arange(8 - depth, -1, -depth, dtype=np.uint8)
+    vals = (rows[:, :, None] >> shifts) & np.uint8((1 << depth) - 1)
+    return vals.reshape(h, rows.shape[1] * per_byte)[:, :width, None]
+
+
+def _to8(samples: np.ndarray, depth: int) -> np.ndarray:
+    if depth == 16:
+        return ((samples.astype(np.uint32) * 255 + 32767) // 65535).astype(np.uint8)
+    if depth < 8:
+        return (samples * np.uint8(255 // ((1 << depth) - 1))).astype(np.uint8)
+    return samples.astype(np.uint8)
+
+
+def read_png(data: bytes) -> np.ndarray:
+    """Decode a PNG image: ``(height, width, 4) uint8`` RGBA, straight alpha, the stored sRGB values (gAMA, iCCP, sRGB,
+    cHRM and text chunks are ignored).  16-bit samples become ``(v * 255 + 32767) // 65535``; gray below 8 bits is scaled
+    to 0-255; a tRNS colour key makes its pixels transparent.  ValueError on malformed input."""
+    data = bytes(data)
+    ihdr = plte = trns = None
+    idat = []
+    for ctype, body in _chunks(data):
+        if ctype == b"IHDR":
+            if ihdr is not None or len(body) != 13:
+                raise ValueError("bad IHDR chunk")
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif ihdr is None:
+            raise ValueError("the first PNG chunk is not IHDR")
+        elif ctype == b"PLTE":
+            if len(body) % 3 or not 3 <= len(body) <= 768:
+                raise ValueError("bad PLTE chunk length")
+            plte = np.frombuffer(body, dtype=np.uint8).reshape(-1, 3)
+        elif ctype == b"tRNS":
+            trns = body
+        elif ctype == b"IDAT":
+            idat.append(body)
+        elif ctype == b"IEND":
+            break
+        elif not ctype[0] & 0x20:   # (an unknown critical chunk: the image cannot be read correctly without it)
+            raise ValueError(f"unsupported critical PNG chunk {ctype!r}")
+    if ihdr is None:
+        raise ValueError("no IHDR chunk")
+    width, height, depth, ctype_, compression, filtering, interlace = ihdr
+    if ctype_ not in _DEPTHS or depth not in _DEPTHS[ctype_]:
+        raise ValueError(f"bad IHDR: bit depth {depth} with colour type {ctype_}")
+    if width == 0 or height == 0 or width > 0x7FFFFFFF or height > 0x7FFFFFFF or width * height > _MAX_PIXELS:
+        raise ValueError(f"bad IHDR: image size {width} x {height}")
+    if compression != 0 or filtering != 0 or interlace not in (0, 1):
+        raise ValueError(f"bad IHDR: compression {compression}, filter method {filtering}, interlace {interlace}")
+    if ctype_ == 3 and plte is None:
+        raise ValueError("a palette image without a PLTE chunk")
+    if not idat:
+        raise ValueError("no IDAT chunk")
+    channels = _CHANNELS[ctype_]
+    bits = channels * depth
+    passes = _ADAM7 if interlace else ((0, 0, 1, 1),)
+    sizes = []
+    for r0, c0, rs, cs in passes:
+        ph, pw = (height - r0 + rs - 1) // rs, (width - c0 + cs - 1) // cs
+        sizes.append((ph, pw, (pw * bits + 7) // 8))
+    need = sum(ph * (rb + 1) for ph, pw, rb in sizes if ph and pw)
+    inflater = zlib.decompressobj()
+    try:
+        raw = inflater.decompress(b"".join(idat), need + 1)
+    except zlib.error as e:
+        raise ValueError(f"bad PNG image data: {e}") from None
+    if len(raw) < need:
+        raise ValueError("truncated PNG image data")
+
+    samples = np.empty((height, width, channels), dtype=np.uint16 if depth == 16 else np.uint8)
+    pos = 0
+    for (r0, c0, rs, cs), (ph, pw, rb) in zip(passes, sizes):
+        if ph == 0 or pw == 0:
+            continue
+        rows = _abi.png_unfilter(raw[pos:pos + ph * (rb + 1)], ph, rb, max(1, bits // 8))
+        pos += ph * (rb + 1)
+        samples[r0::rs, c0::cs] = _samples(rows, pw, channels, depth)
+
+    out = np.empty((height, width, 4), dtype=np.uint8)
+    if ctype_ == 3:
+        idx = samples[..., 0]
+        if int(idx.max()) >= len(plte):
+            raise ValueError("a palette index beyond the PLTE chunk")
+        table = np.full((256, 4), 255, dtype=np.uint8)
+        table[:len(plte), :3] = plte
+        if trns is not None:
+            alpha = np.frombuffer(trns, dtype=np.uint8)[:len(plte)]
+            table[:len(alpha), 3] = alpha
+        return table[idx]
+    colour = samples[..., :3] if ctype_ in (2, 6) else np.repeat(samples[..., :1], 3, axis=2)
+    out[..., :3] = _to8(colour, depth)
+    if ctype_ in (4, 6):
+        out[..., 3] = _to8(samples[..., -1], depth)
+    else:
+        out[..., 3] = 255
+        if trns is not None:   # colour key: one 16-bit value per channel, compared with the samples as stored
+            key = np.frombuffer(trns, dtype=">u2").astype(np.int64)
+            if len(key) != channels:
+                raise ValueError("bad tRNS chunk length")
+            out[np.all(samples.astype(np.int64) == key, axis=2), 3] = 0
+    return out

@@ -10,7 +10,7 @@ routes, both of them HIP:
   target are single paths (clip source + clipped entry), and a CLIP or an OPACITY over a GROUP of plain
   leaves (an isolated group: its members composite into a group tile on the device, which is clipped /
   faded as a whole, ``svgr_batch_set_groups``).
-* per node: everything else (gradient and pattern fills, filters, masks, isolated groups that are not flat)
+* per node: everything else (gradient, pattern and image fills, filters, masks, isolated groups that are not flat)
   is rendered node by node into device-resident Layers and merged with ``Layer.compose`` exactly as the
   reference does.
 
@@ -28,7 +28,7 @@ from . import _abi
 from ._state import RENDER_LOCK, STATE, next_serial
 from .geometry import ConvexHull, Path, Transform, solid_paint, _RULES, FLATNESS
 from .layer import COMPOSE_IN, COMPOSE_OVER, Layer
-from .paint import _SPREAD, is_gradient, needs_mask   # (paint.py imports nothing of this module)
+from .paint import _SPREAD, ImagePaint, is_gradient, needs_mask   # (paint.py imports nothing of this module)
 
 RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY = 0, 1, 2, 3
 RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER = 4, 5, 6, 7
@@ -137,6 +137,44 @@ def clear_render_cache() -> None:
         st.release()
 
 
+_ALIGNS = {f"x{x}Y{y}": (i, j) for i, x in enumerate(("Min", "Mid", "Max")) for j, y in enumerate(("Min", "Mid", "Max"))}
+
+
+def parse_preserve_aspect_ratio(text: str):
+    """SVG 1.1 section 7.8 ``preserveAspectRatio``: ``None`` for ``none``, else ``((ax, ay), slice)`` with ax / ay = 0, 1,
+    2 for Min / Mid / Max.  A leading ``defer`` is accepted and ignored.  ValueError on anything else."""
+    words = (text or "").split()
+    if words[:1] == ["defer"]:
+        words = words[1:]
+    if words == ["none"]:
+        return None
+    if not 1 <= len(words) <= 2 or words[0] not in _ALIGNS or (len(words) == 2 and words[1] not in ("meet", "slice")):
+        raise ValueError(f"invalid preserveAspectRatio: {text!r}")
+    return _ALIGNS[words[0]], len(words) == 2 and words[1] == "slice"
+
+
+def image_placement(size, x: float, y: float, width: float, height: float, preserve_aspect_ratio="xMidYMid meet"):
+    """Where an (h, w) = `size` image goes in the viewport (x, y, width, height) (SVG 1.1 section 7.8): ``(transform,
+    visible)`` with `transform` from image space to user space and `visible` = (x0, y0, x1, y1) the viewport intersected with
+    the placed image; None for an empty viewport."""
+    h, w = size
+    if not (width > 0 and height > 0 and h > 0 and w > 0):
+        return None
+    par = parse_preserve_aspect_ratio(preserve_aspect_ratio)
+    if par is None:
+        sx, sy, tx, ty = width / w, height / h, x, y
+    else:
+        (ax, ay), slice_ = par
+        sx = sy = (max if slice_ else min)(width / w, height / h)
+        tx = x + (width - w * sx) * ax / 2
+        ty = y + (height - h * sy) * ay / 2
+    tr = Transform().translate(tx, ty).scale(sx, sy)
+    visible = (max(x, tx), max(y, ty), min(x + width, tx + w * sx), min(y + height, ty + h * sy))
+    if not (visible[2] > visible[0] and visible[3] > visible[1]):
+        return None
+    return tr, visible
+
+
 class Scene(tuple):
     __slots__ = []
 
@@ -147,6 +185,23 @@ class Scene(tuple):
     @classmethod
     def fill(cls, path: Path, paint, fill_rule=None) -> "Scene":
         return cls(RENDER_FILL, (path, paint, fill_rule))
+
+    @classmethod
+    def image(cls, pixels, x: float, y: float, width: float, height: float, preserve_aspect_ratio: str = "xMidYMid meet",
+              smooth: bool = True) -> "Scene | None":
+        """An (h, w, 4) uint8 straight-alpha sRGB raster placed in the viewport (x, y, width, height) like SVG's <image>:
+        a FILL of the visible part of the viewport with an ``ImagePaint`` (trilinear if `smooth`, else nearest texel).
+        None when nothing is visible (a zero width or height)."""
+        from .geometry import PATH_CLOSED, PATH_LINE  # noqa: PLC0415
+
+        pixels = np.asarray(pixels)
+        placed = image_placement(pixels.shape[:2], x, y, width, height, preserve_aspect_ratio)
+        if placed is None:
+            return None
+        tr, (x0, y0, x1, y1) = placed
+        frame = [(PATH_LINE, [[x0, y0], [x1, y0]]), (PATH_LINE, [[x1, y0], [x1, y1]]), (PATH_LINE, [[x1, y1], [x0, y1]]),
+                 (PATH_CLOSED, [[x0, y1], [x0, y0]])]
+        return cls.fill(Path([frame]), ImagePaint(pixels, tr, smooth))
 
     @classmethod
     def stroke(cls, path: Path, paint, width: float, linecap=None, linejoin=None) -> "Scene":

@@ -10,7 +10,7 @@ import json
 import numpy as np
 
 from .geometry import Path, Transform
-from .paint import GradLinear, GradRadial, Pattern
+from .paint import GradLinear, GradRadial, ImagePaint, Pattern
 from .scene import Scene
 
 
@@ -37,6 +37,8 @@ def load_scene(npz_path: str):
             return np.array(p["v"], dtype=np.float64)
         if p["k"] == "pattern":
             return Pattern(node(p["scene"]), p["scene_bbox_units"], p["scene_view_box"], *p["cell"], _tr(p["tr"]), p["bbox_units"])
+        if p["k"] == "image":
+            return ImagePaint(z[p["pixels"]], _tr(p["tr"]), p["smooth"])
         tr = None if p.get("tr") is None else _tr(p["tr"])
         stops = [(o, np.array(c)) for o, c in p["stops"]]
         if p["k"] == "linear":
@@ -81,13 +83,15 @@ def gather_path(path: Path):
 
 def dump_scene(scene: Scene):
     """The inverse of `load_scene`: a Scene as plain data in the dump format of oracle/gen_golden.py (class Dumper):
-    ``(tree, arrays)`` with arrays = lines (N, 2, 2), cubics (M, 4, 2), line_off, cubic_off (per path index).
+    ``(tree, arrays)`` with arrays = lines (N, 2, 2), cubics (M, 4, 2), line_off, cubic_off (per path index), and the
+    pixels of every image paint under the name its paint entry gives (``image_<n>``).
     STROKE nodes are stored as FILL nodes of their stroke outline (``from_stroke``), exactly like the reference dumps."""
     from .filters import FE_GAUSSIAN_BLUR
     from .scene import (RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MASK, RENDER_OPACITY, RENDER_STROKE,
                         RENDER_TRANSFORM)
 
     lines, cubics, loff, coff = [], [], [0], [0]
+    images: dict = {}   # array name -> pixels of an ImagePaint
 
     def add_path(path: Path) -> int:
         l, c = gather_path(path)
@@ -107,6 +111,10 @@ def dump_scene(scene: Scene):
                         scene_view_box=None if p.scene_view_box is None else [float(x) for x in p.scene_view_box],
                         cell=[float(p.x), float(p.y), float(p.width), float(p.height)],
                         tr=[float(x) for x in p.transform.m[:2].ravel()], bbox_units=bool(p.bbox_units))
+        if isinstance(p, ImagePaint):
+            name = f"image_{len(images)}"
+            images[name] = p.pixels
+            return dict(k="image", pixels=name, tr=[float(x) for x in p.transform.m[:2].ravel()], smooth=bool(p.smooth))
         if not isinstance(p, (GradLinear, GradRadial)):
             return dict(k="unsupported", name=type(p).__name__)
         common = dict(stops=[[float(o), [float(x) for x in c]] for o, c in p.stops],
@@ -148,7 +156,7 @@ def dump_scene(scene: Scene):
     tree = node(scene)
     cat = lambda xs, shape: np.concatenate(xs) if xs else np.zeros(shape)
     arrays = dict(lines=cat(lines, (0, 2, 2)), cubics=cat(cubics, (0, 4, 2)), line_off=np.array(loff, dtype=np.int64),
-                  cubic_off=np.array(coff, dtype=np.int64))
+                  cubic_off=np.array(coff, dtype=np.int64), **images)
     return tree, arrays
 
 

@@ -10,11 +10,15 @@ Supported: svg (nested, viewBox), g, defs, path, rect, circle, ellipse, line, po
 linearGradient / radialGradient / stop, pattern, clipPath, mask, filter (feOffset, feGaussianBlur, feMerge, feBlend, feComposite,
 feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, and beyond the reference feFlood, feTurbulence,
 feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow; the <filter>'s region for the generators), text / tspan set in
-SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``.
-Not supported (a warning, the element is skipped): textPath, image, foreignObject, switch, marker, ...
+SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``, and beyond the
+reference image (PNG, from a ``data:image/png;base64`` URI or a local file next to the document; ``png.py``).
+Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
+or remote URLs.
 """
 from __future__ import annotations
 
+import base64
+import binascii
 import gzip
 import io
 import math
@@ -35,7 +39,8 @@ from .geometry import (
 )
 from .layer import COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
 from .paint import GradLinear, GradRadial, Pattern
-from .scene import Scene
+from .png import read_png
+from .scene import Scene, parse_preserve_aspect_ratio
 
 UNITS_USER = "userSpaceOnUse"
 UNITS_BBOX = "objectBoundingBox"
@@ -45,7 +50,9 @@ FONT_SIZE = 12  # S:2658
 _INHERITED = {
     "color", "fill", "fill-rule", "fill-opacity", "stroke", "stroke-opacity", "stroke-width", "stroke-linecap",
     "stroke-linejoin", "stroke-miterlimit", "font-family", "font-size", "font-weight", "text-anchor",
+    "image-rendering",   # (beyond the reference: <image>)
 }
+_NEAREST = {"pixelated", "optimizespeed", "crisp-edges"}   # image-rendering values that ask for the nearest texel
 _NUMBER = re.compile(r"[-+]?(?:(?:\d*\.\d+)|(?:\d+\.?))(?:[Ee][+-]?\d+)?")
 _HEX = re.compile("#?([0-9A-Fa-f]+)$")
 _FUNC = re.compile(r"\s*(rgba?|hsl)\(([^\)]+)\)\s*")
@@ -628,12 +635,86 @@ def ellipse_path_data(cx, cy, rx, ry) -> str:
 # the loader
 # ---------------------------------------------------------------------------------------------------------------------
 class _Loader:
-    def __init__(self, fg, width, fonts=None):
+    def __init__(self, fg, width, fonts=None, base_dir=None):
         self.fonts = FontsDB() if fonts is None else fonts
         self.ids: dict = {}
         self.size = None
         self.fg = fg
         self.width = width
+        self.base_dir = base_dir   # the document's directory (<image> files resolve against it); None: not from a file
+
+    def image_pixels(self, href):
+        """The RGBA pixels an <image> href points at, or None (+ warning): a PNG data URI or a local PNG file.  Nothing is
+        ever fetched from the network."""
+        if not href:
+            warnings.warn("image without href")
+            return None
+        href = href.strip()
+        if href[:5].lower() == "data:":
+            head, _, payload = href[5:].partition(",")
+            params = [p.strip().lower() for p in head.split(";")]
+            if params[0] != "image/png" or "base64" not in params[1:]:
+                warnings.warn(f"unsupported image data: {head or 'text/plain'} (only base64 PNG is read)")
+                return None
+            try:
+                data = base64.b64decode("".join(payload.split()), validate=True)
+            except (binascii.Error, ValueError) as e:
+                warnings.warn(f"bad base64 image data: {e}")
+                return None
+            where = "data URI"
+        else:
+            if re.match(r"[A-Za-z][A-Za-z0-9+.-]*:", href) and not re.match(r"[A-Za-z]:[\\/]", href):
+                warnings.warn(f"image not loaded (only data URIs and local files are read): {href}")
+                return None
+            if not href.lower().endswith(".png"):
+                warnings.warn(f"unsupported image format (only PNG is read): {href}")
+                return None
+            if self.base_dir is None:
+                warnings.warn(f"image file not loaded (the document is not from a file): {href}")
+                return None
+            path = os.path.join(self.base_dir, href)
+            try:
+                with open(path, "rb") as f:
+                    data = f.read()
+            except OSError as e:
+                warnings.warn(f"image file not readable: {href}: {e}")
+                return None
+            where = href
+        try:
+            return read_png(data)
+        except ValueError as e:
+            warnings.warn(f"undecodable PNG ({where}): {e}")
+            return None
+
+    def image(self, attrs) -> list:
+        """<image>: a fill of the visible part of its viewport with the image as the paint (Scene.image)."""
+        href = attrs.get("href")
+        if href is None:
+            href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
+        pixels = self.image_pixels(href)
+        if pixels is None:
+            return []
+        h, w = pixels.shape[:2]
+        x, y = parse_size(attrs.get("x", "0")), parse_size(attrs.get("y", "0"))
+        width, height = parse_size(attrs.get("width")), parse_size(attrs.get("height"))
+        if width is None and height is None:   # (SVG 2 `auto`: the intrinsic size, or the aspect ratio kept)
+            width, height = float(w), float(h)
+        elif width is None:
+            width = height * w / h
+        elif height is None:
+            height = width * h / w
+        par = attrs.get("preserveAspectRatio", "xMidYMid meet")
+        try:
+            parse_preserve_aspect_ratio(par)
+        except ValueError:
+            warnings.warn(f"invalid preserveAspectRatio: {par!r}, using xMidYMid meet")
+            par = "xMidYMid meet"
+        if x is None or y is None or not (width > 0 and height > 0):
+            warnings.warn(f"image with an empty or invalid viewport: {x}, {y}, {width}, {height}")
+            return []
+        smooth = attrs.get("image-rendering", "auto").strip().lower() not in _NEAREST
+        node = Scene.image(pixels, x, y, width, height, par, smooth)
+        return [] if node is None else [node]
 
     # -- leaves --------------------------------------------------------------------------------------------------------
     def shape(self, attrs, path=None) -> list:
@@ -859,6 +940,8 @@ class _Loader:
                 item = ids.get(href[1:])
                 if isinstance(item, Scene):
                     group = [item]
+        elif tag == "image":
+            group = self.image(attrs)
         else:
             warnings.warn(f"unsupported element type: {tag}")
 
@@ -894,12 +977,12 @@ class _Loader:
         return group
 
 
-def svg_scene(file, fg=None, width=None, fonts=None):
+def svg_scene(file, fg=None, width=None, fonts=None, base_dir=None):
     """Load an SVG document from a file object: ``(Scene | None, ids, size)`` with ``size = (width, height)`` of the
     outermost viewport (S:2803-3083).  ``width`` rescales the document to that many pixels, ``fg`` replaces the default
     black of shapes without a ``fill``, ``fonts`` is the ``FontsDB`` text is set from (<font> elements of the document are
-    added to it)."""
-    loader = _Loader(fg, width, fonts)
+    added to it), ``base_dir`` the directory relative <image> files are read from (None: only data URIs)."""
+    loader = _Loader(fg, width, fonts, base_dir)
     root = etree.parse(file).getroot()
     inherit = dict(color=np.array([0.0, 0.0, 0.0, 1.0]) if fg is None else fg)
     group = loader.element(root, inherit, top=True)
@@ -914,11 +997,12 @@ def svg_scene_from_str(text: str, fg=None, width=None, fonts=None):
 
 def svg_scene_from_filepath(path: str, fg=None, width=None, fonts=None):
     path = os.path.expanduser(path)
+    base_dir = os.path.dirname(os.path.abspath(path))
     if os.path.splitext(path)[1] in (".gz", ".svgz"):
         with gzip.open(path, mode="rt", encoding="utf-8") as f:
-            return svg_scene(f, fg, width, fonts)
+            return svg_scene(f, fg, width, fonts, base_dir)
     with open(path, encoding="utf-8") as f:
-        return svg_scene(f, fg, width, fonts)
+        return svg_scene(f, fg, width, fonts, base_dir)
 
 
 def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transform=None, linear_rgb=False, fonts=None,
