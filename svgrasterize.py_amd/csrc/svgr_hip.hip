@@ -43,6 +43,7 @@
 #include <cstdio>
 #include <cstring>
 #include <ctime>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -281,12 +282,43 @@ struct DevPool {
 DevPool g_pool;
 }  // namespace
 
-// small RAII-less device array helper (explicit release keeps the ABI exception free)
+// One scratch block of the pool for the length of a call: the destructor gives it back.  By the pool's stream-order rule
+// (above) a block may go back as soon as the last copy or kernel that uses it is enqueued -- its next user is queued behind
+// them on the same stream -- so going back at scope end, whatever waits came before, is safe.
+struct PoolBlock {
+    void* p = nullptr;
+    PoolBlock() = default;
+    PoolBlock(const PoolBlock&) = delete;
+    PoolBlock& operator=(const PoolBlock&) = delete;
+    ~PoolBlock() { g_pool.release(p); }
+    hipError_t alloc(size_t bytes, int dev = -1) {
+        hipError_t e = g_pool.alloc(&p, bytes, dev);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    template <class T>
+    T* as() const { return (T*)p; }
+};
+
+// a device array that owns its block (unless it is a view); release() frees it early
 template <class T>
 struct DevArr {
     T* p = nullptr;
     size_t cap = 0;  // elements
     bool view = false;  // p points into somebody else's block (the batch's input blob): never released here
+    DevArr() = default;
+    DevArr(const DevArr&) = delete;
+    DevArr& operator=(const DevArr&) = delete;
+    DevArr(DevArr&& o) noexcept : p(o.p), cap(o.cap), view(o.view) { o.p = nullptr; o.cap = 0; o.view = false; }
+    DevArr& operator=(DevArr&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p; cap = o.cap; view = o.view;
+            o.p = nullptr; o.cap = 0; o.view = false;
+        }
+        return *this;
+    }
+    ~DevArr() { release(); }
     void point_at(void* base, size_t byte_off, size_t n) {
         release();
         p = (T*)((char*)base + byte_off);
@@ -4341,20 +4373,11 @@ struct svgr_batch {
         return rc;
     }
 
-    void release() {
-        segs.release(); path_m6.release(); path_paint.release(); seg_kind.release(); path_rule.release();
-        seg_path.release(); in_dev.release(); arena.release(); edge_path.release(); bbox.release(); bins.release();
-        band_start.release(); band_count.release(); entries.release();
-        path_group.release(); group_clip_src.release(); group_opacity.release(); groups_dev.release();
-        grads.release(); path_grad.release(); grad_path.release(); grad_flags.release(); grads_dev.release();
-        edges.release(); cell_hdr.release(); cell_plan.release(); pair_idx.release(); slabs.release(); slab_at.release(); seg_cnt.release(); seg_off.release(); lane_off.release(); path_seg0.release(); tile_mask.release(); seg_list.release(); path_list.release(); layer_off.release();
-        adds.release(); items.release(); tile_info.release(); pages.release(); band_item0.release(); work_block.release();
+    // (the device arrays free themselves)
+    ~svgr_batch() {
         for (auto& t : events) { (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2); }
-        events.clear();
         for (auto e : event_pool) (void)hipEventDestroy(e);
-        event_pool.clear();
         if (up_ev) (void)hipEventDestroy(up_ev);
-        up_ev = nullptr;
     }
 };
 
@@ -4380,12 +4403,6 @@ struct WorkSpare {
     DevArr<uint4> items, pages;
     DevArr<Slab> slabs;
     DevArr<unsigned long long> tile_mask;
-    void release() {
-        edge_path.release(); band_start.release(); band_count.release(); pair_idx.release(); slab_at.release(); seg_cnt.release();
-        seg_off.release(); lane_off.release(); band_item0.release(); entries.release(); edges.release(); cell_hdr.release();
-        cell_plan.release(); tile_info.release(); adds.release(); items.release(); pages.release(); slabs.release(); tile_mask.release();
-        work_block.release();
-    }
 };
 #define SVGR_SPARE_ARRAYS(X) X(edge_path) X(band_start) X(band_count) X(pair_idx) X(slab_at) X(seg_cnt) X(seg_off) X(lane_off) X(band_item0) \
     X(entries) X(edges) X(cell_hdr) X(work_block) X(cell_plan) X(tile_info) X(adds) X(items) X(pages) X(slabs) X(tile_mask)
@@ -4396,10 +4413,9 @@ static void spare_stash(svgr_batch* b) {
     if (!c->spare) c->spare = new (std::nothrow) WorkSpare();
     if (!c->spare) return;
     WorkSpare& w = *c->spare;
-    w.release();
     for (int k = 0; k < 4; ++k) w.vp[k] = b->sized_vp[k];
     w.n_segs = b->n_segs; w.n_paths = b->n_paths; w.mask_words = b->mask_words; w.add_shards = b->add_shards; w.n_adds = b->n_adds; w.adds_roomy = b->adds_roomy;
-#define X(a) w.a = b->a; b->a.p = nullptr; b->a.cap = 0; b->a.view = false;
+#define X(a) w.a = std::move(b->a);   // (the spare's old arrays are freed by the move)
     SVGR_SPARE_ARRAYS(X)
 #undef X
 }
@@ -4412,7 +4428,7 @@ static bool spare_adopt(svgr_batch* b) {
     if (b->n_segs * 2 < w->n_segs || b->n_segs > w->n_segs + w->n_segs / 2 || b->n_paths * 2 < w->n_paths || b->n_paths > w->n_paths + w->n_paths / 2) return false;
     // (the capacities that are per path / per segment have to hold outright; the others are the pass's guesses)
     if (w->slab_at.cap && w->slab_at.cap < (size_t)b->n_paths) return false;
-#define X(a) b->a.release(); b->a = w->a; w->a.p = nullptr; w->a.cap = 0; w->a.view = false;
+#define X(a) b->a = std::move(w->a);
     SVGR_SPARE_ARRAYS(X)
 #undef X
     b->mask_words = w->mask_words; b->add_shards = w->add_shards; b->n_adds = w->n_adds; b->adds_roomy = w->adds_roomy;
@@ -4724,6 +4740,118 @@ static void with_tile_variant(const svgr_batch* b, int out_kind, F&& launch) {
     }
 }
 
+// ---- the layer entries' common parts
+static int bbox_ok(const int64_t* bb) {
+    return bb && bb[2] >= 0 && bb[3] >= 0 && bb[2] < (1ll << 30) && bb[3] < (1ll << 30) && std::llabs(bb[0]) < (1ll << 30) &&
+           std::llabs(bb[1]) < (1ll << 30);
+}
+// the over / blend / crop4 / in entries: an RGBA layer over the box `ob` and a source of `ch` (1 or 4) values per pixel over `sb`
+static int check_layer_pair(const char* entry, const svgr_ctx* ctx, const svgr_buf* out, const int64_t* ob, const svgr_buf* src,
+                            const int64_t* sb, int ch) {
+    if (!ctx || !out || !src || !bbox_ok(ob) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (out->bytes < (size_t)ob[2] * ob[3] * 32 || src->bytes < (size_t)sb[2] * sb[3] * 8 * ch) return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
+    return 0;
+}
+
+// the end of an entry with one plain launch: on the context's stream, checked, no wait
+template <class... Param, class... Arg>
+static int launch_tail(svgr_ctx* ctx, void (*kernel)(Param...), dim3 grid, dim3 block, unsigned lds, Arg... args) {
+    HIPCHK(enter_ctx(ctx));
+    SVGR_LAUNCH(kernel, grid, block, lds, ctx->stream, args...);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The end of an entry that hands the device host arrays of its caller: the pieces go back to back into one pool block on the
+// context's stream, `launch(block)` enqueues the work, and ONE wait lets the copies finish reading the caller's memory before
+// the call returns.  The caller has entered the context.
+struct HostSpan { const void* p; size_t bytes; };
+template <class Launch>
+static int upload_launch_wait(svgr_ctx* ctx, const char* entry, std::initializer_list<HostSpan> host, Launch&& launch) {
+    size_t bytes = 0;
+    for (const HostSpan& h : host) bytes += h.bytes;
+    PoolBlock dev;
+    hipError_t e = dev.alloc(bytes);
+    size_t at = 0;
+    for (const HostSpan& h : host) {
+        if (e == hipSuccess) e = hipMemcpyAsync(dev.as<char>() + at, h.p, h.bytes, hipMemcpyHostToDevice, ctx->stream);
+        at += h.bytes;
+    }
+    if (e == hipSuccess) {
+        launch(dev.p);
+        e = hipGetLastError();
+        const hipError_t w = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = w;
+    }
+    if (e != hipSuccess) return fail(SVGR_E_HIP, "%s: %s", entry, hipGetErrorString(e));
+    return 0;
+}
+
+// Separable?  blur_kernel (S:1903-1944) is a product of two 1-D Gaussians whenever the transform is axis aligned
+// (scale, translate, x/y swap): K = u v^T / S with u, v the row / column sums and S the total, to a few ulp.  Then two
+// 1-D passes do the work of the kw x kh stencil (146 taps instead of 5329 for the largest blur of icons.svg).  A
+// rotated or skewed blur is not rank 1 and takes the direct 2-D kernel.  (The reference lets scipy pick an FFT here,
+// which carries ~1e-16 absolute noise itself; both device forms sum in double and stay below that.)
+// (row / column sums in extended precision: summed in plain doubles their own rounding -- not the kernel's rank --
+// decided the test below for some sizes, and a separable blur then took the 625-tap stencil)
+// (the analysis of a kernel is kept: a document's blurs come back with every render, and the row / column sums of a
+//  73 x 73 kernel are 5 000 long-double additions and as many comparisons -- 26 us of host time per call)
+struct Analysed { std::vector<double> k, u, v; double total; bool separable; };
+static std::shared_ptr<const Analysed> analyse_kernel(const double* kernel, int64_t kw, int64_t kh) {
+    static std::mutex an_mu;
+    static std::unordered_map<unsigned long long, std::shared_ptr<const Analysed>> an_cache;
+    // (in front of the hash: the caller's array itself -- a document's blur kernels are kept by the caller and come back at the
+    //  same address; hashing a 73 x 73 kernel was 5 us of the call's 9)
+    struct ByPtr { const double* p = nullptr; int64_t kw = 0, kh = 0; std::shared_ptr<const Analysed> an; };
+    static ByPtr by_ptr[64];
+    ByPtr& slot = by_ptr[((uintptr_t)kernel >> 4) & 63];
+    std::shared_ptr<const Analysed> an;
+    {
+        std::lock_guard<std::mutex> lk(an_mu);
+        if (slot.p == kernel && slot.kw == kw && slot.kh == kh && slot.an && memcmp(slot.an->k.data(), kernel, sizeof(double) * (size_t)kw * kh) == 0)
+            an = slot.an;
+    }
+    unsigned long long hkey = 1469598103934665603ull ^ (unsigned long long)kw * 1099511628211ull ^ ((unsigned long long)kh << 32);
+    if (!an) {
+        const unsigned long long* w64 = (const unsigned long long*)kernel;   // (doubles: 8 bytes each)
+        for (int64_t i = 0; i < kw * kh; ++i) hkey = (hkey ^ w64[i]) * 1099511628211ull;
+        std::lock_guard<std::mutex> lk(an_mu);
+        auto it = an_cache.find(hkey);
+        if (it != an_cache.end() && it->second->u.size() == (size_t)kw && it->second->v.size() == (size_t)kh &&
+            memcmp(it->second->k.data(), kernel, sizeof(double) * (size_t)kw * kh) == 0) {
+            an = it->second;
+            slot.p = kernel; slot.kw = kw; slot.kh = kh; slot.an = an;
+        }
+    }
+    if (!an) {
+        auto fresh = std::make_shared<Analysed>();
+        std::vector<long double> ul((size_t)kw, 0.0L), vl((size_t)kh, 0.0L);
+        long double total_l = 0.0L;
+        double kmax = 0.0;
+        for (int64_t i = 0; i < kw; ++i)
+            for (int64_t j = 0; j < kh; ++j) {
+                const double k = kernel[i * kh + j];
+                ul[(size_t)i] += k; vl[(size_t)j] += k; total_l += k;
+                kmax = std::fabs(k) > kmax ? std::fabs(k) : kmax;
+            }
+        fresh->u.resize((size_t)kw); fresh->v.resize((size_t)kh);
+        for (int64_t i = 0; i < kw; ++i) fresh->u[(size_t)i] = (double)ul[(size_t)i];
+        for (int64_t j = 0; j < kh; ++j) fresh->v[(size_t)j] = (double)vl[(size_t)j];
+        fresh->total = (double)total_l;
+        bool sep = kw > 1 && kh > 1 && std::isfinite(fresh->total) && fresh->total != 0.0;
+        for (int64_t i = 0; i < kw && sep; ++i)
+            for (int64_t j = 0; j < kh; ++j)
+                if (!(std::fabs(kernel[i * kh + j] - fresh->u[(size_t)i] * fresh->v[(size_t)j] / fresh->total) <= 8 * 2.220446049250313e-16 * kmax)) { sep = false; break; }
+        fresh->separable = sep;
+        fresh->k.assign(kernel, kernel + kw * kh);
+        std::lock_guard<std::mutex> lk(an_mu);
+        if (an_cache.size() > 256) an_cache.clear();
+        an_cache[hkey] = fresh;
+        an = fresh;
+        slot.p = kernel; slot.kw = kw; slot.kh = kh; slot.an = an;
+    }
+    return an;
+}
 // ======================================================================================
 // C ABI
 // ======================================================================================
@@ -4850,7 +4978,7 @@ int svgr_shutdown(svgr_ctx* ctx) {
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     for (auto e : ctx->meas_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->pin_ev) (void)hipEventDestroy(ctx->pin_ev);
-    if (ctx->spare) { ctx->spare->release(); delete ctx->spare; ctx->spare = nullptr; }
+    delete ctx->spare;
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->up_busy && ctx->up_ev) (void)hipEventSynchronize(ctx->up_ev);
     if (ctx->up_stage) (void)hipHostFree(ctx->up_stage);
@@ -5069,15 +5197,15 @@ static int batch_create_impl(svgr_ctx* ctx, const svgr_batch_desc* d, svgr_batch
         }
         if (bad | bad_kind)
             for (int64_t s = 0; s < d->n_segs; ++s) {
-                if (d->seg_kind[s] > 1) { b->release(); delete b; return fail(SVGR_E_INVALID, "unsupported path type: `%d`", (int)d->seg_kind[s]); }  // S:945
+                if (d->seg_kind[s] > 1) { delete b; return fail(SVGR_E_INVALID, "unsupported path type: `%d`", (int)d->seg_kind[s]); }  // S:945
                 int npts = d->seg_kind[s] == SVGR_SEG_CUBIC ? 8 : 4;
                 for (int k = 0; k < npts; ++k)
-                    if (!std::isfinite(d->segs[8 * s + k])) { b->release(); delete b; return fail(SVGR_E_INVALID, "non-finite coordinate in segment %lld", (long long)s); }
+                    if (!std::isfinite(d->segs[8 * s + k])) { delete b; return fail(SVGR_E_INVALID, "non-finite coordinate in segment %lld", (long long)s); }
             }
         const uint64_t* um = (const uint64_t*)(hb + o_m6);
         uint64_t bad_m = 0;
         for (int64_t i = 0; i < 6 * d->n_paths; ++i) bad_m |= nonfin(um[i]);
-        if (bad_m) { b->release(); delete b; return fail(SVGR_E_INVALID, "non-finite transform"); }
+        if (bad_m) { delete b; return fail(SVGR_E_INVALID, "non-finite transform"); }
     }
     rc = b->in_dev.ensure(total);
     if (!rc) {
@@ -5101,7 +5229,7 @@ static int batch_create_impl(svgr_ctx* ctx, const svgr_batch_desc* d, svgr_batch
     rc = rc ? rc : b->bbox.ensure(4 * np);
     rc = rc ? rc : b->bins.ensure(np + 1);
     rc = rc ? rc : b->layout_arena();
-    if (rc) { b->release(); delete b; return rc; }
+    if (rc) { delete b; return rc; }
     *out = b;
     return 0;
 }
@@ -5113,7 +5241,6 @@ int svgr_batch_destroy(svgr_batch* b) {
     //  them on the same stream; what must not go away under a running copy is the batch's HOST memory)
     b->wait_uploads();
     spare_stash(b);
-    b->release();
     delete b;
     return 0;
 }
@@ -5977,22 +6104,19 @@ static int batch_all_edges_impl(svgr_batch* b, double* edges, int32_t* edge_path
     if (!edges || total == 0) return 0;  // (a size query)
     if (cap < total) return fail(SVGR_E_INVALID, "edge buffer holds %lld, need %lld", (long long)cap, (long long)total);
     if (total > 0x7fffffff / 4) return fail(SVGR_E_OVERFLOW, "%lld edges: beyond the 32-bit edge index", (long long)total);
-    double* d_edges = nullptr;
-    int* d_path = nullptr;
-    HIPCHK(g_pool.alloc((void**)&d_edges, sizeof(double) * 4 * (size_t)total));
-    if (hipError_t e = g_pool.alloc((void**)&d_path, sizeof(int) * (size_t)total); e != hipSuccess) { g_pool.release(d_edges); HIPCHK(e); }
+    PoolBlock d_edges, d_path;
+    HIPCHK(d_edges.alloc(sizeof(double) * 4 * (size_t)total));
+    HIPCHK(d_path.alloc(sizeof(int) * (size_t)total));
     hipError_t e = hipMemsetAsync(b->arena.p, 0, b->arena_bytes, st);
     if (e == hipSuccess) {
         SVGR_LAUNCH(k_flatten<true>, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p, (const uint8_t*)b->seg_kind.p,
-                           (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr, d_edges, d_path, sh, b->pkeys(), b->bd(),
+                           (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr, d_edges.as<double>(), d_path.as<int>(), sh, b->pkeys(), b->bd(),
                            whole, 0, 0, (const unsigned*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
-        e = hipMemcpyAsync(edges, d_edges, sizeof(double) * 4 * (size_t)total, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && edge_path) e = hipMemcpyAsync(edge_path, d_path, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(edges, d_edges.p, sizeof(double) * 4 * (size_t)total, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && edge_path) e = hipMemcpyAsync(edge_path, d_path.p, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    g_pool.release(d_edges);
-    g_pool.release(d_path);
     if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_batch_all_edges: %s", hipGetErrorString(e));
     return 0;
 }
@@ -6361,53 +6485,32 @@ int svgr_batch_timings(svgr_batch* b, int* n_renders, double* ms_total, double* 
 // ---------------------------------------------------------------------------------------------
 // layer ops
 // ---------------------------------------------------------------------------------------------
-static int bbox_ok(const int64_t* bb) {
-    return bb && bb[2] >= 0 && bb[3] >= 0 && bb[2] < (1ll << 30) && bb[3] < (1ll << 30) && std::llabs(bb[0]) < (1ll << 30) &&
-           std::llabs(bb[1]) < (1ll << 30);
-}
-
 int svgr_layer_over(svgr_ctx* ctx, svgr_buf* dst, const int64_t* db, const svgr_buf* src, const int64_t* sb, int ch, int first) {
-    if (!ctx || !dst || !src || !bbox_ok(db) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "svgr_layer_over: bad arguments");
+    if (int rc = check_layer_pair("svgr_layer_over", ctx, dst, db, src, sb, ch)) return rc;
     size_t n = (size_t)sb[2] * sb[3];
-    if (dst->bytes < (size_t)db[2] * db[3] * 32 || src->bytes < n * 8 * ch) return fail(SVGR_E_INVALID, "svgr_layer_over: buffer too small");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_over, grid1(n), dim3(256), 0, ctx->stream, (double*)dst->ptr, (int)db[0], (int)db[1], (int)db[2],
+    return launch_tail(ctx, k_layer_over, grid1(n), dim3(256), 0, (double*)dst->ptr, (int)db[0], (int)db[1], (int)db[2],
                        (int)db[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch, first);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 int svgr_layer_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch, int mode,
                      const double* k4) {
-    if (!ctx || !out || !src || !bbox_ok(ob) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "svgr_layer_blend: bad arguments");
     if (!(mode == 1 || mode == 3 || mode == 4 || mode == 5) || (mode == 5 && !k4)) return fail(SVGR_E_INVALID, "invalid compose mode: %d", mode);
+    if (int rc = check_layer_pair("svgr_layer_blend", ctx, out, ob, src, sb, ch)) return rc;
     const size_t n = (size_t)ob[2] * ob[3];
-    if (out->bytes < n * 32 || src->bytes < (size_t)sb[2] * sb[3] * 8 * ch) return fail(SVGR_E_INVALID, "svgr_layer_blend: buffer too small");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_blend, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2], (int)ob[3],
+    return launch_tail(ctx, k_layer_blend, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2], (int)ob[3],
                        (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch, mode, mode == 5 ? k4[0] : 0.0,
                        mode == 5 ? k4[1] : 0.0, mode == 5 ? k4[2] : 0.0, mode == 5 ? k4[3] : 0.0);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 int svgr_layer_color_matrix(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const double* m20) {
     if (!ctx || !img || !m20 || n_px < 0 || img->bytes < (size_t)n_px * 32) return fail(SVGR_E_INVALID, "svgr_layer_color_matrix: bad arguments");
     if (n_px == 0) return 0;
     HIPCHK(enter_ctx(ctx));
-    double* dm = nullptr;
-    HIPCHK(g_pool.alloc((void**)&dm, sizeof(double) * 20));
-    hipError_t e = hipMemcpyAsync(dm, m20, sizeof(double) * 20, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    return upload_launch_wait(ctx, "svgr_layer_color_matrix", {{m20, sizeof(double) * 20}}, [&](void* dm) {
         SVGR_LAUNCH(k_layer_color_matrix, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (double*)img->ptr, (size_t)n_px, (const double*)dm);
-        e = hipStreamSynchronize(ctx->stream);  // (m20 is the caller's host memory)
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    g_pool.release(dm);
-    if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_color_matrix: %s", hipGetErrorString(e));
-    return 0;
+    });
 }
 
 int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, int64_t ky, int64_t kx, int is_max) {
@@ -6415,20 +6518,8 @@ int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int
         return fail(SVGR_E_INVALID, "svgr_layer_morphology: bad arguments (the window must fit the layer)");
     const size_t n = (size_t)(rows - ky + 1) * (size_t)(cols - kx + 1);
     if (src->bytes < (size_t)rows * cols * 32 || out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_morphology: buffer too small");
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_morphology, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)src->ptr, (int)rows, (int)cols,
+    return launch_tail(ctx, k_layer_morphology, grid1(n), dim3(256), 0, (double*)out->ptr, (const double*)src->ptr, (int)rows, (int)cols,
                        (int)ky, (int)kx, is_max);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// Host array -> a pool block on the context's stream; the caller synchronises the stream before it returns (the host array is
-// the caller's) and gives the block back.
-static hipError_t upload_tmp(svgr_ctx* ctx, void** dev, const void* host, size_t bytes) {
-    *dev = nullptr;
-    hipError_t e = g_pool.alloc(dev, bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    return e;
 }
 
 static_assert(svgr::kTurbMaxOctaves == SVGR_TURBULENCE_MAX_OCTAVES, "one octave limit");
@@ -6452,18 +6543,10 @@ int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, con
         a.p = svgr::turb_params(base_fx, base_fy, tile, octaves, fractal, stitch);
         a.o0 = (int)bbox[0]; a.o1 = (int)bbox[1]; a.rows = (int)bbox[2]; a.cols = (int)bbox[3];
         HIPCHK(enter_ctx(ctx));
-        void* dev = nullptr;
-        hipError_t e = upload_tmp(ctx, &dev, host.data(), host.size());
-        if (e == hipSuccess) {
+        return upload_launch_wait(ctx, "svgr_layer_turbulence", {{host.data(), host.size()}}, [&](void* dev) {
             SVGR_LAUNCH(k_layer_turbulence, dim3(stride_blocks(n)), dim3(256), 0, ctx->stream, (double*)out->ptr,
                         (const int*)((const double*)dev + svgr::kTurbLattice * 8), (const double*)dev, a);
-            e = hipGetLastError();
-            hipError_t e2 = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = e2;
-        }
-        if (dev) g_pool.release(dev);
-        if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_turbulence: %s", hipGetErrorString(e));
-        return 0;
+        });
     });
 }
 
@@ -6494,18 +6577,10 @@ int svgr_layer_component_transfer(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, co
         a.off0 = off[0]; a.off1 = off[1]; a.off2 = off[2]; a.off3 = off[3];
         a.n_blob = (int)blob.size();
         HIPCHK(enter_ctx(ctx));
-        void* dev = nullptr;
-        hipError_t e = upload_tmp(ctx, &dev, blob.data(), sizeof(double) * blob.size());
-        if (e == hipSuccess) {
+        return upload_launch_wait(ctx, "svgr_layer_component_transfer", {{blob.data(), sizeof(double) * blob.size()}}, [&](void* dev) {
             SVGR_LAUNCH(k_layer_component_transfer, dim3(stride_blocks((size_t)n_px)), dim3(256), (unsigned)(sizeof(double) * blob.size()),
                         ctx->stream, (double*)img->ptr, (size_t)n_px, (const double*)dev, a);
-            e = hipGetLastError();
-            hipError_t e2 = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = e2;
-        }
-        if (dev) g_pool.release(dev);
-        if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_component_transfer: %s", hipGetErrorString(e));
-        return 0;
+        });
     });
 }
 
@@ -6529,18 +6604,10 @@ int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
     a.tiles_x = (int)((cols + T - 1) / T);
     const size_t tiles = (size_t)a.tiles_x * (size_t)((rows + T - 1) / T);
     HIPCHK(enter_ctx(ctx));
-    void* dev = nullptr;
-    hipError_t e = upload_tmp(ctx, &dev, kernel, sizeof(double) * (size_t)(order_x * order_y));
-    if (e == hipSuccess) {
+    return upload_launch_wait(ctx, "svgr_layer_convolve_matrix", {{kernel, sizeof(double) * (size_t)(order_x * order_y)}}, [&](void* dev) {
         SVGR_LAUNCH(k_layer_convolve_matrix, dim3((unsigned)tiles), dim3(T, T), (unsigned)lds(T), ctx->stream, (double*)out->ptr,
                     (const double*)src->ptr, (const double*)dev, a);
-        e = hipGetLastError();
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = e2;
-    }
-    if (dev) g_pool.release(dev);
-    if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_convolve_matrix: %s", hipGetErrorString(e));
-    return 0;
+    });
 }
 
 int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* map, const svgr_buf* src,
@@ -6558,84 +6625,58 @@ int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out
     a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
     a.xc = x_channel; a.yc = y_channel;
     a.l00 = lin4[0]; a.l01 = lin4[1]; a.l10 = lin4[2]; a.l11 = lin4[3]; a.scale = scale;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_displacement_map, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)map->ptr,
-                (const double*)src->ptr, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_displacement_map, grid1(n), dim3(256), 0, (double*)out->ptr, (const double*)map->ptr,
+                       (const double*)src->ptr, a);
 }
 
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t n_px) {
     if (!ctx || !out || !src || n_px < 0 || out->bytes < (size_t)n_px * 8 || src->bytes < (size_t)n_px * 32) return fail(SVGR_E_INVALID, "svgr_layer_luminance: bad arguments");
     if (n_px == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_luminance, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)src->ptr, (size_t)n_px);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_luminance, grid1((size_t)n_px), dim3(256), 0, (double*)out->ptr, (const double*)src->ptr, (size_t)n_px);
 }
 
 int svgr_layer_crop4(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch) {
-    if (!ctx || !out || !src || !bbox_ok(ob) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "svgr_layer_crop4: bad arguments");
+    if (int rc = check_layer_pair("svgr_layer_crop4", ctx, out, ob, src, sb, ch)) return rc;
     size_t n = (size_t)ob[2] * ob[3];
-    if (out->bytes < n * 32 || src->bytes < (size_t)sb[2] * sb[3] * 8 * ch) return fail(SVGR_E_INVALID, "svgr_layer_crop4: buffer too small");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_crop4, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
+    return launch_tail(ctx, k_layer_crop4, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
                        (int)ob[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 int svgr_layer_in(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch) {
-    if (!ctx || !out || !src || !bbox_ok(ob) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "svgr_layer_in: bad arguments");
+    if (int rc = check_layer_pair("svgr_layer_in", ctx, out, ob, src, sb, ch)) return rc;
     size_t n = (size_t)ob[2] * ob[3];
-    if (out->bytes < n * 32 || src->bytes < (size_t)sb[2] * sb[3] * 8 * ch) return fail(SVGR_E_INVALID, "svgr_layer_in: buffer too small");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_in, grid1(n), dim3(256), 0, ctx->stream, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
+    return launch_tail(ctx, k_layer_in, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
                        (int)ob[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 int svgr_layer_scale_to(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n, double f) {
     if (!ctx || !dst || !src || n < 0 || dst->bytes < (size_t)n * 8 || src->bytes < (size_t)n * 8)
         return fail(SVGR_E_INVALID, "svgr_layer_scale: bad arguments");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_scale, grid1((size_t)n), dim3(256), 0, ctx->stream, (double*)dst->ptr, (const double*)src->ptr, (size_t)n, f);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_scale, grid1((size_t)n), dim3(256), 0, (double*)dst->ptr, (const double*)src->ptr, (size_t)n, f);
 }
 int svgr_layer_scale(svgr_ctx* ctx, svgr_buf* img, int64_t n, double f) { return svgr_layer_scale_to(ctx, img, img, n, f); }
 
 int svgr_layer_clip01(svgr_ctx* ctx, svgr_buf* img, int64_t n) {
     if (!ctx || !img || n < 0 || img->bytes < (size_t)n * 8) return fail(SVGR_E_INVALID, "svgr_layer_clip01: bad arguments");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_clip01, grid1((size_t)n), dim3(256), 0, ctx->stream, (double*)img->ptr, (size_t)n);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_clip01, grid1((size_t)n), dim3(256), 0, (double*)img->ptr, (size_t)n);
 }
 
 int svgr_layer_background(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const double* rgba) {
     if (!ctx || !img || !rgba || n_px < 0 || img->bytes < (size_t)n_px * 32) return fail(SVGR_E_INVALID, "svgr_layer_background: bad arguments");
     if (n_px == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_background, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (double*)img->ptr, (size_t)n_px, rgba[0],
+    return launch_tail(ctx, k_layer_background, grid1((size_t)n_px), dim3(256), 0, (double*)img->ptr, (size_t)n_px, rgba[0],
                        rgba[1], rgba[2], rgba[3]);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 int svgr_layer_convert_to(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n_px, unsigned ops) {
     if (!ctx || !dst || !src || n_px < 0 || dst->bytes < (size_t)n_px * 32 || src->bytes < (size_t)n_px * 32 || (ops & ~15u))
         return fail(SVGR_E_INVALID, "svgr_layer_convert: bad arguments");
     if (n_px == 0 || (ops == 0 && dst->ptr == src->ptr)) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_convert<false>, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (double*)dst->ptr, (const double*)src->ptr, (size_t)n_px, ops, 1.0);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_convert<false>, grid1((size_t)n_px), dim3(256), 0, (double*)dst->ptr, (const double*)src->ptr, (size_t)n_px, ops, 1.0);
 }
 int svgr_layer_convert(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, unsigned ops) { return svgr_layer_convert_to(ctx, img, img, n_px, ops); }
 
@@ -6643,10 +6684,7 @@ int svgr_layer_convert_scale_to(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* sr
     if (!ctx || !dst || !src || n_px < 0 || dst->bytes < (size_t)n_px * 32 || src->bytes < (size_t)n_px * 32 || (ops & ~15u))
         return fail(SVGR_E_INVALID, "svgr_layer_convert_scale_to: bad arguments");
     if (n_px == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_layer_convert<true>, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (double*)dst->ptr, (const double*)src->ptr, (size_t)n_px, ops, factor);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_layer_convert<true>, grid1((size_t)n_px), dim3(256), 0, (double*)dst->ptr, (const double*)src->ptr, (size_t)n_px, ops, factor);
 }
 
 static int layer_compose_many(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, int64_t n, svgr_buf* const* srcs, const int64_t* sbs,
@@ -6699,19 +6737,13 @@ static int layer_compose_many(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, i
 int svgr_layer_to_f32(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n, int clip01) {
     if (!ctx || !dst || !src || n < 0 || dst->bytes < (size_t)n * 4 || src->bytes < (size_t)n * 8) return fail(SVGR_E_INVALID, "svgr_layer_to_f32: bad arguments");
     if (n == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_to_f32, grid1((size_t)n), dim3(256), 0, ctx->stream, (float*)dst->ptr, (const double*)src->ptr, (size_t)n, clip01);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_to_f32, grid1((size_t)n), dim3(256), 0, (float*)dst->ptr, (const double*)src->ptr, (size_t)n, clip01);
 }
 
 int svgr_layer_to_rgba8(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n_px) {
     if (!ctx || !dst || !src || n_px < 0 || dst->bytes < (size_t)n_px * 4 || src->bytes < (size_t)n_px * 32) return fail(SVGR_E_INVALID, "svgr_layer_to_rgba8: bad arguments");
     if (n_px == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    SVGR_LAUNCH(k_to_rgba8, grid1((size_t)n_px), dim3(256), 0, ctx->stream, (uchar4*)dst->ptr, (const double4*)src->ptr, (size_t)n_px);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, k_to_rgba8, grid1((size_t)n_px), dim3(256), 0, (uchar4*)dst->ptr, (const double4*)src->ptr, (size_t)n_px);
 }
 
 // the gradient over the pixel grid of `bbox` times `mask` (pts == nullptr), or at the n = bbox[2] * bbox[3] points of `pts`
@@ -6727,7 +6759,7 @@ static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts
     HIPCHK(enter_ctx(ctx));
     hipError_t e = hipSuccess;
     const dim3 ggrid((unsigned)(((long long)bbox[3] + 255) / 256), (unsigned)std::min<long long>(bbox[2], 32768));
-    double* ext = nullptr;  // long stop lists: one device block {offsets, colours}, held until the stream has drained
+    PoolBlock ext;  // long stop lists: one device block {offsets, colours}
     if (g->n_stops <= GRAD_MAX_STOPS) {
         for (int i = 0; i < g->n_stops; ++i) {
             h.stop_off[i] = g->stop_off[i];
@@ -6735,34 +6767,31 @@ static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts
         }
     } else {
         const size_t ns = (size_t)g->n_stops;
-        HIPCHK(g_pool.alloc((void**)&ext, sizeof(double) * 5 * ns, ctx->device));
-        e = hipMemcpyAsync(ext, g->stop_off, sizeof(double) * ns, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ext + ns, g->stop_rgba, sizeof(double) * 4 * ns, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { g_pool.release(ext); return fail(SVGR_E_HIP, "svgr_gradient_fill: %s", hipGetErrorString(e)); }
-        h.ext_stops = ext;
+        HIPCHK(ext.alloc(sizeof(double) * 5 * ns, ctx->device));
+        e = hipMemcpyAsync(ext.p, g->stop_off, sizeof(double) * ns, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ext.as<double>() + ns, g->stop_rgba, sizeof(double) * 4 * ns, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_gradient_fill: %s", hipGetErrorString(e));
+        h.ext_stops = ext.as<double>();
     }
     if (g->kind == 3) {
         // the two-circle gradient needs a device flag (any det < 0 ?) between its two kernels: a word from the block cache
-        int* flag = nullptr;
-        HIPCHK(g_pool.alloc((void**)&flag, 16));
-        e = hipMemsetAsync(flag, 0, 16, ctx->stream);
+        PoolBlock flag;
+        HIPCHK(flag.alloc(16));
+        e = hipMemsetAsync(flag.p, 0, 16, ctx->stream);
         if (e == hipSuccess) {
             SVGR_LAUNCH(k_gradient_detneg, ggrid, dim3(256), 0, ctx->stream, h, pts, (int)bbox[0], (int)bbox[1],
-                               (int)bbox[2], (int)bbox[3], flag);
+                               (int)bbox[2], (int)bbox[3], flag.as<int>());
             SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, (int)bbox[0], (int)bbox[1],
-                               (int)bbox[2], (int)bbox[3], (const int*)flag, (double*)out->ptr);
+                               (int)bbox[2], (int)bbox[3], (const int*)flag.p, (double*)out->ptr);
             e = hipGetLastError();
         }
-        g_pool.release(flag);  // (stream order keeps the word's next user behind the two kernels: nothing to wait for)
     } else {
         SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, (int)bbox[0], (int)bbox[1],
                            (int)bbox[2], (int)bbox[3], (const int*)nullptr, (double*)out->ptr);
         e = hipGetLastError();
     }
-    if (ext) {  // (the stops are the caller's host arrays: the copies above must have been consumed before returning)
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        g_pool.release(ext);
-    }
+    // (the stops are the caller's host arrays: the copies above must have been consumed before returning)
+    if (ext.p && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_gradient_fill: %s", hipGetErrorString(e));
     return 0;
 }
@@ -6790,18 +6819,17 @@ int svgr_pattern_fill(svgr_ctx* ctx, const svgr_pattern* pt, const svgr_buf* til
         return fail(SVGR_E_INVALID, "svgr_pattern_fill: buffer too small");
     if (n == 0) return 0;
     HIPCHK(enter_ctx(ctx));
-    int* flag = nullptr;
-    HIPCHK(g_pool.alloc((void**)&flag, 16));
+    PoolBlock flag;
+    HIPCHK(flag.alloc(16));
     int oob = 0;
-    hipError_t e = hipMemsetAsync(flag, 0, 16, ctx->stream);
+    hipError_t e = hipMemsetAsync(flag.p, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         SVGR_LAUNCH(k_pattern_fill, grid1(n), dim3(256), 0, ctx->stream, *pt, (const double*)tile->ptr, (const double*)mask->ptr,
-                           (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], flag, (double*)out->ptr);
-        e = hipMemcpyAsync(&oob, flag, sizeof oob, hipMemcpyDeviceToHost, ctx->stream);
+                           (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], flag.as<int>(), (double*)out->ptr);
+        e = hipMemcpyAsync(&oob, flag.p, sizeof oob, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    g_pool.release(flag);
     if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_pattern_fill: %s", hipGetErrorString(e));
     if (oob) return fail(SVGR_E_INVALID, "svgr_pattern_fill: a tile offset falls outside the pattern canvas");
     return 0;
@@ -6834,13 +6862,13 @@ int svgr_image_upload(svgr_ctx* ctx, const uint8_t* rgba, int64_t h, int64_t w, 
     if (levels->bytes < (size_t)total * 16) return fail(SVGR_E_INVALID, "svgr_image_upload: buffer too small");
     HIPCHK(enter_ctx(ctx));
     const size_t n0 = (size_t)h * w;
-    uchar4* staging = nullptr;
-    HIPCHK(g_pool.alloc((void**)&staging, n0 * 4, ctx->device));
+    PoolBlock staging;
+    HIPCHK(staging.alloc(n0 * 4, ctx->device));
     float4* tex = (float4*)levels->ptr;
-    hipError_t e = hipMemcpyAsync(staging, rgba, n0 * 4, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(staging.p, rgba, n0 * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         const dim3 pgrid((unsigned)std::min<size_t>((n0 + 255) / 256, 2048));
-        SVGR_LAUNCH(k_image_prepare, pgrid, dim3(256), 0, ctx->stream, (const uchar4*)staging, n0, linear_rgb ? 1 : 0, tex);
+        SVGR_LAUNCH(k_image_prepare, pgrid, dim3(256), 0, ctx->stream, (const uchar4*)staging.p, n0, linear_rgb ? 1 : 0, tex);
         int64_t ph = h, pw = w, off = 0;
         for (int64_t k = 1; k < nl; ++k) {
             const int64_t dh = (ph + 1) / 2, dw = (pw + 1) / 2;
@@ -6854,7 +6882,6 @@ int svgr_image_upload(svgr_ctx* ctx, const uint8_t* rgba, int64_t h, int64_t w, 
         // (the caller's array must have been read before the call returns)
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    g_pool.release(staging);
     if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_image_upload: %s", hipGetErrorString(e));
     return 0;
 }
@@ -6879,16 +6906,9 @@ int svgr_image_fill(svgr_ctx* ctx, const svgr_image* im, const svgr_buf* levels,
     const int64_t o0 = image_level(im->height, im->width, k, &h0, &w0), o1 = image_level(im->height, im->width, k1, &h1, &w1);
     const float4* tex = (const float4*)levels->ptr;
     const ImageLevel lo{tex + o0, (int)h0, (int)w0, std::ldexp(1.0, -(int)k)}, hi{tex + o1, (int)h1, (int)w1, std::ldexp(1.0, -(int)k1)};
-    HIPCHK(enter_ctx(ctx));
     const dim3 grid((unsigned)((bbox[3] + IMG_TW - 1) / IMG_TW), (unsigned)std::min<int64_t>((bbox[2] + IMG_TH - 1) / IMG_TH, 32768));
-    if (im->smooth)
-        SVGR_LAUNCH(k_image_fill<true>, grid, dim3(256), 0, ctx->stream, *im, lo, hi, blend, (const double*)mask->ptr, (int)bbox[0],
-                    (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
-    else
-        SVGR_LAUNCH(k_image_fill<false>, grid, dim3(256), 0, ctx->stream, *im, lo, hi, 0.0, (const double*)mask->ptr, (int)bbox[0],
-                    (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_tail(ctx, im->smooth ? k_image_fill<true> : k_image_fill<false>, grid, dim3(256), 0, *im, lo, hi, blend,
+                       (const double*)mask->ptr, (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
 }
 
 static int layer_convolve_impl(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, const double* kernel,
@@ -6912,141 +6932,65 @@ static int layer_convolve_impl(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
     const size_t n_out = (size_t)(rows + kw - 1) * (size_t)(cols + kh - 1);
     if (src->bytes < (size_t)rows * cols * 32 || out->bytes < n_out * 32) return fail(SVGR_E_INVALID, "svgr_layer_convolve: buffer too small");
     HIPCHK(enter_ctx(ctx));
-    // Separable?  blur_kernel (S:1903-1944) is a product of two 1-D Gaussians whenever the transform is axis aligned
-    // (scale, translate, x/y swap): K = u v^T / S with u, v the row / column sums and S the total, to a few ulp.  Then two
-    // 1-D passes do the work of the kw x kh stencil (146 taps instead of 5329 for the largest blur of icons.svg).  A
-    // rotated or skewed blur is not rank 1 and takes the direct 2-D kernel.  (The reference lets scipy pick an FFT here,
-    // which carries ~1e-16 absolute noise itself; both device forms sum in double and stay below that.)
-    // (row / column sums in extended precision: summed in plain doubles their own rounding -- not the kernel's rank --
-    // decided the test below for some sizes, and a separable blur then took the 625-tap stencil)
-    // (the analysis of a kernel is kept: a document's blurs come back with every render, and the row / column sums of a
-    //  73 x 73 kernel are 5 000 long-double additions and as many comparisons -- 26 us of host time per call)
-    struct Analysed { std::vector<double> k, u, v; double total; bool separable; };
-    static std::mutex an_mu;
-    static std::unordered_map<unsigned long long, std::shared_ptr<const Analysed>> an_cache;
-    // (in front of the hash: the caller's array itself -- a document's blur kernels are kept by the caller and come back at the
-    //  same address; hashing a 73 x 73 kernel was 5 us of the call's 9)
-    struct ByPtr { const double* p = nullptr; int64_t kw = 0, kh = 0; std::shared_ptr<const Analysed> an; };
-    static ByPtr by_ptr[64];
-    ByPtr& slot = by_ptr[((uintptr_t)kernel >> 4) & 63];
-    std::shared_ptr<const Analysed> an;
-    {
-        std::lock_guard<std::mutex> lk(an_mu);
-        if (slot.p == kernel && slot.kw == kw && slot.kh == kh && slot.an && memcmp(slot.an->k.data(), kernel, sizeof(double) * (size_t)kw * kh) == 0)
-            an = slot.an;
-    }
-    unsigned long long hkey = 1469598103934665603ull ^ (unsigned long long)kw * 1099511628211ull ^ ((unsigned long long)kh << 32);
-    if (!an) {
-        const unsigned long long* w64 = (const unsigned long long*)kernel;   // (doubles: 8 bytes each)
-        for (int64_t i = 0; i < kw * kh; ++i) hkey = (hkey ^ w64[i]) * 1099511628211ull;
-        std::lock_guard<std::mutex> lk(an_mu);
-        auto it = an_cache.find(hkey);
-        if (it != an_cache.end() && it->second->u.size() == (size_t)kw && it->second->v.size() == (size_t)kh &&
-            memcmp(it->second->k.data(), kernel, sizeof(double) * (size_t)kw * kh) == 0) {
-            an = it->second;
-            slot.p = kernel; slot.kw = kw; slot.kh = kh; slot.an = an;
-        }
-    }
-    if (!an) {
-        auto fresh = std::make_shared<Analysed>();
-        std::vector<long double> ul((size_t)kw, 0.0L), vl((size_t)kh, 0.0L);
-        long double total_l = 0.0L;
-        double kmax = 0.0;
-        for (int64_t i = 0; i < kw; ++i)
-            for (int64_t j = 0; j < kh; ++j) {
-                const double k = kernel[i * kh + j];
-                ul[(size_t)i] += k; vl[(size_t)j] += k; total_l += k;
-                kmax = std::fabs(k) > kmax ? std::fabs(k) : kmax;
-            }
-        fresh->u.resize((size_t)kw); fresh->v.resize((size_t)kh);
-        for (int64_t i = 0; i < kw; ++i) fresh->u[(size_t)i] = (double)ul[(size_t)i];
-        for (int64_t j = 0; j < kh; ++j) fresh->v[(size_t)j] = (double)vl[(size_t)j];
-        fresh->total = (double)total_l;
-        bool sep = kw > 1 && kh > 1 && std::isfinite(fresh->total) && fresh->total != 0.0;
-        for (int64_t i = 0; i < kw && sep; ++i)
-            for (int64_t j = 0; j < kh; ++j)
-                if (!(std::fabs(kernel[i * kh + j] - fresh->u[(size_t)i] * fresh->v[(size_t)j] / fresh->total) <= 8 * 2.220446049250313e-16 * kmax)) { sep = false; break; }
-        fresh->separable = sep;
-        fresh->k.assign(kernel, kernel + kw * kh);
-        std::lock_guard<std::mutex> lk(an_mu);
-        if (an_cache.size() > 256) an_cache.clear();
-        an_cache[hkey] = fresh;
-        an = fresh;
-        slot.p = kernel; slot.kw = kw; slot.kh = kh; slot.an = an;
-    }
-    std::vector<double> u = an->u, v = an->v;
+    const std::shared_ptr<const Analysed> an = analyse_kernel(kernel, kw, kh);
     const double total = an->total;
     const bool separable = an->separable && getenv("SVGR_BLUR_DIRECT") == nullptr;
-    hipError_t e = hipSuccess;
     static const bool dbg_conv = getenv("SVGR_DBG_CONV") != nullptr;
     const bool blocked = separable && kw <= CONV_TAPS && kh <= CONV_TAPS && rows <= 65535;  // (the row index rides in gridDim.y)
     if (dbg_conv) fprintf(stderr, "[convolve] %lld x %lld layer, %lld x %lld kernel, ops %u: %s\n", (long long)rows, (long long)cols, (long long)kw,
                           (long long)kh, src_ops, blocked ? "two blocked passes" : separable ? "two plain passes" : "direct");
     // (the passes that do not convert as they read: the source converted first, into a block of its own)
-    double* conv_src = nullptr;
+    PoolBlock conv_src;
     const double* src_px = (const double*)src->ptr;
     if (src_ops && !blocked) {
-        HIPCHK(g_pool.alloc((void**)&conv_src, (size_t)rows * cols * 32, ctx->device));
-        SVGR_LAUNCH(k_layer_convert<false>, grid1((size_t)rows * cols), dim3(256), 0, ctx->stream, conv_src, src_px, (size_t)rows * cols, src_ops, 1.0);
-        src_px = conv_src;
+        HIPCHK(conv_src.alloc((size_t)rows * cols * 32, ctx->device));
+        SVGR_LAUNCH(k_layer_convert<false>, grid1((size_t)rows * cols), dim3(256), 0, ctx->stream, conv_src.as<double>(), src_px, (size_t)rows * cols, src_ops, 1.0);
+        src_px = conv_src.as<double>();
     }
-    struct Release { double* p; ~Release() { if (p) g_pool.release(p); } } release_conv{conv_src};   // (stream order: behind the kernels below)
     if (blocked) {
-        // along the rows first (the pass that stages its source in LDS converts it there), then down the columns
-        for (auto& x : u) x /= total;  // K = (u / S) v^T
+        // along the rows first (the pass that stages its source in LDS converts it there), then down the columns; K = (u / S) v^T
         ConvW cu{}, cv{};
         cu.n = (int)kw; cv.n = (int)kh;
-        for (int64_t i = 0; i < kw; ++i) cu.w[i] = u[(size_t)i];
-        for (int64_t j = 0; j < kh; ++j) cv.w[j] = v[(size_t)j];
-        double* tmp = nullptr;
+        for (int64_t i = 0; i < kw; ++i) cu.w[i] = an->u[(size_t)i] / total;
+        for (int64_t j = 0; j < kh; ++j) cv.w[j] = an->v[(size_t)j];
         const int64_t ocols = cols + kh - 1;
         const size_t n_tmp = (size_t)rows * (size_t)ocols;
-        HIPCHK(g_pool.alloc((void**)&tmp, n_tmp * 32, ctx->device));
-        SVGR_LAUNCH(k_convolve_cols, dim3((unsigned)((ocols + 255) / 256), (unsigned)rows), dim3(256), 0, ctx->stream, tmp, src_px,
+        PoolBlock tmp;
+        HIPCHK(tmp.alloc(n_tmp * 32, ctx->device));
+        SVGR_LAUNCH(k_convolve_cols, dim3((unsigned)((ocols + 255) / 256), (unsigned)rows), dim3(256), 0, ctx->stream, tmp.as<double>(), src_px,
                            (int)rows, (int)cols, cv, src_ops);
         SVGR_LAUNCH(k_convolve_rows, dim3((unsigned)((ocols + 63) / 64), (unsigned)((rows + kw - 1 + CONV_RB - 1) / CONV_RB)), dim3(64), 0,
-                           ctx->stream, (double*)out->ptr, (const double*)tmp, (int)rows, (int)ocols, cu);
-        e = hipGetLastError();
-        g_pool.release(tmp);  // (stream order keeps the block's next user behind the two kernels)
-    } else if (separable) {
+                           ctx->stream, (double*)out->ptr, (const double*)tmp.p, (int)rows, (int)ocols, cu);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_convolve: %s", hipGetErrorString(e));
+        return 0;
+    }
+    if (separable) {
+        std::vector<double> u(an->u);
         for (auto& x : u) x /= total;  // K = (u / S) v^T
-        double *dw = nullptr, *tmp = nullptr;
         const size_t n_tmp = (size_t)(rows + kw - 1) * (size_t)cols;
-        HIPCHK(g_pool.alloc((void**)&dw, sizeof(double) * (size_t)(kw + kh)));
-        if (hipError_t a = g_pool.alloc((void**)&tmp, n_tmp * 32); a != hipSuccess) { g_pool.release(dw); HIPCHK(a); }
-        e = hipMemcpyAsync(dw, u.data(), sizeof(double) * (size_t)kw, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dw + kw, v.data(), sizeof(double) * (size_t)kh, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            SVGR_LAUNCH(k_layer_convolve_1d<0>, grid1(n_tmp), dim3(256), 0, ctx->stream, tmp, src_px, (int)rows,
+        PoolBlock tmp;
+        HIPCHK(tmp.alloc(n_tmp * 32));
+        return upload_launch_wait(ctx, "svgr_layer_convolve", {{u.data(), sizeof(double) * (size_t)kw}, {an->v.data(), sizeof(double) * (size_t)kh}},
+                                  [&](void* dw) {
+            SVGR_LAUNCH(k_layer_convolve_1d<0>, grid1(n_tmp), dim3(256), 0, ctx->stream, tmp.as<double>(), src_px, (int)rows,
                                (int)cols, (const double*)dw, (int)kw);
-            SVGR_LAUNCH(k_layer_convolve_1d<1>, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)tmp,
-                               (int)(rows + kw - 1), (int)cols, (const double*)(dw + kw), (int)kh);
-            e = hipStreamSynchronize(ctx->stream);  // (u, v are host vectors of this call)
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-        g_pool.release(tmp);
-        g_pool.release(dw);
-    } else if (kw * kh <= CONV_TAPS) {
+            SVGR_LAUNCH(k_layer_convolve_1d<1>, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, (const double*)tmp.p,
+                               (int)(rows + kw - 1), (int)cols, (const double*)dw + kw, (int)kh);
+        });
+    }
+    if (kw * kh <= CONV_TAPS) {
         ConvW ck{};
         ck.n = (int)(kw * kh);
         for (int64_t i = 0; i < kw * kh; ++i) ck.w[i] = kernel[i];
         SVGR_LAUNCH(k_layer_convolve_small, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, src_px, (int)rows, (int)cols, ck,
                            (int)kw, (int)kh);
-        e = hipGetLastError();
-    } else {
-        double* dk = nullptr;
-        HIPCHK(g_pool.alloc((void**)&dk, sizeof(double) * (size_t)kw * kh));
-        e = hipMemcpyAsync(dk, kernel, sizeof(double) * (size_t)kw * kh, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            SVGR_LAUNCH(k_layer_convolve, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, src_px,
-                               (int)rows, (int)cols, (const double*)dk, (int)kw, (int)kh);
-            e = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-        g_pool.release(dk);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_convolve: %s", hipGetErrorString(e));
+        return 0;
     }
-    if (e != hipSuccess) return fail(SVGR_E_HIP, "svgr_layer_convolve: %s", hipGetErrorString(e));
-    return 0;
+    return upload_launch_wait(ctx, "svgr_layer_convolve", {{kernel, sizeof(double) * (size_t)kw * kh}}, [&](void* dk) {
+        SVGR_LAUNCH(k_layer_convolve, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, src_px,
+                           (int)rows, (int)cols, (const double*)dk, (int)kw, (int)kh);
+    });
 }
 
 }  // extern "C"
