@@ -39,7 +39,8 @@ extern "C" {
  *    or removed)
  * 6 (later, nothing changed or removed): svgr_layer_turbulence, svgr_layer_component_transfer, svgr_layer_convolve_matrix,
  *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
- *    svgr_png_unfilter added (SVG <image>, beyond the reference) */
+ *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
+ *    feSpecularLighting) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -344,6 +345,24 @@ int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
  * out_bbox[1] + C + 0.5 + (m10 d0 + m11 d1)), transparent outside src.  Channels 0..3 = R, G, B, A.                            */
 int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* map, const svgr_buf* src,
                                 const int64_t* src_bbox, const double* lin4, double scale, int x_channel, int y_channel);
+/* feDiffuseLighting / feSpecularLighting: out (out_bbox[2] x out_bbox[3] x 4, the filter region at device offset (out_bbox[0],
+ * out_bbox[1])) from the alpha channel of src (bbox src_bbox, premultiplied or straight: alpha is the same), read as 0 outside src;
+ * src pixels outside the region are not read.  Frame: d0 = row, d1 = column, z up; pixel [R, C] is the device point
+ * (out_bbox[0] + R + 0.5, out_bbox[1] + C + 0.5) at height surface_scale * A.  In this order, per pixel (svgr_core.h:
+ * light_normal, light_pixel), without contractions:
+ *   1. N = normalize(-ss f0 g0, -ss f1 g1, 1), g0 / g1 the Sobel sums along rows / columns over the 3 x 3 alpha neighbourhood
+ *      with the kernel and factor of the pixel's place in the region (Filter Effects 1's table: corners, edges, interior; a
+ *      line outside the region weighs 0); a region of one row or one column is flat, N = (0, 0, 1).
+ *   2. L: light_kind 0 distant, light_params {L0, L1, L2} (unit, device frame); 1 point, {P0, P1, P2}; 2 spot, {P0, P1, P2,
+ *      S0, S1, S2 (unit pointsAt - P), spot exponent, cos of the cone angle (-1: no cone)}.  Point and spot:
+ *      L = normalize(P - (d0, d1, ss A)), (0, 0, 1) at P itself.
+ *   3. Light colour color3 (linear RGB); spot: times pow(-L.S, spot exponent) where -L.S > 0 and -L.S >= the cone's cos, else 0.
+ *   4. specular 0: rgb = clamp(constant max(N.L, 0) colour, 0, 1), alpha 1.  specular 1: H = normalize(L + (0, 0, 1)),
+ *      rgb = clamp(constant pow(max(N.H, 0), specular_exponent) colour, 0, 1), alpha = max(r, g, b): premultiplied.
+ * out must not be src.                                                                                                        */
+int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
+                        int light_kind, const double* light_params, const double* color3, double surface_scale, double constant,
+                        double specular_exponent, int specular);
 /* Luminance of a straight-alpha RGBA image for RENDER_MASK (S:735): out(n_px doubles) = (rgb . {0.2125, 0.7154, 0.072}) * a */
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out_1ch, const svgr_buf* src_rgba, int64_t n_px);
 

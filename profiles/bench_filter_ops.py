@@ -61,6 +61,18 @@ def main():
         k = rng.random((order, order))
         run(f"k_layer_convolve_matrix {order}x{order}", 2 * px, lambda k=k: pre.convolve_matrix(k, None, 0.0, None, "duplicate", False))
     run("k_layer_displacement_map (scale 20)", 3 * px, lambda: pre.displacement_map(layer, tr, 20.0, "R", "G"))
+    # lighting over the layer's own extent: 32 B read (alpha, one double of each pixel, whole lines) + 32 B written per pixel
+    from svgrasterize_amd.filters import DistantLight, PointLight, SpotLight
+
+    cx, cy = tr.invert(np.array([n / 2, n / 2]))
+    lx, ly = tr.invert(np.array([n / 4, n / 3]))
+    white = (1.0, 1.0, 1.0)
+    run("k_layer_lighting diffuse, distant", 2 * px,
+        lambda: pre.lighting(tr, (0, 0), (n, n), DistantLight(45.0, 30.0), white, 2.0, 1.0))
+    run("k_layer_lighting specular, point, exponent 20", 2 * px,
+        lambda: pre.lighting(tr, (0, 0), (n, n), PointLight(lx, ly, 500.0), white, 2.0, 1.0, 20.0))
+    run("k_layer_lighting specular, spot with a cone, exponent 20", 2 * px,
+        lambda: pre.lighting(tr, (0, 0), (n, n), SpotLight(lx, ly, 2000.0, cx, cy, 0.0, 8.0, 40.0), white, 2.0, 1.0, 20.0))
     for r in res:
         print(json.dumps(r))
 

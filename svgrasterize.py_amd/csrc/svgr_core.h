@@ -612,4 +612,90 @@ SVGR_HD double transfer_fn(double c, int type, const double* prm, const double* 
     return r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
 }
 
+// ------------------------------------------------------------------------------------
+// feDiffuseLighting / feSpecularLighting: one output pixel from the 3 x 3 alpha neighbourhood around it (Filter Effects 1).
+// Device frame (d0 = row, d1 = column, z); a[3 k + j] is the alpha at row offset k - 1 and column offset j - 1, zero outside
+// the input.  top / bottom / left / right: the pixel is in the first / last row / column of the region (the spec's Sobel table,
+// include/svgr.h).  light.l: distant {L0, L1, L2} (unit, constant); point {P0, P1, P2}; spot {P0, P1, P2, S0, S1, S2 (unit),
+// spot exponent, cos of the cone (-1: no cone)}.
+// ------------------------------------------------------------------------------------
+enum { kLightDistant = 0, kLightPoint = 1, kLightSpot = 2 };
+
+struct LightParams {
+    double l[8];
+    double color[3];
+    double surface_scale, constant, specular_exponent;
+    int kind, specular;
+};
+
+// N (unit) from the neighbourhood.  Along each axis: the difference across the pixel (hi - lo, one-sided at an edge) in each
+// of the three lines across it, weighted 1, 2, 1 (a line outside the region weighs 0) and summed in line order; times
+// -surface_scale * 2 / (sum of the weights * the span of the difference).  A region one row or one column wide is flat.
+SVGR_HD void light_normal(const double* a, int top, int bottom, int left, int right, double ss, double* n) {
+    if ((top && bottom) || (left && right)) {
+        n[0] = 0.0; n[1] = 0.0; n[2] = 1.0;
+        return;
+    }
+    const int r_lo = top ? 1 : 0, r_hi = bottom ? 1 : 2, c_lo = left ? 1 : 0, c_hi = right ? 1 : 2;
+    const double wt = top ? 0.0 : 1.0, wb = bottom ? 0.0 : 1.0;     // weights of the rows above / below
+    const double wl = left ? 0.0 : 1.0, wr = right ? 0.0 : 1.0;     // and of the columns left / right
+    // along d0: column-wise differences (row r_hi - row r_lo), columns left, centre, right
+    const double g0 = wl * (a[3 * r_hi + 0] - a[3 * r_lo + 0]) + 2.0 * (a[3 * r_hi + 1] - a[3 * r_lo + 1]) + wr * (a[3 * r_hi + 2] - a[3 * r_lo + 2]);
+    // along d1: row-wise differences (column c_hi - column c_lo), rows top, middle, bottom
+    const double g1 = wt * (a[c_hi] - a[c_lo]) + 2.0 * (a[3 + c_hi] - a[3 + c_lo]) + wb * (a[6 + c_hi] - a[6 + c_lo]);
+    const double f0 = 2.0 / ((wl + 2.0 + wr) * (double)(r_hi - r_lo));
+    const double f1 = 2.0 / ((wt + 2.0 + wb) * (double)(c_hi - c_lo));
+    const double n0 = -ss * f0 * g0, n1 = -ss * f1 * g1;
+    const double len = sqrt(n0 * n0 + n1 * n1 + 1.0);
+    n[0] = n0 / len; n[1] = n1 / len; n[2] = 1.0 / len;
+}
+
+// One pixel: (d0, d1) its device centre, a / edge flags as for light_normal.  out = {r, g, b, a}: diffuse opaque, specular
+// premultiplied (alpha = the largest colour channel).
+SVGR_HD void light_pixel(const LightParams& p, const double* a, int top, int bottom, int left, int right, double d0, double d1,
+                         double* out) {
+    double n[3];
+    light_normal(a, top, bottom, left, right, p.surface_scale, n);
+    double l0, l1, l2;
+    if (p.kind == kLightDistant) {
+        l0 = p.l[0]; l1 = p.l[1]; l2 = p.l[2];
+    } else {
+        const double v0 = p.l[0] - d0, v1 = p.l[1] - d1, v2 = p.l[2] - p.surface_scale * a[4];
+        const double len = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+        if (len > 0.0) {
+            l0 = v0 / len; l1 = v1 / len; l2 = v2 / len;
+        } else {
+            l0 = 0.0; l1 = 0.0; l2 = 1.0;
+        }
+    }
+    double c0 = p.color[0], c1 = p.color[1], c2 = p.color[2];
+    if (p.kind == kLightSpot) {
+        const double m = -(l0 * p.l[3] + l1 * p.l[4] + l2 * p.l[5]);
+        if (m > 0.0 && m >= p.l[7]) {
+            const double f = pow(m, p.l[6]);
+            c0 = c0 * f; c1 = c1 * f; c2 = c2 * f;
+        } else {
+            c0 = 0.0; c1 = 0.0; c2 = 0.0;
+        }
+    }
+    double k;
+    if (p.specular) {
+        const double h0 = l0, h1 = l1, h2 = l2 + 1.0;
+        const double len = sqrt(h0 * h0 + h1 * h1 + h2 * h2);
+        double nh = 0.0;
+        if (len > 0.0) nh = n[0] * (h0 / len) + n[1] * (h1 / len) + n[2] * (h2 / len);
+        nh = nh > 0.0 ? nh : 0.0;
+        k = p.constant * pow(nh, p.specular_exponent);
+    } else {
+        const double nl = n[0] * l0 + n[1] * l1 + n[2] * l2;
+        k = p.constant * (nl > 0.0 ? nl : 0.0);
+    }
+    double r = k * c0, g = k * c1, b = k * c2;
+    r = r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
+    g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g);
+    b = b < 0.0 ? 0.0 : (b > 1.0 ? 1.0 : b);
+    out[0] = r; out[1] = g; out[2] = b;
+    out[3] = p.specular ? (r > g ? (r > b ? r : b) : (g > b ? g : b)) : 1.0;
+}
+
 }  // namespace svgr

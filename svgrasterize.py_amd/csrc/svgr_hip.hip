@@ -3663,6 +3663,40 @@ __global__ __launch_bounds__(256) void k_layer_displacement_map(double* __restri
     reinterpret_cast<double4*>(out)[i] = v;
 }
 
+// feDiffuseLighting / feSpecularLighting over the region (o0, o1, rows, cols): a 16 x 16 workgroup stages the alpha of its
+// tile and a one-pixel halo (18 x 18 doubles, 2.6 KB) in LDS -- zero outside the source and outside the region, so no input
+// pixel outside the region is read -- then each lane picks its Sobel case from its place in the region and shades through
+// svgr::light_pixel.  One double4 store per pixel; every region pixel is written.
+constexpr int kLightTile = 16;
+struct LightLaunch {
+    svgr::LightParams p;
+    int o0, o1, rows, cols, s0, s1, srows, scols, tiles_x;
+};
+__global__ __launch_bounds__(256) void k_layer_lighting(double* __restrict__ out, const double* __restrict__ src, LightLaunch a) {
+    constexpr int T = kLightTile, H = kLightTile + 2;
+    __shared__ double alpha[H * H];
+    const int tile_r = (int)blockIdx.x / a.tiles_x, tile_c = (int)blockIdx.x % a.tiles_x;
+    const int tid = threadIdx.y * T + threadIdx.x;
+    const int r0 = tile_r * T - 1, c0 = tile_c * T - 1;   // (region coordinates of the halo's first pixel)
+    for (int q = tid; q < H * H; q += T * T) {
+        const int r = r0 + q / H, c = c0 + q % H;
+        const long long sr = (long long)r + a.o0 - a.s0, sc = (long long)c + a.o1 - a.s1;
+        double v = 0.0;
+        if (r >= 0 && r < a.rows && c >= 0 && c < a.cols && sr >= 0 && sr < a.srows && sc >= 0 && sc < a.scols)
+            v = src[((size_t)sr * a.scols + sc) * 4 + 3];
+        alpha[q] = v;
+    }
+    __syncthreads();
+    const int R = tile_r * T + (int)threadIdx.y, C = tile_c * T + (int)threadIdx.x;
+    if (R >= a.rows || C >= a.cols) return;
+    double nb[9];
+    for (int k = 0; k < 3; ++k)
+        for (int j = 0; j < 3; ++j) nb[3 * k + j] = alpha[((int)threadIdx.y + k) * H + (int)threadIdx.x + j];
+    double px[4];
+    svgr::light_pixel(a.p, nb, R == 0, R == a.rows - 1, C == 0, C == a.cols - 1, (double)(a.o0 + R) + 0.5, (double)(a.o1 + C) + 0.5, px);
+    reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(px[0], px[1], px[2], px[3]);
+}
+
 // luminance mask (S:735): out(1 channel) = (rgb @ [0.2125, 0.7154, 0.072]) * alpha of a straight-alpha layer
 __global__ void k_layer_luminance(double* __restrict__ out, const double* __restrict__ src, size_t n_px) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -6626,6 +6660,31 @@ int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out
     a.xc = x_channel; a.yc = y_channel;
     a.l00 = lin4[0]; a.l01 = lin4[1]; a.l10 = lin4[2]; a.l11 = lin4[3]; a.scale = scale;
     return launch_tail(ctx, k_layer_displacement_map, grid1(n), dim3(256), 0, (double*)out->ptr, (const double*)map->ptr,
+                       (const double*)src->ptr, a);
+}
+
+int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
+                        int light_kind, const double* light_params, const double* color3, double surface_scale, double constant,
+                        double specular_exponent, int specular) {
+    if (!ctx || !out || !src || !light_params || !color3 || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || light_kind < svgr::kLightDistant ||
+        light_kind > svgr::kLightSpot || (specular != 0 && specular != 1))
+        return fail(SVGR_E_INVALID, "svgr_layer_lighting: bad arguments (light kind 0..2, specular 0 or 1)");
+    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
+    const size_t tiles = (size_t)((out_bbox[3] + kLightTile - 1) / kLightTile) * (size_t)((out_bbox[2] + kLightTile - 1) / kLightTile);
+    if (tiles > 0x7fffffff) return fail(SVGR_E_INVALID, "svgr_layer_lighting: region too large");
+    if (out->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+        return fail(SVGR_E_INVALID, "svgr_layer_lighting: buffer too small");
+    if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_lighting: out must not be src");
+    if (n == 0) return 0;
+    LightLaunch a;
+    memcpy(a.p.l, light_params, sizeof a.p.l);
+    memcpy(a.p.color, color3, sizeof a.p.color);
+    a.p.surface_scale = surface_scale; a.p.constant = constant; a.p.specular_exponent = specular_exponent;
+    a.p.kind = light_kind; a.p.specular = specular;
+    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
+    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
+    a.tiles_x = (a.cols + kLightTile - 1) / kLightTile;
+    return launch_tail(ctx, k_layer_lighting, dim3((unsigned)tiles), dim3(kLightTile, kLightTile), 0, (double*)out->ptr,
                        (const double*)src->ptr, a);
 }
 

@@ -1,19 +1,22 @@
 """Filter effects (reference S:1716-1944): feGaussianBlur (the one on the hot path) and the other
 primitives the reference implements -- feOffset, feMerge, feBlend, feComposite, feColorMatrix, feMorphology (8f-4) --,
 plus primitives the reference does not have: feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix,
-feDisplacementMap and feDropShadow (expanded into the others by ``Filter.drop_shadow``).
+feDisplacementMap, feDropShadow (expanded into the others by ``Filter.drop_shadow``), feDiffuseLighting and feSpecularLighting
+(with a ``DistantLight``, ``PointLight`` or ``SpotLight``).
 
 ``Filter`` keeps the reference's (names, filters) structure so scene dumps replay unchanged.  The blur weights are
 built on the host exactly like ``blur_kernel`` does (a few thousand numbers); every per-pixel operation runs on the
 GPU (``svgr_layer_convolve``, ``svgr_layer_blend``, ``svgr_layer_color_matrix``, ``svgr_layer_morphology``,
-``svgr_layer_turbulence``, ``svgr_layer_component_transfer``, ``svgr_layer_convolve_matrix``, ``svgr_layer_displacement_map``).
+``svgr_layer_turbulence``, ``svgr_layer_component_transfer``, ``svgr_layer_convolve_matrix``, ``svgr_layer_displacement_map``,
+``svgr_layer_lighting``).
 
 The chain runs in linearRGB (``color-interpolation-filters`` is ignored, as in the reference).  The generators (feFlood,
-feTurbulence) cover the filter region: the ``<filter>``'s x / y / width / height in ``filterUnits`` (default
+feTurbulence) and the lighting primitives cover the filter region: the ``<filter>``'s x / y / width / height in ``filterUnits`` (default
 objectBoundingBox, -10% / -10% / 120% / 120%), resolved at call time against the hull's bounding box in user space (or the
 source layer's extent when there is no hull) and rounded out to whole device pixels.  The other primitives keep the extent
 of their input; in particular feComponentTransfer leaves the pixels outside its input transparent even where feFuncA maps
-0 to something else.  Primitive subregions and ``primitiveUnits`` are not supported."""
+0 to something else.  Light sources stay in user space in the chain and are mapped to device space at call time
+(``Layer.lighting``).  Primitive subregions and ``primitiveUnits`` are not supported."""
 from __future__ import annotations
 
 import math
@@ -88,6 +91,31 @@ def filter_region(region, transform: Transform, source: Layer, hull=None):
     lo, hi = np.floor(corners.min(axis=0)), np.ceil(corners.max(axis=0))
     shape = (max(int(hi[0] - lo[0]), 1), max(int(hi[1] - lo[1]), 1))
     return (int(lo[0]), int(lo[1])), shape, (x, y, w, h)
+
+
+class DistantLight(NamedTuple):
+    """feDistantLight: direction angles in degrees, user space."""
+    azimuth: float = 0.0
+    elevation: float = 0.0
+
+
+class PointLight(NamedTuple):
+    """fePointLight: position in user space (z in user units)."""
+    x: float = 0.0
+    y: float = 0.0
+    z: float = 0.0
+
+
+class SpotLight(NamedTuple):
+    """feSpotLight: position and pointsAt in user space; `limiting_cone_angle` in degrees, None = no cone."""
+    x: float = 0.0
+    y: float = 0.0
+    z: float = 0.0
+    points_at_x: float = 0.0
+    points_at_y: float = 0.0
+    points_at_z: float = 0.0
+    specular_exponent: float = 1.0
+    limiting_cone_angle: float | None = None
 
 
 FE_SOURCE_ALPHA = "SourceAlpha"
@@ -202,6 +230,18 @@ class Filter(NamedTuple):
     def displacement_map(self, in1, in2, scale=0.0, x_channel="A", y_channel="A", result=None) -> "Filter":
         return self.add_filter(FE_DISPLACEMENT_MAP, (scale, x_channel, y_channel), [in1, in2], result)
 
+    def diffuse_lighting(self, input, light, color=(1.0, 1.0, 1.0), surface_scale=1.0, diffuse_constant=1.0, region=None,
+                         result=None) -> "Filter":
+        """feDiffuseLighting: `light` a DistantLight / PointLight / SpotLight, `color` linear RGB; covers the filter region."""
+        return self.add_filter(FE_DIFFUSE_LIGHTING, (light, tuple(float(c) for c in color), float(surface_scale),
+                                                     float(diffuse_constant), region), [input], result)
+
+    def specular_lighting(self, input, light, color=(1.0, 1.0, 1.0), surface_scale=1.0, specular_constant=1.0,
+                          specular_exponent=1.0, region=None, result=None) -> "Filter":
+        """feSpecularLighting (premultiplied result), otherwise as ``diffuse_lighting``."""
+        return self.add_filter(FE_SPECULAR_LIGHTING, (light, tuple(float(c) for c in color), float(surface_scale),
+                                                      float(specular_constant), float(specular_exponent), region), [input], result)
+
     def drop_shadow(self, dx=2.0, dy=2.0, std_x=2.0, std_y=None, color=(0.0, 0.0, 0.0, 1.0), region=None, input=None,
                     result=None) -> "Filter":
         """feDropShadow as the six entries it stands for: the alpha of `input`, blurred, offset, a flood of `color` IN that
@@ -277,6 +317,14 @@ class Filter(NamedTuple):
             elif ftype == FE_DISPLACEMENT_MAP:
                 scale, x_channel, y_channel = attrs
                 res = args[0].displacement_map(args[1], transform, scale, x_channel, y_channel)
+            elif ftype == FE_DIFFUSE_LIGHTING:
+                light, color, surface_scale, constant, region = attrs
+                offset, shape, _ = filter_region(region, transform, source, hull)
+                res = args[0].lighting(transform, offset, shape, light, color, surface_scale, constant)
+            elif ftype == FE_SPECULAR_LIGHTING:
+                light, color, surface_scale, constant, exponent, region = attrs
+                offset, shape, _ = filter_region(region, transform, source, hull)
+                res = args[0].lighting(transform, offset, shape, light, color, surface_scale, constant, exponent)
             else:
                 raise ValueError(f"unsupported filter type: {ftype}")
             stack.append(res)

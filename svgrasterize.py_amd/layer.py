@@ -16,6 +16,7 @@ from typing import Sequence
 import warnings
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -28,6 +29,7 @@ FLOAT = np.float64
 TRANSFER_TYPES = {"identity": 0, "table": 1, "discrete": 2, "linear": 3, "gamma": 4}
 EDGE_MODES = {"duplicate": 0, "wrap": 1, "none": 2}
 CHANNELS = {"R": 0, "G": 1, "B": 2, "A": 3}
+LIGHT_DISTANT, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2   # svgr_layer_lighting's light kinds
 _TURB_M = 2147483647
 
 
@@ -40,6 +42,41 @@ def turbulence_seed(seed) -> int:
     if s <= 0:
         return -((-s) % (_TURB_M - 1))   # (C's `s % (m - 1)` of a negative s)
     return s
+
+
+def light_frame(transform, light):
+    """(kind, params) of svgr_layer_lighting: `light` (filters.DistantLight / PointLight / SpotLight, user space) in the device
+    frame (d0, d1, z).  A point (x, y, z) goes to (transform(x, y), z s), s = sqrt(|det M|) of the linear part M; a distant light
+    to (v / |v| cos(elevation), sin(elevation)), v = M (cos(azimuth), sin(azimuth)).  Exact for similarity transforms, an
+    approximation under anisotropic ones."""
+    from .filters import DistantLight, PointLight, SpotLight
+
+    lin = np.asarray(transform.m, dtype=FLOAT)[:2, :2]
+    scale = math.sqrt(abs(lin[0, 0] * lin[1, 1] - lin[0, 1] * lin[1, 0]))
+    params = np.zeros(8, dtype=FLOAT)
+    if isinstance(light, DistantLight):
+        az, el = math.radians(float(light.azimuth)), math.radians(float(light.elevation))
+        v = lin @ np.array([math.cos(az), math.sin(az)])
+        norm = math.sqrt(v[0] * v[0] + v[1] * v[1])
+        if norm > 0:
+            params[0:2] = v / norm * math.cos(el)
+        params[2] = math.sin(el)
+        return LIGHT_DISTANT, params
+    if not isinstance(light, (PointLight, SpotLight)):
+        raise ValueError(f"unknown light source: {light!r}")
+    params[0:2] = transform(np.array([float(light.x), float(light.y)]))
+    params[2] = float(light.z) * scale
+    if isinstance(light, PointLight):
+        return LIGHT_POINT, params
+    at = np.array([*transform(np.array([float(light.points_at_x), float(light.points_at_y)])), float(light.points_at_z) * scale])
+    d = at - params[0:3]
+    norm = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    if norm > 0:
+        params[3:6] = d / norm
+    params[6] = float(light.specular_exponent)
+    cone = light.limiting_cone_angle
+    params[7] = -1.0 if cone is None else math.cos(math.radians(abs(float(cone))))
+    return LIGHT_SPOT, params
 
 
 def _bbox_arr(offset, shape):
@@ -416,6 +453,28 @@ class Layer:
                                                         s_buf.handle, _bbox_arr(src.offset, src._shape), _abi.ptr(lin), float(scale),
                                                         CHANNELS[x_channel], CHANNELS[y_channel]))
         return Layer._from_device(out, disp._shape, disp.offset, pre_alpha=True, linear_rgb=True)
+
+    def lighting(self, transform, offset, shape, light, color, surface_scale: float, constant: float,
+                 specular_exponent=None) -> "Layer":
+        """feDiffuseLighting (`specular_exponent` None) or feSpecularLighting over the (rows, cols) region at `offset`, lit by
+        `light` (``light_frame``) in `color` (linear RGB).  The surface is this layer's alpha times `surface_scale` in device
+        pixels, 0 outside this layer.  Diffuse is opaque; specular is premultiplied (alpha = its largest colour channel)."""
+        if self.channels != 4:
+            raise ValueError("lighting expects an RGBA layer")
+        rows, cols = int(shape[0]), int(shape[1])
+        offset = (int(offset[0]), int(offset[1]))
+        kind, params = light_frame(transform, light)
+        rgb = np.ascontiguousarray(color, dtype=FLOAT).reshape(3)
+        specular = specular_exponent is not None
+        ctx = _abi.Context.get()
+        out = ctx.alloc(max(rows * cols, 1) * 32)
+        # only alpha is read, and no noted conversion changes alpha: the pixels as they are
+        src = self._dev if self._host is None else self._device()
+        _abi._check(ctx.lib.svgr_layer_lighting(ctx.handle, out.handle, _bbox_arr(offset, (rows, cols)), src.handle,
+                                                _bbox_arr(self.offset, self._shape), kind, _abi.ptr(params), _abi.ptr(rgb),
+                                                float(surface_scale), float(constant),
+                                                float(specular_exponent) if specular else 1.0, int(specular)))
+        return Layer._from_device(out, (rows, cols, 4), offset, pre_alpha=specular, linear_rgb=True)
 
     # -- Layer.compose  S:177-207 ----------------------------------------------------------
     @staticmethod

@@ -9,7 +9,8 @@ exactly like the scene dumps extracted from the reference (``tests/test_svg_load
 Supported: svg (nested, viewBox), g, defs, path, rect, circle, ellipse, line, polyline, polygon, use,
 linearGradient / radialGradient / stop, pattern, clipPath, mask, filter (feOffset, feGaussianBlur, feMerge, feBlend, feComposite,
 feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, and beyond the reference feFlood, feTurbulence,
-feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow; the <filter>'s region for the generators), text / tspan set in
+feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow, feDiffuseLighting, feSpecularLighting with feDistantLight /
+fePointLight / feSpotLight; the <filter>'s region for the generators and the lighting primitives), text / tspan set in
 SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``, and beyond the
 reference image (PNG, from a ``data:image/png;base64`` URI or a local file next to the document; ``png.py``).
 Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
@@ -30,8 +31,8 @@ import xml.etree.ElementTree as etree
 import numpy as np
 
 from .filters import (
-    COLOR_MATRIX_LUM, CONVOLVE_MATRIX_MAX_ORDER, TRANSFER_MAX_VALUES, TURBULENCE_MAX_OCTAVES, Filter, color_matrix_hue_rotate,
-    color_matrix_saturate,
+    COLOR_MATRIX_LUM, CONVOLVE_MATRIX_MAX_ORDER, TRANSFER_MAX_VALUES, TURBULENCE_MAX_OCTAVES, DistantLight, Filter, PointLight,
+    SpotLight, color_matrix_hue_rotate, color_matrix_saturate,
 )
 from .fonts import FONT_STYLE_NORMAL, Font, FontsDB, Glyph
 from .geometry import (
@@ -437,9 +438,57 @@ def _convolve_matrix_args(attrs):
     return kernel, divisor, parse_float(attrs.get("bias", "0")), (tx, ty), edge_mode, attrs.get("preserveAlpha") == "true"
 
 
+def _light_source(element):
+    """The first feDistantLight / fePointLight / feSpotLight child as a filters light tuple (user space); None without one."""
+    for child in element:
+        tag, attrs = child.tag.split("}")[-1], child.attrib
+
+        def num(key, default="0"):
+            return parse_float(attrs.get(key, default))
+
+        if tag == "feDistantLight":
+            return DistantLight(num("azimuth"), num("elevation"))
+        if tag == "fePointLight":
+            return PointLight(num("x"), num("y"), num("z"))
+        if tag == "feSpotLight":
+            cone = attrs.get("limitingConeAngle")
+            return SpotLight(num("x"), num("y"), num("z"), num("pointsAtX"), num("pointsAtY"), num("pointsAtZ"),
+                             num("specularExponent", "1"), None if cone is None else parse_float(cone))
+    return None
+
+
+def _lighting_args(element, tag):
+    """feDiffuseLighting / feSpecularLighting -> (light, linear RGB colour, surfaceScale, constant, specularExponent or None);
+    None (+ warning) without a light source, with a negative constant or an invalid lighting-color."""
+    attrs = _expand_style(element.attrib)
+    light = _light_source(element)
+    if light is None:
+        warnings.warn(f"{tag} without a light source")
+        return None
+    specular = tag == "feSpecularLighting"
+    name = "specularConstant" if specular else "diffuseConstant"
+    constant = parse_float(attrs.get(name, "1"))
+    if constant < 0:
+        warnings.warn(f"{tag}: negative {name}: {constant}")
+        return None
+    color = parse_color(attrs.get("lighting-color", "white").strip())
+    if color is None:
+        return None
+    rgb = color[:3] / color[3] if color[3] > 0 else np.zeros(3)   # (as _flood_color; the alpha is ignored)
+    exponent = None
+    if specular:
+        exponent = parse_float(attrs.get("specularExponent", "1"))
+        if not 1.0 <= exponent <= 128.0:
+            warnings.warn(f"specularExponent outside [1, 128] clamped: {exponent}")
+            exponent = min(max(exponent, 1.0), 128.0)
+    if attrs.get("kernelUnitLength") is not None:
+        warnings.warn("kernelUnitLength is not supported: one Sobel cell is one device pixel")
+    return light, tuple(rgb), parse_float(attrs.get("surfaceScale", "1")), constant, exponent
+
+
 def _filter(element) -> Filter:
-    """<filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap
-    and feDropShadow beyond the reference)."""
+    """<filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap,
+    feDropShadow, feDiffuseLighting and feSpecularLighting beyond the reference)."""
     flt = Filter.empty()
     region = _filter_region(element.attrib)
     for child in element:
@@ -487,6 +536,14 @@ def _filter(element) -> Filter:
             if color is not None:
                 flt = flt.drop_shadow(parse_float(attrs.get("dx", "2")), parse_float(attrs.get("dy", "2")), std_x, std_y, color,
                                       region, src, result)
+        elif tag in ("feDiffuseLighting", "feSpecularLighting"):
+            args = _lighting_args(child, tag)
+            if args is not None:
+                light, color, surface_scale, constant, exponent = args
+                if exponent is None:
+                    flt = flt.diffuse_lighting(src, light, color, surface_scale, constant, region, result)
+                else:
+                    flt = flt.specular_lighting(src, light, color, surface_scale, constant, exponent, region, result)
         elif tag == "feOffset":
             flt = flt.offset(parse_float(attrs.get("dx", "0")), parse_float(attrs.get("dy", "0")), src, result)
         elif tag == "feGaussianBlur":
