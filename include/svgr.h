@@ -40,7 +40,7 @@ extern "C" {
  * 6 (later, nothing changed or removed): svgr_layer_turbulence, svgr_layer_component_transfer, svgr_layer_convolve_matrix,
  *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
  *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
- *    feSpecularLighting) */
+ *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -363,6 +363,32 @@ int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out
 int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
                         int light_kind, const double* light_params, const double* color3, double surface_scale, double constant,
                         double specular_exponent, int specular);
+/* mix-blend-mode (W3C Compositing and Blending Level 1, section 5): the source src (src_bbox, src_channels 1 or 4) blended over
+ * the backdrop (backdrop_bbox, backdrop_channels 1 or 4), both premultiplied, zero outside their boxes; a single channel is alpha
+ * broadcast to all four.  Per pixel (svgr_core.h: mix_blend_px), Cb = cb / ab and Cs = cs / as (0 where the alpha is 0):
+ *   co = cs (1 - ab) + cb (1 - as) + as ab B(Cb, Cs),  ao = as + ab (1 - as);
+ * SVGR_BLEND_NORMAL is source-over, co = cs + cb (1 - as), bit for bit svgr_layer_compose_over of the two.
+ * Out of place (backdrop is not out): every pixel of out (out_bbox, RGBA) is written.  In place (backdrop is out: 4 channels and
+ * out_bbox): only the pixels under the source are read and written, the others keep the backdrop (which is what the formula
+ * gives where as = 0).  src must not be out.  An unknown mode or a bad box is SVGR_E_INVALID.                                   */
+#define SVGR_BLEND_NORMAL 0
+#define SVGR_BLEND_MULTIPLY 1
+#define SVGR_BLEND_SCREEN 2
+#define SVGR_BLEND_OVERLAY 3
+#define SVGR_BLEND_DARKEN 4
+#define SVGR_BLEND_LIGHTEN 5
+#define SVGR_BLEND_COLOR_DODGE 6
+#define SVGR_BLEND_COLOR_BURN 7
+#define SVGR_BLEND_HARD_LIGHT 8
+#define SVGR_BLEND_SOFT_LIGHT 9
+#define SVGR_BLEND_DIFFERENCE 10
+#define SVGR_BLEND_EXCLUSION 11
+#define SVGR_BLEND_HUE 12         /* 12..15 non-separable: Lum / ClipColor / SetLum / Sat / SetSat, weights 0.3 / 0.59 / 0.11 */
+#define SVGR_BLEND_SATURATION 13
+#define SVGR_BLEND_COLOR 14
+#define SVGR_BLEND_LUMINOSITY 15
+int svgr_layer_mix_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* backdrop, const int64_t* backdrop_bbox,
+                         int backdrop_channels, const svgr_buf* src, const int64_t* src_bbox, int src_channels, int mode);
 /* Luminance of a straight-alpha RGBA image for RENDER_MASK (S:735): out(n_px doubles) = (rgb . {0.2125, 0.7154, 0.072}) * a */
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out_1ch, const svgr_buf* src_rgba, int64_t n_px);
 

@@ -14,6 +14,7 @@ from .geometry import (  # noqa: F401
 from .layer import (  # noqa: F401
     Layer, canvas_to_png, canvas_create, canvas_compose, canvas_merge_at, canvas_merge_union, canvas_merge_intersect,
     CANVAS_COMPOSE_OVER, COMPOSE_OVER, COMPOSE_OUT, COMPOSE_IN, COMPOSE_ATOP, COMPOSE_XOR,
+    BLEND_MODES,
 )
 from .paint import GradLinear, GradRadial, ImagePaint, Pattern  # noqa: F401
 from .png import read_png  # noqa: F401
@@ -23,7 +24,7 @@ from .filters import (  # noqa: F401
 )
 from .scene import (  # noqa: F401
     Scene, render_canvas, build_batch, clear_render_cache, set_render_cache,
-    RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER,
+    RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER, RENDER_BLEND,
 )
 from .fonts import Font, FontsDB, Glyph  # noqa: F401
 from .svg import render_svg, svg_scene, svg_scene_from_filepath, svg_scene_from_str  # noqa: F401

@@ -698,4 +698,121 @@ SVGR_HD void light_pixel(const LightParams& p, const double* a, int top, int bot
     out[3] = p.specular ? (r > g ? (r > b ? r : b) : (g > b ? g : b)) : 1.0;
 }
 
+// ------------------------------------------------------------------------------------
+// mix-blend-mode (W3C Compositing and Blending Level 1, sections 5.1-5.9): one pixel of a premultiplied source over a
+// premultiplied backdrop.  Modes in the spec's order (SVGR_BLEND_*, include/svgr.h); 0..11 separable, 12..15 not.
+// With Cb = cb / ab and Cs = cs / as (0 where the alpha is 0):
+//   co = cs (1 - ab) + cb (1 - as) + as ab B(Cb, Cs),  ao = as + ab (1 - as)
+// Normal is computed as source-over, co = cs + cb (1 - as) (over_px's expression): the same value in exact arithmetic,
+// and bit for bit what Layer.compose(OVER) gives.
+// ------------------------------------------------------------------------------------
+enum {
+    kBlendNormal = 0, kBlendMultiply, kBlendScreen, kBlendOverlay, kBlendDarken, kBlendLighten, kBlendColorDodge,
+    kBlendColorBurn, kBlendHardLight, kBlendSoftLight, kBlendDifference, kBlendExclusion,
+    kBlendHue, kBlendSaturation, kBlendColor, kBlendLuminosity, kBlendModes
+};
+
+// B(Cb, Cs) of a separable mode, one channel
+SVGR_HD double blend_sep(int mode, double b, double s) {
+    switch (mode) {
+        case kBlendMultiply: return b * s;
+        case kBlendScreen: return b + s - b * s;
+        case kBlendOverlay: {   // HardLight(Cs, Cb): the roles swapped
+            const double b2 = 2.0 * b;
+            return b <= 0.5 ? s * b2 : s + (b2 - 1.0) - s * (b2 - 1.0);
+        }
+        case kBlendDarken: return b < s ? b : s;
+        case kBlendLighten: return b > s ? b : s;
+        case kBlendColorDodge: {
+            if (b == 0.0) return 0.0;
+            if (s == 1.0) return 1.0;
+            const double q = b / (1.0 - s);
+            return q < 1.0 ? q : 1.0;
+        }
+        case kBlendColorBurn: {
+            if (b == 1.0) return 1.0;
+            if (s == 0.0) return 0.0;
+            const double q = (1.0 - b) / s;
+            return 1.0 - (q < 1.0 ? q : 1.0);
+        }
+        case kBlendHardLight: {
+            const double s2 = 2.0 * s;
+            return s <= 0.5 ? b * s2 : b + (s2 - 1.0) - b * (s2 - 1.0);
+        }
+        case kBlendSoftLight: {
+            if (s <= 0.5) return b - (1.0 - 2.0 * s) * b * (1.0 - b);
+            const double d = b <= 0.25 ? ((16.0 * b - 12.0) * b + 4.0) * b : sqrt(b);
+            return b + (2.0 * s - 1.0) * (d - b);
+        }
+        case kBlendDifference: return b > s ? b - s : s - b;
+        case kBlendExclusion: return b + s - 2.0 * b * s;
+        default: return s;   // (normal)
+    }
+}
+
+SVGR_HD double blend_lum(const double* c) { return 0.3 * c[0] + 0.59 * c[1] + 0.11 * c[2]; }
+
+// SetLum(c, l) = ClipColor(c + (l - Lum(c))), in place.  ClipColor's divisions are skipped when their divisor is not positive
+// (every channel equal to the luminance: nothing to clip towards it).
+SVGR_HD void blend_set_lum(double* c, double l) {
+    const double d = l - blend_lum(c);
+    c[0] = c[0] + d; c[1] = c[1] + d; c[2] = c[2] + d;
+    const double L = blend_lum(c);
+    const double n = fmin(fmin(c[0], c[1]), c[2]), x = fmax(fmax(c[0], c[1]), c[2]);
+    if (n < 0.0 && L - n > 0.0)
+        for (int k = 0; k < 3; ++k) c[k] = L + ((c[k] - L) * L) / (L - n);
+    if (x > 1.0 && x - L > 0.0)
+        for (int k = 0; k < 3; ++k) c[k] = L + ((c[k] - L) * (1.0 - L)) / (x - L);
+}
+
+// SetSat(c, s), in place: the largest channel becomes s, the smallest 0, the middle one (Cmid - Cmin) s / (Cmax - Cmin); all 0
+// when Cmax = Cmin.  Ties take the same value (two largest: both s; two smallest: both 0), whichever the spec's sort put first.
+SVGR_HD void blend_set_sat(double* c, double s) {
+    const double n = fmin(fmin(c[0], c[1]), c[2]), x = fmax(fmax(c[0], c[1]), c[2]);
+    for (int k = 0; k < 3; ++k) {
+        if (x <= n) c[k] = 0.0;
+        else if (c[k] == x) c[k] = s;
+        else if (c[k] == n) c[k] = 0.0;
+        else c[k] = ((c[k] - n) * s) / (x - n);
+    }
+}
+
+// B(Cb, Cs) of a non-separable mode: hue SetLum(SetSat(Cs, Sat(Cb)), Lum(Cb)), saturation SetLum(SetSat(Cb, Sat(Cs)), Lum(Cb)),
+// color SetLum(Cs, Lum(Cb)), luminosity SetLum(Cb, Lum(Cs))
+SVGR_HD void blend_nonsep(int mode, const double* b, const double* s, double* out) {
+    double t[3];
+    if (mode == kBlendHue || mode == kBlendColor) { t[0] = s[0]; t[1] = s[1]; t[2] = s[2]; }
+    else { t[0] = b[0]; t[1] = b[1]; t[2] = b[2]; }
+    if (mode == kBlendHue || mode == kBlendSaturation) {
+        const double* f = mode == kBlendHue ? b : s;   // (the colour whose saturation is taken)
+        blend_set_sat(t, fmax(fmax(f[0], f[1]), f[2]) - fmin(fmin(f[0], f[1]), f[2]));
+    }
+    blend_set_lum(t, blend_lum(mode == kBlendLuminosity ? s : b));
+    out[0] = t[0]; out[1] = t[1]; out[2] = t[2];
+}
+
+// One pixel, premultiplied in and out: d = the backdrop {cb, ab}, replaced by the result; s = the source.  `mode` is uniform
+// over a launch: the kernel instantiates this per family (template parameter) and passes a constant.
+SVGR_HD void mix_blend_px(int mode, double* d, const double* s) {
+    const double ab = d[3], as = s[3];
+    const double ka = 1.0 - as;
+    if (mode == kBlendNormal) {
+        d[0] = s[0] + d[0] * ka; d[1] = s[1] + d[1] * ka; d[2] = s[2] + d[2] * ka; d[3] = as + ab * ka;
+        return;
+    }
+    double Cb[3], Cs[3], B[3];
+    for (int k = 0; k < 3; ++k) {
+        Cb[k] = ab > 0.0 ? d[k] / ab : 0.0;
+        Cs[k] = as > 0.0 ? s[k] / as : 0.0;
+    }
+    if (mode >= kBlendHue) {
+        blend_nonsep(mode, Cb, Cs, B);
+    } else {
+        for (int k = 0; k < 3; ++k) B[k] = blend_sep(mode, Cb[k], Cs[k]);
+    }
+    const double kb = 1.0 - ab, w = as * ab;
+    for (int k = 0; k < 3; ++k) d[k] = (s[k] * kb + d[k] * ka) + w * B[k];
+    d[3] = as + ab * ka;
+}
+
 }  // namespace svgr

@@ -50,6 +50,7 @@
 #include <vector>
 #include <memory>
 #include <unordered_map>
+#include <utility>
 
 #include "../../include/svgr.h"
 #include "svgr_core.h"
@@ -3697,6 +3698,54 @@ __global__ __launch_bounds__(256) void k_layer_lighting(double* __restrict__ out
     reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(px[0], px[1], px[2], px[3]);
 }
 
+// mix-blend-mode (svgr::mix_blend_px): every pixel of the window (device rows w0.., columns w1..; inside out's box) gets the
+// backdrop (zero outside its box), blended with the source where the source covers it.  Out of place the window is out's whole
+// box; in place (out is the backdrop) it is the source's box, and what lies outside it is left as it is.  A 1-channel layer is
+// alpha broadcast to all four.  Mode is a template parameter: each instantiation folds its mode's branches away.  One lane per
+// pixel, 16-byte loads and stores (two double2 per RGBA pixel).  out and backdrop may be one buffer: each lane reads its
+// pixel before it writes it.
+struct MixBlendLaunch {
+    int o0, o1, ocols;                  // out's box (rows are not needed: the window lies inside)
+    int b0, b1, brows, bcols, bch;      // backdrop
+    int s0, s1, srows, scols, sch;      // source
+    int w0, w1, wcols;                  // the window's first device row / column and its width
+    size_t n;                           // pixels in the window
+};
+__device__ __forceinline__ void load_px(const double* p, int ch, size_t at, double* v) {
+    if (ch == 4) {
+        const double2* q = reinterpret_cast<const double2*>(p) + 2 * at;
+        const double2 lo = q[0], hi = q[1];
+        v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+    } else {
+        v[0] = v[1] = v[2] = v[3] = p[at];
+    }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_layer_mix_blend(double* out, const double* backdrop, const double* __restrict__ src,
+                                                         MixBlendLaunch a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const int R = a.w0 + (int)(i / (size_t)a.wcols), C = a.w1 + (int)(i % (size_t)a.wcols);
+    double d[4] = {0.0, 0.0, 0.0, 0.0};
+    const int br = R - a.b0, bc = C - a.b1;
+    if (br >= 0 && br < a.brows && bc >= 0 && bc < a.bcols) load_px(backdrop, a.bch, (size_t)br * a.bcols + bc, d);
+    const int sr = R - a.s0, sc = C - a.s1;
+    if (sr >= 0 && sr < a.srows && sc >= 0 && sc < a.scols) {
+        double s[4];
+        load_px(src, a.sch, (size_t)sr * a.scols + sc, s);
+        svgr::mix_blend_px(MODE, d, s);
+    }
+    double2* o = reinterpret_cast<double2*>(out) + 2 * ((size_t)(R - a.o0) * a.ocols + (C - a.o1));
+    o[0] = make_double2(d[0], d[1]);
+    o[1] = make_double2(d[2], d[3]);
+}
+template <int... M>
+static decltype(&k_layer_mix_blend<0>) mix_blend_kernel(int mode, std::integer_sequence<int, M...>) {
+    decltype(&k_layer_mix_blend<0>) k = nullptr;
+    ((k = mode == M ? &k_layer_mix_blend<M> : k), ...);
+    return k;
+}
+
 // luminance mask (S:735): out(1 channel) = (rgb @ [0.2125, 0.7154, 0.072]) * alpha of a straight-alpha layer
 __global__ void k_layer_luminance(double* __restrict__ out, const double* __restrict__ src, size_t n_px) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -6686,6 +6735,30 @@ int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, c
     a.tiles_x = (a.cols + kLightTile - 1) / kLightTile;
     return launch_tail(ctx, k_layer_lighting, dim3((unsigned)tiles), dim3(kLightTile, kLightTile), 0, (double*)out->ptr,
                        (const double*)src->ptr, a);
+}
+
+int svgr_layer_mix_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* backdrop, const int64_t* bb, int bch,
+                         const svgr_buf* src, const int64_t* sb, int sch, int mode) {
+    if (mode < svgr::kBlendNormal || mode >= svgr::kBlendModes) return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: unknown mode %d", mode);
+    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, src, sb, sch)) return rc;
+    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, backdrop, bb, bch)) return rc;
+    if (src->ptr == out->ptr) return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: out must not be the source");
+    const bool in_place = backdrop->ptr == out->ptr;
+    if (in_place && (bch != 4 || bb[0] != ob[0] || bb[1] != ob[1] || bb[2] != ob[2] || bb[3] != ob[3]))
+        return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: in place, the backdrop is out (4 channels, the same box)");
+    MixBlendLaunch a;
+    a.o0 = (int)ob[0]; a.o1 = (int)ob[1]; a.ocols = (int)ob[3];
+    a.b0 = (int)bb[0]; a.b1 = (int)bb[1]; a.brows = (int)bb[2]; a.bcols = (int)bb[3]; a.bch = bch;
+    a.s0 = (int)sb[0]; a.s1 = (int)sb[1]; a.srows = (int)sb[2]; a.scols = (int)sb[3]; a.sch = sch;
+    int64_t w0 = ob[0], w1 = ob[1], w2 = ob[0] + ob[2], w3 = ob[1] + ob[3];
+    if (in_place) {   // (only the pixels under the source change: the window is the source's box, clipped to out's)
+        w0 = std::max(w0, sb[0]); w1 = std::max(w1, sb[1]); w2 = std::min(w2, sb[0] + sb[2]); w3 = std::min(w3, sb[1] + sb[3]);
+    }
+    if (w2 <= w0 || w3 <= w1) return 0;
+    a.w0 = (int)w0; a.w1 = (int)w1; a.wcols = (int)(w3 - w1);
+    a.n = (size_t)(w2 - w0) * (size_t)(w3 - w1);
+    return launch_tail(ctx, mix_blend_kernel(mode, std::make_integer_sequence<int, svgr::kBlendModes>{}), grid1(a.n), dim3(256), 0,
+                       (double*)out->ptr, (const double*)backdrop->ptr, (const double*)src->ptr, a);
 }
 
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t n_px) {

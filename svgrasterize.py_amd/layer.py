@@ -30,6 +30,14 @@ TRANSFER_TYPES = {"identity": 0, "table": 1, "discrete": 2, "linear": 3, "gamma"
 EDGE_MODES = {"duplicate": 0, "wrap": 1, "none": 2}
 CHANNELS = {"R": 0, "G": 1, "B": 2, "A": 3}
 LIGHT_DISTANT, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2   # svgr_layer_lighting's light kinds
+# mix-blend-mode codes of svgr_layer_mix_blend (SVGR_BLEND_*), in the order of Compositing and Blending Level 1
+(BLEND_NORMAL, BLEND_MULTIPLY, BLEND_SCREEN, BLEND_OVERLAY, BLEND_DARKEN, BLEND_LIGHTEN, BLEND_COLOR_DODGE, BLEND_COLOR_BURN,
+ BLEND_HARD_LIGHT, BLEND_SOFT_LIGHT, BLEND_DIFFERENCE, BLEND_EXCLUSION, BLEND_HUE, BLEND_SATURATION, BLEND_COLOR,
+ BLEND_LUMINOSITY) = range(16)
+BLEND_MODES = {name: code for code, name in enumerate((
+    "normal", "multiply", "screen", "overlay", "darken", "lighten", "color-dodge", "color-burn", "hard-light", "soft-light",
+    "difference", "exclusion", "hue", "saturation", "color", "luminosity"))}
+BLEND_NAMES = {code: name for name, code in BLEND_MODES.items()}
 _TURB_M = 2147483647
 
 
@@ -550,6 +558,43 @@ class Layer:
         _abi._check(lib.svgr_layer_compose_in(ctx.handle, out.handle, _bbox_arr((r0, c0), shape), n, handles, bbs, chs, ops))
         offset = (max(l.x for l in conv), max(l.y for l in conv))
         return Layer._from_device(out, shape, offset, True, linear_rgb)
+
+    @staticmethod
+    def mix_blend(backdrop: "Layer | None", source: "Layer | None", mode: int, linear_rgb: bool = False, *,
+                  reuse_backdrop: bool = False) -> "Layer | None":
+        """`source` blended over `backdrop` with the mix-blend-mode `mode` (``BLEND_*``), both converted to premultiplied in the
+        requested colour space as `compose` converts them; the result covers the union of their extents.  With either input
+        None the other is returned as it is.  `reuse_backdrop`: the caller owns the backdrop's pixels and drops the backdrop
+        (a result made for this blend), so when the source lies inside it the blend runs in place over the source's
+        rectangle alone; otherwise a fresh layer is written in one pass over the union."""
+        if backdrop is None:
+            return source
+        if source is None:
+            return backdrop
+        mode = int(mode)
+        if mode not in BLEND_NAMES:
+            raise ValueError(f"invalid blend mode: {mode}")
+        b = backdrop.convert(pre_alpha=True, linear_rgb=linear_rgb)
+        s = source.convert(pre_alpha=True, linear_rgb=linear_rgb)
+        ctx = _abi.Context.get()
+        # (an upload, or a conversion noted on the converted copy alone, is run into a fresh buffer by _device(); an unconverted
+        #  layer's buffer is the caller's)
+        fresh = reuse_backdrop or b._host is not None or (b is not backdrop and b._ops != 0)
+        bdev = b._device()
+        sdev = s._device()
+        bbb, sbb = _bbox_arr(b.offset, b._shape), _bbox_arr(s.offset, s._shape)
+        inside = (b.channels == 4 and b.x <= s.x and b.y <= s.y and s.x + s.height <= b.x + b.height and
+                  s.y + s.width <= b.y + b.width)
+        if fresh and inside:
+            _abi._check(ctx.lib.svgr_layer_mix_blend(ctx.handle, bdev.handle, bbb, bdev.handle, bbb, 4, sdev.handle, sbb,
+                                                     s.channels, mode))
+            return Layer._from_device(bdev, b._shape, b.offset, True, linear_rgb)
+        r0, c0 = min(b.x, s.x), min(b.y, s.y)
+        shape = (max(b.x + b.height, s.x + s.height) - r0, max(b.y + b.width, s.y + s.width) - c0, 4)
+        out = ctx.alloc(shape[0] * shape[1] * 32)
+        _abi._check(ctx.lib.svgr_layer_mix_blend(ctx.handle, out.handle, _bbox_arr((r0, c0), shape), bdev.handle, bbb, b.channels,
+                                                 sdev.handle, sbb, s.channels, mode))
+        return Layer._from_device(out, shape, (r0, c0), True, linear_rgb)
 
     def on_canvas(self, rows: int, cols: int) -> "Layer":
         """This layer merged onto a transparent (rows, cols) canvas at the origin and clipped to [0, 1]: the

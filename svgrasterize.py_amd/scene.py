@@ -10,7 +10,7 @@ routes, both of them HIP:
   target are single paths (clip source + clipped entry), and a CLIP or an OPACITY over a GROUP of plain
   leaves (an isolated group: its members composite into a group tile on the device, which is clipped /
   faded as a whole, ``svgr_batch_set_groups``).
-* per node: everything else (gradient, pattern and image fills, filters, masks, isolated groups that are not flat)
+* per node: everything else (gradient, pattern and image fills, filters, masks, blend modes, isolated groups that are not flat)
   is rendered node by node into device-resident Layers and merged with ``Layer.compose`` exactly as the
   reference does.
 
@@ -27,11 +27,12 @@ import numpy as np
 from . import _abi
 from ._state import RENDER_LOCK, STATE, next_serial
 from .geometry import ConvexHull, Path, Transform, solid_paint, _RULES, FLATNESS
-from .layer import COMPOSE_IN, COMPOSE_OVER, Layer
+from .layer import BLEND_MODES, BLEND_NAMES, BLEND_NORMAL, COMPOSE_IN, COMPOSE_OVER, Layer
 from .paint import _SPREAD, ImagePaint, is_gradient, needs_mask   # (paint.py imports nothing of this module)
 
 RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY = 0, 1, 2, 3
 RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER = 4, 5, 6, 7
+RENDER_BLEND = 8   # (beyond the reference: CSS mix-blend-mode against the earlier siblings of the enclosing GROUP)
 
 
 class _Retained:
@@ -229,6 +230,8 @@ class Scene(tuple):
 
     def transform(self, transform: Transform) -> "Scene":
         type, args = self
+        if type == RENDER_BLEND:   # (the blend stays outermost: it acts on the node's place among its siblings)
+            return Scene(RENDER_BLEND, (args[0].transform(transform), args[1]))
         if type == RENDER_TRANSFORM:
             target, target_transform = args
             return Scene(RENDER_TRANSFORM, (target, transform @ target_transform))
@@ -236,6 +239,17 @@ class Scene(tuple):
 
     def filter(self, filter) -> "Scene":
         return Scene(RENDER_FILTER, (self, filter))
+
+    def blend(self, mode) -> "Scene":
+        """This node drawn with the mix-blend-mode `mode` (a name of ``layer.BLEND_MODES`` or its code) against what the
+        enclosing GROUP has drawn before it; anywhere else (no earlier siblings: the empty backdrop of an isolated group) it
+        draws as it is.  ``normal`` returns the node itself."""
+        code = BLEND_MODES[mode] if isinstance(mode, str) else int(mode)
+        if code not in BLEND_NAMES:
+            raise ValueError(f"invalid blend mode: {mode!r}")
+        if code == BLEND_NORMAL:
+            return self
+        return Scene(RENDER_BLEND, (self, code))
 
     def to_path(self, transform: Transform) -> Path:
         """All leaf outlines of the scene as one path, transforms applied on the host, strokes outlined after their
@@ -252,7 +266,7 @@ class Scene(tuple):
                     yield from outlines(child, tr)
             elif kind == RENDER_TRANSFORM:
                 yield from outlines(args[0], tr @ args[1])
-            elif kind in (RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_FILTER):
+            elif kind in (RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_FILTER, RENDER_BLEND):
                 yield from outlines(args[0], tr)
             else:
                 raise ValueError(f"unhandled scene type: {kind}")
@@ -298,6 +312,9 @@ class Scene(tuple):
                 dump(args[0], depth + 1, out)
             elif kind == RENDER_FILTER:
                 out.append(f"{head}FILTER {args[1]}")
+                dump(args[0], depth + 1, out)
+            elif kind == RENDER_BLEND:
+                out.append(f"{head}BLEND {BLEND_NAMES[args[1]]}")
                 dump(args[0], depth + 1, out)
             else:
                 raise ValueError(f"unhandled scene scene[0]: {kind}")
@@ -434,12 +451,29 @@ class Scene(tuple):
                     layers.append(res[0])
                     hulls.append(res[1])
 
+            blended = None   # the layer the last blend made: the walk owns its pixels while it is the only one in `layers`
             for child in args:
                 leaves = None if mask_only else _leaves_memo(child, transform, linear_rgb)
                 if leaves is not None:
                     run.extend(leaves)
                     continue
                 flush()
+                if child[0] == RENDER_BLEND and not mask_only:
+                    # mix-blend-mode: the source against everything drawn so far, which collapses into one accumulator -- N blended
+                    # children cost N blends, and the next one blends in place when it lies inside the accumulator
+                    res = child[1][0]._render(transform, mask_only, viewport, linear_rgb)
+                    if res is None:
+                        continue
+                    own = len(layers) > 1 or (len(layers) == 1 and layers[0] is blended)   # (compose of several: a fresh layer)
+                    backdrop = Layer.compose(layers, COMPOSE_OVER, linear_rgb)
+                    if backdrop is None:
+                        blended = None   # (nothing drawn before it: the source as it is, not the walk's to write into)
+                        layers[:] = [res[0]]
+                    else:
+                        blended = Layer.mix_blend(backdrop, res[0], child[1][1], linear_rgb, reuse_backdrop=own)
+                        layers[:] = [blended]
+                    hulls.append(res[1])
+                    continue
                 res = child._render(transform, mask_only, viewport, linear_rgb, not mask_only)
                 if res is None:
                     continue
@@ -503,6 +537,10 @@ class Scene(tuple):
                 return None
             image, hull = res
             return flt(transform, image, hull), hull
+        if kind == RENDER_BLEND:
+            # not directly under a GROUP (a GROUP's loop blends its BLEND children itself): the backdrop is the empty one of an
+            # isolated group, over which every mode leaves the source as it is; under mask_only, the target's coverage
+            return args[0]._render(transform, mask_only, viewport, linear_rgb)
         raise ValueError(f"unhandled scene type: {kind}")
 
     # -- whole-scene batched render: the bench / production entry -----------------------------
@@ -549,7 +587,7 @@ def _collect_mask_jobs(scene: Scene, transform: Transform, mask_only: bool, line
             runs.append(run)
     elif kind == RENDER_TRANSFORM:
         _collect_mask_jobs(args[0], transform @ args[1], mask_only, linear_rgb, jobs, runs, fills)
-    elif kind in (RENDER_OPACITY, RENDER_FILTER):
+    elif kind in (RENDER_OPACITY, RENDER_FILTER, RENDER_BLEND):
         _collect_mask_jobs(args[0], transform, mask_only, linear_rgb, jobs, runs, fills)
     elif kind == RENDER_CLIP:
         target, clip, bbox_units = args

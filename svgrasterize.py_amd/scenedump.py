@@ -10,6 +10,7 @@ import json
 import numpy as np
 
 from .geometry import Path, Transform
+from .layer import BLEND_MODES, BLEND_NAMES
 from .paint import GradLinear, GradRadial, ImagePaint, Pattern
 from .scene import Scene
 
@@ -63,6 +64,8 @@ def load_scene(npz_path: str):
             return Scene(5, (node(n["c"]), node(n["mask"]), n["bbox_units"]))
         if t == "transform":
             return Scene(6, (node(n["c"]), _tr(n["m"])))
+        if t == "blend":
+            return Scene(8, (node(n["c"]), BLEND_MODES[n["mode"]]))
         if t == "filter":
             from .filters import Filter
 
@@ -87,8 +90,8 @@ def dump_scene(scene: Scene):
     pixels of every image paint under the name its paint entry gives (``image_<n>``).
     STROKE nodes are stored as FILL nodes of their stroke outline (``from_stroke``), exactly like the reference dumps."""
     from .filters import FE_GAUSSIAN_BLUR
-    from .scene import (RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MASK, RENDER_OPACITY, RENDER_STROKE,
-                        RENDER_TRANSFORM)
+    from .scene import (RENDER_BLEND, RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MASK, RENDER_OPACITY,
+                        RENDER_STROKE, RENDER_TRANSFORM)
 
     lines, cubics, loff, coff = [], [], [0], [0]
     images: dict = {}   # array name -> pixels of an ImagePaint
@@ -151,6 +154,8 @@ def dump_scene(scene: Scene):
                 fl.append(dict(type=int(ftype), attrs=[None if v is None else float(v) for v in attrs]
                                if ftype == FE_GAUSSIAN_BLUR else repr(attrs), inputs=[int(i) for i in inputs]))
             return dict(t="filter", c=node(a[0]), filters=fl)
+        if kind == RENDER_BLEND:   # (beyond the reference's dumps: mix-blend-mode by name)
+            return dict(t="blend", c=node(a[0]), mode=BLEND_NAMES[a[1]])
         raise ValueError(kind)
 
     tree = node(scene)

@@ -12,7 +12,10 @@ feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, an
 feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow, feDiffuseLighting, feSpecularLighting with feDistantLight /
 fePointLight / feSpotLight; the <filter>'s region for the generators and the lighting primitives), text / tspan set in
 SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``, and beyond the
-reference image (PNG, from a ``data:image/png;base64`` URI or a local file next to the document; ``png.py``).
+reference image (PNG, from a ``data:image/png;base64`` URI or a local file next to the document; ``png.py``) and CSS
+``mix-blend-mode`` (all 16 modes of Compositing and Blending Level 1, not inherited; applied outermost, after the transform, as a
+BLEND node that blends with the earlier siblings in its group node) and ``isolation: isolate`` (the element's content becomes
+one group node).  ``plus-lighter``, ``plus-darker`` and unknown modes warn and draw as ``normal``.
 Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
 or remote URLs.
 """
@@ -38,10 +41,10 @@ from .fonts import FONT_STYLE_NORMAL, Font, FontsDB, Glyph
 from .geometry import (
     PATH_CLOSED, PATH_FILL_NONZERO, PATH_LINE, STROKE_CAP_BUTT, STROKE_JOIN_MITER, Path, Transform,
 )
-from .layer import COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
+from .layer import BLEND_MODES, COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
 from .paint import GradLinear, GradRadial, Pattern
 from .png import read_png
-from .scene import Scene, parse_preserve_aspect_ratio
+from .scene import RENDER_BLEND, Scene, parse_preserve_aspect_ratio
 
 UNITS_USER = "userSpaceOnUse"
 UNITS_BBOX = "objectBoundingBox"
@@ -303,6 +306,19 @@ def _expand_style(attrib, inherit=None) -> dict:
                 key, value = decl.split(":", 1)
                 attrs[key.strip()] = value.strip()
     return attrs if inherit is None else {**inherit, **attrs}
+
+
+def _keyword(text) -> str:
+    """A CSS keyword compared ASCII case-insensitively (no Unicode case folding)."""
+    return text.strip().encode("utf-8").lower().decode("utf-8")
+
+
+def _isolated(group: list) -> list:
+    """The nodes of an element with ``isolation: isolate``: one GROUP node, so that a blend inside sees only this content.  A
+    single BLEND node has nothing of the element's before it: it draws as its target."""
+    if len(group) == 1:
+        return [group[0][1][0]] if group[0][0] == RENDER_BLEND else group
+    return [Scene.group(group)]
 
 
 def _gradient_stops(element):
@@ -1004,8 +1020,14 @@ class _Loader:
 
         if not group:
             return group
+        isolation = attrs.get("isolation")
+        if isolation is not None and _keyword(isolation) not in ("auto", "isolate"):
+            warnings.warn(f"unsupported isolation: {isolation}")
+        elif isolation is not None and _keyword(isolation) == "isolate":
+            group = _isolated(group)
         # decorations, innermost first: filter, group opacity, clip-path, mask; the element's transform goes last, so that
-        # clips and masks live in the transformed space (S:3031-3071)
+        # clips and masks live in the transformed space (S:3031-3071); beyond the reference, mix-blend-mode outside all of them
+        # (it places the element among its siblings)
         name = attrs.get("filter")
         if name is not None:
             flt = _resolve_url(name, ids)
@@ -1029,6 +1051,13 @@ class _Loader:
         tr = parse_transform(attrs.get("transform"))
         if tr is not None:
             group = [node.transform(tr) for node in group]
+        blend = attrs.get("mix-blend-mode")
+        if blend is not None:
+            mode = BLEND_MODES.get(_keyword(blend))
+            if mode is None:   # (plus-lighter, plus-darker and anything else: drawn as normal)
+                warnings.warn(f"unsupported mix-blend-mode: {blend}")
+            elif mode != BLEND_MODES["normal"]:
+                group = [Scene.group(group).blend(mode)]
         if attrs.get("id") is not None:
             ids[attrs["id"]] = Scene.group(group)
         return group
