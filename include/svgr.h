@@ -40,7 +40,8 @@ extern "C" {
  * 6 (later, nothing changed or removed): svgr_layer_turbulence, svgr_layer_component_transfer, svgr_layer_convolve_matrix,
  *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
  *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
- *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode) */
+ *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode); svgr_jpeg_entropy and
+ *    svgr_jpeg_decode added (JPEG in SVG <image>) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -509,6 +510,50 @@ void svgr_stroke_out_free(svgr_stroke_out* s);
  * read past src_bytes. */
 int svgr_png_unfilter(const uint8_t* src, int64_t src_bytes, int64_t rows, int64_t row_bytes, int64_t bytes_per_pixel,
                       uint8_t* dst);
+
+/* JPEG (read_jpeg): the caller reads the markers; the entropy-coded data is decoded on the host and the pixels are made on
+ * the device.  Both entries describe the frame the same way and lay its coefficients out the same way: component after
+ * component, each a row-major grid of 8 x 8 blocks of 64 int16 in natural (row-major) order, the grid padded to whole MCUs --
+ * with hmax, vmax the largest sampling factors, mcus_x = ceil(width / (8 hmax)), mcus_y = ceil(height / (8 vmax)), component
+ * i has mcus_x * h[i] blocks per row and mcus_y * v[i] rows of them. */
+#define SVGR_JPEG_GREY 0   /* one component */
+#define SVGR_JPEG_YCBCR 1  /* three: JFIF Y, Cb, Cr */
+#define SVGR_JPEG_RGB 2    /* three: R, G, B as they are */
+typedef struct svgr_jpeg_frame {
+    int32_t width, height; /* 1 .. 65535 */
+    int32_t n_comp;        /* 1 or 3 */
+    int32_t h[3], v[3];    /* sampling factors, 1 or 2 (1 for a lone component) */
+    int32_t colour;        /* SVGR_JPEG_* (svgr_jpeg_decode only) */
+} svgr_jpeg_frame;
+typedef struct svgr_jpeg_scan {
+    svgr_jpeg_frame frame;
+    int32_t progressive;        /* 0: SOF0 / SOF1, 1: SOF2 */
+    int32_t restart_interval;   /* MCUs between restart markers (DRI), 0: none */
+    int32_t n_scan;             /* components in this scan */
+    int32_t scan_comp[3];       /* their indices in the frame, ascending */
+    int32_t dc_table[3], ac_table[3];   /* Huffman table of each, 0 .. 3 */
+    int32_t ss, se, ah, al;     /* spectral selection and successive approximation (0, 63, 0, 0 when not progressive) */
+} svgr_jpeg_scan;
+/* svgr_jpeg_entropy (host only): decode the entropy-coded segment `data` of one scan (from behind the SOS header up to, not
+ * including, the next marker that is not RSTn; stuffed bytes and restart markers still in it) into `coef`, which holds
+ * n_coef int16 -- the whole frame -- is zero before the frame's first scan and is carried from scan to scan.  The Huffman
+ * tables in force: huff_counts[8][16] codes per length and huff_symbols[8][256] in code order, DC tables 0-3 then AC tables
+ * 0-3 (all-zero counts: not defined).  Returns SVGR_OK, SVGR_E_INVALID for a description that makes no sense, or one of the
+ * SVGR_JPEG_* statuses below for data that does not decode; nothing is read or written outside the arrays. */
+#define SVGR_JPEG_TRUNCATED 1    /* the data ended before the scan did */
+#define SVGR_JPEG_BAD_CODE 2     /* a Huffman table that is not a prefix code, or bits that are no code of the table */
+#define SVGR_JPEG_BAD_RESTART 3  /* the restart marker due is missing or out of sequence */
+#define SVGR_JPEG_BAD_INDEX 4    /* a run that leads past the last coefficient of the block or band */
+int svgr_jpeg_entropy(const svgr_jpeg_scan* scan, const uint8_t* huff_counts, const uint8_t* huff_symbols, const uint8_t* data,
+                      int64_t n_bytes, int16_t* coef, int64_t n_coef);
+/* svgr_jpeg_decode: the pixels of a frame from its coefficients (host array, n_coef int16 as above) and each component's
+ * quantisation table (quant[n_comp][64], natural order).  Per sample: coefficient * table entry, inverse DCT, + 128, clamp
+ * to 0 .. 255.  Per pixel: subsampled components are brought to full resolution with the centred triangle filter (3/4, 1/4
+ * per axis, edge sample repeated), YCbCr goes through the JFIF matrix, alpha is 255.  All of it is integer arithmetic
+ * (csrc/svgr_core.h), so the result is defined to the bit.  out_rgba receives (height, width, 4) uint8, straight alpha,
+ * sRGB as stored: what svgr_image_upload takes. */
+int svgr_jpeg_decode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const int16_t* coef, int64_t n_coef, const uint16_t* quant,
+                     svgr_buf* out_rgba);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,25 @@ class ImageArgs(C.Structure):  # svgr_image
     ]
 
 
+class JpegFrame(C.Structure):  # svgr_jpeg_frame
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("n_comp", C.c_int32), ("h", C.c_int32 * 3), ("v", C.c_int32 * 3),
+        ("colour", C.c_int32),
+    ]
+
+
+class JpegScan(C.Structure):  # svgr_jpeg_scan
+    _fields_ = [
+        ("frame", JpegFrame), ("progressive", C.c_int32), ("restart_interval", C.c_int32), ("n_scan", C.c_int32),
+        ("scan_comp", C.c_int32 * 3), ("dc_table", C.c_int32 * 3), ("ac_table", C.c_int32 * 3),
+        ("ss", C.c_int32), ("se", C.c_int32), ("ah", C.c_int32), ("al", C.c_int32),
+    ]
+
+
+JPEG_GREY, JPEG_YCBCR, JPEG_RGB = 0, 1, 2
+_JPEG_STATUS = {1: "the entropy-coded data ends before the scan does", 2: "a bad Huffman table or code",
+                3: "a restart marker is missing or out of sequence", 4: "a run of zeros leads past the end of the block"}
+
 _P = C.c_void_p
 _PROTOS = {
     "svgr_abi_version": (C.c_int, []),
@@ -151,6 +170,8 @@ _PROTOS = {
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
     "svgr_png_unfilter": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "svgr_jpeg_entropy": (C.c_int, [C.POINTER(JpegScan), _P, _P, _P, C.c_int64, _P, C.c_int64]),
+    "svgr_jpeg_decode": (C.c_int, [_P, C.POINTER(JpegFrame), _P, C.c_int64, _P, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -573,3 +594,28 @@ def png_unfilter(data, rows: int, row_bytes: int, bytes_per_pixel: int) -> np.nd
     if rc != 0:
         raise ValueError("PNG scanlines: unknown filter type or truncated data")
     return dst
+
+
+def jpeg_entropy(scan: JpegScan, huff_counts: np.ndarray, huff_symbols: np.ndarray, data, coef: np.ndarray) -> None:
+    """svgr_jpeg_entropy (host only): one scan's entropy-coded segment decoded into `coef`, the frame's int16 coefficients
+    (include/svgr.h has the layout), in place.  ValueError with the reason when the data does not decode."""
+    src = np.frombuffer(data, dtype=np.uint8)
+    assert huff_counts.dtype == np.uint8 and huff_counts.shape == (8, 16) and huff_counts.flags.c_contiguous
+    assert huff_symbols.dtype == np.uint8 and huff_symbols.shape == (8, 256) and huff_symbols.flags.c_contiguous
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.flags.writeable
+    rc = load_library().svgr_jpeg_entropy(C.byref(scan), ptr(huff_counts), ptr(huff_symbols), src.ctypes.data_as(_P), src.size,
+                                          ptr(coef), coef.size)
+    if rc:
+        raise ValueError(_JPEG_STATUS.get(rc, "a scan header that does not fit the frame"))
+
+
+def jpeg_decode(ctx: Context, frame: JpegFrame, coef: np.ndarray, quant: np.ndarray) -> np.ndarray:
+    """svgr_jpeg_decode: the (height, width, 4) uint8 pixels of a frame from its coefficients and its components'
+    quantisation tables (n_comp, 64) uint16, made on the device and downloaded."""
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    quant = np.ascontiguousarray(quant, dtype=np.uint16)
+    if quant.shape != (frame.n_comp, 64):
+        raise ValueError("jpeg_decode: one quantisation table of 64 entries per component")
+    out = ctx.alloc(frame.width * frame.height * 4)
+    _check(ctx.lib.svgr_jpeg_decode(ctx.handle, C.byref(frame), ptr(coef), coef.size, ptr(quant), out.handle))
+    return out.download((frame.height, frame.width, 4), np.uint8)

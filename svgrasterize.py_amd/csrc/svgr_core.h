@@ -20,8 +20,10 @@
 
 #if defined(__HIPCC__)
 #define SVGR_HD __host__ __device__ __forceinline__
+#define SVGR_UNROLL _Pragma("unroll")
 #else
 #define SVGR_HD static inline
+#define SVGR_UNROLL
 #endif
 
 namespace svgr {
@@ -813,6 +815,121 @@ SVGR_HD void mix_blend_px(int mode, double* d, const double* s) {
     const double kb = 1.0 - ab, w = as * ab;
     for (int k = 0; k < 3; ++k) d[k] = (s[k] * kb + d[k] * ka) + w * B[k];
     d[3] = as + ab * ka;
+}
+
+
+// =====================================================================================
+// JPEG pixel stage (read_jpeg; beyond the reference): coefficients -> 8-bit samples -> RGBA.
+// Everything is integer arithmetic, so the host build of this file (tests/jpeg_harness.cpp) and the
+// kernels (k_jpeg_idct, k_jpeg_colour) produce the same bits.
+//
+// Inverse DCT: the separable definition itself, s(y, x) = sum_v sum_u T[y][v] T[x][u] F(v, u) with
+// T[k][j] = 1/2 c(j) cos((2k + 1) j pi / 16), c(0) = 1 / sqrt 2, as two 8-tap passes.  T is stored as
+// round(2^15 T); the passes accumulate in 64 bits and nothing is rounded before the one shift at the
+// end.  A dequantised coefficient is clamped to +-2^16: an 8-bit image cannot produce one beyond
+// +-2^11 (+-2^12 after the quantiser's rounding), and with the clamp no stream, however corrupt, can
+// overflow: sum_j |2^15 T[k][j]| < 2^17, so pass 1 stays below 2^33 and pass 2 below 2^50.
+// =====================================================================================
+constexpr int kJpegIdctBits = 15;
+constexpr int32_t kJpegIdct[64] = {   // [k][j]: output k, frequency j
+    11585,  16069,  15137,  13623,  11585,   9102,   6270,   3196,
+    11585,  13623,   6270,  -3196, -11585, -16069, -15137,  -9102,
+    11585,   9102,  -6270, -16069, -11585,   3196,  15137,  13623,
+    11585,   3196, -15137,  -9102,  11585,  13623,  -6270, -16069,
+    11585,  -3196, -15137,   9102,  11585, -13623,  -6270,  16069,
+    11585,  -9102,  -6270,  16069, -11585,  -3196,  15137, -13623,
+    11585, -13623,   6270,   3196, -11585,  16069, -15137,   9102,
+    11585, -16069,  15137, -13623,  11585,  -9102,   6270,  -3196,
+};
+
+SVGR_HD int32_t jpeg_dequant(int16_t coef, uint16_t q) {
+    const int32_t v = (int32_t)coef * (int32_t)q;   // (|v| <= 32768 * 65535 < 2^31)
+    return v < -65536 ? -65536 : (v > 65536 ? 65536 : v);
+}
+
+// one 8-tap pass: out[k] = sum_j 2^15 T[k][j] in[j * stride]  (In: int32_t for the first pass, int64_t for the second)
+template <class In>
+SVGR_HD void jpeg_idct_pass(const In* in, int stride, int64_t* out) {
+    SVGR_UNROLL
+    for (int k = 0; k < 8; ++k) {
+        int64_t acc = 0;
+        SVGR_UNROLL
+        for (int j = 0; j < 8; ++j) acc += (int64_t)kJpegIdct[8 * k + j] * (int64_t)in[j * stride];
+        out[k] = acc;
+    }
+}
+
+// the sample of a finished sum of both passes: scaled back (round half up), level shift, clamp
+SVGR_HD uint8_t jpeg_sample(int64_t acc) {
+    const int64_t v = ((acc + ((int64_t)1 << (2 * kJpegIdctBits - 1))) >> (2 * kJpegIdctBits)) + 128;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// A whole block on one thread (the host harness; the kernel spreads the same calls over eight lanes per block): coef[64] in
+// natural order, q[64] likewise, out = the block's top-left sample in a plane whose rows are `stride` bytes apart.
+SVGR_HD void jpeg_idct_block(const int16_t* coef, const uint16_t* q, uint8_t* out, int64_t stride) {
+    int32_t d[64];
+    int64_t t[64], row[8];
+    for (int i = 0; i < 64; ++i) d[i] = jpeg_dequant(coef[i], q[i]);
+    for (int u = 0; u < 8; ++u) {   // columns: t[y][u] = sum_v T[y][v] d[v][u]
+        jpeg_idct_pass(d + u, 8, row);
+        for (int y = 0; y < 8; ++y) t[8 * y + u] = row[y];
+    }
+    for (int y = 0; y < 8; ++y) {   // rows: s[y][x] = sum_u T[x][u] t[y][u]
+        jpeg_idct_pass(t + 8 * y, 1, row);
+        for (int x = 0; x < 8; ++x) out[y * stride + x] = jpeg_sample(row[x]);
+    }
+}
+
+// A component's plane of samples: `w` x `h` of them are the component's own (its edge, for the replication below), in rows
+// `stride` bytes apart; `hs`, `vs` = 1 or 2 full-resolution pixels per sample along each axis.
+struct JpegPlane {
+    const uint8_t* p;
+    int64_t stride;
+    int w, h, hs, vs;
+};
+
+// 16 x the component's value at full-resolution pixel (x, y).  Along a subsampled axis the pixel lies a quarter of a sample
+// from its own sample's centre: 3/4 of that sample and 1/4 of the neighbour on the pixel's side, the edge sample repeated
+// ("fancy" upsampling; not pixel replication).  Along a full-resolution axis the neighbour is the sample itself, so the same
+// sum is 4 x the sample.  Exact: the one rounding comes after the colour matrix.
+SVGR_HD int jpeg_upsampled16(const JpegPlane& c, int x, int y) {
+    if (c.hs == 1 && c.vs == 1) return 16 * (int)c.p[y * c.stride + x];
+    int x0 = x, x1 = x, y0 = y, y1 = y;
+    if (c.hs == 2) {
+        x0 = x >> 1;
+        x1 = (x & 1) ? (x0 + 1 < c.w ? x0 + 1 : x0) : (x0 > 0 ? x0 - 1 : 0);
+    }
+    if (c.vs == 2) {
+        y0 = y >> 1;
+        y1 = (y & 1) ? (y0 + 1 < c.h ? y0 + 1 : y0) : (y0 > 0 ? y0 - 1 : 0);
+    }
+    const uint8_t *r0 = c.p + y0 * c.stride, *r1 = c.p + y1 * c.stride;
+    const int near = 3 * (int)r0[x0] + (int)r0[x1], far = 3 * (int)r1[x0] + (int)r1[x1];
+    return 3 * near + far;
+}
+
+// colour models of a frame
+constexpr int kJpegGrey = 0, kJpegYCbCr = 1, kJpegRGB = 2;
+
+SVGR_HD int jpeg_clamp8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// One pixel from its three 16 x samples (jpeg_upsampled16): R | G << 8 | B << 16 | 255 << 24.  YCbCr is the JFIF matrix
+// (R = Y + 1.402 Cr', G = Y - 0.344136 Cb' - 0.714136 Cr', B = Y + 1.772 Cb', primes = minus 128) with the factors rounded
+// to 16 fractional bits; 20 bits come off at the end, rounding half up.  Grey and RGB only drop the 4 bits.
+SVGR_HD uint32_t jpeg_rgba(int colour, int s0, int s1, int s2) {
+    int r, g, b;
+    if (colour == kJpegYCbCr) {
+        const int y = s0 * 65536 + (1 << 19), cb = s1 - 128 * 16, cr = s2 - 128 * 16;
+        r = jpeg_clamp8((y + 91881 * cr) >> 20);
+        g = jpeg_clamp8((y - 22553 * cb - 46802 * cr) >> 20);
+        b = jpeg_clamp8((y + 116130 * cb) >> 20);
+    } else {
+        r = (s0 + 8) >> 4;
+        g = colour == kJpegRGB ? (s1 + 8) >> 4 : r;
+        b = colour == kJpegRGB ? (s2 + 8) >> 4 : r;
+    }
+    return (uint32_t)r | (uint32_t)g << 8 | (uint32_t)b << 16 | 0xFF000000u;
 }
 
 }  // namespace svgr

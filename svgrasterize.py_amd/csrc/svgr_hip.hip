@@ -4067,6 +4067,115 @@ __global__ void k_image_downsample(const float4* __restrict__ src, int h, int w,
                          (float)((((double)a.w + b.w) + ((double)d.w + e.w)) * 0.25));
 }
 
+// --------------------------------------------------------------------------------------
+// JPEG pixel stage (read_jpeg): coefficients -> sample planes -> RGBA.  The arithmetic is svgr_core.h's integer code,
+// so the planes and the pixels equal the host build's bit for bit.
+// --------------------------------------------------------------------------------------
+// The coefficient layout of a frame (include/svgr.h): per component its first block, blocks per row and rows of blocks, and
+// where its plane of samples starts (one byte per sample, 8 * bw bytes per row).  False if the frame makes no sense.
+struct JpegLayout {
+    int64_t base[3], bw[3], bh[3], plane[3];
+    int64_t blocks, plane_bytes;
+    int cw[3], ch[3], hs[3], vs[3];   // the component's own size in samples; full-resolution pixels per sample
+};
+static bool jpeg_layout(const svgr_jpeg_frame& f, JpegLayout& L) {
+    if ((f.n_comp != 1 && f.n_comp != 3) || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return false;
+    int hmax = 1, vmax = 1;
+    for (int i = 0; i < f.n_comp; ++i) {
+        if (f.h[i] < 1 || f.h[i] > 2 || f.v[i] < 1 || f.v[i] > 2) return false;
+        hmax = std::max(hmax, (int)f.h[i]);
+        vmax = std::max(vmax, (int)f.v[i]);
+    }
+    if (f.n_comp == 1 && (hmax != 1 || vmax != 1)) return false;
+    if (f.n_comp == 1 ? f.colour != SVGR_JPEG_GREY : (f.colour != SVGR_JPEG_YCBCR && f.colour != SVGR_JPEG_RGB)) return false;
+    const int64_t mcus_x = (f.width + 8 * hmax - 1) / (8 * hmax), mcus_y = (f.height + 8 * vmax - 1) / (8 * vmax);
+    L.blocks = 0;
+    for (int i = 0; i < 3; ++i) {
+        const int k = i < f.n_comp ? i : 0;   // (a grey frame's unused slots repeat its one component)
+        L.hs[i] = hmax / f.h[k];
+        L.vs[i] = vmax / f.v[k];
+        L.cw[i] = (f.width + L.hs[i] - 1) / L.hs[i];
+        L.ch[i] = (f.height + L.vs[i] - 1) / L.vs[i];
+        L.bw[i] = mcus_x * f.h[k];
+        L.bh[i] = mcus_y * f.v[k];
+        if (i < f.n_comp) {
+            L.base[i] = L.blocks;
+            L.blocks += L.bw[i] * L.bh[i];
+        } else {
+            L.base[i] = L.base[0];
+        }
+        L.plane[i] = L.base[i] * 64;
+    }
+    L.plane_bytes = L.blocks * 64;
+    return true;
+}
+
+// Dequantise + inverse DCT + level shift + clamp.  Eight lanes per block, 32 blocks per workgroup: lane (block, k) loads row k
+// of the block's coefficients and of its quantisation table as 16 bytes each (a wave reads 1 KiB of consecutive
+// coefficients), the products go to LDS; lane (block, u) then runs the column pass of column u, lane (block, y) the row pass
+// of row y and stores its eight samples as one 8-byte word.  Rows of 72 words keep the four blocks of a half-wave on
+// different LDS banks in the column pass.
+constexpr int JPEG_WG_BLOCKS = 32, JPEG_LDS_ROW = 72;
+struct JpegIdctArgs {
+    const int16_t* coef;
+    const uint16_t* quant;   // [component][64]
+    uint8_t* planes;
+    long long end[3];        // one past each component's last block (the components follow each other)
+    long long bw[3], plane[3];
+};
+__global__ void __launch_bounds__(256) k_jpeg_idct(JpegIdctArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t d[JPEG_WG_BLOCKS * JPEG_LDS_ROW];
+    __shared__ __attribute__((aligned(16))) int64_t t[JPEG_WG_BLOCKS * JPEG_LDS_ROW];
+    const int blk = threadIdx.x >> 3, k = threadIdx.x & 7;
+    const long long b = (long long)blockIdx.x * JPEG_WG_BLOCKS + blk;
+    const bool live = b < a.end[2];
+    const int ci = b < a.end[0] ? 0 : (b < a.end[1] ? 1 : 2);
+    if (live) {
+        union { uint4 v; int16_t s[8]; } c;
+        union { uint4 v; uint16_t s[8]; } q;
+        c.v = *reinterpret_cast<const uint4*>(a.coef + b * 64 + 8 * k);
+        q.v = *reinterpret_cast<const uint4*>(a.quant + 64 * ci + 8 * k);
+        int32_t* row = d + blk * JPEG_LDS_ROW + 8 * k;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) row[j] = jpeg_dequant(c.s[j], q.s[j]);
+    }
+    __syncthreads();
+    if (live) {   // column k: t[y][k] = sum_v T[y][v] d[v][k]
+        int64_t col[8];
+        jpeg_idct_pass(d + blk * JPEG_LDS_ROW + k, 8, col);
+#pragma unroll
+        for (int y = 0; y < 8; ++y) t[blk * JPEG_LDS_ROW + 8 * y + k] = col[y];
+    }
+    __syncthreads();
+    if (live) {   // row k: s[k][x] = sum_u T[x][u] t[k][u]
+        int64_t acc[8];
+        jpeg_idct_pass(t + blk * JPEG_LDS_ROW + 8 * k, 1, acc);
+        union { uint2 v; uint8_t s[8]; } o;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) o.s[x] = jpeg_sample(acc[x]);
+        const long long first = ci == 0 ? 0 : a.end[ci - 1], lb = b - first;
+        const long long by = lb / a.bw[ci], bx = lb - by * a.bw[ci];
+        *reinterpret_cast<uint2*>(a.planes + a.plane[ci] + (by * 8 + k) * (a.bw[ci] * 8) + bx * 8) = o.v;
+    }
+}
+
+// Upsampling + colour + alpha: one pixel per lane, a 64 x 4 tile per workgroup, so that a wave writes 256 consecutive bytes
+struct JpegColourArgs {
+    JpegPlane c[3];
+    int width, height, colour;
+};
+__global__ void __launch_bounds__(256) k_jpeg_colour(JpegColourArgs a, uint32_t* __restrict__ out) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.width || y >= a.height) return;
+    const int s0 = jpeg_upsampled16(a.c[0], x, y);
+    int s1 = s0, s2 = s0;
+    if (a.colour != kJpegGrey) {
+        s1 = jpeg_upsampled16(a.c[1], x, y);
+        s2 = jpeg_upsampled16(a.c[2], x, y);
+    }
+    out[(size_t)y * a.width + x] = jpeg_rgba(a.colour, s0, s1, s2);
+}
+
 struct ImageLevel {
     const float4* tex;
     int h, w;
@@ -7041,6 +7150,38 @@ int svgr_image_fill(svgr_ctx* ctx, const svgr_image* im, const svgr_buf* levels,
     const dim3 grid((unsigned)((bbox[3] + IMG_TW - 1) / IMG_TW), (unsigned)std::min<int64_t>((bbox[2] + IMG_TH - 1) / IMG_TH, 32768));
     return launch_tail(ctx, im->smooth ? k_image_fill<true> : k_image_fill<false>, grid, dim3(256), 0, *im, lo, hi, blend,
                        (const double*)mask->ptr, (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
+}
+
+int svgr_jpeg_decode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const int16_t* coef, int64_t n_coef, const uint16_t* quant,
+                     svgr_buf* out) {
+    JpegLayout L;
+    if (!ctx || !frame || !coef || !quant || !out || !jpeg_layout(*frame, L) || !image_size_ok(frame->height, frame->width))
+        return fail(SVGR_E_INVALID, "svgr_jpeg_decode: bad arguments");
+    if (n_coef != L.blocks * 64) return fail(SVGR_E_INVALID, "svgr_jpeg_decode: %lld coefficients for a frame of %lld", (long long)n_coef, (long long)L.blocks * 64);
+    if (out->bytes < (size_t)frame->width * frame->height * 4) return fail(SVGR_E_INVALID, "svgr_jpeg_decode: buffer too small");
+    static_assert(kJpegGrey == SVGR_JPEG_GREY && kJpegYCbCr == SVGR_JPEG_YCBCR && kJpegRGB == SVGR_JPEG_RGB, "colour models");
+    HIPCHK(enter_ctx(ctx));
+    PoolBlock planes;
+    HIPCHK(planes.alloc((size_t)L.plane_bytes, ctx->device));
+    const size_t coef_bytes = (size_t)n_coef * 2;   // (a multiple of 128: the tables behind it stay 16-byte aligned)
+    return upload_launch_wait(ctx, "svgr_jpeg_decode", {{coef, coef_bytes}, {quant, (size_t)frame->n_comp * 128}}, [&](void* dev) {
+        JpegIdctArgs ia;
+        ia.coef = (const int16_t*)dev;
+        ia.quant = (const uint16_t*)((const char*)dev + coef_bytes);
+        ia.planes = planes.as<uint8_t>();
+        JpegColourArgs ca;
+        for (int i = 0; i < 3; ++i) {
+            const int k = i < frame->n_comp ? i : frame->n_comp - 1;
+            ia.end[i] = L.base[k] + L.bw[k] * L.bh[k];
+            ia.bw[i] = L.bw[i];
+            ia.plane[i] = L.plane[i];
+            ca.c[i] = JpegPlane{planes.as<uint8_t>() + L.plane[i], L.bw[i] * 8, L.cw[i], L.ch[i], L.hs[i], L.vs[i]};
+        }
+        ca.width = frame->width; ca.height = frame->height; ca.colour = frame->colour;
+        SVGR_LAUNCH(k_jpeg_idct, dim3((unsigned)((L.blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS)), dim3(256), 0, ctx->stream, ia);
+        SVGR_LAUNCH(k_jpeg_colour, dim3((unsigned)((frame->width + 63) / 64), (unsigned)((frame->height + 3) / 4)), dim3(256), 0,
+                    ctx->stream, ca, (uint32_t*)out->ptr);
+    });
 }
 
 static int layer_convolve_impl(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int64_t rows, int64_t cols, const double* kernel,

@@ -12,12 +12,13 @@ feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, an
 feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow, feDiffuseLighting, feSpecularLighting with feDistantLight /
 fePointLight / feSpotLight; the <filter>'s region for the generators and the lighting primitives), text / tspan set in
 SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``, and beyond the
-reference image (PNG, from a ``data:image/png;base64`` URI or a local file next to the document; ``png.py``) and CSS
+reference image (PNG or JPEG, from a base64 ``data:image/png`` / ``data:image/jpeg`` URI or a local file next to the document, the
+decoder picked by the data's first bytes; ``png.py``, ``jpeg.py``) and CSS
 ``mix-blend-mode`` (all 16 modes of Compositing and Blending Level 1, not inherited; applied outermost, after the transform, as a
 BLEND node that blends with the earlier siblings in its group node) and ``isolation: isolate`` (the element's content becomes
 one group node).  ``plus-lighter``, ``plus-darker`` and unknown modes warn and draw as ``normal``.
 Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
-or remote URLs.
+(GIF, WebP, SVG) or remote URLs.
 """
 from __future__ import annotations
 
@@ -43,6 +44,9 @@ from .geometry import (
 )
 from .layer import BLEND_MODES, COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
 from .paint import GradLinear, GradRadial, Pattern
+from .jpeg import read_jpeg
+from .jpeg import SIGNATURE as _JPEG_SIGNATURE
+from .png import SIGNATURE as _PNG_SIGNATURE
 from .png import read_png
 from .scene import RENDER_BLEND, Scene, parse_preserve_aspect_ratio
 
@@ -707,6 +711,10 @@ def ellipse_path_data(cx, cy, rx, ry) -> str:
 # ---------------------------------------------------------------------------------------------------------------------
 # the loader
 # ---------------------------------------------------------------------------------------------------------------------
+_IMAGE_MIME_TYPES = {"image/png": "PNG", "image/jpeg": "JPEG", "image/jpg": "JPEG"}
+_IMAGE_EXTENSIONS = {".png": "PNG", ".jpg": "JPEG", ".jpeg": "JPEG", ".jpe": "JPEG"}
+
+
 class _Loader:
     def __init__(self, fg, width, fonts=None, base_dir=None):
         self.fonts = FontsDB() if fonts is None else fonts
@@ -717,8 +725,9 @@ class _Loader:
         self.base_dir = base_dir   # the document's directory (<image> files resolve against it); None: not from a file
 
     def image_pixels(self, href):
-        """The RGBA pixels an <image> href points at, or None (+ warning): a PNG data URI or a local PNG file.  Nothing is
-        ever fetched from the network."""
+        """The RGBA pixels an <image> href points at, or None (+ warning): a PNG or JPEG data URI or local file.  The name or
+        MIME type says whether the source is worth reading; the decoder is picked by the data's first bytes.  Nothing is ever
+        fetched from the network."""
         if not href:
             warnings.warn("image without href")
             return None
@@ -726,21 +735,22 @@ class _Loader:
         if href[:5].lower() == "data:":
             head, _, payload = href[5:].partition(",")
             params = [p.strip().lower() for p in head.split(";")]
-            if params[0] != "image/png" or "base64" not in params[1:]:
-                warnings.warn(f"unsupported image data: {head or 'text/plain'} (only base64 PNG is read)")
+            if params[0] not in _IMAGE_MIME_TYPES or "base64" not in params[1:]:
+                warnings.warn(f"unsupported image data: {head or 'text/plain'} (base64 PNG and JPEG are read)")
                 return None
             try:
                 data = base64.b64decode("".join(payload.split()), validate=True)
             except (binascii.Error, ValueError) as e:
                 warnings.warn(f"bad base64 image data: {e}")
                 return None
-            where = "data URI"
+            where, kind = "data URI", _IMAGE_MIME_TYPES[params[0]]
         else:
             if re.match(r"[A-Za-z][A-Za-z0-9+.-]*:", href) and not re.match(r"[A-Za-z]:[\\/]", href):
                 warnings.warn(f"image not loaded (only data URIs and local files are read): {href}")
                 return None
-            if not href.lower().endswith(".png"):
-                warnings.warn(f"unsupported image format (only PNG is read): {href}")
+            kind = _IMAGE_EXTENSIONS.get(os.path.splitext(href)[1].lower())
+            if kind is None:
+                warnings.warn(f"unsupported image format (PNG and JPEG are read): {href}")
                 return None
             if self.base_dir is None:
                 warnings.warn(f"image file not loaded (the document is not from a file): {href}")
@@ -753,10 +763,18 @@ class _Loader:
                 warnings.warn(f"image file not readable: {href}: {e}")
                 return None
             where = href
+        # (a JPEG named .png, or the other way round, is read as what it is)
+        if data[:len(_PNG_SIGNATURE)] == _PNG_SIGNATURE:
+            kind = "PNG"
+        elif data[:len(_JPEG_SIGNATURE)] == _JPEG_SIGNATURE:
+            kind = "JPEG"
         try:
-            return read_png(data)
+            return read_png(data) if kind == "PNG" else read_jpeg(data)
         except ValueError as e:
-            warnings.warn(f"undecodable PNG ({where}): {e}")
+            # (PNG keeps the text it had.  A JPEG source used to be turned away as "unsupported image data" before its bytes
+            #  were looked at; one that cannot be decoded still is, now with what is wrong with it)
+            what = f"undecodable {kind} ({where}): {e}"
+            warnings.warn(what if kind == "PNG" else f"unsupported image data: {what}")
             return None
 
     def image(self, attrs) -> list:
