@@ -41,7 +41,7 @@ extern "C" {
  *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
  *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
  *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode); svgr_jpeg_entropy and
- *    svgr_jpeg_decode added (JPEG in SVG <image>) */
+ *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -390,6 +390,15 @@ int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, c
 #define SVGR_BLEND_LUMINOSITY 15
 int svgr_layer_mix_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* backdrop, const int64_t* backdrop_bbox,
                          int backdrop_channels, const svgr_buf* src, const int64_t* src_bbox, int src_channels, int mode);
+/* feTile: out (RGBA, out_bbox) is filled with repeats of the tile tile_bbox of src (RGBA, src_bbox; a bbox is {row0, col0, rows, cols} in device pixels):
+ *   out[r, c] = tile[(r - tile_row0) mod tile_rows, (c - tile_col0) mod tile_cols]   (floor modulo: out may start before the tile)
+ * where tile is src seen through tile_bbox, transparent black where src does not reach (svgr_core.h: tile_wrap, tile_next,
+ * tile_source).  A copy: the values are src's bits, whatever its alpha convention and colour space.  Every pixel of out is
+ * written once; out needs no clearing.  With tile_bbox == out_bbox nothing repeats: out is src cropped / zero-extended to
+ * out_bbox (what svgr_layer_compose_over with this one source writes too; the filter chain cuts a result to its primitive
+ * subregion with that entry).  An empty tile or output is SVGR_E_INVALID; out must not be src.                                */
+int svgr_layer_tile(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
+                    const int64_t* tile_bbox);
 /* Luminance of a straight-alpha RGBA image for RENDER_MASK (S:735): out(n_px doubles) = (rgb . {0.2125, 0.7154, 0.072}) * a */
 int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out_1ch, const svgr_buf* src_rgba, int64_t n_px);
 

@@ -73,6 +73,12 @@ def main():
         lambda: pre.lighting(tr, (0, 0), (n, n), PointLight(lx, ly, 500.0), white, 2.0, 1.0, 20.0))
     run("k_layer_lighting specular, spot with a cone, exponent 20", 2 * px,
         lambda: pre.lighting(tr, (0, 0), (n, n), SpotLight(lx, ly, 2000.0, cx, cy, 0.0, 8.0, 40.0), white, 2.0, 1.0, 20.0))
+    # feTile over the whole layer's box: 32 B written per pixel; what is read is the tile, over and over (64 x 64: 131 KB, from
+    # cache; 1024 x 1024: 33.5 MB).  The window (a result cut to its subregion) next to it: svgr_layer_compose_over with one source
+    for t in (64, 1024):
+        run(f"k_layer_tile {t}x{t} tile", px, lambda t=t: pre.tile((0, 0), (n, n), (17, 29), (t, t)))
+    run("k_layer_tile tile = output (a crop by one pixel)", 2 * px, lambda: pre.tile((1, 1), (n, n), (1, 1), (n, n)))
+    run("k_layer_compose_over, one source (window, a crop by one pixel)", 2 * px, lambda: pre.window((1, 1), (n, n)))
     for r in res:
         print(json.dumps(r))
 

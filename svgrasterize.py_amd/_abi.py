@@ -158,6 +158,7 @@ _PROTOS = {
     "svgr_layer_displacement_map": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_int, C.c_int]),
     "svgr_layer_lighting": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int]),
     "svgr_layer_mix_blend": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int]),
+    "svgr_layer_tile": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "svgr_gradient_fill": (C.c_int, [_P, C.POINTER(Gradient), _P, _P, _P]),
     "svgr_gradient_eval": (C.c_int, [_P, C.POINTER(Gradient), _P, C.c_int64, _P]),
     "svgr_pattern_fill": (C.c_int, [_P, C.POINTER(PatternArgs), _P, _P, _P, _P]),

@@ -932,4 +932,25 @@ SVGR_HD uint32_t jpeg_rgba(int colour, int s0, int s1, int s2) {
     return (uint32_t)r | (uint32_t)g << 8 | (uint32_t)b << 16 | 0xFF000000u;
 }
 
+
+// =====================================================================================
+// feTile (k_layer_tile; beyond the reference): which pixel of the source layer an output pixel copies.
+// Along one axis the tile covers the device coordinates [t0, t0 + tn) and the source layer [s0, s0 + sn).
+// The output coordinate p repeats the tile: its tile coordinate is t = (p - t0) floor-mod tn (p may lie
+// before t0; the caller keeps p - t0 inside an int), the next coordinate's is tile_next(t) -- a walk
+// along an axis takes one modulo, not one per pixel --, and what p copies is the source index
+// t0 + t - s0, or nothing (-1: transparent) where the tile reaches beyond the layer.  With t0 = the
+// output's first coordinate and tn = its extent nothing repeats and the map is a plain crop
+// ("window").  The two axes are independent.
+// =====================================================================================
+SVGR_HD int tile_wrap(int v, int n) {
+    const int m = v % n;
+    return m < 0 ? m + n : m;
+}
+SVGR_HD int tile_next(int t, int n) { return t + 1 == n ? 0 : t + 1; }
+SVGR_HD int tile_source(int t, int t0, int s0, int sn) {
+    const int64_t s = (int64_t)t0 + t - s0;
+    return s >= 0 && s < sn ? (int)s : -1;
+}
+
 }  // namespace svgr

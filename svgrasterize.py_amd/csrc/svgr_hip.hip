@@ -3746,6 +3746,36 @@ static decltype(&k_layer_mix_blend<0>) mix_blend_kernel(int mode, std::integer_s
     return k;
 }
 
+// feTile (svgr::tile_wrap / tile_next / tile_source): the output box (o0, o1, rows, cols) filled with repeats of the tile box
+// (t0, t1, trows, tcols) of the source layer (s0, s1, srows, scols), transparent where the tile reaches beyond the layer.  A pure
+// copy: every output pixel is written once, nothing is cleared in front.  One lane moves one 16-byte half of an RGBA-f64 pixel
+// (a wave's accesses are 1 KiB contiguous in the output, and in the source up to the tile's seam) down kTileRows output rows:
+// the column's modulo once per lane, the rows' once per workgroup (uniform: scalar) and a wrapping increment from row to row;
+// all loads of a lane are issued before its first store.
+constexpr int kTileRows = 8;
+struct TileLaunch {
+    int o0, o1, rows, cols, t0, t1, trows, tcols, s0, s1, srows, scols;
+    int chunks;   // workgroups per output row: ceil(2 * cols / 256)
+};
+__global__ __launch_bounds__(256) void k_layer_tile(double2* __restrict__ out, const double2* __restrict__ src, TileLaunch a) {
+    const int chunk = (int)(blockIdx.x % (unsigned)a.chunks), R0 = (int)(blockIdx.x / (unsigned)a.chunks) * kTileRows;
+    const int h = chunk * 256 + (int)threadIdx.x;   // (half pixel h of the row: pixel h / 2, doubles 2 (h % 2) ..)
+    if (h >= 2 * a.cols) return;
+    const int sc = svgr::tile_source(svgr::tile_wrap(a.o1 - a.t1 + (h >> 1), a.tcols), a.t1, a.s1, a.scols);
+    int tr = svgr::tile_wrap(a.o0 - a.t0 + R0, a.trows);
+    double2 v[kTileRows];
+    SVGR_UNROLL
+    for (int k = 0; k < kTileRows; ++k) {
+        const int sr = svgr::tile_source(tr, a.t0, a.s0, a.srows);
+        v[k] = make_double2(0.0, 0.0);
+        if (R0 + k < a.rows && sr >= 0 && sc >= 0) v[k] = src[((size_t)sr * a.scols + sc) * 2 + (h & 1)];
+        tr = svgr::tile_next(tr, a.trows);
+    }
+    SVGR_UNROLL
+    for (int k = 0; k < kTileRows; ++k)
+        if (R0 + k < a.rows) out[(size_t)(R0 + k) * a.cols * 2 + h] = v[k];
+}
+
 // luminance mask (S:735): out(1 channel) = (rgb @ [0.2125, 0.7154, 0.072]) * alpha of a straight-alpha layer
 __global__ void k_layer_luminance(double* __restrict__ out, const double* __restrict__ src, size_t n_px) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -6844,6 +6874,30 @@ int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, c
     a.tiles_x = (a.cols + kLightTile - 1) / kLightTile;
     return launch_tail(ctx, k_layer_lighting, dim3((unsigned)tiles), dim3(kLightTile, kLightTile), 0, (double*)out->ptr,
                        (const double*)src->ptr, a);
+}
+
+int svgr_layer_tile(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
+                    const int64_t* tile_bbox) {
+    if (!ctx || !out || !src || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || !bbox_ok(tile_bbox))
+        return fail(SVGR_E_INVALID, "svgr_layer_tile: bad arguments");
+    if (out_bbox[2] == 0 || out_bbox[3] == 0 || tile_bbox[2] == 0 || tile_bbox[3] == 0)
+        return fail(SVGR_E_INVALID, "svgr_layer_tile: empty tile or output");
+    // (the kernel's index arithmetic is 32-bit: an output coordinate relative to the tile's origin, and the half pixels of a row)
+    for (int k = 0; k < 2; ++k)
+        if (std::llabs(out_bbox[k] - tile_bbox[k]) + out_bbox[2 + k] + kTileRows >= (1ll << 31)) return fail(SVGR_E_INVALID, "svgr_layer_tile: output too far from the tile");
+    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
+    const size_t chunks = ((size_t)out_bbox[3] * 2 + 255) / 256;
+    const size_t groups = chunks * (size_t)((out_bbox[2] + kTileRows - 1) / kTileRows);
+    if (out_bbox[3] >= (1ll << 29) || groups > 0x7fffffff) return fail(SVGR_E_INVALID, "svgr_layer_tile: output too large");
+    if (out->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+        return fail(SVGR_E_INVALID, "svgr_layer_tile: buffer too small");
+    if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_tile: out must not be src");
+    TileLaunch a;
+    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
+    a.t0 = (int)tile_bbox[0]; a.t1 = (int)tile_bbox[1]; a.trows = (int)tile_bbox[2]; a.tcols = (int)tile_bbox[3];
+    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
+    a.chunks = (int)chunks;
+    return launch_tail(ctx, k_layer_tile, dim3((unsigned)groups), dim3(256), 0, (double2*)out->ptr, (const double2*)src->ptr, a);
 }
 
 int svgr_layer_mix_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* backdrop, const int64_t* bb, int bch,

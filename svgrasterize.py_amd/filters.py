@@ -16,7 +16,23 @@ objectBoundingBox, -10% / -10% / 120% / 120%), resolved at call time against the
 source layer's extent when there is no hull) and rounded out to whole device pixels.  The other primitives keep the extent
 of their input; in particular feComponentTransfer leaves the pixels outside its input transparent even where feFuncA maps
 0 to something else.  Light sources stay in user space in the chain and are mapped to device space at call time
-(``Layer.lighting``).  Primitive subregions and ``primitiveUnits`` are not supported."""
+(``Layer.lighting``).
+
+Primitive subregions (``Filter.subregion``; x / y / width / height on a primitive) and ``primitiveUnits`` (``Filter.empty``'s
+`primitive_bbox`) follow Filter Effects 1 on the device-pixel grid.  A primitive with at least one of the four has a subregion;
+the missing ones come from its default subregion: the union of the subregions of the results it references when each has one,
+else the filter region (always the filter region for feTile, whose purpose is to cover more than its input).  A primitive without any has the union of its inputs' subregions when each has one and otherwise NONE:
+it runs as described above, which keeps filters without these attributes bit for bit what they were.  A subregion is a
+rectangle in user space (fractions of the bounding box under objectBoundingBox) and becomes the integer box around its
+transformed corners, cut to the filter region's box -- under a rotation the axis-aligned box around the rotated rectangle,
+as for the filter region.  The result of a primitive with box B is a layer of exactly B (``Layer.window``); generators,
+lighting, feTile and feImage fill B instead of the filter region; an empty B is a transparent result.  Under
+objectBoundingBox the lengths of feGaussianBlur / feOffset / feMorphology (and feDropShadow) are fractions of the box too;
+light positions, ``surfaceScale`` and feDisplacementMap's ``scale`` are not rescaled.
+
+feTile (``Layer.tile``, ``svgr_layer_tile``) repeats the subregion of its input (the filter region when the input has none) over
+its own box.  feImage draws a raster (placed into its subregion by ``preserveAspectRatio`` and sampled by the image fill) or an
+element of the document (looked up when the filter runs; rendered in the filtered element's user space, like ``<use>``)."""
 from __future__ import annotations
 
 import math
@@ -32,6 +48,7 @@ import warnings
 FE_BLEND, FE_COLOR_MATRIX, FE_COMPONENT_TRANSFER, FE_COMPOSITE, FE_CONVOLVE_MATRIX = 0, 1, 2, 3, 4  # S:1716-1730
 FE_DIFFUSE_LIGHTING, FE_DISPLACEMENT_MAP, FE_FLOOD, FE_GAUSSIAN_BLUR, FE_MERGE = 5, 6, 7, 8, 9
 FE_MORPHOLOGY, FE_OFFSET, FE_SPECULAR_LIGHTING, FE_TILE, FE_TURBULENCE = 10, 11, 12, 13, 14
+FE_IMAGE = 15   # (not in the reference's list)
 COLOR_MATRIX_LUM = np.array([[0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0, 0, 0, 0, 0], [0.2125, 0.7154, 0.0721, 0, 0]], dtype=np.float64)
 # feColorMatrix type="saturate" / "hueRotate" (the SVG 1.1 filter chapter's constants; S:1740-1747): the colour block is
 # _HUE_BASE + cos(a) * _HUE_COS + sin(a) * _HUE_SIN; saturate(s) is the same with (cos, sin) := (s, 0)
@@ -170,13 +187,42 @@ def _blur_weights(transform: Transform, sigma_x: float, sigma_y: float):
     return weights / weights.sum()
 
 
+def _device_box(transform: Transform, rect):
+    """(row0, col0, row1, col1): the integer box (floor / ceil) around the four transformed corners of the user-space
+    rectangle `rect` = (x, y, width, height) -- ``filter_region``'s rounding, without its one-pixel minimum."""
+    x, y, w, h = rect
+    corners = transform(np.array([[x, y], [x + w, y], [x, y + h], [x + w, y + h]], dtype=np.float64))
+    lo, hi = np.floor(corners.min(axis=0)), np.ceil(corners.max(axis=0))
+    return int(lo[0]), int(lo[1]), int(hi[0]), int(hi[1])
+
+
+def _union(regions):
+    """The union of resolved subregions [(rect, box)]: the bounding rectangle in user space and the bounding device box."""
+    rects, boxes = [r for r, _ in regions], [b for _, b in regions]
+    x0, y0 = min(r[0] for r in rects), min(r[1] for r in rects)
+    x1, y1 = max(r[0] + r[2] for r in rects), max(r[1] + r[3] for r in rects)
+    r0, c0 = min(b[0] for b in boxes), min(b[1] for b in boxes)
+    r1, c1 = max(b[0] + b[2] for b in boxes), max(b[1] + b[3] for b in boxes)
+    return (x0, y0, x1 - x0, y1 - y0), (r0, c0, r1 - r0, c1 - c0)
+
+
+_IMAGE_ACTIVE: set = set()   # the feImage element references being rendered (a reference that leads back to itself stops there)
+
+
 class Filter(NamedTuple):
     names: dict
     filters: list  # [(type, attrs, inputs)]
+    # entry index -> the primitive's subregion (x, y, width, height), None = not given; for the two entries of a drop shadow
+    # that share one see ``drop_shadow``.  Entries without one are not in the table.
+    subregions: dict = {}
+    primitive_bbox: bool = False   # primitiveUnits="objectBoundingBox"
+    # the <filter>'s region in the form of FILTER_REGION_DEFAULT: the frame of the subregions and what feTile / feImage cover
+    # without one (the older generators carry the region in their own attrs)
+    region: tuple | None = None
 
     @classmethod
-    def empty(cls) -> "Filter":
-        return cls({FE_SOURCE_ALPHA: 0, FE_SOURCE_GRAPHIC: 1}, [])
+    def empty(cls, primitive_bbox: bool = False, region=None) -> "Filter":
+        return cls({FE_SOURCE_ALPHA: 0, FE_SOURCE_GRAPHIC: 1}, [], {}, bool(primitive_bbox), region)
 
     def add_filter(self, type, attrs, inputs, result=None) -> "Filter":
         names, filters = dict(self.names), list(self.filters)
@@ -187,7 +233,37 @@ class Filter(NamedTuple):
         if result is not None:
             names[result] = len(filters) + 2
         filters.append((type, attrs, args))
-        return Filter(names, filters)
+        return self._replace(names=names, filters=filters)
+
+    def subregion(self, x=None, y=None, width=None, height=None) -> "Filter":
+        """The primitive subregion of the entry added last, in primitiveUnits (user space, or fractions of the bounding box);
+        None = not given (it comes from the default subregion).  A negative `width` or `height` is an error here; 0 makes the
+        result transparent."""
+        if not self.filters:
+            raise ValueError("subregion: the filter has no primitive yet")
+        vals = tuple(None if v is None else float(v) for v in (x, y, width, height))
+        if any(v is not None and v < 0 for v in vals[2:]):
+            raise ValueError(f"negative subregion size: {vals[2]}, {vals[3]}")
+        table = dict(self.subregions)
+        table[len(self.filters) - 1] = vals
+        return self._replace(subregions=table)
+
+    def tile(self, input=None, result=None) -> "Filter":
+        """feTile: the subregion of `input` (the filter region when it has none) repeated over this primitive's subregion
+        (``subregion``; the filter region without one)."""
+        return self.add_filter(FE_TILE, tuple(), [input], result)
+
+    def image(self, pixels=None, preserve_aspect_ratio="xMidYMid meet", smooth=True, element=None, ids=None, result=None) -> "Filter":
+        """feImage: the (h, w, 4) uint8 straight-alpha sRGB raster `pixels` placed into the primitive's subregion like an
+        <image> into its viewport; or the scene ``ids[element]``, looked up when the filter runs and rendered in the filtered
+        element's user space.  With neither (a source that could not be read) the result is transparent."""
+        if pixels is not None:
+            attrs = ("raster", np.asarray(pixels), preserve_aspect_ratio, bool(smooth))
+        elif element is not None:
+            attrs = ("element", element, None if ids is None else ids.get)   # (the look-up, not the table: a short repr)
+        else:
+            attrs = ("none",)
+        return self.add_filter(FE_IMAGE, attrs, [], result)
 
     def offset(self, dx, dy, input=None, result=None) -> "Filter":
         return self.add_filter(FE_OFFSET, (dx, dy), [input], result)
@@ -243,9 +319,11 @@ class Filter(NamedTuple):
                                                       float(specular_constant), float(specular_exponent), region), [input], result)
 
     def drop_shadow(self, dx=2.0, dy=2.0, std_x=2.0, std_y=None, color=(0.0, 0.0, 0.0, 1.0), region=None, input=None,
-                    result=None) -> "Filter":
+                    result=None, subregion=None) -> "Filter":
         """feDropShadow as the six entries it stands for: the alpha of `input`, blurred, offset, a flood of `color` IN that
-        shadow, and the merge of [shadow, `input`].  Only the merge can be named (`result`)."""
+        shadow, and the merge of [shadow, `input`].  Only the merge can be named (`result`).  `subregion` = (x, y, width,
+        height) as in ``subregion``: it applies to the merge -- its default is the subregion of `input`, feDropShadow's one
+        input -- and the flood fills the same box."""
         names, filters = dict(self.names), list(self.filters)
         src = names.get(input) if input is not None else None
         src = len(filters) + 1 if src is None else src   # (the default input: add_filter's rule)
@@ -258,11 +336,87 @@ class Filter(NamedTuple):
         filters.append((FE_MERGE, tuple(), [at + 4, src]))
         if result is not None:
             names[result] = at + 5
-        return Filter(names, filters)
+        table = self.subregions
+        if subregion is not None:
+            merged = self._replace(names=names, filters=filters).subregion(*subregion)
+            table = dict(merged.subregions)
+            table[len(filters) - 1] = (*table[len(filters) - 1], [src])   # (the default subregion: from `input` alone)
+            table[len(filters) - 3] = len(filters) - 1                     # (the flood: the box of the merge)
+        return self._replace(names=names, filters=filters, subregions=table)
+
+    def _regions(self, transform: Transform, source: Layer, hull, frame):
+        """stack index -> the result's subregion ((x, y, width, height) in user space, (row0, col0, rows, cols) in device
+        pixels) or None; `frame` = the filter region in the same form.  See the module docstring."""
+        memo: dict = {}
+        bbox = _user_bbox(transform, source, hull) if self.primitive_bbox else None
+        f0, f1, frows, fcols = frame[1]
+
+        def region(s):
+            if s < 2:
+                return None   # (SourceAlpha, SourceGraphic)
+            if s in memo:
+                return memo[s]
+            _ftype, _attrs, inputs = self.filters[s - 2]
+            spec = self.subregions.get(s - 2)
+            if isinstance(spec, int):   # (a drop shadow's flood: the box of its merge)
+                res = region(spec + 2)
+            else:
+                refs = [region(j) for j in (inputs if spec is None or len(spec) == 4 else spec[4])]
+                res = _union(refs) if refs and all(r is not None for r in refs) else None
+                if _ftype == FE_TILE:   # (the specification's exception: feTile is there to cover more than its input)
+                    res = frame
+                if spec is not None:
+                    vals = spec[:4]
+                    if bbox is not None:
+                        bx, by, bw, bh = bbox
+                        vals = tuple(None if v is None else o + v * n for v, o, n in zip(vals, (bx, by, 0.0, 0.0), (bw, bh, bw, bh)))
+                    rect = tuple(d if v is None else v for v, d in zip(vals, (frame if res is None else res)[0]))
+                    r0, c0, r1, c1 = _device_box(transform, rect)
+                    if not (rect[2] > 0 and rect[3] > 0):
+                        r1, c1 = r0, c0
+                    r0, c0, r1, c1 = max(r0, f0), max(c0, f1), min(r1, f0 + frows), min(c1, f1 + fcols)
+                    rows, cols = max(r1 - r0, 0), max(c1 - c0, 0)
+                    res = (rect, (r0, c0, rows, cols) if rows and cols else (r0, c0, 0, 0))
+            memo[s] = res
+            return res
+
+        return region
+
+    def _image(self, attrs, transform: Transform, source: Layer, rect):
+        """feImage's picture as a layer (any extent), or None: see ``image``.  `rect`: the subregion in user space."""
+        from .scene import Scene   # noqa: PLC0415 (scene imports this module)
+
+        kind = attrs[0]
+        if kind == "raster":
+            _, pixels, par, smooth = attrs
+            scene = Scene.image(pixels, *rect, par, smooth)
+            if scene is None:
+                return None
+            key = None
+        elif kind == "element":
+            _, name, lookup = attrs
+            scene = None if lookup is None else lookup(name)
+            if not isinstance(scene, Scene):
+                warnings.warn(f"feImage: no drawable element with id: {name}")
+                return None
+            key = id(attrs)
+            if key in _IMAGE_ACTIVE:
+                warnings.warn(f"feImage: element {name} is drawn through this very feImage: transparent")
+                return None
+            _IMAGE_ACTIVE.add(key)
+        else:
+            return None
+        try:
+            # (inside the filtered element's render: Scene.render's lock is re-entrant, and without a viewport the walk shares the
+            #  outer render's state, like a pattern's tile)
+            res = scene.render(transform, linear_rgb=source.linear_rgb)
+        finally:
+            _IMAGE_ACTIVE.discard(key)
+        return None if res is None else res[0]
 
     def __call__(self, transform: Transform, source: Layer, hull=None) -> Layer:
         """Execute the filter chain on `source` (S:1801-1831).  `hull`: the filtered node's ConvexHull, the frame of an
-        objectBoundingBox filter region (only the generators use the region)."""
+        objectBoundingBox filter region and of objectBoundingBox primitive units."""
         stack: list = [None, source.convert(pre_alpha=False, linear_rgb=True)]
 
         def get(i):
@@ -271,14 +425,41 @@ class Filter(NamedTuple):
                 stack[0] = Layer(alpha, source.offset, pre_alpha=True, linear_rgb=True)
             return stack[i]
 
-        for ftype, attrs, inputs in self.filters:
+        frame = regions = None
+        if self.subregions or any(f[0] in (FE_TILE, FE_IMAGE) for f in self.filters):
+            f_off, f_shape, f_rect = filter_region(self.region, transform, source, hull)
+            frame = (f_rect, (*f_off, *f_shape))
+            if self.subregions:
+                regions = self._regions(transform, source, hull, frame)
+        unit_x = unit_y = 1.0   # a primitive's lengths in user units: fractions of the bounding box under objectBoundingBox
+        if self.primitive_bbox:
+            _, _, unit_x, unit_y = _user_bbox(transform, source, hull)
+
+        for index, (ftype, attrs, inputs) in enumerate(self.filters):
+            sub = None if regions is None else regions(index + 2)
+            box = None if sub is None else sub[1]
+            if box is not None and box[2] * box[3] == 0:   # (an empty subregion: nothing to compute)
+                stack.append(Layer.transparent(box[:2]))
+                continue
+
+            def area(region):
+                """(offset, shape, user rectangle) a generator fills: its subregion, or without one the filter region"""
+                if box is not None:
+                    return box[:2], box[2:], sub[0]
+                return filter_region(region, transform, source, hull)
+
             args = [get(i) for i in inputs]
             if ftype == FE_GAUSSIAN_BLUR:
                 std_x, std_y = attrs
-                kernel = blur_kernel(transform, (std_x, std_x if std_y is None else std_y))
+                std_y = std_x if std_y is None else std_y
+                if self.primitive_bbox:
+                    std_x, std_y = std_x * unit_x, std_y * unit_y
+                kernel = blur_kernel(transform, (std_x, std_y))
                 res = args[0] if kernel is None else args[0].convolve(kernel)
             elif ftype == FE_OFFSET:  # S:1844-1850
                 dx, dy = attrs
+                if self.primitive_bbox:
+                    dx, dy = dx * unit_x, dy * unit_y
                 x, y = args[0].offset
                 tx, ty = transform(transform.invert([x, y]) + [dx, dy])
                 res = args[0].translate(int(tx) - x, int(ty) - y)
@@ -298,16 +479,18 @@ class Filter(NamedTuple):
                     res = args[0].color_matrix(matrix)
             elif ftype == FE_MORPHOLOGY:  # S:1853-1864
                 rx, ry, method = attrs
+                if self.primitive_bbox:
+                    rx, ry = rx * unit_x, ry * unit_y
                 ux, uy = transform([[rx, 0], [0, ry]]) - transform([[0, 0], [0, 0]])
                 x, y = int(np.linalg.norm(ux) * 2), int(np.linalg.norm(uy) * 2)
                 res = args[0] if x < 1 or y < 1 else args[0].morphology(x, y, method)
             elif ftype == FE_FLOOD:
                 color, region = attrs
-                offset, shape, _ = filter_region(region, transform, source, hull)
+                offset, shape, _ = area(region)
                 res = Layer.flood(color, offset, shape)
             elif ftype == FE_TURBULENCE:
                 freq, octaves, seed, stitch, fractal, region = attrs
-                offset, shape, rect = filter_region(region, transform, source, hull)
+                offset, shape, rect = area(region)
                 res = Layer.turbulence(transform, offset, shape, freq, octaves, seed, rect if stitch else None, fractal)
             elif ftype == FE_COMPONENT_TRANSFER:
                 res = args[0].component_transfer(attrs[0])
@@ -319,13 +502,31 @@ class Filter(NamedTuple):
                 res = args[0].displacement_map(args[1], transform, scale, x_channel, y_channel)
             elif ftype == FE_DIFFUSE_LIGHTING:
                 light, color, surface_scale, constant, region = attrs
-                offset, shape, _ = filter_region(region, transform, source, hull)
+                offset, shape, _ = area(region)
                 res = args[0].lighting(transform, offset, shape, light, color, surface_scale, constant)
             elif ftype == FE_SPECULAR_LIGHTING:
                 light, color, surface_scale, constant, exponent, region = attrs
-                offset, shape, _ = filter_region(region, transform, source, hull)
+                offset, shape, _ = area(region)
                 res = args[0].lighting(transform, offset, shape, light, color, surface_scale, constant, exponent)
+            elif ftype == FE_TILE:
+                # the tile: the input's subregion, or without one the filter region; the output: this primitive's, likewise
+                of = None if regions is None else regions(inputs[0])
+                tile = frame[1] if of is None else of[1]
+                out = frame[1] if box is None else box
+                if tile[2] * tile[3] == 0:
+                    res = Layer.transparent(out[:2])
+                else:
+                    res = args[0].tile(out[:2], out[2:], tile[:2], tile[2:])
+            elif ftype == FE_IMAGE:
+                out, rect = (frame[1], frame[0]) if box is None else (box, sub[0])
+                res = self._image(attrs, transform, source, rect)
+                res = Layer.transparent(out[:2]) if res is None else res.window(out[:2], out[2:])
             else:
                 raise ValueError(f"unsupported filter type: {ftype}")
+            if box is not None:   # the result is a layer of exactly the subregion's box
+                if res is None:
+                    res = Layer.transparent(box[:2])
+                elif (int(res.x), int(res.y), res.height, res.width) != box:
+                    res = res.window(box[:2], box[2:])
             stack.append(res)
         return get(len(stack) - 1)

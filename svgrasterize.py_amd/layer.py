@@ -484,6 +484,52 @@ class Layer:
                                                 float(specular_exponent) if specular else 1.0, int(specular)))
         return Layer._from_device(out, (rows, cols, 4), offset, pre_alpha=specular, linear_rgb=True)
 
+    # -- filter primitive subregions and feTile: copies, so the result keeps this layer's alpha convention and colour space ------
+    @classmethod
+    def transparent(cls, offset, pre_alpha: bool = True, linear_rgb: bool = True) -> "Layer":
+        """The empty result of the filter chain (a subregion without pixels): layers hold at least one pixel, so one
+        transparent pixel at `offset`."""
+        buf = _abi.Context.get().alloc(32)
+        buf.zero()
+        return cls._from_device(buf, (1, 1, 4), (int(offset[0]), int(offset[1])), pre_alpha, linear_rgb)
+
+    def window(self, offset, shape) -> "Layer":
+        """This layer seen through the (rows, cols) box at `offset`: its pixels where it covers the box, transparent black
+        elsewhere, bit for bit.  One pass that writes the box whole (``svgr_layer_compose_over`` with this one source)."""
+        if self.channels != 4:
+            raise ValueError("window expects an RGBA layer")
+        rows, cols = int(shape[0]), int(shape[1])
+        offset = (int(offset[0]), int(offset[1]))
+        if rows <= 0 or cols <= 0:
+            return Layer.transparent(offset, self.pre_alpha, self.linear_rgb)
+        if offset == (int(self.x), int(self.y)) and (rows, cols) == self._shape[:2]:
+            return self
+        ctx = _abi.Context.get()
+        out = ctx.alloc(rows * cols * 32)
+        src = self._dev if self._host is None else self._device()   # (a noted conversion runs as the pixels are read)
+        _abi._check(ctx.lib.svgr_layer_compose_over(ctx.handle, out.handle, _bbox_arr(offset, (rows, cols)), 1, (_abi._P * 1)(src.handle),
+                                                    _bbox_arr(self.offset, self._shape), (C.c_int32 * 1)(4),
+                                                    (C.c_uint32 * 1)(self._ops if self._host is None else 0)))
+        return Layer._from_device(out, (rows, cols, 4), offset, self.pre_alpha, self.linear_rgb)
+
+    def tile(self, offset, shape, tile_offset, tile_shape) -> "Layer":
+        """feTile: the (rows, cols) = `shape` box at `offset` filled with repeats of the tile -- this layer seen through the
+        `tile_shape` box at `tile_offset`, transparent where the layer does not reach it: result[r, c] = tile[(r - tile row0) mod
+        tile rows, (c - tile col0) mod tile cols] in device coordinates (floor modulo).  A copy, bit for bit, in one launch
+        (``svgr_layer_tile``)."""
+        if self.channels != 4:
+            raise ValueError("tile expects an RGBA layer")
+        rows, cols = int(shape[0]), int(shape[1])
+        offset = (int(offset[0]), int(offset[1]))
+        if rows <= 0 or cols <= 0 or int(tile_shape[0]) <= 0 or int(tile_shape[1]) <= 0:
+            raise ValueError("tile expects a tile and an output of at least one pixel")
+        ctx = _abi.Context.get()
+        out = ctx.alloc(rows * cols * 32)
+        src = self._device()
+        _abi._check(ctx.lib.svgr_layer_tile(ctx.handle, out.handle, _bbox_arr(offset, (rows, cols)), src.handle,
+                                            _bbox_arr(self.offset, self._shape), _bbox_arr(tile_offset, tile_shape)))
+        return Layer._from_device(out, (rows, cols, 4), offset, self.pre_alpha, self.linear_rgb)
+
     # -- Layer.compose  S:177-207 ----------------------------------------------------------
     @staticmethod
     def compose(layers: Sequence["Layer"], method: int = COMPOSE_OVER, linear_rgb: bool = False) -> "Layer | None":

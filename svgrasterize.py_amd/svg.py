@@ -10,7 +10,9 @@ Supported: svg (nested, viewBox), g, defs, path, rect, circle, ellipse, line, po
 linearGradient / radialGradient / stop, pattern, clipPath, mask, filter (feOffset, feGaussianBlur, feMerge, feBlend, feComposite,
 feColorMatrix matrix / saturate / hueRotate / luminanceToAlpha, feMorphology, and beyond the reference feFlood, feTurbulence,
 feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow, feDiffuseLighting, feSpecularLighting with feDistantLight /
-fePointLight / feSpotLight; the <filter>'s region for the generators and the lighting primitives), text / tspan set in
+fePointLight / feSpotLight, feTile, feImage (a raster from <image>'s sources, or ``#id``: an element, looked up when the filter runs);
+the <filter>'s region for the generators and the lighting primitives; x / y / width / height on a primitive -- its subregion --
+and ``primitiveUnits``, see ``filters.py``), text / tspan set in
 SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``), presentation attributes and ``style``, and beyond the
 reference image (PNG or JPEG, from a base64 ``data:image/png`` / ``data:image/jpeg`` URI or a local file next to the document, the
 decoder picked by the data's first bytes; ``png.py``, ``jpeg.py``) and CSS
@@ -35,7 +37,8 @@ import xml.etree.ElementTree as etree
 import numpy as np
 
 from .filters import (
-    COLOR_MATRIX_LUM, CONVOLVE_MATRIX_MAX_ORDER, TRANSFER_MAX_VALUES, TURBULENCE_MAX_OCTAVES, DistantLight, Filter, PointLight,
+    COLOR_MATRIX_LUM, CONVOLVE_MATRIX_MAX_ORDER, FE_IMAGE, FE_TILE, TRANSFER_MAX_VALUES, TURBULENCE_MAX_OCTAVES, DistantLight, Filter,
+    PointLight,
     SpotLight, color_matrix_hue_rotate, color_matrix_saturate,
 )
 from .fonts import FONT_STYLE_NORMAL, Font, FontsDB, Glyph
@@ -506,16 +509,51 @@ def _lighting_args(element, tag):
     return light, tuple(rgb), parse_float(attrs.get("surfaceScale", "1")), constant, exponent
 
 
-def _filter(element) -> Filter:
+def _primitive_subregion(attrs, tag, bbox_units):
+    """x / y / width / height of a filter primitive in the form of ``Filter.subregion``; None without any.  Under
+    userSpaceOnUse a percentage warns and counts as absent (the viewport is not known here); a negative width or height warns
+    and leaves the primitive its default subregion (four None)."""
+    vals = []
+    for key in ("x", "y", "width", "height"):
+        text = attrs.get(key)
+        if text is not None and text.strip().endswith("%") and not bbox_units:
+            warnings.warn(f"{tag}: {key}=\"{text.strip()}\" needs the viewport, which is not known here: ignored")
+            text = None
+        vals.append(parse_float(text) if bbox_units else parse_size(text))
+    if all(v is None for v in vals):
+        return None
+    if any(v is not None and v < 0 for v in vals[2:]):
+        warnings.warn(f"{tag}: negative subregion size: {vals[2]}, {vals[3]}: the default subregion is used")
+        return (None, None, None, None)
+    return tuple(vals)
+
+
+def _filter(element, loader=None) -> Filter:
     """<filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap,
-    feDropShadow, feDiffuseLighting and feSpecularLighting beyond the reference)."""
-    flt = Filter.empty()
+    feDropShadow, feDiffuseLighting, feSpecularLighting, feTile, feImage, primitive subregions and primitiveUnits beyond the
+    reference).  `loader`: the document's loader, which reads feImage's rasters and holds the ids its element references are
+    looked up in when the filter runs."""
     region = _filter_region(element.attrib)
+    units = element.attrib.get("primitiveUnits")
+    if units is not None and units not in (UNITS_BBOX, UNITS_USER):
+        warnings.warn(f"invalid primitive units: {units}")
+        units = UNITS_USER
+    flt = Filter.empty(units == UNITS_BBOX)
+    bbox_units = flt.primitive_bbox
+    unscaled = set()   # what objectBoundingBox primitive units do not rescale, for one warning
     for child in element:
         tag = child.tag.split("}")[-1]
         attrs = child.attrib
         result, src = attrs.get("result"), attrs.get("in")
-        if tag == "feFlood":
+        before = len(flt.filters)
+        sub = _primitive_subregion(attrs, tag, bbox_units) if tag.startswith("fe") else None
+        if bbox_units and tag in ("feDiffuseLighting", "feSpecularLighting", "feDisplacementMap"):
+            unscaled.add(tag)
+        if tag == "feTile":
+            flt = flt.tile(src, result)
+        elif tag == "feImage":
+            flt = _fe_image(flt, attrs, loader, result)
+        elif tag == "feFlood":
             color = _flood_color(_expand_style(attrs))
             if color is not None:
                 flt = flt.flood(color, region, result)
@@ -555,7 +593,8 @@ def _filter(element) -> Filter:
             std_x, std_y = stds * 2 if len(stds) == 1 else stds
             if color is not None:
                 flt = flt.drop_shadow(parse_float(attrs.get("dx", "2")), parse_float(attrs.get("dy", "2")), std_x, std_y, color,
-                                      region, src, result)
+                                      region, src, result, sub)
+                sub = None
         elif tag in ("feDiffuseLighting", "feSpecularLighting"):
             args = _lighting_args(child, tag)
             if args is not None:
@@ -610,7 +649,35 @@ def _filter(element) -> Filter:
                 flt = flt.morphology(rx, ry, method, src, result)
         else:
             warnings.warn(f"unsupported filter type: {tag}")
+        if sub is not None and len(flt.filters) > before:
+            flt = flt.subregion(*sub)
+    if flt.subregions or flt.primitive_bbox or any(f[0] in (FE_TILE, FE_IMAGE) for f in flt.filters):
+        flt = flt._replace(region=region)   # (a chain without any of them stays what it has always been)
+    if unscaled:
+        warnings.warn(f"primitiveUnits=\"objectBoundingBox\": light positions, surfaceScale and the displacement scale stay in user "
+                      f"units ({', '.join(sorted(unscaled))})")
     return flt
+
+
+def _fe_image(flt: Filter, attrs, loader, result) -> Filter:
+    """<feImage>: a raster (the sources and warnings of <image>) or ``#id``, an element of the document.  Whatever cannot be
+    read still takes its place in the chain, with a transparent result."""
+    href = attrs.get("href")
+    if href is None:
+        href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
+    if href is not None and href.strip().startswith("#"):
+        return flt.image(element=href.strip()[1:], ids=None if loader is None else loader.ids, result=result)
+    pixels = (loader if loader is not None else _Loader(None, None)).image_pixels(href)
+    if pixels is None:
+        return flt.image(result=result)
+    par = attrs.get("preserveAspectRatio", "xMidYMid meet")
+    try:
+        parse_preserve_aspect_ratio(par)
+    except ValueError:
+        warnings.warn(f"invalid preserveAspectRatio: {par!r}, using xMidYMid meet")
+        par = "xMidYMid meet"
+    smooth = _expand_style(attrs).get("image-rendering", "auto").strip().lower() not in _NEAREST
+    return flt.image(pixels, par, smooth, result=result)
 
 
 def _font_weight(text) -> int:
@@ -972,7 +1039,7 @@ class _Loader:
                 ids[attrs["id"]] = (scene, attrs.get("maskContentUnits") == UNITS_BBOX)
         elif tag == "filter":
             if attrs.get("id") is not None:
-                ids[attrs["id"]] = _filter(element)
+                ids[attrs["id"]] = _filter(element, self)
         elif tag == "pattern":  # S:2914-2951
             if attrs.get("id") is not None:
                 w, h = parse_float(attrs.get("width")), parse_float(attrs.get("height"))

@@ -1,0 +1,158 @@
+"""numpy restatement of filter primitive subregions and feTile (Filter Effects 1, "Filter primitive subregion") on the device
+pixel grid: subregion resolution to boxes, the window (a result cut to its box), the tile, and a small chain evaluator for the
+primitives the subregion tests use.  Written from the specification's rules, not from svgrasterize_amd/filters.py; boxes are
+(row0, col0, rows, cols), images straight-alpha linear RGBA float64.  Also loads the host build of svgr_core.h's tile index
+functions (tests/subregion_harness.cpp)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HARNESS = os.path.join(ROOT, "tests", "_subregion_harness.so")
+
+
+def harness():
+    src = os.path.join(ROOT, "tests", "subregion_harness.cpp")
+    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
+    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        tmp = f"{HARNESS}.{os.getpid()}"
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
+        os.replace(tmp, HARNESS)
+    L = C.CDLL(HARNESS)
+    L.sh_axis.argtypes = [C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                          np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")]
+    L.sh_axis.restype = None
+    return L
+
+
+def harness_axis(L, o0, n, t0, tn, s0, sn, walk):
+    out = np.zeros(n, dtype=np.int32)
+    L.sh_axis(o0, n, t0, tn, s0, sn, int(walk), out)
+    return out
+
+
+def axis_source(o0, n, t0, tn, s0, sn):
+    """Source index of the output coordinates o0 .. o0 + n - 1 along one axis (numpy's % is the floor modulo), -1 outside."""
+    s = t0 + (np.arange(o0, o0 + n) - t0) % tn - s0
+    return np.where((s >= 0) & (s < sn), s, -1).astype(np.int32)
+
+
+# -- boxes ------------------------------------------------------------------------------------------------------------------
+def device_box(tr, rect):
+    """The integer box (floor / ceil) around the transformed corners of the user-space rectangle (x, y, width, height);
+    a rectangle without area is an empty box."""
+    x, y, w, h = rect
+    pts = np.array([tr(np.array([px, py], dtype=np.float64)) for px, py in ((x, y), (x + w, y), (x, y + h), (x + w, y + h))])
+    r0, c0 = (math.floor(v) for v in pts.min(axis=0))
+    r1, c1 = (math.ceil(v) for v in pts.max(axis=0))
+    if not (w > 0 and h > 0):
+        return (r0, c0, 0, 0)
+    return (r0, c0, r1 - r0, c1 - c0)
+
+
+def intersect(a, b):
+    r0, c0 = max(a[0], b[0]), max(a[1], b[1])
+    r1, c1 = min(a[0] + a[2], b[0] + b[2]), min(a[1] + a[3], b[1] + b[3])
+    return (r0, c0, r1 - r0, c1 - c0) if r1 > r0 and c1 > c0 else (r0, c0, 0, 0)
+
+
+def union_boxes(boxes):
+    r0, c0 = min(b[0] for b in boxes), min(b[1] for b in boxes)
+    return (r0, c0, max(b[0] + b[2] for b in boxes) - r0, max(b[1] + b[3] for b in boxes) - c0)
+
+
+def union_rects(rects):
+    x0, y0 = min(r[0] for r in rects), min(r[1] for r in rects)
+    return (x0, y0, max(r[0] + r[2] for r in rects) - x0, max(r[1] + r[3] for r in rects) - y0)
+
+
+def resolve(chain, tr, frame_rect, bbox=None):
+    """The subregion of every entry of `chain` = [dict(inputs=[stack indices], sub=None | (x, y, width, height) with None for
+    a missing one, op=...)]: a list of None (no subregion) or (rect, box).  Stack indices 0 and 1 are the standard inputs, entry k is
+    index k + 2.  `frame_rect`: the filter region in user space; `bbox` = (x, y, width, height): the values are fractions of it
+    (primitiveUnits="objectBoundingBox")."""
+    frame = (tuple(frame_rect), device_box(tr, frame_rect))
+    out = [None, None]
+    for entry in chain:
+        refs = [out[i] for i in entry["inputs"]]
+        default = None
+        if refs and all(r is not None for r in refs):
+            default = (union_rects([r[0] for r in refs]), union_boxes([r[1] for r in refs]))
+        if entry.get("op") == "tile":   # (Filter Effects 1: feTile's default subregion is the filter region)
+            default = frame
+        sub = entry.get("sub")
+        if sub is None:
+            out.append(default)
+            continue
+        if bbox is not None:
+            bx, by, bw, bh = bbox
+            sub = tuple(None if v is None else o + v * n for v, o, n in zip(sub, (bx, by, 0, 0), (bw, bh, bw, bh)))
+        base = (frame if default is None else default)[0]
+        rect = tuple(b if v is None else v for v, b in zip(sub, base))
+        out.append((rect, intersect(device_box(tr, rect), frame[1])))
+    return out[2:], frame
+
+
+# -- pixels -----------------------------------------------------------------------------------------------------------------
+def window(img, off, box):
+    """`img` at `off` seen through `box`: zero where it does not reach."""
+    out = np.zeros((box[2], box[3], 4), dtype=np.float64)
+    r0, c0 = max(off[0], box[0]), max(off[1], box[1])
+    r1, c1 = min(off[0] + img.shape[0], box[0] + box[2]), min(off[1] + img.shape[1], box[1] + box[3])
+    if r1 > r0 and c1 > c0:
+        out[r0 - box[0]:r1 - box[0], c0 - box[1]:c1 - box[1]] = img[r0 - off[0]:r1 - off[0], c0 - off[1]:c1 - off[1]]
+    return out
+
+
+def tile(img, off, out_box, tile_box):
+    """out[r, c] = tile[(r - T.row0) mod T.rows, (c - T.col0) mod T.cols], tile = `img` at `off` seen through `tile_box`."""
+    t = window(img, off, tile_box)
+    rr = (np.arange(out_box[0], out_box[0] + out_box[2]) - tile_box[0]) % tile_box[2]
+    cc = (np.arange(out_box[1], out_box[1] + out_box[3]) - tile_box[1]) % tile_box[3]
+    return t[rr[:, None], cc[None, :]]
+
+
+def evaluate(chain, tr, source, source_off, frame_rect, bbox=None):
+    """The chain's last result as (image, offset).  Entries: dict(op=..., inputs, sub) with op "flood" (color: straight linear
+    RGBA), "offset" (dx, dy), "blur" (std: (x, y); the weights are svgrasterize_amd.filters.blur_kernel's, the convolution
+    scipy's) or "tile".  Stack index 1 is `source` (straight-alpha linear RGBA) at `source_off`; SourceAlpha is not modelled."""
+    from scipy.signal import convolve as sconv
+
+    from svgrasterize_amd.filters import blur_kernel
+
+    regions, frame = resolve(chain, tr, frame_rect, bbox)
+    ux, uy = (bbox[2], bbox[3]) if bbox is not None else (1.0, 1.0)
+    stack = [None, (source, tuple(source_off))]
+    for entry, region in zip(chain, regions):
+        box = None if region is None else region[1]
+        ins = [stack[i] for i in entry["inputs"]]
+        op = entry["op"]
+        if box is not None and box[2] * box[3] == 0:
+            stack.append((np.zeros((1, 1, 4)), box[:2]))
+            continue
+        if op == "flood":
+            b = frame[1] if box is None else box
+            res = (np.broadcast_to(np.array(entry["color"], dtype=np.float64), (b[2], b[3], 4)).copy(), b[:2])
+        elif op == "offset":
+            img, (x, y) = ins[0]
+            tx, ty = tr(tr.invert([x, y]) + [entry["dx"] * ux, entry["dy"] * uy])
+            res = (img, (x + int(tx) - x, y + int(ty) - y))
+        elif op == "blur":
+            img, (x, y) = ins[0]
+            kernel = blur_kernel(tr, (entry["std"][0] * ux, entry["std"][1] * uy))
+            kw, kh = kernel.shape
+            res = (sconv(img, kernel[..., None], mode="full", method="direct"), (int(x - kw / 2), int(y - kh / 2)))
+        elif op == "tile":
+            of = regions[entry["inputs"][0] - 2] if entry["inputs"][0] >= 2 else None
+            t = frame[1] if of is None else of[1]
+            b = frame[1] if box is None else box
+            res = (tile(ins[0][0], ins[0][1], b, t), b[:2]) if t[2] * t[3] else (np.zeros((1, 1, 4)), b[:2])
+        else:
+            raise ValueError(op)
+        if box is not None:
+            res = (window(res[0], res[1], box), box[:2])
+        stack.append(res)
+    return stack[-1]
