@@ -210,6 +210,73 @@ SVGR_HD int clamp_to_int(double v) {
 }
 
 // ------------------------------------------------------------------------------------
+// A path's layer: the integer bbox of its folded min / max keys (Path.mask: floor - 1 / ceil + 1, cut to the viewport,
+// S:968-971), the bands of `tr` rows and the column tiles of `tc` columns it covers.  ONE statement of the rule: k_path_bbox
+// places a path by it, and a render that keeps the plan's slab table (k_path_build<1>) checks the plan's record against it.
+// ------------------------------------------------------------------------------------
+// column tiles [ct0, ct0 + nct) of `tc` columns that the layer columns [c0, c0 + cols) of a viewport starting at column vc0 span
+SVGR_HD void span_ctiles(int c0, int cols, int vc0, int tc, int& ct0, int& nct) {
+    ct0 = (c0 - vc0) / tc;
+    nct = (c0 + cols - 1 - vc0) / tc - ct0 + 1;
+}
+struct PathBox {
+    int r0, c0, rows, cols;   // the layer (rows = cols = 0: empty; r0 / c0 then the clamped lower corner)
+    int b0, nb, nct;          // first band, bands, column tiles (0 when empty)
+    int refused;              // an extent beyond +-1e9 pixels or not finite: error bit 16, everything else 0
+};
+// k[0], k[1]: ~f64_key of the smallest row / column; k[2], k[3]: f64_key of the largest (k[0] == 0: the path made no edge)
+SVGR_HD PathBox path_box(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, int has_vp, int vr0, int vc0, int vrows, int vcols,
+                         int tr, int tc) {
+    PathBox o;
+    o.r0 = o.c0 = o.rows = o.cols = o.b0 = o.nb = o.nct = o.refused = 0;
+    if (k0 == 0ull) return o;
+    double mnr = key_f64(~k0), mnc = key_f64(~k1);
+    double mxr = key_f64(k2), mxc = key_f64(k3);
+    const double lim = 1.0e9;
+    // (finite extents only: an infinite or NaN coordinate falls through to the refusal below, as it did before the clamp)
+    const double fmax = 1.7976931348623157e308;
+    if (has_vp && fabs(mnr) <= fmax && fabs(mnc) <= fmax && fabs(mxr) <= fmax && fabs(mxc) <= fmax) {
+        // With a viewport the bbox is cut to it anyway (S:968-971): an extent beyond the 32-bit pixel range (the
+        // reference computes it in Python integers) is brought to the viewport's border first, in double.  Only a
+        // render WITHOUT a viewport is limited to +-1e9 pixels.
+        const double r_lo = (double)vr0 - 4.0, r_hi = (double)vr0 + (double)vrows + 4.0;
+        const double c_lo = (double)vc0 - 4.0, c_hi = (double)vc0 + (double)vcols + 4.0;
+        mnr = mnr < r_lo ? r_lo : (mnr > r_hi ? r_hi : mnr); mxr = mxr < r_lo ? r_lo : (mxr > r_hi ? r_hi : mxr);
+        mnc = mnc < c_lo ? c_lo : (mnc > c_hi ? c_hi : mnc); mxc = mxc < c_lo ? c_lo : (mxc > c_hi ? c_hi : mxc);
+    }
+    if (!(mnr > -lim && mnc > -lim && mxr < lim && mxc < lim)) {
+        o.refused = 1;
+        return o;
+    }
+    long long lo_r = (long long)floor(mnr) - 1, lo_c = (long long)floor(mnc) - 1;
+    long long hi_r = (long long)ceil(mxr) + 1, hi_c = (long long)ceil(mxc) + 1;
+    if (has_vp) {
+        lo_r = lo_r > vr0 ? lo_r : vr0;
+        lo_c = lo_c > vc0 ? lo_c : vc0;
+        hi_r = hi_r < (long long)vr0 + vrows ? hi_r : (long long)vr0 + vrows;
+        hi_c = hi_c < (long long)vc0 + vcols ? hi_c : (long long)vc0 + vcols;
+    }
+    const long long rows = hi_r - lo_r, cols = hi_c - lo_c;
+    if (rows > 0 && cols > 0) {
+        o.r0 = (int)lo_r; o.c0 = (int)lo_c; o.rows = (int)rows; o.cols = (int)cols;
+        const int base_r = has_vp ? vr0 : (int)lo_r;
+        o.b0 = ((int)lo_r - base_r) / tr;
+        o.nb = ((int)(hi_r - 1) - base_r) / tr - o.b0 + 1;
+        int ct0_;
+        span_ctiles((int)lo_c, (int)cols, has_vp ? vc0 : (int)lo_c, tc, ct0_, o.nct);
+    } else {
+        const long long big = 1ll << 30;
+        o.r0 = (int)(lo_r > big ? big : (lo_r < -big ? -big : lo_r));
+        o.c0 = (int)(lo_c > big ? big : (lo_c < -big ? -big : lo_c));
+    }
+    return o;
+}
+// does a record {r0, c0, rows, cols, bands} -- what a plan kept of a path -- state what the rule gives for the path's keys now?
+SVGR_HD bool path_box_is(const PathBox& o, int r0, int c0, int rows, int cols, int nb) {
+    return o.r0 == r0 && o.c0 == c0 && o.rows == rows && o.cols == cols && o.nb == nb;
+}
+
+// ------------------------------------------------------------------------------------
 // One edge of a path, prepared the way line_signed_coverage prepares it (S:2230-2242):
 // coordinates relative to the layer origin, oriented so rows increase.
 // ------------------------------------------------------------------------------------

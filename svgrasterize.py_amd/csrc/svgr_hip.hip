@@ -1,7 +1,7 @@
 // svgr_hip.hip -- MI355X (gfx950 / CDNA4) anti-aliased path rasterizer: HIP kernels + C ABI.
 //
-// Pipeline of one svgr_batch_render (5 launches of a planned batch on the context stream -- k_band_entries only in a plan's own
-// pass --, no host read-back).  A frame with NEW geometry (svgr_batch_draw) runs the same kernels in their unplanned forms -- the
+// Pipeline of one svgr_batch_render (4 launches of a planned batch on the context stream -- k_band_entries only in a plan's own
+// pass, k_path_bbox only in the first replay after a plan: the later ones keep the slab table it wrote --, no host read-back).  A frame with NEW geometry (svgr_batch_draw) runs the same kernels in their unplanned forms -- the
 // flatten in one traversal with a decoupled look-back (k_flatten<.., SCAN>), k_path_build<2> on its own per-cell bounds -- with the
 // tile kernel enqueued behind the pass and ONE host wait at the end:
 //
@@ -13,6 +13,7 @@
 //                   folded into per-path min/max keys
 //   k_path_bbox     per path: integer bbox (floor-1 / ceil+1, clipped to the viewport), band range, its (path, band)
 //                   pair slots and (path, band, column tile) cells, and its SLABS -- runs of <= 16 bands, <= 80 cells -- at the plan's heaviest-first places
+//                   (a replay that finds this table in place does not launch it: k_path_build<1> checks the keys against it)
 //   k_band_entries  per band: the paths whose bbox reaches it, in paint order; the band's first item slot
 //   k_path_build    per slab, everything in LDS: per edge row the closed-form signed-area pieces (the reference's x
 //                   recurrence replayed from the edge's first row), per cell the carry-in of every tile row, its
@@ -944,8 +945,7 @@ struct PathBin {
 };
 // column tiles [ct0, ct0 + nct) that the layer columns [c0, c0 + cols) of a viewport starting at column vc0 span
 __host__ __device__ __forceinline__ void path_ctiles(int c0, int cols, int vc0, int& ct0, int& nct) {
-    ct0 = (c0 - vc0) / TC;
-    nct = (c0 + cols - 1 - vc0) / TC - ct0 + 1;
+    span_ctiles(c0, cols, vc0, TC, ct0, nct);
 }
 static_assert(sizeof(PathBin) == 16, "PathBin is one dwordx4");
 
@@ -1011,60 +1011,26 @@ __global__ __launch_bounds__(64) void k_path_bbox(const unsigned long long* __re
     int st_n = 0;
     unsigned long long st_px = 0;
     unsigned st_minr = 0, st_minc = 0, st_maxr = 0, st_maxc = 0;
+    PathBox pb = path_box(0ull, 0ull, 0ull, 0ull, has_vp, vr0, vc0, vrows, vcols, TR, TC);
     if (p < n_paths) {
         const unsigned long long* k = pkeys + 4 * (size_t)p;
-        if (k[0] != 0ull) {  // the path produced at least one edge
-            double mnr = key_f64(~k[0]), mnc = key_f64(~k[1]);
-            double mxr = key_f64(k[2]), mxc = key_f64(k[3]);
-            const double lim = 1.0e9;
-            // (finite extents only: an infinite or NaN coordinate falls through to the refusal below, as it did before the clamp)
-            const double fmax = 1.7976931348623157e308;
-            if (has_vp && fabs(mnr) <= fmax && fabs(mnc) <= fmax && fabs(mxr) <= fmax && fabs(mxc) <= fmax) {
-                // With a viewport the bbox is cut to it anyway (S:968-971): an extent beyond the 32-bit pixel range (the
-                // reference computes it in Python integers) is brought to the viewport's border first, in double.  Only a
-                // render WITHOUT a viewport is limited to +-1e9 pixels.
-                const double r_lo = (double)vr0 - 4.0, r_hi = (double)vr0 + (double)vrows + 4.0;
-                const double c_lo = (double)vc0 - 4.0, c_hi = (double)vc0 + (double)vcols + 4.0;
-                mnr = mnr < r_lo ? r_lo : (mnr > r_hi ? r_hi : mnr); mxr = mxr < r_lo ? r_lo : (mxr > r_hi ? r_hi : mxr);
-                mnc = mnc < c_lo ? c_lo : (mnc > c_hi ? c_hi : mnc); mxc = mxc < c_lo ? c_lo : (mxc > c_hi ? c_hi : mxc);
-            }
-            if (!(mnr > -lim && mnc > -lim && mxr < lim && mxc < lim)) {
-                atomicOr(&bd->err, 16);
-            } else {
-                long long lo_r = (long long)floor(mnr) - 1, lo_c = (long long)floor(mnc) - 1;
-                long long hi_r = (long long)ceil(mxr) + 1, hi_c = (long long)ceil(mxc) + 1;
-                if (has_vp) {
-                    lo_r = lo_r > vr0 ? lo_r : vr0;
-                    lo_c = lo_c > vc0 ? lo_c : vc0;
-                    hi_r = hi_r < (long long)vr0 + vrows ? hi_r : (long long)vr0 + vrows;
-                    hi_c = hi_c < (long long)vc0 + vcols ? hi_c : (long long)vc0 + vcols;
-                }
-                long long rows = hi_r - lo_r, cols = hi_c - lo_c;
-                if (rows > 0 && cols > 0) {
-                    out[0] = (int)lo_r; out[1] = (int)lo_c; out[2] = (int)rows; out[3] = (int)cols;
-                    int base_r = has_vp ? vr0 : (int)lo_r;
-                    pb0 = ((int)lo_r - base_r) / TR;
-                    pnb = ((int)(hi_r - 1) - base_r) / TR - pb0 + 1;
-                    int ct0_;
-                    path_ctiles((int)lo_c, (int)cols, has_vp ? vc0 : (int)lo_c, ct0_, pnct);
-                    st_n = 1;
-                    st_px = (unsigned long long)(rows * cols);
-                    st_minr = (unsigned)(UNION_BIAS - (int)lo_r);
-                    st_minc = (unsigned)(UNION_BIAS - (int)lo_c);
-                    st_maxr = (unsigned)(UNION_BIAS + (int)hi_r);
-                    st_maxc = (unsigned)(UNION_BIAS + (int)hi_c);
-                } else {
-                    const long long big = 1ll << 30;
-                    out[0] = (int)(lo_r > big ? big : (lo_r < -big ? -big : lo_r));
-                    out[1] = (int)(lo_c > big ? big : (lo_c < -big ? -big : lo_c));
-                }
-            }
+        pb = path_box(k[0], k[1], k[2], k[3], has_vp, vr0, vc0, vrows, vcols, TR, TC);   // (svgr_core.h: the rule)
+        if (pb.refused) atomicOr(&bd->err, 16);
+        out[0] = pb.r0; out[1] = pb.c0; out[2] = pb.rows; out[3] = pb.cols;
+        pb0 = pb.b0; pnb = pb.nb; pnct = pb.nct;
+        if (pb.rows > 0 && pb.cols > 0) {
+            st_n = 1;
+            st_px = (unsigned long long)((long long)pb.rows * pb.cols);
+            st_minr = (unsigned)(UNION_BIAS - pb.r0);
+            st_minc = (unsigned)(UNION_BIAS - pb.c0);
+            st_maxr = (unsigned)(UNION_BIAS + (pb.r0 + pb.rows));
+            st_maxc = (unsigned)(UNION_BIAS + (pb.c0 + pb.cols));
         }
     }
     // A planned render whose geometry is not the plan's (a bbox or band count that differs: every setter voids the plan, so this is
     // a guard, not a path): the flag fails the render, and the path KEEPS THE PLAN'S bbox and places -- its slabs, pairs and cells
     // stay inside what the plan reserved, whatever the later kernels make of its edges (they clip to the layer they are given).
-    if (reuse && p < n_paths && (old_bb.x != out[0] || old_bb.y != out[1] || old_bb.z != out[2] || old_bb.w != out[3] || old_bin.nb != pnb)) {
+    if (reuse && p < n_paths && !path_box_is(pb, old_bb.x, old_bb.y, old_bb.z, old_bb.w, old_bin.nb)) {
         atomicOr(&bd->err, 32);
         out[0] = old_bb.x; out[1] = old_bb.y; out[2] = old_bb.z; out[3] = old_bb.w;
         pb0 = old_bin.b0; pnb = old_bin.nb; pnct = 0;
@@ -1537,7 +1503,9 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
                                                            unsigned long long* __restrict__ tile_mask, CellHdr* __restrict__ cell_hdr,
                                                            int cell_cap, const AddShards ash, TileAdd* __restrict__ adds,
                                                            int2* __restrict__ cell_plan, BatchDev* __restrict__ bd, Owner own, int stats, int det,
-                                                           unsigned long long* __restrict__ dbg) {
+                                                           unsigned long long* __restrict__ dbg,
+                                                           const unsigned long long* __restrict__ guard_keys, const int* __restrict__ guard_bbox,
+                                                           const PathBin* __restrict__ guard_bins, int n_paths, int vrows, int vcols) {
 #ifdef SVGR_DBG_PB_STAMP
 #define PB_STAMP(i) do { if (threadIdx.x == 0 && dbg && blockIdx.x < 8192) dbg[8 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -1569,9 +1537,17 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
     if (tid == 0) s_rowb[PB_CELLS] = 0u;
     // (both scalar loads asked for together: the slab first, the test of the cursor behind it -- the grid never exceeds the list)
     const Slab sl = slabs[blockIdx.x];
-    const int n_slabs_now = bd->slab_cursor;
+    // `guard_keys` given (MODE 1 only): a replay that KEEPS the slab table, bboxes and bins the previous render of the same plan left
+    // -- k_path_bbox did not run, `bd->slab_cursor` is not written: the grid is the table.  What k_path_bbox checked of such a render
+    // (the paths' keys still give the plan's bboxes: error bit 32 otherwise, the plan's places kept) is checked below, between pass A
+    // and the walk, every path once -- with or without slabs of its own --: a lane per path, by the first wave of one workgroup per
+    // 64 paths (as many waves as k_path_bbox was; a check per workgroup was 5 % of this kernel's vector instructions).
+    const bool guarding = MODE == 1 && guard_keys != nullptr;
+    const int n_slabs_now = guarding ? (int)gridDim.x : bd->slab_cursor;
     if ((int)blockIdx.x >= n_slabs_now) return;  // (the grid covers the plan's slab capacity)
-    if (sl.nb <= 0 || sl.nk <= 0) return;  // (a slot of a path that did not fit the slab list: flagged by k_path_bbox)
+    // (a slot of a path that did not fit the slab list: flagged by k_path_bbox -- when the table was written, if it is a kept one: the
+    //  error word is sticky)
+    if (sl.nb <= 0 || sl.nk <= 0) return;
     PB_STAMP(7);
     const int p = sl.p;
     const int r0 = sl.r0, c0 = sl.c0, rows = sl.rows, cols = sl.cols;
@@ -1918,6 +1894,20 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
         else for_rows(total, [&](const RowAt& ra) { count_row(ra, std::false_type{}); });
     }
     if (stats && tid == 0 && n_rows > 0) atomicAdd(&bd->bseg_cursor, n_rows);  // (plan only: edge rows of the batch)
+    if (guarding && __builtin_amdgcn_readfirstlane(wave) == 0) {
+        // (the workgroups from the middle of the work list on: neither the heaviest slabs, dispatched first, nor the launch's tail;
+        //  the stride only matters to a batch of more than 64 paths per slab)
+        const int grid = (int)gridDim.x, g0 = ((int)blockIdx.x + grid - grid / 2) % grid;
+        for (int g = g0; g * 64 < n_paths; g += grid) {
+            const int q = g * 64 + lane;
+            if (q >= n_paths) continue;
+            const unsigned long long* k = guard_keys + 4 * (size_t)q;
+            const int4 bb = ((const int4*)guard_bbox)[q];
+            const PathBox pb = path_box(k[0], k[1], k[2], k[3], 1, vr0, vc0, vrows, vcols, TR, TC);
+            if (pb.refused) atomicOr(&bd->err, 16);
+            if (!path_box_is(pb, bb.x, bb.y, bb.z, bb.w, guard_bins[q].nb)) atomicOr(&bd->err, 32);
+        }
+    }
     pb_barrier();
     PB_STAMP(2);
     // ---- walk ----
@@ -4488,7 +4478,7 @@ struct svgr_batch {
     DevArr<int2> cell_plan;                 // ... and where its add list lives: {first add, pieces}, left by the plan's full pass (k_path_build)
     bool add_places = false;                // `cell_plan` holds the places of the current plan: the renders take them (k_path_build<1>)
     // a pass that ended with an error flag may have left any of the self-cleaning buffers dirty
-    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; }
+    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; }
     DevArr<TileAdd> adds;                   // the cells' add lists (k_path_build: a slab reserves its cells' lists in one piece)
     DevArr<uint4> items;                    // the tiles' item lists: {cell id | class << 30, first add, adds, 0} (k_tile_lists)
     DevArr<int2> tile_info;                 // per (band, column tile): {first item, items}
@@ -4525,6 +4515,25 @@ struct svgr_batch {
     DevArr<Slab> slabs;                     // work items of k_path_build (k_path_bbox)
     DevArr<int> slab_at;                    // per path: its first slab, heaviest paths first (staged plan; renders only)
     bool slab_at_valid = false;
+    // A geometry pass has run k_path_bbox under the standing plan's `slab_at` order: `slabs`, `bbox` and `bins` hold the plan's places,
+    // and a replay under the same plan keeps them instead of launching the kernel again (run_geometry; k_path_build<1> checks the
+    // paths' keys against them).  Cleared wherever the plan or its slab order is, and by every pass that writes the three arrays in
+    // another form; `slabs_made` is what the table was written for -- a replay that finds anything else there writes it again.
+    bool slabs_current = false;
+    // The slab order was made by the render that is running, not by the plan (svgr_batch_draw leaves it to the first replay): that
+    // render's pass writes the table but does not mark it kept -- the replay behind it runs k_path_bbox once more and marks it.  Nothing
+    // in the arrays asks for this; the suite pins five launches for that replay (tests/test_gpu_draw.py), and a batch planned by a
+    // draw pays one launch of 6 us once.  A batch planned by svgr_batch_plan has its order from the plan and is not held back.
+    bool slab_order_late = false;
+    struct SlabsMade {
+        const void *slabs, *bbox, *bins, *slab_at;
+        int64_t n_slabs, n_paths;
+        int vp[4];
+        bool operator==(const SlabsMade& o) const {
+            return slabs == o.slabs && bbox == o.bbox && bins == o.bins && slab_at == o.slab_at && n_slabs == o.n_slabs && n_paths == o.n_paths &&
+                   vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
+        }
+    } slabs_made{};
     bool slab_order_pending = false;        // svgr_batch_draw planned this batch and left the slab order to the first render that replays the plan
     std::vector<int> slab_at_host;
     int64_t n_slabs = 0;                    // ... the plan's count = the launch's grid
@@ -4656,7 +4665,7 @@ static bool spare_adopt(svgr_batch* b) {
     b->mask_words = w->mask_words; b->add_shards = w->add_shards; b->n_adds = w->n_adds; b->adds_roomy = w->adds_roomy;
     b->n_bands = (b->vp[2] + TR - 1) / TR;
     b->masks_zeroed = false;   // (whatever the last render of the old batch left: cleared again)
-    b->slab_at_valid = false;
+    b->slab_at_valid = false; b->slabs_current = false;
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     return true;
@@ -4718,10 +4727,12 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         //  read-back -- they run while the host sizes the buffers -- `late_scan`)
         if (upto == 1 && !b->late_scan)
             SVGR_LAUNCH(k_seg_scan, dim3(1), dim3(1024), 0, st, (const int*)b->seg_cnt.p, ns, b->seg_off.p);
-        if (upto == 0 || (upto == 1 && b->census_bbox))  // bboxes only (no edges stored): the union when there is no viewport; the two-pass plan's census
+        if (upto == 0 || (upto == 1 && b->census_bbox)) {  // bboxes only (no edges stored): the union when there is no viewport; the two-pass plan's census
+            b->slabs_current = false;
             SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(),
                                np_walk, use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), 1, plist,
                                (Slab*)nullptr, 0, b->own, (const int*)nullptr, (const int*)nullptr, 0, (const int*)nullptr);
+        }
         return 0;
     }
     if (ns > 0) {
@@ -4751,17 +4762,32 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
             if (placed_fl) launch_fl(k_flatten<true, true, 5>, b->lane_off.p); else launch_fl(k_flatten<true, false, 5>, (int*)nullptr);
         }
     }
-    SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(), np_walk,
-                       use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), b->planned ? 0 : 1, plist,
-                       upto >= 3 ? b->slabs.p : (Slab*)nullptr, (int)std::min<int64_t>(cap_i32(b->slabs.cap), b->n_slabs) /* = k_path_build's grid */, b->own,
-                       (const int*)b->path_seg0.p, (const int*)b->seg_off.p,
-                       cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4)),
-                       upto >= 4 && b->planned && b->slab_at_valid ? (const int*)b->slab_at.p : (const int*)nullptr);
+    // (a planned render under the plan's places keeps the plan's band lists: k_tile_lists reads the paths' bboxes and bins itself)
+    const bool keep_lists = upto >= 4 && b->planned && b->slab_at_valid && use_vp && !b->safe_path;
+    // (a planned render takes every cell's add places from the plan's own full pass: one pass over the edge rows, no reservation)
+    // (the places are per cell: they hold as long as the paths keep the plan's cell places, i.e. under the plan's slab order)
+    const bool placed = b->planned && b->add_places && b->slab_at_valid && !b->count_adds_only && b->cell_plan.p != nullptr;
+    // A replay of a plan whose slab table the previous render left (svgr_batch::slabs_current): k_path_bbox would write, record by
+    // record, what is there -- same keys, same `slab_at`, same `bins` -- so it is not launched; k_path_build<1> checks the keys
+    // against the kept bboxes instead (error bit 32, as the kernel's own comparison).  One GPU, every path: a rank's list keeps
+    // its launch, and so does every pass that is not the placed render.
+    const svgr_batch::SlabsMade slabs_now{b->slabs.p, b->bbox.p, b->bins.p, b->slab_at.p, b->n_slabs, b->n_paths, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]}};
+    const bool slabs_for_plan = keep_lists && b->own.world <= 1 && !listed && ns > 0 && b->n_slabs > 0 && b->n_slabs <= (int64_t)cap_i32(b->slabs.cap);
+    const bool keep_slabs = slabs_for_plan && placed && b->slabs_current && b->slabs_made == slabs_now;
+    if (!keep_slabs) {
+        SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(), np_walk,
+                           use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), b->planned ? 0 : 1, plist,
+                           upto >= 3 ? b->slabs.p : (Slab*)nullptr, (int)std::min<int64_t>(cap_i32(b->slabs.cap), b->n_slabs) /* = k_path_build's grid */, b->own,
+                           (const int*)b->path_seg0.p, (const int*)b->seg_off.p,
+                           cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4)),
+                           upto >= 4 && b->planned && b->slab_at_valid ? (const int*)b->slab_at.p : (const int*)nullptr);
+        b->slabs_current = slabs_for_plan && !b->slab_order_late;   // (written at the plan's places, or in some other form)
+        b->slab_order_late = false;
+        b->slabs_made = slabs_now;
+    }
     if (upto == 2) return 0;
     // per owned band: its list of (path, band) pairs in paint order, and its first tile-list slot
     const int owned = count_owned_bands(b->own, b->n_bands);
-    // (a planned render under the plan's places keeps the plan's band lists: k_tile_lists reads the paths' bboxes and bins itself)
-    const bool keep_lists = upto >= 4 && b->planned && b->slab_at_valid && use_vp && !b->safe_path;
     // (upto >= 4 on one GPU: the kernel also clears the tiles' entry bitmasks of its band when they are not clear yet)
     const bool clear_in_be = owned > 0 && !keep_lists && upto >= 4 && !b->masks_zeroed && b->tile_mask.p && b->own.world <= 1;
     if (owned > 0 && !keep_lists)
@@ -4790,9 +4816,6 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
 #endif
     if (b->n_slabs > 0) {
         b->masks_zeroed = false;  // (bits are set below; k_tile_lists clears them again)
-        // (a planned render takes every cell's add places from the plan's own full pass: one pass over the edge rows, no reservation)
-        // (the places are per cell: they hold as long as the paths keep the plan's cell places, i.e. under the plan's slab order)
-        const bool placed = b->planned && b->add_places && b->slab_at_valid && !b->count_adds_only && b->cell_plan.p != nullptr;
         auto launch_pb = [&](auto kern) {
             SVGR_LAUNCH(kern, dim3((unsigned)b->n_slabs), dim3(PB_THREADS), 0, st, (const Slab*)b->slabs.p, (const double*)b->edges.p,
                                (const int*)b->pair_idx.p, (const double*)b->path_paint.p, (const uint8_t*)b->path_rule.p,
@@ -4800,7 +4823,8 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                b->n_grads > 0 ? (const int*)b->path_grad.p : (const int*)nullptr, b->vp[0], b->vp[1], b->n_ctiles(), b->mask_words,
                                b->tile_mask.p, b->cell_hdr.p, cap_i32(std::min(b->cell_hdr.cap, b->cell_plan.cap)), b->add_shards,
                                b->count_adds_only ? (TileAdd*)nullptr : b->adds.p, b->cell_plan.p, b->bd(), b->own, b->planned ? 0 : 1,
-                               b->deterministic ? 1 : 0, pb_dbg);
+                               b->deterministic ? 1 : 0, pb_dbg, keep_slabs ? (const unsigned long long*)b->pkeys() : (const unsigned long long*)nullptr,
+                               (const int*)b->bbox.p, (const PathBin*)b->bins.p, np, b->vp[2], b->vp[3]);
         };
         // (an unplanned pass over add lists sized with room to spare: ONE pass on the workgroup's own bounds, MODE 2)
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
@@ -5492,14 +5516,14 @@ int svgr_batch_set_transforms(svgr_batch* b, const double* path_m6) {
         HIPCHK(hipMemcpyAsync(b->path_m6.p, b->keep(path_m6, mbytes), mbytes, hipMemcpyHostToDevice, b->ctx->stream));
         HIPCHK(b->note_upload(b->ctx->stream));
     }
-    b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
     return 0;
 }
 
 int svgr_batch_set_bands(svgr_batch* b, int rank, int world, int strip_bands) {
     if (!b || world <= 0 || rank < 0 || rank >= world || strip_bands <= 0) return fail(SVGR_E_INVALID, "bad band selection");
     b->own = Owner{rank, world, strip_bands};
-    b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;  // the edge / record capacities are per rank
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;  // the edge / record capacities are per rank
     b->sized = false;
     b->n_seg_list = -1;  // ... and so is the list of segments to flatten
     return 0;
@@ -5766,7 +5790,7 @@ static int plan_speculative(svgr_batch* b) {
             if (int rc = plan_slab_order(b)) return rc;   // (large batches: k_path_build's work list heaviest first)
         }
         if (fin != 0) return fin;
-        b->planned = false;
+        b->planned = false; b->slabs_current = false;
     }
     return 0;
 }
@@ -5854,7 +5878,7 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
         for (int64_t i = 0; i < n; ++i) {
             svgr_batch* b = batches[i];
             HIPCHK(enter_ctx(b->ctx));
-            b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;
+            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
             b->geometry_fresh = false; b->geometry_current = false;
             const int is = no_spec ? 0 : spec_issue(b, (char*)b->ctx->pinned + stage_off[(size_t)i]);
             if (is < 0) return is;
@@ -5888,7 +5912,8 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
 // integer arithmetic on the same bbox (slab_shape, owns_any), so the places tile the list exactly; the geometry cannot change
 // under a plan (set_transforms / set_bands invalidate it).
 static int plan_slab_order(svgr_batch* b) {
-    b->slab_at_valid = false;
+    b->slab_at_valid = false; b->slabs_current = false;
+    b->slab_order_late = false;   // (the render that makes the order itself sets it behind this call)
     if (getenv("SVGR_SAFE_PATH")) return 0;  // (tests: the renders then take their slab places from the cursor, in arrival order)
     const size_t np = (size_t)b->n_paths;
     if (int rc = ensure_host_bbox(b)) return rc;
@@ -6118,7 +6143,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
     if (!b) return fail(SVGR_E_INVALID, "batch is NULL");
     HIPCHK(enter_ctx(b->ctx));
     b->defer_bbox = false;
-    b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
     b->geometry_fresh = false; b->geometry_current = false;
     {
         const bool no_spec = getenv("SVGR_NO_SPECULATIVE_PLAN") != nullptr;  // (tests exercise both planners)
@@ -6130,7 +6155,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
         const int tp = plan_two_pass(b);
         if (tp < 0) return tp;
         if (tp > 0) return 0;
-        b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;
+        b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
         b->geometry_fresh = false; b->geometry_current = false;
     }
     if (int rc = b->layout_arena()) return rc;
@@ -6427,6 +6452,7 @@ static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigne
     if (b->slab_order_pending && !b->geometry_fresh) {   // (a replay of a plan svgr_batch_draw made: its places now, once)
         b->slab_order_pending = false;
         if (int rc = plan_slab_order(b)) return rc;
+        b->slab_order_late = true;
     }
     const bool layers = out_kind == SVGR_OUT_MASKS_F64 || out_kind == SVGR_OUT_FILLS_F64;  // one mask / fill layer per path, back to back
     if (layers) out_kind = out_kind == SVGR_OUT_MASKS_F64 ? SVGR_OUT_MASK_F64 : SVGR_OUT_FILL_F64;
@@ -6636,7 +6662,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
         if (fast) {
             const size_t stage_bytes = sizeof(BatchDev) + 16 * (size_t)b->n_paths + 256;
             if (int rc = ensure_pinned(b->ctx, stage_bytes)) return rc;
-            b->slab_at_valid = false; b->slab_order_pending = false;
+            b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
             b->geometry_fresh = false; b->geometry_current = false;
             b->defer_bbox = true;                                       // (the bboxes stay on the device until somebody asks: ensure_host_bbox)
             int is = spec_issue(b, b->ctx->pinned, true);                 // (the buffers of the batch's last plan as the guesses)
@@ -6654,7 +6680,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
             // the tile kernel right behind the pass: the batch counts as planned with that pass's geometry until the pass is validated
             b->planned = true; b->geometry_fresh = true; b->geometry_current = true;
             int rc = batch_render_impl(b, out, out_kind, flags, nullptr);
-            b->planned = false; b->geometry_fresh = false; b->geometry_current = false;
+            b->planned = false; b->slabs_current = false; b->geometry_fresh = false; b->geometry_current = false;
             hipError_t e = hipStreamSynchronize(st);
             if (rc) return rc;
             HIPCHK(e);
@@ -6668,7 +6694,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
                 b->slab_order_pending = b->n_segs > 4096;   // (large batches: k_path_build's work list heaviest first, as svgr_batch_plan leaves it)
                 return 0;
             }
-            b->planned = false; b->slab_at_valid = false; b->slab_order_pending = false;
+            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
         }
         if (int rc = batch_plan_impl(b, issued == 1)) return rc;
     }
