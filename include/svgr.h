@@ -41,7 +41,8 @@ extern "C" {
  *    svgr_layer_displacement_map added (filter primitives beyond the reference); svgr_image_upload, svgr_image_fill,
  *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
  *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode); svgr_jpeg_entropy and
- *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile) */
+ *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile); svgr_jpeg_encode,
+ *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -563,6 +564,36 @@ int svgr_jpeg_entropy(const svgr_jpeg_scan* scan, const uint8_t* huff_counts, co
  * sRGB as stored: what svgr_image_upload takes. */
 int svgr_jpeg_decode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const int16_t* coef, int64_t n_coef, const uint16_t* quant,
                      svgr_buf* out_rgba);
+
+/* JPEG output (write_jpeg): the same split the other way round -- the device makes the coefficients, the host codes them,
+ * the caller writes the markers.
+ * svgr_jpeg_encode: the quantised coefficients of a frame from src_rgba8, (height, width, 4) uint8 on the device as
+ * svgr_layer_to_rgba8 writes them (alpha is ignored).  frame->colour is SVGR_JPEG_YCBCR (three components, h[0] x v[0] the
+ * luma sampling factors, 1 x 1 for both chroma components: 4:4:4, 4:2:2, 4:4:0, 4:2:0) or SVGR_JPEG_GREY (one component, Y
+ * alone).  Per pixel: the JFIF matrix in 16-bit fixed point, rounded half up, clamped.  Per chroma sample: the mean of the
+ * pixels it covers, rounded half up.  The planes are padded to whole MCUs by repeating the last column and row.  Per block:
+ * - 128, forward DCT, each value divided by its table entry (quant[n_comp][64], natural order, entries 1 .. 255) and rounded
+ * half away from zero, clamped to -1024 .. 1023 (DC) and -1023 .. 1023 (AC).  Integer arithmetic (csrc/svgr_core.h): the
+ * result is defined to the bit.  coef_out is a host array of n_coef int16 in the layout above -- what svgr_jpeg_entropy_encode
+ * and svgr_jpeg_decode take.  SVGR_E_INVALID for any other colour model or sampling, a short buffer, an n_coef that is not
+ * the frame's, or a table entry outside 1 .. 255. */
+int svgr_jpeg_encode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const svgr_buf* src_rgba8, const uint16_t* quant,
+                     int16_t* coef_out, int64_t n_coef);
+/* svgr_jpeg_entropy_encode (host only): the entropy-coded segment of one baseline sequential scan (progressive 0, ss 0, se 63,
+ * ah 0, al 0) of the frame's coefficients, svgr_jpeg_entropy's inverse: described the same way, tables in the same convention.
+ * A scan of all three components is interleaved (MCU by MCU, each component's h x v blocks in turn), a scan of one component
+ * walks its own blocks.  DC is coded as the difference from the component's last DC, AC as run / size pairs with ZRL and EOB;
+ * an FF byte is followed by a stuffed 00 and the last byte is filled with one bits.  With a restart_interval, RSTn goes
+ * between the intervals and the predictors start again.  At most out_cap bytes are written to out; *n_bytes always receives
+ * the segment's full length, and the status is SVGR_JPEG_NO_ROOM when that is more than out_cap.  SVGR_JPEG_BAD_CODE when a
+ * table is no prefix code or has no code for a symbol the data needs (a DC difference beyond +-2047 and an AC value beyond
+ * +-1023 need symbols no baseline table has). */
+#define SVGR_JPEG_NO_ROOM 5      /* the output buffer is too small */
+int svgr_jpeg_entropy_encode(const svgr_jpeg_scan* scan, const uint8_t* huff_counts, const uint8_t* huff_symbols,
+                             const int16_t* coef, int64_t n_coef, uint8_t* out, int64_t out_cap, int64_t* n_bytes);
+/* svgr_jpeg_symbol_counts (host only): how often the same walk uses each symbol, for tables made to measure: counts[8][256],
+ * DC tables 0-3 then AC tables 0-3 as the scan assigns them to its components; the caller zeroes it (counts add up over calls). */
+int svgr_jpeg_symbol_counts(const svgr_jpeg_scan* scan, const int16_t* coef, int64_t n_coef, int64_t* counts);
 
 #ifdef __cplusplus
 }

@@ -12,12 +12,12 @@ from .geometry import (  # noqa: F401
     PATH_FILL_NONZERO, PATH_FILL_EVENODD,
 )
 from .layer import (  # noqa: F401
-    Layer, canvas_to_png, canvas_create, canvas_compose, canvas_merge_at, canvas_merge_union, canvas_merge_intersect,
+    Layer, canvas_to_png, canvas_to_jpeg, canvas_create, canvas_compose, canvas_merge_at, canvas_merge_union, canvas_merge_intersect,
     CANVAS_COMPOSE_OVER, COMPOSE_OVER, COMPOSE_OUT, COMPOSE_IN, COMPOSE_ATOP, COMPOSE_XOR,
     BLEND_MODES,
 )
 from .paint import GradLinear, GradRadial, ImagePaint, Pattern  # noqa: F401
-from .jpeg import read_jpeg  # noqa: F401
+from .jpeg import read_jpeg, write_jpeg  # noqa: F401
 from .png import read_png  # noqa: F401
 from .filters import (  # noqa: F401
     Filter, blur_kernel, COLOR_MATRIX_LUM, FE_SOURCE_ALPHA, FE_SOURCE_GRAPHIC, FE_BLEND, FE_COLOR_MATRIX, FE_COMPOSITE,
@@ -31,4 +31,5 @@ from .fonts import Font, FontsDB, Glyph  # noqa: F401
 from .svg import render_svg, svg_scene, svg_scene_from_filepath, svg_scene_from_str  # noqa: F401
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
-           "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg"]
+           "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg",
+           "write_jpeg", "canvas_to_jpeg"]

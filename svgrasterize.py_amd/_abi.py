@@ -87,6 +87,7 @@ class JpegScan(C.Structure):  # svgr_jpeg_scan
 JPEG_GREY, JPEG_YCBCR, JPEG_RGB = 0, 1, 2
 _JPEG_STATUS = {1: "the entropy-coded data ends before the scan does", 2: "a bad Huffman table or code",
                 3: "a restart marker is missing or out of sequence", 4: "a run of zeros leads past the end of the block"}
+JPEG_NO_ROOM = 5
 
 _P = C.c_void_p
 _PROTOS = {
@@ -173,6 +174,9 @@ _PROTOS = {
     "svgr_png_unfilter": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
     "svgr_jpeg_entropy": (C.c_int, [C.POINTER(JpegScan), _P, _P, _P, C.c_int64, _P, C.c_int64]),
     "svgr_jpeg_decode": (C.c_int, [_P, C.POINTER(JpegFrame), _P, C.c_int64, _P, _P]),
+    "svgr_jpeg_encode": (C.c_int, [_P, C.POINTER(JpegFrame), _P, _P, _P, C.c_int64]),
+    "svgr_jpeg_entropy_encode": (C.c_int, [C.POINTER(JpegScan), _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "svgr_jpeg_symbol_counts": (C.c_int, [C.POINTER(JpegScan), _P, C.c_int64, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -620,3 +624,60 @@ def jpeg_decode(ctx: Context, frame: JpegFrame, coef: np.ndarray, quant: np.ndar
     out = ctx.alloc(frame.width * frame.height * 4)
     _check(ctx.lib.svgr_jpeg_decode(ctx.handle, C.byref(frame), ptr(coef), coef.size, ptr(quant), out.handle))
     return out.download((frame.height, frame.width, 4), np.uint8)
+
+
+def jpeg_n_coef(frame: JpegFrame) -> int:
+    """The number of int16 coefficients of a frame (the layout of include/svgr.h)."""
+    hmax, vmax = max(frame.h[:frame.n_comp]), max(frame.v[:frame.n_comp])
+    mcus = -(-frame.width // (8 * hmax)) * -(-frame.height // (8 * vmax))
+    return 64 * mcus * sum(frame.h[i] * frame.v[i] for i in range(frame.n_comp))
+
+
+def jpeg_encode(ctx: Context, frame: JpegFrame, rgba8, quant: np.ndarray) -> np.ndarray:
+    """svgr_jpeg_encode: the frame's quantised int16 coefficients from its (height, width, 4) uint8 pixels -- a DeviceBuffer
+    that holds them, or a host array, which is uploaded first -- and its components' quantisation tables (n_comp, 64)."""
+    quant = np.ascontiguousarray(quant, dtype=np.uint16)
+    if quant.shape != (frame.n_comp, 64):
+        raise ValueError("jpeg_encode: one quantisation table of 64 entries per component")
+    if not isinstance(rgba8, DeviceBuffer):
+        px = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if px.shape != (frame.height, frame.width, 4):
+            raise ValueError("jpeg_encode: the pixels are a (height, width, 4) uint8 array of the frame's size")
+        rgba8 = ctx.from_host(px)
+    coef = np.empty(jpeg_n_coef(frame), dtype=np.int16)
+    _check(ctx.lib.svgr_jpeg_encode(ctx.handle, C.byref(frame), rgba8.handle, ptr(quant), ptr(coef), coef.size))
+    return coef
+
+
+def _huff_tables(huff_counts, huff_symbols):
+    assert huff_counts.dtype == np.uint8 and huff_counts.shape == (8, 16) and huff_counts.flags.c_contiguous
+    assert huff_symbols.dtype == np.uint8 and huff_symbols.shape == (8, 256) and huff_symbols.flags.c_contiguous
+
+
+def jpeg_entropy_encode(scan: JpegScan, huff_counts: np.ndarray, huff_symbols: np.ndarray, coef: np.ndarray) -> bytes:
+    """svgr_jpeg_entropy_encode (host only): the entropy-coded segment of one baseline scan of `coef`.  ValueError when the
+    tables cannot code the data."""
+    _huff_tables(huff_counts, huff_symbols)
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous
+    lib, n = load_library(), C.c_int64()
+    out = np.empty(coef.size // 4 + 4096, dtype=np.uint8)   # (a first guess; the call reports what it needs)
+    for _ in range(2):
+        rc = lib.svgr_jpeg_entropy_encode(C.byref(scan), ptr(huff_counts), ptr(huff_symbols), ptr(coef), coef.size, ptr(out), out.size,
+                                          C.byref(n))
+        if rc != JPEG_NO_ROOM:
+            break
+        out = np.empty(n.value, dtype=np.uint8)
+    if rc:
+        raise ValueError("the Huffman tables have no code for a value of the scan" if rc == 2 else
+                         "a scan description that does not fit the frame")
+    return out[:n.value].tobytes()
+
+
+def jpeg_symbol_counts(scan: JpegScan, coef: np.ndarray) -> np.ndarray:
+    """svgr_jpeg_symbol_counts (host only): (8, 256) int64, how often the scan uses each symbol of DC tables 0-3 and AC
+    tables 0-3."""
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous
+    counts = np.zeros((8, 256), dtype=np.int64)
+    if load_library().svgr_jpeg_symbol_counts(C.byref(scan), ptr(coef), coef.size, ptr(counts)):
+        raise ValueError("a scan description that does not fit the frame, or a value no baseline table can code")
+    return counts

@@ -1001,6 +1001,140 @@ SVGR_HD uint32_t jpeg_rgba(int colour, int s0, int s1, int s2) {
 
 
 // =====================================================================================
+// JPEG encode stage (write_jpeg; beyond the reference): RGBA -> sample planes -> quantised coefficients,
+// the decode stage run backwards.  Integer arithmetic again: the host build (tests/jpeg_enc_harness.cpp)
+// and the kernels (k_jpeg_planes, k_jpeg_fdct) produce the same bits.
+//
+// Colour: the JFIF matrix Y = 0.299 R + 0.587 G + 0.114 B, Cb = -0.168736 R - 0.331264 G + 0.5 B + 128,
+// Cr = 0.5 R - 0.418688 G - 0.081312 B + 128 with every factor stored as round(2^16 factor):
+//     Y : 19595  38470   7471      Cb : -11058 -21710  32768      Cr : 32768 -27439  -5329
+// (each row of Y sums to 2^16, each chroma row to 0: grey stays grey).  2^15 is added before the 16 bits
+// come off with an arithmetic shift, which is rounding half up; the result is clamped to 0 .. 255 (pure
+// blue gives Cb = 128 + 128).  Alpha is ignored.
+//
+// Chroma: the mean of the h x v (1 or 2 per axis) 8-bit values a sample covers, rounded half up -- the box filter whose
+// samples sit where the decoder's triangle upsampler (jpeg_upsampled16) takes them to sit.  A plane is padded to whole
+// MCUs by repeating the image's last column and row (the pixel index is clamped, before the colour matrix and the mean).
+//
+// Forward DCT: the transpose of the inverse above, with the same table: F(v, u) = sum_y sum_x T[y][v] T[x][u] (s(y, x) - 128)
+// as two 8-tap passes over kJpegIdct = 2^15 T, nothing rounded in between, so a finished sum is 2^30 F whichever axis went
+// first.  No overflow: |s - 128| <= 128 = 2^7 and sum_k |2^15 T[k][j]| < 2^17, so the first pass stays below 2^24 (int32)
+// and the second below 2^41 (int64).  The quantiser divides the sum by q 2^30 in one step, rounding half away from zero:
+// with n = |sum|, (n + q 2^29) / (q 2^30) = ((n + q 2^29) >> 30) / q exactly (floors of non-negative numbers nest), and
+// the shifted numerator is below 2^12, so the division is a 32-bit one.  The quotient is clamped to what the Huffman
+// categories of a baseline scan can carry: -1024 .. 1023 for DC (differences then fit category 11), +-1023 for AC
+// (category 10).  8-bit samples cannot reach the AC clamp (|F(v, u)| <= 128 sum_k |T[k][v]| sum_k |T[k][u]| < 929 off DC); DC reaches -1024.
+// =====================================================================================
+
+// R | G << 8 | B << 16 (| A << 24, ignored) -> Y, Cb, Cr in 0 .. 255
+SVGR_HD void jpeg_ycc(uint32_t px, int* y, int* cb, int* cr) {
+    const int r = (int)(px & 255u), g = (int)((px >> 8) & 255u), b = (int)((px >> 16) & 255u);
+    *y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;   // (a weighted mean of bytes: no clamp needed)
+    *cb = jpeg_clamp8(((-11058 * r - 21710 * g + 32768 * b + 32768) >> 16) + 128);
+    *cr = jpeg_clamp8(((32768 * r - 27439 * g - 5329 * b + 32768) >> 16) + 128);
+}
+
+// One H x V group of pixels (row-major in px): its H x V luma samples and the one chroma pair that covers it
+template <int H, int V>
+SVGR_HD void jpeg_group(const uint32_t* px, uint8_t* y, int* cb, int* cr) {
+    int sb = 0, sr = 0;
+    SVGR_UNROLL
+    for (int i = 0; i < H * V; ++i) {
+        int yy, b, r;
+        jpeg_ycc(px[i], &yy, &b, &r);
+        y[i] = (uint8_t)yy;
+        sb += b;
+        sr += r;
+    }
+    *cb = (sb + H * V / 2) / (H * V);
+    *cr = (sr + H * V / 2) / (H * V);
+}
+
+// one 8-tap pass of the forward transform: out[j] = sum_k 2^15 T[k][j] in[k * stride]  (int32 in -> int32 out for the
+// first pass, int32 in -> int64 out for the second)
+template <class Out, class In>
+SVGR_HD void jpeg_fdct_pass(const In* in, int stride, Out* out) {
+    SVGR_UNROLL
+    for (int j = 0; j < 8; ++j) {
+        Out acc = 0;
+        SVGR_UNROLL
+        for (int k = 0; k < 8; ++k) acc += (Out)kJpegIdct[8 * k + j] * (Out)in[k * stride];
+        out[j] = acc;
+    }
+}
+
+// acc = 2^30 F, q = 1 .. 255: F / q rounded half away from zero
+SVGR_HD int32_t jpeg_quantise(int64_t acc, uint16_t q) {
+    const uint64_t n = (uint64_t)(acc < 0 ? -acc : acc);
+    const uint32_t m = (uint32_t)((n + ((uint64_t)q << 29)) >> 30) / (uint32_t)q;
+    return acc < 0 ? -(int32_t)m : (int32_t)m;
+}
+// the quantised value as the scan stores it (index 0 of a block is its DC)
+SVGR_HD int16_t jpeg_coefficient(int64_t acc, uint16_t q, bool dc) {
+    const int32_t v = jpeg_quantise(acc, q), lo = dc ? -1024 : -1023;
+    return (int16_t)(v < lo ? lo : (v > 1023 ? 1023 : v));
+}
+
+// A whole block on one thread (the host harness; the kernel spreads the same sums over eight lanes per block): in = the
+// block's top-left sample in a plane whose rows are `stride` bytes apart, q[64] and coef[64] in natural order.
+SVGR_HD void jpeg_fdct_block(const uint8_t* in, int64_t stride, const uint16_t* q, int16_t* coef) {
+    int32_t s[8], r[64];
+    int64_t col[8];
+    for (int y = 0; y < 8; ++y) {   // rows: r[y][u] = sum_x T[x][u] (s[y][x] - 128)
+        for (int x = 0; x < 8; ++x) s[x] = (int32_t)in[y * stride + x] - 128;
+        jpeg_fdct_pass(s, 1, r + 8 * y);
+    }
+    for (int u = 0; u < 8; ++u) {   // columns: F[v][u] = sum_y T[y][v] r[y][u]
+        jpeg_fdct_pass(r + u, 8, col);
+        for (int v = 0; v < 8; ++v) coef[8 * v + u] = jpeg_coefficient(col[v], q[8 * v + u], v == 0 && u == 0);
+    }
+}
+
+// A whole frame on one thread (the host harness): rgba = height x width pixels, hmax x vmax = the luma sampling factors
+// (chroma has 1 x 1; n_comp = 1: a grey frame, Y alone), planes = room for the MCU-padded planes (64 bytes per block, the
+// components one after the other), coef = the coefficients in the layout of include/svgr.h.
+template <int H, int V>
+SVGR_HD void jpeg_encode_frame_hv(const uint32_t* rgba, int width, int height, int n_comp, const uint16_t* quant, uint8_t* planes,
+                                  int16_t* coef) {
+    const int64_t mcus_x = (width + 8 * H - 1) / (8 * H), mcus_y = (height + 8 * V - 1) / (8 * V);
+    const int64_t yw = mcus_x * 8 * H, yh = mcus_y * 8 * V, cw = mcus_x * 8, ch = mcus_y * 8;
+    uint8_t *py = planes, *pb = py + yw * yh, *pr = pb + cw * ch;
+    for (int64_t gy = 0; gy < ch; ++gy)
+        for (int64_t gx = 0; gx < cw; ++gx) {
+            uint32_t px[H * V];
+            uint8_t y[H * V];
+            int cb, cr;
+            for (int j = 0; j < V; ++j)
+                for (int i = 0; i < H; ++i) {
+                    const int64_t sx = gx * H + i < width ? gx * H + i : width - 1, sy = gy * V + j < height ? gy * V + j : height - 1;
+                    px[j * H + i] = rgba[sy * width + sx];
+                }
+            jpeg_group<H, V>(px, y, &cb, &cr);
+            for (int j = 0; j < V; ++j)
+                for (int i = 0; i < H; ++i) py[(gy * V + j) * yw + gx * H + i] = y[j * H + i];
+            if (n_comp == 3) {
+                pb[gy * cw + gx] = (uint8_t)cb;
+                pr[gy * cw + gx] = (uint8_t)cr;
+            }
+        }
+    int64_t b = 0;
+    for (int c = 0; c < n_comp; ++c) {
+        const uint8_t* p = c == 0 ? py : (c == 1 ? pb : pr);
+        const int64_t bw = (c == 0 ? yw : cw) / 8, bh = (c == 0 ? yh : ch) / 8;
+        for (int64_t by = 0; by < bh; ++by)
+            for (int64_t bx = 0; bx < bw; ++bx, ++b) jpeg_fdct_block(p + by * 8 * bw * 8 + bx * 8, bw * 8, quant + 64 * c, coef + b * 64);
+    }
+}
+SVGR_HD void jpeg_encode_frame(const uint32_t* rgba, int width, int height, int n_comp, int hmax, int vmax, const uint16_t* quant,
+                               uint8_t* planes, int16_t* coef) {
+    if (hmax == 2 && vmax == 2) jpeg_encode_frame_hv<2, 2>(rgba, width, height, n_comp, quant, planes, coef);
+    else if (hmax == 2) jpeg_encode_frame_hv<2, 1>(rgba, width, height, n_comp, quant, planes, coef);
+    else if (vmax == 2) jpeg_encode_frame_hv<1, 2>(rgba, width, height, n_comp, quant, planes, coef);
+    else jpeg_encode_frame_hv<1, 1>(rgba, width, height, n_comp, quant, planes, coef);
+}
+
+
+// =====================================================================================
 // feTile (k_layer_tile; beyond the reference): which pixel of the source layer an output pixel copies.
 // Along one axis the tile covers the device coordinates [t0, t0 + tn) and the source layer [s0, s0 + sn).
 // The output coordinate p repeats the tile: its tile coordinate is t = (p - t0) floor-mod tn (p may lie

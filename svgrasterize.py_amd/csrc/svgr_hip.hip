@@ -4196,6 +4196,114 @@ __global__ void __launch_bounds__(256) k_jpeg_colour(JpegColourArgs a, uint32_t*
     out[(size_t)y * a.width + x] = jpeg_rgba(a.colour, s0, s1, s2);
 }
 
+// --------------------------------------------------------------------------------------
+// JPEG encode stage (write_jpeg): RGBA -> sample planes -> quantised coefficients, svgr_core.h's integer code again.
+// --------------------------------------------------------------------------------------
+// Colour + chroma downsampling: one lane per H x V group of pixels (the luma sampling factors; chroma has 1 x 1), so the lane
+// that read a chroma sample's sources makes it.  A 64 x 4 tile of groups per workgroup: a wave reads 256 (H = 1) or 512
+// consecutive bytes per pixel row and writes 64 consecutive bytes per chroma plane.  The planes are padded to whole MCUs:
+// the grid covers the padding, whose groups read the image's last column / row (clamped indices).
+struct JpegPlanesArgs {
+    const uint32_t* rgba;
+    uint8_t *y, *cb, *cr;
+    int width, height;
+    int gw, gh;   // groups per row and rows of groups = the chroma planes' size
+    int n_comp;   // 1: Y alone
+};
+template <int H, int V>
+__global__ void __launch_bounds__(256) k_jpeg_planes(JpegPlanesArgs a) {
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63), gy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx >= a.gw || gy >= a.gh) return;
+    uint32_t px[H * V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const uint32_t* row = a.rgba + (size_t)min(gy * V + j, a.height - 1) * a.width;
+        if (H == 2) {
+            const int x0 = gx * 2;
+            if ((a.width & 1) == 0 && x0 + 1 < a.width) {   // (an even width keeps every pair 8-byte aligned)
+                const uint2 p = *reinterpret_cast<const uint2*>(row + x0);
+                px[j * H] = p.x;
+                px[j * H + H - 1] = p.y;
+            } else {
+                px[j * H] = row[min(x0, a.width - 1)];
+                px[j * H + H - 1] = row[min(x0 + 1, a.width - 1)];
+            }
+        } else {
+            px[j * H] = row[min(gx, a.width - 1)];
+        }
+    }
+    uint8_t y[H * V];
+    int cb, cr;
+    jpeg_group<H, V>(px, y, &cb, &cr);
+    const size_t yw = (size_t)a.gw * H;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        uint8_t* o = a.y + ((size_t)gy * V + j) * yw + (size_t)gx * H;
+        if (H == 2) *reinterpret_cast<uchar2*>(o) = make_uchar2(y[j * H], y[j * H + H - 1]);
+        else *o = y[j * H];
+    }
+    if (a.n_comp == 3) {
+        a.cb[(size_t)gy * a.gw + gx] = (uint8_t)cb;
+        a.cr[(size_t)gy * a.gw + gx] = (uint8_t)cr;
+    }
+}
+
+// Level shift + forward DCT + quantiser: k_jpeg_idct's counterpart, eight lanes per block, 32 blocks per workgroup.  Lane
+// (block, k) loads row k of the block's samples as one 8-byte word, runs the row pass and leaves r[k][0..7] in LDS (int32, rows
+// of JPEG_LDS_ROW words as above).  Lane (block, v) then runs the pass down the columns for output row v -- all eight columns at
+// once: F[v][u] = sum_y T[y][v] r[y][u], r read as 16-byte words (the eight lanes of a block read the same words: a broadcast;
+// the blocks of a lane group are 72 words = 8 banks apart) -- quantises and stores its eight int16 as one 16-byte word: a wave
+// writes 1 KiB of consecutive coefficients.  T[.][v] depends on the lane, so the table sits in LDS, transposed.
+struct JpegFdctArgs {
+    const uint8_t* planes;
+    const uint16_t* quant;   // [component][64]
+    int16_t* coef;
+    long long end[3];        // one past each component's last block (the components follow each other)
+    long long bw[3], plane[3];
+};
+__global__ void __launch_bounds__(256) k_jpeg_fdct(JpegFdctArgs a) {
+    __shared__ __attribute__((aligned(16))) int32_t r[JPEG_WG_BLOCKS * JPEG_LDS_ROW];
+    __shared__ __attribute__((aligned(16))) int32_t tt[64];   // [v][y] = 2^15 T[y][v]
+    const int blk = threadIdx.x >> 3, k = threadIdx.x & 7;
+    const long long b = (long long)blockIdx.x * JPEG_WG_BLOCKS + blk;
+    const bool live = b < a.end[2];
+    const int ci = b < a.end[0] ? 0 : (b < a.end[1] ? 1 : 2);
+    if (threadIdx.x < 64) tt[threadIdx.x] = kJpegIdct[8 * (threadIdx.x & 7) + (threadIdx.x >> 3)];
+    if (live) {
+        const long long first = ci == 0 ? 0 : a.end[ci - 1], lb = b - first;
+        const long long by = lb / a.bw[ci], bx = lb - by * a.bw[ci];
+        union { uint2 v; uint8_t s[8]; } in;
+        in.v = *reinterpret_cast<const uint2*>(a.planes + a.plane[ci] + (by * 8 + k) * (a.bw[ci] * 8) + bx * 8);
+        int32_t s[8], row[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) s[x] = (int32_t)in.s[x] - 128;
+        jpeg_fdct_pass(s, 1, row);
+        int4* o = reinterpret_cast<int4*>(r + blk * JPEG_LDS_ROW + 8 * k);
+        o[0] = make_int4(row[0], row[1], row[2], row[3]);
+        o[1] = make_int4(row[4], row[5], row[6], row[7]);
+    }
+    __syncthreads();
+    if (live) {
+        const int4 t0 = *reinterpret_cast<const int4*>(tt + 8 * k), t1 = *reinterpret_cast<const int4*>(tt + 8 * k + 4);
+        const int32_t t[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+        int64_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int y = 0; y < 8; ++y) {
+            const int4* p = reinterpret_cast<const int4*>(r + blk * JPEG_LDS_ROW + 8 * y);
+            const int4 lo = p[0], hi = p[1];
+            const int32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc[u] += (int64_t)t[y] * (int64_t)v[u];
+        }
+        union { uint4 v; uint16_t s[8]; } q;
+        union { uint4 v; int16_t s[8]; } o;
+        q.v = *reinterpret_cast<const uint4*>(a.quant + 64 * ci + 8 * k);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) o.s[u] = jpeg_coefficient(acc[u], q.s[u], k == 0 && u == 0);
+        *reinterpret_cast<uint4*>(a.coef + b * 64 + 8 * k) = o.v;
+    }
+}
+
 struct ImageLevel {
     const float4* tex;
     int h, w;
@@ -7261,6 +7369,53 @@ int svgr_jpeg_decode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const int16_t*
         SVGR_LAUNCH(k_jpeg_idct, dim3((unsigned)((L.blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS)), dim3(256), 0, ctx->stream, ia);
         SVGR_LAUNCH(k_jpeg_colour, dim3((unsigned)((frame->width + 63) / 64), (unsigned)((frame->height + 3) / 4)), dim3(256), 0,
                     ctx->stream, ca, (uint32_t*)out->ptr);
+    });
+}
+
+int svgr_jpeg_encode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const svgr_buf* src_rgba8, const uint16_t* quant, int16_t* coef_out,
+                     int64_t n_coef) {
+    JpegLayout L;
+    if (!ctx || !frame || !src_rgba8 || !quant || !coef_out || !jpeg_layout(*frame, L) || !image_size_ok(frame->height, frame->width))
+        return fail(SVGR_E_INVALID, "svgr_jpeg_encode: bad arguments");
+    if (frame->colour != (frame->n_comp == 1 ? SVGR_JPEG_GREY : SVGR_JPEG_YCBCR))
+        return fail(SVGR_E_INVALID, "svgr_jpeg_encode: a frame is written as YCbCr (three components) or grey (one)");
+    if (frame->n_comp == 3 && (frame->h[1] != 1 || frame->v[1] != 1 || frame->h[2] != 1 || frame->v[2] != 1))
+        return fail(SVGR_E_INVALID, "svgr_jpeg_encode: the chroma components take sampling factors 1 x 1");
+    if (n_coef != L.blocks * 64) return fail(SVGR_E_INVALID, "svgr_jpeg_encode: room for %lld coefficients, the frame has %lld", (long long)n_coef, (long long)L.blocks * 64);
+    if (src_rgba8->bytes < (size_t)frame->width * frame->height * 4) return fail(SVGR_E_INVALID, "svgr_jpeg_encode: buffer too small");
+    for (int i = 0; i < frame->n_comp * 64; ++i)
+        if (quant[i] < 1 || quant[i] > 255) return fail(SVGR_E_INVALID, "svgr_jpeg_encode: quantisation table entry %d of component %d is %d (1 .. 255)", i & 63, i >> 6, (int)quant[i]);
+    HIPCHK(enter_ctx(ctx));
+    PoolBlock planes, coef;
+    HIPCHK(planes.alloc((size_t)L.plane_bytes, ctx->device));
+    HIPCHK(coef.alloc((size_t)n_coef * 2, ctx->device));
+    return upload_launch_wait(ctx, "svgr_jpeg_encode", {{quant, (size_t)frame->n_comp * 128}}, [&](void* dev) {
+        const int H = frame->h[0], V = frame->v[0];   // (1 x 1 for a grey frame)
+        JpegPlanesArgs pa;
+        pa.rgba = (const uint32_t*)src_rgba8->ptr;
+        pa.y = planes.as<uint8_t>() + L.plane[0];
+        pa.cb = planes.as<uint8_t>() + L.plane[1];
+        pa.cr = planes.as<uint8_t>() + L.plane[2];
+        pa.width = frame->width; pa.height = frame->height; pa.n_comp = frame->n_comp;
+        pa.gw = (int)(L.bw[0] * 8 / H); pa.gh = (int)(L.bh[0] * 8 / V);
+        JpegFdctArgs fa;
+        fa.planes = planes.as<uint8_t>();
+        fa.quant = (const uint16_t*)dev;
+        fa.coef = coef.as<int16_t>();
+        for (int i = 0; i < 3; ++i) {
+            const int k = i < frame->n_comp ? i : frame->n_comp - 1;
+            fa.end[i] = L.base[k] + L.bw[k] * L.bh[k];
+            fa.bw[i] = L.bw[i];
+            fa.plane[i] = L.plane[i];
+        }
+        const dim3 pgrid((unsigned)((pa.gw + 63) / 64), (unsigned)((pa.gh + 3) / 4));
+        if (H == 2 && V == 2) SVGR_LAUNCH((k_jpeg_planes<2, 2>), pgrid, dim3(256), 0, ctx->stream, pa);
+        else if (H == 2) SVGR_LAUNCH((k_jpeg_planes<2, 1>), pgrid, dim3(256), 0, ctx->stream, pa);
+        else if (V == 2) SVGR_LAUNCH((k_jpeg_planes<1, 2>), pgrid, dim3(256), 0, ctx->stream, pa);
+        else SVGR_LAUNCH((k_jpeg_planes<1, 1>), pgrid, dim3(256), 0, ctx->stream, pa);
+        SVGR_LAUNCH(k_jpeg_fdct, dim3((unsigned)((L.blocks + JPEG_WG_BLOCKS - 1) / JPEG_WG_BLOCKS)), dim3(256), 0, ctx->stream, fa);
+        // (the one wait of upload_launch_wait covers this copy too)
+        (void)hipMemcpyAsync(coef_out, coef.p, (size_t)n_coef * 2, hipMemcpyDeviceToHost, ctx->stream);
     });
 }
 

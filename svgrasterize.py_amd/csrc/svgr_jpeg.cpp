@@ -1,4 +1,5 @@
-// svgr_jpeg.cpp -- the entropy-coded data of one JPEG scan decoded on the host (jpeg.py reads the markers).
+// svgr_jpeg.cpp -- the entropy-coded data of one JPEG scan decoded on the host (jpeg.py reads the markers), and, at the end of
+// the file, coded on the host (write_jpeg).
 //
 // Huffman decoding is a serial walk over the bits (each code's length is known only once it is read; the DC predictor and
 // the end-of-band run carry from block to block), so it is native host code, like the PNG filters, and rides in the same
@@ -357,6 +358,222 @@ int svgr_jpeg_entropy(const svgr_jpeg_scan* s, const uint8_t* huff_counts, const
         }
     }
     return SVGR_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The way back (write_jpeg): one baseline sequential scan coded from the frame's coefficients.  T.81 F.1.2 (Huffman
+// encoding), with the byte stuffing and restart rules above.  The same walk either writes the bits or counts the symbols.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Bytes out, most significant bit first; never past `cap`, but `pos` counts on, so the caller learns the room needed.
+struct BitsOut {
+    uint8_t* p;
+    int64_t cap, pos = 0;
+    uint64_t buf = 0;   // the low `cnt` bits are waiting
+    int cnt = 0;
+
+    BitsOut(uint8_t* out, int64_t n) : p(out), cap(n) {}
+    void byte(uint8_t b) {
+        if (pos < cap) p[pos] = b;
+        ++pos;
+    }
+    void put(uint32_t bits, int k) {   // 0 <= k <= 27, bits < 2^k
+        buf = buf << k | bits;
+        cnt += k;
+        while (cnt >= 8) {
+            const uint8_t b = (uint8_t)(buf >> (cnt - 8));
+            byte(b);
+            if (b == 0xFF) byte(0);
+            cnt -= 8;
+        }
+    }
+    void flush() {   // the last byte filled with ones
+        if (cnt) put((1u << (8 - cnt)) - 1, 8 - cnt);
+    }
+    void marker(uint8_t code) {
+        flush();
+        byte(0xFF);
+        byte(code);
+    }
+};
+
+struct HuffCode {
+    bool defined = false;
+    uint16_t code[256];
+    uint8_t len[256];   // 0: the table has no code for the symbol
+
+    bool build(const uint8_t* counts, const uint8_t* symbols) {
+        int total = 0;
+        for (int i = 0; i < 16; ++i) total += counts[i];
+        if (total == 0 || total > 256) return false;
+        memset(len, 0, sizeof len);
+        int32_t c = 0;
+        int k = 0;
+        for (int l = 1; l <= 16; ++l) {
+            for (int i = 0; i < counts[l - 1]; ++i, ++c, ++k) {
+                if (c >= (1 << l) || len[symbols[k]]) return false;   // (more codes than the length has; a symbol twice)
+                code[symbols[k]] = (uint16_t)c;
+                len[symbols[k]] = (uint8_t)l;
+            }
+            c <<= 1;
+        }
+        defined = true;
+        return true;
+    }
+};
+
+inline int category(int v) {   // the number of bits of |v|
+    int a = v < 0 ? -v : v, n = 0;
+    for (; a; a >>= 1) ++n;
+    return n;
+}
+
+// What a walk does with a symbol and the extra bits behind it: write them, or count the symbol.
+struct Writer {
+    BitsOut bits;
+    HuffCode dc[4], ac[4];
+    bool missing = false;
+    Writer(uint8_t* out, int64_t cap) : bits(out, cap) {}
+    void symbol(bool is_ac, int table, int sym, uint32_t extra, int n_extra) {
+        const HuffCode& h = is_ac ? ac[table] : dc[table];
+        if (!h.len[sym]) {
+            missing = true;
+            return;
+        }
+        bits.put((uint32_t)h.code[sym] << n_extra | extra, h.len[sym] + n_extra);
+    }
+    void restart(int m) { bits.marker((uint8_t)(0xD0 + m)); }
+};
+struct Counter {
+    int64_t* counts;
+    bool missing = false;
+    void symbol(bool is_ac, int table, int sym, uint32_t, int) { ++counts[256 * (4 * (int)is_ac + table) + sym]; }
+    void restart(int) {}
+};
+
+// the description of a sequential scan checked as svgr_jpeg_entropy checks it, and each component's place in the array
+struct ScanLayout {
+    int64_t base[3], bw[3], mcus_x, mcus_y, units_x, units_y;
+};
+int scan_layout(const svgr_jpeg_scan* s, int64_t n_coef, ScanLayout& L) {
+    const svgr_jpeg_frame& f = s->frame;
+    if ((f.n_comp != 1 && f.n_comp != 3) || f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return SVGR_E_INVALID;
+    int hmax = 1, vmax = 1;
+    for (int i = 0; i < f.n_comp; ++i) {
+        if (f.h[i] < 1 || f.h[i] > 2 || f.v[i] < 1 || f.v[i] > 2) return SVGR_E_INVALID;
+        hmax = f.h[i] > hmax ? f.h[i] : hmax;
+        vmax = f.v[i] > vmax ? f.v[i] : vmax;
+    }
+    if (f.n_comp == 1 && (hmax != 1 || vmax != 1)) return SVGR_E_INVALID;
+    L.mcus_x = (f.width + 8 * hmax - 1) / (8 * hmax);
+    L.mcus_y = (f.height + 8 * vmax - 1) / (8 * vmax);
+    int64_t total = 0;
+    for (int i = 0; i < f.n_comp; ++i) {
+        L.base[i] = total;
+        L.bw[i] = L.mcus_x * f.h[i];
+        total += L.bw[i] * L.mcus_y * f.v[i];
+    }
+    if (n_coef != total * 64) return SVGR_E_INVALID;
+    if (s->n_scan < 1 || s->n_scan > f.n_comp || s->restart_interval < 0 || s->restart_interval > 65535) return SVGR_E_INVALID;
+    for (int j = 0; j < s->n_scan; ++j) {
+        if (s->scan_comp[j] < 0 || s->scan_comp[j] >= f.n_comp || (j && s->scan_comp[j] <= s->scan_comp[j - 1])) return SVGR_E_INVALID;
+        if (s->dc_table[j] < 0 || s->dc_table[j] > 3 || s->ac_table[j] < 0 || s->ac_table[j] > 3) return SVGR_E_INVALID;
+    }
+    if (s->progressive || s->ss != 0 || s->se != 63 || s->ah != 0 || s->al != 0) return SVGR_E_INVALID;
+    L.units_x = L.mcus_x;
+    L.units_y = L.mcus_y;
+    if (s->n_scan == 1) {   // (one component: its own blocks, A.2.2)
+        const int ci = s->scan_comp[0];
+        const int64_t cw = ((int64_t)f.width * f.h[ci] + hmax - 1) / hmax, ch = ((int64_t)f.height * f.v[ci] + vmax - 1) / vmax;
+        L.units_x = (cw + 7) / 8;
+        L.units_y = (ch + 7) / 8;
+    }
+    return SVGR_OK;
+}
+
+template <class Sink>
+void code_block(Sink& sink, const int16_t* blk, int32_t* pred, int td, int ta) {
+    const int diff = (int)blk[0] - *pred;
+    *pred = blk[0];
+    int n = category(diff);
+    // (F.1.2.1: the low n bits of diff, of diff - 1 when it is negative; n beyond 11 has no symbol in a baseline table)
+    if (n > 11) sink.missing = true;
+    else sink.symbol(false, td, n, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1), n);
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int v = blk[kZigzag[k]];
+        if (v == 0) {
+            ++run;
+            continue;
+        }
+        for (; run >= 16; run -= 16) sink.symbol(true, ta, 0xF0, 0, 0);   // ZRL
+        n = category(v);
+        if (n > 10) sink.missing = true;
+        else sink.symbol(true, ta, run << 4 | n, (uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1), n);
+        run = 0;
+    }
+    if (run) sink.symbol(true, ta, 0x00, 0, 0);   // EOB
+}
+
+template <class Sink>
+void walk(const svgr_jpeg_scan* s, const ScanLayout& L, const int16_t* coef, Sink& sink) {
+    const svgr_jpeg_frame& f = s->frame;
+    int32_t pred[3] = {0, 0, 0};
+    int64_t since_restart = 0;
+    int next_restart = 0;
+    for (int64_t uy = 0; uy < L.units_y; ++uy)
+        for (int64_t ux = 0; ux < L.units_x; ++ux) {
+            if (s->restart_interval && since_restart == s->restart_interval) {
+                sink.restart(next_restart);
+                next_restart = (next_restart + 1) & 7;
+                since_restart = 0;
+                pred[0] = pred[1] = pred[2] = 0;
+            }
+            ++since_restart;
+            for (int j = 0; j < s->n_scan; ++j) {
+                const int ci = s->scan_comp[j];
+                const int nv = s->n_scan == 1 ? 1 : f.v[ci], nh = s->n_scan == 1 ? 1 : f.h[ci];
+                for (int y = 0; y < nv; ++y)
+                    for (int x = 0; x < nh; ++x)
+                        code_block(sink, coef + (L.base[ci] + (uy * nv + y) * L.bw[ci] + ux * nh + x) * 64, &pred[ci], s->dc_table[j],
+                                   s->ac_table[j]);
+            }
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int svgr_jpeg_entropy_encode(const svgr_jpeg_scan* s, const uint8_t* huff_counts, const uint8_t* huff_symbols, const int16_t* coef,
+                             int64_t n_coef, uint8_t* out, int64_t out_cap, int64_t* n_bytes) {
+    if (!s || !huff_counts || !huff_symbols || !coef || !n_bytes || out_cap < 0 || (!out && out_cap)) return SVGR_E_INVALID;
+    *n_bytes = 0;
+    ScanLayout L;
+    if (int rc = scan_layout(s, n_coef, L)) return rc;
+    Writer w(out, out_cap);
+    for (int j = 0; j < s->n_scan; ++j) {
+        const int d = s->dc_table[j], a = s->ac_table[j];
+        if (!w.dc[d].defined && !w.dc[d].build(huff_counts + 16 * d, huff_symbols + 256 * d)) return kBadCode;
+        if (!w.ac[a].defined && !w.ac[a].build(huff_counts + 16 * (4 + a), huff_symbols + 256 * (4 + a))) return kBadCode;
+    }
+    walk(s, L, coef, w);
+    w.bits.flush();
+    if (w.missing) return kBadCode;
+    *n_bytes = w.bits.pos;
+    return w.bits.pos > out_cap ? SVGR_JPEG_NO_ROOM : SVGR_OK;
+}
+
+int svgr_jpeg_symbol_counts(const svgr_jpeg_scan* s, const int16_t* coef, int64_t n_coef, int64_t* counts) {
+    if (!s || !coef || !counts) return SVGR_E_INVALID;
+    ScanLayout L;
+    if (int rc = scan_layout(s, n_coef, L)) return rc;
+    Counter c{counts};
+    walk(s, L, coef, c);
+    return c.missing ? (int)kBadCode : (int)SVGR_OK;
 }
 
 }  // extern "C"

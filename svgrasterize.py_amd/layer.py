@@ -670,9 +670,8 @@ class Layer:
         _abi._check(ctx.lib.svgr_layer_to_f32(ctx.handle, out32.handle, canvas.handle, rows * cols * 4, int(clip01)))
         return out32.download((rows, cols, 4), np.float32)
 
-    def to_rgba8(self) -> np.ndarray:
-        """(rows, cols, 4) uint8: straight-alpha sRGB, ``np.round(image * 255).astype(np.uint8)`` (S:211-212, S:262),
-        converted and quantised on the device; only the bytes cross PCIe (4 B per pixel instead of 32)."""
+    def _to_rgba8_device(self):
+        """(device buffer, rows, cols): the bytes of ``to_rgba8``, still on the device."""
         if self.channels != 4:
             raise ValueError("Only RGBA layers are supported")
         ctx = _abi.Context.get()
@@ -681,12 +680,38 @@ class Layer:
         rows, cols = layer._shape[0], layer._shape[1]
         out = ctx.alloc(max(rows * cols * 4, 4))
         _abi._check(ctx.lib.svgr_layer_to_rgba8(ctx.handle, out.handle, src.handle, rows * cols))
+        return out, rows, cols
+
+    def to_rgba8(self) -> np.ndarray:
+        """(rows, cols, 4) uint8: straight-alpha sRGB, ``np.round(image * 255).astype(np.uint8)`` (S:211-212, S:262),
+        converted and quantised on the device; only the bytes cross PCIe (4 B per pixel instead of 32)."""
+        out, rows, cols = self._to_rgba8_device()
         return out.download((rows, cols, 4), np.uint8)
 
     def write_png(self, output=None, level: int = 9, threads: int = 1):
         """PNG of the layer (Layer.write_png, S:209-213): 8-bit RGBA, filter 0, one IDAT -- byte-identical to the
         reference's file at the reference's zlib level 9 (``level`` trades size for speed, the pixels are the same)."""
         return canvas_to_png(self.to_rgba8(), output, level=level, threads=threads)
+
+    def write_jpeg(self, output=None, bg=None, **kw) -> bytes:
+        """Baseline JFIF JPEG of the layer (beyond the reference); returns the file's bytes, also written to ``output`` (a path
+        or a binary file object).  JPEG has no alpha: the layer goes over ``bg`` (premultiplied linear RGBA like every paint;
+        default opaque white) in float on the device, is quantised to 8 bits there, and the bytes go straight into the encoder's
+        device stage -- only the int16 DCT coefficients cross PCIe.  ``kw``: ``jpeg.write_jpeg``'s ``quality``,
+        ``subsampling``, ``grey``, ``optimize``, ``restart_interval``."""
+        from . import jpeg  # noqa: PLC0415
+
+        unknown = set(kw) - {"quality", "subsampling", "grey", "optimize", "restart_interval"}
+        if unknown:
+            raise TypeError(f"write_jpeg: unexpected arguments {sorted(unknown)}")
+        args = {"quality": 90, "subsampling": "4:2:0", "grey": False, "optimize": True, "restart_interval": 0, **kw}
+        jpeg.quant_tables(args["quality"])   # (bad arguments are refused before any device work)
+        if args["subsampling"] not in jpeg.SUBSAMPLINGS:
+            raise ValueError(f"JPEG subsampling is one of {', '.join(jpeg.SUBSAMPLINGS)}, not {args['subsampling']!r}")
+        if self.channels != 4:
+            raise ValueError("Only RGBA layers are supported")
+        buf, rows, cols = self.background((1.0, 1.0, 1.0, 1.0) if bg is None else bg)._to_rgba8_device()
+        return jpeg._encode_rgba8(buf, rows, cols, output, **args)
 
     def __repr__(self):
         return "Layer(x={}, y={}, w={}, h={}, pre_alpha={}, linear_rgb={})".format(
@@ -756,6 +781,20 @@ def canvas_to_png(canvas, output=None, level: int = 9, threads: int = 1):
     pack(output, b"IDAT", data)
     pack(output, b"IEND", b"")
     return output
+
+
+def canvas_to_jpeg(canvas, output=None, **kw) -> bytes:
+    """(height, width, 4) -> JPEG bytes, ``canvas_to_png``'s sibling (beyond the reference).  ``canvas`` is the uint8 array
+    of ``Layer.to_rgba8`` or float RGBA in [0, 1] (quantised like ``canvas_to_png``); it is uploaded and encoded by
+    ``jpeg.write_jpeg``, which takes ``kw``.  Alpha is ignored."""
+    from . import jpeg  # noqa: PLC0415
+
+    canvas = np.asarray(canvas)
+    if canvas.dtype != np.uint8:
+        canvas = np.round(canvas * 255.0).astype(np.uint8)
+    if canvas.ndim != 3 or canvas.shape[2] != 4:
+        raise ValueError("Only RGBA layers are supported")
+    return jpeg.write_jpeg(canvas, output, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

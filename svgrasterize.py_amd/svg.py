@@ -1176,14 +1176,30 @@ def svg_scene_from_filepath(path: str, fg=None, width=None, fonts=None):
         return svg_scene(f, fg, width, fonts, base_dir)
 
 
+def _output_format(output, format):
+    if format is None:
+        ext = os.path.splitext(os.fspath(output))[1].lower() if isinstance(output, (str, os.PathLike)) else ""
+        return "jpeg" if ext in (".jpg", ".jpeg", ".jpe") else "png"
+    if format not in ("png", "jpeg"):
+        raise ValueError(f"render_svg: format is 'png' or 'jpeg', not {format!r}")
+    return format
+
+
 def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transform=None, linear_rgb=False, fonts=None,
-               level: int = 9, threads: int = 1):
+               level: int = 9, threads: int = 1, format=None, quality: int = 90, subsampling: str = "4:2:0"):
     """Document in, PNG out: the steps of the reference's command line (S:3796-3877) as one library call, every pixel
     operation on the device.  ``svg`` is a file path or a file object; ``bg`` / ``fg`` are colours as ``parse_color``
     returns them; ``id`` renders a single element (on its own bounding box); ``transform`` is applied on top of the x/y
     swap of presentation space; ``level`` / ``threads`` go to the PNG writer (the defaults write the reference's exact
     file, ``threads`` > 1 the same pixels much faster).  Returns the PNG bytes (also written to ``output``: a path or a binary file object)
-    or None when there is nothing to draw."""
+    or None when there is nothing to draw.
+
+    ``format`` is "png" or "jpeg"; None takes it from ``output`` when that is a path ending in ``.jpg``, ``.jpeg`` or
+    ``.jpe`` (any case) and is PNG otherwise.  (Before JPEG output existed such a path received PNG bytes.)  A JPEG goes
+    through ``Layer.write_jpeg`` with ``quality`` and ``subsampling``: it has no alpha, so the image lies over ``bg``, or over
+    opaque white when there is none; its colour transform, DCT and quantiser run on the device, which makes it far quicker
+    to write than the PNG."""
+    format = _output_format(output, format)
     view = Transform().matrix(0, 1, 0, 1, 0, 0)
     if transform is not None:
         view = view @ transform
@@ -1207,6 +1223,8 @@ def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transfor
     layer, _hull = result
     if size is not None:
         layer = layer.convert(pre_alpha=True, linear_rgb=linear_rgb).on_canvas(int(h), int(w))
+    if format == "jpeg":
+        return layer.write_jpeg(output, bg=bg, quality=quality, subsampling=subsampling)
     if bg is not None:
         layer = layer.background(bg)
     png = layer.write_png(None, level, threads).getvalue()
