@@ -195,6 +195,17 @@ def convolve_matrix(image, kernel, divisor, bias, target, edge_mode, preserve_al
     return res
 
 
+def convolve_matrix_lds(tile, order_y, order_x):
+    """Bytes of dynamic LDS of a feConvolveMatrix launch with `tile` x `tile` workgroups: the input tile with its halo
+    (RGBA doubles) and the weights."""
+    return (tile + order_y - 1) * (tile + order_x - 1) * 32 + order_x * order_y * 8
+
+
+def convolve_matrix_tile(order_y, order_x):
+    """The workgroup tile svgr_layer_convolve_matrix picks: 16 while that fits in 64 KiB of LDS, else 8."""
+    return 16 if convolve_matrix_lds(16, order_y, order_x) <= 64 << 10 else 8
+
+
 def displacement_map(src, src_offset, disp, disp_offset, lin, scale, xc, yc):
     """feDisplacementMap: src premultiplied (rows_s, cols_s, 4) at src_offset, disp straight (rows, cols, 4) at disp_offset,
     lin = the 2 x 2 linear part of the transform; channels 0..3."""
