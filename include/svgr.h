@@ -514,6 +514,27 @@ int svgr_stroke_out_counts(const svgr_stroke_out* s, int64_t* n_segs, int64_t* n
 int svgr_stroke_out_copy(const svgr_stroke_out* s, int32_t* seg_types, double* seg_params, int32_t* subpath_sizes);
 void svgr_stroke_out_free(svgr_stroke_out* s);
 
+/* Path.dash (beyond the reference): stroke-dasharray / stroke-dashoffset applied to a path in the layout above, in front of
+ * svgr_path_stroke.  Every "on" dash comes back as one open subpath (its pieces in order, then a PATH_UNCLOSED line from its
+ * end to its start); a closed subpath that begins and ends inside a dash gets that dash as ONE subpath, and stays closed when
+ * a single dash covers it.  Lines (PATH_LINE, PATH_CLOSED) and cubics are dashed, a PATH_UNCLOSED line is not part of the
+ * outline; quadratics and arcs are converted by the caller.  `dashes`: n_dashes lengths, used twice over when their count is
+ * odd (at most 64 entries then); `offset` may be negative or beyond the period; every subpath restarts the pattern.
+ * `path_length` > 0 (SVG pathLength) multiplies the dashes and the offset by (measured length of all subpaths) / path_length.
+ * An empty list, a negative or non-finite entry, a zero sum or a list without a gap is a solid stroke: the input comes back
+ * unchanged (no device work).  Arc length: a line is sqrt(dx^2 + dy^2); a cubic is 32 equal parameter sub-intervals of 4-point
+ * Gauss-Legendre quadrature each (within 5.5e-5 relative of the true length on near-cusp cubics, 1e-14 on smooth ones).
+ * SVGR_E_INVALID, before anything is launched, for a coordinate that is not finite or lies beyond +-1e150 (its square would
+ * leave the doubles) or an unknown segment type.  SVGR_E_OVERFLOW when the result leaves the 32-bit counts of svgr_stroke_out
+ * or one segment alone has more than 2^20 pieces: that is known from the counting kernels, so those have run; nothing is
+ * launched after them.  SVGR_E_STATE should the placing kernels meet a place outside the result (the tables disagree: a
+ * defect, never an input's doing).  The result is identical from run to run.
+ * svgr_dash_scan_segments: the number of segments one workgroup of the dasher's scans covers (its launch seam).            */
+int svgr_path_dash(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
+                   int64_t n_subpaths, const double* dashes, int64_t n_dashes, double offset, double path_length,
+                   svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
+int svgr_dash_scan_segments(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

@@ -168,6 +168,8 @@ _PROTOS = {
     "svgr_layer_convolve": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64]),
     "svgr_layer_convolve_ops": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_uint]),
     "svgr_path_stroke": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_int, C.POINTER(_P)]),
+    "svgr_path_dash": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(_P)]),
+    "svgr_dash_scan_segments": (C.c_int, []),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
@@ -553,6 +555,11 @@ def path_stroke(seg_types, seg_params, subpath_sizes, width: float, linecap: int
         why = {-1: "unsupported segment type or bad cap / join", -3: "out of memory"}.get(
             rc, "the offset of a cubic does not converge (degenerate control points)")
         raise ValueError(f"svgr_path_stroke failed ({rc}): {why}")
+    return _stroke_out(lib, out)
+
+
+def _stroke_out(lib, out):
+    """The arrays of a svgr_stroke_out, which is freed."""
     try:
         n, ns = C.c_int64(), C.c_int64()
         lib.svgr_stroke_out_counts(out, C.byref(n), C.byref(ns))
@@ -563,6 +570,40 @@ def path_stroke(seg_types, seg_params, subpath_sizes, width: float, linecap: int
     finally:
         lib.svgr_stroke_out_free(out)
     return types, params, sizes
+
+
+def dash_is_solid(dashes) -> bool:
+    """Whether a dash list asks for a solid stroke (svgr_path_dash hands the path back unchanged, without touching a device):
+    empty, a negative or non-finite entry, a zero sum, or no gap of non-zero length."""
+    d = [float(v) for v in dashes] if dashes is not None else []
+    if not d or any(not np.isfinite(v) or v < 0 for v in d) or not sum(d) > 0 or not np.isfinite(sum(d)):
+        return True
+    return not any(v > 0 for v in (d * 2 if len(d) & 1 else d)[1::2])
+
+
+def path_dash(seg_types, seg_params, subpath_sizes, dashes, offset: float = 0.0, path_length: float = 0.0, ctx: "Context | None" = None):
+    """svgr_path_dash: (types, params (n, 8), sizes) of the path cut into its dashes, on the device of `ctx` (default: the
+    process's context; none is made for a dash list that asks for a solid stroke)."""
+    lib = load_library()
+    seg_types = np.ascontiguousarray(seg_types, dtype=np.int32)
+    seg_params = np.ascontiguousarray(seg_params, dtype=np.float64).reshape(-1, 8)
+    subpath_sizes = np.ascontiguousarray(subpath_sizes, dtype=np.int32)
+    dashes = np.ascontiguousarray(dashes if dashes is not None else [], dtype=np.float64).reshape(-1)
+    if int(subpath_sizes.sum()) != len(seg_types) or len(seg_params) != len(seg_types):
+        raise ValueError("segment arrays do not match the subpath sizes")
+    handle = None
+    if not dash_is_solid(dashes) and len(seg_types):
+        handle = (ctx if ctx is not None else Context.get()).handle
+    out = _P()
+    _check(lib.svgr_path_dash(handle, seg_types.ctypes.data_as(_P), seg_params.ctypes.data_as(_P), subpath_sizes.ctypes.data_as(_P),
+                              len(subpath_sizes), dashes.ctypes.data_as(_P), len(dashes), float(offset),
+                              float(path_length or 0.0), C.byref(out)))
+    return _stroke_out(lib, out)
+
+
+def dash_scan_segments() -> int:
+    """Segments per workgroup of the dasher's scans (svgr_dash_scan_segments)."""
+    return int(load_library().svgr_dash_scan_segments())
 
 
 def image_levels(h: int, w: int):

@@ -7502,3 +7502,454 @@ static int layer_convolve_impl(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
 }
 
 }  // extern "C"
+
+// ======================================================================================
+// Path.dash: stroke-dasharray / stroke-dashoffset in front of the host stroker (svgr_path_dash).
+// The per-lane arithmetic is svgr_dash.h; DESIGN.md "Dashed strokes" has the definitions.
+//
+//   k_dash_measure   32 lanes per segment (two segments per wave): lane i integrates sub-interval i of a cubic, a 32-lane
+//                    inclusive scan gives the segment's cumulative table and its length; a line costs one lane
+//   k_scan_*         two-level scans, DASH_S items per workgroup: the segment lengths restart at every subpath (a segmented
+//                    scan), the piece / dash counts run over the whole path.  Their association depends on the launch
+//                    geometry alone, never on the order in which waves run
+//   k_dash_pattern   one workgroup: the path's total length (pathLength scales the pattern by it) and the pattern's tables
+//   k_dash_count     per segment, closed form: the pieces it emits and the output subpaths it starts
+//   k_dash_wrap      per subpath: where its pieces and dashes begin, and, for a closed subpath whose trailing and leading
+//                    dash are one, how many pieces the leading dash has (they are placed behind the trailing ones)
+//   k_dash_emit      32 lanes per segment stride over its pieces: invert both ends, split, store at the piece's place
+//   k_dash_close     per output subpath: its terminating line and its size
+// Every place is a prefix sum; no atomic takes part.  All geometry is f64.
+// ======================================================================================
+#include "svgr_dash.h"
+#include "svgr_stroke_out.h"
+
+constexpr int DASH_S = 1024;      // segments one workgroup scans (256 threads x 4): the test shapes sit at its multiples
+constexpr int DASH_SEGS_WG = 8;   // segments per workgroup of the 32-lanes-per-segment kernels
+// The pieces one segment may have.  Its 32 lanes stride over them, so this bounds the time of one half-wave: 2^15 rounds of two
+// inversions.  (The path's total is bounded by the 32-bit counts of the result alone.)
+constexpr long long DASH_SEG_PIECES_MAX = 1ll << 20;
+constexpr double DASH_COORD_MAX = 1e150;   // beyond it dx * dx leaves the doubles and a length would be infinite
+
+struct DashFV { double v; int f; int pad; };        // segmented sum: f = a subpath begins at or in front of this item
+struct DashCnt { long long p, d; };                 // pieces, output subpaths
+struct DashFVOp {
+    __device__ static DashFV zero() { return DashFV{0.0, 0, 0}; }
+    __device__ static DashFV add(const DashFV& a, const DashFV& b) { return DashFV{b.f ? b.v : a.v + b.v, a.f | b.f, 0}; }
+};
+struct DashCntOp {
+    __device__ static DashCnt zero() { return DashCnt{0, 0}; }
+    __device__ static DashCnt add(const DashCnt& a, const DashCnt& b) { return DashCnt{a.p + b.p, a.d + b.d}; }
+};
+struct DashSub { long long A, n, nl, dbase, nd; int mode, pad; };   // k_dash_wrap's row of a subpath
+struct DashTot { DashCnt c; int too_many, pad; };                   // what the host reads back after the counting kernels
+struct StreamDrain {   // no block and no host buffer of a call goes away while the stream may still use it
+    hipStream_t st;
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+};
+
+// inclusive scan of DASH_S items per workgroup, in place; tot[b] = the workgroup's sum
+template <class T, class Op>
+__global__ __launch_bounds__(256) void k_scan_block(T* __restrict__ a, T* __restrict__ tot, int n) {
+    __shared__ T sh[256];
+    const int t = threadIdx.x, base = blockIdx.x * DASH_S + t * 4;
+    T v[4];
+    T acc = Op::zero();
+    for (int i = 0; i < 4; ++i) {
+        v[i] = base + i < n ? a[base + i] : Op::zero();
+        acc = Op::add(acc, v[i]);
+        v[i] = acc;
+    }
+    sh[t] = acc;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        T x = sh[t];
+        if (t >= d) x = Op::add(sh[t - d], x);
+        __syncthreads();
+        sh[t] = x;
+        __syncthreads();
+    }
+    const T pre = t ? sh[t - 1] : Op::zero();
+    for (int i = 0; i < 4; ++i)
+        if (base + i < n) a[base + i] = Op::add(pre, v[i]);
+    if (t == 255) tot[blockIdx.x] = sh[255];
+}
+// one workgroup: tot[b] <- sum of the workgroups in front of b
+template <class T, class Op>
+__global__ __launch_bounds__(256) void k_scan_tops(T* __restrict__ tot, int nb) {
+    __shared__ T sh[256];
+    const int t = threadIdx.x;
+    T carry = Op::zero();
+    for (int base = 0; base < nb; base += 256) {
+        const T mine = base + t < nb ? tot[base + t] : Op::zero();
+        sh[t] = mine;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            T x = sh[t];
+            if (t >= d) x = Op::add(sh[t - d], x);
+            __syncthreads();
+            sh[t] = x;
+            __syncthreads();
+        }
+        const T excl = Op::add(carry, t ? sh[t - 1] : Op::zero());
+        if (base + t < nb) tot[base + t] = excl;
+        carry = Op::add(carry, sh[255]);
+        __syncthreads();
+    }
+}
+template <class T, class Op>
+__global__ __launch_bounds__(256) void k_scan_apply(T* __restrict__ a, const T* __restrict__ tot, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int b = i / DASH_S;
+    if (i < n && b > 0) a[i] = Op::add(tot[b], a[i]);
+}
+
+__global__ __launch_bounds__(256) void k_dash_measure(const int* __restrict__ types, const double* __restrict__ params,
+                                                      const int* __restrict__ seg_sub, const int* __restrict__ sub_off, int n,
+                                                      double* __restrict__ tab, double* __restrict__ len, DashFV* __restrict__ cum) {
+    const int l = threadIdx.x & 31, seg = blockIdx.x * DASH_SEGS_WG + (threadIdx.x >> 5);
+    if (seg >= n) return;   // (uniform over the 32 lanes of a segment)
+    const int type = types[seg];
+    const double* c = params + (size_t)seg * 8;
+    double total = 0.0;
+    if (type == SVGR_PATH_CUBIC) {
+        double x = dash_sub_length(c, l);
+        for (int d = 1; d < 32; d <<= 1) {
+            const double y = __shfl_up(x, d, 32);
+            if (l >= d) x += y;
+        }
+        tab[(size_t)seg * DASH_SUB + l] = x;
+        total = __shfl(x, 31, 32);
+    } else if (type != SVGR_PATH_UNCLOSED) {
+        total = dash_line_length(c);
+    }
+    if (l == 0) {
+        len[seg] = total;
+        cum[seg] = DashFV{total, seg == sub_off[seg_sub[seg]] ? 1 : 0, 0};
+    }
+}
+
+// one workgroup: the sum of the subpaths' lengths (strided partial sums, then a tree: a fixed association), the pattern from it
+__global__ __launch_bounds__(256) void k_dash_pattern(const DashFV* __restrict__ cum, const int* __restrict__ sub_off, int n_sub,
+                                                      const double* __restrict__ raw, int n_raw, double offset, double path_length,
+                                                      DashPat* __restrict__ pat) {
+    __shared__ double sh[256];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    if (path_length > 0.0)
+        for (int s = t; s < n_sub; s += 256) acc += cum[sub_off[s + 1] - 1].v;
+    sh[t] = acc;
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {
+        if (t < d) sh[t] += sh[t + d];
+        __syncthreads();
+    }
+    if (t == 0) {
+        double scale = 1.0;
+        if (path_length > 0.0) scale = sh[0] / path_length;
+        if (!(scale > 0.0) || !(scale < 1.7e308)) scale = 1.0;   // (a path without length has no pieces either way)
+        DashPat p;
+        dash_build_pattern(raw, n_raw, offset, scale, p);
+        if (!(p.P > 0.0) || !(p.P < 1.7e308)) p.N = 0;           // (a scaled period that left the doubles: nothing is drawn)
+        *pat = p;
+    }
+}
+
+struct DashSegIn { int type, first, last, mode; double len, s0, s1; };
+__device__ __forceinline__ DashSegIn dash_seg_in(const DashPat& pat, const int* types, const int* seg_sub, const int* sub_off,
+                                                 const double* len, const DashFV* cum, int i) {
+    DashSegIn s;
+    const int sp = seg_sub[i];
+    s.first = sub_off[sp];
+    s.last = sub_off[sp + 1] - 1;
+    s.type = types[i];
+    s.len = len[i];
+    s.s1 = cum[i].v;
+    s.s0 = i == s.first ? 0.0 : cum[i - 1].v;
+    s.mode = dash_sub_mode(pat, cum[s.last].v, types[s.last] == SVGR_PATH_CLOSED);
+    return s;
+}
+
+__global__ __launch_bounds__(256) void k_dash_count(const DashPat* __restrict__ patp, const int* __restrict__ types,
+                                                    const int* __restrict__ seg_sub, const int* __restrict__ sub_off,
+                                                    const double* __restrict__ len, const DashFV* __restrict__ cum, int n,
+                                                    DashCnt* __restrict__ cnt, DashTot* __restrict__ tot) {
+    __shared__ DashPat pat;
+    for (int w = threadIdx.x; w < (int)(sizeof(DashPat) / 4); w += 256) ((int*)&pat)[w] = ((const int*)patp)[w];
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const DashSegIn s = dash_seg_in(pat, types, seg_sub, sub_off, len, cum, i);
+    DashSeg g;
+    dash_seg_pieces(pat, s.type, s.len, s.s0, s.s1, s.mode, g);
+    cnt[i] = DashCnt{g.cnt, g.cnt - g.cont};
+    if (g.cnt > DASH_SEG_PIECES_MAX) tot->too_many = 1;   // (the host zeroed it; every writer stores the same value)
+}
+
+// (cnt: the inclusive scan of k_dash_count's rows; tot[0] = the path's totals, read back by the host)
+__global__ __launch_bounds__(256) void k_dash_wrap(const DashPat* __restrict__ patp, const int* __restrict__ types,
+                                                   const int* __restrict__ sub_off, const DashFV* __restrict__ cum,
+                                                   const DashCnt* __restrict__ cnt, int n, int n_sub, DashSub* __restrict__ sub,
+                                                   DashTot* __restrict__ tot) {
+    const int sp = blockIdx.x * 256 + threadIdx.x;
+    if (sp == 0) tot->c = n ? cnt[n - 1] : DashCnt{0, 0};
+    if (sp >= n_sub) return;
+    const DashPat& pat = *patp;
+    const int first = sub_off[sp], last = sub_off[sp + 1] - 1;
+    DashSub r;
+    r.A = first ? cnt[first - 1].p : 0;
+    r.dbase = first ? cnt[first - 1].d : 0;
+    r.n = cnt[last].p - r.A;
+    r.nd = cnt[last].d - r.dbase;
+    r.mode = dash_sub_mode(pat, cum[last].v, types[last] == SVGR_PATH_CLOSED);
+    r.nl = 0;
+    r.pad = 0;
+    if (r.mode == DASH_MERGED) {
+        // the last segment that begins inside the leading dash's interval: the pieces up to its first one are the leading dash
+        long long k0, k;
+        int j0, j;
+        double rr;
+        dash_idx_ge(pat, pat.phase, k0, j0, rr);
+        int lo = first, hi = last;   // (the first segment begins at 0: inside)
+        while (lo < hi) {            // at most 31 halvings of an int range
+            const int mid = lo + (hi - lo + 1) / 2;
+            dash_idx_ge(pat, cum[mid - 1].v + pat.phase, k, j, rr);
+            if (k < k0 || (k == k0 && j <= j0)) lo = mid; else hi = mid - 1;
+        }
+        const long long before = lo ? cnt[lo - 1].p : 0, own = cnt[lo].p - before;
+        r.nl = before + (own > 0 ? 1 : 0) - r.A;
+    }
+    sub[sp] = r;
+}
+
+__global__ __launch_bounds__(256) void k_dash_emit(const DashPat* __restrict__ patp, const int* __restrict__ types,
+                                                   const double* __restrict__ params, const int* __restrict__ seg_sub,
+                                                   const int* __restrict__ sub_off, const double* __restrict__ tab,
+                                                   const double* __restrict__ len, const DashFV* __restrict__ cum,
+                                                   const DashCnt* __restrict__ cnt, const DashSub* __restrict__ sub, int n,
+                                                   long long n_out, long long n_dash, int* __restrict__ out_types,
+                                                   double* __restrict__ out_params, int* __restrict__ dstart, int* __restrict__ dkind,
+                                                   int* __restrict__ bad) {
+    __shared__ DashPat pat;
+    for (int w = threadIdx.x; w < (int)(sizeof(DashPat) / 4); w += 256) ((int*)&pat)[w] = ((const int*)patp)[w];
+    __syncthreads();
+    const int l = threadIdx.x & 31, i = blockIdx.x * DASH_SEGS_WG + (threadIdx.x >> 5);
+    if (i >= n) return;
+    const DashSegIn s = dash_seg_in(pat, types, seg_sub, sub_off, len, cum, i);
+    DashSeg g;
+    dash_seg_pieces(pat, s.type, s.len, s.s0, s.s1, s.mode, g);
+    if (g.cnt == 0) return;
+    const DashSub sb = sub[seg_sub[i]];
+    const long long poff = i ? cnt[i - 1].p : 0, doff = i ? cnt[i - 1].d : 0;
+    long long k0 = 0;
+    int j0 = 0;
+    if (s.mode == DASH_MERGED) {
+        double rr;
+        dash_idx_ge(pat, pat.phase, k0, j0, rr);
+    }
+    const double* c = params + (size_t)i * 8;
+    const double* tb = tab + (size_t)i * DASH_SUB;
+    const double own_len = s.type == SVGR_PATH_CUBIC ? tb[DASH_SUB - 1] : s.len;
+    for (long long q = l; q < g.cnt; q += 32) {
+        long long k;
+        int j;
+        double o[8];
+        const int ot = dash_piece(pat, g, s.type, c, tb, own_len, s.mode, q, k, j, o);
+        long long place = poff + q, d = doff + q - (g.cont ? 1 : 0);
+        if (s.mode == DASH_MERGED) {
+            long long local = place - sb.A - sb.nl;
+            if (local < 0) local += sb.n;
+            place = sb.A + local;
+            if (k == k0 && j == j0) d = sb.dbase + sb.nd - 1;   // the leading dash: part of the subpath's last one
+        }
+        const long long at = place + d;
+        if (d < 0 || d >= n_dash || at < 0 || at >= n_out) {   // no place outside the arrays, whatever the tables say:
+            *bad = 1;                                          // the host reports it
+            continue;
+        }
+        if (q > 0 || !g.cont) {
+            dstart[d] = (int)place;
+            dkind[d] = s.mode == DASH_WHOLE ? SVGR_PATH_CLOSED : SVGR_PATH_UNCLOSED;
+        }
+        out_types[at] = ot;
+        double* dst = out_params + (size_t)at * 8;
+        for (int e = 0; e < 8; ++e) dst[e] = o[e];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dash_close(const int* __restrict__ dstart, const int* __restrict__ dkind, long long n_pieces,
+                                                    long long n_dash, int* __restrict__ out_types, double* __restrict__ out_params,
+                                                    int* __restrict__ out_sizes, int* __restrict__ bad) {
+    const long long d = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (d >= n_dash) return;
+    const long long first = dstart[d] + d, end = (d + 1 < n_dash ? (long long)dstart[d + 1] : n_pieces) + d;
+    if (first < 0 || end <= first || end >= n_pieces + n_dash) { out_sizes[d] = 0; *bad = 1; return; }
+    const double* a = out_params + (size_t)first * 8;
+    const double* b = out_params + (size_t)(end - 1) * 8;
+    const int be = out_types[end - 1] == SVGR_PATH_CUBIC ? 6 : 2;
+    double* o = out_params + (size_t)end * 8;
+    o[0] = b[be]; o[1] = b[be + 1]; o[2] = a[0]; o[3] = a[1];
+    o[4] = o[5] = o[6] = o[7] = 0.0;
+    out_types[end] = dkind[d];
+    out_sizes[d] = (int)(end - first + 1);
+}
+
+template <class T, class Op>
+static void dash_scan(hipStream_t st, T* a, T* tot, int n) {
+    const int nb = (n + DASH_S - 1) / DASH_S;
+    SVGR_LAUNCH((k_scan_block<T, Op>), dim3((unsigned)nb), dim3(256), 0, st, a, tot, n);
+    if (nb > 1) {
+        SVGR_LAUNCH((k_scan_tops<T, Op>), dim3(1), dim3(256), 0, st, tot, nb);
+        SVGR_LAUNCH((k_scan_apply<T, Op>), grid1((size_t)n), dim3(256), 0, st, a, (const T*)tot, n);
+    }
+}
+
+static int path_dash_impl(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
+                          int64_t n_subpaths, const double* dashes, int64_t n_dashes, double offset, double path_length,
+                          svgr_stroke_out** out) {
+    if (!out || n_subpaths < 0 || n_dashes < 0 || (n_subpaths > 0 && (!seg_types || !seg_params || !subpath_sizes)) || (n_dashes > 0 && !dashes))
+        return fail(SVGR_E_INVALID, "svgr_path_dash: bad arguments");
+    if (!std::isfinite(offset)) return fail(SVGR_E_INVALID, "svgr_path_dash: the offset is not finite");
+    int64_t n = 0;
+    for (int64_t s = 0; s < n_subpaths; ++s) {
+        if (subpath_sizes[s] < 0) return fail(SVGR_E_INVALID, "svgr_path_dash: negative subpath size");
+        n += subpath_sizes[s];
+        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "svgr_path_dash: more than 2^30 segments");
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const int t = seg_types[i];
+        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
+            return fail(SVGR_E_INVALID, "svgr_path_dash: segment %lld has type %d (quadratics and arcs are converted by the caller)", (long long)i, t);
+        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
+        for (int e = 0; e < np; ++e)
+            if (!(std::fabs(seg_params[8 * i + e]) <= DASH_COORD_MAX))
+                return fail(SVGR_E_INVALID, "svgr_path_dash: segment %lld has a coordinate that is not finite or beyond 1e150", (long long)i);
+    }
+    std::unique_ptr<svgr_stroke_out> res(new svgr_stroke_out());
+    // a pattern that asks for a solid stroke: the input comes back as it is
+    bool solid = n_dashes < 1;
+    double sum = 0.0;
+    int gaps = 0;
+    for (int64_t j = 0; j < n_dashes && !solid; ++j) {
+        if (!std::isfinite(dashes[j]) || dashes[j] < 0.0) solid = true;
+        else sum += dashes[j];
+    }
+    if (!solid) {
+        const int64_t m = (n_dashes & 1) ? 2 * n_dashes : n_dashes;
+        for (int64_t j = 0; j < m; ++j) gaps += (j & 1) && dashes[j % n_dashes] > 0.0;
+        if (!(sum > 0.0) || !std::isfinite(sum) || gaps == 0) solid = true;
+        else if (m > DASH_MAX) return fail(SVGR_E_INVALID, "svgr_path_dash: %lld dash entries (at most %d, counting an odd list twice)", (long long)m, DASH_MAX);
+    }
+    if (solid || n == 0) {
+        res->types.assign(seg_types, seg_types + n);
+        res->params.assign(seg_params, seg_params + 8 * n);
+        for (int64_t s = 0; s < n_subpaths; ++s) res->sizes.push_back(subpath_sizes[s]);
+        *out = res.release();
+        return 0;
+    }
+    if (!ctx) return fail(SVGR_E_INVALID, "svgr_path_dash: no context");
+    // ---- one upload: coordinates, types, the subpath of every segment, the subpaths' first segments, the dash list
+    std::vector<int32_t> sub_off{0};
+    for (int64_t s = 0; s < n_subpaths; ++s)
+        if (subpath_sizes[s] > 0) sub_off.push_back(sub_off.back() + subpath_sizes[s]);
+    const int n_sub = (int)sub_off.size() - 1, ni = (int)n, nd_raw = (int)n_dashes;
+    const size_t b_params = (size_t)n * 64, b_types = (((size_t)n * 4) + 63) & ~(size_t)63, b_sub = (((size_t)(n_sub + 1) * 4) + 63) & ~(size_t)63;
+    const size_t b_raw = (size_t)nd_raw * 8;
+    std::vector<char> blob(b_params + 2 * b_types + b_sub + b_raw);
+    memcpy(blob.data(), seg_params, b_params);
+    memcpy(blob.data() + b_params, seg_types, (size_t)n * 4);
+    int32_t* h_seg_sub = (int32_t*)(blob.data() + b_params + b_types);
+    for (int s = 0; s < n_sub; ++s)
+        for (int i = sub_off[(size_t)s]; i < sub_off[(size_t)s + 1]; ++i) h_seg_sub[i] = s;
+    memcpy(blob.data() + b_params + 2 * b_types, sub_off.data(), (size_t)(n_sub + 1) * 4);
+    memcpy(blob.data() + b_params + 2 * b_types + b_sub, dashes, b_raw);
+
+    HIPCHK(enter_ctx(ctx));
+    if (int rc = ensure_pinned(ctx, sizeof(DashTot))) return rc;
+    hipStream_t st = ctx->stream;
+    const int nb = (ni + DASH_S - 1) / DASH_S;
+    std::vector<char> back;
+    PoolBlock in, tab, len, cum, cnt, tops_fv, tops_cnt, sub, pat, tot, outb, dstart, dkind;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(tab.alloc((size_t)n * DASH_SUB * 8, ctx->device));
+    HIPCHK(len.alloc((size_t)n * 8, ctx->device));
+    HIPCHK(cum.alloc((size_t)n * sizeof(DashFV), ctx->device));
+    HIPCHK(cnt.alloc((size_t)n * sizeof(DashCnt), ctx->device));
+    HIPCHK(tops_fv.alloc((size_t)nb * sizeof(DashFV), ctx->device));
+    HIPCHK(tops_cnt.alloc((size_t)nb * sizeof(DashCnt), ctx->device));
+    HIPCHK(sub.alloc((size_t)n_sub * sizeof(DashSub), ctx->device));
+    HIPCHK(pat.alloc(sizeof(DashPat), ctx->device));
+    HIPCHK(tot.alloc(sizeof(DashTot), ctx->device));
+    HIPCHK(hipMemsetAsync(tot.p, 0, sizeof(DashTot), st));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const double* d_params = in.as<double>();
+    const int* d_types = (const int*)(in.as<char>() + b_params);
+    const int* d_seg_sub = (const int*)(in.as<char>() + b_params + b_types);
+    const int* d_sub_off = (const int*)(in.as<char>() + b_params + 2 * b_types);
+    const double* d_raw = (const double*)(in.as<char>() + b_params + 2 * b_types + b_sub);
+    const dim3 seg_grid((unsigned)((ni + DASH_SEGS_WG - 1) / DASH_SEGS_WG));
+    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, d_seg_sub, d_sub_off, ni, tab.as<double>(), len.as<double>(),
+                cum.as<DashFV>());
+    dash_scan<DashFV, DashFVOp>(st, cum.as<DashFV>(), tops_fv.as<DashFV>(), ni);
+    SVGR_LAUNCH(k_dash_pattern, dim3(1), dim3(256), 0, st, (const DashFV*)cum.p, d_sub_off, n_sub, d_raw, nd_raw, offset, path_length,
+                pat.as<DashPat>());
+    SVGR_LAUNCH(k_dash_count, grid1((size_t)ni), dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_seg_sub, d_sub_off, (const double*)len.p,
+                (const DashFV*)cum.p, ni, cnt.as<DashCnt>(), tot.as<DashTot>());
+    dash_scan<DashCnt, DashCntOp>(st, cnt.as<DashCnt>(), tops_cnt.as<DashCnt>(), ni);
+    SVGR_LAUNCH(k_dash_wrap, grid1((size_t)n_sub), dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_sub_off, (const DashFV*)cum.p,
+                (const DashCnt*)cnt.p, ni, n_sub, sub.as<DashSub>(), tot.as<DashTot>());
+    HIPCHK(hipGetLastError());
+    // ---- the counts come back through the context's page-locked staging
+    HIPCHK(hipMemcpyAsync(ctx->pinned, tot.p, sizeof(DashTot), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    DashTot counted;
+    memcpy(&counted, ctx->pinned, sizeof counted);
+    const DashCnt total = counted.c;
+    if (counted.too_many)
+        return fail(SVGR_E_OVERFLOW, "svgr_path_dash: a segment with more than %lld pieces", DASH_SEG_PIECES_MAX);
+    if (total.p < 0 || total.d < 0 || total.p + total.d > INT32_MAX)
+        return fail(SVGR_E_OVERFLOW, "svgr_path_dash: %lld pieces in %lld dashes do not fit the 32-bit counts of the result", total.p, total.d);
+    if (total.p == 0 || total.d == 0) {   // nothing is drawn
+        *out = res.release();
+        return 0;
+    }
+    const size_t n_out = (size_t)(total.p + total.d), n_dash = (size_t)total.d;
+    const size_t o_types = n_out * 64, o_sizes = o_types + ((n_out * 4 + 63) & ~(size_t)63);
+    const size_t o_bad = o_sizes + ((n_dash * 4 + 63) & ~(size_t)63), o_end = o_bad + 4;   // (the placing kernels' error flag travels with the result)
+    HIPCHK(outb.alloc(o_end, ctx->device));
+    HIPCHK(dstart.alloc(n_dash * 4, ctx->device));
+    HIPCHK(dkind.alloc(n_dash * 4, ctx->device));
+    double* d_out_params = outb.as<double>();
+    int* d_out_types = (int*)(outb.as<char>() + o_types);
+    int* d_out_sizes = (int*)(outb.as<char>() + o_sizes);
+    int* d_bad = (int*)(outb.as<char>() + o_bad);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, st));
+    SVGR_LAUNCH(k_dash_emit, seg_grid, dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_params, d_seg_sub, d_sub_off, (const double*)tab.p,
+                (const double*)len.p, (const DashFV*)cum.p, (const DashCnt*)cnt.p, (const DashSub*)sub.p, ni, (long long)n_out,
+                (long long)n_dash, d_out_types, d_out_params, dstart.as<int>(), dkind.as<int>(), d_bad);
+    SVGR_LAUNCH(k_dash_close, grid1(n_dash), dim3(256), 0, st, (const int*)dstart.p, (const int*)dkind.p, total.p, total.d, d_out_types,
+                d_out_params, d_out_sizes, d_bad);
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    back.resize(o_end);
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "svgr_path_dash: the counting and the placing kernels disagree about a place");
+    res->params.assign((const double*)back.data(), (const double*)back.data() + n_out * 8);
+    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    res->sizes.assign((const int32_t*)(back.data() + o_sizes), (const int32_t*)(back.data() + o_sizes) + n_dash);
+    *out = res.release();
+    return 0;
+}
+
+extern "C" {
+int svgr_dash_scan_segments(void) { return DASH_S; }
+int svgr_path_dash(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes, int64_t n_subpaths,
+                   const double* dashes, int64_t n_dashes, double offset, double path_length, svgr_stroke_out** out) {
+    return abi_guard("svgr_path_dash", [&]() {
+        return path_dash_impl(ctx, seg_types, seg_params, subpath_sizes, n_subpaths, dashes, n_dashes, offset, path_length, out);
+    });
+}
+}  // extern "C"

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/svgr.h"
+#include "svgr_stroke_out.h"
 
 namespace {
 
@@ -242,20 +243,16 @@ static Curve reversed(const Curve& c) {
 
 }  // namespace
 
-struct svgr_stroke_out {
-    std::vector<int32_t> types;
-    std::vector<double> params;  // 8 per segment
-    std::vector<int32_t> sizes;
-    void add_subpath(const std::vector<Curve>& curves) {
-        for (const Curve& c : curves) {
-            types.push_back(c.n == 2 ? SVGR_PATH_LINE : (c.n == 3 ? SVGR_PATH_QUAD : SVGR_PATH_CUBIC));
-            double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 0; i < c.n; ++i) { q[2 * i] = c.p[i].x; q[2 * i + 1] = c.p[i].y; }
-            params.insert(params.end(), q, q + 8);
-        }
-        sizes.push_back((int32_t)curves.size());
+// one subpath of curves appended to the result
+static void add_subpath(svgr_stroke_out* res, const std::vector<Curve>& curves) {
+    for (const Curve& c : curves) {
+        res->types.push_back(c.n == 2 ? SVGR_PATH_LINE : (c.n == 3 ? SVGR_PATH_QUAD : SVGR_PATH_CUBIC));
+        double q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < c.n; ++i) { q[2 * i] = c.p[i].x; q[2 * i + 1] = c.p[i].y; }
+        res->params.insert(res->params.end(), q, q + 8);
     }
-};
+    res->sizes.push_back((int32_t)curves.size());
+}
 
 extern "C" {
 
@@ -322,7 +319,7 @@ static int path_stroke_impl(const int32_t* seg_types, const double* seg_params, 
         }
         if (closed) {
             line_join(curves.back(), curves.front(), linejoin, curves);
-            res->add_subpath(curves);
+            add_subpath(res, curves);
             curves.clear();
         } else {
             line_cap(curves.back().back(), backward.back().back(), linecap, curves);
@@ -335,7 +332,7 @@ static int path_stroke_impl(const int32_t* seg_types, const double* seg_params, 
         }
         if (closed) line_join(curves.back(), curves.front(), linejoin, curves);
         else line_cap(curves.back().back(), curves.front().p[0], linecap, curves);
-        res->add_subpath(curves);
+        add_subpath(res, curves);
     }
     *out = res;
     return SVGR_OK;

@@ -521,6 +521,14 @@ class Path:
             raise ValueError(f"unkown line cap type: `{linecap}`")
         if linejoin not in joins:
             raise ValueError(f"unknown line join type: `{linejoin}`")
+        types, params, sizes = self._segment_arrays()
+        if not types:
+            return Path([])
+        ot, op, osz = _abi.path_stroke(types, np.array(params), sizes, width, caps[linecap], joins[linejoin])
+        return Path.from_segments(ot, op, osz)
+
+    def _segment_arrays(self):
+        """(types, params, sizes) in the stroker's array form: quadratic and arc segments become cubics (S:1133-1140)."""
         types, params, sizes = [], [], []
         for sub in self.subpaths:
             if not sub:
@@ -544,9 +552,17 @@ class Path:
                 else:
                     raise ValueError(f"unsupported path type: `{t}`")
             sizes.append(len(types) - n0)
+        return types, params, sizes
+
+    def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
+        """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
+        "on" dash an open subpath, ready for ``stroke``.  Eager, on the device (svgr_path_dash); quadratic and arc segments are
+        turned into cubics first as ``stroke`` does.  A dash list that asks for a solid stroke -- empty, a negative entry, a zero
+        sum, no gap -- gives the path back unchanged without touching a device.  `path_length`: the author's ``pathLength``."""
+        types, params, sizes = self._segment_arrays()
         if not types:
             return Path([])
-        ot, op, osz = _abi.path_stroke(types, np.array(params), sizes, width, caps[linecap], joins[linejoin])
+        ot, op, osz = _abi.path_dash(types, np.array(params), sizes, dashes, offset, path_length or 0.0)
         return Path.from_segments(ot, op, osz)
 
     @classmethod
@@ -554,6 +570,38 @@ class Path:
         from .pathdata import parse_path_data  # noqa: PLC0415
 
         return cls(parse_path_data(d))
+
+
+class DashedPath(Path):
+    """A path that is stroked with a dash pattern: the source path plus ``stroke-dasharray`` / ``stroke-dashoffset`` /
+    ``pathLength``.  It stands where the plain path would in a STROKE node, whose five fields stay as they are.  Building
+    one needs no device; ``stroke`` dashes first (once: the result is kept), ``transform`` dashes first and transforms the
+    result, since dashes live in user space.  Everything else -- ``repr``, the fill-side accessors -- sees the source path."""
+
+    __slots__ = ["dasharray", "dashoffset", "path_length", "_dashed"]
+
+    def __init__(self, source: Path, dasharray, dashoffset: float = 0.0, path_length: float | None = None):
+        super().__init__(source.subpaths)
+        self.dasharray = tuple(float(v) for v in dasharray)
+        self.dashoffset = float(dashoffset)
+        self.path_length = None if path_length is None else float(path_length)
+        self._dashed = None
+
+    def dashed(self) -> Path:
+        if self._dashed is None:
+            self._dashed = Path(self.subpaths).dash(self.dasharray, self.dashoffset, self.path_length)
+        return self._dashed
+
+    def stroke(self, width: float, linecap: str | None = None, linejoin: str | None = None) -> Path:
+        return self.dashed().stroke(width, linecap, linejoin)
+
+    def transform(self, transform: Transform) -> Path:
+        return self.dashed().transform(transform)
+
+    def __repr__(self) -> str:
+        dashes = " ".join(f"{v:g}" for v in self.dasharray)
+        extra = "" if self.path_length is None else f" pathLength:{self.path_length:g}"
+        return f"DASH {dashes} offset:{self.dashoffset:g}{extra}\n{super().__repr__()}"
 
 
 class MaskPrefetch:

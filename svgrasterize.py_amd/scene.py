@@ -205,7 +205,14 @@ class Scene(tuple):
         return cls.fill(Path([frame]), ImagePaint(pixels, tr, smooth))
 
     @classmethod
-    def stroke(cls, path: Path, paint, width: float, linecap=None, linejoin=None) -> "Scene":
+    def stroke(cls, path: Path, paint, width: float, linecap=None, linejoin=None, dasharray=None, dashoffset: float = 0.0,
+               path_length: float | None = None) -> "Scene":
+        """`dasharray` (beyond the reference): the stroke is dashed -- the node keeps its five fields and carries the pattern
+        in its path (``geometry.DashedPath``); the dashing itself happens at the first stroke."""
+        if dasharray is not None and not _abi.dash_is_solid(dasharray):
+            from .geometry import DashedPath  # noqa: PLC0415
+
+            path = DashedPath(path, dasharray, dashoffset, path_length)
         return cls(RENDER_STROKE, (path, paint, width, linecap, linejoin))
 
     @classmethod

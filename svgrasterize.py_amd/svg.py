@@ -19,6 +19,11 @@ decoder picked by the data's first bytes; ``png.py``, ``jpeg.py``) and CSS
 ``mix-blend-mode`` (all 16 modes of Compositing and Blending Level 1, not inherited; applied outermost, after the transform, as a
 BLEND node that blends with the earlier siblings in its group node) and ``isolation: isolate`` (the element's content becomes
 one group node).  ``plus-lighter``, ``plus-darker`` and unknown modes warn and draw as ``normal``.
+Also beyond the reference: dashed strokes -- ``stroke-dasharray`` (comma / white space separated lengths, ``none``),
+``stroke-dashoffset`` (both inherited) and ``pathLength`` on path, rect, circle, ellipse, line, polyline and polygon (not
+inherited); text strokes take them like any shape.  The pattern rides in the STROKE node's path (``geometry.DashedPath``) and is
+applied on the device at the first stroke; loading needs no device.  A percentage or a negative length warns and draws solid;
+dashes of length 0 are not drawn (one warning per document).  ``stroke-miterlimit`` stays the reference's 4.
 Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
 (GIF, WebP, SVG) or remote URLs.
 """
@@ -62,6 +67,7 @@ _INHERITED = {
     "color", "fill", "fill-rule", "fill-opacity", "stroke", "stroke-opacity", "stroke-width", "stroke-linecap",
     "stroke-linejoin", "stroke-miterlimit", "font-family", "font-size", "font-weight", "text-anchor",
     "image-rendering",   # (beyond the reference: <image>)
+    "stroke-dasharray", "stroke-dashoffset",   # (beyond the reference: dashed strokes)
 }
 _NEAREST = {"pixelated", "optimizespeed", "crisp-edges"}   # image-rendering values that ask for the nearest texel
 _NUMBER = re.compile(r"[-+]?(?:(?:\d*\.\d+)|(?:\d+\.?))(?:[Ee][+-]?\d+)?")
@@ -790,6 +796,7 @@ class _Loader:
         self.fg = fg
         self.width = width
         self.base_dir = base_dir   # the document's directory (<image> files resolve against it); None: not from a file
+        self.warned_zero_dash = False
 
     def image_pixels(self, href):
         """The RGBA pixels an <image> href points at, or None (+ warning): a PNG or JPEG data URI or local file.  The name or
@@ -898,10 +905,52 @@ class _Loader:
         stroke = attrs.get("color") if stroke == "currentColor" else parse_paint(stroke, self.ids)
         if stroke is not None:
             node = Scene.stroke(path, stroke, parse_float(attrs.get("stroke-width", "1")), attrs.get("stroke-linecap"),
-                                attrs.get("stroke-linejoin"))
+                                attrs.get("stroke-linejoin"), *self.dashes(attrs))
             opacity = parse_float(attrs.get("stroke-opacity"))
             out.append(node if opacity is None else node.opacity(opacity))
         return out
+
+    def dashes(self, attrs):
+        """(dasharray, dashoffset, path_length) of a stroke from ``stroke-dasharray`` / ``stroke-dashoffset`` / ``pathLength``
+        (beyond the reference); dasharray None: a solid stroke.  Lengths are comma and / or white space separated sizes.  A
+        percentage needs the viewport, which is not known here, and a negative length is an error: both warn and draw solid."""
+        text = attrs.get("stroke-dasharray")
+        if text is None or _keyword(text) in ("none", ""):
+            return None, 0.0, None
+        values = []
+        for word in text.replace(",", " ").split():
+            if word.endswith("%"):
+                warnings.warn(f"stroke-dasharray=\"{text.strip()}\" needs the viewport, which is not known here: the stroke is solid")
+                return None, 0.0, None
+            value = parse_size(word)
+            if value is None or not math.isfinite(value):
+                warnings.warn(f"invalid stroke-dasharray: {text.strip()}: the stroke is solid")
+                return None, 0.0, None
+            if value < 0:
+                warnings.warn(f"negative stroke-dasharray length: {text.strip()}: the stroke is solid")
+                return None, 0.0, None
+            values.append(value)
+        if not values or not sum(values) > 0:
+            return None, 0.0, None
+        if len(values) * (2 if len(values) & 1 else 1) > 64:
+            warnings.warn("stroke-dasharray with more than 64 lengths (an odd list counts twice): the stroke is solid")
+            return None, 0.0, None
+        if any(v == 0 for v in (values * 2 if len(values) & 1 else values)[0::2]) and not self.warned_zero_dash:
+            self.warned_zero_dash = True   # (once per document)
+            warnings.warn("stroke-dasharray: dashes of length 0 are not drawn (no dots from round or square caps)")
+        offset = attrs.get("stroke-dashoffset")
+        if offset is not None and offset.strip().endswith("%"):
+            warnings.warn(f"stroke-dashoffset=\"{offset.strip()}\" needs the viewport, which is not known here: ignored")
+            offset = None
+        offset = parse_size(offset, 0.0)
+        try:
+            length = parse_float(attrs.get("pathLength"))
+        except ValueError:
+            warnings.warn(f"invalid pathLength: {attrs.get('pathLength')}")
+            length = None
+        if length is not None and not (length > 0 and math.isfinite(length)):
+            length = None
+        return values, 0.0 if offset is None or not math.isfinite(offset) else offset, length
 
     def text(self, element, attrs) -> list:
         """<text> with nested <tspan>: one transformed shape per run of characters (S:3716-3788).
