@@ -1052,14 +1052,31 @@ def _plain(leaves) -> bool:
     return all(leaf[4] == 0 and leaf[5] is None for leaf in leaves)  # (gradient entries are plain too)
 
 
-def _batchable_leaves(scene: Scene, transform: Transform, linear_rgb: bool, opacity: float | None = None):
+class _Walk:
+    """What the leaf analysis leaves to its caller.  Here, for `Scene.render`'s walk: the transform is a `Transform`, a leaf holds
+    its six numbers and its converted colour.  (`displaylist._Symbolic`: a chain of TRANSFORM matrices, the document's own paint.)"""
+
+    step = staticmethod(Transform.__matmul__)   # step(transform, m): a TRANSFORM node's matrix `m` under `transform`
+    place = staticmethod(Transform.m6)          # place(transform): slot [1] of a leaf
+
+    @staticmethod
+    def solid(path, transform: Transform, rule, paint, linear_rgb: bool, opacity):
+        p4 = solid_paint(paint, linear_rgb)
+        if opacity is not None:
+            p4 = p4 * opacity  # Layer.opacity: image * opacity (S:174)
+        return (path, transform.m6(), rule, p4, 0, None, None)
+
+    gradient = staticmethod(_gradient_leaf)     # gradient(path, paint, rule, transform, linear_rgb, opacity): its entry, or None
+
+
+def _batchable_leaves(scene: Scene, transform: Transform, linear_rgb: bool, opacity: float | None = None, how=_Walk):
     """Memo in front of `_batchable_leaves_`: during one top-level render the same (node, transform) is asked about once per
     enclosing group that turned out not to be batchable."""
     # (only GROUP nodes are remembered: every repeated question passes through one -- a leaf, a transform or a clip over leaves is
     #  answered again faster than its key is made; material-design's 935 clip nodes went through this wrapper 29 000 times)
     memo = STATE.leaf_memo
-    if memo is None or scene[0] != RENDER_GROUP:
-        return _batchable_leaves_(scene, transform, linear_rgb, opacity)
+    if memo is None or scene[0] != RENDER_GROUP or how is not _Walk:
+        return _batchable_leaves_(scene, transform, linear_rgb, opacity, how)
     key = (id(scene), transform.key(), linear_rgb, opacity, "sub")
     if key in memo:
         return memo[key]
@@ -1067,16 +1084,20 @@ def _batchable_leaves(scene: Scene, transform: Transform, linear_rgb: bool, opac
     return res
 
 
-def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opacity: float | None = None):
-    """[(path, m6, rule, paint4, flags, group)] when `scene` is only GROUP / TRANSFORM / solid FILL / OPACITY directly over a
+def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opacity: float | None = None, how=_Walk):
+    """[(path, m6, rule, paint4, flags, group, grad)] when `scene` is only GROUP / TRANSFORM / solid FILL / OPACITY directly over a
     leaf, a CLIP by a single path of a leaf or of a group of plain leaves, or an OPACITY over a group of plain leaves;
     None otherwise.  flags: 0 painted, 1 clip source (coverage only), 2 clipped by the clip source right in front of it;
     group: None, or the tag of the isolated group the leaf is a member of (the device composites the members into a group
     tile and clips / fades that as a whole, svgr_batch_set_groups).  Source-over is associative, so flattening nested
-    plain groups keeps the per-pixel result (to double rounding)."""
+    plain groups keeps the per-pixel result (to double rounding).
+
+    The ONE place that decides what a node becomes, for the walk and for the display lists: `how` (`_Walk`, or
+    `displaylist._Symbolic` with a chain of matrices as `transform`) accumulates a TRANSFORM, makes a leaf's placement [1] and a
+    solid leaf's paint [3], and answers for a gradient paint.  Everything else -- order, rule, flags, group tags -- is the same."""
     kind, args = scene
     while kind == RENDER_TRANSFORM:   # (a chain of transforms over a node: unwrapped here, not by a call per level)
-        transform = transform @ args[1]
+        transform = how.step(transform, args[1])
         kind, args = scene = args[0]
     if kind == RENDER_FILL:
         path, paint, rule = args
@@ -1087,42 +1108,39 @@ def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opa
         if not (isinstance(paint, np.ndarray) and paint.shape == (4,)):
             if not is_gradient(paint):
                 return None
-            leaf = _gradient_leaf(path, paint, rule, transform, linear_rgb, opacity)
+            leaf = how.gradient(path, paint, rule, transform, linear_rgb, opacity)
             return None if leaf is None else [leaf]
-        p4 = solid_paint(paint, linear_rgb)
-        if opacity is not None:
-            p4 = p4 * opacity  # Layer.opacity: image * opacity (S:174)
-        return [_leaf(path, transform.m6(), _RULES[rule], p4)]
+        return [how.solid(path, transform, _RULES[rule], paint, linear_rgb, opacity)]
     if kind == RENDER_STROKE:  # a solid stroke is a solid fill of its outline (S:666-672), nonzero rule
         path, paint, width, linecap, linejoin = args
-        return _batchable_leaves(Scene.fill(_stroked(scene), paint, None), transform, linear_rgb, opacity)
+        return _batchable_leaves_(Scene.fill(_stroked(scene), paint, None), transform, linear_rgb, opacity, how)
     if kind == RENDER_OPACITY and opacity is None:
         target = args[0]
         while target[0] == RENDER_TRANSFORM:
             target = target[1][0]
         if target[0] in (RENDER_FILL, RENDER_STROKE):  # opacity over a single leaf commutes with the fill
-            return _batchable_leaves(args[0], transform, linear_rgb, args[1])
+            return _batchable_leaves_(args[0], transform, linear_rgb, args[1], how)
         # OPACITY over a group of plain leaves (S:690-696): the group is composited on its own and faded as a whole
-        members = _batchable_leaves(args[0], transform, linear_rgb) if _BATCH_GROUPS else None
+        members = _batchable_leaves(args[0], transform, linear_rgb, None, how) if _BATCH_GROUPS else None
         if members is None or not members or not _plain(members):
             return None
         tag = _new_group(args[1], False)
-        return [_leaf(m[0], m[1], m[2], m[3], 0, tag, m[6]) for m in members]
+        return [(m[0], m[1], m[2], m[3], 0, tag, m[6]) for m in members]
     if kind == RENDER_CLIP and opacity is None and not args[2]:
         # CLIP whose target and clip are single paths: two consecutive batch entries, the clip path as a
         # coverage-only "clip source" and the fill multiplied by it (Layer.compose([mask, image], IN), S:698-715).
         # (A group under a clip is NOT the same as clipping each child: (A over B)*c != (A*c) over (B*c).)
         tgt, src = args[0], args[1]
-        if tgt[0] == RENDER_FILL and src[0] == RENDER_FILL:
-            # (a solid fill clipped by one path, both right here -- material-design's 935 icons --: the two entries made in
-            #  this frame, not in three more; what they are is what the general route below makes)
+        if how is _Walk and tgt[0] == RENDER_FILL and src[0] == RENDER_FILL:
+            # (a solid fill clipped by one path, both right here -- material-design's 935 icons --: the walk's two entries made
+            #  in this frame, not in three more; what they are is what the general route below makes)
             path, paint, rule = tgt[1]
             spath, _spaint, srule = src[1]
             if type(paint) is np.ndarray and paint.shape == (4,) and rule in _RULES and srule in _RULES:
                 m6 = transform.m6()
                 return [(spath, m6, _RULES[srule], _ZERO4, 1, None, None), (path, m6, _RULES[rule], solid_paint(paint, linear_rgb), 2, None, None)]
-        target = _batchable_leaves_(tgt, transform, linear_rgb) if tgt[0] == RENDER_FILL else _batchable_leaves(tgt, transform, linear_rgb)
-        clip_leaf = _single_mask_leaf(src, transform)
+        target = _batchable_leaves_(tgt, transform, linear_rgb, None, how) if tgt[0] == RENDER_FILL else _batchable_leaves(tgt, transform, linear_rgb, None, how)
+        clip_leaf = _single_mask_leaf(src, transform, how)
         if target is None or clip_leaf is None or not target:
             return None
         if len(target) == 1:
@@ -1136,12 +1154,12 @@ def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opa
             return None
         # a GROUP under the clip: composited on its own, then multiplied by the clip's coverage as a whole
         tag = _new_group(1.0, True)
-        return [clip_leaf] + [_leaf(t[0], t[1], t[2], t[3], 0, tag, t[6]) for t in target]
+        return [clip_leaf] + [(t[0], t[1], t[2], t[3], 0, tag, t[6]) for t in target]
     if kind == RENDER_GROUP and opacity is None:
         out = []
         for child in args:
             # (only GROUP nodes have a memo in front of the analysis)
-            sub = _batchable_leaves(child, transform, linear_rgb) if child[0] == RENDER_GROUP else _batchable_leaves_(child, transform, linear_rgb)
+            sub = _batchable_leaves(child, transform, linear_rgb, None, how) if child[0] == RENDER_GROUP else _batchable_leaves_(child, transform, linear_rgb, None, how)
             if sub is None:
                 return None
             out.extend(sub)
@@ -1149,27 +1167,33 @@ def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opa
     return None
 
 
-def _single_mask_leaf(scene: Scene, transform: Transform):
-    """(path, m6, rule, zeros, 1) when `scene` rendered mask_only is ONE Path.mask (a FILL under transforms)."""
+def _single_mask_leaf(scene: Scene, transform: Transform, how=_Walk):
+    """The clip source (path, placement, rule, zeros, 1) when `scene` rendered mask_only is ONE Path.mask (a FILL under transforms)."""
     kind, args = scene
     while kind == RENDER_TRANSFORM:
-        transform = transform @ args[1]
+        transform = how.step(transform, args[1])
         kind, args = args[0]
     if kind != RENDER_FILL:
         return None
     path, _paint, rule = args
     if rule not in _RULES:
         raise ValueError(f"Invalid fill rule: {rule}")
-    return (path, transform.m6(), _RULES[rule], _ZERO4, 1, None, None)
+    return (path, how.place(transform), _RULES[rule], _ZERO4, 1, None, None)
 
 
 def _effective_boxes(leaves, bboxes):
     """`effective_bboxes` as arrays: (painted leaf indices, their boxes [r0, c0, r1, c1], which of them draw something).  One
     pass over the leaves for their flags, the rest in numpy (a document's 2 000 leaves were 3 ms of tuples)."""
+    return _effective_boxes_arrays(*_leaf_flags(leaves), bboxes)
+
+
+def _leaf_flags(leaves):
+    """(flags, clipped) of the leaves as arrays: 0 painted / 1 clip source / 2 clipped, and "clipped by the source in front of
+    it" (a clipped fill, a member of a clipped group).  All a window needs of its leaves; a display list keeps just these."""
     n = len(leaves)
     flags = np.fromiter((leaf[4] for leaf in leaves), dtype=np.int64, count=n)
     clipped = np.fromiter((leaf[4] == 2 or (leaf[5] is not None and leaf[5][2]) for leaf in leaves), dtype=bool, count=n)
-    return _effective_boxes_arrays(flags, clipped, bboxes)
+    return flags, clipped
 
 
 def _effective_boxes_arrays(flags, clipped, bboxes):
@@ -1193,6 +1217,23 @@ def _effective_boxes_arrays(flags, clipped, bboxes):
     out_ok = ok & np.where(clipped, inter_ok, True)
     painted = np.nonzero(~is_src)[0]
     return painted, out_box[painted], out_ok[painted]
+
+
+def _window_and_hull(flags, clipped, bboxes):
+    """(window, hull membership) of planned leaves: the union (r0, c0, rows, cols) of their effective bboxes (None: nothing to
+    draw) and, per leaf, whether its lines belong to the hull."""
+    painted, box, ok = _effective_boxes_arrays(flags, clipped, bboxes)
+    win = None
+    if ok.any():
+        v = box[ok]
+        ur0, uc0 = int(v[:, 0].min()), int(v[:, 1].min())
+        win = (ur0, uc0, int(v[:, 2].max()) - ur0, int(v[:, 3].max()) - uc0)
+    # The group's hull merges the hulls of the children that drew something (S:676-684): a leaf whose clipped bbox is
+    # empty returned None there and does not count; one that is partly visible counts with ALL its lines (S:993).  Clip
+    # paths do not belong to it (S:715 returns the target's hull).
+    in_hull = np.zeros(len(flags), dtype=bool)
+    in_hull[painted] = ok
+    return win, in_hull
 
 
 def effective_bboxes(leaves, bboxes):
@@ -1235,6 +1276,29 @@ def _packed_paths(paths):
     return segs, kinds, offs
 
 
+def _rules_and_groups(leaves):
+    """(rules, path_group, group_src, group_op) of paint-ordered leaves: the rule byte of every leaf, and the tables of
+    svgr_batch_set_groups (None, None, None without an isolated group) -- the groups numbered in order of first appearance, per
+    leaf its group or -1, per group its clip source or -1 and its opacity."""
+    n = len(leaves)
+    rules = np.fromiter((leaf[2] | (leaf[4] << 1) for leaf in leaves), dtype=np.uint8, count=n)  # SVGR_PATH_CLIP_SOURCE = 2, SVGR_PATH_CLIPPED = 4
+    if not any(len(leaf) > 5 and leaf[5] is not None for leaf in leaves):
+        return rules, None, None, None
+    path_group, group_src, group_op, serial_to_gid = [], [], [], {}
+    for i, leaf in enumerate(leaves):
+        group = leaf[5] if len(leaf) > 5 else None
+        if group is None:
+            path_group.append(-1)
+            continue
+        gid = serial_to_gid.get(group[0])
+        if gid is None:
+            gid = serial_to_gid[group[0]] = len(group_src)
+            group_src.append(i - 1 if group[2] else -1)  # the clip source sits right in front of the first member
+            group_op.append(group[1])
+        path_group.append(gid)
+    return rules, path_group, group_src, group_op
+
+
 def build_batch(leaves, viewport, ctx=None, row_shift=None) -> "_abi.Batch":
     """Pack paint-ordered leaves [(path, m6, rule, paint4, flags[, group[, grad]])] into one device batch.  `row_shift`: per leaf
     the rows its geometry (and its gradient's frame) is moved down by (`_shift_leaf`, for all leaves at once)."""
@@ -1244,23 +1308,9 @@ def build_batch(leaves, viewport, ctx=None, row_shift=None) -> "_abi.Batch":
     m6s = np.concatenate([leaf[1] for leaf in leaves]).astype(np.float64, copy=False).reshape(n, 6) if n else np.zeros((0, 6))
     if row_shift is not None and n:
         m6s[:, 2] += np.asarray(row_shift, dtype=np.float64)
-    rules = np.fromiter((leaf[2] | (leaf[4] << 1) for leaf in leaves), dtype=np.uint8, count=n)  # SVGR_PATH_CLIP_SOURCE = 2, SVGR_PATH_CLIPPED = 4
+    rules, path_group, group_src, group_op = _rules_and_groups(leaves)
     paints = np.concatenate([leaf[3] for leaf in leaves]).astype(np.float64, copy=False).reshape(n, 4) if n else np.zeros((0, 4))
-    path_group, group_src, group_op, serial_to_gid = None, [], [], {}
     path_grad, grads, keep_alive, pending = None, [], [], []
-    if any(len(leaf) > 5 and leaf[5] is not None for leaf in leaves):
-        path_group = []
-        for i, leaf in enumerate(leaves):
-            group = leaf[5] if len(leaf) > 5 else None
-            if group is None:
-                path_group.append(-1)
-                continue
-            gid = serial_to_gid.get(group[0])
-            if gid is None:
-                gid = serial_to_gid[group[0]] = len(group_src)
-                group_src.append(i - 1 if group[2] else -1)  # the clip source sits right in front of the first member
-                group_op.append(group[1])
-            path_group.append(gid)
     if any(len(leaf) > 6 and leaf[6] is not None for leaf in leaves):
         path_grad = []
         for i, leaf in enumerate(leaves):
@@ -1286,7 +1336,7 @@ def build_batch(leaves, viewport, ctx=None, row_shift=None) -> "_abi.Batch":
                 keep_alive.append(grad[1])
     vp = None if viewport is None else [int(v) for v in viewport]
     batch = _abi.Batch(ctx, segs, kinds, offs, m6s, rules, paints, viewport=vp, flatness=FLATNESS)
-    if group_src:
+    if path_group is not None:
         batch.set_groups(path_group, group_src, group_op)
     if grads:
         batch.set_gradients(path_grad, grads)  # (copies the descriptions to the device before it returns)
@@ -1332,17 +1382,21 @@ def _render_run(leaves, viewport, linear_rgb):
         if pre is None or retain is None:
             batch.destroy()
         return None
+    out, ready = None, getattr(batch, "ready", None)
+    if ready is not None and ready[0] == serial:
+        out, batch.ready = ready[1], None   # (drawn by `_prefetch_windows` together with the document's other runs)
+    return _window_layer(batch, win, in_hull, linear_rgb, out)
+
+
+def _window_layer(batch, win, in_hull, linear_rgb, out=None):
+    """(Layer, lazy hull) of a planned batch's window, drawn now unless `out` holds it already."""
     ur0, uc0, urows, ucols = win
     # only the union of the leaves' bboxes is rendered (a render window of the batch's canvas): the tiles outside it are
     # not touched, and the layer needs no crop
-    shape = (urows, ucols, 4)
-    ready = getattr(batch, "ready", None)
-    if ready is not None and ready[0] == serial:
-        out, batch.ready = ready[1], None   # (drawn by `_prefetch_windows` together with the document's other runs)
-    else:
-        out = ctx.alloc(urows * ucols * 32)
+    if out is None:
+        out = _abi.Context.get().alloc(urows * ucols * 32)
         batch.render(out, _abi.OUT_CANVAS_F64, window=(ur0, uc0, urows, ucols))
-    layer = Layer._from_device(out, shape, (ur0, uc0), True, linear_rgb)
+    layer = Layer._from_device(out, (urows, ucols, 4), (ur0, uc0), True, linear_rgb)
 
     def hull_points():
         edges, edge_path = batch.all_edges()
@@ -1365,17 +1419,7 @@ def _run_window(leaves, batch):
             return None, in_hull
         in_hull[0] = True
         return (r0, c0, rows, cols), in_hull
-    painted, box, ok = _effective_boxes(leaves, batch.bboxes())
-    win = None
-    if ok.any():
-        v = box[ok]
-        ur0, uc0 = int(v[:, 0].min()), int(v[:, 1].min())
-        win = (ur0, uc0, int(v[:, 2].max()) - ur0, int(v[:, 3].max()) - uc0)
-    # The group's hull merges the hulls of the children that drew something (S:676-684): a leaf whose clipped bbox is
-    # empty returned None there and does not count; one that is partly visible counts with ALL its lines (S:993).  Clip
-    # paths do not belong to it (S:715 returns the target's hull).
-    in_hull[painted] = ok
-    return win, in_hull
+    return _window_and_hull(*_leaf_flags(leaves), batch.bboxes())
 
 
 # (round 4 drew the windows a launch each on eight streams: 1.59 -> 0.73 ms of GPU time for icons.svg's 30, off by default because the

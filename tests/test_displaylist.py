@@ -1,6 +1,7 @@
 """A scene that is batch entries only, compiled once to flat arrays (svgrasterize.py_amd/displaylist.py): the arrays a render draws
-from must be, leaf for leaf and bit for bit, what `Scene.render`'s walk (S:649-752 as `scene._batchable_leaves_` + `_drop_empty` +
-`build_batch` restate it) hands to the device -- the chain products of stacked 3x3 matmuls included."""
+from must be, leaf for leaf and bit for bit, what `Scene.render`'s walk (S:649-752: `scene._batchable_leaves_` + `_drop_empty` +
+`build_batch`, whose analysis and packing the display list shares) hands to the device -- the chain products of stacked 3x3 matmuls
+and the paints read again at every render included."""
 import os
 
 import numpy as np
@@ -21,6 +22,34 @@ def _walk_arrays(sc_mod, scene, tr, lin):
     return leaves, m6, paints, rules, groups
 
 
+def _transforms(S):
+    base = S.Transform().matrix(0, 1, 0, 1, 0, 0)
+    return base, base.scale(0.37).rotate(0.3).translate(11.5, -3.25)
+
+
+def _assert_is_the_walk(dl, sc_mod, scene, tr, lin):
+    leaves, m6, paints, rules, groups = _walk_arrays(sc_mod, scene, tr, lin)
+    assert dl.n == len(leaves) and all(a[0] is b for a, b in zip(leaves, dl.paths))
+    assert np.array_equal(dl.matrices(tr), m6), "chain products differ from the walk's Transform.__matmul__"
+    assert np.array_equal(dl.current_paints(), paints)
+    assert np.array_equal(dl.rules, rules)
+    # isolated groups: same members, same opacity / clipped, same clip source position
+    if dl.group_src is None:
+        assert all(g is None for g in groups)
+    else:
+        seen = {}
+        for i, g in enumerate(groups):
+            if g is None:
+                assert dl.path_group[i] == -1
+                continue
+            first = g[0] not in seen
+            gid = seen.setdefault(g[0], len(seen))
+            assert dl.path_group[i] == gid and dl.group_op[gid] == g[1]
+            assert (dl.group_src[gid] >= 0) == g[2]
+            if first and g[2]:
+                assert dl.group_src[gid] == i - 1 and leaves[i - 1][4] == 1   # (right in front of the first member)
+
+
 @pytest.mark.parametrize("name", ["tiger", "material"])
 @pytest.mark.parametrize("lin", [False, True])
 def test_display_list_is_the_walk(name, lin):
@@ -30,24 +59,38 @@ def test_display_list_is_the_walk(name, lin):
     scene, _info, _z = scenedump.load_scene(os.path.join(GOLDEN, f"scene_{name}.npz"))
     dl = displaylist._compile(scene, lin)
     assert dl is not None
-    for tr in (S.Transform().matrix(0, 1, 0, 1, 0, 0), S.Transform().matrix(0, 1, 0, 1, 0, 0).scale(0.37).rotate(0.3).translate(11.5, -3.25)):
-        leaves, m6, paints, rules, groups = _walk_arrays(sc_mod, scene, tr, lin)
-        assert dl.n == len(leaves) and all(a[0] is b for a, b in zip(leaves, dl.paths))
-        assert np.array_equal(dl.matrices(tr), m6), "chain products differ from the walk's Transform.__matmul__"
-        assert np.array_equal(dl.current_paints(), paints)
-        assert np.array_equal(dl.rules, rules)
-        # isolated groups: same members, same opacity / clipped, same clip source position
-        if dl.group_src is None:
-            assert all(g is None for g in groups)
+    for tr in _transforms(S):
+        _assert_is_the_walk(dl, sc_mod, scene, tr, lin)
+
+
+@pytest.mark.parametrize("groups", [True, False])
+@pytest.mark.parametrize("lin", [False, True])
+def test_display_list_is_the_walk_branch_by_branch(lin, groups, monkeypatch):
+    """One small scene per branch of the analysis (tests/displaylist_cases.py): where the walk finds batch entries made of solid
+    paints the display list holds the same ones, and it refuses what the walk refuses -- with isolated groups turned off, too."""
+    import svgrasterize_amd as S
+    from svgrasterize_amd import displaylist, scene as sc_mod
+
+    from .displaylist_cases import cases
+
+    monkeypatch.setattr(sc_mod, "_BATCH_GROUPS", groups)
+    trs = _transforms(S)
+    seen = set()
+    for name, verdict, scene in cases(host_dashes=True):
+        dl = displaylist._compile(scene, lin)
+        if verdict == "flat" or (verdict == "group" and groups):
+            assert dl is not None, name
+            for tr in trs:
+                _assert_is_the_walk(dl, sc_mod, scene, tr, lin)
+            seen.update(int(f) for f in dl.flags)
+            continue
+        assert dl is None, name
+        walk = _walk_arrays(sc_mod, scene, trs[0], lin)
+        if verdict == "gradient":
+            assert walk is not None and walk[0][0][6] is not None, name   # (the walk still has batch entries: a gradient one)
         else:
-            seen = {}
-            for i, g in enumerate(groups):
-                if g is None:
-                    assert dl.path_group[i] == -1
-                    continue
-                gid = seen.setdefault(g[0], len(seen))
-                assert dl.path_group[i] == gid and dl.group_op[gid] == g[1]
-                assert (dl.group_src[gid] >= 0) == g[2]
+            assert walk is None, name
+    assert seen == {0, 1, 2}
 
 
 def test_display_list_refuses_what_is_not_flat_and_rereads_paints():
@@ -103,3 +146,33 @@ def test_display_list_render_is_the_walks_render(name, monkeypatch):
         assert np.abs(a2[0].image - b2[0].image).max() <= 1e-12
     monkeypatch.setattr(displaylist, "ENABLED", True)
     assert scene.render(tr, viewport=[5000, 5000, 64, 64], linear_rgb=False) is None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["flat", "general"])
+def test_display_list_render_is_the_walks_render_branch_by_branch(which, monkeypatch):
+    """The scenes of tests/displaylist_cases.py side by side in one group, drawn into a viewport that starts off a tile border
+    and crosses band and column-tile borders: the display list's layer against the general route's (same bound as above, for the
+    same reason).  "general": with the gradient and the objectBoundingBox clip among them the group is not a display list, and
+    `Scene.render` draws the same with the display lists on or off."""
+    import svgrasterize_amd as S
+    from svgrasterize_amd import displaylist
+
+    from .displaylist_cases import cases
+
+    keep = ("flat", "group") if which == "flat" else ("flat", "group", "gradient", "node")
+    scene = S.Scene.group([node for _name, verdict, node in cases() if verdict in keep])
+    assert (displaylist._compile(scene, False) is not None) == (which == "flat")
+    tr = S.Transform().matrix(0, 1, 0, 1, 0, 0)
+    for lin in (False, True):
+        monkeypatch.setattr(displaylist, "ENABLED", True)
+        a_layer, a_hull = scene.render(tr, viewport=[8, 40, 80, 144], linear_rgb=lin)
+        a_none = scene.render(tr, viewport=[400, 400, 32, 32], linear_rgb=lin)
+        monkeypatch.setattr(displaylist, "ENABLED", False)
+        b_layer, b_hull = scene.render(tr, viewport=[8, 40, 80, 144], linear_rgb=lin)
+        b_none = scene.render(tr, viewport=[400, 400, 32, 32], linear_rgb=lin)
+        assert tuple(int(v) for v in a_layer.offset) == tuple(int(v) for v in b_layer.offset)
+        assert a_layer.image.shape == b_layer.image.shape and (a_layer.pre_alpha, a_layer.linear_rgb) == (b_layer.pre_alpha, b_layer.linear_rgb)
+        assert np.abs(a_layer.image - b_layer.image).max() <= 1e-12 and a_layer.image.any()
+        assert np.array_equal(np.asarray(a_hull.points), np.asarray(b_hull.points))
+        assert a_none is None and b_none is None
