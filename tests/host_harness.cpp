@@ -15,7 +15,8 @@ void hh_xform(const double* m6, const double* in, long n, double* out) {
 double hh_flatness(const double* c) { return cubic_flatness(c); }
 
 // mode 0: recursive (explicit stack), mode 1: stack-free form the GPU uses, mode 2: the GPU's
-// 32-lane decomposition (lane j owns the depth-5 node with path bits j) emulated lane by lane
+// 32-lane decomposition (lane j owns the depth-5 node with path bits j) emulated lane by lane, mode 3: the same at 64 lanes
+// (depth 6: the launch that does not fill the chip)
 long hh_flatten(const double* cubic, double tol, double* edges, long cap, int mode) {
     const double thr = (tol * tol) * 16.0;
     long n = 0;
@@ -29,7 +30,7 @@ long hh_flatten(const double* cubic, double tol, double* edges, long cap, int mo
         bool ovf = false;
         flatten_subtree(cubic, thr, kMaxFlattenDepth, emit, ovf);
     } else {
-        const int SUB = 5;
+        const int SUB = mode == 3 ? 6 : 5;
         for (int sub = 0; sub < (1 << SUB); ++sub) {
             double node[8];
             for (int i = 0; i < 8; ++i) node[i] = cubic[i];
