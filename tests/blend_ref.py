@@ -3,12 +3,10 @@ B(Cb, Cs) of the 16 modes, one premultiplied pixel of a source over a backdrop, 
 boxes.  Operations are written in the order of csrc/svgr_core.h (mix_blend_px), so that the host build (tests/blend_harness.cpp)
 and the kernel can be compared with it bit for bit.  Test infrastructure only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import host_build
 
 MODES = ["normal", "multiply", "screen", "overlay", "darken", "lighten", "color-dodge", "color-burn", "hard-light", "soft-light",
          "difference", "exclusion", "hue", "saturation", "color", "luminosity"]
@@ -148,17 +146,8 @@ def mix_blend_layers(mode: str, b_img, b_off, s_img, s_off, px=None):
 
 
 # -- the host build of svgr_core.h's blend arithmetic ----------------------------------------------------------------------
-HARNESS = os.path.join(ROOT, "tests", "_blend_harness.so")
-
-
 def harness():
-    src = os.path.join(ROOT, "tests", "blend_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("blend_harness")
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     L.bh_px.argtypes = [C.c_int, C.c_long, f64p, f64p, f64p]
     L.bh_b.argtypes = [C.c_int, C.c_long, f64p, f64p, f64p]

@@ -1,5 +1,5 @@
 // dash_harness.cpp -- the dasher's per-lane header (csrc/svgr_dash.h) compiled for the host, for tests/test_dash_host.py
-// (g++ -ffp-contract=off): sub-interval lengths, inversion, split and the piece counts of a segment range, one C entry each.
+// (built by tests/util.py: host_build): sub-interval lengths, inversion, split and the piece counts of a segment range, one C entry each.
 #include "../svgrasterize.py_amd/csrc/svgr_dash.h"
 
 extern "C" {

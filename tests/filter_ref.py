@@ -3,12 +3,10 @@ feDisplacementMap), written from the Filter Effects text in the operation order 
 build of their arithmetic (tests/filter_harness.cpp over csrc/svgr_core.h).  Test infrastructure only."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-from tests.util import ROOT
+from tests.util import host_build
 
 BSIZE, BM, PERLIN_N = 0x100, 0xFF, 0x1000
 RAND_M, RAND_A, RAND_Q, RAND_R = 2147483647, 16807, 127773, 2836
@@ -225,17 +223,8 @@ def displacement_map(src, src_offset, disp, disp_offset, lin, scale, xc, yc):
 
 
 # -- the host build of svgr_core.h's filter arithmetic ---------------------------------------------------------------------
-HARNESS = os.path.join(ROOT, "tests", "_filter_harness.so")
-
-
 def harness():
-    src = os.path.join(ROOT, "tests", "filter_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("filter_harness")
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
     L.fh_lattice.argtypes = [C.c_int64, i32p, f64p]

@@ -3,14 +3,12 @@ MCU padding, the forward DCT over the inverse's table and the quantiser: csrc/sv
 scaling of the quantisation tables, the exact float64 DCT, and the loader for the host build of the same arithmetic
 (tests/jpeg_enc_harness.cpp).  Test infrastructure only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from svgrasterize_amd import _abi
 from tests.jpeg_ref import _T   # [x][u] = 1/2 c(u) cos((2x + 1) u pi / 16)
-from tests.util import ROOT
+from tests.util import host_build
 
 SAMPLINGS = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:4:0": (1, 2), "4:2:0": (2, 2)}
 _K = np.round(_T * 2.0 ** 15).astype(np.int64)   # the table the product stores (kJpegIdct), [k][j]
@@ -91,17 +89,8 @@ def quant_tables(quality):
 
 
 # -- the host build of svgr_core.h's encode arithmetic -----------------------------------------------------------------------
-HARNESS = os.path.join(ROOT, "tests", "_jpeg_enc_harness.so")
-
-
 def harness():
-    src = os.path.join(ROOT, "tests", "jpeg_enc_harness.cpp")
-    deps = [src, os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h"), os.path.join(ROOT, "include", "svgr.h")]
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(d) for d in deps):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("jpeg_enc_harness")
     L.jeh_encode.restype = C.c_int
     L.jeh_encode.argtypes = [C.POINTER(_abi.JpegFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L

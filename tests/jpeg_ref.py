@@ -4,12 +4,11 @@ csrc/svgr_core.h's integer arithmetic (tests/jpeg_harness.cpp).  Test infrastruc
 import ctypes as C
 import glob
 import os
-import subprocess
 
 import numpy as np
 
 from svgrasterize_amd import _abi, jpeg
-from tests.util import ROOT
+from tests.util import ROOT, host_build
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "jpeg")
 FIXTURES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.jpg")))
@@ -82,17 +81,8 @@ def pixels(frame, coef, quant):
 
 
 # -- the host build of svgr_core.h's JPEG arithmetic -------------------------------------------------------------------------
-HARNESS = os.path.join(ROOT, "tests", "_jpeg_harness.so")
-
-
 def harness():
-    src = os.path.join(ROOT, "tests", "jpeg_harness.cpp")
-    deps = [src, os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h"), os.path.join(ROOT, "include", "svgr.h")]
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(d) for d in deps):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("jpeg_harness")
     L.jh_decode.restype = C.c_int
     L.jh_decode.argtypes = [C.POINTER(_abi.JpegFrame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L

@@ -3,12 +3,10 @@ csrc/svgr_core.h (light_normal, light_pixel), plus the spec's Sobel table as pri
 frame, and the loader for the host build of the arithmetic (tests/lighting_harness.cpp).  Test infrastructure only."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-from tests.util import ROOT
+from tests.util import host_build
 
 DISTANT, POINT, SPOT = 0, 1, 2
 
@@ -133,17 +131,8 @@ def lighting(A, offset, kind, params, color, ss, constant, se=None):
 
 
 # -- the host build of svgr_core.h's lighting arithmetic ---------------------------------------------------------------------
-HARNESS = os.path.join(ROOT, "tests", "_lighting_harness.so")
-
-
 def harness():
-    src = os.path.join(ROOT, "tests", "lighting_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("lighting_harness")
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     L.lh_normal.argtypes = [f64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, f64p]
     L.lh_layer.argtypes = [C.c_int, f64p, f64p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,

@@ -5,23 +5,14 @@ primitives the subregion tests use.  Written from the specification's rules, not
 functions (tests/subregion_harness.cpp)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "_subregion_harness.so")
+from tests.util import host_build
 
 
 def harness():
-    src = os.path.join(ROOT, "tests", "subregion_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    L = C.CDLL(HARNESS)
+    L = host_build("subregion_harness")
     L.sh_axis.argtypes = [C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                           np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")]
     L.sh_axis.restype = None

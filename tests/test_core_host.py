@@ -4,24 +4,17 @@ the built library.  No GPU needed; nothing here is a product code path."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from tests.util import ROOT, load, sort_edges
-
-HARNESS = os.path.join(ROOT, "tests", "_host_harness.so")
+from tests.util import ROOT, host_build, load, sort_edges
 
 
 @pytest.fixture(scope="module")
 def hh():
-    src = os.path.join(ROOT, "tests", "host_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-o", HARNESS, src])
-    L = C.CDLL(HARNESS)
+    L = host_build("host_harness")
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     L.hh_xform.argtypes = [f64p, f64p, C.c_long, f64p]
     L.hh_flatness.argtypes = [f64p]

@@ -4,7 +4,6 @@ the shared test inputs must meet, and the SVG loader's dash attributes.  No GPU 
 import ctypes as C
 import math
 import os
-import subprocess
 import warnings
 
 import numpy as np
@@ -12,9 +11,8 @@ import pytest
 
 from tests import dash_cases as cases
 from tests import dash_ref as R
-from tests.util import ROOT
+from tests.util import ROOT, host_build
 
-HARNESS = os.path.join(ROOT, "tests", "_dash_harness.so")
 RECT = R.polyline([(0, 0), (100, 0), (100, 50), (0, 50)], closed=True)
 
 
@@ -163,11 +161,7 @@ def test_cubic_outline_distance_is_as_recorded():
 # ---- the per-lane header against the reference ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def dh():
-    src = os.path.join(ROOT, "tests", "dash_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_dash.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", HARNESS, src])
-    L = C.CDLL(HARNESS)
+    L = host_build("dash_harness")
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
     L.dh_sub_lengths.argtypes = [f64p, f64p]

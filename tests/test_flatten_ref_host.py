@@ -2,17 +2,14 @@
 fixtures, the oracle and the host build of the lanes' traversal; and every case the GPU comparison of k_flatten's launch forms
 is to run is shown, from the reference's `info` alone, to cross the seams it is there for.  No GPU needed."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from tests import flatten_ref as F
-from tests.util import ROOT, load, sort_edges
+from tests.util import host_build, load, sort_edges
 
-HARNESS = os.path.join(ROOT, "tests", "_host_harness.so")
 KAT = ["rand_small", "rand_big", "tiny_curves", "degenerate", "tiger512"]
 IDENT = np.array([[1.0, 0.0, 0.0, 0.0, 1.0, 0.0]])
 CASES = F.case_ids(F.MI355X_CUS)
@@ -20,12 +17,7 @@ CASES = F.case_ids(F.MI355X_CUS)
 
 @pytest.fixture(scope="module")
 def hh():
-    # (the same build as tests/test_core_host.py's, of the same file)
-    src = os.path.join(ROOT, "tests", "host_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared", "-o", HARNESS, src])
-    L = C.CDLL(HARNESS)
+    L = host_build("host_harness")   # (the build and the library tests/test_core_host.py uses)
     L.hh_flatten.argtypes = [np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), C.c_double,
                              np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS"), C.c_long, C.c_int]
     L.hh_flatten.restype = C.c_long

@@ -94,6 +94,29 @@ def test_layer_background(kat):
         assert np.allclose(out.image, z[f"bg{idx}_out"], rtol=0, atol=1e-15)
 
 
+def test_host_build_compiles_once_and_again_when_stale(tmp_path):
+    """tests/util.py: host_build, the one builder of the host harnesses, on a harness of its own in a directory of its own: the
+    first call compiles, the second starts no compiler (the object keeps its time stamp and inode), a newer dependency
+    compiles again, nothing is left beside the object, and the process gets one library per harness."""
+    from tests import util
+
+    src, target, where = tmp_path / "two_harness.cpp", tmp_path / "_two_harness.so", str(tmp_path)
+    src.write_text('extern "C" int two();\nint two() { return 2; }\n')
+    build = util.host_build.__wrapped__   # (the rule itself; host_build remembers what it returned)
+    assert build("two_harness", where).two() == 2
+    first = target.stat()
+    assert [p.name for p in tmp_path.iterdir() if p.name.endswith(".tmp")] == []
+    assert build("two_harness", where).two() == 2
+    assert (target.stat().st_mtime_ns, target.stat().st_ino) == (first.st_mtime_ns, first.st_ino)
+    assert util.host_build("two_harness", where) is util.host_build("two_harness", where)
+    assert target.stat().st_ino == first.st_ino
+    newer = first.st_mtime_ns + 10 ** 9
+    os.utime(src, ns=(newer, newer))
+    assert build("two_harness", where).two() == 2
+    assert target.stat().st_ino != first.st_ino   # (a new file moved into place)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["_two_harness.so", "two_harness.cpp"]
+
+
 def test_default_strip_bands_one_strip_per_rank():
     """The bench's sharding default: one strip per rank, never under 128 scanlines; every band has one owner."""
     from svgrasterize_amd import dist as sdist

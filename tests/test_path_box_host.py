@@ -4,26 +4,18 @@ oracle's bbox (oracle.py: floor - 1 / ceil + 1, cut to the viewport) on random e
 integers where the oracle's 64-bit arithmetic does not reach (|x| > 1e9).  No GPU needed."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "tests", "_pathbox_harness.so")
+from tests.util import host_build
+
 TR, TC = 16, 64   # rows per band, columns per tile (svgr_hip.hip)
 
 
 @pytest.fixture(scope="module")
 def L():
-    src = os.path.join(ROOT, "tests", "pathbox_harness.cpp")
-    hdr = os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "svgr_core.h")
-    if not os.path.exists(HARNESS) or os.path.getmtime(HARNESS) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        tmp = f"{HARNESS}.{os.getpid()}"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, src])
-        os.replace(tmp, HARNESS)
-    lib = C.CDLL(HARNESS)
+    lib = host_build("pathbox_harness")
     f64 = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     i32 = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
     u8 = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")

@@ -1,11 +1,35 @@
 """Shared helpers for the parity tests."""
+import ctypes
+import functools
+import glob
 import json
 import os
+import subprocess
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+# How every host build of the per-lane headers is compiled:
+#   -ffp-contract=off  the product's own rule (csrc/Makefile): no a * b + c is fused unless the source says fma()
+#   -mfma              the explicit fma() calls become the instruction instead of a libm call (both round once: same values)
+#   -O2 -std=c++17     as the product; -fPIC -shared: the result is loaded with ctypes
+HOST_FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-shared"]
+
+
+@functools.lru_cache(maxsize=None)
+def host_build(stem, directory=os.path.join(ROOT, "tests")):
+    """The ctypes library of <directory>/<stem>.cpp, built as <directory>/_<stem>.so when that is missing or older than the
+    source, a header of csrc/ or include/svgr.h; written under another name and moved into place, loaded once per process."""
+    src, target = os.path.join(directory, stem + ".cpp"), os.path.join(directory, f"_{stem}.so")
+    deps = [src, os.path.join(ROOT, "include", "svgr.h"), *glob.glob(os.path.join(ROOT, "svgrasterize.py_amd", "csrc", "*.h"))]
+    if not os.path.exists(target) or os.path.getmtime(target) < max(os.path.getmtime(d) for d in deps):
+        tmp = f"{target}.{os.getpid()}.tmp"
+        subprocess.check_call(["g++", *HOST_FLAGS, "-o", tmp, src])
+        os.replace(tmp, target)
+    return ctypes.CDLL(target)
 
 
 def load(name):
