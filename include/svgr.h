@@ -535,6 +535,32 @@ int svgr_path_dash(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_pa
                    svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
 int svgr_dash_scan_segments(void);
 
+/* Path.vertices (beyond the reference): the vertices of a path in the layout above with a unit direction each, for
+ * marker-start / marker-mid / marker-end (SVG 2 11.6; directions: SVG 1.1 F.5).  `seg_vertex` (may be NULL: every segment):
+ * non-zero where a segment ends at a vertex of the author's path -- the cubics made from one arc carry 0 on all but the last.
+ * A trailing PATH_UNCLOSED line is not part of the outline; PATH_CLOSED is a line.  The vertices of a subpath: the start point
+ * of its first segment, then the end point of every flagged segment; positions are copies of the input.  Per vertex the
+ * result holds x, y, ux, uy and a kind: 0 the first vertex of the path, 2 the last one (of a path with more than one), 1
+ * every other.  Segment directions: a line P1 - P0; a cubic the first of P1 - P0, P2 - P0, P3 - P0 that is not (0, 0) at its
+ * start and the first of P3 - P2, P3 - P1, P3 - P0 at its end; a segment without one takes both from the end of the nearest
+ * earlier segment of its subpath that has one, else from the start of the nearest later one, else (1, 0); no wrap-around.
+ * Vertex direction: the first vertex of an open subpath its outgoing, the last its incoming direction; every other one, and
+ * both end vertices of a closed subpath (incoming: the closing segment's end, outgoing: the first segment's start),
+ * normalise(u_in + u_out), or u_in turned by +90 degrees, (-u_in.y, u_in.x), when neither component of the sum exceeds 2^-40.
+ * SVGR_E_INVALID, before anything is launched, for a coordinate that is not finite or lies beyond +-1e150 or an unknown
+ * segment type; SVGR_E_OVERFLOW, likewise, when the vertex count leaves 32 bits.  A path without vertices gives an empty
+ * result and launches nothing (ctx may then be NULL).  SVGR_E_STATE should a kernel meet a slot outside the result (a
+ * defect, never an input's doing).  The result is identical from run to run.
+ * svgr_marker_block_segments: segments per workgroup of the pass's own kernels; its scans are the dasher's
+ * (svgr_dash_scan_segments).                                                                                             */
+typedef struct svgr_marker_out svgr_marker_out;
+int svgr_path_markers(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* seg_vertex,
+                      const int32_t* subpath_sizes, int64_t n_subpaths, svgr_marker_out** out);
+int svgr_marker_out_counts(const svgr_marker_out* m, int64_t* n_vertices);
+int svgr_marker_out_copy(const svgr_marker_out* m, double* xyuv /* 4 per vertex */, int32_t* kind);
+void svgr_marker_out_free(svgr_marker_out* m);
+int svgr_marker_block_segments(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

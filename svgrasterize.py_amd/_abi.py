@@ -170,6 +170,11 @@ _PROTOS = {
     "svgr_path_stroke": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_int, C.POINTER(_P)]),
     "svgr_path_dash": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(_P)]),
     "svgr_dash_scan_segments": (C.c_int, []),
+    "svgr_path_markers": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "svgr_marker_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "svgr_marker_out_copy": (C.c_int, [_P, _P, _P]),
+    "svgr_marker_out_free": (None, [_P]),
+    "svgr_marker_block_segments": (C.c_int, []),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
@@ -604,6 +609,42 @@ def path_dash(seg_types, seg_params, subpath_sizes, dashes, offset: float = 0.0,
 def dash_scan_segments() -> int:
     """Segments per workgroup of the dasher's scans (svgr_dash_scan_segments)."""
     return int(load_library().svgr_dash_scan_segments())
+
+
+def path_markers(seg_types, seg_params, subpath_sizes, seg_vertex=None, ctx: "Context | None" = None):
+    """svgr_path_markers: (xy (n, 2), direction (n, 2), kind (n,) int32) of the path's vertices, on the device of `ctx` (default:
+    the process's context; none is made for a path without segments).  `seg_vertex`: non-zero where a segment ends at a vertex
+    of the author's path (None: every segment does)."""
+    lib = load_library()
+    seg_types = np.ascontiguousarray(seg_types, dtype=np.int32)
+    seg_params = np.ascontiguousarray(seg_params, dtype=np.float64).reshape(-1, 8)
+    subpath_sizes = np.ascontiguousarray(subpath_sizes, dtype=np.int32)
+    if int(subpath_sizes.sum()) != len(seg_types) or len(seg_params) != len(seg_types):
+        raise ValueError("segment arrays do not match the subpath sizes")
+    vertex = None
+    if seg_vertex is not None:
+        vertex = np.ascontiguousarray(seg_vertex, dtype=np.int32).reshape(-1)
+        if len(vertex) != len(seg_types):
+            raise ValueError("the vertex flags do not match the segments")
+    handle = (ctx if ctx is not None else Context.get()).handle if len(seg_types) else None
+    out = _P()
+    _check(lib.svgr_path_markers(handle, seg_types.ctypes.data_as(_P), seg_params.ctypes.data_as(_P),
+                                 None if vertex is None else vertex.ctypes.data_as(_P), subpath_sizes.ctypes.data_as(_P),
+                                 len(subpath_sizes), C.byref(out)))
+    try:
+        n = C.c_int64()
+        lib.svgr_marker_out_counts(out, C.byref(n))
+        xyuv = np.zeros((n.value, 4), dtype=np.float64)
+        kind = np.zeros(n.value, dtype=np.int32)
+        lib.svgr_marker_out_copy(out, xyuv.ctypes.data_as(_P), kind.ctypes.data_as(_P))
+    finally:
+        lib.svgr_marker_out_free(out)
+    return np.ascontiguousarray(xyuv[:, :2]), np.ascontiguousarray(xyuv[:, 2:]), kind
+
+
+def marker_block_segments() -> int:
+    """Segments per workgroup of the marker pass's own kernels (svgr_marker_block_segments)."""
+    return int(load_library().svgr_marker_block_segments())
 
 
 def image_levels(h: int, w: int):

@@ -7953,3 +7953,183 @@ int svgr_path_dash(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_pa
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// Path.vertices: the vertices of a path with their directions, for marker-start / -mid / -end (svgr_path_markers).
+// The per-lane arithmetic is svgr_marker.h; DESIGN.md "Markers" has the definitions.
+//
+//   k_marker_classify   one lane per segment: its 64-byte record in two loads, its two unit directions, its flags, its row of counts
+//   k_scan_*            the dasher's two-level sum scan (DASH_S segments per workgroup) over (segments with a direction, vertices):
+//                       a segment's place in the compacted table and every vertex's slot
+//   k_marker_table      one lane per segment: a segment with a direction enters the compacted table at its count
+//   k_marker_emit       one lane per segment: the vertices it owns (the first of its subpath, its end point); a degenerate segment
+//                       finds its neighbours' directions through the table, backwards and forwards, within its subpath
+// Every slot is a prefix sum; no atomic takes part.  All geometry is f64.
+// ======================================================================================
+#include "svgr_marker.h"
+
+constexpr int MARKER_B = 256;   // segments (= lanes) per workgroup of the classify / table / emit kernels
+// The tile kernel's cold paths live in subsection 1 of .text, behind every kernel of this file, and its branches to them reach
+// 2^15 instructions: what is added to .text behind the tile kernel lengthens them.  These kernels go into a section of their own.
+#define MARKER_KERNEL __global__ __launch_bounds__(MARKER_B) __attribute__((section(".text.svgr_marker")))
+
+struct svgr_marker_out {
+    std::vector<double> xyuv;    // 4 per vertex: x, y, ux, uy
+    std::vector<int32_t> kind;   // MARKER_START / _MID / _END
+};
+struct MarkerCntOp {
+    __device__ static MarkerCnt zero() { return MarkerCnt{0, 0}; }
+    __device__ static MarkerCnt add(const MarkerCnt& a, const MarkerCnt& b) { return MarkerCnt{a.nd + b.nd, a.v + b.v}; }
+};
+
+MARKER_KERNEL void k_marker_classify(const int* __restrict__ types, const double* __restrict__ params,
+                                                              const int* __restrict__ seg_sub, const int* __restrict__ sub_off,
+                                                              const int* __restrict__ seg_vertex, int n, int* __restrict__ flags,
+                                                              MarkerDirs* __restrict__ dirs, MarkerCnt* __restrict__ cnt) {
+    const int i = blockIdx.x * MARKER_B + threadIdx.x;
+    if (i >= n) return;
+    const double4* rec = reinterpret_cast<const double4*>(params) + (size_t)i * 2;
+    const double4 lo = rec[0], hi = rec[1];
+    const double c[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    MarkerDirs d{0.0, 0.0, 0.0, 0.0};
+    MarkerCnt row;
+    flags[i] = marker_classify(types, seg_sub, sub_off, seg_vertex, i, c, d, row);
+    marker_store2(&dirs[i].sx, d.sx, d.sy);
+    marker_store2(&dirs[i].ex, d.ex, d.ey);
+    cnt[i] = row;
+}
+
+// (cnt: the inclusive scan of k_marker_classify's rows)
+MARKER_KERNEL void k_marker_table(const int* __restrict__ flags, const MarkerCnt* __restrict__ cnt, int n,
+                                                           int* __restrict__ tab, int* __restrict__ bad) {
+    const int i = blockIdx.x * MARKER_B + threadIdx.x;
+    if (i >= n || !(flags[i] & MARKER_F_DIR)) return;
+    const long long k = cnt[i].nd - 1;
+    if (k < 0 || k >= n) { *bad = 1; return; }   // (the host zeroed it; every writer stores the same value)
+    tab[k] = i;
+}
+
+MARKER_KERNEL void k_marker_emit(MarkerView v, long long n_vert, double* __restrict__ xyuv, int* __restrict__ kind,
+                                                          int* __restrict__ bad) {
+    const int i = blockIdx.x * MARKER_B + threadIdx.x;
+    if (i >= v.n) return;
+    if (!marker_emit(v, i, n_vert, xyuv, kind)) *bad = 1;
+}
+
+static int path_markers_impl(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* seg_vertex,
+                             const int32_t* subpath_sizes, int64_t n_subpaths, svgr_marker_out** out) {
+    if (!out || n_subpaths < 0 || (n_subpaths > 0 && !subpath_sizes))
+        return fail(SVGR_E_INVALID, "svgr_path_markers: bad arguments");
+    int64_t n = 0;
+    for (int64_t s = 0; s < n_subpaths; ++s) {
+        if (subpath_sizes[s] < 0) return fail(SVGR_E_INVALID, "svgr_path_markers: negative subpath size");
+        n += subpath_sizes[s];
+        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "svgr_path_markers: more than 2^30 segments");
+    }
+    if (n > 0 && (!seg_types || !seg_params)) return fail(SVGR_E_INVALID, "svgr_path_markers: bad arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        const int t = seg_types[i];
+        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
+            return fail(SVGR_E_INVALID, "svgr_path_markers: segment %lld has type %d (quadratics and arcs are converted by the caller)", (long long)i, t);
+        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
+        for (int e = 0; e < np; ++e)
+            if (!(std::fabs(seg_params[8 * i + e]) <= DASH_COORD_MAX))
+                return fail(SVGR_E_INVALID, "svgr_path_markers: segment %lld has a coordinate that is not finite or beyond 1e150", (long long)i);
+    }
+    // the vertex count is a matter of types and flags alone: known before anything is launched
+    std::vector<int32_t> sub_off{0};
+    int64_t n_vert = 0;
+    for (int64_t s = 0, at = 0; s < n_subpaths; at += subpath_sizes[s], ++s) {
+        if (subpath_sizes[s] == 0) continue;
+        sub_off.push_back((int32_t)(at + subpath_sizes[s]));
+        const int64_t end = at + subpath_sizes[s] - (seg_types[at + subpath_sizes[s] - 1] == SVGR_PATH_UNCLOSED ? 1 : 0);
+        if (end == at) continue;
+        n_vert += 1;
+        if (!seg_vertex) n_vert += end - at;
+        else for (int64_t i = at; i < end; ++i) n_vert += seg_vertex[i] != 0;
+    }
+    if (n_vert > INT32_MAX) return fail(SVGR_E_OVERFLOW, "svgr_path_markers: %lld vertices do not fit a 32-bit count", (long long)n_vert);
+    std::unique_ptr<svgr_marker_out> res(new svgr_marker_out());
+    if (n == 0 || n_vert == 0) {
+        *out = res.release();
+        return 0;
+    }
+    if (!ctx) return fail(SVGR_E_INVALID, "svgr_path_markers: no context");
+    // ---- one upload: coordinates, types, the subpath of every segment, the subpaths' first segments, the vertex flags
+    const int n_sub = (int)sub_off.size() - 1, ni = (int)n;
+    const size_t b_params = (size_t)n * 64, b_types = (((size_t)n * 4) + 63) & ~(size_t)63, b_sub = (((size_t)(n_sub + 1) * 4) + 63) & ~(size_t)63;
+    std::vector<char> blob(b_params + 2 * b_types + b_sub + (seg_vertex ? b_types : 0));
+    memcpy(blob.data(), seg_params, b_params);
+    memcpy(blob.data() + b_params, seg_types, (size_t)n * 4);
+    int32_t* h_seg_sub = (int32_t*)(blob.data() + b_params + b_types);
+    for (int s = 0; s < n_sub; ++s)
+        for (int i = sub_off[(size_t)s]; i < sub_off[(size_t)s + 1]; ++i) h_seg_sub[i] = s;
+    memcpy(blob.data() + b_params + 2 * b_types, sub_off.data(), (size_t)(n_sub + 1) * 4);
+    if (seg_vertex) memcpy(blob.data() + b_params + 2 * b_types + b_sub, seg_vertex, (size_t)n * 4);
+
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const int nb = (ni + DASH_S - 1) / DASH_S;
+    const size_t o_kind = (size_t)n_vert * 32, o_bad = o_kind + (((size_t)n_vert * 4 + 63) & ~(size_t)63), o_end = o_bad + 4;
+    std::vector<char> back(o_end);
+    PoolBlock in, flags, dirs, cnt, tops, tab, outb;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(flags.alloc((size_t)n * 4, ctx->device));
+    HIPCHK(dirs.alloc((size_t)n * sizeof(MarkerDirs), ctx->device));
+    HIPCHK(cnt.alloc((size_t)n * sizeof(MarkerCnt), ctx->device));
+    HIPCHK(tops.alloc((size_t)nb * sizeof(MarkerCnt), ctx->device));
+    HIPCHK(tab.alloc((size_t)n * 4, ctx->device));
+    HIPCHK(outb.alloc(o_end, ctx->device));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const double* d_params = in.as<double>();
+    const int* d_types = (const int*)(in.as<char>() + b_params);
+    const int* d_seg_sub = (const int*)(in.as<char>() + b_params + b_types);
+    const int* d_sub_off = (const int*)(in.as<char>() + b_params + 2 * b_types);
+    const int* d_vertex = seg_vertex ? (const int*)(in.as<char>() + b_params + 2 * b_types + b_sub) : nullptr;
+    double* d_xyuv = outb.as<double>();
+    int* d_kind = (int*)(outb.as<char>() + o_kind);
+    int* d_bad = (int*)(outb.as<char>() + o_bad);   // (the placing kernels' error flag travels with the result)
+    HIPCHK(hipMemsetAsync(d_bad, 0, 4, st));
+    const dim3 grid = grid1((size_t)ni, MARKER_B);
+    SVGR_LAUNCH(k_marker_classify, grid, dim3(MARKER_B), 0, st, d_types, d_params, d_seg_sub, d_sub_off, d_vertex, ni, flags.as<int>(),
+                dirs.as<MarkerDirs>(), cnt.as<MarkerCnt>());
+    dash_scan<MarkerCnt, MarkerCntOp>(st, cnt.as<MarkerCnt>(), tops.as<MarkerCnt>(), ni);
+    SVGR_LAUNCH(k_marker_table, grid, dim3(MARKER_B), 0, st, (const int*)flags.p, (const MarkerCnt*)cnt.p, ni, tab.as<int>(), d_bad);
+    const MarkerView view{d_types, d_params, d_seg_sub, d_sub_off, (const int*)flags.p, (const MarkerDirs*)dirs.p, (const MarkerCnt*)cnt.p,
+                          (const int*)tab.p, ni};
+    SVGR_LAUNCH(k_marker_emit, grid, dim3(MARKER_B), 0, st, view, (long long)n_vert, d_xyuv, d_kind, d_bad);
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "svgr_path_markers: the counting and the placing kernels disagree about a place");
+    res->xyuv.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_vert * 4);
+    res->kind.assign((const int32_t*)(back.data() + o_kind), (const int32_t*)(back.data() + o_kind) + n_vert);
+    *out = res.release();
+    return 0;
+}
+
+extern "C" {
+int svgr_marker_block_segments(void) { return MARKER_B; }
+int svgr_path_markers(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* seg_vertex,
+                      const int32_t* subpath_sizes, int64_t n_subpaths, svgr_marker_out** out) {
+    return abi_guard("svgr_path_markers", [&]() {
+        return path_markers_impl(ctx, seg_types, seg_params, seg_vertex, subpath_sizes, n_subpaths, out);
+    });
+}
+int svgr_marker_out_counts(const svgr_marker_out* m, int64_t* n_vertices) {
+    if (!m) return SVGR_E_INVALID;
+    if (n_vertices) *n_vertices = (int64_t)m->kind.size();
+    return SVGR_OK;
+}
+int svgr_marker_out_copy(const svgr_marker_out* m, double* xyuv, int32_t* kind) {
+    if (!m) return SVGR_E_INVALID;
+    if (xyuv && !m->xyuv.empty()) memcpy(xyuv, m->xyuv.data(), sizeof(double) * m->xyuv.size());
+    if (kind && !m->kind.empty()) memcpy(kind, m->kind.data(), sizeof(int32_t) * m->kind.size());
+    return SVGR_OK;
+}
+void svgr_marker_out_free(svgr_marker_out* m) { delete m; }
+}  // extern "C"

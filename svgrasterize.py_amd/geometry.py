@@ -529,7 +529,12 @@ class Path:
 
     def _segment_arrays(self):
         """(types, params, sizes) in the stroker's array form: quadratic and arc segments become cubics (S:1133-1140)."""
-        types, params, sizes = [], [], []
+        return self._flagged_segment_arrays()[:3]
+
+    def _flagged_segment_arrays(self):
+        """`_segment_arrays` and, per segment, whether it ends at a vertex of the path as written: of the cubics made from one
+        arc only the last does."""
+        types, params, sizes, vertex = [], [], [], []
         for sub in self.subpaths:
             if not sub:
                 continue
@@ -551,8 +556,20 @@ class Path:
                         params.append(c.reshape(8))
                 else:
                     raise ValueError(f"unsupported path type: `{t}`")
+                pieces = len(types) - len(vertex)
+                vertex.extend([0] * (pieces - 1) + [1] * min(pieces, 1))
             sizes.append(len(types) - n0)
-        return types, params, sizes
+        return types, params, sizes, vertex
+
+    def vertices(self):
+        """``(xy (n, 2), direction (n, 2), kind (n,))`` of the path's vertices, for markers (SVG 2 11.6; beyond the reference): per
+        subpath the start point of its first segment and the end point of every segment as written (an arc is one segment), a unit
+        direction each -- the bisector of the incoming and the outgoing direction, see DESIGN.md "Markers" -- and a kind: 0 the
+        path's first vertex, 2 its last, 1 every other.  Eager, on the device (svgr_path_markers)."""
+        types, params, sizes, vertex = self._flagged_segment_arrays()
+        if not types:
+            return np.zeros((0, 2)), np.zeros((0, 2)), np.zeros(0, dtype=np.int32)
+        return _abi.path_markers(types, np.array(params), sizes, None if all(vertex) else vertex)
 
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every

@@ -28,11 +28,20 @@ from . import _abi
 from ._state import RENDER_LOCK, STATE, next_serial
 from .geometry import ConvexHull, Path, Transform, solid_paint, _RULES, FLATNESS
 from .layer import BLEND_MODES, BLEND_NAMES, BLEND_NORMAL, COMPOSE_IN, COMPOSE_OVER, Layer
+from .markers import MarkerInstances   # (markers.py imports this module only inside its functions)
 from .paint import _SPREAD, ImagePaint, is_gradient, needs_mask   # (paint.py imports nothing of this module)
 
 RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY = 0, 1, 2, 3
 RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER = 4, 5, 6, 7
 RENDER_BLEND = 8   # (beyond the reference: CSS mix-blend-mode against the earlier siblings of the enclosing GROUP)
+# (beyond the reference: SVG markers.  The node's second field is a `markers.MarkerInstances`, which becomes a GROUP of marker
+#  instances the first time something draws or walks it -- `_expanded` -- and every walker goes on with that group)
+RENDER_MARKERS = 9
+
+
+def _expanded(scene: "Scene"):
+    """`scene` itself, or for a MARKERS node the GROUP of its instances (made once, kept by the node); None: it draws nothing."""
+    return scene[1].expand() if scene[0] == RENDER_MARKERS else scene
 
 
 class _Retained:
@@ -216,6 +225,13 @@ class Scene(tuple):
         return cls(RENDER_STROKE, (path, paint, width, linecap, linejoin))
 
     @classmethod
+    def markers(cls, path: Path, start=None, mid=None, end=None, stroke_width: float = 1.0) -> "Scene":
+        """The markers of `path` (beyond the reference): `start` / `mid` / `end` are ``markers.Marker`` or None, `stroke_width`
+        scales those with `units_stroke_width`.  Lazy: the node becomes one instance per vertex -- separate nodes in vertex order,
+        each under its own transform and clip -- when it is first drawn or walked, which takes the vertices from the device."""
+        return cls(RENDER_MARKERS, MarkerInstances(path, start, mid, end, stroke_width))
+
+    @classmethod
     def group(cls, children) -> "Scene":
         children = tuple(children)
         if not children:
@@ -275,6 +291,10 @@ class Scene(tuple):
                 yield from outlines(args[0], tr @ args[1])
             elif kind in (RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_FILTER, RENDER_BLEND):
                 yield from outlines(args[0], tr)
+            elif kind == RENDER_MARKERS:
+                group = _expanded(scene)
+                if group is not None:
+                    yield from outlines(group, tr)
             else:
                 raise ValueError(f"unhandled scene type: {kind}")
 
@@ -323,6 +343,16 @@ class Scene(tuple):
             elif kind == RENDER_BLEND:
                 out.append(f"{head}BLEND {BLEND_NAMES[args[1]]}")
                 dump(args[0], depth + 1, out)
+            elif kind == RENDER_MARKERS:   # (as it was built: printing does not expand it)
+                out.append(f"{head}MARKERS stroke_width:{args.stroke_width:g}\n{textwrap.indent(repr(args.path), pad * (depth + 1))}")
+                for name, m in (("START", args.start), ("MID", args.mid), ("END", args.end)):
+                    if m is None:
+                        continue
+                    out.append(f"{head}{pad}MARKER_{name} ref:{m.ref} size:{m.size} viewbox:{m.viewbox} "
+                               f"preserve_aspect_ratio:{m.preserve_aspect_ratio} units_stroke_width:{m.units_stroke_width} "
+                               f"orient:{m.orient} clip:{m.clip}")
+                    if m.scene is not None:
+                        dump(m.scene, depth + 2, out)
             else:
                 raise ValueError(f"unhandled scene scene[0]: {kind}")
             return out
@@ -338,6 +368,9 @@ class Scene(tuple):
         run of fills the walk will meet and plans them all behind one wait (``svgr_batch_plan_many``)."""
         # (one context, one stream, no lock in the library: the renders of a process run one after the other; the lock is re-entrant)
         with RENDER_LOCK:
+            if self[0] == RENDER_MARKERS:
+                group = _expanded(self)
+                return None if group is None else group.render(transform, mask_only, viewport, linear_rgb)
             # (a render inside a render -- a pattern's tile -- walks without a pre-pass of its own: the outer call's state stays)
             if STATE.leaf_memo is not None or STATE.mask_prefetch is not None or viewport is None or self[0] in (RENDER_FILL, RENDER_STROKE):
                 return self._render(transform, mask_only, viewport, linear_rgb)
@@ -422,6 +455,10 @@ class Scene(tuple):
                 gc.enable()
 
     def _render(self, transform: Transform, mask_only: bool = False, viewport=None, linear_rgb: bool = False, _asked: bool = False):
+        if self[0] == RENDER_MARKERS:
+            self = _expanded(self)
+            if self is None:
+                return None
         kind, args = self
         # (`_asked`: the caller -- a GROUP's loop -- has asked `_leaves_memo` about this node already: it is not batch entries)
         if _NODE_RUNS and not _asked and kind != RENDER_GROUP and not mask_only and viewport is not None and STATE.leaf_memo is not None:
@@ -561,6 +598,9 @@ def _collect_mask_jobs(scene: Scene, transform: Transform, mask_only: bool, line
     ``mask_only`` (clip subtrees) and gradient-filled leaves.  Mirrors the routing of `_render`; a wrong guess only
     costs an unused mask or an on-demand one.  `runs` (a list) also receives every run of batchable leaves a GROUP will
     flush, in the order of the walk; `fills` the solid fills that go node by node: (path, transform, rule, paint)."""
+    scene = _expanded(scene)
+    if scene is None:
+        return
     kind, args = scene
     if _NODE_RUNS and kind != RENDER_GROUP and not mask_only and runs is not None:
         leaves = _leaves_memo(scene, transform, linear_rgb, store=True)   # (as Scene._render routes it)
@@ -1096,8 +1136,14 @@ def _batchable_leaves_(scene: Scene, transform: Transform, linear_rgb: bool, opa
     `displaylist._Symbolic` with a chain of matrices as `transform`) accumulates a TRANSFORM, makes a leaf's placement [1] and a
     solid leaf's paint [3], and answers for a gradient paint.  Everything else -- order, rule, flags, group tags -- is the same."""
     kind, args = scene
-    while kind == RENDER_TRANSFORM:   # (a chain of transforms over a node: unwrapped here, not by a call per level)
-        transform = how.step(transform, args[1])
+    while kind == RENDER_TRANSFORM or kind == RENDER_MARKERS:
+        if kind == RENDER_MARKERS:    # (the GROUP of its instances in its place)
+            scene = _expanded(scene)
+            if scene is None:
+                return []
+            kind, args = scene
+            continue
+        transform = how.step(transform, args[1])   # (a chain of transforms over a node: unwrapped here, not by a call per level)
         kind, args = scene = args[0]
     if kind == RENDER_FILL:
         path, paint, rule = args

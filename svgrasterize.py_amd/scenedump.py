@@ -90,7 +90,7 @@ def dump_scene(scene: Scene):
     pixels of every image paint under the name its paint entry gives (``image_<n>``).
     STROKE nodes are stored as FILL nodes of their stroke outline (``from_stroke``), exactly like the reference dumps."""
     from .filters import FE_GAUSSIAN_BLUR
-    from .scene import (RENDER_BLEND, RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MASK, RENDER_OPACITY,
+    from .scene import (RENDER_BLEND, RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MARKERS, RENDER_MASK, RENDER_OPACITY,
                         RENDER_STROKE, RENDER_TRANSFORM)
 
     lines, cubics, loff, coff = [], [], [0], [0]
@@ -133,6 +133,9 @@ def dump_scene(scene: Scene):
 
     def node(s: Scene):
         kind, a = s
+        if kind == RENDER_MARKERS:   # (beyond the reference's dumps: the GROUP of marker instances the node stands for)
+            group = a.expand()
+            return dict(t="group", c=[]) if group is None else node(group)
         if kind == RENDER_FILL:
             return dict(t="fill", path=add_path(a[0]), paint=paint(a[1]), rule=a[2])
         if kind == RENDER_STROKE:

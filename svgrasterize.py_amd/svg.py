@@ -24,7 +24,11 @@ Also beyond the reference: dashed strokes -- ``stroke-dasharray`` (comma / white
 inherited); text strokes take them like any shape.  The pattern rides in the STROKE node's path (``geometry.DashedPath``) and is
 applied on the device at the first stroke; loading needs no device.  A percentage or a negative length warns and draws solid;
 dashes of length 0 are not drawn (one warning per document).  ``stroke-miterlimit`` stays the reference's 4.
-Not supported (a warning, the element is skipped): textPath, foreignObject, switch, marker, ...; <image> of other formats
+Also beyond the reference: markers -- ``<marker>`` (markerWidth / markerHeight, refX / refY, viewBox, preserveAspectRatio,
+markerUnits, orient, overflow) and ``marker-start`` / ``marker-mid`` / ``marker-end`` / ``marker`` (inherited) on path, line,
+polyline and polygon.  They become one MARKERS node behind the shape's fill and stroke nodes, which turns into the marker
+instances on the device at the first render (``markers.py``); loading needs no device.  A marker is defined before its use.
+Not supported (a warning, the element is skipped): textPath, foreignObject, switch, ...; <image> of other formats
 (GIF, WebP, SVG) or remote URLs.
 """
 from __future__ import annotations
@@ -51,6 +55,7 @@ from .geometry import (
     PATH_CLOSED, PATH_FILL_NONZERO, PATH_LINE, STROKE_CAP_BUTT, STROKE_JOIN_MITER, Path, Transform,
 )
 from .layer import BLEND_MODES, COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
+from .markers import ORIENT_AUTO, ORIENT_AUTO_START_REVERSE, Marker
 from .paint import GradLinear, GradRadial, Pattern
 from .jpeg import read_jpeg
 from .jpeg import SIGNATURE as _JPEG_SIGNATURE
@@ -68,7 +73,9 @@ _INHERITED = {
     "stroke-linejoin", "stroke-miterlimit", "font-family", "font-size", "font-weight", "text-anchor",
     "image-rendering",   # (beyond the reference: <image>)
     "stroke-dasharray", "stroke-dashoffset",   # (beyond the reference: dashed strokes)
+    "marker-start", "marker-mid", "marker-end",   # (beyond the reference: markers; the shorthand ``marker`` is spelled out into them)
 }
+_MARKER_PROPERTIES = ("marker-start", "marker-mid", "marker-end")
 _NEAREST = {"pixelated", "optimizespeed", "crisp-edges"}   # image-rendering values that ask for the nearest texel
 _NUMBER = re.compile(r"[-+]?(?:(?:\d*\.\d+)|(?:\d+\.?))(?:[Ee][+-]?\d+)?")
 _HEX = re.compile("#?([0-9A-Fa-f]+)$")
@@ -952,6 +959,66 @@ class _Loader:
             length = None
         return values, 0.0 if offset is None or not math.isfinite(offset) else offset, length
 
+    def marker(self, element, attrs, inherit) -> Marker:
+        """<marker> -> Marker (beyond the reference); its content inherits from the place of definition, as a pattern's does."""
+        def size(key, default):
+            text = attrs.get(key)
+            if text is not None and _keyword(text) in ("left", "center", "right", "top", "bottom"):
+                warnings.warn(f"marker: {key}=\"{text.strip()}\" is not supported: 0 is used")
+                return 0.0
+            value = parse_size(text, default)
+            return default if value is None or not math.isfinite(value) else value
+
+        content = self.children(element, inherit)
+        units = attrs.get("markerUnits", "strokeWidth")
+        if units not in ("strokeWidth", UNITS_USER):
+            warnings.warn(f"invalid marker units: {units}")
+            units = "strokeWidth"
+        orient = _keyword(attrs.get("orient", "0"))
+        if orient not in (ORIENT_AUTO, ORIENT_AUTO_START_REVERSE):
+            try:
+                orient = float(orient[:-3] if orient.endswith("deg") else orient)
+                if not math.isfinite(orient):
+                    raise ValueError(orient)
+            except ValueError:
+                warnings.warn(f"invalid marker orient: {attrs.get('orient')}: 0 is used")
+                orient = 0.0
+        par = attrs.get("preserveAspectRatio", "xMidYMid meet")
+        try:
+            parse_preserve_aspect_ratio(par)
+        except ValueError:
+            warnings.warn(f"invalid preserveAspectRatio: {par!r}, using xMidYMid meet")
+            par = "xMidYMid meet"
+        try:
+            viewbox = parse_floats(attrs.get("viewBox"), 4, 4)
+        except ValueError:
+            warnings.warn(f"invalid marker viewBox: {attrs.get('viewBox')}")
+            viewbox = None
+        return Marker(Scene.group(content) if content else None, (size("refX", 0.0), size("refY", 0.0)),
+                      (size("markerWidth", 3.0), size("markerHeight", 3.0)), None if viewbox is None else tuple(viewbox), par,
+                      units == "strokeWidth", orient, _keyword(attrs.get("overflow", "hidden")) not in ("visible", "auto"))
+
+    def marked_shape(self, attrs) -> list:
+        """A path, line, polyline or polygon: `shape`, and behind its fill and stroke the markers its ``marker-start`` /
+        ``marker-mid`` / ``marker-end`` ask for -- with or without a fill or a stroke, scaled by ``stroke-width`` even then,
+        untouched by ``fill-opacity`` / ``stroke-opacity``."""
+        refs = []
+        for key in _MARKER_PROPERTIES:
+            text = attrs.get(key)
+            target = None
+            if text is not None and _keyword(text) != "none":
+                target = _resolve_url(text, self.ids)
+                if not isinstance(target, Marker):
+                    if target is not None or _URL.match(text.strip()) is None:
+                        warnings.warn(f"{key}: not a marker referenced: {text.strip()}")
+                    target = None
+            refs.append(target)
+        d = attrs.get("d")
+        if d is None or not any(refs):
+            return self.shape(attrs)
+        path = Path.from_svg(d)
+        return self.shape(attrs, path) + [Scene.markers(path, *refs, stroke_width=parse_float(attrs.get("stroke-width", "1")))]
+
     def text(self, element, attrs) -> list:
         """<text> with nested <tspan>: one transformed shape per run of characters (S:3716-3788).
 
@@ -1053,13 +1120,16 @@ class _Loader:
     def element(self, element, inherit, top=False) -> list:
         tag = element.tag.split("}")[-1]
         attrs = _expand_style(element.attrib, inherit)
+        if "marker" in attrs:   # (the shorthand, never handed down itself: this element's; its own longhands go first)
+            short, own = attrs.pop("marker"), _expand_style(element.attrib)
+            attrs.update({k: short for k in _MARKER_PROPERTIES if k not in own})
         inherit = {k: v for k, v in attrs.items() if k in _INHERITED}
         ids = self.ids
         group: list = []
         if tag == "svg":
             group = self.svg(element, attrs, inherit, top)
         elif tag == "path":
-            group = self.shape(attrs)
+            group = self.marked_shape(attrs)
         elif tag == "g":
             group = self.children(element, inherit)
         elif tag == "defs":
@@ -1100,6 +1170,10 @@ class _Loader:
                     content, attrs.get("patternContentUnits", UNITS_USER) == UNITS_BBOX,
                     parse_floats(attrs.get("viewBox"), 4, 4), parse_float(attrs.get("x", "0")), parse_float(attrs.get("y", "0")),
                     w, h, Transform() if tr is None else tr, attrs.get("patternUnits", UNITS_BBOX) == UNITS_BBOX)
+        elif tag == "marker":
+            if attrs.get("id") is not None:
+                ids[attrs["id"]] = self.marker(element, attrs, inherit)
+            return []
         elif tag == "rect":
             x, y = parse_size(attrs.pop("x", "0")), parse_size(attrs.pop("y", "0"))
             w, h = parse_size(attrs.pop("width")), parse_size(attrs.pop("height"))
@@ -1116,15 +1190,15 @@ class _Loader:
             group = self.shape(attrs)
         elif tag == "polygon":
             attrs["d"] = f"M{attrs.pop('points')}z"
-            group = self.shape(attrs)
+            group = self.marked_shape(attrs)
         elif tag == "polyline":
             attrs["d"] = f"M{attrs.pop('points')}"
-            group = self.shape(attrs)
+            group = self.marked_shape(attrs)
         elif tag == "line":
             x1, y1 = parse_size(attrs.pop("x1", "0")), parse_size(attrs.pop("y1", "0"))
             x2, y2 = parse_size(attrs.pop("x2", "0")), parse_size(attrs.pop("y2", "0"))
             attrs["d"] = f"M{x1},{y1} {x2},{y2}"
-            group = self.shape(attrs)
+            group = self.marked_shape(attrs)
         elif tag in ("title", "desc", "metadata"):
             return []
         elif tag == "font":
