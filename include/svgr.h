@@ -561,6 +561,42 @@ int svgr_marker_out_copy(const svgr_marker_out* m, double* xyuv /* 4 per vertex 
 void svgr_marker_out_free(svgr_marker_out* m);
 int svgr_marker_block_segments(void);
 
+/* Path.length / Path.point_at and text on a path (beyond the reference; <textPath>, SVG 1.1 10.13): the frame -- point and unit
+ * tangent -- of a path in the layout above at arc lengths, and glyph outlines placed in such frames.  The metric is the
+ * dasher's: a line's length is sqrt(dx^2 + dy^2), a cubic's the sum of 32 sub-intervals of 4-point Gauss-Legendre; the length
+ * runs over all subpaths in order, a move between subpaths has length 0, PATH_CLOSED is a line, a PATH_UNCLOSED line has
+ * length 0.  cum[i] is the length in front of segment i, L the total.
+ * svgr_path_sample: for each of the `n` arc lengths `s` the result holds x, y, ux, uy (4 per query) and inside = 0 <= s <= L;
+ * outside that range s is clamped for the point.  The segment of s is the last one of non-zero length with cum[i] <= s, for
+ * s = L the last one of non-zero length, at its end.  A line gives P0 + d r / len and d normalised; a cubic B(t) by de
+ * Casteljau and B'(t) normalised at the t of the dasher's inversion -- or, where B'(t) is exactly (0, 0), the segment's
+ * direction by svgr_path_markers' rule at its start (t < 0.5) or its end.  A path with L = 0 reports inside = 0 everywhere
+ * (the point is then the start of its first segment, the direction (1, 0)).  n = 0 returns only the length
+ * (`total_length_out`, may be NULL).
+ * svgr_path_place_glyphs: `n_inst` glyph instances on the path.  The atlas holds the segments of each distinct glyph once, in
+ * the same layout as a path's, relative to the glyph's origin: glyph g owns atlas segments [glyph_seg_off[g],
+ * glyph_seg_off[g + 1]).  Instance k shows glyph inst_glyph[k]; with (P, u) the frame at inst_s_mid[k], an outline point (x, y)
+ * goes to  X = Px + ux (x - h) - uy (y + dy),  Y = Py + uy (x - h) + ux (y + dy),  h = inst_half[k], dy = inst_dy[k].
+ * `params_out` receives 8 doubles per output segment, in instance order and within an instance in atlas order (unused slots
+ * of a line 0); the caller knows every slot, types and subpath sizes from its own tables.  An instance whose s_mid is not inside
+ * is hidden: visible_out[k] = 0, and its slots hold 0.
+ * Both: SVGR_E_INVALID, before anything is launched, for a coordinate that is not finite or lies beyond +-1e150, an unknown
+ * segment type, a glyph id out of range, glyph offsets that decrease, or a query / advance / shift that is not finite;
+ * SVGR_E_OVERFLOW, likewise, when a count leaves 32 bits.  A path without segments launches nothing (ctx may then be NULL):
+ * L = 0, every flag 0.  SVGR_E_STATE should a lane meet a slot outside the result (a defect, never an input's doing).  The
+ * result is identical from run to run.
+ * svgr_textpath_block: queries / output segments per workgroup of the pass's own kernels; its scan is the dasher's
+ * (svgr_dash_scan_segments).                                                                                             */
+int svgr_path_sample(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
+                     int64_t n_subpaths, const double* s, int64_t n, double* xyuv_out /* 4 per query */, int32_t* inside_out,
+                     double* total_length_out);
+int svgr_path_place_glyphs(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
+                           int64_t n_subpaths, const int32_t* atlas_types, const double* atlas_params,
+                           const int32_t* glyph_seg_off /* n_glyphs + 1 */, int64_t n_glyphs, const int32_t* inst_glyph,
+                           const double* inst_s_mid, const double* inst_half, const double* inst_dy, int64_t n_inst,
+                           double* params_out /* 8 per output segment */, int32_t* visible_out, double* total_length_out);
+int svgr_textpath_block(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

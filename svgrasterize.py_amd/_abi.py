@@ -175,6 +175,10 @@ _PROTOS = {
     "svgr_marker_out_copy": (C.c_int, [_P, _P, _P]),
     "svgr_marker_out_free": (None, [_P]),
     "svgr_marker_block_segments": (C.c_int, []),
+    "svgr_path_sample": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.POINTER(C.c_double)]),
+    "svgr_path_place_glyphs": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64, _P, _P,
+                                        C.POINTER(C.c_double)]),
+    "svgr_textpath_block": (C.c_int, []),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
@@ -645,6 +649,69 @@ def path_markers(seg_types, seg_params, subpath_sizes, seg_vertex=None, ctx: "Co
 def marker_block_segments() -> int:
     """Segments per workgroup of the marker pass's own kernels (svgr_marker_block_segments)."""
     return int(load_library().svgr_marker_block_segments())
+
+
+def _path_arrays(seg_types, seg_params, subpath_sizes):
+    seg_types = np.ascontiguousarray(seg_types, dtype=np.int32)
+    seg_params = np.ascontiguousarray(seg_params, dtype=np.float64).reshape(-1, 8)
+    subpath_sizes = np.ascontiguousarray(subpath_sizes, dtype=np.int32)
+    if int(subpath_sizes.sum()) != len(seg_types) or len(seg_params) != len(seg_types):
+        raise ValueError("segment arrays do not match the subpath sizes")
+    return seg_types, seg_params, subpath_sizes
+
+
+def path_sample(seg_types, seg_params, subpath_sizes, s=(), ctx: "Context | None" = None):
+    """svgr_path_sample: (xy (n, 2), direction (n, 2), inside (n,) bool, total length) of the path at the arc lengths `s`, on the
+    device of `ctx` (default: the process's context; none is made for a path without segments)."""
+    lib = load_library()
+    seg_types, seg_params, subpath_sizes = _path_arrays(seg_types, seg_params, subpath_sizes)
+    s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+    handle = (ctx if ctx is not None else Context.get()).handle if len(seg_types) else None
+    xyuv = np.zeros((len(s), 4), dtype=np.float64)
+    inside = np.zeros(len(s), dtype=np.int32)
+    total = C.c_double()
+    _check(lib.svgr_path_sample(handle, seg_types.ctypes.data_as(_P), seg_params.ctypes.data_as(_P), subpath_sizes.ctypes.data_as(_P),
+                                len(subpath_sizes), s.ctypes.data_as(_P), len(s), xyuv.ctypes.data_as(_P), inside.ctypes.data_as(_P),
+                                C.byref(total)))
+    return np.ascontiguousarray(xyuv[:, :2]), np.ascontiguousarray(xyuv[:, 2:]), inside != 0, total.value
+
+
+def path_place_glyphs(seg_types, seg_params, subpath_sizes, atlas_types, atlas_params, glyph_seg_off, inst_glyph, inst_s_mid, inst_half,
+                      inst_dy, ctx: "Context | None" = None):
+    """svgr_path_place_glyphs: (params (n_out, 8), visible (n_inst,) bool, total length): the atlas segments of every instance's
+    glyph, in instance order, placed on the path; the rows of a hidden instance are 0.  Instance k owns the rows
+    [off[k], off[k + 1]), off = the prefix sums of ``diff(glyph_seg_off)[inst_glyph]``."""
+    lib = load_library()
+    seg_types, seg_params, subpath_sizes = _path_arrays(seg_types, seg_params, subpath_sizes)
+    atlas_types = np.ascontiguousarray(atlas_types, dtype=np.int32)
+    atlas_params = np.ascontiguousarray(atlas_params, dtype=np.float64).reshape(-1, 8)
+    glyph_seg_off = np.ascontiguousarray(glyph_seg_off, dtype=np.int32)
+    inst_glyph = np.ascontiguousarray(inst_glyph, dtype=np.int32).reshape(-1)
+    inst = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (inst_s_mid, inst_half, inst_dy)]
+    n_inst = len(inst_glyph)
+    if len(glyph_seg_off) < 1 or len(atlas_types) != len(atlas_params) or any(len(a) != n_inst for a in inst):
+        raise ValueError("the glyph arrays do not match")
+    if len(atlas_types) != int(glyph_seg_off[-1]):
+        raise ValueError("the atlas does not match the glyph offsets")
+    n_glyphs = len(glyph_seg_off) - 1
+    counts = np.diff(glyph_seg_off.astype(np.int64))
+    ok = (inst_glyph >= 0) & (inst_glyph < n_glyphs)
+    n_out = int(counts[inst_glyph[ok]].clip(min=0).sum()) if n_glyphs else 0   # (the library refuses what is not `ok`)
+    handle = (ctx if ctx is not None else Context.get()).handle if len(seg_types) else None
+    params = np.zeros((n_out, 8), dtype=np.float64)
+    visible = np.zeros(n_inst, dtype=np.int32)
+    total = C.c_double()
+    _check(lib.svgr_path_place_glyphs(handle, seg_types.ctypes.data_as(_P), seg_params.ctypes.data_as(_P), subpath_sizes.ctypes.data_as(_P),
+                                      len(subpath_sizes), atlas_types.ctypes.data_as(_P), atlas_params.ctypes.data_as(_P),
+                                      glyph_seg_off.ctypes.data_as(_P), n_glyphs, inst_glyph.ctypes.data_as(_P), inst[0].ctypes.data_as(_P),
+                                      inst[1].ctypes.data_as(_P), inst[2].ctypes.data_as(_P), n_inst, params.ctypes.data_as(_P),
+                                      visible.ctypes.data_as(_P), C.byref(total)))
+    return params, visible != 0, total.value
+
+
+def textpath_block() -> int:
+    """Queries / output segments per workgroup of the text-on-a-path kernels (svgr_textpath_block)."""
+    return int(load_library().svgr_textpath_block())
 
 
 def image_levels(h: int, w: int):

@@ -8133,3 +8133,226 @@ int svgr_marker_out_copy(const svgr_marker_out* m, double* xyuv, int32_t* kind) 
 }
 void svgr_marker_out_free(svgr_marker_out* m) { delete m; }
 }  // extern "C"
+
+// ======================================================================================
+// Text on a path: the frame of a path at an arc length (svgr_path_sample) and glyph outlines placed in such frames
+// (svgr_path_place_glyphs).  The per-lane arithmetic is svgr_textpath.h; DESIGN.md "Text on a path" has the definitions.
+//
+//   k_dash_measure      the dasher's: per-segment lengths and the cubics' tables
+//   k_scan_*            the dasher's two-level sum scan (DASH_S segments per workgroup) over the lengths of the whole path -- no
+//                       restart at a subpath: inc[i], the length up to and with segment i
+//   k_textpath_locate   one lane per query: binary search in inc, then the frame (x, y, ux, uy) and the inside flag
+//   k_textpath_emit     one lane per output segment: its instance by binary search in the host-built prefix sums of the instances'
+//                       segment counts, the instance's frame, its 64-byte atlas record in two loads, 8 transformed doubles
+// Every slot is known to the host before the launch; no atomic takes part.  All geometry is f64.
+// ======================================================================================
+#include "svgr_textpath.h"
+
+constexpr int TEXTPATH_B = 256;   // queries / output segments (= lanes) per workgroup
+// (a section of its own, like the marker kernels': the tile kernel's branches to its cold paths keep their reach)
+#define TEXTPATH_KERNEL __global__ __launch_bounds__(TEXTPATH_B) __attribute__((section(".text.svgr_textpath")))
+
+struct TextLenOp {
+    __device__ static double zero() { return 0.0; }
+    __device__ static double add(const double& a, const double& b) { return a + b; }
+};
+
+TEXTPATH_KERNEL void k_textpath_locate(TextPathView v, const double* __restrict__ s, int nq, double* __restrict__ xyuv,
+                                       int* __restrict__ inside) {
+    const int q = blockIdx.x * TEXTPATH_B + threadIdx.x;
+    if (q >= nq) return;
+    TextFrame f;
+    inside[q] = textpath_locate(v, s[q], f);
+    marker_store2(xyuv + (size_t)q * 4, f.x, f.y);
+    marker_store2(xyuv + (size_t)q * 4 + 2, f.ux, f.uy);
+}
+
+TEXTPATH_KERNEL void k_textpath_emit(TextEmitView v, int n_out, double* __restrict__ out, int* __restrict__ bad) {
+    const int j = blockIdx.x * TEXTPATH_B + threadIdx.x;
+    if (j >= n_out) return;
+    if (!textpath_emit(v, j, out + (size_t)j * 8)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
+}
+
+// types and coordinates of n segments in the stroker's array form
+static int textpath_check_segments(const char* what, const int32_t* types, const double* params, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int t = types[i];
+        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
+            return fail(SVGR_E_INVALID, "%s: segment %lld has type %d (quadratics and arcs are converted by the caller)", what, (long long)i, t);
+        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
+        for (int e = 0; e < np; ++e)
+            if (!(std::fabs(params[8 * i + e]) <= DASH_COORD_MAX))
+                return fail(SVGR_E_INVALID, "%s: segment %lld has a coordinate that is not finite or beyond 1e150", what, (long long)i);
+    }
+    return 0;
+}
+
+struct TextPlaceIn {   // the glyph side of svgr_path_place_glyphs
+    const int32_t* atlas_types;
+    const double* atlas_params;
+    const int32_t* glyph_seg_off;
+    int64_t n_glyphs;
+    const int32_t* inst_glyph;
+    const double *inst_half, *inst_dy;
+};
+
+static inline size_t pad64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+
+// Both entries: the frames of `nq` arc lengths `s`; with `pl`, the queries are the instances' anchors and their outlines follow.
+static int textpath_impl(const char* what, svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
+                         int64_t n_subpaths, const double* s, int64_t nq, const TextPlaceIn* pl, double* xyuv_out, int32_t* flag_out,
+                         double* params_out, double* total_length_out) {
+    if (n_subpaths < 0 || nq < 0 || (n_subpaths > 0 && !subpath_sizes) || (nq > 0 && (!s || !flag_out || (!pl && !xyuv_out))))
+        return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+    int64_t n = 0;
+    for (int64_t k = 0; k < n_subpaths; ++k) {
+        if (subpath_sizes[k] < 0) return fail(SVGR_E_INVALID, "%s: negative subpath size", what);
+        n += subpath_sizes[k];
+        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: more than 2^30 segments", what);
+    }
+    if (n > 0 && (!seg_types || !seg_params)) return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+    if (nq > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: %lld queries do not fit a 32-bit count", what, (long long)nq);
+    if (int rc = textpath_check_segments(what, seg_types, seg_params, n)) return rc;
+    for (int64_t q = 0; q < nq; ++q)
+        if (!std::isfinite(s[q])) return fail(SVGR_E_INVALID, "%s: arc length %lld is not finite", what, (long long)q);
+    // ---- the glyph side: every output slot is a matter of the segment counts alone, known before anything is launched
+    std::vector<int32_t> inst_off;
+    int64_t n_out = 0, n_atlas = 0;
+    if (pl) {
+        if (pl->n_glyphs < 0 || pl->n_glyphs > INT32_MAX / 2 || !pl->glyph_seg_off || (nq > 0 && (!pl->inst_glyph || !pl->inst_half || !pl->inst_dy)))
+            return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+        if (pl->glyph_seg_off[0] != 0) return fail(SVGR_E_INVALID, "%s: the glyph offsets do not begin at 0", what);
+        for (int64_t g = 0; g < pl->n_glyphs; ++g)
+            if (pl->glyph_seg_off[g + 1] < pl->glyph_seg_off[g]) return fail(SVGR_E_INVALID, "%s: the glyph offsets decrease at glyph %lld", what, (long long)g);
+        n_atlas = pl->glyph_seg_off[pl->n_glyphs];
+        if (n_atlas > 0 && (!pl->atlas_types || !pl->atlas_params)) return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+        if (int rc = textpath_check_segments(what, pl->atlas_types, pl->atlas_params, n_atlas)) return rc;
+        inst_off.assign((size_t)nq + 1, 0);
+        for (int64_t k = 0; k < nq; ++k) {
+            const int64_t g = pl->inst_glyph[k];
+            if (g < 0 || g >= pl->n_glyphs) return fail(SVGR_E_INVALID, "%s: instance %lld names glyph %lld of %lld", what, (long long)k, (long long)g, (long long)pl->n_glyphs);
+            if (!std::isfinite(pl->inst_half[k]) || !std::isfinite(pl->inst_dy[k]))
+                return fail(SVGR_E_INVALID, "%s: instance %lld has an advance or a shift that is not finite", what, (long long)k);
+            n_out += pl->glyph_seg_off[g + 1] - pl->glyph_seg_off[g];
+            if (n_out > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: the placed outlines do not fit a 32-bit count of segments", what);
+            inst_off[(size_t)k + 1] = (int32_t)n_out;
+        }
+        if (n_out > 0 && !params_out) return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+    }
+    if (total_length_out) *total_length_out = 0.0;
+    if (nq > 0) {
+        memset(flag_out, 0, (size_t)nq * 4);
+        if (xyuv_out) memset(xyuv_out, 0, (size_t)nq * 32);
+    }
+    if (n_out > 0) memset(params_out, 0, (size_t)n_out * 64);
+    if (n == 0) return 0;   // a path without segments: L = 0, nothing is inside, nothing is launched
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: no context", what);
+    // ---- one upload: the path (coordinates, types, subpath of every segment, the subpaths' first segments), the queries, and the
+    //      glyph side (atlas, offsets, instances)
+    std::vector<int32_t> sub_off{0};
+    for (int64_t k = 0; k < n_subpaths; ++k)
+        if (subpath_sizes[k] > 0) sub_off.push_back(sub_off.back() + subpath_sizes[k]);
+    const int n_sub = (int)sub_off.size() - 1, ni = (int)n, nqi = (int)nq, n_outi = (int)n_out, n_gl = pl ? (int)pl->n_glyphs : 0;
+    const size_t b_params = (size_t)n * 64, b_types = pad64((size_t)n * 4), b_sub = pad64((size_t)(n_sub + 1) * 4), b_s = pad64((size_t)nq * 8);
+    const size_t i_types = b_params, i_seg_sub = i_types + b_types, i_sub_off = i_seg_sub + b_types, i_s = i_sub_off + b_sub;
+    const size_t i_atlas = i_s + b_s, i_atypes = i_atlas + (size_t)n_atlas * 64, i_goff = i_atypes + pad64((size_t)n_atlas * 4);
+    const size_t i_iglyph = i_goff + (pl ? pad64((size_t)(n_gl + 1) * 4) : 0), i_ioff = i_iglyph + (pl ? pad64((size_t)nq * 4) : 0);
+    const size_t i_half = i_ioff + (pl ? pad64((size_t)(nq + 1) * 4) : 0), i_dy = i_half + (pl ? b_s : 0), i_end = i_dy + (pl ? b_s : 0);
+    std::vector<char> blob(i_end);
+    memcpy(blob.data(), seg_params, b_params);
+    memcpy(blob.data() + i_types, seg_types, (size_t)n * 4);
+    int32_t* h_seg_sub = (int32_t*)(blob.data() + i_seg_sub);
+    for (int k = 0; k < n_sub; ++k)
+        for (int i = sub_off[(size_t)k]; i < sub_off[(size_t)k + 1]; ++i) h_seg_sub[i] = k;
+    memcpy(blob.data() + i_sub_off, sub_off.data(), (size_t)(n_sub + 1) * 4);
+    if (nq > 0) memcpy(blob.data() + i_s, s, (size_t)nq * 8);
+    if (pl) {
+        if (n_atlas > 0) {
+            memcpy(blob.data() + i_atlas, pl->atlas_params, (size_t)n_atlas * 64);
+            memcpy(blob.data() + i_atypes, pl->atlas_types, (size_t)n_atlas * 4);
+        }
+        memcpy(blob.data() + i_goff, pl->glyph_seg_off, (size_t)(n_gl + 1) * 4);
+        memcpy(blob.data() + i_ioff, inst_off.data(), (size_t)(nq + 1) * 4);
+        if (nq > 0) {
+            memcpy(blob.data() + i_iglyph, pl->inst_glyph, (size_t)nq * 4);
+            memcpy(blob.data() + i_half, pl->inst_half, (size_t)nq * 8);
+            memcpy(blob.data() + i_dy, pl->inst_dy, (size_t)nq * 8);
+        }
+    }
+
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const int nb = (ni + DASH_S - 1) / DASH_S;
+    // the result block: placed outlines, frames, flags, the total length, the kernels' error flag
+    const size_t o_frames = (size_t)n_out * 64, o_flag = o_frames + (size_t)nq * 32, o_len = o_flag + pad64((size_t)nq * 4), o_bad = o_len + 8;
+    const size_t o_end = o_bad + 8;
+    std::vector<char> back(o_end);
+    PoolBlock in, tab, len, cum, inc, tops, outb;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(tab.alloc((size_t)n * DASH_SUB * 8, ctx->device));
+    HIPCHK(len.alloc((size_t)n * 8, ctx->device));
+    HIPCHK(cum.alloc((size_t)n * sizeof(DashFV), ctx->device));
+    HIPCHK(inc.alloc((size_t)n * 8, ctx->device));
+    HIPCHK(tops.alloc((size_t)nb * 8, ctx->device));
+    HIPCHK(outb.alloc(o_end, ctx->device));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const char* d_in = in.as<char>();
+    const double* d_params = (const double*)d_in;
+    const int* d_types = (const int*)(d_in + i_types);
+    double* d_frames = (double*)(outb.as<char>() + o_frames);
+    int* d_flag = (int*)(outb.as<char>() + o_flag);
+    int* d_bad = (int*)(outb.as<char>() + o_bad);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
+    const dim3 seg_grid((unsigned)((ni + DASH_SEGS_WG - 1) / DASH_SEGS_WG));
+    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, (const int*)(d_in + i_seg_sub), (const int*)(d_in + i_sub_off), ni,
+                tab.as<double>(), len.as<double>(), cum.as<DashFV>());
+    HIPCHK(hipMemcpyAsync(inc.p, len.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    dash_scan<double, TextLenOp>(st, inc.as<double>(), tops.as<double>(), ni);
+    HIPCHK(hipMemcpyAsync(outb.as<char>() + o_len, inc.as<double>() + (ni - 1), 8, hipMemcpyDeviceToDevice, st));
+    if (nqi > 0) {
+        const TextPathView view{d_types, d_params, (const double*)len.p, (const double*)tab.p, (const double*)inc.p, ni};
+        SVGR_LAUNCH(k_textpath_locate, grid1((size_t)nqi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, view, (const double*)(d_in + i_s), nqi, d_frames, d_flag);
+    }
+    if (n_outi > 0) {
+        const TextEmitView ev{(const int*)(d_in + i_atypes), (const double*)(d_in + i_atlas), (const int*)(d_in + i_goff), (const int*)(d_in + i_iglyph),
+                              (const int*)(d_in + i_ioff), (const double*)(d_in + i_half), (const double*)(d_in + i_dy), (const double*)d_frames,
+                              (const int*)d_flag, nqi, (int)n_atlas};
+        SVGR_LAUNCH(k_textpath_emit, grid1((size_t)n_outi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, ev, n_outi, outb.as<double>(), d_bad);
+    }
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "%s: a lane met a slot outside the result", what);
+    if (total_length_out) memcpy(total_length_out, back.data() + o_len, 8);
+    if (n_out > 0) memcpy(params_out, back.data(), (size_t)n_out * 64);
+    if (nq > 0) {
+        if (xyuv_out) memcpy(xyuv_out, back.data() + o_frames, (size_t)nq * 32);
+        memcpy(flag_out, back.data() + o_flag, (size_t)nq * 4);
+    }
+    return 0;
+}
+
+extern "C" {
+int svgr_textpath_block(void) { return TEXTPATH_B; }
+int svgr_path_sample(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes, int64_t n_subpaths,
+                     const double* s, int64_t n, double* xyuv_out, int32_t* inside_out, double* total_length_out) {
+    return abi_guard("svgr_path_sample", [&]() {
+        return textpath_impl("svgr_path_sample", ctx, seg_types, seg_params, subpath_sizes, n_subpaths, s, n, nullptr, xyuv_out, inside_out,
+                             nullptr, total_length_out);
+    });
+}
+int svgr_path_place_glyphs(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes, int64_t n_subpaths,
+                           const int32_t* atlas_types, const double* atlas_params, const int32_t* glyph_seg_off, int64_t n_glyphs,
+                           const int32_t* inst_glyph, const double* inst_s_mid, const double* inst_half, const double* inst_dy, int64_t n_inst,
+                           double* params_out, int32_t* visible_out, double* total_length_out) {
+    return abi_guard("svgr_path_place_glyphs", [&]() {
+        const TextPlaceIn pl{atlas_types, atlas_params, glyph_seg_off, n_glyphs, inst_glyph, inst_half, inst_dy};
+        return textpath_impl("svgr_path_place_glyphs", ctx, seg_types, seg_params, subpath_sizes, n_subpaths, inst_s_mid, n_inst, &pl, nullptr,
+                             visible_out, params_out, total_length_out);
+    });
+}
+}  // extern "C"

@@ -9,6 +9,9 @@ from __future__ import annotations
 import os
 import warnings
 
+import numpy as np
+
+from . import _abi
 from .geometry import PATH_ARC, Path
 
 FONT_STYLE_NORMAL = "normal"
@@ -20,10 +23,21 @@ _GENERIC = (
 )
 
 
+def _ranges(begin, end):
+    """The concatenation of ``arange(begin[k], end[k])`` over k."""
+    begin, end = np.asarray(begin, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    count = end - begin
+    total = int(count.sum())
+    if total == 0:
+        return np.zeros(0, dtype=np.int64)
+    first = np.cumsum(count) - count   # where each range begins in the result
+    return np.arange(total, dtype=np.int64) - np.repeat(first - begin, count)
+
+
 class Glyph:
     """One glyph: its outline is kept as path data and parsed on first use."""
 
-    __slots__ = ["unicode", "advance", "name", "path_source", "_path"]
+    __slots__ = ["unicode", "advance", "name", "path_source", "_path", "_arrays"]
 
     def __init__(self, unicode, advance: float, path_source: str, name=None):
         self.unicode = unicode
@@ -31,12 +45,22 @@ class Glyph:
         self.name = name
         self.path_source = path_source
         self._path = None
+        self._arrays = None
 
     @property
     def path(self) -> Path:
         if self._path is None:
             self._path = Path.from_svg(self.path_source)
         return self._path
+
+    @property
+    def arrays(self):
+        """The outline in the stroker's array form, in glyph units: ``(types int32, params (n, 8), sizes int32)``, converted once."""
+        if self._arrays is None:
+            types, params, sizes = self.path._segment_arrays()
+            self._arrays = (np.array(types, dtype=np.int32), np.array(params, dtype=np.float64).reshape(-1, 8),
+                            np.array(sizes, dtype=np.int32))
+        return self._arrays
 
     def __repr__(self) -> str:
         return f"Glyph(unicode={self.unicode}, name={self.name})"
@@ -98,6 +122,43 @@ class Font:
                     sub.append((kind, [[(x + pen) * scale, -y * scale] for x, y in pts]))
                 subpaths.append(sub)
         return Path(subpaths), advance * scale
+
+    def str_on_path(self, path: Path, size: float, string: str, offset: float = 0.0, dy: float = 0.0):
+        """Outline of ``string`` set along `path` (beyond the reference; ``<textPath>``, SVG 1.1 10.13): ``(Path, advance)``.
+        Pen positions, ligatures and kerning are `str_to_glyphs`'; a glyph is anchored where the middle of its advance,
+        ``offset + (pen + advance / 2) * scale``, falls on the path, turned into the path's direction there and moved by `dy` across
+        it; scaling and y flip are `str_to_path`'s.  A glyph whose anchor lies off the path is left out.  Eager, on the device
+        (svgr_path_place_glyphs)."""
+        scale = size / self.units_per_em
+        placed, advance = self.str_to_glyphs(string)
+        types, params, sizes = path._segment_arrays()
+        if not placed or not types:
+            return Path([]), advance * scale
+        index, atlas = {}, []
+        for _pen, glyph in placed:
+            if id(glyph) not in index:
+                index[id(glyph)] = len(atlas)
+                atlas.append(glyph)
+        inst_glyph = np.array([index[id(g)] for _pen, g in placed], dtype=np.int32)
+        pens = np.array([pen for pen, _g in placed], dtype=np.float64)
+        advances = np.array([g.advance for g in atlas], dtype=np.float64)[inst_glyph]
+        a_types = np.concatenate([g.arrays[0] for g in atlas])
+        a_params = np.concatenate([g.arrays[1] for g in atlas])
+        a_sizes = np.concatenate([g.arrays[2] for g in atlas])
+        seg_off = np.concatenate([[0], np.cumsum([len(g.arrays[0]) for g in atlas])]).astype(np.int32)
+        sub_off = np.concatenate([[0], np.cumsum([len(g.arrays[2]) for g in atlas])]).astype(np.int64)
+        scaled = np.empty_like(a_params)
+        scaled[:, 0::2] = a_params[:, 0::2] * scale
+        scaled[:, 1::2] = -a_params[:, 1::2] * scale
+        out, visible, _length = _abi.path_place_glyphs(types, np.array(params), sizes, a_types, scaled, seg_off, inst_glyph,
+                                                       offset + (pens + advances / 2) * scale, advances * scale / 2,
+                                                       np.full(len(placed), float(dy)))
+        # types and subpath sizes of the result: gathers of the atlas' tables over the visible instances
+        shown = inst_glyph[visible]
+        seg_rows = _ranges(seg_off[shown], seg_off[shown + 1])
+        seg_count = np.diff(seg_off.astype(np.int64))[inst_glyph]
+        keep = np.repeat(visible, seg_count)
+        return Path.from_segments(a_types[seg_rows], out[keep], a_sizes[_ranges(sub_off[shown], sub_off[shown + 1])]), advance * scale
 
     def names(self) -> dict:
         return {g.name: g.unicode for g in self.glyphs.values()}

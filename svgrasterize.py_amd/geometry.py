@@ -571,6 +571,25 @@ class Path:
             return np.zeros((0, 2)), np.zeros((0, 2)), np.zeros(0, dtype=np.int32)
         return _abi.path_markers(types, np.array(params), sizes, None if all(vertex) else vertex)
 
+    def length(self) -> float:
+        """The path's length (beyond the reference; ``getTotalLength``): over all subpaths in order, a move counting 0, in the
+        dasher's metric -- DESIGN.md "Text on a path".  Eager, on the device (svgr_path_sample)."""
+        types, params, sizes = self._segment_arrays()
+        if not types:
+            return 0.0
+        return _abi.path_sample(types, np.array(params), sizes)[3]
+
+    def point_at(self, s):
+        """``(xy (n, 2), direction (n, 2), inside (n,) bool)`` of the path at the arc lengths `s`, a number or an array (beyond
+        the reference; ``getPointAtLength`` and the tangent there).  `inside`: ``0 <= s <= length()``; outside, the point is that
+        of the nearer end.  A path without length reports ``inside = False`` everywhere.  Eager, on the device
+        (svgr_path_sample)."""
+        s = np.atleast_1d(np.asarray(s, dtype=FLOAT)).reshape(-1)
+        types, params, sizes = self._segment_arrays()
+        if not types:
+            return np.zeros((len(s), 2)), np.tile([1.0, 0.0], (len(s), 1)), np.zeros(len(s), dtype=bool)
+        return _abi.path_sample(types, np.array(params), sizes, s)[:3]
+
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
         "on" dash an open subpath, ready for ``stroke``.  Eager, on the device (svgr_path_dash); quadratic and arc segments are

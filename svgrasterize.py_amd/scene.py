@@ -30,12 +30,14 @@ from .geometry import ConvexHull, Path, Transform, solid_paint, _RULES, FLATNESS
 from .layer import BLEND_MODES, BLEND_NAMES, BLEND_NORMAL, COMPOSE_IN, COMPOSE_OVER, Layer
 from .markers import MarkerInstances   # (markers.py imports this module only inside its functions)
 from .paint import _SPREAD, ImagePaint, is_gradient, needs_mask   # (paint.py imports nothing of this module)
+from .textpath import TextOnPath       # (textpath.py imports this module only inside its functions)
 
 RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY = 0, 1, 2, 3
 RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER = 4, 5, 6, 7
 RENDER_BLEND = 8   # (beyond the reference: CSS mix-blend-mode against the earlier siblings of the enclosing GROUP)
 # (beyond the reference: SVG markers.  The node's second field is a `markers.MarkerInstances`, which becomes a GROUP of marker
-#  instances the first time something draws or walks it -- `_expanded` -- and every walker goes on with that group)
+#  instances the first time something draws or walks it -- `_expanded` -- and every walker goes on with that group.  Text on a
+#  path is the same kind of node with a `textpath.TextOnPath` in that field: all a walker asks of it is `expand()`)
 RENDER_MARKERS = 9
 
 
@@ -232,6 +234,14 @@ class Scene(tuple):
         return cls(RENDER_MARKERS, MarkerInstances(path, start, mid, end, stroke_width))
 
     @classmethod
+    def text_on_path(cls, path: Path, runs, start_offset: float = 0.0, percent: bool = False, path_length: "float | None" = None,
+                     anchor: "str | None" = None, shape=None) -> "Scene":
+        """Text set along `path` (beyond the reference; ``<textPath>``): `runs` are ``textpath.TextRun``s or tuples ``(text, font,
+        size, attrs, dx, dy)``, the other arguments ``textpath.TextOnPath``'s.  Lazy, as `markers` is: the node becomes the runs'
+        FILL / STROKE nodes when it is first drawn or walked, which places the glyphs on the device."""
+        return cls(RENDER_MARKERS, TextOnPath(path, runs, start_offset, percent, path_length, anchor, shape))
+
+    @classmethod
     def group(cls, children) -> "Scene":
         children = tuple(children)
         if not children:
@@ -343,6 +353,12 @@ class Scene(tuple):
             elif kind == RENDER_BLEND:
                 out.append(f"{head}BLEND {BLEND_NAMES[args[1]]}")
                 dump(args[0], depth + 1, out)
+            elif kind == RENDER_MARKERS and isinstance(args, TextOnPath):   # (as it was built: printing does not expand it)
+                extra = "" if args.path_length is None else f" pathLength:{args.path_length:g}"
+                out.append(f"{head}TEXT_ON_PATH start_offset:{args.start_offset:g}{'%' if args.percent else ''} anchor:{args.anchor}{extra}\n"
+                           f"{textwrap.indent(repr(args.path), pad * (depth + 1))}")
+                for run in args.runs:
+                    out.append(f"{head}{pad}RUN {run.text!r} font:{run.font.family} size:{run.size:g} dx:{run.dx:g} dy:{run.dy:g}")
             elif kind == RENDER_MARKERS:   # (as it was built: printing does not expand it)
                 out.append(f"{head}MARKERS stroke_width:{args.stroke_width:g}\n{textwrap.indent(repr(args.path), pad * (depth + 1))}")
                 for name, m in (("START", args.start), ("MID", args.mid), ("END", args.end)):

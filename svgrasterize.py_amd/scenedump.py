@@ -133,7 +133,7 @@ def dump_scene(scene: Scene):
 
     def node(s: Scene):
         kind, a = s
-        if kind == RENDER_MARKERS:   # (beyond the reference's dumps: the GROUP of marker instances the node stands for)
+        if kind == RENDER_MARKERS:   # (beyond the reference's dumps: the GROUP the node stands for -- marker instances, or the shapes of a text on a path)
             group = a.expand()
             return dict(t="group", c=[]) if group is None else node(group)
         if kind == RENDER_FILL:

@@ -28,7 +28,14 @@ Also beyond the reference: markers -- ``<marker>`` (markerWidth / markerHeight, 
 markerUnits, orient, overflow) and ``marker-start`` / ``marker-mid`` / ``marker-end`` / ``marker`` (inherited) on path, line,
 polyline and polygon.  They become one MARKERS node behind the shape's fill and stroke nodes, which turns into the marker
 instances on the device at the first render (``markers.py``); loading needs no device.  A marker is defined before its use.
-Not supported (a warning, the element is skipped): textPath, foreignObject, switch, ...; <image> of other formats
+Also beyond the reference: text on a path -- ``<textPath>`` inside ``<text>`` with ``href`` / ``xlink:href`` to a path, rect,
+circle, ellipse, line, polyline or polygon defined before it (its own ``transform`` applied), ``startOffset`` (a length, scaled
+by the path's ``pathLength``, or a percentage of the path's length), ``text-anchor``, nested ``<tspan>``s with ``dx`` (along the
+path) and ``dy`` (across it); ``x`` / ``y`` inside it are ignored.  It becomes one lazy node (``textpath.py``) that turns into the
+runs' fill and stroke nodes, the glyphs placed on the device, at the first render; loading needs no device.  A glyph whose
+midpoint is off the path is not drawn, there is no wrap on closed paths, text after the ``<textPath>`` goes on from the pen
+where it began; ``method="stretch"``, ``spacing`` and ``side="right"`` warn and the defaults are used.
+Not supported (a warning, the element is skipped): foreignObject, switch, ...; <image> of other formats
 (GIF, WebP, SVG) or remote URLs.
 """
 from __future__ import annotations
@@ -56,6 +63,7 @@ from .geometry import (
 )
 from .layer import BLEND_MODES, COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
 from .markers import ORIENT_AUTO, ORIENT_AUTO_START_REVERSE, Marker
+from .textpath import ANCHORS, TextRun
 from .paint import GradLinear, GradRadial, Pattern
 from .jpeg import read_jpeg
 from .jpeg import SIGNATURE as _JPEG_SIGNATURE
@@ -76,6 +84,7 @@ _INHERITED = {
     "marker-start", "marker-mid", "marker-end",   # (beyond the reference: markers; the shorthand ``marker`` is spelled out into them)
 }
 _MARKER_PROPERTIES = ("marker-start", "marker-mid", "marker-end")
+_PATH_SHAPES = {"path", "rect", "circle", "ellipse", "line", "polyline", "polygon"}   # what a <textPath> may reference
 _NEAREST = {"pixelated", "optimizespeed", "crisp-edges"}   # image-rendering values that ask for the nearest texel
 _NUMBER = re.compile(r"[-+]?(?:(?:\d*\.\d+)|(?:\d+\.?))(?:[Ee][+-]?\d+)?")
 _HEX = re.compile("#?([0-9A-Fa-f]+)$")
@@ -331,6 +340,21 @@ def _expand_style(attrib, inherit=None) -> dict:
 def _keyword(text) -> str:
     """A CSS keyword compared ASCII case-insensitively (no Unicode case folding)."""
     return text.strip().encode("utf-8").lower().decode("utf-8")
+
+
+def _collapse(text, after_blank):
+    """The characters of a text node as they are set (S:3737-3745) and whether they end in a blank: white space collapses to
+    single blanks; one leading blank is kept unless the previous run ended in one, and one trailing blank.  ``(None,
+    after_blank)`` when nothing is set."""
+    if not text:
+        return None, after_blank
+    text = text.replace("\n", " ")
+    lead = " " if text[0] in " \t" and len(text) > 1 and not after_blank else ""
+    trail = " " if text[-1] in " \t" else ""
+    words = " ".join(text.split())
+    if not words:
+        return None, after_blank
+    return lead + words + trail, bool(trail)
 
 
 def _isolated(group: list) -> list:
@@ -799,6 +823,7 @@ class _Loader:
     def __init__(self, fg, width, fonts=None, base_dir=None):
         self.fonts = FontsDB() if fonts is None else fonts
         self.ids: dict = {}
+        self.shape_paths: dict = {}   # id -> (path data, transform, pathLength) of the basic shapes and paths, for <textPath>
         self.size = None
         self.fg = fg
         self.width = width
@@ -1041,42 +1066,112 @@ class _Loader:
                     ox += value
                 else:
                     oy += value
-            if not text:
+            words, blank = _collapse(text, after_blank)
+            if words is None:
                 return [], (ox, oy), after_blank
-            text = text.replace("\n", " ")
-            lead = " " if text[0] in " \t" and len(text) > 1 and not after_blank else ""
-            trail = " " if text[-1] in " \t" else ""
-            words = " ".join(text.split())
-            if not words:
-                return [], (ox, oy), after_blank
-            words = lead + words + trail
             size = parse_float(attrs.get("font-size", f"{FONT_SIZE}"))
             font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")))
             if font is None:
                 return [], (ox, oy), after_blank
             path, advance = font.str_to_path(size, words)
             place = Transform().translate(ox, oy)
-            return [node.transform(place) for node in self.shape(attrs, path)], (ox + advance, oy), bool(trail)
+            return [node.transform(place) for node in self.shape(attrs, path)], (ox + advance, oy), blank
 
         def walk(element, attrs, pen, after_blank):
             out, pen, after_blank = run(element.text, attrs, pen, after_blank)
             # whether children are descended into is decided by the tag of ``element`` itself (S:3766-3767)
             descend = element.tag.split("}")[-1] in ("text", "tspan")
             for child in element:
-                if descend:
+                if descend and child.tag.split("}")[-1] == "textPath":   # (beyond the reference; the pen stays where it is)
+                    nodes = self.text_path(child, _expand_style(child.attrib, attrs))
+                    on_path.extend(nodes)
+                    out.extend(nodes)
+                elif descend:
                     nodes, pen, after_blank = walk(child, _expand_style(child.attrib, attrs), pen, after_blank)
                     out.extend(nodes)
                 nodes, pen, after_blank = run(child.tail, attrs, pen, after_blank)
                 out.extend(nodes)
             return out, pen, after_blank
 
+        on_path: list = []   # the nodes of <textPath> children: ``text-anchor`` moves those along their paths instead
         start_x = parse_float(attrs.get("x", "0"))
         nodes, (end_x, _), _ = walk(element, attrs, (0, 0), True)
         anchor = attrs.get("text-anchor")
         if anchor in ("middle", "end"):
             shift = Transform().translate((start_x - end_x) / (2 if anchor == "middle" else 1), 0)
-            nodes = [node.transform(shift) for node in nodes]
+            nodes = [node if any(node is n for n in on_path) else node.transform(shift) for node in nodes]
         return nodes
+
+    def text_path(self, element, attrs) -> list:
+        """<textPath> inside <text> (beyond the reference): one lazy node that sets the runs of the element and of its nested
+        <tspan>s along the referenced shape -- white space, font, size and paint per run as `text` has them; the distance along
+        the path goes on from run to run, ``dx`` moves along the path, ``dy`` across it, ``x`` / ``y`` are ignored."""
+        href = attrs.get("href")
+        if href is None:
+            href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
+        target = self.shape_paths.get(href[1:]) if href and href.startswith("#") else None
+        if target is None:
+            warnings.warn(f"textPath: not a shape referenced: {href}")
+            return []
+        for key, default in (("method", "align"), ("spacing", "exact"), ("side", "left")):
+            value = attrs.get(key)
+            if value is not None and _keyword(value) != default:
+                warnings.warn(f"textPath: {key}=\"{value.strip()}\" is not supported: {default} is used")
+        d, transform, length = target
+        path = Path.from_svg(d)
+        tr = parse_transform(transform)
+        if tr is not None:
+            path = path.transform(tr)
+        try:
+            length = parse_float(length)
+        except ValueError:
+            warnings.warn(f"invalid pathLength: {length}")
+            length = None
+        if length is not None and not (length > 0 and math.isfinite(length)):
+            length = None
+        offset, percent = attrs.get("startOffset", "0").strip(), False
+        if offset.endswith("%"):
+            offset, percent = offset[:-1], True
+        try:
+            offset = (parse_float(offset) if percent else parse_size(offset, 0.0)) or 0.0
+        except ValueError:
+            offset = math.nan
+        if not math.isfinite(offset):
+            warnings.warn(f"invalid startOffset: {attrs.get('startOffset')}: 0 is used")
+            offset, percent = 0.0, False
+        anchor = attrs.get("text-anchor")
+        if anchor is not None and _keyword(anchor) not in ANCHORS:
+            warnings.warn(f"invalid text-anchor: {anchor}")
+            anchor = None
+        runs = []
+
+        def run(text, attrs, after_blank, moves):
+            for key in ("x", "y", "dx", "dy"):  # consumed here, so that they do not reach the runs that follow
+                value = parse_size(attrs.pop(key, None))
+                if value is not None and key in moves:
+                    moves[key] += value
+            words, blank = _collapse(text, after_blank)
+            if words is None:
+                return after_blank
+            font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")))
+            if font is None:
+                return after_blank
+            runs.append(TextRun(words, font, parse_float(attrs.get("font-size", f"{FONT_SIZE}")), dict(attrs), moves["dx"], moves["dy"]))
+            moves["dx"] = moves["dy"] = 0.0
+            return blank
+
+        def walk(element, attrs, after_blank, moves):
+            after_blank = run(element.text, attrs, after_blank, moves)
+            for child in element:
+                if child.tag.split("}")[-1] == "tspan":
+                    after_blank = walk(child, _expand_style(child.attrib, attrs), after_blank, moves)
+                after_blank = run(child.tail, attrs, after_blank, moves)
+            return after_blank
+
+        walk(element, attrs, True, {"dx": 0.0, "dy": 0.0})   # (moves: the dx / dy met since the last run that was set)
+        if not runs:
+            return []
+        return [Scene.text_on_path(path, runs, offset, percent, length, None if anchor is None else _keyword(anchor), self.shape)]
 
     def children(self, element, inherit) -> list:
         out = []
@@ -1226,6 +1321,9 @@ class _Loader:
         else:
             warnings.warn(f"unsupported element type: {tag}")
 
+        if tag in _PATH_SHAPES and attrs.get("id") is not None and attrs.get("d") is not None:
+            # (what a <textPath> may reference: the shape's path data, parsed when one does)
+            self.shape_paths[attrs["id"]] = (attrs["d"], attrs.get("transform"), attrs.get("pathLength"))
         if not group:
             return group
         isolation = attrs.get("isolation")
