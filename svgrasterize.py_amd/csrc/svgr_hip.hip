@@ -4936,6 +4936,9 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         };
         // (an unplanned pass over add lists sized with room to spare: ONE pass on the workgroup's own bounds, MODE 2)
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
+        if (getenv("SVGR_DBG_PLAN"))   // (diagnostic: which instantiation this pass launches, and whether it found the slab table in place)
+            fprintf(stderr, "[geometry] k_path_build<%d>%s, %lld slabs, slab table %s\n", placed ? 1 : bounded ? 2 : 0,
+                    b->count_adds_only ? " measuring" : "", (long long)b->n_slabs, keep_slabs ? "kept" : "written");
         if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
 #ifdef SVGR_DBG_PB_STAMP
         if (pb_dbg && b->planned && !b->count_adds_only) {

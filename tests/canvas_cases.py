@@ -24,7 +24,7 @@ ORIGINS = ((0, 0), (-7, 83))
 VIEW = (61, 250)           # directed cases: 4 bands x 4 column tiles, the last of each cut
 DEEP_VIEW = (35, 180)      # deep tiles: 3 bands x 3 column tiles
 DEEP_TILE = (1, 1)
-DEEP_COUNTS = (1, 2, 3, 4, 63, 64, 65, 130)
+DEEP_COUNTS = (1, 2, 3, 4, 23, 24, 25, 26, 63, 64, 65, 130)   # (23 .. 26: on either side of the 24 items a tile's page holds)
 ROUND = 64                 # items per round of the tile kernel's list
 
 _A = (0.55, 0.8, 0.4, 0.65, 0.9, 0.35, 0.7, 0.5)

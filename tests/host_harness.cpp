@@ -75,6 +75,19 @@ void hh_trace_edge(double* trace, long rows, long cols, const double* e, int use
     }
 }
 
+// what k_path_build's stage() asks of an edge (tests/pathbuild_cases.py): `n` edges (r0, c0, r1, c1) in absolute coordinates against
+// the layer {r0, c0, rows, cols} -- out[3 i ..] = {y_begin, y_end (layer rows), kept: valid and not wholly right of the layer}
+void hh_edge_rows(const double* edges, long n, int r0, int c0, int rows, int cols, int* out) {
+    for (long i = 0; i < n; ++i) {
+        const double* e = edges + 4 * i;
+        const double ar = e[0] - (double)r0, ac = e[1] - (double)c0, br = e[2] - (double)r0, bc = e[3] - (double)c0;
+        const EdgeSetup es = edge_setup(ar, ac, br, bc, rows);
+        const double cmin = ac < bc ? ac : bc;
+        out[3 * i] = es.y_begin; out[3 * i + 1] = es.y_end;
+        out[3 * i + 2] = es.valid && !(cmin >= (double)cols + 2.0) ? 1 : 0;
+    }
+}
+
 double hh_fill(double s, int rule) { return fill_rule(s, rule); }
 double hh_fill_raw(double s, int rule) { return rule ? fill_evenodd_raw(s) : fill_nonzero_raw(s); }
 
