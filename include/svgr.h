@@ -597,6 +597,39 @@ int svgr_path_place_glyphs(svgr_ctx* ctx, const int32_t* seg_types, const double
                            double* params_out /* 8 per output segment */, int32_t* visible_out, double* total_length_out);
 int svgr_textpath_block(void);
 
+/* TrueType outlines (beyond the reference; the `glyf` table of a .ttf): the contours of simple glyphs -- points in font units
+ * with an on-curve flag each -- as a path in the layout above.  Table parsing, hinting-free, is the caller's (truetype.py);
+ * composite glyphs arrive flattened into parts.
+ * The atlas holds every distinct simple glyph once: `pt_xy` (2 int16 per point), `pt_on` (non-zero: on the curve),
+ * `contour_off` (n_contours + 1, in points: contour c owns the points [contour_off[c], contour_off[c + 1])) and
+ * `glyph_contour_off` (n_glyphs + 1, in contours).  Part k shows glyph part_glyph[k]: a point (x, y) goes to
+ * x' = (m00 x + m10 y) + dx, y' = (m01 x + m11 y) + dy with part_m[6 k ..] = m00, m01, m10, m11, dx, dy, then to
+ * X = (x' + pen) sx, Y = y' sy -- each product and sum rounded on its own, in this order.
+ * A contour p[0 .. n-1], prev and next cyclic within it: n < 2 gives nothing, no subpath either.  Else an off-curve p[i] gives
+ * the quadratic from (prev if prev is on the curve, else the midpoint of prev and p[i]) over p[i] to (next if next is on the
+ * curve, else the midpoint of p[i] and next); an on-curve p[i] with an on-curve next gives the line p[i] -> next; an on-curve
+ * p[i] with an off-curve next gives nothing.  The segments stand in point order and form a closed chain; behind them comes one
+ * PATH_CLOSED line of length 0 at the chain's start -- p[0] if it is on the curve, else p[n-1] if that is, else their midpoint
+ * -- which is what the path reader leaves for an outline written `... z`.  Midpoints are (a + b) * 0.5 in font units.  A
+ * quadratic P0 Q P1 is stored as the PATH_CUBIC P0, (1/3) P0 + (2/3) Q, (2/3) Q + (1/3) P1, P1, made from the transformed
+ * points, two products and one sum each; a PATH_LINE has its slots 4..7 zero.
+ * The result holds types, params and one subpath size per contour with n >= 2, in part order, then contour order.  One
+ * launch, one lane per pair of a part and a point of its glyph; the slot of every segment is a matter of the flags alone and
+ * is worked out on the host during the validation walk.
+ * SVGR_E_INVALID, before anything is launched, for offsets that decrease, do not begin at 0 or do not end at the sizes given,
+ * a part's glyph id out of range, or a matrix entry, pen or scale that is not finite or lies beyond +-1e150; SVGR_E_OVERFLOW,
+ * likewise, when a count leaves 32 bits.  Without lanes -- no parts, parts of empty glyphs only -- or without segments the
+ * result is empty and nothing is launched (ctx may then be NULL).  SVGR_E_STATE should a lane meet a slot outside the result
+ * (a defect, never an input's doing).  The result is identical from run to run.
+ * svgr_glyf_block: lanes per workgroup of the pass's kernel.                                                               */
+int svgr_glyf_outline(svgr_ctx* ctx, const int16_t* pt_xy /* 2 per point */, const uint8_t* pt_on, int64_t n_points,
+                      const int32_t* contour_off /* n_contours + 1 */, int64_t n_contours,
+                      const int32_t* glyph_contour_off /* n_glyphs + 1 */, int64_t n_glyphs, const int32_t* part_glyph,
+                      const double* part_m /* 6 per part */, const double* part_pen, const double* part_sx,
+                      const double* part_sy, int64_t n_parts,
+                      svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
+int svgr_glyf_block(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

@@ -8359,3 +8359,107 @@ int svgr_path_place_glyphs(svgr_ctx* ctx, const int32_t* seg_types, const double
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// TrueType outlines: the contours of simple glyphs (`glyf`) as the lines and cubics of a path (svgr_glyf_outline).  The
+// per-lane arithmetic and the host's validation walk are svgr_glyf.h; DESIGN.md "TrueType fonts" has the definitions.
+//
+//   k_glyf_emit   one lane per (part, atlas point) pair: its part by binary search in the host-built prefix sums of the parts'
+//                 point counts, its contour by binary search in the contour offsets, three int16 points and their flags, at most
+//                 one segment (type + 8 doubles) and, for a contour's last point, the closing line
+// Every slot is a glyph constant the host made while it checked the input; stores are disjoint and no atomic takes part (the
+// `bad` flag is a plain store of the same value by every writer).  All geometry is f64.
+// ======================================================================================
+#include "svgr_glyf.h"
+
+constexpr int GLYF_B = 256;   // (part, point) pairs (= lanes) per workgroup
+// (a section of its own, like the marker kernels': the tile kernel's branches to its cold paths keep their reach)
+#define GLYF_KERNEL __global__ __launch_bounds__(GLYF_B) __attribute__((section(".text.svgr_glyf")))
+
+GLYF_KERNEL void k_glyf_emit(GlyfView v, int n_lanes, int* __restrict__ types, double* __restrict__ params, int* __restrict__ bad) {
+    const int j = blockIdx.x * GLYF_B + threadIdx.x;
+    if (j >= n_lanes) return;
+    if (!glyf_emit(v, j, types, params)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
+}
+
+static int glyf_outline_impl(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
+                             int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph,
+                             const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts,
+                             svgr_stroke_out** out) {
+    if (!out || (n_points > 0 && !pt_xy)) return fail(SVGR_E_INVALID, "svgr_glyf_outline: bad arguments");
+    GlyfTables t;
+    if (int rc = glyf_tables(pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m, part_pen, part_sx,
+                             part_sy, n_parts, t))
+        return fail(rc, "svgr_glyf_outline: %s", t.why);
+    std::unique_ptr<svgr_stroke_out> res(new svgr_stroke_out());
+    const int n_lanes = t.part_lane_off[(size_t)n_parts], n_out = t.part_seg_off[(size_t)n_parts];
+    if (n_lanes == 0 || n_out == 0) {   // no part, parts of empty glyphs, or contours of a single point only
+        *out = res.release();
+        return 0;
+    }
+    if (!ctx) return fail(SVGR_E_INVALID, "svgr_glyf_outline: no context");
+    // ---- one upload: the atlas with its slot table, the parts with their prefix sums
+    const int np = (int)n_parts, npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs;
+    const size_t i_on = pad64((size_t)npt * 4), i_slot = i_on + pad64((size_t)npt), i_coff = i_slot + pad64((size_t)npt * 4);
+    const size_t i_goff = i_coff + pad64((size_t)(nc + 1) * 4), i_pglyph = i_goff + pad64((size_t)(ng + 1) * 4);
+    const size_t i_plane = i_pglyph + pad64((size_t)np * 4), i_pseg = i_plane + pad64((size_t)(np + 1) * 4);
+    const size_t i_m = i_pseg + pad64((size_t)(np + 1) * 4), i_pen = i_m + pad64((size_t)np * 48), i_sx = i_pen + pad64((size_t)np * 8);
+    const size_t i_sy = i_sx + pad64((size_t)np * 8), i_end = i_sy + pad64((size_t)np * 8);
+    std::vector<char> blob(i_end);
+    memcpy(blob.data(), pt_xy, (size_t)npt * 4);
+    memcpy(blob.data() + i_on, pt_on, (size_t)npt);
+    memcpy(blob.data() + i_slot, t.pt_slot.data(), (size_t)npt * 4);
+    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
+    memcpy(blob.data() + i_goff, glyph_contour_off, (size_t)(ng + 1) * 4);
+    memcpy(blob.data() + i_pglyph, part_glyph, (size_t)np * 4);
+    memcpy(blob.data() + i_plane, t.part_lane_off.data(), (size_t)(np + 1) * 4);
+    memcpy(blob.data() + i_pseg, t.part_seg_off.data(), (size_t)(np + 1) * 4);
+    memcpy(blob.data() + i_m, part_m, (size_t)np * 48);
+    memcpy(blob.data() + i_pen, part_pen, (size_t)np * 8);
+    memcpy(blob.data() + i_sx, part_sx, (size_t)np * 8);
+    memcpy(blob.data() + i_sy, part_sy, (size_t)np * 8);
+
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    // the result block: params, types, the kernel's error flag
+    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 8;
+    std::vector<char> back(o_end);
+    PoolBlock in, outb;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(outb.alloc(o_end, ctx->device));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const char* d_in = in.as<char>();
+    int* d_bad = (int*)(outb.as<char>() + o_bad);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
+    const GlyfView view{(const int16_t*)d_in, (const uint8_t*)(d_in + i_on), (const int*)(d_in + i_slot), (const int*)(d_in + i_coff),
+                        (const int*)(d_in + i_goff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_plane), (const int*)(d_in + i_pseg),
+                        (const double*)(d_in + i_m), (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy),
+                        nc, np, npt, n_out};
+    SVGR_LAUNCH(k_glyf_emit, grid1((size_t)n_lanes, GLYF_B), dim3(GLYF_B), 0, st, view, n_lanes, (int*)(outb.as<char>() + o_types),
+                outb.as<double>(), d_bad);
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "svgr_glyf_outline: a lane met a slot outside the result");
+    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
+    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    res->sizes = std::move(t.sizes);
+    *out = res.release();
+    return 0;
+}
+
+extern "C" {
+int svgr_glyf_block(void) { return GLYF_B; }
+int svgr_glyf_outline(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
+                      int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph, const double* part_m,
+                      const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts, svgr_stroke_out** out) {
+    return abi_guard("svgr_glyf_outline", [&]() {
+        return glyf_outline_impl(ctx, pt_xy, pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m,
+                                 part_pen, part_sx, part_sy, n_parts, out);
+    });
+}
+}  // extern "C"

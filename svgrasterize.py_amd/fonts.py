@@ -1,8 +1,11 @@
-"""SVG fonts: ``<font>`` glyph tables -> text outlines (reference ``Glyph`` / ``Font`` / ``FontsDB``, S:2563-2718).
+"""Fonts: glyph tables -> text outlines (reference ``Glyph`` / ``Font`` / ``FontsDB``, S:2563-2718).
 
 Host code in front of the hot path: a string becomes one ``Path`` of glyph outlines, which is then filled / stroked like
-any other path.  Only SVG fonts are understood (``<font>`` elements inside a document, or whole documents of them
-registered with ``FontsDB.register_file`` and loaded on first use) -- the same restriction the reference has.
+any other path.  ``Font`` is an SVG font (``<font>`` elements inside a document, or whole documents of them registered with
+``FontsDB.register_file`` and loaded on first use) -- the only kind the reference has.  Beyond it, ``truetype.TrueTypeFont``
+is a ``Font`` read from a ``.ttf`` (``FontsDB.register_file`` of such a file, ``FontsDB.register_ttf``); other font formats
+(CFF / OpenType ``OTTO``, collections, WOFF) are refused.  Nothing looks for fonts on its own: no system directory is
+scanned and nothing is fetched, the caller says which files.
 """
 from __future__ import annotations
 
@@ -182,8 +185,42 @@ class FontsDB:
             self.fonts.setdefault(alias.lower(), []).append(font)
 
     def register_file(self, path: str) -> None:
-        """Remember an SVG document of ``<font>`` elements; it is loaded by the first ``resolve``."""
-        self.fonts_files.append(path)
+        """A font file, told by its first four bytes: a TrueType font is read now (``truetype.read_ttf``) and registered under
+        the family of its ``name`` table (without one: the file's name); ``OTTO`` / ``ttcf`` / ``wOFF`` / ``wOF2`` and a TrueType
+        file that is malformed or lacks a required table warn with the reason and are skipped (nothing is raised); anything else is an SVG document of ``<font>`` elements, remembered and loaded by the first
+        ``resolve``."""
+        from . import truetype  # noqa: PLC0415  (truetype.py imports this module)
+
+        try:
+            with open(path, "rb") as f:
+                head = f.read(4)
+        except OSError:
+            head = b""   # (the first `resolve` warns about a file that is not there)
+        if head in truetype.REFUSED:
+            warnings.warn(f"font file skipped: {path}: {truetype.REFUSED[head]}")
+        elif truetype.is_truetype(head):
+            try:
+                self.register(truetype.read_ttf_file(path))
+            except ValueError as why:   # (a malformed file, or one without a required table)
+                warnings.warn(f"font file skipped: {path}: {why}")
+        else:
+            self.fonts_files.append(path)
+
+    def register_ttf(self, data_or_path, family=None):
+        """Register a TrueType font from bytes in memory or from a file's path, under `family` when given (an alias: the font's
+        own family stays registered too), and return it."""
+        from . import truetype  # noqa: PLC0415
+
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            font = truetype.TrueTypeFont(bytes(data_or_path))
+            if font.family is None:   # (a font that names no family takes the caller's)
+                if family is None:
+                    raise ValueError("truetype: the font names no family (name id 1): pass family=")
+                font.family = family
+        else:
+            font = truetype.read_ttf_file(os.fspath(data_or_path))
+        self.register(font, alias=family)
+        return font
 
     def _load_pending(self) -> None:
         from .svg import svg_scene_from_filepath  # the loader registers every <font> it meets

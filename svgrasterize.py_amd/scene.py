@@ -30,7 +30,7 @@ from .geometry import ConvexHull, Path, Transform, solid_paint, _RULES, FLATNESS
 from .layer import BLEND_MODES, BLEND_NAMES, BLEND_NORMAL, COMPOSE_IN, COMPOSE_OVER, Layer
 from .markers import MarkerInstances   # (markers.py imports this module only inside its functions)
 from .paint import _SPREAD, ImagePaint, is_gradient, needs_mask   # (paint.py imports nothing of this module)
-from .textpath import TextOnPath       # (textpath.py imports this module only inside its functions)
+from .textpath import TextOnPath, TextOutline       # (textpath.py imports this module only inside its functions)
 
 RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY = 0, 1, 2, 3
 RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER = 4, 5, 6, 7
@@ -242,6 +242,13 @@ class Scene(tuple):
         return cls(RENDER_MARKERS, TextOnPath(path, runs, start_offset, percent, path_length, anchor, shape))
 
     @classmethod
+    def text(cls, font, size: float, string: str, attrs=None, shape=None) -> "Scene":
+        """A straight run of `string` in `font` at `size` user units per em, its pen at the origin (beyond the reference; a
+        ``truetype.TrueTypeFont``): `attrs` and `shape` are ``textpath.TextOutline``'s.  Lazy, as `markers` is: the node becomes
+        the run's FILL / STROKE nodes when it is first drawn or walked, which makes the outline on the device."""
+        return cls(RENDER_MARKERS, TextOutline(font, size, string, attrs, shape))
+
+    @classmethod
     def group(cls, children) -> "Scene":
         children = tuple(children)
         if not children:
@@ -359,6 +366,8 @@ class Scene(tuple):
                            f"{textwrap.indent(repr(args.path), pad * (depth + 1))}")
                 for run in args.runs:
                     out.append(f"{head}{pad}RUN {run.text!r} font:{run.font.family} size:{run.size:g} dx:{run.dx:g} dy:{run.dy:g}")
+            elif kind == RENDER_MARKERS and isinstance(args, TextOutline):   # (as it was built: printing does not expand it)
+                out.append(f"{head}TEXT {args.text!r} font:{args.font.family} size:{args.size:g}")
             elif kind == RENDER_MARKERS:   # (as it was built: printing does not expand it)
                 out.append(f"{head}MARKERS stroke_width:{args.stroke_width:g}\n{textwrap.indent(repr(args.path), pad * (depth + 1))}")
                 for name, m in (("START", args.start), ("MID", args.mid), ("END", args.end)):
@@ -1555,10 +1564,12 @@ def _drop_empty(leaves):
 
 
 def render_canvas(scene_or_leaves, transform: Transform | None, viewport, linear_rgb: bool = False,
-                  out_f64: bool = False, clip01: bool = True):
+                  out_f64: bool = False, clip01: bool = True, deterministic: bool = False):
     """Production entry: whole scene -> (rows, cols, 4) premultiplied canvas over `viewport`,
     float32 by default.  Equivalent to the reference CLI's render + ``canvas_merge_at`` on a zero
-    canvas (S:3857-3875) for scenes made of solid fills; returns (canvas ndarray, stats)."""
+    canvas (S:3857-3875) for scenes made of solid fills; returns (canvas ndarray, stats).  `deterministic`
+    (SVGR_RENDER_DETERMINISTIC): one wave does every accumulation in list order, so two renders of the same geometry give the
+    same bits, at about 1.3 times the cost; by default the order of the adds is free and the last bit may differ."""
     if isinstance(scene_or_leaves, Scene):
         leaves = _batchable_leaves(scene_or_leaves, transform, linear_rgb)
         if leaves is None:
@@ -1571,7 +1582,8 @@ def render_canvas(scene_or_leaves, transform: Transform | None, viewport, linear
     _resolve_frames(batch)
     rows, cols = int(viewport[2]), int(viewport[3])
     out = ctx.alloc(rows * cols * (32 if out_f64 else 16))
-    batch.render(out, _abi.OUT_CANVAS_F64 if out_f64 else _abi.OUT_CANVAS_F32, _abi.RENDER_CLIP01 if clip01 else 0)
+    flags = (_abi.RENDER_CLIP01 if clip01 else 0) | (_abi.RENDER_DETERMINISTIC if deterministic else 0)
+    batch.render(out, _abi.OUT_CANVAS_F64 if out_f64 else _abi.OUT_CANVAS_F32, flags)
     img = out.download((rows, cols, 4), np.float64 if out_f64 else np.float32)
     batch.destroy()
     return img, st

@@ -3,7 +3,8 @@ holds the referenced path, the runs of text and the offsets, and turns into ordi
 run -- when it is first drawn or walked.  The glyphs are placed on the device (``Font.str_on_path``,
 svgr_path_place_glyphs) and a percentage ``startOffset`` needs the path's length (``Path.length``), so the node stays as it
 is until then: building one -- loading a document -- needs no device.  It rides in the node kind of the markers
-(``scene.RENDER_MARKERS``), whose payload only has to offer ``expand()``."""
+(``scene.RENDER_MARKERS``), whose payload only has to offer ``expand()``.  ``TextOutline`` is the same for a straight run set in a
+face whose outlines are made on the device (a TrueType font): the run's shapes, made at the first render."""
 from __future__ import annotations
 
 import threading
@@ -34,6 +35,41 @@ def _fill_shape(attrs, path) -> list:
 
     paint = attrs.get("fill")
     return [Scene.fill(path, np.array([0.0, 0.0, 0.0, 1.0]) if paint is None else paint)]
+
+
+class TextOutline:
+    """Payload of a straight run of text whose outline is made on the device (``Scene.text``; a ``truetype.TrueTypeFont``'s
+    ``str_to_path``): `font`, `size` in user units per em, `text`, the attributes `attrs` its shape is made from and `shape`:
+    ``(attrs, Path) -> [Scene]`` (the loader's; without one a fill with ``attrs["fill"]``).  `expand()` makes the nodes once and
+    keeps them in `scene` (None before, and for an empty outline)."""
+
+    __slots__ = ("font", "size", "text", "attrs", "shape", "scene", "_expanded", "_lock")
+
+    def __init__(self, font, size: float, text: str, attrs=None, shape=None):
+        self.font, self.size, self.text = font, float(size), text
+        self.attrs = {} if attrs is None else dict(attrs)
+        self.shape = _fill_shape if shape is None else shape
+        self.scene = None
+        self._expanded = False
+        self._lock = threading.Lock()
+
+    def expand(self):
+        """The GROUP of the run's shapes (a single node: that node); None for an empty outline."""
+        if not self._expanded:
+            with self._lock:
+                if not self._expanded:
+                    self.scene = self._shapes()
+                    self._expanded = True
+        return self.scene
+
+    def _shapes(self):
+        from .scene import Scene  # noqa: PLC0415
+
+        outline, _advance = self.font.str_to_path(self.size, self.text)
+        if not outline.subpaths:
+            return None
+        out = self.shape(dict(self.attrs), outline)
+        return Scene.group(out) if out else None
 
 
 class TextOnPath:
