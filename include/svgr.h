@@ -630,6 +630,44 @@ int svgr_glyf_outline(svgr_ctx* ctx, const int16_t* pt_xy /* 2 per point */, con
                       svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
 int svgr_glyf_block(void);
 
+/* Variable fonts (beyond the reference; the `gvar` table of a .ttf): the outlines above at one instance of the font.  Table
+ * parsing, axis normalisation and the tuples' scalars are the caller's (truetype_var.py); tuples whose scalar is 0, phantom
+ * points and the deltas of composite glyphs' components never arrive here.
+ * The atlas is svgr_glyf_outline's.  Glyph g owns the tuples [glyph_tuple_off[g], glyph_tuple_off[g + 1]) in the file's order;
+ * tuple t has the scalar tuple_scalar[t] and the entries [tuple_pt_off[t], tuple_pt_off[t + 1]): tp_index[k], a point's index
+ * within its glyph, strictly increasing within the tuple, and its delta tp_dxy[2 k], tp_dxy[2 k + 1].
+ * The delta of point i of a contour that owns the glyph-local indices [f, l], in one tuple: the tuple's entries with an index
+ * in [f, l] are the contour's touched points.  None gives (0, 0); i among them gives its stored delta; else, with p the touched
+ * point before i (wrapping to the contour's last touched one) and q the one after (wrapping to the first), per axis and in
+ * double, from the int16 coordinates c_p, c_q, c_i and the deltas d_p, d_q: c_p == c_q gives d_p when d_p == d_q, else 0;
+ * otherwise, the pair ordered so that c_1 < c_2: d_1 when c_i <= c_1, d_2 when c_i >= c_2, else
+ * d_1 + (c_i - c_1) * ((d_2 - d_1) / (c_2 - c_1)), every operation rounded on its own.  D(i) starts at 0.0 and takes
+ * D = D + scalar_t * delta_t(i) tuple by tuple; the varied point is (double)int16 + D, never rounded to an integer.
+ * svgr_gvar_deltas: D of every atlas point, 2 doubles per point, into `pt_dxy_out`; one launch, one lane per point.  Without
+ * points, or without any tuple, the result is zeros and nothing is launched (ctx may then be NULL).
+ * svgr_glyf_outline_var: svgr_glyf_outline of the varied points: the delta pass, then the outline pass, on the context's
+ * stream -- two launches, one upload, one download, one wait; the deltas stay on the device.  A midpoint of two varied points
+ * is (a + b) * 0.5 of the two doubles.  Without any tuple it is svgr_glyf_outline, bytes and launch count.
+ * Both: SVGR_E_INVALID, before anything is launched, for what svgr_glyf_outline refuses and for offsets (glyph_tuple_off,
+ * tuple_pt_off) that decrease, do not begin at 0 or do not end at the counts given, a tp_index that does not increase strictly
+ * within its tuple or is not below its glyph's point count, or a scalar that is not finite or lies outside [-1, 1];
+ * SVGR_E_OVERFLOW, likewise, when a count exceeds INT32_MAX / 2.  SVGR_E_STATE should a lane meet a point or slot outside
+ * its tables (a defect, never an input's doing).  The result is identical from run to run.
+ * svgr_gvar_block: lanes (= atlas points) per workgroup of the delta pass's kernel.                                        */
+int svgr_gvar_deltas(svgr_ctx* ctx, const int16_t* pt_xy /* 2 per point */, int64_t n_points,
+                     const int32_t* contour_off /* n_contours + 1 */, int64_t n_contours,
+                     const int32_t* glyph_contour_off /* n_glyphs + 1 */, int64_t n_glyphs,
+                     const int32_t* glyph_tuple_off /* n_glyphs + 1 */, const double* tuple_scalar, int64_t n_tuples,
+                     const int32_t* tuple_pt_off /* n_tuples + 1 */, const int32_t* tp_index, const int16_t* tp_dxy /* 2 per entry */,
+                     int64_t n_entries, double* pt_dxy_out /* 2 per point */);
+int svgr_glyf_outline_var(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
+                          int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph,
+                          const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy,
+                          int64_t n_parts, const int32_t* glyph_tuple_off, const double* tuple_scalar, int64_t n_tuples,
+                          const int32_t* tuple_pt_off, const int32_t* tp_index, const int16_t* tp_dxy, int64_t n_entries,
+                          svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
+int svgr_gvar_block(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

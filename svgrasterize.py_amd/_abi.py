@@ -181,6 +181,10 @@ _PROTOS = {
     "svgr_textpath_block": (C.c_int, []),
     "svgr_glyf_outline": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "svgr_glyf_block": (C.c_int, []),
+    "svgr_gvar_deltas": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "svgr_glyf_outline_var": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64,
+                                        _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "svgr_gvar_block": (C.c_int, []),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
@@ -724,6 +728,15 @@ def glyf_outline(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_
     ``X = (x' + pen) * sx``, ``Y = y' * sy``.  On the device of `ctx` (default: the process's context; none is made when no part
     has a point)."""
     lib = load_library()
+    args, _n_glyphs, lanes = _glyf_args(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_m, part_pen, part_sx, part_sy)
+    handle = (ctx if ctx is not None else Context.get()).handle if lanes else None
+    out = _P()
+    _check(lib.svgr_glyf_outline(handle, *args, C.byref(out)))
+    return _stroke_out(lib, out)
+
+
+def _glyf_args(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_m, part_pen, part_sx, part_sy):
+    """(the atlas and part arguments of svgr_glyf_outline behind its context, the glyph count, the lanes the call has)."""
     pt_xy = np.ascontiguousarray(pt_xy, dtype=np.int16).reshape(-1, 2)
     pt_on = np.ascontiguousarray(pt_on, dtype=np.uint8).reshape(-1)
     contour_off = np.ascontiguousarray(contour_off, dtype=np.int32).reshape(-1)
@@ -743,18 +756,71 @@ def glyf_outline(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_
             and int(glyph_contour_off.min()) >= 0 and int(glyph_contour_off.max()) <= n_contours):
         first = contour_off.astype(np.int64)[glyph_contour_off]
         lanes = int((first[part_glyph + 1] - first[part_glyph]).clip(min=0).sum())
-    handle = (ctx if ctx is not None else Context.get()).handle if lanes else None
-    out = _P()
-    _check(lib.svgr_glyf_outline(handle, pt_xy.ctypes.data_as(_P), pt_on.ctypes.data_as(_P), len(pt_xy), contour_off.ctypes.data_as(_P),
-                                 n_contours, glyph_contour_off.ctypes.data_as(_P), n_glyphs, part_glyph.ctypes.data_as(_P),
-                                 part_m.ctypes.data_as(_P), part[0].ctypes.data_as(_P), part[1].ctypes.data_as(_P),
-                                 part[2].ctypes.data_as(_P), n_parts, C.byref(out)))
-    return _stroke_out(lib, out)
+    args = (pt_xy.ctypes.data_as(_P), pt_on.ctypes.data_as(_P), len(pt_xy), contour_off.ctypes.data_as(_P), n_contours,
+            glyph_contour_off.ctypes.data_as(_P), n_glyphs, part_glyph.ctypes.data_as(_P), part_m.ctypes.data_as(_P),
+            part[0].ctypes.data_as(_P), part[1].ctypes.data_as(_P), part[2].ctypes.data_as(_P), n_parts)   # (a pointer keeps its array alive)
+    return args, n_glyphs, lanes
 
 
 def glyf_block() -> int:
     """(part, point) pairs per workgroup of the TrueType outline kernel (svgr_glyf_block)."""
     return int(load_library().svgr_glyf_block())
+
+
+def _tuple_arrays(n_glyphs, glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy):
+    """The tuple arrays of the two variable-font entries in the library's types; what the library cannot see -- that the tables
+    are as long as the counts say -- is checked here, what they hold it checks itself."""
+    glyph_tuple_off = np.ascontiguousarray(glyph_tuple_off, dtype=np.int32).reshape(-1)
+    tuple_scalar = np.ascontiguousarray(tuple_scalar, dtype=np.float64).reshape(-1)
+    tuple_pt_off = np.ascontiguousarray(tuple_pt_off, dtype=np.int32).reshape(-1)
+    tp_index = np.ascontiguousarray(tp_index, dtype=np.int32).reshape(-1)
+    tp_dxy = np.ascontiguousarray(tp_dxy, dtype=np.int16).reshape(-1, 2)
+    if len(glyph_tuple_off) != n_glyphs + 1 or len(tuple_pt_off) != len(tuple_scalar) + 1 or len(tp_dxy) != len(tp_index):
+        raise ValueError("the tuple arrays do not match")
+    return glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy
+
+
+def gvar_deltas(pt_xy, contour_off, glyph_contour_off, glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy,
+                ctx: "Context | None" = None):
+    """svgr_gvar_deltas: (n_points, 2) float64, the delta of every atlas point at one instance of a variable font.  The atlas is
+    `glyf_outline`'s; glyph g owns the tuples ``[glyph_tuple_off[g], glyph_tuple_off[g + 1])``, tuple t the scalar
+    ``tuple_scalar[t]`` and the entries ``[tuple_pt_off[t], tuple_pt_off[t + 1])`` of `tp_index` (glyph-local, strictly increasing)
+    and `tp_dxy` (n, 2) int16.  On the device of `ctx` (default: the process's context; none is made without points or tuples)."""
+    lib = load_library()
+    pt_xy = np.ascontiguousarray(pt_xy, dtype=np.int16).reshape(-1, 2)
+    contour_off = np.ascontiguousarray(contour_off, dtype=np.int32).reshape(-1)
+    glyph_contour_off = np.ascontiguousarray(glyph_contour_off, dtype=np.int32).reshape(-1)
+    if len(contour_off) < 1 or len(glyph_contour_off) < 1:
+        raise ValueError("the atlas arrays do not match")
+    n_glyphs, n_contours = len(glyph_contour_off) - 1, len(contour_off) - 1
+    tuples = _tuple_arrays(n_glyphs, glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy)
+    handle = (ctx if ctx is not None else Context.get()).handle if len(pt_xy) and len(tuples[1]) else None
+    out = np.zeros((len(pt_xy), 2), dtype=np.float64)
+    _check(lib.svgr_gvar_deltas(handle, pt_xy.ctypes.data_as(_P), len(pt_xy), contour_off.ctypes.data_as(_P), n_contours,
+                                glyph_contour_off.ctypes.data_as(_P), n_glyphs, tuples[0].ctypes.data_as(_P), tuples[1].ctypes.data_as(_P),
+                                len(tuples[1]), tuples[2].ctypes.data_as(_P), tuples[3].ctypes.data_as(_P), tuples[4].ctypes.data_as(_P),
+                                len(tuples[3]), out.ctypes.data_as(_P)))
+    return out
+
+
+def glyf_outline_var(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_m, part_pen, part_sx, part_sy,
+                     glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy, ctx: "Context | None" = None):
+    """svgr_glyf_outline_var: `glyf_outline` of the points varied by `gvar_deltas`' tuples -- the delta pass and the outline pass
+    in one call; the deltas stay on the device."""
+    lib = load_library()
+    args, n_glyphs, lanes = _glyf_args(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, part_m, part_pen, part_sx, part_sy)
+    tuples = _tuple_arrays(n_glyphs, glyph_tuple_off, tuple_scalar, tuple_pt_off, tp_index, tp_dxy)
+    handle = (ctx if ctx is not None else Context.get()).handle if lanes else None
+    out = _P()
+    _check(lib.svgr_glyf_outline_var(handle, *args, tuples[0].ctypes.data_as(_P), tuples[1].ctypes.data_as(_P), len(tuples[1]),
+                                     tuples[2].ctypes.data_as(_P), tuples[3].ctypes.data_as(_P), tuples[4].ctypes.data_as(_P),
+                                     len(tuples[3]), C.byref(out)))
+    return _stroke_out(lib, out)
+
+
+def gvar_block() -> int:
+    """Atlas points per workgroup of the variable-font delta kernel (svgr_gvar_block)."""
+    return int(load_library().svgr_gvar_block())
 
 
 def image_levels(h: int, w: int):

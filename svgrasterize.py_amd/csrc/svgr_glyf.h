@@ -14,7 +14,8 @@
 //             on, else the midpoint of prev and p[i]) over p[i] to (next if on, else the midpoint of p[i] and next); an on-curve
 //             p[i] with an on-curve next emits the line p[i] -> next; an on-curve p[i] with an off-curve next emits nothing.
 //             After the contour's last segment comes one PATH_CLOSED line of length 0 at the chain's start: p[0] if on, else
-//             p[n-1] if on, else their midpoint.  Midpoints are (a + b) * 0.5 in font units (exact in double); a quadratic
+//             p[n-1] if on, else their midpoint.  Midpoints are (a + b) * 0.5 in font units (exact in double for the int16
+//             points; with the deltas of a variable font's instance, pt_dxy, one rounded sum and an exact halving); a quadratic
 //             P0 Q P1 is stored as the cubic P0, (1/3) P0 + (2/3) Q, (2/3) Q + (1/3) P1, P1 made from the transformed points
 //   slots     whether a point emits is a matter of the flags alone: pt_slot[a], the place of point a's segment among the
 //             segments of its glyph, and contour_segs[c] are glyph constants, made by glyf_tables on the host
@@ -49,6 +50,7 @@ struct GlyfView {
     const double* part_sx;
     const double* part_sy;
     int n_contours, n_parts, n_points, n_out;
+    const double* pt_dxy;            // 2 per atlas point, or null: the deltas of a variable font's instance (svgr_gvar.h)
 };
 
 struct GlyfPart { double m00, m01, m10, m11, dx, dy, pen, sx, sy; };
@@ -58,6 +60,18 @@ GLYF_HD void glyf_transform(const GlyfPart& p, double x, double y, double& X, do
     const double yp = (p.m01 * x + p.m11 * y) + p.dy;
     X = (xp + p.pen) * p.sx;
     Y = yp * p.sy;
+}
+
+// Atlas point a in font units: the int16 point, plus its delta at an instance of a variable font.
+GLYF_HD void glyf_point(const GlyfView& v, int a, double& x, double& y) {
+    x = (double)v.pt_xy[2 * (size_t)a];
+    y = (double)v.pt_xy[2 * (size_t)a + 1];
+    if (v.pt_dxy) {
+        double dx, dy;
+        marker_load2(v.pt_dxy + 2 * (size_t)a, dx, dy);
+        x = x + dx;
+        y = y + dy;
+    }
 }
 
 GLYF_HD void glyf_store(int* types, double* params, long long slot, int type, const double* o) {
@@ -85,8 +99,9 @@ GLYF_HD bool glyf_emit(const GlyfView& v, int j, int* types, double* params) {
     const bool on = v.pt_on[a] != 0, on_p = v.pt_on[ap] != 0, on_n = v.pt_on[an] != 0;
     const bool emits = !on || on_n;
     if (!emits && !last) return true;
-    const double x = (double)v.pt_xy[2 * (size_t)a], y = (double)v.pt_xy[2 * (size_t)a + 1];
-    const double xn = (double)v.pt_xy[2 * (size_t)an], yn = (double)v.pt_xy[2 * (size_t)an + 1];
+    double x, y, xn, yn;
+    glyf_point(v, a, x, y);
+    glyf_point(v, an, xn, yn);
     GlyfPart p;
     {
         const double* m = v.part_m + (size_t)k * 6;
@@ -106,7 +121,8 @@ GLYF_HD bool glyf_emit(const GlyfView& v, int j, int* types, double* params) {
             glyf_transform(p, xn, yn, o[2], o[3]);
             glyf_store(types, params, slot, SVGR_PATH_LINE, o);
         } else {    // the quadratic over p[i]
-            const double xp = (double)v.pt_xy[2 * (size_t)ap], yp = (double)v.pt_xy[2 * (size_t)ap + 1];
+            double xp, yp;
+            glyf_point(v, ap, xp, yp);
             const double sx = on_p ? xp : (xp + x) * 0.5, sy = on_p ? yp : (yp + y) * 0.5;
             const double ex = on_n ? xn : (x + xn) * 0.5, ey = on_n ? yn : (y + yn) * 0.5;
             double qx, qy;

@@ -8367,10 +8367,15 @@ int svgr_path_place_glyphs(svgr_ctx* ctx, const int32_t* seg_types, const double
 //   k_glyf_emit   one lane per (part, atlas point) pair: its part by binary search in the host-built prefix sums of the parts'
 //                 point counts, its contour by binary search in the contour offsets, three int16 points and their flags, at most
 //                 one segment (type + 8 doubles) and, for a contour's last point, the closing line
+//   k_gvar_delta  (svgr_glyf_outline_var, svgr_gvar_deltas; svgr_gvar.h, DESIGN.md "Variable fonts") one lane per atlas point: its
+//                 contour and glyph by binary search, then per tuple of the glyph three binary searches in the tuple's sorted point
+//                 indices and the stored or interpolated delta; one pair of doubles per point, which k_glyf_emit then adds to the
+//                 int16 point it reads
 // Every slot is a glyph constant the host made while it checked the input; stores are disjoint and no atomic takes part (the
-// `bad` flag is a plain store of the same value by every writer).  All geometry is f64.
+// `bad` flag is a plain store of the same value by every writer).  No LDS.  All geometry is f64.
 // ======================================================================================
 #include "svgr_glyf.h"
+#include "svgr_gvar.h"
 
 constexpr int GLYF_B = 256;   // (part, point) pairs (= lanes) per workgroup
 // (a section of its own, like the marker kernels': the tile kernel's branches to its cold paths keep their reach)
@@ -8382,29 +8387,89 @@ GLYF_KERNEL void k_glyf_emit(GlyfView v, int n_lanes, int* __restrict__ types, d
     if (!glyf_emit(v, j, types, params)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
 }
 
-static int glyf_outline_impl(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
-                             int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph,
-                             const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts,
-                             svgr_stroke_out** out) {
-    if (!out || (n_points > 0 && !pt_xy)) return fail(SVGR_E_INVALID, "svgr_glyf_outline: bad arguments");
+// The tuples of a variable font's instance, as svgr_glyf_outline_var and svgr_gvar_deltas take them (svgr_gvar.h).
+struct GvarIn {
+    const int32_t* glyph_tuple_off;
+    const double* tuple_scalar;
+    int64_t n_tuples;
+    const int32_t* tuple_pt_off;
+    const int32_t* tp_index;
+    const int16_t* tp_dxy;
+    int64_t n_entries;
+};
+
+// Where the tuple arrays lie in an upload that begins them at `at`.
+struct GvarBlob {
+    size_t i_toff, i_scalar, i_poff, i_index, i_dxy, i_end;
+    GvarBlob(size_t at, int ng, int nt, int ne) {
+        i_toff = at;
+        i_scalar = i_toff + pad64((size_t)(ng + 1) * 4);
+        i_poff = i_scalar + pad64((size_t)nt * 8);
+        i_index = i_poff + pad64((size_t)(nt + 1) * 4);
+        i_dxy = i_index + pad64((size_t)ne * 4);
+        i_end = i_dxy + pad64((size_t)ne * 4);
+    }
+    void fill(char* blob, const GvarIn& g, int ng, int nt, int ne) const {
+        memcpy(blob + i_toff, g.glyph_tuple_off, (size_t)(ng + 1) * 4);
+        if (nt) memcpy(blob + i_scalar, g.tuple_scalar, (size_t)nt * 8);
+        memcpy(blob + i_poff, g.tuple_pt_off, (size_t)(nt + 1) * 4);
+        if (ne) memcpy(blob + i_index, g.tp_index, (size_t)ne * 4);
+        if (ne) memcpy(blob + i_dxy, g.tp_dxy, (size_t)ne * 4);
+    }
+    GvarView view(const char* d_in, const int16_t* pt_xy, const int* contour_off, const int* glyph_contour_off, int nc, int ng, int npt,
+                  int nt) const {
+        return GvarView{pt_xy, contour_off, glyph_contour_off, (const int*)(d_in + i_toff), (const double*)(d_in + i_scalar),
+                        (const int*)(d_in + i_poff), (const int*)(d_in + i_index), (const int16_t*)(d_in + i_dxy), nc, ng, npt, nt};
+    }
+};
+
+constexpr int GVAR_B = 256;   // atlas points (= lanes) per workgroup
+
+// One lane per atlas point: its delta at the instance, summed over its glyph's tuples (gvar_delta), stored as one pair.
+__global__ __launch_bounds__(GVAR_B) __attribute__((section(".text.svgr_glyf")))
+void k_gvar_delta(GvarView v, double* __restrict__ pt_dxy, int* __restrict__ bad) {
+    const int a = blockIdx.x * GVAR_B + threadIdx.x;
+    if (a >= v.n_points) return;
+    double dx, dy;
+    if (!gvar_delta(v, a, dx, dy)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
+    marker_store2(pt_dxy + 2 * (size_t)a, dx, dy);
+}
+
+// svgr_glyf_outline (gv null) and svgr_glyf_outline_var: with tuples, k_gvar_delta runs in front of k_glyf_emit on the same
+// stream and the deltas stay on the device.
+static int glyf_outline_impl(const char* name, svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points,
+                             const int32_t* contour_off, int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs,
+                             const int32_t* part_glyph, const double* part_m, const double* part_pen, const double* part_sx,
+                             const double* part_sy, int64_t n_parts, const GvarIn* gv, svgr_stroke_out** out) {
+    if (!out || (n_points > 0 && !pt_xy)) return fail(SVGR_E_INVALID, "%s: bad arguments", name);
     GlyfTables t;
     if (int rc = glyf_tables(pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m, part_pen, part_sx,
                              part_sy, n_parts, t))
-        return fail(rc, "svgr_glyf_outline: %s", t.why);
+        return fail(rc, "%s: %s", name, t.why);
+    if (gv) {
+        const char* why = "";
+        if (int rc = gvar_tables(n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, gv->glyph_tuple_off, gv->tuple_scalar,
+                                 gv->n_tuples, gv->tuple_pt_off, gv->tp_index, gv->tp_dxy, gv->n_entries, why))
+            return fail(rc, "%s: %s", name, why);
+        if (gv->n_tuples == 0) gv = nullptr;   // (no tuple: the default instance, svgr_glyf_outline's own launch)
+    }
     std::unique_ptr<svgr_stroke_out> res(new svgr_stroke_out());
     const int n_lanes = t.part_lane_off[(size_t)n_parts], n_out = t.part_seg_off[(size_t)n_parts];
     if (n_lanes == 0 || n_out == 0) {   // no part, parts of empty glyphs, or contours of a single point only
         *out = res.release();
         return 0;
     }
-    if (!ctx) return fail(SVGR_E_INVALID, "svgr_glyf_outline: no context");
-    // ---- one upload: the atlas with its slot table, the parts with their prefix sums
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: no context", name);
+    // ---- one upload: the atlas with its slot table, the parts with their prefix sums, the tuples
     const int np = (int)n_parts, npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs;
+    const int nt = gv ? (int)gv->n_tuples : 0, ne = gv ? (int)gv->n_entries : 0;
     const size_t i_on = pad64((size_t)npt * 4), i_slot = i_on + pad64((size_t)npt), i_coff = i_slot + pad64((size_t)npt * 4);
     const size_t i_goff = i_coff + pad64((size_t)(nc + 1) * 4), i_pglyph = i_goff + pad64((size_t)(ng + 1) * 4);
     const size_t i_plane = i_pglyph + pad64((size_t)np * 4), i_pseg = i_plane + pad64((size_t)(np + 1) * 4);
     const size_t i_m = i_pseg + pad64((size_t)(np + 1) * 4), i_pen = i_m + pad64((size_t)np * 48), i_sx = i_pen + pad64((size_t)np * 8);
-    const size_t i_sy = i_sx + pad64((size_t)np * 8), i_end = i_sy + pad64((size_t)np * 8);
+    const size_t i_sy = i_sx + pad64((size_t)np * 8), i_gvar = i_sy + pad64((size_t)np * 8);
+    const GvarBlob gb(i_gvar, ng, nt, ne);
+    const size_t i_end = gv ? gb.i_end : i_gvar;
     std::vector<char> blob(i_end);
     memcpy(blob.data(), pt_xy, (size_t)npt * 4);
     memcpy(blob.data() + i_on, pt_on, (size_t)npt);
@@ -8418,11 +8483,74 @@ static int glyf_outline_impl(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t*
     memcpy(blob.data() + i_pen, part_pen, (size_t)np * 8);
     memcpy(blob.data() + i_sx, part_sx, (size_t)np * 8);
     memcpy(blob.data() + i_sy, part_sy, (size_t)np * 8);
+    if (gv) gb.fill(blob.data(), *gv, ng, nt, ne);
 
     HIPCHK(enter_ctx(ctx));
     hipStream_t st = ctx->stream;
-    // the result block: params, types, the kernel's error flag
-    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 8;
+    // the result block: params, types, the kernels' error flag; behind what is downloaded, the deltas (they stay on the device)
+    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 64;
+    const size_t o_all = o_end + (gv ? pad64((size_t)npt * 16) : 0);
+    std::vector<char> back(o_end);
+    PoolBlock in, outb;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(outb.alloc(o_all, ctx->device));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const char* d_in = in.as<char>();
+    int* d_bad = (int*)(outb.as<char>() + o_bad);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
+    double* d_dxy = gv ? (double*)(outb.as<char>() + o_end) : nullptr;
+    if (gv) {
+        const GvarView gview = gb.view(d_in, (const int16_t*)d_in, (const int*)(d_in + i_coff), (const int*)(d_in + i_goff), nc, ng, npt, nt);
+        SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, st, gview, d_dxy, d_bad);
+        HIPCHK(hipGetLastError());
+    }
+    const GlyfView view{(const int16_t*)d_in, (const uint8_t*)(d_in + i_on), (const int*)(d_in + i_slot), (const int*)(d_in + i_coff),
+                        (const int*)(d_in + i_goff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_plane), (const int*)(d_in + i_pseg),
+                        (const double*)(d_in + i_m), (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy),
+                        nc, np, npt, n_out, d_dxy};
+    SVGR_LAUNCH(k_glyf_emit, grid1((size_t)n_lanes, GLYF_B), dim3(GLYF_B), 0, st, view, n_lanes, (int*)(outb.as<char>() + o_types),
+                outb.as<double>(), d_bad);
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "%s: a lane met a slot outside the result", name);
+    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
+    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    res->sizes = std::move(t.sizes);
+    *out = res.release();
+    return 0;
+}
+
+// svgr_gvar_deltas: the deltas alone.
+static int gvar_deltas_impl(svgr_ctx* ctx, const int16_t* pt_xy, int64_t n_points, const int32_t* contour_off, int64_t n_contours,
+                            const int32_t* glyph_contour_off, int64_t n_glyphs, const GvarIn& gv, double* pt_dxy_out) {
+    if ((n_points > 0 && (!pt_xy || !pt_dxy_out))) return fail(SVGR_E_INVALID, "svgr_gvar_deltas: bad arguments");
+    const char* why = "";
+    if (int rc = gvar_tables(n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, gv.glyph_tuple_off, gv.tuple_scalar, gv.n_tuples,
+                             gv.tuple_pt_off, gv.tp_index, gv.tp_dxy, gv.n_entries, why))
+        return fail(rc, "svgr_gvar_deltas: %s", why);
+    if (n_points == 0) return 0;
+    if (gv.n_tuples == 0) {   // the default instance: zeros, nothing is launched
+        for (int64_t k = 0; k < 2 * n_points; ++k) pt_dxy_out[k] = 0.0;
+        return 0;
+    }
+    if (!ctx) return fail(SVGR_E_INVALID, "svgr_gvar_deltas: no context");
+    const int npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs, nt = (int)gv.n_tuples, ne = (int)gv.n_entries;
+    const size_t i_coff = pad64((size_t)npt * 4), i_goff = i_coff + pad64((size_t)(nc + 1) * 4), i_gvar = i_goff + pad64((size_t)(ng + 1) * 4);
+    const GvarBlob gb(i_gvar, ng, nt, ne);
+    std::vector<char> blob(gb.i_end);
+    memcpy(blob.data(), pt_xy, (size_t)npt * 4);
+    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
+    memcpy(blob.data() + i_goff, glyph_contour_off, (size_t)(ng + 1) * 4);
+    gb.fill(blob.data(), gv, ng, nt, ne);
+
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t o_bad = pad64((size_t)npt * 16), o_end = o_bad + 64;
     std::vector<char> back(o_end);
     PoolBlock in, outb;
     StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
@@ -8432,34 +8560,47 @@ static int glyf_outline_impl(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t*
     const char* d_in = in.as<char>();
     int* d_bad = (int*)(outb.as<char>() + o_bad);
     HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
-    const GlyfView view{(const int16_t*)d_in, (const uint8_t*)(d_in + i_on), (const int*)(d_in + i_slot), (const int*)(d_in + i_coff),
-                        (const int*)(d_in + i_goff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_plane), (const int*)(d_in + i_pseg),
-                        (const double*)(d_in + i_m), (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy),
-                        nc, np, npt, n_out};
-    SVGR_LAUNCH(k_glyf_emit, grid1((size_t)n_lanes, GLYF_B), dim3(GLYF_B), 0, st, view, n_lanes, (int*)(outb.as<char>() + o_types),
-                outb.as<double>(), d_bad);
+    const GvarView gview = gb.view(d_in, (const int16_t*)d_in, (const int*)(d_in + i_coff), (const int*)(d_in + i_goff), nc, ng, npt, nt);
+    SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, st, gview, outb.as<double>(), d_bad);
     HIPCHK(hipGetLastError());
-    // ---- one download
     HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     int bad = 0;
     memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "svgr_glyf_outline: a lane met a slot outside the result");
-    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
-    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
-    res->sizes = std::move(t.sizes);
-    *out = res.release();
+    if (bad) return fail(SVGR_E_STATE, "svgr_gvar_deltas: a lane met a point outside its tables");
+    memcpy(pt_dxy_out, back.data(), (size_t)npt * 16);
     return 0;
 }
 
 extern "C" {
 int svgr_glyf_block(void) { return GLYF_B; }
+int svgr_gvar_block(void) { return GVAR_B; }
 int svgr_glyf_outline(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
                       int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph, const double* part_m,
                       const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts, svgr_stroke_out** out) {
     return abi_guard("svgr_glyf_outline", [&]() {
-        return glyf_outline_impl(ctx, pt_xy, pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m,
-                                 part_pen, part_sx, part_sy, n_parts, out);
+        return glyf_outline_impl("svgr_glyf_outline", ctx, pt_xy, pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs,
+                                 part_glyph, part_m, part_pen, part_sx, part_sy, n_parts, nullptr, out);
+    });
+}
+int svgr_glyf_outline_var(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off,
+                          int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph,
+                          const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts,
+                          const int32_t* glyph_tuple_off, const double* tuple_scalar, int64_t n_tuples, const int32_t* tuple_pt_off,
+                          const int32_t* tp_index, const int16_t* tp_dxy, int64_t n_entries, svgr_stroke_out** out) {
+    return abi_guard("svgr_glyf_outline_var", [&]() {
+        const GvarIn gv{glyph_tuple_off, tuple_scalar, n_tuples, tuple_pt_off, tp_index, tp_dxy, n_entries};
+        return glyf_outline_impl("svgr_glyf_outline_var", ctx, pt_xy, pt_on, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs,
+                                 part_glyph, part_m, part_pen, part_sx, part_sy, n_parts, &gv, out);
+    });
+}
+int svgr_gvar_deltas(svgr_ctx* ctx, const int16_t* pt_xy, int64_t n_points, const int32_t* contour_off, int64_t n_contours,
+                     const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* glyph_tuple_off, const double* tuple_scalar,
+                     int64_t n_tuples, const int32_t* tuple_pt_off, const int32_t* tp_index, const int16_t* tp_dxy, int64_t n_entries,
+                     double* pt_dxy_out) {
+    return abi_guard("svgr_gvar_deltas", [&]() {
+        const GvarIn gv{glyph_tuple_off, tuple_scalar, n_tuples, tuple_pt_off, tp_index, tp_dxy, n_entries};
+        return gvar_deltas_impl(ctx, pt_xy, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, gv, pt_dxy_out);
     });
 }
 }  // extern "C"

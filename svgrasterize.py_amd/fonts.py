@@ -231,9 +231,11 @@ class FontsDB:
                 continue
             svg_scene_from_filepath(source, fonts=self)
 
-    def resolve(self, family, weight=None, style=None):
+    def resolve(self, family, weight=None, style=None, variations=None):
         """Best face for ``family`` or None: exact family, else its generic family (unknown names count as serif);
-        then the requested style (else normal); then the nearest weight (first registered wins ties)."""
+        then the requested style (else normal); then the nearest weight (first registered wins ties).  A variable TrueType
+        face with a ``wght`` axis is as near as the weight is to the axis' range (0 inside it) and comes back as its instance at
+        that weight and at `variations`, ``{axis tag: value}``, of which the tags the face lacks are left out."""
         self._load_pending()
         family = "serif" if family is None else family.lower()
         faces = self.fonts.get(family)
@@ -252,4 +254,16 @@ class FontsDB:
         if not styled:
             return None
         weight = weight or 400
-        return min(styled, key=lambda f: abs(f.weight - weight))
+
+        def distance(face):
+            axis = next((a for a in getattr(face, "axes", ()) if a.tag == "wght"), None)
+            if axis is None:
+                return abs(face.weight - weight)
+            return 0 if axis.minimum <= weight <= axis.maximum else min(abs(weight - axis.minimum), abs(weight - axis.maximum))
+
+        face = min(styled, key=distance)
+        tags = [a.tag for a in getattr(face, "axes", ())]
+        if not tags:
+            return face
+        wanted = {"wght": weight, **(variations or {})}
+        return face.instance({tag: value for tag, value in wanted.items() if tag in tags})

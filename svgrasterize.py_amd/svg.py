@@ -37,6 +37,9 @@ path) and ``dy`` (across it); ``x`` / ``y`` inside it are ignored.  It becomes o
 runs' fill and stroke nodes, the glyphs placed on the device, at the first render; loading needs no device.  A glyph whose
 midpoint is off the path is not drawn, there is no wrap on closed paths, text after the ``<textPath>`` goes on from the pen
 where it began; ``method="stretch"``, ``spacing`` and ``side="right"`` warn and the defaults are used.
+Also beyond the reference: variable TrueType fonts -- ``font-weight`` picks the ``wght`` of a variable face, ``font-stretch`` (the
+nine keywords or a percentage) its ``wdth``, ``font-variation-settings`` (``normal``, or ``"tag" number`` separated by commas) any
+axis the face has, and wins over both; all inherited; a malformed value warns and counts as ``normal`` (``truetype_var.py``).
 Not supported (a warning, the element is skipped): foreignObject, switch, ...; <image> of other formats
 (GIF, WebP, SVG) or remote URLs.
 """
@@ -85,6 +88,7 @@ _INHERITED = {
     "image-rendering",   # (beyond the reference: <image>)
     "stroke-dasharray", "stroke-dashoffset",   # (beyond the reference: dashed strokes)
     "marker-start", "marker-mid", "marker-end",   # (beyond the reference: markers; the shorthand ``marker`` is spelled out into them)
+    "font-variation-settings", "font-stretch",   # (beyond the reference: variable TrueType fonts)
 }
 _MARKER_PROPERTIES = ("marker-start", "marker-mid", "marker-end")
 _PATH_SHAPES = {"path", "rect", "circle", "ellipse", "line", "polyline", "polygon"}   # what a <textPath> may reference
@@ -727,6 +731,45 @@ def _font_weight(text) -> int:
     return {"normal": 400, "bold": 700}.get(text) or int(float(text))
 
 
+_FONT_STRETCH = {"ultra-condensed": 50.0, "extra-condensed": 62.5, "condensed": 75.0, "semi-condensed": 87.5, "normal": 100.0,
+                 "semi-expanded": 112.5, "expanded": 125.0, "extra-expanded": 150.0, "ultra-expanded": 200.0}
+_VARIATION = re.compile(r"""\s*(?:"([ -~]{4})"|'([ -~]{4})')\s+([-+]?(?:\d*\.\d+|\d+\.?)(?:[Ee][-+]?\d+)?)\s*$""")
+
+
+def _font_variations(attrs):
+    """``{axis tag: value}`` a run asks of a variable font beyond its weight, or None: ``font-stretch`` (a keyword or a
+    percentage) sets ``wdth``; ``font-variation-settings`` (``normal``, or a comma-separated list of ``"tag" number``) sets what it
+    names and wins.  A malformed value warns and counts as ``normal``."""
+    out = {}
+    stretch = attrs.get("font-stretch")
+    if stretch is not None:
+        word = _keyword(stretch)
+        value = _FONT_STRETCH.get(word)
+        if value is None and word.endswith("%"):
+            try:
+                value = float(word[:-1])
+            except ValueError:
+                value = None
+            if value is not None and not (value >= 0 and math.isfinite(value)):
+                value = None
+        if value is None:
+            warnings.warn(f"invalid font-stretch: {stretch}")
+        else:
+            out["wdth"] = value
+    settings = attrs.get("font-variation-settings")
+    if settings is not None and _keyword(settings) != "normal":
+        named = {}
+        for item in settings.split(","):
+            match = _VARIATION.match(item)
+            if match is None or not math.isfinite(float(match.group(3))):
+                warnings.warn(f"invalid font-variation-settings: {settings}")
+                named = {}
+                break
+            named[match.group(1) or match.group(2)] = float(match.group(3))
+        out.update(named)
+    return out or None
+
+
 def _names_to_unicode(names, by_name) -> list:
     """Glyph names of an hkern ``g1`` / ``g2`` list -> their unicode strings (unknown or unicode-less names drop out)."""
     out = []
@@ -1073,7 +1116,7 @@ class _Loader:
             if words is None:
                 return [], (ox, oy), after_blank
             size = parse_float(attrs.get("font-size", f"{FONT_SIZE}"))
-            font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")))
+            font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")), None, _font_variations(attrs))
             if font is None:
                 return [], (ox, oy), after_blank
             if isinstance(font, TrueTypeFont):   # (the outline is made on the device, at the first render; the advance is host arithmetic)
@@ -1160,7 +1203,7 @@ class _Loader:
             words, blank = _collapse(text, after_blank)
             if words is None:
                 return after_blank
-            font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")))
+            font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")), None, _font_variations(attrs))
             if font is None:
                 return after_blank
             runs.append(TextRun(words, font, parse_float(attrs.get("font-size", f"{FONT_SIZE}")), dict(attrs), moves["dx"], moves["dy"]))

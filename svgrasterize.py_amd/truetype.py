@@ -16,8 +16,7 @@ Refused with a ``ValueError`` that says which: ``OTTO`` (CFF outlines), ``ttcf``
 ``head maxp hhea hmtx cmap loca glyf``.
 
 Ignored: hinting (``fpgm``, ``prep``, ``cvt`` and the glyphs' instructions are skipped over, never interpreted), ``GSUB`` / ``GPOS``
-(no ligatures, no shaping, no GPOS kerning), ``gvar`` (the default instance is drawn), vertical metrics, bitmaps and colour
-tables.  One glyph per character; a character the ``cmap`` does not map takes glyph 0 (``.notdef``).
+(no ligatures, no shaping, no GPOS kerning), vertical metrics, bitmaps and colour tables.  One glyph per character; a character the ``cmap`` does not map takes glyph 0 (``.notdef``).
 
 A font file is untrusted: every offset, length and count is checked against the data before it is used, and a malformed
 file raises ``ValueError`` -- when it is read or, for a glyph's outline, when that glyph is first used (glyphs are decoded
@@ -32,6 +31,9 @@ ARG_1_AND_2_ARE_WORDS, ARGS_ARE_XY_VALUES, the three scale forms (F2Dot14) and M
 SCALED_COMPONENT_OFFSET is ignored (offsets are unscaled, FreeType's and Microsoft's default); a component placed by point
 matching warns once per font and gets the offset (0, 0); nesting deeper than 8, a cycle, or more than ``MAX_PARTS`` glyphs visited while flattening
 (components and the composites that hold them) warn and leave the glyph empty; USE_MY_METRICS is ignored (the advance is the glyph's own ``hmtx`` entry).
+
+Variable fonts (``fvar`` / ``avar`` / ``gvar``; ``truetype_var.py``): `TrueTypeFont.axes`, `is_variable`, and
+`TrueTypeFont.instance`, the font at a position of its axes.  A font without ``fvar`` takes none of that code.
 """
 from __future__ import annotations
 
@@ -132,7 +134,7 @@ class TrueTypeFont(Font):
     """A face read from a ``.ttf`` (``read_ttf``).  `hkern` maps ``(left glyph id, right glyph id)`` to what is subtracted from
     the pen, SVG's ``hkern k``: the negated value of the ``kern`` table."""
 
-    __slots__ = ["data", "tables", "n_glyphs", "advances", "loca", "_cmap", "_simple", "_parts", "_by_gid", "_composite", "_warned_matching"]
+    __slots__ = ["data", "tables", "n_glyphs", "advances", "loca", "_cmap", "_simple", "_parts", "_by_gid", "_composite", "_warned_matching", "_var", "_instances"]
 
     def __init__(self, data: bytes, family=None):
         self.data = data = bytes(data)
@@ -182,6 +184,45 @@ class TrueTypeFont(Font):
         self._simple, self._parts, self._by_gid, self._composite = {}, {}, {}, {}
         self._warned_matching = False
         self.missing_glyph = self.glyph(0, None)
+        from . import truetype_var  # noqa: PLC0415  (truetype_var.py imports this module)
+
+        self._var, self._instances = truetype_var.read_variations(self), {}
+
+    # -- variable fonts ------------------------------------------------------------------------------------------------
+    @property
+    def axes(self) -> tuple:
+        """The axes of a variable font, ``Axis(tag, minimum, default, maximum)`` in ``fvar`` order; empty for a static font."""
+        return self._var.axes if self._var is not None else ()
+
+    @property
+    def is_variable(self) -> bool:
+        return bool(self.axes)
+
+    def instance(self, coords=None, **axes):
+        """The font at a position of its axes, ``{tag: value}`` in user units as `coords` and / or as keywords
+        (``font.instance(wght=650)``): a ``truetype_var.TrueTypeInstance``, made once per position; an axis not named stays at
+        its default, a value is clamped to the axis' range, a tag the font does not have raises ``ValueError``.  With every axis
+        at its default the result is the font itself."""
+        from . import truetype_var  # noqa: PLC0415
+
+        return truetype_var.instance(self, coords, axes)
+
+    def glyph_deltas(self, gid: int, coords=None, **axes) -> np.ndarray:
+        """(n, 2) float64: what the instance at `coords` adds to each of the n points of the simple glyph `gid` (a composite or
+        empty glyph has none), on the device (svgr_gvar_deltas)."""
+        from . import truetype_var  # noqa: PLC0415
+
+        _user, normal = truetype_var.coordinates(self, coords, axes)
+        glyph = self.simple_glyph(gid)
+        if not len(glyph.on):
+            return np.zeros((0, 2), dtype=np.float64)
+        ends = glyph.ends.astype(np.int64) + 1
+        return _abi.gvar_deltas(glyph.xy, [0, *ends.tolist()], [0, len(ends)], **truetype_var.tuple_arrays(self, [gid], normal))
+
+    def point_count(self, gid: int) -> int:
+        """The points ``gvar`` numbers in a glyph: the points of a simple glyph, the components of a composite one."""
+        components = self._components(gid)
+        return len(self.simple_glyph(gid).on) if components is None else len(components)
 
     # -- cmap, metrics -------------------------------------------------------------------------------------------------
     def glyph_id(self, code: int) -> int:
@@ -238,11 +279,12 @@ class TrueTypeFont(Font):
 
     def outline(self, parts, sx: float, sy: float):
         """(types, params (n, 8), sizes) of `parts`, ``[((simple glyph id, m00, m01, m10, m11, dx, dy), pen)]``, through the device."""
-        index, atlas = {}, []
+        index, atlas, gids = {}, [], []
         for part, _pen in parts:
             if part[0] not in index:
                 index[part[0]] = len(atlas)
                 atlas.append(self.simple_glyph(part[0]))
+                gids.append(part[0])
         n = len(parts)
         contour_off, glyph_contour_off, points = [0], [0], 0
         for glyph in atlas:
@@ -251,9 +293,15 @@ class TrueTypeFont(Font):
             glyph_contour_off.append(len(contour_off) - 1)
         xy = np.concatenate([g.xy for g in atlas]) if atlas else np.zeros((0, 2), np.int16)
         on = np.concatenate([g.on for g in atlas]) if atlas else np.zeros(0, np.uint8)
-        return _abi.glyf_outline(xy, on, contour_off, glyph_contour_off, [index[part[0]] for part, _pen in parts],
-                                 np.array([part[1:] for part, _pen in parts], dtype=np.float64).reshape(n, 6),
-                                 np.array([pen for _part, pen in parts], dtype=np.float64), np.full(n, float(sx)), np.full(n, float(sy)))
+        return self._outline_call(gids, dict(
+            pt_xy=xy, pt_on=on, contour_off=contour_off, glyph_contour_off=glyph_contour_off, part_glyph=[index[part[0]] for part, _pen in parts],
+            part_m=np.array([part[1:] for part, _pen in parts], dtype=np.float64).reshape(n, 6),
+            part_pen=np.array([pen for _part, pen in parts], dtype=np.float64), part_sx=np.full(n, float(sx)), part_sy=np.full(n, float(sy))))
+
+    def _outline_call(self, atlas_gids, args):
+        """The device call of `outline`: `args` are svgr_glyf_outline's, `atlas_gids` the glyph ids of the atlas (an instance of a
+        variable font adds their tuples)."""
+        return _abi.glyf_outline(**args)
 
     # -- glyf ----------------------------------------------------------------------------------------------------------
     def _glyph_bytes(self, gid: int):
@@ -341,6 +389,10 @@ class TrueTypeFont(Font):
             self._composite[gid] = self._read_components(gid)
         return self._composite[gid]
 
+    def _placed_components(self, gid: int):
+        """`_components` as they are placed: an instance of a variable font moves the offsets."""
+        return self._components(gid)
+
     def _read_components(self, gid: int):
         off, length = self._glyph_bytes(gid)
         if length == 0:
@@ -385,7 +437,7 @@ class TrueTypeFont(Font):
         count[0] += 1   # (every glyph visited counts, composites too: the walk itself is bounded, not only its result)
         if count[0] > MAX_PARTS:
             raise _TooDeep(f"more than {MAX_PARTS} parts")
-        components = self._components(gid)
+        components = self._placed_components(gid)
         if components is None:
             return [(gid, *_IDENTITY)] if len(self.simple_glyph(gid).on) else []
         out = []
