@@ -1154,4 +1154,33 @@ SVGR_HD int tile_source(int t, int t0, int s0, int sn) {
     return s >= 0 && s < sn ? (int)s : -1;
 }
 
+// =====================================================================================
+// <image>: from a coordinate to texel indices (k_image_fill; on the host: tests/image_harness.cpp)
+//
+// image_corner: (x, y) in the texel grid of one (h, w) level, texel centres on the integers -> the four clamped indices of
+// the bilinear footprint and its two fractions.  The corner is clamped in double before it becomes an index, so a NaN or
+// huge coordinate lands on the edge, never outside the level: floor(NaN) goes through fmax(., -1) to -1, anything >= w to
+// w; every index lies in [0, w - 1] / [0, h - 1] and both fractions in [0, 1].
+// image_nearest: the level-0 texel (floor v, floor u) of nearest sampling, clamped the same way (NaN -> 0).
+// =====================================================================================
+#if !defined(__HIPCC__)
+static inline int min(int a, int b) { return b < a ? b : a; }
+static inline int max(int a, int b) { return a < b ? b : a; }
+#endif
+struct ImageCorner {
+    int c0, c1, r0, r1;
+    double fx, fy;
+};
+SVGR_HD ImageCorner image_corner(double x, double y, int w, int h) {
+    const double xf = fmin(fmax(floor(x), -1.0), (double)w), yf = fmin(fmax(floor(y), -1.0), (double)h);
+    const double fx = fmin(fmax(x - xf, 0.0), 1.0), fy = fmin(fmax(y - yf, 0.0), 1.0);
+    const int xi = (int)xf, yi = (int)yf;
+    const int c0 = min(max(xi, 0), w - 1), c1 = min(xi + 1, w - 1), r0 = min(max(yi, 0), h - 1), r1 = min(yi + 1, h - 1);
+    return ImageCorner{c0, c1, r0, r1, fx, fy};
+}
+SVGR_HD void image_nearest(double u, double v, int w, int h, double& xf, double& yf) {
+    xf = fmin(fmax(floor(u), 0.0), (double)(w - 1));
+    yf = fmin(fmax(floor(v), 0.0), (double)(h - 1));
+}
+
 }  // namespace svgr

@@ -4311,15 +4311,14 @@ struct ImageLevel {
 };
 
 // bilinear at image-space (u, v) of one level: texel centres at + 0.5, clamp to edge.  The corner is clamped in double
-// before it becomes an index, so a NaN or huge coordinate lands on the edge, never outside the level.  Interpolation in the
-// form a + f (b - a): a uniform image gives back its texel exactly.
+// before it becomes an index (svgr::image_corner), so a NaN or huge coordinate lands on the edge, never outside the level.
+// Interpolation in the form a + f (b - a): a uniform image gives back its texel exactly.
 __device__ __forceinline__ double lerp_d(double a, double b, double f) { return a + f * (b - a); }
 __device__ __forceinline__ double4 image_bilinear(const ImageLevel& L, double u, double v) {
     const double x = u * L.scale - 0.5, y = v * L.scale - 0.5;
-    const double xf = fmin(fmax(floor(x), -1.0), (double)L.w), yf = fmin(fmax(floor(y), -1.0), (double)L.h);
-    const double fx = fmin(fmax(x - xf, 0.0), 1.0), fy = fmin(fmax(y - yf, 0.0), 1.0);
-    const int xi = (int)xf, yi = (int)yf;
-    const int c0 = min(max(xi, 0), L.w - 1), c1 = min(xi + 1, L.w - 1), r0 = min(max(yi, 0), L.h - 1), r1 = min(yi + 1, L.h - 1);
+    const ImageCorner k = image_corner(x, y, L.w, L.h);
+    const int c0 = k.c0, c1 = k.c1, r0 = k.r0, r1 = k.r1;
+    const double fx = k.fx, fy = k.fy;
     const float4 t00 = L.tex[(size_t)r0 * L.w + c0], t01 = L.tex[(size_t)r0 * L.w + c1];
     const float4 t10 = L.tex[(size_t)r1 * L.w + c0], t11 = L.tex[(size_t)r1 * L.w + c1];
     return make_double4(lerp_d(lerp_d(t00.x, t01.x, fx), lerp_d(t10.x, t11.x, fx), fy),
@@ -4351,7 +4350,8 @@ __global__ void __launch_bounds__(256) k_image_fill(const svgr_image im, ImageLe
                 s = make_double4(lerp_d(s.x, t.x, blend), lerp_d(s.y, t.y, blend), lerp_d(s.z, t.z, blend), lerp_d(s.w, t.w, blend));
             }
         } else {
-            const double xf = fmin(fmax(floor(u), 0.0), (double)(lo.w - 1)), yf = fmin(fmax(floor(v), 0.0), (double)(lo.h - 1));
+            double xf, yf;
+            image_nearest(u, v, lo.w, lo.h, xf, yf);
             const float4 t = lo.tex[(size_t)(int)yf * lo.w + (int)xf];
             s = make_double4(t.x, t.y, t.z, t.w);
         }

@@ -1,6 +1,7 @@
 // Host build of the filter-primitive arithmetic in svgrasterize.py_amd/csrc/svgr_core.h (turb_init, turb_params, turb_point),
-// for CPU-side unit tests only (tests/test_filter_primitives_host.py, tests/test_gpu_filter_primitives.py).  NOT a CPU fallback
-// of the product: the package never loads it.
+// and a restatement of the displacement map's source-index guard, for CPU-side unit tests only
+// (tests/test_filter_primitives_host.py, tests/test_gpu_filter_primitives.py, tests/test_image_cases_host.py).  NOT a CPU
+// fallback of the product: the package never loads it.
 #include "../svgrasterize.py_amd/csrc/svgr_core.h"
 
 using namespace svgr;
@@ -33,6 +34,17 @@ void fh_turbulence_layer(int64_t seed, double fx, double fy, const double* tile,
             const double py = inv[3] * d0 + inv[4] * d1 + inv[5];
             turb_point(sel, grad, p, px, py, out + 4 * (R * cols + C));
         }
+    }
+}
+
+// k_layer_displacement_map's guard, restated: the displaced point (p0[i], p1[i]) against a source box (s0, s1, srows, scols),
+// compared as doubles and cast only behind the comparison.  out[i] = the flat pixel index the kernel would read, -1 where it
+// writes a transparent pixel.
+void fh_dm_index(const double* p0, const double* p1, long n, int s0, int s1, int srows, int scols, int64_t* out) {
+    for (long i = 0; i < n; ++i) {
+        const double r = floor(p0[i]) - s0, c = floor(p1[i]) - s1;
+        out[i] = -1;
+        if (r >= 0.0 && r < (double)srows && c >= 0.0 && c < (double)scols) out[i] = (int64_t)((size_t)r * scols + (size_t)c);
     }
 }
 

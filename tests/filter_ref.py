@@ -222,9 +222,51 @@ def displacement_map(src, src_offset, disp, disp_offset, lin, scale, xc, yc):
     return np.where(inside[..., None], src[ri, ci], 0.0)
 
 
+def displaced_points(disp, disp_offset, lin, scale, xc, yc, dtype=np.float64):
+    """The device points (p0, p1) that feDisplacementMap looks up, in `dtype` (the kernel's order of operations)."""
+    rows, cols = disp.shape[:2]
+    lin = np.asarray(lin, dtype=np.float64).astype(dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
+        du0 = dtype(scale) * (disp[..., xc].astype(dtype) - dtype(0.5))
+        du1 = dtype(scale) * (disp[..., yc].astype(dtype) - dtype(0.5))
+        dd0 = lin[0, 0] * du0 + lin[0, 1] * du1
+        dd1 = lin[1, 0] * du0 + lin[1, 1] * du1
+        p0 = (disp_offset[0] + np.arange(rows)[:, None]).astype(dtype) + dtype(0.5) + dd0
+        p1 = (disp_offset[1] + np.arange(cols)[None, :]).astype(dtype) + dtype(0.5) + dd1
+    return p0, p1
+
+
+def displacement_map_wide(src, src_offset, disp, disp_offset, lin, scale, xc, yc):
+    """`displacement_map` with the displaced points in long double.  The output is a copy of source pixels, so it equals a
+    double evaluation bit for bit wherever no displaced point lies within that evaluation's rounding error (a few 2^-53 of
+    the point's magnitude) of a pixel edge: `displacement_clearance` measures the distance.  A non-finite point compares
+    false with everything and gives a transparent pixel, as does a far one."""
+    p0, p1 = displaced_points(disp, disp_offset, lin, scale, xc, yc, np.longdouble)
+    r = np.floor(p0) - src_offset[0]
+    c = np.floor(p1) - src_offset[1]
+    with np.errstate(invalid="ignore"):
+        inside = (r >= 0) & (r < src.shape[0]) & (c >= 0) & (c < src.shape[1])
+    ri = np.where(inside, r, 0).astype(np.int64)
+    ci = np.where(inside, c, 0).astype(np.int64)
+    return np.where(inside[..., None], src[ri, ci], 0.0)
+
+
+def displacement_clearance(src_shape, src_offset, disp, disp_offset, lin, scale, xc, yc) -> float:
+    """The smallest distance of a finite displaced p0 / p1 from a pixel edge of the source (the integers s .. s + n of its
+    axis; beyond them both sides of an edge are transparent).  inf if no point is finite."""
+    d = np.inf
+    for p, s, n in zip(displaced_points(disp, disp_offset, lin, scale, xc, yc, np.longdouble), src_offset, src_shape):
+        p = p[np.isfinite(p)]
+        if p.size:
+            d = min(d, float(np.abs(p - np.clip(np.rint(p), s, s + n)).min()))
+    return d
+
+
 # -- the host build of svgr_core.h's filter arithmetic ---------------------------------------------------------------------
 def harness():
     L = host_build("filter_harness")
+    L.fh_dm_index.argtypes = [np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")] * 2 + [C.c_long] + [C.c_int] * 4 + [
+        np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")]
     f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
     i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
     L.fh_lattice.argtypes = [C.c_int64, i32p, f64p]
