@@ -668,6 +668,36 @@ int svgr_glyf_outline_var(svgr_ctx* ctx, const int16_t* pt_xy, const uint8_t* pt
                           svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
 int svgr_gvar_block(void);
 
+/* OpenType / CFF outlines (beyond the reference; the `CFF ` table of an .otf): the contours a Type 2 charstring draws --
+ * absolute points in font units, in double, with a kind each -- as a path in the layout above.  Table parsing and the
+ * charstring machine, hinting-free, are the caller's (opentype_cff.py); CFF has no composites, a part is a placed glyph.
+ * The atlas holds every distinct glyph once: `pt_xy` (2 doubles per point), `pt_kind` (0 MOVE, 1 LINE, 2 C1, 3 C2, 4 CURVE: a
+ * cubic's two control points and its end point), `contour_off` (n_contours + 1, in points) and `glyph_contour_off`
+ * (n_glyphs + 1, in contours).  The parts, and the transform of a point -- x' = (m00 x + m10 y) + dx, y' = (m01 x + m11 y) + dy,
+ * X = (x' + pen) sx, Y = y' sy, each product and sum rounded on its own -- are svgr_glyf_outline's.
+ * Within a contour p[first .. last] a LINE point a gives the PATH_LINE p[a-1] -> p[a] (slots 4..7 zero), a CURVE point a gives
+ * the PATH_CUBIC p[a-3], p[a-2], p[a-1], p[a]; MOVE, C1 and C2 give nothing.  The segments stand in point order; behind the last
+ * segment of a contour with at least 2 points comes one PATH_CLOSED line from p[last] to p[first] -- of length 0 when the
+ * charstring returned to its start itself, which is what svgr_glyf_outline leaves too.  A contour of a lone MOVE gives nothing,
+ * no subpath either.
+ * The result holds types, params and one subpath size per contour with segments, in part order, then contour order.  One
+ * launch, one lane per OUTPUT segment: which points emit is a matter of the kinds alone, and the table of the atlas'
+ * segments -- per segment its end point, or its contour for a closing line -- is made on the host during the validation walk.
+ * SVGR_E_INVALID, before anything is launched, for what svgr_glyf_outline refuses for offsets and parts, a contour whose
+ * first kind is not MOVE or that holds a second MOVE, a C1 that C2 and CURVE do not follow, a C2 or CURVE without its
+ * predecessors, a kind above 4, or a coordinate that is not finite or lies beyond +-1e150; SVGR_E_OVERFLOW, likewise, when a
+ * count exceeds INT32_MAX / 2.  Without segments -- no parts, parts of empty glyphs, lone MOVEs only -- the result is empty and
+ * nothing is launched (ctx may then be NULL).  SVGR_E_STATE should a lane meet an index outside its tables (a defect, never
+ * an input's doing).  The result is identical from run to run.
+ * svgr_cff_block: lanes (= output segments) per workgroup of the pass's kernel.                                             */
+int svgr_cff_outline(svgr_ctx* ctx, const double* pt_xy /* 2 per point */, const uint8_t* pt_kind, int64_t n_points,
+                     const int32_t* contour_off /* n_contours + 1 */, int64_t n_contours,
+                     const int32_t* glyph_contour_off /* n_glyphs + 1 */, int64_t n_glyphs, const int32_t* part_glyph,
+                     const double* part_m /* 6 per part */, const double* part_pen, const double* part_sx,
+                     const double* part_sy, int64_t n_parts,
+                     svgr_stroke_out** out);   /* read with svgr_stroke_out_counts / _copy / _free */
+int svgr_cff_block(void);
+
 /* PNG scanlines (read_png, host side): reverse the filters None / Sub / Up / Average / Paeth of `rows` filtered rows of
  * 1 + row_bytes bytes each (filter type first) into rows * row_bytes bytes of dst.  bytes_per_pixel is the filter's
  * stride (1 below 8 bits per pixel).  SVGR_E_INVALID on a filter type above 4 or when src_bytes is short; src is never

@@ -185,6 +185,8 @@ _PROTOS = {
     "svgr_glyf_outline_var": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64,
                                         _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "svgr_gvar_block": (C.c_int, []),
+    "svgr_cff_outline": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "svgr_cff_block": (C.c_int, []),
     "svgr_stroke_out_counts": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svgr_stroke_out_copy": (C.c_int, [_P, _P, _P, _P]),
     "svgr_stroke_out_free": (None, [_P]),
@@ -821,6 +823,47 @@ def glyf_outline_var(pt_xy, pt_on, contour_off, glyph_contour_off, part_glyph, p
 def gvar_block() -> int:
     """Atlas points per workgroup of the variable-font delta kernel (svgr_gvar_block)."""
     return int(load_library().svgr_gvar_block())
+
+
+def cff_outline(pt_xy, pt_kind, contour_off, glyph_contour_off, part_glyph, part_m, part_pen, part_sx, part_sy,
+                ctx: "Context | None" = None):
+    """svgr_cff_outline: (types, params (n, 8), sizes) of the CFF outlines of the parts.  The atlas holds every distinct glyph
+    once: `pt_xy` (n_points, 2) float64 in font units, `pt_kind` uint8 (0 MOVE, 1 LINE, 2 C1, 3 C2, 4 CURVE), `contour_off`
+    (n_contours + 1, in points), `glyph_contour_off` (n_glyphs + 1, in contours); the parts are `glyf_outline`'s.  On the device of
+    `ctx` (default: the process's context; none is made when nothing can be drawn)."""
+    lib = load_library()
+    pt_xy = np.ascontiguousarray(pt_xy, dtype=np.float64).reshape(-1, 2)
+    pt_kind = np.ascontiguousarray(pt_kind, dtype=np.uint8).reshape(-1)
+    contour_off = np.ascontiguousarray(contour_off, dtype=np.int32).reshape(-1)
+    glyph_contour_off = np.ascontiguousarray(glyph_contour_off, dtype=np.int32).reshape(-1)
+    part_glyph = np.ascontiguousarray(part_glyph, dtype=np.int32).reshape(-1)
+    part_m = np.ascontiguousarray(part_m, dtype=np.float64).reshape(-1, 6)
+    part = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (part_pen, part_sx, part_sy)]
+    n_parts = len(part_glyph)
+    if len(contour_off) < 1 or len(glyph_contour_off) < 1 or len(pt_kind) != len(pt_xy):
+        raise ValueError("the atlas arrays do not match")
+    if len(part_m) != n_parts or any(len(a) != n_parts for a in part):
+        raise ValueError("the part arrays do not match")
+    # (what the library cannot see: that the tables are as long as the counts say; what they hold it checks itself)
+    n_glyphs, n_contours = len(glyph_contour_off) - 1, len(contour_off) - 1
+    points = 0   # (tables the library is going to refuse count as none: it refuses them before it asks for a context)
+    if (n_parts and n_glyphs and int(part_glyph.min()) >= 0 and int(part_glyph.max()) < n_glyphs
+            and int(glyph_contour_off.min()) >= 0 and int(glyph_contour_off.max()) <= n_contours):
+        first = contour_off.astype(np.int64)[glyph_contour_off]
+        points = int((first[part_glyph + 1] - first[part_glyph]).clip(min=0).sum())
+    draws = points and bool(((pt_kind == 1) | (pt_kind == 4)).any())   # (lone MOVEs draw nothing: no launch, no context)
+    handle = (ctx if ctx is not None else Context.get()).handle if draws else None
+    out = _P()
+    _check(lib.svgr_cff_outline(handle, pt_xy.ctypes.data_as(_P), pt_kind.ctypes.data_as(_P), len(pt_xy), contour_off.ctypes.data_as(_P),
+                                n_contours, glyph_contour_off.ctypes.data_as(_P), n_glyphs, part_glyph.ctypes.data_as(_P),
+                                part_m.ctypes.data_as(_P), part[0].ctypes.data_as(_P), part[1].ctypes.data_as(_P),
+                                part[2].ctypes.data_as(_P), n_parts, C.byref(out)))
+    return _stroke_out(lib, out)
+
+
+def cff_block() -> int:
+    """Output segments per workgroup of the CFF outline kernel (svgr_cff_block)."""
+    return int(load_library().svgr_cff_block())
 
 
 def image_levels(h: int, w: int):

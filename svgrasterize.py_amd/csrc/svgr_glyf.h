@@ -160,33 +160,45 @@ struct GlyfTables {
     const char* why = "";
 };
 
+// What the outline passes of both formats (svgr_cff.h too) check of the offsets and the parts: SVGR_OK, SVGR_E_INVALID or
+// SVGR_E_OVERFLOW (why says which).  No array is read beyond the counts given.
+inline int glyf_check(int64_t n_points, const int32_t* contour_off, int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs,
+                      const int32_t* part_glyph, const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy,
+                      int64_t n_parts, const char*& why) {
+    if (n_points < 0 || n_contours < 0 || n_glyphs < 0 || n_parts < 0 || !contour_off || !glyph_contour_off ||
+        (n_parts > 0 && (!part_glyph || !part_m || !part_pen || !part_sx || !part_sy))) {
+        why = "bad arguments";
+        return SVGR_E_INVALID;
+    }
+    if (n_points > GLYF_COUNT_MAX || n_contours > GLYF_COUNT_MAX || n_glyphs > GLYF_COUNT_MAX || n_parts > GLYF_COUNT_MAX) {
+        why = "a count does not fit 32 bits";
+        return SVGR_E_OVERFLOW;
+    }
+    if (contour_off[0] != 0 || glyph_contour_off[0] != 0) { why = "offsets that do not begin at 0"; return SVGR_E_INVALID; }
+    for (int64_t c = 0; c < n_contours; ++c)
+        if (contour_off[c + 1] < contour_off[c]) { why = "contour offsets that decrease"; return SVGR_E_INVALID; }
+    if (contour_off[n_contours] != n_points) { why = "contour offsets that do not end at the point count"; return SVGR_E_INVALID; }
+    for (int64_t g = 0; g < n_glyphs; ++g)
+        if (glyph_contour_off[g + 1] < glyph_contour_off[g]) { why = "glyph offsets that decrease"; return SVGR_E_INVALID; }
+    if (glyph_contour_off[n_glyphs] != n_contours) { why = "glyph offsets that do not end at the contour count"; return SVGR_E_INVALID; }
+    for (int64_t k = 0; k < n_parts; ++k) {
+        if (part_glyph[k] < 0 || part_glyph[k] >= n_glyphs) { why = "a part's glyph id out of range"; return SVGR_E_INVALID; }
+        bool ok = std::fabs(part_pen[k]) <= GLYF_VALUE_MAX && std::fabs(part_sx[k]) <= GLYF_VALUE_MAX && std::fabs(part_sy[k]) <= GLYF_VALUE_MAX;
+        for (int e = 0; e < 6; ++e) ok = ok && std::fabs(part_m[6 * k + e]) <= GLYF_VALUE_MAX;
+        if (!ok) { why = "a matrix, pen or scale that is not finite or beyond 1e150"; return SVGR_E_INVALID; }
+    }
+    return SVGR_OK;
+}
+
 // SVGR_OK, SVGR_E_INVALID or SVGR_E_OVERFLOW (t.why says which).  No array is read beyond the counts given, and none is
 // indexed by a value that has not been checked.
 inline int glyf_tables(const uint8_t* pt_on, int64_t n_points, const int32_t* contour_off, int64_t n_contours,
                        const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph, const double* part_m,
                        const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts, GlyfTables& t) {
-    if (n_points < 0 || n_contours < 0 || n_glyphs < 0 || n_parts < 0 || !contour_off || !glyph_contour_off ||
-        (n_points > 0 && !pt_on) || (n_parts > 0 && (!part_glyph || !part_m || !part_pen || !part_sx || !part_sy))) {
-        t.why = "bad arguments";
-        return SVGR_E_INVALID;
-    }
-    if (n_points > GLYF_COUNT_MAX || n_contours > GLYF_COUNT_MAX || n_glyphs > GLYF_COUNT_MAX || n_parts > GLYF_COUNT_MAX) {
-        t.why = "a count does not fit 32 bits";
-        return SVGR_E_OVERFLOW;
-    }
-    if (contour_off[0] != 0 || glyph_contour_off[0] != 0) { t.why = "offsets that do not begin at 0"; return SVGR_E_INVALID; }
-    for (int64_t c = 0; c < n_contours; ++c)
-        if (contour_off[c + 1] < contour_off[c]) { t.why = "contour offsets that decrease"; return SVGR_E_INVALID; }
-    if (contour_off[n_contours] != n_points) { t.why = "contour offsets that do not end at the point count"; return SVGR_E_INVALID; }
-    for (int64_t g = 0; g < n_glyphs; ++g)
-        if (glyph_contour_off[g + 1] < glyph_contour_off[g]) { t.why = "glyph offsets that decrease"; return SVGR_E_INVALID; }
-    if (glyph_contour_off[n_glyphs] != n_contours) { t.why = "glyph offsets that do not end at the contour count"; return SVGR_E_INVALID; }
-    for (int64_t k = 0; k < n_parts; ++k) {
-        if (part_glyph[k] < 0 || part_glyph[k] >= n_glyphs) { t.why = "a part's glyph id out of range"; return SVGR_E_INVALID; }
-        bool ok = std::fabs(part_pen[k]) <= GLYF_VALUE_MAX && std::fabs(part_sx[k]) <= GLYF_VALUE_MAX && std::fabs(part_sy[k]) <= GLYF_VALUE_MAX;
-        for (int e = 0; e < 6; ++e) ok = ok && std::fabs(part_m[6 * k + e]) <= GLYF_VALUE_MAX;
-        if (!ok) { t.why = "a matrix, pen or scale that is not finite or beyond 1e150"; return SVGR_E_INVALID; }
-    }
+    if (n_points > 0 && !pt_on) { t.why = "bad arguments"; return SVGR_E_INVALID; }
+    if (int rc = glyf_check(n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m, part_pen, part_sx, part_sy,
+                            n_parts, t.why))
+        return rc;
     // the slot of every point and the segment count of every contour: the flags alone decide
     t.pt_slot.assign((size_t)n_points, 0);
     t.contour_segs.assign((size_t)n_contours, 0);

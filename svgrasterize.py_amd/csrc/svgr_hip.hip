@@ -8604,3 +8604,104 @@ int svgr_gvar_deltas(svgr_ctx* ctx, const int16_t* pt_xy, int64_t n_points, cons
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// OpenType / CFF outlines: the contours of Type 2 charstrings as the lines and cubics of a path (svgr_cff_outline).  The
+// per-lane arithmetic and the host's validation walk are svgr_cff.h; DESIGN.md 7m has the definitions.
+//
+//   k_cff_emit   one lane per OUTPUT segment: its part by binary search in the host-built prefix sums of the parts' segment
+//                counts, its atlas segment, the 2 or 4 double points that segment reads, one type and one row of 8 doubles --
+//                a wave's stores are one contiguous run
+// Which points emit is a glyph constant the host made while it checked the input; stores are disjoint and no atomic takes part
+// (the `bad` flag is a plain store of the same value by every writer).  No LDS.  All geometry is f64.
+// ======================================================================================
+#include "svgr_cff.h"
+
+constexpr int CFF_B = 256;   // output segments (= lanes) per workgroup
+#define CFF_KERNEL __global__ __launch_bounds__(CFF_B) __attribute__((section(".text.svgr_cff")))
+
+CFF_KERNEL void k_cff_emit(CffView v, int* __restrict__ types, double* __restrict__ params, int* __restrict__ bad) {
+    const int j = blockIdx.x * CFF_B + threadIdx.x;
+    if (j >= v.n_out) return;
+    if (!cff_emit(v, j, types, params)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
+}
+
+static int cff_outline_impl(svgr_ctx* ctx, const double* pt_xy, const uint8_t* pt_kind, int64_t n_points, const int32_t* contour_off,
+                            int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph,
+                            const double* part_m, const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts,
+                            svgr_stroke_out** out) {
+    if (!out) return fail(SVGR_E_INVALID, "svgr_cff_outline: bad arguments");
+    CffTables t;
+    if (int rc = cff_tables(pt_xy, pt_kind, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m, part_pen,
+                            part_sx, part_sy, n_parts, t))
+        return fail(rc, "svgr_cff_outline: %s", t.why);
+    std::unique_ptr<svgr_stroke_out> res(new svgr_stroke_out());
+    const int n_out = t.part_seg_off[(size_t)n_parts];
+    if (n_out == 0) {   // no part, parts of empty glyphs, or contours of a lone MOVE only
+        *out = res.release();
+        return 0;
+    }
+    if (!ctx) return fail(SVGR_E_INVALID, "svgr_cff_outline: no context");
+    // ---- one upload: the atlas with its segment tables, the parts with their prefix sums
+    const int np = (int)n_parts, npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs, ns = (int)t.seg_ref.size();
+    const size_t i_kind = pad64((size_t)npt * 16), i_ref = i_kind + pad64((size_t)npt), i_gseg = i_ref + pad64((size_t)ns * 4);
+    const size_t i_coff = i_gseg + pad64((size_t)(ng + 1) * 4), i_pglyph = i_coff + pad64((size_t)(nc + 1) * 4);
+    const size_t i_pseg = i_pglyph + pad64((size_t)np * 4), i_m = i_pseg + pad64((size_t)(np + 1) * 4);
+    const size_t i_pen = i_m + pad64((size_t)np * 48), i_sx = i_pen + pad64((size_t)np * 8), i_sy = i_sx + pad64((size_t)np * 8);
+    const size_t i_end = i_sy + pad64((size_t)np * 8);
+    std::vector<char> blob(i_end);
+    memcpy(blob.data(), pt_xy, (size_t)npt * 16);
+    memcpy(blob.data() + i_kind, pt_kind, (size_t)npt);
+    memcpy(blob.data() + i_ref, t.seg_ref.data(), (size_t)ns * 4);
+    memcpy(blob.data() + i_gseg, t.glyph_seg_off.data(), (size_t)(ng + 1) * 4);
+    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
+    memcpy(blob.data() + i_pglyph, part_glyph, (size_t)np * 4);
+    memcpy(blob.data() + i_pseg, t.part_seg_off.data(), (size_t)(np + 1) * 4);
+    memcpy(blob.data() + i_m, part_m, (size_t)np * 48);
+    memcpy(blob.data() + i_pen, part_pen, (size_t)np * 8);
+    memcpy(blob.data() + i_sx, part_sx, (size_t)np * 8);
+    memcpy(blob.data() + i_sy, part_sy, (size_t)np * 8);
+
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    // the result block: params, types, the kernel's error flag
+    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 64;
+    std::vector<char> back(o_end);
+    PoolBlock in, outb;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(in.alloc(blob.size(), ctx->device));
+    HIPCHK(outb.alloc(o_end, ctx->device));
+    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const char* d_in = in.as<char>();
+    int* d_bad = (int*)(outb.as<char>() + o_bad);
+    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
+    const CffView view{(const double*)d_in, (const uint8_t*)(d_in + i_kind), (const int*)(d_in + i_ref), (const int*)(d_in + i_gseg),
+                       (const int*)(d_in + i_coff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_pseg), (const double*)(d_in + i_m),
+                       (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy), nc, np, npt, ns, n_out};
+    SVGR_LAUNCH(k_cff_emit, grid1((size_t)n_out, CFF_B), dim3(CFF_B), 0, st, view, (int*)(outb.as<char>() + o_types), outb.as<double>(),
+                d_bad);
+    HIPCHK(hipGetLastError());
+    // ---- one download
+    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int bad = 0;
+    memcpy(&bad, back.data() + o_bad, 4);
+    if (bad) return fail(SVGR_E_STATE, "svgr_cff_outline: a lane met an index outside its tables");
+    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
+    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    res->sizes = std::move(t.sizes);
+    *out = res.release();
+    return 0;
+}
+
+extern "C" {
+int svgr_cff_block(void) { return CFF_B; }
+int svgr_cff_outline(svgr_ctx* ctx, const double* pt_xy, const uint8_t* pt_kind, int64_t n_points, const int32_t* contour_off,
+                     int64_t n_contours, const int32_t* glyph_contour_off, int64_t n_glyphs, const int32_t* part_glyph, const double* part_m,
+                     const double* part_pen, const double* part_sx, const double* part_sy, int64_t n_parts, svgr_stroke_out** out) {
+    return abi_guard("svgr_cff_outline", [&]() {
+        return cff_outline_impl(ctx, pt_xy, pt_kind, n_points, contour_off, n_contours, glyph_contour_off, n_glyphs, part_glyph, part_m,
+                                part_pen, part_sx, part_sy, n_parts, out);
+    });
+}
+}  // extern "C"

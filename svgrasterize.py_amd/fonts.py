@@ -3,8 +3,9 @@
 Host code in front of the hot path: a string becomes one ``Path`` of glyph outlines, which is then filled / stroked like
 any other path.  ``Font`` is an SVG font (``<font>`` elements inside a document, or whole documents of them registered with
 ``FontsDB.register_file`` and loaded on first use) -- the only kind the reference has.  Beyond it, ``truetype.TrueTypeFont``
-is a ``Font`` read from a ``.ttf`` (``FontsDB.register_file`` of such a file, ``FontsDB.register_ttf``); other font formats
-(CFF / OpenType ``OTTO``, collections, WOFF) are refused.  Nothing looks for fonts on its own: no system directory is
+is a ``Font`` read from a ``.ttf`` (``FontsDB.register_file`` of such a file, ``FontsDB.register_ttf``) and
+``opentype_cff.CFFFont`` one read from an ``.otf`` with CFF outlines (``OTTO``; ``register_file``, ``FontsDB.register_font``); other
+font formats (collections, WOFF, CFF2) are refused.  Nothing looks for fonts on its own: no system directory is
 scanned and nothing is fetched, the caller says which files.
 """
 from __future__ import annotations
@@ -185,18 +186,24 @@ class FontsDB:
             self.fonts.setdefault(alias.lower(), []).append(font)
 
     def register_file(self, path: str) -> None:
-        """A font file, told by its first four bytes: a TrueType font is read now (``truetype.read_ttf``) and registered under
-        the family of its ``name`` table (without one: the file's name); ``OTTO`` / ``ttcf`` / ``wOFF`` / ``wOF2`` and a TrueType
-        file that is malformed or lacks a required table warn with the reason and are skipped (nothing is raised); anything else is an SVG document of ``<font>`` elements, remembered and loaded by the first
-        ``resolve``."""
-        from . import truetype  # noqa: PLC0415  (truetype.py imports this module)
+        """A font file, told by its first four bytes: a TrueType font (``truetype.read_ttf``) or an ``OTTO`` font with CFF outlines
+        (``opentype_cff.read_otf``) is read now and registered under the family of its ``name`` table (without one: the file's
+        name); ``ttcf`` / ``wOFF`` / ``wOF2`` and a TrueType or ``OTTO`` file that is malformed or lacks a required table warn with the
+        reason and are skipped (nothing is raised); anything else is an SVG document of ``<font>`` elements, remembered and loaded
+        by the first ``resolve``."""
+        from . import opentype_cff, truetype  # noqa: PLC0415  (both import this module)
 
         try:
             with open(path, "rb") as f:
                 head = f.read(4)
         except OSError:
             head = b""   # (the first `resolve` warns about a file that is not there)
-        if head in truetype.REFUSED:
+        if opentype_cff.is_cff(head):
+            try:
+                self.register(opentype_cff.read_otf_file(path))
+            except ValueError as why:   # (a malformed file, or an OTTO one without a CFF table)
+                warnings.warn(f"font file skipped: {path}: {why}")
+        elif head in truetype.REFUSED:
             warnings.warn(f"font file skipped: {path}: {truetype.REFUSED[head]}")
         elif truetype.is_truetype(head):
             try:
@@ -205,6 +212,30 @@ class FontsDB:
                 warnings.warn(f"font file skipped: {path}: {why}")
         else:
             self.fonts_files.append(path)
+
+    def register_font(self, data_or_path, family=None):
+        """Register a TrueType or an OpenType / CFF font, told by its first four bytes, from bytes in memory or from a file's
+        path, under `family` when given (an alias: the font's own family stays registered too), and return it."""
+        from . import opentype_cff  # noqa: PLC0415
+
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(data_or_path)
+            if not opentype_cff.is_cff(data):
+                return self.register_ttf(data, family)
+            font = opentype_cff.CFFFont(data)
+            if font.family is None:   # (a font that names no family takes the caller's)
+                if family is None:
+                    raise ValueError("opentype: the font names no family (name id 1): pass family=")
+                font.family = family
+        else:
+            path = os.fspath(data_or_path)
+            with open(path, "rb") as f:
+                head = f.read(4)
+            if not opentype_cff.is_cff(head):
+                return self.register_ttf(path, family)
+            font = opentype_cff.read_otf_file(path)
+        self.register(font, alias=family)
+        return font
 
     def register_ttf(self, data_or_path, family=None):
         """Register a TrueType font from bytes in memory or from a file's path, under `family` when given (an alias: the font's

@@ -244,8 +244,9 @@ class Scene(tuple):
     @classmethod
     def text(cls, font, size: float, string: str, attrs=None, shape=None) -> "Scene":
         """A straight run of `string` in `font` at `size` user units per em, its pen at the origin (beyond the reference; a
-        ``truetype.TrueTypeFont``): `attrs` and `shape` are ``textpath.TextOutline``'s.  Lazy, as `markers` is: the node becomes
-        the run's FILL / STROKE nodes when it is first drawn or walked, which makes the outline on the device."""
+        ``truetype.TrueTypeFont`` or an ``opentype_cff.CFFFont``): `attrs` and `shape` are ``textpath.TextOutline``'s.  Lazy, as
+        `markers` is: the node becomes the run's FILL / STROKE nodes when it is first drawn or walked, which makes the outline on
+        the device."""
         return cls(RENDER_MARKERS, TextOutline(font, size, string, attrs, shape))
 
     @classmethod

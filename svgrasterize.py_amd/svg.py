@@ -13,8 +13,8 @@ feComponentTransfer, feConvolveMatrix, feDisplacementMap, feDropShadow, feDiffus
 fePointLight / feSpotLight, feTile, feImage (a raster from <image>'s sources, or ``#id``: an element, looked up when the filter runs);
 the <filter>'s region for the generators and the lighting primitives; x / y / width / height on a primitive -- its subregion --
 and ``primitiveUnits``, see ``filters.py``), text / tspan set in
-SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``) or, beyond the reference, in TrueType fonts registered with
-the ``FontsDB`` (``truetype.py``: such a run becomes one lazy node whose outline is made on the device at the first render, its
+SVG fonts (font, font-face, glyph, missing-glyph, hkern; ``fonts.py``) or, beyond the reference, in TrueType or OpenType / CFF fonts registered with
+the ``FontsDB`` (``truetype.py``, ``opentype_cff.py``: such a run becomes one lazy node whose outline is made on the device at the first render, its
 advance is host arithmetic from ``hmtx`` / ``kern``; loading needs no device), presentation attributes and ``style``, and beyond the
 reference image (PNG or JPEG, from a base64 ``data:image/png`` / ``data:image/jpeg`` URI or a local file next to the document, the
 decoder picked by the data's first bytes; ``png.py``, ``jpeg.py``) and CSS
@@ -63,7 +63,7 @@ from .filters import (
     SpotLight, color_matrix_hue_rotate, color_matrix_saturate,
 )
 from .fonts import FONT_STYLE_NORMAL, Font, FontsDB, Glyph
-from .truetype import TrueTypeFont
+from .truetype import SfntFont
 from .geometry import (
     PATH_CLOSED, PATH_FILL_NONZERO, PATH_LINE, STROKE_CAP_BUTT, STROKE_JOIN_MITER, Path, Transform,
 )
@@ -1119,7 +1119,7 @@ class _Loader:
             font = self.fonts.resolve(attrs.get("font-family"), _font_weight(attrs.get("font-weight")), None, _font_variations(attrs))
             if font is None:
                 return [], (ox, oy), after_blank
-            if isinstance(font, TrueTypeFont):   # (the outline is made on the device, at the first render; the advance is host arithmetic)
+            if isinstance(font, SfntFont):   # (a TrueType or CFF face: the outline is made on the device, at the first render; the advance is host arithmetic)
                 advance = font.str_to_glyphs(words)[1] * (size / font.units_per_em)
                 node = Scene.text(font, size, words, dict(attrs), self.shape)
                 return [node.transform(Transform().translate(ox, oy))], (ox + advance, oy), blank

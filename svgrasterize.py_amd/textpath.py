@@ -4,7 +4,7 @@ run -- when it is first drawn or walked.  The glyphs are placed on the device (`
 svgr_path_place_glyphs) and a percentage ``startOffset`` needs the path's length (``Path.length``), so the node stays as it
 is until then: building one -- loading a document -- needs no device.  It rides in the node kind of the markers
 (``scene.RENDER_MARKERS``), whose payload only has to offer ``expand()``.  ``TextOutline`` is the same for a straight run set in a
-face whose outlines are made on the device (a TrueType font): the run's shapes, made at the first render."""
+face whose outlines are made on the device (a TrueType or OpenType / CFF font): the run's shapes, made at the first render."""
 from __future__ import annotations
 
 import threading
@@ -38,8 +38,8 @@ def _fill_shape(attrs, path) -> list:
 
 
 class TextOutline:
-    """Payload of a straight run of text whose outline is made on the device (``Scene.text``; a ``truetype.TrueTypeFont``'s
-    ``str_to_path``): `font`, `size` in user units per em, `text`, the attributes `attrs` its shape is made from and `shape`:
+    """Payload of a straight run of text whose outline is made on the device (``Scene.text``; the ``str_to_path`` of a
+    ``truetype.TrueTypeFont`` or an ``opentype_cff.CFFFont``, of any font for that matter): `font`, `size` in user units per em, `text`, the attributes `attrs` its shape is made from and `shape`:
     ``(attrs, Path) -> [Scene]`` (the loader's; without one a fill with ``attrs["fill"]``).  `expand()` makes the nodes once and
     keeps them in `scene` (None before, and for an empty outline)."""
 

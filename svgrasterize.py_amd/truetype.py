@@ -12,8 +12,9 @@ the last advance), ``cmap`` (formats 4 and 12; platform 3 encoding 10 before 3 /
 macStyle bit 1 make the style ``italic``; without the table the weight is 700 with macStyle bit 0, else 400) and ``kern``
 (format 0, horizontal, not cross-stream; optional).
 
-Refused with a ``ValueError`` that says which: ``OTTO`` (CFF outlines), ``ttcf`` collections, WOFF / WOFF2, a font without one of
-``head maxp hhea hmtx cmap loca glyf``.
+Refused with a ``ValueError`` that says which: ``ttcf`` collections, WOFF / WOFF2, a font without one of
+``head maxp hhea hmtx cmap loca glyf``, and, by ``read_ttf``, ``OTTO`` (CFF outlines: ``opentype_cff.read_otf`` reads those, and
+``read_font`` picks the reader by the first four bytes; the sfnt tables around the outlines are read by ``SfntFont`` here for both).
 
 Ignored: hinting (``fpgm``, ``prep``, ``cvt`` and the glyphs' instructions are skipped over, never interpreted), ``GSUB`` / ``GPOS``
 (no ligatures, no shaping, no GPOS kerning), vertical metrics, bitmaps and colour tables.  One glyph per character; a character the ``cmap`` does not map takes glyph 0 (``.notdef``).
@@ -50,8 +51,10 @@ from .geometry import Path
 
 FONT_STYLE_ITALIC = "italic"
 REQUIRED = ("head", "maxp", "hhea", "hmtx", "cmap", "loca", "glyf")
-REFUSED = {
-    b"OTTO": "OTTO: an OpenType font with CFF outlines, only TrueType (glyf) outlines are read",
+REQUIRED_CFF = ("head", "maxp", "hhea", "hmtx", "cmap")   # (and ``CFF ``, which opentype_cff.py asks for by name)
+SFNT_CFF = b"OTTO"
+REFUSED = {   # what `read_ttf` turns away by the first four bytes
+    b"OTTO": "OTTO: an OpenType font with CFF outlines, read_ttf reads TrueType (glyf) outlines only: read_otf / read_font read it",
     b"ttcf": "ttcf: a TrueType collection, only single fonts are read",
     b"wOFF": "wOFF: a WOFF container, only plain sfnt files are read",
     b"wOF2": "wOF2: a WOFF2 container, only plain sfnt files are read",
@@ -130,15 +133,39 @@ class TrueTypeGlyph(Glyph):
         return f"TrueTypeGlyph(unicode={self.unicode}, gid={self.gid})"
 
 
-class TrueTypeFont(Font):
-    """A face read from a ``.ttf`` (``read_ttf``).  `hkern` maps ``(left glyph id, right glyph id)`` to what is subtracted from
-    the pen, SVG's ``hkern k``: the negated value of the ``kern`` table."""
+class _reader:
+    """Around the shared sfnt reading of a format other than TrueType: a ``ValueError`` of the shared code path names that
+    format's reader (``opentype: head: ...``) in place of ``truetype:``.  `TrueTypeFont` does not use it: its messages are as
+    they were."""
 
-    __slots__ = ["data", "tables", "n_glyphs", "advances", "loca", "_cmap", "_simple", "_parts", "_by_gid", "_composite", "_warned_matching", "_var", "_instances"]
+    def __init__(self, prefix: str):
+        self.prefix = prefix
 
-    def __init__(self, data: bytes, family=None):
-        self.data = data = bytes(data)
-        self.tables = tables = _directory(data)
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, why, _trace):
+        if kind is ValueError:
+            text = str(why)
+            text = text[len("truetype:"):].lstrip() if text.startswith("truetype:") else text
+            raise ValueError(text if text.startswith(f"{self.prefix}:") else f"{self.prefix}: {text}") from None
+        return False
+
+
+class SfntFont(Font):
+    """What the two outline formats of an sfnt share (``TrueTypeFont``; ``opentype_cff.CFFFont``): the table directory and the
+    tables ``head``, ``maxp``, ``hhea`` + ``hmtx``, ``cmap``, ``name``, ``OS/2`` and ``kern``, read by one code path -- a format
+    other than TrueType reads them inside ``_reader(prefix)``, which puts its own reader's name in front of the messages --, and
+    the string measuring on top of them.  A subclass offers ``glyph_parts(gid)``
+    and ``outline(parts, sx, sy)``; `GLYPH` is the type of its glyph objects."""
+
+    __slots__ = ["data", "tables", "n_glyphs", "advances", "_cmap", "_by_gid"]
+    GLYPH = None
+
+    def _read_metrics(self, loca: bool):
+        """``head``, ``maxp``, ``hhea``, ``hmtx`` of `self.data` / `self.tables`: sets `n_glyphs` and `advances`, returns
+        (unitsPerEm, macStyle, indexToLocFormat, ascent, descent).  `loca`: the font has a ``loca`` table, whose format is checked."""
+        data, tables = self.data, self.tables
         head, length = tables["head"]
         _need(data, head, 54, "head")
         if length < 54:
@@ -148,9 +175,9 @@ class TrueTypeFont(Font):
         loc_format, = _unpack(">h", data, head + 50, "head")
         if units < 1:
             raise ValueError("truetype: head: unitsPerEm is 0")
-        if loc_format not in (0, 1):
+        if loca and loc_format not in (0, 1):
             raise ValueError(f"truetype: head: indexToLocFormat is {loc_format}")
-        self.n_glyphs, = _unpack(">H", data, _table(tables, "maxp", 6) + 4, "maxp")
+        self.n_glyphs, = _unpack(">H", data, _table(tables, "maxp", 6) + 4, "maxp")   # (version 0.5, of a CFF font, has 6 bytes)
         if self.n_glyphs < 1:
             raise ValueError("truetype: maxp: the font has no glyph")
         hhea = _table(tables, "hhea", 36)
@@ -160,6 +187,89 @@ class TrueTypeFont(Font):
             raise ValueError("truetype: hhea: numberOfHMetrics is 0")
         hmtx = _table(tables, "hmtx", 4 * n_metrics)
         self.advances = _array(data, ">u2", hmtx, 2 * n_metrics, "hmtx")[0::2].astype(np.int64)
+        return units, mac_style, loc_format, ascent, descent
+
+    def _read_naming(self, family, units, mac_style, ascent, descent) -> None:
+        """``cmap``, ``OS/2``, ``name``, ``kern``, and with them ``Font.__init__``."""
+        data, tables = self.data, self.tables
+        self._cmap = _read_cmap(data, *tables["cmap"])
+        weight, italic = (700 if mac_style & 1 else 400), bool(mac_style & 2)
+        if "OS/2" in tables:
+            os2 = _table(tables, "OS/2", 64)
+            weight = _unpack(">H", data, os2 + 4, "OS/2")[0] or 400
+            italic = italic or bool(_unpack(">H", data, os2 + 62, "OS/2")[0] & 1)
+        if family is None and "name" in tables:
+            family = _read_family(data, *tables["name"])
+        kern = _read_kern(data, *tables["kern"]) if "kern" in tables else {}
+        Font.__init__(self, family, weight, FONT_STYLE_ITALIC if italic else FONT_STYLE_NORMAL, float(ascent), float(descent), float(units),
+                      hkern={pair: -float(value) for pair, value in kern.items()})
+        self._by_gid = {}
+
+    # -- cmap, metrics -------------------------------------------------------------------------------------------------
+    def glyph_id(self, code: int) -> int:
+        """The glyph of a character code; 0 (``.notdef``) when the cmap has none or names a glyph the font has not."""
+        gid = self._cmap.lookup(code)
+        return gid if 0 <= gid < self.n_glyphs else 0
+
+    def cmap(self) -> dict:
+        """``{character code: glyph id}`` of every mapped code (glyph 0 left out)."""
+        out = {}
+        for code in self._cmap.codes():
+            gid = self.glyph_id(code)
+            if gid:
+                out[code] = gid
+        return out
+
+    def advance(self, gid: int) -> float:
+        return float(self.advances[min(gid, len(self.advances) - 1)])
+
+    def glyph(self, gid: int, char=None):
+        glyph = self._by_gid.get(gid)
+        if glyph is None:
+            glyph = self._by_gid[gid] = self.GLYPH(self, gid, char, self.advance(gid))
+            if char is not None:
+                self.glyphs[char] = glyph
+        return glyph
+
+    def names(self) -> dict:
+        return {g.name: g.unicode for g in self._by_gid.values()}
+
+    def str_to_glyphs(self, string: str):
+        """``([(pen x, glyph)], total advance)`` in font units: one glyph per character through the cmap, ``kern`` pairs by glyph
+        id subtracted from the pen before the right glyph is placed.  Host arithmetic."""
+        placed, pen, prev = [], 0.0, None
+        for char in string:
+            gid = self.glyph_id(ord(char))
+            glyph = self.glyph(gid, char if gid else None)
+            if prev is not None:
+                kern = self.hkern.get((prev, gid))
+                if kern is not None:
+                    pen -= kern
+            placed.append((pen, glyph))
+            pen += glyph.advance
+            prev = gid
+        return placed, pen
+
+    def str_to_path(self, size: float, string: str):
+        """Outline of ``string`` at ``size`` user units per em, y flipped to the SVG's y-down: ``(Path, advance)``.  Eager, on the
+        device: the parts of all glyphs go through the format's outline pass in one call, with sx = scale and sy = -scale."""
+        scale = size / self.units_per_em
+        placed, advance = self.str_to_glyphs(string)
+        parts = [(part, pen) for pen, glyph in placed for part in glyph.parts]
+        return Path.from_segments(*self.outline(parts, scale, -scale)), advance * scale
+
+
+class TrueTypeFont(SfntFont):
+    """A face read from a ``.ttf`` (``read_ttf``).  `hkern` maps ``(left glyph id, right glyph id)`` to what is subtracted from
+    the pen, SVG's ``hkern k``: the negated value of the ``kern`` table."""
+
+    __slots__ = ["loca", "_simple", "_parts", "_composite", "_warned_matching", "_var", "_instances"]
+    GLYPH = TrueTypeGlyph
+
+    def __init__(self, data: bytes, family=None):
+        self.data = data = bytes(data)
+        self.tables = tables = _directory(data)
+        units, mac_style, loc_format, ascent, descent = self._read_metrics(loca=True)
         loca_off, loca_len = tables["loca"]
         glyf_len = tables["glyf"][1]
         if loc_format == 0:
@@ -170,18 +280,8 @@ class TrueTypeFont(Font):
             self.loca = _array(data, ">u4", loca_off, self.n_glyphs + 1, "loca").astype(np.int64)
         if (np.diff(self.loca) < 0).any() or int(self.loca[-1]) > glyf_len:
             raise ValueError("truetype: loca: the offsets decrease or leave the glyf table")
-        self._cmap = _read_cmap(data, *tables["cmap"])
-        weight, italic = (700 if mac_style & 1 else 400), bool(mac_style & 2)
-        if "OS/2" in tables:
-            os2 = _table(tables, "OS/2", 64)
-            weight = _unpack(">H", data, os2 + 4, "OS/2")[0] or 400
-            italic = italic or bool(_unpack(">H", data, os2 + 62, "OS/2")[0] & 1)
-        if family is None and "name" in tables:
-            family = _read_family(data, *tables["name"])
-        kern = _read_kern(data, *tables["kern"]) if "kern" in tables else {}
-        super().__init__(family, weight, FONT_STYLE_ITALIC if italic else FONT_STYLE_NORMAL, float(ascent), float(descent), float(units),
-                         hkern={pair: -float(value) for pair, value in kern.items()})
-        self._simple, self._parts, self._by_gid, self._composite = {}, {}, {}, {}
+        self._read_naming(family, units, mac_style, ascent, descent)
+        self._simple, self._parts, self._composite = {}, {}, {}
         self._warned_matching = False
         self.missing_glyph = self.glyph(0, None)
         from . import truetype_var  # noqa: PLC0415  (truetype_var.py imports this module)
@@ -223,59 +323,6 @@ class TrueTypeFont(Font):
         """The points ``gvar`` numbers in a glyph: the points of a simple glyph, the components of a composite one."""
         components = self._components(gid)
         return len(self.simple_glyph(gid).on) if components is None else len(components)
-
-    # -- cmap, metrics -------------------------------------------------------------------------------------------------
-    def glyph_id(self, code: int) -> int:
-        """The glyph of a character code; 0 (``.notdef``) when the cmap has none or names a glyph the font has not."""
-        gid = self._cmap.lookup(code)
-        return gid if 0 <= gid < self.n_glyphs else 0
-
-    def cmap(self) -> dict:
-        """``{character code: glyph id}`` of every mapped code (glyph 0 left out)."""
-        out = {}
-        for code in self._cmap.codes():
-            gid = self.glyph_id(code)
-            if gid:
-                out[code] = gid
-        return out
-
-    def advance(self, gid: int) -> float:
-        return float(self.advances[min(gid, len(self.advances) - 1)])
-
-    def glyph(self, gid: int, char=None) -> TrueTypeGlyph:
-        glyph = self._by_gid.get(gid)
-        if glyph is None:
-            glyph = self._by_gid[gid] = TrueTypeGlyph(self, gid, char, self.advance(gid))
-            if char is not None:
-                self.glyphs[char] = glyph
-        return glyph
-
-    def names(self) -> dict:
-        return {g.name: g.unicode for g in self._by_gid.values()}
-
-    def str_to_glyphs(self, string: str):
-        """``([(pen x, glyph)], total advance)`` in font units: one glyph per character through the cmap, ``kern`` pairs by glyph
-        id subtracted from the pen before the right glyph is placed.  Host arithmetic."""
-        placed, pen, prev = [], 0.0, None
-        for char in string:
-            gid = self.glyph_id(ord(char))
-            glyph = self.glyph(gid, char if gid else None)
-            if prev is not None:
-                kern = self.hkern.get((prev, gid))
-                if kern is not None:
-                    pen -= kern
-            placed.append((pen, glyph))
-            pen += glyph.advance
-            prev = gid
-        return placed, pen
-
-    def str_to_path(self, size: float, string: str):
-        """Outline of ``string`` at ``size`` user units per em, y flipped to the SVG's y-down: ``(Path, advance)``.  Eager, on the
-        device: the parts of all glyphs go through svgr_glyf_outline in one call, with sx = scale and sy = -scale."""
-        scale = size / self.units_per_em
-        placed, advance = self.str_to_glyphs(string)
-        parts = [(part, pen) for pen, glyph in placed for part in glyph.parts]
-        return Path.from_segments(*self.outline(parts, scale, -scale)), advance * scale
 
     def outline(self, parts, sx: float, sy: float):
         """(types, params (n, 8), sizes) of `parts`, ``[((simple glyph id, m00, m01, m10, m11, dx, dy), pen)]``, through the device."""
@@ -458,14 +505,18 @@ class _TooDeep(Exception):
 # ----------------------------------------------------------------------------------------------------------------------
 # tables
 # ----------------------------------------------------------------------------------------------------------------------
-def _directory(data: bytes) -> dict:
-    """``{tag: (offset, length)}`` of an sfnt with TrueType outlines, every table inside the data."""
+def _directory(data: bytes, cff: bool = False) -> dict:
+    """``{tag: (offset, length)}`` of an sfnt with TrueType outlines -- with `cff`, of an ``OTTO`` one, whose outline tables the
+    caller asks for itself --, every table inside the data."""
     if len(data) < 4:
         raise ValueError("truetype: the data is shorter than an sfnt version")
     version = data[:4]
-    if version in REFUSED:
+    if cff:
+        if version != SFNT_CFF:
+            raise ValueError(f"opentype: not an OpenType font with CFF outlines (the data begins with {version!r}, not b'OTTO')")
+    elif version in REFUSED:
         raise ValueError(f"truetype: {REFUSED[version]}")
-    if version not in SFNT_TRUETYPE:
+    elif version not in SFNT_TRUETYPE:
         raise ValueError(f"truetype: not a TrueType font (the data begins with {version!r})")
     n_tables, = _unpack(">H", data, 4, "table directory")
     _need(data, 12, 16 * n_tables, "table directory")
@@ -474,7 +525,7 @@ def _directory(data: bytes) -> dict:
         tag, _checksum, off, length = struct.unpack_from(">4sIII", data, 12 + 16 * i)
         _need(data, off, length, f"table {tag!r}")
         tables.setdefault(tag.decode("latin-1"), (off, length))
-    missing = [tag for tag in REQUIRED if tag not in tables]
+    missing = [tag for tag in (REQUIRED_CFF if cff else REQUIRED) if tag not in tables]
     if missing:
         raise ValueError(f"truetype: the font has no {' / '.join(missing)} table")
     return tables
