@@ -22,7 +22,7 @@
 //                   {offset in the tile's delta tile, value}, so that the tile kernel's scatter is one load + one LDS add
 //   k_tile_lists    per band: bitmasks -> per-tile item lists (cell ids in paint order, each with its add list), the
 //                   tiles in heaviest-first order, one PAGE per tile (which tile + its first 24 items: one load);
-//                   clears the bitmasks for the next render
+//                   clears the bitmasks for the next render; in a placed replay a band whose bitmasks repeat keeps its lists
 //   k_tile_render   one 128-thread workgroup per 16x64 canvas tile, canvas tile resident in registers as
 //                   double RGBA; per item in paint order: header and add list prefetched into registers items ahead;
 //                   the adds of item k+1 go into one LDS delta tile (ds_add_f64) while item k's is scanned
@@ -689,7 +689,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
             n_found = 1;
             if (n_plan >= 1 && base_p < edge_cap) {
                 store_edge(edges, base_p, node[0], node[1], node[6], node[7]);
-                edge_path[base_p] = p;
+                if (edge_path) edge_path[base_p] = p;   // (null in a replay: the plan's pass has written it)
             }
         } else if (mode == 2) {
             track(node[0], node[1]);
@@ -698,7 +698,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
                 track(r1, c1);
                 if (at < n_plan && base_p + at < edge_cap) {
                     store_edge(edges, base_p + at, r0_, c0_, r1, c1);
-                    edge_path[base_p + at] = p;
+                    if (edge_path) edge_path[base_p + at] = p;
                 }
                 ++at;
             }, ovf);
@@ -1171,25 +1171,6 @@ __global__ __launch_bounds__(64) void k_path_bbox(const unsigned long long* __re
         pbin.b0 = pb0; pbin.nb = pnb; pbin.pb_off = off; pbin.cell_off = cell_off;
         bins[p] = pbin;
     }
-}
-
-// shared by count and emit so both take identical decisions
-__device__ __forceinline__ bool edge_prepare(const double* __restrict__ edges, const int* __restrict__ edge_path,
-                                             const int* __restrict__ bbox, int e, EdgeSetup& es, int& p, int& r0) {
-    p = edge_path[e];
-    const int4 bb = ((const int4*)bbox)[p];
-    r0 = bb.x;
-    const int rows = bb.z, cols = bb.w;
-    if (rows <= 0 || cols <= 0) return false;
-    const double o_r = (double)bb.x, o_c = (double)bb.y;  // `lines - [min_x, min_y]` (S:979)
-    const double* ed = edges + 4 * (size_t)e;
-    double ar = ed[0] - o_r, ac = ed[1] - o_c, br = ed[2] - o_r, bc = ed[3] - o_c;
-    es = edge_setup(ar, ac, br, bc, rows);
-    if (!es.valid) return false;
-    // an edge whose every column is beyond the layer never stores anything (S:2260, S:2274)
-    double cmin = ac < bc ? ac : bc;
-    if (cmin >= (double)cols + 2.0) return false;
-    return true;
 }
 
 // rows of an edge inside band `band` (layer-local [ya, yb))
@@ -2112,7 +2093,8 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
                                                          int mask_words, int n_ct, int vc0, Owner own, int n_owned,
                                                          int2* __restrict__ tile_info, uint4* __restrict__ pages,
                                                          uint4* __restrict__ items, const CellHdr* __restrict__ cell_hdr, int item_cap, int cell_cap,
-                                                         BatchDev* __restrict__ bd, const PathBin* __restrict__ bins, const int* __restrict__ bbox) {
+                                                         BatchDev* __restrict__ bd, const PathBin* __restrict__ bins, const int* __restrict__ bbox,
+                                                         unsigned long long* __restrict__ tile_mask_kept, int kept) {
     constexpr int NWV = TL_BLOCK / 64;
     __shared__ int s_base[TL_BLOCK + 1], s_rank[TL_BLOCK];
     __shared__ int s_hist[64], s_cur[64], s_wtot[NWV];
@@ -2120,8 +2102,49 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int band = owned_band_at(own, blockIdx.x);
     const int W = mask_words;
-    const int ent0 = band_start[band], item_band0 = band_item0[band];
     unsigned long long* const mband = tile_mask + (size_t)band * n_ct * 2 * W;
+    // `tile_mask_kept` (a placed replay that keeps its lists): the band's mask words as they stood when the lists now in place were
+    // made -- the full path below saves them just before it clears them.  `kept`: those lists ARE in place (the host's record,
+    // svgr_batch::lists_current).  Everything else an item is made of -- cell id, add place, add count -- is the plan's, checked by
+    // k_path_build<1> (error bit 32), so a band whose words repeat would rewrite, item by item, what stands there: one round of
+    // loads, both arrays asked for together, the words cleared, done.  A band with any other word is listed again as if entered here.
+    unsigned long long* const kband = tile_mask_kept ? tile_mask_kept + (size_t)band * n_ct * 2 * W : nullptr;
+    if (kept) {
+        __shared__ int s_wdiff[NWV];
+        auto any_differs = [&](bool d) {   // (one barrier: a flag per wave, every lane ORs the sixteen)
+            const bool wd = __ballot(d) != 0ull;
+            if (lane == 0) s_wdiff[wave] = wd ? 1 : 0;
+            __syncthreads();
+            int a = 0;
+#pragma unroll
+            for (int w = 0; w < NWV; ++w) a |= s_wdiff[w];
+            return a != 0;
+        };
+        unsigned long long diff = 0ull;
+        if (W == 1 && n_ct <= TL_BLOCK) {
+            ulonglong2 m = make_ulonglong2(0ull, 0ull), k = m;
+            if (tid < n_ct) { m = ((const ulonglong2*)mband)[tid]; k = ((const ulonglong2*)kband)[tid]; }
+            diff = (m.x ^ k.x) | (m.y ^ k.y);
+            if (!any_differs(diff != 0ull)) {
+                if ((m.x | m.y) != 0ull) ((ulonglong2*)mband)[tid] = make_ulonglong2(0ull, 0ull);
+                return;
+            }
+        } else {
+            for (int ct = tid; ct < n_ct; ct += TL_BLOCK) {
+                const unsigned long long* mw = mband + (size_t)ct * 2 * W;
+                const unsigned long long* kw = kband + (size_t)ct * 2 * W;
+                for (int w = 0; w < 2 * W; ++w) diff |= mw[w] ^ kw[w];
+            }
+            if (!any_differs(diff != 0ull)) {
+                for (int ct = tid; ct < n_ct; ct += TL_BLOCK) {
+                    unsigned long long* mw = mband + (size_t)ct * 2 * W;
+                    for (int w = 0; w < 2 * W; ++w) mw[w] = 0ull;
+                }
+                return;
+            }
+        }
+    }
+    const int ent0 = band_start[band], item_band0 = band_item0[band];
     auto count_tile = [&](int ct, int& n, int& n2) {
         n = 0; n2 = 0;
         const unsigned long long* mw = mband + (size_t)ct * 2 * W;
@@ -2232,6 +2255,10 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
         if (tid == 0) s_run = run0 + total;
         if (ct < n_ct) {  // this tile has listed everything: its words are cleared for the next render's atomicOr
             unsigned long long* mw = mband + (size_t)ct * 2 * W;
+            if (kband) {  // (what these lists were made from: the next replay compares against it)
+                unsigned long long* kw = kband + (size_t)ct * 2 * W;
+                for (int w = 0; w < 2 * W; ++w) kw[w] = mw[w];
+            }
             for (int w = 0; w < 2 * W; ++w) mw[w] = 0ull;
         }
         __syncthreads();
@@ -4586,7 +4613,7 @@ struct svgr_batch {
     DevArr<int2> cell_plan;                 // ... and where its add list lives: {first add, pieces}, left by the plan's full pass (k_path_build)
     bool add_places = false;                // `cell_plan` holds the places of the current plan: the renders take them (k_path_build<1>)
     // a pass that ended with an error flag may have left any of the self-cleaning buffers dirty
-    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; }
+    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; lists_current = false; }
     DevArr<TileAdd> adds;                   // the cells' add lists (k_path_build: a slab reserves its cells' lists in one piece)
     DevArr<uint4> items;                    // the tiles' item lists: {cell id | class << 30, first add, adds, 0} (k_tile_lists)
     DevArr<int2> tile_info;                 // per (band, column tile): {first item, items}
@@ -4642,6 +4669,27 @@ struct svgr_batch {
                    vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
         }
     } slabs_made{};
+    // The same for what k_tile_lists leaves (`items`, `pages`, `tile_info`): a placed replay that keeps its slab table would list, band
+    // by band, what the previous one listed unless a band's mask words differ -- and the kernel compares them against `tile_mask_kept`,
+    // the words its last full run saved.  Set by a full run that saved them, for what `lists_made` records; cleared wherever the
+    // plan or the slab table is, by every pass that stops short of the lists, lists the bands again (k_band_entries) or builds the
+    // cells by another k_path_build than <1>.  Passes that only read the lists (windows, the other outputs) leave it alone.
+    bool lists_current = false;
+    struct ListsMade {
+        const void *items, *pages, *tile_info, *entries, *bins, *bbox, *cell_hdr, *cell_plan, *tile_mask, *tile_mask_kept;
+        size_t items_cap, pages_cap, tile_info_cap, entries_cap, bins_cap, bbox_cap, cell_hdr_cap, cell_plan_cap, tile_mask_cap, tile_mask_kept_cap;
+        int n_ctiles, mask_words, owned;
+        int vp[4];
+        bool operator==(const ListsMade& o) const {
+            return items == o.items && pages == o.pages && tile_info == o.tile_info && entries == o.entries && bins == o.bins && bbox == o.bbox &&
+                   cell_hdr == o.cell_hdr && cell_plan == o.cell_plan && tile_mask == o.tile_mask && tile_mask_kept == o.tile_mask_kept &&
+                   items_cap == o.items_cap && pages_cap == o.pages_cap && tile_info_cap == o.tile_info_cap && entries_cap == o.entries_cap &&
+                   bins_cap == o.bins_cap && bbox_cap == o.bbox_cap && cell_hdr_cap == o.cell_hdr_cap && cell_plan_cap == o.cell_plan_cap &&
+                   tile_mask_cap == o.tile_mask_cap && tile_mask_kept_cap == o.tile_mask_kept_cap && n_ctiles == o.n_ctiles &&
+                   mask_words == o.mask_words && owned == o.owned && vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
+        }
+    } lists_made{};
+    unsigned long long stale_word = 0ull;   // SVGR_DBG_STALE_BAND: source of the one-word upload (alive until the stream has taken it)
     bool slab_order_pending = false;        // svgr_batch_draw planned this batch and left the slab order to the first render that replays the plan
     std::vector<int> slab_at_host;
     int64_t n_slabs = 0;                    // ... the plan's count = the launch's grid
@@ -4654,6 +4702,7 @@ struct svgr_batch {
     DevArr<int> path_list;                  // ... and the paths they belong to, ascending: what k_path_bbox / k_band_entries walk
     int64_t n_path_list = 0;
     DevArr<unsigned long long> tile_mask;   // per (band, column tile): 2 x mask_words words over the band's list (k_path_build)
+    DevArr<unsigned long long> tile_mask_kept;   // same layout: the words the lists in place were made from (k_tile_lists, placed replays)
     int mask_words = 1;
     bool masks_zeroed = false;              // the last tile kernel left the masks cleared
     DevArr<long long> layer_off;            // SVGR_OUT_MASKS_F64: per path the start of its mask in the output
@@ -4687,6 +4736,8 @@ struct svgr_batch {
     int size_masks(int64_t longest) {
         mask_words = (int)std::max<int64_t>((longest + 63) / 64, 1);
         masks_zeroed = false;
+        lists_current = false;
+        if (int rc = tile_mask_kept.ensure(mask_bytes() / sizeof(unsigned long long) + 1)) return rc;
         return tile_mask.ensure(mask_bytes() / sizeof(unsigned long long) + 1);
     }
     // Two sets of device scalars at the head of the arena: the passes and the renders count into the first (its first word is the
@@ -4741,10 +4792,10 @@ struct WorkSpare {
     DevArr<TileAdd> adds;
     DevArr<uint4> items, pages;
     DevArr<Slab> slabs;
-    DevArr<unsigned long long> tile_mask;
+    DevArr<unsigned long long> tile_mask, tile_mask_kept;
 };
 #define SVGR_SPARE_ARRAYS(X) X(edge_path) X(band_start) X(band_count) X(pair_idx) X(slab_at) X(seg_cnt) X(seg_off) X(lane_off) X(band_item0) \
-    X(entries) X(edges) X(cell_hdr) X(work_block) X(cell_plan) X(tile_info) X(adds) X(items) X(pages) X(slabs) X(tile_mask)
+    X(entries) X(edges) X(cell_hdr) X(work_block) X(cell_plan) X(tile_info) X(adds) X(items) X(pages) X(slabs) X(tile_mask) X(tile_mask_kept)
 // a destroyed batch leaves its work arrays to its context (large planned batches with a viewport on one GPU only)
 static void spare_stash(svgr_batch* b) {
     svgr_ctx* c = b->ctx;
@@ -4773,7 +4824,7 @@ static bool spare_adopt(svgr_batch* b) {
     b->mask_words = w->mask_words; b->add_shards = w->add_shards; b->n_adds = w->n_adds; b->adds_roomy = w->adds_roomy;
     b->n_bands = (b->vp[2] + TR - 1) / TR;
     b->masks_zeroed = false;   // (whatever the last render of the old batch left: cleared again)
-    b->slab_at_valid = false; b->slabs_current = false;
+    b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false;
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     return true;
@@ -4794,6 +4845,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     const int ns = (int)b->n_segs, np = (int)b->n_paths;
     if (!b->arena_zeroed) HIPCHK(hipMemsetAsync(b->arena.p, 0, b->arena_bytes, st));
     b->arena_zeroed = false;  // (the kernels below count into it)
+    if (upto < 4) b->lists_current = false;   // (a pass that stops short of the tile lists leaves other geometry under them)
     // multi-GPU with a viewport: the plan listed the segments of the paths whose rows can reach this rank's bands
     // (build_seg_list); a pass without such a list finds the reach itself and lets the flatten skip foreign paths
     const bool listed = use_vp && b->own.world > 1 && b->n_seg_list >= 0;
@@ -4836,7 +4888,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         if (upto == 1 && !b->late_scan)
             SVGR_LAUNCH(k_seg_scan, dim3(1), dim3(1024), 0, st, (const int*)b->seg_cnt.p, ns, b->seg_off.p);
         if (upto == 0 || (upto == 1 && b->census_bbox)) {  // bboxes only (no edges stored): the union when there is no viewport; the two-pass plan's census
-            b->slabs_current = false;
+            b->slabs_current = false; b->lists_current = false;
             SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(),
                                np_walk, use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), 1, plist,
                                (Slab*)nullptr, 0, b->own, (const int*)nullptr, (const int*)nullptr, 0, (const int*)nullptr);
@@ -4846,10 +4898,13 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     if (ns > 0) {
         // (the counting pass that made `seg_off` left every lane's place inside its segment's slots beside it)
         const bool lane_places = !b->safe_path;
+        // (`edge_path` says which path an edge belongs to -- svgr_batch_get_edges is its only reader -- and under a standing plan's lane
+        //  places the pass that made the plan has written it, slot by slot, with what this one would store: a placed replay does not)
+        const bool keep_edge_path = b->planned && lane_places && b->lane_off.p && b->lane_off.cap >= ((size_t)ns << fl_sub) && !b->fl_scan;
         auto launch_fl = [&](auto kern, int* places) {
             SVGR_LAUNCH(kern, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p,
                                (const uint8_t*)b->seg_kind.p, (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr,
-                               b->edges.p, b->edge_path.p, b->shards, b->pkeys(), b->bd(), b->own, b->vp[0],
+                               b->edges.p, keep_edge_path ? (int*)nullptr : b->edge_path.p, b->shards, b->pkeys(), b->bd(), b->own, b->vp[0],
                                n_bands_vp, prow, seg_list, n_items, (int*)nullptr, (const int*)b->seg_off.p,
                                cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4)), places, (int*)nullptr, (unsigned long long*)nullptr);
         };
@@ -4898,6 +4953,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     const int owned = count_owned_bands(b->own, b->n_bands);
     // (upto >= 4 on one GPU: the kernel also clears the tiles' entry bitmasks of its band when they are not clear yet)
     const bool clear_in_be = owned > 0 && !keep_lists && upto >= 4 && !b->masks_zeroed && b->tile_mask.p && b->own.world <= 1;
+    if (!keep_lists) b->lists_current = false;   // (the bands are listed again: the tile lists in place follow the old band lists)
     if (owned > 0 && !keep_lists)
         SVGR_LAUNCH(k_band_entries, dim3(owned), dim3(BE_BLOCK), 0, st, (const PathBin*)b->bins.p, np_walk, plist,
                            (const int*)b->bbox.p, b->band_start.p, b->band_count.p, b->band_item0.p, b->entries.p,
@@ -4922,6 +4978,17 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         pb_dbg = buf;
     }
 #endif
+    // A placed replay that keeps its band lists and writes or keeps the plan's slab table lists every band from the plan's places and
+    // its own mask words alone: its full k_tile_lists saves the words (`tile_mask_kept`), and the replay behind it -- slab table kept,
+    // the same arrays (`lists_made`) -- asks the kernel to list only the bands whose words differ from the saved ones.
+    const size_t mask_n = b->mask_bytes() / sizeof(unsigned long long);
+    const bool lists_for_plan = slabs_for_plan && placed && owned > 0 && b->n_ctiles() > 0 && b->tile_mask.p && b->tile_mask_kept.p &&
+                                b->tile_mask.cap >= mask_n && b->tile_mask_kept.cap >= mask_n;
+    const svgr_batch::ListsMade lists_now{b->items.p, b->pages.p, b->tile_info.p, b->entries.p, b->bins.p, b->bbox.p, b->cell_hdr.p, b->cell_plan.p,
+                                          b->tile_mask.p, b->tile_mask_kept.p, b->items.cap, b->pages.cap, b->tile_info.cap, b->entries.cap,
+                                          b->bins.cap, b->bbox.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask.cap, b->tile_mask_kept.cap,
+                                          b->n_ctiles(), b->mask_words, owned, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]}};
+    const bool lists_kept = lists_for_plan && keep_slabs && b->lists_current && b->lists_made == lists_now;
     if (b->n_slabs > 0) {
         b->masks_zeroed = false;  // (bits are set below; k_tile_lists clears them again)
         auto launch_pb = [&](auto kern) {
@@ -4937,8 +5004,10 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         // (an unplanned pass over add lists sized with room to spare: ONE pass on the workgroup's own bounds, MODE 2)
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
         if (getenv("SVGR_DBG_PLAN"))   // (diagnostic: which instantiation this pass launches, and whether it found the slab table in place)
-            fprintf(stderr, "[geometry] k_path_build<%d>%s, %lld slabs, slab table %s\n", placed ? 1 : bounded ? 2 : 0,
-                    b->count_adds_only ? " measuring" : "", (long long)b->n_slabs, keep_slabs ? "kept" : "written");
+            fprintf(stderr, "[geometry] k_path_build<%d>%s, %lld slabs, tile lists %s, slab table %s\n", placed ? 1 : bounded ? 2 : 0,
+                    b->count_adds_only ? " measuring" : "", (long long)b->n_slabs,
+                    lists_kept ? "kept" : "rebuilt" /* (what k_tile_lists is asked for: a band whose words differ is listed again on the device) */,
+                    keep_slabs ? "kept" : "written");
         if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
 #ifdef SVGR_DBG_PB_STAMP
         if (pb_dbg && b->planned && !b->count_adds_only) {
@@ -4966,12 +5035,26 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     }
     // per owned band: the tiles' item lists and the launch order of the tile kernel; clears the bitmasks again
     if (owned > 0 && b->n_ctiles() > 0) {
+        if (lists_kept)
+            if (const char* sb = getenv("SVGR_DBG_STALE_BAND")) {   // (tests: one saved word of band `sb` made wrong -- that band, and no other, is listed again)
+                const int band = atoi(sb);
+                if (band >= 0 && band < b->n_bands) {
+                    unsigned long long* const w0 = b->tile_mask_kept.p + (size_t)band * b->n_ctiles() * 2 * b->mask_words;
+                    HIPCHK(hipMemcpyAsync(&b->stale_word, w0, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
+                    b->stale_word ^= 1ull;
+                    HIPCHK(hipMemcpyAsync(w0, &b->stale_word, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+                }
+            }
         SVGR_LAUNCH(k_tile_lists, dim3(owned), dim3(TL_BLOCK), 0, st, (const int*)b->band_start.p, (const int*)b->band_item0.p,
                            (const TileEntry*)b->entries.p, b->tile_mask.p, b->mask_words, b->n_ctiles(), b->vp[1], b->own, owned,
                            b->tile_info.p, b->pages.p, b->items.p, (const CellHdr*)b->cell_hdr.p, cap_i32(b->items.cap), cap_i32(b->cell_hdr.cap), b->bd(),
-                           keep_lists ? (const PathBin*)b->bins.p : (const PathBin*)nullptr, (const int*)b->bbox.p);
+                           keep_lists ? (const PathBin*)b->bins.p : (const PathBin*)nullptr, (const int*)b->bbox.p,
+                           lists_for_plan ? b->tile_mask_kept.p : (unsigned long long*)nullptr, lists_kept ? 1 : 0);
         b->masks_zeroed = true;
     }
+    b->lists_current = lists_for_plan;
+    b->lists_made = lists_now;
     return 0;
 }
 
@@ -5627,14 +5710,14 @@ int svgr_batch_set_transforms(svgr_batch* b, const double* path_m6) {
         HIPCHK(hipMemcpyAsync(b->path_m6.p, b->keep(path_m6, mbytes), mbytes, hipMemcpyHostToDevice, b->ctx->stream));
         HIPCHK(b->note_upload(b->ctx->stream));
     }
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
     return 0;
 }
 
 int svgr_batch_set_bands(svgr_batch* b, int rank, int world, int strip_bands) {
     if (!b || world <= 0 || rank < 0 || rank >= world || strip_bands <= 0) return fail(SVGR_E_INVALID, "bad band selection");
     b->own = Owner{rank, world, strip_bands};
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;  // the edge / record capacities are per rank
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;  // the edge / record capacities are per rank
     b->sized = false;
     b->n_seg_list = -1;  // ... and so is the list of segments to flatten
     return 0;
@@ -5901,7 +5984,7 @@ static int plan_speculative(svgr_batch* b) {
             if (int rc = plan_slab_order(b)) return rc;   // (large batches: k_path_build's work list heaviest first)
         }
         if (fin != 0) return fin;
-        b->planned = false; b->slabs_current = false;
+        b->planned = false; b->slabs_current = false; b->lists_current = false;
     }
     return 0;
 }
@@ -5989,7 +6072,7 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
         for (int64_t i = 0; i < n; ++i) {
             svgr_batch* b = batches[i];
             HIPCHK(enter_ctx(b->ctx));
-            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
             b->geometry_fresh = false; b->geometry_current = false;
             const int is = no_spec ? 0 : spec_issue(b, (char*)b->ctx->pinned + stage_off[(size_t)i]);
             if (is < 0) return is;
@@ -6023,7 +6106,7 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
 // integer arithmetic on the same bbox (slab_shape, owns_any), so the places tile the list exactly; the geometry cannot change
 // under a plan (set_transforms / set_bands invalidate it).
 static int plan_slab_order(svgr_batch* b) {
-    b->slab_at_valid = false; b->slabs_current = false;
+    b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false;
     b->slab_order_late = false;   // (the render that makes the order itself sets it behind this call)
     if (getenv("SVGR_SAFE_PATH")) return 0;  // (tests: the renders then take their slab places from the cursor, in arrival order)
     const size_t np = (size_t)b->n_paths;
@@ -6170,6 +6253,7 @@ static int two_pass_issue(svgr_batch* b, void* staging) {
     }
     b->mask_words = (int)std::max<int64_t>(((int64_t)std::max(longest, 1) + 63) / 64, 1);
     b->masks_zeroed = false;
+    b->lists_current = false;
     {
         // every work array of the batch out of ONE device block (each with the eighth of slack an allocation of its own would
         // have: a re-plan of a drawing that moved a little fits the same arrays, spec_issue(again))
@@ -6189,6 +6273,7 @@ static int two_pass_issue(svgr_batch* b, void* staging) {
             c.take(b->entries, n_pairs);
             c.take(b->pair_idx, n_pairs);
             c.take(b->tile_mask, b->mask_bytes() / sizeof(unsigned long long) + 1);
+            c.take(b->tile_mask_kept, b->mask_bytes() / sizeof(unsigned long long) + 1);
             c.take(b->tile_info, n_tiles);
             c.take(b->pages, owned * (size_t)std::max(b->n_ctiles(), 1) * PAGE_STRIDE);
             c.take(b->items, n_c);
@@ -6199,7 +6284,7 @@ static int two_pass_issue(svgr_batch* b, void* staging) {
         // (the arrays may be views of an earlier block of this batch: let go of them before the block)
         b->edges.release(); b->edge_path.release(); b->band_start.release(); b->band_count.release(); b->band_item0.release();
         b->cell_hdr.release(); b->cell_plan.release(); b->slabs.release(); b->entries.release(); b->pair_idx.release();
-        b->tile_mask.release(); b->tile_info.release(); b->pages.release(); b->items.release(); b->adds.release();
+        b->tile_mask.release(); b->tile_mask_kept.release(); b->tile_info.release(); b->pages.release(); b->items.release(); b->adds.release();
         b->work_block.release();
         if ((rc = b->work_block.ensure(sizing.at))) return rc;
         Carver carve;
@@ -6254,7 +6339,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
     if (!b) return fail(SVGR_E_INVALID, "batch is NULL");
     HIPCHK(enter_ctx(b->ctx));
     b->defer_bbox = false;
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
     b->geometry_fresh = false; b->geometry_current = false;
     {
         const bool no_spec = getenv("SVGR_NO_SPECULATIVE_PLAN") != nullptr;  // (tests exercise both planners)
@@ -6266,7 +6351,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
         const int tp = plan_two_pass(b);
         if (tp < 0) return tp;
         if (tp > 0) return 0;
-        b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+        b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
         b->geometry_fresh = false; b->geometry_current = false;
     }
     if (int rc = b->layout_arena()) return rc;
@@ -6773,7 +6858,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
         if (fast) {
             const size_t stage_bytes = sizeof(BatchDev) + 16 * (size_t)b->n_paths + 256;
             if (int rc = ensure_pinned(b->ctx, stage_bytes)) return rc;
-            b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+            b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
             b->geometry_fresh = false; b->geometry_current = false;
             b->defer_bbox = true;                                       // (the bboxes stay on the device until somebody asks: ensure_host_bbox)
             int is = spec_issue(b, b->ctx->pinned, true);                 // (the buffers of the batch's last plan as the guesses)
@@ -6791,7 +6876,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
             // the tile kernel right behind the pass: the batch counts as planned with that pass's geometry until the pass is validated
             b->planned = true; b->geometry_fresh = true; b->geometry_current = true;
             int rc = batch_render_impl(b, out, out_kind, flags, nullptr);
-            b->planned = false; b->slabs_current = false; b->geometry_fresh = false; b->geometry_current = false;
+            b->planned = false; b->slabs_current = false; b->lists_current = false; b->geometry_fresh = false; b->geometry_current = false;
             hipError_t e = hipStreamSynchronize(st);
             if (rc) return rc;
             HIPCHK(e);
@@ -6805,7 +6890,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
                 b->slab_order_pending = b->n_segs > 4096;   // (large batches: k_path_build's work list heaviest first, as svgr_batch_plan leaves it)
                 return 0;
             }
-            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->slab_order_pending = false;
+            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
         }
         if (int rc = batch_plan_impl(b, issued == 1)) return rc;
     }
