@@ -435,8 +435,8 @@ int svgr_gradient_fill(svgr_ctx* ctx, const svgr_gradient* g, const svgr_buf* ma
  * svgr_batch_plan.  The fills of a document then need no Path.mask + svgr_gradient_fill + Layer.compose round trip each. */
 int svgr_batch_set_gradients(svgr_batch* batch, const int32_t* path_grad, int64_t n_grads, const svgr_gradient* grads);
 /* GradLinear.fill / GradRadial.fill (S:1553-1563, S:1577-1651): the gradient at n_points caller-supplied coordinates
- * (x, y doubles interleaved; user space, i.e. what Path.fill passes after its own user transform: set user_m6 to the
- * identity), no mask; out_rgba receives n_points x 4 doubles.                                                     */
+ * (x, y doubles interleaved; user space, i.e. what Path.fill passes after its own user transform: user_m6 is not
+ * applied, so that infinite coordinates arrive as given), no mask; out_rgba receives n_points x 4 doubles.        */
 int svgr_gradient_eval(svgr_ctx* ctx, const svgr_gradient* g, const svgr_buf* points, int64_t n_points, svgr_buf* out_rgba);
 
 /* Path.fill, pattern branch (S:1049-1094): out_rgba = pattern tile looked up per pixel * mask.  `tile` is the

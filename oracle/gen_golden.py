@@ -1143,6 +1143,63 @@ def gen_gradlong(ref) -> None:
     save("gradlong_kat.npz", **out)
 
 
+def save_reproducible(name: str, **arrays) -> None:
+    """`save` with nothing of the moment in the file: np.savez stamps every member with the time of writing, so two runs
+    never give the same bytes.  The members in the order given, each dated 1980-01-01, deflated."""
+    import io
+    import zipfile
+
+    path = os.path.join(GOLD, name)
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+    print(f"  wrote {name}: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
+def gen_gradedge(ref) -> None:
+    """The gradient edge cases of tests/grad_cases.py (stops, spread periods, the focal form's all-or-nothing mask) as the
+    reference answers them: Grad*.fill on the listed points in both colour spaces (S:1553 / S:1577), Path.fill on the listed
+    pixel grids (S:1021-1047).  Arrays and a JSON `meta` only; the inputs are the case list's, pinned by a digest each."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests import grad_cases as gc
+
+    out, meta, lins, srgbs = {}, dict(points=[], grid=[]), [], []
+    with np.errstate(all="ignore"):   # (the non-finite probes and the a == 0 / r == 0 forms divide by zero on purpose)
+        for i, c in enumerate(gc.POINT_CASES):
+            paint = gc.make_paint(ref, c["geom"], gc.stops_at(c["stops"]), c["spread"])
+            pts = np.array(c["pts"], dtype=np.float64)
+            lin, srgb = paint.fill(pts, linear_rgb=True), paint.fill(pts, linear_rgb=False)
+            assert np.isfinite(lin).all() and np.isfinite(srgb).all(), c["name"]
+            lins.append(lin)
+            srgbs.append(srgb)
+            meta["points"].append(dict(name=c["name"], n=len(pts), digest=gc.digest(c)))
+        # (one array per colour space, the cases one after the other: 123 cases as members of their own cost more than their data)
+        out["points_lin"], out["points_srgb"] = np.concatenate(lins), np.concatenate(srgbs)
+        for i, c in enumerate(gc.GRID_CASES):
+            paint = gc.make_paint(ref, c["geom"], gc.stops_at(c["stops"]), c["spread"])
+            layer, _hull = ref.Path.from_svg(c["path"]).fill(gc.make_transform(ref, c["tr"]), paint, viewport=c["viewport"],
+                                                             linear_rgb=c["linear_rgb"])
+            assert np.isfinite(layer.image).all() and layer.image.shape[0] * layer.image.shape[1] < 20000, c["name"]
+            out[f"g{i}_image"] = layer.image
+            # the second leaf of the group the batched route is drawn as: a solid fill that shares no pixel with the gradient's layer
+            solid, _hull = ref.Path.from_svg(c["solid"]).fill(gc.make_transform(ref, c["tr"]), np.array(gc.SOLID_PAINT), viewport=c["viewport"],
+                                                              linear_rgb=c["linear_rgb"])
+            (r0, c0), (r1, c1) = layer.offset, solid.offset
+            apart = (r0 + layer.image.shape[0] <= r1 or r1 + solid.image.shape[0] <= r0 or c0 + layer.image.shape[1] <= c1 or
+                     c1 + solid.image.shape[1] <= c0)
+            assert apart and (solid.image[..., 3] > 0).any(), c["name"]
+            out[f"s{i}_image"] = solid.image
+            meta["grid"].append(dict(name=c["name"], offset=[int(v) for v in layer.offset], shape=list(layer.image.shape[:2]),
+                                     solid_offset=[int(v) for v in solid.offset], linear_rgb=bool(layer.linear_rgb), digest=gc.digest(c)))
+    out["meta"] = np.array(json.dumps(meta))
+    save_reproducible("gradedge_kat.npz", **out)
+
+
 # --------------------------------------------------------------------------------------
 # S. the headline workload's generator, rendered by the reference itself (VERDICT r3 #6)
 # --------------------------------------------------------------------------------------
@@ -1217,6 +1274,8 @@ def main() -> None:
         gen_canvasfn(ref)
     if todo("gradlong"):
         gen_gradlong(ref)
+    if todo("gradedge"):
+        gen_gradedge(ref)
     if todo("gradient"):
         gen_gradient(ref)
     if todo("tiger"):

@@ -266,6 +266,14 @@ def gradient_image(kind, bbox, user_m, gt_m, spread, stop_off, stop_rgba, p0=Non
     px = _affine(user_m, px)
     if gt_m is not None:
         px = _affine(gt_m, px)  # the caller passes the INVERSE gradientTransform (S:1559 / S:1603)
+    return gradient_points(kind, px, spread, stop_off, stop_rgba, p0, p1, center, radius, fcenter, fradius)
+
+
+def gradient_offsets(kind, px, p0=None, p1=None, center=None, radius=None, fcenter=None, fradius=None):
+    """(offset, mask) of Grad*.fill (S:1561-1562 / S:1606-1607 / S:1619-1644) at the points `px` (..., 2), already in the
+    gradient's own space, before the spread.  `mask` is None unless some point of `px` has det < 0 (S:1627): the focal form's
+    mask is all or nothing over `px` as a whole."""
+    px = np.asarray(px, dtype=np.float64)
     mask = None
     if kind == "linear":
         vec = np.asarray(p1, float) - np.asarray(p0, float)
@@ -294,12 +302,25 @@ def gradient_image(kind, bbox, user_m, gt_m, spread, stop_off, stop_rgba, p0=Non
             offset = np.where(mask, off_all, 0.0)
             if fr != radius:
                 mask = mask & (offset > (fr / (fr - radius)))
+    return offset, mask
+
+
+def gradient_spread(offset, spread):
+    """grad_spread, S:1661-1668."""
     if spread == "repeat":
-        offset = np.modf(offset)[0]
-    elif spread == "reflect":
-        offset = np.fabs(np.remainder(offset + 1.0, 2.0) - 1.0)
-    elif spread != "pad":
+        return np.modf(offset)[0]
+    if spread == "reflect":
+        return np.fabs(np.remainder(offset + 1.0, 2.0) - 1.0)
+    if spread != "pad":
         raise ValueError(f"invalid spread method: {spread}")
+    return offset
+
+
+def gradient_points(kind, px, spread, stop_off, stop_rgba, p0=None, p1=None, center=None, radius=None, fcenter=None, fradius=None):
+    """Grad*.fill (S:1553-1563 / S:1577-1650) at the points `px` (..., 2): gradient_offsets, grad_spread (S:1661-1668) and
+    grad_interpolate (S:1671-1683), for stops already in the target colour space."""
+    offset, mask = gradient_offsets(kind, px, p0, p1, center, radius, fcenter, fradius)
+    offset = gradient_spread(offset, spread)
     out = np.zeros(offset.shape + (4,))
     out[offset <= stop_off[0]] = stop_rgba[0]
     out[offset > stop_off[-1]] = stop_rgba[-1]

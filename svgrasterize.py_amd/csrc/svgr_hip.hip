@@ -2285,16 +2285,16 @@ struct GradDev {
 // (S:1023-1027) and the gradient's own transform (S:1559 / S:1603), both in numpy's fma form
 __device__ __forceinline__ void grad_point(const GradDev& g, const double* __restrict__ pts, int i, int j, int r0, int c0, int cols,
                                            double& x, double& y) {
-    double px, py;
-    if (pts) {  // Grad*.fill on a caller's coordinate array (S:1553, S:1577): the points as given
+    if (pts) {  // Grad*.fill on a caller's coordinate array (S:1553, S:1577): the points as given -- the reference maps them by
+                // nothing but the gradient's own transform, and even an identity matrix makes NaN of an infinite coordinate (inf * 0)
         const size_t idx = (size_t)i * cols + j;
-        px = pts[2 * idx];
-        py = pts[2 * idx + 1];
+        x = pts[2 * idx];
+        y = pts[2 * idx + 1];
     } else {
-        px = (double)i + ((double)r0 + 0.5);
-        py = (double)j + ((double)c0 + 0.5);
+        const double px = (double)i + ((double)r0 + 0.5);
+        const double py = (double)j + ((double)c0 + 0.5);
+        xform_point(g.user_m6, px, py, x, y);
     }
-    xform_point(g.user_m6, px, py, x, y);
     if (g.has_gt) {
         double tx, ty;
         xform_point(g.gt_m6, x, y, tx, ty);
@@ -2337,8 +2337,8 @@ __device__ __forceinline__ void grad_colour_user(const GradDev& g, double x, dou
             if (use_mask && g.excl_enabled && !(offset > g.excl_thresh)) masked = true;  // negative r(t), S:1642-1644
         }
     }
-    if (g.spread == 1) {  // repeat: np.modf(offset)[0]
-        offset = offset - trunc(offset);
+    if (g.spread == 1) {  // repeat: np.modf(offset)[0], which is +-0 at +-inf (inf - trunc(inf) would be NaN: no stop at all)
+        offset = isinf(offset) ? copysign(0.0, offset) : offset - trunc(offset);
     } else if (g.spread == 2) {  // reflect
         double a1 = offset + 1.0;
         offset = fabs((a1 - 2.0 * floor(a1 * 0.5)) - 1.0);

@@ -16,27 +16,41 @@ from . import _abi
 _SPREAD = {"pad": 0, "repeat": 1, "reflect": 2}
 
 
-_STOPS_MEMO: dict = {}  # (id(stops), linear_rgb) -> (stops, converted): a gradient is usually filled many times
-_STOP_ARRAYS: dict = {}  # ... -> (stops, offsets array, colours array): what the ABI struct points at
+# (stops' contents, linear_rgb) -> (offsets array, colours array): what the ABI struct points at.  A gradient is usually filled many
+# times; keyed by VALUE (`stops_key`), because a stops list is the caller's to edit -- an entry replaced or a colour array written
+# in place is drawn with its new values by the next fill, as in the reference, which keeps nothing between fills.
+_STOP_ARRAYS: dict = {}
 _D6, _D2 = C.c_double * 6, C.c_double * 2
+
+
+def stops_key(stops) -> tuple:
+    """The contents of a stops list as a hashable value: the offsets and the bytes of the colours."""
+    return (tuple(float(o) for o, _ in stops), b"".join(np.asarray(c, dtype=np.float64).tobytes() for _, c in stops))
 
 
 def _stops_colorspace(stops, linear_rgb: bool):
     """grad_stops_colorspace, S:1686-1695: premultiplied linear RGBA stops -> target colour space."""
     from .geometry import solid_paint
 
-    key = (id(stops), bool(linear_rgb))
-    hit = _STOPS_MEMO.get(key)
-    if hit is not None and hit[0] is stops:
-        return hit[1]
-    out = [(float(o), solid_paint(np.asarray(c, dtype=np.float64), linear_rgb)) for o, c in stops]
-    if len(_STOPS_MEMO) > 4096:
-        _STOPS_MEMO.clear()
-    _STOPS_MEMO[key] = (stops, out)
-    return out
+    return [(float(o), solid_paint(np.asarray(c, dtype=np.float64), linear_rgb)) for o, c in stops]
 
 
 class _GradMixin:
+    def content_key(self) -> tuple:
+        """Everything `abi` reads from this paint, by value: what a memo of its ABI description is checked against before it
+        is used again (the fields hold arrays and a list that their owner may edit in place)."""
+        out = []
+        for name, val in zip(self._fields, self):
+            if name == "stops":
+                out.append(stops_key(val))
+            elif name == "transform":
+                out.append(None if val is None else val.key())
+            elif isinstance(val, (np.ndarray, list, tuple)):
+                out.append(np.asarray(val, dtype=np.float64).tobytes())
+            else:
+                out.append(val)
+        return tuple(out)
+
     def _common(self, g: "_abi.Gradient", user_tr, linear_rgb: bool):
         if self.spread not in _SPREAD:
             raise ValueError(f"invalid spread method: {self.spread}")
@@ -45,19 +59,20 @@ class _GradMixin:
         if self.transform is not None:
             g.has_gt = 1
             g.gt_m6 = _D6(*np.asarray(self.transform.invert.m, dtype=np.float64)[:2].ravel().tolist())
-        key = (id(self.stops), bool(linear_rgb))
+        key = (stops_key(self.stops), bool(linear_rgb))
         hit = _STOP_ARRAYS.get(key)
-        if hit is not None and hit[0] is self.stops:
-            _stops, off, col = hit
+        if hit is not None:
+            off, col = hit
         else:
             stops = _stops_colorspace(self.stops, linear_rgb)
             if not stops:
                 raise ValueError("a gradient needs at least one stop")
             off = np.ascontiguousarray([o for o, _ in stops], dtype=np.float64)
             col = np.ascontiguousarray([c for _, c in stops], dtype=np.float64).reshape(-1, 4)
+            off.flags.writeable = col.flags.writeable = False   # (shared by every fill with these stops)
             if len(_STOP_ARRAYS) > 4096:
                 _STOP_ARRAYS.clear()
-            _STOP_ARRAYS[key] = (self.stops, off, col)
+            _STOP_ARRAYS[key] = (off, col)
         g.n_stops = len(off)
         g.stop_off = _abi.ptr(off)
         g.stop_rgba = _abi.ptr(col)

@@ -1001,7 +1001,7 @@ _ONES = np.ones(4)
 _ZERO4 = np.zeros(4)
 _ZERO4.flags.writeable = False   # (the paint of every clip source)
 _PAUSE_GC = __import__("os").environ.get("SVGR_PAUSE_GC") is not None  # (set: the cyclic collector pauses for the duration of a top-level Scene.render)
-_GRAD_ABI_MEMO: dict = {}  # (id(gradient), transform bytes, linear_rgb) -> (gradient, svgr_gradient struct, keep-alive)
+_GRAD_ABI_MEMO: dict = {}  # (id(gradient), transform bytes, linear_rgb) -> (gradient, svgr_gradient struct, keep-alive, content key)
 
 
 def _leaf(path, m6, rule, paint4, flags=0, group=None, grad=None):
@@ -1034,13 +1034,14 @@ def _gradient_leaf(path, paint, rule, transform: Transform, linear_rgb: bool, op
     # by Batch.set_gradients, never written to)
     key = (id(paint), transform.key(), bool(linear_rgb))
     hit = _GRAD_ABI_MEMO.get(key)
-    if hit is not None and hit[0] is paint:
+    content = paint.content_key()   # (its arrays and its stops list are the caller's to edit in place: compared before reuse)
+    if hit is not None and hit[0] is paint and hit[3] == content:
         g, keep = hit[1], hit[2]
     else:
         g, keep = paint.abi(transform.invert, linear_rgb)
         if len(_GRAD_ABI_MEMO) > 8192:
             _GRAD_ABI_MEMO.clear()
-        _GRAD_ABI_MEMO[key] = (paint, g, keep)
+        _GRAD_ABI_MEMO[key] = (paint, g, keep, content)
     mult = _ONES if opacity is None else _ONES * opacity  # Layer.opacity over the leaf: image * opacity (S:174)
     return _leaf(path, transform.m6(), _RULES[rule], mult, grad=(g, keep, paint, transform, bool(linear_rgb)))
 
@@ -1396,9 +1397,10 @@ def build_batch(leaves, viewport, ctx=None, row_shift=None) -> "_abi.Batch":
                     _g0, _k0, paint, transform, lin = grad
                     pkey = (id(paint), transform.key(), lin, "stand-in")
                     hit = _GRAD_ABI_MEMO.get(pkey)
-                    if hit is None or hit[0] is not paint:
+                    content = paint.content_key()
+                    if hit is None or hit[0] is not paint or hit[3] != content:
                         g, keep = paint.abi(transform.invert, lin)
-                        _GRAD_ABI_MEMO[pkey] = hit = (paint, g, keep)
+                        _GRAD_ABI_MEMO[pkey] = hit = (paint, g, keep, content)
                     pending.append((len(grads), i, paint, transform, lin, shift))
                     grad = (hit[1], hit[2])
                 elif shift:
