@@ -42,7 +42,8 @@ extern "C" {
  *    svgr_png_unfilter added (SVG <image>, beyond the reference); svgr_layer_lighting added (feDiffuseLighting,
  *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode); svgr_jpeg_entropy and
  *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile); svgr_jpeg_encode,
- *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output) */
+ *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output); svgr_png_filter, svgr_deflate and
+ *    svgr_deflate_chunk added (the device PNG encoder) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -778,6 +779,38 @@ int svgr_jpeg_entropy_encode(const svgr_jpeg_scan* scan, const uint8_t* huff_cou
 /* svgr_jpeg_symbol_counts (host only): how often the same walk uses each symbol, for tables made to measure: counts[8][256],
  * DC tables 0-3 then AC tables 0-3 as the scan assigns them to its components; the caller zeroes it (counts add up over calls). */
 int svgr_jpeg_symbol_counts(const svgr_jpeg_scan* scan, const int16_t* coef, int64_t n_coef, int64_t* counts);
+
+/* PNG output on the device (Layer.write_png(encoder="device")): the scanline filters and the deflate stream of an 8-bit RGBA
+ * image; the caller writes the container (signature, IHDR, IDAT, IEND, the CRCs).
+ * svgr_png_filter: out_filtered (device, rows * (1 + 4 * cols) bytes) <- the filtered scanlines of src_rgba8 (device, rows *
+ * cols * 4 bytes as svgr_layer_to_rgba8 writes them): per row the filter type, then its bytes under PNG 1.2 section 6 (Sub,
+ * Up, Average, Paeth with the tie order a, b, c, modulo 256; the row above row 0 and the pixel left of column 0 are zero).
+ * `filter` forces one type, or SVGR_PNG_FILTER_ADAPTIVE chooses per row by libpng's heuristic: the type whose filtered bytes have
+ * the smallest sum of min(v, 256 - v), a tie going to the lower type.  Enqueued on the context's stream, no wait.
+ * SVGR_E_INVALID for an empty or oversized image, an unknown filter, a short buffer, or out_filtered == src_rgba8.             */
+#define SVGR_PNG_FILTER_NONE 0
+#define SVGR_PNG_FILTER_SUB 1
+#define SVGR_PNG_FILTER_UP 2
+#define SVGR_PNG_FILTER_AVERAGE 3
+#define SVGR_PNG_FILTER_PAETH 4
+#define SVGR_PNG_FILTER_ADAPTIVE 5
+int svgr_png_filter(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, int filter, svgr_buf* out_filtered);
+/* svgr_deflate: a complete zlib stream (78 01, the deflate blocks, Adler-32) of the first n_bytes of src (device) into out (host).
+ * The input is cut into chunks of svgr_deflate_chunk() bytes, one workgroup and one block each; matches reach back across the
+ * chunks (distance <= 32768) and are cut at their chunk's end; every chunk but the last ends with an empty stored block, so a
+ * chunk begins on a byte boundary.  One code pair serves the whole stream: SVGR_DEFLATE_DYNAMIC counts the symbols on the device,
+ * builds length-limited codes on the host (one round trip of 316 counts) and repeats the block header in every chunk;
+ * SVGR_DEFLATE_FIXED uses the fixed code of RFC 1951.  Every code written is complete.  The tokens, and so the bytes, are defined
+ * sequentially (csrc/svgr_deflate.h) and identical from run to run.  n_bytes == 0 is valid (src may then hold nothing).  At most
+ * out_cap bytes are written to out; *n_out always receives the stream's full length, and the status is SVGR_DEFLATE_NO_ROOM when
+ * that is more than out_cap (nothing is written then).  SVGR_E_INVALID for a negative or oversized (> 5 GiB) n_bytes, a short
+ * src or an unknown mode.  Waits for the device.
+ * svgr_deflate_chunk: the bytes of one chunk (the launch seam of the deflate kernels).                                          */
+#define SVGR_DEFLATE_FIXED 0
+#define SVGR_DEFLATE_DYNAMIC 1
+#define SVGR_DEFLATE_NO_ROOM 5   /* the output buffer is too small */
+int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out);
+int svgr_deflate_chunk(void);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,9 @@ _PROTOS = {
     "svgr_jpeg_encode": (C.c_int, [_P, C.POINTER(JpegFrame), _P, _P, _P, C.c_int64]),
     "svgr_jpeg_entropy_encode": (C.c_int, [C.POINTER(JpegScan), _P, _P, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "svgr_jpeg_symbol_counts": (C.c_int, [C.POINTER(JpegScan), _P, C.c_int64, _P]),
+    "svgr_png_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
+    "svgr_deflate": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "svgr_deflate_chunk": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -982,3 +985,45 @@ def jpeg_symbol_counts(scan: JpegScan, coef: np.ndarray) -> np.ndarray:
     if load_library().svgr_jpeg_symbol_counts(C.byref(scan), ptr(coef), coef.size, ptr(counts)):
         raise ValueError("a scan description that does not fit the frame, or a value no baseline table can code")
     return counts
+
+
+DEFLATE_NO_ROOM = 5   # SVGR_DEFLATE_NO_ROOM
+
+
+def deflate_chunk() -> int:
+    """Bytes per chunk (= per workgroup and per block of the stream) of the deflate kernels (svgr_deflate_chunk)."""
+    return int(load_library().svgr_deflate_chunk())
+
+
+def png_filter(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, filter: int) -> DeviceBuffer:
+    """svgr_png_filter: the filtered scanlines (rows * (1 + 4 * cols) bytes, on the device) of the RGBA8 bytes in `rgba8`;
+    `filter` is a type 0-4 or 5 for the adaptive choice."""
+    out = ctx.alloc(max(rows, 1) * (1 + 4 * max(cols, 1)))
+    _check(ctx.lib.svgr_png_filter(ctx.handle, rgba8.handle, rows, cols, filter, out.handle))
+    return out
+
+
+def deflate_once(ctx: Context, src: DeviceBuffer, n_bytes: int, huffman: int, out_cap: int):
+    """One svgr_deflate call with room for `out_cap` bytes: ``(status, length needed, bytes written)``; the status is 0 or
+    DEFLATE_NO_ROOM (nothing is written then)."""
+    n = C.c_int64()
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    rc = ctx.lib.svgr_deflate(ctx.handle, src.handle, n_bytes, huffman, ptr(out), out_cap, C.byref(n))
+    if rc not in (0, DEFLATE_NO_ROOM):
+        _check(rc)
+    return rc, int(n.value), out[:n.value if rc == 0 else 0].tobytes()
+
+
+def deflate(ctx: Context, src: DeviceBuffer, n_bytes: int, huffman: int) -> bytes:
+    """svgr_deflate: the zlib stream of the first `n_bytes` of `src`."""
+    n = C.c_int64()
+    # (9 bits per byte at the worst plus a header per chunk: untouched pages of the array cost nothing, a second call would
+    #  compress everything again; the call reports what it needs all the same)
+    out = np.empty(n_bytes + n_bytes // 4 + 4096, dtype=np.uint8)
+    for _ in range(2):
+        rc = ctx.lib.svgr_deflate(ctx.handle, src.handle, n_bytes, huffman, ptr(out), out.size, C.byref(n))
+        if rc != DEFLATE_NO_ROOM:
+            break
+        out = np.empty(n.value, dtype=np.uint8)
+    _check(rc)
+    return out[:n.value].tobytes()

@@ -8790,3 +8790,318 @@ int svgr_cff_outline(svgr_ctx* ctx, const double* pt_xy, const uint8_t* pt_kind,
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// PNG output on the device: scanline filters and deflate (svgr_png_filter, svgr_deflate).  The per-lane arithmetic, the token
+// rule and the host's code builder are svgr_png.h / svgr_deflate.h; DESIGN.md 7n has the definitions.
+//
+//   k_png_filter      one workgroup per row, a lane per pixel (striding): for the adaptive choice the row's five sums first (per
+//                     wave in registers, then five LDS adds per wave), then the filtered bytes of the chosen type
+//   k_deflate_tokens  one workgroup per chunk.  The hash table lives in LDS and takes positions with an atomic MAX: first the 32 KiB
+//                     in front of the chunk, then the chunk sub-window by sub-window, each sub-window reading its candidates
+//                     before it enters itself.  Every position's best match, then the greedy parse without a walk over the chunk:
+//                     each lane resolves, backwards, where a parse entering its segment at any position leaves it; one lane hops
+//                     from segment to segment (as many steps as there are segments); each lane then walks its own segment from its
+//                     entry, counts, and -- after a scan of the counts -- stores its tokens.  Histogram in LDS, then one global
+//                     add per used symbol; the chunk's Adler pair
+//   k_deflate_emit    one workgroup per chunk: a lane sums the bit lengths of its run of tokens, a scan gives each run its bit
+//                     offset, the bits are OR-ed into the slot in LDS (ds_or: lanes share words), the slot is stored with dwords
+//   k_scan_*          the dasher's two-level scan over the chunks' byte counts
+//   k_deflate_gather  one workgroup per chunk: its bytes to their place in the one stream
+// Integer sums, maxima and ORs only: the result does not depend on the order in which lanes or workgroups run.
+// ======================================================================================
+#include "svgr_png.h"
+#include "svgr_deflate.h"
+
+constexpr int PNG_B = 256;                        // lanes per workgroup of k_png_filter (= per row) and k_deflate_gather
+constexpr int DEFL_B = 512;                       // lanes per workgroup of the two deflate kernels
+constexpr int DEFL_SEG = DEFLATE_CH / DEFL_B;     // positions per lane of the parse
+static_assert(DEFL_SEG == 32 && DEFL_B >= DEFLATE_SUB && DEFL_B >= DEFLATE_NSYM, "the LDS paddings below assume 32 positions per lane");
+#define PNG_KERNEL(B) __global__ __launch_bounds__(B) __attribute__((section(".text.svgr_png")))
+// a lane walks 32 consecutive entries: one word (two halfwords) of padding per segment keeps the lanes on different banks
+#define DEFL_BI(p) ((p) + ((p) >> 5))
+#define DEFL_EI(p) ((p) + (((p) >> 5) << 1))
+
+PNG_KERNEL(PNG_B) void k_png_filter(const uint32_t* __restrict__ src, int cols, int mode, uint8_t* __restrict__ out) {
+    __shared__ uint32_t sums[PNG_FILTER_TYPES];
+    const int64_t row = blockIdx.x;
+    int type = mode;
+    if (mode == PNG_FILTER_ADAPTIVE) {   // (uniform over the launch)
+        if (threadIdx.x < PNG_FILTER_TYPES) sums[threadIdx.x] = 0;
+        __syncthreads();
+        uint32_t s[PNG_FILTER_TYPES] = {0, 0, 0, 0, 0};
+        for (int x = threadIdx.x; x < cols; x += PNG_B) {
+            uint32_t px, a, b, c;
+            png_neighbours(src, row, cols, x, px, a, b, c);
+#pragma unroll
+            for (int t = 0; t < PNG_FILTER_TYPES; ++t) s[t] += png_cost_px(png_filter_px(t, px, a, b, c));
+        }
+#pragma unroll
+        for (int t = 0; t < PNG_FILTER_TYPES; ++t) {
+            for (int d = 32; d; d >>= 1) s[t] += __shfl_down(s[t], d, 64);
+            if ((threadIdx.x & 63) == 0) atomicAdd(&sums[t], s[t]);
+        }
+        __syncthreads();
+        type = png_pick(sums);
+    }
+    uint8_t* o = out + (size_t)row * (1 + 4 * (size_t)cols);
+    if (threadIdx.x == 0) o[0] = (uint8_t)type;
+    for (int x = threadIdx.x; x < cols; x += PNG_B) {
+        uint32_t px, a, b, c;
+        png_neighbours(src, row, cols, x, px, a, b, c);
+        png_store_px(o, x, png_filter_px(type, px, a, b, c));
+    }
+}
+
+// inclusive sum scan over the workgroup's DEFL_B values, in sh
+__device__ __forceinline__ void defl_scan(uint32_t* sh, uint32_t v) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int d = 1; d < DEFL_B; d <<= 1) {
+        uint32_t x = sh[t];
+        if (t >= d) x += sh[t - d];
+        __syncthreads();
+        sh[t] = x;
+        __syncthreads();
+    }
+}
+
+struct DeflTokArgs {
+    const uint8_t* src;
+    long long n;
+    uint32_t* tok;               // DEFLATE_CH per chunk
+    int* n_tok;
+    uint32_t* adler;             // 2 per chunk
+    unsigned long long* hist;    // DEFLATE_NSYM, zeroed by the host
+};
+PNG_KERNEL(DEFL_B) void k_deflate_tokens(DeflTokArgs a) {
+    __shared__ uint32_t table[1 << DEFLATE_HASH_BITS];
+    __shared__ uint32_t best[DEFLATE_CH + DEFLATE_CH / 32];   // first the hash candidates, then the positions' tokens
+    __shared__ uint16_t exitp[DEFLATE_CH + DEFLATE_CH / 16];
+    __shared__ uint32_t hist[DEFL_B];
+    __shared__ uint32_t scan[DEFL_B];
+    __shared__ uint16_t entry[DEFL_B];
+    __shared__ unsigned long long ad[2];
+    const int t = threadIdx.x;
+    const long long start = (long long)blockIdx.x * DEFLATE_CH, base = start - DEFLATE_WINDOW;
+    const long long end = a.n < start + DEFLATE_CH ? a.n : start + DEFLATE_CH;
+    const int len = (int)(end - start);   // (0 for the one chunk of an empty input)
+    for (int i = t; i < (1 << DEFLATE_HASH_BITS); i += DEFL_B) table[i] = 0;
+    hist[t] = 0;
+    entry[t] = 0xFFFF;
+    if (t < 2) ad[t] = 0;
+    __syncthreads();
+    // ---- the window in front of the chunk (an entry is position - base + 1; 0: none)
+    for (long long q = (base > 0 ? base : 0) + t; q < start; q += DEFL_B)
+        if (deflate_hashed(q, a.n)) atomicMax(&table[deflate_hash3(a.src + q)], (uint32_t)(q - base + 1));
+    __syncthreads();
+    // ---- the chunk, sub-window by sub-window: read the candidates, then enter the sub-window
+    for (int w = 0; w < len; w += DEFLATE_SUB) {
+        const int i = w + t;
+        const bool in = t < DEFLATE_SUB && i < len, hashed = in && start + i + 2 < end;
+        uint32_t h = 0, cand = 0;
+        if (hashed) {
+            h = deflate_hash3(a.src + start + i);
+            cand = table[h];
+        }
+        if (in) best[DEFL_BI(i)] = cand;
+        __syncthreads();
+        if (hashed) atomicMax(&table[h], (uint32_t)(start + i - base + 1));
+        __syncthreads();
+    }
+    // ---- every position's token, and the Adler sums on the way
+    unsigned long long A = 0, B = 0;
+    for (int i = t; i < len; i += DEFL_B) {
+        const uint32_t cand = best[DEFL_BI(i)];
+        best[DEFL_BI(i)] = deflate_best(a.src, start + i, end, cand ? base + cand - 1 : -1);
+        const uint32_t b = a.src[start + i];
+        A += b;
+        B += (unsigned long long)(len - i) * b;
+    }
+    __syncthreads();
+    // ---- the parse: where a parse that enters my segment at i leaves it
+    const int s0 = t * DEFL_SEG, s1 = s0 + DEFL_SEG < len ? s0 + DEFL_SEG : len;
+    for (int i = s1 - 1; i >= s0; --i) {
+        const int nx = i + deflate_tok_hop(best[DEFL_BI(i)]);
+        exitp[DEFL_EI(i)] = nx >= s1 ? (uint16_t)nx : exitp[DEFL_EI(nx)];
+    }
+    __syncthreads();
+    if (t == 0)
+        for (int e = 0; e < len; e = exitp[DEFL_EI(e)]) entry[e / DEFL_SEG] = (uint16_t)e;
+    __syncthreads();
+    const int e0 = entry[t];
+    uint32_t cnt = 0;
+    if (e0 != 0xFFFF)
+        for (int p = e0; p < s1; p += deflate_tok_hop(best[DEFL_BI(p)])) ++cnt;
+    defl_scan(scan, cnt);
+    if (e0 != 0xFFFF) {
+        uint32_t* o = a.tok + (size_t)blockIdx.x * DEFLATE_CH + (scan[t] - cnt);
+        for (int p = e0; p < s1;) {
+            const uint32_t tok = best[DEFL_BI(p)];
+            *o++ = tok;
+            int ls, ds;
+            deflate_token_syms(tok, ls, ds);
+            atomicAdd(&hist[ls], 1u);
+            if (ds >= 0) atomicAdd(&hist[DEFLATE_NLIT + ds], 1u);
+            p += deflate_tok_hop(tok);
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        A += __shfl_down(A, d, 64);
+        B += __shfl_down(B, d, 64);
+    }
+    if ((t & 63) == 0) {
+        atomicAdd(&ad[0], A);
+        atomicAdd(&ad[1], B);
+    }
+    __syncthreads();
+    if (t < DEFLATE_NSYM) {
+        const uint32_t h = hist[t] + (t == DEFLATE_EOB ? 1u : 0u);
+        if (h) atomicAdd(&a.hist[t], (unsigned long long)h);
+    }
+    if (t == 0) {
+        a.n_tok[blockIdx.x] = (int)scan[DEFL_B - 1];
+        a.adler[2 * (size_t)blockIdx.x] = (uint32_t)(ad[0] % ADLER_MOD);
+        a.adler[2 * (size_t)blockIdx.x + 1] = (uint32_t)(ad[1] % ADLER_MOD);
+    }
+}
+
+struct DeflEmitArgs {
+    const uint32_t* tok;
+    const int* n_tok;
+    const DeflateCodes* codes;
+    uint8_t* slots;              // DEFLATE_SLOT per chunk
+    long long* cnt;              // the chunk's bytes
+    long long* incl;             // the same again: scanned in place afterwards
+    int n_chunks;
+};
+PNG_KERNEL(DEFL_B) void k_deflate_emit(DeflEmitArgs a) {
+    __shared__ uint32_t words[DEFLATE_SLOT / 4];
+    __shared__ DeflateCodes c;
+    __shared__ uint32_t scan[DEFL_B];
+    __shared__ uint32_t n_bytes;
+    const int t = threadIdx.x;
+    const bool last = (int)blockIdx.x == a.n_chunks - 1;
+    for (int i = t; i < (int)(sizeof(DeflateCodes) / 4); i += DEFL_B) ((uint32_t*)&c)[i] = ((const uint32_t*)a.codes)[i];
+    for (int i = t; i < DEFLATE_SLOT / 4; i += DEFL_B) words[i] = 0;
+    __syncthreads();
+    const uint32_t* tok = a.tok + (size_t)blockIdx.x * DEFLATE_CH;
+    const int n = a.n_tok[blockIdx.x], per = (n + DEFL_B - 1) / DEFL_B;
+    const int i0 = t * per < n ? t * per : n, i1 = i0 + per < n ? i0 + per : n;
+    uint32_t bits = 0;
+    uint64_t v;
+    for (int i = i0; i < i1; ++i) bits += (uint32_t)deflate_token_bits(c.lcode, c.llen, c.dcode, c.dlen, tok[i], v);
+    defl_scan(scan, bits);
+    if (t < (int)((c.hdr_bits + 31) / 32)) atomicOr(&words[t], c.hdr[t] | (t == 0 && last ? 1u : 0u));   // (BFINAL is the first bit)
+    uint32_t pos = c.hdr_bits + scan[t] - bits;
+    for (int i = i0; i < i1; ++i) {
+        const int nb = deflate_token_bits(c.lcode, c.llen, c.dcode, c.dlen, tok[i], v);
+        deflate_put(words, pos, v);
+        pos += (uint32_t)nb;
+    }
+    if (t == 0) n_bytes = deflate_chunk_tail(words, c.hdr_bits + scan[DEFL_B - 1], c.lcode[DEFLATE_EOB], c.llen[DEFLATE_EOB], last);
+    __syncthreads();
+    uint32_t* o = (uint32_t*)(a.slots + (size_t)blockIdx.x * DEFLATE_SLOT);
+    for (int i = t; i < (int)((n_bytes + 3) / 4); i += DEFL_B) o[i] = words[i];
+    if (t == 0) a.cnt[blockIdx.x] = a.incl[blockIdx.x] = n_bytes;
+}
+
+struct DeflSumOp {
+    __device__ static long long zero() { return 0; }
+    __device__ static long long add(const long long& a, const long long& b) { return a + b; }
+};
+PNG_KERNEL(PNG_B) void k_deflate_gather(const uint8_t* __restrict__ slots, const long long* __restrict__ cnt,
+                                        const long long* __restrict__ incl, uint8_t* __restrict__ out) {
+    const long long n = cnt[blockIdx.x];
+    const uint8_t* s = slots + (size_t)blockIdx.x * DEFLATE_SLOT;
+    uint8_t* o = out + (incl[blockIdx.x] - n);
+    for (long long i = threadIdx.x; i < n; i += PNG_B) o[i] = s[i];
+}
+
+constexpr int64_t DEFLATE_MAX_BYTES = (int64_t)5 << 30;   // (the filtered stream of the largest image: 2^30 pixels and their rows' type bytes)
+
+static int deflate_impl(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out) {
+    if (!ctx || !src || !n_out || n_bytes < 0 || out_cap < 0 || (!out && out_cap) || (n_bytes && !src->ptr))
+        return fail(SVGR_E_INVALID, "svgr_deflate: bad arguments");
+    if (huffman != SVGR_DEFLATE_FIXED && huffman != SVGR_DEFLATE_DYNAMIC) return fail(SVGR_E_INVALID, "svgr_deflate: unknown Huffman mode %d", huffman);
+    if (n_bytes > DEFLATE_MAX_BYTES) return fail(SVGR_E_INVALID, "svgr_deflate: %lld bytes are more than %lld", (long long)n_bytes, (long long)DEFLATE_MAX_BYTES);
+    if (src->bytes < (size_t)n_bytes) return fail(SVGR_E_INVALID, "svgr_deflate: buffer too small");
+    static_assert(SVGR_DEFLATE_FIXED == DEFLATE_FIXED && SVGR_DEFLATE_DYNAMIC == DEFLATE_DYNAMIC, "Huffman modes");
+    const int nc = n_bytes ? (int)((n_bytes + DEFLATE_CH - 1) / DEFLATE_CH) : 1;
+    const int nb = (nc + DASH_S - 1) / DASH_S;
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    // one block of small arrays: histogram, codes, per chunk the token count, the Adler pair, the byte count twice, the scan's tops
+    const size_t i_codes = pad64(DEFLATE_NSYM * 8), i_ntok = i_codes + pad64(sizeof(DeflateCodes)), i_adler = i_ntok + pad64((size_t)nc * 4);
+    const size_t i_cnt = i_adler + pad64((size_t)nc * 8), i_incl = i_cnt + pad64((size_t)nc * 8), i_tops = i_incl + pad64((size_t)nc * 8);
+    const size_t i_end = i_tops + pad64((size_t)nb * 8);
+    unsigned long long counts[DEFLATE_NSYM] = {0};
+    DeflateCodes codes;
+    std::vector<uint32_t> adler((size_t)nc * 2);
+    long long total = 0;
+    PoolBlock small, toks, slots, packed;
+    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
+    HIPCHK(small.alloc(i_end, ctx->device));
+    HIPCHK(toks.alloc((size_t)nc * DEFLATE_CH * 4, ctx->device));
+    HIPCHK(slots.alloc((size_t)nc * DEFLATE_SLOT, ctx->device));
+    char* d = small.as<char>();
+    HIPCHK(hipMemsetAsync(d, 0, DEFLATE_NSYM * 8, st));
+    const DeflTokArgs ta{(const uint8_t*)src->ptr, (long long)n_bytes, toks.as<uint32_t>(), (int*)(d + i_ntok), (uint32_t*)(d + i_adler),
+                         (unsigned long long*)d};
+    SVGR_LAUNCH(k_deflate_tokens, dim3((unsigned)nc), dim3(DEFL_B), 0, st, ta);
+    HIPCHK(hipGetLastError());
+    if (huffman == DEFLATE_DYNAMIC) {   // the one round trip: 316 counts down, the tables and the header up
+        HIPCHK(hipMemcpyAsync(counts, d, sizeof counts, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counts");
+    deflate_build_codes((const uint64_t*)counts, huffman, codes);
+    HIPCHK(hipMemcpyAsync(d + i_codes, &codes, sizeof codes, hipMemcpyHostToDevice, st));
+    const DeflEmitArgs ea{toks.as<uint32_t>(), (const int*)(d + i_ntok), (const DeflateCodes*)(d + i_codes), slots.as<uint8_t>(),
+                          (long long*)(d + i_cnt), (long long*)(d + i_incl), nc};
+    SVGR_LAUNCH(k_deflate_emit, dim3((unsigned)nc), dim3(DEFL_B), 0, st, ea);
+    dash_scan<long long, DeflSumOp>(st, (long long*)(d + i_incl), (long long*)(d + i_tops), nc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&total, d + i_incl + (size_t)(nc - 1) * 8, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(adler.data(), d + i_adler, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total <= 0 || total > (long long)nc * DEFLATE_SLOT) return fail(SVGR_E_STATE, "svgr_deflate: the chunks' byte counts do not add up");
+    *n_out = 2 + total + 4;
+    if (*n_out > out_cap) return SVGR_DEFLATE_NO_ROOM;
+    // ---- only the compressed bytes cross: the chunks' bytes to one run, then one download
+    HIPCHK(packed.alloc((size_t)total, ctx->device));
+    SVGR_LAUNCH(k_deflate_gather, dim3((unsigned)nc), dim3(PNG_B), 0, st, slots.as<uint8_t>(), (const long long*)(d + i_cnt),
+                (const long long*)(d + i_incl), packed.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out + 2, packed.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out[0] = 0x78;   // CMF: deflate, 32 KiB window; FLG: fastest, FCHECK
+    out[1] = 0x01;
+    uint32_t s1 = 1, s2 = 0;
+    for (int k = 0; k < nc; ++k) {
+        const long long len = std::min<long long>(DEFLATE_CH, (long long)n_bytes - (long long)k * DEFLATE_CH);
+        adler_combine(s1, s2, adler[2 * (size_t)k], adler[2 * (size_t)k + 1], len);
+    }
+    const uint32_t ad = (s2 << 16) | s1;
+    uint8_t* tail = out + 2 + total;
+    tail[0] = (uint8_t)(ad >> 24); tail[1] = (uint8_t)(ad >> 16); tail[2] = (uint8_t)(ad >> 8); tail[3] = (uint8_t)ad;
+    return 0;
+}
+
+extern "C" {
+int svgr_deflate_chunk(void) { return DEFLATE_CH; }
+int svgr_png_filter(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, int filter, svgr_buf* out_filtered) {
+    if (!ctx || !src_rgba8 || !out_filtered || !image_size_ok(rows, cols)) return fail(SVGR_E_INVALID, "svgr_png_filter: bad arguments");
+    if (filter < 0 || filter > SVGR_PNG_FILTER_ADAPTIVE) return fail(SVGR_E_INVALID, "svgr_png_filter: unknown filter %d", filter);
+    static_assert(SVGR_PNG_FILTER_ADAPTIVE == PNG_FILTER_ADAPTIVE, "filter numbers");
+    if (src_rgba8->bytes < (size_t)rows * cols * 4 || out_filtered->bytes < (size_t)rows * (1 + 4 * (size_t)cols))
+        return fail(SVGR_E_INVALID, "svgr_png_filter: buffer too small");
+    if (src_rgba8->ptr == out_filtered->ptr) return fail(SVGR_E_INVALID, "svgr_png_filter: the output must not be the source");
+    return launch_tail(ctx, k_png_filter, dim3((unsigned)rows), dim3(PNG_B), 0, (const uint32_t*)src_rgba8->ptr, (int)cols, filter,
+                       (uint8_t*)out_filtered->ptr);
+}
+int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out) {
+    return abi_guard("svgr_deflate", [&]() { return deflate_impl(ctx, src, n_bytes, huffman, out, out_cap, n_out); });
+}
+}  // extern "C"

@@ -688,10 +688,20 @@ class Layer:
         out, rows, cols = self._to_rgba8_device()
         return out.download((rows, cols, 4), np.uint8)
 
-    def write_png(self, output=None, level: int = 9, threads: int = 1):
+    def write_png(self, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None):
         """PNG of the layer (Layer.write_png, S:209-213): 8-bit RGBA, filter 0, one IDAT -- byte-identical to the
-        reference's file at the reference's zlib level 9 (``level`` trades size for speed, the pixels are the same)."""
-        return canvas_to_png(self.to_rgba8(), output, level=level, threads=threads)
+        reference's file at the reference's zlib level 9 (``level``, default 9, trades size for speed; ``threads``, default 1,
+        compresses in parallel pieces; the pixels are the same).  ``encoder="device"`` filters and compresses on the device
+        instead (``canvas_to_png`` has the details): the bytes go from the 8-bit conversion straight into the filter kernel
+        and only the compressed stream crosses PCIe.  It takes ``filter`` and ``huffman`` in place of ``level`` and
+        ``threads``."""
+        from . import png  # noqa: PLC0415
+
+        args = png.encoder_arguments(encoder, level, threads, filter, huffman)
+        if args[0] == "device":
+            buf, rows, cols = self._to_rgba8_device()
+            return png.encode_rgba8(buf, rows, cols, output, filter, huffman)
+        return canvas_to_png(self.to_rgba8(), output, level=args[1], threads=args[2])
 
     def write_jpeg(self, output=None, bg=None, **kw) -> bytes:
         """Baseline JFIF JPEG of the layer (beyond the reference); returns the file's bytes, also written to ``output`` (a path
@@ -744,27 +754,33 @@ def _deflate_parallel(raw: bytes, level: int, threads: int) -> bytes:
     return bytes([cmf, flg]) + b"".join(parts) + (zlib.adler32(raw) & 0xFFFFFFFF).to_bytes(4, "big")
 
 
-def canvas_to_png(canvas, output=None, level: int = 9, threads: int = 1):
+def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None):
     """(height, width, 4) -> PNG (canvas_to_png, S:249-274).  ``canvas`` is either the uint8 array of
     ``Layer.to_rgba8`` or float RGBA in [0, 1] (quantised like the reference: ``np.round(canvas * 255)``).
-    ``threads`` > 1 compresses the scanlines in parallel pieces: same pixels, a different (slightly larger) file than the
-    reference's, written several times faster (4096 x 4096 at level 9: seconds -> a few tenths)."""
+    ``level`` (default 9) is zlib's; ``threads`` (default 1) > 1 compresses the scanlines in parallel pieces: same pixels, a
+    different (slightly larger) file than the reference's, written several times faster (4096 x 4096 at level 9: seconds -> a
+    few tenths).
+
+    ``encoder="device"`` (beyond the reference) uploads the bytes and makes the scanline filters and the deflate stream on
+    the device: ``filter`` is "adaptive" (default: per row the type libpng's heuristic picks), "none", "sub", "up", "average"
+    or "paeth"; ``huffman`` is "dynamic" (default: one code pair made to measure for the whole image) or "fixed".  The file
+    decodes to the same pixels and differs from the host encoder's in its bytes.  ``level`` and ``threads`` do not apply to
+    it (TypeError); an unknown value is a ValueError before any device work."""
     import io
-    import struct
     import zlib
 
+    from . import png  # noqa: PLC0415
+
+    args = png.encoder_arguments(encoder, level, threads, filter, huffman)
     canvas = np.asarray(canvas)
     if canvas.dtype != np.uint8:
         canvas = np.round(canvas * 255.0).astype(np.uint8)
     if canvas.ndim != 3 or canvas.shape[2] != 4:
         raise ValueError("Only RGBA layers are supported")
     height, width, _ = canvas.shape
-
-    def pack(out, tag: bytes, data: bytes) -> None:
-        out.write(struct.pack("!I", len(data)))
-        out.write(tag)
-        out.write(data)
-        out.write(struct.pack("!I", 0xFFFFFFFF & zlib.crc32(data, zlib.crc32(tag))))
+    if args[0] == "device":
+        return png.encode_rgba8(canvas, height, width, output, filter, huffman)
+    _, level, threads = args
 
     # filter byte 0 in front of every scanline, then ONE deflate stream (deflate output does not depend on how the
     # input is chunked, so one call gives the bytes of the reference's row-by-row loop)
@@ -775,12 +791,7 @@ def canvas_to_png(canvas, output=None, level: int = 9, threads: int = 1):
     else:
         comp = zlib.compressobj(level=level)
         data = comp.compress(rows.tobytes()) + comp.flush()
-    output = io.BytesIO() if output is None else output
-    output.write(b"\x89PNG\r\n\x1a\n")
-    pack(output, b"IHDR", struct.pack("!2I5B", width, height, 8, 6, 0, 0, 0))
-    pack(output, b"IDAT", data)
-    pack(output, b"IEND", b"")
-    return output
+    return png.write_container(io.BytesIO() if output is None else output, width, height, data)
 
 
 def canvas_to_jpeg(canvas, output=None, **kw) -> bytes:

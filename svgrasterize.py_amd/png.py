@@ -1,10 +1,17 @@
-"""PNG reader for SVG <image> (beyond the reference): bytes in, an (h, w, 4) uint8 array out, straight alpha, sRGB as stored.
+"""PNG reader for SVG <image> and the device PNG encoder (both beyond the reference).
+
+Reader: bytes in, an (h, w, 4) uint8 array out, straight alpha, sRGB as stored.
 
 Chunks are read here (signature, CRC of every chunk, IHDR / PLTE / tRNS / IDAT; ancillary chunks are skipped) and the
 image data is inflated with the standard library's zlib.  Reversing the scanline filters is a sequential walk over the
 bytes and runs in native host code (``svgr_png_unfilter``, csrc/svgr_png.cpp); unpacking samples below 8 bits, the palette
 lookup, 16 -> 8 bit reduction and the Adam7 scatter are numpy.  Every colour type and bit depth of the specification is
-read.  Malformed input raises ValueError with the reason."""
+read.  Malformed input raises ValueError with the reason.
+
+Encoder (``encoder="device"`` of ``canvas_to_png``, ``Layer.write_png`` and ``render_svg``): the scanline filters and the
+deflate stream are made on the device (``svgr_png_filter``, ``svgr_deflate``; csrc/svgr_png.h and csrc/svgr_deflate.h have the
+definitions) from the RGBA8 bytes that are already there; only the compressed bytes come back, and the container -- signature,
+IHDR, one IDAT, IEND, the CRCs -- is written here."""
 from __future__ import annotations
 
 import struct
@@ -153,3 +160,106 @@ def read_png(data: bytes) -> np.ndarray:
                 raise ValueError("bad tRNS chunk length")
             out[np.all(samples.astype(np.int64) == key, axis=2), 3] = 0
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the encoder
+# ---------------------------------------------------------------------------------------------------------------------
+FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}   # SVGR_PNG_FILTER_*
+HUFFMAN = {"fixed": 0, "dynamic": 1}                                                # SVGR_DEFLATE_*
+
+
+def _filter_number(filter) -> int:
+    if not isinstance(filter, str) or filter not in FILTERS:
+        raise ValueError(f"PNG filter is one of {', '.join(FILTERS)}, not {filter!r}")
+    return FILTERS[filter]
+
+
+def _huffman_number(huffman) -> int:
+    if not isinstance(huffman, str) or huffman not in HUFFMAN:
+        raise ValueError(f"deflate Huffman mode is one of {', '.join(HUFFMAN)}, not {huffman!r}")
+    return HUFFMAN[huffman]
+
+
+def write_container(output, width: int, height: int, idat: bytes):
+    """The file around a zlib stream of 8-bit RGBA scanlines: signature, IHDR, one IDAT, IEND (canvas_to_png, S:249-274)."""
+    def pack(tag: bytes, data: bytes) -> None:
+        output.write(struct.pack("!I", len(data)))
+        output.write(tag)
+        output.write(data)
+        output.write(struct.pack("!I", 0xFFFFFFFF & zlib.crc32(data, zlib.crc32(tag))))
+
+    output.write(SIGNATURE)
+    pack(b"IHDR", struct.pack("!2I5B", width, height, 8, 6, 0, 0, 0))
+    pack(b"IDAT", idat)
+    pack(b"IEND", b"")
+    return output
+
+
+def filter_device(rgba8, filter: str = "adaptive", *, rows: int | None = None, cols: int | None = None) -> "_abi.DeviceBuffer":
+    """The filtered scanlines of an 8-bit RGBA image, made on the device and left there: ``rows * (1 + 4 * cols)`` bytes.
+    ``rgba8`` is a ``(rows, cols, 4)`` uint8 array, which is uploaded, or a DeviceBuffer that holds such bytes (then ``rows``
+    and ``cols`` say its shape)."""
+    mode = _filter_number(filter)
+    ctx = _abi.Context.get()
+    if not isinstance(rgba8, _abi.DeviceBuffer):
+        px = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if px.ndim != 3 or px.shape[2] != 4 or px.size == 0:
+            raise ValueError("filter_device: the pixels are a non-empty (rows, cols, 4) uint8 array")
+        rows, cols = px.shape[0], px.shape[1]
+        rgba8 = ctx.from_host(px)
+    elif rows is None or cols is None:
+        raise ValueError("filter_device: a device buffer needs rows and cols")
+    return _abi.png_filter(ctx, rgba8, int(rows), int(cols), mode)
+
+
+def deflate_device(data, huffman: str = "dynamic", *, n_bytes: int | None = None) -> bytes:
+    """A complete zlib stream of ``data`` -- bytes or a uint8 array, which are uploaded, or a DeviceBuffer (its first
+    ``n_bytes`` bytes; default all of it) -- compressed on the device.  ``zlib.decompress`` returns the input."""
+    mode = _huffman_number(huffman)
+    ctx = _abi.Context.get()
+    if not isinstance(data, _abi.DeviceBuffer):
+        arr = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        n_bytes = arr.size
+        data = ctx.from_host(arr) if arr.size else ctx.alloc(4)
+    elif n_bytes is None:
+        n_bytes = data.nbytes
+    return _abi.deflate(ctx, data, int(n_bytes), mode)
+
+
+def _idat_stage(rgba8, rows: int, cols: int, filter: int, huffman: int) -> bytes:
+    """The IDAT payload of an image on the device: ``rgba8`` is a DeviceBuffer of its bytes or a (rows, cols, 4) uint8 array,
+    which is uploaded first.  (The CPU tests put the host build of the same headers here.)"""
+    ctx = _abi.Context.get()
+    if not isinstance(rgba8, _abi.DeviceBuffer):
+        rgba8 = ctx.from_host(np.ascontiguousarray(rgba8, dtype=np.uint8))
+    filtered = _abi.png_filter(ctx, rgba8, rows, cols, filter)
+    return _abi.deflate(ctx, filtered, rows * (1 + 4 * cols), huffman)
+
+
+def encode_rgba8(rgba8, rows: int, cols: int, output=None, filter=None, huffman=None):
+    """``canvas_to_png(encoder="device")``: the PNG of 8-bit RGBA pixels (an array or a DeviceBuffer) into ``output`` (a binary
+    file object; default a new BytesIO), which is returned.  Bad arguments are refused before any device work."""
+    import io
+
+    mode = _filter_number("adaptive" if filter is None else filter)
+    code = _huffman_number("dynamic" if huffman is None else huffman)
+    if rows <= 0 or cols <= 0:
+        raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+    idat = _idat_stage(rgba8, int(rows), int(cols), mode, code)
+    return write_container(io.BytesIO() if output is None else output, int(cols), int(rows), idat)
+
+
+def encoder_arguments(encoder, level, threads, filter, huffman):
+    """What ``canvas_to_png`` and its callers accept: ("host", level, threads) or ("device", filter, huffman), checked."""
+    if encoder == "host":
+        if filter is not None or huffman is not None:
+            raise TypeError('filter and huffman belong to encoder="device"')
+        return "host", 9 if level is None else level, 1 if threads is None else threads
+    if encoder != "device":
+        raise ValueError(f'PNG encoder is "host" or "device", not {encoder!r}')
+    if level is not None or threads is not None:
+        raise TypeError('level and threads belong to encoder="host"')
+    _filter_number("adaptive" if filter is None else filter)
+    _huffman_number("dynamic" if huffman is None else huffman)
+    return "device", filter, huffman
