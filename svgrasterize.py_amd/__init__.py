@@ -28,7 +28,8 @@ from .scene import (  # noqa: F401
     RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER, RENDER_BLEND,
     RENDER_MARKERS,
 )
-from .markers import Marker  # noqa: F401
+from .markers import Marker, Symbol  # noqa: F401
+from .css import Stylesheet, parse_css  # noqa: F401
 from .textpath import TextOnPath, TextOutline, TextRun  # noqa: F401
 from .fonts import Font, FontsDB, Glyph  # noqa: F401
 from .truetype import TrueTypeFont, read_ttf  # noqa: F401
@@ -38,4 +39,5 @@ from .svg import render_svg, svg_scene, svg_scene_from_filepath, svg_scene_from_
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
            "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg",
-           "write_jpeg", "canvas_to_jpeg", "Marker", "TextOnPath", "TextRun", "TextOutline", "TrueTypeFont", "read_ttf", "Axis", "CFFFont", "read_otf", "read_font"]
+           "write_jpeg", "canvas_to_jpeg", "Marker", "TextOnPath", "TextRun", "TextOutline", "TrueTypeFont", "read_ttf", "Axis", "CFFFont", "read_otf", "read_font",
+           "parse_css", "Stylesheet", "Symbol"]

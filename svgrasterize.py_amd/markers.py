@@ -7,6 +7,7 @@ from __future__ import annotations
 import math
 import threading
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -74,6 +75,61 @@ class Marker:
             c, s = math.cos(angle), math.sin(angle)
         k = float(stroke_width) if self.units_stroke_width else 1.0
         return Transform().translate(x, y).matrix(c, -s, 0, s, c, 0).scale(k * scale[0], k * scale[1]).translate(-float(self.ref[0]), -float(self.ref[1]))
+
+
+class Symbol(NamedTuple):
+    """What a ``<symbol>`` element says (beyond the reference).  `scene`: its content in the symbol's own coordinates (None:
+    empty); `viewbox` = (x, y, w, h) or None; `x`, `y`, `width`, `height`: the symbol's own (None: not given); `clip`: the
+    content is clipped to the viewport (``overflow`` neither ``visible`` nor ``auto``)."""
+
+    scene: "tuple | None"
+    viewbox: "tuple | None" = None
+    preserve_aspect_ratio: str = "xMidYMid meet"
+    x: float = 0.0
+    y: float = 0.0
+    width: "float | None" = None
+    height: "float | None" = None
+    clip: bool = True
+
+    def viewport(self, width=None, height=None):
+        """``(width, height)`` of the viewport an instance gets: the <use>'s `width` / `height`, else the symbol's own, else
+        the viewBox's size (a deviation: SVG says 100 %, which needs a viewport that is not known when a document loads);
+        None for each that none of them gives."""
+        box = (None, None) if self.viewbox is None else self.viewbox[2:]
+        return tuple(next((float(v) for v in (given, own, fallback) if v is not None), None)
+                     for given, own, fallback in ((width, self.width, box[0]), (height, self.height, box[1])))
+
+    def instance(self, x: float = 0.0, y: float = 0.0, width=None, height=None):
+        """What a ``<use>`` at (`x`, `y`) with `width` / `height` (None: not given) draws: the content under one transform --
+        the translation by (`x`, `y`) and the symbol's own ``x`` / ``y``, times the fit of the viewBox into the viewport
+        (``scene.image_placement``, the mapping a <marker> uses) -- and, unless `clip` is off, clipped to the viewport, a
+        rectangle in content coordinates as a nested <svg>'s frame is.  Without a viewBox the content is not scaled; without
+        any size it is not clipped.  None when nothing is drawn (no content, an empty viewport or viewBox)."""
+        from .scene import Scene, image_placement  # noqa: PLC0415
+
+        if self.scene is None:
+            return None
+        w, h = self.viewport(width, height)
+        if (w is not None and not w > 0) or (h is not None and not h > 0):
+            return None
+        content, place = self.scene, Transform().translate(float(x) + float(self.x or 0.0), float(y) + float(self.y or 0.0))
+        sx = sy = 1.0
+        tx = ty = 0.0
+        if self.viewbox is not None:
+            vx, vy, vw, vh = (float(v) for v in self.viewbox)
+            fit = image_placement((vh, vw), 0.0, 0.0, w, h, self.preserve_aspect_ratio)
+            if fit is None:
+                return None
+            m = fit[0].m
+            sx, sy = float(m[0, 0]), float(m[1, 1])
+            tx, ty = float(m[0, 2]) - sx * vx, float(m[1, 2]) - sy * vy
+            place = place.translate(float(m[0, 2]), float(m[1, 2])).scale(sx, sy).translate(-vx, -vy)
+        if self.clip and w is not None and h is not None:
+            x0, y0, x1, y1 = (0.0 - tx) / sx, (0.0 - ty) / sy, (w - tx) / sx, (h - ty) / sy
+            frame = [(PATH_LINE, [[x0, y0], [x1, y0]]), (PATH_LINE, [[x1, y0], [x1, y1]]), (PATH_LINE, [[x1, y1], [x0, y1]]),
+                     (PATH_CLOSED, [[x0, y1], [x0, y0]])]
+            content = content.clip(Scene.fill(Path([frame]), np.ones(4)))
+        return content.transform(place)
 
 
 class MarkerInstances:

@@ -40,7 +40,11 @@ where it began; ``method="stretch"``, ``spacing`` and ``side="right"`` warn and 
 Also beyond the reference: variable TrueType fonts -- ``font-weight`` picks the ``wght`` of a variable face, ``font-stretch`` (the
 nine keywords or a percentage) its ``wdth``, ``font-variation-settings`` (``normal``, or ``"tag" number`` separated by commas) any
 axis the face has, and wins over both; all inherited; a malformed value warns and counts as ``normal`` (``truetype_var.py``).
-Not supported (a warning, the element is skipped): foreignObject, switch, ...; <image> of other formats
+Also beyond the reference: stylesheets and document structure -- ``<style>`` elements and the ``css=`` argument (``css.py``: the
+cascade of presentation attributes, rules, the inline ``style`` and ``!important``, see ``_Loader.props``), ``display`` and
+``visibility``, ``<symbol>`` (``markers.Symbol``; ``<use>`` with ``width`` / ``height``), ``<switch>`` (``requiredExtensions``,
+``systemLanguage`` against ``languages=``), ``<a>`` (a ``<g>``, inside text a ``<tspan>``); ``foreignObject`` draws nothing.
+Not supported (a warning, the element is skipped): animation elements, script, ...; <image> of other formats
 (GIF, WebP, SVG) or remote URLs.
 """
 from __future__ import annotations
@@ -68,14 +72,15 @@ from .geometry import (
     PATH_CLOSED, PATH_FILL_NONZERO, PATH_LINE, STROKE_CAP_BUTT, STROKE_JOIN_MITER, Path, Transform,
 )
 from .layer import BLEND_MODES, COMPOSE_ATOP, COMPOSE_IN, COMPOSE_OUT, COMPOSE_OVER, COMPOSE_XOR
-from .markers import ORIENT_AUTO, ORIENT_AUTO_START_REVERSE, Marker
+from .css import Matcher, Stylesheet, parse_css, parse_declarations
+from .markers import ORIENT_AUTO, ORIENT_AUTO_START_REVERSE, Marker, Symbol
 from .textpath import ANCHORS, TextRun
 from .paint import GradLinear, GradRadial, Pattern
 from .jpeg import read_jpeg
 from .jpeg import SIGNATURE as _JPEG_SIGNATURE
 from .png import SIGNATURE as _PNG_SIGNATURE
 from .png import read_png
-from .scene import RENDER_BLEND, Scene, parse_preserve_aspect_ratio
+from .scene import RENDER_BLEND, RENDER_GROUP, Scene, parse_preserve_aspect_ratio
 
 UNITS_USER = "userSpaceOnUse"
 UNITS_BBOX = "objectBoundingBox"
@@ -89,7 +94,14 @@ _INHERITED = {
     "stroke-dasharray", "stroke-dashoffset",   # (beyond the reference: dashed strokes)
     "marker-start", "marker-mid", "marker-end",   # (beyond the reference: markers; the shorthand ``marker`` is spelled out into them)
     "font-variation-settings", "font-stretch",   # (beyond the reference: variable TrueType fonts)
+    "visibility",   # (beyond the reference)
 }
+# the elements whose own ``display`` is read; on the resource elements (clipPath, mask, pattern, marker, symbol, the gradients,
+# filter, font, defs) it is ignored, as SVG says, while their children's is honoured
+_DISPLAYED = {"svg", "g", "a", "switch", "use", "image", "text", "foreignObject", "path", "rect", "circle", "ellipse", "line", "polyline",
+              "polygon"}
+_CSS_WIDE = ("initial", "unset")   # keywords (and ``var()``) that warn and drop their declaration
+_NOTHING = Scene(RENDER_GROUP, ())   # what the id of an element with ``display: none`` stands for: a <use> of it draws nothing
 _MARKER_PROPERTIES = ("marker-start", "marker-mid", "marker-end")
 _PATH_SHAPES = {"path", "rect", "circle", "ellipse", "line", "polyline", "polygon"}   # what a <textPath> may reference
 _NEAREST = {"pixelated", "optimizespeed", "crisp-edges"}   # image-rendering values that ask for the nearest texel
@@ -349,6 +361,28 @@ def _keyword(text) -> str:
     return text.strip().encode("utf-8").lower().decode("utf-8")
 
 
+def _props(loader, element, inherit=None) -> dict:
+    """An element's properties: the loader's cascade, or without a loader its attributes and inline ``style``."""
+    return _expand_style(element.attrib, inherit) if loader is None else loader.props(element, inherit)
+
+
+def _display_none(attrs) -> bool:
+    display = attrs.get("display")
+    return display is not None and _keyword(display) == "none"
+
+
+def _invisible(attrs) -> bool:
+    visibility = attrs.get("visibility")
+    return visibility is not None and _keyword(visibility) in ("hidden", "collapse")
+
+
+def _href(attrs):
+    href = attrs.get("href")
+    if href is None:
+        href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
+    return href
+
+
 def _collapse(text, after_blank):
     """The characters of a text node as they are set (S:3737-3745) and whether they end in a blank: white space collapses to
     single blanks; one leading blank is kept unless the previous run ended in one, and one trailing blank.  ``(None,
@@ -372,12 +406,12 @@ def _isolated(group: list) -> list:
     return [Scene.group(group)]
 
 
-def _gradient_stops(element):
+def _gradient_stops(element, loader=None):
     stops = []
     for child in element:
         if not child.tag.endswith("stop"):
             continue
-        attrs = _expand_style(child.attrib)
+        attrs = _props(loader, child)
         offset = parse_float(attrs.get("offset")) or 0
         offset = min(max(offset, 0), 1)
         color = parse_color(attrs["stop-color"])
@@ -391,7 +425,7 @@ def _gradient_stops(element):
     return stops
 
 
-def _gradient(element, linear: bool):
+def _gradient(element, linear: bool, loader=None):
     """<linearGradient> / <radialGradient> -> GradLinear / GradRadial, a plain colour (one stop) or None (no stops).
     Like the reference (S:2873-2878, S:3181-3249) a gradient is built from its own element only: ``href`` is not followed."""
     attr = element.attrib
@@ -402,7 +436,7 @@ def _gradient(element, linear: bool):
     if units not in (UNITS_BBOX, UNITS_USER):
         raise ValueError(f"invalid gradient unites: {units}")
     bbox_units = units == UNITS_BBOX
-    stops = _gradient_stops(element)
+    stops = _gradient_stops(element, loader)
     if not stops:
         return None
     if len(stops) == 1:
@@ -524,10 +558,10 @@ def _light_source(element):
     return None
 
 
-def _lighting_args(element, tag):
+def _lighting_args(element, tag, loader=None):
     """feDiffuseLighting / feSpecularLighting -> (light, linear RGB colour, surfaceScale, constant, specularExponent or None);
     None (+ warning) without a light source, with a negative constant or an invalid lighting-color."""
-    attrs = _expand_style(element.attrib)
+    attrs = _props(loader, element)
     light = _light_source(element)
     if light is None:
         warnings.warn(f"{tag} without a light source")
@@ -596,9 +630,9 @@ def _filter(element, loader=None) -> Filter:
         if tag == "feTile":
             flt = flt.tile(src, result)
         elif tag == "feImage":
-            flt = _fe_image(flt, attrs, loader, result)
+            flt = _fe_image(flt, child, loader, result)
         elif tag == "feFlood":
-            color = _flood_color(_expand_style(attrs))
+            color = _flood_color(_props(loader, child))
             if color is not None:
                 flt = flt.flood(color, region, result)
         elif tag == "feTurbulence":
@@ -631,7 +665,7 @@ def _filter(element, loader=None) -> Filter:
             else:
                 flt = flt.displacement_map(src, attrs.get("in2"), parse_float(attrs.get("scale", "0")), xc, yc, result)
         elif tag == "feDropShadow":
-            style = _expand_style(attrs)
+            style = _props(loader, child)
             color = _flood_color(style)
             stds = parse_floats(attrs.get("stdDeviation", "2"), 1, 2)
             std_x, std_y = stds * 2 if len(stds) == 1 else stds
@@ -640,7 +674,7 @@ def _filter(element, loader=None) -> Filter:
                                       region, src, result, sub)
                 sub = None
         elif tag in ("feDiffuseLighting", "feSpecularLighting"):
-            args = _lighting_args(child, tag)
+            args = _lighting_args(child, tag, loader)
             if args is not None:
                 light, color, surface_scale, constant, exponent = args
                 if exponent is None:
@@ -703,12 +737,11 @@ def _filter(element, loader=None) -> Filter:
     return flt
 
 
-def _fe_image(flt: Filter, attrs, loader, result) -> Filter:
+def _fe_image(flt: Filter, element, loader, result) -> Filter:
     """<feImage>: a raster (the sources and warnings of <image>) or ``#id``, an element of the document.  Whatever cannot be
     read still takes its place in the chain, with a transparent result."""
-    href = attrs.get("href")
-    if href is None:
-        href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
+    attrs = element.attrib
+    href = _href(attrs)
     if href is not None and href.strip().startswith("#"):
         return flt.image(element=href.strip()[1:], ids=None if loader is None else loader.ids, result=result)
     pixels = (loader if loader is not None else _Loader(None, None)).image_pixels(href)
@@ -720,7 +753,7 @@ def _fe_image(flt: Filter, attrs, loader, result) -> Filter:
     except ValueError:
         warnings.warn(f"invalid preserveAspectRatio: {par!r}, using xMidYMid meet")
         par = "xMidYMid meet"
-    smooth = _expand_style(attrs).get("image-rendering", "auto").strip().lower() not in _NEAREST
+    smooth = _props(loader, element).get("image-rendering", "auto").strip().lower() not in _NEAREST
     return flt.image(pixels, par, smooth, result=result)
 
 
@@ -780,7 +813,7 @@ def _names_to_unicode(names, by_name) -> list:
     return out
 
 
-def _font(element):
+def _font(element, loader=None):
     """<font> -> Font, or None without a <font-face> (S:3627-3702).  Children inherit the <font>'s own attributes, so a
     ``horiz-adv-x`` on the <font> is the default advance; a glyph lacking ``unicode`` or any advance is dropped; kerning
     pairs are the cross product of (u1 + g1) x (u2 + g2), later <hkern> elements overriding earlier ones."""
@@ -788,7 +821,7 @@ def _font(element):
     missing, font = None, None
     for child in element:
         tag = child.tag.split("}")[-1]
-        attrs = _expand_style(child.attrib, element.attrib)
+        attrs = _props(loader, child, element.attrib)
         if tag == "glyph":
             code, advance = attrs.get("unicode"), attrs.get("horiz-adv-x")
             if code is None or advance is None:
@@ -866,7 +899,14 @@ _IMAGE_EXTENSIONS = {".png": "PNG", ".jpg": "JPEG", ".jpeg": "JPEG", ".jpe": "JP
 
 
 class _Loader:
-    def __init__(self, fg, width, fonts=None, base_dir=None):
+    def __init__(self, fg, width, fonts=None, base_dir=None, languages=("en",)):
+        self.matcher = None   # css.Matcher when the document has style rules; None: `props` is `_expand_style`
+        self.own: dict = {}        # element -> its own cascaded properties (with rules only)
+        self.computed: dict = {}   # element -> its properties with what it inherits, for the keyword ``inherit``
+        self.css_seen: set = set()   # what the style sheets have warned about (each kind once per document)
+        self.languages = tuple(_keyword(tag) for tag in ([languages] if isinstance(languages, str) else languages or ()))
+        self.viewports: dict = {}    # id -> (<svg> element, inherited properties where it stands), for <use> with a size
+        self.use_size: dict = {}     # <svg> element -> the (width, height) a <use> gives it while it is instantiated
         self.fonts = FontsDB() if fonts is None else fonts
         self.ids: dict = {}
         self.shape_paths: dict = {}   # id -> (path data, transform, pathLength) of the basic shapes and paths, for <textPath>
@@ -875,6 +915,68 @@ class _Loader:
         self.width = width
         self.base_dir = base_dir   # the document's directory (<image> files resolve against it); None: not from a file
         self.warned_zero_dash = False
+
+    # -- style -----------------------------------------------------------------------------------------------------------
+    def css_warn(self, key, message):
+        if key not in self.css_seen:
+            self.css_seen.add(key)
+            warnings.warn(message)
+
+    def stylesheets(self, root, css=None):
+        """Collect the document's <style> elements (a sheet applies to the whole document wherever it stands) and the caller's
+        `css`, which goes last: at equal specificity it wins.  Parents and siblings are mapped only if a rule was found."""
+        sheet = None
+        if root.find(".//{*}style") is not None:
+            for element in root.iter():
+                if not isinstance(element.tag, str) or element.tag.split("}")[-1] != "style":
+                    continue
+                kind = element.attrib.get("type")
+                if kind is not None and kind.strip() and _keyword(kind) != "text/css":
+                    warnings.warn(f"style of type {kind.strip()!r} is not read (only text/css is)")
+                    continue
+                text = "".join(element.itertext())
+                one = parse_css(text, self.css_seen)
+                sheet = one if sheet is None else sheet + one
+        if css is not None:
+            one = css if isinstance(css, Stylesheet) else parse_css(css, self.css_seen)
+            sheet = one if sheet is None else sheet + one
+        if sheet is not None and len(sheet):
+            self.matcher = Matcher(sheet, root)
+
+    def props(self, element, inherit=None) -> dict:
+        """An element's properties on top of what the parent hands down.  Without style rules: its attributes with the inline
+        ``style`` folded in (`_expand_style`).  With rules, later layers overwriting earlier ones: presentation attributes,
+        the rules' normal declarations by specificity and source order, the inline ``style``'s, the rules' ``!important`` ones,
+        the inline ``style``'s.  Property names of declarations are lower case; ``inherit`` takes the parent's value."""
+        if self.matcher is None:
+            return _expand_style(element.attrib, inherit)
+        own = self.own.get(element)
+        if own is None:
+            own = dict(element.attrib)
+            style = own.pop("style", None)
+            layers = [d for decls in self.matcher.declarations(element) for d in decls]
+            inline = parse_declarations(style, self.css_warn) if style is not None else ()
+            parent = None
+            ordered = ([d for d in layers if not d[2]] + [d for d in inline if not d[2]]
+                       + [d for d in layers if d[2]] + [d for d in inline if d[2]])
+            for name, value, _important in ordered:
+                word = _keyword(value)
+                if word in _CSS_WIDE or "var(" in word or name.startswith("--"):
+                    self.css_warn("css-wide", "initial, unset and custom properties (var()) are not supported: the declaration is dropped")
+                elif word == "inherit":
+                    if parent is None:   # (the parent's full dictionary, kept on the walk)
+                        parent = {**(inherit or {}), **self.computed.get(self.matcher.parent.get(element), {})}
+                    if name in parent:
+                        own[name] = parent[name]
+                    else:
+                        own.pop(name, None)
+                else:
+                    own[name] = value
+            self.own[element] = own
+        attrs = dict(own) if inherit is None else {**inherit, **own}
+        if inherit is not None:
+            self.computed[element] = dict(attrs)
+        return attrs
 
     def image_pixels(self, href):
         """The RGBA pixels an <image> href points at, or None (+ warning): a PNG or JPEG data URI or local file.  The name or
@@ -931,6 +1033,8 @@ class _Loader:
 
     def image(self, attrs) -> list:
         """<image>: a fill of the visible part of its viewport with the image as the paint (Scene.image)."""
+        if _invisible(attrs):
+            return []
         href = attrs.get("href")
         if href is None:
             href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
@@ -961,7 +1065,10 @@ class _Loader:
 
     # -- leaves --------------------------------------------------------------------------------------------------------
     def shape(self, attrs, path=None) -> list:
-        """Fill and stroke scenes of one shape from its (inherited + own) attributes (S:3136-3178)."""
+        """Fill and stroke scenes of one shape from its (inherited + own) attributes (S:3136-3178); none under
+        ``visibility: hidden`` / ``collapse`` (text runs come through here too: a hidden run still advances the pen)."""
+        if _invisible(attrs):
+            return []
         if path is None:
             d = attrs.get("d")
             if d is None:
@@ -1085,7 +1192,7 @@ class _Loader:
                     target = None
             refs.append(target)
         d = attrs.get("d")
-        if d is None or not any(refs):
+        if d is None or not any(refs) or _invisible(attrs):
             return self.shape(attrs)
         path = Path.from_svg(d)
         return self.shape(attrs, path) + [Scene.markers(path, *refs, stroke_width=parse_float(attrs.get("stroke-width", "1")))]
@@ -1130,14 +1237,17 @@ class _Loader:
         def walk(element, attrs, pen, after_blank):
             out, pen, after_blank = run(element.text, attrs, pen, after_blank)
             # whether children are descended into is decided by the tag of ``element`` itself (S:3766-3767)
-            descend = element.tag.split("}")[-1] in ("text", "tspan")
+            descend = element.tag.split("}")[-1] in ("text", "tspan", "a")   # (<a> inside text is a <tspan>)
             for child in element:
-                if descend and child.tag.split("}")[-1] == "textPath":   # (beyond the reference; the pen stays where it is)
-                    nodes = self.text_path(child, _expand_style(child.attrib, attrs))
+                own = self.props(child, attrs) if descend else None
+                if own is not None and _display_none(own):   # (sets nothing and advances nothing)
+                    pass
+                elif descend and child.tag.split("}")[-1] == "textPath":   # (beyond the reference; the pen stays where it is)
+                    nodes = self.text_path(child, own)
                     on_path.extend(nodes)
                     out.extend(nodes)
                 elif descend:
-                    nodes, pen, after_blank = walk(child, _expand_style(child.attrib, attrs), pen, after_blank)
+                    nodes, pen, after_blank = walk(child, own, pen, after_blank)
                     out.extend(nodes)
                 nodes, pen, after_blank = run(child.tail, attrs, pen, after_blank)
                 out.extend(nodes)
@@ -1213,8 +1323,10 @@ class _Loader:
         def walk(element, attrs, after_blank, moves):
             after_blank = run(element.text, attrs, after_blank, moves)
             for child in element:
-                if child.tag.split("}")[-1] == "tspan":
-                    after_blank = walk(child, _expand_style(child.attrib, attrs), after_blank, moves)
+                if child.tag.split("}")[-1] in ("tspan", "a"):
+                    own = self.props(child, attrs)
+                    if not _display_none(own):
+                        after_blank = walk(child, own, after_blank, moves)
                 after_blank = run(child.tail, attrs, after_blank, moves)
             return after_blank
 
@@ -1222,6 +1334,49 @@ class _Loader:
         if not runs:
             return []
         return [Scene.text_on_path(path, runs, offset, percent, length, None if anchor is None else _keyword(anchor), self.shape)]
+
+    def passes(self, element) -> bool:
+        """Whether a child of <switch> passes its conditions.  ``requiredExtensions``: any value fails, even an empty one (no
+        extension is implemented); ``requiredFeatures`` always passes (SVG 2); ``systemLanguage``: a comma list that passes when
+        one entry is one of the loader's `languages` or a prefix of one up to a ``-``, compared case-insensitively."""
+        attrib = element.attrib
+        if attrib.get("requiredExtensions") is not None:
+            return False
+        wanted = attrib.get("systemLanguage")
+        if wanted is None:
+            return True
+        for entry in wanted.split(","):
+            entry = _keyword(entry)
+            if entry and any(tag == entry or tag.startswith(entry + "-") for tag in self.languages):
+                return True
+        return False
+
+    def symbol(self, element, attrs, inherit) -> Symbol:
+        """<symbol> -> Symbol (beyond the reference); its content inherits from the place of definition, as a marker's does."""
+        content = self.children(element, inherit)
+        par = attrs.get("preserveAspectRatio", "xMidYMid meet")
+        try:
+            parse_preserve_aspect_ratio(par)
+        except ValueError:
+            warnings.warn(f"invalid preserveAspectRatio: {par!r}, using xMidYMid meet")
+            par = "xMidYMid meet"
+        try:
+            viewbox = parse_floats(attrs.get("viewBox"), 4, 4)
+        except ValueError:
+            warnings.warn(f"invalid symbol viewBox: {attrs.get('viewBox')}")
+            viewbox = None
+
+        def size(key, default=None):
+            text = attrs.get(key)
+            if text is not None and text.strip().endswith("%"):
+                warnings.warn(f"symbol: {key}=\"{text.strip()}\" needs the viewport, which is not known here: ignored")
+                return default
+            value = parse_size(text, default)
+            return default if value is None or not math.isfinite(value) else value
+
+        return Symbol(Scene.group(content) if content else None, None if viewbox is None else tuple(viewbox), par,
+                      size("x", 0.0), size("y", 0.0), size("width"), size("height"),
+                      _keyword(attrs.get("overflow", "hidden")) not in ("visible", "auto"))
 
     def children(self, element, inherit) -> list:
         out = []
@@ -1237,6 +1392,8 @@ class _Loader:
         scene = Scene.group(group)
         x, y = parse_size(attrs.get("x", "0")), parse_size(attrs.get("y", "0"))
         w, h = parse_size(attrs.get("width")), parse_size(attrs.get("height"))
+        if element in self.use_size:   # (a <use> with a size: its width and height override the target's)
+            w, h = (given if given is not None else own for given, own in zip(self.use_size[element], (w, h)))
         viewbox = [0, 0, w, h] if w is not None and h is not None else None
         width = self.width if top else None
         if width is not None:
@@ -1264,24 +1421,42 @@ class _Loader:
 
     def element(self, element, inherit, top=False) -> list:
         tag = element.tag.split("}")[-1]
-        attrs = _expand_style(element.attrib, inherit)
+        attrs = self.props(element, inherit)
         if "marker" in attrs:   # (the shorthand, never handed down itself: this element's; its own longhands go first)
-            short, own = attrs.pop("marker"), _expand_style(element.attrib)
+            short, own = attrs.pop("marker"), self.props(element)
             attrs.update({k: short for k in _MARKER_PROPERTIES if k not in own})
-        inherit = {k: v for k, v in attrs.items() if k in _INHERITED}
         ids = self.ids
+        if tag in _DISPLAYED and _display_none(attrs):   # (nothing of it or below it; its id stays known, and stands for nothing)
+            if attrs.get("id") is not None:
+                ids[attrs["id"]] = _NOTHING
+            return []
+        up = inherit
+        inherit = {k: v for k, v in attrs.items() if k in _INHERITED}
         group: list = []
         if tag == "svg":
+            if not top and attrs.get("id") is not None:
+                self.viewports[attrs["id"]] = (element, up)
             group = self.svg(element, attrs, inherit, top)
         elif tag == "path":
             group = self.marked_shape(attrs)
-        elif tag == "g":
+        elif tag in ("g", "a"):   # (a link is a group; links are not recorded)
             group = self.children(element, inherit)
+        elif tag == "switch":   # (the first direct child that passes its conditions, and nothing else)
+            for child in element:
+                if self.passes(child):
+                    group = self.element(child, inherit)
+                    break
+        elif tag in ("style", "foreignObject"):   # (the sheets were read before the walk; foreign content draws nothing)
+            return []
+        elif tag == "symbol":   # (never drawn where it stands)
+            if attrs.get("id") is not None:
+                ids[attrs["id"]] = self.symbol(element, attrs, inherit)
+            return []
         elif tag == "defs":
             self.children(element, inherit)
         elif tag in ("linearGradient", "radialGradient"):
             if attrs.get("id") is not None:
-                ids[attrs["id"]] = _gradient(element, tag == "linearGradient")
+                ids[attrs["id"]] = _gradient(element, tag == "linearGradient", None if self.matcher is None else self)
             return []
         elif tag == "clipPath":
             inherit.setdefault("fill-rule", attrs.get("clip-rule"))
@@ -1347,7 +1522,7 @@ class _Loader:
         elif tag in ("title", "desc", "metadata"):
             return []
         elif tag == "font":
-            font = _font(element)
+            font = _font(element, None if self.matcher is None else self)
             if font is not None:
                 self.fonts.register(font, attrs.get("id"))
                 if attrs.get("id") is not None:
@@ -1364,7 +1539,26 @@ class _Loader:
                 href = next((v for k, v in attrs.items() if k.endswith("}href")), None)
             if href and href.startswith("#"):
                 item = ids.get(href[1:])
-                if isinstance(item, Scene):
+                size = (None, None)
+                if isinstance(item, Symbol) or href[1:] in self.viewports:   # (what a width and a height mean something to)
+                    size = [attrs.get(key) for key in ("width", "height")]
+                    if any(v is not None and v.strip().endswith("%") for v in size):
+                        warnings.warn("use: a percentage width or height needs the viewport, which is not known here: ignored")
+                        size = [None if v is not None and v.strip().endswith("%") else v for v in size]
+                    size = tuple(parse_size(v) for v in size)
+                if isinstance(item, Symbol):
+                    placed = item.instance(0.0, 0.0, *size)   # (x and y are in the transform already)
+                    group = [] if placed is None else [placed]
+                elif isinstance(item, Scene) and href[1:] in self.viewports and any(v is not None for v in size):
+                    target, where = self.viewports[href[1:]]
+                    if target not in self.use_size:   # (not a <use> of an <svg> from inside itself)
+                        self.use_size[target] = size
+                        try:
+                            group = self.element(target, where)
+                        finally:
+                            del self.use_size[target]
+                            ids[href[1:]] = item
+                elif isinstance(item, Scene) and item is not _NOTHING:
                     group = [item]
         elif tag == "image":
             group = self.image(attrs)
@@ -1419,13 +1613,17 @@ class _Loader:
         return group
 
 
-def svg_scene(file, fg=None, width=None, fonts=None, base_dir=None):
+def svg_scene(file, fg=None, width=None, fonts=None, base_dir=None, *, css=None, languages=("en",)):
     """Load an SVG document from a file object: ``(Scene | None, ids, size)`` with ``size = (width, height)`` of the
     outermost viewport (S:2803-3083).  ``width`` rescales the document to that many pixels, ``fg`` replaces the default
     black of shapes without a ``fill``, ``fonts`` is the ``FontsDB`` text is set from (<font> elements of the document are
-    added to it), ``base_dir`` the directory relative <image> files are read from (None: only data URIs)."""
-    loader = _Loader(fg, width, fonts, base_dir)
+    added to it), ``base_dir`` the directory relative <image> files are read from (None: only data URIs).  ``css``: extra
+    author style, text or a ``Stylesheet``, that goes after the document's own <style> sheets (at equal specificity it wins);
+    ``languages``: the language tags a <switch> tests ``systemLanguage`` against.  Nothing outside the document is read for
+    style: ``<?xml-stylesheet?>``, <link> and ``@import`` are never fetched."""
+    loader = _Loader(fg, width, fonts, base_dir, languages)
     root = etree.parse(file).getroot()
+    loader.stylesheets(root, css)
     inherit = dict(color=np.array([0.0, 0.0, 0.0, 1.0]) if fg is None else fg)
     group = loader.element(root, inherit, top=True)
     if not group:
@@ -1433,18 +1631,18 @@ def svg_scene(file, fg=None, width=None, fonts=None, base_dir=None):
     return Scene.group(group), loader.ids, loader.size
 
 
-def svg_scene_from_str(text: str, fg=None, width=None, fonts=None):
-    return svg_scene(io.StringIO(text), fg, width, fonts)
+def svg_scene_from_str(text: str, fg=None, width=None, fonts=None, *, css=None, languages=("en",)):
+    return svg_scene(io.StringIO(text), fg, width, fonts, css=css, languages=languages)
 
 
-def svg_scene_from_filepath(path: str, fg=None, width=None, fonts=None):
+def svg_scene_from_filepath(path: str, fg=None, width=None, fonts=None, *, css=None, languages=("en",)):
     path = os.path.expanduser(path)
     base_dir = os.path.dirname(os.path.abspath(path))
     if os.path.splitext(path)[1] in (".gz", ".svgz"):
         with gzip.open(path, mode="rt", encoding="utf-8") as f:
-            return svg_scene(f, fg, width, fonts, base_dir)
+            return svg_scene(f, fg, width, fonts, base_dir, css=css, languages=languages)
     with open(path, encoding="utf-8") as f:
-        return svg_scene(f, fg, width, fonts, base_dir)
+        return svg_scene(f, fg, width, fonts, base_dir, css=css, languages=languages)
 
 
 def _output_format(output, format):
@@ -1458,7 +1656,7 @@ def _output_format(output, format):
 
 def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transform=None, linear_rgb=False, fonts=None,
                level=None, threads=None, format=None, quality: int = 90, subsampling: str = "4:2:0", *, encoder: str = "host",
-               filter=None, huffman=None):
+               filter=None, huffman=None, css=None, languages=("en",)):
     """Document in, PNG out: the steps of the reference's command line (S:3796-3877) as one library call, every pixel
     operation on the device.  ``svg`` is a file path or a file object; ``bg`` / ``fg`` are colours as ``parse_color``
     returns them; ``id`` renders a single element (on its own bounding box); ``transform`` is applied on top of the x/y
@@ -1471,7 +1669,7 @@ def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transfor
     ``.jpe`` (any case) and is PNG otherwise.  (Before JPEG output existed such a path received PNG bytes.)  A JPEG goes
     through ``Layer.write_jpeg`` with ``quality`` and ``subsampling``: it has no alpha, so the image lies over ``bg``, or over
     opaque white when there is none; its colour transform, DCT and quantiser run on the device, which makes it far quicker
-    to write than the PNG."""
+    to write than the PNG.  ``css`` and ``languages`` are ``svg_scene``'s."""
     format = _output_format(output, format)
     if format == "png":   # (bad arguments are refused before the document is read)
         from . import png as png_encoder  # noqa: PLC0415
@@ -1481,13 +1679,19 @@ def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transfor
     if transform is not None:
         view = view @ transform
     if isinstance(svg, (str, os.PathLike)):
-        scene, ids, size = svg_scene_from_filepath(os.fspath(svg), fg=fg, width=width, fonts=fonts)
+        scene, ids, size = svg_scene_from_filepath(os.fspath(svg), fg=fg, width=width, fonts=fonts, css=css, languages=languages)
     else:
-        scene, ids, size = svg_scene(svg, fg=fg, width=width, fonts=fonts)
+        scene, ids, size = svg_scene(svg, fg=fg, width=width, fonts=fonts, css=css, languages=languages)
     if scene is not None and id is not None:
         scene, size = ids.get(id), None
-        if not isinstance(scene, Scene):
+        if isinstance(scene, Symbol):   # (a symbol by id: one instance at the origin, on its own viewport when it has one)
+            symbol = scene
+            scene, size = symbol.instance(0, 0, None, None), symbol.viewport()
+            size = None if None in size else size
+        elif not isinstance(scene, Scene):
             raise KeyError(f"no object with id: {id}")
+        if scene is _NOTHING:
+            return None
     if scene is None:
         return None
     if size is not None:
