@@ -43,7 +43,8 @@ extern "C" {
  *    feSpecularLighting); svgr_layer_mix_blend and SVGR_BLEND_* added (CSS mix-blend-mode); svgr_jpeg_entropy and
  *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile); svgr_jpeg_encode,
  *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output); svgr_png_filter, svgr_deflate and
- *    svgr_deflate_chunk added (the device PNG encoder) */
+ *    svgr_deflate_chunk added (the device PNG encoder); svgr_layer_to_tensor, svgr_tensor_to_layer, svgr_tensor_block,
+ *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -811,6 +812,65 @@ int svgr_png_filter(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int6
 #define SVGR_DEFLATE_NO_ROOM 5   /* the output buffer is too small */
 int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out);
 int svgr_deflate_chunk(void);
+
+/* Tensor output (Layer.to_tensor / Layer.to_array, beyond the reference): a layer packed into the element type and layout a
+ * framework wants, written by the kernel into memory the caller names -- a svgr_buf of the library's or a wrapped pointer
+ * (svgr_buf_wrap of torch's data_ptr()).  Per pixel, in double (csrc/svgr_tensor.h):
+ *   source      the RGBA pixel as the caller prepared it (svgr_layer_convert for colour space and alpha state): a float64 RGBA
+ *               layer, a float32 RGBA canvas (widened exactly) or a float64 1-channel mask (broadcast to all four channels)
+ *   background  has_bg, premultiplied input only: c = c + bg[c] * (1 - a) for the three colours, then a = 1
+ *   channels    RGBA (4), RGB (3), ALPHA (1), LUMA (1: svgr_layer_luminance's weights and order, not multiplied by alpha)
+ *   affine      y = v * scale[k] + bias[k] per output channel ((v - mean) / std arrives as scale = 1 / std, bias = -mean / std)
+ *   dtype       F32: y rounded to nearest-even; F16 / BF16: that float32 rounded to nearest-even again (overflow gives infinity,
+ *               subnormals are kept, NaN leaves as the type's quiet NaN); U8: rint(y * 255) saturated to [0, 255], NaN gives 0
+ *               (with identity affine, RGBA and straight sRGB input: the bytes of svgr_layer_to_rgba8)
+ * The tensor is a rows x cols plane of `channels` elements per pixel, addressed in ELEMENTS: pixel (r, c)'s channel k is element
+ * offset + k * stride_c + r * stride_h + c * stride_w.  Planar (CHW): stride_w == 1, stride_h >= cols, stride_c free.
+ * Interleaved (HWC): stride_c == 1, stride_w == channels, stride_h >= cols * channels.  So the destination may be one slice of a
+ * batch or a window of a larger picture, its rows beginning at any element alignment. */
+#define SVGR_TENSOR_SRC_RGBA_F64 0
+#define SVGR_TENSOR_SRC_RGBA_F32 1
+#define SVGR_TENSOR_SRC_MASK_F64 2
+#define SVGR_TENSOR_F32 0
+#define SVGR_TENSOR_F16 1
+#define SVGR_TENSOR_BF16 2
+#define SVGR_TENSOR_U8 3
+#define SVGR_TENSOR_RGBA 0
+#define SVGR_TENSOR_RGB 1
+#define SVGR_TENSOR_ALPHA 2
+#define SVGR_TENSOR_LUMA 3
+typedef struct {
+    int32_t source;    /* SVGR_TENSOR_SRC_*: what the layer side holds (svgr_tensor_to_layer always writes float64) */
+    int32_t dtype;     /* SVGR_TENSOR_F32 / F16 / BF16 / U8 */
+    int32_t channels;  /* SVGR_TENSOR_RGBA / RGB / ALPHA / LUMA */
+    int32_t has_bg;    /* 0 or 1 */
+    double bg[3];
+    double scale[4], bias[4];   /* per output channel; entries beyond the channel count are ignored (but must be finite) */
+    int64_t rows, cols;         /* the plane */
+    int64_t stride_c, stride_h, stride_w, offset;   /* in elements */
+} svgr_tensor_desc;
+/* svgr_layer_to_tensor: dst <- the plane packed as `desc` says; src_bbox {row0, col0, rows, cols} places the source on the plane
+ * (negative offsets and partial overlap are fine: outside the box the pixel is (0, 0, 0, 0), which background and affine then
+ * see like any other).  Every element of the plane is written, nothing else of dst is touched.  One launch on the context's
+ * stream, no wait.  A workgroup packs svgr_tensor_block() consecutive pixels of one row, a lane svgr_tensor_run() of them; the
+ * stores of a row's aligned interior are 16 bytes wide.
+ * svgr_tensor_to_layer: the inverse, element -> double exactly (U8: v / 255): dst_f64 <- rows * cols pixels of 4 doubles
+ * (RGBA; RGB with a = 1) or of 1 double (ALPHA, LUMA); bg, scale and bias are not applied.
+ * SVGR_E_INVALID, before anything is launched: an unknown enum, has_bg not 0 / 1, a stride combination that is neither planar nor
+ * interleaved, a negative stride, size or offset, a stride_h below the row's elements, a scale, bias or bg that is not finite, a
+ * tensor pointer that is not a multiple of the element size, a short layer buffer, and the largest element index -- from
+ * strides, sizes and offset -- reaching past svgr_buf_bytes() of the tensor.  rows * cols == 0 launches nothing and succeeds,
+ * with ctx == NULL too. */
+int svgr_layer_to_tensor(svgr_ctx* ctx, const svgr_tensor_desc* desc, const svgr_buf* src, const int64_t* src_bbox, svgr_buf* dst);
+int svgr_tensor_to_layer(svgr_ctx* ctx, const svgr_tensor_desc* desc, const svgr_buf* src, svgr_buf* dst_f64);
+int svgr_tensor_block(void);
+int svgr_tensor_run(void);
+/* Ordering against another stream of the same runtime (torch.cuda.current_stream().cuda_stream) without moving the context
+ * onto it (svgr_set_stream drains and destroys the context's own stream).  svgr_stream_wait_for: the context's stream waits for
+ * all work enqueued on `other` so far.  svgr_stream_signal_to: `other` waits for all work enqueued on the context's stream so
+ * far.  Each through an event the context keeps; neither blocks the host.  other == NULL is the runtime's default stream. */
+int svgr_stream_wait_for(svgr_ctx* ctx, void* other);
+int svgr_stream_signal_to(svgr_ctx* ctx, void* other);
 
 #ifdef __cplusplus
 }

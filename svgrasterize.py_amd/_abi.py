@@ -84,6 +84,17 @@ class JpegScan(C.Structure):  # svgr_jpeg_scan
     ]
 
 
+class TensorDesc(C.Structure):  # svgr_tensor_desc
+    _fields_ = [
+        ("source", C.c_int32), ("dtype", C.c_int32), ("channels", C.c_int32), ("has_bg", C.c_int32), ("bg", C.c_double * 3),
+        ("scale", C.c_double * 4), ("bias", C.c_double * 4), ("rows", C.c_int64), ("cols", C.c_int64),
+        ("stride_c", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64), ("offset", C.c_int64),
+    ]
+
+
+TENSOR_SRC_RGBA_F64, TENSOR_SRC_RGBA_F32, TENSOR_SRC_MASK_F64 = 0, 1, 2
+TENSOR_F32, TENSOR_F16, TENSOR_BF16, TENSOR_U8 = 0, 1, 2, 3
+TENSOR_RGBA, TENSOR_RGB, TENSOR_ALPHA, TENSOR_LUMA = 0, 1, 2, 3
 JPEG_GREY, JPEG_YCBCR, JPEG_RGB = 0, 1, 2
 _JPEG_STATUS = {1: "the entropy-coded data ends before the scan does", 2: "a bad Huffman table or code",
                 3: "a restart marker is missing or out of sequence", 4: "a run of zeros leads past the end of the block"}
@@ -199,6 +210,12 @@ _PROTOS = {
     "svgr_png_filter": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     "svgr_deflate": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "svgr_deflate_chunk": (C.c_int, []),
+    "svgr_layer_to_tensor": (C.c_int, [_P, C.POINTER(TensorDesc), _P, _P, _P]),
+    "svgr_tensor_to_layer": (C.c_int, [_P, C.POINTER(TensorDesc), _P, _P]),
+    "svgr_tensor_block": (C.c_int, []),
+    "svgr_tensor_run": (C.c_int, []),
+    "svgr_stream_wait_for": (C.c_int, [_P, _P]),
+    "svgr_stream_signal_to": (C.c_int, [_P, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -168,6 +168,7 @@ struct svgr_ctx {
     hipEvent_t side_ev[N_SIDE] = {};
     hipEvent_t fork_ev = nullptr;
     bool side_ready = false;
+    hipEvent_t xs_ev[2] = {nullptr, nullptr};    // svgr_stream_wait_for / svgr_stream_signal_to: the mark each records on the stream waited for
 };
 // the context whose call is running on this thread (set by enter_ctx at the top of every entry point): the block cache
 // files what is allocated and released under it
@@ -5416,6 +5417,7 @@ int svgr_shutdown(svgr_ctx* ctx) {
         if (ctx->side_ev[k]) (void)hipEventDestroy(ctx->side_ev[k]);
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
+    for (auto e : ctx->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto e : ctx->meas_ev) if (e) (void)hipEventDestroy(e);
     if (ctx->pin_ev) (void)hipEventDestroy(ctx->pin_ev);
     delete ctx->spare;
@@ -9103,5 +9105,227 @@ int svgr_png_filter(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int6
 }
 int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out) {
     return abi_guard("svgr_deflate", [&]() { return deflate_impl(ctx, src, n_bytes, huffman, out, out_cap, n_out); });
+}
+}  // extern "C"
+
+// ======================================================================================
+// tensor output: svgr_layer_to_tensor / svgr_tensor_to_layer (csrc/svgr_tensor.h has the per-pixel arithmetic, DESIGN.md 7p the
+// rest), and the two stream-ordering entries
+// ======================================================================================
+#include "svgr_tensor.h"
+
+// k_tensor_pack is a transposition from 32-byte (or 16-byte) pixels to narrow planes, through LDS: a workgroup takes TENSOR_BLOCK
+// consecutive pixels of ONE row (rows are strided: nothing runs across a row's end).
+//   phase 1  lane t takes the pixels t, t + 256, ...: consecutive lanes read consecutive pixels (a double4 apiece: whole cache
+//            lines per instruction), run them through tensor_px / tensor_encode, and put the ELEMENTS -- 1, 2 or 4 bytes --
+//            into LDS, a row per plane.  What is transposed is the narrow result, not the doubles
+//   phase 2  the LDS rows go out in 16-byte units, a unit per lane: TENSOR_RUN pixels of a 2-byte plane.  An element sits in
+//            LDS at its GLOBAL element address modulo a unit, so a unit is aligned in LDS exactly when it is in memory, wherever
+//            the row begins: the stores of a row's interior are all dwordx4.  For that a workgroup's share of a plane's row
+//            does not end at its pixels' ends but at the unit boundary at or below them (it reaches back TENSOR_MARGIN elements
+//            at most into the pixels of the workgroup before, which it converts again: 16 of 2048); only the first
+//            workgroup's head and the last one's tail, the row's own ragged ends, are stored element by element
+// An interleaved destination is one plane of cols * channels elements per row.
+constexpr int TENSOR_LANES = 256, TENSOR_RUN = 8, TENSOR_BLOCK = TENSOR_LANES * TENSOR_RUN, TENSOR_MARGIN = 16;
+struct TensorLaunch {
+    TensorOp op;
+    int src_kind, n_ch;
+    int planes, per_px;        // planar: n_ch planes of 1 element per pixel; interleaved: 1 plane of n_ch
+    long long s0, s1, srows, scols;
+    long long rows, cols;
+    long long stride_p, stride_h, offset;   // elements
+};
+static_assert(SVGR_TENSOR_SRC_RGBA_F64 == TENSOR_SRC_RGBA_F64 && SVGR_TENSOR_SRC_RGBA_F32 == TENSOR_SRC_RGBA_F32 &&
+              SVGR_TENSOR_SRC_MASK_F64 == TENSOR_SRC_MASK_F64 && SVGR_TENSOR_F32 == TENSOR_F32 && SVGR_TENSOR_F16 == TENSOR_F16 &&
+              SVGR_TENSOR_BF16 == TENSOR_BF16 && SVGR_TENSOR_U8 == TENSOR_U8 && SVGR_TENSOR_RGBA == TENSOR_RGBA &&
+              SVGR_TENSOR_RGB == TENSOR_RGB && SVGR_TENSOR_ALPHA == TENSOR_ALPHA && SVGR_TENSOR_LUMA == TENSOR_LUMA, "tensor enums");
+
+template <class T>   // the element: uint32_t (F32), uint16_t (F16, BF16), uint8_t (U8)
+__global__ __launch_bounds__(TENSOR_LANES) void k_tensor_pack(T* __restrict__ dst, const void* __restrict__ src, const TensorLaunch a) {
+    constexpr long long E = 16 / sizeof(T);                     // elements of a unit
+    constexpr int PLANE = 4 * (TENSOR_BLOCK + 2 * TENSOR_MARGIN);   // elements of LDS: four planes of a block and its margins (planar RGBA)
+    __shared__ __align__(16) T lds[PLANE];                          // (interleaved RGBA: one plane of 4 * TENSOR_BLOCK + 2 * TENSOR_MARGIN)
+    const int tid = threadIdx.x, Q = a.per_px, plane_lds = Q * TENSOR_BLOCK + 2 * TENSOR_MARGIN;
+    const long long C0 = (long long)blockIdx.x * TENSOR_BLOCK, C1 = C0 + TENSOR_BLOCK < a.cols ? C0 + TENSOR_BLOCK : a.cols;
+    const long long J0 = C0 * Q, J1 = C1 * Q;                          // this workgroup's pixels as elements of a plane's row
+    const long long jlo = J0 > TENSOR_MARGIN ? J0 - TENSOR_MARGIN : 0;  // the first element it may have to provide
+    const long long clo = jlo / Q;
+    const long long abs0 = (long long)((uintptr_t)dst / sizeof(T));     // the tensor's first element as an absolute element address
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        // plane p's row begins at absolute element gb[p]; the element j of it sits in LDS at gb[p] + j - lb[p], lb a unit boundary
+        long long gb[4], lb[4];
+        SVGR_UNROLL
+        for (int p = 0; p < 4; ++p) {
+            gb[p] = abs0 + a.offset + (long long)p * a.stride_p + row * a.stride_h;
+            lb[p] = (gb[p] + jlo) & ~(E - 1);
+        }
+        // ---- phase 1
+        const int n_px = (int)(C1 - clo);
+        for (int i = tid; i < n_px; i += TENSOR_LANES) {
+            const long long col = clo + i;
+            double px[4], y[4];
+            tensor_load_px(src, a.src_kind, row, col, a.s0, a.s1, a.srows, a.scols, px);
+            const int n = tensor_px(a.op, px[0], px[1], px[2], px[3], y);
+            SVGR_UNROLL
+            for (int k = 0; k < 4; ++k) {
+                if (k >= n) break;
+                const T v = (T)tensor_encode(a.op.dtype, y[k]);
+                if (Q == 1) lds[k * plane_lds + (int)(gb[k] + col - lb[k])] = v;
+                else if (col * Q + k >= jlo) lds[(int)(gb[0] + col * Q + k - lb[0])] = v;
+            }
+        }
+        __syncthreads();
+        // ---- phase 2
+        for (int p = 0; p < a.planes; ++p) {
+            const long long g = p == 0 ? gb[0] : p == 1 ? gb[1] : p == 2 ? gb[2] : gb[3], l = p == 0 ? lb[0] : p == 1 ? lb[1] : p == 2 ? lb[2] : lb[3];
+            // this workgroup's share [js, je) of the plane's row: from unit boundary to unit boundary, the row's own ends as they are
+            const long long js = C0 == 0 ? 0 : J0 - ((g + J0) & (E - 1)), je = C1 == a.cols ? J1 : J1 - ((g + J1) & (E - 1));
+            const int is = (int)(g + js - l), ie = (int)(g + je - l);   // the same in LDS positions
+            const T* lp = lds + p * plane_lds;
+            T* gp = (T*)(uintptr_t)(l * (long long)sizeof(T));          // LDS position i is the element gp[i]
+            for (int u = is / (int)E + tid; u * (int)E < ie; u += TENSOR_LANES) {
+                const int i0 = u * (int)E;
+                if (i0 >= is && i0 + (int)E <= ie) {
+                    *(uint4*)(gp + i0) = *(const uint4*)(lp + i0);
+                } else {
+                    for (int i = i0 > is ? i0 : is; i < i0 + (int)E && i < ie; ++i) gp[i] = lp[i];
+                }
+            }
+        }
+        __syncthreads();   // (the next row writes the same LDS)
+    }
+}
+
+// the inverse: a lane per pixel (consecutive lanes read consecutive elements of a plane, or consecutive pixels of an interleaved row)
+template <class T>
+__global__ __launch_bounds__(256) void k_tensor_unpack(double* __restrict__ dst, const T* __restrict__ src, const TensorLaunch a, long long stride_c,
+                                                       long long stride_w) {
+    const long long col = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= a.cols) return;
+    for (long long row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        double v[4], px[4];
+        SVGR_UNROLL
+        for (int k = 0; k < 4; ++k)
+            if (k < a.n_ch) v[k] = tensor_decode(a.op.dtype, (uint32_t)src[a.offset + k * stride_c + row * a.stride_h + col * stride_w]);
+        const int n = tensor_unpack_px(a.op.channels, v, px);
+        double* o = dst + (row * a.cols + col) * n;
+        if (n == 4) *(double4*)o = make_double4(px[0], px[1], px[2], px[3]);
+        else o[0] = px[0];
+    }
+}
+
+// Everything of a description that can be wrong, and the launch's numbers from it.  `tensor_bytes`: of the buffer on the tensor's
+// side, `tensor_ptr` its address.  *empty: nothing to do.
+static int tensor_check(const char* entry, const svgr_tensor_desc* d, TensorLaunch& a, long long& stride_c, long long& stride_w, bool& empty) {
+    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
+    if (d->source < 0 || d->source >= TENSOR_SRC_KINDS) return fail(SVGR_E_INVALID, "%s: unknown source kind %d", entry, (int)d->source);
+    if (d->dtype < 0 || d->dtype >= TENSOR_DTYPES) return fail(SVGR_E_INVALID, "%s: unknown dtype %d", entry, (int)d->dtype);
+    if (d->channels < 0 || d->channels >= TENSOR_CHANNEL_KINDS) return fail(SVGR_E_INVALID, "%s: unknown channel selection %d", entry, (int)d->channels);
+    if (d->has_bg != 0 && d->has_bg != 1) return fail(SVGR_E_INVALID, "%s: has_bg is 0 or 1", entry);
+    constexpr int64_t kMaxSide = 1ll << 30, kMaxStride = 1ll << 40;
+    if (d->rows < 0 || d->cols < 0 || d->rows >= kMaxSide || d->cols >= kMaxSide) return fail(SVGR_E_INVALID, "%s: rows and cols are 0 .. 2^30 - 1", entry);
+    if (d->stride_c < 0 || d->stride_h < 0 || d->stride_w < 0 || d->offset < 0 || d->stride_c > kMaxStride || d->stride_h > kMaxStride ||
+        d->stride_w > kMaxStride || d->offset > (1ll << 50))
+        return fail(SVGR_E_INVALID, "%s: a stride or the offset is negative (or beyond 2^40)", entry);
+    const int n_ch = tensor_n_channels(d->channels);
+    const bool planar = d->stride_w == 1, interleaved = !planar && d->stride_c == 1 && d->stride_w == n_ch;
+    if (!planar && !interleaved)
+        return fail(SVGR_E_INVALID, "%s: strides (%lld, %lld, %lld) are neither planar (stride_w 1) nor interleaved (stride_c 1, stride_w %d)", entry,
+                    (long long)d->stride_c, (long long)d->stride_h, (long long)d->stride_w, n_ch);
+    const int per_px = planar ? 1 : n_ch;
+    if (d->stride_h < d->cols * per_px) return fail(SVGR_E_INVALID, "%s: stride_h %lld is below the row's %lld elements", entry, (long long)d->stride_h, (long long)(d->cols * per_px));
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(d->scale[k]) || !std::isfinite(d->bias[k]) || (k < 3 && !std::isfinite(d->bg[k])))
+            return fail(SVGR_E_INVALID, "%s: scale, bias and bg must be finite", entry);
+    memset(&a, 0, sizeof a);
+    a.op.dtype = d->dtype; a.op.channels = d->channels; a.op.has_bg = d->has_bg;
+    for (int k = 0; k < 4; ++k) {
+        a.op.scale[k] = d->scale[k]; a.op.bias[k] = d->bias[k];
+        if (k < n_ch && (d->scale[k] != 1.0 || d->bias[k] != 0.0)) a.op.affine = 1;
+        if (k < 3) a.op.bg[k] = d->bg[k];
+    }
+    a.src_kind = d->source; a.n_ch = n_ch;
+    a.planes = planar ? n_ch : 1; a.per_px = per_px;
+    a.rows = d->rows; a.cols = d->cols;
+    a.stride_p = planar ? d->stride_c : 0; a.stride_h = d->stride_h; a.offset = d->offset;
+    stride_c = d->stride_c; stride_w = d->stride_w;
+    empty = d->rows == 0 || d->cols == 0;
+    return 0;
+}
+// the tensor's side of either entry: the buffer holds the largest element the description reaches, and its address is an element's
+static int tensor_bounds(const char* entry, const svgr_tensor_desc* d, const TensorLaunch& a, const svgr_buf* t) {
+    const unsigned es = (unsigned)tensor_elem_bytes(d->dtype);
+    const unsigned __int128 last = (unsigned __int128)d->offset + (unsigned __int128)(a.planes - 1) * (unsigned __int128)a.stride_p +
+                                   (unsigned __int128)(d->rows - 1) * (unsigned __int128)d->stride_h + (unsigned __int128)(d->cols * a.per_px - 1);
+    if ((last + 1) * es > (unsigned __int128)t->bytes)
+        return fail(SVGR_E_INVALID, "%s: the largest element index %llu reaches past the tensor's %zu bytes (%u per element)", entry,
+                    (unsigned long long)last, t->bytes, es);
+    if ((uintptr_t)t->ptr % es) return fail(SVGR_E_INVALID, "%s: the tensor's address is no multiple of its element size", entry);
+    return 0;
+}
+
+extern "C" {
+int svgr_tensor_block(void) { return TENSOR_BLOCK; }
+int svgr_tensor_run(void) { return TENSOR_RUN; }
+
+int svgr_layer_to_tensor(svgr_ctx* ctx, const svgr_tensor_desc* desc, const svgr_buf* src, const int64_t* src_bbox, svgr_buf* dst) {
+    static const char* entry = "svgr_layer_to_tensor";
+    TensorLaunch a;
+    long long sc, sw;
+    bool empty;
+    if (int rc = tensor_check(entry, desc, a, sc, sw, empty)) return rc;
+    if (empty) return 0;
+    if (!src || !dst || !bbox_ok(src_bbox)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (int rc = tensor_bounds(entry, desc, a, dst)) return rc;
+    const size_t px_bytes = desc->source == TENSOR_SRC_RGBA_F64 ? 32 : desc->source == TENSOR_SRC_RGBA_F32 ? 16 : 8;
+    if (src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * px_bytes) return fail(SVGR_E_INVALID, "%s: the source buffer is too small for its box", entry);
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
+    a.s0 = src_bbox[0]; a.s1 = src_bbox[1]; a.srows = src_bbox[2]; a.scols = src_bbox[3];
+    const dim3 grid((unsigned)((a.cols + TENSOR_BLOCK - 1) / TENSOR_BLOCK), (unsigned)std::min<long long>(a.rows, 65535));
+    switch (tensor_elem_bytes(desc->dtype)) {
+        case 4: return launch_tail(ctx, k_tensor_pack<uint32_t>, grid, dim3(TENSOR_LANES), 0, (uint32_t*)dst->ptr, (const void*)src->ptr, a);
+        case 2: return launch_tail(ctx, k_tensor_pack<uint16_t>, grid, dim3(TENSOR_LANES), 0, (uint16_t*)dst->ptr, (const void*)src->ptr, a);
+        default: return launch_tail(ctx, k_tensor_pack<uint8_t>, grid, dim3(TENSOR_LANES), 0, (uint8_t*)dst->ptr, (const void*)src->ptr, a);
+    }
+}
+
+int svgr_tensor_to_layer(svgr_ctx* ctx, const svgr_tensor_desc* desc, const svgr_buf* src, svgr_buf* dst_f64) {
+    static const char* entry = "svgr_tensor_to_layer";
+    TensorLaunch a;
+    long long sc, sw;
+    bool empty;
+    if (int rc = tensor_check(entry, desc, a, sc, sw, empty)) return rc;
+    if (empty) return 0;
+    if (!src || !dst_f64) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (int rc = tensor_bounds(entry, desc, a, src)) return rc;
+    const size_t out_ch = desc->channels == TENSOR_RGBA || desc->channels == TENSOR_RGB ? 4 : 1;
+    if (dst_f64->bytes < (size_t)desc->rows * (size_t)desc->cols * out_ch * 8) return fail(SVGR_E_INVALID, "%s: the layer buffer is too small", entry);
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
+    const dim3 grid((unsigned)((a.cols + 255) / 256), (unsigned)std::min<long long>(a.rows, 65535));
+    switch (tensor_elem_bytes(desc->dtype)) {
+        case 4: return launch_tail(ctx, k_tensor_unpack<uint32_t>, grid, dim3(256), 0, (double*)dst_f64->ptr, (const uint32_t*)src->ptr, a, sc, sw);
+        case 2: return launch_tail(ctx, k_tensor_unpack<uint16_t>, grid, dim3(256), 0, (double*)dst_f64->ptr, (const uint16_t*)src->ptr, a, sc, sw);
+        default: return launch_tail(ctx, k_tensor_unpack<uint8_t>, grid, dim3(256), 0, (double*)dst_f64->ptr, (const uint8_t*)src->ptr, a, sc, sw);
+    }
+}
+
+// Both through an event of the context's own: recorded on the stream that is waited for, waited for on the other.  (An event
+// recorded again while an earlier wait on it is still pending is fine: a wait holds the record it was enqueued behind.)
+static int stream_order(svgr_ctx* ctx, int which, hipStream_t first, hipStream_t then) {
+    HIPCHK(enter_ctx(ctx));
+    if (!ctx->xs_ev[which]) HIPCHK(hipEventCreateWithFlags(&ctx->xs_ev[which], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ctx->xs_ev[which], first));
+    HIPCHK(hipStreamWaitEvent(then, ctx->xs_ev[which], 0));
+    return 0;
+}
+int svgr_stream_wait_for(svgr_ctx* ctx, void* other) {
+    if (!ctx) return fail(SVGR_E_INVALID, "ctx is NULL");
+    if ((hipStream_t)other == ctx->stream) return 0;
+    return stream_order(ctx, 0, (hipStream_t)other, ctx->stream);
+}
+int svgr_stream_signal_to(svgr_ctx* ctx, void* other) {
+    if (!ctx) return fail(SVGR_E_INVALID, "ctx is NULL");
+    if ((hipStream_t)other == ctx->stream) return 0;
+    return stream_order(ctx, 1, ctx->stream, (hipStream_t)other);
 }
 }  // extern "C"

@@ -723,6 +723,46 @@ class Layer:
         buf, rows, cols = self.background((1.0, 1.0, 1.0, 1.0) if bg is None else bg)._to_rgba8_device()
         return jpeg._encode_rgba8(buf, rows, cols, output, **args)
 
+    # -- tensor output (beyond the reference; tensor.py) -----------------------------------------------------------------------
+    def to_array(self, size=None, *, dtype=np.float32, layout="chw", channels="rgba", alpha="premultiplied", linear_rgb=False,
+                 bg=None, mean=None, std=None) -> np.ndarray:
+        """The layer packed on the device and downloaded as numpy: ``dtype`` float32, float16 or uint8 (rounded to nearest-even;
+        uint8 is ``round(v * 255)`` saturated), ``layout`` "chw" (planar) or "hwc", ``channels`` "rgba", "rgb", "alpha" or "luma".
+        ``size=(rows, cols)`` places the layer on a transparent plane at the origin, as ``on_canvas`` does; without it the plane
+        is the layer's own extent.  ``alpha`` ("premultiplied" or "straight") and ``linear_rgb`` say what the pixels are to be
+        (``Layer.convert``); ``bg``, three premultiplied colour values in that colour space, puts the picture over an opaque
+        background; ``mean`` / ``std`` (one value, or one per output channel) give ``(v - mean) / std``.  Only the packed
+        bytes cross PCIe: 2 per value for float16 where ``Layer.image`` moves 8.  Needs no torch."""
+        from . import tensor  # noqa: PLC0415
+
+        return tensor.to_array(self, size, dtype=dtype, layout=layout, channels=channels, alpha=alpha, linear_rgb=linear_rgb, bg=bg,
+                               mean=mean, std=std)
+
+    def to_tensor(self, out=None, size=None, *, dtype=None, layout="chw", channels="rgba", alpha="premultiplied", linear_rgb=False,
+                  bg=None, mean=None, std=None):
+        """``to_array`` into a ``torch.Tensor`` on the context's device, never leaving it.  ``dtype`` is torch.float32 (the
+        default), float16, bfloat16 or uint8.  ``out`` may be any view whose last three dimensions are (C, rows, cols) or
+        (rows, cols, C) with unit stride along a row's elements -- ``batch[n]``, a window ``big[:, 1:1 + rows, 3:3 + cols]`` --;
+        nothing outside it is written.  A wrong dtype is a TypeError, a wrong shape or device a ValueError, before any device
+        work.  The call orders itself against ``torch.cuda.current_stream()`` on the device: torch work queued on ``out``
+        before and after it is safe, and the host is not made to wait.  torch must have been imported, and have touched CUDA,
+        before this package's first call (tensor.py)."""
+        from . import tensor  # noqa: PLC0415
+
+        return tensor.to_tensor(self, out, size, dtype=dtype, layout=layout, channels=channels, alpha=alpha, linear_rgb=linear_rgb,
+                                bg=bg, mean=mean, std=std)
+
+    @staticmethod
+    def from_tensor(t, offset=(0, 0), pre_alpha=True, linear_rgb=False, channels=None, layout=None) -> "Layer":
+        """A device-resident layer from a ``torch.Tensor`` on the device (or a numpy array, which is uploaded as it is): float32,
+        float16, bfloat16 or uint8 (``v / 255``), widened exactly.  (C, rows, cols) or (rows, cols, C) -- told apart by which
+        end holds 1, 3 or 4, torch's channels-first when both do, or by ``layout`` --, or (rows, cols) alpha.  3 channels are RGB with
+        alpha 1; 1 channel (``channels`` "alpha" or "luma") gives a 1-channel layer.  ``pre_alpha`` and ``linear_rgb`` say what
+        the values ARE; nothing is converted."""
+        from . import tensor  # noqa: PLC0415
+
+        return tensor.from_tensor(t, offset, pre_alpha, linear_rgb, channels, layout)
+
     def __repr__(self):
         return "Layer(x={}, y={}, w={}, h={}, pre_alpha={}, linear_rgb={})".format(
             self.x, self.y, self.width, self.height, self.pre_alpha, self.linear_rgb
