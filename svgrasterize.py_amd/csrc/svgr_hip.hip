@@ -584,8 +584,13 @@ constexpr int FL_BLOCK = 256;     // (the waves are independent up to the last s
 // renders that follow.  Workgroups are dispatched in index order, so the lowest unfinished one is always resident and finds every
 // predecessor finished: the chain cannot stall.  (A dead-man count ends a look-back that does not return all the same: error bit
 // 2, the staged plan takes over.)
+// LEAN (with EMIT and PLACED): the placed pass of a replay that keeps its slab table (run_geometry).  Nobody reads what such a pass
+// leaves beside the edges -- k_path_bbox, the keys' only consumer, is not launched; the shard cursors are zeroed unread by the tile
+// kernel -- and its inputs are those of the full placed pass in front of it, whose counts were compared with the plan's: no
+// min / max keys (no fold, no LDS, no barrier, no atomics), no row reach, no counting atomic, no comparison of the counts.  The
+// traversal is the full form's, and every store stays inside the lane's own place and the array: `at < n_plan`, `edge_cap`.
 constexpr int FL_WAVES = 1;
-template <bool EMIT, bool PLACED = false, int SUB = FL_SUB, bool SCAN = false>
+template <bool EMIT, bool PLACED = false, int SUB = FL_SUB, bool SCAN = false, bool LEAN = false>
 __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __restrict__ segs, const uint8_t* __restrict__ kind,
                                                  const int* __restrict__ seg_path, const double* __restrict__ path_m6,
                                                  int n_segs, double thr, double* __restrict__ edges,
@@ -598,6 +603,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
                                                  unsigned long long* __restrict__ scan_state = nullptr) {
     static_assert(!PLACED || EMIT, "places are what an emitting pass takes");
     static_assert(!SCAN || (EMIT && !PLACED), "the scanning pass counts, places and stores");
+    static_assert(!LEAN || (EMIT && PLACED), "the lean form is a placed pass");
     // Where the edges go.  `seg_off` given (the renders and the plan's later passes): segment s owns the slots
     // [seg_off[s], seg_off[s + 1]) -- the exclusive prefix sums of the per-segment counts the plan's counting pass left in
     // `seg_cnt` -- and its lanes take them in curve order.  The edge array is then in (path, segment, curve) order whatever
@@ -648,7 +654,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
     // tracks min/max over ALL segments of such a path), but it only stores the edges of segments that can
     // reach one of its own bands (the curve stays inside the row range of its control points; +-1 row of slack).
     bool keep = true;
-    if (n_bands > 0 && mode != 0) {  // (also drops what lies entirely above / below the viewport)
+    if (!LEAN && n_bands > 0 && mode != 0) {  // (also drops what lies entirely above / below the viewport)
         double rlo = node[0] < node[6] ? node[0] : node[6], rhi = node[0] < node[6] ? node[6] : node[0];
         if (mode == 2) {
             rlo = fmin(rlo, fmin(node[2], node[4]));
@@ -665,6 +671,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
     }
     double mnr = INFINITY, mnc = INFINITY, mxr = -INFINITY, mxc = -INFINITY;
     auto track = [&](double r, double c) {
+        if constexpr (LEAN) return;
         mnr = r < mnr ? r : mnr; mxr = r > mxr ? r : mxr;
         mnc = c < mnc ? c : mnc; mxc = c > mxc ? c : mxc;
     };
@@ -706,9 +713,9 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
         }
         if (ovf) atomicOr(&bd->err, 1);
         // (a lane whose pieces cannot reach this rank's rows has an empty place; any other count that differs is not the plan's geometry)
-        if (keep && n_found != n_plan) atomicOr(&bd->err, 2);
+        if (!LEAN && keep && n_found != n_plan) atomicOr(&bd->err, 2);
         // (the shard cursors only count: their sum is the number of edges the pass kept)
-        if (seg_ok && sub == 0 && so1 > so0) atomicAdd(&bd->shard[(int)((blockIdx.x * (FL_BLOCK / 64) + (threadIdx.x >> 6)) % NSH)].cursor, so1 - so0);
+        if (!LEAN && seg_ok && sub == 0 && so1 > so0) atomicAdd(&bd->shard[(int)((blockIdx.x * (FL_BLOCK / 64) + (threadIdx.x >> 6)) % NSH)].cursor, so1 - so0);
     } else {
     const bool census = !EMIT && seg_cnt != nullptr;
     double rows_x = 0.0, cols_x = 0.0;
@@ -854,6 +861,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
         }
     }
     }  // (!PLACED)
+    if constexpr (!LEAN) {
     // fold the lanes of a segment, then one set of atomics per segment
 #pragma unroll
     for (int d = 1; d < (1 << SUB); d <<= 1) {
@@ -884,6 +892,7 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
         atomicMax(&k[2], f64_key(mxr));
         atomicMax(&k[3], f64_key(mxc));
     }
+    }  // (!LEAN)
 }
 
 // Plan only: exclusive prefix sums of the per-segment edge counts (seg_off[n] = their total).  One workgroup, a chunk of
@@ -4652,9 +4661,9 @@ struct svgr_batch {
     DevArr<int> slab_at;                    // per path: its first slab, heaviest paths first (staged plan; renders only)
     bool slab_at_valid = false;
     // A geometry pass has run k_path_bbox under the standing plan's `slab_at` order: `slabs`, `bbox` and `bins` hold the plan's places,
-    // and a replay under the same plan keeps them instead of launching the kernel again (run_geometry; k_path_build<1> checks the
-    // paths' keys against them).  Cleared wherever the plan or its slab order is, and by every pass that writes the three arrays in
-    // another form; `slabs_made` is what the table was written for -- a replay that finds anything else there writes it again.
+    // and a replay under the same plan keeps them instead of launching the kernel again (run_geometry; its flatten is the lean form,
+    // which writes no keys -- behind a full flatten k_path_build<1> checks the paths' keys against them).  Cleared wherever the plan
+    // or its slab order is, and by every pass that writes the three arrays in another form; `slabs_made` is what the table was written for -- a replay that finds anything else there writes it again.
     bool slabs_current = false;
     // The slab order was made by the render that is running, not by the plan (svgr_batch_draw leaves it to the first replay): that
     // render's pass writes the table but does not mark it kept -- the replay behind it runs k_path_bbox once more and marks it.  Nothing
@@ -4665,9 +4674,15 @@ struct svgr_batch {
         const void *slabs, *bbox, *bins, *slab_at;
         int64_t n_slabs, n_paths;
         int vp[4];
+        // (what the flatten of that pass stored by: a replay that keeps the table launches k_flatten<.., LEAN>, which takes the places on trust)
+        const void *edges, *seg_off, *lane_off;
+        int64_t n_segs;
+        int edge_cap, fl_sub;
+        double thr;
         bool operator==(const SlabsMade& o) const {
             return slabs == o.slabs && bbox == o.bbox && bins == o.bins && slab_at == o.slab_at && n_slabs == o.n_slabs && n_paths == o.n_paths &&
-                   vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
+                   vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3] && edges == o.edges && seg_off == o.seg_off &&
+                   lane_off == o.lane_off && n_segs == o.n_segs && edge_cap == o.edge_cap && fl_sub == o.fl_sub && thr == o.thr;
         }
     } slabs_made{};
     // The same for what k_tile_lists leaves (`items`, `pages`, `tile_info`): a placed replay that keeps its slab table would list, band
@@ -4882,6 +4897,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                    use_vp ? b->vp[3] : 0 /* a counting pass: the viewport's width (bounds the columns it adds up) */,
                                    upto == 1 ? b->lane_off.p : (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
             };
+            if (getenv("SVGR_DBG_PLAN")) fprintf(stderr, "[geometry] k_flatten<count, %d> full\n", fl_sub);   // (diagnostic, as below)
             if (fl_sub == 6) launch_cnt(k_flatten<false, false, 6>); else launch_cnt(k_flatten<false, false, 5>);
         }
         // (the prefix sums are pass 2's input, not the census's: a census whose read-back waits for an event has them enqueued BEHIND the
@@ -4896,6 +4912,25 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         }
         return 0;
     }
+    // (a planned render under the plan's places keeps the plan's band lists: k_tile_lists reads the paths' bboxes and bins itself)
+    const bool keep_lists = upto >= 4 && b->planned && b->slab_at_valid && use_vp && !b->safe_path;
+    // (a planned render takes every cell's add places from the plan's own full pass: one pass over the edge rows, no reservation)
+    // (the places are per cell: they hold as long as the paths keep the plan's cell places, i.e. under the plan's slab order)
+    const bool placed = b->planned && b->add_places && b->slab_at_valid && !b->count_adds_only && b->cell_plan.p != nullptr;
+    // A replay of a plan whose slab table the previous render left (svgr_batch::slabs_current): k_path_bbox would write, record by
+    // record, what is there -- same keys, same `slab_at`, same `bins` -- so it is not launched; k_path_build<1> checks the keys
+    // against the kept bboxes instead (error bit 32, as the kernel's own comparison).  One GPU, every path: a rank's list keeps
+    // its launch, and so does every pass that is not the placed render.
+    const int edge_cap = cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4));
+    const svgr_batch::SlabsMade slabs_now{b->slabs.p, b->bbox.p, b->bins.p, b->slab_at.p, b->n_slabs, b->n_paths, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]},
+                                          b->edges.p, b->seg_off.p, b->lane_off.p, b->n_segs, edge_cap, fl_sub, b->thr};
+    const bool slabs_for_plan = keep_lists && b->own.world <= 1 && !listed && ns > 0 && b->n_slabs > 0 && b->n_slabs <= (int64_t)cap_i32(b->slabs.cap);
+    const bool keep_slabs = slabs_for_plan && placed && b->slabs_current && b->slabs_made == slabs_now;
+    // ... and the flatten of such a replay is the lean form (k_flatten<.., LEAN>): it stores the edges at the lanes' places and leaves
+    // the keys zero, so k_path_build<1> is given no path to check (below).  What the flatten reads and where it stores -- the
+    // transforms, the viewport, the bands, `seg_off`, `lane_off`, the edge array -- is what the full pass that made the table had:
+    // whatever changes one of them clears `slabs_current` or is part of `slabs_made`.
+    bool lean_fl = false;
     if (ns > 0) {
         // (the counting pass that made `seg_off` left every lane's place inside its segment's slots beside it)
         const bool lane_places = !b->safe_path;
@@ -4907,10 +4942,15 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                (const uint8_t*)b->seg_kind.p, (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr,
                                b->edges.p, keep_edge_path ? (int*)nullptr : b->edge_path.p, b->shards, b->pkeys(), b->bd(), b->own, b->vp[0],
                                n_bands_vp, prow, seg_list, n_items, (int*)nullptr, (const int*)b->seg_off.p,
-                               cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4)), places, (int*)nullptr, (unsigned long long*)nullptr);
+                               edge_cap, places, (int*)nullptr, (unsigned long long*)nullptr);
         };
         const bool placed_fl = lane_places && b->lane_off.p && b->lane_off.cap >= ((size_t)ns << fl_sub);
-        if (b->fl_scan) {
+        lean_fl = keep_slabs && placed_fl && !b->fl_scan && keep_edge_path;
+        if (getenv("SVGR_DBG_PLAN"))   // (diagnostic: which form of the flatten this pass launches)
+            fprintf(stderr, "[geometry] k_flatten<%s, %d> %s\n", b->fl_scan ? "scan" : placed_fl ? "placed" : "offsets", fl_sub, lean_fl ? "lean" : "full");
+        if (lean_fl) {
+            if (fl_sub == 6) launch_fl(k_flatten<true, true, 6, false, true>, b->lane_off.p); else launch_fl(k_flatten<true, true, 5, false, true>, b->lane_off.p);
+        } else if (b->fl_scan) {
             // ONE traversal: count, look back, store; leaves seg_cnt / seg_off / lane_off for the renders (needs: one GPU, no list)
             auto launch_scan = [&](auto kern) {
                 SVGR_LAUNCH(kern, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p,
@@ -4926,24 +4966,11 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
             if (placed_fl) launch_fl(k_flatten<true, true, 5>, b->lane_off.p); else launch_fl(k_flatten<true, false, 5>, (int*)nullptr);
         }
     }
-    // (a planned render under the plan's places keeps the plan's band lists: k_tile_lists reads the paths' bboxes and bins itself)
-    const bool keep_lists = upto >= 4 && b->planned && b->slab_at_valid && use_vp && !b->safe_path;
-    // (a planned render takes every cell's add places from the plan's own full pass: one pass over the edge rows, no reservation)
-    // (the places are per cell: they hold as long as the paths keep the plan's cell places, i.e. under the plan's slab order)
-    const bool placed = b->planned && b->add_places && b->slab_at_valid && !b->count_adds_only && b->cell_plan.p != nullptr;
-    // A replay of a plan whose slab table the previous render left (svgr_batch::slabs_current): k_path_bbox would write, record by
-    // record, what is there -- same keys, same `slab_at`, same `bins` -- so it is not launched; k_path_build<1> checks the keys
-    // against the kept bboxes instead (error bit 32, as the kernel's own comparison).  One GPU, every path: a rank's list keeps
-    // its launch, and so does every pass that is not the placed render.
-    const svgr_batch::SlabsMade slabs_now{b->slabs.p, b->bbox.p, b->bins.p, b->slab_at.p, b->n_slabs, b->n_paths, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]}};
-    const bool slabs_for_plan = keep_lists && b->own.world <= 1 && !listed && ns > 0 && b->n_slabs > 0 && b->n_slabs <= (int64_t)cap_i32(b->slabs.cap);
-    const bool keep_slabs = slabs_for_plan && placed && b->slabs_current && b->slabs_made == slabs_now;
     if (!keep_slabs) {
         SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(), np_walk,
                            use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), b->planned ? 0 : 1, plist,
                            upto >= 3 ? b->slabs.p : (Slab*)nullptr, (int)std::min<int64_t>(cap_i32(b->slabs.cap), b->n_slabs) /* = k_path_build's grid */, b->own,
-                           (const int*)b->path_seg0.p, (const int*)b->seg_off.p,
-                           cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4)),
+                           (const int*)b->path_seg0.p, (const int*)b->seg_off.p, edge_cap,
                            upto >= 4 && b->planned && b->slab_at_valid ? (const int*)b->slab_at.p : (const int*)nullptr);
         b->slabs_current = slabs_for_plan && !b->slab_order_late;   // (written at the plan's places, or in some other form)
         b->slab_order_late = false;
@@ -5000,7 +5027,8 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                b->tile_mask.p, b->cell_hdr.p, cap_i32(std::min(b->cell_hdr.cap, b->cell_plan.cap)), b->add_shards,
                                b->count_adds_only ? (TileAdd*)nullptr : b->adds.p, b->cell_plan.p, b->bd(), b->own, b->planned ? 0 : 1,
                                b->deterministic ? 1 : 0, pb_dbg, keep_slabs ? (const unsigned long long*)b->pkeys() : (const unsigned long long*)nullptr,
-                               (const int*)b->bbox.p, (const PathBin*)b->bins.p, np, b->vp[2], b->vp[3]);
+                               (const int*)b->bbox.p, (const PathBin*)b->bins.p,
+                               lean_fl ? 0 /* (no keys behind the lean flatten: the guard's loop over the paths makes no trip) */ : np, b->vp[2], b->vp[3]);
         };
         // (an unplanned pass over add lists sized with room to spare: ONE pass on the workgroup's own bounds, MODE 2)
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
