@@ -222,6 +222,50 @@ int svgr_batch_get_edges(const svgr_batch* batch, double* edges, int32_t* edge_p
  * edges == NULL to learn the count (*n_edges), then with a buffer of at least that many (2, 2) doubles.          */
 int svgr_batch_all_edges(svgr_batch* batch, double* edges, int32_t* edge_path, int64_t cap, int64_t* n_edges);
 
+/* Hit testing: which paths of the batch hold a point (SVG DOM isPointInFill / isPointInStroke), and which one is on top there
+ * (elementFromPoint).  Both entries work on the batch's FULL edge set -- the block svgr_batch_all_edges downloads, edges that
+ * cannot reach the viewport included -- which they flatten on the first call, group by path and keep on the device until
+ * svgr_batch_set_transforms; the batch needs no plan, and one it has is left as it is.
+ *
+ * The predicate (csrc/svgr_hit.h is its one home, compiled for host and device without fused multiply-adds): for an edge
+ * (a0, b0) -> (a1, b1), `a` being the first coordinate of an edge as svgr_batch_all_edges stores it and `b` the second, and a
+ * point (pa, pb) in the same order:
+ *     up = b0 <= pb && b1 > pb,  down = b1 <= pb && b0 > pb,  d = (a1 - a0) * (pb - b0) - (pa - a0) * (b1 - b0)
+ *     the edge counts +1 if up && d > 0, -1 if down && d < 0, else 0
+ * A path's winding number is the sum over its edges; it is inside for w != 0 (SVGR_FILL_NONZERO) or w & 1 (SVGR_FILL_EVENODD).  A
+ * point with a NaN or infinite coordinate has winding 0 everywhere: it is outside, not an error.  The edges are the ones the
+ * renderer flattens under the batch's transforms and flatness, so "inside" agrees with what is drawn; a point within rounding
+ * distance of an edge may fall either way, but falls the same way on host and device and from run to run.
+ *
+ * The points are either `points`, n_points x 2 host doubles (pa, pb), or -- points == NULL -- the pixel centres of
+ * grid = {row0, col0, rows, cols}, rows * cols == n_points: (row0 + r + 0.5, col0 + c + 0.5) in row-major order, made in the
+ * kernel.  Exactly one of the two is given (SVGR_E_INVALID otherwise).
+ *
+ * svgr_batch_winding: winding_out[i * n_paths + p] = the winding number of path p at point i.  SVGR_E_OVERFLOW when
+ * n_points * n_paths leaves 31 bits.
+ *
+ * svgr_batch_pick: the paths are hit regions in paint order.  Path p is clipped by the groups
+ * clip_group[clip_off[p] .. clip_off[p + 1]); group g has the sources group_src[group_off[g] .. group_off[g + 1]), paths with a
+ * SMALLER index than every path that uses the group:
+ *     pass(p) = inside(p) && for every clip group g of p: (some source s of g has pass(s))
+ *     top_out[i] = the largest p with pickable[p] != 0 && pass(p) at point i, or -1
+ * clip_off holds n_paths + 1 and group_off n_groups + 1 ascending offsets from 0 (clip_group / group_off / group_src may be NULL
+ * when nothing refers to them).  Tables that break this -- a clip source whose index is not smaller than its user's among them
+ * -- are SVGR_E_INVALID before anything is launched.  bits_out, optional: n_points x ceil(n_paths / 32) words of pass bits (path
+ * p: bit p % 32 of word p / 32).  The point-by-path bit matrix lives in device scratch of at most scratch_bytes (0: 256 MiB; never
+ * less than one workgroup's rows), and the points are taken in as many passes as that needs: an id map of a large canvas cannot
+ * exhaust memory.
+ *
+ * A batch without paths, and n_points == 0, launch nothing and succeed (top_out is then all -1).  The results come back behind
+ * one wait.  svgr_hit_block: points per workgroup (a grid query's workgroup is a square tile of that many pixels);
+ * svgr_hit_chunk: edges of a path staged through LDS at a time.                                                              */
+int svgr_batch_winding(svgr_batch* batch, const double* points, const int64_t* grid, int64_t n_points, int32_t* winding_out);
+int svgr_batch_pick(svgr_batch* batch, const double* points, const int64_t* grid, int64_t n_points, const uint8_t* pickable,
+                    const int32_t* clip_off, const int32_t* clip_group, const int32_t* group_off, const int32_t* group_src,
+                    int64_t n_groups, size_t scratch_bytes, int32_t* top_out, uint32_t* bits_out);
+int svgr_hit_block(void);
+int svgr_hit_chunk(void);
+
 /* Full device pipeline, asynchronous on the context stream, no host read-back:
  * transform+flatten -> bbox -> band binning -> tile kernel (LDS delta-coverage scatter, row scan,
  * fill rule, paint, source-over) -> store.  `out` must hold the output kind's bytes:

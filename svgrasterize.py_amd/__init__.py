@@ -24,7 +24,7 @@ from .filters import (  # noqa: F401
     FE_GAUSSIAN_BLUR, FE_MERGE, FE_MORPHOLOGY, FE_OFFSET,
 )
 from .scene import (  # noqa: F401
-    Scene, render_canvas, build_batch, clear_render_cache, set_render_cache,
+    Scene, HitLeaf, render_canvas, build_batch, clear_render_cache, set_render_cache,
     RENDER_FILL, RENDER_STROKE, RENDER_GROUP, RENDER_OPACITY, RENDER_CLIP, RENDER_MASK, RENDER_TRANSFORM, RENDER_FILTER, RENDER_BLEND,
     RENDER_MARKERS,
 )
@@ -37,8 +37,9 @@ from .opentype_cff import CFFFont, read_font, read_otf  # noqa: F401
 from .truetype_var import Axis  # noqa: F401
 from .svg import render_svg, svg_scene, svg_scene_from_filepath, svg_scene_from_str  # noqa: F401
 from .tensor import render_to_tensor, render_svgs_to_tensor  # noqa: F401
+from .hit import elements_at  # noqa: F401
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
            "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg",
            "write_jpeg", "canvas_to_jpeg", "Marker", "TextOnPath", "TextRun", "TextOutline", "TrueTypeFont", "read_ttf", "Axis", "CFFFont", "read_otf", "read_font",
-           "parse_css", "Stylesheet", "Symbol", "render_to_tensor", "render_svgs_to_tensor"]
+           "parse_css", "Stylesheet", "Symbol", "render_to_tensor", "render_svgs_to_tensor", "elements_at"]

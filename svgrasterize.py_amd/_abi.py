@@ -216,6 +216,10 @@ _PROTOS = {
     "svgr_tensor_run": (C.c_int, []),
     "svgr_stream_wait_for": (C.c_int, [_P, _P]),
     "svgr_stream_signal_to": (C.c_int, [_P, _P]),
+    "svgr_batch_winding": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "svgr_batch_pick": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_size_t, _P, _P]),
+    "svgr_hit_block": (C.c_int, []),
+    "svgr_hit_chunk": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -475,6 +479,42 @@ class Batch:
             _check(self.ctx.lib.svgr_batch_all_edges(self.handle, edges.ctypes.data_as(_P), edge_path.ctypes.data_as(_P), n.value, C.byref(n)))
         return edges, edge_path
 
+    def _hit_points(self, points, grid):
+        """(points pointer, grid pointer, n, keep-alive) of a hit query: `points` (n, 2) doubles, or grid = (row0, col0, rows, cols)."""
+        if (points is None) == (grid is None):
+            raise ValueError("give the points or the grid, one of them")
+        if grid is not None:
+            g = _i64x4(grid)
+            if g[2] < 0 or g[3] < 0:
+                raise ValueError("a grid has rows >= 0 and cols >= 0")
+            return None, g, int(g[2]) * int(g[3]), g
+        pts = hit_points(points)
+        return ptr(pts), None, len(pts), pts
+
+    def winding(self, points=None, grid=None) -> np.ndarray:
+        """svgr_batch_winding: the (n, n_paths) int32 winding numbers of every path at the points (`points`: (n, 2) in the
+        edges' coordinate order, or the pixel centres of grid = (row0, col0, rows, cols), row-major)."""
+        p, g, n, _keep = self._hit_points(points, grid)
+        out = np.zeros((n, self.n_paths), dtype=np.int32)
+        _check(self.ctx.lib.svgr_batch_winding(self.handle, p, g, n, ptr(out) if out.size else None))
+        return out
+
+    def pick(self, points=None, grid=None, pickable=None, clips=None, scratch_bytes: int = 0, want_bits: bool = False):
+        """svgr_batch_pick: (top (n,) int32, pass bits (n, ceil(n_paths / 32)) uint32 or None).  `clips`: per path a sequence of
+        clip groups, each a sequence of earlier path indices (None: no clips)."""
+        p, g, n, _keep = self._hit_points(points, grid)
+        npaths = self.n_paths
+        pk = np.ones(npaths, dtype=np.uint8) if pickable is None else np.ascontiguousarray(pickable, dtype=np.uint8).reshape(-1)
+        if len(pk) != npaths:
+            raise ValueError("one pickable flag per path")
+        clip_off, clip_group, group_off, group_src = clip_tables(clips, npaths)
+        top = np.full(n, -1, dtype=np.int32)
+        bits = np.zeros((n, (npaths + 31) // 32), dtype=np.uint32) if want_bits else None
+        _check(self.ctx.lib.svgr_batch_pick(self.handle, p, g, n, ptr(pk) if npaths else None, ptr(clip_off), ptr(clip_group) if len(clip_group) else None,
+                                            ptr(group_off), ptr(group_src) if len(group_src) else None, len(group_off) - 1, int(scratch_bytes),
+                                            ptr(top) if n else None, ptr(bits) if want_bits and bits.size else None))
+        return top, bits
+
     def set_bands(self, rank: int, world: int, strip_bands: int = 1):
         """Shard by interleaved strips of `strip_bands` bands; call plan() again afterwards."""
         _check(self.ctx.lib.svgr_batch_set_bands(self.handle, rank, world, strip_bands))
@@ -686,6 +726,34 @@ def _path_arrays(seg_types, seg_params, subpath_sizes):
     if int(subpath_sizes.sum()) != len(seg_types) or len(seg_params) != len(seg_types):
         raise ValueError("segment arrays do not match the subpath sizes")
     return seg_types, seg_params, subpath_sizes
+
+
+def hit_points(points) -> np.ndarray:
+    """The points of a hit query as a contiguous (n, 2) float64 array: (n, 2), or a single pair.  Anything else is a ValueError
+    (before any device work)."""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim == 1 and pts.shape == (2,):
+        pts = pts.reshape(1, 2)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"points are (n, 2) or a single pair, not {pts.shape}")
+    return np.ascontiguousarray(pts)
+
+
+def clip_tables(clips, n_paths):
+    """The four int32 tables of svgr_batch_pick from `clips`: per path a sequence of clip groups, each a sequence of path indices
+    (None: no path is clipped).  Equal groups are stored once.  Returns (clip_off, clip_group, group_off, group_src)."""
+    clip_off, clip_group, group_off, group_src, seen = [0], [], [0], [], {}
+    for p in range(n_paths):
+        for grp in (clips[p] if clips is not None else ()):
+            key = tuple(int(s) for s in grp)
+            g = seen.get(key)
+            if g is None:
+                g = seen[key] = len(group_off) - 1
+                group_src.extend(key)
+                group_off.append(len(group_src))
+            clip_group.append(g)
+        clip_off.append(len(clip_group))
+    return tuple(np.asarray(a, dtype=np.int32) for a in (clip_off, clip_group, group_off, group_src))
 
 
 def path_sample(seg_types, seg_params, subpath_sizes, s=(), ctx: "Context | None" = None):

@@ -895,6 +895,158 @@ __global__ __launch_bounds__(FL_BLOCK, FL_WAVES) void k_flatten(const double* __
     }  // (!LEAN)
 }
 
+// ======================================================================================
+// Hit testing kernels (svgr_batch_winding, svgr_batch_pick: the entries are at the end of the file).  They stand here, in front
+// of the tile kernel: its out-of-line class-1 bodies sit at the END of the text section and are reached by 16-bit branches, so
+// nothing may grow between it and that end.
+// ======================================================================================
+#include "svgr_hit.h"
+
+// Grouping the flattened edges by path (the flatten leaves them in sixteen shards, in the order its waves came by): count per
+// path, place by a cursor per path (the order inside a path is whatever the atomics give: a winding number is an integer sum),
+// then the extents, a wave per path.
+__global__ __launch_bounds__(256) void k_hit_count(const int* __restrict__ edge_path, long long n, int n_paths, int* __restrict__ cnt) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int p = edge_path[e];
+    if (p >= 0 && p < n_paths) atomicAdd(&cnt[p], 1);
+}
+__global__ __launch_bounds__(256) void k_hit_place(const double* __restrict__ in, const int* __restrict__ edge_path, long long n, int n_paths,
+                                                   const int* __restrict__ off, int* __restrict__ cur, double* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const int p = edge_path[e];
+    if (p < 0 || p >= n_paths) return;
+    const int at = off[p] + atomicAdd(&cur[p], 1);
+    if (at >= off[p + 1]) return;   // (cannot be: the counts are this array's own)
+    const double2* src = (const double2*)(in + 4 * e);
+    double2* dst = (double2*)(out + 4 * (size_t)at);
+    dst[0] = src[0]; dst[1] = src[1];
+}
+__global__ __launch_bounds__(64) void k_hit_extent(const double* __restrict__ edges, const int* __restrict__ off, int n_paths, double* __restrict__ ext) {
+    const int p = blockIdx.x;
+    if (p >= n_paths) return;
+    double mna = INFINITY, mnb = INFINITY, mxa = -INFINITY, mxb = -INFINITY;
+    for (int e = off[p] + (int)threadIdx.x; e < off[p + 1]; e += 64) {
+        const double2 q0 = ((const double2*)(edges + 4 * (size_t)e))[0], q1 = ((const double2*)(edges + 4 * (size_t)e))[1];
+        mna = fmin(mna, fmin(q0.x, q1.x)); mxa = fmax(mxa, fmax(q0.x, q1.x));
+        mnb = fmin(mnb, fmin(q0.y, q1.y)); mxb = fmax(mxb, fmax(q0.y, q1.y));
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        mna = fmin(mna, __shfl_xor(mna, d)); mnb = fmin(mnb, __shfl_xor(mnb, d));
+        mxa = fmax(mxa, __shfl_xor(mxa, d)); mxb = fmax(mxb, __shfl_xor(mxb, d));
+    }
+    if (threadIdx.x == 0) { ext[4 * p] = mna; ext[4 * p + 1] = mnb; ext[4 * p + 2] = mxa; ext[4 * p + 3] = mxb; }
+}
+
+// Where the lanes of a workgroup find their points: an array on the device, HIT_BLOCK consecutive points to a workgroup, or the
+// pixel centres of a grid, a HIT_TILE x HIT_TILE tile to a workgroup (compact, so that the cull below bites).  `id` is the
+// point's place in the caller's row-major order.
+struct HitQuery {
+    const double* pts;
+    long long n;
+    long long row0, col0, rows, cols, tiles_x;
+};
+__device__ __forceinline__ bool hit_point(const HitQuery& q, long long group, int lane, double& pa, double& pb, long long& id) {
+    if (q.pts) {
+        id = group * HIT_BLOCK + lane;
+        if (id >= q.n) return false;
+        pa = q.pts[2 * id]; pb = q.pts[2 * id + 1];
+        return true;
+    }
+    const long long r = (group / q.tiles_x) * HIT_TILE + lane / HIT_TILE, c = (group % q.tiles_x) * HIT_TILE + lane % HIT_TILE;
+    if (r >= q.rows || c >= q.cols) return false;
+    id = r * q.cols + c;
+    pa = (double)(q.row0 + r) + 0.5; pb = (double)(q.col0 + c) + 0.5;
+    return true;
+}
+
+// A workgroup of HIT_BLOCK points against every path.  HIT_BLOCK paths at a time, a lane each, are tested against the extent of
+// the workgroup's points: a path is skipped when its b range misses the points' (no edge is then `up` or `down` for any of them)
+// or when it lies wholly at a <= min(pa) (every d of an `up` edge is then <= 0 and of a `down` edge >= 0, in the rounded arithmetic
+// as well: the differences and products of svgr_hit.h are monotone).  The edges of a path that stays go through LDS HIT_CHUNK at
+// a time; every lane reads the same address (a broadcast) and keeps its own point's winding number in a register.
+// BITS: one inside bit per (point, path) into row `slot` of `bits` (32 paths to a word); else the winding numbers into wind[id].
+template <bool BITS>
+__global__ __launch_bounds__(HIT_BLOCK) void k_hit_winding(const double* __restrict__ edges, const int* __restrict__ off, const double* __restrict__ ext,
+                                                           const uint8_t* __restrict__ rule, int n_paths, const HitQuery q, long long group0,
+                                                           int* __restrict__ wind, uint32_t* __restrict__ bits, int words) {
+    __shared__ __align__(16) double s_e[4 * HIT_CHUNK];
+    __shared__ double s_red[3][HIT_BLOCK / 64];
+    __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK];
+    const int lane = threadIdx.x;
+    const long long group = group0 + blockIdx.x;
+    double pa = 0.0, pb = 0.0;
+    long long id = 0;
+    const bool live = hit_point(q, group, lane, pa, pb, id);
+    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (compares false with every edge: winding 0)
+    // the extent of the workgroup's finite points
+    double lo_a = pa == pa ? pa : INFINITY, lo_b = pb == pb ? pb : INFINITY, hi_b = pb == pb ? pb : -INFINITY;
+    for (int d = 32; d > 0; d >>= 1) {
+        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
+    }
+    if ((lane & 63) == 0) { s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = lo_b; s_red[2][lane >> 6] = hi_b; }
+    __syncthreads();
+    for (int k = 0; k < HIT_BLOCK / 64; ++k) { lo_a = fmin(lo_a, s_red[0][k]); lo_b = fmin(lo_b, s_red[1][k]); hi_b = fmax(hi_b, s_red[2][k]); }
+    const size_t row = (size_t)((long long)blockIdx.x * HIT_BLOCK + lane) * (size_t)words;
+    uint32_t word = 0u;
+    for (int base = 0; base < n_paths; base += HIT_BLOCK) {
+        __syncthreads();   // (the previous round's table has been read)
+        {
+            const int p = base + lane;
+            int e0 = 0, e1 = 0;
+            if (p < n_paths) {
+                e0 = off[p]; e1 = off[p + 1];
+                const double mnb = ext[4 * p + 1], mxa = ext[4 * p + 2], mxb = ext[4 * p + 3];
+                if (!(e1 > e0 && hi_b >= mnb && lo_b < mxb && mxa > lo_a)) e1 = e0;
+            }
+            s_e0[lane] = e0; s_e1[lane] = e1;
+        }
+        __syncthreads();
+        const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
+        for (int j = 0; j < n_here; ++j) {
+            const int p = base + j;
+            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+            int w = 0;
+            for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
+                const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
+                __syncthreads();   // (the previous chunk has been read)
+                if (lane < n) {
+                    const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
+                    ((double2*)s_e)[2 * lane] = src[0];
+                    ((double2*)s_e)[2 * lane + 1] = src[1];
+                }
+                __syncthreads();
+                for (int k = 0; k < n; ++k) {
+                    const double2 q0 = ((const double2*)s_e)[2 * k], q1 = ((const double2*)s_e)[2 * k + 1];
+                    w += hit_edge_term(q0.x, q0.y, q1.x, q1.y, pa, pb);
+                }
+            }
+            if constexpr (BITS) {
+                if (hit_inside(w, rule[p] & 1)) word |= 1u << (p & 31);
+                if ((p & 31) == 31 || p == n_paths - 1) {
+                    if (live) bits[row + (size_t)(p >> 5)] = word;
+                    word = 0u;
+                }
+            } else {
+                if (live) wind[(size_t)id * (size_t)n_paths + (size_t)p] = w;
+            }
+        }
+    }
+}
+
+// a lane per point: the clips and the paint order over its row of bits (svgr_hit.h), in place
+__global__ __launch_bounds__(HIT_BLOCK) void k_hit_resolve(uint32_t* __restrict__ bits, int words, int n_paths, const HitQuery q, long long group0,
+                                                           const uint8_t* __restrict__ pickable, const int32_t* __restrict__ clip_off,
+                                                           const int32_t* __restrict__ clip_group, const int32_t* __restrict__ group_off,
+                                                           const int32_t* __restrict__ group_src, int32_t* __restrict__ top) {
+    double pa, pb;
+    long long id;
+    if (!hit_point(q, group0 + blockIdx.x, threadIdx.x, pa, pb, id)) return;
+    uint32_t* row = bits + (size_t)((long long)blockIdx.x * HIT_BLOCK + threadIdx.x) * (size_t)words;
+    top[id] = hit_resolve(row, n_paths, pickable, clip_off, clip_group, group_off, group_src);
+}
+
 // Plan only: exclusive prefix sums of the per-segment edge counts (seg_off[n] = their total).  One workgroup, a chunk of
 // 1024 segments per step with the running total carried along: a plan-time pass over a few thousand to a few million ints.
 __global__ __launch_bounds__(1024) void k_seg_scan(const int* __restrict__ seg_cnt, int n, int* __restrict__ seg_off) {
@@ -4737,6 +4889,12 @@ struct svgr_batch {
     bool defer_bbox = false;        // ... this pass's read-back is the scalars alone
     std::vector<TimedEvents> events;
     std::vector<hipEvent_t> event_pool;
+    // Hit testing (svgr_batch_winding / svgr_batch_pick): every flattened edge of the batch grouped by path, the paths' places in
+    // that block and their extents {min a, min b, max a, max b}.  Made by the first query, kept until the transforms change; in
+    // arrays of its own, so a plan the batch has is not touched.
+    DevArr<double> hit_edges, hit_ext;
+    DevArr<int> hit_off;
+    bool hit_ready = false;
 
     int n_ctiles() const { return (vp[3] + TC - 1) / TC; }
     // the arrays k_tile_lists fills, for the planned band / tile / cell counts
@@ -5741,6 +5899,7 @@ int svgr_batch_set_transforms(svgr_batch* b, const double* path_m6) {
         HIPCHK(b->note_upload(b->ctx->stream));
     }
     b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+    b->hit_ready = false;
     return 0;
 }
 
@@ -9355,5 +9514,210 @@ int svgr_stream_signal_to(svgr_ctx* ctx, void* other) {
     if (!ctx) return fail(SVGR_E_INVALID, "ctx is NULL");
     if ((hipStream_t)other == ctx->stream) return 0;
     return stream_order(ctx, 1, ctx->stream, (hipStream_t)other);
+}
+}  // extern "C"
+
+// ======================================================================================
+// Hit testing: winding numbers of points against the batch's paths, and the topmost path under each point
+// (svgr_batch_winding, svgr_batch_pick; the arithmetic and its contract: svgr_hit.h)
+// ======================================================================================
+// The batch's full edge set, grouped by path, on the device (b->hit_*): a counting and an emitting flatten without row culling,
+// as svgr_batch_all_edges runs them, but with a counter arena of their own -- the batch's arena, plan and geometry stay as they are.
+static int hit_prepare(svgr_batch* b) {
+    if (b->hit_ready) return 0;
+    hipStream_t st = b->ctx->stream;
+    const int ns = (int)b->n_segs, np = (int)b->n_paths;
+    if (int rc = b->hit_off.ensure((size_t)np + 1)) return rc;
+    if (int rc = b->hit_ext.ensure(4 * (size_t)np)) return rc;
+    std::vector<int> off((size_t)np + 1, 0);
+    int64_t total = 0;
+    PoolBlock d_edges, d_path, scratch, d_cnt;
+    if (ns > 0) {
+        if (b->arena_bytes == 0)
+            if (int rc = b->layout_arena()) return rc;
+        HIPCHK(scratch.alloc(b->arena_bytes));
+        BatchDev* bd = scratch.as<BatchDev>();
+        unsigned long long* pkeys = (unsigned long long*)(scratch.as<unsigned char>() + b->off_pkeys);
+        const dim3 fgrid = grid1((size_t)ns << FL_SUB, FL_BLOCK);
+        const Owner whole{0, 1, 1};
+        HIPCHK(hipMemsetAsync(scratch.p, 0, b->arena_bytes, st));
+        SVGR_LAUNCH(k_flatten<false>, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p, (const uint8_t*)b->seg_kind.p,
+                           (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr, (double*)nullptr, (int*)nullptr, b->shards,
+                           pkeys, bd, whole, 0, 0, (const unsigned*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
+        BatchDev counts;
+        HIPCHK(hipMemcpyAsync(&counts, bd, sizeof counts, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (counts.err & 1) return fail(SVGR_E_OVERFLOW, "flatten depth cap (%d) hit: non-finite or absurd control points", kMaxFlattenDepth);
+        EdgeShards sh{};
+        for (int k = 0; k < NSH; ++k) {
+            sh.base[k] = (int)std::min<int64_t>(total, 0x7fffffff);
+            sh.cap[k] = counts.shard[k].cursor;
+            total += counts.shard[k].cursor;
+        }
+        if (total > 0x7fffffff / 4) return fail(SVGR_E_OVERFLOW, "%lld edges: beyond the 32-bit edge index", (long long)total);
+        if (total > 0) {
+            HIPCHK(d_edges.alloc(sizeof(double) * 4 * (size_t)total));
+            HIPCHK(d_path.alloc(sizeof(int) * (size_t)total));
+            HIPCHK(d_cnt.alloc(sizeof(int) * 2 * ((size_t)np + 1)));
+            HIPCHK(hipMemsetAsync(scratch.p, 0, b->arena_bytes, st));
+            HIPCHK(hipMemsetAsync(d_path.p, 0xff, sizeof(int) * (size_t)total, st));   // (a slot the flatten should leave empty is no path's)
+            HIPCHK(hipMemsetAsync(d_cnt.p, 0, sizeof(int) * 2 * ((size_t)np + 1), st));
+            SVGR_LAUNCH(k_flatten<true>, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p, (const uint8_t*)b->seg_kind.p,
+                               (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr, d_edges.as<double>(), d_path.as<int>(), sh, pkeys, bd,
+                               whole, 0, 0, (const unsigned*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (const int*)nullptr, 0, (int*)nullptr, (int*)nullptr, (unsigned long long*)nullptr);
+            SVGR_LAUNCH(k_hit_count, grid1((size_t)total), dim3(256), 0, st, d_path.as<int>(), (long long)total, np, d_cnt.as<int>());
+            std::vector<int> cnt((size_t)np);
+            HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(int) * (size_t)np, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (int p = 0; p < np; ++p) off[(size_t)p + 1] = off[(size_t)p] + cnt[(size_t)p];
+        }
+    }
+    const int64_t kept = off[(size_t)np];
+    if (int rc = b->hit_edges.ensure(4 * (size_t)std::max<int64_t>(kept, 1))) return rc;
+    HIPCHK(hipMemcpyAsync(b->hit_off.p, off.data(), sizeof(int) * ((size_t)np + 1), hipMemcpyHostToDevice, st));
+    if (kept > 0)
+        SVGR_LAUNCH(k_hit_place, grid1((size_t)total), dim3(256), 0, st, d_edges.as<double>(), d_path.as<int>(), (long long)total, np,
+                    (const int*)b->hit_off.p, d_cnt.as<int>() + np + 1, b->hit_edges.p);
+    SVGR_LAUNCH(k_hit_extent, dim3((unsigned)np), dim3(64), 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p, np, b->hit_ext.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));   // (`off` is the source of an upload)
+    b->hit_ready = true;
+    return 0;
+}
+
+// the points of a query: `points` (n x 2 doubles of the caller's) or the grid {row0, col0, rows, cols}; checked, nothing uploaded yet
+static int hit_query(const char* entry, const double* points, const int64_t* grid, int64_t n_points, HitQuery& q, long long& n_groups) {
+    memset(&q, 0, sizeof q);
+    if ((points != nullptr) == (grid != nullptr)) return fail(SVGR_E_INVALID, "%s: give the points or the grid, one of them", entry);
+    if (grid) {
+        if (grid[2] < 0 || grid[3] < 0 || grid[2] >= (1ll << 30) || grid[3] >= (1ll << 30) || grid[2] * grid[3] != n_points)
+            return fail(SVGR_E_INVALID, "%s: the grid's rows x cols are not n_points", entry);
+        if (grid[0] < -(1ll << 50) || grid[0] > (1ll << 50) || grid[1] < -(1ll << 50) || grid[1] > (1ll << 50))
+            return fail(SVGR_E_INVALID, "%s: the grid's origin is beyond 2^50", entry);
+        q.row0 = grid[0]; q.col0 = grid[1]; q.rows = grid[2]; q.cols = grid[3];
+        q.tiles_x = std::max<long long>((q.cols + HIT_TILE - 1) / HIT_TILE, 1);
+        n_groups = q.tiles_x * ((q.rows + HIT_TILE - 1) / HIT_TILE);
+    } else {
+        q.n = n_points;
+        n_groups = (n_points + HIT_BLOCK - 1) / HIT_BLOCK;
+    }
+    if (n_groups > 0x7fffffffll) return fail(SVGR_E_OVERFLOW, "%s: %lld points are more than one launch takes", entry, (long long)n_points);
+    return 0;
+}
+static int hit_upload_points(svgr_batch* b, const double* points, int64_t n_points, PoolBlock& dev, HitQuery& q) {
+    if (!points || n_points == 0) return 0;
+    HIPCHK(dev.alloc(sizeof(double) * 2 * (size_t)n_points));
+    HIPCHK(hipMemcpyAsync(dev.p, points, sizeof(double) * 2 * (size_t)n_points, hipMemcpyHostToDevice, b->ctx->stream));
+    q.pts = dev.as<double>();
+    return 0;
+}
+
+extern "C" {
+int svgr_hit_block(void) { return HIT_BLOCK; }
+int svgr_hit_chunk(void) { return HIT_CHUNK; }
+
+int svgr_batch_winding(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, int32_t* winding_out) {
+    static const char* entry = "svgr_batch_winding";
+    return abi_guard(entry, [&]() -> int {
+        if (!b || n_points < 0) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+        PoolBlock d_pts, d_out;
+        HitQuery q;
+        long long n_groups = 0;
+        if (int rc = hit_query(entry, points, grid, n_points, q, n_groups)) return rc;
+        const int64_t np = b->n_paths;
+        if (np == 0 || n_points == 0) return 0;
+        if (n_points > 0x7fffffffll / np) return fail(SVGR_E_OVERFLOW, "%s: %lld points x %lld paths leave 31 bits", entry, (long long)n_points, (long long)np);
+        if (!winding_out) return fail(SVGR_E_INVALID, "%s: winding_out is NULL", entry);
+        HIPCHK(enter_ctx(b->ctx));
+        hipStream_t st = b->ctx->stream;
+        if (int rc = hit_prepare(b)) return rc;
+        if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
+        const size_t bytes = sizeof(int32_t) * (size_t)n_points * (size_t)np;
+        HIPCHK(d_out.alloc(bytes));
+        SVGR_LAUNCH(k_hit_winding<false>, dim3((unsigned)n_groups), dim3(HIT_BLOCK), 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p,
+                    (const double*)b->hit_ext.p, (const uint8_t*)b->path_rule.p, (int)np, q, 0ll, d_out.as<int>(), (uint32_t*)nullptr, 0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(winding_out, d_out.p, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+
+int svgr_batch_pick(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, const uint8_t* pickable, const int32_t* clip_off,
+                    const int32_t* clip_group, const int32_t* group_off, const int32_t* group_src, int64_t n_clip_groups, size_t scratch_bytes,
+                    int32_t* top_out, uint32_t* bits_out) {
+    static const char* entry = "svgr_batch_pick";
+    return abi_guard(entry, [&]() -> int {
+        if (!b || n_points < 0 || n_clip_groups < 0 || n_clip_groups > 0x7fffffffll) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+        PoolBlock d_pts, d_top, d_bits, d_tab;
+        HitQuery q;
+        long long n_groups = 0;
+        if (int rc = hit_query(entry, points, grid, n_points, q, n_groups)) return rc;
+        const int64_t np = b->n_paths;
+        if (n_points > 0 && !top_out) return fail(SVGR_E_INVALID, "%s: top_out is NULL", entry);
+        if (np == 0) {
+            for (int64_t i = 0; i < n_points; ++i) top_out[i] = -1;
+            return 0;
+        }
+        if (!pickable || !clip_off) return fail(SVGR_E_INVALID, "%s: pickable or clip_off is NULL", entry);
+        if (n_clip_groups > 0 && (!group_off || (group_off[n_clip_groups] > 0 && !group_src))) return fail(SVGR_E_INVALID, "%s: the clip groups' tables are NULL", entry);
+        if (clip_off[np] > 0 && !clip_group) return fail(SVGR_E_INVALID, "%s: clip_group is NULL", entry);
+        if (clip_off[np] > 0 && n_clip_groups == 0) return fail(SVGR_E_INVALID, "%s: clip groups are used and none is given", entry);
+        if (const long long bad = hit_check_tables(np, clip_off, clip_group, group_off, group_src, n_clip_groups))
+            return fail(SVGR_E_INVALID, "%s: the clip tables of path %lld: offsets must ascend from 0, a group must exist, and every clip source must lie in front of the path that uses it",
+                        entry, bad - 1);
+        if (n_points == 0) return 0;
+        const int words = (int)((np + 31) / 32);
+        if ((size_t)n_points > SIZE_MAX / 8 / (size_t)words) return fail(SVGR_E_OVERFLOW, "%s: the bit matrix leaves the address space", entry);
+        HIPCHK(enter_ctx(b->ctx));
+        hipStream_t st = b->ctx->stream;
+        if (int rc = hit_prepare(b)) return rc;
+        if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
+        // the tables in one block: the four int arrays, then the pickable bytes
+        const size_t n_co = (size_t)np + 1, n_cg = (size_t)clip_off[np], n_go = (size_t)n_clip_groups + 1, n_gs = n_clip_groups > 0 ? (size_t)group_off[n_clip_groups] : 0;
+        const int32_t zero = 0;
+        HIPCHK(d_tab.alloc(sizeof(int32_t) * (n_co + n_cg + n_go + n_gs) + (size_t)np));
+        int32_t* t_co = d_tab.as<int32_t>(), *t_cg = t_co + n_co, *t_go = t_cg + n_cg, *t_gs = t_go + n_go;
+        uint8_t* t_pick = (uint8_t*)(t_gs + n_gs);
+        HIPCHK(hipMemcpyAsync(t_co, clip_off, sizeof(int32_t) * n_co, hipMemcpyHostToDevice, st));
+        if (n_cg) HIPCHK(hipMemcpyAsync(t_cg, clip_group, sizeof(int32_t) * n_cg, hipMemcpyHostToDevice, st));
+        if (n_clip_groups > 0) HIPCHK(hipMemcpyAsync(t_go, group_off, sizeof(int32_t) * n_go, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemcpyAsync(t_go, &zero, sizeof zero, hipMemcpyHostToDevice, st));
+        if (n_gs) HIPCHK(hipMemcpyAsync(t_gs, group_src, sizeof(int32_t) * n_gs, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(t_pick, pickable, (size_t)np, hipMemcpyHostToDevice, st));
+        // the point-by-path bit matrix: as many workgroups' rows at a time as the scratch holds
+        const size_t group_bytes = sizeof(uint32_t) * (size_t)words * HIT_BLOCK;
+        const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
+        const long long per_pass = std::min<long long>(n_groups, std::max<long long>((long long)(budget / group_bytes), 1));
+        HIPCHK(d_bits.alloc(group_bytes * (size_t)per_pass));
+        HIPCHK(d_top.alloc(sizeof(int32_t) * (size_t)n_points));
+        std::vector<uint32_t> staged;   // a grid's rows come back in tile order: put in row-major order behind the wait
+        if (bits_out && grid) staged.resize((size_t)n_groups * HIT_BLOCK * (size_t)words);
+        for (long long g0 = 0; g0 < n_groups; g0 += per_pass) {
+            const long long ng = std::min<long long>(per_pass, n_groups - g0);
+            SVGR_LAUNCH(k_hit_winding<true>, dim3((unsigned)ng), dim3(HIT_BLOCK), 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p,
+                        (const double*)b->hit_ext.p, (const uint8_t*)b->path_rule.p, (int)np, q, g0, (int*)nullptr, d_bits.as<uint32_t>(), words);
+            SVGR_LAUNCH(k_hit_resolve, dim3((unsigned)ng), dim3(HIT_BLOCK), 0, st, d_bits.as<uint32_t>(), words, (int)np, q, g0, (const uint8_t*)t_pick,
+                        (const int32_t*)t_co, (const int32_t*)t_cg, (const int32_t*)t_go, (const int32_t*)t_gs, d_top.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            if (bits_out && grid) {
+                HIPCHK(hipMemcpyAsync(staged.data() + (size_t)g0 * HIT_BLOCK * (size_t)words, d_bits.p, group_bytes * (size_t)ng, hipMemcpyDeviceToHost, st));
+            } else if (bits_out) {
+                const long long i0 = g0 * HIT_BLOCK, i1 = std::min<long long>(n_points, (g0 + ng) * HIT_BLOCK);
+                HIPCHK(hipMemcpyAsync(bits_out + (size_t)i0 * (size_t)words, d_bits.p, sizeof(uint32_t) * (size_t)words * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
+            }
+        }
+        HIPCHK(hipMemcpyAsync(top_out, d_top.p, sizeof(int32_t) * (size_t)n_points, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bits_out && grid)
+            for (long long g = 0; g < n_groups; ++g)
+                for (int lane = 0; lane < HIT_BLOCK; ++lane) {
+                    const long long r = (g / q.tiles_x) * HIT_TILE + lane / HIT_TILE, c = (g % q.tiles_x) * HIT_TILE + lane % HIT_TILE;
+                    if (r >= q.rows || c >= q.cols) continue;
+                    memcpy(bits_out + (size_t)(r * q.cols + c) * (size_t)words, staged.data() + ((size_t)g * HIT_BLOCK + (size_t)lane) * (size_t)words,
+                           sizeof(uint32_t) * (size_t)words);
+                }
+        return 0;
+    });
 }
 }  // extern "C"

@@ -590,6 +590,39 @@ class Path:
             return np.zeros((len(s), 2)), np.tile([1.0, 0.0], (len(s), 1)), np.zeros(len(s), dtype=bool)
         return _abi.path_sample(types, np.array(params), sizes, s)[:3]
 
+    def winding(self, points, transform: Transform | None = None, flatness: float = FLATNESS) -> np.ndarray:
+        """The path's winding number at `points`, an int32 array ``(n,)`` (beyond the reference).  `points` is ``(n, 2)`` or a
+        single pair, in the coordinates `transform` maps into -- those of a ``viewport``, in the order of the renderer's edges:
+        ``(row, col)`` -- ``transform=None`` being the identity.  The edges are the ones the renderer flattens under that transform
+        and `flatness`, so the answer agrees with what ``mask`` draws; a point within rounding distance of an edge may fall either
+        way, but falls the same way every time.  A NaN or infinite point has winding 0.  An empty path is 0 everywhere and touches no
+        device.  Eager, on the device (svgr_batch_winding); DESIGN.md 7q has the predicate."""
+        pts = _abi.hit_points(points)   # (a wrong shape: ValueError before any device work)
+        segs, kinds = self.packed()
+        if len(segs) == 0 or len(pts) == 0:
+            return np.zeros(len(pts), dtype=np.int32)
+        batch = _abi.Batch(_abi.Context.get(), segs, kinds, [0, len(segs)], (transform if transform is not None else Transform()).m6(),
+                           [_RULES[None]], [np.zeros(4)], viewport=None, flatness=flatness)
+        try:
+            return np.ascontiguousarray(batch.winding(pts)[:, 0])
+        finally:
+            batch.destroy()
+
+    def contains(self, points, transform: Transform | None = None, fill_rule: str | None = None, flatness: float = FLATNESS) -> np.ndarray:
+        """Is each of `points` inside the path's fill: a bool array ``(n,)`` (beyond the reference; ``isPointInFill``).  Points,
+        transform and contract as for ``winding``; inside is ``w != 0`` under the nonzero rule (the default) and ``w & 1`` under
+        even-odd."""
+        if fill_rule not in _RULES:
+            raise ValueError(f"Invalid fill rule: {fill_rule}")
+        w = self.winding(points, transform, flatness)
+        return (w & 1).astype(bool) if _RULES[fill_rule] == 1 else w != 0
+
+    def stroke_contains(self, points, width: float, linecap: str | None = None, linejoin: str | None = None,
+                        transform: Transform | None = None) -> np.ndarray:
+        """Is each of `points` inside the path's stroke (beyond the reference; ``isPointInStroke``): the stroke outline is built
+        in user space and then transformed, as a render does."""
+        return self.stroke(width, linecap, linejoin).contains(points, transform, PATH_FILL_NONZERO)
+
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
         "on" dash an open subpath, ready for ``stroke``.  Eager, on the device (svgr_path_dash); quadratic and arc segments are

@@ -618,6 +618,124 @@ class Scene(tuple):
         """Flatten to paint-ordered solid leaves if the whole scene is batchable, else None."""
         return _batchable_leaves(self, transform, linear_rgb)
 
+    # -- hit testing (beyond the reference; DESIGN.md 7q) ---------------------------------------
+    def hit_leaves(self, transform: Transform):
+        """The scene's hit regions in paint order, a list of ``HitLeaf``: FILL nodes (image fills included) give their path under
+        their rule, STROKE nodes their outline under nonzero; GROUP keeps its order, TRANSFORM accumulates, marker and text nodes are
+        walked as the groups they expand to.  OPACITY, FILTER, MASK and BLEND are looked through: pointer events ignore them, and an
+        element of opacity 0 is still hit.  A CLIP emits its clip scene's leaves first -- not pickable, kind "clip", together one
+        clip group -- and adds that group to every leaf of its target (a leaf passes a group when it lies in any of its sources;
+        a source that is clipped itself carries groups of its own).  Loading a document needs no device; this walk needs one for
+        what a render of the scene would need one too: lazy nodes, and the frame of a clip in objectBoundingBox units."""
+        out: list = []
+        _hit_walk(self, transform, (), None, None, out)
+        return out
+
+    def _pick(self, transform: Transform, points, grid):
+        leaves = self.hit_leaves(transform)
+        n = len(_abi.hit_points(points)) if grid is None else int(grid[2]) * int(grid[3])
+        if not leaves or n == 0:
+            return np.full(n, -1, dtype=np.int32), leaves
+        segs, kinds, offs = _packed_paths([leaf.path for leaf in leaves])
+        batch = _abi.Batch(_abi.Context.get(), segs, kinds, offs, np.array([leaf.m6 for leaf in leaves], dtype=np.float64).reshape(-1, 6),
+                           [leaf.rule for leaf in leaves], np.zeros((len(leaves), 4)), viewport=None, flatness=FLATNESS)
+        try:
+            top, _bits = batch.pick(points, grid, [leaf.pickable for leaf in leaves], [leaf.clips for leaf in leaves])
+        finally:
+            batch.destroy()
+        return top, leaves
+
+    def pick(self, transform: Transform, points):
+        """``(index (n,) int32, leaves)``: per point -- ``(n, 2)`` or a single pair, ``(row, col)`` in the coordinates `transform`
+        maps into -- the index into ``leaves = hit_leaves(transform)`` of the topmost pickable leaf that holds it and whose clips
+        all let it pass, or -1 (``elementFromPoint``).  Eager, on the device (svgr_batch_pick)."""
+        return self._pick(transform, _abi.hit_points(points), None)
+
+    def id_map(self, transform: Transform, viewport):
+        """``(map (rows, cols) int32, leaves)``: ``pick`` at the centre of every pixel of ``viewport = (row0, col0, rows, cols)``,
+        the points made on the device -- the instance-id map that goes with a render into the same viewport."""
+        row0, col0, rows, cols = (int(v) for v in viewport)
+        if rows < 0 or cols < 0:
+            raise ValueError("a viewport has rows >= 0 and cols >= 0")
+        top, leaves = self._pick(transform, None, (row0, col0, rows, cols))
+        return top.reshape(rows, cols), leaves
+
+
+class HitLeaf(tuple):
+    """One hit region of ``Scene.hit_leaves``: ``path`` under the six numbers ``m6`` and the fill rule ``rule`` (0 nonzero, 1
+    even-odd); ``kind`` "fill", "stroke" or "clip"; ``pickable``; ``clips``, a tuple of clip groups, each a tuple of earlier
+    indices; ``source``, the Path object of the node the region comes from (a STROKE node's own path, not its outline) or, for a
+    region of a lazy node -- markers, text -- that node's payload object."""
+    __slots__ = []
+    _fields = ("path", "m6", "rule", "kind", "pickable", "clips", "source")
+
+    def __new__(cls, path, m6, rule, kind, pickable, clips, source):
+        return tuple.__new__(cls, (path, m6, rule, kind, pickable, clips, source))
+
+    path = property(lambda self: self[0])
+    m6 = property(lambda self: self[1])
+    rule = property(lambda self: self[2])
+    kind = property(lambda self: self[3])
+    pickable = property(lambda self: self[4])
+    clips = property(lambda self: self[5])
+    source = property(lambda self: self[6])
+
+    def __repr__(self) -> str:
+        return "HitLeaf(" + ", ".join(f"{k}={v!r}" for k, v in zip(self._fields, self) if k not in ("path", "m6", "source")) + ")"
+
+
+def _hit_hull(scene: Scene, transform: Transform) -> "ConvexHull | None":
+    """The hull a render of `scene` returns (every flattened point of every leaf): the frame of an objectBoundingBox clip.  None:
+    the scene has no edges (a render of it draws nothing)."""
+    leaves: list = []
+    _hit_walk(scene, transform, (), None, None, leaves)
+    leaves = [leaf for leaf in leaves if leaf.kind != "clip" and leaf.path]
+    if not leaves:
+        return None
+    segs, kinds, offs = _packed_paths([leaf.path for leaf in leaves])
+    batch = _abi.Batch(_abi.Context.get(), segs, kinds, offs, np.array([leaf.m6 for leaf in leaves], dtype=np.float64).reshape(-1, 6),
+                       [leaf.rule for leaf in leaves], np.zeros((len(leaves), 4)), viewport=None, flatness=FLATNESS)
+    try:
+        edges = batch.all_edges()[0]
+    finally:
+        batch.destroy()
+    return ConvexHull(edges) if len(edges) else None
+
+
+def _hit_walk(scene: Scene, transform: Transform, clips: tuple, as_clip, lazy_source, out: list) -> None:
+    """`Scene.hit_leaves`: append the leaves of `scene` under `transform`; `clips`: the groups every one of them carries;
+    `as_clip`: a list that takes the indices (the walk is inside a clip scene: its leaves are sources); `lazy_source`: the payload
+    of the lazy node the walk is inside of."""
+    if scene[0] == RENDER_MARKERS:
+        lazy_source = lazy_source if lazy_source is not None else scene[1]
+        scene = _expanded(scene)
+        if scene is None:
+            return
+    kind, args = scene
+    if kind in (RENDER_FILL, RENDER_STROKE):
+        path = args[0] if kind == RENDER_FILL else _stroked(scene)
+        rule = _RULES[args[2]] if kind == RENDER_FILL else 0
+        if as_clip is not None:
+            as_clip.append(len(out))
+        out.append(HitLeaf(path, transform.m6(), rule, "clip" if as_clip is not None else ("fill" if kind == RENDER_FILL else "stroke"),
+                           as_clip is None, clips, lazy_source if lazy_source is not None else args[0]))
+    elif kind == RENDER_GROUP:
+        for child in args:
+            _hit_walk(child, transform, clips, as_clip, lazy_source, out)
+    elif kind == RENDER_TRANSFORM:
+        _hit_walk(args[0], transform @ args[1], clips, as_clip, lazy_source, out)
+    elif kind in (RENDER_OPACITY, RENDER_FILTER, RENDER_MASK, RENDER_BLEND):
+        _hit_walk(args[0], transform, clips, as_clip, lazy_source, out)
+    elif kind == RENDER_CLIP:
+        target, clip, bbox_units = args
+        hull = _hit_hull(target, transform) if bbox_units else None
+        clip_transform = hull.bbox_transform(transform) if hull is not None else transform
+        sources: list = []
+        _hit_walk(clip, clip_transform, (), sources, lazy_source, out)   # (a source answers for its own clips only)
+        _hit_walk(target, transform, clips + (tuple(sources),), as_clip, lazy_source, out)
+    else:
+        raise ValueError(f"unhandled scene type: {kind}")
+
 
 def _collect_mask_jobs(scene: Scene, transform: Transform, mask_only: bool, linear_rgb: bool, jobs: list, runs=None, fills=None) -> None:
     """(path, transform, rule) of every Path.mask the per-node route of `render` will call: leaves rendered
