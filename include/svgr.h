@@ -266,6 +266,47 @@ int svgr_batch_pick(svgr_batch* batch, const double* points, const int64_t* grid
 int svgr_hit_block(void);
 int svgr_hit_chunk(void);
 
+/* Signed distance fields: how far every point is from the outline of every path of the batch, on the same kept edges, point
+ * forms and workgroup geometry as the hit-testing entries above (no plan is needed, and one the batch has is left as it is).
+ *
+ * The arithmetic (csrc/svgr_sdf.h is its one home, compiled for host and device without fused multiply-adds): for an edge
+ * (a0, b0) -> (a1, b1) and a finite point (pa, pb), in the coordinate order of svgr_batch_all_edges,
+ *     x = a1 - a0;  y = b1 - b0;  len2 = x*x + y*y;  inv = len2 > 0 ? 1.0 / len2 : 0.0          (once per edge)
+ *     t = clamp(((pa - a0)*x + (pb - b0)*y) * inv, 0, 1);  qa = a0 + t*x;  qb = b0 + t*y
+ *     d2 = (pa - qa)*(pa - qa) + (pb - qb)*(pb - qb)
+ * A path's unsigned distance is sqrt(min d2) over its edges (an edge of length zero counts as its point; a path without edges
+ * is +inf away).  The sign is the inside predicate above under the path's fill rule: NEGATIVE inside, positive outside; with
+ * SVGR_SDF_UNSIGNED the result is the unsigned distance.  A point with a NaN or infinite coordinate is +inf away from
+ * everything, and outside.  Then d = min(max(d, -spread), spread); `spread` is +inf or finite and > 0.  With a finite spread the
+ * kernel skips the paths out of reach of a workgroup's points; that cannot show in a result as long as every path's edges form
+ * closed loops (every vertex ends as many edges as it starts), which is what a fill needs anyway and what every path of the
+ * library gives: an open subpath carries its closing line, and that line is part of the outline measured here.
+ *
+ * Encodings (the low bits of `flags`):
+ *     SVGR_SDF_F64   double: the clamped distance
+ *     SVGR_SDF_F32   float: (float)(0.5 - d / (2*spread)), in [0, 1], 0.5 on the outline, larger inside
+ *     SVGR_SDF_U8    uint8: rint((0.5 - d / (2*spread)) * 255) of the double, ties to even, saturated
+ * SVGR_SDF_F32 and SVGR_SDF_U8 need a finite spread.
+ *
+ * out[i * n_paths + p] is path p's value at point i; with SVGR_SDF_UNION out[i] is the minimum over the paths of their signed
+ * clamped distances, encoded.  The union is exact outside every path, and its sign is exact everywhere; INSIDE overlapping
+ * paths it is the depth in the deepest single path, not the distance to the union's outline.  A union over no paths is all
+ * +spread in its encoding.
+ *
+ * SVGR_E_INVALID, before anything is launched: points together with a grid or neither; a spread that is NaN or <= 0;
+ * SVGR_SDF_F32 or SVGR_SDF_U8 with an infinite spread; unknown flag bits.  SVGR_E_OVERFLOW when n_points * n_paths leaves 31
+ * bits (not for a union).  n_points == 0 launches nothing and succeeds.  The results of a pass live in device scratch of at
+ * most scratch_bytes (0: 256 MiB; never less than one workgroup's points, a grid's row of tiles) and the points are taken in as
+ * many passes as that needs; the results come back behind one wait, in the caller's row-major order.                          */
+#define SVGR_SDF_F64 0
+#define SVGR_SDF_F32 1
+#define SVGR_SDF_U8 2
+#define SVGR_SDF_ENCODING_MASK 3
+#define SVGR_SDF_UNION 4
+#define SVGR_SDF_UNSIGNED 8
+int svgr_batch_distance(svgr_batch* batch, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags,
+                        size_t scratch_bytes, void* out);
+
 /* Full device pipeline, asynchronous on the context stream, no host read-back:
  * transform+flatten -> bbox -> band binning -> tile kernel (LDS delta-coverage scatter, row scan,
  * fill rule, paint, source-over) -> store.  `out` must hold the output kind's bytes:

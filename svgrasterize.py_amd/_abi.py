@@ -7,6 +7,7 @@ library and inspecting its symbols (used by the CPU-side ABI test).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -220,6 +221,7 @@ _PROTOS = {
     "svgr_batch_pick": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.c_size_t, _P, _P]),
     "svgr_hit_block": (C.c_int, []),
     "svgr_hit_chunk": (C.c_int, []),
+    "svgr_batch_distance": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -515,6 +517,21 @@ class Batch:
                                             ptr(top) if n else None, ptr(bits) if want_bits and bits.size else None))
         return top, bits
 
+    def distance(self, points=None, grid=None, spread: float = math.inf, out: str = "f64", union: bool = False, signed: bool = True,
+                 scratch_bytes: int = 0) -> np.ndarray:
+        """svgr_batch_distance: the distance of every point to every path's outline, negative inside (`signed`), clamped to
+        +-`spread`: (n, n_paths), or (n,) with `union` (the minimum over the paths).  `out`: "f64" the clamped distance, "f32" /
+        "u8" the value 0.5 - d / (2 * spread) as float32 / rounded to uint8 (a finite spread).  Points as for `winding`."""
+        if out not in SDF_OUT:
+            raise ValueError(f"out is one of {sorted(SDF_OUT)}, not {out!r}")
+        enc, dtype = SDF_OUT[out]
+        spread = sdf_spread(spread, finite=enc != SDF_F64)
+        p, g, n, _keep = self._hit_points(points, grid)
+        res = np.zeros(n if union else (n, self.n_paths), dtype=dtype)
+        flags = enc | (SDF_UNION if union else 0) | (0 if signed else SDF_UNSIGNED)
+        _check(self.ctx.lib.svgr_batch_distance(self.handle, p, g, n, spread, flags, int(scratch_bytes), ptr(res) if res.size else None))
+        return res
+
     def set_bands(self, rank: int, world: int, strip_bands: int = 1):
         """Shard by interleaved strips of `strip_bands` bands; call plan() again afterwards."""
         _check(self.ctx.lib.svgr_batch_set_bands(self.handle, rank, world, strip_bands))
@@ -737,6 +754,37 @@ def hit_points(points) -> np.ndarray:
     if pts.ndim != 2 or pts.shape[1] != 2:
         raise ValueError(f"points are (n, 2) or a single pair, not {pts.shape}")
     return np.ascontiguousarray(pts)
+
+
+# svgr_batch_distance's flags (include/svgr.h)
+SDF_F64, SDF_F32, SDF_U8, SDF_UNION, SDF_UNSIGNED = 0, 1, 2, 4, 8
+SDF_OUT = {"f64": (SDF_F64, np.float64), "f32": (SDF_F32, np.float32), "u8": (SDF_U8, np.uint8)}
+
+
+def sdf_spread(spread, finite: bool = False) -> float:
+    """A spread as a float: +inf or finite and > 0, `finite` asking for the latter.  Anything else is a ValueError (before any
+    device work)."""
+    try:
+        s = float(spread)
+    except (TypeError, ValueError):
+        raise ValueError(f"a spread is a number, not {spread!r}") from None
+    if not s > 0.0:
+        raise ValueError(f"a spread is +inf or a finite value > 0, not {spread!r}")
+    if finite and math.isinf(s):
+        raise ValueError("the float32 and uint8 encodings need a finite spread")
+    return s
+
+
+def sdf_encode(d, spread: float, out: str) -> np.ndarray:
+    """Clamped distances in svgr_batch_distance's encoding `out` (csrc/svgr_sdf.h), on the host: for the constant fields of
+    queries that never reach a device (an empty path, an empty atlas)."""
+    d = np.asarray(d, dtype=np.float64)
+    if out == "f64":
+        return d
+    v = 0.5 - d / (2.0 * spread)
+    if out == "f32":
+        return v.astype(np.float32)
+    return np.clip(np.rint(v * 255.0), 0.0, 255.0).astype(np.uint8)
 
 
 def clip_tables(clips, n_paths):

@@ -1047,6 +1047,124 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_hit_resolve(uint32_t* __restrict_
     top[id] = hit_resolve(row, n_paths, pickable, clip_off, clip_group, group_off, group_src);
 }
 
+// ======================================================================================
+// Signed distance fields (svgr_batch_distance: the entry is at the end of the file; the arithmetic: svgr_sdf.h).
+// In front of the tile kernel for the same reason as the hit kernels.
+// ======================================================================================
+#include "svgr_sdf.h"
+
+// A workgroup of HIT_BLOCK points against every path, in k_hit_winding's structure: the points' extent is reduced once, the paths
+// are taken HIT_BLOCK at a time, a lane each, for the cull, and the edges of a path that stays go through LDS HIT_CHUNK at a time
+// -- prepared: the staging lane works out x, y and inv once per edge (svgr_sdf.h), so that the walk over the points has no
+// division -- and are read as broadcasts.  A lane keeps its point's min d2 and winding number in registers and takes one sqrt
+// per path.
+// The cull (finite `cull_spread` only; the host passes +inf for an infinite spread and for one below 2^-100): a path is skipped,
+// and counts as +spread, when its extent lies farther than `thr` from the points' box in a or in b, thr = spread * (1 + 2^-40) +
+// 2^-40 * (the largest magnitude among the extent's four numbers).  DESIGN.md 7r shows that every point of the workgroup then
+// gets exactly +spread from the walk as well (a distance that clamps, and winding 0), so the cull cannot show.  The side on which
+// the points' rays run THROUGH the path (the path wholly at larger a) is taken only when no point of the workgroup has |pb| <
+// 2^-400: the argument needs the predicate's products clear of underflow there.
+// OUT: the encoding (SDF_*).  UNION: one value per point, the minimum over the paths; else one per (point, path).  Results go to
+// out[(id - id0) * stride + p] in elements of the encoding: the caller's row-major order, the pass beginning at point id0.
+template <int OUT, bool UNION>
+__global__ __launch_bounds__(HIT_BLOCK) void k_sdf_distance(const double* __restrict__ edges, const int* __restrict__ off, const double* __restrict__ ext,
+                                                            const uint8_t* __restrict__ rule, int n_paths, const HitQuery q, long long group0,
+                                                            long long id0, double spread, double cull_spread, int is_signed, void* __restrict__ out) {
+    __shared__ __align__(16) double s_e[SDF_EDGE_DOUBLES * HIT_CHUNK];
+    __shared__ double s_red[5][HIT_BLOCK / 64];
+    __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK];
+    const int lane = threadIdx.x;
+    const long long group = group0 + blockIdx.x;
+    double pa = 0.0, pb = 0.0;
+    long long id = 0;
+    const bool live = hit_point(q, group, lane, pa, pb, id);
+    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (every d2 is NaN, which fmin drops, and every compare false: +inf away, winding 0)
+    // the extent of the workgroup's finite points, and their smallest |pb|
+    const bool fin = pa == pa;
+    double lo_a = fin ? pa : INFINITY, hi_a = fin ? pa : -INFINITY, lo_b = fin ? pb : INFINITY, hi_b = fin ? pb : -INFINITY;
+    double min_absb = fin ? fabs(pb) : INFINITY;
+    for (int d = 32; d > 0; d >>= 1) {
+        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); hi_a = fmax(hi_a, __shfl_xor(hi_a, d));
+        lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
+        min_absb = fmin(min_absb, __shfl_xor(min_absb, d));
+    }
+    if ((lane & 63) == 0) {
+        s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = hi_a; s_red[2][lane >> 6] = lo_b; s_red[3][lane >> 6] = hi_b;
+        s_red[4][lane >> 6] = min_absb;
+    }
+    __syncthreads();
+    for (int k = 0; k < HIT_BLOCK / 64; ++k) {
+        lo_a = fmin(lo_a, s_red[0][k]); hi_a = fmax(hi_a, s_red[1][k]); lo_b = fmin(lo_b, s_red[2][k]); hi_b = fmax(hi_b, s_red[3][k]);
+        min_absb = fmin(min_absb, s_red[4][k]);
+    }
+    const bool through_ok = min_absb >= 0x1p-400;
+    const size_t stride = UNION ? 1 : (size_t)n_paths;
+    const size_t at = (size_t)(id - id0) * stride;
+    double best = spread;   // (UNION: a skipped path counts as +spread, and no path can give more)
+    for (int base = 0; base < n_paths; base += HIT_BLOCK) {
+        __syncthreads();   // (the previous round's table has been read)
+        {
+            const int p = base + lane;
+            int e0 = 0, e1 = 0;
+            if (p < n_paths) {
+                e0 = off[p]; e1 = off[p + 1];
+                if (e1 > e0 && cull_spread < INFINITY) {
+                    const double mna = ext[4 * p], mnb = ext[4 * p + 1], mxa = ext[4 * p + 2], mxb = ext[4 * p + 3];
+                    const double big = fmax(fmax(fabs(mna), fabs(mxa)), fmax(fabs(mnb), fabs(mxb)));
+                    const double thr = cull_spread * (1.0 + 0x1p-40) + 0x1p-40 * big;
+                    if (mnb - hi_b > thr || lo_b - mxb > thr || lo_a - mxa > thr || (through_ok && mna - hi_a > thr)) e1 = e0;
+                }
+            }
+            s_e0[lane] = e0; s_e1[lane] = e1;
+        }
+        __syncthreads();
+        const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
+        for (int j = 0; j < n_here; ++j) {
+            const int p = base + j;
+            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+            double v = spread;
+            if (e1 > e0) {
+                double m = INFINITY;
+                int w = 0;
+                for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
+                    const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
+                    __syncthreads();   // (the previous chunk has been read)
+                    if (lane < n) {
+                        const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
+                        const double2 q0 = src[0], q1 = src[1];
+                        double pe[SDF_EDGE_DOUBLES];
+                        sdf_edge_prepare(q0.x, q0.y, q1.x, q1.y, pe);
+                        double2* dst = (double2*)s_e + 3 * lane;
+                        dst[0] = make_double2(pe[0], pe[1]); dst[1] = make_double2(pe[2], pe[3]); dst[2] = make_double2(pe[4], pe[5]);
+                    }
+                    __syncthreads();
+                    for (int k = 0; k < n; ++k) {
+                        const double2 ab = ((const double2*)s_e)[3 * k], xy = ((const double2*)s_e)[3 * k + 1], ib = ((const double2*)s_e)[3 * k + 2];
+                        const double da = pa - ab.x, db = pb - ab.y;
+                        m = fmin(m, sdf_edge_d2(ab.x, ab.y, xy.x, xy.y, ib.x, pa, pb, da, db));
+                        w += sdf_edge_term(ab.y, ib.y, xy.x, xy.y, pb, da, db);
+                    }
+                }
+                v = sdf_finish(m, w, rule[p] & 1, is_signed, spread);
+            }
+            if constexpr (UNION) {
+                best = fmin(best, v);
+            } else if (live) {
+                if constexpr (OUT == SDF_F64) ((double*)out)[at + (size_t)p] = v;
+                else if constexpr (OUT == SDF_F32) ((float*)out)[at + (size_t)p] = sdf_encode_f32(v, spread);
+                else ((uint8_t*)out)[at + (size_t)p] = sdf_encode_u8(v, spread);
+            }
+        }
+    }
+    if constexpr (UNION) {
+        if (live) {
+            if constexpr (OUT == SDF_F64) ((double*)out)[at] = best;
+            else if constexpr (OUT == SDF_F32) ((float*)out)[at] = sdf_encode_f32(best, spread);
+            else ((uint8_t*)out)[at] = sdf_encode_u8(best, spread);
+        }
+    }
+}
+
 // Plan only: exclusive prefix sums of the per-segment edge counts (seg_off[n] = their total).  One workgroup, a chunk of
 // 1024 segments per step with the running total carried along: a plan-time pass over a few thousand to a few million ints.
 __global__ __launch_bounds__(1024) void k_seg_scan(const int* __restrict__ seg_cnt, int n, int* __restrict__ seg_off) {
@@ -9717,6 +9835,76 @@ int svgr_batch_pick(svgr_batch* b, const double* points, const int64_t* grid, in
                     memcpy(bits_out + (size_t)(r * q.cols + c) * (size_t)words, staged.data() + ((size_t)g * HIT_BLOCK + (size_t)lane) * (size_t)words,
                            sizeof(uint32_t) * (size_t)words);
                 }
+        return 0;
+    });
+}
+
+// Signed distance fields (the arithmetic and its contract: svgr_sdf.h).  The points go through in passes of whole
+// workgroups -- of whole rows of tiles for a grid, so that a pass is a contiguous run of the caller's row-major order -- as
+// many at a time as the scratch holds.
+int svgr_batch_distance(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags, size_t scratch_bytes,
+                        void* out) {
+    static const char* entry = "svgr_batch_distance";
+    return abi_guard(entry, [&]() -> int {
+        if (!b || n_points < 0) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+        if (flags & ~(SVGR_SDF_ENCODING_MASK | SVGR_SDF_UNION | SVGR_SDF_UNSIGNED)) return fail(SVGR_E_INVALID, "%s: unknown flags 0x%x", entry, (unsigned)flags);
+        const int enc = flags & SVGR_SDF_ENCODING_MASK;
+        if (enc >= SDF_ENCODINGS) return fail(SVGR_E_INVALID, "%s: unknown encoding %d", entry, enc);
+        if (!(spread > 0.0)) return fail(SVGR_E_INVALID, "%s: the spread is +inf or a finite value > 0, not %g", entry, spread);
+        if (enc != SDF_F64 && !(spread < INFINITY)) return fail(SVGR_E_INVALID, "%s: the float32 and uint8 encodings need a finite spread", entry);
+        PoolBlock d_pts, d_out;
+        HitQuery q;
+        long long n_groups = 0;
+        if (int rc = hit_query(entry, points, grid, n_points, q, n_groups)) return rc;
+        const int64_t np = b->n_paths;
+        const bool uni = (flags & SVGR_SDF_UNION) != 0;
+        if (n_points == 0 || (np == 0 && !uni)) return 0;
+        if (!uni && n_points > 0x7fffffffll / np) return fail(SVGR_E_OVERFLOW, "%s: %lld points x %lld paths leave 31 bits", entry, (long long)n_points, (long long)np);
+        if (!out) return fail(SVGR_E_INVALID, "%s: out is NULL", entry);
+        const size_t elem = (size_t)sdf_elem_bytes(enc);
+        if (np == 0) {   // a union over no paths: +spread everywhere
+            for (int64_t i = 0; i < n_points; ++i) {
+                if (enc == SDF_F64) ((double*)out)[i] = spread;
+                else if (enc == SDF_F32) ((float*)out)[i] = sdf_encode_f32(spread, spread);
+                else ((uint8_t*)out)[i] = sdf_encode_u8(spread, spread);
+            }
+            return 0;
+        }
+        HIPCHK(enter_ctx(b->ctx));
+        hipStream_t st = b->ctx->stream;
+        if (int rc = hit_prepare(b)) return rc;
+        if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
+        // a pass unit: a workgroup's points, or a row of tiles of a grid
+        const size_t point_bytes = elem * (uni ? 1 : (size_t)np);
+        const long long unit_groups = grid ? q.tiles_x : 1, unit_points = grid ? HIT_TILE * q.cols : HIT_BLOCK;
+        const long long n_units = n_groups / unit_groups;
+        const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
+        const long long per_pass = std::min<long long>(n_units, std::max<long long>((long long)(budget / (point_bytes * (size_t)unit_points)), 1));
+        const long long pass_points = std::min<long long>(n_points, per_pass * unit_points);
+        HIPCHK(d_out.alloc(point_bytes * (size_t)pass_points));
+        const double cull_spread = (spread < INFINITY && spread >= 0x1p-100) ? spread : (double)INFINITY;
+        const int is_signed = (flags & SVGR_SDF_UNSIGNED) ? 0 : 1;
+        for (long long u0 = 0; u0 < n_units; u0 += per_pass) {
+            const long long nu = std::min<long long>(per_pass, n_units - u0);
+            const long long i0 = u0 * unit_points, i1 = std::min<long long>(n_points, (u0 + nu) * unit_points);
+            const dim3 g((unsigned)(nu * unit_groups)), blk(HIT_BLOCK);
+#define SDF_LAUNCH(OUT, UNI)                                                                                                                   \
+    SVGR_LAUNCH((k_sdf_distance<OUT, UNI>), g, blk, 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p, (const double*)b->hit_ext.p, \
+                (const uint8_t*)b->path_rule.p, (int)np, q, u0 * unit_groups, i0, spread, cull_spread, is_signed, d_out.p)
+            if (uni) {
+                if (enc == SDF_F64) SDF_LAUNCH(SDF_F64, true);
+                else if (enc == SDF_F32) SDF_LAUNCH(SDF_F32, true);
+                else SDF_LAUNCH(SDF_U8, true);
+            } else {
+                if (enc == SDF_F64) SDF_LAUNCH(SDF_F64, false);
+                else if (enc == SDF_F32) SDF_LAUNCH(SDF_F32, false);
+                else SDF_LAUNCH(SDF_U8, false);
+            }
+#undef SDF_LAUNCH
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
         return 0;
     });
 }

@@ -16,7 +16,8 @@ import warnings
 import numpy as np
 
 from . import _abi
-from .geometry import PATH_ARC, Path
+from .geometry import FLATNESS, PATH_ARC, Path
+from .sdf import SdfAtlas, font_sdf_atlas
 
 FONT_STYLE_NORMAL = "normal"
 # generic families the well-known names fall back to (S:2653-2655)
@@ -163,6 +164,16 @@ class Font:
         seg_count = np.diff(seg_off.astype(np.int64))[inst_glyph]
         keep = np.repeat(visible, seg_count)
         return Path.from_segments(a_types[seg_rows], out[keep], a_sizes[_ranges(sub_off[shown], sub_off[shown + 1])]), advance * scale
+
+    def sdf_atlas(self, string: str, size: float, spread: float, dtype=np.uint8, max_cols: int = 1024, flatness: float = FLATNESS) -> SdfAtlas:
+        """An SDF atlas of the distinct glyphs of `string` (beyond the reference), ligatures and the missing glyph as
+        `str_to_glyphs` resolves them: every glyph scaled by ``size / units_per_em`` and y-flipped, in a cell of its own -- the
+        integer box around its control points grown by ``ceil(spread)`` pixels on every side --, the cells shelf-packed into an
+        image at most `max_cols` wide.  ``dtype`` uint8 / float32: ``0.5 - d / (2 * spread)``, 0.5 on the outline and larger inside
+        (times 255 and rounded for uint8); float64: the signed distance in pixels clamped to ``+-spread``, negative inside.  A glyph
+        without an outline (a space) gets a cell of zero size and its advance; a string without glyphs a 0 x 0 image.  One batch,
+        a path per glyph, and one union grid query on the device (svgr_batch_distance); see sdf.py."""
+        return font_sdf_atlas(self, string, size, spread, dtype, max_cols, flatness)
 
     def names(self) -> dict:
         return {g.name: g.unicode for g in self.glyphs.values()}

@@ -31,6 +31,15 @@ STROKE_CAP_BUTT, STROKE_CAP_ROUND, STROKE_CAP_SQUARE = "butt", "round", "square"
 _RULES = {None: 0, PATH_FILL_NONZERO: 0, PATH_FILL_EVENODD: 1}
 
 FLATNESS = 0.1  # S:955
+# Path.sdf's dtypes -> Batch.distance's encodings
+_SDF_DTYPES = {np.dtype(np.float64): "f64", np.dtype(np.float32): "f32", np.dtype(np.uint8): "u8"}
+
+
+def _sdf_dtype(dtype):
+    try:
+        return np.dtype(dtype)
+    except TypeError:
+        return None
 
 
 # --------------------------------------------------------------------------------------
@@ -622,6 +631,55 @@ class Path:
         """Is each of `points` inside the path's stroke (beyond the reference; ``isPointInStroke``): the stroke outline is built
         in user space and then transformed, as a render does."""
         return self.stroke(width, linecap, linejoin).contains(points, transform, PATH_FILL_NONZERO)
+
+    def distance(self, points, transform: Transform | None = None, fill_rule: str | None = None, spread: float = math.inf,
+                 signed: bool = True, flatness: float = FLATNESS) -> np.ndarray:
+        """How far each of `points` is from the path's outline, a float64 array ``(n,)`` (beyond the reference): negative inside
+        the fill under `fill_rule`, positive outside -- ``signed=False``: the unsigned distance, which answers "is the pointer
+        within 3 px of this line" without a stroke outline (the outline is the fill's: a subpath left open is measured with its
+        closing line) -- clamped to ``+-spread``.  Points,
+        coordinate order and contract are those of ``winding``; the outline is the flattened one, so a distance is off the true
+        curve's by at most `flatness`.  A NaN or infinite point is ``+spread`` away.  An empty path is ``+inf`` (or `spread`) away
+        and touches no device.  Eager, on the device (svgr_batch_distance); DESIGN.md 7r has the arithmetic."""
+        pts = _abi.hit_points(points)   # (a wrong shape, rule or spread: ValueError before any device work)
+        if fill_rule not in _RULES:
+            raise ValueError(f"Invalid fill rule: {fill_rule}")
+        spread = _abi.sdf_spread(spread)
+        segs, kinds = self.packed()
+        if len(segs) == 0 or len(pts) == 0:
+            return np.full(len(pts), spread, dtype=np.float64)
+        batch = _abi.Batch(_abi.Context.get(), segs, kinds, [0, len(segs)], (transform if transform is not None else Transform()).m6(),
+                           [_RULES[fill_rule]], [np.zeros(4)], viewport=None, flatness=flatness)
+        try:
+            return np.ascontiguousarray(batch.distance(pts, spread=spread, signed=signed)[:, 0])
+        finally:
+            batch.destroy()
+
+    def sdf(self, transform: Transform | None, viewport, spread: float, dtype=np.float32, fill_rule: str | None = None,
+            flatness: float = FLATNESS) -> np.ndarray:
+        """The path's signed distance field over ``viewport = (row0, col0, rows, cols)``: a ``(rows, cols)`` array of the values at
+        the pixel centres (beyond the reference).  ``dtype`` float64: the signed distance clamped to ``+-spread``, negative
+        inside; float32: ``0.5 - d / (2 * spread)``, in [0, 1], 0.5 on the outline and larger inside, what SDF text shaders
+        sample; uint8: that value times 255, rounded to nearest-even.  Any other dtype is a ``TypeError``.  The points are made
+        on the device (svgr_batch_distance's grid form)."""
+        enc = _SDF_DTYPES.get(_sdf_dtype(dtype))
+        if enc is None:
+            raise TypeError(f"an SDF is float64, float32 or uint8, not {dtype!r}")
+        if fill_rule not in _RULES:
+            raise ValueError(f"Invalid fill rule: {fill_rule}")
+        row0, col0, rows, cols = (int(v) for v in viewport)
+        if rows < 0 or cols < 0:
+            raise ValueError("a viewport has rows >= 0 and cols >= 0")
+        spread = _abi.sdf_spread(spread, finite=enc != "f64")
+        segs, kinds = self.packed()
+        if len(segs) == 0 or rows * cols == 0:
+            return _abi.sdf_encode(np.full((rows, cols), spread), spread, enc)
+        batch = _abi.Batch(_abi.Context.get(), segs, kinds, [0, len(segs)], (transform if transform is not None else Transform()).m6(),
+                           [_RULES[fill_rule]], [np.zeros(4)], viewport=None, flatness=flatness)
+        try:
+            return batch.distance(grid=(row0, col0, rows, cols), spread=spread, out=enc, union=True).reshape(rows, cols)
+        finally:
+            batch.destroy()
 
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
