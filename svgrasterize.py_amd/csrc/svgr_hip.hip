@@ -55,6 +55,7 @@
 
 #include "../../include/svgr.h"
 #include "svgr_core.h"
+#include "svgr_blob.h"
 
 using namespace svgr;
 
@@ -301,6 +302,70 @@ struct PoolBlock {
     }
     template <class T>
     T* as() const { return (T*)p; }
+};
+
+struct StreamDrain {   // no block and no host buffer of a call goes away while the stream may still use it
+    hipStream_t st;
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+};
+
+// The call frame of a pass entry (svgr_path_dash ... svgr_deflate): arrays of the caller go up in one piece (svgr_blob.h), the
+// context's stream works on them, one result block whose last section is the kernels' error flag comes down.  The frame owns all
+// the stream may touch -- host blob, device blocks, scratch, the result's host copy -- and `drain` is its LAST member: on every
+// way out the stream is waited for before any of them is released.  So scratch comes from scratch(), never from a PoolBlock of
+// the entry's own, and a host buffer the stream writes is declared in front of the frame.
+struct PassFrame {
+    svgr_ctx* ctx;
+    hipStream_t st;
+    HostBlob blob;              // what upload() sends
+    PoolBlock in, out;
+    PoolBlock extra[13];        // scratch(): device-only blocks of the call
+    int n_extra = 0, err = 0;   // err: the first failure of scratch(), which the entry returns before it launches anything
+    std::vector<char> back;     // finish(): the host copy of out's first `out_bytes`
+    size_t out_bytes = 0;
+    Section<int> bad;           // the error flag, behind the entry's own sections of `out`
+    StreamDrain drain;
+    explicit PassFrame(svgr_ctx* c) : ctx(c), st(c->stream), drain{c->stream} {}
+
+    // enters the context, enqueues the one upload
+    int upload() {
+        HIPCHK(enter_ctx(ctx));
+        HIPCHK(in.alloc(blob.bytes(), ctx->device));
+        HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.bytes(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    // the result block: the sections the entry took from `lay`, the error flag (cleared here), and `device_only` bytes that are
+    // never downloaded (behind())
+    int result(Layout lay, size_t device_only = 0) {
+        bad = lay.take<int>(1);
+        out_bytes = lay.bytes();
+        HIPCHK(out.alloc(out_bytes + device_only, ctx->device));
+        HIPCHK(hipMemsetAsync(bad.on(out.p), 0, sizeof(int), st));
+        return 0;
+    }
+    int begin(Layout lay, size_t device_only = 0) {
+        if (int rc = upload()) return rc;
+        return result(lay, device_only);
+    }
+    template <class T>
+    T* behind() const { return (T*)(out.as<char>() + out_bytes); }
+    template <class T>
+    T* scratch(size_t n) {
+        if (err) return nullptr;
+        if (n_extra == (int)(sizeof extra / sizeof extra[0])) err = fail(SVGR_E_STATE, "PassFrame: out of scratch blocks");
+        else if (hipError_t e = extra[n_extra].alloc(n * sizeof(T), ctx->device))
+            err = fail(SVGR_E_HIP, "a scratch block of %zu bytes: %s", n * sizeof(T), hipGetErrorString(e));
+        return err ? nullptr : extra[n_extra++].as<T>();
+    }
+    // the one download and the one wait; `what`: `message` if a kernel raised the flag
+    int finish(const char* what, const char* message) {
+        HIPCHK(hipGetLastError());
+        back.resize(out_bytes);
+        HIPCHK(hipMemcpyAsync(back.data(), out.p, out_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (*bad.on(back.data())) return fail(SVGR_E_STATE, "%s: %s", what, message);
+        return 0;
+    }
 };
 
 // a device array that owns its block (unless it is a view); release() frees it early
@@ -7937,10 +8002,6 @@ struct DashCntOp {
 };
 struct DashSub { long long A, n, nl, dbase, nd; int mode, pad; };   // k_dash_wrap's row of a subpath
 struct DashTot { DashCnt c; int too_many, pad; };                   // what the host reads back after the counting kernels
-struct StreamDrain {   // no block and no host buffer of a call goes away while the stream may still use it
-    hipStream_t st;
-    ~StreamDrain() { (void)hipStreamSynchronize(st); }
-};
 
 // inclusive scan of DASH_S items per workgroup, in place; tot[b] = the workgroup's sum
 template <class T, class Op>
@@ -8198,6 +8259,62 @@ static void dash_scan(hipStream_t st, T* a, T* tot, int n) {
     }
 }
 
+// ---- what the passes over a path (dash, markers, text on a path) share: the check and the upload of the path
+// the segment count of `n_subpaths` subpaths; the segment arrays may be null while there is no segment
+static int path_count(const char* what, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes, int64_t n_subpaths,
+                      int64_t& n) {
+    n = 0;
+    for (int64_t s = 0; s < n_subpaths; ++s) {
+        if (subpath_sizes[s] < 0) return fail(SVGR_E_INVALID, "%s: negative subpath size", what);
+        n += subpath_sizes[s];
+        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: more than 2^30 segments", what);
+    }
+    if (n > 0 && (!seg_types || !seg_params)) return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+    return 0;
+}
+// types and coordinates of n segments in the stroker's array form
+static int textpath_check_segments(const char* what, const int32_t* types, const double* params, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int t = types[i];
+        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
+            return fail(SVGR_E_INVALID, "%s: segment %lld has type %d (quadratics and arcs are converted by the caller)", what, (long long)i, t);
+        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
+        for (int e = 0; e < np; ++e)
+            if (!(std::fabs(params[8 * i + e]) <= DASH_COORD_MAX))
+                return fail(SVGR_E_INVALID, "%s: segment %lld has a coordinate that is not finite or beyond 1e150", what, (long long)i);
+    }
+    return 0;
+}
+// The head of the three uploads: coordinates, types, the subpath of every segment, the subpaths' first segments (empty
+// subpaths are skipped).  The path has passed path_count.
+struct PathSections {
+    Section<double> params;
+    Section<int32_t> types, seg_sub, sub_off;
+    int n, n_sub;
+};
+static PathSections path_put(HostBlob& blob, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes, int64_t n_subpaths,
+                             int64_t n) {
+    std::vector<int32_t> sub_off{0};
+    for (int64_t s = 0; s < n_subpaths; ++s)
+        if (subpath_sizes[s] > 0) sub_off.push_back(sub_off.back() + subpath_sizes[s]);
+    PathSections p;
+    p.n = (int)n;
+    p.n_sub = (int)sub_off.size() - 1;
+    p.params = blob.put(seg_params, (size_t)n * 8);
+    p.types = blob.put(seg_types, (size_t)n);
+    int32_t* seg_sub;
+    p.seg_sub = blob.reserve((size_t)n, seg_sub);
+    for (int s = 0; seg_sub && s < p.n_sub; ++s)   // (null in HostBlob::build's sizing pass)
+        for (int i = sub_off[(size_t)s]; i < sub_off[(size_t)s + 1]; ++i) seg_sub[i] = s;
+    p.sub_off = blob.put(sub_off.data(), sub_off.size());
+    return p;
+}
+// params and types of a result that is a path, from the downloaded block
+static void stroke_out_take(svgr_stroke_out& res, const char* back, Section<double> params, Section<int32_t> types) {
+    res.params.assign(params.on(back), params.on(back) + params.n);
+    res.types.assign(types.on(back), types.on(back) + types.n);
+}
+
 static int path_dash_impl(svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
                           int64_t n_subpaths, const double* dashes, int64_t n_dashes, double offset, double path_length,
                           svgr_stroke_out** out) {
@@ -8205,20 +8322,8 @@ static int path_dash_impl(svgr_ctx* ctx, const int32_t* seg_types, const double*
         return fail(SVGR_E_INVALID, "svgr_path_dash: bad arguments");
     if (!std::isfinite(offset)) return fail(SVGR_E_INVALID, "svgr_path_dash: the offset is not finite");
     int64_t n = 0;
-    for (int64_t s = 0; s < n_subpaths; ++s) {
-        if (subpath_sizes[s] < 0) return fail(SVGR_E_INVALID, "svgr_path_dash: negative subpath size");
-        n += subpath_sizes[s];
-        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "svgr_path_dash: more than 2^30 segments");
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        const int t = seg_types[i];
-        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
-            return fail(SVGR_E_INVALID, "svgr_path_dash: segment %lld has type %d (quadratics and arcs are converted by the caller)", (long long)i, t);
-        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
-        for (int e = 0; e < np; ++e)
-            if (!(std::fabs(seg_params[8 * i + e]) <= DASH_COORD_MAX))
-                return fail(SVGR_E_INVALID, "svgr_path_dash: segment %lld has a coordinate that is not finite or beyond 1e150", (long long)i);
-    }
+    if (int rc = path_count("svgr_path_dash", seg_types, seg_params, subpath_sizes, n_subpaths, n)) return rc;
+    if (int rc = textpath_check_segments("svgr_path_dash", seg_types, seg_params, n)) return rc;
     std::unique_ptr<svgr_stroke_out> res(new svgr_stroke_out());
     // a pattern that asks for a solid stroke: the input comes back as it is
     bool solid = n_dashes < 1;
@@ -8242,60 +8347,41 @@ static int path_dash_impl(svgr_ctx* ctx, const int32_t* seg_types, const double*
         return 0;
     }
     if (!ctx) return fail(SVGR_E_INVALID, "svgr_path_dash: no context");
-    // ---- one upload: coordinates, types, the subpath of every segment, the subpaths' first segments, the dash list
-    std::vector<int32_t> sub_off{0};
-    for (int64_t s = 0; s < n_subpaths; ++s)
-        if (subpath_sizes[s] > 0) sub_off.push_back(sub_off.back() + subpath_sizes[s]);
-    const int n_sub = (int)sub_off.size() - 1, ni = (int)n, nd_raw = (int)n_dashes;
-    const size_t b_params = (size_t)n * 64, b_types = (((size_t)n * 4) + 63) & ~(size_t)63, b_sub = (((size_t)(n_sub + 1) * 4) + 63) & ~(size_t)63;
-    const size_t b_raw = (size_t)nd_raw * 8;
-    std::vector<char> blob(b_params + 2 * b_types + b_sub + b_raw);
-    memcpy(blob.data(), seg_params, b_params);
-    memcpy(blob.data() + b_params, seg_types, (size_t)n * 4);
-    int32_t* h_seg_sub = (int32_t*)(blob.data() + b_params + b_types);
-    for (int s = 0; s < n_sub; ++s)
-        for (int i = sub_off[(size_t)s]; i < sub_off[(size_t)s + 1]; ++i) h_seg_sub[i] = s;
-    memcpy(blob.data() + b_params + 2 * b_types, sub_off.data(), (size_t)(n_sub + 1) * 4);
-    memcpy(blob.data() + b_params + 2 * b_types + b_sub, dashes, b_raw);
-
-    HIPCHK(enter_ctx(ctx));
+    // ---- one upload: the path, the dash list
+    PassFrame f(ctx);
+    hipStream_t st = f.st;
+    PathSections path;
+    Section<double> raw;
+    f.blob.build([&](HostBlob& b) {
+        path = path_put(b, seg_types, seg_params, subpath_sizes, n_subpaths, n);
+        raw = b.put(dashes, (size_t)n_dashes);
+    });
+    const int n_sub = path.n_sub, ni = path.n, nd_raw = (int)n_dashes;
+    if (int rc = f.upload()) return rc;
     if (int rc = ensure_pinned(ctx, sizeof(DashTot))) return rc;
-    hipStream_t st = ctx->stream;
     const int nb = (ni + DASH_S - 1) / DASH_S;
-    std::vector<char> back;
-    PoolBlock in, tab, len, cum, cnt, tops_fv, tops_cnt, sub, pat, tot, outb, dstart, dkind;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(tab.alloc((size_t)n * DASH_SUB * 8, ctx->device));
-    HIPCHK(len.alloc((size_t)n * 8, ctx->device));
-    HIPCHK(cum.alloc((size_t)n * sizeof(DashFV), ctx->device));
-    HIPCHK(cnt.alloc((size_t)n * sizeof(DashCnt), ctx->device));
-    HIPCHK(tops_fv.alloc((size_t)nb * sizeof(DashFV), ctx->device));
-    HIPCHK(tops_cnt.alloc((size_t)nb * sizeof(DashCnt), ctx->device));
-    HIPCHK(sub.alloc((size_t)n_sub * sizeof(DashSub), ctx->device));
-    HIPCHK(pat.alloc(sizeof(DashPat), ctx->device));
-    HIPCHK(tot.alloc(sizeof(DashTot), ctx->device));
-    HIPCHK(hipMemsetAsync(tot.p, 0, sizeof(DashTot), st));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const double* d_params = in.as<double>();
-    const int* d_types = (const int*)(in.as<char>() + b_params);
-    const int* d_seg_sub = (const int*)(in.as<char>() + b_params + b_types);
-    const int* d_sub_off = (const int*)(in.as<char>() + b_params + 2 * b_types);
-    const double* d_raw = (const double*)(in.as<char>() + b_params + 2 * b_types + b_sub);
+    double *tab = f.scratch<double>((size_t)n * DASH_SUB), *len = f.scratch<double>((size_t)n);
+    DashFV *cum = f.scratch<DashFV>((size_t)n), *tops_fv = f.scratch<DashFV>((size_t)nb);
+    DashCnt *cnt = f.scratch<DashCnt>((size_t)n), *tops_cnt = f.scratch<DashCnt>((size_t)nb);
+    DashSub* sub = f.scratch<DashSub>((size_t)n_sub);
+    DashPat* pat = f.scratch<DashPat>(1);
+    DashTot* tot = f.scratch<DashTot>(1);
+    if (f.err) return f.err;
+    HIPCHK(hipMemsetAsync(tot, 0, sizeof(DashTot), st));
+    const double* d_params = path.params.on(f.in.p);
+    const int* d_types = path.types.on(f.in.p);
+    const int* d_seg_sub = path.seg_sub.on(f.in.p);
+    const int* d_sub_off = path.sub_off.on(f.in.p);
     const dim3 seg_grid((unsigned)((ni + DASH_SEGS_WG - 1) / DASH_SEGS_WG));
-    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, d_seg_sub, d_sub_off, ni, tab.as<double>(), len.as<double>(),
-                cum.as<DashFV>());
-    dash_scan<DashFV, DashFVOp>(st, cum.as<DashFV>(), tops_fv.as<DashFV>(), ni);
-    SVGR_LAUNCH(k_dash_pattern, dim3(1), dim3(256), 0, st, (const DashFV*)cum.p, d_sub_off, n_sub, d_raw, nd_raw, offset, path_length,
-                pat.as<DashPat>());
-    SVGR_LAUNCH(k_dash_count, grid1((size_t)ni), dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_seg_sub, d_sub_off, (const double*)len.p,
-                (const DashFV*)cum.p, ni, cnt.as<DashCnt>(), tot.as<DashTot>());
-    dash_scan<DashCnt, DashCntOp>(st, cnt.as<DashCnt>(), tops_cnt.as<DashCnt>(), ni);
-    SVGR_LAUNCH(k_dash_wrap, grid1((size_t)n_sub), dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_sub_off, (const DashFV*)cum.p,
-                (const DashCnt*)cnt.p, ni, n_sub, sub.as<DashSub>(), tot.as<DashTot>());
+    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, d_seg_sub, d_sub_off, ni, tab, len, cum);
+    dash_scan<DashFV, DashFVOp>(st, cum, tops_fv, ni);
+    SVGR_LAUNCH(k_dash_pattern, dim3(1), dim3(256), 0, st, cum, d_sub_off, n_sub, raw.on(f.in.p), nd_raw, offset, path_length, pat);
+    SVGR_LAUNCH(k_dash_count, grid1((size_t)ni), dim3(256), 0, st, pat, d_types, d_seg_sub, d_sub_off, len, cum, ni, cnt, tot);
+    dash_scan<DashCnt, DashCntOp>(st, cnt, tops_cnt, ni);
+    SVGR_LAUNCH(k_dash_wrap, grid1((size_t)n_sub), dim3(256), 0, st, pat, d_types, d_sub_off, cum, cnt, ni, n_sub, sub, tot);
     HIPCHK(hipGetLastError());
     // ---- the counts come back through the context's page-locked staging
-    HIPCHK(hipMemcpyAsync(ctx->pinned, tot.p, sizeof(DashTot), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ctx->pinned, tot, sizeof(DashTot), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     DashTot counted;
     memcpy(&counted, ctx->pinned, sizeof counted);
@@ -8308,33 +8394,24 @@ static int path_dash_impl(svgr_ctx* ctx, const int32_t* seg_types, const double*
         *out = res.release();
         return 0;
     }
+    // ---- the second phase: now that its size is known, the result (the placing kernels' error flag travels with it)
     const size_t n_out = (size_t)(total.p + total.d), n_dash = (size_t)total.d;
-    const size_t o_types = n_out * 64, o_sizes = o_types + ((n_out * 4 + 63) & ~(size_t)63);
-    const size_t o_bad = o_sizes + ((n_dash * 4 + 63) & ~(size_t)63), o_end = o_bad + 4;   // (the placing kernels' error flag travels with the result)
-    HIPCHK(outb.alloc(o_end, ctx->device));
-    HIPCHK(dstart.alloc(n_dash * 4, ctx->device));
-    HIPCHK(dkind.alloc(n_dash * 4, ctx->device));
-    double* d_out_params = outb.as<double>();
-    int* d_out_types = (int*)(outb.as<char>() + o_types);
-    int* d_out_sizes = (int*)(outb.as<char>() + o_sizes);
-    int* d_bad = (int*)(outb.as<char>() + o_bad);
-    HIPCHK(hipMemsetAsync(d_bad, 0, 4, st));
-    SVGR_LAUNCH(k_dash_emit, seg_grid, dim3(256), 0, st, (const DashPat*)pat.p, d_types, d_params, d_seg_sub, d_sub_off, (const double*)tab.p,
-                (const double*)len.p, (const DashFV*)cum.p, (const DashCnt*)cnt.p, (const DashSub*)sub.p, ni, (long long)n_out,
-                (long long)n_dash, d_out_types, d_out_params, dstart.as<int>(), dkind.as<int>(), d_bad);
-    SVGR_LAUNCH(k_dash_close, grid1(n_dash), dim3(256), 0, st, (const int*)dstart.p, (const int*)dkind.p, total.p, total.d, d_out_types,
-                d_out_params, d_out_sizes, d_bad);
-    HIPCHK(hipGetLastError());
-    // ---- one download
-    back.resize(o_end);
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "svgr_path_dash: the counting and the placing kernels disagree about a place");
-    res->params.assign((const double*)back.data(), (const double*)back.data() + n_out * 8);
-    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
-    res->sizes.assign((const int32_t*)(back.data() + o_sizes), (const int32_t*)(back.data() + o_sizes) + n_dash);
+    Layout lay;
+    const Section<double> o_params = lay.take<double>(n_out * 8);
+    const Section<int32_t> o_types = lay.take<int32_t>(n_out), o_sizes = lay.take<int32_t>(n_dash);
+    if (int rc = f.result(lay)) return rc;
+    int *dstart = f.scratch<int>(n_dash), *dkind = f.scratch<int>(n_dash);
+    if (f.err) return f.err;
+    double* d_out_params = o_params.on(f.out.p);
+    int* d_out_types = o_types.on(f.out.p);
+    int* d_bad = f.bad.on(f.out.p);
+    SVGR_LAUNCH(k_dash_emit, seg_grid, dim3(256), 0, st, pat, d_types, d_params, d_seg_sub, d_sub_off, tab, len, cum, cnt, sub, ni,
+                (long long)n_out, (long long)n_dash, d_out_types, d_out_params, dstart, dkind, d_bad);
+    SVGR_LAUNCH(k_dash_close, grid1(n_dash), dim3(256), 0, st, dstart, dkind, total.p, total.d, d_out_types, d_out_params, o_sizes.on(f.out.p),
+                d_bad);
+    if (int rc = f.finish("svgr_path_dash", "the counting and the placing kernels disagree about a place")) return rc;
+    stroke_out_take(*res, f.back.data(), o_params, o_types);
+    res->sizes.assign(o_sizes.on(f.back.data()), o_sizes.on(f.back.data()) + n_dash);
     *out = res.release();
     return 0;
 }
@@ -8416,27 +8493,12 @@ static int path_markers_impl(svgr_ctx* ctx, const int32_t* seg_types, const doub
     if (!out || n_subpaths < 0 || (n_subpaths > 0 && !subpath_sizes))
         return fail(SVGR_E_INVALID, "svgr_path_markers: bad arguments");
     int64_t n = 0;
-    for (int64_t s = 0; s < n_subpaths; ++s) {
-        if (subpath_sizes[s] < 0) return fail(SVGR_E_INVALID, "svgr_path_markers: negative subpath size");
-        n += subpath_sizes[s];
-        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "svgr_path_markers: more than 2^30 segments");
-    }
-    if (n > 0 && (!seg_types || !seg_params)) return fail(SVGR_E_INVALID, "svgr_path_markers: bad arguments");
-    for (int64_t i = 0; i < n; ++i) {
-        const int t = seg_types[i];
-        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
-            return fail(SVGR_E_INVALID, "svgr_path_markers: segment %lld has type %d (quadratics and arcs are converted by the caller)", (long long)i, t);
-        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
-        for (int e = 0; e < np; ++e)
-            if (!(std::fabs(seg_params[8 * i + e]) <= DASH_COORD_MAX))
-                return fail(SVGR_E_INVALID, "svgr_path_markers: segment %lld has a coordinate that is not finite or beyond 1e150", (long long)i);
-    }
+    if (int rc = path_count("svgr_path_markers", seg_types, seg_params, subpath_sizes, n_subpaths, n)) return rc;
+    if (int rc = textpath_check_segments("svgr_path_markers", seg_types, seg_params, n)) return rc;
     // the vertex count is a matter of types and flags alone: known before anything is launched
-    std::vector<int32_t> sub_off{0};
     int64_t n_vert = 0;
     for (int64_t s = 0, at = 0; s < n_subpaths; at += subpath_sizes[s], ++s) {
         if (subpath_sizes[s] == 0) continue;
-        sub_off.push_back((int32_t)(at + subpath_sizes[s]));
         const int64_t end = at + subpath_sizes[s] - (seg_types[at + subpath_sizes[s] - 1] == SVGR_PATH_UNCLOSED ? 1 : 0);
         if (end == at) continue;
         n_vert += 1;
@@ -8450,59 +8512,39 @@ static int path_markers_impl(svgr_ctx* ctx, const int32_t* seg_types, const doub
         return 0;
     }
     if (!ctx) return fail(SVGR_E_INVALID, "svgr_path_markers: no context");
-    // ---- one upload: coordinates, types, the subpath of every segment, the subpaths' first segments, the vertex flags
-    const int n_sub = (int)sub_off.size() - 1, ni = (int)n;
-    const size_t b_params = (size_t)n * 64, b_types = (((size_t)n * 4) + 63) & ~(size_t)63, b_sub = (((size_t)(n_sub + 1) * 4) + 63) & ~(size_t)63;
-    std::vector<char> blob(b_params + 2 * b_types + b_sub + (seg_vertex ? b_types : 0));
-    memcpy(blob.data(), seg_params, b_params);
-    memcpy(blob.data() + b_params, seg_types, (size_t)n * 4);
-    int32_t* h_seg_sub = (int32_t*)(blob.data() + b_params + b_types);
-    for (int s = 0; s < n_sub; ++s)
-        for (int i = sub_off[(size_t)s]; i < sub_off[(size_t)s + 1]; ++i) h_seg_sub[i] = s;
-    memcpy(blob.data() + b_params + 2 * b_types, sub_off.data(), (size_t)(n_sub + 1) * 4);
-    if (seg_vertex) memcpy(blob.data() + b_params + 2 * b_types + b_sub, seg_vertex, (size_t)n * 4);
-
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const int nb = (ni + DASH_S - 1) / DASH_S;
-    const size_t o_kind = (size_t)n_vert * 32, o_bad = o_kind + (((size_t)n_vert * 4 + 63) & ~(size_t)63), o_end = o_bad + 4;
-    std::vector<char> back(o_end);
-    PoolBlock in, flags, dirs, cnt, tops, tab, outb;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(flags.alloc((size_t)n * 4, ctx->device));
-    HIPCHK(dirs.alloc((size_t)n * sizeof(MarkerDirs), ctx->device));
-    HIPCHK(cnt.alloc((size_t)n * sizeof(MarkerCnt), ctx->device));
-    HIPCHK(tops.alloc((size_t)nb * sizeof(MarkerCnt), ctx->device));
-    HIPCHK(tab.alloc((size_t)n * 4, ctx->device));
-    HIPCHK(outb.alloc(o_end, ctx->device));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const double* d_params = in.as<double>();
-    const int* d_types = (const int*)(in.as<char>() + b_params);
-    const int* d_seg_sub = (const int*)(in.as<char>() + b_params + b_types);
-    const int* d_sub_off = (const int*)(in.as<char>() + b_params + 2 * b_types);
-    const int* d_vertex = seg_vertex ? (const int*)(in.as<char>() + b_params + 2 * b_types + b_sub) : nullptr;
-    double* d_xyuv = outb.as<double>();
-    int* d_kind = (int*)(outb.as<char>() + o_kind);
-    int* d_bad = (int*)(outb.as<char>() + o_bad);   // (the placing kernels' error flag travels with the result)
-    HIPCHK(hipMemsetAsync(d_bad, 0, 4, st));
+    // ---- one upload: the path, the vertex flags
+    PassFrame f(ctx);
+    hipStream_t st = f.st;
+    PathSections path;
+    Section<int32_t> vertex;
+    f.blob.build([&](HostBlob& b) {
+        path = path_put(b, seg_types, seg_params, subpath_sizes, n_subpaths, n);
+        if (seg_vertex) vertex = b.put(seg_vertex, (size_t)n);
+    });
+    const int ni = path.n, nb = (ni + DASH_S - 1) / DASH_S;
+    Layout lay;
+    const Section<double> o_xyuv = lay.take<double>((size_t)n_vert * 4);
+    const Section<int32_t> o_kind = lay.take<int32_t>((size_t)n_vert);
+    if (int rc = f.begin(lay)) return rc;
+    int *flags = f.scratch<int>((size_t)n), *tab = f.scratch<int>((size_t)n);
+    MarkerDirs* dirs = f.scratch<MarkerDirs>((size_t)n);
+    MarkerCnt *cnt = f.scratch<MarkerCnt>((size_t)n), *tops = f.scratch<MarkerCnt>((size_t)nb);
+    if (f.err) return f.err;
+    const double* d_params = path.params.on(f.in.p);
+    const int* d_types = path.types.on(f.in.p);
+    const int* d_seg_sub = path.seg_sub.on(f.in.p);
+    const int* d_sub_off = path.sub_off.on(f.in.p);
+    const int* d_vertex = seg_vertex ? vertex.on(f.in.p) : nullptr;
+    int* d_bad = f.bad.on(f.out.p);
     const dim3 grid = grid1((size_t)ni, MARKER_B);
-    SVGR_LAUNCH(k_marker_classify, grid, dim3(MARKER_B), 0, st, d_types, d_params, d_seg_sub, d_sub_off, d_vertex, ni, flags.as<int>(),
-                dirs.as<MarkerDirs>(), cnt.as<MarkerCnt>());
-    dash_scan<MarkerCnt, MarkerCntOp>(st, cnt.as<MarkerCnt>(), tops.as<MarkerCnt>(), ni);
-    SVGR_LAUNCH(k_marker_table, grid, dim3(MARKER_B), 0, st, (const int*)flags.p, (const MarkerCnt*)cnt.p, ni, tab.as<int>(), d_bad);
-    const MarkerView view{d_types, d_params, d_seg_sub, d_sub_off, (const int*)flags.p, (const MarkerDirs*)dirs.p, (const MarkerCnt*)cnt.p,
-                          (const int*)tab.p, ni};
-    SVGR_LAUNCH(k_marker_emit, grid, dim3(MARKER_B), 0, st, view, (long long)n_vert, d_xyuv, d_kind, d_bad);
-    HIPCHK(hipGetLastError());
-    // ---- one download
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "svgr_path_markers: the counting and the placing kernels disagree about a place");
-    res->xyuv.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_vert * 4);
-    res->kind.assign((const int32_t*)(back.data() + o_kind), (const int32_t*)(back.data() + o_kind) + n_vert);
+    SVGR_LAUNCH(k_marker_classify, grid, dim3(MARKER_B), 0, st, d_types, d_params, d_seg_sub, d_sub_off, d_vertex, ni, flags, dirs, cnt);
+    dash_scan<MarkerCnt, MarkerCntOp>(st, cnt, tops, ni);
+    SVGR_LAUNCH(k_marker_table, grid, dim3(MARKER_B), 0, st, flags, cnt, ni, tab, d_bad);
+    const MarkerView view{d_types, d_params, d_seg_sub, d_sub_off, flags, dirs, cnt, tab, ni};
+    SVGR_LAUNCH(k_marker_emit, grid, dim3(MARKER_B), 0, st, view, (long long)n_vert, o_xyuv.on(f.out.p), o_kind.on(f.out.p), d_bad);
+    if (int rc = f.finish("svgr_path_markers", "the counting and the placing kernels disagree about a place")) return rc;
+    res->xyuv.assign(o_xyuv.on(f.back.data()), o_xyuv.on(f.back.data()) + o_xyuv.n);
+    res->kind.assign(o_kind.on(f.back.data()), o_kind.on(f.back.data()) + o_kind.n);
     *out = res.release();
     return 0;
 }
@@ -8568,20 +8610,6 @@ TEXTPATH_KERNEL void k_textpath_emit(TextEmitView v, int n_out, double* __restri
     if (!textpath_emit(v, j, out + (size_t)j * 8)) *bad = 1;   // (the host zeroed it; every writer stores the same value)
 }
 
-// types and coordinates of n segments in the stroker's array form
-static int textpath_check_segments(const char* what, const int32_t* types, const double* params, int64_t n) {
-    for (int64_t i = 0; i < n; ++i) {
-        const int t = types[i];
-        if (t != SVGR_PATH_LINE && t != SVGR_PATH_CUBIC && t != SVGR_PATH_CLOSED && t != SVGR_PATH_UNCLOSED)
-            return fail(SVGR_E_INVALID, "%s: segment %lld has type %d (quadratics and arcs are converted by the caller)", what, (long long)i, t);
-        const int np = t == SVGR_PATH_CUBIC ? 8 : 4;
-        for (int e = 0; e < np; ++e)
-            if (!(std::fabs(params[8 * i + e]) <= DASH_COORD_MAX))
-                return fail(SVGR_E_INVALID, "%s: segment %lld has a coordinate that is not finite or beyond 1e150", what, (long long)i);
-    }
-    return 0;
-}
-
 struct TextPlaceIn {   // the glyph side of svgr_path_place_glyphs
     const int32_t* atlas_types;
     const double* atlas_params;
@@ -8591,8 +8619,6 @@ struct TextPlaceIn {   // the glyph side of svgr_path_place_glyphs
     const double *inst_half, *inst_dy;
 };
 
-static inline size_t pad64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
-
 // Both entries: the frames of `nq` arc lengths `s`; with `pl`, the queries are the instances' anchors and their outlines follow.
 static int textpath_impl(const char* what, svgr_ctx* ctx, const int32_t* seg_types, const double* seg_params, const int32_t* subpath_sizes,
                          int64_t n_subpaths, const double* s, int64_t nq, const TextPlaceIn* pl, double* xyuv_out, int32_t* flag_out,
@@ -8600,12 +8626,7 @@ static int textpath_impl(const char* what, svgr_ctx* ctx, const int32_t* seg_typ
     if (n_subpaths < 0 || nq < 0 || (n_subpaths > 0 && !subpath_sizes) || (nq > 0 && (!s || !flag_out || (!pl && !xyuv_out))))
         return fail(SVGR_E_INVALID, "%s: bad arguments", what);
     int64_t n = 0;
-    for (int64_t k = 0; k < n_subpaths; ++k) {
-        if (subpath_sizes[k] < 0) return fail(SVGR_E_INVALID, "%s: negative subpath size", what);
-        n += subpath_sizes[k];
-        if (n > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: more than 2^30 segments", what);
-    }
-    if (n > 0 && (!seg_types || !seg_params)) return fail(SVGR_E_INVALID, "%s: bad arguments", what);
+    if (int rc = path_count(what, seg_types, seg_params, subpath_sizes, n_subpaths, n)) return rc;
     if (nq > INT32_MAX / 2) return fail(SVGR_E_OVERFLOW, "%s: %lld queries do not fit a 32-bit count", what, (long long)nq);
     if (int rc = textpath_check_segments(what, seg_types, seg_params, n)) return rc;
     for (int64_t q = 0; q < nq; ++q)
@@ -8642,91 +8663,57 @@ static int textpath_impl(const char* what, svgr_ctx* ctx, const int32_t* seg_typ
     if (n_out > 0) memset(params_out, 0, (size_t)n_out * 64);
     if (n == 0) return 0;   // a path without segments: L = 0, nothing is inside, nothing is launched
     if (!ctx) return fail(SVGR_E_INVALID, "%s: no context", what);
-    // ---- one upload: the path (coordinates, types, subpath of every segment, the subpaths' first segments), the queries, and the
-    //      glyph side (atlas, offsets, instances)
-    std::vector<int32_t> sub_off{0};
-    for (int64_t k = 0; k < n_subpaths; ++k)
-        if (subpath_sizes[k] > 0) sub_off.push_back(sub_off.back() + subpath_sizes[k]);
-    const int n_sub = (int)sub_off.size() - 1, ni = (int)n, nqi = (int)nq, n_outi = (int)n_out, n_gl = pl ? (int)pl->n_glyphs : 0;
-    const size_t b_params = (size_t)n * 64, b_types = pad64((size_t)n * 4), b_sub = pad64((size_t)(n_sub + 1) * 4), b_s = pad64((size_t)nq * 8);
-    const size_t i_types = b_params, i_seg_sub = i_types + b_types, i_sub_off = i_seg_sub + b_types, i_s = i_sub_off + b_sub;
-    const size_t i_atlas = i_s + b_s, i_atypes = i_atlas + (size_t)n_atlas * 64, i_goff = i_atypes + pad64((size_t)n_atlas * 4);
-    const size_t i_iglyph = i_goff + (pl ? pad64((size_t)(n_gl + 1) * 4) : 0), i_ioff = i_iglyph + (pl ? pad64((size_t)nq * 4) : 0);
-    const size_t i_half = i_ioff + (pl ? pad64((size_t)(nq + 1) * 4) : 0), i_dy = i_half + (pl ? b_s : 0), i_end = i_dy + (pl ? b_s : 0);
-    std::vector<char> blob(i_end);
-    memcpy(blob.data(), seg_params, b_params);
-    memcpy(blob.data() + i_types, seg_types, (size_t)n * 4);
-    int32_t* h_seg_sub = (int32_t*)(blob.data() + i_seg_sub);
-    for (int k = 0; k < n_sub; ++k)
-        for (int i = sub_off[(size_t)k]; i < sub_off[(size_t)k + 1]; ++i) h_seg_sub[i] = k;
-    memcpy(blob.data() + i_sub_off, sub_off.data(), (size_t)(n_sub + 1) * 4);
-    if (nq > 0) memcpy(blob.data() + i_s, s, (size_t)nq * 8);
-    if (pl) {
-        if (n_atlas > 0) {
-            memcpy(blob.data() + i_atlas, pl->atlas_params, (size_t)n_atlas * 64);
-            memcpy(blob.data() + i_atypes, pl->atlas_types, (size_t)n_atlas * 4);
-        }
-        memcpy(blob.data() + i_goff, pl->glyph_seg_off, (size_t)(n_gl + 1) * 4);
-        memcpy(blob.data() + i_ioff, inst_off.data(), (size_t)(nq + 1) * 4);
-        if (nq > 0) {
-            memcpy(blob.data() + i_iglyph, pl->inst_glyph, (size_t)nq * 4);
-            memcpy(blob.data() + i_half, pl->inst_half, (size_t)nq * 8);
-            memcpy(blob.data() + i_dy, pl->inst_dy, (size_t)nq * 8);
-        }
-    }
-
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const int nb = (ni + DASH_S - 1) / DASH_S;
-    // the result block: placed outlines, frames, flags, the total length, the kernels' error flag
-    const size_t o_frames = (size_t)n_out * 64, o_flag = o_frames + (size_t)nq * 32, o_len = o_flag + pad64((size_t)nq * 4), o_bad = o_len + 8;
-    const size_t o_end = o_bad + 8;
-    std::vector<char> back(o_end);
-    PoolBlock in, tab, len, cum, inc, tops, outb;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(tab.alloc((size_t)n * DASH_SUB * 8, ctx->device));
-    HIPCHK(len.alloc((size_t)n * 8, ctx->device));
-    HIPCHK(cum.alloc((size_t)n * sizeof(DashFV), ctx->device));
-    HIPCHK(inc.alloc((size_t)n * 8, ctx->device));
-    HIPCHK(tops.alloc((size_t)nb * 8, ctx->device));
-    HIPCHK(outb.alloc(o_end, ctx->device));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const char* d_in = in.as<char>();
-    const double* d_params = (const double*)d_in;
-    const int* d_types = (const int*)(d_in + i_types);
-    double* d_frames = (double*)(outb.as<char>() + o_frames);
-    int* d_flag = (int*)(outb.as<char>() + o_flag);
-    int* d_bad = (int*)(outb.as<char>() + o_bad);
-    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
+    // ---- one upload: the path, the queries, and the glyph side (atlas, offsets, instances)
+    PassFrame f(ctx);
+    hipStream_t st = f.st;
+    PathSections path;
+    Section<double> q_s, atlas, half, dy;
+    Section<int32_t> atypes, goff, iglyph, ioff;
+    f.blob.build([&](HostBlob& b) {
+        path = path_put(b, seg_types, seg_params, subpath_sizes, n_subpaths, n);
+        q_s = b.put(s, (size_t)nq);
+        if (!pl) return;
+        atlas = b.put(pl->atlas_params, (size_t)n_atlas * 8), atypes = b.put(pl->atlas_types, (size_t)n_atlas);
+        goff = b.put(pl->glyph_seg_off, (size_t)pl->n_glyphs + 1), iglyph = b.put(pl->inst_glyph, (size_t)nq);
+        ioff = b.put(inst_off.data(), inst_off.size()), half = b.put(pl->inst_half, (size_t)nq), dy = b.put(pl->inst_dy, (size_t)nq);
+    });
+    const int ni = path.n, nqi = (int)nq, n_outi = (int)n_out, nb = (ni + DASH_S - 1) / DASH_S;
+    // the result block: placed outlines, frames, flags, the total length
+    Layout lay;
+    const Section<double> o_params = lay.take<double>((size_t)n_out * 8), o_frames = lay.take<double>((size_t)nq * 4);
+    const Section<int32_t> o_flag = lay.take<int32_t>((size_t)nq);
+    const Section<double> o_len = lay.take<double>(1);
+    if (int rc = f.begin(lay)) return rc;
+    double *tab = f.scratch<double>((size_t)n * DASH_SUB), *len = f.scratch<double>((size_t)n), *inc = f.scratch<double>((size_t)n);
+    double* tops = f.scratch<double>((size_t)nb);
+    DashFV* cum = f.scratch<DashFV>((size_t)n);
+    if (f.err) return f.err;
+    const void* d_in = f.in.p;
+    const double* d_params = path.params.on(d_in);
+    const int* d_types = path.types.on(d_in);
+    double* d_frames = o_frames.on(f.out.p);
+    int* d_flag = o_flag.on(f.out.p);
     const dim3 seg_grid((unsigned)((ni + DASH_SEGS_WG - 1) / DASH_SEGS_WG));
-    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, (const int*)(d_in + i_seg_sub), (const int*)(d_in + i_sub_off), ni,
-                tab.as<double>(), len.as<double>(), cum.as<DashFV>());
-    HIPCHK(hipMemcpyAsync(inc.p, len.p, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-    dash_scan<double, TextLenOp>(st, inc.as<double>(), tops.as<double>(), ni);
-    HIPCHK(hipMemcpyAsync(outb.as<char>() + o_len, inc.as<double>() + (ni - 1), 8, hipMemcpyDeviceToDevice, st));
+    SVGR_LAUNCH(k_dash_measure, seg_grid, dim3(256), 0, st, d_types, d_params, path.seg_sub.on(d_in), path.sub_off.on(d_in), ni, tab, len, cum);
+    HIPCHK(hipMemcpyAsync(inc, len, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+    dash_scan<double, TextLenOp>(st, inc, tops, ni);
+    HIPCHK(hipMemcpyAsync(o_len.on(f.out.p), inc + (ni - 1), 8, hipMemcpyDeviceToDevice, st));
     if (nqi > 0) {
-        const TextPathView view{d_types, d_params, (const double*)len.p, (const double*)tab.p, (const double*)inc.p, ni};
-        SVGR_LAUNCH(k_textpath_locate, grid1((size_t)nqi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, view, (const double*)(d_in + i_s), nqi, d_frames, d_flag);
+        const TextPathView view{d_types, d_params, len, tab, inc, ni};
+        SVGR_LAUNCH(k_textpath_locate, grid1((size_t)nqi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, view, q_s.on(d_in), nqi, d_frames, d_flag);
     }
     if (n_outi > 0) {
-        const TextEmitView ev{(const int*)(d_in + i_atypes), (const double*)(d_in + i_atlas), (const int*)(d_in + i_goff), (const int*)(d_in + i_iglyph),
-                              (const int*)(d_in + i_ioff), (const double*)(d_in + i_half), (const double*)(d_in + i_dy), (const double*)d_frames,
-                              (const int*)d_flag, nqi, (int)n_atlas};
-        SVGR_LAUNCH(k_textpath_emit, grid1((size_t)n_outi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, ev, n_outi, outb.as<double>(), d_bad);
+        const TextEmitView ev{atypes.on(d_in), atlas.on(d_in), goff.on(d_in), iglyph.on(d_in), ioff.on(d_in), half.on(d_in), dy.on(d_in),
+                              d_frames,        d_flag,         nqi,           (int)n_atlas};
+        SVGR_LAUNCH(k_textpath_emit, grid1((size_t)n_outi, TEXTPATH_B), dim3(TEXTPATH_B), 0, st, ev, n_outi, o_params.on(f.out.p), f.bad.on(f.out.p));
     }
-    HIPCHK(hipGetLastError());
-    // ---- one download
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "%s: a lane met a slot outside the result", what);
-    if (total_length_out) memcpy(total_length_out, back.data() + o_len, 8);
-    if (n_out > 0) memcpy(params_out, back.data(), (size_t)n_out * 64);
+    if (int rc = f.finish(what, "a lane met a slot outside the result")) return rc;
+    const char* back = f.back.data();
+    if (total_length_out) *total_length_out = *o_len.on(back);
+    if (n_out > 0) memcpy(params_out, o_params.on(back), (size_t)n_out * 64);
     if (nq > 0) {
-        if (xyuv_out) memcpy(xyuv_out, back.data() + o_frames, (size_t)nq * 32);
-        memcpy(flag_out, back.data() + o_flag, (size_t)nq * 4);
+        if (xyuv_out) memcpy(xyuv_out, o_frames.on(back), (size_t)nq * 32);
+        memcpy(flag_out, o_flag.on(back), (size_t)nq * 4);
     }
     return 0;
 }
@@ -8790,30 +8777,25 @@ struct GvarIn {
     int64_t n_entries;
 };
 
-// Where the tuple arrays lie in an upload that begins them at `at`.
-struct GvarBlob {
-    size_t i_toff, i_scalar, i_poff, i_index, i_dxy, i_end;
-    GvarBlob(size_t at, int ng, int nt, int ne) {
-        i_toff = at;
-        i_scalar = i_toff + pad64((size_t)(ng + 1) * 4);
-        i_poff = i_scalar + pad64((size_t)nt * 8);
-        i_index = i_poff + pad64((size_t)(nt + 1) * 4);
-        i_dxy = i_index + pad64((size_t)ne * 4);
-        i_end = i_dxy + pad64((size_t)ne * 4);
-    }
-    void fill(char* blob, const GvarIn& g, int ng, int nt, int ne) const {
-        memcpy(blob + i_toff, g.glyph_tuple_off, (size_t)(ng + 1) * 4);
-        if (nt) memcpy(blob + i_scalar, g.tuple_scalar, (size_t)nt * 8);
-        memcpy(blob + i_poff, g.tuple_pt_off, (size_t)(nt + 1) * 4);
-        if (ne) memcpy(blob + i_index, g.tp_index, (size_t)ne * 4);
-        if (ne) memcpy(blob + i_dxy, g.tp_dxy, (size_t)ne * 4);
-    }
-    GvarView view(const char* d_in, const int16_t* pt_xy, const int* contour_off, const int* glyph_contour_off, int nc, int ng, int npt,
-                  int nt) const {
-        return GvarView{pt_xy, contour_off, glyph_contour_off, (const int*)(d_in + i_toff), (const double*)(d_in + i_scalar),
-                        (const int*)(d_in + i_poff), (const int*)(d_in + i_index), (const int16_t*)(d_in + i_dxy), nc, ng, npt, nt};
+// Where the tuple arrays lie in an upload, and the delta pass's view of it.
+struct GvarSections {
+    Section<int32_t> toff, poff, index;
+    Section<double> scalar;
+    Section<int16_t> dxy;
+    GvarView view(const void* d_in, const int16_t* pt_xy, const int* contour_off, const int* glyph_contour_off, int nc, int ng, int npt) const {
+        return GvarView{pt_xy, contour_off, glyph_contour_off, toff.on(d_in), scalar.on(d_in), poff.on(d_in), index.on(d_in), dxy.on(d_in),
+                        nc,    ng,          npt,               (int)scalar.n};
     }
 };
+static GvarSections gvar_put(HostBlob& blob, const GvarIn& g, int64_t n_glyphs) {
+    GvarSections v;
+    v.toff = blob.put(g.glyph_tuple_off, (size_t)n_glyphs + 1);
+    v.scalar = blob.put(g.tuple_scalar, (size_t)g.n_tuples);
+    v.poff = blob.put(g.tuple_pt_off, (size_t)g.n_tuples + 1);
+    v.index = blob.put(g.tp_index, (size_t)g.n_entries);
+    v.dxy = blob.put(g.tp_dxy, (size_t)g.n_entries * 2);
+    return v;
+}
 
 constexpr int GVAR_B = 256;   // atlas points (= lanes) per workgroup
 
@@ -8854,64 +8836,38 @@ static int glyf_outline_impl(const char* name, svgr_ctx* ctx, const int16_t* pt_
     if (!ctx) return fail(SVGR_E_INVALID, "%s: no context", name);
     // ---- one upload: the atlas with its slot table, the parts with their prefix sums, the tuples
     const int np = (int)n_parts, npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs;
-    const int nt = gv ? (int)gv->n_tuples : 0, ne = gv ? (int)gv->n_entries : 0;
-    const size_t i_on = pad64((size_t)npt * 4), i_slot = i_on + pad64((size_t)npt), i_coff = i_slot + pad64((size_t)npt * 4);
-    const size_t i_goff = i_coff + pad64((size_t)(nc + 1) * 4), i_pglyph = i_goff + pad64((size_t)(ng + 1) * 4);
-    const size_t i_plane = i_pglyph + pad64((size_t)np * 4), i_pseg = i_plane + pad64((size_t)(np + 1) * 4);
-    const size_t i_m = i_pseg + pad64((size_t)(np + 1) * 4), i_pen = i_m + pad64((size_t)np * 48), i_sx = i_pen + pad64((size_t)np * 8);
-    const size_t i_sy = i_sx + pad64((size_t)np * 8), i_gvar = i_sy + pad64((size_t)np * 8);
-    const GvarBlob gb(i_gvar, ng, nt, ne);
-    const size_t i_end = gv ? gb.i_end : i_gvar;
-    std::vector<char> blob(i_end);
-    memcpy(blob.data(), pt_xy, (size_t)npt * 4);
-    memcpy(blob.data() + i_on, pt_on, (size_t)npt);
-    memcpy(blob.data() + i_slot, t.pt_slot.data(), (size_t)npt * 4);
-    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
-    memcpy(blob.data() + i_goff, glyph_contour_off, (size_t)(ng + 1) * 4);
-    memcpy(blob.data() + i_pglyph, part_glyph, (size_t)np * 4);
-    memcpy(blob.data() + i_plane, t.part_lane_off.data(), (size_t)(np + 1) * 4);
-    memcpy(blob.data() + i_pseg, t.part_seg_off.data(), (size_t)(np + 1) * 4);
-    memcpy(blob.data() + i_m, part_m, (size_t)np * 48);
-    memcpy(blob.data() + i_pen, part_pen, (size_t)np * 8);
-    memcpy(blob.data() + i_sx, part_sx, (size_t)np * 8);
-    memcpy(blob.data() + i_sy, part_sy, (size_t)np * 8);
-    if (gv) gb.fill(blob.data(), *gv, ng, nt, ne);
-
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    // the result block: params, types, the kernels' error flag; behind what is downloaded, the deltas (they stay on the device)
-    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 64;
-    const size_t o_all = o_end + (gv ? pad64((size_t)npt * 16) : 0);
-    std::vector<char> back(o_end);
-    PoolBlock in, outb;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(outb.alloc(o_all, ctx->device));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const char* d_in = in.as<char>();
-    int* d_bad = (int*)(outb.as<char>() + o_bad);
-    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
-    double* d_dxy = gv ? (double*)(outb.as<char>() + o_end) : nullptr;
+    PassFrame f(ctx);
+    Section<int16_t> xy;
+    Section<uint8_t> on;
+    Section<int32_t> slot, coff, goff, pglyph, plane, pseg;
+    Section<double> m, pen, sx, sy;
+    GvarSections gs;
+    f.blob.build([&](HostBlob& b) {
+        xy = b.put(pt_xy, (size_t)npt * 2), on = b.put(pt_on, (size_t)npt), slot = b.put(t.pt_slot.data(), (size_t)npt);
+        coff = b.put(contour_off, (size_t)nc + 1), goff = b.put(glyph_contour_off, (size_t)ng + 1), pglyph = b.put(part_glyph, (size_t)np);
+        plane = b.put(t.part_lane_off.data(), (size_t)np + 1), pseg = b.put(t.part_seg_off.data(), (size_t)np + 1);
+        m = b.put(part_m, (size_t)np * 6), pen = b.put(part_pen, (size_t)np), sx = b.put(part_sx, (size_t)np), sy = b.put(part_sy, (size_t)np);
+        if (gv) gs = gvar_put(b, *gv, n_glyphs);
+    });
+    // the result block: params, types; behind what is downloaded, the deltas (they stay on the device)
+    Layout lay;
+    const Section<double> o_params = lay.take<double>((size_t)n_out * 8);
+    const Section<int32_t> o_types = lay.take<int32_t>((size_t)n_out);
+    if (int rc = f.begin(lay, gv ? pad64((size_t)npt * 16) : 0)) return rc;
+    const void* d_in = f.in.p;
+    int* d_bad = f.bad.on(f.out.p);
+    double* d_dxy = gv ? f.behind<double>() : nullptr;
     if (gv) {
-        const GvarView gview = gb.view(d_in, (const int16_t*)d_in, (const int*)(d_in + i_coff), (const int*)(d_in + i_goff), nc, ng, npt, nt);
-        SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, st, gview, d_dxy, d_bad);
+        SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, f.st, gs.view(d_in, xy.on(d_in), coff.on(d_in), goff.on(d_in), nc, ng, npt),
+                    d_dxy, d_bad);
         HIPCHK(hipGetLastError());
     }
-    const GlyfView view{(const int16_t*)d_in, (const uint8_t*)(d_in + i_on), (const int*)(d_in + i_slot), (const int*)(d_in + i_coff),
-                        (const int*)(d_in + i_goff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_plane), (const int*)(d_in + i_pseg),
-                        (const double*)(d_in + i_m), (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy),
-                        nc, np, npt, n_out, d_dxy};
-    SVGR_LAUNCH(k_glyf_emit, grid1((size_t)n_lanes, GLYF_B), dim3(GLYF_B), 0, st, view, n_lanes, (int*)(outb.as<char>() + o_types),
-                outb.as<double>(), d_bad);
-    HIPCHK(hipGetLastError());
-    // ---- one download
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "%s: a lane met a slot outside the result", name);
-    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
-    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    const GlyfView view{xy.on(d_in),  on.on(d_in), slot.on(d_in), coff.on(d_in), goff.on(d_in), pglyph.on(d_in), plane.on(d_in), pseg.on(d_in),
+                        m.on(d_in),   pen.on(d_in), sx.on(d_in),  sy.on(d_in),   nc,            np,              npt,            n_out,
+                        d_dxy};
+    SVGR_LAUNCH(k_glyf_emit, grid1((size_t)n_lanes, GLYF_B), dim3(GLYF_B), 0, f.st, view, n_lanes, o_types.on(f.out.p), o_params.on(f.out.p), d_bad);
+    if (int rc = f.finish(name, "a lane met a slot outside the result")) return rc;
+    stroke_out_take(*res, f.back.data(), o_params, o_types);
     res->sizes = std::move(t.sizes);
     *out = res.release();
     return 0;
@@ -8931,36 +8887,23 @@ static int gvar_deltas_impl(svgr_ctx* ctx, const int16_t* pt_xy, int64_t n_point
         return 0;
     }
     if (!ctx) return fail(SVGR_E_INVALID, "svgr_gvar_deltas: no context");
-    const int npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs, nt = (int)gv.n_tuples, ne = (int)gv.n_entries;
-    const size_t i_coff = pad64((size_t)npt * 4), i_goff = i_coff + pad64((size_t)(nc + 1) * 4), i_gvar = i_goff + pad64((size_t)(ng + 1) * 4);
-    const GvarBlob gb(i_gvar, ng, nt, ne);
-    std::vector<char> blob(gb.i_end);
-    memcpy(blob.data(), pt_xy, (size_t)npt * 4);
-    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
-    memcpy(blob.data() + i_goff, glyph_contour_off, (size_t)(ng + 1) * 4);
-    gb.fill(blob.data(), gv, ng, nt, ne);
-
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const size_t o_bad = pad64((size_t)npt * 16), o_end = o_bad + 64;
-    std::vector<char> back(o_end);
-    PoolBlock in, outb;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(outb.alloc(o_end, ctx->device));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const char* d_in = in.as<char>();
-    int* d_bad = (int*)(outb.as<char>() + o_bad);
-    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
-    const GvarView gview = gb.view(d_in, (const int16_t*)d_in, (const int*)(d_in + i_coff), (const int*)(d_in + i_goff), nc, ng, npt, nt);
-    SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, st, gview, outb.as<double>(), d_bad);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "svgr_gvar_deltas: a lane met a point outside its tables");
-    memcpy(pt_dxy_out, back.data(), (size_t)npt * 16);
+    const int npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs;
+    PassFrame f(ctx);
+    Section<int16_t> xy;
+    Section<int32_t> coff, goff;
+    GvarSections gs;
+    f.blob.build([&](HostBlob& b) {
+        xy = b.put(pt_xy, (size_t)npt * 2), coff = b.put(contour_off, (size_t)nc + 1), goff = b.put(glyph_contour_off, (size_t)ng + 1);
+        gs = gvar_put(b, gv, n_glyphs);
+    });
+    Layout lay;
+    const Section<double> o_dxy = lay.take<double>((size_t)npt * 2);
+    if (int rc = f.begin(lay)) return rc;
+    const void* d_in = f.in.p;
+    SVGR_LAUNCH(k_gvar_delta, grid1((size_t)npt, GVAR_B), dim3(GVAR_B), 0, f.st, gs.view(d_in, xy.on(d_in), coff.on(d_in), goff.on(d_in), nc, ng, npt),
+                o_dxy.on(f.out.p), f.bad.on(f.out.p));
+    if (int rc = f.finish("svgr_gvar_deltas", "a lane met a point outside its tables")) return rc;
+    memcpy(pt_dxy_out, o_dxy.on(f.back.data()), (size_t)npt * 16);
     return 0;
 }
 
@@ -9036,51 +8979,27 @@ static int cff_outline_impl(svgr_ctx* ctx, const double* pt_xy, const uint8_t* p
     if (!ctx) return fail(SVGR_E_INVALID, "svgr_cff_outline: no context");
     // ---- one upload: the atlas with its segment tables, the parts with their prefix sums
     const int np = (int)n_parts, npt = (int)n_points, nc = (int)n_contours, ng = (int)n_glyphs, ns = (int)t.seg_ref.size();
-    const size_t i_kind = pad64((size_t)npt * 16), i_ref = i_kind + pad64((size_t)npt), i_gseg = i_ref + pad64((size_t)ns * 4);
-    const size_t i_coff = i_gseg + pad64((size_t)(ng + 1) * 4), i_pglyph = i_coff + pad64((size_t)(nc + 1) * 4);
-    const size_t i_pseg = i_pglyph + pad64((size_t)np * 4), i_m = i_pseg + pad64((size_t)(np + 1) * 4);
-    const size_t i_pen = i_m + pad64((size_t)np * 48), i_sx = i_pen + pad64((size_t)np * 8), i_sy = i_sx + pad64((size_t)np * 8);
-    const size_t i_end = i_sy + pad64((size_t)np * 8);
-    std::vector<char> blob(i_end);
-    memcpy(blob.data(), pt_xy, (size_t)npt * 16);
-    memcpy(blob.data() + i_kind, pt_kind, (size_t)npt);
-    memcpy(blob.data() + i_ref, t.seg_ref.data(), (size_t)ns * 4);
-    memcpy(blob.data() + i_gseg, t.glyph_seg_off.data(), (size_t)(ng + 1) * 4);
-    memcpy(blob.data() + i_coff, contour_off, (size_t)(nc + 1) * 4);
-    memcpy(blob.data() + i_pglyph, part_glyph, (size_t)np * 4);
-    memcpy(blob.data() + i_pseg, t.part_seg_off.data(), (size_t)(np + 1) * 4);
-    memcpy(blob.data() + i_m, part_m, (size_t)np * 48);
-    memcpy(blob.data() + i_pen, part_pen, (size_t)np * 8);
-    memcpy(blob.data() + i_sx, part_sx, (size_t)np * 8);
-    memcpy(blob.data() + i_sy, part_sy, (size_t)np * 8);
-
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    // the result block: params, types, the kernel's error flag
-    const size_t o_types = (size_t)n_out * 64, o_bad = o_types + pad64((size_t)n_out * 4), o_end = o_bad + 64;
-    std::vector<char> back(o_end);
-    PoolBlock in, outb;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(in.alloc(blob.size(), ctx->device));
-    HIPCHK(outb.alloc(o_end, ctx->device));
-    HIPCHK(hipMemcpyAsync(in.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    const char* d_in = in.as<char>();
-    int* d_bad = (int*)(outb.as<char>() + o_bad);
-    HIPCHK(hipMemsetAsync(d_bad, 0, 8, st));
-    const CffView view{(const double*)d_in, (const uint8_t*)(d_in + i_kind), (const int*)(d_in + i_ref), (const int*)(d_in + i_gseg),
-                       (const int*)(d_in + i_coff), (const int*)(d_in + i_pglyph), (const int*)(d_in + i_pseg), (const double*)(d_in + i_m),
-                       (const double*)(d_in + i_pen), (const double*)(d_in + i_sx), (const double*)(d_in + i_sy), nc, np, npt, ns, n_out};
-    SVGR_LAUNCH(k_cff_emit, grid1((size_t)n_out, CFF_B), dim3(CFF_B), 0, st, view, (int*)(outb.as<char>() + o_types), outb.as<double>(),
-                d_bad);
-    HIPCHK(hipGetLastError());
-    // ---- one download
-    HIPCHK(hipMemcpyAsync(back.data(), outb.p, o_end, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int bad = 0;
-    memcpy(&bad, back.data() + o_bad, 4);
-    if (bad) return fail(SVGR_E_STATE, "svgr_cff_outline: a lane met an index outside its tables");
-    res->params.assign((const double*)back.data(), (const double*)back.data() + (size_t)n_out * 8);
-    res->types.assign((const int32_t*)(back.data() + o_types), (const int32_t*)(back.data() + o_types) + n_out);
+    PassFrame f(ctx);
+    Section<double> xy, m, pen, sx, sy;
+    Section<uint8_t> kind;
+    Section<int32_t> ref, gseg, coff, pglyph, pseg;
+    f.blob.build([&](HostBlob& b) {
+        xy = b.put(pt_xy, (size_t)npt * 2), kind = b.put(pt_kind, (size_t)npt), ref = b.put(t.seg_ref.data(), (size_t)ns);
+        gseg = b.put(t.glyph_seg_off.data(), (size_t)ng + 1), coff = b.put(contour_off, (size_t)nc + 1), pglyph = b.put(part_glyph, (size_t)np);
+        pseg = b.put(t.part_seg_off.data(), (size_t)np + 1), m = b.put(part_m, (size_t)np * 6), pen = b.put(part_pen, (size_t)np);
+        sx = b.put(part_sx, (size_t)np), sy = b.put(part_sy, (size_t)np);
+    });
+    // the result block: params, types
+    Layout lay;
+    const Section<double> o_params = lay.take<double>((size_t)n_out * 8);
+    const Section<int32_t> o_types = lay.take<int32_t>((size_t)n_out);
+    if (int rc = f.begin(lay)) return rc;
+    const void* d_in = f.in.p;
+    const CffView view{xy.on(d_in), kind.on(d_in), ref.on(d_in), gseg.on(d_in), coff.on(d_in), pglyph.on(d_in), pseg.on(d_in), m.on(d_in),
+                       pen.on(d_in), sx.on(d_in),  sy.on(d_in),  nc,            np,            npt,             ns,            n_out};
+    SVGR_LAUNCH(k_cff_emit, grid1((size_t)n_out, CFF_B), dim3(CFF_B), 0, f.st, view, o_types.on(f.out.p), o_params.on(f.out.p), f.bad.on(f.out.p));
+    if (int rc = f.finish("svgr_cff_outline", "a lane met an index outside its tables")) return rc;
+    stroke_out_take(*res, f.back.data(), o_params, o_types);
     res->sizes = std::move(t.sizes);
     *out = res.release();
     return 0;
@@ -9337,51 +9256,53 @@ static int deflate_impl(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int
     static_assert(SVGR_DEFLATE_FIXED == DEFLATE_FIXED && SVGR_DEFLATE_DYNAMIC == DEFLATE_DYNAMIC, "Huffman modes");
     const int nc = n_bytes ? (int)((n_bytes + DEFLATE_CH - 1) / DEFLATE_CH) : 1;
     const int nb = (nc + DASH_S - 1) / DASH_S;
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
     // one block of small arrays: histogram, codes, per chunk the token count, the Adler pair, the byte count twice, the scan's tops
-    const size_t i_codes = pad64(DEFLATE_NSYM * 8), i_ntok = i_codes + pad64(sizeof(DeflateCodes)), i_adler = i_ntok + pad64((size_t)nc * 4);
-    const size_t i_cnt = i_adler + pad64((size_t)nc * 8), i_incl = i_cnt + pad64((size_t)nc * 8), i_tops = i_incl + pad64((size_t)nc * 8);
-    const size_t i_end = i_tops + pad64((size_t)nb * 8);
+    Layout lay;
+    const Section<unsigned long long> s_hist = lay.take<unsigned long long>(DEFLATE_NSYM);
+    const Section<DeflateCodes> s_codes = lay.take<DeflateCodes>(1);
+    const Section<int> s_ntok = lay.take<int>((size_t)nc);
+    const Section<uint32_t> s_adler = lay.take<uint32_t>((size_t)nc * 2);
+    const Section<long long> s_cnt = lay.take<long long>((size_t)nc), s_incl = lay.take<long long>((size_t)nc), s_tops = lay.take<long long>((size_t)nb);
     unsigned long long counts[DEFLATE_NSYM] = {0};
     DeflateCodes codes;
     std::vector<uint32_t> adler((size_t)nc * 2);
     long long total = 0;
-    PoolBlock small, toks, slots, packed;
-    StreamDrain drain{st};   // (declared last: it waits before any of the above is released, on every way out)
-    HIPCHK(small.alloc(i_end, ctx->device));
-    HIPCHK(toks.alloc((size_t)nc * DEFLATE_CH * 4, ctx->device));
-    HIPCHK(slots.alloc((size_t)nc * DEFLATE_SLOT, ctx->device));
-    char* d = small.as<char>();
-    HIPCHK(hipMemsetAsync(d, 0, DEFLATE_NSYM * 8, st));
-    const DeflTokArgs ta{(const uint8_t*)src->ptr, (long long)n_bytes, toks.as<uint32_t>(), (int*)(d + i_ntok), (uint32_t*)(d + i_adler),
-                         (unsigned long long*)d};
+    PassFrame f(ctx);   // (no upload and no result block: its scratch blocks and its drain)
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = f.st;
+    char* d = f.scratch<char>(lay.bytes());
+    uint32_t* toks = f.scratch<uint32_t>((size_t)nc * DEFLATE_CH);
+    uint8_t* slots = f.scratch<uint8_t>((size_t)nc * DEFLATE_SLOT);
+    if (f.err) return f.err;
+    unsigned long long* d_hist = s_hist.on(d);
+    long long *d_cnt = s_cnt.on(d), *d_incl = s_incl.on(d);
+    HIPCHK(hipMemsetAsync(d_hist, 0, DEFLATE_NSYM * 8, st));
+    const DeflTokArgs ta{(const uint8_t*)src->ptr, (long long)n_bytes, toks, s_ntok.on(d), s_adler.on(d), d_hist};
     SVGR_LAUNCH(k_deflate_tokens, dim3((unsigned)nc), dim3(DEFL_B), 0, st, ta);
     HIPCHK(hipGetLastError());
     if (huffman == DEFLATE_DYNAMIC) {   // the one round trip: 316 counts down, the tables and the header up
-        HIPCHK(hipMemcpyAsync(counts, d, sizeof counts, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(counts, d_hist, sizeof counts, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counts");
     deflate_build_codes((const uint64_t*)counts, huffman, codes);
-    HIPCHK(hipMemcpyAsync(d + i_codes, &codes, sizeof codes, hipMemcpyHostToDevice, st));
-    const DeflEmitArgs ea{toks.as<uint32_t>(), (const int*)(d + i_ntok), (const DeflateCodes*)(d + i_codes), slots.as<uint8_t>(),
-                          (long long*)(d + i_cnt), (long long*)(d + i_incl), nc};
+    HIPCHK(hipMemcpyAsync(s_codes.on(d), &codes, sizeof codes, hipMemcpyHostToDevice, st));
+    const DeflEmitArgs ea{toks, s_ntok.on(d), s_codes.on(d), slots, d_cnt, d_incl, nc};
     SVGR_LAUNCH(k_deflate_emit, dim3((unsigned)nc), dim3(DEFL_B), 0, st, ea);
-    dash_scan<long long, DeflSumOp>(st, (long long*)(d + i_incl), (long long*)(d + i_tops), nc);
+    dash_scan<long long, DeflSumOp>(st, d_incl, s_tops.on(d), nc);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&total, d + i_incl + (size_t)(nc - 1) * 8, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(adler.data(), d + i_adler, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, d_incl + (nc - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(adler.data(), s_adler.on(d), (size_t)nc * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (total <= 0 || total > (long long)nc * DEFLATE_SLOT) return fail(SVGR_E_STATE, "svgr_deflate: the chunks' byte counts do not add up");
     *n_out = 2 + total + 4;
     if (*n_out > out_cap) return SVGR_DEFLATE_NO_ROOM;
     // ---- only the compressed bytes cross: the chunks' bytes to one run, then one download
-    HIPCHK(packed.alloc((size_t)total, ctx->device));
-    SVGR_LAUNCH(k_deflate_gather, dim3((unsigned)nc), dim3(PNG_B), 0, st, slots.as<uint8_t>(), (const long long*)(d + i_cnt),
-                (const long long*)(d + i_incl), packed.as<uint8_t>());
+    uint8_t* packed = f.scratch<uint8_t>((size_t)total);
+    if (f.err) return f.err;
+    SVGR_LAUNCH(k_deflate_gather, dim3((unsigned)nc), dim3(PNG_B), 0, st, slots, d_cnt, d_incl, packed);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out + 2, packed.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out + 2, packed, (size_t)total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     out[0] = 0x78;   // CMF: deflate, 32 KiB window; FLG: fastest, FCHECK
     out[1] = 0x01;
@@ -9767,7 +9688,7 @@ int svgr_batch_pick(svgr_batch* b, const double* points, const int64_t* grid, in
     static const char* entry = "svgr_batch_pick";
     return abi_guard(entry, [&]() -> int {
         if (!b || n_points < 0 || n_clip_groups < 0 || n_clip_groups > 0x7fffffffll) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
-        PoolBlock d_pts, d_top, d_bits, d_tab;
+        PoolBlock d_pts, d_top, d_bits;
         HitQuery q;
         long long n_groups = 0;
         if (int rc = hit_query(entry, points, grid, n_points, q, n_groups)) return rc;
@@ -9791,32 +9712,32 @@ int svgr_batch_pick(svgr_batch* b, const double* points, const int64_t* grid, in
         hipStream_t st = b->ctx->stream;
         if (int rc = hit_prepare(b)) return rc;
         if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
-        // the tables in one block: the four int arrays, then the pickable bytes
-        const size_t n_co = (size_t)np + 1, n_cg = (size_t)clip_off[np], n_go = (size_t)n_clip_groups + 1, n_gs = n_clip_groups > 0 ? (size_t)group_off[n_clip_groups] : 0;
+        // the tables in one upload: the four int arrays, then the pickable bytes.  (`staged` is declared in front of the frame:
+        // the frame's drain waits for the copies into it on every way out)
+        std::vector<uint32_t> staged;   // a grid's rows come back in tile order: put in row-major order behind the wait
+        PassFrame f(b->ctx);
         const int32_t zero = 0;
-        HIPCHK(d_tab.alloc(sizeof(int32_t) * (n_co + n_cg + n_go + n_gs) + (size_t)np));
-        int32_t* t_co = d_tab.as<int32_t>(), *t_cg = t_co + n_co, *t_go = t_cg + n_cg, *t_gs = t_go + n_go;
-        uint8_t* t_pick = (uint8_t*)(t_gs + n_gs);
-        HIPCHK(hipMemcpyAsync(t_co, clip_off, sizeof(int32_t) * n_co, hipMemcpyHostToDevice, st));
-        if (n_cg) HIPCHK(hipMemcpyAsync(t_cg, clip_group, sizeof(int32_t) * n_cg, hipMemcpyHostToDevice, st));
-        if (n_clip_groups > 0) HIPCHK(hipMemcpyAsync(t_go, group_off, sizeof(int32_t) * n_go, hipMemcpyHostToDevice, st));
-        else HIPCHK(hipMemcpyAsync(t_go, &zero, sizeof zero, hipMemcpyHostToDevice, st));
-        if (n_gs) HIPCHK(hipMemcpyAsync(t_gs, group_src, sizeof(int32_t) * n_gs, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(t_pick, pickable, (size_t)np, hipMemcpyHostToDevice, st));
+        const Section<int32_t> s_co = f.blob.put(clip_off, (size_t)np + 1), s_cg = f.blob.put(clip_group, (size_t)clip_off[np]);
+        const Section<int32_t> s_go = n_clip_groups > 0 ? f.blob.put(group_off, (size_t)n_clip_groups + 1) : f.blob.put(&zero, 1);
+        const Section<int32_t> s_gs = f.blob.put(group_src, n_clip_groups > 0 ? (size_t)group_off[n_clip_groups] : 0);
+        const Section<uint8_t> s_pick = f.blob.put(pickable, (size_t)np);
+        if (int rc = f.upload()) return rc;
+        const void* d_tab = f.in.p;
+        const int32_t *t_co = s_co.on(d_tab), *t_cg = s_cg.on(d_tab), *t_go = s_go.on(d_tab), *t_gs = s_gs.on(d_tab);
+        const uint8_t* t_pick = s_pick.on(d_tab);
         // the point-by-path bit matrix: as many workgroups' rows at a time as the scratch holds
         const size_t group_bytes = sizeof(uint32_t) * (size_t)words * HIT_BLOCK;
         const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
         const long long per_pass = std::min<long long>(n_groups, std::max<long long>((long long)(budget / group_bytes), 1));
         HIPCHK(d_bits.alloc(group_bytes * (size_t)per_pass));
         HIPCHK(d_top.alloc(sizeof(int32_t) * (size_t)n_points));
-        std::vector<uint32_t> staged;   // a grid's rows come back in tile order: put in row-major order behind the wait
         if (bits_out && grid) staged.resize((size_t)n_groups * HIT_BLOCK * (size_t)words);
         for (long long g0 = 0; g0 < n_groups; g0 += per_pass) {
             const long long ng = std::min<long long>(per_pass, n_groups - g0);
             SVGR_LAUNCH(k_hit_winding<true>, dim3((unsigned)ng), dim3(HIT_BLOCK), 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p,
                         (const double*)b->hit_ext.p, (const uint8_t*)b->path_rule.p, (int)np, q, g0, (int*)nullptr, d_bits.as<uint32_t>(), words);
-            SVGR_LAUNCH(k_hit_resolve, dim3((unsigned)ng), dim3(HIT_BLOCK), 0, st, d_bits.as<uint32_t>(), words, (int)np, q, g0, (const uint8_t*)t_pick,
-                        (const int32_t*)t_co, (const int32_t*)t_cg, (const int32_t*)t_go, (const int32_t*)t_gs, d_top.as<int32_t>());
+            SVGR_LAUNCH(k_hit_resolve, dim3((unsigned)ng), dim3(HIT_BLOCK), 0, st, d_bits.as<uint32_t>(), words, (int)np, q, g0, t_pick, t_co,
+                        t_cg, t_go, t_gs, d_top.as<int32_t>());
             HIPCHK(hipGetLastError());
             if (bits_out && grid) {
                 HIPCHK(hipMemcpyAsync(staged.data() + (size_t)g0 * HIT_BLOCK * (size_t)words, d_bits.p, group_bytes * (size_t)ng, hipMemcpyDeviceToHost, st));
