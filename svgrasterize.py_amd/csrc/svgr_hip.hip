@@ -1821,7 +1821,11 @@ __device__ __forceinline__ void pb_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // stored as they are computed, the walk writes the cells (and `cell_plan`: the planned renders that follow take these places).  The
 // lists keep the slack between them (memory, not traffic: only what is written is read).  A bound that did not hold is caught like
 // a plan that does not fit: the pieces are not stored, error bit 32, the staged plan (MODE 0, exact) takes over.
-template <int MODE>
+// LEAN (with MODE 1): the placed pass of a replay that keeps its slab table behind the lean flatten (run_geometry), on one GPU, not
+// deterministic, without groups or gradients.  What such a pass is given for its options -- one rank, `det` and `stats` 0, no keys
+// to guard, no group or gradient table, no stamps -- is known when the kernel is compiled: no owns_band test, no guard block, no
+// option lives in a register through the row loop.  Everything that keeps a wrong plan harmless is the full form's.
+template <int MODE, bool LEAN = false>
 __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab* __restrict__ slabs, const double* __restrict__ edges,
                                                            const int* __restrict__ pair_idx, const double* __restrict__ path_paint,
                                                            const uint8_t* __restrict__ path_rule, const int* __restrict__ path_group,
@@ -1839,6 +1843,11 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
 #endif
     constexpr bool PLANNED = MODE != 0;     // the cells' places are known BEFORE the rows' pieces are computed: one pass, the walk writes the cells
     constexpr bool BOUNDED = MODE == 2;     // ... known from bounds this workgroup makes itself, not from a plan
+    static_assert(!LEAN || MODE == 1, "the lean form is a placed pass");
+    if constexpr (LEAN) {   // (the values run_geometry would pass: constants from here on)
+        own.world = 1; det = 0; stats = 0;
+        path_group = nullptr; path_grad = nullptr; dbg = nullptr; guard_keys = nullptr;
+    }
     PB_STAMP(0);
     __shared__ __attribute__((aligned(16))) double s_sum[PB_CELLS * TR];
     __shared__ double s_left[TR];
@@ -1852,15 +1861,19 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
     __shared__ __attribute__((aligned(8))) int2 s_info[PB_CELLS];   // per cell: adds in front of it in its band, class
     __shared__ unsigned s_rowm[PB_CELLS];                           // ... rows with a carry-in add | rows with a sentinel << 16
     __shared__ int s_ptot[PB_BANDS], s_pidx[PB_BANDS], s_base, s_ok;
+    __shared__ int s_rl;                                            // (LEAN) the path's rule byte, parked like the pairs' places
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // (the LDS tables are cleared whole, not just the slab's part of them: that needs nothing of the slab, so it runs while the
     //  slab record is on its way)
     for (int i = tid; i < PB_CELLS * TR / 2; i += PB_THREADS) ((double2*)s_sum)[i] = make_double2(0.0, 0.0);
     for (int i = tid; i < PB_CELLS; i += PB_THREADS) {
-        s_cnt[i] = 0; s_pos[i] = (int)0x80000000; s_plan_n[i] = 0; s_rowb[i] = 0u; s_info[i] = make_int2(0, 0);
+        s_cnt[i] = 0; s_pos[i] = (int)0x80000000; s_plan_n[i] = 0; s_rowb[i] = 0u;
+        if (!LEAN) s_info[i] = make_int2(0, 0);   // (a planned pass never reads it)
     }
     if (tid < TR) s_left[tid] = 0.0;
     if (tid == 0) s_rowb[PB_CELLS] = 0u;
+    if (LEAN && tid < PB_BANDS) s_pidx[tid] = 0;
+    if (LEAN && tid == 0) s_rl = 0;
     // (both scalar loads asked for together: the slab first, the test of the cursor behind it -- the grid never exceeds the list)
     const Slab sl = slabs[blockIdx.x];
     // `guard_keys` given (MODE 1 only): a replay that KEEPS the slab table, bboxes and bins the previous render of the same plan left
@@ -1868,8 +1881,9 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
     // (the paths' keys still give the plan's bboxes: error bit 32 otherwise, the plan's places kept) is checked below, between pass A
     // and the walk, every path once -- with or without slabs of its own --: a lane per path, by the first wave of one workgroup per
     // 64 paths (as many waves as k_path_bbox was; a check per workgroup was 5 % of this kernel's vector instructions).
+    // (the lean form is launched on a kept table only, behind the lean flatten, which leaves no key to check)
     const bool guarding = MODE == 1 && guard_keys != nullptr;
-    const int n_slabs_now = guarding ? (int)gridDim.x : bd->slab_cursor;
+    const int n_slabs_now = LEAN || guarding ? (int)gridDim.x : bd->slab_cursor;
     if ((int)blockIdx.x >= n_slabs_now) return;  // (the grid covers the plan's slab capacity)
     // (a slot of a path that did not fit the slab list: flagged by k_path_bbox -- when the table was written, if it is a kept one: the
     //  error word is sticky)
@@ -1885,7 +1899,8 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
     const int n_cell = sl.nb * sl.nk;
     const double o_r = (double)r0, o_c = (double)c0;  // `lines - [min_x, min_y]` (S:979)
     // (what the later phases need of the path -- scalar loads: asked for here, not behind a barrier each)
-    const int rl = path_rule[p], rule = rl & 1;
+    // (a byte load lands in a vector register: in the lean form it does not live through the row loop either)
+    int rl = path_rule[p], rule = rl & 1;
     const int group = path_group ? path_group[p] : -1;
     const int grad1 = path_grad ? path_grad[p] + 1 : 0;  // gradient index + 1 (0: solid colour)
     const double4 paint = ((const double4*)path_paint)[p];
@@ -1946,6 +1961,9 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
         pb_barrier();  // (the previous batch's tasks are done with s_edge / s_pref)
         if (PLANNED && plan_pending) {
             if (tid < PB_CELLS) { s_pos[tid] = my_plan.x; s_plan_n[tid] = my_plan.y; }
+            // (the lean form has no register to carry the pairs' places and the rule byte through the row loop: they wait in LDS like the places)
+            if (LEAN && (tid & (TR - 1)) == 0) s_pidx[tid / TR] = my_pidx;
+            if (LEAN && tid == 0) s_rl = rl;
             plan_pending = false;
         }
         if (BOUNDED && bounds) {
@@ -2211,6 +2229,17 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
                 for_rows(tot, [&](const RowAt& ra) { count_row(ra, std::true_type{}); });
             }
         }
+    } else if constexpr (LEAN) {
+        // (the first batch apart from the loop over the others: what only its stage() parks in LDS -- the places, the pairs' places, the
+        //  rule byte -- is in no register while the later batches run, and most slabs have one batch)
+        if (e_begin < e_end) {
+            total = stage(e_begin);
+            for_rows(total, [&](const RowAt& ra) { count_row(ra, std::true_type{}); });
+            for (int eb = e_begin + PB_BATCH; eb < e_end; eb += PB_BATCH) {
+                total = stage(eb);
+                for_rows(total, [&](const RowAt& ra) { count_row(ra, std::true_type{}); });
+            }
+        }
     } else
     for (int eb = e_begin; eb < e_end; eb += PB_BATCH) {
         total = stage(eb);
@@ -2236,6 +2265,7 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
     }
     pb_barrier();
     PB_STAMP(2);
+    if constexpr (LEAN) { rl = s_rl; rule = rl & 1; }
     // ---- walk ----
     // what one lane (tile row row_l) writes of a cell of class 1 or 2: its carry-in (class 1: into the header; class 2: an add at
     // the layer's first column in the tile, if any row piece lies left of the cell), its sentinel (behind the layer's last
@@ -2293,7 +2323,7 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
         int cursor = 0;                                    // adds of the column tiles walked so far
         bool mismatch = false;
         if (__ballot(active) != 0ull) {  // (a wave none of whose bands exists has nothing to walk)
-            const int idx = my_pidx;                           // the pair's place in its band's list
+            const int idx = LEAN ? s_pidx[g] : my_pidx;        // the pair's place in its band's list
             if (!PLANNED && active && row_l == 0) s_pidx[g] = idx;
             double run = sl.k0 > 0 ? s_left[row_l] : 0.0;      // the row's running sum left of the column tile
             unsigned had = sl.k0 > 0 ? s_rowb[PB_CELLS] : 0u;  // tile rows with a piece left of the column tile
@@ -5373,12 +5403,21 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         };
         // (an unplanned pass over add lists sized with room to spare: ONE pass on the workgroup's own bounds, MODE 2)
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
-        if (getenv("SVGR_DBG_PLAN"))   // (diagnostic: which instantiation this pass launches, and whether it found the slab table in place)
+        // The placed pass of a kept replay behind the lean flatten has nothing to guard; on one GPU, not deterministic, without groups or
+        // gradients and with the plan standing (no statistics) every option of the kernel has the value k_path_build<1, LEAN> is compiled for.
+        bool lean_pb = placed && keep_slabs && lean_fl && b->own.world <= 1 && !b->deterministic && b->n_groups == 0 && b->n_grads == 0 &&
+                       b->planned && !b->count_adds_only && b->adds.p != nullptr;
+#ifdef SVGR_DBG_PB_STAMP
+        lean_pb = false;   // (the stamps are the full form's)
+#endif
+        if (getenv("SVGR_DBG_PLAN")) {   // (diagnostic: which instantiation this pass launches, and whether it found the slab table in place)
+            fprintf(stderr, "[geometry] path build form %s\n", lean_pb ? "lean" : "full");
             fprintf(stderr, "[geometry] k_path_build<%d>%s, %lld slabs, tile lists %s, slab table %s\n", placed ? 1 : bounded ? 2 : 0,
                     b->count_adds_only ? " measuring" : "", (long long)b->n_slabs,
                     lists_kept ? "kept" : "rebuilt" /* (what k_tile_lists is asked for: a band whose words differ is listed again on the device) */,
                     keep_slabs ? "kept" : "written");
-        if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
+        }
+        if (lean_pb) launch_pb(k_path_build<1, true>); else if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
 #ifdef SVGR_DBG_PB_STAMP
         if (pb_dbg && b->planned && !b->count_adds_only) {
             static int n_dump = 0;
