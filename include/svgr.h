@@ -307,6 +307,43 @@ int svgr_hit_chunk(void);
 int svgr_batch_distance(svgr_batch* batch, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags,
                         size_t scratch_bytes, void* out);
 
+/* Multi-channel distance fields: four values to a point, R, G, B and A, on the kept edges, point forms, passes and encodings of
+ * svgr_batch_distance.  A is that entry's signed distance; R, G and B each follow the nearest edge of one colour and report the
+ * signed distance to that edge's LINE, so that median(R, G, B) keeps a corner sharp where A rounds it.
+ *
+ * The paths 0 .. group_off[n_groups] of the batch are dealt into groups: group g, one shape, is the paths group_off[g] ..
+ * group_off[g + 1] under one fill rule; colour[p] says which channels path p's edges belong to (bit 0 R, bit 1 G, bit 2 B);
+ * orient[g] is +1 or -1, chosen so that orient * ((a1 - a0) * (pb - b0) - (pa - a0) * (b1 - b0)) > 0 inside a well-oriented
+ * outline.  Paths behind the last group are ignored.  Only a group's edges TOGETHER need to close.
+ *
+ * The arithmetic (csrc/svgr_msdf.h is its one home, without fused multiply-adds): with x, y, inv of svgr_batch_distance, rl = len2
+ * > 0 ? 1.0 / sqrt(len2) : 0.0, da = pa - a0, db = pb - b0, s = da*x + db*y and t = s * inv (not clamped), an edge of len2 > 0 is a
+ * candidate with
+ *     t <= 0:     d2c = da*da + db*db,                                    se = s
+ *     t >= 1:     d2c = (pa - a1)*(pa - a1) + (pb - b1)*(pb - b1),        se = (pa - a1)*x + (pb - b1)*y
+ *     otherwise:  d2c = d2 of svgr_batch_distance,                         se = 0
+ *     o = (se*se) * inv;  perp = (x*db - da*y) * rl
+ * A channel keeps, among the edges of its colour, the candidate with the smallest d2c; ties go to the smaller o, then to the
+ * larger perp, so the edges' order does not matter.  Its value is sdf_clamp(-orient * perp); it is A instead when the channel
+ * kept nothing, when the point is not finite, or when the spread is finite and d2c >= spread * spread.  Then, with m = median(R,
+ * G, B): if ((m < 0) != (A < 0)) R = G = B = A, so the median's side is exactly A's.  Over the groups every channel takes the
+ * minimum; a group out of reach of a workgroup's points is skipped and counts as +spread, which is what it would have given.
+ * Without groups, or with groups that hold no path, all four are +spread.
+ *
+ * out[4 * i + {0, 1, 2, 3}] = R, G, B, A of point i in the encoding of the low bits of `flags` (those of svgr_batch_distance).
+ *
+ * SVGR_E_INVALID, before anything is launched: points together with a grid or neither; a spread that is NaN or <= 0;
+ * SVGR_MSDF_F32 or SVGR_MSDF_U8 with an infinite spread; unknown flag bits; a colour (of any path of the batch) outside 1 .. 7;
+ * a group_off that does not begin at 0, does not ascend or ends beyond the batch's paths; an orient that is not +1 or -1; a group
+ * whose paths differ in fill rule.  n_points == 0 launches nothing and succeeds.  scratch_bytes as for svgr_batch_distance.   */
+#define SVGR_MSDF_F64 0
+#define SVGR_MSDF_F32 1
+#define SVGR_MSDF_U8 2
+#define SVGR_MSDF_ENCODING_MASK 3
+int svgr_batch_msdf(svgr_batch* batch, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags,
+                    const uint8_t* colour, const int32_t* group_off, const int8_t* orient, int64_t n_groups, size_t scratch_bytes,
+                    void* out);
+
 /* Full device pipeline, asynchronous on the context stream, no host read-back:
  * transform+flatten -> bbox -> band binning -> tile kernel (LDS delta-coverage scatter, row scan,
  * fill rule, paint, source-over) -> store.  `out` must hold the output kind's bytes:

@@ -222,6 +222,7 @@ _PROTOS = {
     "svgr_hit_block": (C.c_int, []),
     "svgr_hit_chunk": (C.c_int, []),
     "svgr_batch_distance": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_size_t, _P]),
+    "svgr_batch_msdf": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, _P, _P, _P, C.c_int64, C.c_size_t, _P]),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -530,6 +531,26 @@ class Batch:
         res = np.zeros(n if union else (n, self.n_paths), dtype=dtype)
         flags = enc | (SDF_UNION if union else 0) | (0 if signed else SDF_UNSIGNED)
         _check(self.ctx.lib.svgr_batch_distance(self.handle, p, g, n, spread, flags, int(scratch_bytes), ptr(res) if res.size else None))
+        return res
+
+    def msdf(self, colour, group_off, orient, points=None, grid=None, spread: float = math.inf, out: str = "f64", scratch_bytes: int = 0) -> np.ndarray:
+        """svgr_batch_msdf: (n, 4) R, G, B, A at every point -- A the signed distance of `distance`, R / G / B the pseudo-distance to
+        the nearest edge of that colour -- over groups of paths: `colour` (n_paths,) masks 1 .. 7, group g the paths
+        group_off[g] .. group_off[g + 1], `orient` (n_groups,) +1 / -1; every channel the minimum over the groups.  `out` and the
+        points as for `distance`."""
+        if out not in SDF_OUT:
+            raise ValueError(f"out is one of {sorted(SDF_OUT)}, not {out!r}")
+        enc, dtype = SDF_OUT[out]
+        spread = sdf_spread(spread, finite=enc != SDF_F64)
+        colour = np.ascontiguousarray(colour, dtype=np.uint8).reshape(-1)
+        group_off = np.ascontiguousarray(group_off, dtype=np.int32).reshape(-1)
+        orient = np.ascontiguousarray(orient, dtype=np.int8).reshape(-1)
+        if len(colour) != self.n_paths or len(group_off) != len(orient) + 1:
+            raise ValueError("one colour per path, one orient per group and one more group_off than groups")
+        p, g, n, _keep = self._hit_points(points, grid)
+        res = np.zeros((n, 4), dtype=dtype)
+        _check(self.ctx.lib.svgr_batch_msdf(self.handle, p, g, n, spread, enc, ptr(colour), ptr(group_off), ptr(orient) if len(orient) else None,
+                                            len(orient), int(scratch_bytes), ptr(res) if res.size else None))
         return res
 
     def set_bands(self, rank: int, world: int, strip_bands: int = 1):

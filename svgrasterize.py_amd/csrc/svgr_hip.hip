@@ -1230,6 +1230,145 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_sdf_distance(const double* __rest
     }
 }
 
+// ======================================================================================
+// Multi-channel distance fields (svgr_batch_msdf: the entry is at the end of the file; the arithmetic: svgr_msdf.h).
+// ======================================================================================
+#include "svgr_msdf.h"
+
+// what the host says of a path in k_msdf_distance's table: its colour mask in bits 0 .. 2, and of the group it belongs to
+constexpr int MSDF_PATH_LAST = 8, MSDF_PATH_NEGATIVE = 16, MSDF_PATH_EVENODD = 32;   // the group ends here; sigma = -1; its fill rule
+
+// a lane per group: the union of its paths' extents (a path without edges has the empty extent +inf .. -inf, which changes nothing)
+__global__ __launch_bounds__(256) void k_msdf_group_extent(const double* __restrict__ ext, const int32_t* __restrict__ group_off, int n_groups,
+                                                            double* __restrict__ gext) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_groups) return;
+    double mna = INFINITY, mnb = INFINITY, mxa = -INFINITY, mxb = -INFINITY;
+    for (int p = group_off[g]; p < group_off[g + 1]; ++p) {
+        mna = fmin(mna, ext[4 * p]); mnb = fmin(mnb, ext[4 * p + 1]); mxa = fmax(mxa, ext[4 * p + 2]); mxb = fmax(mxb, ext[4 * p + 3]);
+    }
+    gext[4 * g] = mna; gext[4 * g + 1] = mnb; gext[4 * g + 2] = mxa; gext[4 * g + 3] = mxb;
+}
+
+// k_sdf_distance's structure -- HIT_BLOCK points or a tile per workgroup, the points' extent reduced once, the path table filled
+// HIT_BLOCK paths at a time, the edges of a path that stays prepared by the staging lane (msdf_edge_prepare: 8 doubles) and read
+// from LDS as broadcasts -- over GROUPS of paths: the paths 0 .. n_paths of the table are the groups' runs one after the other,
+// path_info[p] has the path's colour mask and MSDF_PATH_* of its group, path_group[p] the group.  The cull is k_sdf_distance's
+// with the same thr and through_ok, on the union of the group's extents (gext): it skips a group as a whole, never a single path
+// of one, because only the group's edges together close (colour_edges deals a subpath's segments out to several paths) and
+// because a channel may keep an edge of any of them.  DESIGN.md 7s: the spread guard of msdf_finish makes the skipped group's
+// four values exactly the +spread they count as.
+// A lane keeps one MsdfState in registers: A's min d2 and winding number and (d2, o, perp) for each of the three channels.  It
+// lives across the rounds of the table, as a group may straddle two; at a group's last path the lane takes the one sqrt, the
+// repair and the union.  A path's mask is wave-uniform, so the channel updates of msdf_edge sit behind scalar branches.
+// Results: out[4 * (id - id0) + {0, 1, 2, 3}] = R, G, B, A in elements of the encoding.
+template <int OUT>
+__global__ __launch_bounds__(HIT_BLOCK) void k_msdf_distance(const double* __restrict__ edges, const int* __restrict__ off, const double* __restrict__ gext,
+                                                             const uint8_t* __restrict__ path_info, const int32_t* __restrict__ path_group, int n_paths,
+                                                             const HitQuery q, long long group0, long long id0, double spread, double cull_spread,
+                                                             void* __restrict__ out) {
+    __shared__ __align__(16) double s_e[MSDF_EDGE_DOUBLES * HIT_CHUNK];
+    __shared__ double s_red[5][HIT_BLOCK / 64];
+    __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK], s_info[HIT_BLOCK];
+    const int lane = threadIdx.x;
+    const long long group = group0 + blockIdx.x;
+    double pa = 0.0, pb = 0.0;
+    long long id = 0;
+    const bool live = hit_point(q, group, lane, pa, pb, id);
+    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (every d2 is NaN, which fmin drops, and every compare false: nothing is kept)
+    const bool fin = pa == pa;
+    double lo_a = fin ? pa : INFINITY, hi_a = fin ? pa : -INFINITY, lo_b = fin ? pb : INFINITY, hi_b = fin ? pb : -INFINITY;
+    double min_absb = fin ? fabs(pb) : INFINITY;
+    for (int d = 32; d > 0; d >>= 1) {
+        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); hi_a = fmax(hi_a, __shfl_xor(hi_a, d));
+        lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
+        min_absb = fmin(min_absb, __shfl_xor(min_absb, d));
+    }
+    if ((lane & 63) == 0) {
+        s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = hi_a; s_red[2][lane >> 6] = lo_b; s_red[3][lane >> 6] = hi_b;
+        s_red[4][lane >> 6] = min_absb;
+    }
+    __syncthreads();
+    for (int k = 0; k < HIT_BLOCK / 64; ++k) {
+        lo_a = fmin(lo_a, s_red[0][k]); hi_a = fmax(hi_a, s_red[1][k]); lo_b = fmin(lo_b, s_red[2][k]); hi_b = fmax(hi_b, s_red[3][k]);
+        min_absb = fmin(min_absb, s_red[4][k]);
+    }
+    const bool through_ok = min_absb >= 0x1p-400;
+    double best[4] = {spread, spread, spread, spread};   // (a skipped group counts as +spread, and no group can give more)
+    MsdfState state;
+    msdf_begin(state);
+    bool touched = false;   // (block-uniform: the group at hand has had an edge)
+    for (int base = 0; base < n_paths; base += HIT_BLOCK) {
+        __syncthreads();   // (the previous round's table has been read)
+        {
+            const int p = base + lane;
+            int e0 = 0, e1 = 0, info = 0;
+            if (p < n_paths) {
+                e0 = off[p]; e1 = off[p + 1];
+                info = path_info[p];
+                if (e1 > e0 && cull_spread < INFINITY) {
+                    const int g = path_group[p];
+                    const double mna = gext[4 * g], mnb = gext[4 * g + 1], mxa = gext[4 * g + 2], mxb = gext[4 * g + 3];
+                    const double big = fmax(fmax(fabs(mna), fabs(mxa)), fmax(fabs(mnb), fabs(mxb)));
+                    const double thr = cull_spread * (1.0 + 0x1p-40) + 0x1p-40 * big;
+                    if (mnb - hi_b > thr || lo_b - mxb > thr || lo_a - mxa > thr || (through_ok && mna - hi_a > thr)) e1 = e0;
+                }
+            }
+            s_e0[lane] = e0; s_e1[lane] = e1; s_info[lane] = info;
+        }
+        __syncthreads();
+        const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
+        for (int j = 0; j < n_here; ++j) {
+            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+            const int info = __builtin_amdgcn_readfirstlane(s_info[j]);
+            if (e1 > e0) {
+                touched = true;
+                for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
+                    const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
+                    __syncthreads();   // (the previous chunk has been read)
+                    if (lane < n) {
+                        const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
+                        const double2 q0 = src[0], q1 = src[1];
+                        double pe[MSDF_EDGE_DOUBLES];
+                        msdf_edge_prepare(q0.x, q0.y, q1.x, q1.y, pe);
+                        double2* dst = (double2*)s_e + 4 * lane;
+                        dst[0] = make_double2(pe[0], pe[1]); dst[1] = make_double2(pe[2], pe[3]);
+                        dst[2] = make_double2(pe[4], pe[5]); dst[3] = make_double2(pe[6], pe[7]);
+                    }
+                    __syncthreads();
+                    for (int k = 0; k < n; ++k) {
+                        const double2 ab = ((const double2*)s_e)[4 * k], xy = ((const double2*)s_e)[4 * k + 1];
+                        const double2 ia = ((const double2*)s_e)[4 * k + 2], br = ((const double2*)s_e)[4 * k + 3];
+                        msdf_edge(state, info & 7, ab.x, ab.y, xy.x, xy.y, ia.x, ia.y, br.x, br.y, pa, pb);
+                    }
+                }
+            }
+            if (info & MSDF_PATH_LAST) {
+                if (touched) {
+                    double v[4];
+                    msdf_finish(state, (info & MSDF_PATH_EVENODD) ? 1 : 0, (info & MSDF_PATH_NEGATIVE) ? -1 : 1, spread, fin, v);
+                    msdf_union(best, v);
+                    msdf_begin(state);
+                    touched = false;
+                }
+            }
+        }
+    }
+    if (live) {
+        const size_t at = 4 * (size_t)(id - id0);
+        if constexpr (OUT == SDF_F64) {
+            double2* dst = (double2*)((double*)out + at);
+            dst[0] = make_double2(best[0], best[1]); dst[1] = make_double2(best[2], best[3]);
+        } else if constexpr (OUT == SDF_F32) {
+            *(float4*)((float*)out + at) = make_float4(sdf_encode_f32(best[0], spread), sdf_encode_f32(best[1], spread),
+                                                       sdf_encode_f32(best[2], spread), sdf_encode_f32(best[3], spread));
+        } else {
+            *(uchar4*)((uint8_t*)out + at) = make_uchar4(sdf_encode_u8(best[0], spread), sdf_encode_u8(best[1], spread),
+                                                         sdf_encode_u8(best[2], spread), sdf_encode_u8(best[3], spread));
+        }
+    }
+}
+
 // Plan only: exclusive prefix sums of the per-segment edge counts (seg_off[n] = their total).  One workgroup, a chunk of
 // 1024 segments per step with the running total carried along: a plan-time pass over a few thousand to a few million ints.
 __global__ __launch_bounds__(1024) void k_seg_scan(const int* __restrict__ seg_cnt, int n, int* __restrict__ seg_off) {
@@ -9861,6 +10000,96 @@ int svgr_batch_distance(svgr_batch* b, const double* points, const int64_t* grid
                 else SDF_LAUNCH(SDF_U8, false);
             }
 #undef SDF_LAUNCH
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    });
+}
+
+// Multi-channel distance fields (the arithmetic and its contract: svgr_msdf.h): svgr_batch_distance's frame -- the
+// kept edges, the point forms, the passes -- with four values to a point and the groups' tables in one upload.
+int svgr_batch_msdf(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags, const uint8_t* colour,
+                    const int32_t* group_off, const int8_t* orient, int64_t n_groups, size_t scratch_bytes, void* out) {
+    static const char* entry = "svgr_batch_msdf";
+    return abi_guard(entry, [&]() -> int {
+        if (!b || n_points < 0 || n_groups < 0 || n_groups > 0x7fffffffll) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+        if (flags & ~SVGR_MSDF_ENCODING_MASK) return fail(SVGR_E_INVALID, "%s: unknown flags 0x%x", entry, (unsigned)flags);
+        const int enc = flags & SVGR_MSDF_ENCODING_MASK;
+        if (enc >= SDF_ENCODINGS) return fail(SVGR_E_INVALID, "%s: unknown encoding %d", entry, enc);
+        if (!(spread > 0.0)) return fail(SVGR_E_INVALID, "%s: the spread is +inf or a finite value > 0, not %g", entry, spread);
+        if (enc != SDF_F64 && !(spread < INFINITY)) return fail(SVGR_E_INVALID, "%s: the float32 and uint8 encodings need a finite spread", entry);
+        PoolBlock d_pts, d_out;
+        HitQuery q;
+        long long n_wgs = 0;
+        if (int rc = hit_query(entry, points, grid, n_points, q, n_wgs)) return rc;
+        const int64_t np = b->n_paths;
+        if (!colour || (n_groups > 0 && (!group_off || !orient))) return fail(SVGR_E_INVALID, "%s: colour, group_off or orient is NULL", entry);
+        for (int64_t p = 0; p < np; ++p)
+            if (colour[p] < 1 || colour[p] > 7) return fail(SVGR_E_INVALID, "%s: the colour of path %lld is a mask 1 .. 7, not %d", entry, (long long)p, (int)colour[p]);
+        if (n_groups > 0 && group_off[0] != 0) return fail(SVGR_E_INVALID, "%s: group_off begins at 0", entry);
+        for (int64_t g = 0; g < n_groups; ++g)
+            if (group_off[g + 1] < group_off[g] || group_off[g + 1] > np)
+                return fail(SVGR_E_INVALID, "%s: group_off ascends and ends within the batch's %lld paths (group %lld)", entry, (long long)np, (long long)g);
+        for (int64_t g = 0; g < n_groups; ++g) {
+            if (orient[g] != 1 && orient[g] != -1) return fail(SVGR_E_INVALID, "%s: the orient of group %lld is +1 or -1, not %d", entry, (long long)g, (int)orient[g]);
+            for (int32_t p = group_off[g] + 1; p < group_off[g + 1]; ++p)
+                if ((b->host_rule[(size_t)p] & 1) != (b->host_rule[(size_t)group_off[g]] & 1))
+                    return fail(SVGR_E_INVALID, "%s: the paths of group %lld differ in fill rule", entry, (long long)g);
+        }
+        if (n_points == 0) return 0;
+        if (!out) return fail(SVGR_E_INVALID, "%s: out is NULL", entry);
+        const size_t elem = (size_t)sdf_elem_bytes(enc);
+        const int used = n_groups > 0 ? group_off[n_groups] : 0;   // the paths the groups cover: 0 .. used
+        if (used == 0) {   // no group, or none with a path: +spread everywhere
+            for (int64_t i = 0; i < 4 * n_points; ++i) {
+                if (enc == SDF_F64) ((double*)out)[i] = spread;
+                else if (enc == SDF_F32) ((float*)out)[i] = sdf_encode_f32(spread, spread);
+                else ((uint8_t*)out)[i] = sdf_encode_u8(spread, spread);
+            }
+            return 0;
+        }
+        // per path of the groups: its colour and its group's marks, and its group
+        std::vector<uint8_t> info((size_t)used);
+        std::vector<int32_t> owner((size_t)used);
+        for (int64_t g = 0; g < n_groups; ++g)
+            for (int32_t p = group_off[g]; p < group_off[g + 1]; ++p) {
+                info[(size_t)p] = (uint8_t)(colour[p] | (p == group_off[g + 1] - 1 ? MSDF_PATH_LAST : 0) | (orient[g] < 0 ? MSDF_PATH_NEGATIVE : 0) |
+                                            ((b->host_rule[(size_t)p] & 1) ? MSDF_PATH_EVENODD : 0));
+                owner[(size_t)p] = (int32_t)g;
+            }
+        HIPCHK(enter_ctx(b->ctx));
+        hipStream_t st = b->ctx->stream;
+        if (int rc = hit_prepare(b)) return rc;
+        if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
+        PassFrame f(b->ctx);
+        const Section<int32_t> s_go = f.blob.put(group_off, (size_t)n_groups + 1), s_own = f.blob.put(owner.data(), owner.size());
+        const Section<uint8_t> s_info = f.blob.put(info.data(), info.size());
+        if (int rc = f.upload()) return rc;
+        double* gext = f.scratch<double>(4 * (size_t)n_groups);
+        if (f.err) return f.err;
+        SVGR_LAUNCH(k_msdf_group_extent, grid1((size_t)n_groups), dim3(256), 0, st, (const double*)b->hit_ext.p, (const int32_t*)s_go.on(f.in.p), (int)n_groups, gext);
+        // a pass unit: a workgroup's points, or a row of tiles of a grid
+        const size_t point_bytes = 4 * elem;
+        const long long unit_groups = grid ? q.tiles_x : 1, unit_points = grid ? HIT_TILE * q.cols : HIT_BLOCK;
+        const long long n_units = n_wgs / unit_groups;
+        const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
+        const long long per_pass = std::min<long long>(n_units, std::max<long long>((long long)(budget / (point_bytes * (size_t)unit_points)), 1));
+        const long long pass_points = std::min<long long>(n_points, per_pass * unit_points);
+        HIPCHK(d_out.alloc(point_bytes * (size_t)pass_points));
+        const double cull_spread = (spread < INFINITY && spread >= 0x1p-100) ? spread : (double)INFINITY;
+        for (long long u0 = 0; u0 < n_units; u0 += per_pass) {
+            const long long nu = std::min<long long>(per_pass, n_units - u0);
+            const long long i0 = u0 * unit_points, i1 = std::min<long long>(n_points, (u0 + nu) * unit_points);
+            const dim3 g((unsigned)(nu * unit_groups)), blk(HIT_BLOCK);
+#define MSDF_LAUNCH(OUT)                                                                                                                \
+    SVGR_LAUNCH((k_msdf_distance<OUT>), g, blk, 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p, (const double*)gext,     \
+                (const uint8_t*)s_info.on(f.in.p), (const int32_t*)s_own.on(f.in.p), used, q, u0 * unit_groups, i0, spread, cull_spread, d_out.p)
+            if (enc == SDF_F64) MSDF_LAUNCH(SDF_F64);
+            else if (enc == SDF_F32) MSDF_LAUNCH(SDF_F32);
+            else MSDF_LAUNCH(SDF_U8);
+#undef MSDF_LAUNCH
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
         }

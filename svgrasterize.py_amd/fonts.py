@@ -175,6 +175,15 @@ class Font:
         a path per glyph, and one union grid query on the device (svgr_batch_distance); see sdf.py."""
         return font_sdf_atlas(self, string, size, spread, dtype, max_cols, flatness)
 
+    def msdf_atlas(self, string: str, size: float, spread: float, dtype=np.uint8, max_cols: int = 1024, angle: float = 3.0,
+                   flatness: float = FLATNESS) -> SdfAtlas:
+        """`sdf_atlas` with four channels (beyond the reference): the same cells, keys and layout, ``image`` of shape ``(rows, cols,
+        4)``: R, G, B whose median (``sdf.median``) keeps the glyphs' corners sharp, and in A the field of `sdf_atlas` itself.  One
+        batch, one group per glyph, and one query on the device (svgr_batch_msdf); see msdf.py."""
+        from .msdf import font_msdf_atlas
+
+        return font_msdf_atlas(self, string, size, spread, dtype, max_cols, angle, flatness)
+
     def names(self) -> dict:
         return {g.name: g.unicode for g in self.glyphs.values()}
 

@@ -681,6 +681,19 @@ class Path:
         finally:
             batch.destroy()
 
+    def msdf(self, transform: Transform | None, viewport, spread: float = 8.0, dtype=np.float32, fill_rule: str | None = None,
+             angle: float = 3.0, flatness: float = FLATNESS) -> np.ndarray:
+        """The path's multi-channel distance field over ``viewport = (row0, col0, rows, cols)``: a ``(rows, cols, 4)`` array R, G,
+        B, A at the pixel centres (beyond the reference).  A is ``sdf``'s field.  R, G and B each follow the nearest edge of one
+        colour -- the segments are coloured per subpath by ``msdf.colour_edges``, a corner wherever the outline turns by more than
+        ``pi - angle`` -- and report the signed distance to that edge's line, so that ``sdf.median`` of the three keeps corners
+        sharp under interpolation where A rounds them; where the median would disagree with A about the side, all three are A.
+        Dtypes, encodings and argument checks are those of ``sdf``.  An empty path gives all ``+spread`` and touches no device.  One
+        query on the device (svgr_batch_msdf); DESIGN.md 7s has the arithmetic."""
+        from .msdf import path_msdf
+
+        return path_msdf(self, transform, viewport, spread, dtype, fill_rule, angle, flatness)
+
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
         "on" dash an open subpath, ready for ``stroke``.  Eager, on the device (svgr_path_dash); quadratic and arc segments are

@@ -40,7 +40,7 @@ class SdfCell(tuple):
 
 
 class SdfAtlas:
-    """``image`` (rows, cols) in the dtype asked for, ``size`` (pixels per em), ``spread`` (pixels) and ``cells``: per glyph --
+    """``image`` (rows, cols) -- (rows, cols, 4) from ``Font.msdf_atlas`` -- in the dtype asked for, ``size`` (pixels per em), ``spread`` (pixels) and ``cells``: per glyph --
     keyed by ``glyph.unicode``, or by the glyph id (a name for an SVG font) where it has none -- its ``SdfCell``."""
     __slots__ = ["image", "size", "spread", "cells"]
 
@@ -153,6 +153,14 @@ def glyphs_sdf_atlas(glyphs, keys, units_per_em: float, size: float, spread: flo
     finally:
         batch.destroy()
     return SdfAtlas(image, size, spread, cells)
+
+
+def median(image) -> np.ndarray:
+    """The median of the first three channels of an MSDF image ``(..., 3 or 4)`` (``Path.msdf``, ``Font.msdf_atlas``): what a shader
+    computes from a sample before it thresholds."""
+    image = np.asarray(image)
+    r, g, b = image[..., 0], image[..., 1], image[..., 2]
+    return np.maximum(np.minimum(r, g), np.minimum(np.maximum(r, g), b))
 
 
 def cell_m6(cell: SdfCell, scale: float) -> list:
