@@ -1,9 +1,11 @@
 """Hit testing on the GPU: svgr_batch_winding and svgr_batch_pick through the C ABI against the numpy reference (tests/hit_ref.py)
 evaluated on the batch's own flattened edges (``batch.all_edges()``), exactly, at the seams of the launch geometry -- B =
 svgr_hit_block() points per workgroup, C = svgr_hit_chunk() edges per LDS stage, 32 paths per word of the bit matrix --; the
-scratch passes of the pick; ``Path.contains`` against ``Path.mask`` as an independent witness that also pins the coordinate order;
-``Scene.pick`` / ``Scene.id_map`` / ``Path.stroke_contains``; and the errors.  tests/test_hit_host.py checks on the CPU that the
-reference and the per-lane header are the same predicate."""
+rounds of the path table (256 paths a round), with clip tables across its words and rounds; the cull's comparisons, which only a
+query of one point lets decide; the scratch passes of the pick, for points and for grids; ``Path.contains`` against ``Path.mask`` as
+an independent witness that also pins the coordinate order; ``Scene.pick`` / ``Scene.id_map`` / ``Path.stroke_contains``; and the
+errors.  tests/test_hit_host.py checks on the CPU that the reference and the per-lane header are the same predicate;
+tests/test_gpu_hit_witness.py holds ``Scene.pick`` against what the renderer draws."""
 import numpy as np
 import pytest
 
@@ -63,16 +65,7 @@ def make_batch(S, paths, rules=None, transform=None):
 
 
 def query_points(seed, n, extent=40.0):
-    """Scattered points, a few on integer positions (vertices and edges of the integer polygons), a few far away, one NaN."""
-    rng = np.random.default_rng(seed)
-    pts = rng.uniform(-3.0, extent + 3.0, size=(n, 2))
-    k = n // 4
-    pts[:k] = rng.integers(0, int(extent), size=(k, 2))
-    if n > 8:
-        pts[-1] = (np.nan, 5.0)
-        pts[-2] = (1e9, -1e9)
-        pts[-3] = (-np.inf, 5.0)
-    return pts
+    return cases.scattered_points(seed, n, extent)
 
 
 def check_against_reference(S, batch, pts, rules=None):
@@ -190,6 +183,153 @@ def test_scratch_passes(S, seams):
     ok, top = R.resolve(inside, pickable, clips)
     assert np.array_equal(bits1, R.pack_bits(ok)) and np.array_equal(top1, top)
     assert (top >= 0).any() and (top < 0).any() and (inside[:, 32] & ~ok[:, 32]).any() and ok[:, 32].any()   # (the clips bite)
+
+
+# ---- the rounds of the path table, the cull's comparisons, grids in passes ---------------------------------------------------------
+def check_pick(batch, rules, pickable, clips, want_w, points=None, grid=None, **kw):
+    """winding and pick (top and bits) of a query against the reference evaluated on the reference's windings `want_w`."""
+    n_paths = batch.n_paths
+    got_w = batch.winding(points, grid)
+    assert got_w.dtype == np.int32 and got_w.shape == want_w.shape
+    assert np.array_equal(got_w, want_w), f"{int((got_w != want_w).sum())} of {got_w.size} winding numbers differ"
+    ok, top = R.resolve(R.inside(want_w, rules), pickable, clips)
+    got_top, got_bits = batch.pick(points, grid, pickable=pickable, clips=clips, want_bits=True, **kw)
+    assert got_bits.shape == (len(want_w), (n_paths + 31) // 32)
+    assert np.array_equal(got_bits, R.pack_bits(ok)), f"{int((R.unpack_bits(got_bits, n_paths) != ok).sum())} pass bits differ"
+    assert np.array_equal(got_top, top), f"{int((got_top != top).sum())} of {len(top)} tops differ"
+    return got_w, got_top, got_bits
+
+
+def table_round_batch(S, n_paths):
+    case = cases.table_round_case(n_paths)
+    return case, make_batch(S, [poly_path(S, p) for p in case.polys], case.rules)
+
+
+def reference_winding(batch, pts):
+    edges, edge_path = batch.all_edges()
+    return R.winding(edges, edge_path, batch.n_paths, pts)
+
+
+def grid_centres(grid):
+    row0, col0, rows, cols = grid
+    rr, cc = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    return np.stack([row0 + rr.ravel() + 0.5, col0 + cc.ravel() + 0.5], axis=1)
+
+
+@pytest.mark.parametrize("n_paths", cases.TABLE_ROUND_COUNTS)
+def test_path_counts_at_the_table_rounds(S, seams, n_paths):
+    block, _chunk = seams
+    assert block == 256     # the rounds the case is built around
+    case, batch = table_round_batch(S, n_paths)
+    want = reference_winding(batch, case.points)
+    case.check(want)        # paths on both sides of every seam hold a point; the emptied ones -- 0, 255, 256, the last -- hold none
+    assert set(batch.all_edges()[1].tolist()) == set(range(n_paths)) - set(case.empty)
+    _w, top, _bits = check_pick(batch, case.rules, case.pickable, None, want, case.points)
+    assert (top >= 0).any() and (top < 0).any() and not (top % 5 == 0).any()
+
+
+def test_clip_tables_across_words_and_rounds(S, seams):
+    block, _chunk = seams
+    case = cases.clip_table_case()
+    batch = make_batch(S, [poly_path(S, p) for p in case.polys], case.rules)
+    want = reference_winding(batch, case.points)
+    inside = R.inside(want, case.rules)
+    case.check(inside, R.resolve(inside, case.pickable, case.clips)[0])     # every clip bites and lets pass; path 100 never passes
+    _w, top1, bits1 = check_pick(batch, case.rules, case.pickable, case.clips, want, case.points)
+    words = (case.n_paths + 31) // 32
+    ctx = S.Context.get()
+    n0 = ctx.launches()
+    top3, bits3 = batch.pick(case.points, pickable=case.pickable, clips=case.clips, scratch_bytes=4 * words * block, want_bits=True)
+    assert ctx.launches() - n0 == 2 * 3       # 600 points: three workgroups, one to a pass
+    assert np.array_equal(top1, top3) and np.array_equal(bits1, bits3)
+
+
+def cull_batch(S, shift=0.0):
+    polys = [p + shift for p in cases.cull_polygons()]
+    pts = np.concatenate([cases.cull_boundary_points(p) for p in cases.cull_polygons()])
+    return make_batch(S, [poly_path(S, p) for p in polys]), pts
+
+
+def test_one_point_queries_on_the_extent(S, seams):
+    # a query of one point: the workgroup's extent is that point, and the cull's comparisons with a path's extent decide alone
+    batch, pts = cull_batch(S)
+    n_paths = batch.n_paths
+    rules, pickable = np.zeros(n_paths, dtype=np.uint8), np.array([1, 1, 0, 1], dtype=np.uint8)
+    want = reference_winding(batch, pts)
+    assert len(pts) == 52 and (want[[6, 13 + 6], [0, 1]] != 0).all()       # (6, 2) on the square's, (6, 3) on the triangle's b == mnb
+    rows = [check_pick(batch, rules, pickable, None, want[i:i + 1], pts[i:i + 1]) for i in range(len(pts))]
+    together = check_pick(batch, rules, pickable, None, want, pts)
+    for k in range(3):
+        assert np.array_equal(np.concatenate([r[k] for r in rows]), together[k])
+    assert (together[1] == 2).sum() == 0 and (together[1] >= 0).any() and (together[1] < 0).any()
+
+
+def test_one_pixel_grids_on_the_extent(S, seams):
+    # the same for the grid form of the query: polygons with half-integer corners, 1 x 1 grids whose pixel centre lies on an extent
+    batch, corners = cull_batch(S, shift=0.5)
+    n_paths = batch.n_paths
+    rules, pickable = np.zeros(n_paths, dtype=np.uint8), np.ones(n_paths, dtype=np.uint8)
+    want = reference_winding(batch, corners + 0.5)
+    assert (want[[6, 13 + 6], [0, 1]] != 0).all() and (want == 0).any()
+    for i, (r, c) in enumerate(corners.astype(np.int64).tolist()):
+        check_pick(batch, rules, pickable, None, want[i:i + 1], grid=(r, c, 1, 1))
+
+
+def test_grid_queries_in_scratch_passes(S, seams):
+    block, _chunk = seams
+    n_paths = 40
+    batch = make_batch(S, [poly_path(S, p) for p in cases.random_polygons(20, n_paths)])
+    rules = np.zeros(n_paths, dtype=np.uint8)
+    clips = [() for _ in range(n_paths)]
+    clips[33] = ((2, 31),)
+    clips[39] = ((33,), (32, 38))
+    clips[20] = ((3,), (4, 5))
+    pickable = np.arange(n_paths) % 5 != 0
+    words = (n_paths + 31) // 32
+    assert words == 2
+    ctx = S.Context.get()
+    batch.winding(np.zeros((1, 2)))   # (flattened now: what follows launches the two kernels of a pass and nothing else)
+    for grid in [(-3, 2, 37, 21), (0, 0, 16, 16), (5, -4, 1, 40), (5, -4, 40, 1), (0, 0, 17, 32)]:
+        centres = grid_centres(grid)
+        want = reference_winding(batch, centres)
+        n_groups = -(-grid[2] // 16) * -(-grid[3] // 16)
+        runs = []
+        for tiles in (None, 1, 3):    # one pass; a tile to a pass; three tiles: a pass ends in the middle of a row of tiles
+            n0 = ctx.launches()
+            top, bits = batch.pick(grid=grid, pickable=pickable, clips=clips, want_bits=True,
+                                   scratch_bytes=0 if tiles is None else 4 * words * block * tiles)
+            passes = 1 if tiles is None else -(-n_groups // tiles)
+            assert ctx.launches() - n0 == 2 * passes, (grid, tiles)
+            runs.append((top, bits))
+        for top, bits in runs[1:]:
+            assert np.array_equal(top, runs[0][0]) and np.array_equal(bits, runs[0][1]), grid
+        _w, top_p, bits_p = check_pick(batch, rules, pickable, clips, want, centres)
+        assert np.array_equal(runs[0][0], top_p) and np.array_equal(runs[0][1], bits_p), grid
+        if grid[2] * grid[3] > 100:
+            inside = R.inside(want, rules)
+            assert (top_p >= 0).any() and (inside[:, 39] & ~R.unpack_bits(bits_p, n_paths)[:, 39]).any()    # (the clips bite)
+
+
+def test_winding_of_a_grid_beyond_one_round(S, seams):
+    case, batch = table_round_batch(S, 257)
+    grid = (-2, -2, 20, 35)
+    centres = grid_centres(grid)
+    want = reference_winding(batch, centres)
+    got = batch.winding(grid=grid)
+    assert np.array_equal(got, batch.winding(centres)) and np.array_equal(got, want)
+    assert (want != 0).any(axis=0).sum() > 50           # (tiny triangles: most hold no pixel centre, many do)
+    check_pick(batch, case.rules, case.pickable, None, want, grid=grid)
+
+
+def test_a_fresh_batch_gives_the_same_rows(S, seams):
+    # k_hit_place orders a path's edges by atomics: the rows must not depend on that order
+    results = []
+    for _ in range(2):
+        case, batch = table_round_batch(S, 257)
+        top, bits = batch.pick(case.points, pickable=case.pickable, want_bits=True)
+        results.append((batch.winding(case.points).tobytes(), top.tobytes(), bits.tobytes()))
+        batch.destroy()
+    assert results[0] == results[1]
 
 
 # ---- an independent witness: the renderer -----------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Hit testing on the CPU: the per-lane header (csrc/svgr_hit.h, through tests/hit_harness.cpp) against the numpy reference
-(tests/hit_ref.py) and both against exact rational arithmetic; the seam cases by hand; the resolve of clips and paint order; and
-the library layer without a device: ``Scene.hit_leaves`` on a hand-built scene and the ownership rule of ``elements_at`` on a
-loaded document."""
+(tests/hit_ref.py) and both against exact rational arithmetic; the seam cases by hand; the resolve of clips and paint order; the
+conditions of the cases of tests/hit_cases.py that the device tests run (table rounds, clip tables, points on a path's extent);
+and the library layer without a device: ``Scene.hit_leaves`` on a hand-built scene and the ownership rule of ``elements_at`` on
+a loaded document."""
 import ctypes
 
 import numpy as np
@@ -111,6 +112,39 @@ def test_header_and_reference_agree_off_the_integers():
     assert np.array_equal(harness_winding(edges, off, pts), R.winding(edges, ep, len(polys), pts))
 
 
+def test_points_on_a_paths_extent():
+    # what the device's cull must not change (tests/test_gpu_hit.py sends every one of these as a query of its own): the header,
+    # the reference and exact arithmetic give the same numbers, and the closed sides of the extent do hold points
+    polys = cases.cull_polygons()
+    edges, ep, off = cases.edge_table(polys)
+    on_min_b = 0
+    for which, poly in enumerate(polys):
+        pts = cases.cull_boundary_points(poly)
+        assert pts.shape == (13, 2) and (pts == np.round(pts)).all()
+        (mna, mnb), (mxa, mxb) = poly.min(axis=0), poly.max(axis=0)
+        assert {(a, b) for a in (mna, mxa) for b in (mnb, mxb)} <= {tuple(p) for p in pts.tolist()}
+        assert ((pts[:, 0] > mna) & (pts[:, 0] < mxa) & (pts[:, 1] > mnb) & (pts[:, 1] < mxb)).sum() == 1
+        assert ((pts[:, 0] < mna) | (pts[:, 0] > mxa) | (pts[:, 1] < mnb) | (pts[:, 1] > mxb)).sum() == 4
+        exact = np.array([[R.winding_exact(edges[off[p]:off[p + 1]], pt) for p in range(len(polys))] for pt in pts], dtype=np.int32)
+        assert np.array_equal(harness_winding(edges, off, pts), exact)
+        assert np.array_equal(R.winding(edges, ep, len(polys), pts), exact)
+        outside = (pts[:, 0] < mna) | (pts[:, 0] > mxa) | (pts[:, 1] < mnb) | (pts[:, 1] > mxb) | (pts[:, 1] == mxb) | (pts[:, 0] == mxa)
+        assert (exact[outside, which] == 0).all()          # b == mxb is the open end of every edge, a == mxa is left of none
+        on_min_b += int((exact[pts[:, 1] == mnb, which] != 0).sum())
+    assert on_min_b >= 2    # b == mnb is closed: SQUARE holds (2, 2) and (6, 2), TRIANGLE (6, 3)
+
+
+@pytest.mark.parametrize("n_paths", cases.TABLE_ROUND_COUNTS)
+def test_the_table_round_cases_meet_their_condition(n_paths):
+    case = cases.table_round_case(n_paths)
+    edges, ep, off = cases.edge_table(case.polys)
+    want = R.winding(edges, ep, n_paths, case.points)
+    case.check(want)
+    assert 100 <= len(case.points) <= 130 and not np.isfinite(case.points).all()
+    assert {0, n_paths - 1} <= set(case.empty) and set(case.empty) <= {0, 255, 256, n_paths - 1}
+    assert np.array_equal(harness_winding(edges, off, case.points), want)
+
+
 def test_inside_rules_and_bit_packing():
     w = np.array([[0, 1, 2, -1, -2, 3] * 6], dtype=np.int32)[:, :33]
     rules = np.array([0, 1] * 17, dtype=np.uint8)[:33]
@@ -169,6 +203,26 @@ def test_resolve_across_the_word_seam():
     ok, top = both_resolves(inside, pickable, clips)
     assert np.array_equal(ok[:, 40], inside[:, 40] & ok[:, 33] & (inside[:, 32] | inside[:, 39]))
     assert (top >= 0).any()
+
+
+def test_resolve_clip_tables_across_words_and_rounds():
+    # chains over the 31 / 32 / 33 and the 255 / 256 / 257 seams, a source at bit 0 of a later word, sources in the user's own
+    # word and in earlier ones within one group (tests/test_gpu_hit.py runs the same tables on the device)
+    case = cases.clip_table_case()
+    assert case.n_paths == 300 and len(case.points) == 600
+    assert case.clips[33] == ((32,),) and case.clips[257] == ((256,), (256,)) and case.clips[299] == ((3, 255), (256, 290))
+    edges, ep, _off = cases.edge_table(case.polys)
+    inside = R.inside(R.winding(edges, ep, case.n_paths, case.points), case.rules)
+    ok, top = both_resolves(inside, case.pickable, case.clips)
+    case.check(inside, ok)
+    assert not (top % 7 == 3).any() and (top >= 0).any()
+    rng = np.random.default_rng(31)
+    for density in (0.5, 0.8, 0.95):
+        flags = rng.random((200, case.n_paths)) < density
+        ok, _top = both_resolves(flags, case.pickable, case.clips)
+        assert np.array_equal(ok[:, 33], flags[:, 30] & flags[:, 31] & flags[:, 32] & flags[:, 33])
+        assert np.array_equal(ok[:, 299], flags[:, 299] & (flags[:, 3] | ok[:, 255]) & (ok[:, 256] | flags[:, 290]))
+        assert not ok[:, 100].any()
 
 
 @pytest.mark.parametrize("clips", [[(), ((1,),)], [(), ((2,),), ()], [((0,),)], [(), ((-1,),)]])
