@@ -44,7 +44,8 @@ extern "C" {
  *    svgr_jpeg_decode added (JPEG in SVG <image>); svgr_layer_tile added (feTile); svgr_jpeg_encode,
  *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output); svgr_png_filter, svgr_deflate and
  *    svgr_deflate_chunk added (the device PNG encoder); svgr_layer_to_tensor, svgr_tensor_to_layer, svgr_tensor_block,
- *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output) */
+ *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output); svgr_quant_distinct,
+ *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -993,6 +994,34 @@ int svgr_tensor_run(void);
  * far.  Each through an event the context keeps; neither blocks the host.  other == NULL is the runtime's default stream. */
 int svgr_stream_wait_for(svgr_ctx* ctx, void* other);
 int svgr_stream_signal_to(svgr_ctx* ctx, void* other);
+
+/* Indexed PNG output (Layer.write_png(palette=...), quantize; beyond the reference): the colour quantiser's device stages over
+ * src_rgba8 (device, rows * cols * 4 bytes as svgr_layer_to_rgba8 writes them: a pixel is the little-endian uint32 r | g << 8 |
+ * b << 16 | a << 24).  csrc/svgr_quant.h has the arithmetic: a pixel with a == 0 counts as 0 (canonical); X(p) = (r a, g a, b a,
+ * 255 a) and D(p, q) = the sum of the squared differences of X, unsigned 64-bit; the bin of a pixel is (r >> 3, g >> 3, b >> 3,
+ * a >> 3), r in the highest of its 20 bits.  The palette itself is built by the caller from the bins.  An image is 1 .. 2^16 a
+ * side and at most 2^30 pixels (SVGR_E_INVALID beyond: the bins' 64-bit sums, at most 2^30 * 65025 < 2^46, cannot overflow in it).
+ * svgr_quant_distinct: the set of distinct canonical pixels if there are at most max_colors (1 .. 256) of them: colors[0 ..
+ *   *n_colors - 1], ascending as uint32, and *overflow = 0; otherwise *overflow = 1 and *n_colors = 0.  colors has room for
+ *   max_colors values.  Waits for the device.
+ * svgr_quant_bins: the non-empty bins in ascending key order: keys[i] and bins[5 * i .. 5 * i + 4] = {pixels, sum of X0, X1, X2, X3}
+ *   over the bin's pixels, integer sums and so the same from run to run.  *n_bins always receives their number; with more than
+ *   `cap` of them nothing is written and the status is SVGR_E_INVALID (min(rows * cols, 2^20) always suffices).  Waits.
+ * svgr_quant_index: per pixel the index of the nearest of the palette's n_palette (1 .. 256) entries (device, uint32 pixels as
+ *   above) under D, a tie going to the lowest index.  out_stream (device, or NULL) receives the scanlines of a colour type 3
+ *   PNG at depth = the smallest of 1, 2, 4, 8 with 2^depth >= n_palette: per row the filter byte 0 and ceil(cols * depth / 8)
+ *   bytes, indices MSB first, the padding bits zero -- ready for svgr_deflate.  out_indices (device, or NULL) receives rows * cols
+ *   bytes, an index each.  At least one of the two is given.  Enqueued on the context's stream, no wait.
+ * svgr_quant_block: the pixels of one workgroup of the three kernels (their launch seam); a lane takes 8 consecutive ones.
+ * svgr_quant_groups: the most workgroups svgr_quant_bins launches; with more blocks than that a workgroup takes several. */
+int svgr_quant_distinct(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, int max_colors, uint32_t* colors,
+                        int64_t* n_colors, int* overflow);
+int svgr_quant_bins(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, uint32_t* keys, uint64_t* bins, int64_t cap,
+                    int64_t* n_bins);
+int svgr_quant_index(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, const svgr_buf* palette, int n_palette,
+                     svgr_buf* out_stream, svgr_buf* out_indices);
+int svgr_quant_block(void);
+int svgr_quant_groups(void);
 
 #ifdef __cplusplus
 }

@@ -223,6 +223,11 @@ _PROTOS = {
     "svgr_hit_chunk": (C.c_int, []),
     "svgr_batch_distance": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, C.c_size_t, _P]),
     "svgr_batch_msdf": (C.c_int, [_P, _P, _P, C.c_int64, C.c_double, C.c_int, _P, _P, _P, C.c_int64, C.c_size_t, _P]),
+    "svgr_quant_distinct": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "svgr_quant_bins": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "svgr_quant_index": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, _P, _P]),
+    "svgr_quant_block": (C.c_int, []),
+    "svgr_quant_groups": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -1181,3 +1186,46 @@ def deflate(ctx: Context, src: DeviceBuffer, n_bytes: int, huffman: int) -> byte
         out = np.empty(n.value, dtype=np.uint8)
     _check(rc)
     return out[:n.value].tobytes()
+
+
+def quant_block() -> int:
+    """Pixels per workgroup of the quantiser's kernels (svgr_quant_block)."""
+    return int(load_library().svgr_quant_block())
+
+
+def quant_groups() -> int:
+    """The most workgroups of svgr_quant_bins' histogram kernel (svgr_quant_groups): beyond that many blocks a workgroup takes several."""
+    return int(load_library().svgr_quant_groups())
+
+
+def quant_distinct(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, max_colors: int):
+    """svgr_quant_distinct: the distinct canonical pixels of the image as ascending uint32, or None when there are more than
+    `max_colors`."""
+    colors = np.zeros(max(max_colors, 1), dtype=np.uint32)
+    n, overflow = C.c_int64(), C.c_int()
+    _check(ctx.lib.svgr_quant_distinct(ctx.handle, rgba8.handle, rows, cols, max_colors, ptr(colors), C.byref(n), C.byref(overflow)))
+    return None if overflow.value else colors[:n.value].copy()
+
+
+def quant_bins(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int):
+    """svgr_quant_bins: ``(keys (n,) uint32 ascending, bins (n, 5) uint64)``: per non-empty bin its pixels and the sums of X."""
+    cap = max(min(rows * cols, 1 << 20), 1)
+    keys, bins = np.empty(cap, dtype=np.uint32), np.empty((cap, 5), dtype=np.uint64)   # (untouched pages cost nothing)
+    n = C.c_int64()
+    _check(ctx.lib.svgr_quant_bins(ctx.handle, rgba8.handle, rows, cols, ptr(keys), ptr(bins), cap, C.byref(n)))
+    return keys[:n.value].copy(), bins[:n.value].copy()
+
+
+def quant_index(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, palette: np.ndarray, stream: bool = True, indices: bool = False):
+    """svgr_quant_index: ``(stream, indices)``, each a DeviceBuffer or None: the packed scanlines (filter bytes included) and
+    the plain byte indices of the image under `palette`, an (n, 4) uint8 array of RGBA entries."""
+    pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 4)
+    n = len(pal)
+    depth = 1 if n <= 2 else 2 if n <= 4 else 4 if n <= 16 else 8
+    d_pal = ctx.from_host(pal) if n else ctx.alloc(4)
+    out_s = ctx.alloc(max(rows, 1) * (1 + (max(cols, 1) * depth + 7) // 8)) if stream else None
+    out_i = ctx.alloc(max(rows * cols, 1)) if indices else None
+    _check(ctx.lib.svgr_quant_index(ctx.handle, rgba8.handle, rows, cols, d_pal.handle, n, out_s.handle if stream else None,
+                                    out_i.handle if indices else None))
+    ctx.sync()   # (the palette's block is released when this returns)
+    return out_s, out_i

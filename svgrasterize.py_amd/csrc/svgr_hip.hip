@@ -10098,3 +10098,310 @@ int svgr_batch_msdf(svgr_batch* b, const double* points, const int64_t* grid, in
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// Indexed PNG output: the colour quantiser's device stages (svgr_quant_distinct, svgr_quant_bins, svgr_quant_index).  The
+// per-lane arithmetic is svgr_quant.h; DESIGN.md 7t has the definitions and the palette builder, which runs on the host over
+// the bins.  A lane takes QUANT_RUN consecutive pixels, a workgroup QUANT_BLOCK: flat art repeats its pixels, and a lane that
+// meets the pixel it has just had does no work for it.
+//
+//   k_quant_distinct  an open-addressed set of QUANT_SLOTS words in memory: a lane reads the slot (most pixels find their colour
+//                     there), and only an empty one is claimed with a compare-and-swap, which also counts.  A slot changes once,
+//                     from empty to a colour, so a stale read costs a swap that fails and nothing else.  Lanes stop once the
+//                     count is past max_colors; the set itself is the result, and no order of arrival changes a set
+//   k_quant_bins      per lane the run's pixels of one bin summed in registers; a wave whose lanes all end in the same bin adds
+//                     them up with shuffles and one lane sends the five adds -- to a small table of bins in LDS, which the
+//                     workgroup, striding over many blocks, sends to memory once at its end: the few bins of flat art would
+//                     otherwise take every wave's adds at the same five addresses.  Integer adds only
+//   k_quant_flag / k_scan_* / k_quant_compact   the dasher's two-level scan over "bin is not empty": the bins in key order
+//   k_quant_index     the palette's coordinates in LDS (every lane reads the same entry at the same time: a broadcast), per
+//                     pixel the nearest entry, the run's indices packed to `depth` bytes and stored
+// ======================================================================================
+#include "svgr_quant.h"
+
+constexpr int QUANT_LANES = 256, QUANT_BLOCK = QUANT_LANES * QUANT_RUN;
+// (a section of its own, like the marker kernels': the tile kernel's branches to its cold paths keep their reach)
+#define QUANT_KERNEL __global__ __launch_bounds__(QUANT_LANES) __attribute__((section(".text.svgr_quant")))
+struct QuantSet { uint32_t slot[QUANT_SLOTS]; uint32_t count, full; };
+struct QuantSumOp {
+    __device__ static int zero() { return 0; }
+    __device__ static int add(const int& a, const int& b) { return a + b; }
+};
+
+// the lane's run: pixels i0 .. i0 + n - 1 (i0 is a multiple of QUANT_RUN; 0 <= n <= QUANT_RUN)
+__device__ __forceinline__ int quant_load_run(const uint32_t* __restrict__ src, long long n_px, long long i0, uint32_t* px) {
+    const long long left = n_px - i0;
+    const int n = left >= QUANT_RUN ? QUANT_RUN : left > 0 ? (int)left : 0;
+    if (n == QUANT_RUN && ((uintptr_t)src & 15) == 0) {
+        const uint4 lo = *(const uint4*)(src + i0), hi = *(const uint4*)(src + i0 + 4);
+        px[0] = lo.x; px[1] = lo.y; px[2] = lo.z; px[3] = lo.w; px[4] = hi.x; px[5] = hi.y; px[6] = hi.z; px[7] = hi.w;
+    } else {
+        SVGR_UNROLL
+        for (int k = 0; k < QUANT_RUN; ++k) px[k] = k < n ? src[i0 + k] : 0u;
+    }
+    return n;
+}
+
+QUANT_KERNEL void k_quant_distinct(const uint32_t* __restrict__ src, long long n_px, uint32_t max_colors, QuantSet* set) {
+    const long long i0 = ((long long)blockIdx.x * QUANT_LANES + threadIdx.x) * QUANT_RUN;
+    uint32_t px[QUANT_RUN];
+    const int n = quant_load_run(src, n_px, i0, px);
+    uint32_t prev = QUANT_EMPTY;
+    for (int k = 0; k < n; ++k) {
+        const uint32_t c = quant_canon(px[k]);
+        if (c == prev) continue;
+        prev = c;
+        if (__hip_atomic_load(&set->count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > max_colors) return;
+        uint32_t s = quant_slot(c), probes = 0;
+        for (; probes < QUANT_SLOTS; ++probes, s = (s + 1) & (QUANT_SLOTS - 1)) {
+            uint32_t cur = set->slot[s];
+            if (cur == QUANT_EMPTY) {
+                cur = atomicCAS(&set->slot[s], QUANT_EMPTY, c);
+                if (cur == QUANT_EMPTY) {
+                    atomicAdd(&set->count, 1u);
+                    break;
+                }
+            }
+            if (cur == c) break;
+        }
+        if (probes == QUANT_SLOTS) atomicOr(&set->full, 1u);   // (every slot holds another colour: more than max_colors of them)
+    }
+}
+
+// At most QUANT_GROUPS workgroups stride over the image's blocks; each keeps QUANT_CACHE bins in LDS (claimed by compare-and-swap,
+// QUANT_PROBES slots tried) and sends them to memory once, at its end; a bin that finds no slot goes to memory directly.
+constexpr int QUANT_GROUPS = 1024, QUANT_CACHE = QUANT_LANES, QUANT_PROBES = 4;
+QUANT_KERNEL void k_quant_bins(const uint32_t* __restrict__ src, long long n_px, long long n_blocks, QuantBin* __restrict__ hist) {
+    __shared__ uint32_t ckey[QUANT_CACHE];
+    __shared__ unsigned long long csum[QUANT_CACHE][5];
+    ckey[threadIdx.x] = 0xFFFFFFFFu;
+    SVGR_UNROLL
+    for (int j = 0; j < 5; ++j) csum[threadIdx.x][j] = 0;
+    __syncthreads();
+    uint32_t key, cnt, s[4];   // (a run's sums: 8 * 65025 at the most)
+    auto flush = [&]() {
+        if (!cnt) return;
+        uint32_t slot = (key * 2654435761u) >> 24;
+        static_assert(QUANT_CACHE == 256, "the slot is the hash's top eight bits");
+        for (int p = 0; p < QUANT_PROBES; ++p, slot = (slot + 1) & (QUANT_CACHE - 1)) {
+            const uint32_t old = atomicCAS(&ckey[slot], 0xFFFFFFFFu, key);
+            if (old == 0xFFFFFFFFu || old == key) {
+                atomicAdd(&csum[slot][0], (unsigned long long)cnt);
+                SVGR_UNROLL
+                for (int j = 0; j < 4; ++j) atomicAdd(&csum[slot][1 + j], (unsigned long long)s[j]);
+                return;
+            }
+        }
+        unsigned long long* b = (unsigned long long*)&hist[key];
+        atomicAdd(b, (unsigned long long)cnt);
+        SVGR_UNROLL
+        for (int j = 0; j < 4; ++j) atomicAdd(b + 1 + j, (unsigned long long)s[j]);
+    };
+    for (long long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+        const long long i0 = (blk * QUANT_LANES + threadIdx.x) * QUANT_RUN;
+        uint32_t px[QUANT_RUN];
+        const int n = quant_load_run(src, n_px, i0, px);
+        key = 0xFFFFFFFFu;
+        cnt = s[0] = s[1] = s[2] = s[3] = 0;
+        for (int k = 0; k < n; ++k) {
+            const uint32_t c = quant_canon(px[k]), kk = quant_bin_key(c);
+            if (kk != key) {
+                flush();
+                key = kk;
+                cnt = s[0] = s[1] = s[2] = s[3] = 0;
+            }
+            uint32_t x[4];
+            quant_x(c, x);
+            ++cnt;
+            SVGR_UNROLL
+            for (int j = 0; j < 4; ++j) s[j] += x[j];
+        }
+        // what is left: one bin for the whole wave (a wave's sums: 512 * 65025 at the most), or each lane for itself
+        if (__all(key == (uint32_t)__builtin_amdgcn_readfirstlane((int)key))) {
+            for (int d = 32; d; d >>= 1) {
+                cnt += __shfl_down(cnt, d, 64);
+                SVGR_UNROLL
+                for (int j = 0; j < 4; ++j) s[j] += __shfl_down(s[j], d, 64);
+            }
+            if ((threadIdx.x & 63) == 0) flush();
+        } else {
+            flush();
+        }
+    }
+    __syncthreads();
+    const uint32_t mine = ckey[threadIdx.x];
+    if (mine != 0xFFFFFFFFu) {
+        unsigned long long* b = (unsigned long long*)&hist[mine];
+        SVGR_UNROLL
+        for (int j = 0; j < 5; ++j)
+            if (csum[threadIdx.x][j]) atomicAdd(b + j, csum[threadIdx.x][j]);
+    }
+}
+
+QUANT_KERNEL void k_quant_flag(const QuantBin* __restrict__ hist, int* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * QUANT_LANES + threadIdx.x;
+    if (i < QUANT_BINS) flag[i] = hist[i].n != 0;
+}
+QUANT_KERNEL void k_quant_compact(const QuantBin* __restrict__ hist, const int* __restrict__ incl, int n_out, uint32_t* __restrict__ keys,
+                                  QuantBin* __restrict__ out) {
+    const uint32_t i = blockIdx.x * QUANT_LANES + threadIdx.x;
+    if (i >= QUANT_BINS) return;
+    const QuantBin b = hist[i];
+    if (!b.n) return;
+    const int pos = incl[i] - 1;
+    if (pos < 0 || pos >= n_out) return;
+    keys[pos] = i;
+    out[pos] = b;
+}
+
+QUANT_KERNEL void k_quant_index(const uint32_t* __restrict__ src, int rows, int cols, const uint32_t* __restrict__ pal, int n_pal, int depth,
+                                uint8_t* __restrict__ stream, uint8_t* __restrict__ indices) {
+    __shared__ uint32_t pal_x[4 * QUANT_MAX_COLORS];
+    if ((int)threadIdx.x < n_pal) quant_x(quant_canon(pal[threadIdx.x]), pal_x + 4 * threadIdx.x);
+    __syncthreads();
+    const long long c0 = ((long long)blockIdx.x * QUANT_LANES + threadIdx.x) * QUANT_RUN;
+    if (c0 >= cols) return;
+    const int n = cols - c0 >= QUANT_RUN ? QUANT_RUN : (int)(cols - c0);
+    const long long rb = quant_row_bytes(cols, depth);
+    for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
+        const uint32_t* p = src + row * cols + c0;
+        uint8_t idx[QUANT_RUN], bytes[QUANT_RUN];
+        uint32_t prev = 0;
+        SVGR_UNROLL
+        for (int k = 0; k < QUANT_RUN; ++k) {
+            idx[k] = 0;
+            if (k < n) {
+                const uint32_t c = quant_canon(p[k]);
+                if (k && c == prev) {
+                    idx[k] = idx[k - 1];
+                } else {
+                    uint32_t x[4];
+                    quant_x(c, x);
+                    idx[k] = (uint8_t)quant_nearest(pal_x, n_pal, x);
+                }
+                prev = c;
+            }
+        }
+        if (indices) {
+            SVGR_UNROLL
+            for (int k = 0; k < QUANT_RUN; ++k)
+                if (k < n) indices[row * cols + c0 + k] = idx[k];
+        }
+        if (stream) {
+            uint8_t* o = stream + row * rb;
+            if (c0 == 0) o[0] = 0;
+            quant_pack_run(idx, n, depth, bytes);
+            const int nb = (n * depth + 7) / 8;
+            o += 1 + c0 * depth / 8;
+            SVGR_UNROLL
+            for (int j = 0; j < QUANT_RUN; ++j)
+                if (j < nb) o[j] = bytes[j];
+        }
+    }
+}
+
+// Widths: a bin's count is at most 2^30 and a sum at most 2^30 * 65025 < 2^46 at the largest image image_size_ok lets in (2^30
+// pixels, 2^16 a side): the 64-bit fields cannot overflow.
+static int quant_check(const char* entry, svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t cols) {
+    if (!ctx || !src) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (!image_size_ok(rows, cols)) return fail(SVGR_E_INVALID, "%s: %lld x %lld is empty or beyond 2^16 a side, 2^30 pixels", entry, (long long)rows, (long long)cols);
+    if (src->bytes < (size_t)rows * cols * 4) return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
+    return 0;
+}
+
+static int quant_distinct_impl(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t cols, int max_colors, uint32_t* colors, int64_t* n_colors, int* overflow) {
+    static const char* entry = "svgr_quant_distinct";
+    if (int rc = quant_check(entry, ctx, src, rows, cols)) return rc;
+    if (!colors || !n_colors || !overflow) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (max_colors < 1 || max_colors > QUANT_MAX_COLORS) return fail(SVGR_E_INVALID, "%s: max_colors is 1 .. %d, not %d", entry, QUANT_MAX_COLORS, max_colors);
+    std::vector<QuantSet> host(1);
+    PassFrame f(ctx);
+    HIPCHK(enter_ctx(ctx));
+    QuantSet* set = f.scratch<QuantSet>(1);
+    if (f.err) return f.err;
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)set->slot, (int)QUANT_EMPTY, QUANT_SLOTS, f.st));
+    HIPCHK(hipMemsetAsync(&set->count, 0, 8, f.st));
+    const long long n_px = (long long)rows * cols;
+    SVGR_LAUNCH(k_quant_distinct, grid1((size_t)n_px, QUANT_BLOCK), dim3(QUANT_LANES), 0, f.st, (const uint32_t*)src->ptr, n_px, (uint32_t)max_colors, set);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(host.data(), set, sizeof(QuantSet), hipMemcpyDeviceToHost, f.st));
+    HIPCHK(hipStreamSynchronize(f.st));
+    const QuantSet& h = host[0];
+    *n_colors = 0;
+    *overflow = h.full || h.count > (uint32_t)max_colors;
+    if (*overflow) return 0;
+    int64_t n = 0;
+    for (uint32_t s = 0; s < QUANT_SLOTS; ++s)
+        if (h.slot[s] != QUANT_EMPTY) {
+            if (n == max_colors) return fail(SVGR_E_STATE, "%s: the set holds more colours than it counted", entry);
+            colors[n++] = h.slot[s];
+        }
+    if (n != (int64_t)h.count) return fail(SVGR_E_STATE, "%s: the set holds %lld colours and counted %u", entry, (long long)n, h.count);
+    std::sort(colors, colors + n);
+    *n_colors = n;
+    return 0;
+}
+
+static int quant_bins_impl(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t cols, uint32_t* keys, uint64_t* bins, int64_t cap, int64_t* n_bins) {
+    static const char* entry = "svgr_quant_bins";
+    if (int rc = quant_check(entry, ctx, src, rows, cols)) return rc;
+    if (!n_bins || cap < 0 || (cap && (!keys || !bins))) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    static_assert(sizeof(QuantBin) == 40, "five 64-bit fields");
+    int total = 0;
+    PassFrame f(ctx);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = f.st;
+    QuantBin* hist = f.scratch<QuantBin>(QUANT_BINS);
+    int* flag = f.scratch<int>(QUANT_BINS);
+    int* tops = f.scratch<int>(QUANT_BINS / DASH_S);
+    if (f.err) return f.err;
+    HIPCHK(hipMemsetAsync(hist, 0, (size_t)QUANT_BINS * sizeof(QuantBin), st));
+    const long long n_px = (long long)rows * cols;
+    const long long n_blocks = (n_px + QUANT_BLOCK - 1) / QUANT_BLOCK;
+    SVGR_LAUNCH(k_quant_bins, dim3((unsigned)std::min<long long>(n_blocks, QUANT_GROUPS)), dim3(QUANT_LANES), 0, st, (const uint32_t*)src->ptr, n_px, n_blocks, hist);
+    SVGR_LAUNCH(k_quant_flag, grid1(QUANT_BINS, QUANT_LANES), dim3(QUANT_LANES), 0, st, (const QuantBin*)hist, flag);
+    dash_scan<int, QuantSumOp>(st, flag, tops, (int)QUANT_BINS);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&total, flag + (QUANT_BINS - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total <= 0 || (long long)total > n_px) return fail(SVGR_E_STATE, "%s: %d bins for %lld pixels", entry, total, n_px);
+    *n_bins = total;
+    if (total > cap) return fail(SVGR_E_INVALID, "%s: %d bins need more room than %lld", entry, total, (long long)cap);
+    uint32_t* d_keys = f.scratch<uint32_t>((size_t)total);
+    QuantBin* d_bins = f.scratch<QuantBin>((size_t)total);
+    if (f.err) return f.err;
+    SVGR_LAUNCH(k_quant_compact, grid1(QUANT_BINS, QUANT_LANES), dim3(QUANT_LANES), 0, st, (const QuantBin*)hist, (const int*)flag, total, d_keys, d_bins);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(keys, d_keys, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bins, d_bins, (size_t)total * sizeof(QuantBin), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" {
+int svgr_quant_block(void) { return QUANT_BLOCK; }
+int svgr_quant_groups(void) { return QUANT_GROUPS; }
+int svgr_quant_distinct(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, int max_colors, uint32_t* colors, int64_t* n_colors,
+                        int* overflow) {
+    return abi_guard("svgr_quant_distinct", [&]() { return quant_distinct_impl(ctx, src_rgba8, rows, cols, max_colors, colors, n_colors, overflow); });
+}
+int svgr_quant_bins(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, uint32_t* keys, uint64_t* bins, int64_t cap, int64_t* n_bins) {
+    return abi_guard("svgr_quant_bins", [&]() { return quant_bins_impl(ctx, src_rgba8, rows, cols, keys, bins, cap, n_bins); });
+}
+int svgr_quant_index(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, const svgr_buf* palette, int n_palette, svgr_buf* out_stream,
+                     svgr_buf* out_indices) {
+    static const char* entry = "svgr_quant_index";
+    if (int rc = quant_check(entry, ctx, src_rgba8, rows, cols)) return rc;
+    if (!palette || (!out_stream && !out_indices)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (n_palette < 1 || n_palette > QUANT_MAX_COLORS) return fail(SVGR_E_INVALID, "%s: a palette has 1 .. %d entries, not %d", entry, QUANT_MAX_COLORS, n_palette);
+    const int depth = quant_depth(n_palette);
+    if (palette->bytes < (size_t)n_palette * 4 || (out_stream && out_stream->bytes < (size_t)rows * (size_t)quant_row_bytes(cols, depth)) ||
+        (out_indices && out_indices->bytes < (size_t)rows * cols))
+        return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
+    if ((out_stream && out_stream->ptr == src_rgba8->ptr) || (out_indices && out_indices->ptr == src_rgba8->ptr))
+        return fail(SVGR_E_INVALID, "%s: an output must not be the source", entry);
+    const dim3 grid((unsigned)((cols + QUANT_BLOCK - 1) / QUANT_BLOCK), (unsigned)std::min<int64_t>(rows, 65535));
+    return launch_tail(ctx, k_quant_index, grid, dim3(QUANT_LANES), 0, (const uint32_t*)src_rgba8->ptr, (int)rows, (int)cols, (const uint32_t*)palette->ptr,
+                       n_palette, depth, out_stream ? (uint8_t*)out_stream->ptr : (uint8_t*)nullptr, out_indices ? (uint8_t*)out_indices->ptr : (uint8_t*)nullptr);
+}
+}  // extern "C"

@@ -11,7 +11,10 @@ read.  Malformed input raises ValueError with the reason.
 Encoder (``encoder="device"`` of ``canvas_to_png``, ``Layer.write_png`` and ``render_svg``): the scanline filters and the
 deflate stream are made on the device (``svgr_png_filter``, ``svgr_deflate``; csrc/svgr_png.h and csrc/svgr_deflate.h have the
 definitions) from the RGBA8 bytes that are already there; only the compressed bytes come back, and the container -- signature,
-IHDR, one IDAT, IEND, the CRCs -- is written here."""
+IHDR, one IDAT, IEND, the CRCs -- is written here.
+
+Indexed output (``palette=`` of the same three): the colour quantiser (quant.py, ``svgr_quant_*``) leaves a palette and the packed
+index scanlines on the device; either encoder compresses them, and the container gains PLTE and tRNS."""
 from __future__ import annotations
 
 import struct
@@ -263,3 +266,75 @@ def encoder_arguments(encoder, level, threads, filter, huffman):
     _filter_number("adaptive" if filter is None else filter)
     _huffman_number("dynamic" if huffman is None else huffman)
     return "device", filter, huffman
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# indexed output (colour type 3): the quantiser's row stream in a PLTE / tRNS container
+# ---------------------------------------------------------------------------------------------------------------------
+def palette_argument(palette, encoder, filter):
+    """``palette`` of ``canvas_to_png`` and its callers, checked: None (8-bit RGBA as before) or the largest number of entries.
+    Indexed rows carry filter 0 only: with a palette the device encoder's ``filter`` is None or "none"."""
+    from . import quant  # noqa: PLC0415
+
+    n = quant.palette_argument(palette)
+    if n is not None and encoder == "device" and filter not in (None, "none"):
+        raise ValueError(f'indexed PNG rows are written with filter "none"; filter {filter!r} does not go with palette')
+    return n
+
+
+def write_indexed_container(output, width: int, height: int, palette: np.ndarray, idat: bytes):
+    """The file around a zlib stream of index scanlines: signature, IHDR (colour type 3, the depth of the palette's length), PLTE,
+    tRNS unless every entry is opaque, one IDAT, IEND."""
+    from . import quant  # noqa: PLC0415
+
+    palette = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 4)
+    if not 1 <= len(palette) <= 256:
+        raise ValueError(f"a PNG palette has 1 to 256 entries, not {len(palette)}")
+
+    def pack(tag: bytes, data: bytes) -> None:
+        output.write(struct.pack("!I", len(data)))
+        output.write(tag)
+        output.write(data)
+        output.write(struct.pack("!I", 0xFFFFFFFF & zlib.crc32(data, zlib.crc32(tag))))
+
+    output.write(SIGNATURE)
+    pack(b"IHDR", struct.pack("!2I5B", width, height, quant.depth_of(len(palette)), 3, 0, 0, 0))
+    pack(b"PLTE", palette[:, :3].tobytes())
+    alphas = quant.trns(palette)
+    if alphas:
+        pack(b"tRNS", alphas)
+    pack(b"IDAT", idat)
+    pack(b"IEND", b"")
+    return output
+
+
+def encode_indexed(rgba8, rows: int, cols: int, output, max_colors: int, *, encoder: str = "host", level=9, threads=1, huffman=None,
+                   refine: int = 3):
+    """``canvas_to_png(palette=...)``: the colour type 3 PNG of 8-bit RGBA pixels (an array or a DeviceBuffer) into ``output``
+    (default a new BytesIO), which is returned.  The palette and the packed scanlines are made on the device (quant.py); the
+    "device" encoder deflates them there, the "host" encoder downloads them -- a byte or less per pixel -- for zlib."""
+    import io
+
+    from . import quant  # noqa: PLC0415
+
+    code = _huffman_number("dynamic" if huffman is None else huffman) if encoder == "device" else None
+    if rows <= 0 or cols <= 0:
+        raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+    ctx = _abi.Context.get()
+    if not isinstance(rgba8, _abi.DeviceBuffer):
+        rgba8 = ctx.from_host(np.ascontiguousarray(rgba8, dtype=np.uint8))
+    palette = quant.palette_of(rgba8, int(rows), int(cols), max_colors, refine)
+    stream, _ = _abi.quant_index(ctx, rgba8, int(rows), int(cols), palette, stream=True, indices=False)
+    n_bytes = int(rows) * (1 + (int(cols) * quant.depth_of(len(palette)) + 7) // 8)
+    if encoder == "device":
+        idat = _abi.deflate(ctx, stream, n_bytes, code)
+    else:
+        raw = stream.download((n_bytes,), np.uint8).tobytes()
+        if threads > 1:
+            from .layer import _deflate_parallel  # noqa: PLC0415
+
+            idat = _deflate_parallel(raw, level, threads)
+        else:
+            comp = zlib.compressobj(level=level)
+            idat = comp.compress(raw) + comp.flush()
+    return write_indexed_container(io.BytesIO() if output is None else output, int(cols), int(rows), palette, idat)
