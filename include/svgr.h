@@ -45,7 +45,8 @@ extern "C" {
  *    svgr_jpeg_entropy_encode and svgr_jpeg_symbol_counts added (JPEG output); svgr_png_filter, svgr_deflate and
  *    svgr_deflate_chunk added (the device PNG encoder); svgr_layer_to_tensor, svgr_tensor_to_layer, svgr_tensor_block,
  *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output); svgr_quant_distinct,
- *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output) */
+ *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output); svgr_quant_dither,
+ *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1022,6 +1023,20 @@ int svgr_quant_index(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int
                      svgr_buf* out_stream, svgr_buf* out_indices);
 int svgr_quant_block(void);
 int svgr_quant_groups(void);
+
+/* Dithering for indexed PNG output (dither= of Layer.write_png and quantize; csrc/svgr_dither.h has the arithmetic).
+ * svgr_quant_dither: svgr_quant_index -- the same buffers, checks and outputs -- with every pixel matched at a moved target.
+ *   mode 1, ordered: the colour coordinates of X move by off = (((2 B + 1) h) >> 7) - (h >> 1), B the 8 x 8 Bayer matrix at
+ *   (row & 7, col & 7) and h = amp * a / 255; `amp` (0 .. 65025) belongs to the palette and is computed by the caller.  Enqueued, no
+ *   wait.  mode 2, diffusion: Floyd-Steinberg, every row left to right, t = clamp(x + floor((acc + 8) / 16)) with acc the 7, 3, 5,
+ *   1 weighted errors of the pixels to the left and above, in int32; a pixel with a == 0 takes the entry nearest to X = 0 and
+ *   passes no error on; `amp` is not used.  One launch per front of tiles (block + 2 * strip), in stream order; waits for the
+ *   device.  Any other mode is SVGR_E_INVALID.
+ * svgr_dither_tile_rows, svgr_dither_tile_cols: a diffusion tile's rows (a strip) and columns (a block): its launch seams. */
+int svgr_quant_dither(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, const svgr_buf* palette, int n_palette, int mode,
+                      int amp, svgr_buf* out_stream, svgr_buf* out_indices);
+int svgr_dither_tile_rows(void);
+int svgr_dither_tile_cols(void);
 
 #ifdef __cplusplus
 }

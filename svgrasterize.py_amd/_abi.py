@@ -228,6 +228,9 @@ _PROTOS = {
     "svgr_quant_index": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, _P, _P]),
     "svgr_quant_block": (C.c_int, []),
     "svgr_quant_groups": (C.c_int, []),
+    "svgr_quant_dither": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "svgr_dither_tile_rows": (C.c_int, []),
+    "svgr_dither_tile_cols": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -1216,16 +1219,42 @@ def quant_bins(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int):
     return keys[:n.value].copy(), bins[:n.value].copy()
 
 
-def quant_index(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, palette: np.ndarray, stream: bool = True, indices: bool = False):
-    """svgr_quant_index: ``(stream, indices)``, each a DeviceBuffer or None: the packed scanlines (filter bytes included) and
-    the plain byte indices of the image under `palette`, an (n, 4) uint8 array of RGBA entries."""
+def _quant_index_buffers(ctx: Context, rows: int, cols: int, palette: np.ndarray, stream: bool, indices: bool):
+    """(entries, palette on the device, stream buffer or None, index buffer or None) of svgr_quant_index and svgr_quant_dither."""
     pal = np.ascontiguousarray(palette, dtype=np.uint8).reshape(-1, 4)
     n = len(pal)
     depth = 1 if n <= 2 else 2 if n <= 4 else 4 if n <= 16 else 8
     d_pal = ctx.from_host(pal) if n else ctx.alloc(4)
     out_s = ctx.alloc(max(rows, 1) * (1 + (max(cols, 1) * depth + 7) // 8)) if stream else None
     out_i = ctx.alloc(max(rows * cols, 1)) if indices else None
+    return n, d_pal, out_s, out_i
+
+
+def quant_index(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, palette: np.ndarray, stream: bool = True, indices: bool = False):
+    """svgr_quant_index: ``(stream, indices)``, each a DeviceBuffer or None: the packed scanlines (filter bytes included) and
+    the plain byte indices of the image under `palette`, an (n, 4) uint8 array of RGBA entries."""
+    n, d_pal, out_s, out_i = _quant_index_buffers(ctx, rows, cols, palette, stream, indices)
     _check(ctx.lib.svgr_quant_index(ctx.handle, rgba8.handle, rows, cols, d_pal.handle, n, out_s.handle if stream else None,
                                     out_i.handle if indices else None))
+    ctx.sync()   # (the palette's block is released when this returns)
+    return out_s, out_i
+
+
+DITHER_MODES = {"ordered": 1, "diffusion": 2}
+
+
+def dither_tile() -> tuple:
+    """(rows, columns) of a tile of the diffusion kernel (svgr_dither_tile_rows, svgr_dither_tile_cols): its launch seams."""
+    lib = load_library()
+    return int(lib.svgr_dither_tile_rows()), int(lib.svgr_dither_tile_cols())
+
+
+def quant_dither(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, palette: np.ndarray, mode, amp: int = 0, stream: bool = True,
+                 indices: bool = False):
+    """svgr_quant_dither: ``quant_index`` with dithering: ``mode`` is "ordered" (with ``amp``, the palette's amplitude:
+    ``quant.ordered_amplitude``), "diffusion", or the entry's own number."""
+    n, d_pal, out_s, out_i = _quant_index_buffers(ctx, rows, cols, palette, stream, indices)
+    _check(ctx.lib.svgr_quant_dither(ctx.handle, rgba8.handle, rows, cols, d_pal.handle, n, DITHER_MODES.get(mode, mode), int(amp),
+                                     out_s.handle if stream else None, out_i.handle if indices else None))
     ctx.sync()   # (the palette's block is released when this returns)
     return out_s, out_i

@@ -10405,3 +10405,239 @@ int svgr_quant_index(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int
                        n_palette, depth, out_stream ? (uint8_t*)out_stream->ptr : (uint8_t*)nullptr, out_indices ? (uint8_t*)out_indices->ptr : (uint8_t*)nullptr);
 }
 }  // extern "C"
+
+// ======================================================================================
+// Dithering for indexed PNG output (svgr_quant_dither): svgr_dither.h has the arithmetic, DESIGN.md 7u the definitions.
+//
+//   k_quant_dither_ordered   k_quant_index with the Bayer offset added to the pixel's coordinates: a map over the pixels.  The
+//                            target, not the pixel, decides whether a lane may reuse its previous pixel's entry
+//   k_quant_dither_diffuse   Floyd-Steinberg is sequential as written: (r, c) needs (r, c-1), (r-1, c-1), (r-1, c), (r-1, c+1), so
+//                            the pixels with equal c + 2 r are independent.  A tile is a strip of DITHER_S rows, skewed two
+//                            columns to the left per row into a parallelogram DITHER_W wide: at step j every row works on its j-th
+//                            pixel, and what it needs from the row above was made at the steps j-1, j-2 and j-3.  One workgroup
+//                            takes one tile, DITHER_L lanes a pixel: each lane searches its slice of the palette (read from LDS
+//                            once and held in registers: it is the same for every pixel of the tile), and a
+//                            butterfly of shuffles takes the minimum of (D << 8 | index) -- D < 2^36, so the one 64-bit compare
+//                            orders by D and then by index, the sequential loop's tie rule.  The errors of the tile's rows live
+//                            in LDS.  A tile needs its left neighbour and, for its first row, the two tiles above it and above to
+//                            the right (DITHER_W > 2 (DITHER_S - 1) keeps it to those): tiles with equal block + 2 strip share a
+//                            launch, the launches follow each other on the stream, and no workgroup ever waits for another.  What
+//                            crosses a tile's edge goes through memory: the errors of a strip's last row (one buffer per strip
+//                            parity, the pixel at c+1 included) and the last three errors of every row of a tile
+// ======================================================================================
+#include "svgr_dither.h"
+
+QUANT_KERNEL void k_quant_dither_ordered(const uint32_t* __restrict__ src, int rows, int cols, const uint32_t* __restrict__ pal, int n_pal, int depth,
+                                         uint32_t amp, uint8_t* __restrict__ stream, uint8_t* __restrict__ indices) {
+    __shared__ uint32_t pal_x[4 * QUANT_MAX_COLORS];
+    if ((int)threadIdx.x < n_pal) quant_x(quant_canon(pal[threadIdx.x]), pal_x + 4 * threadIdx.x);
+    __syncthreads();
+    const long long c0 = ((long long)blockIdx.x * QUANT_LANES + threadIdx.x) * QUANT_RUN;
+    if (c0 >= cols) return;
+    const int n = cols - c0 >= QUANT_RUN ? QUANT_RUN : (int)(cols - c0);
+    const long long rb = quant_row_bytes(cols, depth);
+    for (long long row = blockIdx.y; row < rows; row += gridDim.y) {
+        const uint32_t* p = src + row * cols + c0;
+        uint8_t idx[QUANT_RUN], bytes[QUANT_RUN];
+        uint32_t prev[4] = {0, 0, 0, 0};
+        SVGR_UNROLL
+        for (int k = 0; k < QUANT_RUN; ++k) {
+            idx[k] = 0;
+            if (k < n) {
+                const uint32_t c = quant_canon(p[k]);
+                uint32_t x[4], t[4];
+                quant_x(c, x);
+                dither_ordered_target(x, c >> 24, amp, row, c0 + k, t);
+                if (k && t[0] == prev[0] && t[1] == prev[1] && t[2] == prev[2] && t[3] == prev[3]) idx[k] = idx[k - 1];
+                else idx[k] = (uint8_t)quant_nearest(pal_x, n_pal, t);
+                SVGR_UNROLL
+                for (int j = 0; j < 4; ++j) prev[j] = t[j];
+            }
+        }
+        if (indices) {
+            SVGR_UNROLL
+            for (int k = 0; k < QUANT_RUN; ++k)
+                if (k < n) indices[row * cols + c0 + k] = idx[k];
+        }
+        if (stream) {
+            uint8_t* o = stream + row * rb;
+            if (c0 == 0) o[0] = 0;
+            quant_pack_run(idx, n, depth, bytes);
+            const int nb = (n * depth + 7) / 8;
+            o += 1 + c0 * depth / 8;
+            SVGR_UNROLL
+            for (int j = 0; j < QUANT_RUN; ++j)
+                if (j < nb) o[j] = bytes[j];
+        }
+    }
+}
+
+constexpr int DITHER_S = 16, DITHER_W = 32, DITHER_L = QUANT_LANES / DITHER_S, DITHER_EDGE = 3;
+static_assert(DITHER_W > 2 * (DITHER_S - 1), "a tile's first row reaches no further than the tile above to the right");
+static_assert(DITHER_L <= 64 && 64 % DITHER_L == 0 && (DITHER_L & (DITHER_L - 1)) == 0, "a pixel's lanes are one aligned group of a wave");
+static_assert(DITHER_S * DITHER_W == 2 * QUANT_LANES, "the load and store phases give a lane two pixels");
+
+// The nearest entry to the target (t0, t1, t2, t3) over the group's DITHER_L lanes; every lane of the group gets the result.  A lane
+// searches the same entries for every pixel of the tile -- l, l + DITHER_L, ... (l: its place in the group) -- and holds them in
+// registers: `mine`, the first n_mine of which exist in some lane.  quant_dist, a coordinate at a time on the entry's four words.
+constexpr int DITHER_SLICE = QUANT_MAX_COLORS / DITHER_L;
+__device__ __forceinline__ int dither_group_nearest(const uint4 (&mine)[DITHER_SLICE], int n_mine, int n_pal, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, int l) {
+    unsigned long long best = ~0ull;
+    SVGR_UNROLL
+    for (int q = 0; q < DITHER_SLICE; ++q) {
+        if (q < n_mine) {   // (the same in every lane)
+            const uint4 y = mine[q];
+            const uint32_t d0 = t0 > y.x ? t0 - y.x : y.x - t0, d1 = t1 > y.y ? t1 - y.y : y.y - t1, d2 = t2 > y.z ? t2 - y.z : y.z - t2,
+                           d3 = t3 > y.w ? t3 - y.w : y.w - t3;   // (each <= 65025: its square fits 32 bits)
+            const unsigned long long d = (unsigned long long)(d0 * d0) + (unsigned long long)(d1 * d1) + (unsigned long long)(d2 * d2) + (unsigned long long)(d3 * d3);
+            const unsigned long long key = l + q * DITHER_L < n_pal ? d << 8 | (unsigned)(l + q * DITHER_L) : ~0ull;
+            best = key < best ? key : best;
+        }
+    }
+    SVGR_UNROLL
+    for (int m = DITHER_L / 2; m; m >>= 1) {
+        const unsigned long long other = __shfl_xor(best, m, DITHER_L);
+        best = other < best ? other : best;
+    }
+    return (int)(best & 255u);
+}
+
+// The tiles (strip, block) with block + 2 strip == front, strip = strip0 + blockIdx.x.  row_err: 2 * cols errors, the last row of a
+// strip at [(strip & 1) * cols + c]; col_err: per image row DITHER_EDGE errors, those of the row's last pixels in the tile that
+// has just been through it.
+QUANT_KERNEL void k_quant_dither_diffuse(const uint32_t* __restrict__ src, int rows, int cols, const uint32_t* __restrict__ pal, int n_pal, int depth,
+                                         int front, int strip0, int4* __restrict__ row_err, int4* __restrict__ col_err, uint8_t* __restrict__ stream,
+                                         uint8_t* __restrict__ indices) {
+    __shared__ uint4 pal_x[QUANT_MAX_COLORS];
+    __shared__ int4 err[DITHER_S + 1][DITHER_W + DITHER_EDGE];   // [1 + row][EDGE + step]; row -1 is the strip above
+    __shared__ uint32_t px_s[DITHER_S][DITHER_W];
+    __shared__ uint8_t idx_s[DITHER_S][DITHER_W];
+    const int tid = (int)threadIdx.x, strip = strip0 + (int)blockIdx.x, block = front - 2 * strip;
+    const int row0 = strip * DITHER_S, col0 = block * DITHER_W;   // the tile's row i begins at the column col0 - 2 i
+    if (tid < n_pal) {
+        uint32_t y[4];
+        quant_x(quant_canon(pal[tid]), y);
+        pal_x[tid] = make_uint4(y[0], y[1], y[2], y[3]);
+    }
+    SVGR_UNROLL
+    for (int p = tid; p < DITHER_S * DITHER_W; p += QUANT_LANES) {
+        const int i = p / DITHER_W, j = p % DITHER_W, r = row0 + i, c = col0 - 2 * i + j;
+        px_s[i][j] = (r < rows && c >= 0 && c < cols) ? quant_canon(src[(long long)r * cols + c]) : 0u;   // (outside: no error, no store)
+    }
+    if (tid < DITHER_W + DITHER_EDGE) {   // the row above: step j' of it is the column col0 + j' + 2
+        const int c = col0 - 1 + tid;
+        int4 e = make_int4(0, 0, 0, 0);
+        if (strip > 0 && c >= 0 && c < cols) e = row_err[(long long)((strip - 1) & 1) * cols + c];
+        err[0][tid] = e;
+    }
+    if (tid < DITHER_S * DITHER_EDGE) {
+        const int i = tid / DITHER_EDGE, q = tid % DITHER_EDGE;
+        int4 e = make_int4(0, 0, 0, 0);
+        if (block > 0) e = col_err[(long long)(row0 + i) * DITHER_EDGE + q];
+        err[1 + i][q] = e;
+    }
+    __syncthreads();
+    const int i = tid / DITHER_L, l = tid % DITHER_L;
+    uint4 mine[DITHER_SLICE];
+    const int n_mine = (n_pal + DITHER_L - 1) / DITHER_L;
+    SVGR_UNROLL
+    for (int q = 0; q < DITHER_SLICE; ++q) mine[q] = pal_x[l + q * DITHER_L];   // (beyond n_pal: read, never used)
+    const int clear = dither_group_nearest(mine, n_mine, n_pal, 0u, 0u, 0u, 0u, l);
+    for (int j = 0; j < DITHER_W; ++j) {
+        const uint32_t px = px_s[i][j];
+        // errors: of this row's last pixel; of the row above at the columns c + 1, c, c - 1, which it had at the steps j - 1, j - 2, j - 3
+        const int4 left = err[1 + i][DITHER_EDGE + j - 1], u1 = err[i][DITHER_EDGE + j - 1], u2 = err[i][DITHER_EDGE + j - 2], u3 = err[i][DITHER_EDGE + j - 3];
+        const int32_t acc[4] = {7 * left.x + 3 * u1.x + 5 * u2.x + u3.x, 7 * left.y + 3 * u1.y + 5 * u2.y + u3.y,
+                                7 * left.z + 3 * u1.z + 5 * u2.z + u3.z, 7 * left.w + 3 * u1.w + 5 * u2.w + u3.w};
+        uint32_t x[4], t[4];
+        quant_x(px, x);
+        dither_diffusion_target(x, acc, t);
+        const int k = dither_group_nearest(mine, n_mine, n_pal, t[0], t[1], t[2], t[3], l);   // (every lane takes part, whatever its pixel: the shuffles stay whole)
+        if (l == 0) {
+            const uint4 y = pal_x[k];
+            err[1 + i][DITHER_EDGE + j] = px ? make_int4((int)t[0] - (int)y.x, (int)t[1] - (int)y.y, (int)t[2] - (int)y.z, (int)t[3] - (int)y.w) : make_int4(0, 0, 0, 0);
+            idx_s[i][j] = (uint8_t)(px ? k : clear);
+        }
+        __syncthreads();   // (step j + 1 reads what step j wrote, and writes where nobody reads before the next barrier)
+    }
+    // what the tiles to the right and below need
+    if (tid < DITHER_S * DITHER_EDGE) {
+        const int ii = tid / DITHER_EDGE, q = tid % DITHER_EDGE;
+        col_err[(long long)(row0 + ii) * DITHER_EDGE + q] = err[1 + ii][DITHER_W + q];   // (it has a strip's rows for every strip)
+    }
+    if (tid < DITHER_W) {
+        const int c = col0 - 2 * (DITHER_S - 1) + tid;
+        if (c >= 0 && c < cols) row_err[(long long)(strip & 1) * cols + c] = err[DITHER_S][DITHER_EDGE + tid];
+    }
+    if (indices) {
+        SVGR_UNROLL
+        for (int p = tid; p < DITHER_S * DITHER_W; p += QUANT_LANES) {
+            const int ii = p / DITHER_W, j = p % DITHER_W, r = row0 + ii, c = col0 - 2 * ii + j;
+            if (r < rows && c >= 0 && c < cols) indices[(long long)r * cols + c] = idx_s[ii][j];
+        }
+    }
+    if (stream && row0 + i < rows) {
+        // the row's bytes that hold a pixel of this tile; a byte shared with the tile to the left or right (another launch, earlier
+        // or later on the stream) gets this tile's bits added: the stream was cleared before the first launch
+        const int first = col0 - 2 * i, c_lo = first > 0 ? first : 0, c_hi = first + DITHER_W - 1 < cols - 1 ? first + DITHER_W - 1 : cols - 1;
+        const int per = 8 / depth;
+        uint8_t* o = stream + (long long)(row0 + i) * quant_row_bytes(cols, depth) + 1;
+        if (c_lo <= c_hi)
+            for (int q = c_lo / per + l; q <= c_hi / per; q += DITHER_L) {
+                uint32_t v = 0;
+                for (int k = 0; k < per; ++k) {
+                    const int c = q * per + k;
+                    if (c >= c_lo && c <= c_hi) v |= (uint32_t)idx_s[i][c - first] << (8 - depth * (k + 1));
+                }
+                o[q] = depth == 8 ? (uint8_t)v : (uint8_t)(o[q] | v);
+            }
+    }
+}
+
+static int quant_dither_impl(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t cols, const svgr_buf* palette, int n_palette, int mode, int amp,
+                             svgr_buf* out_stream, svgr_buf* out_indices) {
+    static const char* entry = "svgr_quant_dither";
+    if (int rc = quant_check(entry, ctx, src, rows, cols)) return rc;
+    if (!palette || (!out_stream && !out_indices)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (mode != DITHER_ORDERED && mode != DITHER_DIFFUSION) return fail(SVGR_E_INVALID, "%s: mode is 1 (ordered) or 2 (diffusion), not %d", entry, mode);
+    if (amp < 0 || amp > DITHER_X_MAX) return fail(SVGR_E_INVALID, "%s: the amplitude is 0 .. %d, not %d", entry, (int)DITHER_X_MAX, amp);
+    if (n_palette < 1 || n_palette > QUANT_MAX_COLORS) return fail(SVGR_E_INVALID, "%s: a palette has 1 .. %d entries, not %d", entry, QUANT_MAX_COLORS, n_palette);
+    const int depth = quant_depth(n_palette);
+    const size_t stream_bytes = (size_t)rows * (size_t)quant_row_bytes(cols, depth);
+    if (palette->bytes < (size_t)n_palette * 4 || (out_stream && out_stream->bytes < stream_bytes) || (out_indices && out_indices->bytes < (size_t)rows * cols))
+        return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
+    if ((out_stream && out_stream->ptr == src->ptr) || (out_indices && out_indices->ptr == src->ptr))
+        return fail(SVGR_E_INVALID, "%s: an output must not be the source", entry);
+    uint8_t* stream = out_stream ? (uint8_t*)out_stream->ptr : (uint8_t*)nullptr;
+    uint8_t* indices = out_indices ? (uint8_t*)out_indices->ptr : (uint8_t*)nullptr;
+    if (mode == DITHER_ORDERED) {
+        const dim3 grid((unsigned)((cols + QUANT_BLOCK - 1) / QUANT_BLOCK), (unsigned)std::min<int64_t>(rows, 65535));
+        return launch_tail(ctx, k_quant_dither_ordered, grid, dim3(QUANT_LANES), 0, (const uint32_t*)src->ptr, (int)rows, (int)cols, (const uint32_t*)palette->ptr,
+                           n_palette, depth, (uint32_t)amp, stream, indices);
+    }
+    // the blocks cover the last row of a strip, which begins 2 (DITHER_S - 1) columns to the left of the first
+    const int strips = (int)((rows + DITHER_S - 1) / DITHER_S), blocks = (int)((cols + 2 * (DITHER_S - 1) + DITHER_W - 1) / DITHER_W);
+    PassFrame f(ctx);
+    HIPCHK(enter_ctx(ctx));
+    int4* row_err = f.scratch<int4>(2 * (size_t)cols);
+    int4* col_err = f.scratch<int4>((size_t)strips * DITHER_S * DITHER_EDGE);
+    if (f.err) return f.err;
+    if (stream) HIPCHK(hipMemsetAsync(stream, 0, stream_bytes, f.st));
+    for (int front = 0; front <= blocks - 1 + 2 * (strips - 1); ++front) {
+        const int lo = front - (blocks - 1) > 0 ? (front - (blocks - 1) + 1) / 2 : 0, hi = std::min(strips - 1, front / 2);
+        if (lo > hi) continue;
+        SVGR_LAUNCH(k_quant_dither_diffuse, dim3((unsigned)(hi - lo + 1)), dim3(QUANT_LANES), 0, f.st, (const uint32_t*)src->ptr, (int)rows, (int)cols,
+                    (const uint32_t*)palette->ptr, n_palette, depth, front, lo, row_err, col_err, stream, indices);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;   // (the frame waits for the stream before its scratch goes)
+}
+
+extern "C" {
+int svgr_dither_tile_rows(void) { return DITHER_S; }
+int svgr_dither_tile_cols(void) { return DITHER_W; }
+int svgr_quant_dither(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int64_t cols, const svgr_buf* palette, int n_palette, int mode, int amp,
+                      svgr_buf* out_stream, svgr_buf* out_indices) {
+    return abi_guard("svgr_quant_dither", [&]() { return quant_dither_impl(ctx, src_rgba8, rows, cols, palette, n_palette, mode, amp, out_stream, out_indices); });
+}
+}  // extern "C"

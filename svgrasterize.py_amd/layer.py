@@ -688,22 +688,24 @@ class Layer:
         out, rows, cols = self._to_rgba8_device()
         return out.download((rows, cols, 4), np.uint8)
 
-    def write_png(self, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None):
+    def write_png(self, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None):
         """PNG of the layer (Layer.write_png, S:209-213): 8-bit RGBA, filter 0, one IDAT -- byte-identical to the
         reference's file at the reference's zlib level 9 (``level``, default 9, trades size for speed; ``threads``, default 1,
         compresses in parallel pieces; the pixels are the same).  ``encoder="device"`` filters and compresses on the device
         instead (``canvas_to_png`` has the details): the bytes go from the 8-bit conversion straight into the filter kernel
         and only the compressed stream crosses PCIe.  It takes ``filter`` and ``huffman`` in place of ``level`` and
         ``threads``.  ``palette`` (True, or the largest number of entries, 2 .. 256) writes an indexed file instead: the colours
-        are quantised on the device (``quantize``) and only the index rows reach either encoder."""
+        are quantised on the device (``quantize``) and only the index rows reach either encoder; ``dither`` ("ordered" or
+        "diffusion"; None and "none": no dithering) goes with it."""
         from . import png  # noqa: PLC0415
 
         args = png.encoder_arguments(encoder, level, threads, filter, huffman)
         max_colors = png.palette_argument(palette, args[0], filter)
+        dither = png.dither_argument(dither, max_colors)
         if max_colors is not None:
             buf, rows, cols = self._to_rgba8_device()
             kw = {"huffman": huffman} if args[0] == "device" else {"level": args[1], "threads": args[2]}
-            return png.encode_indexed(buf, rows, cols, output, max_colors, encoder=args[0], **kw)
+            return png.encode_indexed(buf, rows, cols, output, max_colors, encoder=args[0], dither=dither, **kw)
         if args[0] == "device":
             buf, rows, cols = self._to_rgba8_device()
             return png.encode_rgba8(buf, rows, cols, output, filter, huffman)
@@ -800,7 +802,7 @@ def _deflate_parallel(raw: bytes, level: int, threads: int) -> bytes:
     return bytes([cmf, flg]) + b"".join(parts) + (zlib.adler32(raw) & 0xFFFFFFFF).to_bytes(4, "big")
 
 
-def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None):
+def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None):
     """(height, width, 4) -> PNG (canvas_to_png, S:249-274).  ``canvas`` is either the uint8 array of
     ``Layer.to_rgba8`` or float RGBA in [0, 1] (quantised like the reference: ``np.round(canvas * 255)``).
     ``level`` (default 9) is zlib's; ``threads`` (default 1) > 1 compresses the scanlines in parallel pieces: same pixels, a
@@ -815,10 +817,15 @@ def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str
 
     ``palette`` (beyond the reference; None and False: as above) writes an indexed file -- colour type 3 with PLTE, tRNS where an
     entry is not opaque, one IDAT: True allows 256 entries, an int from 2 to 256 that many.  The pixels are uploaded and
-    quantised on the device (``quantize``: exact when the image has no more colours than that, a median cut otherwise; no
-    dithering), the index rows are packed there at the smallest depth of 1, 2, 4, 8 that holds the palette, with filter 0.
+    quantised on the device (``quantize``: exact when the image has no more colours than that, a median cut otherwise), the
+    index rows are packed there at the smallest depth of 1, 2, 4, 8 that holds the palette, with filter 0.
     ``encoder="host"`` downloads the rows and honours ``level`` and ``threads``; ``encoder="device"`` deflates them on the
-    device, honours ``huffman``, and takes no ``filter`` but None or "none" (ValueError)."""
+    device, honours ``huffman``, and takes no ``filter`` but None or "none" (ValueError).
+
+    ``dither`` (with ``palette`` only; None and "none": every pixel takes its nearest entry) dithers the median cut's image on
+    the device: "ordered" with the 8 x 8 Bayer matrix, "diffusion" with Floyd-Steinberg error diffusion (``quantize`` has the
+    details).  The palette and the container stay as they are, only the indices change; an image kept exactly is not dithered.
+    An unknown word is a ValueError, anything but a string or None a TypeError, a dither without ``palette`` a ValueError."""
     import io
     import zlib
 
@@ -826,6 +833,7 @@ def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str
 
     args = png.encoder_arguments(encoder, level, threads, filter, huffman)
     max_colors = png.palette_argument(palette, args[0], filter)
+    dither = png.dither_argument(dither, max_colors)
     canvas = np.asarray(canvas)
     if canvas.dtype != np.uint8:
         canvas = np.round(canvas * 255.0).astype(np.uint8)
@@ -834,7 +842,7 @@ def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str
     height, width, _ = canvas.shape
     if max_colors is not None:
         kw = {"huffman": huffman} if args[0] == "device" else {"level": args[1], "threads": args[2]}
-        return png.encode_indexed(canvas, height, width, output, max_colors, encoder=args[0], **kw)
+        return png.encode_indexed(canvas, height, width, output, max_colors, encoder=args[0], dither=dither, **kw)
     if args[0] == "device":
         return png.encode_rgba8(canvas, height, width, output, filter, huffman)
     _, level, threads = args

@@ -14,7 +14,8 @@ definitions) from the RGBA8 bytes that are already there; only the compressed by
 IHDR, one IDAT, IEND, the CRCs -- is written here.
 
 Indexed output (``palette=`` of the same three): the colour quantiser (quant.py, ``svgr_quant_*``) leaves a palette and the packed
-index scanlines on the device; either encoder compresses them, and the container gains PLTE and tRNS."""
+index scanlines on the device, dithered if ``dither=`` says so; either encoder compresses them, and the container gains PLTE and
+tRNS."""
 from __future__ import annotations
 
 import struct
@@ -282,6 +283,14 @@ def palette_argument(palette, encoder, filter):
     return n
 
 
+def dither_argument(dither, max_colors):
+    """``dither`` of the same callers, checked, next to what ``palette_argument`` made of their ``palette``: None, "ordered" or
+    "diffusion"; a dither without a palette is a ValueError."""
+    from . import quant  # noqa: PLC0415
+
+    return quant.dither_argument(dither, max_colors is not None)
+
+
 def write_indexed_container(output, width: int, height: int, palette: np.ndarray, idat: bytes):
     """The file around a zlib stream of index scanlines: signature, IHDR (colour type 3, the depth of the palette's length), PLTE,
     tRNS unless every entry is opaque, one IDAT, IEND."""
@@ -309,10 +318,11 @@ def write_indexed_container(output, width: int, height: int, palette: np.ndarray
 
 
 def encode_indexed(rgba8, rows: int, cols: int, output, max_colors: int, *, encoder: str = "host", level=9, threads=1, huffman=None,
-                   refine: int = 3):
+                   refine: int = 3, dither=None):
     """``canvas_to_png(palette=...)``: the colour type 3 PNG of 8-bit RGBA pixels (an array or a DeviceBuffer) into ``output``
-    (default a new BytesIO), which is returned.  The palette and the packed scanlines are made on the device (quant.py); the
-    "device" encoder deflates them there, the "host" encoder downloads them -- a byte or less per pixel -- for zlib."""
+    (default a new BytesIO), which is returned.  The palette and the packed scanlines are made on the device (quant.py), dithered
+    as ``dither`` (checked by ``quant.dither_argument``) says; the "device" encoder deflates them there, the "host" encoder
+    downloads them -- a byte or less per pixel -- for zlib."""
     import io
 
     from . import quant  # noqa: PLC0415
@@ -323,8 +333,7 @@ def encode_indexed(rgba8, rows: int, cols: int, output, max_colors: int, *, enco
     ctx = _abi.Context.get()
     if not isinstance(rgba8, _abi.DeviceBuffer):
         rgba8 = ctx.from_host(np.ascontiguousarray(rgba8, dtype=np.uint8))
-    palette = quant.palette_of(rgba8, int(rows), int(cols), max_colors, refine)
-    stream, _ = _abi.quant_index(ctx, rgba8, int(rows), int(cols), palette, stream=True, indices=False)
+    palette, stream, _ = quant.index_rows(rgba8, int(rows), int(cols), max_colors, refine, dither, stream=True, indices=False)
     n_bytes = int(rows) * (1 + (int(cols) * quant.depth_of(len(palette)) + 7) // 8)
     if encoder == "device":
         idat = _abi.deflate(ctx, stream, n_bytes, code)

@@ -12,8 +12,17 @@ built here, on the host, over the bins -- thousands of them, not millions of pix
            centroids rounded back to RGBA8, duplicates removed
   order    ascending (a, r, g, b): the entries that need a tRNS byte come first
 
-No dithering, no perceptual or gamma-aware metric."""
+Dithering (``dither=``; csrc/svgr_dither.h) changes the indices only, never the palette, and only on the lossy
+route -- an image the palette holds exactly is left alone:
+
+  ordered    the colour coordinates of X move by an offset from the 8 x 8 Bayer matrix, scaled by ``ordered_amplitude`` of the
+             palette and the pixel's alpha, before the nearest entry is taken
+  diffusion  Floyd-Steinberg, every row left to right, the error of a pixel being its target minus its entry in X
+
+No perceptual or gamma-aware metric."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -49,6 +58,39 @@ def palette_argument(palette):
     if palette is True:
         return MAX_COLORS
     return check_max_colors(palette, "palette")
+
+
+DITHER_MODES = ("none", "ordered", "diffusion")
+
+
+def dither_argument(dither, with_palette: bool = True):
+    """``dither`` of ``quantize``, ``write_png`` and its callers, checked: None (None and "none": every pixel takes its nearest
+    entry), "ordered" or "diffusion".  ``with_palette`` False: the call writes no indexed file, and there is nothing to dither."""
+    if dither is None:
+        return None
+    if not isinstance(dither, str):
+        raise TypeError(f'dither is None, "none", "ordered" or "diffusion", not {dither!r}')
+    if dither not in DITHER_MODES:
+        raise ValueError(f'dither is None, "none", "ordered" or "diffusion", not {dither!r}')
+    if dither == "none":
+        return None
+    if not with_palette:
+        raise ValueError(f"dither={dither!r} goes with indexed output only: it needs palette=")
+    return dither
+
+
+def ordered_amplitude(palette) -> int:
+    """The amplitude of ordered dithering under ``palette`` ((n, 4) uint8): with d_i the smallest D of entry i to another entry,
+    ``min(65025, isqrt(sum(d_i) // (3 n)))`` -- the typical gap between neighbouring entries along one colour axis; 0 for a single
+    entry."""
+    x = coordinates(canonical(np.asarray(palette, dtype=np.uint8).reshape(-1, 4)))
+    n = len(x)
+    if n < 2:
+        return 0
+    d = ((x[:, None, :] - x[None, :, :]) ** 2).sum(axis=2)   # (int64 holds 4 * 65025^2)
+    d[np.arange(n), np.arange(n)] = np.iinfo(np.int64).max
+    total = sum(int(v) for v in d.min(axis=1))
+    return min(65025, math.isqrt(total // (3 * n)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -209,26 +251,46 @@ def colors_of_u32(values: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(values, dtype="<u4").view(np.uint8).reshape(-1, 4)
 
 
-def palette_of(rgba8, rows: int, cols: int, max_colors: int = MAX_COLORS, refine: int = 3) -> np.ndarray:
-    """The palette of the RGBA8 bytes in the DeviceBuffer ``rgba8``: the distinct colours when there are at most ``max_colors``,
-    the median cut over the bins otherwise."""
+def palette_and_route(rgba8, rows: int, cols: int, max_colors: int = MAX_COLORS, refine: int = 3):
+    """``(palette, exact)`` of the RGBA8 bytes in the DeviceBuffer ``rgba8``: the distinct colours when there are at most
+    ``max_colors`` (``exact``: the palette holds the image), the median cut over the bins otherwise."""
     ctx = _abi.Context.get()
     exact = _abi.quant_distinct(ctx, rgba8, rows, cols, max_colors)
     if exact is not None:
-        return order_palette(colors_of_u32(exact))
+        return order_palette(colors_of_u32(exact)), True
     _, bins = _abi.quant_bins(ctx, rgba8, rows, cols)
-    return build_palette(bins, max_colors, refine)
+    return build_palette(bins, max_colors, refine), False
 
 
-def quantize(image, max_colors: int = MAX_COLORS, refine: int = 3):
+def index_rows(rgba8, rows: int, cols: int, max_colors: int, refine: int, dither, stream: bool, indices: bool):
+    """``(palette, stream, indices)`` of the RGBA8 bytes in the DeviceBuffer ``rgba8``: the palette, and the packed scanlines and /
+    or the plain indices on the device, dithered as ``dither`` (checked: None, "ordered" or "diffusion") says.  The palette is that
+    of the undithered image.  An image that it holds exactly takes the plain route under every ``dither``: diffusion has no error
+    to pass on there, and ordered dithering is not let loose on pixels that need none."""
+    ctx = _abi.Context.get()
+    palette, exact = palette_and_route(rgba8, rows, cols, max_colors, refine)
+    if dither is None or exact:
+        out = _abi.quant_index(ctx, rgba8, rows, cols, palette, stream=stream, indices=indices)
+    else:
+        amp = ordered_amplitude(palette) if dither == "ordered" else 0
+        out = _abi.quant_dither(ctx, rgba8, rows, cols, palette, dither, amp, stream=stream, indices=indices)
+    return (palette, *out)
+
+
+def quantize(image, max_colors: int = MAX_COLORS, refine: int = 3, dither=None):
     """``(indices, palette)``: ``indices`` (rows, cols) uint8 and ``palette`` (n, 4) uint8 straight RGBA, n <= ``max_colors``,
     with ``palette[indices]`` the quantised image.  ``image`` is a Layer or a (rows, cols, 4) uint8 array as ``to_rgba8`` gives
     it.  An image of at most ``max_colors`` (2 .. 256) colours is kept exactly (fully transparent pixels become (0, 0, 0, 0));
     otherwise the palette is a median cut over the colour histogram, improved by ``refine`` Lloyd iterations, and every pixel gets
     its nearest entry under D, the squared distance of (r a, g a, b a, 255 a).  The palette is in ascending (a, r, g, b)
-    order.  No dithering.  The same image gives the same result every time."""
-    max_colors, refine = check_max_colors(max_colors), check_refine(refine)
+    order.
+
+    ``dither`` (None or "none": as above) spreads the rounding error of the lossy route over neighbouring pixels, so that a
+    gradient shows as a fine pattern instead of bands: "ordered" moves every pixel by an offset from the 8 x 8 Bayer matrix
+    before it takes its nearest entry, "diffusion" is Floyd-Steinberg error diffusion, every row left to right.  Both are integer
+    arithmetic on the device; the palette does not depend on ``dither``, and an exactly kept image is never touched.  The same
+    image gives the same result every time."""
+    max_colors, refine, dither = check_max_colors(max_colors), check_refine(refine), dither_argument(dither)
     buf, rows, cols = _on_device(image)
-    palette = palette_of(buf, rows, cols, max_colors, refine)
-    _, idx = _abi.quant_index(_abi.Context.get(), buf, rows, cols, palette, stream=False, indices=True)
+    palette, _, idx = index_rows(buf, rows, cols, max_colors, refine, dither, stream=False, indices=True)
     return idx.download((rows, cols), np.uint8), palette
