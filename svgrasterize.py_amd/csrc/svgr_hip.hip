@@ -20,6 +20,9 @@
 //                   class (nothing visible / constant per row / has pieces), header, entry-bitmask bits and -- for
 //                   the cells with pieces -- its ADD LIST: every piece, carry-in and layer-edge sentinel resolved to
 //                   {offset in the tile's delta tile, value}, so that the tile kernel's scatter is one load + one LDS add
+//                   (a kept replay's lean form writes only what a replay can change: pieces, carry-in adds and the class-1
+//                   cells; the class-2 cells' headers, sentinels and mask bits stand from the last full placed pass --
+//                   svgr_batch::cells_current says when they do; svgr_batch_set_paints asks for one full pass)
 //   k_tile_lists    per band: bitmasks -> per-tile item lists (cell ids in paint order, each with its add list), the
 //                   tiles in heaviest-first order, one PAGE per tile (which tile + its first 24 items: one load);
 //                   clears the bitmasks for the next render; in a placed replay a band whose bitmasks repeat keeps its lists
@@ -1964,6 +1967,14 @@ __device__ __forceinline__ void pb_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // deterministic, without groups or gradients.  What such a pass is given for its options -- one rank, `det` and `stats` 0, no keys
 // to guard, no group or gradient table, no stamps -- is known when the kernel is compiled: no owns_band test, no guard block, no
 // option lives in a register through the row loop.  Everything that keeps a wrong plan harmless is the full form's.
+// The lean form also WRITES only what a replay can change.  A cell with pieces is class 2 by the geometry's integers, and of such a
+// cell it stores the pieces and the carry-in adds (their values move with the order of the LDS atomics) but neither the header (80
+// bytes that repeat from pass to pass under one set of paints), nor the sentinels (`{where, NaN}` at places that are counts), nor the
+// two mask bits (k_tile_lists is told so -- `kept` == 2 -- and expects the saved class >= 1 row without the saved class-2 row).  The
+// count check, the `add0 < 0` refusal and the `cell_cap` / `mask_ok` tests stay in front of all of it; class-1 cells are written as
+// ever.  The host launches it only where the last pass that wrote `cell_hdr` and `adds` was a placed pass of this plan over every
+// band, without groups or gradients, into the same blocks, with the paints that stand now (svgr_batch::cells_current), and where
+// k_tile_lists keeps its lists.
 template <int MODE, bool LEAN = false>
 __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab* __restrict__ slabs, const double* __restrict__ edges,
                                                            const int* __restrict__ pair_idx, const double* __restrict__ path_paint,
@@ -2427,7 +2438,9 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
             // at the layer's first column in the tile
             store_add(adds + ((size_t)add0 + own_n + __popc(cm & below)), add_where(row_l, cell_c0 < 0 ? -cell_c0 : 0, 1), cin);
         }
-        if (((sm >> row_l) & 1u) && adds) {
+        // (the lean form stores none: where it stands and what it holds follows from the geometry's integers, and the full pass of this
+        //  plan that the host's record asks for -- svgr_batch::cells_current -- has put it there)
+        if (!LEAN && ((sm >> row_l) & 1u) && adds) {
             // behind the layer's last column
             store_add(adds + ((size_t)add0 + own_n + n_carry + __popc(sm & below)), add_where(row_l, cols - cell_c0, 1), __builtin_nan(""));
         }
@@ -2436,8 +2449,13 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
             // list has a cell of class >= 1 (row 0) / class 2 (row 1) here.  Classes 0 simply stay unset.
             unsigned long long* const mw = tile_mask + ((size_t)band * n_ct + ct0 + sl.k0 + k) * 2 * mask_words + (idx >> 6);
             const unsigned long long mbit = 1ull << (idx & 63);
+            // (the lean form sets neither bit of a class-2 cell: the cell is class 2 by the plan's count alone, and k_tile_lists, which the
+            //  host then asks to keep its lists, takes both bits from the words it saved -- `kept` == 2 there)
+            if (LEAN && cls == 2) return true;
             atomicOr(mw, mbit);
             if (cls == 2) atomicOr(mw + mask_words, mbit);
+            // (a class-2 cell's header -- paint, layer box, rule, its list's place and length, path, group -- is the same 80 bytes in every
+            //  pass of one plan with one set of paints: the lean form has left above, and what the full pass wrote stands)
             hd->paint[0] = paint.x; hd->paint[1] = paint.y; hd->paint[2] = paint.z; hd->paint[3] = paint.w;
             hd->r0 = r0; hd->c0 = c0; hd->rows = rows; hd->cols = cols;
             hd->bits = rule | (((rl >> 1) & 3) << 1) | (cls << 3) | (grad1 << 5);
@@ -2634,11 +2652,15 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
             for (int w = 0; w < NWV; ++w) a |= s_wdiff[w];
             return a != 0;
         };
+        // `kept` == 2: the path build was the lean form, which sets no bit of a class-2 cell -- those cells are class 2 by the plan's
+        // counts, in every replay.  The words to expect are then the saved class >= 1 row without the saved class-2 row, and an empty
+        // class-2 row; a band that differs gets its full words back (row 0 | saved row 1, saved row 1) and is listed as ever.
+        const bool implied = kept == 2;
         unsigned long long diff = 0ull;
         if (W == 1 && n_ct <= TL_BLOCK) {
             ulonglong2 m = make_ulonglong2(0ull, 0ull), k = m;
             if (tid < n_ct) { m = ((const ulonglong2*)mband)[tid]; k = ((const ulonglong2*)kband)[tid]; }
-            diff = (m.x ^ k.x) | (m.y ^ k.y);
+            diff = implied ? (m.x ^ (k.x & ~k.y)) | m.y : (m.x ^ k.x) | (m.y ^ k.y);
             if (!any_differs(diff != 0ull)) {
                 if ((m.x | m.y) != 0ull) ((ulonglong2*)mband)[tid] = make_ulonglong2(0ull, 0ull);
                 return;
@@ -2647,7 +2669,8 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
             for (int ct = tid; ct < n_ct; ct += TL_BLOCK) {
                 const unsigned long long* mw = mband + (size_t)ct * 2 * W;
                 const unsigned long long* kw = kband + (size_t)ct * 2 * W;
-                for (int w = 0; w < 2 * W; ++w) diff |= mw[w] ^ kw[w];
+                if (implied) for (int w = 0; w < W; ++w) diff |= (mw[w] ^ (kw[w] & ~kw[W + w])) | mw[W + w];
+                else for (int w = 0; w < 2 * W; ++w) diff |= mw[w] ^ kw[w];
             }
             if (!any_differs(diff != 0ull)) {
                 for (int ct = tid; ct < n_ct; ct += TL_BLOCK) {
@@ -2656,6 +2679,15 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
                 }
                 return;
             }
+        }
+        if (implied) {   // (the band is listed again: from its full words)
+            for (int ct = tid; ct < n_ct; ct += TL_BLOCK) {
+                unsigned long long* mw = mband + (size_t)ct * 2 * W;
+                const unsigned long long* kw = kband + (size_t)ct * 2 * W;
+                for (int w = 0; w < W; ++w) { const unsigned long long c2 = kw[W + w]; mw[w] |= c2; mw[W + w] = c2; }
+            }
+            __threadfence_block();
+            __syncthreads();
         }
     }
     const int ent0 = band_start[band], item_band0 = band_item0[band];
@@ -5127,7 +5159,7 @@ struct svgr_batch {
     DevArr<int2> cell_plan;                 // ... and where its add list lives: {first add, pieces}, left by the plan's full pass (k_path_build)
     bool add_places = false;                // `cell_plan` holds the places of the current plan: the renders take them (k_path_build<1>)
     // a pass that ended with an error flag may have left any of the self-cleaning buffers dirty
-    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; lists_current = false; }
+    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; lists_current = false; cells_current = false; }
     DevArr<TileAdd> adds;                   // the cells' add lists (k_path_build: a slab reserves its cells' lists in one piece)
     DevArr<uint4> items;                    // the tiles' item lists: {cell id | class << 30, first add, adds, 0} (k_tile_lists)
     DevArr<int2> tile_info;                 // per (band, column tile): {first item, items}
@@ -5209,6 +5241,35 @@ struct svgr_batch {
                    mask_words == o.mask_words && owned == o.owned && vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
         }
     } lists_made{};
+    // And for what k_path_build<1, LEAN> no longer writes -- the headers of the class-2 cells and the layer-edge sentinels of their add
+    // lists, the same bytes at the same places in every placed pass of one plan with one set of paints and rules --: the last pass
+    // that wrote `cell_hdr` and `adds` was a placed pass (full or lean) over every band, with add lists, without groups or gradients,
+    // into the blocks `cells_made` records, and nothing has changed a header field since.  Where this does not hold the placed pass
+    // is the full form, once.  Decided case by case:
+    //   a measuring pass (`adds` == nullptr), every unplanned pass (<0>, <2>)       void it: they reserve other places / write no list
+    //   a pass of one rank of several                                               voids it: the other ranks' cells are not written
+    //   a pass with groups or gradients                                             voids it: the header's `group` and `bits` differ
+    //   a pass that stops short of the path build (upto < 4), or ends in an error   voids it
+    //   a deterministic render                                                      valid: the full form, same plan, same bytes
+    //   a window render, an OUT_CANVAS_F64 render                                   valid: the geometry pass in front of them is an
+    //                                                                               ordinary placed pass, the tile kernels only read
+    //   svgr_batch_set_paints                                                       voids it (`paint`); `path_rule` is written when the
+    //                                                                               batch is made and never again; groups and gradients
+    //                                                                               void it by the passes that run under them (above)
+    //   new transforms, bands, viewport, a re-plan, inherited arrays                unplanned passes follow (above); a new batch
+    //                                                                               starts with the flag clear
+    bool cells_current = false;
+    struct CellsMade {
+        const void *adds, *cell_hdr, *cell_plan, *tile_mask_kept, *path_paint, *path_rule;
+        size_t adds_cap, cell_hdr_cap, cell_plan_cap, tile_mask_kept_cap;
+        AddShards shards;
+        bool operator==(const CellsMade& o) const {
+            return adds == o.adds && cell_hdr == o.cell_hdr && cell_plan == o.cell_plan && tile_mask_kept == o.tile_mask_kept &&
+                   path_paint == o.path_paint && path_rule == o.path_rule && adds_cap == o.adds_cap && cell_hdr_cap == o.cell_hdr_cap &&
+                   cell_plan_cap == o.cell_plan_cap && tile_mask_kept_cap == o.tile_mask_kept_cap &&
+                   memcmp(&shards, &o.shards, sizeof(AddShards)) == 0;
+        }
+    } cells_made{};
     unsigned long long stale_word = 0ull;   // SVGR_DBG_STALE_BAND: source of the one-word upload (alive until the stream has taken it)
     bool slab_order_pending = false;        // svgr_batch_draw planned this batch and left the slab order to the first render that replays the plan
     std::vector<int> slab_at_host;
@@ -5372,6 +5433,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     if (!b->arena_zeroed) HIPCHK(hipMemsetAsync(b->arena.p, 0, b->arena_bytes, st));
     b->arena_zeroed = false;  // (the kernels below count into it)
     if (upto < 4) b->lists_current = false;   // (a pass that stops short of the tile lists leaves other geometry under them)
+    if (upto < 4) b->cells_current = false;   // (... and under the cells)
     // multi-GPU with a viewport: the plan listed the segments of the paths whose rows can reach this rank's bands
     // (build_seg_list); a pass without such a list finds the reach itself and lets the flatten skip foreign paths
     const bool listed = use_vp && b->own.world > 1 && b->n_seg_list >= 0;
@@ -5527,6 +5589,8 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                           b->bins.cap, b->bbox.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask.cap, b->tile_mask_kept.cap,
                                           b->n_ctiles(), b->mask_words, owned, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]}};
     const bool lists_kept = lists_for_plan && keep_slabs && b->lists_current && b->lists_made == lists_now;
+    bool bits_implied = false;   // the path build set no class-2 cell's mask bits (its lean form): k_tile_lists takes them from the saved words
+    if (b->n_slabs <= 0) b->cells_current = false;
     if (b->n_slabs > 0) {
         b->masks_zeroed = false;  // (bits are set below; k_tile_lists clears them again)
         auto launch_pb = [&](auto kern) {
@@ -5544,18 +5608,31 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         const bool bounded = !placed && !b->count_adds_only && b->adds.p && b->adds_roomy && !b->safe_path && !getenv("SVGR_SAFE_PATH");
         // The placed pass of a kept replay behind the lean flatten has nothing to guard; on one GPU, not deterministic, without groups or
         // gradients and with the plan standing (no statistics) every option of the kernel has the value k_path_build<1, LEAN> is compiled for.
+        // The lean form writes neither the class-2 cells' headers nor the sentinels of their lists: it runs where the last pass that wrote
+        // the cells left them as this one would (svgr_batch::cells_current).  In a run of kept replays that is the pass that wrote the slab
+        // table; after svgr_batch_set_paints one full pass comes first.
+        const svgr_batch::CellsMade cells_now{b->adds.p, b->cell_hdr.p, b->cell_plan.p, b->tile_mask_kept.p, b->path_paint.p, b->path_rule.p,
+                                              b->adds.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask_kept.cap, b->add_shards};
+        const bool cells_pass = placed && b->own.world <= 1 && b->n_groups == 0 && b->n_grads == 0 && b->planned && !b->count_adds_only &&
+                                b->adds.p != nullptr;   // (deterministic or not: the same headers and sentinels at the same places)
+        const bool cells_kept = cells_pass && b->cells_current && b->cells_made == cells_now;
         bool lean_pb = placed && keep_slabs && lean_fl && b->own.world <= 1 && !b->deterministic && b->n_groups == 0 && b->n_grads == 0 &&
-                       b->planned && !b->count_adds_only && b->adds.p != nullptr;
+                       b->planned && !b->count_adds_only && b->adds.p != nullptr && cells_kept &&
+                       lists_kept /* (it sets no class-2 cell's mask bits: the saved words have them) */;
+        b->cells_current = cells_pass;
+        b->cells_made = cells_now;
 #ifdef SVGR_DBG_PB_STAMP
         lean_pb = false;   // (the stamps are the full form's)
 #endif
         if (getenv("SVGR_DBG_PLAN")) {   // (diagnostic: which instantiation this pass launches, and whether it found the slab table in place)
             fprintf(stderr, "[geometry] path build form %s\n", lean_pb ? "lean" : "full");
+            fprintf(stderr, "[geometry] cells %s\n", cells_kept ? "current" : "stale");   // (what stands in `cell_hdr` / `adds` is what this pass would write, or not)
             fprintf(stderr, "[geometry] k_path_build<%d>%s, %lld slabs, tile lists %s, slab table %s\n", placed ? 1 : bounded ? 2 : 0,
                     b->count_adds_only ? " measuring" : "", (long long)b->n_slabs,
                     lists_kept ? "kept" : "rebuilt" /* (what k_tile_lists is asked for: a band whose words differ is listed again on the device) */,
                     keep_slabs ? "kept" : "written");
         }
+        bits_implied = lean_pb;
         if (lean_pb) launch_pb(k_path_build<1, true>); else if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
 #ifdef SVGR_DBG_PB_STAMP
         if (pb_dbg && b->planned && !b->count_adds_only) {
@@ -5598,7 +5675,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                            (const TileEntry*)b->entries.p, b->tile_mask.p, b->mask_words, b->n_ctiles(), b->vp[1], b->own, owned,
                            b->tile_info.p, b->pages.p, b->items.p, (const CellHdr*)b->cell_hdr.p, cap_i32(b->items.cap), cap_i32(b->cell_hdr.cap), b->bd(),
                            keep_lists ? (const PathBin*)b->bins.p : (const PathBin*)nullptr, (const int*)b->bbox.p,
-                           lists_for_plan ? b->tile_mask_kept.p : (unsigned long long*)nullptr, lists_kept ? 1 : 0);
+                           lists_for_plan ? b->tile_mask_kept.p : (unsigned long long*)nullptr, lists_kept ? (bits_implied ? 2 : 1) : 0);
         b->masks_zeroed = true;
     }
     b->lists_current = lists_for_plan;
@@ -6242,6 +6319,7 @@ int svgr_batch_set_paints(svgr_batch* b, const double* path_paint) {
                           hipMemcpyHostToDevice, b->ctx->stream));
     HIPCHK(b->note_upload(b->ctx->stream));
     b->geometry_fresh = false; b->geometry_current = false;  // the cell headers carry the paint
+    b->cells_current = false;   // (... and the lean path build leaves the class-2 cells' headers as they are: one full pass first)
     return 0;
 }
 
