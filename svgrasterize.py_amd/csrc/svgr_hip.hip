@@ -1,5 +1,5 @@
 // svgr_hip.hip -- MI355X (gfx950 / CDNA4) anti-aliased path rasterizer: HIP kernels + C ABI.
-//
+// (What the host remembers between renders -- a plan stands, its slab order, which results a replay finds in place -- is svgr_batch::plan: svgr_plan_state.h.)
 // Pipeline of one svgr_batch_render (4 launches of a planned batch on the context stream -- k_band_entries only in a plan's own
 // pass, k_path_bbox only in the first replay after a plan: the later ones keep the slab table it wrote --, no host read-back).  A frame with NEW geometry (svgr_batch_draw) runs the same kernels in their unplanned forms -- the
 // flatten in one traversal with a decoupled look-back (k_flatten<.., SCAN>), k_path_build<2> on its own per-cell bounds -- with the
@@ -22,7 +22,7 @@
 //                   {offset in the tile's delta tile, value}, so that the tile kernel's scatter is one load + one LDS add
 //                   (a kept replay's lean form writes only what a replay can change: pieces, carry-in adds and the class-1
 //                   cells; the class-2 cells' headers, sentinels and mask bits stand from the last full placed pass --
-//                   svgr_batch::cells_current says when they do; svgr_batch_set_paints asks for one full pass)
+//                   PlanState::cells (svgr_plan_state.h) says when they do; svgr_batch_set_paints asks for one full pass)
 //   k_tile_lists    per band: bitmasks -> per-tile item lists (cell ids in paint order, each with its add list), the
 //                   tiles in heaviest-first order, one PAGE per tile (which tile + its first 24 items: one load);
 //                   clears the bitmasks for the next render; in a placed replay a band whose bitmasks repeat keeps its lists
@@ -1973,7 +1973,7 @@ __device__ __forceinline__ void pb_barrier() { asm volatile("s_waitcnt lgkmcnt(0
 // two mask bits (k_tile_lists is told so -- `kept` == 2 -- and expects the saved class >= 1 row without the saved class-2 row).  The
 // count check, the `add0 < 0` refusal and the `cell_cap` / `mask_ok` tests stay in front of all of it; class-1 cells are written as
 // ever.  The host launches it only where the last pass that wrote `cell_hdr` and `adds` was a placed pass of this plan over every
-// band, without groups or gradients, into the same blocks, with the paints that stand now (svgr_batch::cells_current), and where
+// band, without groups or gradients, into the same blocks, with the paints that stand now (PlanState::cells), and where
 // k_tile_lists keeps its lists.
 template <int MODE, bool LEAN = false>
 __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab* __restrict__ slabs, const double* __restrict__ edges,
@@ -2439,7 +2439,7 @@ __global__ __launch_bounds__(PB_THREADS, PB_WAVES) void k_path_build(const Slab*
             store_add(adds + ((size_t)add0 + own_n + __popc(cm & below)), add_where(row_l, cell_c0 < 0 ? -cell_c0 : 0, 1), cin);
         }
         // (the lean form stores none: where it stands and what it holds follows from the geometry's integers, and the full pass of this
-        //  plan that the host's record asks for -- svgr_batch::cells_current -- has put it there)
+        //  plan that the host's record asks for -- PlanState::cells -- has put it there)
         if (!LEAN && ((sm >> row_l) & 1u) && adds) {
             // behind the layer's last column
             store_add(adds + ((size_t)add0 + own_n + n_carry + __popc(sm & below)), add_where(row_l, cols - cell_c0, 1), __builtin_nan(""));
@@ -2637,7 +2637,7 @@ __global__ __launch_bounds__(TL_BLOCK) void k_tile_lists(const int* __restrict__
     unsigned long long* const mband = tile_mask + (size_t)band * n_ct * 2 * W;
     // `tile_mask_kept` (a placed replay that keeps its lists): the band's mask words as they stood when the lists now in place were
     // made -- the full path below saves them just before it clears them.  `kept`: those lists ARE in place (the host's record,
-    // svgr_batch::lists_current).  Everything else an item is made of -- cell id, add place, add count -- is the plan's, checked by
+    // PlanState::lists).  Everything else an item is made of -- cell id, add place, add count -- is the plan's, checked by
     // k_path_build<1> (error bit 32), so a band whose words repeat would rewrite, item by item, what stands there: one round of
     // loads, both arrays asked for together, the words cleared, done.  A band with any other word is listed again as if entered here.
     unsigned long long* const kband = tile_mask_kept ? tile_mask_kept + (size_t)band * n_ct * 2 * W : nullptr;
@@ -5082,6 +5082,8 @@ __global__ __launch_bounds__(64) void k_convolve_rows(double* __restrict__ out, 
 // ======================================================================================
 // batch object
 // ======================================================================================
+#include "svgr_plan_state.h"   // (host only: the plan-standing flags, the results kept on the device and their transitions)
+
 struct TimedEvents {
     hipEvent_t e0, e1, e2;  // start, before tile kernel, after tile kernel
 };
@@ -5093,7 +5095,7 @@ struct svgr_batch {
     bool has_vp = false;       // as given by the caller
     double thr = 0.16000000000000003;
     Owner own{0, 1, 1};
-    bool planned = false;
+    PlanState plan;               // does a plan stand, with which slab order, and which of its passes' results are kept on the device (svgr_plan_state.h)
     bool sized = false;           // a plan has succeeded with the viewport `sized_vp`: the buffers' capacities are a re-plan's guesses
     int sized_vp[4] = {0, 0, 0, 0};
     // SVGR_SAFE_PATH (a test hook, read when a plan is made): the renders take NO place from the plan -- slab places, band-list
@@ -5159,7 +5161,7 @@ struct svgr_batch {
     DevArr<int2> cell_plan;                 // ... and where its add list lives: {first add, pieces}, left by the plan's full pass (k_path_build)
     bool add_places = false;                // `cell_plan` holds the places of the current plan: the renders take them (k_path_build<1>)
     // a pass that ended with an error flag may have left any of the self-cleaning buffers dirty
-    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; slabs_current = false; lists_current = false; cells_current = false; }
+    void invalidate_work() { masks_zeroed = false; arena_zeroed = false; plan.pass_failed(); }
     DevArr<TileAdd> adds;                   // the cells' add lists (k_path_build: a slab reserves its cells' lists in one piece)
     DevArr<uint4> items;                    // the tiles' item lists: {cell id | class << 30, first add, adds, 0} (k_tile_lists)
     DevArr<int2> tile_info;                 // per (band, column tile): {first item, items}
@@ -5195,83 +5197,7 @@ struct svgr_batch {
     DevArr<int> pair_idx;                   // per (path, band) pair: its place in its band's list (k_band_entries)
     DevArr<Slab> slabs;                     // work items of k_path_build (k_path_bbox)
     DevArr<int> slab_at;                    // per path: its first slab, heaviest paths first (staged plan; renders only)
-    bool slab_at_valid = false;
-    // A geometry pass has run k_path_bbox under the standing plan's `slab_at` order: `slabs`, `bbox` and `bins` hold the plan's places,
-    // and a replay under the same plan keeps them instead of launching the kernel again (run_geometry; its flatten is the lean form,
-    // which writes no keys -- behind a full flatten k_path_build<1> checks the paths' keys against them).  Cleared wherever the plan
-    // or its slab order is, and by every pass that writes the three arrays in another form; `slabs_made` is what the table was written for -- a replay that finds anything else there writes it again.
-    bool slabs_current = false;
-    // The slab order was made by the render that is running, not by the plan (svgr_batch_draw leaves it to the first replay): that
-    // render's pass writes the table but does not mark it kept -- the replay behind it runs k_path_bbox once more and marks it.  Nothing
-    // in the arrays asks for this; the suite pins five launches for that replay (tests/test_gpu_draw.py), and a batch planned by a
-    // draw pays one launch of 6 us once.  A batch planned by svgr_batch_plan has its order from the plan and is not held back.
-    bool slab_order_late = false;
-    struct SlabsMade {
-        const void *slabs, *bbox, *bins, *slab_at;
-        int64_t n_slabs, n_paths;
-        int vp[4];
-        // (what the flatten of that pass stored by: a replay that keeps the table launches k_flatten<.., LEAN>, which takes the places on trust)
-        const void *edges, *seg_off, *lane_off;
-        int64_t n_segs;
-        int edge_cap, fl_sub;
-        double thr;
-        bool operator==(const SlabsMade& o) const {
-            return slabs == o.slabs && bbox == o.bbox && bins == o.bins && slab_at == o.slab_at && n_slabs == o.n_slabs && n_paths == o.n_paths &&
-                   vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3] && edges == o.edges && seg_off == o.seg_off &&
-                   lane_off == o.lane_off && n_segs == o.n_segs && edge_cap == o.edge_cap && fl_sub == o.fl_sub && thr == o.thr;
-        }
-    } slabs_made{};
-    // The same for what k_tile_lists leaves (`items`, `pages`, `tile_info`): a placed replay that keeps its slab table would list, band
-    // by band, what the previous one listed unless a band's mask words differ -- and the kernel compares them against `tile_mask_kept`,
-    // the words its last full run saved.  Set by a full run that saved them, for what `lists_made` records; cleared wherever the
-    // plan or the slab table is, by every pass that stops short of the lists, lists the bands again (k_band_entries) or builds the
-    // cells by another k_path_build than <1>.  Passes that only read the lists (windows, the other outputs) leave it alone.
-    bool lists_current = false;
-    struct ListsMade {
-        const void *items, *pages, *tile_info, *entries, *bins, *bbox, *cell_hdr, *cell_plan, *tile_mask, *tile_mask_kept;
-        size_t items_cap, pages_cap, tile_info_cap, entries_cap, bins_cap, bbox_cap, cell_hdr_cap, cell_plan_cap, tile_mask_cap, tile_mask_kept_cap;
-        int n_ctiles, mask_words, owned;
-        int vp[4];
-        bool operator==(const ListsMade& o) const {
-            return items == o.items && pages == o.pages && tile_info == o.tile_info && entries == o.entries && bins == o.bins && bbox == o.bbox &&
-                   cell_hdr == o.cell_hdr && cell_plan == o.cell_plan && tile_mask == o.tile_mask && tile_mask_kept == o.tile_mask_kept &&
-                   items_cap == o.items_cap && pages_cap == o.pages_cap && tile_info_cap == o.tile_info_cap && entries_cap == o.entries_cap &&
-                   bins_cap == o.bins_cap && bbox_cap == o.bbox_cap && cell_hdr_cap == o.cell_hdr_cap && cell_plan_cap == o.cell_plan_cap &&
-                   tile_mask_cap == o.tile_mask_cap && tile_mask_kept_cap == o.tile_mask_kept_cap && n_ctiles == o.n_ctiles &&
-                   mask_words == o.mask_words && owned == o.owned && vp[0] == o.vp[0] && vp[1] == o.vp[1] && vp[2] == o.vp[2] && vp[3] == o.vp[3];
-        }
-    } lists_made{};
-    // And for what k_path_build<1, LEAN> no longer writes -- the headers of the class-2 cells and the layer-edge sentinels of their add
-    // lists, the same bytes at the same places in every placed pass of one plan with one set of paints and rules --: the last pass
-    // that wrote `cell_hdr` and `adds` was a placed pass (full or lean) over every band, with add lists, without groups or gradients,
-    // into the blocks `cells_made` records, and nothing has changed a header field since.  Where this does not hold the placed pass
-    // is the full form, once.  Decided case by case:
-    //   a measuring pass (`adds` == nullptr), every unplanned pass (<0>, <2>)       void it: they reserve other places / write no list
-    //   a pass of one rank of several                                               voids it: the other ranks' cells are not written
-    //   a pass with groups or gradients                                             voids it: the header's `group` and `bits` differ
-    //   a pass that stops short of the path build (upto < 4), or ends in an error   voids it
-    //   a deterministic render                                                      valid: the full form, same plan, same bytes
-    //   a window render, an OUT_CANVAS_F64 render                                   valid: the geometry pass in front of them is an
-    //                                                                               ordinary placed pass, the tile kernels only read
-    //   svgr_batch_set_paints                                                       voids it (`paint`); `path_rule` is written when the
-    //                                                                               batch is made and never again; groups and gradients
-    //                                                                               void it by the passes that run under them (above)
-    //   new transforms, bands, viewport, a re-plan, inherited arrays                unplanned passes follow (above); a new batch
-    //                                                                               starts with the flag clear
-    bool cells_current = false;
-    struct CellsMade {
-        const void *adds, *cell_hdr, *cell_plan, *tile_mask_kept, *path_paint, *path_rule;
-        size_t adds_cap, cell_hdr_cap, cell_plan_cap, tile_mask_kept_cap;
-        AddShards shards;
-        bool operator==(const CellsMade& o) const {
-            return adds == o.adds && cell_hdr == o.cell_hdr && cell_plan == o.cell_plan && tile_mask_kept == o.tile_mask_kept &&
-                   path_paint == o.path_paint && path_rule == o.path_rule && adds_cap == o.adds_cap && cell_hdr_cap == o.cell_hdr_cap &&
-                   cell_plan_cap == o.cell_plan_cap && tile_mask_kept_cap == o.tile_mask_kept_cap &&
-                   memcmp(&shards, &o.shards, sizeof(AddShards)) == 0;
-        }
-    } cells_made{};
     unsigned long long stale_word = 0ull;   // SVGR_DBG_STALE_BAND: source of the one-word upload (alive until the stream has taken it)
-    bool slab_order_pending = false;        // svgr_batch_draw planned this batch and left the slab order to the first render that replays the plan
     std::vector<int> slab_at_host;
     int64_t n_slabs = 0;                    // ... the plan's count = the launch's grid
     DevArr<int> seg_cnt, seg_off;           // per segment: edges it flattens into (the plan's counting pass), their prefix sums
@@ -5323,7 +5249,7 @@ struct svgr_batch {
     int size_masks(int64_t longest) {
         mask_words = (int)std::max<int64_t>((longest + 63) / 64, 1);
         masks_zeroed = false;
-        lists_current = false;
+        plan.masks_resized();
         if (int rc = tile_mask_kept.ensure(mask_bytes() / sizeof(unsigned long long) + 1)) return rc;
         return tile_mask.ensure(mask_bytes() / sizeof(unsigned long long) + 1);
     }
@@ -5411,7 +5337,7 @@ static bool spare_adopt(svgr_batch* b) {
     b->mask_words = w->mask_words; b->add_shards = w->add_shards; b->n_adds = w->n_adds; b->adds_roomy = w->adds_roomy;
     b->n_bands = (b->vp[2] + TR - 1) / TR;
     b->masks_zeroed = false;   // (whatever the last render of the old batch left: cleared again)
-    b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false;
+    b->plan.arrays_inherited();
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     return true;
@@ -5432,8 +5358,8 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     const int ns = (int)b->n_segs, np = (int)b->n_paths;
     if (!b->arena_zeroed) HIPCHK(hipMemsetAsync(b->arena.p, 0, b->arena_bytes, st));
     b->arena_zeroed = false;  // (the kernels below count into it)
-    if (upto < 4) b->lists_current = false;   // (a pass that stops short of the tile lists leaves other geometry under them)
-    if (upto < 4) b->cells_current = false;   // (... and under the cells)
+    if (upto < 4) b->plan.lists.drop();   // (a pass that stops short of the tile lists leaves other geometry under them)
+    if (upto < 4) b->plan.cells.drop();   // (... and under the cells)
     // multi-GPU with a viewport: the plan listed the segments of the paths whose rows can reach this rank's bands
     // (build_seg_list); a pass without such a list finds the reach itself and lets the flatten skip foreign paths
     const bool listed = use_vp && b->own.world > 1 && b->n_seg_list >= 0;
@@ -5477,7 +5403,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         if (upto == 1 && !b->late_scan)
             SVGR_LAUNCH(k_seg_scan, dim3(1), dim3(1024), 0, st, (const int*)b->seg_cnt.p, ns, b->seg_off.p);
         if (upto == 0 || (upto == 1 && b->census_bbox)) {  // bboxes only (no edges stored): the union when there is no viewport; the two-pass plan's census
-            b->slabs_current = false; b->lists_current = false;
+            b->plan.slabs.drop(); b->plan.lists.drop();
             SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(),
                                np_walk, use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), 1, plist,
                                (Slab*)nullptr, 0, b->own, (const int*)nullptr, (const int*)nullptr, 0, (const int*)nullptr);
@@ -5485,30 +5411,31 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         return 0;
     }
     // (a planned render under the plan's places keeps the plan's band lists: k_tile_lists reads the paths' bboxes and bins itself)
-    const bool keep_lists = upto >= 4 && b->planned && b->slab_at_valid && use_vp && !b->safe_path;
+    const bool keep_lists = upto >= 4 && b->plan.planned() && b->plan.slab_at_valid() && use_vp && !b->safe_path;
     // (a planned render takes every cell's add places from the plan's own full pass: one pass over the edge rows, no reservation)
     // (the places are per cell: they hold as long as the paths keep the plan's cell places, i.e. under the plan's slab order)
-    const bool placed = b->planned && b->add_places && b->slab_at_valid && !b->count_adds_only && b->cell_plan.p != nullptr;
-    // A replay of a plan whose slab table the previous render left (svgr_batch::slabs_current): k_path_bbox would write, record by
+    const bool placed = b->plan.planned() && b->add_places && b->plan.slab_at_valid() && !b->count_adds_only && b->cell_plan.p != nullptr;
+    // A replay of a plan whose slab table the previous render left (PlanState::slabs): k_path_bbox would write, record by
     // record, what is there -- same keys, same `slab_at`, same `bins` -- so it is not launched; k_path_build<1> checks the keys
     // against the kept bboxes instead (error bit 32, as the kernel's own comparison).  One GPU, every path: a rank's list keeps
     // its launch, and so does every pass that is not the placed render.
     const int edge_cap = cap_i32(std::min(b->edge_path.cap, b->edges.cap / 4));
-    const svgr_batch::SlabsMade slabs_now{b->slabs.p, b->bbox.p, b->bins.p, b->slab_at.p, b->n_slabs, b->n_paths, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]},
-                                          b->edges.p, b->seg_off.p, b->lane_off.p, b->n_segs, edge_cap, fl_sub, b->thr};
+    // (from `edges` on: what the flatten of that pass stored by -- a replay that keeps the table launches k_flatten<.., LEAN>, which takes the places on trust)
+    const PlanPrint slabs_now = plan_print(b->slabs.p, b->bbox.p, b->bins.p, b->slab_at.p, b->n_slabs, b->n_paths, b->vp[0], b->vp[1], b->vp[2], b->vp[3],
+                                           b->edges.p, b->seg_off.p, b->lane_off.p, b->n_segs, edge_cap, fl_sub, b->thr);
     const bool slabs_for_plan = keep_lists && b->own.world <= 1 && !listed && ns > 0 && b->n_slabs > 0 && b->n_slabs <= (int64_t)cap_i32(b->slabs.cap);
-    const bool keep_slabs = slabs_for_plan && placed && b->slabs_current && b->slabs_made == slabs_now;
+    const bool keep_slabs = b->plan.slabs.holds(slabs_for_plan && placed, slabs_now);
     // ... and the flatten of such a replay is the lean form (k_flatten<.., LEAN>): it stores the edges at the lanes' places and leaves
     // the keys zero, so k_path_build<1> is given no path to check (below).  What the flatten reads and where it stores -- the
     // transforms, the viewport, the bands, `seg_off`, `lane_off`, the edge array -- is what the full pass that made the table had:
-    // whatever changes one of them clears `slabs_current` or is part of `slabs_made`.
+    // whatever changes one of them drops PlanState::slabs or is part of `slabs_now`.
     bool lean_fl = false;
     if (ns > 0) {
         // (the counting pass that made `seg_off` left every lane's place inside its segment's slots beside it)
         const bool lane_places = !b->safe_path;
         // (`edge_path` says which path an edge belongs to -- svgr_batch_get_edges is its only reader -- and under a standing plan's lane
         //  places the pass that made the plan has written it, slot by slot, with what this one would store: a placed replay does not)
-        const bool keep_edge_path = b->planned && lane_places && b->lane_off.p && b->lane_off.cap >= ((size_t)ns << fl_sub) && !b->fl_scan;
+        const bool keep_edge_path = b->plan.planned() && lane_places && b->lane_off.p && b->lane_off.cap >= ((size_t)ns << fl_sub) && !b->fl_scan;
         auto launch_fl = [&](auto kern, int* places) {
             SVGR_LAUNCH(kern, fgrid, dim3(FL_BLOCK), 0, st, (const double*)b->segs.p,
                                (const uint8_t*)b->seg_kind.p, (const int*)b->seg_path.p, (const double*)b->path_m6.p, ns, b->thr,
@@ -5540,26 +5467,24 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
     }
     if (!keep_slabs) {
         SVGR_LAUNCH(k_path_bbox, grid1((size_t)std::max(np_walk, 1), 64), dim3(64), 0, st, (const unsigned long long*)b->pkeys(), np_walk,
-                           use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), b->planned ? 0 : 1, plist,
+                           use_vp ? 1 : 0, b->vp[0], b->vp[1], b->vp[2], b->vp[3], b->bbox.p, b->bins.p, b->bd(), b->plan.planned() ? 0 : 1, plist,
                            upto >= 3 ? b->slabs.p : (Slab*)nullptr, (int)std::min<int64_t>(cap_i32(b->slabs.cap), b->n_slabs) /* = k_path_build's grid */, b->own,
                            (const int*)b->path_seg0.p, (const int*)b->seg_off.p, edge_cap,
-                           upto >= 4 && b->planned && b->slab_at_valid ? (const int*)b->slab_at.p : (const int*)nullptr);
-        b->slabs_current = slabs_for_plan && !b->slab_order_late;   // (written at the plan's places, or in some other form)
-        b->slab_order_late = false;
-        b->slabs_made = slabs_now;
+                           upto >= 4 && b->plan.planned() && b->plan.slab_at_valid() ? (const int*)b->slab_at.p : (const int*)nullptr);
+        b->plan.slab_table_written(slabs_for_plan, slabs_now);   // (written at the plan's places, or in some other form)
     }
     if (upto == 2) return 0;
     // per owned band: its list of (path, band) pairs in paint order, and its first tile-list slot
     const int owned = count_owned_bands(b->own, b->n_bands);
     // (upto >= 4 on one GPU: the kernel also clears the tiles' entry bitmasks of its band when they are not clear yet)
     const bool clear_in_be = owned > 0 && !keep_lists && upto >= 4 && !b->masks_zeroed && b->tile_mask.p && b->own.world <= 1;
-    if (!keep_lists) b->lists_current = false;   // (the bands are listed again: the tile lists in place follow the old band lists)
+    if (!keep_lists) b->plan.lists.drop();   // (the bands are listed again: the tile lists in place follow the old band lists)
     if (owned > 0 && !keep_lists)
         SVGR_LAUNCH(k_band_entries, dim3(owned), dim3(BE_BLOCK), 0, st, (const PathBin*)b->bins.p, np_walk, plist,
                            (const int*)b->bbox.p, b->band_start.p, b->band_count.p, b->band_item0.p, b->entries.p,
                            b->pair_idx.p, cap_i32(std::min(b->entries.cap, b->pair_idx.cap)),
                            upto >= 4 ? cap_i32(b->items.cap) : 0x7fffffff, b->vp[1], b->bd(), b->own,
-                           upto >= 4 && b->planned && use_vp && !b->safe_path ? 1 : 0,
+                           upto >= 4 && b->plan.planned() && use_vp && !b->safe_path ? 1 : 0,
                            clear_in_be ? b->tile_mask.p : (unsigned long long*)nullptr, b->n_ctiles() * 2 * b->mask_words);
     if (clear_in_be) b->masks_zeroed = true;
     if (upto == 3) return 0;
@@ -5580,17 +5505,17 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
 #endif
     // A placed replay that keeps its band lists and writes or keeps the plan's slab table lists every band from the plan's places and
     // its own mask words alone: its full k_tile_lists saves the words (`tile_mask_kept`), and the replay behind it -- slab table kept,
-    // the same arrays (`lists_made`) -- asks the kernel to list only the bands whose words differ from the saved ones.
+    // the same arrays (`lists_now`) -- asks the kernel to list only the bands whose words differ from the saved ones.
     const size_t mask_n = b->mask_bytes() / sizeof(unsigned long long);
     const bool lists_for_plan = slabs_for_plan && placed && owned > 0 && b->n_ctiles() > 0 && b->tile_mask.p && b->tile_mask_kept.p &&
                                 b->tile_mask.cap >= mask_n && b->tile_mask_kept.cap >= mask_n;
-    const svgr_batch::ListsMade lists_now{b->items.p, b->pages.p, b->tile_info.p, b->entries.p, b->bins.p, b->bbox.p, b->cell_hdr.p, b->cell_plan.p,
-                                          b->tile_mask.p, b->tile_mask_kept.p, b->items.cap, b->pages.cap, b->tile_info.cap, b->entries.cap,
-                                          b->bins.cap, b->bbox.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask.cap, b->tile_mask_kept.cap,
-                                          b->n_ctiles(), b->mask_words, owned, {b->vp[0], b->vp[1], b->vp[2], b->vp[3]}};
-    const bool lists_kept = lists_for_plan && keep_slabs && b->lists_current && b->lists_made == lists_now;
+    const PlanPrint lists_now = plan_print(b->items.p, b->pages.p, b->tile_info.p, b->entries.p, b->bins.p, b->bbox.p, b->cell_hdr.p, b->cell_plan.p,
+                                           b->tile_mask.p, b->tile_mask_kept.p, b->items.cap, b->pages.cap, b->tile_info.cap, b->entries.cap,
+                                           b->bins.cap, b->bbox.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask.cap, b->tile_mask_kept.cap,
+                                           b->n_ctiles(), b->mask_words, owned, b->vp[0], b->vp[1], b->vp[2], b->vp[3]);
+    const bool lists_kept = b->plan.lists.holds(lists_for_plan && keep_slabs, lists_now);
     bool bits_implied = false;   // the path build set no class-2 cell's mask bits (its lean form): k_tile_lists takes them from the saved words
-    if (b->n_slabs <= 0) b->cells_current = false;
+    if (b->n_slabs <= 0) b->plan.cells.drop();
     if (b->n_slabs > 0) {
         b->masks_zeroed = false;  // (bits are set below; k_tile_lists clears them again)
         auto launch_pb = [&](auto kern) {
@@ -5599,7 +5524,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                                b->n_groups > 0 ? (const int*)b->path_group.p : (const int*)nullptr,
                                b->n_grads > 0 ? (const int*)b->path_grad.p : (const int*)nullptr, b->vp[0], b->vp[1], b->n_ctiles(), b->mask_words,
                                b->tile_mask.p, b->cell_hdr.p, cap_i32(std::min(b->cell_hdr.cap, b->cell_plan.cap)), b->add_shards,
-                               b->count_adds_only ? (TileAdd*)nullptr : b->adds.p, b->cell_plan.p, b->bd(), b->own, b->planned ? 0 : 1,
+                               b->count_adds_only ? (TileAdd*)nullptr : b->adds.p, b->cell_plan.p, b->bd(), b->own, b->plan.planned() ? 0 : 1,
                                b->deterministic ? 1 : 0, pb_dbg, keep_slabs ? (const unsigned long long*)b->pkeys() : (const unsigned long long*)nullptr,
                                (const int*)b->bbox.p, (const PathBin*)b->bins.p,
                                lean_fl ? 0 /* (no keys behind the lean flatten: the guard's loop over the paths makes no trip) */ : np, b->vp[2], b->vp[3]);
@@ -5609,18 +5534,17 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         // The placed pass of a kept replay behind the lean flatten has nothing to guard; on one GPU, not deterministic, without groups or
         // gradients and with the plan standing (no statistics) every option of the kernel has the value k_path_build<1, LEAN> is compiled for.
         // The lean form writes neither the class-2 cells' headers nor the sentinels of their lists: it runs where the last pass that wrote
-        // the cells left them as this one would (svgr_batch::cells_current).  In a run of kept replays that is the pass that wrote the slab
+        // the cells left them as this one would (PlanState::cells).  In a run of kept replays that is the pass that wrote the slab
         // table; after svgr_batch_set_paints one full pass comes first.
-        const svgr_batch::CellsMade cells_now{b->adds.p, b->cell_hdr.p, b->cell_plan.p, b->tile_mask_kept.p, b->path_paint.p, b->path_rule.p,
-                                              b->adds.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask_kept.cap, b->add_shards};
-        const bool cells_pass = placed && b->own.world <= 1 && b->n_groups == 0 && b->n_grads == 0 && b->planned && !b->count_adds_only &&
+        const PlanPrint cells_now = plan_print(b->adds.p, b->cell_hdr.p, b->cell_plan.p, b->tile_mask_kept.p, b->path_paint.p, b->path_rule.p,
+                                               b->adds.cap, b->cell_hdr.cap, b->cell_plan.cap, b->tile_mask_kept.cap, b->add_shards);
+        const bool cells_pass = placed && b->own.world <= 1 && b->n_groups == 0 && b->n_grads == 0 && b->plan.planned() && !b->count_adds_only &&
                                 b->adds.p != nullptr;   // (deterministic or not: the same headers and sentinels at the same places)
-        const bool cells_kept = cells_pass && b->cells_current && b->cells_made == cells_now;
+        const bool cells_kept = b->plan.cells.holds(cells_pass, cells_now);
         bool lean_pb = placed && keep_slabs && lean_fl && b->own.world <= 1 && !b->deterministic && b->n_groups == 0 && b->n_grads == 0 &&
-                       b->planned && !b->count_adds_only && b->adds.p != nullptr && cells_kept &&
+                       b->plan.planned() && !b->count_adds_only && b->adds.p != nullptr && cells_kept &&
                        lists_kept /* (it sets no class-2 cell's mask bits: the saved words have them) */;
-        b->cells_current = cells_pass;
-        b->cells_made = cells_now;
+        b->plan.cells.wrote(cells_pass, cells_now);
 #ifdef SVGR_DBG_PB_STAMP
         lean_pb = false;   // (the stamps are the full form's)
 #endif
@@ -5635,7 +5559,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
         bits_implied = lean_pb;
         if (lean_pb) launch_pb(k_path_build<1, true>); else if (placed) launch_pb(k_path_build<1>); else if (bounded) launch_pb(k_path_build<2>); else launch_pb(k_path_build<0>);
 #ifdef SVGR_DBG_PB_STAMP
-        if (pb_dbg && b->planned && !b->count_adds_only) {
+        if (pb_dbg && b->plan.planned() && !b->count_adds_only) {
             static int n_dump = 0;
             if (++n_dump == 20) {  // one render, well into the run
                 HIPCHK(hipStreamSynchronize(st));
@@ -5678,8 +5602,7 @@ static int run_geometry(svgr_batch* b, int upto, bool use_vp) {
                            lists_for_plan ? b->tile_mask_kept.p : (unsigned long long*)nullptr, lists_kept ? (bits_implied ? 2 : 1) : 0);
         b->masks_zeroed = true;
     }
-    b->lists_current = lists_for_plan;
-    b->lists_made = lists_now;
+    b->plan.lists.wrote(lists_for_plan, lists_now);
     return 0;
 }
 
@@ -6319,7 +6242,7 @@ int svgr_batch_set_paints(svgr_batch* b, const double* path_paint) {
                           hipMemcpyHostToDevice, b->ctx->stream));
     HIPCHK(b->note_upload(b->ctx->stream));
     b->geometry_fresh = false; b->geometry_current = false;  // the cell headers carry the paint
-    b->cells_current = false;   // (... and the lean path build leaves the class-2 cells' headers as they are: one full pass first)
+    b->plan.paints_changed();
     return 0;
 }
 
@@ -6337,7 +6260,7 @@ int svgr_batch_set_transforms(svgr_batch* b, const double* path_m6) {
         HIPCHK(hipMemcpyAsync(b->path_m6.p, b->keep(path_m6, mbytes), mbytes, hipMemcpyHostToDevice, b->ctx->stream));
         HIPCHK(b->note_upload(b->ctx->stream));
     }
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+    b->plan.geometry_changed();
     b->hit_ready = false;
     return 0;
 }
@@ -6345,7 +6268,7 @@ int svgr_batch_set_transforms(svgr_batch* b, const double* path_m6) {
 int svgr_batch_set_bands(svgr_batch* b, int rank, int world, int strip_bands) {
     if (!b || world <= 0 || rank < 0 || rank >= world || strip_bands <= 0) return fail(SVGR_E_INVALID, "bad band selection");
     b->own = Owner{rank, world, strip_bands};
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;  // the edge / record capacities are per rank
+    b->plan.geometry_changed();  // the edge / record capacities are per rank
     b->sized = false;
     b->n_seg_list = -1;  // ... and so is the list of segments to flatten
     return 0;
@@ -6591,7 +6514,7 @@ static int spec_finish(svgr_batch* b) {
     b->n_edges_live = 0;
     for (int k = 0; k < NSH; ++k) b->n_edges_live += b->host_bd.shard[k].cursor;
     b->n_bsegs = b->host_bd.bseg_cursor;
-    b->planned = true;
+    b->plan.plan_made();
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     b->read_switches();
@@ -6612,7 +6535,7 @@ static int plan_speculative(svgr_batch* b) {
             if (int rc = plan_slab_order(b)) return rc;   // (large batches: k_path_build's work list heaviest first)
         }
         if (fin != 0) return fin;
-        b->planned = false; b->slabs_current = false; b->lists_current = false;
+        b->plan.pass_withdrawn();
     }
     return 0;
 }
@@ -6700,7 +6623,7 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
         for (int64_t i = 0; i < n; ++i) {
             svgr_batch* b = batches[i];
             HIPCHK(enter_ctx(b->ctx));
-            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+            b->plan.plan_begins();
             b->geometry_fresh = false; b->geometry_current = false;
             const int is = no_spec ? 0 : spec_issue(b, (char*)b->ctx->pinned + stage_off[(size_t)i]);
             if (is < 0) return is;
@@ -6734,8 +6657,7 @@ int svgr_batch_plan_many(svgr_batch** batches, int64_t n) {
 // integer arithmetic on the same bbox (slab_shape, owns_any), so the places tile the list exactly; the geometry cannot change
 // under a plan (set_transforms / set_bands invalidate it).
 static int plan_slab_order(svgr_batch* b) {
-    b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false;
-    b->slab_order_late = false;   // (the render that makes the order itself sets it behind this call)
+    b->plan.slab_order_begins();
     if (getenv("SVGR_SAFE_PATH")) return 0;  // (tests: the renders then take their slab places from the cursor, in arrival order)
     const size_t np = (size_t)b->n_paths;
     if (int rc = ensure_host_bbox(b)) return rc;
@@ -6780,7 +6702,7 @@ static int plan_slab_order(svgr_batch* b) {
     b->wait_uploads();
     HIPCHK(hipMemcpyAsync(b->slab_at.p, b->slab_at_host.data(), sizeof(int) * np, hipMemcpyHostToDevice, b->ctx->stream));
     HIPCHK(b->note_upload(b->ctx->stream));
-    b->slab_at_valid = true;
+    b->plan.slab_order_made();
     return 0;
 }
 
@@ -6881,7 +6803,7 @@ static int two_pass_issue(svgr_batch* b, void* staging) {
     }
     b->mask_words = (int)std::max<int64_t>(((int64_t)std::max(longest, 1) + 63) / 64, 1);
     b->masks_zeroed = false;
-    b->lists_current = false;
+    b->plan.masks_resized();
     {
         // every work array of the batch out of ONE device block (each with the eighth of slack an allocation of its own would
         // have: a re-plan of a drawing that moved a little fits the same arrays, spec_issue(again))
@@ -6945,7 +6867,7 @@ static int two_pass_finish(svgr_batch* b, const void* staging) {
     b->n_entries = b->host_bd.entry_cursor;
     b->n_edges_live = b->n_edges;
     b->n_bsegs = b->host_bd.bseg_cursor;
-    b->planned = true;
+    b->plan.plan_made();
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     b->read_switches();
@@ -6967,7 +6889,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
     if (!b) return fail(SVGR_E_INVALID, "batch is NULL");
     HIPCHK(enter_ctx(b->ctx));
     b->defer_bbox = false;
-    b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+    b->plan.plan_begins();
     b->geometry_fresh = false; b->geometry_current = false;
     {
         const bool no_spec = getenv("SVGR_NO_SPECULATIVE_PLAN") != nullptr;  // (tests exercise both planners)
@@ -6979,7 +6901,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
         const int tp = plan_two_pass(b);
         if (tp < 0) return tp;
         if (tp > 0) return 0;
-        b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+        b->plan.plan_begins();
         b->geometry_fresh = false; b->geometry_current = false;
     }
     if (int rc = b->layout_arena()) return rc;
@@ -7054,7 +6976,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
     b->n_edges_live = b->n_edges;
     b->n_bsegs = b->host_bd.bseg_cursor;
     if (int rc = plan_slab_order(b)) return rc;
-    b->planned = true;
+    b->plan.plan_made();
     b->sized = true;
     for (int k = 0; k < 4; ++k) b->sized_vp[k] = b->vp[k];
     b->read_switches();
@@ -7064,7 +6986,7 @@ static int batch_plan_impl(svgr_batch* b, bool skip_speculative) {
 
 int svgr_batch_get_stats(const svgr_batch* b, svgr_batch_stats* out) {
     if (!b || !out) return fail(SVGR_E_INVALID, "bad arguments");
-    if (!b->planned) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
+    if (!b->plan.planned()) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
     out->n_edges = b->n_edges_live;
     out->path_pixels = (int64_t)b->host_bd.path_pixels;
     out->n_band_segs = b->n_bsegs;  // (edge rows)
@@ -7086,7 +7008,7 @@ int svgr_batch_get_stats(const svgr_batch* b, svgr_batch_stats* out) {
 
 int svgr_batch_get_bboxes(const svgr_batch* b, int32_t* out) {
     if (!b || !out) return fail(SVGR_E_INVALID, "bad arguments");
-    if (!b->planned) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
+    if (!b->plan.planned()) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
     if (b->host_bbox_stale) {
         HIPCHK(enter_ctx(b->ctx));
         if (int rc = ensure_host_bbox(const_cast<svgr_batch*>(b))) return rc;
@@ -7103,7 +7025,7 @@ int svgr_batch_get_bboxes(const svgr_batch* b, int32_t* out) {
 int svgr_batch_get_extents(svgr_batch* b, double* out) {
     return abi_guard("svgr_batch_get_extents", [&]() -> int {
         if (!b || !out) return fail(SVGR_E_INVALID, "bad arguments");
-        if (!b->planned || !b->geometry_fresh)
+        if (!b->plan.planned() || !b->geometry_fresh)
             return fail(SVGR_E_STATE, "the extents are read from the plan's own geometry pass: call between svgr_batch_plan and the first render");
         const size_t np = (size_t)b->n_paths;
         if (np == 0) return 0;
@@ -7122,7 +7044,7 @@ int svgr_batch_get_extents(svgr_batch* b, double* out) {
 
 int svgr_batch_get_edges(const svgr_batch* b, double* edges, int32_t* edge_path, int64_t cap) {
     if (!b || !edges) return fail(SVGR_E_INVALID, "bad arguments");
-    if (!b->planned) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
+    if (!b->plan.planned()) return fail(SVGR_E_STATE, "svgr_batch_plan has not run");
     if (cap < b->n_edges_live) return fail(SVGR_E_INVALID, "edge buffer holds %lld, need %lld", (long long)cap, (long long)b->n_edges_live);
     if (b->n_edges_live == 0) return 0;
     HIPCHK(enter_ctx(b->ctx));
@@ -7193,7 +7115,7 @@ static int batch_all_edges_impl(svgr_batch* b, double* edges, int32_t* edge_path
 }
 
 int64_t svgr_batch_owned_rows(const svgr_batch* b) {
-    if (!b || !b->planned) return -1;
+    if (!b || !b->plan.planned()) return -1;
     if (b->own.world <= 1) return b->vp[2];
     return (int64_t)count_owned_bands(b->own, b->n_bands) * TR;
 }
@@ -7271,12 +7193,12 @@ int svgr_batch_render_windows(svgr_batch* b, int64_t n, svgr_buf* const* outs, i
 
 static int batch_render_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned flags, const int32_t* window, int phase, hipStream_t tile_st, WinTable* wt) {
     if (!b || !out) return fail(SVGR_E_INVALID, "bad arguments");
-    if (!b->planned) return fail(SVGR_E_STATE, "svgr_batch_plan must run before svgr_batch_render");
+    if (!b->plan.planned()) return fail(SVGR_E_STATE, "svgr_batch_plan must run before svgr_batch_render");
     if (out_kind < 0 || out_kind > 5) return fail(SVGR_E_INVALID, "unknown output kind %d", out_kind);
-    if (b->slab_order_pending && !b->geometry_fresh) {   // (a replay of a plan svgr_batch_draw made: its places now, once)
-        b->slab_order_pending = false;
+    if (b->plan.slab_order_pending() && !b->geometry_fresh) {   // (a replay of a plan svgr_batch_draw made: its places now, once)
+        b->plan.slab_order_taken_up();
         if (int rc = plan_slab_order(b)) return rc;
-        b->slab_order_late = true;
+        b->plan.slab_order_made_late();
     }
     const bool layers = out_kind == SVGR_OUT_MASKS_F64 || out_kind == SVGR_OUT_FILLS_F64;  // one mask / fill layer per path, back to back
     if (layers) out_kind = out_kind == SVGR_OUT_MASKS_F64 ? SVGR_OUT_MASK_F64 : SVGR_OUT_FILL_F64;
@@ -7478,7 +7400,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
     HIPCHK(enter_ctx(b->ctx));
     hipStream_t st = b->ctx->stream;
     b->defer_bbox = false;
-    if (!b->planned) {
+    if (!b->plan.planned()) {
         const bool canvas = out_kind == SVGR_OUT_CANVAS_F32 || out_kind == SVGR_OUT_CANVAS_F64;
         const bool fast = canvas && b->has_vp && b->own.world <= 1 && b->n_segs > 0 && !(flags & (SVGR_RENDER_TIMED | SVGR_RENDER_DETERMINISTIC)) &&
                           getenv("SVGR_NO_SPECULATIVE_PLAN") == nullptr && getenv("SVGR_SAFE_PATH") == nullptr;
@@ -7486,7 +7408,7 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
         if (fast) {
             const size_t stage_bytes = sizeof(BatchDev) + 16 * (size_t)b->n_paths + 256;
             if (int rc = ensure_pinned(b->ctx, stage_bytes)) return rc;
-            b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+            b->plan.plan_begins();
             b->geometry_fresh = false; b->geometry_current = false;
             b->defer_bbox = true;                                       // (the bboxes stay on the device until somebody asks: ensure_host_bbox)
             int is = spec_issue(b, b->ctx->pinned, true);                 // (the buffers of the batch's last plan as the guesses)
@@ -7502,9 +7424,9 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
         }
         if (issued) {
             // the tile kernel right behind the pass: the batch counts as planned with that pass's geometry until the pass is validated
-            b->planned = true; b->geometry_fresh = true; b->geometry_current = true;
+            b->plan.plan_made(); b->geometry_fresh = true; b->geometry_current = true;
             int rc = batch_render_impl(b, out, out_kind, flags, nullptr);
-            b->planned = false; b->slabs_current = false; b->lists_current = false; b->geometry_fresh = false; b->geometry_current = false;
+            b->plan.pass_withdrawn(); b->geometry_fresh = false; b->geometry_current = false;
             hipError_t e = hipStreamSynchronize(st);
             if (rc) return rc;
             HIPCHK(e);
@@ -7515,10 +7437,10 @@ static int batch_draw_impl(svgr_batch* b, svgr_buf* out, int out_kind, unsigned 
             if (fin < 0) return fin;
             if (fin > 0) {
                 b->geometry_fresh = false;          // (consumed by the tile kernel above)
-                b->slab_order_pending = b->n_segs > 4096;   // (large batches: k_path_build's work list heaviest first, as svgr_batch_plan leaves it)
+                b->plan.slab_order_left_to_replay(b->n_segs > 4096);  // (large batches: k_path_build's work list heaviest first, as svgr_batch_plan leaves it)
                 return 0;
             }
-            b->planned = false; b->slab_at_valid = false; b->slabs_current = false; b->lists_current = false; b->slab_order_pending = false;
+            b->plan.plan_begins();
         }
         if (int rc = batch_plan_impl(b, issued == 1)) return rc;
     }

@@ -1,7 +1,7 @@
 """What the lean placed path build (k_path_build<1, LEAN>) leaves standing between kept replays: the headers of the class-2 cells, the
 layer-edge sentinels of their add lists and their two mask bits (k_tile_lists takes those from the words it saved).  All three are
 the same bytes in every placed pass of one plan with one set of paints, so the lean form writes none of them -- and the host runs it
-only behind a placed pass that did (svgr_batch::cells_current).
+only behind a placed pass that did (PlanState::cells, csrc/svgr_plan_state.h).
 
 The cases are those of tests/pathbuild_cases.py, put into batches of more than 4096 segments exactly as
 tests/test_gpu_path_build_lean.py does (only a batch with a slab order replays under the plan's places), at both origins:
@@ -16,7 +16,8 @@ the plain float64 reference of tests/canvas_ref.py with the tolerances of tests/
 float32), the device's error word clear.  Then the sequences that must void what a lean pass relies on, or leave it valid, each step
 also against a FRESH batch of the same inputs (deterministic renders bit for bit; the others, whose adds land in another order, within
 the float64 tolerance): new paints, new transforms + draw, a window and a float64 canvas between float32 replays, a deterministic
-render between replays, another drawing on the arrays a destroyed batch left, one band's saved words made wrong
+render between replays, a second plan between replays, the same bands set again (set_bands(0, 1, 1)) in front of a plan and in front
+of a draw, another drawing on the arrays a destroyed batch left, one band's saved words made wrong
 (SVGR_DBG_STALE_BAND) where the flipped bit is a class-2 cell's and where it is not.  A fresh interpreter under SVGR_DBG_PLAN reports
 the form of every pass: the pass behind set_paints is `full`, the one behind it `lean` again.
 
@@ -242,6 +243,52 @@ def other_outputs_between(S, name):
         r.close()
 
 
+def _cut(text):
+    """(in the child interpreter) a transition: no pass behind it may be lean before a full placed pass has run"""
+    _mark(f"[transition] {text}")
+
+
+def plan_again(S, name):
+    """svgr_batch_plan between kept replays: the planner's own passes are unplanned ones and write the cells at other places"""
+    _mark(f"[case] plan again {name}")
+    with _env():
+        pb = CASES[name]
+        want = _fresh(S, pb)
+        r = _Run(S, pb)
+        r.warm()
+        r.render("lean replay before the second plan")
+        _cut("plan")
+        r.plan()
+        for nth in (1, 2, 3, 4):
+            _close64(r.render(f"replay {nth} after the second plan"), want, f"{name}: replay {nth} after the second plan")
+        r.render("float32 after the second plan", np.float32)
+        r.close()
+
+
+def same_bands(S, name):
+    """set_bands(0, 1, 1) on a batch that has all the bands already: nothing moves, and the plan is void all the same -- a new plan
+    and replays, then the same in front of a draw"""
+    _mark(f"[case] same bands {name}")
+    with _env():
+        pb = CASES[name]
+        want = _fresh(S, pb)
+        r = _Run(S, pb)
+        r.warm()
+        r.render("lean replay before set_bands")
+        _cut("set_bands, plan")
+        r.batch.set_bands(0, 1, 1)
+        r.plan()
+        for nth in (1, 2, 3, 4):
+            _close64(r.render(f"replay {nth} after set_bands and a plan"), want, f"{name}: replay {nth} after set_bands and a plan")
+        _cut("set_bands, draw")
+        r.batch.set_bands(0, 1, 1)
+        _close64(r.render("draw after set_bands", draw=True), want, f"{name}: draw after set_bands")
+        for nth in (1, 2, 3, 4):
+            _close64(r.render(f"replay {nth} after set_bands and a draw"), want, f"{name}: replay {nth} after set_bands and a draw")
+        r.render("float32 after set_bands", np.float32)
+        r.close()
+
+
 def inherited(S, first, second):
     """destroy, then a batch of another drawing (same viewport) on the arrays the first one left"""
     _mark(f"[case] inherited {second}")
@@ -299,6 +346,16 @@ def test_other_outputs_and_deterministic_renders_between_replays(S, name):
     other_outputs_between(S, name)
 
 
+@pytest.mark.parametrize("name", SEQ)
+def test_a_second_plan_between_replays(S, name):
+    plan_again(S, name)
+
+
+@pytest.mark.parametrize("name", SEQ)
+def test_the_same_bands_set_again(S, name):
+    same_bands(S, name)
+
+
 def test_another_drawing_on_inherited_arrays(S):
     inherited(S, "ends_1-o-7_83", "ends_63-o-7_83")
 
@@ -324,6 +381,9 @@ def _child():
         replays(S, name)
     new_paints(S, SEQ[0])
     other_outputs_between(S, SEQ[0])
+    for name in SEQ:
+        plan_again(S, name)
+        same_bands(S, name)
     print("[case] end", file=sys.stderr, flush=True)
 
 
@@ -337,10 +397,13 @@ def test_the_pass_behind_set_paints_is_full():
     res = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert res.returncode == 0, res.stderr[-3000:]
     got, key, what, form, cells = {}, None, None, None, None
+    cuts = {}   # per case: (what happened, the passes reported before it)
     for line in res.stderr.splitlines():
         if line.startswith("[case] "):
             key = line[7:].strip()
             got[key] = []
+        elif line.startswith("[transition] "):
+            cuts.setdefault(key, []).append((line[13:].strip(), len(got[key])))
         elif line.startswith("[pass] "):
             what = line[7:].strip()
         elif line.startswith("[geometry] path build form "):
@@ -352,21 +415,32 @@ def test_the_pass_behind_set_paints_is_full():
         elif line.startswith("[geometry] k_path_build<"):
             assert form is not None and cells is not None, line
             assert form != "lean" or cells == "current", (key, what, line)   # (the lean form never runs over cells it would have to write)
-            got[key].append((what, form, cells))
+            got[key].append((what, form, cells, int(line[len("[geometry] k_path_build<")])))   # (<1>: a placed pass)
             form = cells = None
     assert got.pop("end", None) == []
     for k, v in got.items():
-        print(k, "".join("L" if f == "lean" else "f" for _w, f, _c in v))
+        print(k, "".join("L" if f == "lean" else "f" for _w, f, _c, _m in v))
     for n in CHILD_CASES:
-        forms = "".join("L" if f == "lean" else "f" for _w, f, _c in got[f"replays {n}"])
+        forms = "".join("L" if f == "lean" else "f" for _w, f, _c, _m in got[f"replays {n}"])
         assert re.fullmatch(r"f{2,}L{4}", forms), (n, forms)
     # the fresh batch's passes come first; then: plan, the full placed pass, a lean replay -- set_paints -- full, lean, lean, lean
-    tail = [(w, f) for w, f, _c in got[f"paints {SEQ[0]}"]][-5:]
+    tail = [(w, f) for w, f, _c, _m in got[f"paints {SEQ[0]}"]][-5:]
     assert tail[0][1] == "lean" and "render 3" in tail[0][0], tail
     assert tail[1][1] == "full" and "replay 1 after set_paints" in tail[1][0], tail
     assert [f for _w, f in tail[2:]] == ["lean"] * 3, tail
     # a window, a float64 canvas and the deterministic renders (themselves full) leave the cells valid: lean right behind them
     seq = got[f"between {SEQ[0]}"]
-    by = {w.partition(" ")[2]: f for w, f, _c in seq}
+    by = {w.partition(" ")[2]: f for w, f, _c, _m in seq}
     assert by["float32 replay after the window"] == "lean" and by["float32 replay after the float64 canvas"] == "lean", seq
     assert by["deterministic between replays"] == "full" and by["replay 1 after the deterministic renders"] == "lean", seq
+    # a second plan, and the same bands set again (in front of a plan, in front of a draw): lean right before each, behind it no lean
+    # pass until a full placed pass (k_path_build<1>) has written the cells again, and the lean form comes back
+    for name in SEQ:
+        for key, n_cuts in ((f"plan again {name}", 1), (f"same bands {name}", 2)):
+            seq, ends = got[key], [at for _t, at in cuts[key]] + [len(got[key])]
+            assert len(ends) == n_cuts + 1, (key, cuts[key])
+            for (text, at), end in zip(cuts[key], ends[1:]):
+                assert seq[at - 1][1] == "lean", (key, text, seq[at - 1])
+                behind = [(f, m) for _w, f, _c, m in seq[at:end]]
+                assert ("full", 1) in behind and behind[-1][0] == "lean", (key, text, behind)
+                assert "lean" not in [f for f, _m in behind[:behind.index(("full", 1))]], (key, text, behind)
