@@ -46,7 +46,8 @@ extern "C" {
  *    svgr_deflate_chunk added (the device PNG encoder); svgr_layer_to_tensor, svgr_tensor_to_layer, svgr_tensor_block,
  *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output); svgr_quant_distinct,
  *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output); svgr_quant_dither,
- *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering) */
+ *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering); svgr_png_samples, svgr_png_filter_bytes and
+ *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -936,6 +937,36 @@ int svgr_png_filter(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, int6
 #define SVGR_DEFLATE_NO_ROOM 5   /* the output buffer is too small */
 int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffman, uint8_t* out, int64_t out_cap, int64_t* n_out);
 int svgr_deflate_chunk(void);
+
+/* PNG sample formats (color= and depth= of Layer.write_png; csrc/svgr_png.h has the arithmetic): the colour types 0 grey, 2 RGB,
+ * 4 grey + alpha and 6 RGBA at depth 8 or 16, bpp = channels * depth / 8 bytes a pixel.  svgr_deflate takes the filtered stream
+ * as it takes svgr_png_filter's.
+ * svgr_png_samples: dst (device, rows * cols * bpp bytes) <- the packed samples of src (device), pixel after pixel, a pixel's
+ * samples in the file's order, a 16-bit sample most significant byte first.  src_kind says what src holds:
+ *   RGBA_F64  rows * cols * 4 doubles, straight alpha, sRGB-encoded (svgr_layer_convert's output; a layer that is to lose its
+ *             alpha has been put over its background by the caller)
+ *   MASK_F64  rows * cols doubles, one channel; colour type 0 only
+ *   RGBA_U8   rows * cols * 4 bytes R, G, B, A; each is v / 255.0
+ * A sample is rint(v * M) saturated to [0, M], NaN giving 0, M = 255 or 65535 (at 255 svgr_layer_to_rgba8's rule).  Grey is
+ * y = (0.2126 * r + 0.7152 * g) + 0.0722 * b with every product and sum rounded on its own; colour types 0 and 2 drop alpha.
+ * Enqueued on the context's stream, no wait.  SVGR_E_INVALID for an unknown kind, colour type or depth, a mask with a colour
+ * type other than 0, an empty or oversized image, a short or misaligned buffer, or dst == src.
+ * svgr_png_filter_bytes: svgr_png_filter for rows of row_bytes bytes at bpp bytes a pixel (1, 2, 3, 4, 6 or 8): out_filtered
+ * (device, rows * (1 + row_bytes) bytes) <- per row the filter type, then its bytes; byte i of a row has the neighbours
+ * a = row[i - bpp], b = above[i], c = above[i - bpp], zero outside the image.  At bpp 4 the stream is svgr_png_filter's byte for
+ * byte.  Enqueued on the context's stream, no wait.  SVGR_E_INVALID as svgr_png_filter, and for another bpp or a row_bytes that
+ * is no multiple of it.
+ * svgr_png_filter_span: the bytes of a row that one pass of a workgroup covers (the launch seam of the filter kernel).          */
+#define SVGR_PNG_COLOR_GREY 0
+#define SVGR_PNG_COLOR_RGB 2
+#define SVGR_PNG_COLOR_GREY_ALPHA 4
+#define SVGR_PNG_COLOR_RGBA 6
+#define SVGR_PNG_SRC_RGBA_F64 0
+#define SVGR_PNG_SRC_MASK_F64 1
+#define SVGR_PNG_SRC_RGBA_U8 2
+int svgr_png_samples(svgr_ctx* ctx, const svgr_buf* src, int src_kind, int64_t rows, int64_t cols, int color, int depth, svgr_buf* dst);
+int svgr_png_filter_bytes(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t row_bytes, int bpp, int filter, svgr_buf* out_filtered);
+int svgr_png_filter_span(void);
 
 /* Tensor output (Layer.to_tensor / Layer.to_array, beyond the reference): a layer packed into the element type and layout a
  * framework wants, written by the kernel into memory the caller names -- a svgr_buf of the library's or a wrapped pointer

@@ -231,6 +231,9 @@ _PROTOS = {
     "svgr_quant_dither": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "svgr_dither_tile_rows": (C.c_int, []),
     "svgr_dither_tile_cols": (C.c_int, []),
+    "svgr_png_samples": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P]),
+    "svgr_png_filter_bytes": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P]),
+    "svgr_png_filter_span": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 
@@ -1162,6 +1165,31 @@ def png_filter(ctx: Context, rgba8: DeviceBuffer, rows: int, cols: int, filter: 
     `filter` is a type 0-4 or 5 for the adaptive choice."""
     out = ctx.alloc(max(rows, 1) * (1 + 4 * max(cols, 1)))
     _check(ctx.lib.svgr_png_filter(ctx.handle, rgba8.handle, rows, cols, filter, out.handle))
+    return out
+
+
+PNG_SRC_RGBA_F64, PNG_SRC_MASK_F64, PNG_SRC_RGBA_U8 = 0, 1, 2   # SVGR_PNG_SRC_*
+PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}                         # SVGR_PNG_COLOR_* -> samples per pixel
+
+
+def png_filter_span() -> int:
+    """Bytes of a row per pass of a workgroup of the general filter kernel (svgr_png_filter_span)."""
+    return int(load_library().svgr_png_filter_span())
+
+
+def png_samples(ctx: Context, src: DeviceBuffer, kind: int, rows: int, cols: int, color: int, depth: int) -> DeviceBuffer:
+    """svgr_png_samples: the packed samples (rows * cols * bpp bytes, on the device) of the pixels in `src`; `kind` is one of
+    PNG_SRC_*, `color` a PNG colour type (0, 2, 4, 6), `depth` 8 or 16."""
+    out = ctx.alloc(max(rows * cols, 1) * PNG_CHANNELS.get(color, 4) * 2)
+    _check(ctx.lib.svgr_png_samples(ctx.handle, src.handle, kind, rows, cols, color, depth, out.handle))
+    return out
+
+
+def png_filter_bytes(ctx: Context, src: DeviceBuffer, rows: int, row_bytes: int, bpp: int, filter: int) -> DeviceBuffer:
+    """svgr_png_filter_bytes: the filtered scanlines (rows * (1 + row_bytes) bytes, on the device) of `rows` rows of `row_bytes`
+    bytes at `bpp` bytes a pixel; `filter` is a type 0-4 or 5 for the adaptive choice."""
+    out = ctx.alloc(max(rows, 1) * (1 + max(row_bytes, 1)))
+    _check(ctx.lib.svgr_png_filter_bytes(ctx.handle, src.handle, rows, row_bytes, bpp, filter, out.handle))
     return out
 
 

@@ -9512,6 +9512,236 @@ int svgr_deflate(svgr_ctx* ctx, const svgr_buf* src, int64_t n_bytes, int huffma
 }
 }  // extern "C"
 
+// --------------------------------------------------------------------------------------
+// PNG sample formats (svgr_png_samples, svgr_png_filter_bytes): grey, grey + alpha, RGB and RGBA at 8 or 16 bits.  The arithmetic
+// is the second part of svgr_png.h; DESIGN.md 7v has the definitions.
+//
+//   k_png_samples       a lane per pixel: one 32-byte load (a double4; 8 bytes of a mask, 4 of a byte pixel), the pixel's 1 to 8
+//                       sample bytes put together in registers, and the widest stores their place allows: a dword pair at bpp
+//                       8, a dword at 4, a short at 2; at 6 a dword and a short, at 3 a short and a byte, in the order the
+//                       pixel's parity asks for; a byte at 1
+//   k_png_filter_bytes  one workgroup per row, PNGF_SPAN bytes of the row per pass, a lane four consecutive bytes of them at a time.
+//                       A row of a 1-, 2-, 3- or 6-byte format begins anywhere, so a pass first brings the ALIGNED dwords that
+//                       cover its span and the 8 bytes in front of it (the furthest a left neighbour lies back) into LDS, the
+//                       current row's and the row's above, lane t the words t, t + 256, ...  A lane then reads four consecutive words of each,
+//                       shifts them into the three dwords that begin 8 bytes in front of its own four bytes (the row's
+//                       misalignment is the same for every lane), and has x, a, b, c of its bytes in registers, a dword each:
+//                       the operands of png_filter_px, whose bytes are filtered on their own whatever the pixel size.  The adaptive
+//                       choice sums as k_png_filter does: per lane, a wave shuffle, one LDS add per wave and type
+// --------------------------------------------------------------------------------------
+constexpr int PNGF_LANE_WORDS = 8;                            // dwords of a span per lane
+constexpr int PNGF_SPAN = 4 * PNGF_LANE_WORDS * PNG_B;        // bytes of a row per pass of k_png_filter_bytes
+constexpr int PNGF_BACK = 8;                                  // bytes in front of a span that its first bytes' neighbours may lie in (the largest bpp)
+constexpr int PNGF_WORDS = (PNGF_BACK + PNGF_SPAN) / 4 + 1;   // aligned dwords that cover them at any misalignment
+
+template <int KIND>
+PNG_KERNEL(PNG_B) void k_png_samples(const void* __restrict__ src, long long n_px, int color, int depth, uint8_t* __restrict__ dst) {
+    const long long i = (long long)blockIdx.x * PNG_B + threadIdx.x;
+    if (i >= n_px) return;
+    uint64_t s;
+    if (KIND == PNG_SRC_RGBA_F64) {
+        const double4 v = ((const double4*)src)[i];
+        s = png_samples_px(v.x, v.y, v.z, v.w, color, depth);
+    } else if (KIND == PNG_SRC_MASK_F64) {
+        s = png_samples_px(((const double*)src)[i], depth);
+    } else {
+        s = png_samples_px(((const uint32_t*)src)[i], color, depth);
+    }
+    const uint32_t lo = (uint32_t)s, hi = (uint32_t)(s >> 32);
+    const int bpp = png_bpp(color, depth);   // (uniform over the launch)
+    uint8_t* o = dst + i * bpp;
+    if (bpp == 8) {
+        *(uint2*)o = make_uint2(lo, hi);
+    } else if (bpp == 4) {
+        *(uint32_t*)o = lo;
+    } else if (bpp == 2) {
+        *(uint16_t*)o = (uint16_t)lo;
+    } else if (bpp == 1) {
+        *o = (uint8_t)lo;
+    } else if (bpp == 6) {   // (6 i is a multiple of 4 at an even pixel, of 2 at an odd one)
+        if (i & 1) {
+            *(uint16_t*)o = (uint16_t)lo;
+            *(uint32_t*)(o + 2) = (lo >> 16) | (hi << 16);
+        } else {
+            *(uint32_t*)o = lo;
+            *(uint16_t*)(o + 4) = (uint16_t)hi;
+        }
+    } else {                 // bpp 3: 3 i is even at an even pixel
+        if (i & 1) {
+            *o = (uint8_t)lo;
+            *(uint16_t*)(o + 1) = (uint16_t)(lo >> 8);
+        } else {
+            *(uint16_t*)o = (uint16_t)lo;
+            o[2] = (uint8_t)(lo >> 16);
+        }
+    }
+}
+
+// Aligned dword d of an image of `total` bytes; zero in front of it and behind it, the last bytes one by one where the image does
+// not end on a dword.
+__device__ __forceinline__ uint32_t pngf_load_word(const uint8_t* __restrict__ src, long long d, long long total) {
+    const long long o = d * 4;
+    if (d < 0 || o >= total) return 0u;
+    if (o + 4 <= total) return *(const uint32_t*)(src + o);
+    uint32_t w = 0;
+    for (int k = 0; k < 3; ++k)
+        if (o + k < total) w |= (uint32_t)src[o + k] << (8 * k);
+    return w;
+}
+
+// The aligned dwords that cover `bytes` image bytes from byte `first` on (which may lie in front of the image) into LDS, zeros
+// behind them up to PNGF_WORDS; lane t has the words t, t + 256, ... (its loads are independent and go out together).  Returns
+// where in the first dword that byte is.
+__device__ __forceinline__ int pngf_stage(uint32_t* lds, const uint8_t* __restrict__ src, long long first, int bytes, long long total) {
+    const int m = (int)(first & 3), t = threadIdx.x;
+    const long long d0 = (first - m) / 4;
+    const int n_words = (m + bytes + 3) >> 2;
+    uint32_t w[PNGF_LANE_WORDS];
+#pragma unroll
+    for (int j = 0; j < PNGF_LANE_WORDS; ++j) w[j] = t + j * PNG_B < n_words ? pngf_load_word(src, d0 + t + j * PNG_B, total) : 0u;
+#pragma unroll
+    for (int j = 0; j < PNGF_LANE_WORDS; ++j) lds[t + j * PNG_B] = w[j];
+    constexpr int DONE = PNGF_LANE_WORDS * PNG_B;
+    if (t < PNGF_WORDS - DONE) lds[DONE + t] = DONE + t < n_words ? pngf_load_word(src, d0 + DONE + t, total) : 0u;
+    return m;
+}
+
+// The three dwords that begin PNGF_BACK bytes in front of lane t's four bytes, out of the staged words.
+__device__ __forceinline__ void pngf_window(const uint32_t* lds, int t, int m, uint32_t* w) {
+    const uint32_t q0 = lds[t], q1 = lds[t + 1], q2 = lds[t + 2], q3 = lds[t + 3];
+    const int sh = 8 * m;
+    w[0] = (uint32_t)((((uint64_t)q1 << 32) | q0) >> sh);
+    w[1] = (uint32_t)((((uint64_t)q2 << 32) | q1) >> sh);
+    w[2] = (uint32_t)((((uint64_t)q3 << 32) | q2) >> sh);
+}
+// The dword at byte `off` (a constant, at most 8) of such a window.
+__device__ __forceinline__ uint32_t pngf_dword(const uint32_t* w, int off) {
+    const int i = off >> 2, sh = 8 * (off & 3);
+    return sh ? (w[i] >> sh) | (w[i + 1] << (32 - sh)) : w[i];
+}
+
+// Four filtered bytes to their place in the stream, which begins anywhere: the widest stores `o`'s alignment allows.
+__device__ __forceinline__ void pngf_store(uint8_t* o, uint32_t f, int n) {
+    const int al = (int)((uintptr_t)o & 3);
+    if (n == 4 && al == 0) {
+        *(uint32_t*)o = f;
+    } else if (n == 4 && al == 2) {
+        *(uint16_t*)o = (uint16_t)f;
+        *(uint16_t*)(o + 2) = (uint16_t)(f >> 16);
+    } else if (n == 4) {
+        o[0] = (uint8_t)f;
+        *(uint16_t*)(o + 1) = (uint16_t)(f >> 8);
+        o[3] = (uint8_t)(f >> 24);
+    } else {
+        for (int k = 0; k < n; ++k) o[k] = (uint8_t)(f >> (8 * k));
+    }
+}
+
+template <int BPP>
+PNG_KERNEL(PNG_B) void k_png_filter_bytes(const uint8_t* __restrict__ src, long long total, int row_bytes, int mode, uint8_t* __restrict__ out) {
+    __shared__ uint32_t cur[PNGF_WORDS], abv[PNGF_WORDS];   // (the last lane's last window ends with the last word)
+    __shared__ uint32_t sums[PNG_FILTER_TYPES];
+    const int row = blockIdx.x, t = threadIdx.x;
+    const long long g0 = (long long)row * row_bytes;
+    int type = mode;
+    if (mode == PNG_FILTER_ADAPTIVE && t < PNG_FILTER_TYPES) sums[t] = 0;
+    uint32_t s[PNG_FILTER_TYPES] = {0, 0, 0, 0, 0};
+    uint8_t* const o_row = out + (size_t)row * (1 + (size_t)row_bytes);
+    // pass 0 sums (adaptive only), pass 1 writes
+    for (int pass = mode == PNG_FILTER_ADAPTIVE ? 0 : 1; pass < 2; ++pass) {
+        for (int s0 = 0; s0 < row_bytes; s0 += PNGF_SPAN) {
+            __syncthreads();   // (the words of the span before have been read)
+            const int need = PNGF_BACK + (row_bytes - s0 < PNGF_SPAN ? row_bytes - s0 : PNGF_SPAN);
+            const int m = pngf_stage(cur, src, g0 + s0 - PNGF_BACK, need, total);
+            const int ma = row ? pngf_stage(abv, src, g0 - row_bytes + s0 - PNGF_BACK, need, total) : 0;
+            __syncthreads();
+            for (int j = 0; j < PNGF_LANE_WORDS; ++j) {   // (lane t: the span's dwords t, t + 256, ...)
+                const int q = t + j * PNG_B, i0 = s0 + 4 * q;
+                if (i0 >= row_bytes) break;
+                uint32_t wc[3], wa[3] = {0u, 0u, 0u};
+                pngf_window(cur, q, m, wc);
+                if (row) pngf_window(abv, q, ma, wa);
+                const int n = row_bytes - i0 < 4 ? row_bytes - i0 : 4;
+                // its four bytes x, their left neighbours a, and b, c above them, a dword each: png_filter_px's operands
+                const uint32_t x = wc[2], b = wa[2];
+                uint32_t a = pngf_dword(wc, PNGF_BACK - BPP), c = pngf_dword(wa, PNGF_BACK - BPP);
+                if (i0 < BPP) {   // (the row's first pixel: nothing to its left)
+                    uint32_t keep = 0;
+                    for (int k = 0; k < 4; ++k)
+                        if (i0 + k >= BPP) keep |= 255u << (8 * k);
+                    a &= keep;
+                    c &= keep;
+                }
+                const uint32_t inside = n == 4 ? 0xFFFFFFFFu : (1u << (8 * n)) - 1u;   // (a filtered byte of 0 adds nothing to a sum)
+                if (pass == 0) {
+#pragma unroll
+                    for (int ty = 0; ty < PNG_FILTER_TYPES; ++ty) s[ty] += png_cost_px(png_filter_px(ty, x, a, b, c) & inside);
+                } else {
+                    pngf_store(o_row + 1 + i0, png_filter_px(type, x, a, b, c), n);
+                }
+            }
+        }
+        if (pass == 0) {
+#pragma unroll
+            for (int ty = 0; ty < PNG_FILTER_TYPES; ++ty) {
+                for (int d = 32; d; d >>= 1) s[ty] += __shfl_down(s[ty], d, 64);
+                if ((t & 63) == 0) atomicAdd(&sums[ty], s[ty]);
+            }
+            __syncthreads();
+            type = png_pick(sums);
+        }
+    }
+    if (t == 0) o_row[0] = (uint8_t)type;
+}
+
+template <int BPP>
+static int png_filter_bytes_launch(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t row_bytes, int filter, svgr_buf* out) {
+    return launch_tail(ctx, k_png_filter_bytes<BPP>, dim3((unsigned)rows), dim3(PNG_B), 0, (const uint8_t*)src->ptr, (long long)(rows * row_bytes),
+                       (int)row_bytes, filter, (uint8_t*)out->ptr);
+}
+
+extern "C" {
+int svgr_png_filter_span(void) { return PNGF_SPAN; }
+int svgr_png_samples(svgr_ctx* ctx, const svgr_buf* src, int src_kind, int64_t rows, int64_t cols, int color, int depth, svgr_buf* dst) {
+    if (!ctx || !src || !dst || !image_size_ok(rows, cols)) return fail(SVGR_E_INVALID, "svgr_png_samples: bad arguments");
+    static_assert(SVGR_PNG_SRC_RGBA_F64 == PNG_SRC_RGBA_F64 && SVGR_PNG_SRC_MASK_F64 == PNG_SRC_MASK_F64 && SVGR_PNG_SRC_RGBA_U8 == PNG_SRC_RGBA_U8, "source kinds");
+    static_assert(SVGR_PNG_COLOR_GREY == PNG_COLOR_GREY && SVGR_PNG_COLOR_RGB == PNG_COLOR_RGB && SVGR_PNG_COLOR_GREY_ALPHA == PNG_COLOR_GREY_ALPHA &&
+                  SVGR_PNG_COLOR_RGBA == PNG_COLOR_RGBA, "colour types");
+    const int bpp = png_bpp(color, depth);
+    if (!bpp) return fail(SVGR_E_INVALID, "svgr_png_samples: unknown colour type %d or depth %d", color, depth);
+    if (src_kind < SVGR_PNG_SRC_RGBA_F64 || src_kind > SVGR_PNG_SRC_RGBA_U8) return fail(SVGR_E_INVALID, "svgr_png_samples: unknown source kind %d", src_kind);
+    if (src_kind == SVGR_PNG_SRC_MASK_F64 && color != SVGR_PNG_COLOR_GREY) return fail(SVGR_E_INVALID, "svgr_png_samples: a mask is written as grey only");
+    const size_t n = (size_t)rows * cols, src_px = src_kind == SVGR_PNG_SRC_RGBA_F64 ? 32 : src_kind == SVGR_PNG_SRC_MASK_F64 ? 8 : 4;
+    if (src->bytes < n * src_px || dst->bytes < n * (size_t)bpp) return fail(SVGR_E_INVALID, "svgr_png_samples: buffer too small");
+    if (src->ptr == dst->ptr) return fail(SVGR_E_INVALID, "svgr_png_samples: the output must not be the source");
+    if ((uintptr_t)src->ptr % src_px || (uintptr_t)dst->ptr % 8) return fail(SVGR_E_INVALID, "svgr_png_samples: a buffer is not aligned to its elements");
+    const dim3 grid((unsigned)((n + PNG_B - 1) / PNG_B));
+    uint8_t* o = (uint8_t*)dst->ptr;
+    if (src_kind == SVGR_PNG_SRC_RGBA_F64) return launch_tail(ctx, k_png_samples<PNG_SRC_RGBA_F64>, grid, dim3(PNG_B), 0, (const void*)src->ptr, (long long)n, color, depth, o);
+    if (src_kind == SVGR_PNG_SRC_MASK_F64) return launch_tail(ctx, k_png_samples<PNG_SRC_MASK_F64>, grid, dim3(PNG_B), 0, (const void*)src->ptr, (long long)n, color, depth, o);
+    return launch_tail(ctx, k_png_samples<PNG_SRC_RGBA_U8>, grid, dim3(PNG_B), 0, (const void*)src->ptr, (long long)n, color, depth, o);
+}
+int svgr_png_filter_bytes(svgr_ctx* ctx, const svgr_buf* src, int64_t rows, int64_t row_bytes, int bpp, int filter, svgr_buf* out_filtered) {
+    if (!ctx || !src || !out_filtered) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: bad arguments");
+    if (!png_bpp_ok(bpp)) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: %d bytes per pixel is none of 1, 2, 3, 4, 6, 8", bpp);
+    if (row_bytes <= 0 || row_bytes % bpp) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: a row of %lld bytes is no whole number of %d-byte pixels", (long long)row_bytes, bpp);
+    if (!image_size_ok(rows, row_bytes / bpp)) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: bad arguments");
+    if (filter < 0 || filter > SVGR_PNG_FILTER_ADAPTIVE) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: unknown filter %d", filter);
+    if (src->bytes < (size_t)rows * row_bytes || out_filtered->bytes < (size_t)rows * (1 + (size_t)row_bytes))
+        return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: buffer too small");
+    if (src->ptr == out_filtered->ptr) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: the output must not be the source");
+    if ((uintptr_t)src->ptr % 4 || (uintptr_t)out_filtered->ptr % 4) return fail(SVGR_E_INVALID, "svgr_png_filter_bytes: a buffer is not aligned to a dword");
+    switch (bpp) {
+        case 1: return png_filter_bytes_launch<1>(ctx, src, rows, row_bytes, filter, out_filtered);
+        case 2: return png_filter_bytes_launch<2>(ctx, src, rows, row_bytes, filter, out_filtered);
+        case 3: return png_filter_bytes_launch<3>(ctx, src, rows, row_bytes, filter, out_filtered);
+        case 4: return png_filter_bytes_launch<4>(ctx, src, rows, row_bytes, filter, out_filtered);
+        case 6: return png_filter_bytes_launch<6>(ctx, src, rows, row_bytes, filter, out_filtered);
+        default: return png_filter_bytes_launch<8>(ctx, src, rows, row_bytes, filter, out_filtered);
+    }
+}
+}  // extern "C"
+
 // ======================================================================================
 // tensor output: svgr_layer_to_tensor / svgr_tensor_to_layer (csrc/svgr_tensor.h has the per-pixel arithmetic, DESIGN.md 7p the
 // rest), and the two stream-ordering entries

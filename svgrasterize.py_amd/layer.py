@@ -688,7 +688,23 @@ class Layer:
         out, rows, cols = self._to_rgba8_device()
         return out.download((rows, cols, 4), np.uint8)
 
-    def write_png(self, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None):
+    def _png_samples_device(self, fmt, kind, bg):
+        """(device buffer, rows, cols, depth): the packed samples of the layer under a format of ``png.format_arguments``."""
+        from . import png  # noqa: PLC0415
+
+        colour_type, depth = fmt[0], 8 if fmt[1] is None else fmt[1]
+        layer = self
+        if kind == _abi.PNG_SRC_RGBA_F64:
+            if colour_type in (0, 2):   # (no alpha in the file: the layer goes over its background first, as write_jpeg does)
+                layer = layer.background((1.0, 1.0, 1.0, 1.0) if bg is None else bg)
+            layer = layer.convert(pre_alpha=False, linear_rgb=False)
+        rows, cols = layer._shape[0], layer._shape[1]
+        if rows <= 0 or cols <= 0:
+            raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+        return png.samples_device(layer._device(), kind, rows, cols, colour_type, depth), rows, cols, depth
+
+    def write_png(self, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None,
+                  color=None, depth=None, bg=None):
         """PNG of the layer (Layer.write_png, S:209-213): 8-bit RGBA, filter 0, one IDAT -- byte-identical to the
         reference's file at the reference's zlib level 9 (``level``, default 9, trades size for speed; ``threads``, default 1,
         compresses in parallel pieces; the pixels are the same).  ``encoder="device"`` filters and compresses on the device
@@ -696,12 +712,26 @@ class Layer:
         and only the compressed stream crosses PCIe.  It takes ``filter`` and ``huffman`` in place of ``level`` and
         ``threads``.  ``palette`` (True, or the largest number of entries, 2 .. 256) writes an indexed file instead: the colours
         are quantised on the device (``quantize``) and only the index rows reach either encoder; ``dither`` ("ordered" or
-        "diffusion"; None and "none": no dithering) goes with it."""
+        "diffusion"; None and "none": no dithering) goes with it.
+
+        ``color`` ("rgba", "rgb", "grey-alpha", "grey"; "gray" is read too) and ``depth`` (8 or 16) choose another sample format
+        (``canvas_to_png`` has the rules); with neither, the file is the one described above.  The samples are made on the
+        device from the float layer, so depth 16 keeps what 8 bits round away.  "rgb" and "grey" have no alpha: the layer goes
+        over ``bg`` first (premultiplied linear RGBA like every paint; default opaque white), as in ``write_jpeg``; with the
+        other two ``bg`` is a ValueError.  A one-channel layer (``Path.mask``) is written with ``color="grey"`` only.  Neither
+        goes with ``palette``."""
         from . import png  # noqa: PLC0415
 
         args = png.encoder_arguments(encoder, level, threads, filter, huffman)
         max_colors = png.palette_argument(palette, args[0], filter)
         dither = png.dither_argument(dither, max_colors)
+        fmt = png.format_arguments(color, depth, palette)
+        if fmt is not None:
+            kind = png.layer_format_arguments(fmt, self.channels, bg)
+            buf, rows, cols, depth = self._png_samples_device(fmt, kind, bg)
+            return png.encode_samples(buf, rows, cols, fmt[0], depth, output, args)
+        if bg is not None:
+            raise ValueError('bg goes with the formats without alpha, color="rgb" and color="grey"')
         if max_colors is not None:
             buf, rows, cols = self._to_rgba8_device()
             kw = {"huffman": huffman} if args[0] == "device" else {"level": args[1], "threads": args[2]}
@@ -802,7 +832,8 @@ def _deflate_parallel(raw: bytes, level: int, threads: int) -> bytes:
     return bytes([cmf, flg]) + b"".join(parts) + (zlib.adler32(raw) & 0xFFFFFFFF).to_bytes(4, "big")
 
 
-def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None):
+def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str = "host", filter=None, huffman=None, palette=None, dither=None,
+                  color=None, depth=None):
     """(height, width, 4) -> PNG (canvas_to_png, S:249-274).  ``canvas`` is either the uint8 array of
     ``Layer.to_rgba8`` or float RGBA in [0, 1] (quantised like the reference: ``np.round(canvas * 255)``).
     ``level`` (default 9) is zlib's; ``threads`` (default 1) > 1 compresses the scanlines in parallel pieces: same pixels, a
@@ -825,7 +856,19 @@ def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str
     ``dither`` (with ``palette`` only; None and "none": every pixel takes its nearest entry) dithers the median cut's image on
     the device: "ordered" with the 8 x 8 Bayer matrix, "diffusion" with Floyd-Steinberg error diffusion (``quantize`` has the
     details).  The palette and the container stay as they are, only the indices change; an image kept exactly is not dithered.
-    An unknown word is a ValueError, anything but a string or None a TypeError, a dither without ``palette`` a ValueError."""
+    An unknown word is a ValueError, anything but a string or None a TypeError, a dither without ``palette`` a ValueError.
+
+    ``color`` and ``depth`` (beyond the reference; with neither, everything above) choose the sample format: ``color`` is "rgba"
+    (colour type 6, the default), "rgb" (2), "grey-alpha" (4) or "grey" (0) -- "gray" is read too --, ``depth`` 8 (the default) or
+    16; one IDAT, no ancillary chunks.  The array is then either the samples themselves -- uint8 or uint16 with as many channels
+    as the colour has, (h, w) or (h, w, 1) for grey; uint16 means depth 16, uint8 at depth 16 widens exactly (``v * 257``) -- or
+    straight-alpha sRGB RGBA, (h, w, 4) float or uint8 (``v / 255``), from which the samples are made on the device: a sample is
+    ``rint(v * M)`` saturated to [0, M] with M = 255 or 65535, NaN giving 0, 16-bit samples most significant byte first; grey is
+    the Rec. 709 luma ``(0.2126 * r + 0.7152 * g) + 0.0722 * b`` of the encoded values (grey in, grey out, at every level);
+    "rgb" and "grey" ignore alpha, as ``canvas_to_jpeg`` does.  Both encoders take every format: "host" writes filter 0 rows,
+    "device" all six ``filter`` words over rows of any pixel size.  An unknown word or depth is a ValueError, a colour that is no
+    string a TypeError, a shape that does not go with the colour a ValueError that says what does, either keyword with
+    ``palette`` a ValueError; all before any device work."""
     import io
     import zlib
 
@@ -834,6 +877,12 @@ def canvas_to_png(canvas, output=None, level=None, threads=None, *, encoder: str
     args = png.encoder_arguments(encoder, level, threads, filter, huffman)
     max_colors = png.palette_argument(palette, args[0], filter)
     dither = png.dither_argument(dither, max_colors)
+    fmt = png.format_arguments(color, depth, palette)
+    if fmt is not None:
+        rows, cols, colour_type, depth, samples, source, kind = png.canvas_source(canvas, fmt)
+        if samples is None:
+            samples = png.samples_device(source, kind, rows, cols, colour_type, depth)
+        return png.encode_samples(samples, rows, cols, colour_type, depth, output, args)
     canvas = np.asarray(canvas)
     if canvas.dtype != np.uint8:
         canvas = np.round(canvas * 255.0).astype(np.uint8)

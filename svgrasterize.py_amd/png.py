@@ -15,7 +15,11 @@ IHDR, one IDAT, IEND, the CRCs -- is written here.
 
 Indexed output (``palette=`` of the same three): the colour quantiser (quant.py, ``svgr_quant_*``) leaves a palette and the packed
 index scanlines on the device, dithered if ``dither=`` says so; either encoder compresses them, and the container gains PLTE and
-tRNS."""
+tRNS.
+
+Sample formats (``color=`` and ``depth=`` of the same three): grey, grey + alpha, RGB and RGBA at 8 or 16 bits.  The samples are
+made on the device from the float pixels (``svgr_png_samples``); the device encoder filters rows of any pixel size
+(``svgr_png_filter_bytes``), the host encoder writes filter 0 rows.  ``read_samples`` gives a file's samples back as stored."""
 from __future__ import annotations
 
 import struct
@@ -77,10 +81,9 @@ def _to8(samples: np.ndarray, depth: int) -> np.ndarray:
     return samples.astype(np.uint8)
 
 
-def read_png(data: bytes) -> np.ndarray:
-    """Decode a PNG image: ``(height, width, 4) uint8`` RGBA, straight alpha, the stored sRGB values (gAMA, iCCP, sRGB,
-    cHRM and text chunks are ignored).  16-bit samples become ``(v * 255 + 32767) // 65535``; gray below 8 bits is scaled
-    to 0-255; a tRNS colour key makes its pixels transparent.  ValueError on malformed input."""
+def _decode(data: bytes):
+    """(samples (h, w, channels) uint8 or uint16 as stored, colour type, depth, PLTE entries or None, tRNS body or None): the one
+    decoder under ``read_png`` and ``read_samples``."""
     data = bytes(data)
     ihdr = plte = trns = None
     idat = []
@@ -140,7 +143,23 @@ def read_png(data: bytes) -> np.ndarray:
         rows = _abi.png_unfilter(raw[pos:pos + ph * (rb + 1)], ph, rb, max(1, bits // 8))
         pos += ph * (rb + 1)
         samples[r0::rs, c0::cs] = _samples(rows, pw, channels, depth)
+    return samples, ctype_, depth, plte, trns
 
+
+def read_samples(data: bytes):
+    """``(samples, colour_type, depth)`` of a PNG image: the samples as the file stores them, without ``read_png``'s reduction to
+    8-bit RGBA -- ``(height, width, channels)``, uint16 at depth 16 and uint8 otherwise (depths below 8 unpacked, not scaled); for
+    a palette image the indices.  PLTE, tRNS and every ancillary chunk are left aside.  ValueError on malformed input."""
+    samples, colour_type, depth, _plte, _trns = _decode(data)
+    return samples, colour_type, depth
+
+
+def read_png(data: bytes) -> np.ndarray:
+    """Decode a PNG image: ``(height, width, 4) uint8`` RGBA, straight alpha, the stored sRGB values (gAMA, iCCP, sRGB,
+    cHRM and text chunks are ignored).  16-bit samples become ``(v * 255 + 32767) // 65535``; gray below 8 bits is scaled
+    to 0-255; a tRNS colour key makes its pixels transparent.  ValueError on malformed input."""
+    samples, ctype_, depth, plte, trns = _decode(data)
+    height, width, channels = samples.shape
     out = np.empty((height, width, 4), dtype=np.uint8)
     if ctype_ == 3:
         idx = samples[..., 0]
@@ -185,8 +204,9 @@ def _huffman_number(huffman) -> int:
     return HUFFMAN[huffman]
 
 
-def write_container(output, width: int, height: int, idat: bytes):
-    """The file around a zlib stream of 8-bit RGBA scanlines: signature, IHDR, one IDAT, IEND (canvas_to_png, S:249-274)."""
+def write_container(output, width: int, height: int, idat: bytes, colour_type: int = 6, depth: int = 8):
+    """The file around a zlib stream of scanlines, 8-bit RGBA unless said otherwise: signature, IHDR, one IDAT, IEND
+    (canvas_to_png, S:249-274)."""
     def pack(tag: bytes, data: bytes) -> None:
         output.write(struct.pack("!I", len(data)))
         output.write(tag)
@@ -194,7 +214,7 @@ def write_container(output, width: int, height: int, idat: bytes):
         output.write(struct.pack("!I", 0xFFFFFFFF & zlib.crc32(data, zlib.crc32(tag))))
 
     output.write(SIGNATURE)
-    pack(b"IHDR", struct.pack("!2I5B", width, height, 8, 6, 0, 0, 0))
+    pack(b"IHDR", struct.pack("!2I5B", width, height, depth, colour_type, 0, 0, 0))
     pack(b"IDAT", idat)
     pack(b"IEND", b"")
     return output
@@ -347,3 +367,125 @@ def encode_indexed(rgba8, rows: int, cols: int, output, max_colors: int, *, enco
             comp = zlib.compressobj(level=level)
             idat = comp.compress(raw) + comp.flush()
     return write_indexed_container(io.BytesIO() if output is None else output, int(cols), int(rows), palette, idat)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sample formats (colour types 0, 2, 4, 6 at depth 8 or 16): color= and depth= of canvas_to_png and its callers.  The samples
+# are made on the device (svgr_png_samples; csrc/svgr_png.h has the arithmetic) and either encoder takes their rows.
+# ---------------------------------------------------------------------------------------------------------------------
+COLORS = {"rgba": 6, "rgb": 2, "grey-alpha": 4, "gray-alpha": 4, "grey": 0, "gray": 0}   # SVGR_PNG_COLOR_*
+
+
+def format_arguments(color, depth, palette=None):
+    """``color`` and ``depth`` of ``canvas_to_png`` and its callers, checked: None when neither is given (8-bit RGBA by the code
+    path that has always written it), otherwise ``(colour type, depth or None)``.  An unknown colour word or depth is a ValueError,
+    a colour that is no string a TypeError, either of them next to ``palette`` a ValueError."""
+    if color is None and depth is None:
+        return None
+    if color is not None and not isinstance(color, str):
+        raise TypeError(f"PNG color is a string or None, not {type(color).__name__}")
+    if color is not None and color not in COLORS:
+        raise ValueError(f"PNG color is one of {', '.join(COLORS)}, not {color!r}")
+    if depth is not None and (isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or depth not in (8, 16)):
+        raise ValueError(f"PNG depth is 8 or 16, not {depth!r}")
+    if palette is not None and palette is not False:
+        raise ValueError("an indexed PNG has a format of its own: color and depth do not go with palette")
+    return COLORS["rgba" if color is None else color], None if depth is None else int(depth)
+
+
+def layer_format_arguments(fmt, channels: int, bg):
+    """What ``Layer.write_png`` checks for a format of ``format_arguments`` before any device work: the svgr_png_samples source
+    kind of a layer of `channels` channels.  A one-channel layer is written as grey only; ``bg`` goes with the colour types
+    without alpha (2 and 0) of an RGBA layer only."""
+    colour_type = fmt[0]
+    if channels == 1:
+        if colour_type != 0:
+            raise ValueError('Only RGBA layers are supported (a one-channel layer is written with color="grey")')
+        if bg is not None:
+            raise ValueError("a one-channel layer is written as it is: bg does not go with it")
+        return _abi.PNG_SRC_MASK_F64
+    if channels != 4:
+        raise ValueError("Only RGBA layers are supported")
+    if colour_type in (4, 6) and bg is not None:
+        raise ValueError('bg goes with the formats without alpha, color="rgb" and color="grey"')
+    return _abi.PNG_SRC_RGBA_F64
+
+
+def canvas_source(canvas, fmt):
+    """What ``canvas_to_png`` makes of its array under a format of ``format_arguments``, before any device work:
+    ``(rows, cols, colour type, depth, raw, source, kind)``.  ``raw`` is the ``(rows, cols * bpp)`` uint8 scanline bytes of an array
+    that holds the samples themselves (and ``source`` is None); otherwise ``source`` is the RGBA array to upload for
+    svgr_png_samples and ``kind`` its source kind."""
+    colour_type, depth = fmt
+    ch = _CHANNELS[colour_type]
+    a = np.asarray(canvas)
+    if a.dtype in (np.uint8, np.uint16) and ((a.ndim == 3 and a.shape[2] == ch) or (a.ndim == 2 and ch == 1)):
+        if a.dtype == np.uint16:
+            if depth == 8:
+                raise ValueError("uint16 samples are written at depth 16; depth=8 does not go with them")
+            depth = 16
+        depth = 8 if depth is None else depth
+        rows, cols = a.shape[:2]
+        if rows == 0 or cols == 0:
+            raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+        if depth == 16:   # (most significant byte first; a byte widens exactly: v * 257)
+            wide = a.astype(np.uint16) * np.uint16(257) if a.dtype == np.uint8 else a
+            raw = np.ascontiguousarray(wide.astype(">u2")).view(np.uint8).reshape(rows, cols * ch * 2)
+        else:
+            raw = np.ascontiguousarray(a).reshape(rows, cols * ch)
+        return rows, cols, colour_type, depth, raw, None, None
+    if a.ndim == 3 and a.shape[2] == 4 and (a.dtype == np.uint8 or a.dtype.kind == "f"):
+        rows, cols = a.shape[:2]
+        if rows == 0 or cols == 0:
+            raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+        depth = 8 if depth is None else depth
+        if a.dtype == np.uint8:
+            return rows, cols, colour_type, depth, None, np.ascontiguousarray(a), _abi.PNG_SRC_RGBA_U8
+        return rows, cols, colour_type, depth, None, np.ascontiguousarray(a, dtype=np.float64), _abi.PNG_SRC_RGBA_F64
+    name = next(k for k, v in COLORS.items() if v == colour_type)
+    forms = f"(h, w, {ch})" + (" or (h, w)" if ch == 1 else "")
+    raise ValueError(f'color="{name}" takes uint8 or uint16 samples shaped {forms}, or straight-alpha sRGB RGBA shaped (h, w, 4), '
+                     f"float or uint8; not {a.dtype} {a.shape}")
+
+
+def samples_device(src, kind: int, rows: int, cols: int, colour_type: int, depth: int) -> "_abi.DeviceBuffer":
+    """The packed samples of the pixels in ``src`` (a DeviceBuffer, or an array, which is uploaded), made on the device and left
+    there: ``rows * cols * bpp`` bytes."""
+    ctx = _abi.Context.get()
+    if not isinstance(src, _abi.DeviceBuffer):
+        src = ctx.from_host(np.ascontiguousarray(src))
+    return _abi.png_samples(ctx, src, kind, int(rows), int(cols), colour_type, depth)
+
+
+def encode_samples(samples, rows: int, cols: int, colour_type: int, depth: int, output, args):
+    """The PNG of packed samples -- a DeviceBuffer of ``rows * cols * bpp`` bytes or a ``(rows, cols * bpp)`` uint8 array -- into
+    ``output`` (default a new BytesIO), which is returned.  ``args`` is what ``encoder_arguments`` returned: the host encoder
+    downloads the samples and writes filter 0 rows through zlib, the device encoder filters (svgr_png_filter_bytes) and deflates
+    them there."""
+    import io
+
+    rows, cols = int(rows), int(cols)
+    bpp = _CHANNELS[colour_type] * depth // 8
+    row_bytes = cols * bpp
+    if args[0] == "device":
+        mode = _filter_number("adaptive" if args[1] is None else args[1])
+        code = _huffman_number("dynamic" if args[2] is None else args[2])
+        ctx = _abi.Context.get()
+        if not isinstance(samples, _abi.DeviceBuffer):
+            samples = ctx.from_host(np.ascontiguousarray(samples, dtype=np.uint8))
+        filtered = _abi.png_filter_bytes(ctx, samples, rows, row_bytes, bpp, mode)
+        idat = _abi.deflate(ctx, filtered, rows * (1 + row_bytes), code)
+    else:
+        _, level, threads = args
+        if isinstance(samples, _abi.DeviceBuffer):
+            samples = samples.download((rows, row_bytes), np.uint8)
+        scan = np.zeros((rows, 1 + row_bytes), dtype=np.uint8)   # filter byte 0 in front of every scanline, ONE deflate stream
+        scan[:, 1:] = np.asarray(samples, dtype=np.uint8).reshape(rows, row_bytes)
+        if threads > 1:
+            from .layer import _deflate_parallel  # noqa: PLC0415
+
+            idat = _deflate_parallel(scan.tobytes(), level, threads)
+        else:
+            comp = zlib.compressobj(level=level)
+            idat = comp.compress(scan.tobytes()) + comp.flush()
+    return write_container(io.BytesIO() if output is None else output, cols, rows, idat, colour_type, depth)

@@ -50,6 +50,38 @@ class SdfAtlas:
     def __repr__(self) -> str:
         return f"SdfAtlas(image={self.image.shape} {self.image.dtype}, size={self.size}, spread={self.spread}, cells={len(self.cells)})"
 
+    def write_png(self, output=None, **kw):
+        """The atlas image as a PNG into ``output`` (a binary file object; default a new BytesIO), which is returned: a
+        ``(rows, cols)`` field as grey, a ``(rows, cols, 4)`` MSDF image as RGBA.  A uint8 image is written at depth 8 as it is; a
+        float32 image (codes in [0, 1]) is quantised on the device, at depth 16 unless ``depth=8`` is given.  A float64 atlas holds
+        signed pixel distances, not codes: TypeError.  ``kw``: ``canvas_to_png``'s ``level``, ``threads``, ``encoder``,
+        ``filter``, ``huffman`` and ``depth``."""
+        from . import png  # noqa: PLC0415
+        from .layer import canvas_to_png  # noqa: PLC0415
+
+        unknown = set(kw) - {"level", "threads", "encoder", "filter", "huffman", "depth"}
+        if unknown:
+            raise TypeError(f"SdfAtlas.write_png: unexpected arguments {sorted(unknown)}")
+        image = np.asarray(self.image)
+        if image.dtype not in (np.uint8, np.float32):
+            raise TypeError(f"SdfAtlas.write_png writes a uint8 or float32 atlas, not {image.dtype} (signed distances are no sample codes)")
+        if not (image.ndim == 2 or (image.ndim == 3 and image.shape[2] == 4)):
+            raise ValueError(f"SdfAtlas.write_png: the image is (rows, cols) or (rows, cols, 4), not {image.shape}")
+        color = "grey" if image.ndim == 2 else "rgba"
+        depth = kw.pop("depth", None)
+        if image.dtype == np.uint8:
+            return canvas_to_png(image, output, color=color, depth=8 if depth is None else depth, **kw)
+        if image.ndim == 3:
+            return canvas_to_png(image, output, color=color, depth=16 if depth is None else depth, **kw)
+        # a float field: one channel, which canvas_to_png has no form for -- the mask source of the same device stage
+        args = png.encoder_arguments(kw.get("encoder", "host"), kw.get("level"), kw.get("threads"), kw.get("filter"), kw.get("huffman"))
+        fmt = png.format_arguments(color, 16 if depth is None else depth)
+        rows, cols = image.shape
+        if rows == 0 or cols == 0:
+            raise ValueError(f"a PNG image has at least one pixel, not {cols} x {rows}")
+        samples = png.samples_device(image.astype(np.float64), _abi.PNG_SRC_MASK_F64, rows, cols, fmt[0], fmt[1])
+        return png.encode_samples(samples, rows, cols, fmt[0], fmt[1], output, args)
+
 
 def glyph_key(glyph):
     return glyph.unicode if glyph.unicode is not None else getattr(glyph, "gid", glyph.name)

@@ -1656,15 +1656,17 @@ def _output_format(output, format):
 
 def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transform=None, linear_rgb=False, fonts=None,
                level=None, threads=None, format=None, quality: int = 90, subsampling: str = "4:2:0", *, encoder: str = "host",
-               filter=None, huffman=None, css=None, languages=("en",), palette=None, dither=None):
+               filter=None, huffman=None, css=None, languages=("en",), palette=None, dither=None, color=None, depth=None):
     """Document in, PNG out: the steps of the reference's command line (S:3796-3877) as one library call, every pixel
     operation on the device.  ``svg`` is a file path or a file object; ``bg`` / ``fg`` are colours as ``parse_color``
     returns them; ``id`` renders a single element (on its own bounding box); ``transform`` is applied on top of the x/y
     swap of presentation space; ``level`` / ``threads`` go to the PNG writer (the defaults, 9 and 1, write the reference's exact
     file, ``threads`` > 1 the same pixels much faster), and so do ``encoder``, ``filter`` and ``huffman``
     (``encoder="device"``: filters and deflate on the device, ``canvas_to_png`` has the details) and ``palette`` (an indexed
-    file of at most that many colours, quantised on the device) with ``dither`` ("ordered" or "diffusion").  Returns the PNG bytes (also written to ``output``: a path or a binary file object)
-    or None when there is nothing to draw.
+    file of at most that many colours, quantised on the device) with ``dither`` ("ordered" or "diffusion").  ``color`` ("rgba",
+    "rgb", "grey-alpha", "grey") and ``depth`` (8 or 16) choose the PNG's sample format (``canvas_to_png`` has the rules): "rgb"
+    and "grey" have no alpha, so the image lies over ``bg``, or over opaque white when there is none, as a JPEG does.  Returns
+    the PNG bytes (also written to ``output``: a path or a binary file object) or None when there is nothing to draw.
 
     ``format`` is "png" or "jpeg"; None takes it from ``output`` when that is a path ending in ``.jpg``, ``.jpeg`` or
     ``.jpe`` (any case) and is PNG otherwise.  (Before JPEG output existed such a path received PNG bytes.)  A JPEG goes
@@ -1676,6 +1678,9 @@ def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transfor
         from . import png as png_encoder  # noqa: PLC0415
 
         png_encoder.dither_argument(dither, png_encoder.palette_argument(palette, png_encoder.encoder_arguments(encoder, level, threads, filter, huffman)[0], filter))
+        png_format = png_encoder.format_arguments(color, depth, palette)
+    elif color is not None or depth is not None:
+        raise ValueError("render_svg: color and depth belong to the PNG format")
     view = Transform().matrix(0, 1, 0, 1, 0, 0)
     if transform is not None:
         view = view @ transform
@@ -1707,9 +1712,13 @@ def render_svg(svg, output=None, bg=None, fg=None, width=None, id=None, transfor
         layer = layer.convert(pre_alpha=True, linear_rgb=linear_rgb).on_canvas(int(h), int(w))
     if format == "jpeg":
         return layer.write_jpeg(output, bg=bg, quality=quality, subsampling=subsampling)
-    if bg is not None:
-        layer = layer.background(bg)
-    png = layer.write_png(None, level, threads, encoder=encoder, filter=filter, huffman=huffman, palette=palette, dither=dither).getvalue()
+    if png_format is not None and png_format[0] in (0, 2):   # (no alpha in the file: write_png puts the layer over bg, or over white)
+        png = layer.write_png(None, level, threads, encoder=encoder, filter=filter, huffman=huffman, color=color, depth=depth, bg=bg).getvalue()
+    else:
+        if bg is not None:
+            layer = layer.background(bg)
+        png = layer.write_png(None, level, threads, encoder=encoder, filter=filter, huffman=huffman, palette=palette, dither=dither,
+                              color=color, depth=depth).getvalue()
     if isinstance(output, (str, os.PathLike)):
         with open(output, "wb") as f:
             f.write(png)
