@@ -1029,35 +1029,51 @@ __device__ __forceinline__ bool hit_point(const HitQuery& q, long long group, in
     return true;
 }
 
-// A workgroup of HIT_BLOCK points against every path.  HIT_BLOCK paths at a time, a lane each, are tested against the extent of
-// the workgroup's points: a path is skipped when its b range misses the points' (no edge is then `up` or `down` for any of them)
-// or when it lies wholly at a <= min(pa) (every d of an `up` edge is then <= 0 and of a `down` edge >= 0, in the rounded arithmetic
-// as well: the differences and products of svgr_hit.h are monotone).  The edges of a path that stays go through LDS HIT_CHUNK at
-// a time; every lane reads the same address (a broadcast) and keeps its own point's winding number in a register.
-// BITS: one inside bit per (point, path) into row `slot` of `bits` (32 paths to a word); else the winding numbers into wind[id].
-template <bool BITS>
-__global__ __launch_bounds__(HIT_BLOCK) void k_hit_winding(const double* __restrict__ edges, const int* __restrict__ off, const double* __restrict__ ext,
-                                                           const uint8_t* __restrict__ rule, int n_paths, const HitQuery q, long long group0,
-                                                           int* __restrict__ wind, uint32_t* __restrict__ bits, int words) {
-    __shared__ __align__(16) double s_e[4 * HIT_CHUNK];
-    __shared__ double s_red[3][HIT_BLOCK / 64];
-    __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK];
-    const int lane = threadIdx.x;
-    const long long group = group0 + blockIdx.x;
-    double pa = 0.0, pb = 0.0;
-    long long id = 0;
+// ---- The workgroup frame of the point queries: k_hit_winding, k_sdf_distance and k_msdf_distance are these four pieces around
+// what each of them keeps per point.  A workgroup has HIT_BLOCK points and meets every path: the points' box is reduced once;
+// the paths are taken HIT_BLOCK at a time, a lane each, and tested against the box (the kernel's cull); the edges of a path that
+// stays go through LDS HIT_CHUNK at a time, prepared by the staging lane, and every lane reads the same address (a broadcast)
+// and keeps what it accumulates for its own point in registers.  The pieces take the kernel's parts as callables and know nothing
+// of the kernel that calls them; every barrier of the three kernels is in here.
+
+// The lane's point, and whether the lane has one.  A lane without a point and a point with a NaN or infinite coordinate go on
+// as NaN: every compare with an edge is false and every d2 is NaN, which fmin drops -- winding 0, +inf away, nothing kept.
+__device__ __forceinline__ bool hit_point_or_nan(const HitQuery& q, long long group, int lane, double& pa, double& pb, long long& id) {
+    pa = pb = 0.0;
+    id = 0;
     const bool live = hit_point(q, group, lane, pa, pb, id);
-    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (compares false with every edge: winding 0)
-    // the extent of the workgroup's finite points
-    double lo_a = pa == pa ? pa : INFINITY, lo_b = pb == pb ? pb : INFINITY, hi_b = pb == pb ? pb : -INFINITY;
+    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;
+    return live;
+}
+
+// The box of the workgroup's finite points and their smallest |pb| (svgr_hit.h's HitBox), the same in every lane: shuffles
+// inside a wave, a row of `s_red` per value across the waves.
+__device__ __forceinline__ HitBox hit_point_box(double pa, double pb, int lane, double (*s_red)[HIT_BLOCK / 64]) {
+    const bool fin = pa == pa;
+    double lo_a = fin ? pa : INFINITY, hi_a = fin ? pa : -INFINITY, lo_b = fin ? pb : INFINITY, hi_b = fin ? pb : -INFINITY;
+    double min_absb = fin ? fabs(pb) : INFINITY;
     for (int d = 32; d > 0; d >>= 1) {
-        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
+        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); hi_a = fmax(hi_a, __shfl_xor(hi_a, d));
+        lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
+        min_absb = fmin(min_absb, __shfl_xor(min_absb, d));
     }
-    if ((lane & 63) == 0) { s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = lo_b; s_red[2][lane >> 6] = hi_b; }
+    if ((lane & 63) == 0) {
+        s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = hi_a; s_red[2][lane >> 6] = lo_b; s_red[3][lane >> 6] = hi_b;
+        s_red[4][lane >> 6] = min_absb;
+    }
     __syncthreads();
-    for (int k = 0; k < HIT_BLOCK / 64; ++k) { lo_a = fmin(lo_a, s_red[0][k]); lo_b = fmin(lo_b, s_red[1][k]); hi_b = fmax(hi_b, s_red[2][k]); }
-    const size_t row = (size_t)((long long)blockIdx.x * HIT_BLOCK + lane) * (size_t)words;
-    uint32_t word = 0u;
+    for (int k = 0; k < HIT_BLOCK / 64; ++k) {
+        lo_a = fmin(lo_a, s_red[0][k]); hi_a = fmax(hi_a, s_red[1][k]); lo_b = fmin(lo_b, s_red[2][k]); hi_b = fmax(hi_b, s_red[3][k]);
+        min_absb = fmin(min_absb, s_red[4][k]);
+    }
+    return HitBox{lo_a, hi_a, lo_b, hi_b, min_absb};
+}
+
+// The table rounds.  The lane of path p asks `keep(p, e0, e1)` about its edges e0 .. e1 (a path not kept goes into the table
+// without edges); then every lane calls `path(p, j, e0, e1)` for the round's paths in order, j the path's place in the table
+// and e0, e1 scalars.  What a kernel tables of its own beside s_e0 / s_e1 it stores in `keep` and reads in `path`, at j.
+template <class Keep, class Path>
+__device__ __forceinline__ void hit_table_rounds(const int* __restrict__ off, int n_paths, int lane, int* s_e0, int* s_e1, Keep&& keep, Path&& path) {
     for (int base = 0; base < n_paths; base += HIT_BLOCK) {
         __syncthreads();   // (the previous round's table has been read)
         {
@@ -1065,31 +1081,72 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_hit_winding(const double* __restr
             int e0 = 0, e1 = 0;
             if (p < n_paths) {
                 e0 = off[p]; e1 = off[p + 1];
-                const double mnb = ext[4 * p + 1], mxa = ext[4 * p + 2], mxb = ext[4 * p + 3];
-                if (!(e1 > e0 && hi_b >= mnb && lo_b < mxb && mxa > lo_a)) e1 = e0;
+                if (!keep(p, e0, e1)) e1 = e0;
             }
             s_e0[lane] = e0; s_e1[lane] = e1;
         }
         __syncthreads();
         const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
-        for (int j = 0; j < n_here; ++j) {
-            const int p = base + j;
-            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+        for (int j = 0; j < n_here; ++j)
+            path(base + j, j, __builtin_amdgcn_readfirstlane(s_e0[j]), __builtin_amdgcn_readfirstlane(s_e1[j]));
+    }
+}
+
+// The chunk walk over the edges e0 .. e1 of one path (scalars).  The staging lane loads its edge, `prepare(a0, b0, a1, b1, pe)`
+// makes the ED doubles of it that the walk wants, and `each(staged)` sees every staged edge as ED / 2 double2 of LDS.
+template <int ED, class Prepare, class Each>
+__device__ __forceinline__ void hit_chunk_walk(const double* __restrict__ edges, int e0, int e1, int lane, double* s_e, Prepare&& prepare, Each&& each) {
+    static_assert(ED % 2 == 0, "a staged edge is whole double2");
+    for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
+        const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
+        __syncthreads();   // (the previous chunk has been read)
+        if (lane < n) {
+            const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
+            const double2 q0 = src[0], q1 = src[1];
+            double pe[ED];
+            prepare(q0.x, q0.y, q1.x, q1.y, pe);
+            double2* dst = (double2*)s_e + (ED / 2) * lane;
+#pragma unroll
+            for (int i = 0; i < ED / 2; ++i) dst[i] = make_double2(pe[2 * i], pe[2 * i + 1]);
+        }
+        __syncthreads();
+        for (int k = 0; k < n; ++k) each((const double2*)s_e + (ED / 2) * k);
+    }
+}
+
+// Winding numbers.  The cull: a path is skipped when its b range misses the points' (no edge is then `up` or `down` for any of
+// them) or when it lies wholly at a <= min(pa) (every d of an `up` edge is then <= 0 and of a `down` edge >= 0, in the rounded
+// arithmetic as well: the differences and products of svgr_hit.h are monotone).  A lane keeps its point's winding number.
+// BITS: one inside bit per (point, path) into row `slot` of `bits` (32 paths to a word); else the winding numbers into wind[id].
+template <bool BITS>
+__global__ __launch_bounds__(HIT_BLOCK) void k_hit_winding(const double* __restrict__ edges, const int* __restrict__ off, const double* __restrict__ ext,
+                                                           const uint8_t* __restrict__ rule, int n_paths, const HitQuery q, long long group0,
+                                                           int* __restrict__ wind, uint32_t* __restrict__ bits, int words) {
+    __shared__ __align__(16) double s_e[4 * HIT_CHUNK];
+    __shared__ double s_red[5][HIT_BLOCK / 64];
+    __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK];
+    const int lane = threadIdx.x;
+    double pa, pb;
+    long long id;
+    const bool live = hit_point_or_nan(q, group0 + blockIdx.x, lane, pa, pb, id);
+    const HitBox box = hit_point_box(pa, pb, lane, s_red);
+    const size_t row = (size_t)((long long)blockIdx.x * HIT_BLOCK + lane) * (size_t)words;
+    uint32_t word = 0u;
+    hit_table_rounds(
+        off, n_paths, lane, s_e0, s_e1,
+        [&](int p, int e0, int e1) {
+            const double mnb = ext[4 * p + 1], mxa = ext[4 * p + 2], mxb = ext[4 * p + 3];
+            // (& between the three: with && the compiler loads the numbers one behind the other's compare)
+            return e1 > e0 && ((box.hi_b >= mnb) & (box.lo_b < mxb) & (mxa > box.lo_a));
+        },
+        [&](int p, int, int e0, int e1) {
             int w = 0;
-            for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
-                const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
-                __syncthreads();   // (the previous chunk has been read)
-                if (lane < n) {
-                    const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
-                    ((double2*)s_e)[2 * lane] = src[0];
-                    ((double2*)s_e)[2 * lane + 1] = src[1];
-                }
-                __syncthreads();
-                for (int k = 0; k < n; ++k) {
-                    const double2 q0 = ((const double2*)s_e)[2 * k], q1 = ((const double2*)s_e)[2 * k + 1];
+            hit_chunk_walk<4>(
+                edges, e0, e1, lane, s_e, [](double a0, double b0, double a1, double b1, double* pe) { pe[0] = a0; pe[1] = b0; pe[2] = a1; pe[3] = b1; },
+                [&](const double2* s) {
+                    const double2 q0 = s[0], q1 = s[1];
                     w += hit_edge_term(q0.x, q0.y, q1.x, q1.y, pa, pb);
-                }
-            }
+                });
             if constexpr (BITS) {
                 if (hit_inside(w, rule[p] & 1)) word |= 1u << (p & 31);
                 if ((p & 31) == 31 || p == n_paths - 1) {
@@ -1099,8 +1156,7 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_hit_winding(const double* __restr
             } else {
                 if (live) wind[(size_t)id * (size_t)n_paths + (size_t)p] = w;
             }
-        }
-    }
+        });
 }
 
 // a lane per point: the clips and the paint order over its row of bits (svgr_hit.h), in place
@@ -1121,17 +1177,19 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_hit_resolve(uint32_t* __restrict_
 // ======================================================================================
 #include "svgr_sdf.h"
 
-// A workgroup of HIT_BLOCK points against every path, in k_hit_winding's structure: the points' extent is reduced once, the paths
-// are taken HIT_BLOCK at a time, a lane each, for the cull, and the edges of a path that stays go through LDS HIT_CHUNK at a time
-// -- prepared: the staging lane works out x, y and inv once per edge (svgr_sdf.h), so that the walk over the points has no
-// division -- and are read as broadcasts.  A lane keeps its point's min d2 and winding number in registers and takes one sqrt
-// per path.
-// The cull (finite `cull_spread` only; the host passes +inf for an infinite spread and for one below 2^-100): a path is skipped,
-// and counts as +spread, when its extent lies farther than `thr` from the points' box in a or in b, thr = spread * (1 + 2^-40) +
-// 2^-40 * (the largest magnitude among the extent's four numbers).  DESIGN.md 7r shows that every point of the workgroup then
-// gets exactly +spread from the walk as well (a distance that clamps, and winding 0), so the cull cannot show.  The side on which
-// the points' rays run THROUGH the path (the path wholly at larger a) is taken only when no point of the workgroup has |pb| <
-// 2^-400: the argument needs the predicate's products clear of underflow there.
+// one value in the encoding OUT (SDF_*) to element `at` of `out`
+template <int OUT>
+__device__ __forceinline__ void sdf_store(void* __restrict__ out, size_t at, double v, double spread) {
+    if constexpr (OUT == SDF_F64) ((double*)out)[at] = v;
+    else if constexpr (OUT == SDF_F32) ((float*)out)[at] = sdf_encode_f32(v, spread);
+    else ((uint8_t*)out)[at] = sdf_encode_u8(v, spread);
+}
+
+// Distances, on the point queries' frame (above).  The staging lane works out x, y and inv once per edge (sdf_edge_prepare), so
+// that the walk over the points has no division.  A lane keeps its point's min d2 and winding number and takes one sqrt per path.
+// The cull is sdf_out_of_reach of svgr_sdf.h on the path's extent (finite `cull_spread` only; the host passes +inf for an
+// infinite spread and for one below 2^-100): a path out of reach is skipped and counts as +spread, which DESIGN.md 7r shows to
+// be what the walk gives every point of the workgroup as well, so the cull cannot show.
 // OUT: the encoding (SDF_*).  UNION: one value per point, the minimum over the paths; else one per (point, path).  Results go to
 // out[(id - id0) * stride + p] in elements of the encoding: the caller's row-major order, the pass beginning at point id0.
 template <int OUT, bool UNION>
@@ -1142,95 +1200,35 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_sdf_distance(const double* __rest
     __shared__ double s_red[5][HIT_BLOCK / 64];
     __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK];
     const int lane = threadIdx.x;
-    const long long group = group0 + blockIdx.x;
-    double pa = 0.0, pb = 0.0;
-    long long id = 0;
-    const bool live = hit_point(q, group, lane, pa, pb, id);
-    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (every d2 is NaN, which fmin drops, and every compare false: +inf away, winding 0)
-    // the extent of the workgroup's finite points, and their smallest |pb|
-    const bool fin = pa == pa;
-    double lo_a = fin ? pa : INFINITY, hi_a = fin ? pa : -INFINITY, lo_b = fin ? pb : INFINITY, hi_b = fin ? pb : -INFINITY;
-    double min_absb = fin ? fabs(pb) : INFINITY;
-    for (int d = 32; d > 0; d >>= 1) {
-        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); hi_a = fmax(hi_a, __shfl_xor(hi_a, d));
-        lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
-        min_absb = fmin(min_absb, __shfl_xor(min_absb, d));
-    }
-    if ((lane & 63) == 0) {
-        s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = hi_a; s_red[2][lane >> 6] = lo_b; s_red[3][lane >> 6] = hi_b;
-        s_red[4][lane >> 6] = min_absb;
-    }
-    __syncthreads();
-    for (int k = 0; k < HIT_BLOCK / 64; ++k) {
-        lo_a = fmin(lo_a, s_red[0][k]); hi_a = fmax(hi_a, s_red[1][k]); lo_b = fmin(lo_b, s_red[2][k]); hi_b = fmax(hi_b, s_red[3][k]);
-        min_absb = fmin(min_absb, s_red[4][k]);
-    }
-    const bool through_ok = min_absb >= 0x1p-400;
+    double pa, pb;
+    long long id;
+    const bool live = hit_point_or_nan(q, group0 + blockIdx.x, lane, pa, pb, id);
+    const HitBox box = hit_point_box(pa, pb, lane, s_red);
     const size_t stride = UNION ? 1 : (size_t)n_paths;
     const size_t at = (size_t)(id - id0) * stride;
     double best = spread;   // (UNION: a skipped path counts as +spread, and no path can give more)
-    for (int base = 0; base < n_paths; base += HIT_BLOCK) {
-        __syncthreads();   // (the previous round's table has been read)
-        {
-            const int p = base + lane;
-            int e0 = 0, e1 = 0;
-            if (p < n_paths) {
-                e0 = off[p]; e1 = off[p + 1];
-                if (e1 > e0 && cull_spread < INFINITY) {
-                    const double mna = ext[4 * p], mnb = ext[4 * p + 1], mxa = ext[4 * p + 2], mxb = ext[4 * p + 3];
-                    const double big = fmax(fmax(fabs(mna), fabs(mxa)), fmax(fabs(mnb), fabs(mxb)));
-                    const double thr = cull_spread * (1.0 + 0x1p-40) + 0x1p-40 * big;
-                    if (mnb - hi_b > thr || lo_b - mxb > thr || lo_a - mxa > thr || (through_ok && mna - hi_a > thr)) e1 = e0;
-                }
-            }
-            s_e0[lane] = e0; s_e1[lane] = e1;
-        }
-        __syncthreads();
-        const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
-        for (int j = 0; j < n_here; ++j) {
-            const int p = base + j;
-            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+    hit_table_rounds(
+        off, n_paths, lane, s_e0, s_e1, [&](int p, int e0, int e1) { return !(e1 > e0 && sdf_out_of_reach(ext + 4 * p, box, cull_spread)); },
+        [&](int p, int, int e0, int e1) {
             double v = spread;
             if (e1 > e0) {
                 double m = INFINITY;
                 int w = 0;
-                for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
-                    const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
-                    __syncthreads();   // (the previous chunk has been read)
-                    if (lane < n) {
-                        const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
-                        const double2 q0 = src[0], q1 = src[1];
-                        double pe[SDF_EDGE_DOUBLES];
-                        sdf_edge_prepare(q0.x, q0.y, q1.x, q1.y, pe);
-                        double2* dst = (double2*)s_e + 3 * lane;
-                        dst[0] = make_double2(pe[0], pe[1]); dst[1] = make_double2(pe[2], pe[3]); dst[2] = make_double2(pe[4], pe[5]);
-                    }
-                    __syncthreads();
-                    for (int k = 0; k < n; ++k) {
-                        const double2 ab = ((const double2*)s_e)[3 * k], xy = ((const double2*)s_e)[3 * k + 1], ib = ((const double2*)s_e)[3 * k + 2];
+                hit_chunk_walk<SDF_EDGE_DOUBLES>(
+                    edges, e0, e1, lane, s_e, [](double a0, double b0, double a1, double b1, double* pe) { sdf_edge_prepare(a0, b0, a1, b1, pe); },
+                    [&](const double2* s) {
+                        const double2 ab = s[0], xy = s[1], ib = s[2];
                         const double da = pa - ab.x, db = pb - ab.y;
                         m = fmin(m, sdf_edge_d2(ab.x, ab.y, xy.x, xy.y, ib.x, pa, pb, da, db));
                         w += sdf_edge_term(ab.y, ib.y, xy.x, xy.y, pb, da, db);
-                    }
-                }
+                    });
                 v = sdf_finish(m, w, rule[p] & 1, is_signed, spread);
             }
-            if constexpr (UNION) {
-                best = fmin(best, v);
-            } else if (live) {
-                if constexpr (OUT == SDF_F64) ((double*)out)[at + (size_t)p] = v;
-                else if constexpr (OUT == SDF_F32) ((float*)out)[at + (size_t)p] = sdf_encode_f32(v, spread);
-                else ((uint8_t*)out)[at + (size_t)p] = sdf_encode_u8(v, spread);
-            }
-        }
-    }
-    if constexpr (UNION) {
-        if (live) {
-            if constexpr (OUT == SDF_F64) ((double*)out)[at] = best;
-            else if constexpr (OUT == SDF_F32) ((float*)out)[at] = sdf_encode_f32(best, spread);
-            else ((uint8_t*)out)[at] = sdf_encode_u8(best, spread);
-        }
-    }
+            if constexpr (UNION) best = fmin(best, v);
+            else if (live) sdf_store<OUT>(out, at + (size_t)p, v, spread);
+        });
+    if constexpr (UNION)
+        if (live) sdf_store<OUT>(out, at, best, spread);
 }
 
 // ======================================================================================
@@ -1253,14 +1251,13 @@ __global__ __launch_bounds__(256) void k_msdf_group_extent(const double* __restr
     gext[4 * g] = mna; gext[4 * g + 1] = mnb; gext[4 * g + 2] = mxa; gext[4 * g + 3] = mxb;
 }
 
-// k_sdf_distance's structure -- HIT_BLOCK points or a tile per workgroup, the points' extent reduced once, the path table filled
-// HIT_BLOCK paths at a time, the edges of a path that stays prepared by the staging lane (msdf_edge_prepare: 8 doubles) and read
-// from LDS as broadcasts -- over GROUPS of paths: the paths 0 .. n_paths of the table are the groups' runs one after the other,
-// path_info[p] has the path's colour mask and MSDF_PATH_* of its group, path_group[p] the group.  The cull is k_sdf_distance's
-// with the same thr and through_ok, on the union of the group's extents (gext): it skips a group as a whole, never a single path
-// of one, because only the group's edges together close (colour_edges deals a subpath's segments out to several paths) and
-// because a channel may keep an edge of any of them.  DESIGN.md 7s: the spread guard of msdf_finish makes the skipped group's
-// four values exactly the +spread they count as.
+// Multi-channel distances, on the point queries' frame, over GROUPS of paths: the paths 0 .. n_paths of the table are the groups'
+// runs one after the other, path_info[p] has the path's colour mask and MSDF_PATH_* of its group (tabled in s_info beside the
+// edges), path_group[p] the group.  The staging lane prepares 8 doubles per edge (msdf_edge_prepare).  The cull is
+// sdf_out_of_reach on the union of the group's extents (gext): it skips a group as a whole, never a single path of one, because
+// only the group's edges together close (colour_edges deals a subpath's segments out to several paths) and because a channel may
+// keep an edge of any of them.  DESIGN.md 7s: the spread guard of msdf_finish makes the skipped group's four values exactly the
+// +spread they count as.
 // A lane keeps one MsdfState in registers: A's min d2 and winding number and (d2, o, perp) for each of the three channels.  It
 // lives across the rounds of the table, as a group may straddle two; at a group's last path the lane takes the one sqrt, the
 // repair and the union.  A path's mask is wave-uniform, so the channel updates of msdf_edge sit behind scalar branches.
@@ -1274,89 +1271,40 @@ __global__ __launch_bounds__(HIT_BLOCK) void k_msdf_distance(const double* __res
     __shared__ double s_red[5][HIT_BLOCK / 64];
     __shared__ int s_e0[HIT_BLOCK], s_e1[HIT_BLOCK], s_info[HIT_BLOCK];
     const int lane = threadIdx.x;
-    const long long group = group0 + blockIdx.x;
-    double pa = 0.0, pb = 0.0;
-    long long id = 0;
-    const bool live = hit_point(q, group, lane, pa, pb, id);
-    if (!live || !hit_finite(pa, pb)) pa = pb = NAN;   // (every d2 is NaN, which fmin drops, and every compare false: nothing is kept)
+    double pa, pb;
+    long long id;
+    const bool live = hit_point_or_nan(q, group0 + blockIdx.x, lane, pa, pb, id);
     const bool fin = pa == pa;
-    double lo_a = fin ? pa : INFINITY, hi_a = fin ? pa : -INFINITY, lo_b = fin ? pb : INFINITY, hi_b = fin ? pb : -INFINITY;
-    double min_absb = fin ? fabs(pb) : INFINITY;
-    for (int d = 32; d > 0; d >>= 1) {
-        lo_a = fmin(lo_a, __shfl_xor(lo_a, d)); hi_a = fmax(hi_a, __shfl_xor(hi_a, d));
-        lo_b = fmin(lo_b, __shfl_xor(lo_b, d)); hi_b = fmax(hi_b, __shfl_xor(hi_b, d));
-        min_absb = fmin(min_absb, __shfl_xor(min_absb, d));
-    }
-    if ((lane & 63) == 0) {
-        s_red[0][lane >> 6] = lo_a; s_red[1][lane >> 6] = hi_a; s_red[2][lane >> 6] = lo_b; s_red[3][lane >> 6] = hi_b;
-        s_red[4][lane >> 6] = min_absb;
-    }
-    __syncthreads();
-    for (int k = 0; k < HIT_BLOCK / 64; ++k) {
-        lo_a = fmin(lo_a, s_red[0][k]); hi_a = fmax(hi_a, s_red[1][k]); lo_b = fmin(lo_b, s_red[2][k]); hi_b = fmax(hi_b, s_red[3][k]);
-        min_absb = fmin(min_absb, s_red[4][k]);
-    }
-    const bool through_ok = min_absb >= 0x1p-400;
+    const HitBox box = hit_point_box(pa, pb, lane, s_red);
     double best[4] = {spread, spread, spread, spread};   // (a skipped group counts as +spread, and no group can give more)
     MsdfState state;
     msdf_begin(state);
     bool touched = false;   // (block-uniform: the group at hand has had an edge)
-    for (int base = 0; base < n_paths; base += HIT_BLOCK) {
-        __syncthreads();   // (the previous round's table has been read)
-        {
-            const int p = base + lane;
-            int e0 = 0, e1 = 0, info = 0;
-            if (p < n_paths) {
-                e0 = off[p]; e1 = off[p + 1];
-                info = path_info[p];
-                if (e1 > e0 && cull_spread < INFINITY) {
-                    const int g = path_group[p];
-                    const double mna = gext[4 * g], mnb = gext[4 * g + 1], mxa = gext[4 * g + 2], mxb = gext[4 * g + 3];
-                    const double big = fmax(fmax(fabs(mna), fabs(mxa)), fmax(fabs(mnb), fabs(mxb)));
-                    const double thr = cull_spread * (1.0 + 0x1p-40) + 0x1p-40 * big;
-                    if (mnb - hi_b > thr || lo_b - mxb > thr || lo_a - mxa > thr || (through_ok && mna - hi_a > thr)) e1 = e0;
-                }
-            }
-            s_e0[lane] = e0; s_e1[lane] = e1; s_info[lane] = info;
-        }
-        __syncthreads();
-        const int n_here = n_paths - base < HIT_BLOCK ? n_paths - base : HIT_BLOCK;
-        for (int j = 0; j < n_here; ++j) {
-            const int e0 = __builtin_amdgcn_readfirstlane(s_e0[j]), e1 = __builtin_amdgcn_readfirstlane(s_e1[j]);
+    hit_table_rounds(
+        off, n_paths, lane, s_e0, s_e1,
+        [&](int p, int e0, int e1) {
+            s_info[lane] = path_info[p];
+            return !(e1 > e0 && sdf_out_of_reach(gext + 4 * path_group[p], box, cull_spread));
+        },
+        [&](int, int j, int e0, int e1) {
             const int info = __builtin_amdgcn_readfirstlane(s_info[j]);
             if (e1 > e0) {
                 touched = true;
-                for (int c0 = e0; c0 < e1; c0 += HIT_CHUNK) {
-                    const int n = e1 - c0 < HIT_CHUNK ? e1 - c0 : HIT_CHUNK;
-                    __syncthreads();   // (the previous chunk has been read)
-                    if (lane < n) {
-                        const double2* src = (const double2*)(edges + 4 * (size_t)(c0 + lane));
-                        const double2 q0 = src[0], q1 = src[1];
-                        double pe[MSDF_EDGE_DOUBLES];
-                        msdf_edge_prepare(q0.x, q0.y, q1.x, q1.y, pe);
-                        double2* dst = (double2*)s_e + 4 * lane;
-                        dst[0] = make_double2(pe[0], pe[1]); dst[1] = make_double2(pe[2], pe[3]);
-                        dst[2] = make_double2(pe[4], pe[5]); dst[3] = make_double2(pe[6], pe[7]);
-                    }
-                    __syncthreads();
-                    for (int k = 0; k < n; ++k) {
-                        const double2 ab = ((const double2*)s_e)[4 * k], xy = ((const double2*)s_e)[4 * k + 1];
-                        const double2 ia = ((const double2*)s_e)[4 * k + 2], br = ((const double2*)s_e)[4 * k + 3];
+                hit_chunk_walk<MSDF_EDGE_DOUBLES>(
+                    edges, e0, e1, lane, s_e, [](double a0, double b0, double a1, double b1, double* pe) { msdf_edge_prepare(a0, b0, a1, b1, pe); },
+                    [&](const double2* s) {
+                        const double2 ab = s[0], xy = s[1], ia = s[2], br = s[3];
                         msdf_edge(state, info & 7, ab.x, ab.y, xy.x, xy.y, ia.x, ia.y, br.x, br.y, pa, pb);
-                    }
-                }
+                    });
             }
-            if (info & MSDF_PATH_LAST) {
-                if (touched) {
-                    double v[4];
-                    msdf_finish(state, (info & MSDF_PATH_EVENODD) ? 1 : 0, (info & MSDF_PATH_NEGATIVE) ? -1 : 1, spread, fin, v);
-                    msdf_union(best, v);
-                    msdf_begin(state);
-                    touched = false;
-                }
+            if ((info & MSDF_PATH_LAST) && touched) {
+                double v[4];
+                msdf_finish(state, (info & MSDF_PATH_EVENODD) ? 1 : 0, (info & MSDF_PATH_NEGATIVE) ? -1 : 1, spread, fin, v);
+                msdf_union(best, v);
+                msdf_begin(state);
+                touched = false;
             }
-        }
-    }
+        });
     if (live) {
         const size_t at = 4 * (size_t)(id - id0);
         if constexpr (OUT == SDF_F64) {
@@ -10059,6 +10007,62 @@ static int hit_upload_points(svgr_batch* b, const double* points, int64_t n_poin
     return 0;
 }
 
+// ---- what the two distance entries (svgr_batch_distance, svgr_batch_msdf) share
+// the checks of the flags, the encoding (into `enc`) and the spread, in the order the entries report them
+static int distance_encoding(const char* entry, int flags, int known_flags, double spread, int& enc) {
+    if (flags & ~known_flags) return fail(SVGR_E_INVALID, "%s: unknown flags 0x%x", entry, (unsigned)flags);
+    enc = flags & SVGR_SDF_ENCODING_MASK;
+    if (enc >= SDF_ENCODINGS) return fail(SVGR_E_INVALID, "%s: unknown encoding %d", entry, enc);
+    if (!(spread > 0.0)) return fail(SVGR_E_INVALID, "%s: the spread is +inf or a finite value > 0, not %g", entry, spread);
+    if (enc != SDF_F64 && !(spread < INFINITY)) return fail(SVGR_E_INVALID, "%s: the float32 and uint8 encodings need a finite spread", entry);
+    return 0;
+}
+static_assert(SVGR_MSDF_ENCODING_MASK == SVGR_SDF_ENCODING_MASK && SVGR_MSDF_F64 == SDF_F64 && SVGR_MSDF_F32 == SDF_F32 && SVGR_MSDF_U8 == SDF_U8,
+              "the two entries name the same encodings");
+// the encoding as a compile-time value: `launch(std::integral_constant<int, SDF_*>{})`
+template <class F>
+static void with_sdf_encoding(int enc, F&& launch) {
+    if (enc == SDF_F64) launch(std::integral_constant<int, SDF_F64>{});
+    else if (enc == SDF_F32) launch(std::integral_constant<int, SDF_F32>{});
+    else launch(std::integral_constant<int, SDF_U8>{});
+}
+// what a query without paths answers, on the host: +spread in every one of `n` elements of the caller's
+static int distance_fill_spread(void* out, int64_t n, int enc, double spread) {
+    for (int64_t i = 0; i < n; ++i) {
+        if (enc == SDF_F64) ((double*)out)[i] = spread;
+        else if (enc == SDF_F32) ((float*)out)[i] = sdf_encode_f32(spread, spread);
+        else ((uint8_t*)out)[i] = sdf_encode_u8(spread, spread);
+    }
+    return 0;
+}
+// the spread the kernels cull with (sdf_out_of_reach): none for an infinite spread and for one below 2^-100
+static double distance_cull_spread(double spread) { return (spread < INFINITY && spread >= 0x1p-100) ? spread : (double)INFINITY; }
+// The points go through in passes of whole workgroups -- of whole rows of tiles for a grid, so that a pass is a contiguous run
+// of the caller's row-major order -- as many at a time as the scratch holds: `launch(first workgroup, workgroups, first point)`
+// enqueues a pass that writes `point_bytes` per point into `d_out` (the entry's own block, allocated here), and the run is
+// copied out behind it.  Returns behind the wait for the last copy.
+template <class Launch>
+static int distance_passes(svgr_batch* b, const HitQuery& q, bool grid, long long n_wgs, int64_t n_points, size_t point_bytes, size_t scratch_bytes,
+                           PoolBlock& d_out, void* out, Launch&& launch) {
+    hipStream_t st = b->ctx->stream;
+    // a pass unit: a workgroup's points, or a row of tiles of a grid
+    const long long unit_groups = grid ? q.tiles_x : 1, unit_points = grid ? HIT_TILE * q.cols : HIT_BLOCK;
+    const long long n_units = n_wgs / unit_groups;
+    const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
+    const long long per_pass = std::min<long long>(n_units, std::max<long long>((long long)(budget / (point_bytes * (size_t)unit_points)), 1));
+    const long long pass_points = std::min<long long>(n_points, per_pass * unit_points);
+    HIPCHK(d_out.alloc(point_bytes * (size_t)pass_points));
+    for (long long u0 = 0; u0 < n_units; u0 += per_pass) {
+        const long long nu = std::min<long long>(per_pass, n_units - u0);
+        const long long i0 = u0 * unit_points, i1 = std::min<long long>(n_points, (u0 + nu) * unit_points);
+        launch(u0 * unit_groups, nu * unit_groups, i0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" {
 int svgr_hit_block(void) { return HIT_BLOCK; }
 int svgr_hit_chunk(void) { return HIT_CHUNK; }
@@ -10168,88 +10172,53 @@ int svgr_batch_pick(svgr_batch* b, const double* points, const int64_t* grid, in
     });
 }
 
-// Signed distance fields (the arithmetic and its contract: svgr_sdf.h).  The points go through in passes of whole
-// workgroups -- of whole rows of tiles for a grid, so that a pass is a contiguous run of the caller's row-major order -- as
-// many at a time as the scratch holds.
+// Signed distance fields (the arithmetic and its contract: svgr_sdf.h).
 int svgr_batch_distance(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags, size_t scratch_bytes,
                         void* out) {
     static const char* entry = "svgr_batch_distance";
     return abi_guard(entry, [&]() -> int {
         if (!b || n_points < 0) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
-        if (flags & ~(SVGR_SDF_ENCODING_MASK | SVGR_SDF_UNION | SVGR_SDF_UNSIGNED)) return fail(SVGR_E_INVALID, "%s: unknown flags 0x%x", entry, (unsigned)flags);
-        const int enc = flags & SVGR_SDF_ENCODING_MASK;
-        if (enc >= SDF_ENCODINGS) return fail(SVGR_E_INVALID, "%s: unknown encoding %d", entry, enc);
-        if (!(spread > 0.0)) return fail(SVGR_E_INVALID, "%s: the spread is +inf or a finite value > 0, not %g", entry, spread);
-        if (enc != SDF_F64 && !(spread < INFINITY)) return fail(SVGR_E_INVALID, "%s: the float32 and uint8 encodings need a finite spread", entry);
+        int enc = 0;
+        if (int rc = distance_encoding(entry, flags, SVGR_SDF_ENCODING_MASK | SVGR_SDF_UNION | SVGR_SDF_UNSIGNED, spread, enc)) return rc;
         PoolBlock d_pts, d_out;
         HitQuery q;
-        long long n_groups = 0;
-        if (int rc = hit_query(entry, points, grid, n_points, q, n_groups)) return rc;
+        long long n_wgs = 0;
+        if (int rc = hit_query(entry, points, grid, n_points, q, n_wgs)) return rc;
         const int64_t np = b->n_paths;
         const bool uni = (flags & SVGR_SDF_UNION) != 0;
         if (n_points == 0 || (np == 0 && !uni)) return 0;
         if (!uni && n_points > 0x7fffffffll / np) return fail(SVGR_E_OVERFLOW, "%s: %lld points x %lld paths leave 31 bits", entry, (long long)n_points, (long long)np);
         if (!out) return fail(SVGR_E_INVALID, "%s: out is NULL", entry);
-        const size_t elem = (size_t)sdf_elem_bytes(enc);
-        if (np == 0) {   // a union over no paths: +spread everywhere
-            for (int64_t i = 0; i < n_points; ++i) {
-                if (enc == SDF_F64) ((double*)out)[i] = spread;
-                else if (enc == SDF_F32) ((float*)out)[i] = sdf_encode_f32(spread, spread);
-                else ((uint8_t*)out)[i] = sdf_encode_u8(spread, spread);
-            }
-            return 0;
-        }
+        if (np == 0) return distance_fill_spread(out, n_points, enc, spread);   // a union over no paths
         HIPCHK(enter_ctx(b->ctx));
         hipStream_t st = b->ctx->stream;
         if (int rc = hit_prepare(b)) return rc;
         if (int rc = hit_upload_points(b, points, n_points, d_pts, q)) return rc;
-        // a pass unit: a workgroup's points, or a row of tiles of a grid
-        const size_t point_bytes = elem * (uni ? 1 : (size_t)np);
-        const long long unit_groups = grid ? q.tiles_x : 1, unit_points = grid ? HIT_TILE * q.cols : HIT_BLOCK;
-        const long long n_units = n_groups / unit_groups;
-        const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
-        const long long per_pass = std::min<long long>(n_units, std::max<long long>((long long)(budget / (point_bytes * (size_t)unit_points)), 1));
-        const long long pass_points = std::min<long long>(n_points, per_pass * unit_points);
-        HIPCHK(d_out.alloc(point_bytes * (size_t)pass_points));
-        const double cull_spread = (spread < INFINITY && spread >= 0x1p-100) ? spread : (double)INFINITY;
+        const double cull_spread = distance_cull_spread(spread);
         const int is_signed = (flags & SVGR_SDF_UNSIGNED) ? 0 : 1;
-        for (long long u0 = 0; u0 < n_units; u0 += per_pass) {
-            const long long nu = std::min<long long>(per_pass, n_units - u0);
-            const long long i0 = u0 * unit_points, i1 = std::min<long long>(n_points, (u0 + nu) * unit_points);
-            const dim3 g((unsigned)(nu * unit_groups)), blk(HIT_BLOCK);
-#define SDF_LAUNCH(OUT, UNI)                                                                                                                   \
-    SVGR_LAUNCH((k_sdf_distance<OUT, UNI>), g, blk, 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p, (const double*)b->hit_ext.p, \
-                (const uint8_t*)b->path_rule.p, (int)np, q, u0 * unit_groups, i0, spread, cull_spread, is_signed, d_out.p)
-            if (uni) {
-                if (enc == SDF_F64) SDF_LAUNCH(SDF_F64, true);
-                else if (enc == SDF_F32) SDF_LAUNCH(SDF_F32, true);
-                else SDF_LAUNCH(SDF_U8, true);
-            } else {
-                if (enc == SDF_F64) SDF_LAUNCH(SDF_F64, false);
-                else if (enc == SDF_F32) SDF_LAUNCH(SDF_F32, false);
-                else SDF_LAUNCH(SDF_U8, false);
-            }
-#undef SDF_LAUNCH
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
+        const size_t point_bytes = (size_t)sdf_elem_bytes(enc) * (uni ? 1 : (size_t)np);
+        return distance_passes(b, q, grid != nullptr, n_wgs, n_points, point_bytes, scratch_bytes, d_out, out, [&](long long wg0, long long wgs, long long i0) {
+            with_sdf_encoding(enc, [&](auto e) {
+                auto launch = [&](auto kernel) {
+                    SVGR_LAUNCH(kernel, dim3((unsigned)wgs), dim3(HIT_BLOCK), 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p,
+                                (const double*)b->hit_ext.p, (const uint8_t*)b->path_rule.p, (int)np, q, wg0, i0, spread, cull_spread, is_signed, d_out.p);
+                };
+                if (uni) launch(k_sdf_distance<decltype(e)::value, true>);
+                else launch(k_sdf_distance<decltype(e)::value, false>);
+            });
+        });
     });
 }
 
-// Multi-channel distance fields (the arithmetic and its contract: svgr_msdf.h): svgr_batch_distance's frame -- the
-// kept edges, the point forms, the passes -- with four values to a point and the groups' tables in one upload.
+// Multi-channel distance fields (the arithmetic and its contract: svgr_msdf.h): four values to a point, and the
+// groups' tables in one upload.
 int svgr_batch_msdf(svgr_batch* b, const double* points, const int64_t* grid, int64_t n_points, double spread, int flags, const uint8_t* colour,
                     const int32_t* group_off, const int8_t* orient, int64_t n_groups, size_t scratch_bytes, void* out) {
     static const char* entry = "svgr_batch_msdf";
     return abi_guard(entry, [&]() -> int {
         if (!b || n_points < 0 || n_groups < 0 || n_groups > 0x7fffffffll) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
-        if (flags & ~SVGR_MSDF_ENCODING_MASK) return fail(SVGR_E_INVALID, "%s: unknown flags 0x%x", entry, (unsigned)flags);
-        const int enc = flags & SVGR_MSDF_ENCODING_MASK;
-        if (enc >= SDF_ENCODINGS) return fail(SVGR_E_INVALID, "%s: unknown encoding %d", entry, enc);
-        if (!(spread > 0.0)) return fail(SVGR_E_INVALID, "%s: the spread is +inf or a finite value > 0, not %g", entry, spread);
-        if (enc != SDF_F64 && !(spread < INFINITY)) return fail(SVGR_E_INVALID, "%s: the float32 and uint8 encodings need a finite spread", entry);
+        int enc = 0;
+        if (int rc = distance_encoding(entry, flags, SVGR_MSDF_ENCODING_MASK, spread, enc)) return rc;
         PoolBlock d_pts, d_out;
         HitQuery q;
         long long n_wgs = 0;
@@ -10270,16 +10239,8 @@ int svgr_batch_msdf(svgr_batch* b, const double* points, const int64_t* grid, in
         }
         if (n_points == 0) return 0;
         if (!out) return fail(SVGR_E_INVALID, "%s: out is NULL", entry);
-        const size_t elem = (size_t)sdf_elem_bytes(enc);
         const int used = n_groups > 0 ? group_off[n_groups] : 0;   // the paths the groups cover: 0 .. used
-        if (used == 0) {   // no group, or none with a path: +spread everywhere
-            for (int64_t i = 0; i < 4 * n_points; ++i) {
-                if (enc == SDF_F64) ((double*)out)[i] = spread;
-                else if (enc == SDF_F32) ((float*)out)[i] = sdf_encode_f32(spread, spread);
-                else ((uint8_t*)out)[i] = sdf_encode_u8(spread, spread);
-            }
-            return 0;
-        }
+        if (used == 0) return distance_fill_spread(out, 4 * n_points, enc, spread);   // no group, or none with a path
         // per path of the groups: its colour and its group's marks, and its group
         std::vector<uint8_t> info((size_t)used);
         std::vector<int32_t> owner((size_t)used);
@@ -10300,31 +10261,15 @@ int svgr_batch_msdf(svgr_batch* b, const double* points, const int64_t* grid, in
         double* gext = f.scratch<double>(4 * (size_t)n_groups);
         if (f.err) return f.err;
         SVGR_LAUNCH(k_msdf_group_extent, grid1((size_t)n_groups), dim3(256), 0, st, (const double*)b->hit_ext.p, (const int32_t*)s_go.on(f.in.p), (int)n_groups, gext);
-        // a pass unit: a workgroup's points, or a row of tiles of a grid
-        const size_t point_bytes = 4 * elem;
-        const long long unit_groups = grid ? q.tiles_x : 1, unit_points = grid ? HIT_TILE * q.cols : HIT_BLOCK;
-        const long long n_units = n_wgs / unit_groups;
-        const size_t budget = scratch_bytes ? scratch_bytes : (size_t)256 << 20;
-        const long long per_pass = std::min<long long>(n_units, std::max<long long>((long long)(budget / (point_bytes * (size_t)unit_points)), 1));
-        const long long pass_points = std::min<long long>(n_points, per_pass * unit_points);
-        HIPCHK(d_out.alloc(point_bytes * (size_t)pass_points));
-        const double cull_spread = (spread < INFINITY && spread >= 0x1p-100) ? spread : (double)INFINITY;
-        for (long long u0 = 0; u0 < n_units; u0 += per_pass) {
-            const long long nu = std::min<long long>(per_pass, n_units - u0);
-            const long long i0 = u0 * unit_points, i1 = std::min<long long>(n_points, (u0 + nu) * unit_points);
-            const dim3 g((unsigned)(nu * unit_groups)), blk(HIT_BLOCK);
-#define MSDF_LAUNCH(OUT)                                                                                                                \
-    SVGR_LAUNCH((k_msdf_distance<OUT>), g, blk, 0, st, (const double*)b->hit_edges.p, (const int*)b->hit_off.p, (const double*)gext,     \
-                (const uint8_t*)s_info.on(f.in.p), (const int32_t*)s_own.on(f.in.p), used, q, u0 * unit_groups, i0, spread, cull_spread, d_out.p)
-            if (enc == SDF_F64) MSDF_LAUNCH(SDF_F64);
-            else if (enc == SDF_F32) MSDF_LAUNCH(SDF_F32);
-            else MSDF_LAUNCH(SDF_U8);
-#undef MSDF_LAUNCH
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync((unsigned char*)out + point_bytes * (size_t)i0, d_out.p, point_bytes * (size_t)(i1 - i0), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
-        return 0;
+        const double cull_spread = distance_cull_spread(spread);
+        return distance_passes(b, q, grid != nullptr, n_wgs, n_points, 4 * (size_t)sdf_elem_bytes(enc), scratch_bytes, d_out, out,
+                               [&](long long wg0, long long wgs, long long i0) {
+                                   with_sdf_encoding(enc, [&](auto e) {
+                                       SVGR_LAUNCH((k_msdf_distance<decltype(e)::value>), dim3((unsigned)wgs), dim3(HIT_BLOCK), 0, st, (const double*)b->hit_edges.p,
+                                                   (const int*)b->hit_off.p, (const double*)gext, (const uint8_t*)s_info.on(f.in.p),
+                                                   (const int32_t*)s_own.on(f.in.p), used, q, wg0, i0, spread, cull_spread, d_out.p);
+                                   });
+                               });
     });
 }
 }  // extern "C"

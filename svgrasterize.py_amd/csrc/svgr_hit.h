@@ -37,6 +37,12 @@ constexpr int HIT_TILE = 16;
 constexpr int HIT_CHUNK = 256;   // edges of a path staged through LDS at a time (8 KiB)
 static_assert(HIT_TILE * HIT_TILE == HIT_BLOCK, "a workgroup of a grid query is one square tile");
 
+// the box of a workgroup's finite points, lo <= hi in a and in b, and their smallest |pb|; without a finite point lo = +inf,
+// hi = -inf and min_absb = +inf (what the point queries' culls test a path's extent against)
+struct HitBox {
+    double lo_a, hi_a, lo_b, hi_b, min_absb;
+};
+
 // x - x is 0 for a finite x and NaN for NaN and +-inf
 HIT_HD bool hit_finite(double pa, double pb) { return (pa - pa == 0.0) && (pb - pb == 0.0); }
 

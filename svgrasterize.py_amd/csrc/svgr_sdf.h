@@ -98,6 +98,22 @@ HIT_HD double sdf_path_distance(const double* edges, long long n, int evenodd, i
     return sdf_finish(m, w, evenodd, is_signed, spread);
 }
 
+// The distance kernels' cull: may the path (or group of paths) with the extent ext[0 .. 4) = min a, min b, max a, max b be left
+// out for EVERY point of `box`?  Never for cull_spread = +inf.  Else it is out of reach when the extent lies farther than
+//     thr = cull_spread * (1 + 2^-40) + 2^-40 * (the largest magnitude among the extent's four numbers)
+// from the box in a or in b.  DESIGN.md 7r shows that sdf_path_distance then gives every point of the box exactly +spread (a
+// distance that clamps, and winding 0), so a caller that counts the path as +spread instead cannot be told from one that walks
+// it; tests/test_sdf_host.py holds both the predicate and that claim.  The side on which the points' rays run THROUGH the path
+// (the path wholly at larger a) is taken only when no point of the box has |pb| < 2^-400: the argument needs the winding term's
+// products clear of underflow there.  An empty box (no finite point) is out of reach of everything.
+HIT_HD bool sdf_out_of_reach(const double* ext, const HitBox& box, double cull_spread) {
+    if (!(cull_spread < INFINITY)) return false;
+    const double mna = ext[0], mnb = ext[1], mxa = ext[2], mxb = ext[3];
+    const double big = fmax(fmax(fabs(mna), fabs(mxa)), fmax(fabs(mnb), fabs(mxb)));
+    const double thr = cull_spread * (1.0 + 0x1p-40) + 0x1p-40 * big;
+    return mnb - box.hi_b > thr || box.lo_b - mxb > thr || box.lo_a - mxa > thr || (box.min_absb >= 0x1p-400 && mna - box.hi_a > thr);
+}
+
 // 0.5 - d / (2*spread) of a clamped distance (finite spread): in [0, 1]
 HIT_HD double sdf_unit(double d, double spread) {
     const double two = 2.0 * spread;

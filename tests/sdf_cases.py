@@ -56,6 +56,82 @@ def overlapping_squares():
     return [np.array([(0.0, 0.0), (10.0, 0.0), (10.0, 10.0), (0.0, 10.0)]), np.array([(6.0, 0.0), (16.0, 0.0), (16.0, 10.0), (6.0, 10.0)])]
 
 
+# ---- cases for the kernels' cull (sdf_out_of_reach of csrc/svgr_sdf.h): a closed polygon, a spread and the points of a box beside it
+REACH_SIDES = 4      # the box lies at smaller b than the polygon, at larger b, at larger a, at smaller a (its rays run through the polygon)
+REACH_MODES = ("below", "above", "far", "near", "overlap", "tiny")
+
+
+def reach_threshold(ext, spread):
+    """The predicate's thr for one extent (min a, min b, max a, max b), in its own operations."""
+    return spread * (1.0 + 2.0 ** -40) + 2.0 ** -40 * float(np.abs(np.asarray(ext)).max())
+
+
+def extent_of(polygons):
+    """min a, min b, max a, max b over the corners of one polygon or of a list of them."""
+    v = np.concatenate([np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in (polygons if isinstance(polygons, list) else [polygons])])
+    return np.array([v[:, 0].min(), v[:, 1].min(), v[:, 0].max(), v[:, 1].max()])
+
+
+def box_of(points):
+    """lo_a, hi_a, lo_b, hi_b, min |pb| of finite points: what a workgroup reduces."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    return np.array([p[:, 0].min(), p[:, 0].max(), p[:, 1].min(), p[:, 1].max(), np.abs(p[:, 1]).min()])
+
+
+def reach_case(rng, side, mode):
+    """(polygon (k, 2), spread, points (9, 2)): a box whose gap to the polygon's extent on `side` is thr * (1 - 2^-30) ("below"),
+    thr * (1 + 2^-30) ("above"), many thr ("far"), a fraction of thr ("near") or negative ("overlap"); "tiny" is "far" with a corner
+    at |pb| = 2^-450.  The points are the box's corners and its points nearest the extent's corners and centre.  Spreads run over
+    2^-100 .. 2^40 and coordinates up to 2^50; near the threshold the coordinates stay within 2^12 spreads, so that the gap can be
+    set to 2^-30 of thr."""
+    k = rng.choice([-100.0, 40.0]) if rng.random() < 0.1 else rng.uniform(-100.0, 40.0)
+    spread = 2.0 ** k if k in (-100.0, 40.0) else 2.0 ** k * rng.uniform(1.0, 2.0)
+    spread = min(spread, 2.0 ** 40)
+    c = 2.0 ** min(k + rng.uniform(0.0, 12.0), 49.0) if mode in ("below", "above") else 2.0 ** rng.uniform(max(k - 3.0, -100.0), 49.0)
+    r = c * rng.uniform(0.05, 0.5)
+    centre = c * rng.uniform(-1.0, 1.0, size=2)
+    if mode == "tiny":
+        centre[1] = r * rng.uniform(-0.5, 0.5)       # the polygon's b range reaches across 0, where the box's corner will be
+    poly = centre + r * rng.uniform(-1.0, 1.0, size=(int(rng.integers(3, 8)), 2))
+    ext = extent_of(poly)
+    thr = reach_threshold(ext, spread)
+    gap = {"below": thr * (1.0 - 2.0 ** -30), "above": thr * (1.0 + 2.0 ** -30), "far": thr * 2.0 ** rng.uniform(0.01, 8.0),
+           "tiny": thr * 2.0 ** rng.uniform(0.01, 8.0), "near": thr * rng.uniform(0.0, 0.95), "overlap": -r * rng.uniform(0.0, 1.0)}[mode]
+    width = r * rng.uniform(0.0, 1.0, size=2) * (rng.random(2) < 0.8)      # (a box may be a segment or one point)
+    axis = 1 if side < 2 else 0                                           # the axis the gap is on
+    other = 1 - axis
+    lo, hi = np.zeros(2), np.zeros(2)
+    if side in (0, 3):                                                    # the box at smaller b / smaller a than the polygon
+        hi[axis] = ext[axis] - gap
+        lo[axis] = hi[axis] - width[axis]
+    else:
+        lo[axis] = ext[2 + axis] + gap
+        hi[axis] = lo[axis] + width[axis]
+    if rng.random() < 0.7 or mode == "tiny":                              # beside the polygon: no other clause can hold
+        lo[other] = rng.uniform(ext[other], ext[2 + other])
+    else:                                                                 # off its corner
+        lo[other] = ext[2 + other] + thr * rng.uniform(0.0, 10.0)
+    hi[other] = lo[other] + width[other]
+    if mode == "tiny":
+        lo[1], hi[1] = 2.0 ** -450 * rng.choice([-1.0, 0.0, 1.0]), max(hi[1], 2.0 ** -450)
+    corners = [(lo[0], lo[1]), (lo[0], hi[1]), (hi[0], lo[1]), (hi[0], hi[1])]
+    targets = [(ext[0], ext[1]), (ext[0], ext[3]), (ext[2], ext[1]), (ext[2], ext[3]), ((ext[0] + ext[2]) / 2.0, (ext[1] + ext[3]) / 2.0)]
+    nearest = [(min(max(a, lo[0]), hi[0]), min(max(b, lo[1]), hi[1])) for a, b in targets]
+    return poly, spread, np.array(corners + nearest)
+
+
+def reach_cases(seed, n):
+    """n cases, the sides and the modes taking turns: (side, mode, polygon, spread, points).  |pb| only matters beside the polygon
+    in a, so "tiny" takes those two sides."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        side, mode = i % REACH_SIDES, REACH_MODES[i // REACH_SIDES % len(REACH_MODES)]
+        side = 2 + (side & 1) if mode == "tiny" else side
+        out.append((side, mode) + reach_case(rng, side, mode))
+    return out
+
+
 polygon_edges, edge_table, random_polygons, regular_polygon, pentagram = (hit_cases.polygon_edges, hit_cases.edge_table, hit_cases.random_polygons,
                                                                           hit_cases.regular_polygon, hit_cases.pentagram)
 SQUARE, TRIANGLE = hit_cases.SQUARE, hit_cases.TRIANGLE

@@ -1,5 +1,6 @@
 // sdf_harness.cpp -- the distance-field header (csrc/svgr_sdf.h) compiled for the host, for tests/test_sdf_host.py
-// (g++ -ffp-contract=off): what a lane of k_sdf_distance does, one point after the other, without its cull.
+// (g++ -ffp-contract=off): what a lane of k_sdf_distance does, one point after the other, without its cull,
+// and the cull's predicate by itself.
 #include <cstdint>
 
 #include "../svgrasterize.py_amd/csrc/svgr_sdf.h"
@@ -27,6 +28,14 @@ void sh_distance(const double* edges, const int32_t* off, const uint8_t* rule, l
         for (long long p = 0; p < n_paths; ++p)
             out[i * n_paths + p] = sdf_path_distance(edges + 4 * (long long)off[p], off[p + 1] - off[p], rule[p] & 1, is_signed, spread,
                                                      points[2 * i], points[2 * i + 1]);
+}
+
+// the kernels' cull, case by case: ext[4 * i ..] = min a, min b, max a, max b; box[5 * i ..] = lo_a, hi_a, lo_b, hi_b, min |pb|
+void sh_out_of_reach(const double* ext, const double* box, const double* cull_spread, long long n, uint8_t* out) {
+    for (long long i = 0; i < n; ++i) {
+        const double* k = box + 5 * i;
+        out[i] = sdf_out_of_reach(ext + 4 * i, HitBox{k[0], k[1], k[2], k[3], k[4]}, cull_spread[i]) ? 1 : 0;
+    }
 }
 
 // the union of rows of clamped distances, as the kernel folds it: from +spread, fmin path after path

@@ -1,5 +1,5 @@
 """Host reference of signed distance fields (csrc/svgr_sdf.h), restated in numpy, one operation per line: nothing of
-the HIP code goes in, and nothing is culled.
+the HIP code goes in, and nothing is culled (the kernels' cull is restated by itself: `out_of_reach`).
 
 An edge is (a0, b0) -> (a1, b1) and a point (pa, pb), in the coordinate order of svgr_batch_all_edges (tests/hit_ref.py).
 
@@ -151,6 +151,29 @@ def encode_u8(d, spread):
 
 def encode(d, spread, out):
     return d if out == "f64" else encode_f32(d, spread) if out == "f32" else encode_u8(d, spread)
+
+
+# ---- the kernels' cull (sdf_out_of_reach of csrc/svgr_sdf.h) ---------------------------------------------------------
+def out_of_reach_clauses(ext, box, cull_spread):
+    """(4, n) bool: the predicate's clauses one by one -- the extent beyond the box at larger b, at smaller b, at smaller a, and at
+    larger a (the side the rays run through, with its 2^-400 condition) -- for ext (n, 4) = min a, min b, max a, max b, box (n, 5) =
+    lo_a, hi_a, lo_b, hi_b, min |pb| and cull_spread (n,); all False where cull_spread is +inf."""
+    ext, box = np.asarray(ext, dtype=np.float64).reshape(-1, 4), np.asarray(box, dtype=np.float64).reshape(-1, 5)
+    s = np.broadcast_to(np.asarray(cull_spread, dtype=np.float64), (len(ext),))
+    mna, mnb, mxa, mxb = ext.T
+    lo_a, hi_a, lo_b, hi_b, min_absb = box.T
+    with np.errstate(invalid="ignore", over="ignore"):
+        big = np.maximum(np.maximum(np.abs(mna), np.abs(mxa)), np.maximum(np.abs(mnb), np.abs(mxb)))
+        t0 = s * (1.0 + 2.0 ** -40)
+        t1 = 2.0 ** -40 * big
+        thr = t0 + t1
+        clauses = np.array([mnb - hi_b > thr, lo_b - mxb > thr, lo_a - mxa > thr, (min_absb >= 2.0 ** -400) & (mna - hi_a > thr)])
+    return clauses & (s < np.inf)
+
+
+def out_of_reach(ext, box, cull_spread):
+    """(n,) bool: the path may be left out for every point of the box."""
+    return out_of_reach_clauses(ext, box, cull_spread).any(axis=0)
 
 
 # ---- the tolerance (derived in the module's docstring) ---------------------------------------------------------------------------

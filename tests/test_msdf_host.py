@@ -15,7 +15,7 @@ from tests import msdf_cases as cases
 from tests import msdf_ref as M
 from tests import sdf_cases
 from tests import sdf_ref as R
-from tests.test_sdf_host import host_font
+from tests.test_sdf_host import harness_out_of_reach, host_font
 from tests.util import ROOT
 
 
@@ -223,6 +223,24 @@ def test_orientation_flips_with_a_mirror():
     # the convention of svgr_batch_msdf: sigma * ((a1 - a0) * (pb - b0) - (pa - a0) * (b1 - b0)) > 0 inside
     (a0, b0), (a1, b1) = cases.SQUARE[0], cases.SQUARE[1]
     assert msdf.orientation(square) * ((a1 - a0) * (6.0 - b0) - (6.0 - a0) * (b1 - b0)) > 0
+
+
+# ---- the kernel's cull ------------------------------------------------------------------------------------------------------------
+def test_a_group_out_of_reach_is_exactly_the_spread_away_in_every_channel():
+    """The claim k_msdf_distance's cull rests on: where sdf_out_of_reach holds for the union of the extents of a
+    group's paths, the group's R, G, B and A are +spread at every point of the box."""
+    rng = np.random.default_rng(7)
+    for i in range(12):
+        poly, spread, pts = sdf_cases.reach_case(rng, i % sdf_cases.REACH_SIDES, ("above", "far")[i // 4 % 2])
+        edges = sdf_cases.polygon_edges(poly)
+        k = 2 + i % 3                                                      # the polygon's edges dealt out to 2 .. 4 paths
+        paths = [(int(rng.integers(1, 8)), edges[j::k]) for j in range(k)]
+        shape = cases.Shape([(int(rng.choice([-1, 1])), paths)], [i & 1])
+        extents = np.array([sdf_cases.extent_of(e.reshape(-1, 2)) for _, e in paths if len(e)])
+        union = np.concatenate([extents[:, :2].min(axis=0), extents[:, 2:].max(axis=0)])
+        assert harness_out_of_reach(union, sdf_cases.box_of(pts), spread).all(), f"group {i} is no case: it is within reach"
+        got = cases.harness(shape, pts, spread)
+        assert (got == spread).all(), f"group {i}, out of reach at spread {spread!r}: {got.tolist()}"
 
 
 # ---- encodings and errors ---------------------------------------------------------------------------------------------------------

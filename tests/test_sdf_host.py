@@ -288,6 +288,67 @@ def test_the_union_is_the_minimum_over_the_paths():
     assert np.array_equal(R.union(np.zeros((4, 0)), 2.0), np.full(4, 2.0)) and np.array_equal(harness_union(np.zeros((4, 0)), 2.0), np.full(4, 2.0))
 
 
+# ---- the kernels' cull ------------------------------------------------------------------------------------------------------------
+def harness_out_of_reach(ext, box, spread):
+    ext, box = np.ascontiguousarray(ext, dtype=np.float64).reshape(-1, 4), np.ascontiguousarray(box, dtype=np.float64).reshape(-1, 5)
+    spread = np.ascontiguousarray(np.broadcast_to(np.asarray(spread, dtype=np.float64), (len(ext),)))
+    out = np.full(len(ext), 9, dtype=np.uint8)
+    lib().sh_out_of_reach(ptr(ext), ptr(box), ptr(spread), ctypes.c_longlong(len(ext)), ptr(out))
+    assert set(out.tolist()) <= {0, 1}
+    return out.astype(bool)
+
+
+def reach_tables(n=360, seed=11):
+    """The cases of cases.reach_cases as arrays: (cases, extents (n, 4), boxes (n, 5), spreads (n,))."""
+    cs = cases.reach_cases(seed, n)
+    return (cs, np.array([cases.extent_of(poly) for _, _, poly, _, _ in cs]), np.array([cases.box_of(pts) for *_, pts in cs]),
+            np.array([spread for _, _, _, spread, _ in cs]))
+
+
+def test_out_of_reach_equals_its_reference_case_for_case():
+    cs, ext, box, spread = reach_tables()
+    clauses = R.out_of_reach_clauses(ext, box, spread)
+    want = clauses.any(axis=0)
+    assert np.array_equal(harness_out_of_reach(ext, box, spread), want)
+    assert not harness_out_of_reach(ext, box, np.inf).any() and not R.out_of_reach(ext, box, np.inf).any()     # no cull without a spread
+    # what the cases are: each clause decides some case alone, on both sides of its threshold within 2^-30 of it
+    side = np.array([c[0] for c in cs])
+    mode = np.array([c[1] for c in cs])
+    thr = np.array([cases.reach_threshold(e, s) for e, s in zip(ext, spread)])
+    gap = np.choose(side, [ext[:, 1] - box[:, 3], box[:, 2] - ext[:, 3], box[:, 0] - ext[:, 2], ext[:, 0] - box[:, 1]])
+    alone = clauses.sum(axis=0) == 1
+    for k in range(4):
+        assert (alone & clauses[k]).any(), f"clause {k} decides no case alone"
+        below, above = (side == k) & (mode == "below"), (side == k) & (mode == "above")
+        assert below.sum() >= 5 and above.sum() >= 5
+        assert (gap[below] < thr[below]).all() and (gap[below] >= thr[below] * (1.0 - 2.0 ** -29)).all() and not clauses[k][below].any()
+        assert (gap[above] > thr[above]).all() and (gap[above] <= thr[above] * (1.0 + 2.0 ** -29)).all() and clauses[k][above].all()
+    # the side the rays run through: suppressed where a point has |pb| < 2^-400, and only there
+    tiny = box[:, 4] < 2.0 ** -400
+    suppressed = tiny & (side == 3) & (gap > thr)
+    assert suppressed.sum() >= 5 and not clauses[3][suppressed].any() and (suppressed & ~want).any()
+    assert (tiny & (side == 2) & clauses[2]).any() and clauses[3][~tiny & (side == 3) & (gap > thr)].all()
+    assert spread.min() == 2.0 ** -100 and spread.max() == 2.0 ** 40 and np.abs(ext).max() > 2.0 ** 48 and np.abs(ext).max() <= 2.0 ** 50
+    assert want.mean() >= 0.25 and (~want).mean() >= 0.25
+
+
+@pytest.mark.parametrize("signed", [True, False])
+def test_a_path_out_of_reach_is_exactly_the_spread_away(signed):
+    """The claim the cull rests on: where the predicate holds for a path's true extent, the walk gives every point
+    of the box +spread -- at its corners and at its points nearest the extent, under both rules.  Every culled case is checked."""
+    cs, ext, box, spread = reach_tables()
+    want = R.out_of_reach(ext, box, spread)
+    n_checked = 0
+    for (_, _, poly, s, pts), culled in zip(cs, want):
+        if not culled:
+            continue
+        edges, _, off = cases.edge_table([poly, poly])
+        d = harness_distance(edges, off, pts, rules=[0, 1], spread=s, signed=signed)
+        assert (d == s).all(), f"a path out of reach at spread {s!r}: {d.tolist()}"
+        n_checked += 1
+    assert n_checked == want.sum() >= len(cs) // 4
+
+
 # ---- the atlas packer -------------------------------------------------------------------------------------------------------------
 def check_layout(cells, rows, cols, boxes, scale, spread, max_cols):
     pad = math.ceil(spread)
