@@ -59,6 +59,7 @@
 #include "../../include/svgr.h"
 #include "svgr_core.h"
 #include "svgr_blob.h"
+#include "svgr_box.h"
 
 using namespace svgr;
 
@@ -3939,20 +3940,42 @@ __global__ __launch_bounds__(NT, GROUPS ? 2 : (CLIP ? WAVES_PER_EU - 1 : WAVES_P
 // ======================================================================================
 // layer kernels (double images in HBM)
 // ======================================================================================
-__global__ void k_layer_over(double* __restrict__ dst, int dr0, int dc0, int drows, int dcols,
-                             const double* __restrict__ src, int sr0, int sc0, int srows, int scols, int ch, int first) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)srows * scols) return;
-    int r = (int)(i / scols), c = (int)(i % scols);
-    int R = r + sr0 - dr0, C = c + sc0 - dc0;
-    if (R < 0 || R >= drows || C < 0 || C >= dcols) return;
-    double* d = dst + 4 * ((size_t)R * dcols + C);
-    const double* s = src + (size_t)ch * i;
-    double s0 = s[0], s1 = ch == 4 ? s[1] : s0, s2 = ch == 4 ? s[2] : s0, s3 = ch == 4 ? s[3] : s0;
-    if (first) {
-        d[0] = s0; d[1] = s1; d[2] = s2; d[3] = s3;
+// A layer is `ch` (1 or 4) doubles per pixel, row-major over a Box (svgr_box.h).  layer_px is THE read of "the
+// pixel of that other layer under device pixel (R, C)": v = its four values, a single channel broadcast to all four; false, and v
+// left as it is, where the layer does not reach.  An RGBA pixel goes as two 16-byte loads: a layer begins a pool block, aligned far
+// beyond that, and its pixels are 32 bytes apart.  load_px is its second half, the pixel at a known index.
+__device__ __forceinline__ void load_px(const double* p, int ch, size_t at, double* v) {
+    if (ch == 4) {
+        const double2* q = reinterpret_cast<const double2*>(p) + 2 * at;
+        const double2 lo = q[0], hi = q[1];
+        v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
     } else {
-        over_px(d, s0, s1, s2, s3);
+        v[0] = v[1] = v[2] = v[3] = p[at];
+    }
+}
+__device__ __forceinline__ bool layer_px(const double* p, int ch, const Box& b, int R, int C, double* v) {
+    size_t at;
+    if (!box_find(b, R, C, at)) return false;
+    load_px(p, ch, at, v);
+    return true;
+}
+// channel c of an RGBA pixel held in registers (feDisplacementMap's channel selectors)
+__device__ __forceinline__ double dm_channel(const double4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
+
+// one lane per SOURCE pixel: it goes over (or, `first`, into) the destination pixel under it, where there is one
+__global__ void k_layer_over(double* __restrict__ dst, Box db, const double* __restrict__ src, Box sb, int ch, int first) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, at;
+    if (i >= box_px(sb)) return;
+    int R, C;
+    box_cell(sb, i, R, C);
+    if (!box_find(db, R, C, at)) return;
+    double* d = dst + 4 * at;
+    double s[4];
+    load_px(src, ch, i, s);   // (the lane's own pixel)
+    if (first) {
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+    } else {
+        over_px(d, s[0], s[1], s[2], s[3]);
     }
 }
 
@@ -3960,17 +3983,14 @@ __global__ void k_layer_over(double* __restrict__ dst, int dr0, int dc0, int dro
 // S:348-361): out = blend(out, src zero-extended to the canvas), every pixel of the canvas.
 //   mode 1 OUT: src * (1 - dst_a)      3 ATOP: src * dst_a + dst * (1 - src_a)      4 XOR: src * (1 - dst_a) + dst * (1 - src_a)
 //   mode 5 arithmetic (feComposite k1..k4): clip(k1 * src * dst + k2 * src + k3 * dst + k4, 0, 1)
-__global__ void k_layer_blend(double* __restrict__ out, int or0, int oc0, int orows, int ocols, const double* __restrict__ src,
-                              int sr0, int sc0, int srows, int scols, int ch, int mode, double k1, double k2, double k3, double k4) {
+__global__ void k_layer_blend(double* __restrict__ out, Box ob, const double* __restrict__ src, Box sb, int ch, int mode, double k1,
+                              double k2, double k3, double k4) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)orows * ocols) return;
-    const int R = (int)(i / ocols), C = (int)(i % ocols);
-    const int r = R + or0 - sr0, c = C + oc0 - sc0;
+    if (i >= box_px(ob)) return;
+    int R, C;
+    box_cell(ob, i, R, C);
     double s[4] = {0.0, 0.0, 0.0, 0.0};
-    if (r >= 0 && r < srows && c >= 0 && c < scols) {
-        const double* sp = src + (size_t)ch * ((size_t)r * scols + c);
-        s[0] = sp[0]; s[1] = ch == 4 ? sp[1] : sp[0]; s[2] = ch == 4 ? sp[2] : sp[0]; s[3] = ch == 4 ? sp[3] : sp[0];
-    }
+    layer_px(src, ch, sb, R, C, s);
     double* d = out + 4 * i;
     const double da = d[3], sa = s[3];
     for (int q = 0; q < 4; ++q) {
@@ -4030,13 +4050,13 @@ __global__ void k_layer_morphology(double* __restrict__ out, const double* __res
 // ---- filter primitives the reference does not implement (feTurbulence, feComponentTransfer, feConvolveMatrix,
 //      feDisplacementMap; DESIGN.md "Filter primitives beyond the reference") ----
 
-// feTurbulence over a layer at (o0, o1): pixel [R, C] is the device point (o0 + R + 0.5, o1 + C + 0.5), taken to user space
+// feTurbulence over the layer `ob`: device pixel (R, C) is the device point (R + 0.5, C + 0.5), taken to user space
 // by inv (plain products and sums, left to right) and evaluated by svgr::turb_point.  The lattice (35 KB) is staged in LDS
 // once per workgroup and the workgroup strides over many pixels; one double4 store per pixel.
 struct TurbLaunch {
     double inv[6];
     svgr::TurbParams p;
-    int o0, o1, rows, cols;
+    Box ob;
 };
 __global__ __launch_bounds__(256) void k_layer_turbulence(double* __restrict__ out, const int* __restrict__ sel_g,
                                                           const double* __restrict__ grad_g, TurbLaunch a) {
@@ -4045,10 +4065,11 @@ __global__ __launch_bounds__(256) void k_layer_turbulence(double* __restrict__ o
     for (int q = threadIdx.x; q < svgr::kTurbLattice * 8; q += blockDim.x) grad[q] = grad_g[q];
     for (int q = threadIdx.x; q < svgr::kTurbLattice; q += blockDim.x) sel[q] = sel_g[q];
     __syncthreads();
-    const size_t n = (size_t)a.rows * a.cols;
+    const size_t n = box_px(a.ob);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int R = (int)(i / a.cols), C = (int)(i % a.cols);
-        const double d0 = (double)(a.o0 + R) + 0.5, d1 = (double)(a.o1 + C) + 0.5;
+        int R, C;
+        box_cell(a.ob, i, R, C);
+        const double d0 = (double)R + 0.5, d1 = (double)C + 0.5;
         const double px = a.inv[0] * d0 + a.inv[1] * d1 + a.inv[2];
         const double py = a.inv[3] * d0 + a.inv[4] * d1 + a.inv[5];
         double c[4];
@@ -4151,38 +4172,41 @@ __global__ __launch_bounds__(256) void k_layer_convolve_matrix(double* __restric
     reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(s0, s1, s2, al);
 }
 
-// feDisplacementMap: out has the map's extent (o0, o1, rows, cols).  d_user = scale * (map[XC] - 0.5, map[YC] - 0.5) of the
-// straight-alpha map, d_dev = L d_user, and the output pixel is the premultiplied source pixel containing the device point
-// (o0 + R + 0.5 + d_dev0, o1 + C + 0.5 + d_dev1); transparent outside the source.
+// feDisplacementMap: out has the map's box `ob`.  d_user = scale * (map[XC] - 0.5, map[YC] - 0.5) of the straight-alpha map,
+// d_dev = L d_user, and the output at device pixel (R, C) is the premultiplied pixel of the source (over `sb`) containing the
+// device point (R + 0.5 + d_dev0, C + 0.5 + d_dev1); transparent outside the source.  That point is found in doubles, so the
+// kernel keeps a read of its own.
 struct DmLaunch {
-    int o0, o1, rows, cols, s0, s1, srows, scols, xc, yc;
+    Box ob, sb;
+    int xc, yc;
     double l00, l01, l10, l11, scale;
 };
-__device__ __forceinline__ double dm_channel(const double4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
 __global__ __launch_bounds__(256) void k_layer_displacement_map(double* __restrict__ out, const double* __restrict__ map,
                                                                 const double* __restrict__ src, DmLaunch a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)a.rows * a.cols) return;
-    const int R = (int)(i / a.cols), C = (int)(i % a.cols);
+    if (i >= box_px(a.ob)) return;
+    int R, C;
+    box_cell(a.ob, i, R, C);
     const double4 m = reinterpret_cast<const double4*>(map)[i];
     const double du0 = a.scale * (dm_channel(m, a.xc) - 0.5), du1 = a.scale * (dm_channel(m, a.yc) - 0.5);
     const double dd0 = a.l00 * du0 + a.l01 * du1, dd1 = a.l10 * du0 + a.l11 * du1;
-    const double p0 = (double)(a.o0 + R) + 0.5 + dd0, p1 = (double)(a.o1 + C) + 0.5 + dd1;
-    const double r = floor(p0) - a.s0, c = floor(p1) - a.s1;   // (compared as doubles: a far displacement overflows no int)
+    const double p0 = (double)R + 0.5 + dd0, p1 = (double)C + 0.5 + dd1;
+    const double r = floor(p0) - a.sb.r0, c = floor(p1) - a.sb.c0;   // (compared as doubles: a far displacement overflows no int)
     double4 v = make_double4(0.0, 0.0, 0.0, 0.0);
-    if (r >= 0.0 && r < (double)a.srows && c >= 0.0 && c < (double)a.scols)
-        v = reinterpret_cast<const double4*>(src)[(size_t)r * a.scols + (size_t)c];
+    if (r >= 0.0 && r < (double)a.sb.rows && c >= 0.0 && c < (double)a.sb.cols)
+        v = reinterpret_cast<const double4*>(src)[(size_t)r * a.sb.cols + (size_t)c];
     reinterpret_cast<double4*>(out)[i] = v;
 }
 
-// feDiffuseLighting / feSpecularLighting over the region (o0, o1, rows, cols): a 16 x 16 workgroup stages the alpha of its
+// feDiffuseLighting / feSpecularLighting over the region `ob`: a 16 x 16 workgroup stages the alpha of its
 // tile and a one-pixel halo (18 x 18 doubles, 2.6 KB) in LDS -- zero outside the source and outside the region, so no input
 // pixel outside the region is read -- then each lane picks its Sobel case from its place in the region and shades through
 // svgr::light_pixel.  One double4 store per pixel; every region pixel is written.
 constexpr int kLightTile = 16;
 struct LightLaunch {
     svgr::LightParams p;
-    int o0, o1, rows, cols, s0, s1, srows, scols, tiles_x;
+    Box ob, sb;
+    int tiles_x;
 };
 __global__ __launch_bounds__(256) void k_layer_lighting(double* __restrict__ out, const double* __restrict__ src, LightLaunch a) {
     constexpr int T = kLightTile, H = kLightTile + 2;
@@ -4192,61 +4216,43 @@ __global__ __launch_bounds__(256) void k_layer_lighting(double* __restrict__ out
     const int r0 = tile_r * T - 1, c0 = tile_c * T - 1;   // (region coordinates of the halo's first pixel)
     for (int q = tid; q < H * H; q += T * T) {
         const int r = r0 + q / H, c = c0 + q % H;
-        const long long sr = (long long)r + a.o0 - a.s0, sc = (long long)c + a.o1 - a.s1;
-        double v = 0.0;
-        if (r >= 0 && r < a.rows && c >= 0 && c < a.cols && sr >= 0 && sr < a.srows && sc >= 0 && sc < a.scols)
-            v = src[((size_t)sr * a.scols + sc) * 4 + 3];
+        size_t at;
+        double v = 0.0;   // (alpha alone: a load of its own)
+        if (r >= 0 && r < a.ob.rows && c >= 0 && c < a.ob.cols && box_find(a.sb, a.ob.r0 + r, a.ob.c0 + c, at)) v = src[at * 4 + 3];
         alpha[q] = v;
     }
     __syncthreads();
-    const int R = tile_r * T + (int)threadIdx.y, C = tile_c * T + (int)threadIdx.x;
-    if (R >= a.rows || C >= a.cols) return;
+    const int R = tile_r * T + (int)threadIdx.y, C = tile_c * T + (int)threadIdx.x;   // (region coordinates)
+    if (R >= a.ob.rows || C >= a.ob.cols) return;
     double nb[9];
     for (int k = 0; k < 3; ++k)
         for (int j = 0; j < 3; ++j) nb[3 * k + j] = alpha[((int)threadIdx.y + k) * H + (int)threadIdx.x + j];
     double px[4];
-    svgr::light_pixel(a.p, nb, R == 0, R == a.rows - 1, C == 0, C == a.cols - 1, (double)(a.o0 + R) + 0.5, (double)(a.o1 + C) + 0.5, px);
-    reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(px[0], px[1], px[2], px[3]);
+    svgr::light_pixel(a.p, nb, R == 0, R == a.ob.rows - 1, C == 0, C == a.ob.cols - 1, (double)(a.ob.r0 + R) + 0.5, (double)(a.ob.c0 + C) + 0.5, px);
+    reinterpret_cast<double4*>(out)[(size_t)R * a.ob.cols + C] = make_double4(px[0], px[1], px[2], px[3]);
 }
 
-// mix-blend-mode (svgr::mix_blend_px): every pixel of the window (device rows w0.., columns w1..; inside out's box) gets the
+// mix-blend-mode (svgr::mix_blend_px): every pixel of the window `win` (a box inside out's) gets the
 // backdrop (zero outside its box), blended with the source where the source covers it.  Out of place the window is out's whole
 // box; in place (out is the backdrop) it is the source's box, and what lies outside it is left as it is.  A 1-channel layer is
 // alpha broadcast to all four.  Mode is a template parameter: each instantiation folds its mode's branches away.  One lane per
 // pixel, 16-byte loads and stores (two double2 per RGBA pixel).  out and backdrop may be one buffer: each lane reads its
 // pixel before it writes it.
 struct MixBlendLaunch {
-    int o0, o1, ocols;                  // out's box (rows are not needed: the window lies inside)
-    int b0, b1, brows, bcols, bch;      // backdrop
-    int s0, s1, srows, scols, sch;      // source
-    int w0, w1, wcols;                  // the window's first device row / column and its width
-    size_t n;                           // pixels in the window
+    Box ob, bb, sb, win;   // out, backdrop, source, window
+    int bch, sch;
 };
-__device__ __forceinline__ void load_px(const double* p, int ch, size_t at, double* v) {
-    if (ch == 4) {
-        const double2* q = reinterpret_cast<const double2*>(p) + 2 * at;
-        const double2 lo = q[0], hi = q[1];
-        v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
-    } else {
-        v[0] = v[1] = v[2] = v[3] = p[at];
-    }
-}
 template <int MODE>
 __global__ __launch_bounds__(256) void k_layer_mix_blend(double* out, const double* backdrop, const double* __restrict__ src,
                                                          MixBlendLaunch a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const int R = a.w0 + (int)(i / (size_t)a.wcols), C = a.w1 + (int)(i % (size_t)a.wcols);
-    double d[4] = {0.0, 0.0, 0.0, 0.0};
-    const int br = R - a.b0, bc = C - a.b1;
-    if (br >= 0 && br < a.brows && bc >= 0 && bc < a.bcols) load_px(backdrop, a.bch, (size_t)br * a.bcols + bc, d);
-    const int sr = R - a.s0, sc = C - a.s1;
-    if (sr >= 0 && sr < a.srows && sc >= 0 && sc < a.scols) {
-        double s[4];
-        load_px(src, a.sch, (size_t)sr * a.scols + sc, s);
-        svgr::mix_blend_px(MODE, d, s);
-    }
-    double2* o = reinterpret_cast<double2*>(out) + 2 * ((size_t)(R - a.o0) * a.ocols + (C - a.o1));
+    if (i >= box_px(a.win)) return;
+    int R, C;
+    box_cell(a.win, i, R, C);
+    double d[4] = {0.0, 0.0, 0.0, 0.0}, s[4];
+    layer_px(backdrop, a.bch, a.bb, R, C, d);
+    if (layer_px(src, a.sch, a.sb, R, C, s)) svgr::mix_blend_px(MODE, d, s);
+    double2* o = reinterpret_cast<double2*>(out) + 2 * ((size_t)(R - a.ob.r0) * a.ob.cols + (C - a.ob.c0));   // (the window lies inside out's box)
     o[0] = make_double2(d[0], d[1]);
     o[1] = make_double2(d[2], d[3]);
 }
@@ -4257,34 +4263,34 @@ static decltype(&k_layer_mix_blend<0>) mix_blend_kernel(int mode, std::integer_s
     return k;
 }
 
-// feTile (svgr::tile_wrap / tile_next / tile_source): the output box (o0, o1, rows, cols) filled with repeats of the tile box
-// (t0, t1, trows, tcols) of the source layer (s0, s1, srows, scols), transparent where the tile reaches beyond the layer.  A pure
+// feTile (svgr::tile_wrap / tile_next / tile_source): the output box `ob` filled with repeats of the tile box
+// `tb` of the source layer over `sb`, transparent where the tile reaches beyond the layer.  A pure
 // copy: every output pixel is written once, nothing is cleared in front.  One lane moves one 16-byte half of an RGBA-f64 pixel
 // (a wave's accesses are 1 KiB contiguous in the output, and in the source up to the tile's seam) down kTileRows output rows:
 // the column's modulo once per lane, the rows' once per workgroup (uniform: scalar) and a wrapping increment from row to row;
 // all loads of a lane are issued before its first store.
 constexpr int kTileRows = 8;
 struct TileLaunch {
-    int o0, o1, rows, cols, t0, t1, trows, tcols, s0, s1, srows, scols;
+    Box ob, tb, sb;
     int chunks;   // workgroups per output row: ceil(2 * cols / 256)
 };
 __global__ __launch_bounds__(256) void k_layer_tile(double2* __restrict__ out, const double2* __restrict__ src, TileLaunch a) {
     const int chunk = (int)(blockIdx.x % (unsigned)a.chunks), R0 = (int)(blockIdx.x / (unsigned)a.chunks) * kTileRows;
     const int h = chunk * 256 + (int)threadIdx.x;   // (half pixel h of the row: pixel h / 2, doubles 2 (h % 2) ..)
-    if (h >= 2 * a.cols) return;
-    const int sc = svgr::tile_source(svgr::tile_wrap(a.o1 - a.t1 + (h >> 1), a.tcols), a.t1, a.s1, a.scols);
-    int tr = svgr::tile_wrap(a.o0 - a.t0 + R0, a.trows);
+    if (h >= 2 * a.ob.cols) return;
+    const int sc = svgr::tile_source(svgr::tile_wrap(a.ob.c0 - a.tb.c0 + (h >> 1), a.tb.cols), a.tb.c0, a.sb.c0, a.sb.cols);
+    int tr = svgr::tile_wrap(a.ob.r0 - a.tb.r0 + R0, a.tb.rows);
     double2 v[kTileRows];
     SVGR_UNROLL
     for (int k = 0; k < kTileRows; ++k) {
-        const int sr = svgr::tile_source(tr, a.t0, a.s0, a.srows);
+        const int sr = svgr::tile_source(tr, a.tb.r0, a.sb.r0, a.sb.rows);
         v[k] = make_double2(0.0, 0.0);
-        if (R0 + k < a.rows && sr >= 0 && sc >= 0) v[k] = src[((size_t)sr * a.scols + sc) * 2 + (h & 1)];
-        tr = svgr::tile_next(tr, a.trows);
+        if (R0 + k < a.ob.rows && sr >= 0 && sc >= 0) v[k] = src[((size_t)sr * a.sb.cols + sc) * 2 + (h & 1)];
+        tr = svgr::tile_next(tr, a.tb.rows);
     }
     SVGR_UNROLL
     for (int k = 0; k < kTileRows; ++k)
-        if (R0 + k < a.rows) out[(size_t)(R0 + k) * a.cols * 2 + h] = v[k];
+        if (R0 + k < a.ob.rows) out[(size_t)(R0 + k) * a.ob.cols * 2 + h] = v[k];
 }
 
 // luminance mask (S:735): out(1 channel) = (rgb @ [0.2125, 0.7154, 0.072]) * alpha of a straight-alpha layer
@@ -4296,30 +4302,29 @@ __global__ void k_layer_luminance(double* __restrict__ out, const double* __rest
     out[i] = lum * p[3];
 }
 
-__global__ void k_layer_crop4(double* __restrict__ out, int or0, int oc0, int orows, int ocols,
-                              const double* __restrict__ src, int sr0, int sc0, int srows, int scols, int ch) {
+__global__ void k_layer_crop4(double* __restrict__ out, Box ob, const double* __restrict__ src, Box sb, int ch) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)orows * ocols) return;
-    int R = (int)(i / ocols), C = (int)(i % ocols);
-    int r = R + or0 - sr0, c = C + oc0 - sc0;
+    if (i >= box_px(ob)) return;
+    int R, C;
+    box_cell(ob, i, R, C);
     double v[4] = {0, 0, 0, 0};
-    if (r >= 0 && r < srows && c >= 0 && c < scols) {
-        const double* s = src + (size_t)ch * ((size_t)r * scols + c);
-        v[0] = s[0]; v[1] = ch == 4 ? s[1] : s[0]; v[2] = ch == 4 ? s[2] : s[0]; v[3] = ch == 4 ? s[3] : s[0];
-    }
+    layer_px(src, ch, sb, R, C, v);
     double* o = out + 4 * i;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
 }
 
-__global__ void k_layer_in(double* __restrict__ out, int or0, int oc0, int orows, int ocols,
-                           const double* __restrict__ src, int sr0, int sc0, int srows, int scols, int ch) {
+__global__ void k_layer_in(double* __restrict__ out, Box ob, const double* __restrict__ src, Box sb, int ch) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)orows * ocols) return;
-    int R = (int)(i / ocols), C = (int)(i % ocols);
-    int r = R + or0 - sr0, c = C + oc0 - sc0;
-    if (r < 0 || r >= srows || c < 0 || c >= scols) return;
+    if (i >= box_px(ob)) return;
+    // The one two-layer kernel that keeps a read of its own: with box_find and layer_px its 1-channel row of
+    // profiles/bench_layer_ops.py came out 2.4 % slower, with this form it is where it was (profiles/layer_boxes/README.md).
+    // Box-relative row and column, the differences taken unsigned so that they wrap where an int would overflow: a wrapped
+    // difference is negative or beyond 2^30, outside either way (svgr_box.h, box_find).
+    const int R = (int)(i / ob.cols), C = (int)(i % ob.cols);
+    const int r = (int)((unsigned)R + (unsigned)ob.r0 - (unsigned)sb.r0), c = (int)((unsigned)C + (unsigned)ob.c0 - (unsigned)sb.c0);
+    if (r < 0 || r >= sb.rows || c < 0 || c >= sb.cols) return;
     double* o = out + 4 * i;
-    const double* s = src + (size_t)ch * ((size_t)r * scols + c);
+    const double* s = src + (size_t)ch * ((size_t)r * sb.cols + c);
     double da = o[3];
     o[0] = s[0] * da;
     o[1] = (ch == 4 ? s[1] : s[0]) * da;
@@ -4387,10 +4392,14 @@ __global__ void k_layer_convert(double* dst, const double* src, size_t n_px, uns
 // in their order -- the first is copied where it covers the pixel (S:374-375), the others go OVER what is there (zero outside every
 // earlier layer) --, each source converted on the way in (`ops`: the Layer.convert a caller would have run as a pass of its own).
 // `accumulate`: the canvas holds the result of an earlier launch over the layers before these (more layers than one table holds).
+// Layer.compose(layers, IN) (canvas_merge_intersect, S:382-416 + S:290) is the same walk with another step: the output is the
+// intersection of the layers' boxes; the first layer is cropped to it, every other one multiplied by the alpha of what is there --
+// out = src * out_alpha, in the layers' order.  A source that does not reach the pixel is skipped (IN: the first stays zero,
+// svgr_layer_crop4; the others leave it untouched, svgr_layer_in).
 constexpr int OVER_SRCS = 24;
 struct OverSrc {
     const double* p;
-    int r0, c0, rows, cols;
+    Box b;
     int ch;
     unsigned ops;
 };
@@ -4398,50 +4407,21 @@ struct OverTable {
     int n, accumulate;
     OverSrc s[OVER_SRCS];
 };
-__global__ __launch_bounds__(256) void k_layer_compose_over(double* __restrict__ out, int or0, int oc0, int orows, int ocols, const OverTable t) {
+template <bool IN>
+__global__ __launch_bounds__(256) void k_layer_compose(double* __restrict__ out, Box ob, const OverTable t) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)orows * ocols) return;
-    const int R = (int)(i / ocols) + or0, C = (int)(i % ocols) + oc0;
+    if (i >= box_px(ob)) return;
+    int R, C;
+    box_cell(ob, i, R, C);
     double d[4] = {0.0, 0.0, 0.0, 0.0};
     if (t.accumulate) { const double4 v = ((const double4*)out)[i]; d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
     for (int k = 0; k < t.n; ++k) {
-        const int r = R - t.s[k].r0, c = C - t.s[k].c0;
-        if (r < 0 || r >= t.s[k].rows || c < 0 || c >= t.s[k].cols) continue;
         double v[4];
-        if (t.s[k].ch == 4) {
-            const double4 q = ((const double4*)t.s[k].p)[(size_t)r * t.s[k].cols + c];
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-            convert_px(v, t.s[k].ops);
-        } else {
-            v[0] = v[1] = v[2] = v[3] = t.s[k].p[(size_t)r * t.s[k].cols + c];
-        }
+        if (!layer_px(t.s[k].p, t.s[k].ch, t.s[k].b, R, C, v)) continue;
+        if (t.s[k].ch == 4) convert_px(v, t.s[k].ops);
         if (k == 0 && !t.accumulate) { d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3]; }
+        else if (IN) { const double da = d[3]; d[0] = v[0] * da; d[1] = v[1] * da; d[2] = v[2] * da; d[3] = v[3] * da; }
         else over_px(d, v[0], v[1], v[2], v[3]);
-    }
-    ((double4*)out)[i] = make_double4(d[0], d[1], d[2], d[3]);
-}
-// Layer.compose(layers, IN) in one launch (canvas_merge_intersect, S:382-416 + S:290): the output is the intersection of the layers'
-// boxes; the first layer is cropped to it (a single channel broadcast), every other one multiplied by the alpha of what is there --
-// out = src * out_alpha, in the layers' order --, each source converted as it is read.
-__global__ __launch_bounds__(256) void k_layer_compose_in(double* __restrict__ out, int or0, int oc0, int orows, int ocols, const OverTable t) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)orows * ocols) return;
-    const int R = (int)(i / ocols) + or0, C = (int)(i % ocols) + oc0;
-    double d[4] = {0.0, 0.0, 0.0, 0.0};
-    if (t.accumulate) { const double4 v = ((const double4*)out)[i]; d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
-    for (int k = 0; k < t.n; ++k) {
-        const int r = R - t.s[k].r0, c = C - t.s[k].c0;
-        if (r < 0 || r >= t.s[k].rows || c < 0 || c >= t.s[k].cols) continue;   // (the first: stays zero, svgr_layer_crop4; the others: untouched, svgr_layer_in)
-        double v[4];
-        if (t.s[k].ch == 4) {
-            const double4 q = ((const double4*)t.s[k].p)[(size_t)r * t.s[k].cols + c];
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-            convert_px(v, t.s[k].ops);
-        } else {
-            v[0] = v[1] = v[2] = v[3] = t.s[k].p[(size_t)r * t.s[k].cols + c];
-        }
-        if (k == 0 && !t.accumulate) { d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3]; }
-        else { const double da = d[3]; d[0] = v[0] * da; d[1] = v[1] * da; d[2] = v[2] * da; d[3] = v[3] * da; }
     }
     ((double4*)out)[i] = make_double4(d[0], d[1], d[2], d[3]);
 }
@@ -4472,14 +4452,13 @@ __global__ void k_to_rgba8(uchar4* __restrict__ dst, const double4* __restrict__
 // does any pixel of the layer have det < 0 ?  (the reference only builds its exclusion mask then, S:1627)
 // (two-dimensional launches: block x = 256 columns, block y strides over the rows -- the row / column of a pixel without the
 //  64-bit division that a flat index needs per thread)
-__global__ __launch_bounds__(256) void k_gradient_detneg(const GradDev g, const double* __restrict__ pts, int r0, int c0, int rows,
-                                                        int cols, int* __restrict__ flag) {
+__global__ __launch_bounds__(256) void k_gradient_detneg(const GradDev g, const double* __restrict__ pts, Box box, int* __restrict__ flag) {
     const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= cols) return;
+    if (j >= box.cols) return;
     bool neg = false;
-    for (int i = blockIdx.y; i < rows && !neg; i += gridDim.y) {
+    for (int i = blockIdx.y; i < box.rows && !neg; i += gridDim.y) {
         double x, y, b;
-        grad_point(g, pts, i, j, r0, c0, cols, x, y);
+        grad_point(g, pts, i, j, box.r0, box.c0, box.cols, x, y);
         neg = grad_focal_det(g, x, y, b) < 0.0;
     }
     if (neg) atomicOr(flag, 1);
@@ -4506,15 +4485,14 @@ __global__ __launch_bounds__(256) void k_grad_detneg(const GradDev* __restrict__
 // The parameter block travels as a kernel argument (1.6 KB of kernarg, read with scalar loads): no device copy of it, and
 // for linear / plain radial gradients nothing the host would have to wait for.
 __global__ __launch_bounds__(256) void k_gradient_fill(const GradDev g, const double* __restrict__ pts, const double* __restrict__ mask,
-                                                      int r0, int c0, int rows, int cols, const int* __restrict__ detneg_flag,
-                                                      double* __restrict__ out) {
+                                                      Box box, const int* __restrict__ detneg_flag, double* __restrict__ out) {
     const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= cols) return;
+    if (j >= box.cols) return;
     const bool use_mask = g.kind == 3 && *detneg_flag != 0;
-    for (int i = blockIdx.y; i < rows; i += gridDim.y) {
-        const size_t idx = (size_t)i * cols + j;
+    for (int i = blockIdx.y; i < box.rows; i += gridDim.y) {
+        const size_t idx = (size_t)i * box.cols + j;
         double x, y;
-        grad_point(g, pts, i, j, r0, c0, cols, x, y);
+        grad_point(g, pts, i, j, box.r0, box.c0, box.cols, x, y);
         double col[4];
         grad_colour_user(g, x, y, use_mask, col);
         const double m = mask ? mask[idx] : 1.0;  // canvas_compose(COMPOSE_IN, mask, image) = image * mask (S:1046, S:290)
@@ -4543,12 +4521,12 @@ __device__ __forceinline__ double np_remainder(double a, double b) {
 // offset into the (pw, ph) pattern canvas the reference allocates.  That canvas is zero except for the tile merged OVER
 // it and clipped to [0, 1] (canvas_merge_at, S:304-327), so it is never built: the tile is read in place.  Negative
 // offsets wrap like numpy's; an offset past the canvas (numpy: IndexError) raises the flag.
-__global__ void k_pattern_fill(const svgr_pattern pt, const double* __restrict__ tile, const double* __restrict__ mask, int r0,
-                               int c0, int rows, int cols, int* __restrict__ oob, double* __restrict__ out) {
+__global__ void k_pattern_fill(const svgr_pattern pt, const double* __restrict__ tile, const double* __restrict__ mask, Box box,
+                               int* __restrict__ oob, double* __restrict__ out) {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)rows * cols) return;
-    const int i = (int)(idx / cols), j = (int)(idx % cols);
-    const double px = (double)i + ((double)r0 + 0.5), py = (double)j + ((double)c0 + 0.5);
+    if (idx >= box_px(box)) return;
+    const int i = (int)(idx / box.cols), j = (int)(idx % box.cols);
+    const double px = (double)i + ((double)box.r0 + 0.5), py = (double)j + ((double)box.c0 + 0.5);
     double ux, uy, tx, ty;
     xform_point(pt.inv_m6, px, py, ux, uy);
     const double rx = np_remainder(ux - pt.cell[0], pt.cell[2]), ry = np_remainder(uy - pt.cell[1], pt.cell[3]);
@@ -4854,15 +4832,14 @@ __device__ __forceinline__ double4 image_bilinear(const ImageLevel& L, double u,
 constexpr int IMG_TW = 32, IMG_TH = 8;
 template <bool SMOOTH>
 __global__ void __launch_bounds__(256) k_image_fill(const svgr_image im, ImageLevel lo, ImageLevel hi, double blend,
-                                                    const double* __restrict__ mask, int r0, int c0, int rows, int cols,
-                                                    double* __restrict__ out) {
+                                                    const double* __restrict__ mask, Box box, double* __restrict__ out) {
     const int j = blockIdx.x * IMG_TW + (threadIdx.x % IMG_TW);
-    for (int ti = blockIdx.y; ti * IMG_TH < rows; ti += gridDim.y) {
+    for (int ti = blockIdx.y; ti * IMG_TH < box.rows; ti += gridDim.y) {
         const int i = ti * IMG_TH + (int)(threadIdx.x / IMG_TW);
-        if (i >= rows || j >= cols) continue;
-        const size_t idx = (size_t)i * cols + j;
+        if (i >= box.rows || j >= box.cols) continue;
+        const size_t idx = (size_t)i * box.cols + j;
         double u, v;
-        xform_point(im.inv_m6, (double)i + ((double)r0 + 0.5), (double)j + ((double)c0 + 0.5), u, v);
+        xform_point(im.inv_m6, (double)i + ((double)box.r0 + 0.5), (double)j + ((double)box.c0 + 0.5), u, v);
         double4 s;
         if (SMOOTH) {
             s = image_bilinear(lo, u, v);
@@ -5677,15 +5654,12 @@ static void with_tile_variant(const svgr_batch* b, int out_kind, F&& launch) {
 }
 
 // ---- the layer entries' common parts
-static int bbox_ok(const int64_t* bb) {
-    return bb && bb[2] >= 0 && bb[3] >= 0 && bb[2] < (1ll << 30) && bb[3] < (1ll << 30) && std::llabs(bb[0]) < (1ll << 30) &&
-           std::llabs(bb[1]) < (1ll << 30);
-}
+// (a bbox argument becomes a Box through svgr::box_of, svgr_box.h: the range checks and the narrowing, once)
 // the over / blend / crop4 / in entries: an RGBA layer over the box `ob` and a source of `ch` (1 or 4) values per pixel over `sb`
-static int check_layer_pair(const char* entry, const svgr_ctx* ctx, const svgr_buf* out, const int64_t* ob, const svgr_buf* src,
-                            const int64_t* sb, int ch) {
-    if (!ctx || !out || !src || !bbox_ok(ob) || !bbox_ok(sb) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
-    if (out->bytes < (size_t)ob[2] * ob[3] * 32 || src->bytes < (size_t)sb[2] * sb[3] * 8 * ch) return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
+static int check_layer_pair(const char* entry, const svgr_ctx* ctx, const svgr_buf* out, const int64_t* ob, Box& o, const svgr_buf* src,
+                            const int64_t* sb, Box& s, int ch) {
+    if (!ctx || !out || !src || !box_of(ob, o) || !box_of(sb, s) || (ch != 1 && ch != 4)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (out->bytes < box_px(o) * 32 || src->bytes < box_px(s) * 8 * ch) return fail(SVGR_E_INVALID, "%s: buffer too small", entry);
     return 0;
 }
 
@@ -7428,22 +7402,22 @@ int svgr_batch_timings(svgr_batch* b, int* n_renders, double* ms_total, double* 
 // layer ops
 // ---------------------------------------------------------------------------------------------
 int svgr_layer_over(svgr_ctx* ctx, svgr_buf* dst, const int64_t* db, const svgr_buf* src, const int64_t* sb, int ch, int first) {
-    if (int rc = check_layer_pair("svgr_layer_over", ctx, dst, db, src, sb, ch)) return rc;
-    size_t n = (size_t)sb[2] * sb[3];
+    Box d, s;
+    if (int rc = check_layer_pair("svgr_layer_over", ctx, dst, db, d, src, sb, s, ch)) return rc;
+    const size_t n = box_px(s);
     if (n == 0) return 0;
-    return launch_tail(ctx, k_layer_over, grid1(n), dim3(256), 0, (double*)dst->ptr, (int)db[0], (int)db[1], (int)db[2],
-                       (int)db[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch, first);
+    return launch_tail(ctx, k_layer_over, grid1(n), dim3(256), 0, (double*)dst->ptr, d, (const double*)src->ptr, s, ch, first);
 }
 
 int svgr_layer_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch, int mode,
                      const double* k4) {
     if (!(mode == 1 || mode == 3 || mode == 4 || mode == 5) || (mode == 5 && !k4)) return fail(SVGR_E_INVALID, "invalid compose mode: %d", mode);
-    if (int rc = check_layer_pair("svgr_layer_blend", ctx, out, ob, src, sb, ch)) return rc;
-    const size_t n = (size_t)ob[2] * ob[3];
+    Box o, s;
+    if (int rc = check_layer_pair("svgr_layer_blend", ctx, out, ob, o, src, sb, s, ch)) return rc;
+    const size_t n = box_px(o);
     if (n == 0) return 0;
-    return launch_tail(ctx, k_layer_blend, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2], (int)ob[3],
-                       (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch, mode, mode == 5 ? k4[0] : 0.0,
-                       mode == 5 ? k4[1] : 0.0, mode == 5 ? k4[2] : 0.0, mode == 5 ? k4[3] : 0.0);
+    return launch_tail(ctx, k_layer_blend, grid1(n), dim3(256), 0, (double*)out->ptr, o, (const double*)src->ptr, s, ch, mode,
+                       mode == 5 ? k4[0] : 0.0, mode == 5 ? k4[1] : 0.0, mode == 5 ? k4[2] : 0.0, mode == 5 ? k4[3] : 0.0);
 }
 
 int svgr_layer_color_matrix(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, const double* m20) {
@@ -7469,10 +7443,11 @@ static inline unsigned stride_blocks(size_t n) { return (unsigned)std::max<size_
 
 int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, const double* inv_m6, double base_fx, double base_fy,
                           const double* tile, int64_t seed, int octaves, int fractal, int stitch) {
-    if (!ctx || !out || !inv_m6 || !tile || !bbox_ok(bbox) || octaves < 0 || octaves > svgr::kTurbMaxOctaves || !(base_fx >= 0.0) ||
+    TurbLaunch a;
+    if (!ctx || !out || !inv_m6 || !tile || !box_of(bbox, a.ob) || octaves < 0 || octaves > svgr::kTurbMaxOctaves || !(base_fx >= 0.0) ||
         !(base_fy >= 0.0) || (fractal != 0 && fractal != 1) || (stitch != 0 && stitch != 1))
         return fail(SVGR_E_INVALID, "svgr_layer_turbulence: bad arguments (octaves 0..%d, base frequencies >= 0)", svgr::kTurbMaxOctaves);
-    const size_t n = (size_t)bbox[2] * (size_t)bbox[3];
+    const size_t n = box_px(a.ob);
     if (out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_turbulence: buffer too small");
     if (n == 0) return 0;
     return abi_guard("svgr_layer_turbulence", [&]() -> int {
@@ -7480,10 +7455,8 @@ int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, con
         double* grad = (double*)host.data();
         int* sel = (int*)(grad + svgr::kTurbLattice * 8);
         svgr::turb_init(seed, sel, grad);
-        TurbLaunch a;
         memcpy(a.inv, inv_m6, sizeof a.inv);
         a.p = svgr::turb_params(base_fx, base_fy, tile, octaves, fractal, stitch);
-        a.o0 = (int)bbox[0]; a.o1 = (int)bbox[1]; a.rows = (int)bbox[2]; a.cols = (int)bbox[3];
         HIPCHK(enter_ctx(ctx));
         return upload_launch_wait(ctx, "svgr_layer_turbulence", {{host.data(), host.size()}}, [&](void* dev) {
             SVGR_LAUNCH(k_layer_turbulence, dim3(stride_blocks(n)), dim3(256), 0, ctx->stream, (double*)out->ptr,
@@ -7554,17 +7527,15 @@ int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
 
 int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* map, const svgr_buf* src,
                                 const int64_t* src_bbox, const double* lin4, double scale, int x_channel, int y_channel) {
-    if (!ctx || !out || !map || !src || !lin4 || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || x_channel < 0 || x_channel > 3 ||
+    DmLaunch a;
+    if (!ctx || !out || !map || !src || !lin4 || !box_of(out_bbox, a.ob) || !box_of(src_bbox, a.sb) || x_channel < 0 || x_channel > 3 ||
         y_channel < 0 || y_channel > 3)
         return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: bad arguments (channels 0..3)");
-    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
-    if (out->bytes < n * 32 || map->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+    const size_t n = box_px(a.ob);
+    if (out->bytes < n * 32 || map->bytes < n * 32 || src->bytes < box_px(a.sb) * 32)
         return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: buffer too small");
     if (out->ptr == src->ptr || out->ptr == map->ptr) return fail(SVGR_E_INVALID, "svgr_layer_displacement_map: out must not be an input");
     if (n == 0) return 0;
-    DmLaunch a;
-    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
-    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
     a.xc = x_channel; a.yc = y_channel;
     a.l00 = lin4[0]; a.l01 = lin4[1]; a.l10 = lin4[2]; a.l11 = lin4[3]; a.scale = scale;
     return launch_tail(ctx, k_layer_displacement_map, grid1(n), dim3(256), 0, (double*)out->ptr, (const double*)map->ptr,
@@ -7574,48 +7545,42 @@ int svgr_layer_displacement_map(svgr_ctx* ctx, svgr_buf* out, const int64_t* out
 int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
                         int light_kind, const double* light_params, const double* color3, double surface_scale, double constant,
                         double specular_exponent, int specular) {
-    if (!ctx || !out || !src || !light_params || !color3 || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || light_kind < svgr::kLightDistant ||
+    LightLaunch a;
+    if (!ctx || !out || !src || !light_params || !color3 || !box_of(out_bbox, a.ob) || !box_of(src_bbox, a.sb) || light_kind < svgr::kLightDistant ||
         light_kind > svgr::kLightSpot || (specular != 0 && specular != 1))
         return fail(SVGR_E_INVALID, "svgr_layer_lighting: bad arguments (light kind 0..2, specular 0 or 1)");
-    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
-    const size_t tiles = (size_t)((out_bbox[3] + kLightTile - 1) / kLightTile) * (size_t)((out_bbox[2] + kLightTile - 1) / kLightTile);
+    const size_t n = box_px(a.ob);
+    a.tiles_x = (a.ob.cols + kLightTile - 1) / kLightTile;
+    const size_t tiles = (size_t)a.tiles_x * (size_t)((a.ob.rows + kLightTile - 1) / kLightTile);
     if (tiles > 0x7fffffff) return fail(SVGR_E_INVALID, "svgr_layer_lighting: region too large");
-    if (out->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+    if (out->bytes < n * 32 || src->bytes < box_px(a.sb) * 32)
         return fail(SVGR_E_INVALID, "svgr_layer_lighting: buffer too small");
     if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_lighting: out must not be src");
     if (n == 0) return 0;
-    LightLaunch a;
     memcpy(a.p.l, light_params, sizeof a.p.l);
     memcpy(a.p.color, color3, sizeof a.p.color);
     a.p.surface_scale = surface_scale; a.p.constant = constant; a.p.specular_exponent = specular_exponent;
     a.p.kind = light_kind; a.p.specular = specular;
-    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
-    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
-    a.tiles_x = (a.cols + kLightTile - 1) / kLightTile;
     return launch_tail(ctx, k_layer_lighting, dim3((unsigned)tiles), dim3(kLightTile, kLightTile), 0, (double*)out->ptr,
                        (const double*)src->ptr, a);
 }
 
 int svgr_layer_tile(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const svgr_buf* src, const int64_t* src_bbox,
                     const int64_t* tile_bbox) {
-    if (!ctx || !out || !src || !bbox_ok(out_bbox) || !bbox_ok(src_bbox) || !bbox_ok(tile_bbox))
+    TileLaunch a;
+    if (!ctx || !out || !src || !box_of(out_bbox, a.ob) || !box_of(src_bbox, a.sb) || !box_of(tile_bbox, a.tb))
         return fail(SVGR_E_INVALID, "svgr_layer_tile: bad arguments");
-    if (out_bbox[2] == 0 || out_bbox[3] == 0 || tile_bbox[2] == 0 || tile_bbox[3] == 0)
+    if (box_px(a.ob) == 0 || box_px(a.tb) == 0)
         return fail(SVGR_E_INVALID, "svgr_layer_tile: empty tile or output");
     // (the kernel's index arithmetic is 32-bit: an output coordinate relative to the tile's origin, and the half pixels of a row)
     for (int k = 0; k < 2; ++k)
         if (std::llabs(out_bbox[k] - tile_bbox[k]) + out_bbox[2 + k] + kTileRows >= (1ll << 31)) return fail(SVGR_E_INVALID, "svgr_layer_tile: output too far from the tile");
-    const size_t n = (size_t)out_bbox[2] * (size_t)out_bbox[3];
-    const size_t chunks = ((size_t)out_bbox[3] * 2 + 255) / 256;
-    const size_t groups = chunks * (size_t)((out_bbox[2] + kTileRows - 1) / kTileRows);
-    if (out_bbox[3] >= (1ll << 29) || groups > 0x7fffffff) return fail(SVGR_E_INVALID, "svgr_layer_tile: output too large");
-    if (out->bytes < n * 32 || src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * 32)
+    const size_t chunks = ((size_t)a.ob.cols * 2 + 255) / 256;
+    const size_t groups = chunks * (size_t)((a.ob.rows + kTileRows - 1) / kTileRows);
+    if (a.ob.cols >= (1 << 29) || groups > 0x7fffffff) return fail(SVGR_E_INVALID, "svgr_layer_tile: output too large");
+    if (out->bytes < box_px(a.ob) * 32 || src->bytes < box_px(a.sb) * 32)
         return fail(SVGR_E_INVALID, "svgr_layer_tile: buffer too small");
     if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_tile: out must not be src");
-    TileLaunch a;
-    a.o0 = (int)out_bbox[0]; a.o1 = (int)out_bbox[1]; a.rows = (int)out_bbox[2]; a.cols = (int)out_bbox[3];
-    a.t0 = (int)tile_bbox[0]; a.t1 = (int)tile_bbox[1]; a.trows = (int)tile_bbox[2]; a.tcols = (int)tile_bbox[3];
-    a.s0 = (int)src_bbox[0]; a.s1 = (int)src_bbox[1]; a.srows = (int)src_bbox[2]; a.scols = (int)src_bbox[3];
     a.chunks = (int)chunks;
     return launch_tail(ctx, k_layer_tile, dim3((unsigned)groups), dim3(256), 0, (double2*)out->ptr, (const double2*)src->ptr, a);
 }
@@ -7623,24 +7588,18 @@ int svgr_layer_tile(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, const
 int svgr_layer_mix_blend(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* backdrop, const int64_t* bb, int bch,
                          const svgr_buf* src, const int64_t* sb, int sch, int mode) {
     if (mode < svgr::kBlendNormal || mode >= svgr::kBlendModes) return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: unknown mode %d", mode);
-    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, src, sb, sch)) return rc;
-    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, backdrop, bb, bch)) return rc;
+    MixBlendLaunch a;
+    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, a.ob, src, sb, a.sb, sch)) return rc;
+    if (int rc = check_layer_pair("svgr_layer_mix_blend", ctx, out, ob, a.ob, backdrop, bb, a.bb, bch)) return rc;
     if (src->ptr == out->ptr) return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: out must not be the source");
     const bool in_place = backdrop->ptr == out->ptr;
     if (in_place && (bch != 4 || bb[0] != ob[0] || bb[1] != ob[1] || bb[2] != ob[2] || bb[3] != ob[3]))
         return fail(SVGR_E_INVALID, "svgr_layer_mix_blend: in place, the backdrop is out (4 channels, the same box)");
-    MixBlendLaunch a;
-    a.o0 = (int)ob[0]; a.o1 = (int)ob[1]; a.ocols = (int)ob[3];
-    a.b0 = (int)bb[0]; a.b1 = (int)bb[1]; a.brows = (int)bb[2]; a.bcols = (int)bb[3]; a.bch = bch;
-    a.s0 = (int)sb[0]; a.s1 = (int)sb[1]; a.srows = (int)sb[2]; a.scols = (int)sb[3]; a.sch = sch;
-    int64_t w0 = ob[0], w1 = ob[1], w2 = ob[0] + ob[2], w3 = ob[1] + ob[3];
-    if (in_place) {   // (only the pixels under the source change: the window is the source's box, clipped to out's)
-        w0 = std::max(w0, sb[0]); w1 = std::max(w1, sb[1]); w2 = std::min(w2, sb[0] + sb[2]); w3 = std::min(w3, sb[1] + sb[3]);
-    }
-    if (w2 <= w0 || w3 <= w1) return 0;
-    a.w0 = (int)w0; a.w1 = (int)w1; a.wcols = (int)(w3 - w1);
-    a.n = (size_t)(w2 - w0) * (size_t)(w3 - w1);
-    return launch_tail(ctx, mix_blend_kernel(mode, std::make_integer_sequence<int, svgr::kBlendModes>{}), grid1(a.n), dim3(256), 0,
+    a.bch = bch; a.sch = sch;
+    // (in place only the pixels under the source change: the window is the source's box, clipped to out's)
+    a.win = in_place ? box_meet(a.ob, a.sb) : a.ob;
+    if (box_px(a.win) == 0) return 0;
+    return launch_tail(ctx, mix_blend_kernel(mode, std::make_integer_sequence<int, svgr::kBlendModes>{}), grid1(box_px(a.win)), dim3(256), 0,
                        (double*)out->ptr, (const double*)backdrop->ptr, (const double*)src->ptr, a);
 }
 
@@ -7651,19 +7610,19 @@ int svgr_layer_luminance(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int6
 }
 
 int svgr_layer_crop4(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch) {
-    if (int rc = check_layer_pair("svgr_layer_crop4", ctx, out, ob, src, sb, ch)) return rc;
-    size_t n = (size_t)ob[2] * ob[3];
+    Box o, s;
+    if (int rc = check_layer_pair("svgr_layer_crop4", ctx, out, ob, o, src, sb, s, ch)) return rc;
+    const size_t n = box_px(o);
     if (n == 0) return 0;
-    return launch_tail(ctx, k_layer_crop4, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
-                       (int)ob[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch);
+    return launch_tail(ctx, k_layer_crop4, grid1(n), dim3(256), 0, (double*)out->ptr, o, (const double*)src->ptr, s, ch);
 }
 
 int svgr_layer_in(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, const svgr_buf* src, const int64_t* sb, int ch) {
-    if (int rc = check_layer_pair("svgr_layer_in", ctx, out, ob, src, sb, ch)) return rc;
-    size_t n = (size_t)ob[2] * ob[3];
+    Box o, s;
+    if (int rc = check_layer_pair("svgr_layer_in", ctx, out, ob, o, src, sb, s, ch)) return rc;
+    const size_t n = box_px(o);
     if (n == 0) return 0;
-    return launch_tail(ctx, k_layer_in, grid1(n), dim3(256), 0, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
-                       (int)ob[3], (const double*)src->ptr, (int)sb[0], (int)sb[1], (int)sb[2], (int)sb[3], ch);
+    return launch_tail(ctx, k_layer_in, grid1(n), dim3(256), 0, (double*)out->ptr, o, (const double*)src->ptr, s, ch);
 }
 
 int svgr_layer_scale_to(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n, double f) {
@@ -7714,39 +7673,32 @@ int svgr_layer_compose_in(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, int64
 }
 static int layer_compose_many(svgr_ctx* ctx, svgr_buf* out, const int64_t* ob, int64_t n, svgr_buf* const* srcs, const int64_t* sbs,
                               const int32_t* chs, const uint32_t* ops, bool in_mode) {
-    if (!ctx || !out || !bbox_ok(ob) || n <= 0 || !srcs || !sbs || !chs) return fail(SVGR_E_INVALID, "svgr_layer_compose_over / _in: bad arguments");
-    const size_t n_out = (size_t)ob[2] * ob[3];
+    Box o;
+    if (!ctx || !out || !box_of(ob, o) || n <= 0 || !srcs || !sbs || !chs) return fail(SVGR_E_INVALID, "svgr_layer_compose_over / _in: bad arguments");
+    const size_t n_out = box_px(o);
     if (out->bytes < n_out * 32) return fail(SVGR_E_INVALID, "svgr_layer_compose_over: output buffer too small");
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t* sb = sbs + 4 * i;
-        if (!srcs[i] || !bbox_ok(sb) || (chs[i] != 1 && chs[i] != 4) || (ops && ((ops[i] & ~15u) || (ops[i] && chs[i] != 4))))
-            return fail(SVGR_E_INVALID, "svgr_layer_compose_over: bad source %lld", (long long)i);
-        if (srcs[i]->bytes < (size_t)sb[2] * sb[3] * 8 * chs[i]) return fail(SVGR_E_INVALID, "svgr_layer_compose_over: source %lld too small", (long long)i);
-        if (srcs[i]->ptr == out->ptr) return fail(SVGR_E_INVALID, "svgr_layer_compose_over: the output is one of the sources");
-    }
-    if (n_out == 0) return 0;
-    HIPCHK(enter_ctx(ctx));
-    for (int64_t at = 0; at < n; at += OVER_SRCS) {
-        OverTable t;
-        memset(&t, 0, sizeof t);
-        t.n = (int)std::min<int64_t>(OVER_SRCS, n - at);
-        t.accumulate = at > 0 ? 1 : 0;
-        for (int k = 0; k < t.n; ++k) {
-            const int64_t* sb = sbs + 4 * (at + k);
-            OverSrc& o = t.s[k];
-            o.p = (const double*)srcs[at + k]->ptr;
-            o.r0 = (int)sb[0]; o.c0 = (int)sb[1]; o.rows = (int)sb[2]; o.cols = (int)sb[3];
-            o.ch = chs[at + k]; o.ops = ops ? ops[at + k] : 0u;
+    return abi_guard("svgr_layer_compose_over / _in", [&]() -> int {
+        // every source is checked, and its box narrowed, as it goes into its table: OVER_SRCS to a launch
+        std::vector<OverTable> tables((size_t)((n + OVER_SRCS - 1) / OVER_SRCS));
+        memset(tables.data(), 0, tables.size() * sizeof(OverTable));
+        for (int64_t i = 0; i < n; ++i) {
+            OverTable& t = tables[(size_t)(i / OVER_SRCS)];
+            OverSrc& s = t.s[t.n++];
+            if (!srcs[i] || !box_of(sbs + 4 * i, s.b) || (chs[i] != 1 && chs[i] != 4) || (ops && ((ops[i] & ~15u) || (ops[i] && chs[i] != 4))))
+                return fail(SVGR_E_INVALID, "svgr_layer_compose_over: bad source %lld", (long long)i);
+            if (srcs[i]->bytes < box_px(s.b) * 8 * chs[i]) return fail(SVGR_E_INVALID, "svgr_layer_compose_over: source %lld too small", (long long)i);
+            if (srcs[i]->ptr == out->ptr) return fail(SVGR_E_INVALID, "svgr_layer_compose_over: the output is one of the sources");
+            s.p = (const double*)srcs[i]->ptr;
+            s.ch = chs[i]; s.ops = ops ? ops[i] : 0u;
+            t.accumulate = i >= OVER_SRCS ? 1 : 0;
         }
-        if (in_mode)
-            SVGR_LAUNCH(k_layer_compose_in, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
-                               (int)ob[3], t);
-        else
-            SVGR_LAUNCH(k_layer_compose_over, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, (int)ob[0], (int)ob[1], (int)ob[2],
-                               (int)ob[3], t);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+        if (n_out == 0) return 0;
+        HIPCHK(enter_ctx(ctx));
+        const auto kernel = in_mode ? k_layer_compose<true> : k_layer_compose<false>;
+        for (const OverTable& t : tables) SVGR_LAUNCH(kernel, grid1(n_out), dim3(256), 0, ctx->stream, (double*)out->ptr, o, t);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
 }
 
 int svgr_layer_to_f32(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64_t n, int clip01) {
@@ -7761,11 +7713,10 @@ int svgr_layer_to_rgba8(svgr_ctx* ctx, svgr_buf* dst, const svgr_buf* src, int64
     return launch_tail(ctx, k_to_rgba8, grid1((size_t)n_px), dim3(256), 0, (uchar4*)dst->ptr, (const double4*)src->ptr, (size_t)n_px);
 }
 
-// the gradient over the pixel grid of `bbox` times `mask` (pts == nullptr), or at the n = bbox[2] * bbox[3] points of `pts`
-static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts, const svgr_buf* mask, const int64_t* bbox,
-                        svgr_buf* out) {
+// the gradient over the pixel grid of `box` times `mask` (pts == nullptr), or at the n = rows * cols points of `pts`
+static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts, const svgr_buf* mask, const Box& box, svgr_buf* out) {
     if (int rc = check_gradient(g)) return rc;
-    const size_t n = (size_t)bbox[2] * bbox[3];
+    const size_t n = box_px(box);
     if ((mask && mask->bytes < n * 8) || out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_gradient_fill: buffer too small");
     if (n == 0) return 0;
     const double* mptr = mask ? (const double*)mask->ptr : nullptr;
@@ -7773,7 +7724,7 @@ static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts
     fill_grad_dev(h, g);
     HIPCHK(enter_ctx(ctx));
     hipError_t e = hipSuccess;
-    const dim3 ggrid((unsigned)(((long long)bbox[3] + 255) / 256), (unsigned)std::min<long long>(bbox[2], 32768));
+    const dim3 ggrid((unsigned)(((long long)box.cols + 255) / 256), (unsigned)std::min<long long>(box.rows, 32768));
     PoolBlock ext;  // long stop lists: one device block {offsets, colours}
     if (g->n_stops <= GRAD_MAX_STOPS) {
         for (int i = 0; i < g->n_stops; ++i) {
@@ -7794,15 +7745,12 @@ static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts
         HIPCHK(flag.alloc(16));
         e = hipMemsetAsync(flag.p, 0, 16, ctx->stream);
         if (e == hipSuccess) {
-            SVGR_LAUNCH(k_gradient_detneg, ggrid, dim3(256), 0, ctx->stream, h, pts, (int)bbox[0], (int)bbox[1],
-                               (int)bbox[2], (int)bbox[3], flag.as<int>());
-            SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, (int)bbox[0], (int)bbox[1],
-                               (int)bbox[2], (int)bbox[3], (const int*)flag.p, (double*)out->ptr);
+            SVGR_LAUNCH(k_gradient_detneg, ggrid, dim3(256), 0, ctx->stream, h, pts, box, flag.as<int>());
+            SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, box, (const int*)flag.p, (double*)out->ptr);
             e = hipGetLastError();
         }
     } else {
-        SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, (int)bbox[0], (int)bbox[1],
-                           (int)bbox[2], (int)bbox[3], (const int*)nullptr, (double*)out->ptr);
+        SVGR_LAUNCH(k_gradient_fill, ggrid, dim3(256), 0, ctx->stream, h, pts, mptr, box, (const int*)nullptr, (double*)out->ptr);
         e = hipGetLastError();
     }
     // (the stops are the caller's host arrays: the copies above must have been consumed before returning)
@@ -7812,24 +7760,26 @@ static int gradient_run(svgr_ctx* ctx, const svgr_gradient* g, const double* pts
 }
 
 int svgr_gradient_fill(svgr_ctx* ctx, const svgr_gradient* g, const svgr_buf* mask, const int64_t* bbox, svgr_buf* out) {
-    if (!ctx || !g || !mask || !out || !bbox_ok(bbox)) return fail(SVGR_E_INVALID, "svgr_gradient_fill: bad arguments");
-    return gradient_run(ctx, g, nullptr, mask, bbox, out);
+    Box box;
+    if (!ctx || !g || !mask || !out || !box_of(bbox, box)) return fail(SVGR_E_INVALID, "svgr_gradient_fill: bad arguments");
+    return gradient_run(ctx, g, nullptr, mask, box, out);
 }
 
 int svgr_gradient_eval(svgr_ctx* ctx, const svgr_gradient* g, const svgr_buf* points, int64_t n_points, svgr_buf* out) {
     if (!ctx || !g || !points || !out || n_points < 0 || n_points > ((int64_t)1 << 31) - 1 || points->bytes < (size_t)n_points * 16)
         return fail(SVGR_E_INVALID, "svgr_gradient_eval: bad arguments");
-    const int64_t as_row[4] = {0, 0, 1, n_points};
+    const Box as_row{0, 0, 1, (int)n_points};   // (one row of up to 2^31 - 1 points: wider than box_of admits, and no layer)
     return gradient_run(ctx, g, (const double*)points->ptr, nullptr, as_row, out);
 }
 
 int svgr_pattern_fill(svgr_ctx* ctx, const svgr_pattern* pt, const svgr_buf* tile, const svgr_buf* mask, const int64_t* bbox,
                       svgr_buf* out) {
-    if (!ctx || !pt || !tile || !mask || !out || !bbox_ok(bbox)) return fail(SVGR_E_INVALID, "svgr_pattern_fill: bad arguments");
+    Box box;
+    if (!ctx || !pt || !tile || !mask || !out || !box_of(bbox, box)) return fail(SVGR_E_INVALID, "svgr_pattern_fill: bad arguments");
     if (!(pt->cell[2] == pt->cell[2]) || !(pt->cell[3] == pt->cell[3]) || pt->pat_shape[0] <= 0 || pt->pat_shape[1] <= 0 ||
         pt->tile_bbox[2] < 0 || pt->tile_bbox[3] < 0 || pt->tile_bbox[2] > (1 << 24) || pt->tile_bbox[3] > (1 << 24))
         return fail(SVGR_E_INVALID, "svgr_pattern_fill: bad pattern geometry");
-    const size_t n = (size_t)bbox[2] * bbox[3];
+    const size_t n = box_px(box);
     if (mask->bytes < n * 8 || out->bytes < n * 32 || tile->bytes < (size_t)pt->tile_bbox[2] * (size_t)pt->tile_bbox[3] * 32)
         return fail(SVGR_E_INVALID, "svgr_pattern_fill: buffer too small");
     if (n == 0) return 0;
@@ -7840,7 +7790,7 @@ int svgr_pattern_fill(svgr_ctx* ctx, const svgr_pattern* pt, const svgr_buf* til
     hipError_t e = hipMemsetAsync(flag.p, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         SVGR_LAUNCH(k_pattern_fill, grid1(n), dim3(256), 0, ctx->stream, *pt, (const double*)tile->ptr, (const double*)mask->ptr,
-                           (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], flag.as<int>(), (double*)out->ptr);
+                           box, flag.as<int>(), (double*)out->ptr);
         e = hipMemcpyAsync(&oob, flag.p, sizeof oob, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess) e = hipGetLastError();
@@ -7903,13 +7853,14 @@ int svgr_image_upload(svgr_ctx* ctx, const uint8_t* rgba, int64_t h, int64_t w, 
 
 int svgr_image_fill(svgr_ctx* ctx, const svgr_image* im, const svgr_buf* levels, const svgr_buf* mask, const int64_t* bbox,
                     svgr_buf* out) {
-    if (!ctx || !im || !levels || !mask || !out || !bbox_ok(bbox) || !image_size_ok(im->height, im->width))
+    Box box;
+    if (!ctx || !im || !levels || !mask || !out || !box_of(bbox, box) || !image_size_ok(im->height, im->width))
         return fail(SVGR_E_INVALID, "svgr_image_fill: bad arguments");
     const int64_t nl = image_n_levels(im->height, im->width);
     if (!(im->lod >= 0.0 && im->lod <= (double)(nl - 1)) || (im->smooth != 0 && im->smooth != 1))
         return fail(SVGR_E_INVALID, "svgr_image_fill: bad level of detail or mode");
     int64_t th, tw;
-    const size_t n = (size_t)bbox[2] * bbox[3];
+    const size_t n = box_px(box);
     if (mask->bytes < n * 8 || out->bytes < n * 32 || levels->bytes < (size_t)image_level(im->height, im->width, nl, &th, &tw) * 16)
         return fail(SVGR_E_INVALID, "svgr_image_fill: buffer too small");
     if (n == 0) return 0;
@@ -7921,9 +7872,9 @@ int svgr_image_fill(svgr_ctx* ctx, const svgr_image* im, const svgr_buf* levels,
     const int64_t o0 = image_level(im->height, im->width, k, &h0, &w0), o1 = image_level(im->height, im->width, k1, &h1, &w1);
     const float4* tex = (const float4*)levels->ptr;
     const ImageLevel lo{tex + o0, (int)h0, (int)w0, std::ldexp(1.0, -(int)k)}, hi{tex + o1, (int)h1, (int)w1, std::ldexp(1.0, -(int)k1)};
-    const dim3 grid((unsigned)((bbox[3] + IMG_TW - 1) / IMG_TW), (unsigned)std::min<int64_t>((bbox[2] + IMG_TH - 1) / IMG_TH, 32768));
+    const dim3 grid((unsigned)((box.cols + IMG_TW - 1) / IMG_TW), (unsigned)std::min<int64_t>((box.rows + IMG_TH - 1) / IMG_TH, 32768));
     return launch_tail(ctx, im->smooth ? k_image_fill<true> : k_image_fill<false>, grid, dim3(256), 0, *im, lo, hi, blend,
-                       (const double*)mask->ptr, (int)bbox[0], (int)bbox[1], (int)bbox[2], (int)bbox[3], (double*)out->ptr);
+                       (const double*)mask->ptr, box, (double*)out->ptr);
 }
 
 int svgr_jpeg_decode(svgr_ctx* ctx, const svgr_jpeg_frame* frame, const int16_t* coef, int64_t n_coef, const uint16_t* quant,
@@ -9713,7 +9664,7 @@ struct TensorLaunch {
     TensorOp op;
     int src_kind, n_ch;
     int planes, per_px;        // planar: n_ch planes of 1 element per pixel; interleaved: 1 plane of n_ch
-    long long s0, s1, srows, scols;
+    Box sb;                    // the source layer's box
     long long rows, cols;
     long long stride_p, stride_h, offset;   // elements
 };
@@ -9746,7 +9697,7 @@ __global__ __launch_bounds__(TENSOR_LANES) void k_tensor_pack(T* __restrict__ ds
         for (int i = tid; i < n_px; i += TENSOR_LANES) {
             const long long col = clo + i;
             double px[4], y[4];
-            tensor_load_px(src, a.src_kind, row, col, a.s0, a.s1, a.srows, a.scols, px);
+            tensor_load_px(src, a.src_kind, row, col, a.sb.r0, a.sb.c0, a.sb.rows, a.sb.cols, px);
             const int n = tensor_px(a.op, px[0], px[1], px[2], px[3], y);
             SVGR_UNROLL
             for (int k = 0; k < 4; ++k) {
@@ -9857,12 +9808,11 @@ int svgr_layer_to_tensor(svgr_ctx* ctx, const svgr_tensor_desc* desc, const svgr
     bool empty;
     if (int rc = tensor_check(entry, desc, a, sc, sw, empty)) return rc;
     if (empty) return 0;
-    if (!src || !dst || !bbox_ok(src_bbox)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
+    if (!src || !dst || !box_of(src_bbox, a.sb)) return fail(SVGR_E_INVALID, "%s: bad arguments", entry);
     if (int rc = tensor_bounds(entry, desc, a, dst)) return rc;
     const size_t px_bytes = desc->source == TENSOR_SRC_RGBA_F64 ? 32 : desc->source == TENSOR_SRC_RGBA_F32 ? 16 : 8;
-    if (src->bytes < (size_t)src_bbox[2] * (size_t)src_bbox[3] * px_bytes) return fail(SVGR_E_INVALID, "%s: the source buffer is too small for its box", entry);
+    if (src->bytes < box_px(a.sb) * px_bytes) return fail(SVGR_E_INVALID, "%s: the source buffer is too small for its box", entry);
     if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
-    a.s0 = src_bbox[0]; a.s1 = src_bbox[1]; a.srows = src_bbox[2]; a.scols = src_bbox[3];
     const dim3 grid((unsigned)((a.cols + TENSOR_BLOCK - 1) / TENSOR_BLOCK), (unsigned)std::min<long long>(a.rows, 65535));
     switch (tensor_elem_bytes(desc->dtype)) {
         case 4: return launch_tail(ctx, k_tensor_pack<uint32_t>, grid, dim3(TENSOR_LANES), 0, (uint32_t*)dst->ptr, (const void*)src->ptr, a);
