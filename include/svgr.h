@@ -47,7 +47,8 @@ extern "C" {
  *    svgr_tensor_run, svgr_stream_wait_for and svgr_stream_signal_to added (tensor output); svgr_quant_distinct,
  *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output); svgr_quant_dither,
  *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering); svgr_png_samples, svgr_png_filter_bytes and
- *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output) */
+ *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output); svgr_cover_forward, svgr_cover_backward, svgr_cover_block
+ *    and svgr_cover_scan added (differentiable coverage) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1068,6 +1069,47 @@ int svgr_quant_dither(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, in
                       int amp, svgr_buf* out_stream, svgr_buf* out_indices);
 int svgr_dither_tile_rows(void);
 int svgr_dither_tile_cols(void);
+
+/* Differentiable coverage (svgrasterize_amd.diff, beyond the reference; csrc/svgr_cover.h has the arithmetic, DESIGN.md 7w the
+ * derivation): the exact area coverage of n_paths paths over one viewport, and the derivative of sum(grad_out * cover) with
+ * respect to the control points and the transforms.  Every array is a DEVICE buffer:
+ *   segs          n_segs x 4 x 2 doubles, user space, as svgr_batch_desc.segs (a line uses its first two points)
+ *   seg_kind      n_segs uint8, SVGR_SEG_*
+ *   path_seg_off  n_paths + 1 int32: path p owns the segments [off[p], off[p + 1])
+ *   path_m6       n_paths x 6 doubles;  path_rule  n_paths uint8, SVGR_FILL_*
+ *   cover         n_paths x rows x cols of the plane type (double or float): plane p is Path.mask of path p placed on the viewport
+ *   slope         n_paths x rows x cols int8: the derivative of the fill rule at the pixel's accumulated signed coverage
+ *   grad_out      of cover's shape and type;  grad_segs  n_segs x 4 x 2 doubles;  grad_m6  n_paths x 6 doubles
+ *   status        one uint32 the kernels OR into (the caller clears it): bit 0 the flatten depth cap was hit; bit 1 a transformed
+ *                 control point is not finite or beyond +-1e9 pixels, or an edge's row reaches beyond them (it adds nothing)
+ * svgr_cover_forward: cover and slope are written whole.  The segments add their pieces into a double accumulation plane with
+ *   global atomic adds (cover itself for SVGR_COVER_F64, a block of the library's for SVGR_COVER_F32), so cover's last bits may
+ *   differ from run to run; one row scan per (path, row) then resolves the plane.
+ * svgr_cover_backward: grad_segs and grad_m6 are written whole, from slope and grad_out alone: no atomics, the same bits on
+ *   every run.  The derivative is taken at fixed subdivision and is not defined where a pixel sits on a kink of its rule.
+ * Both enqueue on the context's stream and never wait; they keep no state.  Before any launch: a count or a viewport side that
+ * is not positive (n_segs may be 0), an unknown plane type, a flatness that is not positive and finite, a missing buffer or one
+ * too small for the description give SVGR_E_INVALID; n_paths * rows * cols beyond 2^31 - 1 gives SVGR_E_OVERFLOW.  n_segs == 0
+ * zeroes the outputs and launches nothing else.
+ * svgr_cover_block: the segments of one workgroup of the segment kernels.  svgr_cover_scan: the columns one step of the row scan
+ * covers.  Their launch seams. */
+#define SVGR_COVER_F64 0
+#define SVGR_COVER_F32 1
+typedef struct {
+    int64_t n_segs, n_paths;
+    int64_t viewport[4];   /* {row0, col0, rows, cols} */
+    double flatness;
+    int32_t plane;         /* SVGR_COVER_F64 / SVGR_COVER_F32 */
+    int32_t reserved;      /* 0 */
+} svgr_cover_desc;
+int svgr_cover_forward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_buf* segs, const svgr_buf* seg_kind,
+                       const svgr_buf* path_seg_off, const svgr_buf* path_m6, const svgr_buf* path_rule, svgr_buf* cover, svgr_buf* slope,
+                       svgr_buf* status);
+int svgr_cover_backward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_buf* segs, const svgr_buf* seg_kind,
+                        const svgr_buf* path_seg_off, const svgr_buf* path_m6, const svgr_buf* slope, const svgr_buf* grad_out,
+                        svgr_buf* grad_segs, svgr_buf* grad_m6, svgr_buf* status);
+int svgr_cover_block(void);
+int svgr_cover_scan(void);
 
 #ifdef __cplusplus
 }

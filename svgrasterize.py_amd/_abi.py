@@ -93,7 +93,16 @@ class TensorDesc(C.Structure):  # svgr_tensor_desc
     ]
 
 
+class CoverDesc(C.Structure):  # svgr_cover_desc
+    _fields_ = [
+        ("n_segs", C.c_int64), ("n_paths", C.c_int64), ("viewport", C.c_int64 * 4), ("flatness", C.c_double), ("plane", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 TENSOR_SRC_RGBA_F64, TENSOR_SRC_RGBA_F32, TENSOR_SRC_MASK_F64 = 0, 1, 2
+COVER_F64, COVER_F32 = 0, 1
+COVER_STATUS_DEPTH, COVER_STATUS_RANGE = 1, 2
 TENSOR_F32, TENSOR_F16, TENSOR_BF16, TENSOR_U8 = 0, 1, 2, 3
 TENSOR_RGBA, TENSOR_RGB, TENSOR_ALPHA, TENSOR_LUMA = 0, 1, 2, 3
 JPEG_GREY, JPEG_YCBCR, JPEG_RGB = 0, 1, 2
@@ -234,6 +243,10 @@ _PROTOS = {
     "svgr_png_samples": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _P]),
     "svgr_png_filter_bytes": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _P]),
     "svgr_png_filter_span": (C.c_int, []),
+    "svgr_cover_forward": (C.c_int, [_P, C.POINTER(CoverDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "svgr_cover_backward": (C.c_int, [_P, C.POINTER(CoverDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "svgr_cover_block": (C.c_int, []),
+    "svgr_cover_scan": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -10766,3 +10766,248 @@ int svgr_quant_dither(svgr_ctx* ctx, const svgr_buf* src_rgba8, int64_t rows, in
     return abi_guard("svgr_quant_dither", [&]() { return quant_dither_impl(ctx, src_rgba8, rows, cols, palette, n_palette, mode, amp, out_stream, out_indices); });
 }
 }  // extern "C"
+
+// ======================================================================================
+// differentiable coverage: svgr_cover_forward / svgr_cover_backward (csrc/svgr_cover.h has the per-lane arithmetic, DESIGN.md 7w
+// the derivation).  New kernels beside the renderer's: k_flatten, k_path_build and k_tile_render are not involved.
+//   forward   k_cover_accumulate  a lane per segment: flattens in registers and adds every row piece of every edge into the path's
+//                                 double plane with one global atomic add each (the ATOMIC form: a plane may be any size, so it
+//                                 cannot be staged in LDS, and a segment leaves a handful of pieces per row it crosses)
+//             k_cover_resolve     a wave per (path, row): the running sum of the row, COVER_SCAN columns per step, -> cover, slope
+//   backward  k_cover_vjp         a lane per segment: flattens again with the same code (the same edges to the bit), walks each edge
+//                                 over W = grad_out * slope and writes its own 8 + 6 doubles; no atomics, no edge list
+//             k_cover_vjp_m6      a lane per path: the 6 partials of its segments summed in segment order
+// No host read-back between the launches; nothing waits.
+// ======================================================================================
+#include "svgr_cover.h"
+
+constexpr int COVER_BLOCK = 64;                 // segments per workgroup of the two segment kernels: a lane each, one wave
+constexpr int COVER_RUN = 4;                    // consecutive columns a lane of the row scan takes per step
+constexpr int COVER_SCAN = 64 * COVER_RUN;      // columns per step of the row scan
+
+struct CoverGeom {
+    const double* segs;
+    const uint8_t* kind;
+    const int* seg_off;
+    const double* m6;
+    int n_segs, n_paths, rows, cols;
+    double or0, oc0, thr;
+};
+
+// the path whose range [off[p], off[p + 1]) holds `seg` (empty paths in front of it are passed over); -1: none
+__device__ __forceinline__ int cover_path_of(const int* __restrict__ off, int n_paths, int seg) {
+    int lo = 0, hi = n_paths;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= seg) lo = mid; else hi = mid;
+    }
+    return off[lo] <= seg && seg < off[lo + 1] ? lo : -1;
+}
+
+__global__ __launch_bounds__(COVER_BLOCK) void k_cover_accumulate(const CoverGeom g, double* __restrict__ acc, unsigned* __restrict__ status) {
+    const int seg = blockIdx.x * COVER_BLOCK + threadIdx.x;
+    if (seg >= g.n_segs) return;
+    const int p = cover_path_of(g.seg_off, g.n_paths, seg);
+    if (p < 0) return;
+    double pts[8];
+    for (int i = 0; i < 8; ++i) pts[i] = g.segs[8 * (size_t)seg + i];
+    const int rows = g.rows, cols = g.cols;
+    double* plane = acc + (size_t)p * (size_t)rows * (size_t)cols;
+    const int st = cover_seg_accumulate(pts, g.kind[seg] != SVGR_SEG_LINE, g.m6 + 6 * (size_t)p, g.or0, g.oc0, rows, cols, g.thr,
+                                        [&](int r, int c, double v) {
+                                            if ((unsigned)r < (unsigned)rows && (unsigned)c < (unsigned)cols)
+                                                unsafeAtomicAdd(plane + (size_t)r * (size_t)cols + (size_t)c, v);
+                                        });
+    if (st) atomicOr(status, (unsigned)st);
+}
+
+// (acc and cover are the same memory for double planes: a lane reads its own columns of a step before it writes them)
+template <class T>
+__global__ __launch_bounds__(64) void k_cover_resolve(const double* acc, const uint8_t* __restrict__ rule, int rows, int cols, T* cover,
+                                                      int8_t* __restrict__ slope) {
+    const size_t pr = blockIdx.x;   // path * rows + row
+    const int evenodd = rule[pr / (size_t)rows] & 1;
+    const double* a = acc + pr * (size_t)cols;
+    T* o = cover + pr * (size_t)cols;
+    int8_t* s = slope + pr * (size_t)cols;
+    const int lane = threadIdx.x;
+    double carry = 0.0;
+    for (int c0 = 0; c0 < cols; c0 += COVER_SCAN) {
+        const int c = c0 + lane * COVER_RUN;
+        double v[COVER_RUN];
+        SVGR_UNROLL
+        for (int k = 0; k < COVER_RUN; ++k) v[k] = c + k < cols ? a[c + k] : 0.0;
+        SVGR_UNROLL
+        for (int k = 1; k < COVER_RUN; ++k) v[k] = v[k - 1] + v[k];
+        double inc = v[COVER_RUN - 1];
+        for (int d = 1; d < 64; d <<= 1) {
+            const double up = __shfl_up(inc, d);
+            if (lane >= d) inc = up + inc;
+        }
+        double before = __shfl_up(inc, 1);
+        before = lane == 0 ? carry : carry + before;
+        SVGR_UNROLL
+        for (int k = 0; k < COVER_RUN; ++k) {
+            if (c + k < cols) {
+                const double A = before + v[k];
+                o[c + k] = (T)fill_rule(A, evenodd);
+                s[c + k] = (int8_t)cover_slope(A, evenodd);
+            }
+        }
+        carry = carry + __shfl(inc, 63);
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(COVER_BLOCK) void k_cover_vjp(const CoverGeom g, const int8_t* __restrict__ slope, const T* __restrict__ grad_out,
+                                                           double* __restrict__ grad_segs, double* __restrict__ part,
+                                                           unsigned* __restrict__ status) {
+    const int seg = blockIdx.x * COVER_BLOCK + threadIdx.x;
+    if (seg >= g.n_segs) return;
+    const int p = cover_path_of(g.seg_off, g.n_paths, seg);
+    double gs[8], gm[6];
+    for (int i = 0; i < 8; ++i) gs[i] = 0.0;
+    for (int i = 0; i < 6; ++i) gm[i] = 0.0;
+    if (p >= 0) {
+        double pts[8];
+        for (int i = 0; i < 8; ++i) pts[i] = g.segs[8 * (size_t)seg + i];
+        const int rows = g.rows, cols = g.cols;
+        const size_t base = (size_t)p * (size_t)rows * (size_t)cols;
+        const int st = cover_seg_vjp(pts, g.kind[seg] != SVGR_SEG_LINE, g.m6 + 6 * (size_t)p, g.or0, g.oc0, rows, cols, g.thr,
+                                     [&](int r, int c) {
+                                         if ((unsigned)r >= (unsigned)rows || (unsigned)c >= (unsigned)cols) return 0.0;
+                                         const size_t i = base + (size_t)r * (size_t)cols + (size_t)c;
+                                         const int sl = slope[i];
+                                         return sl ? cover_weight((double)grad_out[i], sl) : 0.0;
+                                     }, gs, gm);
+        if (st) atomicOr(status, (unsigned)st);
+    }
+    for (int i = 0; i < 8; ++i) grad_segs[8 * (size_t)seg + i] = gs[i];
+    for (int i = 0; i < 6; ++i) part[6 * (size_t)seg + i] = gm[i];
+}
+
+__global__ __launch_bounds__(64) void k_cover_vjp_m6(const double* __restrict__ part, const int* __restrict__ seg_off, int n_segs, int n_paths,
+                                                     double* __restrict__ grad_m6) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_paths) return;
+    int s0 = seg_off[p], s1 = seg_off[p + 1];
+    s0 = s0 < 0 ? 0 : s0;
+    s1 = s1 > n_segs ? n_segs : s1;
+    double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int s = s0; s < s1; ++s)
+        for (int k = 0; k < 6; ++k) m[k] = m[k] + part[6 * (size_t)s + k];
+    for (int k = 0; k < 6; ++k) grad_m6[6 * (size_t)p + k] = m[k];
+}
+
+// Everything of a description and its input buffers that can be wrong, and the kernels' numbers from it.
+static int cover_check(const char* entry, const svgr_ctx* ctx, const svgr_cover_desc* d, const svgr_buf* segs, const svgr_buf* kind,
+                       const svgr_buf* off, const svgr_buf* m6, const svgr_buf* status, CoverGeom& g, size_t& n_px) {
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
+    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
+    constexpr int64_t kMax = (1ll << 31) - 1;
+    if (d->n_segs < 0 || d->n_segs > kMax - COVER_BLOCK || d->n_paths <= 0 || d->n_paths > kMax - 64)
+        return fail(SVGR_E_INVALID, "%s: n_segs %lld is negative or n_paths %lld is not positive (or beyond 2^31)", entry, (long long)d->n_segs, (long long)d->n_paths);
+    const int64_t row0 = d->viewport[0], col0 = d->viewport[1], rows = d->viewport[2], cols = d->viewport[3];
+    if (rows <= 0 || cols <= 0) return fail(SVGR_E_INVALID, "%s: a viewport of %lld x %lld", entry, (long long)rows, (long long)cols);
+    if (row0 < -(1ll << 30) || row0 > (1ll << 30) || col0 < -(1ll << 30) || col0 > (1ll << 30))
+        return fail(SVGR_E_INVALID, "%s: the viewport's origin is beyond +-2^30", entry);
+    if (d->plane < 0 || d->plane >= COVER_PLANES || d->reserved != 0) return fail(SVGR_E_INVALID, "%s: unknown plane type %d", entry, (int)d->plane);
+    if (!(d->flatness > 0.0) || !std::isfinite(d->flatness)) return fail(SVGR_E_INVALID, "%s: flatness must be positive and finite", entry);
+    if (rows > kMax || cols > kMax || (unsigned __int128)d->n_paths * (unsigned __int128)rows * (unsigned __int128)cols > (unsigned __int128)kMax)
+        return fail(SVGR_E_OVERFLOW, "%s: %lld planes of %lld x %lld pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_paths, (long long)rows, (long long)cols);
+    if (!off || !m6 || !status || (d->n_segs > 0 && (!segs || !kind))) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if ((d->n_segs > 0 && (segs->bytes < (size_t)d->n_segs * 64 || kind->bytes < (size_t)d->n_segs)) || off->bytes < ((size_t)d->n_paths + 1) * 4 ||
+        m6->bytes < (size_t)d->n_paths * 48 || status->bytes < 4)
+        return fail(SVGR_E_INVALID, "%s: an input buffer is too small for the description", entry);
+    n_px = (size_t)d->n_paths * (size_t)rows * (size_t)cols;
+    g.segs = d->n_segs > 0 ? (const double*)segs->ptr : nullptr;
+    g.kind = d->n_segs > 0 ? (const uint8_t*)kind->ptr : nullptr;
+    g.seg_off = (const int*)off->ptr;
+    g.m6 = (const double*)m6->ptr;
+    g.n_segs = (int)d->n_segs; g.n_paths = (int)d->n_paths; g.rows = (int)rows; g.cols = (int)cols;
+    g.or0 = (double)row0; g.oc0 = (double)col0;
+    g.thr = (d->flatness * d->flatness) * 16.0;   // (svgr_batch_create's)
+    return 0;
+}
+
+static int cover_forward_impl(svgr_ctx* ctx, const svgr_cover_desc* d, const svgr_buf* segs, const svgr_buf* kind, const svgr_buf* off,
+                              const svgr_buf* m6, const svgr_buf* rule, svgr_buf* cover, svgr_buf* slope, svgr_buf* status) {
+    static const char* entry = "svgr_cover_forward";
+    CoverGeom g;
+    size_t n_px;
+    if (int rc = cover_check(entry, ctx, d, segs, kind, off, m6, status, g, n_px)) return rc;
+    if (!rule || !cover || !slope) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    const size_t eb = (size_t)cover_plane_bytes(d->plane);
+    if (rule->bytes < (size_t)g.n_paths || cover->bytes < n_px * eb || slope->bytes < n_px)
+        return fail(SVGR_E_INVALID, "%s: rule, cover or slope is too small for the description", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    if (g.n_segs == 0) {
+        HIPCHK(hipMemsetAsync(cover->ptr, 0, n_px * eb, st));
+        HIPCHK(hipMemsetAsync(slope->ptr, 0, n_px, st));
+        return 0;
+    }
+    PoolBlock scratch;   // (float planes: the double accumulation plane; goes back at scope end by the pool's stream-order rule)
+    double* acc = (double*)cover->ptr;
+    if (d->plane == COVER_F32) {
+        HIPCHK(scratch.alloc(n_px * 8, ctx->device));
+        acc = scratch.as<double>();
+    }
+    HIPCHK(hipMemsetAsync(acc, 0, n_px * 8, st));
+    SVGR_LAUNCH(k_cover_accumulate, grid1((size_t)g.n_segs, COVER_BLOCK), dim3(COVER_BLOCK), 0, st, g, acc, (unsigned*)status->ptr);
+    const dim3 rgrid((unsigned)((size_t)g.n_paths * (size_t)g.rows));
+    if (d->plane == COVER_F32)
+        SVGR_LAUNCH(k_cover_resolve<float>, rgrid, dim3(64), 0, st, (const double*)acc, (const uint8_t*)rule->ptr, g.rows, g.cols, (float*)cover->ptr, (int8_t*)slope->ptr);
+    else
+        SVGR_LAUNCH(k_cover_resolve<double>, rgrid, dim3(64), 0, st, (const double*)acc, (const uint8_t*)rule->ptr, g.rows, g.cols, (double*)cover->ptr, (int8_t*)slope->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int cover_backward_impl(svgr_ctx* ctx, const svgr_cover_desc* d, const svgr_buf* segs, const svgr_buf* kind, const svgr_buf* off,
+                               const svgr_buf* m6, const svgr_buf* slope, const svgr_buf* grad_out, svgr_buf* grad_segs, svgr_buf* grad_m6,
+                               svgr_buf* status) {
+    static const char* entry = "svgr_cover_backward";
+    CoverGeom g;
+    size_t n_px;
+    if (int rc = cover_check(entry, ctx, d, segs, kind, off, m6, status, g, n_px)) return rc;
+    if (!slope || !grad_out || !grad_m6 || (g.n_segs > 0 && !grad_segs)) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    const size_t eb = (size_t)cover_plane_bytes(d->plane);
+    if (slope->bytes < n_px || grad_out->bytes < n_px * eb || grad_m6->bytes < (size_t)g.n_paths * 48 ||
+        (g.n_segs > 0 && grad_segs->bytes < (size_t)g.n_segs * 64))
+        return fail(SVGR_E_INVALID, "%s: slope, grad_out, grad_segs or grad_m6 is too small for the description", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    if (g.n_segs == 0) {
+        HIPCHK(hipMemsetAsync(grad_m6->ptr, 0, (size_t)g.n_paths * 48, st));
+        return 0;
+    }
+    PoolBlock part;   // the segments' 6 partials of their path's transform
+    HIPCHK(part.alloc((size_t)g.n_segs * 48, ctx->device));
+    const dim3 sgrid = grid1((size_t)g.n_segs, COVER_BLOCK);
+    if (d->plane == COVER_F32)
+        SVGR_LAUNCH(k_cover_vjp<float>, sgrid, dim3(COVER_BLOCK), 0, st, g, (const int8_t*)slope->ptr, (const float*)grad_out->ptr, (double*)grad_segs->ptr,
+                    part.as<double>(), (unsigned*)status->ptr);
+    else
+        SVGR_LAUNCH(k_cover_vjp<double>, sgrid, dim3(COVER_BLOCK), 0, st, g, (const int8_t*)slope->ptr, (const double*)grad_out->ptr, (double*)grad_segs->ptr,
+                    part.as<double>(), (unsigned*)status->ptr);
+    SVGR_LAUNCH(k_cover_vjp_m6, grid1((size_t)g.n_paths, 64), dim3(64), 0, st, (const double*)part.p, g.seg_off, g.n_segs, g.n_paths, (double*)grad_m6->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+int svgr_cover_block(void) { return COVER_BLOCK; }
+int svgr_cover_scan(void) { return COVER_SCAN; }
+
+int svgr_cover_forward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_buf* segs, const svgr_buf* seg_kind, const svgr_buf* path_seg_off,
+                       const svgr_buf* path_m6, const svgr_buf* path_rule, svgr_buf* cover, svgr_buf* slope, svgr_buf* status) {
+    return abi_guard("svgr_cover_forward", [&]() { return cover_forward_impl(ctx, desc, segs, seg_kind, path_seg_off, path_m6, path_rule, cover, slope, status); });
+}
+
+int svgr_cover_backward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_buf* segs, const svgr_buf* seg_kind, const svgr_buf* path_seg_off,
+                        const svgr_buf* path_m6, const svgr_buf* slope, const svgr_buf* grad_out, svgr_buf* grad_segs, svgr_buf* grad_m6,
+                        svgr_buf* status) {
+    return abi_guard("svgr_cover_backward", [&]() { return cover_backward_impl(ctx, desc, segs, seg_kind, path_seg_off, path_m6, slope, grad_out, grad_segs, grad_m6, status); });
+}
+}  // extern "C"

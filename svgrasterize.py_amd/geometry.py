@@ -694,6 +694,22 @@ class Path:
 
         return path_msdf(self, transform, viewport, spread, dtype, fill_rule, angle, flatness)
 
+    def coverage(self, transform: Transform | None, viewport, fill_rule: str | None = None, dtype=np.float64):
+        """``(cover, slope)`` over ``viewport = (row0, col0, rows, cols)`` (beyond the reference): ``cover`` is ``mask``'s image placed
+        on the viewport's plane, zeros elsewhere; ``slope`` is the int8 plane of the fill rule's derivative, which
+        ``diff.coverage_backward`` takes.  The single-path form of ``diff.coverage``; DESIGN.md 7w has the arithmetic."""
+        from .diff import path_coverage  # noqa: PLC0415
+
+        return path_coverage(self, transform, viewport, fill_rule, dtype)
+
+    def coverage_vjp(self, transform: Transform | None, viewport, grad_out, fill_rule: str | None = None):
+        """``(grad_segs, grad_m6)``: the derivative of ``sum(grad_out * cover)`` with respect to ``packed()``'s segments,
+        ``(n_segs, 4, 2)`` in user space (a line's last two points stay 0; sum the entries of a point that segments share), and to
+        the transform's ``m6()``, ``(6,)``.  At fixed subdivision; not defined where a pixel sits on a kink of the fill rule."""
+        from .diff import path_coverage_vjp  # noqa: PLC0415
+
+        return path_coverage_vjp(self, transform, viewport, grad_out, fill_rule)
+
     def dash(self, dashes, offset: float = 0.0, path_length: float | None = None) -> "Path":
         """The path cut into its dashes (``stroke-dasharray`` / ``stroke-dashoffset``, SVG 2 13.5; beyond the reference): every
         "on" dash an open subpath, ready for ``stroke``.  Eager, on the device (svgr_path_dash); quadratic and arc segments are
