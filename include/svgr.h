@@ -445,12 +445,16 @@ int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int
                           int is_max);
 /* Filter primitives the reference does not implement (filters.py; DESIGN.md "Filter primitives beyond the reference").  All images
  * are (rows, cols, 4) double, linear RGB; the arithmetic is svgr_core.h's (turb_point, transfer_fn) or written out below, in the
- * order given, without contractions.                                                                                             */
+ * order given, without contractions.  Every floating-point parameter of svgr_layer_turbulence, _component_transfer,
+ * _convolve_matrix and _lighting must be finite, or the entry returns SVGR_E_INVALID before any launch; every clamp to [0, 1]
+ * below sends NaN to 0, so a NaN pixel or intermediate never leaves a primitive (DESIGN.md "Filter primitives at the edges of
+ * their values").                                                                                                                */
 /* feTurbulence (Filter Effects 1): out (bbox[2] x bbox[3] x 4, straight alpha) at device offset (bbox[0], bbox[1]).  Pixel [R, C]
  * is the device point (bbox[0] + R + 0.5, bbox[1] + C + 0.5); inv_m6 (rows 0-1 of the inverse transform) takes it to the user
  * point (x, y) the noise is evaluated at.  tile = {x, y, width, height} of the stitch tile in user space; the lattice is set up
  * on the host from `seed` (svgr::turb_init).  octaves 0..SVGR_TURBULENCE_MAX_OCTAVES, base frequencies >= 0, fractal: 0 turbulence,
- * 1 fractalNoise; stitch: 0 noStitch, 1 stitch.                                                                                 */
+ * 1 fractalNoise; stitch: 0 noStitch, 1 stitch.  With stitch the tile must have width > 0 and height > 0 and keep the stitch state
+ * of the last octave within 2^53 (svgr::turb_params_valid).  Defined for every finite point, however large.                     */
 #define SVGR_TURBULENCE_MAX_OCTAVES 32
 int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, const double* inv_m6, double base_fx, double base_fy,
                           const double* tile, int64_t seed, int octaves, int fractal, int stitch);

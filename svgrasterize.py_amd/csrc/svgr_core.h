@@ -508,12 +508,20 @@ SVGR_HD void over_px_fma(double* dst, double s0, double s1, double s2, double s3
     dst[3] = fma(dst[3], k, s3);
 }
 
+// The final clamp of the filter primitives below: [0, 1], and NaN -> 0 (every comparison with NaN is false), so that a
+// NaN pixel or a NaN intermediate never leaves a primitive.  -0 becomes +0; every other value is what
+// `r < 0 ? 0 : (r > 1 ? 1 : r)` gives.  clamp_to is the same with an upper end `hi` of its own, itself a clamped value.
+SVGR_HD double clamp_unit(double r) { return r > 0.0 ? (r < 1.0 ? r : 1.0) : 0.0; }
+SVGR_HD double clamp_to(double r, double hi) { return r > 0.0 ? (r < hi ? r : hi) : 0.0; }
+
 // ------------------------------------------------------------------------------------
 // feTurbulence (SVG 1.1 / Filter Effects 1, the spec's C reference code).  The lattice depends on the seed only and is
 // set up on the host once per primitive (turb_init); turb_point evaluates the four channels of one user-space point.
 // Gradients are stored lattice-major: grad[(i * 4 + k) * 2 + axis] = the spec's gradient[k][i][axis], so the eight
 // numbers one lattice point contributes to the four channels sit side by side.  Indices and stitch state are int64:
-// the spec's ints overflow once `wrap` has doubled for twenty octaves.
+// the spec's ints overflow once `wrap` has doubled for twenty octaves.  Every finite coordinate has a defined result
+// (turb_cell), and a stitch state that would leave the exactly representable integers is refused (turb_params_valid):
+// no conversion is out of range and no integer overflows (DESIGN.md "Filter primitives at the edges of their values").
 // ------------------------------------------------------------------------------------
 constexpr int kTurbBSize = 0x100, kTurbBM = 0xff, kTurbN = 0x1000;
 constexpr int kTurbLattice = kTurbBSize + kTurbBSize + 2;   // 514
@@ -576,6 +584,35 @@ SVGR_HD double turb_stitch_freq(double f, double w) {
     return f / lo < hi / f ? lo : hi;
 }
 
+// What turb_params and turb_point accept: finite base frequencies >= 0 and, when stitching, a finite tile of positive
+// width and height whose stitch state stays within the exactly representable integers up to the last octave.  The state
+// of octave k is width_k = 2^k width_0 and wrap_k = 2^k (wrap_0 - 4096) + 4096 (wrap' = 2 wrap - 4096 unrolled), with
+// width_0 = trunc(tile.w f + 0.5) and wrap_0 = trunc(tile.x f + 4096 + width_0), f the adjusted frequency; the last
+// octave is k = octaves - 1.  So the bound is  2^(octaves - 1) max(width_0, |wrap_0 - 4096|) + 4096 <= 2^53  on each axis.
+constexpr double kTurbStateMax = 9007199254740992.0;   // 2^53
+
+SVGR_HD bool turb_axis_valid(double f, double t0, double tw, double scale) {
+    if (!(tw > 0.0)) return false;
+    if (f != 0.0) f = turb_stitch_freq(f, tw);
+    const double w0 = tw * f + 0.5;
+    if (!(f >= 0.0) || !(w0 < kTurbStateMax)) return false;   // (NaN and inf fail both)
+    const double width = trunc(w0), r0 = t0 * f + kTurbN + width;
+    if (!(fabs(r0) < kTurbStateMax)) return false;
+    const double wrap = trunc(r0);
+    return scale * fmax(width, fabs(wrap - kTurbN)) + kTurbN <= kTurbStateMax;
+}
+
+SVGR_HD bool turb_params_valid(double fx, double fy, const double* tile, int octaves, int stitch) {
+    if (!(fx >= 0.0 && fx <= 1.7976931348623157e308) || !(fy >= 0.0 && fy <= 1.7976931348623157e308)) return false;
+    if (octaves < 0 || octaves > kTurbMaxOctaves) return false;
+    if (!stitch) return true;
+    for (int k = 0; k < 4; ++k)
+        if (!(fabs(tile[k]) <= 1.7976931348623157e308)) return false;
+    const double scale = (double)((int64_t)1 << (octaves > 0 ? octaves - 1 : 0));
+    return turb_axis_valid(fx, tile[0], tile[2], scale) && turb_axis_valid(fy, tile[1], tile[3], scale);
+}
+
+// The caller has checked turb_params_valid: every conversion below is in range.
 SVGR_HD TurbParams turb_params(double fx, double fy, const double* tile, int octaves, int fractal, int stitch) {
     TurbParams p;
     p.octaves = octaves;
@@ -597,18 +634,34 @@ SVGR_HD TurbParams turb_params(double fx, double fy, const double* tile, int oct
 
 SVGR_HD double turb_s_curve(double t) { return t * t * (3.0 - 2.0 * t); }
 
+// The lattice cell of coordinate t: its integer part (toward zero) and frac = t - trunc(t), which is 0 from 2^52 on.  The
+// integer part is clamped to +-2^62 before it is converted, so no conversion is out of range.  Beyond 2^62, t is a multiple
+// of 2^10, and +-2^62 stands in for it: the same residue modulo 256 (0), the same side of every stitch wrap
+// (|wrap| <= 2^53 + 4096), and room for the + 1 and - width that follow.  So the index is that of the exact integer part in
+// unbounded integers.  An infinite t (an overflowed product of finite numbers) has the fraction inf - inf = NaN, as has a NaN t
+// (from a non-finite coordinate): the point's noise is NaN, which the final clamp turns into 0 in every channel.  The clamp
+// is two f64 min / max in front of the conversion, and the fraction no longer needs the way back from int64: together no
+// slower than the bare cast (profiles/filter_edges/README.md, which also has the forms that were slower).
+SVGR_HD int64_t turb_cell(double t, double& frac) {
+    const double it = trunc(t);
+    frac = t - it;
+    return (int64_t)fmin(fmax(it, -4611686018427387904.0), 4611686018427387904.0);   // (fmax drops a NaN: -2^62)
+}
+
 // The four channels of feTurbulence at user-space point (px, py), clamped to [0, 1] (straight alpha, RGBA).  The lattice
 // indices, the s-curves and the stitch state of an octave are shared by the channels; each channel then runs the spec's
 // noise2 arithmetic in the spec's order.
-SVGR_HD void turb_point(const int* sel, const double* grad, const TurbParams& p, double px, double py, double* out) {
+// sel and grad are read by index only (pointers in the product; the unit tests pass bounds-checked views).
+template <class Sel, class Grad>
+SVGR_HD void turb_point(Sel sel, Grad grad, const TurbParams& p, double px, double py, double* out) {
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
     double vx = px * p.fx, vy = py * p.fy, ratio = 1.0;
     int64_t width = p.width, height = p.height, wrap_x = p.wrap_x, wrap_y = p.wrap_y;
     for (int o = 0; o < p.octaves; ++o) {
         const double tx = vx + kTurbN, ty = vy + kTurbN;
-        int64_t bx0 = (int64_t)tx, by0 = (int64_t)ty;
+        double rx0, ry0;
+        int64_t bx0 = turb_cell(tx, rx0), by0 = turb_cell(ty, ry0);
         int64_t bx1 = bx0 + 1, by1 = by0 + 1;
-        const double rx0 = tx - (double)(int64_t)tx, ry0 = ty - (double)(int64_t)ty;
         const double rx1 = rx0 - 1.0, ry1 = ry0 - 1.0;
         if (p.stitch) {
             if (bx0 >= wrap_x) bx0 -= width;
@@ -621,15 +674,12 @@ SVGR_HD void turb_point(const int* sel, const double* grad, const TurbParams& p,
         const int b00 = sel[i + by0], b10 = sel[j + by0], b01 = sel[i + by1], b11 = sel[j + by1];
         const double sx = turb_s_curve(rx0), sy = turb_s_curve(ry0);
         for (int k = 0; k < 4; ++k) {
-            const double* q00 = grad + (b00 * 4 + k) * 2;
-            const double* q10 = grad + (b10 * 4 + k) * 2;
-            const double* q01 = grad + (b01 * 4 + k) * 2;
-            const double* q11 = grad + (b11 * 4 + k) * 2;
-            double u = rx0 * q00[0] + ry0 * q00[1];
-            double v = rx1 * q10[0] + ry0 * q10[1];
+            const int q00 = (b00 * 4 + k) * 2, q10 = (b10 * 4 + k) * 2, q01 = (b01 * 4 + k) * 2, q11 = (b11 * 4 + k) * 2;
+            double u = rx0 * grad[q00] + ry0 * grad[q00 + 1];
+            double v = rx1 * grad[q10] + ry0 * grad[q10 + 1];
             const double a = u + sx * (v - u);
-            u = rx0 * q01[0] + ry1 * q01[1];
-            v = rx1 * q11[0] + ry1 * q11[1];
+            u = rx0 * grad[q01] + ry1 * grad[q01 + 1];
+            v = rx1 * grad[q11] + ry1 * grad[q11 + 1];
             const double b = u + sx * (v - u);
             const double n = a + sy * (b - a);
             sum[k] = sum[k] + (p.fractal ? n : fabs(n)) / ratio;
@@ -646,7 +696,7 @@ SVGR_HD void turb_point(const int* sel, const double* grad, const TurbParams& p,
     }
     for (int k = 0; k < 4; ++k) {
         double c = p.fractal ? (sum[k] + 1.0) * 0.5 : sum[k];
-        out[k] = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
+        out[k] = clamp_unit(c);
     }
 }
 
@@ -656,7 +706,9 @@ SVGR_HD void turb_point(const int* sel, const double* grad, const TurbParams& p,
 // ------------------------------------------------------------------------------------
 enum { kXferIdentity = 0, kXferTable = 1, kXferDiscrete = 2, kXferLinear = 3, kXferGamma = 4 };
 
-SVGR_HD double transfer_fn(double c, int type, const double* prm, const double* v, int n) {
+// v is read by index only (a pointer in the product; the unit tests pass a bounds-checked view).
+template <class Table>
+SVGR_HD double transfer_fn(double c, int type, const double* prm, Table v, int n) {
     c = c > 0.0 ? (c < 1.0 ? c : 1.0) : 0.0;   // (NaN -> 0: it must not reach a table index)
     double r = c;
     if (type == kXferTable && n > 0) {
@@ -678,7 +730,26 @@ SVGR_HD double transfer_fn(double c, int type, const double* prm, const double* 
     } else if (type == kXferGamma) {
         r = prm[2] * pow(c, prm[3]) + prm[4];
     }
-    return r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
+    return clamp_unit(r);   // (a NaN from finite parameters, 0 * inf or a huge table's inf - inf, ends as 0)
+}
+
+// ------------------------------------------------------------------------------------
+// feConvolveMatrix: what follows the weighted sums s[0..3] of one pixel.  s / divisor + bias, then preserve = 0: alpha clamped
+// to [0, 1] and the premultiplied colours to [0, alpha]; 1: the straight colours clamped to [0, 1] and `alpha` (the source
+// pixel's) copied.  A NaN sum -- a NaN pixel anywhere under the kernel, weight 0 included, or inf - inf -- ends as 0.
+// ------------------------------------------------------------------------------------
+SVGR_HD void convolve_finish(double* s, double divisor, double bias, int preserve, double alpha) {
+    s[0] = s[0] / divisor + bias;
+    s[1] = s[1] / divisor + bias;
+    s[2] = s[2] / divisor + bias;
+    if (preserve) {
+        s[0] = clamp_unit(s[0]); s[1] = clamp_unit(s[1]); s[2] = clamp_unit(s[2]);
+        s[3] = alpha;
+    } else {
+        const double al = clamp_unit(s[3] / divisor + bias);
+        s[0] = clamp_to(s[0], al); s[1] = clamp_to(s[1], al); s[2] = clamp_to(s[2], al);
+        s[3] = al;
+    }
 }
 
 // ------------------------------------------------------------------------------------
@@ -760,9 +831,7 @@ SVGR_HD void light_pixel(const LightParams& p, const double* a, int top, int bot
         k = p.constant * (nl > 0.0 ? nl : 0.0);
     }
     double r = k * c0, g = k * c1, b = k * c2;
-    r = r < 0.0 ? 0.0 : (r > 1.0 ? 1.0 : r);
-    g = g < 0.0 ? 0.0 : (g > 1.0 ? 1.0 : g);
-    b = b < 0.0 ? 0.0 : (b > 1.0 ? 1.0 : b);
+    r = clamp_unit(r); g = clamp_unit(g); b = clamp_unit(b);   // (a NaN alpha in the neighbourhood ends as 0)
     out[0] = r; out[1] = g; out[2] = b;
     out[3] = p.specular ? (r > g ? (r > b ? r : b) : (g > b ? g : b)) : 1.0;
 }

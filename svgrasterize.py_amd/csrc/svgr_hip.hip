@@ -4106,7 +4106,7 @@ __global__ __launch_bounds__(256) void k_layer_component_transfer(double* __rest
 // (edge mode applied as it is loaded) and the weights in LDS.  out[R, C] = sum over I (rows, outer), J (cols, inner) of
 // src[R - ty + I, C - tx + J] * K[oy - 1 - I][ox - 1 - J], then / divisor + bias.  preserve = 0: all four channels of a
 // premultiplied source, alpha clamped to [0, 1] and colour to [0, alpha]; 1: the colours of a straight source clamped to
-// [0, 1], alpha copied.
+// [0, 1], alpha copied (svgr::convolve_finish: a NaN sum ends as 0).
 struct CmLaunch {
     int rows, cols, ox, oy, tx, ty, edge, preserve, tiles_x;
     double divisor, bias;
@@ -4153,23 +4153,9 @@ __global__ __launch_bounds__(256) void k_layer_convolve_matrix(double* __restric
             s3 = s3 + v.w * k;
         }
     }
-    s0 = s0 / a.divisor + a.bias;
-    s1 = s1 / a.divisor + a.bias;
-    s2 = s2 / a.divisor + a.bias;
-    double al;
-    if (a.preserve) {
-        al = s4[(size_t)R * a.cols + C].w;
-        s0 = s0 < 0.0 ? 0.0 : (s0 > 1.0 ? 1.0 : s0);
-        s1 = s1 < 0.0 ? 0.0 : (s1 > 1.0 ? 1.0 : s1);
-        s2 = s2 < 0.0 ? 0.0 : (s2 > 1.0 ? 1.0 : s2);
-    } else {
-        al = s3 / a.divisor + a.bias;
-        al = al < 0.0 ? 0.0 : (al > 1.0 ? 1.0 : al);
-        s0 = s0 < 0.0 ? 0.0 : (s0 > al ? al : s0);
-        s1 = s1 < 0.0 ? 0.0 : (s1 > al ? al : s1);
-        s2 = s2 < 0.0 ? 0.0 : (s2 > al ? al : s2);
-    }
-    reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(s0, s1, s2, al);
+    double s[4] = {s0, s1, s2, s3};
+    svgr::convolve_finish(s, a.divisor, a.bias, a.preserve, a.preserve ? s4[(size_t)R * a.cols + C].w : 0.0);
+    reinterpret_cast<double4*>(out)[(size_t)R * a.cols + C] = make_double4(s[0], s[1], s[2], s[3]);
 }
 
 // feDisplacementMap: out has the map's box `ob`.  d_user = scale * (map[XC] - 0.5, map[YC] - 0.5) of the straight-alpha map,
@@ -7439,6 +7425,13 @@ int svgr_layer_morphology(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src, int
 }
 
 static_assert(svgr::kTurbMaxOctaves == SVGR_TURBULENCE_MAX_OCTAVES, "one octave limit");
+// The floating-point parameters of the filter primitives below come from documents: every one must be finite, or the entry
+// returns SVGR_E_INVALID before any launch (DESIGN.md "Filter primitives at the edges of their values").
+static inline bool all_finite(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
 static inline unsigned stride_blocks(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 1024)); }
 
 int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, const double* inv_m6, double base_fx, double base_fy,
@@ -7449,6 +7442,10 @@ int svgr_layer_turbulence(svgr_ctx* ctx, svgr_buf* out, const int64_t* bbox, con
         return fail(SVGR_E_INVALID, "svgr_layer_turbulence: bad arguments (octaves 0..%d, base frequencies >= 0)", svgr::kTurbMaxOctaves);
     const size_t n = box_px(a.ob);
     if (out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_turbulence: buffer too small");
+    if (!all_finite(inv_m6, 6)) return fail(SVGR_E_INVALID, "svgr_layer_turbulence: the inverse transform is not finite");
+    if (!svgr::turb_params_valid(base_fx, base_fy, tile, octaves, stitch))
+        return fail(SVGR_E_INVALID, "svgr_layer_turbulence: base frequencies and stitch tile must be finite, the tile of positive width and "
+                                    "height, and the stitch state of the last octave within 2^53");
     if (n == 0) return 0;
     return abi_guard("svgr_layer_turbulence", [&]() -> int {
         std::vector<char> host(sizeof(double) * svgr::kTurbLattice * 8 + sizeof(int) * svgr::kTurbLattice);
@@ -7478,6 +7475,8 @@ int svgr_layer_component_transfer(svgr_ctx* ctx, svgr_buf* img, int64_t n_px, co
     if (total > SVGR_TRANSFER_MAX_VALUES)
         return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: %lld table values (at most %d)", (long long)total, SVGR_TRANSFER_MAX_VALUES);
     if (total > 0 && !values) return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: values is NULL");
+    if (!all_finite(params, 20) || !all_finite(values, (size_t)total))
+        return fail(SVGR_E_INVALID, "svgr_layer_component_transfer: parameters and table values must be finite");
     if (n_px == 0) return 0;
     return abi_guard("svgr_layer_component_transfer", [&]() -> int {
         std::vector<double> blob(20 + (size_t)total);
@@ -7508,6 +7507,8 @@ int svgr_layer_convolve_matrix(svgr_ctx* ctx, svgr_buf* out, const svgr_buf* src
         return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: bad arguments (order 1..%d, target inside the kernel, divisor != 0, "
                                     "edge mode 0..2)", SVGR_CONVOLVE_MATRIX_MAX_ORDER);
     const size_t n = (size_t)rows * (size_t)cols;
+    if (!all_finite(kernel, (size_t)(order_x * order_y)) || !std::isfinite(divisor) || !std::isfinite(bias))
+        return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: kernel, divisor and bias must be finite");
     if (src->bytes < n * 32 || out->bytes < n * 32) return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: buffer too small");
     if (out->ptr == src->ptr) return fail(SVGR_E_INVALID, "svgr_layer_convolve_matrix: out must not be src");
     // 16 x 16 tiles while the input tile and the weights fit in 64 KiB of LDS, 8 x 8 beyond (order 32: 56 KiB)
@@ -7549,6 +7550,9 @@ int svgr_layer_lighting(svgr_ctx* ctx, svgr_buf* out, const int64_t* out_bbox, c
     if (!ctx || !out || !src || !light_params || !color3 || !box_of(out_bbox, a.ob) || !box_of(src_bbox, a.sb) || light_kind < svgr::kLightDistant ||
         light_kind > svgr::kLightSpot || (specular != 0 && specular != 1))
         return fail(SVGR_E_INVALID, "svgr_layer_lighting: bad arguments (light kind 0..2, specular 0 or 1)");
+    if (!all_finite(light_params, 8) || !all_finite(color3, 3) || !std::isfinite(surface_scale) || !std::isfinite(constant) ||
+        !std::isfinite(specular_exponent))
+        return fail(SVGR_E_INVALID, "svgr_layer_lighting: light parameters, colour, surface scale, constant and exponent must be finite");
     const size_t n = box_px(a.ob);
     a.tiles_x = (a.ob.cols + kLightTile - 1) / kLightTile;
     const size_t tiles = (size_t)a.tiles_x * (size_t)((a.ob.rows + kLightTile - 1) / kLightTile);

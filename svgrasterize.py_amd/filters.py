@@ -491,6 +491,8 @@ class Filter(NamedTuple):
             elif ftype == FE_TURBULENCE:
                 freq, octaves, seed, stitch, fractal, region = attrs
                 offset, shape, rect = area(region)
+                if not rect[2] > 0 or not rect[3] > 0:
+                    stitch = False   # (a region without area has no pixel to stitch, and a tile must have one)
                 res = Layer.turbulence(transform, offset, shape, freq, octaves, seed, rect if stitch else None, fractal)
             elif ftype == FE_COMPONENT_TRANSFER:
                 res = args[0].component_transfer(attrs[0])

@@ -43,8 +43,12 @@ _TURB_M = 2147483647
 
 def turbulence_seed(seed) -> int:
     """feTurbulence ``seed``, truncated toward zero and brought into int64 without changing the lattice it selects: the set-up
-    clamps seeds above 2^31 - 2 and folds seeds <= 0 by their C remainder modulo 2^31 - 2."""
-    s = int(float(seed))
+    clamps seeds above 2^31 - 2 and folds seeds <= 0 by their C remainder modulo 2^31 - 2.  A seed that is not finite is a
+    ValueError, as every non-finite parameter of the filter primitives."""
+    seed = float(seed)
+    if not math.isfinite(seed):
+        raise ValueError(f"feTurbulence seed must be finite: {seed}")
+    s = int(seed)
     if s > _TURB_M - 1:
         return _TURB_M - 1
     if s <= 0:
@@ -366,7 +370,8 @@ class Layer:
                    fractal_noise: bool = False) -> "Layer":
         """feTurbulence over a (rows, cols) layer at `offset`: the Filter Effects noise of the user-space point of every pixel
         centre.  `base_frequency` = (fx, fy) >= 0; `seed` is truncated toward zero; `stitch_tile` = (x, y, width, height) in
-        user space stitches the noise to that tile, None does not.  Straight-alpha linear RGBA."""
+        user space stitches the noise to that tile, None does not.  Straight-alpha linear RGBA.  Every number must be finite and
+        a stitch tile of positive width and height (ValueError before any launch)."""
         rows, cols = int(shape[0]), int(shape[1])
         fx, fy = (float(f) for f in base_frequency)
         seed = turbulence_seed(seed)
@@ -409,6 +414,8 @@ class Layer:
                 params[k, 2:5] = fn[1:4]
         values = np.ascontiguousarray(np.concatenate(tables) if tables else np.zeros(1), dtype=FLOAT)
         params = np.ascontiguousarray(params, dtype=FLOAT)
+        if not (np.isfinite(params).all() and np.isfinite(values).all()):   # (the entry's own rule, ahead of the copy below)
+            raise ValueError("component_transfer: parameters and table values must be finite")
         layer = self.convert(pre_alpha=False, linear_rgb=True)
         ctx = _abi.Context.get()
         buf = layer._copy_device() if layer is self else layer._device()  # (a converted layer owns a fresh buffer)
@@ -433,6 +440,8 @@ class Layer:
             divisor = float(kernel.sum()) or 1.0
         if edge_mode not in EDGE_MODES:
             raise ValueError(f"invalid edge mode: {edge_mode}")
+        if not (np.isfinite(kernel).all() and math.isfinite(divisor) and math.isfinite(bias)):   # (ahead of the conversion below)
+            raise ValueError("convolve_matrix: kernel, divisor and bias must be finite")
         layer = self.convert(pre_alpha=not preserve_alpha, linear_rgb=True)
         ctx = _abi.Context.get()
         rows, cols = layer.height, layer.width

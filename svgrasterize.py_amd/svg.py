@@ -606,8 +606,40 @@ def _primitive_subregion(attrs, tag, bbox_units):
     return tuple(vals)
 
 
+# every attribute of a filter primitive, of its feFunc*, light source and feMergeNode children, that holds numbers
+_FILTER_NUMBERS = frozenset((
+    "x", "y", "width", "height", "baseFrequency", "numOctaves", "seed", "slope", "intercept", "amplitude", "exponent", "offset",
+    "tableValues", "order", "kernelMatrix", "divisor", "bias", "targetX", "targetY", "kernelUnitLength", "surfaceScale",
+    "diffuseConstant", "specularConstant", "specularExponent", "azimuth", "elevation", "z", "pointsAtX", "pointsAtY", "pointsAtZ",
+    "limitingConeAngle", "k1", "k2", "k3", "k4", "scale", "radius", "stdDeviation", "dx", "dy", "values", "flood-opacity"))
+_NUMBER_SUFFIXES = ("", "%", "px", "pt", "deg", "rad")
+
+
+def _non_finite_attribute(element):
+    """The name of the first numeric attribute of a filter primitive (or of one of its children) that holds a number which is
+    not finite -- ``nan``, ``inf`` or one that overflows, such as ``1e400`` -- or None.  The kernels behind the primitives take
+    finite parameters only, so such a primitive is dropped; what is not a number at all is left to the primitive's own parsing."""
+    for node in (element, *element):
+        for key, text in node.attrib.items():
+            if key not in _FILTER_NUMBERS:
+                continue
+            for token in text.replace(",", " ").split():
+                for suffix in _NUMBER_SUFFIXES:
+                    if suffix and not token.endswith(suffix):
+                        continue
+                    try:
+                        value = float(token[:len(token) - len(suffix)])
+                    except ValueError:
+                        continue
+                    if not math.isfinite(value):
+                        return key if node is element else f"{node.tag.split('}')[-1]} {key}"
+                    break
+    return None
+
+
 def _filter(element, loader=None) -> Filter:
-    """<filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap,
+    """A primitive with a numeric attribute that is not finite is dropped with a warning naming the attribute (no number makes
+    this function raise).  <filter> -> Filter chain (S:3271-3362; feFlood, feTurbulence, feComponentTransfer, feConvolveMatrix, feDisplacementMap,
     feDropShadow, feDiffuseLighting, feSpecularLighting, feTile, feImage, primitive subregions and primitiveUnits beyond the
     reference).  `loader`: the document's loader, which reads feImage's rasters and holds the ids its element references are
     looked up in when the filter runs."""
@@ -624,6 +656,10 @@ def _filter(element, loader=None) -> Filter:
         attrs = child.attrib
         result, src = attrs.get("result"), attrs.get("in")
         before = len(flt.filters)
+        bad = _non_finite_attribute(child) if tag.startswith("fe") else None
+        if bad is not None:
+            warnings.warn(f"{tag}: {bad} is not finite: the primitive is dropped")
+            continue
         sub = _primitive_subregion(attrs, tag, bbox_units) if tag.startswith("fe") else None
         if bbox_units and tag in ("feDiffuseLighting", "feSpecularLighting", "feDisplacementMap"):
             unscaled.add(tag)

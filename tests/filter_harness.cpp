@@ -1,10 +1,31 @@
-// Host build of the filter-primitive arithmetic in svgrasterize.py_amd/csrc/svgr_core.h (turb_init, turb_params, turb_point),
-// and a restatement of the displacement map's source-index guard, for CPU-side unit tests only
-// (tests/test_filter_primitives_host.py, tests/test_gpu_filter_primitives.py, tests/test_image_cases_host.py).  NOT a CPU
-// fallback of the product: the package never loads it.
+// Host build of the filter-primitive arithmetic in svgrasterize.py_amd/csrc/svgr_core.h (turb_init, turb_params_valid,
+// turb_params, turb_point, transfer_fn, convolve_finish), and restatements of the displacement map's source-index guard and of
+// k_layer_convolve_matrix's sums, for CPU-side unit tests only (tests/test_filter_primitives_host.py,
+// tests/test_gpu_filter_primitives.py, tests/test_image_cases_host.py, tests/test_filter_edges_host.py,
+// tests/test_gpu_filter_edges.py).  NOT a CPU fallback of the product: the package never loads it.
+// With -DFILTER_HARNESS_MAIN it is a program that walks a case file (tests/filter_edge_cases.py::case_file), for a run under
+// the undefined-behaviour sanitizer.
+#include <stdio.h>
+#include <stdlib.h>
+
 #include "../svgrasterize.py_amd/csrc/svgr_core.h"
 
 using namespace svgr;
+
+// A table read by index, every index checked: the lattice and the transfer tables go through it, so a read outside one ends the
+// process instead of returning whatever lies there.
+template <class T>
+struct Checked {
+    const T* p;
+    long n;
+    T operator[](long i) const {
+        if (i < 0 || i >= n) {
+            fprintf(stderr, "filter harness: table index %ld outside 0..%ld\n", i, n - 1);
+            abort();
+        }
+        return p[i];
+    }
+};
 
 extern "C" {
 
@@ -17,7 +38,58 @@ void fh_turbulence(int64_t seed, double fx, double fy, const double* tile, int o
     double grad[kTurbLattice * 8];
     turb_init(seed, sel, grad);
     const TurbParams p = turb_params(fx, fy, tile, octaves, fractal, stitch);
-    for (long i = 0; i < n; ++i) turb_point(sel, grad, p, pts[2 * i], pts[2 * i + 1], out + 4 * i);
+    const Checked<int> cs{sel, kTurbLattice};
+    const Checked<double> cg{grad, kTurbLattice * 8};
+    for (long i = 0; i < n; ++i) turb_point(cs, cg, p, pts[2 * i], pts[2 * i + 1], out + 4 * i);
+}
+
+// 1 where svgr_layer_turbulence accepts the parameters (turb_params_valid)
+int fh_turbulence_valid(double fx, double fy, const double* tile, int octaves, int stitch) {
+    return turb_params_valid(fx, fy, tile, octaves, stitch) ? 1 : 0;
+}
+
+// the first octave's state: st = {width, height, wrap_x, wrap_y}, f = the adjusted frequencies
+void fh_turbulence_state(double fx, double fy, const double* tile, int octaves, int stitch, int64_t* st, double* f) {
+    const TurbParams p = turb_params(fx, fy, tile, octaves, 0, stitch);
+    st[0] = p.width; st[1] = p.height; st[2] = p.wrap_x; st[3] = p.wrap_y;
+    f[0] = p.fx; f[1] = p.fy;
+}
+
+// out[i] = transfer_fn(c[i]) for one function: prm = {slope, intercept, amplitude, exponent, offset}, v = its nv table values
+void fh_transfer(const double* c, long n, int type, const double* prm, const double* v, int nv, double* out) {
+    const Checked<double> cv{v, nv};
+    for (long i = 0; i < n; ++i) out[i] = transfer_fn(c[i], type, prm, cv, nv);
+}
+
+// k_layer_convolve_matrix restated: the edge mode as the tile is loaded, the sums over I (rows, outer) and J (columns, inner),
+// then svgr::convolve_finish.  src, out: rows x cols RGBA; w: oy x ox.
+void fh_convolve_matrix(const double* src, long rows, long cols, const double* w, int ox, int oy, int tx, int ty, double divisor,
+                        double bias, int edge, int preserve, double* out) {
+    const Checked<double> px{src, rows * cols * 4}, cw{w, (long)ox * oy};
+    for (long R = 0; R < rows; ++R) {
+        for (long C = 0; C < cols; ++C) {
+            double s[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int I = 0; I < oy; ++I) {
+                for (int J = 0; J < ox; ++J) {
+                    long r = R - ty + I, c = C - tx + J;
+                    bool inside = true;
+                    if (edge == 0) {
+                        r = r < 0 ? 0 : (r >= rows ? rows - 1 : r);
+                        c = c < 0 ? 0 : (c >= cols ? cols - 1 : c);
+                    } else if (edge == 1) {
+                        r = ((r % rows) + rows) % rows;
+                        c = ((c % cols) + cols) % cols;
+                    } else {
+                        inside = r >= 0 && r < rows && c >= 0 && c < cols;
+                    }
+                    const double k = cw[(long)(oy - 1 - I) * ox + (ox - 1 - J)];
+                    for (int q = 0; q < 4; ++q) s[q] = s[q] + (inside ? px[(r * cols + c) * 4 + q] : 0.0) * k;
+                }
+            }
+            convolve_finish(s, divisor, bias, preserve, preserve ? px[(R * cols + C) * 4 + 3] : 0.0);
+            for (int q = 0; q < 4; ++q) out[(R * cols + C) * 4 + q] = s[q];
+        }
+    }
 }
 
 // the layer k_layer_turbulence writes: pixel [R, C] at device point (o0 + R + 0.5, o1 + C + 0.5), user point by inv (plain form)
@@ -32,7 +104,7 @@ void fh_turbulence_layer(int64_t seed, double fx, double fy, const double* tile,
             const double d0 = (double)(o0 + R) + 0.5, d1 = (double)(o1 + C) + 0.5;
             const double px = inv[0] * d0 + inv[1] * d1 + inv[2];
             const double py = inv[3] * d0 + inv[4] * d1 + inv[5];
-            turb_point(sel, grad, p, px, py, out + 4 * (R * cols + C));
+            turb_point(Checked<int>{sel, kTurbLattice}, Checked<double>{grad, kTurbLattice * 8}, p, px, py, out + 4 * (R * cols + C));
         }
     }
 }
@@ -49,3 +121,100 @@ void fh_dm_index(const double* p0, const double* p1, long n, int s0, int s1, int
 }
 
 }  // extern "C"
+
+#ifdef FILTER_HARNESS_MAIN
+// The case file: one case per line, numbers as C hexadecimal floats (or nan / inf / -inf) and decimal integers.
+//   T seed fx fy tile[4] octaves fractal stitch n (px py)[n]      feTurbulence at n points (skipped where not valid: counted)
+//   X type prm[5] nv v[nv] n c[n]                                 one transfer function on n values
+//   C rows cols ox oy tx ty edge preserve divisor bias w[oy ox] src[rows cols 4]
+//   L kind l[8] color[3] ss constant se specular o0 o1 rows cols alpha[rows cols]
+// Every result is checked to be a number in [0, 1].
+#include <vector>
+
+#include "lighting_harness.cpp"
+
+static FILE* g_in;
+static bool next_token(char* buf) { return fscanf(g_in, "%255s", buf) == 1; }
+static double num() {
+    char buf[256];
+    if (!next_token(buf)) { fprintf(stderr, "filter harness: truncated case file\n"); exit(2); }
+    return strtod(buf, nullptr);
+}
+static long integer() {
+    char buf[256];
+    if (!next_token(buf)) { fprintf(stderr, "filter harness: truncated case file\n"); exit(2); }
+    return strtol(buf, nullptr, 10);
+}
+static std::vector<double> nums(long n) {
+    std::vector<double> v((size_t)n);
+    for (long i = 0; i < n; ++i) v[(size_t)i] = num();
+    return v;
+}
+static void check_unit(const std::vector<double>& out, long upto, const char* what, long at) {
+    for (long i = 0; i < upto; ++i)
+        if (!(out[(size_t)i] >= 0.0 && out[(size_t)i] <= 1.0)) {
+            fprintf(stderr, "filter harness: case %ld (%s): value %ld is %g\n", at, what, i, out[(size_t)i]);
+            exit(3);
+        }
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2 || !(g_in = fopen(argv[1], "r"))) { fprintf(stderr, "usage: filter_harness CASEFILE\n"); return 2; }
+    char kind[256];
+    long cases = 0, refused = 0;
+    while (next_token(kind)) {
+        if (kind[0] == 'T') {
+            const long seed = integer();
+            const double fx = num(), fy = num();
+            const std::vector<double> tile = nums(4);
+            const int octaves = (int)integer(), fractal = (int)integer(), stitch = (int)integer();
+            const long n = integer();
+            const std::vector<double> pts = nums(2 * n);
+            std::vector<double> out((size_t)(4 * n) + 1);
+            if (!fh_turbulence_valid(fx, fy, tile.data(), octaves, stitch)) {
+                ++refused;
+            } else {
+                fh_turbulence(seed, fx, fy, tile.data(), octaves, fractal, stitch, pts.data(), n, out.data());
+                check_unit(out, 4 * n, "turbulence", cases);
+            }
+        } else if (kind[0] == 'X') {
+            const int type = (int)integer();
+            const std::vector<double> prm = nums(5);
+            const int nv = (int)integer();
+            const std::vector<double> v = nums(nv);
+            const long n = integer();
+            const std::vector<double> c = nums(n);
+            std::vector<double> out((size_t)n + 1);
+            fh_transfer(c.data(), n, type, prm.data(), v.data(), nv, out.data());
+            check_unit(out, n, "transfer", cases);
+        } else if (kind[0] == 'C') {
+            const long rows = integer(), cols = integer();
+            const int ox = (int)integer(), oy = (int)integer(), tx = (int)integer(), ty = (int)integer(), edge = (int)integer(),
+                      preserve = (int)integer();
+            const double divisor = num(), bias = num();
+            const std::vector<double> w = nums((long)ox * oy), src = nums(rows * cols * 4);
+            std::vector<double> out((size_t)(rows * cols * 4));
+            fh_convolve_matrix(src.data(), rows, cols, w.data(), ox, oy, tx, ty, divisor, bias, edge, preserve, out.data());
+            if (preserve)   // (alpha is a copy of the source's: not a clamped value)
+                for (long i = 0; i < rows * cols; ++i) out[(size_t)(4 * i + 3)] = 0.0;
+            check_unit(out, rows * cols * 4, "convolve matrix", cases);
+        } else if (kind[0] == 'L') {
+            const int lk = (int)integer();
+            const std::vector<double> l = nums(8), color = nums(3);
+            const double ss = num(), constant = num(), se = num();
+            const int specular = (int)integer();
+            const long o0 = integer(), o1 = integer(), rows = integer(), cols = integer();
+            const std::vector<double> alpha = nums(rows * cols);
+            std::vector<double> out((size_t)(rows * cols * 4));
+            lh_layer(lk, l.data(), color.data(), ss, constant, se, specular, o0, o1, rows, cols, alpha.data(), out.data());
+            check_unit(out, rows * cols * 4, "lighting", cases);
+        } else {
+            fprintf(stderr, "filter harness: unknown case kind %s\n", kind);
+            return 2;
+        }
+        ++cases;
+    }
+    printf("filter harness: %ld cases, %ld refused\n", cases, refused);
+    return 0;
+}
+#endif

@@ -51,7 +51,9 @@ def light_frame(transform, kind, light):
     if kind == SPOT:
         at = np.array([*transform(np.array([float(light[3]), float(light[4])])), float(light[5]) * s])
         d = at - p[0:3]
-        p[3:6] = d / math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        n = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        if n > 0:   # (a spot that points at its own position has no direction: S = 0, and it lights nothing)
+            p[3:6] = d / n
         p[6] = float(light[6])
         p[7] = -1.0 if light[7] is None else math.cos(math.radians(abs(float(light[7]))))
     return p
@@ -99,8 +101,9 @@ def normals(A, ss):
 def lighting(A, offset, kind, params, color, ss, constant, se=None):
     """The (rows, cols, 4) result over the region at `offset` whose alpha is A; `se` None = diffuse."""
     rows, cols = A.shape
-    n0, n1, n2 = normals(A, ss)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
+        n0, n1, n2 = normals(A, ss)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         if kind == DISTANT:
             l0, l1, l2 = (np.full((rows, cols), params[k]) for k in range(3))
         else:
@@ -125,7 +128,8 @@ def lighting(A, offset, kind, params, color, ss, constant, se=None):
         else:
             nl = n0 * l0 + n1 * l1 + n2 * l2
             k = constant * np.where(nl > 0.0, nl, 0.0)
-    rgb = [np.clip(k * ck, 0.0, 1.0) for ck in c]
+    with np.errstate(invalid="ignore", over="ignore"):   # (NaN -> 0, as svgr_core.h's clamp_unit: a NaN alpha ends as 0)
+        rgb = [np.where(k * ck > 0.0, np.where(k * ck < 1.0, k * ck, 1.0), 0.0) for ck in c]
     alpha = np.maximum(np.maximum(rgb[0], rgb[1]), rgb[2]) if se is not None else np.ones((rows, cols))
     return np.stack([*rgb, alpha], axis=-1)
 
