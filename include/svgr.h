@@ -48,7 +48,8 @@ extern "C" {
  *    svgr_quant_bins, svgr_quant_index, svgr_quant_block and svgr_quant_groups added (indexed PNG output); svgr_quant_dither,
  *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering); svgr_png_samples, svgr_png_filter_bytes and
  *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output); svgr_cover_forward, svgr_cover_backward, svgr_cover_block
- *    and svgr_cover_scan added (differentiable coverage) */
+ *    and svgr_cover_scan added (differentiable coverage); svgr_compose_forward, svgr_compose_backward, svgr_compose_block and
+ *    svgr_compose_groups added (differentiable compositing) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1114,6 +1115,35 @@ int svgr_cover_backward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_b
                         svgr_buf* grad_segs, svgr_buf* grad_m6, svgr_buf* status);
 int svgr_cover_block(void);
 int svgr_cover_scan(void);
+
+/* Differentiable compositing (svgrasterize_amd.diff, beyond the reference; csrc/svgr_compose.h has the arithmetic, DESIGN.md 7x
+ * the derivation): n_paths solid fills painted source-over in paint order over one viewport, and the derivative of
+ * sum(grad_image * image) with respect to every coverage value and every paint.  Every array is a DEVICE buffer:
+ *   cover        n_paths x rows x cols of the plane type (double or float): what svgr_cover_forward writes
+ *   paints       n_paths x 4 doubles: PREMULTIPLIED RGBA in the render's colour space (no conversion is done here)
+ *   image        rows x cols x 4 of the plane type, premultiplied, 16-byte aligned;  grad_image  of image's shape, type and alignment
+ *   grad_cover   of cover's shape and type;  grad_paints  n_paths x 4 doubles
+ * svgr_compose_forward: per pixel C = bg (0 without has_bg), then for p = 0 .. n_paths - 1: s = m_p paint_p, C = s + C (1 - s_3),
+ *   in double, no clamp, no fused multiply-add; a float image is rounded once at the store.
+ * svgr_compose_backward: grad_cover and grad_paints are written whole.  Two walks per pixel and no division (an opaque paint on a
+ *   covered pixel is no special case); grad_paints is summed without atomics, per workgroup and then in workgroup order: the same
+ *   bits on every run.  bg is a constant: it has no gradient.
+ * Both enqueue on the context's stream and never wait; they keep no state.  Before any launch: a count or a side that is not
+ * positive, an unknown plane type, has_bg other than 0 or 1, a missing buffer, one too small for the description or an image that
+ * is not 16-byte aligned give SVGR_E_INVALID; n_paths * rows * cols beyond 2^31 - 1 gives SVGR_E_OVERFLOW.
+ * svgr_compose_block: the pixels of one workgroup step.  svgr_compose_groups: the most workgroups the backward launches (they
+ * stride over the pixels).  Their launch seams. */
+typedef struct {
+    int64_t n_paths, rows, cols;
+    double bg[4];          /* premultiplied; read only with has_bg */
+    int32_t plane;         /* SVGR_COVER_F64 / SVGR_COVER_F32 */
+    int32_t has_bg;        /* 0 / 1 */
+} svgr_compose_desc;
+int svgr_compose_forward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image);
+int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints,
+                          const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints);
+int svgr_compose_block(void);
+int svgr_compose_groups(void);
 
 #ifdef __cplusplus
 }

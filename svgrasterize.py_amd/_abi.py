@@ -100,6 +100,12 @@ class CoverDesc(C.Structure):  # svgr_cover_desc
     ]
 
 
+class ComposeDesc(C.Structure):  # svgr_compose_desc
+    _fields_ = [
+        ("n_paths", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("bg", C.c_double * 4), ("plane", C.c_int32), ("has_bg", C.c_int32),
+    ]
+
+
 TENSOR_SRC_RGBA_F64, TENSOR_SRC_RGBA_F32, TENSOR_SRC_MASK_F64 = 0, 1, 2
 COVER_F64, COVER_F32 = 0, 1
 COVER_STATUS_DEPTH, COVER_STATUS_RANGE = 1, 2
@@ -247,6 +253,10 @@ _PROTOS = {
     "svgr_cover_backward": (C.c_int, [_P, C.POINTER(CoverDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "svgr_cover_block": (C.c_int, []),
     "svgr_cover_scan": (C.c_int, []),
+    "svgr_compose_forward": (C.c_int, [_P, C.POINTER(ComposeDesc), _P, _P, _P]),
+    "svgr_compose_backward": (C.c_int, [_P, C.POINTER(ComposeDesc), _P, _P, _P, _P, _P]),
+    "svgr_compose_block": (C.c_int, []),
+    "svgr_compose_groups": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -11015,3 +11015,209 @@ int svgr_cover_backward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_b
     return abi_guard("svgr_cover_backward", [&]() { return cover_backward_impl(ctx, desc, segs, seg_kind, path_seg_off, path_m6, slope, grad_out, grad_segs, grad_m6, status); });
 }
 }  // extern "C"
+
+// ======================================================================================
+// differentiable compositing: svgr_compose_forward / svgr_compose_backward (csrc/svgr_compose.h has the per-pixel arithmetic,
+// DESIGN.md 7x the derivation).  Solid fills source-over in paint order, from coverage planes and paints to an image and back.
+// New kernels beside the renderer's and the coverage kernels: none of those is involved.
+//   forward   k_compose_over       a lane per pixel: walks the paths bottom up (plane reads coalesced across the lanes, the paints
+//                                  wave-uniform) and stores the four channels as one vector
+//   backward  k_compose_vjp        a lane per pixel, at most COMPOSE_GROUPS workgroups striding over the pixels.  Walk 1 goes from
+//                                  the top path down and leaves T_p in the pixel's grad_cover slot; walk 2 goes from the bottom up,
+//                                  carries the canvas as the forward does, writes d / d m_p over T_p and reduces the four paint
+//                                  terms of every path: shuffles inside a wave (skipped where no lane of the wave is covered), the
+//                                  waves' sums in LDS for COMPOSE_CHUNK paths at a time, added in wave order into the workgroup's
+//                                  own row of partials.  No atomics.
+//             k_compose_paint_sum  a lane per (path, channel): the workgroups' partials added in workgroup order
+// No host read-back between the launches; nothing waits.
+// ======================================================================================
+#include "svgr_compose.h"
+
+constexpr int COMPOSE_BLOCK = 256;                  // pixels per workgroup step: a lane each, four waves
+constexpr int COMPOSE_WAVES = COMPOSE_BLOCK / 64;
+constexpr int COMPOSE_GROUPS = 512;                 // the workgroup cap of k_compose_vjp: two per CU
+constexpr int COMPOSE_CHUNK = COMPOSE_BLOCK / 4;    // paths whose sums sit in LDS between two flushes: a lane per (path, channel)
+
+struct ComposeBg { double c[4]; };
+template <class T> struct ComposePx;
+template <> struct ComposePx<float> { using type = float4; };
+template <> struct ComposePx<double> { using type = double4; };
+
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over(const T* __restrict__ cover, const double* __restrict__ paints, const ComposeBg bg,
+                                                                int n_paths, size_t n_px, T* __restrict__ image) {
+    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
+    if (i >= n_px) return;
+    double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+#pragma unroll 4
+    for (int p = 0; p < n_paths; ++p) compose_step(C, (double)cover[(size_t)p * n_px + i], paints + 4 * (size_t)p);
+    typename ComposePx<T>::type v;
+    v.x = (T)C[0]; v.y = (T)C[1]; v.z = (T)C[2]; v.w = (T)C[3];
+    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+}
+
+// (through and grad_cover are the same memory for double planes: a lane reads its own T_p before it writes d / d m_p there)
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp(const T* __restrict__ cover, const double* __restrict__ paints, const ComposeBg bg,
+                                                               int n_paths, size_t n_px, const T* __restrict__ grad_image, double* through,
+                                                               T* grad_cover, double* __restrict__ part) {
+    __shared__ double sums[COMPOSE_WAVES][COMPOSE_CHUNK][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fq = threadIdx.x >> 2, fk = threadIdx.x & 3;   // the (path of the chunk, channel) this lane flushes
+    double* mine = part + (size_t)blockIdx.x * (size_t)n_paths * 4;
+    SVGR_UNROLL
+    for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][fq][fk] = 0.0;
+    __syncthreads();
+    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const bool live = i < n_px;
+        double gi[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            double above = 1.0;   // T_p: what the paths above p let through
+            for (int p = n_paths - 1; p >= 0; --p) {
+                const size_t at = (size_t)p * n_px + i;
+                through[at] = above;
+                above = above * compose_through((double)cover[at], paints[4 * (size_t)p + 3]);
+            }
+            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
+            gi[0] = (double)v.x; gi[1] = (double)v.y; gi[2] = (double)v.z; gi[3] = (double)v.w;
+        }
+        double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+        for (int p0 = 0; p0 < n_paths; p0 += COMPOSE_CHUNK) {
+            const int p1 = p0 + COMPOSE_CHUNK < n_paths ? p0 + COMPOSE_CHUNK : n_paths;
+            for (int p = p0; p < p1; ++p) {
+                const double* paint = paints + 4 * (size_t)p;
+                double m = 0.0, t[4] = {0.0, 0.0, 0.0, 0.0};
+                if (live) {
+                    const size_t at = (size_t)p * n_px + i;
+                    m = (double)cover[at];
+                    const double dm = compose_vjp_step(C, through[at], gi, m, paint, t);
+                    grad_cover[at] = (T)dm;
+                    compose_step(C, m, paint);
+                }
+                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
+                SVGR_UNROLL
+                for (int k = 0; k < 4; ++k)
+                    for (int d = 32; d > 0; d >>= 1) t[k] = t[k] + __shfl_down(t[k], d);
+                if (lane == 0) {
+                    double* s = sums[wave][p - p0];
+                    s[0] = s[0] + t[0]; s[1] = s[1] + t[1]; s[2] = s[2] + t[2]; s[3] = s[3] + t[3];
+                }
+            }
+            __syncthreads();
+            if (p0 + fq < p1) {
+                double s = sums[0][fq][fk];
+                SVGR_UNROLL
+                for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][fq][fk];
+                double* o = mine + 4 * (size_t)(p0 + fq) + fk;
+                *o = *o + s;
+            }
+            SVGR_UNROLL
+            for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][fq][fk] = 0.0;
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_compose_paint_sum(const double* __restrict__ part, int n_groups, size_t n4, double* __restrict__ grad_paints) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= n4) return;
+    double s = 0.0;
+    for (int g = 0; g < n_groups; ++g) s = s + part[(size_t)g * n4 + j];
+    grad_paints[j] = s;
+}
+
+struct ComposeShape {
+    int n_paths;
+    size_t n_px, n_all, elem;   // pixels of one plane, of all planes, bytes of a plane element
+    ComposeBg bg;
+};
+
+static bool compose_aligned(const svgr_buf* b) { return ((uintptr_t)b->ptr & 15) == 0; }
+
+// Everything of a description and its two input buffers that can be wrong, and the kernels' numbers from it.
+static int compose_check(const char* entry, const svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, ComposeShape& s) {
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
+    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
+    constexpr int64_t kMax = (1ll << 31) - 1;
+    if (d->n_paths <= 0 || d->rows <= 0 || d->cols <= 0)
+        return fail(SVGR_E_INVALID, "%s: %lld planes of %lld x %lld pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
+    if (d->plane < 0 || d->plane >= COVER_PLANES) return fail(SVGR_E_INVALID, "%s: unknown plane type %d", entry, (int)d->plane);
+    if (d->has_bg != 0 && d->has_bg != 1) return fail(SVGR_E_INVALID, "%s: has_bg is 0 or 1, not %d", entry, (int)d->has_bg);
+    if (d->n_paths > kMax || d->rows > kMax || d->cols > kMax ||
+        (unsigned __int128)d->n_paths * (unsigned __int128)d->rows * (unsigned __int128)d->cols > (unsigned __int128)kMax)
+        return fail(SVGR_E_OVERFLOW, "%s: %lld planes of %lld x %lld pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
+    if (!cover || !paints) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    s.n_paths = (int)d->n_paths;
+    s.n_px = (size_t)d->rows * (size_t)d->cols;
+    s.n_all = s.n_px * (size_t)d->n_paths;
+    s.elem = (size_t)cover_plane_bytes(d->plane);
+    if (cover->bytes < s.n_all * s.elem || paints->bytes < (size_t)d->n_paths * 32)
+        return fail(SVGR_E_INVALID, "%s: cover or paints is too small for the description", entry);
+    for (int k = 0; k < 4; ++k) s.bg.c[k] = d->has_bg ? d->bg[k] : 0.0;
+    return 0;
+}
+
+static int compose_forward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image) {
+    static const char* entry = "svgr_compose_forward";
+    ComposeShape s;
+    if (int rc = compose_check(entry, ctx, d, cover, paints, s)) return rc;
+    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (image->bytes < s.n_px * 4 * s.elem || !compose_aligned(image))
+        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const dim3 grid = grid1(s.n_px, COMPOSE_BLOCK);
+    if (d->plane == COVER_F32)
+        SVGR_LAUNCH(k_compose_over<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths, s.n_px, (float*)image->ptr);
+    else
+        SVGR_LAUNCH(k_compose_over<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths, s.n_px, (double*)image->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int compose_backward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* grad_image,
+                                 svgr_buf* grad_cover, svgr_buf* grad_paints) {
+    static const char* entry = "svgr_compose_backward";
+    ComposeShape s;
+    if (int rc = compose_check(entry, ctx, d, cover, paints, s)) return rc;
+    if (!grad_image || !grad_cover || !grad_paints) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (grad_image->bytes < s.n_px * 4 * s.elem || !compose_aligned(grad_image))
+        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
+    if (grad_cover->bytes < s.n_all * s.elem || grad_paints->bytes < (size_t)s.n_paths * 32)
+        return fail(SVGR_E_INVALID, "%s: grad_cover or grad_paints is too small for the description", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t steps = (s.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
+    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
+    const size_t n4 = (size_t)s.n_paths * 4;
+    // (the blocks go back at scope end by the pool's stream-order rule)
+    PoolBlock part, through;   // the workgroups' partial paint sums; float planes: the double T_p plane of walk 1
+    HIPCHK(part.alloc((size_t)groups * n4 * 8, ctx->device));
+    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n4 * 8, st));
+    if (d->plane == COVER_F32) {
+        HIPCHK(through.alloc(s.n_all * 8, ctx->device));
+        SVGR_LAUNCH(k_compose_vjp<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths,
+                    s.n_px, (const float*)grad_image->ptr, through.as<double>(), (float*)grad_cover->ptr, part.as<double>());
+    } else {
+        SVGR_LAUNCH(k_compose_vjp<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths,
+                    s.n_px, (const double*)grad_image->ptr, (double*)grad_cover->ptr, (double*)grad_cover->ptr, part.as<double>());
+    }
+    SVGR_LAUNCH(k_compose_paint_sum, grid1(n4, 64), dim3(64), 0, st, (const double*)part.p, groups, n4, (double*)grad_paints->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+int svgr_compose_block(void) { return COMPOSE_BLOCK; }
+int svgr_compose_groups(void) { return COMPOSE_GROUPS; }
+
+int svgr_compose_forward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image) {
+    return abi_guard("svgr_compose_forward", [&]() { return compose_forward_impl(ctx, desc, cover, paints, image); });
+}
+
+int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* grad_image,
+                          svgr_buf* grad_cover, svgr_buf* grad_paints) {
+    return abi_guard("svgr_compose_backward", [&]() { return compose_backward_impl(ctx, desc, cover, paints, grad_image, grad_cover, grad_paints); });
+}
+}  // extern "C"

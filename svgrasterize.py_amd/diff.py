@@ -11,6 +11,11 @@ cubic is subdivided is not followed across that change.  It is the derivative of
 keeps every outline closed: the copies of a point that neighbouring segments share must move together (sum their entries;
 torch's indexing does).  Where a pixel's accumulated coverage sits on a kink of its fill rule -- the 1e-6 cut, |A| = 1 under
 nonzero, an integer under even-odd -- the derivative is not defined and the slope takes one side.
+
+Differentiable compositing: ``compose`` paints the planes as solid fills source-over in paint order, with the renderer's
+arithmetic; ``compose_backward`` gives ``d loss / d cover`` and ``d loss / d paints``.  ``compose_tensor`` is both as a
+``torch.autograd.Function`` and ``render_tensor`` chains it behind ``coverage_tensor``: geometry and colours to an RGBA image and
+back.  The kernels are svgr_compose_forward / svgr_compose_backward (csrc/svgr_compose.h).
 """
 from __future__ import annotations
 
@@ -316,3 +321,215 @@ def coverage_tensor(segs, m6, *, kinds, path_seg_off, rules, viewport, dtype=Non
                 or out.device != segs.device:
             raise ValueError(f"out is a contiguous {dtype} tensor of shape {(n_paths, vp[2], vp[3])} on {segs.device}")
     return _function(torch).apply(segs, m6, out, *topo, vp, plane, flatness, bool(check))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# compositing: solid fills source-over in paint order, and the way back (svgr_compose_forward / svgr_compose_backward)
+# ------------------------------------------------------------------------------------------------------------------------------
+def compose_block() -> int:
+    """Pixels per workgroup step of the compositing kernels (their launch seam)."""
+    return int(_abi.load_library().svgr_compose_block())
+
+
+def compose_groups() -> int:
+    """The most workgroups the compositing backward launches: they stride over the pixels (its seam)."""
+    return int(_abi.load_library().svgr_compose_groups())
+
+
+def _is_tensor(x):
+    return not isinstance(x, np.ndarray) and hasattr(x, "requires_grad")
+
+
+def _alpha_split(rgba):
+    if not _is_tensor(rgba):
+        rgba = np.asarray(rgba, dtype=np.float64)
+    if rgba.shape[-1:] != (4,):
+        raise ValueError("colours are (..., 4): RGBA")
+    return rgba, (_torch() if _is_tensor(rgba) else np)
+
+
+def premultiply(rgba_straight):
+    """Straight ``(..., 4)`` RGBA to the premultiplied form ``compose`` takes: numpy in, numpy out; torch in, torch out (and
+    differentiable), so a caller can optimise straight colours.  No kernel."""
+    rgba, xp = _alpha_split(rgba_straight)
+    a = rgba[..., 3:]
+    parts = (rgba[..., :3] * a, a)
+    return xp.cat(parts, dim=-1) if xp is not np else np.concatenate(parts, axis=-1)
+
+
+def unpremultiply(rgba_pre):
+    """The inverse of ``premultiply``; where alpha is 0 the colour is 0."""
+    rgba, xp = _alpha_split(rgba_pre)
+    a = rgba[..., 3:]
+    seen = a > 0
+    parts = (xp.where(seen, rgba[..., :3] / xp.where(seen, a, a * 0 + 1), a * 0), a)
+    return xp.cat(parts, dim=-1) if xp is not np else np.concatenate(parts, axis=-1)
+
+
+def _compose_bg(bg):
+    if bg is None:
+        return None
+    try:
+        bg = np.asarray(bg, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("bg is 4 premultiplied doubles") from None
+    if bg.shape != (4,) or not np.isfinite(bg).all():
+        raise ValueError("bg is 4 finite premultiplied doubles")
+    return tuple(float(v) for v in bg)
+
+
+def _compose_desc(n_paths, rows, cols, plane, bg):
+    d = _abi.ComposeDesc()
+    d.n_paths, d.rows, d.cols, d.plane, d.has_bg = n_paths, rows, cols, plane, int(bg is not None)
+    d.bg = (C.c_double * 4)(*(bg if bg is not None else (0.0,) * 4))
+    return d
+
+
+def _compose_inputs(cover, paints, bg, dtype=None):
+    """cover (n_paths, rows, cols) of a plane type and paints (n_paths, 4) float64 on the host, checked."""
+    cover = np.asarray(cover)
+    if dtype is not None:
+        if _np_dtype(dtype) not in _PLANES:
+            raise TypeError(f"a coverage plane is float64 or float32, not {dtype!r}")
+        cover = cover.astype(_np_dtype(dtype), copy=False)
+    if cover.dtype not in _PLANES:
+        raise TypeError(f"cover is float64 or float32, not {cover.dtype}")
+    if cover.ndim != 3 or min(cover.shape) < 1:
+        raise ValueError(f"cover is (n_paths, rows, cols) with every side positive, not {cover.shape}")
+    if isinstance(paints, np.ndarray) and paints.dtype != np.float64:
+        raise TypeError(f"paints is float64, not {paints.dtype}")
+    try:
+        paints = np.ascontiguousarray(paints, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("paints is (n_paths, 4): premultiplied RGBA") from None
+    if paints.ndim != 2 or paints.shape[1] != 4:
+        raise ValueError(f"paints is (n_paths, 4): premultiplied RGBA, not {paints.shape}")
+    if len(paints) != len(cover):
+        raise ValueError(f"{len(cover)} planes and {len(paints)} paints")
+    if not np.isfinite(paints).all():
+        raise ValueError("the paints must be finite")
+    return np.ascontiguousarray(cover), paints, _compose_bg(bg)
+
+
+def compose(cover, paints, bg=None, dtype=None):
+    """The ``(rows, cols, 4)`` premultiplied image of ``n_paths`` solid fills painted source-over in paint order.
+
+    ``cover`` is ``(n_paths, rows, cols)``, float64 or float32: what ``coverage`` returns.  ``paints`` is ``(n_paths, 4)`` float64,
+    PREMULTIPLIED RGBA in the render's colour space, as the renderer's solid fill takes them (``premultiply`` makes them from
+    straight colours); no colour conversion is done.  ``bg``, 4 premultiplied doubles, is what lies under the first path
+    (transparent by default).  ``dtype``, if given, is the plane type ``cover`` is cast to first.  The arithmetic is the
+    renderer's -- ``mask * paint``, then ``src + dst * (1 - src_a)`` -- in double, without a clamp; a float32 image is rounded once.
+    Wrong shapes, dtypes and non-finite paints are refused before any device work."""
+    cover, paints, bg = _compose_inputs(cover, paints, bg, dtype)
+    n_paths, rows, cols = cover.shape
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    d_cover, d_paints = ctx.from_host(cover), ctx.from_host(paints)
+    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
+    desc = _compose_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg)
+    _abi._check(ctx.lib.svgr_compose_forward(ctx.handle, C.byref(desc), d_cover.handle, d_paints.handle, image.handle))
+    return image.download((rows, cols, 4), cover.dtype)
+
+
+def compose_backward(cover, paints, grad_image, bg=None):
+    """``(grad_cover, grad_paints)``: the derivative of ``sum(grad_image * compose(cover, paints, bg))``.
+
+    ``grad_image`` has the image's shape and ``cover``'s type.  ``grad_cover`` has ``cover``'s shape and type, ``grad_paints`` is
+    ``(n_paths, 4)`` float64; ``bg`` is a constant and has no gradient.  No division (an opaque paint on a covered pixel is no
+    special case) and no atomics: the same bits on every run."""
+    cover, paints, bg = _compose_inputs(cover, paints, bg)
+    n_paths, rows, cols = cover.shape
+    grad_image = np.asarray(grad_image)
+    if grad_image.dtype != cover.dtype:
+        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
+    if grad_image.shape != (rows, cols, 4):
+        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    d_cover, d_paints, d_grad = ctx.from_host(cover), ctx.from_host(paints), ctx.from_host(np.ascontiguousarray(grad_image))
+    g_cover, g_paints = ctx.alloc(cover.nbytes), ctx.alloc(n_paths * 32)
+    desc = _compose_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg)
+    _abi._check(ctx.lib.svgr_compose_backward(ctx.handle, C.byref(desc), d_cover.handle, d_paints.handle, d_grad.handle, g_cover.handle, g_paints.handle))
+    return g_cover.download(cover.shape, cover.dtype), g_paints.download((n_paths, 4), np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def _compose_function(torch):
+    class Compose(torch.autograd.Function):
+        """image = Compose.apply(planes, paints, out, bg)."""
+
+        @staticmethod
+        def forward(fn, planes, paints, out, bg):
+            ctx = _context(torch)
+            n_paths, rows, cols = (int(v) for v in planes.shape)
+            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
+            planes_c, paints_c = planes.detach().contiguous(), paints.detach().contiguous()
+            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
+            desc = _compose_desc(n_paths, rows, cols, plane, bg)
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, planes_c, paints_c, image)
+                _abi._check(ctx.lib.svgr_compose_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            fn.save_for_backward(planes_c, paints_c)
+            fn.compose_desc = desc
+            if out is not None:
+                fn.mark_dirty(out)
+            return image
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(fn, grad):
+            planes_c, paints_c = fn.saved_tensors
+            ctx = _context(torch)
+            grad = grad.contiguous()
+            if grad.data_ptr() % 16:
+                grad = grad.clone(memory_format=torch.contiguous_format)
+            grad_planes, grad_paints = torch.empty_like(planes_c), torch.empty_like(paints_c)
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, planes_c, paints_c, grad, grad_planes, grad_paints)
+                _abi._check(ctx.lib.svgr_compose_backward(ctx.handle, C.byref(fn.compose_desc), *[_h(x) for x in b]))
+            need = fn.needs_input_grad
+            return grad_planes if need[0] else None, grad_paints if need[1] else None, None, None
+
+    return Compose
+
+
+def compose_tensor(planes, paints, *, bg=None, out=None):
+    """``compose`` as a ``torch.autograd.Function``: a ``(rows, cols, 4)`` premultiplied image of ``planes``' type that the kernel
+    writes in place, whose backward is ``compose_backward``.
+
+    ``planes`` is an ``(n_paths, rows, cols)`` float32 or float64 CUDA tensor (``coverage_tensor``'s result), ``paints`` an
+    ``(n_paths, 4)`` float64 CUDA tensor of premultiplied colours; either may require grad.  ``bg`` is 4 premultiplied numbers on
+    the host, a constant.  ``out``, if given, receives the image.  The work is ordered behind torch's current stream and torch's
+    stream behind it; nothing waits.  The import-order rule is ``coverage_tensor``'s (``tensor.IMPORT_ORDER``)."""
+    torch = _torch()
+    for name, t, kinds in (("planes", planes, (torch.float32, torch.float64)), ("paints", paints, (torch.float64,))):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in kinds or not t.is_cuda:
+            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
+    if planes.dim() != 3 or min(planes.shape) < 1:
+        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    if paints.dim() != 2 or paints.shape[1] != 4 or paints.shape[0] != planes.shape[0]:
+        raise ValueError(f"paints is ({planes.shape[0]}, 4): one premultiplied RGBA per plane, not {tuple(paints.shape)}")
+    n_paths, rows, cols = (int(v) for v in planes.shape)
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    bg = _compose_bg(bg)
+    ctx = _context(torch)
+    if planes.device.index != ctx.device or paints.device != planes.device:
+        raise ValueError(f"planes and paints are on {planes.device} and {paints.device}, the library's context on device {ctx.device}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
+                or out.device != planes.device or out.data_ptr() % 16:
+            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
+    return _compose_function(torch).apply(planes, paints, out, bg)
+
+
+def render_tensor(segs, m6, paints, *, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False, flatness: float = FLATNESS):
+    """Geometry and colours to a ``(rows, cols, 4)`` premultiplied image and back: ``coverage_tensor`` followed by
+    ``compose_tensor``, with gradients to ``segs``, ``m6`` and ``paints``.
+
+    Path ``p`` is filled with ``paints[p]`` and painted over the paths before it.  The arguments are ``coverage_tensor``'s and
+    ``compose_tensor``'s; ``dtype`` (torch.float32 by default) is the type of the planes and of the image.  Solid fills only: no
+    gradients or patterns, clips, groups or strokes."""
+    planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=viewport, dtype=dtype, check=check, flatness=flatness)
+    return compose_tensor(planes, paints, bg=bg)
