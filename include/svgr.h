@@ -49,7 +49,8 @@ extern "C" {
  *    svgr_dither_tile_rows and svgr_dither_tile_cols added (dithering); svgr_png_samples, svgr_png_filter_bytes and
  *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output); svgr_cover_forward, svgr_cover_backward, svgr_cover_block
  *    and svgr_cover_scan added (differentiable coverage); svgr_compose_forward, svgr_compose_backward, svgr_compose_block and
- *    svgr_compose_groups added (differentiable compositing) */
+ *    svgr_compose_groups added (differentiable compositing); svgr_compose_painted_forward and svgr_compose_painted_backward
+ *    added (gradient paints in differentiable compositing) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1144,6 +1145,47 @@ int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const sv
                           const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints);
 int svgr_compose_block(void);
 int svgr_compose_groups(void);
+
+/* Gradient paints in differentiable compositing (csrc/svgr_gradpaint.h has the arithmetic, DESIGN.md 7y the derivation): as above,
+ * but path p is a solid fill (kind 0) or the renderer's linear (1) or one-circle radial (2) gradient, evaluated at the centre of
+ * every pixel and multiplied by the coverage and by paints[p].  The description also holds HOST pointers to the topology, which is
+ * validated and copied before the entry returns (the caller may free it then):
+ *   kind[n_paths]            0 solid, 1 linear, 2 radial        spread[n_paths]   0 pad, 1 repeat, 2 reflect (ignored for a solid)
+ *   path_stop_off[n_paths+1] path p owns the stops path_stop_off[p] : path_stop_off[p + 1]; from 0 to n_stops, never decreasing;
+ *                            a solid path owns none, a gradient path 1 to 32
+ * DEVICE buffers, all doubles but the planes and images (which are svgr_compose_forward's):
+ *   paints      n_paths x 4   a solid path's premultiplied colour; a gradient path's component-wise multiplier (ones, or an opacity)
+ *   paint_m6    n_paths x 6   pixel centre (row + row0 + 0.5, col + col0 + 0.5) -> gradient space: the inverse render transform
+ *                             followed by the inverse gradientTransform, composed by the caller (unused for a solid)
+ *   paint_geom  n_paths x 4   linear: p0x, p0y, p1x, p1y; radial: cx, cy, r and an unused slot
+ *   stop_pos    n_stops       non-decreasing per path;   stop_rgba  n_stops x 4  premultiplied, in the render's colour space
+ * svgr_compose_painted_forward: s = (colour m_p) paint_p per channel, C = s + C (1 - s_3); a solid path as svgr_compose_forward.
+ * svgr_compose_painted_backward: grad_cover (cover's shape and type), grad_paints, grad_m6, grad_geom, grad_stop_pos and
+ *   grad_stop_rgba (their inputs' shapes) are written whole; the rows of solid paths in grad_m6 and grad_geom and the unused radial
+ *   slot are 0.  Where a derivative is not defined (an offset on a stop, a clamp, a wrap or a fold; the radial centre) one
+ *   documented side is taken and nothing is NaN for finite input.  No atomics: the same bits on every run.  Degenerate geometry
+ *   (p0 == p1, r <= 0) is not looked at here: it gives NaN or infinities.
+ * Both enqueue on the context's stream and never wait; they keep no state.  Before any launch: everything svgr_compose_forward
+ * refuses, an unknown kind or spread, a stop table that does not go from 0 to n_stops or decreases, a gradient path without a
+ * stop or with more than 32, a solid path with stops and a missing or too small buffer give SVGR_E_INVALID;
+ * n_paths * rows * cols beyond 2^31 - 1 gives SVGR_E_OVERFLOW.  With n_stops == 0 the four stop buffers may be NULL. */
+typedef struct {
+    int64_t n_paths, rows, cols;
+    double bg[4];          /* premultiplied; read only with has_bg */
+    int32_t plane;         /* SVGR_COVER_F64 / SVGR_COVER_F32 */
+    int32_t has_bg;        /* 0 / 1 */
+    int64_t row0, col0;    /* the viewport's origin */
+    int64_t n_stops;
+    const int32_t* kind;
+    const int32_t* spread;
+    const int32_t* path_stop_off;
+} svgr_painted_desc;
+int svgr_compose_painted_forward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image);
+int svgr_compose_painted_backward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
+                                  svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
+                                  svgr_buf* grad_stop_rgba);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,14 @@ class ComposeDesc(C.Structure):  # svgr_compose_desc
     ]
 
 
+class PaintedDesc(C.Structure):  # svgr_painted_desc
+    _fields_ = [
+        ("n_paths", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("bg", C.c_double * 4), ("plane", C.c_int32), ("has_bg", C.c_int32),
+        ("row0", C.c_int64), ("col0", C.c_int64), ("n_stops", C.c_int64), ("kind", C.POINTER(C.c_int32)), ("spread", C.POINTER(C.c_int32)),
+        ("path_stop_off", C.POINTER(C.c_int32)),
+    ]
+
+
 TENSOR_SRC_RGBA_F64, TENSOR_SRC_RGBA_F32, TENSOR_SRC_MASK_F64 = 0, 1, 2
 COVER_F64, COVER_F32 = 0, 1
 COVER_STATUS_DEPTH, COVER_STATUS_RANGE = 1, 2
@@ -257,6 +265,8 @@ _PROTOS = {
     "svgr_compose_backward": (C.c_int, [_P, C.POINTER(ComposeDesc), _P, _P, _P, _P, _P]),
     "svgr_compose_block": (C.c_int, []),
     "svgr_compose_groups": (C.c_int, []),
+    "svgr_compose_painted_forward": (C.c_int, [_P, C.POINTER(PaintedDesc)] + [_P] * 7),
+    "svgr_compose_painted_backward": (C.c_int, [_P, C.POINTER(PaintedDesc)] + [_P] * 13),
 }
 EXPORTS = tuple(_PROTOS)
 

@@ -11221,3 +11221,379 @@ int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const sv
     return abi_guard("svgr_compose_backward", [&]() { return compose_backward_impl(ctx, desc, cover, paints, grad_image, grad_cover, grad_paints); });
 }
 }  // extern "C"
+
+// ======================================================================================
+// gradient paints in differentiable compositing: svgr_compose_painted_forward / svgr_compose_painted_backward
+// (csrc/svgr_gradpaint.h has the per-pixel arithmetic, DESIGN.md 7y the derivation).  A path is a solid fill (kind 0, compose_step
+// as above) or the renderer's linear / one-circle radial gradient evaluated at the pixel centre.  New kernels beside the ones
+// above: those, grad_colour_user and every renderer kernel are not involved.
+//   topology  k_painted_topology     the caller's host tables go up as kernel ARGUMENTS, PAINTED_TOPO paths a launch, into one
+//                                    int4 {kind, spread, first stop, end stop} per path: no copy from memory the caller may free
+//                                    on return, and no wait
+//   forward   k_compose_over_painted a lane per pixel; the path's description, its transform, geometry and stops are wave-uniform:
+//                                    read through uniform addresses of restrict pointers (scalar loads)
+//   backward  k_compose_vjp_painted  the two walks of k_compose_vjp.  Walk 2 reduces, per path, 14 dense terms (4 paint, 6 m6,
+//                                    4 geometry) by the fixed shuffle tree, and 5 terms (position, colour) for every stop whose
+//                                    ballot over the wave is not empty.  The waves' sums sit in LDS for a run of paths whose
+//                                    parameters fit PAINTED_SLOTS, and are added in wave order, at barriers, into the workgroup's
+//                                    own row of the groups x n_params partials, n_params = 14 n_paths + 5 n_stops.  No atomics.
+//             k_compose_param_sum    a lane per parameter: the workgroups' partials added in workgroup order, stored to the five
+//                                    gradient arrays
+// ======================================================================================
+#include "svgr_gradpaint.h"
+
+constexpr int PAINTED_TOPO = 384;     // paths per k_painted_topology launch: 3 ints each, within the 4 KiB of kernel arguments
+constexpr int PAINTED_SLOTS = 1024;   // parameters of one run of paths in LDS, per wave (a path has at most 14 + 5 * 32 = 174)
+static_assert(GRADPAINT_DENSE + GRADPAINT_STOP * GRADPAINT_MAX_STOPS <= PAINTED_SLOTS, "a path's parameters fit one run");
+static_assert(GRADPAINT_MAX_STOPS == GRAD_MAX_STOPS, "one cap");
+
+struct PaintedTopo {
+    int first, n;
+    int kind_spread[PAINTED_TOPO];     // kind | spread << 8
+    int stop_off[PAINTED_TOPO + 1];
+};
+struct PaintedView { long long row0, col0; unsigned cols; };
+
+__global__ __launch_bounds__(64) void k_painted_topology(const PaintedTopo t, int4* __restrict__ desc) {
+    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (q >= t.n) return;
+    desc[t.first + q] = make_int4(t.kind_spread[q] & 255, t.kind_spread[q] >> 8, t.stop_off[q], t.stop_off[q + 1]);
+}
+
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_painted(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                        const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                        const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                        const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
+                                                                        int n_paths, size_t n_px, T* __restrict__ image) {
+    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
+    if (i >= n_px) return;
+    const unsigned row = (unsigned)i / vw.cols, colj = (unsigned)i - row * vw.cols;   // (n_px < 2^31)
+    double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+    for (int p = 0; p < n_paths; ++p) {
+        const int4 d = desc[p];
+        const double m = (double)cover[(size_t)p * n_px + i];
+        if (d.x == 0) {
+            compose_step(C, m, paints + 4 * (size_t)p);
+        } else {
+            double col[4];
+            GradPaintPx e;
+            gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0,
+                             vw.col0, col, e);
+            gradpaint_step(C, m, col, paints + 4 * (size_t)p);
+        }
+    }
+    typename ComposePx<T>::type v;
+    v.x = (T)C[0]; v.y = (T)C[1]; v.z = (T)C[2]; v.w = (T)C[3];
+    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+}
+
+// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_painted(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                       const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
+                                                                       int n_paths, int n_stops, size_t n_px, const T* __restrict__ grad_image,
+                                                                       double* through, T* grad_cover, double* __restrict__ part) {
+    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
+    double* mine = part + (size_t)blockIdx.x * (n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops);
+    for (int j = threadIdx.x; j < PAINTED_SLOTS; j += COMPOSE_BLOCK) {
+        SVGR_UNROLL
+        for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
+    }
+    __syncthreads();
+    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const bool live = i < n_px;
+        const unsigned row = live ? (unsigned)i / vw.cols : 0u, colj = live ? (unsigned)i - row * vw.cols : 0u;
+        double gi[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            double above = 1.0;   // T_p: what the paths above p let through
+            for (int p = n_paths - 1; p >= 0; --p) {
+                const int4 d = desc[p];
+                const size_t at = (size_t)p * n_px + i;
+                const double m = (double)cover[at];
+                double u;
+                if (d.x == 0) {
+                    u = compose_through(m, paints[4 * (size_t)p + 3]);
+                } else {
+                    double col[4];
+                    GradPaintPx e;
+                    gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj,
+                                     vw.row0, vw.col0, col, e);
+                    u = gradpaint_through(m, col, paints + 4 * (size_t)p);
+                }
+                through[at] = above;
+                above = above * u;
+            }
+            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
+            gi[0] = (double)v.x; gi[1] = (double)v.y; gi[2] = (double)v.z; gi[3] = (double)v.w;
+        }
+        double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+        int p0 = 0;
+        while (p0 < n_paths) {
+            // the run of paths p0 .. p1 - 1 whose parameters fit the LDS rows: dense terms first, then the stops' (both contiguous)
+            const int s_first = desc[p0].z;
+            int p1 = p0, used = 0;
+            while (p1 < n_paths) {
+                const int4 d = desc[p1];
+                const int need = GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
+                if (used + need > PAINTED_SLOTS) break;
+                used += need;
+                ++p1;
+            }
+            const int nd = GRADPAINT_DENSE * (p1 - p0);
+            for (int p = p0; p < p1; ++p) {
+                const int4 d = desc[p];
+                const double* paint = paints + 4 * (size_t)p;
+                double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
+                int used_lo = -1, used_hi = -1;
+                if (live) {
+                    const size_t at = (size_t)p * n_px + i;
+                    m = (double)cover[at];
+                    if (d.x == 0) {
+                        const double dm = compose_vjp_step(C, through[at], gi, m, paint, dense);
+                        grad_cover[at] = (T)dm;
+                        compose_step(C, m, paint);
+                    } else {
+                        double col[4], P[4], t[4];
+                        GradPaintPx e;
+                        const double* g4 = geoms + 4 * (size_t)p;
+                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, g4, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0, vw.col0,
+                                         col, e);
+                        gradpaint_effective(col, paint, P);
+                        const double dm = compose_vjp_step(C, through[at], gi, m, P, t);
+                        grad_cover[at] = (T)dm;
+                        gradpaint_vjp(d.x, g4, pos + d.z, rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
+                        gradpaint_step(C, m, col, paint);
+                        used_lo = e.lo;
+                        used_hi = e.hi;
+                    }
+                }
+                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
+                double* rowd = &sums[wave][GRADPAINT_DENSE * (p - p0)];
+                if (d.x == 0) {
+                    SVGR_UNROLL
+                    for (int k = 0; k < 4; ++k)
+                        for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
+                    if (lane == 0) {
+                        SVGR_UNROLL
+                        for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
+                    }
+                    continue;
+                }
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_DENSE; ++k)
+                    for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
+                if (lane == 0) {
+                    SVGR_UNROLL
+                    for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
+                }
+                const int ns = d.w - d.z;
+                for (int s = 0; s < ns; ++s) {
+                    const bool at_lo = used_lo == s, at_hi = used_hi == s;
+                    if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
+                    double v[GRADPAINT_STOP];
+                    SVGR_UNROLL
+                    for (int k = 0; k < GRADPAINT_STOP; ++k) {
+                        v[k] = at_lo ? lo[k] : (at_hi ? hi[k] : 0.0);
+                        for (int q = 32; q > 0; q >>= 1) v[k] = v[k] + __shfl_down(v[k], q);
+                    }
+                    if (lane == 0) {
+                        double* rows = &sums[wave][nd + GRADPAINT_STOP * (d.z - s_first + s)];
+                        SVGR_UNROLL
+                        for (int k = 0; k < GRADPAINT_STOP; ++k) rows[k] = rows[k] + v[k];
+                    }
+                }
+            }
+            __syncthreads();
+            for (int j = threadIdx.x; j < used; j += COMPOSE_BLOCK) {
+                double s = sums[0][j];
+                SVGR_UNROLL
+                for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][j];
+                double* o = mine + (j < nd ? (size_t)GRADPAINT_DENSE * (size_t)p0 + (size_t)j
+                                           : n_dense + (size_t)GRADPAINT_STOP * (size_t)s_first + (size_t)(j - nd));
+                *o = *o + s;
+                SVGR_UNROLL
+                for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
+            }
+            __syncthreads();
+            p0 = p1;
+        }
+    }
+}
+
+// a lane per parameter: the partials in workgroup order, to the array the parameter belongs to
+__global__ __launch_bounds__(64) void k_compose_param_sum(const double* __restrict__ part, int n_groups, size_t n_dense, size_t n_params,
+                                                          double* __restrict__ g_paints, double* __restrict__ g_m6, double* __restrict__ g_geom,
+                                                          double* __restrict__ g_pos, double* __restrict__ g_rgba) {
+    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= n_params) return;
+    double s = 0.0;
+    for (int g = 0; g < n_groups; ++g) s = s + part[(size_t)g * n_params + j];
+    if (j < n_dense) {
+        const size_t p = j / GRADPAINT_DENSE;
+        const int k = (int)(j - p * GRADPAINT_DENSE);
+        if (k < 4) g_paints[4 * p + k] = s;
+        else if (k < 10) g_m6[6 * p + (k - 4)] = s;
+        else g_geom[4 * p + (k - 10)] = s;
+    } else {
+        const size_t q = (j - n_dense) / GRADPAINT_STOP;
+        const int k = (int)((j - n_dense) - q * GRADPAINT_STOP);
+        if (k == 0) g_pos[q] = s;
+        else g_rgba[4 * q + (k - 1)] = s;
+    }
+}
+
+struct PaintedShape {
+    ComposeShape c;
+    int n_stops;
+    PaintedView vw;
+};
+
+static bool painted_has(const svgr_buf* b, size_t bytes) { return b && b->bytes >= bytes && (b->ptr || bytes == 0); }
+
+// Everything of a painted description, its topology and its input buffers that can be wrong.
+static int painted_check(const char* entry, const svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints,
+                         const svgr_buf* m6, const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, PaintedShape& s) {
+    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
+    svgr_compose_desc cd;
+    cd.n_paths = d->n_paths; cd.rows = d->rows; cd.cols = d->cols; cd.plane = d->plane; cd.has_bg = d->has_bg;
+    for (int k = 0; k < 4; ++k) cd.bg[k] = d->bg[k];
+    if (int rc = compose_check(entry, ctx, &cd, cover, paints, s.c)) return rc;
+    const int64_t n = d->n_paths;
+    if (!d->kind || !d->spread || !d->path_stop_off) return fail(SVGR_E_INVALID, "%s: a topology table is NULL", entry);
+    if (d->n_stops < 0 || d->n_stops > n * GRADPAINT_MAX_STOPS) return fail(SVGR_E_INVALID, "%s: %lld stops for %lld paths", entry, (long long)d->n_stops, (long long)n);
+    if (d->path_stop_off[0] != 0 || (int64_t)d->path_stop_off[n] != d->n_stops)
+        return fail(SVGR_E_INVALID, "%s: path_stop_off goes from %d to %d, not from 0 to %lld", entry, (int)d->path_stop_off[0], (int)d->path_stop_off[n], (long long)d->n_stops);
+    for (int64_t p = 0; p < n; ++p) {
+        const int32_t kind = d->kind[p], spread = d->spread[p];
+        const int64_t ns = (int64_t)d->path_stop_off[p + 1] - (int64_t)d->path_stop_off[p];
+        if (kind < 0 || kind > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown kind %d (0 solid, 1 linear, 2 radial)", entry, (long long)p, (int)kind);
+        if (spread < 0 || spread > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown spread %d", entry, (long long)p, (int)spread);
+        if (ns < 0) return fail(SVGR_E_INVALID, "%s: path_stop_off decreases at path %lld", entry, (long long)p);
+        if (kind == 0 && ns != 0) return fail(SVGR_E_INVALID, "%s: the solid path %lld has %lld stops", entry, (long long)p, (long long)ns);
+        if (kind != 0 && (ns < 1 || ns > GRADPAINT_MAX_STOPS))
+            return fail(SVGR_E_INVALID, "%s: the gradient path %lld has %lld stops: 1 to %d", entry, (long long)p, (long long)ns, GRADPAINT_MAX_STOPS);
+    }
+    const size_t np = (size_t)n, nst = (size_t)d->n_stops;
+    if (!painted_has(m6, np * 48) || !painted_has(geom, np * 32) || !m6->ptr || !geom->ptr)
+        return fail(SVGR_E_INVALID, "%s: paint_m6 or paint_geom is missing or too small for the description", entry);
+    if (nst && (!painted_has(stop_pos, nst * 8) || !painted_has(stop_rgba, nst * 32)))
+        return fail(SVGR_E_INVALID, "%s: stop_pos or stop_rgba is missing or too small for the description", entry);
+    s.n_stops = (int)d->n_stops;
+    s.vw.row0 = (long long)d->row0;
+    s.vw.col0 = (long long)d->col0;
+    s.vw.cols = (unsigned)d->cols;
+    return 0;
+}
+
+// the topology tables into the device block, by kernel arguments
+static int painted_topology(const svgr_painted_desc* d, int n_paths, int4* desc, hipStream_t st) {
+    PaintedTopo t;
+    for (int first = 0; first < n_paths; first += PAINTED_TOPO) {
+        t.first = first;
+        t.n = std::min(PAINTED_TOPO, n_paths - first);
+        for (int q = 0; q < t.n; ++q) {
+            t.kind_spread[q] = (int)d->kind[first + q] | ((int)d->spread[first + q] << 8);
+            t.stop_off[q] = (int)d->path_stop_off[first + q];
+        }
+        t.stop_off[t.n] = (int)d->path_stop_off[first + t.n];
+        for (int q = t.n; q < PAINTED_TOPO; ++q) { t.kind_spread[q] = 0; t.stop_off[q + 1] = 0; }
+        SVGR_LAUNCH(k_painted_topology, grid1((size_t)t.n, 64), dim3(64), 0, st, t, desc);
+    }
+    return 0;
+}
+
+static const double* painted_ptr(const svgr_buf* b) { return b ? (const double*)b->ptr : nullptr; }
+
+static int painted_forward_impl(svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
+                                const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image) {
+    static const char* entry = "svgr_compose_painted_forward";
+    PaintedShape s;
+    if (int rc = painted_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, s)) return rc;
+    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (image->bytes < s.c.n_px * 4 * s.c.elem || !compose_aligned(image))
+        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    PoolBlock topo;   // (goes back at scope end by the pool's stream-order rule)
+    HIPCHK(topo.alloc((size_t)s.c.n_paths * sizeof(int4), ctx->device));
+    if (int rc = painted_topology(d, s.c.n_paths, topo.as<int4>(), st)) return rc;
+    const dim3 grid = grid1(s.c.n_px, COMPOSE_BLOCK);
+    if (d->plane == COVER_F32)
+        SVGR_LAUNCH(k_compose_over_painted<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
+                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.c.n_px, (float*)image->ptr);
+    else
+        SVGR_LAUNCH(k_compose_over_painted<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
+                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.c.n_px, (double*)image->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int painted_backward_impl(svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
+                                 const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
+                                 svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
+                                 svgr_buf* grad_stop_rgba) {
+    static const char* entry = "svgr_compose_painted_backward";
+    PaintedShape s;
+    if (int rc = painted_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, s)) return rc;
+    if (!grad_image || !grad_cover || !grad_paints || !grad_m6 || !grad_geom) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (grad_image->bytes < s.c.n_px * 4 * s.c.elem || !compose_aligned(grad_image))
+        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
+    const size_t np = (size_t)s.c.n_paths, nst = (size_t)s.n_stops;
+    if (grad_cover->bytes < s.c.n_all * s.c.elem || grad_paints->bytes < np * 32 || grad_m6->bytes < np * 48 || grad_geom->bytes < np * 32)
+        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is too small for the description", entry);
+    if (nst && (!painted_has(grad_stop_pos, nst * 8) || !painted_has(grad_stop_rgba, nst * 32)))
+        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t steps = (s.c.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
+    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
+    const size_t n_dense = np * GRADPAINT_DENSE, n_params = n_dense + nst * GRADPAINT_STOP;
+    // (the blocks go back at scope end by the pool's stream-order rule)
+    PoolBlock topo, part, through;   // the paths' descriptions; the workgroups' partial sums; float planes: the double T_p plane of walk 1
+    HIPCHK(topo.alloc(np * sizeof(int4), ctx->device));
+    HIPCHK(part.alloc((size_t)groups * n_params * 8, ctx->device));
+    if (d->plane == COVER_F32) HIPCHK(through.alloc(s.c.n_all * 8, ctx->device));
+    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n_params * 8, st));
+    if (int rc = painted_topology(d, s.c.n_paths, topo.as<int4>(), st)) return rc;
+    if (d->plane == COVER_F32) {
+        SVGR_LAUNCH(k_compose_vjp_painted<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr,
+                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.n_stops,
+                    s.c.n_px, (const float*)grad_image->ptr, through.as<double>(), (float*)grad_cover->ptr, part.as<double>());
+    } else {
+        SVGR_LAUNCH(k_compose_vjp_painted<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr,
+                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.n_stops,
+                    s.c.n_px, (const double*)grad_image->ptr, (double*)grad_cover->ptr, (double*)grad_cover->ptr, part.as<double>());
+    }
+    SVGR_LAUNCH(k_compose_param_sum, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_params, (double*)grad_paints->ptr,
+                (double*)grad_m6->ptr, (double*)grad_geom->ptr, nst ? (double*)grad_stop_pos->ptr : nullptr, nst ? (double*)grad_stop_rgba->ptr : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+int svgr_compose_painted_forward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image) {
+    return abi_guard("svgr_compose_painted_forward",
+                     [&]() { return painted_forward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, image); });
+}
+
+int svgr_compose_painted_backward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
+                                  svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
+                                  svgr_buf* grad_stop_rgba) {
+    return abi_guard("svgr_compose_painted_backward", [&]() {
+        return painted_backward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, grad_image, grad_cover, grad_paints, grad_m6,
+                                     grad_geom, grad_stop_pos, grad_stop_rgba);
+    });
+}
+}  // extern "C"

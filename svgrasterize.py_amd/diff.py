@@ -16,11 +16,18 @@ Differentiable compositing: ``compose`` paints the planes as solid fills source-
 arithmetic; ``compose_backward`` gives ``d loss / d cover`` and ``d loss / d paints``.  ``compose_tensor`` is both as a
 ``torch.autograd.Function`` and ``render_tensor`` chains it behind ``coverage_tensor``: geometry and colours to an RGBA image and
 back.  The kernels are svgr_compose_forward / svgr_compose_backward (csrc/svgr_compose.h).
+
+Gradient paints: ``compose_painted`` / ``compose_painted_backward`` are ``compose`` and its backward with every path a solid fill or
+the renderer's linear or one-circle radial gradient (``GradientPaints``, built by ``gradient_paints``), with derivatives to the
+gradients' transforms, end points, centre and radius, stop positions and stop colours.  ``compose_painted_tensor`` and
+``render_painted_tensor`` are the torch forms.  The kernels are svgr_compose_painted_forward / svgr_compose_painted_backward
+(csrc/svgr_gradpaint.h).
 """
 from __future__ import annotations
 
 import ctypes as C
 import functools
+from typing import NamedTuple
 
 import numpy as np
 
@@ -533,3 +540,314 @@ def render_tensor(segs, m6, paints, *, kinds, path_seg_off, rules, viewport, bg=
     gradients or patterns, clips, groups or strokes."""
     planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=viewport, dtype=dtype, check=check, flatness=flatness)
     return compose_tensor(planes, paints, bg=bg)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# gradient paints: linear and one-circle radial fills in the compositor (svgr_compose_painted_forward / _backward,
+# csrc/svgr_gradpaint.h, DESIGN.md 7y)
+# ------------------------------------------------------------------------------------------------------------------------------
+MAX_STOPS = 32
+KIND_SOLID, KIND_LINEAR, KIND_RADIAL = 0, 1, 2
+
+
+class GradientPaints(NamedTuple):
+    """What paints every path of a painted composition besides its ``paints`` row.  The topology -- ``kind`` (0 solid, 1 linear,
+    2 radial), ``spread`` (0 pad, 1 repeat, 2 reflect) and ``path_stop_off`` (path ``p`` owns the stops
+    ``path_stop_off[p] : path_stop_off[p + 1]``; a solid path owns none, a gradient path 1 to 32) -- stays on the host.  ``m6``
+    ``(n_paths, 6)`` takes a pixel centre to gradient space, ``geom`` ``(n_paths, 4)`` is ``p0x, p0y, p1x, p1y`` of a linear and
+    ``cx, cy, r, -`` of a radial gradient, ``stop_pos`` ``(n_stops,)`` and ``stop_rgba`` ``(n_stops, 4)`` are the stops, premultiplied
+    and in the render's colour space.  ``compose_painted_backward`` returns the derivatives in the same shape."""
+
+    kind: object
+    spread: object
+    path_stop_off: object
+    m6: object
+    geom: object
+    stop_pos: object
+    stop_rgba: object
+
+
+def gradient_paints(paints, transform=None, linear_rgb: bool = False):
+    """``(GradientPaints, paint_rows)`` of a list of ``paint.GradLinear``, ``paint.GradRadial`` or 4-number solid colours drawn
+    under the render transform ``transform`` (identity by default).
+
+    ``m6`` is the inverse render transform followed by the gradient's inverse ``gradientTransform``, composed into one matrix;
+    the stops go through the renderer's colour-space step for ``linear_rgb`` (a gradient's own ``linear_rgb`` wins, as in
+    ``Path.fill``).  ``paint_rows`` is ``(n_paths, 4)``: the colour of a solid path as given (premultiplied, in the render's colour
+    space: what ``compose`` takes), ones for a gradient path.  A focal radial gradient, ``bbox_units=True``, an unknown spread, no
+    stop or more than 32 stops is a ``ValueError``.  Host only: no device work."""
+    from .geometry import Transform  # noqa: PLC0415
+    from .paint import _SPREAD, GradLinear, GradRadial, _stops_colorspace  # noqa: PLC0415
+
+    user = (transform if transform is not None else Transform()).invert
+    kind, spread, off, m6, geom, pos, rgba, rows = [], [], [0], [], [], [], [], []
+    for p, paint in enumerate(paints):
+        if not isinstance(paint, (GradLinear, GradRadial)):
+            try:
+                colour = np.asarray(paint, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                colour = np.zeros(0)
+            if colour.shape != (4,):
+                raise ValueError(f"paint {p} is a GradLinear, a GradRadial or 4 numbers")
+            kind.append(KIND_SOLID), spread.append(0), off.append(off[-1]), m6.append(Transform().m6()), geom.append((0.0,) * 4), rows.append(colour)
+            continue
+        if paint.bbox_units:
+            raise ValueError(f"paint {p}: objectBoundingBox units are not supported")
+        if paint.spread not in _SPREAD:
+            raise ValueError(f"paint {p}: invalid spread method: {paint.spread}")
+        if isinstance(paint, GradRadial):
+            if paint.fcenter is not None or paint.fradius is not None:
+                raise ValueError(f"paint {p}: focal radial gradients are not supported")
+            c = np.asarray(paint.center, dtype=np.float64).reshape(2)
+            kind.append(KIND_RADIAL), geom.append((c[0], c[1], float(paint.radius), 0.0))
+        else:
+            p0, p1 = np.asarray(paint.p0, dtype=np.float64).reshape(2), np.asarray(paint.p1, dtype=np.float64).reshape(2)
+            kind.append(KIND_LINEAR), geom.append((p0[0], p0[1], p1[0], p1[1]))
+        stops = _stops_colorspace(paint.stops, linear_rgb if paint.linear_rgb is None else paint.linear_rgb)
+        if not 1 <= len(stops) <= MAX_STOPS:
+            raise ValueError(f"paint {p} has {len(stops)} stops: 1 to {MAX_STOPS}")
+        tr = user if paint.transform is None else paint.transform.invert @ user
+        spread.append(_SPREAD[paint.spread]), m6.append(tr.m6()), rows.append(np.ones(4))
+        pos += [o for o, _ in stops]
+        rgba += [np.asarray(c, dtype=np.float64).reshape(4) for _, c in stops]
+        off.append(len(pos))
+    if not kind:
+        raise ValueError("no paints")
+    gp = GradientPaints(np.array(kind, dtype=np.int32), np.array(spread, dtype=np.int32), np.array(off, dtype=np.int32),
+                        np.array(m6, dtype=np.float64).reshape(-1, 6), np.array(geom, dtype=np.float64).reshape(-1, 4), np.array(pos, dtype=np.float64),
+                        np.array(rgba, dtype=np.float64).reshape(-1, 4))
+    return gp, np.array(rows, dtype=np.float64).reshape(-1, 4)
+
+
+def _painted_topology(gp, n_paths, n_stops):
+    """kind, spread and path_stop_off on the host, checked as svgr_compose_painted_forward checks them: three int32 arrays."""
+    if not isinstance(gp, tuple) or len(gp) != 7:
+        raise TypeError("gp is a GradientPaints")
+    out = []
+    for name, a, n in (("kind", gp.kind, n_paths), ("spread", gp.spread, n_paths), ("path_stop_off", gp.path_stop_off, n_paths + 1)):
+        if _is_tensor(a):
+            raise TypeError(f"gp.{name} stays on the host: a numpy array or a list")
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"gp.{name} holds integers, not {a.dtype}")
+        if a.shape != (n,):
+            raise ValueError(f"gp.{name} has {n} entries, not {a.shape}")
+        out.append(np.ascontiguousarray(a.astype(np.int64)))
+    kind, spread, off = out
+    if not np.isin(kind, (KIND_SOLID, KIND_LINEAR, KIND_RADIAL)).all():
+        raise ValueError("gp.kind holds 0 (solid), 1 (linear) or 2 (radial) per path")
+    if not np.isin(spread, (0, 1, 2)).all():
+        raise ValueError("gp.spread holds 0 (pad), 1 (repeat) or 2 (reflect) per path")
+    count = np.diff(off)
+    if off[0] != 0 or off[-1] != n_stops or (count < 0).any():
+        raise ValueError(f"gp.path_stop_off is n_paths + 1 ascending integers from 0 to the number of stops ({n_stops})")
+    if (count[kind == KIND_SOLID] != 0).any():
+        raise ValueError("a solid path owns no stops")
+    if ((count[kind != KIND_SOLID] < 1) | (count[kind != KIND_SOLID] > MAX_STOPS)).any():
+        raise ValueError(f"a gradient path owns 1 to {MAX_STOPS} stops")
+    return kind.astype(np.int32), spread.astype(np.int32), off.astype(np.int32)
+
+
+def _origin(origin):
+    try:
+        o = tuple(int(v) for v in origin)
+    except (TypeError, ValueError):
+        raise ValueError("origin is (row0, col0)") from None
+    if len(o) != 2 or max(abs(o[0]), abs(o[1])) > 2 ** 30:
+        raise ValueError("origin is (row0, col0), within +-2^30")
+    return o
+
+
+def _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops):
+    """(svgr_painted_desc, what it points at)."""
+    d = _abi.PaintedDesc()
+    d.n_paths, d.rows, d.cols, d.plane, d.has_bg = n_paths, rows, cols, plane, int(bg is not None)
+    d.bg = (C.c_double * 4)(*(bg if bg is not None else (0.0,) * 4))
+    d.row0, d.col0, d.n_stops = origin[0], origin[1], n_stops
+    d.kind, d.spread, d.path_stop_off = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in topo)
+    return d, topo
+
+
+_GP_ARRAYS = (("m6", 6), ("geom", 4), ("stop_pos", None), ("stop_rgba", 4))
+
+
+def _painted_inputs(cover, paints, gp, bg, origin, dtype=None):
+    """Everything of a numpy call on the host, checked: (cover, paints, bg, origin, topo, [m6, geom, stop_pos, stop_rgba])."""
+    cover, paints, bg = _compose_inputs(cover, paints, bg, dtype)
+    origin = _origin(origin)
+    n_paths = len(cover)
+    if not isinstance(gp, tuple) or len(gp) != 7:
+        raise TypeError("gp is a GradientPaints")
+    arrays = []
+    for name, width in _GP_ARRAYS:
+        a = getattr(gp, name)
+        if _is_tensor(a):
+            raise TypeError(f"gp.{name} is a numpy array here; compose_painted_tensor takes tensors")
+        if isinstance(a, np.ndarray) and a.dtype != np.float64:
+            raise TypeError(f"gp.{name} is float64, not {a.dtype}")
+        try:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"gp.{name} is an array of doubles") from None
+        want = (n_paths, width) if name in ("m6", "geom") else ((len(a),) if width is None else (len(a), width))
+        if a.ndim != len(want) or a.shape != want:
+            raise ValueError(f"gp.{name} is {want if name in ('m6', 'geom') else ('n_stops',) + want[1:]}, not {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"gp.{name} must be finite")
+        arrays.append(a)
+    m6, geom, pos, rgba = arrays
+    if len(rgba) != len(pos):
+        raise ValueError(f"{len(pos)} stop positions and {len(rgba)} stop colours")
+    topo = _painted_topology(gp, n_paths, len(pos))
+    kind, _spread, off = topo
+    lin, rad = kind == KIND_LINEAR, kind == KIND_RADIAL
+    if (geom[lin, :2] == geom[lin, 2:]).all(axis=1).any():
+        raise ValueError("a linear gradient needs p0 != p1")
+    if (geom[rad, 2] <= 0.0).any():
+        raise ValueError("a radial gradient needs r > 0")
+    for p in np.nonzero(kind != KIND_SOLID)[0]:
+        if (np.diff(pos[off[p]:off[p + 1]]) < 0.0).any():
+            raise ValueError(f"the stop positions of path {p} decrease")
+    return cover, paints, bg, origin, topo, arrays
+
+
+def compose_painted(cover, paints, gp, bg=None, origin=(0, 0), dtype=None):
+    """``compose`` with gradient paints: the ``(rows, cols, 4)`` premultiplied image of ``n_paths`` fills painted source-over in
+    paint order, path ``p`` a solid fill of ``paints[p]`` (``gp.kind[p] == 0``) or the renderer's linear or radial gradient,
+    evaluated at the pixel centres of the viewport with origin ``origin = (row0, col0)``, times the coverage, times ``paints[p]``
+    component-wise (ones, or an opacity).  ``gp`` is a ``GradientPaints`` of numpy arrays (``gradient_paints`` builds one).  The
+    arithmetic is the renderer's, in double; a float32 image is rounded once.  Wrong shapes and dtypes, non-finite values,
+    ``p0 == p1``, ``r <= 0``, decreasing stop positions and every error of the topology are refused before any device work."""
+    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
+    n_paths, rows, cols = cover.shape
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays]
+    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
+    desc, _keep = _painted_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]))
+    _abi._check(ctx.lib.svgr_compose_painted_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
+    return image.download((rows, cols, 4), cover.dtype)
+
+
+def compose_painted_backward(cover, paints, gp, grad_image, bg=None, origin=(0, 0)):
+    """``(grad_cover, grad_paints, grad_gp)``: the derivative of ``sum(grad_image * compose_painted(cover, paints, gp, bg, origin))``.
+
+    ``grad_image`` has the image's shape and ``cover``'s type.  ``grad_gp`` is a ``GradientPaints`` with ``gp``'s topology and the
+    derivatives with respect to ``m6``, ``geom``, ``stop_pos`` and ``stop_rgba`` (float64); the rows of solid paths and a radial
+    gradient's unused slot are 0.  Where a derivative is not defined -- an offset exactly on a stop, a clamp, a wrap or a fold,
+    the radial centre -- one side is taken and nothing is NaN.  No atomics: the same bits on every run."""
+    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin)
+    n_paths, rows, cols = cover.shape
+    grad_image = np.asarray(grad_image)
+    if grad_image.dtype != cover.dtype:
+        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
+    if grad_image.shape != (rows, cols, 4):
+        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    n_stops = len(arrays[2])
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays]
+    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
+    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4))
+    g_cover = ctx.alloc(cover.nbytes)
+    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]   # (no stops at all: no stop buffers)
+    desc, _keep = _painted_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops)
+    _abi._check(ctx.lib.svgr_compose_painted_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
+    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
+    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:])
+
+
+@functools.lru_cache(maxsize=None)
+def _painted_function(torch):
+    class ComposePainted(torch.autograd.Function):
+        """image = ComposePainted.apply(planes, paints, m6, geom, stop_pos, stop_rgba, out, bg, origin, topo)."""
+
+        @staticmethod
+        def forward(fn, planes, paints, m6, geom, pos, rgba, out, bg, origin, topo):
+            ctx = _context(torch)
+            n_paths, rows, cols = (int(v) for v in planes.shape)
+            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
+            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba))
+            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
+            desc, _keep = _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, image)
+                _abi._check(ctx.lib.svgr_compose_painted_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            fn.save_for_backward(*kept)
+            fn.painted_args = (plane, bg, origin, topo)
+            if out is not None:
+                fn.mark_dirty(out)
+            return image
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(fn, grad):
+            kept = fn.saved_tensors
+            plane, bg, origin, topo = fn.painted_args
+            n_paths, rows, cols = (int(v) for v in kept[0].shape)
+            ctx = _context(torch)
+            grad = grad.contiguous()
+            if grad.data_ptr() % 16:
+                grad = grad.clone(memory_format=torch.contiguous_format)
+            grads = tuple(torch.empty_like(t) for t in kept)
+            desc, _keep = _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, grad, *grads)
+                _abi._check(ctx.lib.svgr_compose_painted_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            need = fn.needs_input_grad
+            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 4
+
+    return ComposePainted
+
+
+def compose_painted_tensor(planes, paints_t, gp_t, *, bg=None, origin=(0, 0), out=None):
+    """``compose_painted`` as a ``torch.autograd.Function``: a ``(rows, cols, 4)`` premultiplied image of ``planes``' type that the
+    kernel writes in place, whose backward is ``compose_painted_backward``.
+
+    ``planes`` is an ``(n_paths, rows, cols)`` float32 or float64 CUDA tensor, ``paints_t`` an ``(n_paths, 4)`` float64 CUDA tensor;
+    ``gp_t`` is a ``GradientPaints`` whose ``m6``, ``geom``, ``stop_pos`` and ``stop_rgba`` are float64 CUDA tensors and whose
+    topology (``kind``, ``spread``, ``path_stop_off``) stays on the host.  Any of the six tensors may require grad.  ``bg``,
+    ``origin`` and ``out`` are ``compose_painted``'s and ``compose_tensor``'s, and so are the stream ordering and the import-order
+    rule (``tensor.IMPORT_ORDER``).  Only the topology, shapes, dtypes and devices are checked: there is no host wait, so the
+    VALUES are not looked at.  Degenerate ones -- ``p0 == p1``, ``r <= 0``, non-finite numbers, decreasing stop positions -- give
+    NaN, infinities or a wrong stop, not an error."""
+    torch = _torch()
+    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
+        raise TypeError("gp_t is a GradientPaints")
+    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
+        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS)
+    for name, t, kinds in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in kinds or not t.is_cuda:
+            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
+    if planes.dim() != 3 or min(planes.shape) < 1:
+        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    n_paths, rows, cols = (int(v) for v in planes.shape)
+    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
+    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
+                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
+        if tuple(t.shape) != want or n_stops < 0:
+            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
+    _n_pixels(n_paths, (0, 0, rows, cols))
+    topo = _painted_topology(gp_t, n_paths, n_stops)
+    bg, origin = _compose_bg(bg), _origin(origin)
+    ctx = _context(torch)
+    for name, t, _k in named:
+        if t.device != planes.device or t.device.index != ctx.device:
+            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
+                or out.device != planes.device or out.data_ptr() % 16:
+            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
+    return _painted_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, out, bg, origin, topo)
+
+
+def render_painted_tensor(segs, m6, paints, gp, *, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
+                          flatness: float = FLATNESS):
+    """Geometry, colours and gradients to a ``(rows, cols, 4)`` premultiplied image and back: ``coverage_tensor`` followed by
+    ``compose_painted_tensor`` with ``origin`` from ``viewport``, with gradients to ``segs``, ``m6``, ``paints`` and the four
+    tensors of ``gp``.  The arguments are theirs; ``dtype`` (torch.float32 by default) is the type of the planes and of the image."""
+    vp = _viewport(viewport)
+    planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=vp, dtype=dtype, check=check, flatness=flatness)
+    return compose_painted_tensor(planes, paints, gp, bg=bg, origin=(vp[0], vp[1]))
