@@ -50,7 +50,8 @@ extern "C" {
  *    svgr_png_filter_span added (grey, RGB and 16-bit PNG output); svgr_cover_forward, svgr_cover_backward, svgr_cover_block
  *    and svgr_cover_scan added (differentiable coverage); svgr_compose_forward, svgr_compose_backward, svgr_compose_block and
  *    svgr_compose_groups added (differentiable compositing); svgr_compose_painted_forward and svgr_compose_painted_backward
- *    added (gradient paints in differentiable compositing) */
+ *    added (gradient paints in differentiable compositing); svgr_compose_grouped_forward, svgr_compose_grouped_backward and
+ *    svgr_group_depth added (isolated groups in differentiable compositing: opacity and clip paths) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1186,6 +1187,50 @@ int svgr_compose_painted_backward(svgr_ctx* ctx, const svgr_painted_desc* desc, 
                                   const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
                                   svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
                                   svgr_buf* grad_stop_rgba);
+
+/* Isolated groups in differentiable compositing (csrc/svgr_group.h has the arithmetic, DESIGN.md 7z the derivation): the painted
+ * composition above, driven by a PROGRAM of n_items items in paint order instead of the flat list of planes.  The description is
+ * svgr_painted_desc followed by the program, HOST tables that are validated and copied before the entry returns:
+ *   items[n_items x 4]   {0, p, 0, 0}                        FILL: plane p painted on the open canvas, exactly as path p above
+ *                        {1, index of its END, 0, 0}         BEGIN: a transparent canvas is opened
+ *                        {2, index of its BEGIN, opacity slot or -1, clip or -1}
+ *                                                            END: the canvas is closed, multiplied by opacity[slot] (Layer.opacity), then
+ *                                                            by the clip's mask (COMPOSE_IN), and painted OVER the canvas below
+ *   clip_off, clip_planes   clip c is the planes clip_planes[clip_off[c] : clip_off[c + 1]], at least one, composed OVER in one
+ *                           channel in that order (the first copied); there are as many clips as END items name, numbered from 0;
+ *                           clip_off goes from 0 to n_clip_planes.  Both may be NULL with n_clip_planes == 0.
+ * Every plane is used exactly once, by one FILL or as one clip plane (its rows of paints and of the paint arrays are ignored, its
+ * rows of their gradients are 0); every opacity slot and every clip by exactly one END; BEGIN and END match and nest at most
+ * svgr_group_depth() (4) deep.  n_items is the number of FILLs plus 2 n_groups, at most 2^24.
+ * DEVICE buffers: svgr_compose_painted_forward's, and opacity, n_opacities doubles (may be NULL with none).
+ * svgr_compose_grouped_backward writes grad_cover whole, clip planes included, the five arrays of svgr_compose_painted_backward
+ * and grad_opacity (n_opacities doubles).  Nothing is divided: an opacity or a mask of 0 and an empty group are ordinary values.
+ * No atomics: the same bits on every run.  A program without groups gives svgr_compose_painted_forward / _backward's bits.
+ * Both enqueue on the context's stream and never wait; they keep no state.  Before any launch: everything
+ * svgr_compose_painted_forward refuses, any violation of the program's rules above and a missing or too small buffer give
+ * SVGR_E_INVALID; more than 2^24 items, or n_groups * rows * cols beyond 2^31 - 1, give SVGR_E_OVERFLOW. */
+typedef struct {
+    int64_t n_paths, rows, cols;
+    double bg[4];          /* premultiplied; read only with has_bg */
+    int32_t plane;         /* SVGR_COVER_F64 / SVGR_COVER_F32 */
+    int32_t has_bg;        /* 0 / 1 */
+    int64_t row0, col0;    /* the viewport's origin */
+    int64_t n_stops;
+    const int32_t* kind;
+    const int32_t* spread;
+    const int32_t* path_stop_off;
+    int64_t n_items, n_groups, n_clip_planes, n_opacities;
+    const int32_t* items;
+    const int32_t* clip_off;
+    const int32_t* clip_planes;
+} svgr_grouped_desc;
+int svgr_compose_grouped_forward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image);
+int svgr_compose_grouped_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
+                                  const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
+                                  svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity);
+int svgr_group_depth(void);
 
 #ifdef __cplusplus
 }

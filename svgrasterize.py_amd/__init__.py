@@ -44,10 +44,14 @@ from .diff import coverage, coverage_backward, coverage_tensor  # noqa: F401
 from .diff import compose, compose_backward, compose_tensor, render_tensor  # noqa: F401
 from .diff import (GradientPaints, compose_painted, compose_painted_backward, compose_painted_tensor, gradient_paints,  # noqa: F401
                    render_painted_tensor)
+from .diff import (Group, Groups, LoweredScene, compose_grouped, compose_grouped_backward, compose_grouped_tensor, group_program,  # noqa: F401
+                   lower_scene, render_grouped_tensor)
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
            "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg",
            "write_jpeg", "canvas_to_jpeg", "Marker", "TextOnPath", "TextRun", "TextOutline", "TrueTypeFont", "read_ttf", "Axis", "CFFFont", "read_otf", "read_font",
            "parse_css", "Stylesheet", "Symbol", "render_to_tensor", "render_svgs_to_tensor", "elements_at", "SdfAtlas", "SdfCell", "quantize",
            "coverage", "coverage_backward", "coverage_tensor", "compose", "compose_backward", "compose_tensor", "render_tensor",
-           "GradientPaints", "gradient_paints", "compose_painted", "compose_painted_backward", "compose_painted_tensor", "render_painted_tensor"]
+           "GradientPaints", "gradient_paints", "compose_painted", "compose_painted_backward", "compose_painted_tensor", "render_painted_tensor",
+           "Group", "Groups", "group_program", "compose_grouped", "compose_grouped_backward", "compose_grouped_tensor", "render_grouped_tensor",
+           "LoweredScene", "lower_scene"]

@@ -114,6 +114,13 @@ class PaintedDesc(C.Structure):  # svgr_painted_desc
     ]
 
 
+class GroupedDesc(C.Structure):  # svgr_grouped_desc
+    _fields_ = PaintedDesc._fields_ + [
+        ("n_items", C.c_int64), ("n_groups", C.c_int64), ("n_clip_planes", C.c_int64), ("n_opacities", C.c_int64),
+        ("items", C.POINTER(C.c_int32)), ("clip_off", C.POINTER(C.c_int32)), ("clip_planes", C.POINTER(C.c_int32)),
+    ]
+
+
 TENSOR_SRC_RGBA_F64, TENSOR_SRC_RGBA_F32, TENSOR_SRC_MASK_F64 = 0, 1, 2
 COVER_F64, COVER_F32 = 0, 1
 COVER_STATUS_DEPTH, COVER_STATUS_RANGE = 1, 2
@@ -267,6 +274,9 @@ _PROTOS = {
     "svgr_compose_groups": (C.c_int, []),
     "svgr_compose_painted_forward": (C.c_int, [_P, C.POINTER(PaintedDesc)] + [_P] * 7),
     "svgr_compose_painted_backward": (C.c_int, [_P, C.POINTER(PaintedDesc)] + [_P] * 13),
+    "svgr_compose_grouped_forward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 8),
+    "svgr_compose_grouped_backward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 15),
+    "svgr_group_depth": (C.c_int, []),
 }
 EXPORTS = tuple(_PROTOS)
 

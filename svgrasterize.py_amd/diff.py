@@ -22,6 +22,12 @@ the renderer's linear or one-circle radial gradient (``GradientPaints``, built b
 gradients' transforms, end points, centre and radius, stop positions and stop colours.  ``compose_painted_tensor`` and
 ``render_painted_tensor`` are the torch forms.  The kernels are svgr_compose_painted_forward / svgr_compose_painted_backward
 (csrc/svgr_gradpaint.h).
+
+Groups: ``compose_grouped`` / ``compose_grouped_backward`` are ``compose_painted`` and its backward driven by a program with
+isolated groups (``Group``, ``group_program``, ``Groups``): a group has an opacity, a clip of its own coverage planes, both or
+neither, and the backward also reaches the opacities and the clip planes.  ``compose_grouped_tensor`` and ``render_grouped_tensor``
+are the torch forms; ``lower_scene`` makes all the arrays from a ``Scene``.  The kernels are svgr_compose_grouped_forward /
+svgr_compose_grouped_backward (csrc/svgr_group.h).
 """
 from __future__ import annotations
 
@@ -851,3 +857,484 @@ def render_painted_tensor(segs, m6, paints, gp, *, kinds, path_seg_off, rules, v
     vp = _viewport(viewport)
     planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=vp, dtype=dtype, check=check, flatness=flatness)
     return compose_painted_tensor(planes, paints, gp, bg=bg, origin=(vp[0], vp[1]))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# isolated groups: group opacity and clip paths in the compositor (svgr_compose_grouped_forward / _backward, csrc/svgr_group.h,
+# DESIGN.md 7z)
+# ------------------------------------------------------------------------------------------------------------------------------
+OP_FILL, OP_BEGIN, OP_END = 0, 1, 2
+MAX_ITEMS = 1 << 24
+
+
+def group_depth() -> int:
+    """How deep groups may nest below the root (svgr_group_depth())."""
+    return int(_abi.load_library().svgr_group_depth())
+
+
+class Group:
+    """An isolated group of a grouped composition: ``children`` is a list of plane indices (fills) and ``Group``s in paint order,
+    ``opacity`` a number or None, ``clip`` a list of plane indices (the clip's coverage planes, composed OVER in one channel in
+    that order) or None.  The group is painted on a transparent canvas, multiplied by the opacity, then by the clip's mask, and
+    composed OVER what lies below: the renderer's ``CLIP(OPACITY(GROUP))``."""
+
+    __slots__ = ("children", "opacity", "clip")
+
+    def __init__(self, children, opacity=None, clip=None):
+        self.children, self.opacity, self.clip = list(children), opacity, (None if clip is None else list(clip))
+
+    def __repr__(self):
+        return f"Group({self.children!r}, opacity={self.opacity!r}, clip={self.clip!r})"
+
+
+class Groups(NamedTuple):
+    """The program of a grouped composition.  The topology stays on the host: ``items`` ``(n_items, 4)`` int32 -- ``{0, p, 0, 0}``
+    paints plane ``p``, ``{1, index of its END, 0, 0}`` opens a group, ``{2, index of its BEGIN, opacity slot or -1, clip or -1}``
+    closes it --, ``clip_off`` and ``clip_planes`` (clip ``c`` is the planes ``clip_planes[clip_off[c] : clip_off[c + 1]]``).
+    ``opacity`` is float64 ``(n_opacities,)``: a numpy array, or a CUDA tensor for ``compose_grouped_tensor``."""
+
+    items: object
+    clip_off: object
+    clip_planes: object
+    opacity: object
+
+
+def group_program(tree):
+    """The ``Groups`` of a tree: a list of ints (fills) and ``Group``s in paint order.  Opacity slots and clips are numbered in
+    the order their groups CLOSE.  Only the tree's own form is checked here; ``compose_grouped`` checks the program against the
+    planes (every plane used exactly once, the depth)."""
+    items, clip_off, clip_planes, opacity = [], [0], [], []
+
+    def walk(children):
+        if isinstance(children, (Group, int, np.integer)) or not hasattr(children, "__iter__"):
+            raise TypeError("a tree is a list of plane indices and Groups")
+        for child in children:
+            if isinstance(child, Group):
+                begin = len(items)
+                items.append([OP_BEGIN, -1, 0, 0])
+                walk(child.children)
+                slot = clip = -1
+                if child.opacity is not None:
+                    slot = len(opacity)
+                    opacity.append(float(child.opacity))
+                if child.clip is not None:
+                    if len(child.clip) == 0:
+                        raise ValueError("a clip has at least one plane")
+                    clip = len(clip_off) - 1
+                    clip_planes.extend(int(p) for p in child.clip)
+                    clip_off.append(len(clip_planes))
+                items[begin][1] = len(items)
+                items.append([OP_END, begin, slot, clip])
+            elif isinstance(child, (int, np.integer)) and not isinstance(child, bool):
+                items.append([OP_FILL, int(child), 0, 0])
+            else:
+                raise TypeError(f"a tree holds plane indices and Groups, not {type(child).__name__}")
+
+    walk(tree)
+    return Groups(np.array(items, dtype=np.int32).reshape(-1, 4), np.array(clip_off, dtype=np.int32), np.array(clip_planes, dtype=np.int32),
+                  np.array(opacity, dtype=np.float64))
+
+
+def _group_topology(groups, n_paths, n_opacities):
+    """items, clip_off and clip_planes on the host, checked as svgr_compose_grouped_forward checks them: (three int32 arrays,
+    n_groups)."""
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    out = []
+    for name, a in (("items", groups.items), ("clip_off", groups.clip_off), ("clip_planes", groups.clip_planes)):
+        if _is_tensor(a):
+            raise TypeError(f"groups.{name} stays on the host: a numpy array or a list")
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"groups.{name} holds integers, not {a.dtype}")
+        out.append(np.ascontiguousarray(a.astype(np.int64)))
+    items, clip_off, clip_planes = out
+    if items.ndim != 2 or items.shape[1] != 4 or len(items) < 1:
+        raise ValueError(f"groups.items is (n_items, 4) with at least one item, not {items.shape}")
+    if len(items) > MAX_ITEMS:
+        raise ValueError(f"a program has at most {MAX_ITEMS} items")
+    if clip_off.ndim != 1 or clip_planes.ndim != 1:
+        raise ValueError("groups.clip_off and groups.clip_planes are lists of integers")
+    depth_max = group_depth()
+    planes, slots, clips = np.zeros(n_paths, dtype=np.int64), np.zeros(n_opacities, dtype=np.int64), {}
+    stack, n_groups = [], 0
+    for i, (op, a, slot, clip) in enumerate(items.tolist()):
+        if op == OP_FILL:
+            if not 0 <= a < n_paths:
+                raise ValueError(f"item {i}: FILL of plane {a}, not one of {n_paths}")
+            planes[a] += 1
+        elif op == OP_BEGIN:
+            if not i < a < len(items) or items[a, 0] != OP_END or items[a, 1] != i:
+                raise ValueError(f"item {i}: BEGIN without its END")
+            if len(stack) == depth_max:
+                raise ValueError(f"item {i}: groups nest deeper than {depth_max}")
+            stack.append(i)
+            n_groups += 1
+        elif op == OP_END:
+            if not stack or stack[-1] != a:
+                raise ValueError(f"item {i}: END does not close the open group")
+            stack.pop()
+            if slot != -1:
+                if not 0 <= slot < n_opacities:
+                    raise ValueError(f"item {i}: opacity slot {slot}, not one of {n_opacities}")
+                slots[slot] += 1
+            if clip != -1:
+                if clip < 0 or clip in clips:
+                    raise ValueError(f"item {i}: clip {clip} is negative or used twice")
+                clips[clip] = i
+        else:
+            raise ValueError(f"item {i}: unknown op {op} (0 FILL, 1 BEGIN, 2 END)")
+    if stack:
+        raise ValueError(f"item {stack[-1]}: the group is not closed")
+    if (slots != 1).any():
+        raise ValueError("every opacity slot is used by exactly one group")
+    if sorted(clips) != list(range(len(clips))):
+        raise ValueError(f"the {len(clips)} clips are numbered from 0")
+    if clips or len(clip_planes):
+        count = np.diff(clip_off)
+        if len(clip_off) != len(clips) + 1 or clip_off[0] != 0 or clip_off[-1] != len(clip_planes) or (count < 1).any():
+            raise ValueError("groups.clip_off is n_clips + 1 strictly ascending integers from 0 to the number of clip planes")
+        if ((clip_planes < 0) | (clip_planes >= n_paths)).any():
+            raise ValueError(f"a clip plane is not one of {n_paths}")
+        np.add.at(planes, clip_planes, 1)
+    if (planes != 1).any():
+        p = int(np.nonzero(planes != 1)[0][0])
+        raise ValueError(f"plane {p} is used {int(planes[p])} times: every plane is used exactly once, by a FILL or as a clip plane")
+    if len(clip_off) == 0:
+        clip_off = np.zeros(1, dtype=np.int64)
+    return (np.ascontiguousarray(items, dtype=np.int32), clip_off.astype(np.int32), clip_planes.astype(np.int32)), n_groups
+
+
+def _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, gtopo, n_groups, n_opacities):
+    """(svgr_grouped_desc, what it points at)."""
+    d = _abi.GroupedDesc()
+    d.n_paths, d.rows, d.cols, d.plane, d.has_bg = n_paths, rows, cols, plane, int(bg is not None)
+    d.bg = (C.c_double * 4)(*(bg if bg is not None else (0.0,) * 4))
+    d.row0, d.col0, d.n_stops = origin[0], origin[1], n_stops
+    d.kind, d.spread, d.path_stop_off = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in topo)
+    d.n_items, d.n_groups, d.n_clip_planes, d.n_opacities = len(gtopo[0]), n_groups, len(gtopo[2]), n_opacities
+    d.items, d.clip_off, d.clip_planes = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in gtopo)
+    return d, (topo, gtopo)
+
+
+def _grouped_inputs(cover, paints, gp, groups, bg, origin, dtype=None):
+    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    opacity = groups.opacity
+    if _is_tensor(opacity):
+        raise TypeError("groups.opacity is a numpy array here; compose_grouped_tensor takes a tensor")
+    if isinstance(opacity, np.ndarray) and opacity.size and opacity.dtype != np.float64:
+        raise TypeError(f"groups.opacity is float64, not {opacity.dtype}")
+    try:
+        opacity = np.ascontiguousarray(opacity, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("groups.opacity is an array of doubles") from None
+    if opacity.ndim != 1:
+        raise ValueError(f"groups.opacity is (n_opacities,), not {opacity.shape}")
+    if not np.isfinite(opacity).all():
+        raise ValueError("groups.opacity must be finite")
+    gtopo, n_groups = _group_topology(groups, len(cover), len(opacity))
+    return cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups
+
+
+def compose_grouped(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=None):
+    """``compose_painted`` with isolated groups: the ``(rows, cols, 4)`` premultiplied image of the program ``groups`` (a
+    ``Groups``; ``group_program`` builds one from a tree of plane indices and ``Group``s) over the planes of ``cover``.  A fill
+    paints its plane exactly as ``compose_painted`` paints a path; a group is painted on a transparent canvas, multiplied by its
+    opacity (``Layer.opacity``), then by its clip's mask (the clip's planes composed OVER in one channel, then ``COMPOSE_IN``), and
+    composed OVER the canvas below.  Every plane is used exactly once, by a fill or as a clip plane; the rows of ``paints`` and
+    ``gp`` of a clip plane are ignored.  Groups nest at most ``group_depth()`` deep.  A program without groups gives
+    ``compose_painted``'s bits.  Everything ``compose_painted`` refuses, non-finite opacities and every error of the program are
+    refused before any device work."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _grouped_inputs(cover, paints, gp, groups, bg, origin, dtype)
+    n_paths, rows, cols = cover.shape
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
+    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
+    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]), gtopo, n_groups, len(opacity))
+    _abi._check(ctx.lib.svgr_compose_grouped_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
+    return image.download((rows, cols, 4), cover.dtype)
+
+
+def compose_grouped_backward(cover, paints, gp, groups, grad_image, bg=None, origin=(0, 0)):
+    """``(grad_cover, grad_paints, grad_gp, grad_opacity)``: the derivative of
+    ``sum(grad_image * compose_grouped(cover, paints, gp, groups, bg, origin))``.
+
+    ``grad_cover`` has ``cover``'s shape and type and holds the clip planes' derivatives too: a clip's outline moves through them.
+    ``grad_paints`` and ``grad_gp`` are ``compose_painted_backward``'s (the rows of clip planes are 0); ``grad_opacity`` is float64
+    ``(n_opacities,)``.  Nothing is divided: an opacity or a mask of 0, an opaque and an empty group are ordinary values.  No
+    atomics: the same bits on every run."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _grouped_inputs(cover, paints, gp, groups, bg, origin)
+    n_paths, rows, cols = cover.shape
+    grad_image = np.asarray(grad_image)
+    if grad_image.dtype != cover.dtype:
+        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
+    if grad_image.shape != (rows, cols, 4):
+        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    n_stops, n_op = len(arrays[2]), len(opacity)
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
+    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
+    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4), (n_op,))
+    g_cover = ctx.alloc(cover.nbytes)
+    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]
+    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops, gtopo, n_groups, n_op)
+    _abi._check(ctx.lib.svgr_compose_grouped_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
+    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
+    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:5]), got[5]
+
+
+@functools.lru_cache(maxsize=None)
+def _grouped_function(torch):
+    class ComposeGrouped(torch.autograd.Function):
+        """image = ComposeGrouped.apply(planes, paints, m6, geom, stop_pos, stop_rgba, opacity, out, bg, origin, topo, gtopo, n_groups)."""
+
+        @staticmethod
+        def forward(fn, planes, paints, m6, geom, pos, rgba, opacity, out, bg, origin, topo, gtopo, n_groups):
+            ctx = _context(torch)
+            n_paths, rows, cols = (int(v) for v in planes.shape)
+            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
+            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba, opacity))
+            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
+            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]), gtopo, n_groups, int(opacity.shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, image)
+                _abi._check(ctx.lib.svgr_compose_grouped_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            fn.save_for_backward(*kept)
+            fn.grouped_args = (plane, bg, origin, topo, gtopo, n_groups)
+            if out is not None:
+                fn.mark_dirty(out)
+            return image
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(fn, grad):
+            kept = fn.saved_tensors
+            plane, bg, origin, topo, gtopo, n_groups = fn.grouped_args
+            n_paths, rows, cols = (int(v) for v in kept[0].shape)
+            ctx = _context(torch)
+            grad = grad.contiguous()
+            if grad.data_ptr() % 16:
+                grad = grad.clone(memory_format=torch.contiguous_format)
+            grads = tuple(torch.empty_like(t) for t in kept)
+            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]), gtopo, n_groups, int(kept[6].shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, grad, *grads)
+                _abi._check(ctx.lib.svgr_compose_grouped_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            need = fn.needs_input_grad
+            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 6
+
+    return ComposeGrouped
+
+
+def compose_grouped_tensor(planes, paints_t, gp_t, groups, opacity_t, *, bg=None, origin=(0, 0), out=None):
+    """``compose_grouped`` as a ``torch.autograd.Function``, whose backward is ``compose_grouped_backward``.
+
+    ``planes``, ``paints_t`` and ``gp_t`` are ``compose_painted_tensor``'s; ``groups`` is a ``Groups`` whose topology (``items``,
+    ``clip_off``, ``clip_planes``) stays on the host and whose ``opacity`` field is not looked at: the opacities are ``opacity_t``,
+    a float64 ``(n_opacities,)`` CUDA tensor.  Any of the seven tensors may require grad.  ``bg``, ``origin``, ``out``, the stream
+    ordering and the import-order rule (``tensor.IMPORT_ORDER``) are ``compose_painted_tensor``'s.  Only the program, shapes, dtypes
+    and devices are checked: there is no host wait, so the VALUES are not looked at."""
+    torch = _torch()
+    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
+        raise TypeError("gp_t is a GradientPaints")
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
+        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS) + (("opacity_t", opacity_t, (torch.float64,)),)
+    for name, t, kinds in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in kinds or not t.is_cuda:
+            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
+    if planes.dim() != 3 or min(planes.shape) < 1:
+        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    n_paths, rows, cols = (int(v) for v in planes.shape)
+    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
+    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
+                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
+        if tuple(t.shape) != want or n_stops < 0:
+            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
+    if opacity_t.dim() != 1:
+        raise ValueError(f"opacity_t is (n_opacities,), not {tuple(opacity_t.shape)}")
+    topo = _painted_topology(gp_t, n_paths, n_stops)
+    gtopo, n_groups = _group_topology(groups, n_paths, int(opacity_t.shape[0]))
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    bg, origin = _compose_bg(bg), _origin(origin)
+    ctx = _context(torch)
+    for name, t, _k in named:
+        if t.device != planes.device or t.device.index != ctx.device:
+            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
+                or out.device != planes.device or out.data_ptr() % 16:
+            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
+    return _grouped_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, opacity_t, out, bg, origin, topo, gtopo,
+                                          n_groups)
+
+
+def render_grouped_tensor(segs, m6, paints, gp, opacity, *, groups, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
+                          flatness: float = FLATNESS):
+    """Geometry, colours, gradients and groups to a ``(rows, cols, 4)`` premultiplied image and back: ``coverage_tensor`` followed
+    by ``compose_grouped_tensor`` with ``origin`` from ``viewport``, with gradients to ``segs`` (a clip's outline included), ``m6``,
+    ``paints``, the four tensors of ``gp`` and ``opacity``.  The arguments are theirs."""
+    vp = _viewport(viewport)
+    planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=vp, dtype=dtype, check=check, flatness=flatness)
+    return compose_grouped_tensor(planes, paints, gp, groups, opacity, bg=bg, origin=(vp[0], vp[1]))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# from a Scene to the differentiable inputs
+# ------------------------------------------------------------------------------------------------------------------------------
+class LoweredScene(NamedTuple):
+    """What ``lower_scene`` makes of a ``Scene``: the inputs of ``coverage`` (``segs``, ``kinds``, ``path_seg_off``, ``rules``,
+    ``m6``: one plane per fill, stroke outline and clip path, every node's own transforms baked into ``segs``, the render
+    transform in every row of ``m6``), of ``compose_grouped`` (``paints``, ``gp``, ``groups``) and ``sources``: per plane
+    ``(role, Path)`` with ``role`` "fill", "stroke" or "clip" and the node's own path (a STROKE node's centre line, not its
+    outline)."""
+
+    segs: object
+    kinds: object
+    path_seg_off: object
+    rules: object
+    m6: object
+    paints: object
+    gp: object
+    groups: object
+    sources: object
+
+
+_NODE_NAMES = ("FILL", "STROKE", "GROUP", "OPACITY", "CLIP", "MASK", "TRANSFORM", "FILTER", "BLEND", "MARKERS")
+
+
+def lower_scene(scene, transform=None, linear_rgb: bool = False):
+    """The ``LoweredScene`` of ``scene`` drawn under the render transform ``transform`` (identity by default): what
+    ``svg_scene_from_filepath`` returns, as the arrays the differentiable route takes.  Host only, apart from the expansion lazy
+    nodes (markers, text) and dashed strokes do themselves.
+
+    FILL is a plane under its rule.  STROKE is a nonzero plane of ``path.stroke(...)``'s outline: a gradient reaches the outline's
+    points, not the width, the joins or the centre line.  TRANSFORM is baked into the segments (``Path.transform``).  A plain GROUP
+    is flattened into its parent: source-over is associative, so the pixels differ from the renderer's separately composited
+    group by roundings only (a few units in the last place), not in what is drawn.  OPACITY is a group with an opacity, CLIP a
+    group with a clip whose planes are the clip scene's fills (FILL, GROUP and TRANSFORM nodes; the planes come before the
+    target's); an OPACITY that is the CLIP's direct target shares its level, any other order takes two.  A clip whose scene has no
+    fill hides its target, as in the renderer: neither gets a plane.  Solid paints are converted as the renderer converts them
+    (``solid_paint``), gradients go through ``gradient_paints`` under the accumulated transform.
+
+    Refused with a ``ValueError`` that names the node, nothing is dropped silently: ``bbox_units=True`` on a CLIP or a gradient,
+    MASK, FILTER and BLEND nodes, pattern and image paints, what ``gradient_paints`` refuses, a CLIP or anything but FILL, GROUP
+    and TRANSFORM inside a clip's scene, groups nested deeper than ``group_depth()``, and a scene that draws nothing."""
+    from .geometry import _RULES, Transform, solid_paint  # noqa: PLC0415
+    from .paint import is_gradient  # noqa: PLC0415
+    from .scene import (RENDER_BLEND, RENDER_CLIP, RENDER_FILL, RENDER_FILTER, RENDER_GROUP, RENDER_MARKERS, RENDER_MASK, RENDER_OPACITY,  # noqa: PLC0415
+                        RENDER_STROKE, RENDER_TRANSFORM, Scene, _expanded, _stroked)
+
+    if not isinstance(scene, Scene):
+        raise TypeError(f"scene is a Scene, not {type(scene).__name__}")
+    render = transform if transform is not None else Transform()
+    depth_max = group_depth()
+    planes = []   # (path with the node's transforms applied, rule, paint, accumulated transform, role, source)
+
+    def refuse(kind, why):
+        raise ValueError(f"{_NODE_NAMES[kind]} node: {why}")
+
+    def plane(path, acc, rule, role, source, paint):
+        if rule not in _RULES:
+            raise ValueError(f"{role.upper()} node: invalid fill rule: {rule}")
+        planes.append((path.transform(acc), _RULES[rule], paint, acc, role, source))
+        return len(planes) - 1
+
+    def clip_planes(node, acc, out):
+        if node[0] == RENDER_MARKERS:
+            node = _expanded(node)
+            if node is None:
+                return
+        kind, args = node
+        if kind == RENDER_FILL:
+            out.append(plane(args[0], acc, args[2], "clip", args[0], None))
+        elif kind == RENDER_GROUP:
+            for child in args:
+                clip_planes(child, acc, out)
+        elif kind == RENDER_TRANSFORM:
+            clip_planes(args[0], acc @ args[1], out)
+        elif kind == RENDER_CLIP:
+            refuse(kind, "a clip inside a clip's scene is not supported")
+        else:
+            refuse(kind, "a clip's scene holds FILL, GROUP and TRANSFORM nodes")
+
+    def walk(node, acc, out, depth):
+        if node[0] == RENDER_MARKERS:
+            node = _expanded(node)
+            if node is None:
+                return
+        kind, args = node
+        if kind == RENDER_FILL or kind == RENDER_STROKE:
+            paint = args[1]
+            if paint is None:   # (the renderer draws nothing)
+                return
+            if not is_gradient(paint) and not (isinstance(paint, np.ndarray) and paint.shape == (4,)):
+                refuse(kind, f"a {type(paint).__name__} paint is not supported: solid colours and gradients are")
+            if is_gradient(paint) and paint.bbox_units:
+                refuse(kind, "a gradient in objectBoundingBox units (bbox_units=True) is not supported")
+            if kind == RENDER_FILL:
+                out.append(plane(args[0], acc, args[2], "fill", args[0], paint))
+            else:
+                out.append(plane(_stroked(node), acc, None, "stroke", args[0], paint))
+        elif kind == RENDER_GROUP:
+            for child in args:
+                walk(child, acc, out, depth)
+        elif kind == RENDER_TRANSFORM:
+            walk(args[0], acc @ args[1], out, depth)
+        elif kind == RENDER_OPACITY or kind == RENDER_CLIP:
+            if depth == depth_max:
+                refuse(kind, f"groups nest deeper than {depth_max}")
+            clip = None
+            if kind == RENDER_CLIP:
+                if args[2]:
+                    refuse(kind, "a clip in objectBoundingBox units (bbox_units=True) is not supported")
+                clip = []
+                clip_planes(args[1], acc, clip)
+                if not clip:   # (the renderer draws nothing)
+                    return
+                node = args[0]
+            opacity = None
+            if node[0] == RENDER_OPACITY:   # (the node itself, or the direct target of the CLIP: one level)
+                opacity, node = float(node[1][1]), node[1][0]
+            group = Group([], opacity, clip)
+            walk(node, acc, group.children, depth + 1)
+            out.append(group)
+        elif kind in (RENDER_MASK, RENDER_FILTER, RENDER_BLEND):
+            refuse(kind, "not supported by the differentiable route")
+        else:
+            raise ValueError(f"unhandled scene type: {kind}")
+
+    tree: list = []
+    walk(scene, Transform(), tree, 0)
+    if not planes:
+        raise ValueError("the scene draws nothing: no plane")
+    packed = [p[0].packed() for p in planes]
+    segs = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 8) for s, _k in packed])
+    kinds = np.concatenate([np.asarray(k, dtype=np.uint8).reshape(-1) for _s, k in packed])
+    off = np.concatenate([[0], np.cumsum([len(k) for _s, k in packed])]).astype(np.int32)
+    parts, rows = [], []
+    for i, (_path, _rule, paint, acc, role, _source) in enumerate(planes):
+        if role == "clip":
+            paint = np.zeros(4)
+        elif not is_gradient(paint):
+            paint = solid_paint(paint, linear_rgb)
+        try:
+            gp, row = gradient_paints([paint], render @ acc, linear_rgb)
+        except ValueError as e:
+            raise ValueError(f"{role.upper()} node (plane {i}): {e}") from None
+        parts.append(gp)
+        rows.append(row)
+    stop_off = np.concatenate([[0], np.cumsum([len(g.stop_pos) for g in parts])]).astype(np.int32)
+    gp = GradientPaints(np.concatenate([g.kind for g in parts]), np.concatenate([g.spread for g in parts]), stop_off,
+                        np.concatenate([g.m6 for g in parts]), np.concatenate([g.geom for g in parts]), np.concatenate([g.stop_pos for g in parts]),
+                        np.concatenate([g.stop_rgba for g in parts]).reshape(-1, 4))
+    m6 = np.tile(np.asarray(render.m6(), dtype=np.float64), (len(planes), 1))
+    return LoweredScene(segs, kinds, off, np.array([p[1] for p in planes], dtype=np.uint8), m6, np.concatenate(rows), gp, group_program(tree),
+                        tuple((p[4], p[5]) for p in planes))
