@@ -51,7 +51,8 @@ extern "C" {
  *    and svgr_cover_scan added (differentiable coverage); svgr_compose_forward, svgr_compose_backward, svgr_compose_block and
  *    svgr_compose_groups added (differentiable compositing); svgr_compose_painted_forward and svgr_compose_painted_backward
  *    added (gradient paints in differentiable compositing); svgr_compose_grouped_forward, svgr_compose_grouped_backward and
- *    svgr_group_depth added (isolated groups in differentiable compositing: opacity and clip paths) */
+ *    svgr_group_depth added (isolated groups in differentiable compositing: opacity and clip paths); svgr_compose_masked_forward
+ *    and svgr_compose_masked_backward added (luminance-masked groups in differentiable compositing) */
 #define SVGR_ABI_VERSION 6
 
 typedef enum {
@@ -1231,6 +1232,28 @@ int svgr_compose_grouped_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, 
                                   const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
                                   svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity);
 int svgr_group_depth(void);
+
+/* Luminance-masked groups in differentiable compositing (csrc/svgr_mask.h has the arithmetic, DESIGN.md 7za the derivation): the
+ * grouped composition above with the same description and buffers, and a program that may hold two more ops:
+ *   {1, index of its closer, 0, 0}                       BEGIN: its closer is an END, a HOLD or an END_MASK
+ *   {3, index of its BEGIN, opacity slot or -1, clip or -1}
+ *                                                        HOLD: closes the TARGET group like END, but keeps it instead of painting it
+ *   {4, index of its BEGIN, 0, 0}                        END_MASK: closes the MASK group; its premultiplied canvas becomes one scalar
+ *                                                        per pixel, luminance of the straight colour (divided where alpha > 1e-4, all
+ *                                                        four clipped to [0, 1]) times alpha, as Layer.luminance_mask; the held group
+ *                                                        is multiplied by it (COMPOSE_IN) and painted OVER the canvas below
+ * A HOLD at item i is followed at i + 1 by the BEGIN of a group closed by END_MASK, and nothing else pairs them; a HOLD is never the
+ * last item.  Target and mask group sit on the same level, may hold anything (pairs too) and both count as groups: in n_groups,
+ * in n_items and towards svgr_group_depth().  A mask has no parameter: the gradients' layout is the grouped one.  The derivative
+ * takes one side at every kink (csrc/svgr_mask.h) and is finite for every finite input.  A program without pairs gives
+ * svgr_compose_grouped_forward / _backward's bits.  Errors are those of the grouped entries, with the pairing rules among the
+ * program's. */
+int svgr_compose_masked_forward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image);
+int svgr_compose_masked_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
+                                 const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
+                                 svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ from .diff import (GradientPaints, compose_painted, compose_painted_backward, co
                    render_painted_tensor)
 from .diff import (Group, Groups, LoweredScene, compose_grouped, compose_grouped_backward, compose_grouped_tensor, group_program,  # noqa: F401
                    lower_scene, render_grouped_tensor)
+from .diff import compose_masked, compose_masked_backward, compose_masked_tensor, mask_program, render_masked_tensor  # noqa: F401
 
 __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas", "svg_scene", "svg_scene_from_str",
            "svg_scene_from_filepath", "render_svg", "FontsDB", "clear_render_cache", "set_render_cache", "ImagePaint", "read_png", "read_jpeg",
@@ -54,4 +55,5 @@ __all__ = ["Scene", "Path", "Transform", "Layer", "ConvexHull", "render_canvas",
            "coverage", "coverage_backward", "coverage_tensor", "compose", "compose_backward", "compose_tensor", "render_tensor",
            "GradientPaints", "gradient_paints", "compose_painted", "compose_painted_backward", "compose_painted_tensor", "render_painted_tensor",
            "Group", "Groups", "group_program", "compose_grouped", "compose_grouped_backward", "compose_grouped_tensor", "render_grouped_tensor",
-           "LoweredScene", "lower_scene"]
+           "LoweredScene", "lower_scene", "mask_program", "compose_masked", "compose_masked_backward", "compose_masked_tensor",
+           "render_masked_tensor"]

@@ -277,6 +277,8 @@ _PROTOS = {
     "svgr_compose_grouped_forward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 8),
     "svgr_compose_grouped_backward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 15),
     "svgr_group_depth": (C.c_int, []),
+    "svgr_compose_masked_forward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 8),
+    "svgr_compose_masked_backward": (C.c_int, [_P, C.POINTER(GroupedDesc)] + [_P] * 15),
 }
 EXPORTS = tuple(_PROTOS)
 

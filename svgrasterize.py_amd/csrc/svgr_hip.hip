@@ -12132,3 +12132,587 @@ int svgr_compose_grouped_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, 
     });
 }
 }  // extern "C"
+
+// ======================================================================================
+// luminance-masked groups in differentiable compositing: svgr_compose_masked_forward / svgr_compose_masked_backward
+// (csrc/svgr_mask.h has the per-pixel arithmetic and the program's check, DESIGN.md 7za the derivation).  The grouped compositor
+// above with two more ops: HOLD closes a group but keeps it, END_MASK closes the mask group that follows it, reduces that canvas to
+// one scalar per pixel and composes the held group through it.  New kernels beside the ones above, which are not involved;
+// k_group_program and k_compose_param_sum_grouped are launched as they are.
+//   forward   k_compose_over_masked   k_compose_over_grouped, and the held group H = (G o) k_clip in LDS, a column per lane, indexed
+//                                     by the wave-uniform level of the pair: no private array, no scratch
+//   backward  k_compose_vjp_masked    walk 0 is that forward (to the last END_MASK) and parks the mask canvas M of every pair in four
+//                                     planes of the call's scratch, as T_end is parked per group: walk 1 needs k_mask and walk 2
+//                                     d k / d M before either arrives at the mask group.  Walks 1 and 2 are svgr_mask.h's; the
+//                                     parameter sums are k_compose_vjp_grouped's, a HOLD's opacity being a slot like an END's.
+// A program without pairs skips walk 0 and takes the grouped kernels' steps: the same bits.
+// ======================================================================================
+#include "svgr_mask.h"
+
+// one pixel of the forward over items[0 .. n_run): X is the root canvas on entry and on return.  below has BELOW rows per level
+// (the canvas in the first four); park, if not null, gets M of every pair.
+template <class T, int BELOW>
+__device__ __forceinline__ void masked_forward_px(const T* __restrict__ cover, const double* __restrict__ paints, const int4* __restrict__ desc,
+                                                  const double* __restrict__ m6s, const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                  const double* __restrict__ rgba, const int4* __restrict__ items, const int* __restrict__ clip_off,
+                                                  const int* __restrict__ clip_planes, const double* __restrict__ opacity, const PaintedView vw, int n_run,
+                                                  size_t n_px, size_t i, unsigned row, unsigned colj, double (*below)[BELOW][COMPOSE_BLOCK],
+                                                  double (*held)[4][COMPOSE_BLOCK], double* park, double* X) {
+    int level = 0;
+    for (int q = 0; q < n_run; ++q) {
+        const int4 it = items[q];
+        const int op = mask_op(it.x);
+        if (op == GROUP_FILL) {
+            const int p = it.y;
+            const int4 d = desc[p];
+            const double m = (double)cover[(size_t)p * n_px + i];
+            if (d.x == 0) {
+                compose_step(X, m, paints + 4 * (size_t)p);
+            } else {
+                double col[4];
+                GradPaintPx e;
+                gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0,
+                                 vw.col0, col, e);
+                gradpaint_step(X, m, col, paints + 4 * (size_t)p);
+            }
+        } else if (op == GROUP_BEGIN || op == MASK_BEGIN_HELD || op == MASK_BEGIN_MASK) {
+            SVGR_UNROLL
+            for (int c = 0; c < 4; ++c) {
+                below[level][c][threadIdx.x] = X[c];
+                X[c] = 0.0;
+            }
+            ++level;
+        } else if (op == GROUP_END) {
+            --level;
+            const double o = it.z < 0 ? 1.0 : opacity[it.z];
+            const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
+            const double G[4] = {X[0], X[1], X[2], X[3]};
+            SVGR_UNROLL
+            for (int c = 0; c < 4; ++c) X[c] = below[level][c][threadIdx.x];
+            group_step(X, G, o, k);
+        } else if (op == MASK_HOLD) {
+            --level;
+            const double o = it.z < 0 ? 1.0 : opacity[it.z];
+            const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
+            double H[4];
+            mask_hold(X, o, k, H);
+            SVGR_UNROLL
+            for (int c = 0; c < 4; ++c) {
+                held[level][c][threadIdx.x] = H[c];
+                X[c] = below[level][c][threadIdx.x];
+            }
+        } else {   // MASK_END
+            --level;
+            const double M[4] = {X[0], X[1], X[2], X[3]};
+            if (park) {
+                const size_t at = (size_t)mask_pair(it.x) * 4 * n_px + i;
+                SVGR_UNROLL
+                for (int c = 0; c < 4; ++c) park[at + (size_t)c * n_px] = M[c];
+            }
+            double H[4];
+            SVGR_UNROLL
+            for (int c = 0; c < 4; ++c) {
+                X[c] = below[level][c][threadIdx.x];
+                H[c] = held[level][c][threadIdx.x];
+            }
+            mask_step(X, H, mask_value(M));
+        }
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_masked(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                       const double* __restrict__ rgba, const int4* __restrict__ items,
+                                                                       const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
+                                                                       const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
+                                                                       int n_items, size_t n_px, T* __restrict__ image) {
+    __shared__ double below[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the canvases under the open level, a column per lane
+    __shared__ double held[GROUP_DEPTH][4][COMPOSE_BLOCK];    // the held group of the pair open on a level
+    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
+    if (i >= n_px) return;   // (no barrier below: a lane reads its own column only)
+    const unsigned row = (unsigned)i / vw.cols, colj = (unsigned)i - row * vw.cols;   // (n_px < 2^31)
+    double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+    masked_forward_px<T, 4>(cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_items, n_px, i, row, colj, below, held,
+                            nullptr, X);
+    typename ComposePx<T>::type v;
+    v.x = (T)X[0]; v.y = (T)X[1]; v.z = (T)X[2]; v.w = (T)X[3];
+    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+}
+
+// the LDS slots an item's parameters take in a run: a FILL's 14 dense terms and 5 per stop, the opacity of an END or a HOLD
+__device__ __forceinline__ int masked_need(const int4 it, const int4* __restrict__ desc) {
+    const int op = mask_op(it.x);
+    if (op == GROUP_FILL) {
+        const int4 d = desc[it.y];
+        return GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
+    }
+    return (op == GROUP_END || op == MASK_HOLD) && it.z >= 0 ? 1 : 0;
+}
+
+// M of a pair from its four planes
+__device__ __forceinline__ void masked_parked(const double* park, int pair, size_t n_px, size_t i, double* M) {
+    const size_t at = (size_t)pair * 4 * n_px + i;
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) M[c] = park[at + (size_t)c * n_px];
+}
+
+// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_masked(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                      const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                      const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                      const double* __restrict__ rgba, const int4* __restrict__ items,
+                                                                      const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
+                                                                      const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
+                                                                      int n_items, int n_walk0, int n_paths, int n_stops, int n_opacities, size_t n_px,
+                                                                      const T* __restrict__ grad_image, double* through, T* grad_cover,
+                                                                      double* __restrict__ t_end, double* park, double* __restrict__ part) {
+    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
+    __shared__ double below[GROUP_DEPTH][8][COMPOSE_BLOCK];   // canvas and base adjoint of the levels under the open one, a column per lane
+    __shared__ double held[GROUP_DEPTH][4][COMPOSE_BLOCK];    // the held group of the pair open on a level
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
+    const size_t n_stop_end = n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops;
+    double* mine = part + (size_t)blockIdx.x * (n_stop_end + (size_t)n_opacities);
+    for (int j = threadIdx.x; j < PAINTED_SLOTS; j += COMPOSE_BLOCK) {
+        SVGR_UNROLL
+        for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
+    }
+    __syncthreads();
+    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const bool live = i < n_px;
+        const unsigned row = live ? (unsigned)i / vw.cols : 0u, colj = live ? (unsigned)i - row * vw.cols : 0u;
+        double B[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            if (n_walk0 > 0) {   // walk 0: the lane reads back below only what it parks here itself
+                double X0[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+                masked_forward_px<T, 8>(cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_walk0, n_px, i, row, colj,
+                                        below, held, park, X0);
+            }
+            double above = 1.0;
+            for (int q = n_items - 1; q >= 0; --q) {
+                const int4 it = items[q];
+                const int op = mask_op(it.x);
+                if (op == GROUP_FILL) {
+                    const int p = it.y;
+                    const int4 d = desc[p];
+                    const size_t at = (size_t)p * n_px + i;
+                    const double m = (double)cover[at];
+                    double u;
+                    if (d.x == 0) {
+                        u = compose_through(m, paints[4 * (size_t)p + 3]);
+                    } else {
+                        double col[4];
+                        GradPaintPx e;
+                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj,
+                                         vw.row0, vw.col0, col, e);
+                        u = gradpaint_through(m, col, paints + 4 * (size_t)p);
+                    }
+                    through[at] = above;
+                    above = above * u;
+                } else if (op == GROUP_END) {
+                    t_end[(size_t)it.y * n_px + i] = above;
+                    above = 1.0;
+                } else if (op == MASK_END) {
+                    t_end[(size_t)it.z * n_px + i] = above;   // (of the pair's target)
+                    above = 1.0;
+                } else if (op == MASK_HOLD) {
+                    above = 1.0;
+                } else if (op == GROUP_BEGIN) {
+                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                    const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
+                    const double u = group_through(above, o, k);
+                    above = t_end[(size_t)it.y * n_px + i] * u;
+                } else if (op == MASK_BEGIN_HELD) {
+                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                    const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
+                    double M[4];
+                    masked_parked(park, mask_pair(it.x), n_px, i, M);
+                    const double u = mask_through(above, o, k, mask_value(M));
+                    above = t_end[(size_t)it.y * n_px + i] * u;
+                }   // (the BEGIN of a mask group: nothing carries over)
+            }
+            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
+            B[0] = (double)v.x; B[1] = (double)v.y; B[2] = (double)v.z; B[3] = (double)v.w;
+        }
+        double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+        double qok = 0.0;   // from a HOLD to the BEGIN after it
+        int level = 0;
+        int q0 = 0;
+        while (q0 < n_items) {
+            // the run of items q0 .. q1 - 1 whose parameters fit the LDS rows, each item's slots after the one before
+            int q1 = q0, used = 0;
+            while (q1 < n_items) {
+                const int need = masked_need(items[q1], desc);
+                if (used + need > PAINTED_SLOTS) break;
+                used += need;
+                ++q1;
+            }
+            int slot = 0;
+            for (int q = q0; q < q1; ++q) {
+                const int4 it = items[q];
+                const int op = mask_op(it.x);
+                double* rowd = &sums[wave][slot];
+                slot += masked_need(it, desc);
+                if (op == GROUP_BEGIN || op == MASK_BEGIN_HELD) {
+                    if (live) {
+                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                        const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
+                        double adj[4];
+                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
+                        SVGR_UNROLL
+                        for (int c = 0; c < 4; ++c) {
+                            below[level][c][threadIdx.x] = X[c];
+                            below[level][4 + c][threadIdx.x] = B[c];
+                            X[c] = 0.0;
+                        }
+                        if (op == GROUP_BEGIN) {
+                            group_base(adj, o, k, B);
+                        } else {
+                            double M[4];
+                            masked_parked(park, mask_pair(it.x), n_px, i, M);
+                            mask_base(adj, o, k, mask_value(M), B);
+                        }
+                    }
+                    ++level;
+                    continue;
+                }
+                if (op == MASK_BEGIN_MASK) {
+                    if (live) {
+                        double M[4];
+                        masked_parked(park, mask_pair(it.x), n_px, i, M);
+                        SVGR_UNROLL
+                        for (int c = 0; c < 4; ++c) {
+                            below[level][c][threadIdx.x] = X[c];
+                            below[level][4 + c][threadIdx.x] = B[c];
+                            X[c] = 0.0;
+                        }
+                        mask_base_of_mask(qok, M, B);
+                    }
+                    ++level;
+                    continue;
+                }
+                if (op == MASK_END) {
+                    --level;
+                    if (live) {
+                        double M[4], H[4];
+                        masked_parked(park, mask_pair(it.x), n_px, i, M);
+                        SVGR_UNROLL
+                        for (int c = 0; c < 4; ++c) {
+                            X[c] = below[level][c][threadIdx.x];
+                            B[c] = below[level][4 + c][threadIdx.x];
+                            H[c] = held[level][c][threadIdx.x];
+                        }
+                        mask_step(X, H, mask_value(M));
+                    }
+                    continue;
+                }
+                if (op == GROUP_END || op == MASK_HOLD) {
+                    --level;
+                    double term = 0.0;
+                    if (live) {
+                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                        const double G[4] = {X[0], X[1], X[2], X[3]};
+                        SVGR_UNROLL
+                        for (int c = 0; c < 4; ++c) {
+                            X[c] = below[level][c][threadIdx.x];
+                            B[c] = below[level][4 + c][threadIdx.x];
+                        }
+                        double adj[4];
+                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
+                        const double qd = compose_dot(adj, G);
+                        double km = 1.0;
+                        if (op == MASK_HOLD) {
+                            double M[4];
+                            masked_parked(park, mask_pair(it.x), n_px, i, M);
+                            km = mask_value(M);
+                        }
+                        const double dk = op == MASK_HOLD ? mask_clip_term(qd, o, km) : qd * o;
+                        double k = 1.0;
+                        if (it.w >= 0) {
+                            const int a0 = clip_off[it.w], a1 = clip_off[it.w + 1];
+                            double suffix = 1.0;   // parked in the planes' own slots, as T_p is
+                            for (int a = a1 - 1; a >= a0; --a) {
+                                const size_t at = (size_t)clip_planes[a] * n_px + i;
+                                through[at] = suffix;
+                                suffix = suffix * (1.0 - (double)cover[at]);
+                            }
+                            k = 0.0;
+                            for (int a = a0; a < a1; ++a) {
+                                const size_t at = (size_t)clip_planes[a] * n_px + i;
+                                const double dm = group_clip_vjp(dk, a == a0, k, through[at]);
+                                grad_cover[at] = (T)dm;
+                                k = group_mask_step(k, (double)cover[at], a == a0);
+                            }
+                        }
+                        if (op == MASK_HOLD) {
+                            term = mask_opacity_term(qd, k, km);
+                            qok = mask_held_dot(qd, o, k);
+                            double H[4];
+                            mask_hold(G, o, k, H);
+                            SVGR_UNROLL
+                            for (int c = 0; c < 4; ++c) held[level][c][threadIdx.x] = H[c];
+                        } else {
+                            term = qd * k;
+                            group_step(X, G, o, k);
+                        }
+                    }
+                    if (it.z >= 0) {
+                        for (int s = 32; s > 0; s >>= 1) term = term + __shfl_down(term, s);
+                        if (lane == 0) rowd[0] = rowd[0] + term;
+                    }
+                    continue;
+                }
+                const int p = it.y;
+                const int4 d = desc[p];
+                const double* paint = paints + 4 * (size_t)p;
+                double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
+                int used_lo = -1, used_hi = -1;
+                if (live) {
+                    const size_t at = (size_t)p * n_px + i;
+                    m = (double)cover[at];
+                    if (d.x == 0) {
+                        const double dm = compose_vjp_step(X, through[at], B, m, paint, dense);
+                        grad_cover[at] = (T)dm;
+                        compose_step(X, m, paint);
+                    } else {
+                        double col[4], P[4], t[4];
+                        GradPaintPx e;
+                        const double* g4 = geoms + 4 * (size_t)p;
+                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, g4, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0, vw.col0,
+                                         col, e);
+                        gradpaint_effective(col, paint, P);
+                        const double dm = compose_vjp_step(X, through[at], B, m, P, t);
+                        grad_cover[at] = (T)dm;
+                        gradpaint_vjp(d.x, g4, pos + d.z, rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
+                        gradpaint_step(X, m, col, paint);
+                        used_lo = e.lo;
+                        used_hi = e.hi;
+                    }
+                }
+                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
+                if (d.x == 0) {
+                    SVGR_UNROLL
+                    for (int k = 0; k < 4; ++k)
+                        for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
+                    if (lane == 0) {
+                        SVGR_UNROLL
+                        for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
+                    }
+                    continue;
+                }
+                SVGR_UNROLL
+                for (int k = 0; k < GRADPAINT_DENSE; ++k)
+                    for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
+                if (lane == 0) {
+                    SVGR_UNROLL
+                    for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
+                }
+                const int ns = d.w - d.z;
+                for (int s = 0; s < ns; ++s) {
+                    const bool at_lo = used_lo == s, at_hi = used_hi == s;
+                    if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
+                    double v[GRADPAINT_STOP];
+                    SVGR_UNROLL
+                    for (int k = 0; k < GRADPAINT_STOP; ++k) {
+                        v[k] = at_lo ? lo[k] : (at_hi ? hi[k] : 0.0);
+                        for (int r = 32; r > 0; r >>= 1) v[k] = v[k] + __shfl_down(v[k], r);
+                    }
+                    if (lane == 0) {
+                        double* rows = rowd + GRADPAINT_DENSE + GRADPAINT_STOP * s;
+                        SVGR_UNROLL
+                        for (int k = 0; k < GRADPAINT_STOP; ++k) rows[k] = rows[k] + v[k];
+                    }
+                }
+            }
+            __syncthreads();
+            slot = 0;
+            for (int q = q0; q < q1; ++q) {
+                const int4 it = items[q];
+                const int need = masked_need(it, desc);
+                if (need == 0) continue;
+                size_t dense_at, stop_at = 0;   // where the item's first GRADPAINT_DENSE slots and the ones after them go
+                if (mask_op(it.x) == GROUP_FILL) {
+                    dense_at = (size_t)GRADPAINT_DENSE * (size_t)it.y;
+                    stop_at = n_dense + (size_t)GRADPAINT_STOP * (size_t)desc[it.y].z;
+                } else {
+                    dense_at = n_stop_end + (size_t)it.z;
+                }
+                for (int j = threadIdx.x; j < need; j += COMPOSE_BLOCK) {
+                    double s = sums[0][slot + j];
+                    SVGR_UNROLL
+                    for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][slot + j];
+                    double* o = mine + (j < GRADPAINT_DENSE ? dense_at + (size_t)j : stop_at + (size_t)(j - GRADPAINT_DENSE));
+                    *o = *o + s;
+                    SVGR_UNROLL
+                    for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][slot + j] = 0.0;
+                }
+                slot += need;
+            }
+            __syncthreads();
+            q0 = q1;
+        }
+    }
+}
+
+struct MaskedShape {
+    GroupedShape g;
+    int n_pairs, n_walk0;   // masked pairs; the items walk 0 runs: to the last END_MASK
+};
+
+// Everything of a masked description that can be wrong, and the program's table: grouped_check with mask_program_check.
+static int masked_check(const char* entry, const svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints,
+                        const svgr_buf* m6, const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
+                        MaskedShape& m) {
+    GroupedShape& s = m.g;
+    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
+    svgr_painted_desc pd;
+    pd.n_paths = d->n_paths; pd.rows = d->rows; pd.cols = d->cols; pd.plane = d->plane; pd.has_bg = d->has_bg;
+    for (int k = 0; k < 4; ++k) pd.bg[k] = d->bg[k];
+    pd.row0 = d->row0; pd.col0 = d->col0; pd.n_stops = d->n_stops;
+    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
+    if (int rc = painted_check(entry, ctx, &pd, cover, paints, m6, geom, stop_pos, stop_rgba, s.p)) return rc;
+    constexpr int64_t kMax = (1ll << 31) - 1;
+    if (d->n_groups < 0 || d->n_groups > kMax || d->n_items < 0 || d->n_items > kMax || d->n_opacities < 0 || d->n_clip_planes < 0)
+        return fail(SVGR_E_INVALID, "%s: %lld items, %lld groups, %lld opacities, %lld clip planes", entry, (long long)d->n_items, (long long)d->n_groups,
+                    (long long)d->n_opacities, (long long)d->n_clip_planes);
+    if (d->n_groups > d->n_items) return fail(SVGR_E_INVALID, "%s: %lld groups in %lld items", entry, (long long)d->n_groups, (long long)d->n_items);
+    if (d->n_items > GROUP_MAX_ITEMS) return fail(SVGR_E_OVERFLOW, "%s: %lld items are beyond %d", entry, (long long)d->n_items, GROUP_MAX_ITEMS);
+    std::vector<int> seen((size_t)d->n_paths + (size_t)d->n_groups + (size_t)std::min(d->n_opacities, d->n_groups) + 1);
+    s.table.assign(4 * (size_t)d->n_items, 0);
+    long long at = -1;
+    int n_clips = 0, last_mask = -1;
+    m.n_pairs = 0;
+    if (const char* what = mask_program_check(d->items, d->n_items, d->n_paths, d->n_groups, d->n_clip_planes, d->n_opacities, d->clip_off, d->clip_planes,
+                                              seen.data(), s.table.data(), &n_clips, &m.n_pairs, &last_mask, &at))
+        return fail(SVGR_E_INVALID, "%s: the program is wrong: %s (at %lld)", entry, what, at);
+    // (this bounds walk 0's planes too: a pair is two groups and parks four planes)
+    if ((unsigned __int128)d->n_groups * (unsigned __int128)s.p.c.n_px > (unsigned __int128)kMax)
+        return fail(SVGR_E_OVERFLOW, "%s: %lld groups of %zu pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_groups, s.p.c.n_px);
+    if (d->n_opacities && (!painted_has(opacity, (size_t)d->n_opacities * 8) || !opacity->ptr))
+        return fail(SVGR_E_INVALID, "%s: opacity is missing or too small for the description", entry);
+    s.n_items = (int)d->n_items;
+    s.n_groups = (int)d->n_groups;
+    s.n_opacities = (int)d->n_opacities;
+    s.n_clips = n_clips;
+    s.n_clip_planes = (int)d->n_clip_planes;
+    m.n_walk0 = last_mask + 1;
+    if (n_clips) {
+        s.table.insert(s.table.end(), d->clip_off, d->clip_off + n_clips + 1);
+        s.table.insert(s.table.end(), d->clip_planes, d->clip_planes + d->n_clip_planes);
+    }
+    return 0;
+}
+
+static int masked_forward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
+                               const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
+    static const char* entry = "svgr_compose_masked_forward";
+    MaskedShape m;
+    if (int rc = masked_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, m)) return rc;
+    const GroupedShape& s = m.g;
+    const ComposeShape& c = s.p.c;
+    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (image->bytes < c.n_px * 4 * c.elem || !compose_aligned(image))
+        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    PoolBlock topo, table;   // (go back at scope end by the pool's stream-order rule)
+    HIPCHK(topo.alloc((size_t)c.n_paths * sizeof(int4), ctx->device));
+    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
+    svgr_painted_desc pd;
+    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
+    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
+    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
+    const dim3 grid = grid1(c.n_px, COMPOSE_BLOCK);
+    if (d->plane == COVER_F32)
+        SVGR_LAUNCH(k_compose_over_masked<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
+                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
+                    c.bg, s.p.vw, g.n_items, c.n_px, (float*)image->ptr);
+    else
+        SVGR_LAUNCH(k_compose_over_masked<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
+                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
+                    c.bg, s.p.vw, g.n_items, c.n_px, (double*)image->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int masked_backward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
+                                const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
+                                const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
+                                svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
+    static const char* entry = "svgr_compose_masked_backward";
+    MaskedShape m;
+    if (int rc = masked_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, m)) return rc;
+    const GroupedShape& s = m.g;
+    const ComposeShape& c = s.p.c;
+    if (!grad_image || !grad_cover || !grad_paints || !grad_m6 || !grad_geom) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (grad_image->bytes < c.n_px * 4 * c.elem || !compose_aligned(grad_image))
+        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
+    const size_t np = (size_t)c.n_paths, nst = (size_t)s.p.n_stops, nop = (size_t)s.n_opacities;
+    if (grad_cover->bytes < c.n_all * c.elem || grad_paints->bytes < np * 32 || grad_m6->bytes < np * 48 || grad_geom->bytes < np * 32 || !grad_cover->ptr ||
+        !grad_paints->ptr || !grad_m6->ptr || !grad_geom->ptr)
+        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is missing or too small for the description", entry);
+    if (nst && (!painted_has(grad_stop_pos, nst * 8) || !painted_has(grad_stop_rgba, nst * 32)))
+        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
+    if (nop && (!painted_has(grad_opacity, nop * 8) || !grad_opacity->ptr))
+        return fail(SVGR_E_INVALID, "%s: grad_opacity is missing or too small for the description", entry);
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t steps = (c.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
+    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
+    const size_t n_dense = np * GRADPAINT_DENSE, n_stop_end = n_dense + nst * GRADPAINT_STOP, n_params = n_stop_end + nop;
+    // (the blocks go back at scope end by the pool's stream-order rule)
+    PoolBlock topo, table, part, through, t_end, park;   // as in the grouped backward; M per pair, four planes
+    HIPCHK(topo.alloc(np * sizeof(int4), ctx->device));
+    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
+    HIPCHK(part.alloc((size_t)groups * n_params * 8, ctx->device));
+    if (d->plane == COVER_F32) HIPCHK(through.alloc(c.n_all * 8, ctx->device));
+    HIPCHK(t_end.alloc(std::max<size_t>(1, (size_t)s.n_groups) * c.n_px * 8, ctx->device));
+    HIPCHK(park.alloc(std::max<size_t>(1, (size_t)m.n_pairs) * 4 * c.n_px * 8, ctx->device));
+    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n_params * 8, st));
+    svgr_painted_desc pd;
+    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
+    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
+    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
+    if (d->plane == COVER_F32) {
+        SVGR_LAUNCH(k_compose_vjp_masked<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr,
+                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
+                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, m.n_walk0, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const float*)grad_image->ptr,
+                    through.as<double>(), (float*)grad_cover->ptr, t_end.as<double>(), park.as<double>(), part.as<double>());
+    } else {
+        SVGR_LAUNCH(k_compose_vjp_masked<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr,
+                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
+                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, m.n_walk0, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const double*)grad_image->ptr,
+                    (double*)grad_cover->ptr, (double*)grad_cover->ptr, t_end.as<double>(), park.as<double>(), part.as<double>());
+    }
+    SVGR_LAUNCH(k_compose_param_sum_grouped, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_stop_end, n_params,
+                (double*)grad_paints->ptr, (double*)grad_m6->ptr, (double*)grad_geom->ptr, nst ? (double*)grad_stop_pos->ptr : nullptr,
+                nst ? (double*)grad_stop_rgba->ptr : nullptr, nop ? (double*)grad_opacity->ptr : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+int svgr_compose_masked_forward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
+    return abi_guard("svgr_compose_masked_forward",
+                     [&]() { return masked_forward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, image); });
+}
+
+int svgr_compose_masked_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
+                                 const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
+                                 svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
+    return abi_guard("svgr_compose_masked_backward", [&]() {
+        return masked_backward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, grad_image, grad_cover, grad_paints,
+                                    grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, grad_opacity);
+    });
+}
+}  // extern "C"

@@ -876,15 +876,19 @@ class Group:
     """An isolated group of a grouped composition: ``children`` is a list of plane indices (fills) and ``Group``s in paint order,
     ``opacity`` a number or None, ``clip`` a list of plane indices (the clip's coverage planes, composed OVER in one channel in
     that order) or None.  The group is painted on a transparent canvas, multiplied by the opacity, then by the clip's mask, and
-    composed OVER what lies below: the renderer's ``CLIP(OPACITY(GROUP))``."""
+    composed OVER what lies below: the renderer's ``CLIP(OPACITY(GROUP))``.  ``mask`` is None or the mask's own tree, a list of
+    plane indices and ``Group``s: it is painted on a transparent canvas of its own, reduced to luminance times alpha per pixel,
+    and multiplies the group after the clip: ``MASK(CLIP(OPACITY(GROUP)))``.  Only ``mask_program`` takes a tree with masks."""
 
-    __slots__ = ("children", "opacity", "clip")
+    __slots__ = ("children", "opacity", "clip", "mask")
 
-    def __init__(self, children, opacity=None, clip=None):
+    def __init__(self, children, opacity=None, clip=None, mask=None):
         self.children, self.opacity, self.clip = list(children), opacity, (None if clip is None else list(clip))
+        self.mask = None if mask is None else list(mask)
 
     def __repr__(self):
-        return f"Group({self.children!r}, opacity={self.opacity!r}, clip={self.clip!r})"
+        mask = "" if self.mask is None else f", mask={self.mask!r}"
+        return f"Group({self.children!r}, opacity={self.opacity!r}, clip={self.clip!r}{mask})"
 
 
 class Groups(NamedTuple):
@@ -910,6 +914,8 @@ def group_program(tree):
             raise TypeError("a tree is a list of plane indices and Groups")
         for child in children:
             if isinstance(child, Group):
+                if child.mask is not None:
+                    raise ValueError("a group has a mask: mask_program makes the program of such a tree, compose_masked draws it")
                 begin = len(items)
                 items.append([OP_BEGIN, -1, 0, 0])
                 walk(child.children)
@@ -1187,14 +1193,311 @@ def render_grouped_tensor(segs, m6, paints, gp, opacity, *, groups, kinds, path_
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# luminance masks: masked groups in the compositor (svgr_compose_masked_forward / _backward, csrc/svgr_mask.h)
+# ------------------------------------------------------------------------------------------------------------------------------
+OP_HOLD, OP_END_MASK = 3, 4
+
+
+def mask_program(tree):
+    """``group_program`` for a tree whose ``Group``s may have a ``mask``: the same ``Groups``, with items that may hold
+    ``{3, index of its BEGIN, opacity slot or -1, clip or -1}`` (HOLD: closes a masked group and keeps it) and
+    ``{4, index of its BEGIN, 0, 0}`` (END_MASK: closes the mask's group, which follows the HOLD at once, and composes the held
+    group through it); a BEGIN names its closer, whichever of the three it is.  A tree without masks gives ``group_program``'s
+    items.  The program goes to ``compose_masked``, not to ``compose_grouped``."""
+    items, clip_off, clip_planes, opacity = [], [0], [], []
+
+    def walk(children):
+        if isinstance(children, (Group, int, np.integer)) or not hasattr(children, "__iter__"):
+            raise TypeError("a tree is a list of plane indices and Groups")
+        for child in children:
+            if isinstance(child, Group):
+                begin = len(items)
+                items.append([OP_BEGIN, -1, 0, 0])
+                walk(child.children)
+                slot = clip = -1
+                if child.opacity is not None:
+                    slot = len(opacity)
+                    opacity.append(float(child.opacity))
+                if child.clip is not None:
+                    if len(child.clip) == 0:
+                        raise ValueError("a clip has at least one plane")
+                    clip = len(clip_off) - 1
+                    clip_planes.extend(int(p) for p in child.clip)
+                    clip_off.append(len(clip_planes))
+                items[begin][1] = len(items)
+                items.append([OP_END if child.mask is None else OP_HOLD, begin, slot, clip])
+                if child.mask is not None:
+                    begin = len(items)
+                    items.append([OP_BEGIN, -1, 0, 0])
+                    walk(child.mask)
+                    items[begin][1] = len(items)
+                    items.append([OP_END_MASK, begin, 0, 0])
+            elif isinstance(child, (int, np.integer)) and not isinstance(child, bool):
+                items.append([OP_FILL, int(child), 0, 0])
+            else:
+                raise TypeError(f"a tree holds plane indices and Groups, not {type(child).__name__}")
+
+    walk(tree)
+    return Groups(np.array(items, dtype=np.int32).reshape(-1, 4), np.array(clip_off, dtype=np.int32), np.array(clip_planes, dtype=np.int32),
+                  np.array(opacity, dtype=np.float64))
+
+
+def _mask_topology(groups, n_paths, n_opacities):
+    """``_group_topology`` for a program that may hold masked pairs, checked as svgr_compose_masked_forward checks it."""
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    out = []
+    for name, a in (("items", groups.items), ("clip_off", groups.clip_off), ("clip_planes", groups.clip_planes)):
+        if _is_tensor(a):
+            raise TypeError(f"groups.{name} stays on the host: a numpy array or a list")
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"groups.{name} holds integers, not {a.dtype}")
+        out.append(np.ascontiguousarray(a.astype(np.int64)))
+    items, clip_off, clip_planes = out
+    if items.ndim != 2 or items.shape[1] != 4 or len(items) < 1:
+        raise ValueError(f"groups.items is (n_items, 4) with at least one item, not {items.shape}")
+    if len(items) > MAX_ITEMS:
+        raise ValueError(f"a program has at most {MAX_ITEMS} items")
+    if clip_off.ndim != 1 or clip_planes.ndim != 1:
+        raise ValueError("groups.clip_off and groups.clip_planes are lists of integers")
+    depth_max = group_depth()
+    planes, slots, clips = np.zeros(n_paths, dtype=np.int64), np.zeros(n_opacities, dtype=np.int64), {}
+    stack, n_groups = [], 0   # the stack holds (index of the BEGIN, op of the closer it names)
+    rows = items.tolist()
+    for i, (op, a, slot, clip) in enumerate(rows):
+        if op == OP_FILL:
+            if not 0 <= a < n_paths:
+                raise ValueError(f"item {i}: FILL of plane {a}, not one of {n_paths}")
+            planes[a] += 1
+        elif op == OP_BEGIN:
+            if not i < a < len(rows) or rows[a][0] not in (OP_END, OP_HOLD, OP_END_MASK) or rows[a][1] != i:
+                raise ValueError(f"item {i}: BEGIN without its closer (an END, a HOLD or an END_MASK)")
+            closer, after_hold = rows[a][0], i > 0 and rows[i - 1][0] == OP_HOLD
+            if closer == OP_END_MASK and not after_hold:
+                raise ValueError(f"item {i}: the BEGIN of an END_MASK does not follow a HOLD")
+            if closer != OP_END_MASK and after_hold:
+                raise ValueError(f"item {i}: a HOLD is followed by the BEGIN of its mask's group, closed by END_MASK")
+            if closer == OP_HOLD and (a + 1 >= len(rows) or rows[a + 1][0] != OP_BEGIN):
+                raise ValueError(f"item {a}: a HOLD is followed by the BEGIN of its mask's group and is never the last item")
+            if len(stack) == depth_max:
+                raise ValueError(f"item {i}: groups nest deeper than {depth_max}")
+            stack.append((i, closer))
+            n_groups += 1
+        elif op in (OP_END, OP_HOLD, OP_END_MASK):
+            if not stack or stack[-1][0] != a:
+                raise ValueError(f"item {i}: {('END', 'HOLD', 'END_MASK')[op - OP_END]} does not close the open group")
+            if stack[-1][1] != op:
+                raise ValueError(f"item {i}: the group is closed by another op than its BEGIN names")
+            stack.pop()
+            if op == OP_END_MASK:
+                continue
+            if op == OP_HOLD and i + 1 >= len(rows):
+                raise ValueError(f"item {i}: a HOLD is never the last item")
+            if slot != -1:
+                if not 0 <= slot < n_opacities:
+                    raise ValueError(f"item {i}: opacity slot {slot}, not one of {n_opacities}")
+                slots[slot] += 1
+            if clip != -1:
+                if clip < 0 or clip in clips:
+                    raise ValueError(f"item {i}: clip {clip} is negative or used twice")
+                clips[clip] = i
+        else:
+            raise ValueError(f"item {i}: unknown op {op} (0 FILL, 1 BEGIN, 2 END, 3 HOLD, 4 END_MASK)")
+    if stack:
+        raise ValueError(f"item {stack[-1][0]}: the group is not closed")
+    if (slots != 1).any():
+        raise ValueError("every opacity slot is used by exactly one group")
+    if sorted(clips) != list(range(len(clips))):
+        raise ValueError(f"the {len(clips)} clips are numbered from 0")
+    if clips or len(clip_planes):
+        count = np.diff(clip_off)
+        if len(clip_off) != len(clips) + 1 or clip_off[0] != 0 or clip_off[-1] != len(clip_planes) or (count < 1).any():
+            raise ValueError("groups.clip_off is n_clips + 1 strictly ascending integers from 0 to the number of clip planes")
+        if ((clip_planes < 0) | (clip_planes >= n_paths)).any():
+            raise ValueError(f"a clip plane is not one of {n_paths}")
+        np.add.at(planes, clip_planes, 1)
+    if (planes != 1).any():
+        p = int(np.nonzero(planes != 1)[0][0])
+        raise ValueError(f"plane {p} is used {int(planes[p])} times: every plane is used exactly once, by a FILL or as a clip plane")
+    if len(clip_off) == 0:
+        clip_off = np.zeros(1, dtype=np.int64)
+    return (np.ascontiguousarray(items, dtype=np.int32), clip_off.astype(np.int32), clip_planes.astype(np.int32)), n_groups
+
+
+def _masked_inputs(cover, paints, gp, groups, bg, origin, dtype=None):
+    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    opacity = groups.opacity
+    if _is_tensor(opacity):
+        raise TypeError("groups.opacity is a numpy array here; compose_masked_tensor takes a tensor")
+    if isinstance(opacity, np.ndarray) and opacity.size and opacity.dtype != np.float64:
+        raise TypeError(f"groups.opacity is float64, not {opacity.dtype}")
+    try:
+        opacity = np.ascontiguousarray(opacity, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("groups.opacity is an array of doubles") from None
+    if opacity.ndim != 1:
+        raise ValueError(f"groups.opacity is (n_opacities,), not {opacity.shape}")
+    if not np.isfinite(opacity).all():
+        raise ValueError("groups.opacity must be finite")
+    gtopo, n_groups = _mask_topology(groups, len(cover), len(opacity))
+    return cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups
+
+
+def compose_masked(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=None):
+    """``compose_grouped`` with luminance masks: ``groups`` is a ``mask_program``.  A masked group is painted, multiplied by its
+    opacity and its clip as in ``compose_grouped``, and then by its mask's value: the mask's own group (fills, gradients, groups,
+    masked groups) painted on a transparent canvas and reduced per pixel to the luminance of its straight colour times its alpha,
+    as ``Layer.luminance_mask`` does (divided where alpha > 1e-4, all four channels clipped to [0, 1],
+    ``0.2125 r + 0.7154 g + 0.072 b``).  The mask's group counts as a group: towards ``group_depth()`` and in the limits.  A
+    program without masks gives ``compose_grouped``'s bits.  Everything ``compose_grouped`` refuses and every wrong pairing of
+    HOLD and END_MASK are refused before any device work."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _masked_inputs(cover, paints, gp, groups, bg, origin, dtype)
+    n_paths, rows, cols = cover.shape
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
+    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
+    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]), gtopo, n_groups, len(opacity))
+    _abi._check(ctx.lib.svgr_compose_masked_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
+    return image.download((rows, cols, 4), cover.dtype)
+
+
+def compose_masked_backward(cover, paints, gp, groups, grad_image, bg=None, origin=(0, 0)):
+    """``(grad_cover, grad_paints, grad_gp, grad_opacity)`` of ``compose_masked``, in ``compose_grouped_backward``'s form: a mask
+    has no parameter of its own; its gradient reaches the planes, paints and gradient descriptions of the fills inside it.
+
+    The mask's value has kinks, and the derivative takes one documented side at each (csrc/svgr_mask.h): the alpha threshold
+    takes the forward's branch, a clip to [0, 1] passes the gradient at 0 and at 1 (an opaque white mask still moves its paint).
+    The only division is by an alpha above 1e-4: every finite input, a mask canvas of 0 included, gives finite gradients.  No
+    atomics: the same bits on every run."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _masked_inputs(cover, paints, gp, groups, bg, origin)
+    n_paths, rows, cols = cover.shape
+    grad_image = np.asarray(grad_image)
+    if grad_image.dtype != cover.dtype:
+        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
+    if grad_image.shape != (rows, cols, 4):
+        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    n_stops, n_op = len(arrays[2]), len(opacity)
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
+    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
+    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4), (n_op,))
+    g_cover = ctx.alloc(cover.nbytes)
+    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]
+    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops, gtopo, n_groups, n_op)
+    _abi._check(ctx.lib.svgr_compose_masked_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
+    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
+    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:5]), got[5]
+
+
+@functools.lru_cache(maxsize=None)
+def _masked_function(torch):
+    class ComposeMasked(torch.autograd.Function):
+        """image = ComposeMasked.apply(planes, paints, m6, geom, stop_pos, stop_rgba, opacity, out, bg, origin, topo, gtopo, n_groups)."""
+
+        @staticmethod
+        def forward(fn, planes, paints, m6, geom, pos, rgba, opacity, out, bg, origin, topo, gtopo, n_groups):
+            ctx = _context(torch)
+            n_paths, rows, cols = (int(v) for v in planes.shape)
+            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
+            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba, opacity))
+            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
+            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]), gtopo, n_groups, int(opacity.shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, image)
+                _abi._check(ctx.lib.svgr_compose_masked_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            fn.save_for_backward(*kept)
+            fn.masked_args = (plane, bg, origin, topo, gtopo, n_groups)
+            if out is not None:
+                fn.mark_dirty(out)
+            return image
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(fn, grad):
+            kept = fn.saved_tensors
+            plane, bg, origin, topo, gtopo, n_groups = fn.masked_args
+            n_paths, rows, cols = (int(v) for v in kept[0].shape)
+            ctx = _context(torch)
+            grad = grad.contiguous()
+            if grad.data_ptr() % 16:
+                grad = grad.clone(memory_format=torch.contiguous_format)
+            grads = tuple(torch.empty_like(t) for t in kept)
+            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]), gtopo, n_groups, int(kept[6].shape[0]))
+            with _Ordered(ctx, torch):
+                b = _buffers(ctx, torch, *kept, grad, *grads)
+                _abi._check(ctx.lib.svgr_compose_masked_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            need = fn.needs_input_grad
+            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 6
+
+    return ComposeMasked
+
+
+def compose_masked_tensor(planes, paints_t, gp_t, groups, opacity_t, *, bg=None, origin=(0, 0), out=None):
+    """``compose_masked`` as a ``torch.autograd.Function``, whose backward is ``compose_masked_backward``: the arguments, the
+    checks (the program, shapes, dtypes and devices, never the values), ``out``, the stream ordering and the import-order rule are
+    ``compose_grouped_tensor``'s; ``groups`` is a ``mask_program``."""
+    torch = _torch()
+    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
+        raise TypeError("gp_t is a GradientPaints")
+    if not isinstance(groups, Groups):
+        raise TypeError("groups is a Groups")
+    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
+        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS) + (("opacity_t", opacity_t, (torch.float64,)),)
+    for name, t, kinds in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in kinds or not t.is_cuda:
+            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
+    if planes.dim() != 3 or min(planes.shape) < 1:
+        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    n_paths, rows, cols = (int(v) for v in planes.shape)
+    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
+    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
+                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
+        if tuple(t.shape) != want or n_stops < 0:
+            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
+    if opacity_t.dim() != 1:
+        raise ValueError(f"opacity_t is (n_opacities,), not {tuple(opacity_t.shape)}")
+    topo = _painted_topology(gp_t, n_paths, n_stops)
+    gtopo, n_groups = _mask_topology(groups, n_paths, int(opacity_t.shape[0]))
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    bg, origin = _compose_bg(bg), _origin(origin)
+    ctx = _context(torch)
+    for name, t, _k in named:
+        if t.device != planes.device or t.device.index != ctx.device:
+            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
+                or out.device != planes.device or out.data_ptr() % 16:
+            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
+    return _masked_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, opacity_t, out, bg, origin, topo, gtopo,
+                                         n_groups)
+
+
+def render_masked_tensor(segs, m6, paints, gp, opacity, *, groups, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
+                         flatness: float = FLATNESS):
+    """``render_grouped_tensor`` through ``compose_masked_tensor``: gradients reach the outlines, paints and gradient descriptions
+    of the fills inside a mask too.  The arguments are theirs; ``groups`` is a ``mask_program``."""
+    vp = _viewport(viewport)
+    planes = coverage_tensor(segs, m6, kinds=kinds, path_seg_off=path_seg_off, rules=rules, viewport=vp, dtype=dtype, check=check, flatness=flatness)
+    return compose_masked_tensor(planes, paints, gp, groups, opacity, bg=bg, origin=(vp[0], vp[1]))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # from a Scene to the differentiable inputs
 # ------------------------------------------------------------------------------------------------------------------------------
 class LoweredScene(NamedTuple):
     """What ``lower_scene`` makes of a ``Scene``: the inputs of ``coverage`` (``segs``, ``kinds``, ``path_seg_off``, ``rules``,
     ``m6``: one plane per fill, stroke outline and clip path, every node's own transforms baked into ``segs``, the render
     transform in every row of ``m6``), of ``compose_grouped`` (``paints``, ``gp``, ``groups``) and ``sources``: per plane
-    ``(role, Path)`` with ``role`` "fill", "stroke" or "clip" and the node's own path (a STROKE node's centre line, not its
-    outline)."""
+    ``(role, Path)`` with ``role`` "fill", "stroke", "clip" or, for a fill or stroke inside a mask's scene, "mask", and the node's
+    own path (a STROKE node's centre line, not its outline).  With ``masks=True`` ``groups`` is a ``mask_program`` and goes to
+    ``compose_masked``."""
 
     segs: object
     kinds: object
@@ -1210,7 +1513,7 @@ class LoweredScene(NamedTuple):
 _NODE_NAMES = ("FILL", "STROKE", "GROUP", "OPACITY", "CLIP", "MASK", "TRANSFORM", "FILTER", "BLEND", "MARKERS")
 
 
-def lower_scene(scene, transform=None, linear_rgb: bool = False):
+def lower_scene(scene, transform=None, linear_rgb: bool = False, *, masks: bool = False):
     """The ``LoweredScene`` of ``scene`` drawn under the render transform ``transform`` (identity by default): what
     ``svg_scene_from_filepath`` returns, as the arrays the differentiable route takes.  Host only, apart from the expansion lazy
     nodes (markers, text) and dashed strokes do themselves.
@@ -1224,8 +1527,15 @@ def lower_scene(scene, transform=None, linear_rgb: bool = False):
     fill hides its target, as in the renderer: neither gets a plane.  Solid paints are converted as the renderer converts them
     (``solid_paint``), gradients go through ``gradient_paints`` under the accumulated transform.
 
-    Refused with a ``ValueError`` that names the node, nothing is dropped silently: ``bbox_units=True`` on a CLIP or a gradient,
-    MASK, FILTER and BLEND nodes, pattern and image paints, what ``gradient_paints`` refuses, a CLIP or anything but FILL, GROUP
+    With ``masks=True`` a MASK is a masked group (``Group(..., mask=...)``) and the returned ``groups`` is a ``mask_program`` for
+    ``compose_masked``, which is why the keyword is explicit.  The mask's scene is lowered like any other, so it may hold fills,
+    strokes, gradients, opacities, clips and masks; its planes come after its target's and have the role "mask".  A CLIP that is
+    the MASK's direct target shares its level, and so does an OPACITY directly under that CLIP; any other order takes a level
+    more, and the mask's own group counts towards ``group_depth()`` like its target.  A mask scene that draws nothing hides its
+    target, as in the renderer: neither gets a plane; a target that draws nothing is dropped with its mask.
+
+    Refused with a ``ValueError`` that names the node, nothing is dropped silently: ``bbox_units=True`` on a CLIP, a MASK or a
+    gradient, MASK nodes without ``masks=True``, FILTER and BLEND nodes, pattern and image paints, what ``gradient_paints`` refuses, a CLIP or anything but FILL, GROUP
     and TRANSFORM inside a clip's scene, groups nested deeper than ``group_depth()``, and a scene that draws nothing."""
     from .geometry import _RULES, Transform, solid_paint  # noqa: PLC0415
     from .paint import is_gradient  # noqa: PLC0415
@@ -1237,6 +1547,7 @@ def lower_scene(scene, transform=None, linear_rgb: bool = False):
     render = transform if transform is not None else Transform()
     depth_max = group_depth()
     planes = []   # (path with the node's transforms applied, rule, paint, accumulated transform, role, source)
+    in_mask = [0]   # how many mask scenes the walk is inside
 
     def refuse(kind, why):
         raise ValueError(f"{_NODE_NAMES[kind]} node: {why}")
@@ -1280,33 +1591,53 @@ def lower_scene(scene, transform=None, linear_rgb: bool = False):
             if is_gradient(paint) and paint.bbox_units:
                 refuse(kind, "a gradient in objectBoundingBox units (bbox_units=True) is not supported")
             if kind == RENDER_FILL:
-                out.append(plane(args[0], acc, args[2], "fill", args[0], paint))
+                out.append(plane(args[0], acc, args[2], "mask" if in_mask[0] else "fill", args[0], paint))
             else:
-                out.append(plane(_stroked(node), acc, None, "stroke", args[0], paint))
+                out.append(plane(_stroked(node), acc, None, "mask" if in_mask[0] else "stroke", args[0], paint))
         elif kind == RENDER_GROUP:
             for child in args:
                 walk(child, acc, out, depth)
         elif kind == RENDER_TRANSFORM:
             walk(args[0], acc @ args[1], out, depth)
-        elif kind == RENDER_OPACITY or kind == RENDER_CLIP:
+        elif kind == RENDER_OPACITY or kind == RENDER_CLIP or (kind == RENDER_MASK and masks):
             if depth == depth_max:
                 refuse(kind, f"groups nest deeper than {depth_max}")
-            clip = None
-            if kind == RENDER_CLIP:
+            first = len(planes)
+            mask_scene = None
+            if kind == RENDER_MASK:
                 if args[2]:
-                    refuse(kind, "a clip in objectBoundingBox units (bbox_units=True) is not supported")
+                    refuse(kind, "a mask in objectBoundingBox units (bbox_units=True) is not supported")
+                mask_scene, node = args[1], args[0]
+            clip = None
+            if node[0] == RENDER_CLIP:   # (the node itself, or the direct target of the MASK: one level)
+                if node[1][2]:
+                    refuse(RENDER_CLIP, "a clip in objectBoundingBox units (bbox_units=True) is not supported")
                 clip = []
-                clip_planes(args[1], acc, clip)
+                clip_planes(node[1][1], acc, clip)
                 if not clip:   # (the renderer draws nothing)
                     return
-                node = args[0]
+                node = node[1][0]
             opacity = None
-            if node[0] == RENDER_OPACITY:   # (the node itself, or the direct target of the CLIP: one level)
+            if node[0] == RENDER_OPACITY and (kind == RENDER_OPACITY or clip is not None):   # (the node itself, or the direct target of the CLIP: one level)
                 opacity, node = float(node[1][1]), node[1][0]
             group = Group([], opacity, clip)
+            drawn = len(planes)
             walk(node, acc, group.children, depth + 1)
+            if mask_scene is not None:
+                if len(planes) == drawn:   # (the target draws nothing: it goes with its mask)
+                    del planes[first:]
+                    return
+                drawn, group.mask = len(planes), []
+                in_mask[0] += 1
+                walk(mask_scene, acc, group.mask, depth + 1)
+                in_mask[0] -= 1
+                if len(planes) == drawn:   # (the mask draws nothing: the renderer draws nothing)
+                    del planes[first:]
+                    return
             out.append(group)
-        elif kind in (RENDER_MASK, RENDER_FILTER, RENDER_BLEND):
+        elif kind == RENDER_MASK:
+            refuse(kind, "not supported by the differentiable route without masks: pass masks=True")
+        elif kind in (RENDER_FILTER, RENDER_BLEND):
             refuse(kind, "not supported by the differentiable route")
         else:
             raise ValueError(f"unhandled scene type: {kind}")
@@ -1336,5 +1667,6 @@ def lower_scene(scene, transform=None, linear_rgb: bool = False):
                         np.concatenate([g.m6 for g in parts]), np.concatenate([g.geom for g in parts]), np.concatenate([g.stop_pos for g in parts]),
                         np.concatenate([g.stop_rgba for g in parts]).reshape(-1, 4))
     m6 = np.tile(np.asarray(render.m6(), dtype=np.float64), (len(planes), 1))
-    return LoweredScene(segs, kinds, off, np.array([p[1] for p in planes], dtype=np.uint8), m6, np.concatenate(rows), gp, group_program(tree),
+    return LoweredScene(segs, kinds, off, np.array([p[1] for p in planes], dtype=np.uint8), m6, np.concatenate(rows), gp,
+                        mask_program(tree) if masks else group_program(tree),
                         tuple((p[4], p[5]) for p in planes))
