@@ -1,7 +1,7 @@
 // svgr_group.h -- per-pixel arithmetic of isolated groups in differentiable compositing: group opacity and clip paths on top of
 // svgr_compose.h (solid fills) and svgr_gradpaint.h (gradient fills), forward and backward, and the check of a group program.
 //
-// Plain double arithmetic for the host (tests/group_harness.cpp) and the device (k_compose_over_grouped, k_compose_vjp_grouped of
+// Plain double arithmetic for the host (tests/group_harness.cpp) and the device (k_compose_over_program, k_compose_vjp_program of
 // svgr_hip.hip), both compiled with -ffp-contract=off.  Nothing here is fused: every product and sum is rounded on its own, in the
 // order written.  DESIGN.md 7z has the derivation, tests/group_ref.py restates all of it in numpy.
 //

@@ -11017,32 +11017,75 @@ int svgr_cover_backward(svgr_ctx* ctx, const svgr_cover_desc* desc, const svgr_b
 }  // extern "C"
 
 // ======================================================================================
-// differentiable compositing: svgr_compose_forward / svgr_compose_backward (csrc/svgr_compose.h has the per-pixel arithmetic,
-// DESIGN.md 7x the derivation).  Solid fills source-over in paint order, from coverage planes and paints to an image and back.
-// New kernels beside the renderer's and the coverage kernels: none of those is involved.
-//   forward   k_compose_over       a lane per pixel: walks the paths bottom up (plane reads coalesced across the lanes, the paints
-//                                  wave-uniform) and stores the four channels as one vector
-//   backward  k_compose_vjp        a lane per pixel, at most COMPOSE_GROUPS workgroups striding over the pixels.  Walk 1 goes from
-//                                  the top path down and leaves T_p in the pixel's grad_cover slot; walk 2 goes from the bottom up,
-//                                  carries the canvas as the forward does, writes d / d m_p over T_p and reduces the four paint
-//                                  terms of every path: shuffles inside a wave (skipped where no lane of the wave is covered), the
-//                                  waves' sums in LDS for COMPOSE_CHUNK paths at a time, added in wave order into the workgroup's
-//                                  own row of partials.  No atomics.
-//             k_compose_paint_sum  a lane per (path, channel): the workgroups' partials added in workgroup order
-// No host read-back between the launches; nothing waits.
+// differentiable compositing: one compositor in four tiers, an entry pair each (DESIGN.md 7x has the scheme and the derivations)
+//   solid    svgr_compose_forward / _backward           solid fills source-over in paint order (csrc/svgr_compose.h)
+//   painted  svgr_compose_painted_forward / _backward   a fill is solid or a linear / radial gradient (csrc/svgr_gradpaint.h)
+//   grouped  svgr_compose_grouped_forward / _backward   a PROGRAM of FILL / BEGIN / END items: isolated groups with an opacity, a
+//                                                       clip mask, both or neither (csrc/svgr_group.h)
+//   masked   svgr_compose_masked_forward / _backward    the program's HOLD and END_MASK: luminance-masked groups (csrc/svgr_mask.h)
+// A tier computes what the one below computes, bit for bit, on input that does not use what it adds.  That holds because the
+// pieces below are written once and every tier's kernels are built from them:
+//   compose_px_load / _store    the four channels of a pixel as one vector
+//   wave_sum                    the fixed 32-to-1 shuffle tree
+//   ComposeIn                   the wave-uniform read-only inputs, built inside each kernel from its own restrict parameters
+//                               (uniform addresses of restrict pointers: scalar loads)
+//   compose_fill / compose_fill_through / compose_fill_vjp
+//                               a FILL in the forward, in walk 1 (T_p into the plane's slot) and in walk 2 (d / d m_p over T_p, the
+//                               4 or 14 dense terms and 5 per stop reduced over the wave into given LDS rows; nothing where no
+//                               lane of the wave is covered)
+//   compose_clip_mask / compose_clip_vjp    a clip's planes composed to one mask, and their gradient
+//   compose_sums_clear / compose_sums_flush the waves' LDS rows: added in wave order, at barriers, into the workgroup's own row of
+//                               partials; no atomics
+//   program_need, program_forward_px        the LDS slots of an item; one pixel of a program's forward
+// Kernels: a pair per tier, so that each keeps its own footprint.  k_compose_over / k_compose_vjp (solid: a leaner 4-slot layout,
+// COMPOSE_CHUNK paths between two flushes), k_compose_over_painted / k_compose_vjp_painted (a flat list of paths, the stops' rows
+// after all dense rows of a run), k_compose_over_program<T, MASKS> / k_compose_vjp_program<T, MASKS> (an item table, an item's
+// stop rows after its own dense row; MASKS is the compile-time tier: the grouped instantiation holds none of the masked one's
+// LDS, ops or walk 0).  k_compose_paint_sum (solid) and k_compose_param_sum (the others) add the workgroups' partials in
+// workgroup order.  The host tables go up as kernel ARGUMENTS (k_painted_topology, k_group_program): no copy from memory the
+// caller may free on return.  No host read-back between the launches; nothing waits.  The renderer's kernels and the coverage
+// kernels are not involved.
 // ======================================================================================
 #include "svgr_compose.h"
+#include "svgr_gradpaint.h"
+#include "svgr_group.h"
+#include "svgr_mask.h"
 
 constexpr int COMPOSE_BLOCK = 256;                  // pixels per workgroup step: a lane each, four waves
 constexpr int COMPOSE_WAVES = COMPOSE_BLOCK / 64;
-constexpr int COMPOSE_GROUPS = 512;                 // the workgroup cap of k_compose_vjp: two per CU
-constexpr int COMPOSE_CHUNK = COMPOSE_BLOCK / 4;    // paths whose sums sit in LDS between two flushes: a lane per (path, channel)
+constexpr int COMPOSE_GROUPS = 512;                 // the workgroup cap of the backward kernels: two per CU
+constexpr int COMPOSE_CHUNK = COMPOSE_BLOCK / 4;    // solid: paths whose sums sit in LDS between two flushes, a lane per (path, channel)
+constexpr int PAINTED_TOPO = 384;     // paths per k_painted_topology launch: 3 ints each, within the 4 KiB of kernel arguments
+constexpr int PAINTED_SLOTS = 1024;   // parameters of one run of paths or items in LDS, per wave (a path has at most 14 + 5 * 32 = 174)
+constexpr int GROUPED_INTS = 960;     // ints per k_group_program launch: within the 4 KiB of kernel arguments
+static_assert(GRADPAINT_DENSE + GRADPAINT_STOP * GRADPAINT_MAX_STOPS <= PAINTED_SLOTS, "a path's parameters fit one run");
+static_assert(GRADPAINT_MAX_STOPS == GRAD_MAX_STOPS, "one cap");
 
 struct ComposeBg { double c[4]; };
+struct PaintedView { long long row0, col0; unsigned cols; };
 template <class T> struct ComposePx;
 template <> struct ComposePx<float> { using type = float4; };
 template <> struct ComposePx<double> { using type = double4; };
 
+template <class T>
+__device__ __forceinline__ void compose_px_load(const T* image, size_t i, double* c) {
+    const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(image)[i];
+    c[0] = (double)v.x; c[1] = (double)v.y; c[2] = (double)v.z; c[3] = (double)v.w;
+}
+
+template <class T>
+__device__ __forceinline__ void compose_px_store(T* image, size_t i, const double* c) {
+    typename ComposePx<T>::type v;
+    v.x = (T)c[0]; v.y = (T)c[1]; v.z = (T)c[2]; v.w = (T)c[3];
+    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int d = 32; d > 0; d >>= 1) v = v + __shfl_down(v, d);
+    return v;
+}
+
+// ---- solid ----
 template <class T>
 __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over(const T* __restrict__ cover, const double* __restrict__ paints, const ComposeBg bg,
                                                                 int n_paths, size_t n_px, T* __restrict__ image) {
@@ -11051,11 +11094,12 @@ __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over(const T* __restr
     double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
 #pragma unroll 4
     for (int p = 0; p < n_paths; ++p) compose_step(C, (double)cover[(size_t)p * n_px + i], paints + 4 * (size_t)p);
-    typename ComposePx<T>::type v;
-    v.x = (T)C[0]; v.y = (T)C[1]; v.z = (T)C[2]; v.w = (T)C[3];
-    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+    compose_px_store(image, i, C);
 }
 
+// a lane per pixel, at most COMPOSE_GROUPS workgroups striding over the pixels.  Walk 1 goes from the top path down and leaves T_p
+// in the pixel's grad_cover slot; walk 2 goes from the bottom up, carries the canvas as the forward does, writes d / d m_p over
+// T_p and reduces the four paint terms of every path.
 // (through and grad_cover are the same memory for double planes: a lane reads its own T_p before it writes d / d m_p there)
 template <class T>
 __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp(const T* __restrict__ cover, const double* __restrict__ paints, const ComposeBg bg,
@@ -11079,8 +11123,7 @@ __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp(const T* __restri
                 through[at] = above;
                 above = above * compose_through((double)cover[at], paints[4 * (size_t)p + 3]);
             }
-            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
-            gi[0] = (double)v.x; gi[1] = (double)v.y; gi[2] = (double)v.z; gi[3] = (double)v.w;
+            compose_px_load(grad_image, i, gi);
         }
         double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
         for (int p0 = 0; p0 < n_paths; p0 += COMPOSE_CHUNK) {
@@ -11097,8 +11140,7 @@ __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp(const T* __restri
                 }
                 if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
                 SVGR_UNROLL
-                for (int k = 0; k < 4; ++k)
-                    for (int d = 32; d > 0; d >>= 1) t[k] = t[k] + __shfl_down(t[k], d);
+                for (int k = 0; k < 4; ++k) t[k] = wave_sum(t[k]);
                 if (lane == 0) {
                     double* s = sums[wave][p - p0];
                     s[0] = s[0] + t[0]; s[1] = s[1] + t[1]; s[2] = s[2] + t[2]; s[3] = s[3] + t[3];
@@ -11119,6 +11161,7 @@ __global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp(const T* __restri
     }
 }
 
+// a lane per (path, channel): the workgroups' partials added in workgroup order
 __global__ __launch_bounds__(64) void k_compose_paint_sum(const double* __restrict__ part, int n_groups, size_t n4, double* __restrict__ grad_paints) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (j >= n4) return;
@@ -11127,823 +11170,196 @@ __global__ __launch_bounds__(64) void k_compose_paint_sum(const double* __restri
     grad_paints[j] = s;
 }
 
-struct ComposeShape {
-    int n_paths;
-    size_t n_px, n_all, elem;   // pixels of one plane, of all planes, bytes of a plane element
-    ComposeBg bg;
-};
-
-static bool compose_aligned(const svgr_buf* b) { return ((uintptr_t)b->ptr & 15) == 0; }
-
-// Everything of a description and its two input buffers that can be wrong, and the kernels' numbers from it.
-static int compose_check(const char* entry, const svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, ComposeShape& s) {
-    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
-    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
-    constexpr int64_t kMax = (1ll << 31) - 1;
-    if (d->n_paths <= 0 || d->rows <= 0 || d->cols <= 0)
-        return fail(SVGR_E_INVALID, "%s: %lld planes of %lld x %lld pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
-    if (d->plane < 0 || d->plane >= COVER_PLANES) return fail(SVGR_E_INVALID, "%s: unknown plane type %d", entry, (int)d->plane);
-    if (d->has_bg != 0 && d->has_bg != 1) return fail(SVGR_E_INVALID, "%s: has_bg is 0 or 1, not %d", entry, (int)d->has_bg);
-    if (d->n_paths > kMax || d->rows > kMax || d->cols > kMax ||
-        (unsigned __int128)d->n_paths * (unsigned __int128)d->rows * (unsigned __int128)d->cols > (unsigned __int128)kMax)
-        return fail(SVGR_E_OVERFLOW, "%s: %lld planes of %lld x %lld pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
-    if (!cover || !paints) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    s.n_paths = (int)d->n_paths;
-    s.n_px = (size_t)d->rows * (size_t)d->cols;
-    s.n_all = s.n_px * (size_t)d->n_paths;
-    s.elem = (size_t)cover_plane_bytes(d->plane);
-    if (cover->bytes < s.n_all * s.elem || paints->bytes < (size_t)d->n_paths * 32)
-        return fail(SVGR_E_INVALID, "%s: cover or paints is too small for the description", entry);
-    for (int k = 0; k < 4; ++k) s.bg.c[k] = d->has_bg ? d->bg[k] : 0.0;
-    return 0;
-}
-
-static int compose_forward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image) {
-    static const char* entry = "svgr_compose_forward";
-    ComposeShape s;
-    if (int rc = compose_check(entry, ctx, d, cover, paints, s)) return rc;
-    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (image->bytes < s.n_px * 4 * s.elem || !compose_aligned(image))
-        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const dim3 grid = grid1(s.n_px, COMPOSE_BLOCK);
-    if (d->plane == COVER_F32)
-        SVGR_LAUNCH(k_compose_over<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths, s.n_px, (float*)image->ptr);
-    else
-        SVGR_LAUNCH(k_compose_over<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths, s.n_px, (double*)image->ptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int compose_backward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* grad_image,
-                                 svgr_buf* grad_cover, svgr_buf* grad_paints) {
-    static const char* entry = "svgr_compose_backward";
-    ComposeShape s;
-    if (int rc = compose_check(entry, ctx, d, cover, paints, s)) return rc;
-    if (!grad_image || !grad_cover || !grad_paints) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (grad_image->bytes < s.n_px * 4 * s.elem || !compose_aligned(grad_image))
-        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
-    if (grad_cover->bytes < s.n_all * s.elem || grad_paints->bytes < (size_t)s.n_paths * 32)
-        return fail(SVGR_E_INVALID, "%s: grad_cover or grad_paints is too small for the description", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const size_t steps = (s.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
-    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
-    const size_t n4 = (size_t)s.n_paths * 4;
-    // (the blocks go back at scope end by the pool's stream-order rule)
-    PoolBlock part, through;   // the workgroups' partial paint sums; float planes: the double T_p plane of walk 1
-    HIPCHK(part.alloc((size_t)groups * n4 * 8, ctx->device));
-    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n4 * 8, st));
-    if (d->plane == COVER_F32) {
-        HIPCHK(through.alloc(s.n_all * 8, ctx->device));
-        SVGR_LAUNCH(k_compose_vjp<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths,
-                    s.n_px, (const float*)grad_image->ptr, through.as<double>(), (float*)grad_cover->ptr, part.as<double>());
-    } else {
-        SVGR_LAUNCH(k_compose_vjp<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, s.bg, s.n_paths,
-                    s.n_px, (const double*)grad_image->ptr, (double*)grad_cover->ptr, (double*)grad_cover->ptr, part.as<double>());
-    }
-    SVGR_LAUNCH(k_compose_paint_sum, grid1(n4, 64), dim3(64), 0, st, (const double*)part.p, groups, n4, (double*)grad_paints->ptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" {
-int svgr_compose_block(void) { return COMPOSE_BLOCK; }
-int svgr_compose_groups(void) { return COMPOSE_GROUPS; }
-
-int svgr_compose_forward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image) {
-    return abi_guard("svgr_compose_forward", [&]() { return compose_forward_impl(ctx, desc, cover, paints, image); });
-}
-
-int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* grad_image,
-                          svgr_buf* grad_cover, svgr_buf* grad_paints) {
-    return abi_guard("svgr_compose_backward", [&]() { return compose_backward_impl(ctx, desc, cover, paints, grad_image, grad_cover, grad_paints); });
-}
-}  // extern "C"
-
-// ======================================================================================
-// gradient paints in differentiable compositing: svgr_compose_painted_forward / svgr_compose_painted_backward
-// (csrc/svgr_gradpaint.h has the per-pixel arithmetic, DESIGN.md 7y the derivation).  A path is a solid fill (kind 0, compose_step
-// as above) or the renderer's linear / one-circle radial gradient evaluated at the pixel centre.  New kernels beside the ones
-// above: those, grad_colour_user and every renderer kernel are not involved.
-//   topology  k_painted_topology     the caller's host tables go up as kernel ARGUMENTS, PAINTED_TOPO paths a launch, into one
-//                                    int4 {kind, spread, first stop, end stop} per path: no copy from memory the caller may free
-//                                    on return, and no wait
-//   forward   k_compose_over_painted a lane per pixel; the path's description, its transform, geometry and stops are wave-uniform:
-//                                    read through uniform addresses of restrict pointers (scalar loads)
-//   backward  k_compose_vjp_painted  the two walks of k_compose_vjp.  Walk 2 reduces, per path, 14 dense terms (4 paint, 6 m6,
-//                                    4 geometry) by the fixed shuffle tree, and 5 terms (position, colour) for every stop whose
-//                                    ballot over the wave is not empty.  The waves' sums sit in LDS for a run of paths whose
-//                                    parameters fit PAINTED_SLOTS, and are added in wave order, at barriers, into the workgroup's
-//                                    own row of the groups x n_params partials, n_params = 14 n_paths + 5 n_stops.  No atomics.
-//             k_compose_param_sum    a lane per parameter: the workgroups' partials added in workgroup order, stored to the five
-//                                    gradient arrays
-// ======================================================================================
-#include "svgr_gradpaint.h"
-
-constexpr int PAINTED_TOPO = 384;     // paths per k_painted_topology launch: 3 ints each, within the 4 KiB of kernel arguments
-constexpr int PAINTED_SLOTS = 1024;   // parameters of one run of paths in LDS, per wave (a path has at most 14 + 5 * 32 = 174)
-static_assert(GRADPAINT_DENSE + GRADPAINT_STOP * GRADPAINT_MAX_STOPS <= PAINTED_SLOTS, "a path's parameters fit one run");
-static_assert(GRADPAINT_MAX_STOPS == GRAD_MAX_STOPS, "one cap");
-
-struct PaintedTopo {
-    int first, n;
-    int kind_spread[PAINTED_TOPO];     // kind | spread << 8
-    int stop_off[PAINTED_TOPO + 1];
-};
-struct PaintedView { long long row0, col0; unsigned cols; };
-
-__global__ __launch_bounds__(64) void k_painted_topology(const PaintedTopo t, int4* __restrict__ desc) {
-    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (q >= t.n) return;
-    desc[t.first + q] = make_int4(t.kind_spread[q] & 255, t.kind_spread[q] >> 8, t.stop_off[q], t.stop_off[q + 1]);
-}
-
+// ---- what the painted and the program kernels share ----
+// The wave-uniform read-only inputs.  A kernel builds this from its own restrict parameters; it is never a kernel argument.
+// The painted tier has no program: items, clip_off, clip_planes and opacity are null there.
 template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_painted(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                        const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                        const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                        const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
-                                                                        int n_paths, size_t n_px, T* __restrict__ image) {
-    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
-    if (i >= n_px) return;
-    const unsigned row = (unsigned)i / vw.cols, colj = (unsigned)i - row * vw.cols;   // (n_px < 2^31)
-    double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-    for (int p = 0; p < n_paths; ++p) {
-        const int4 d = desc[p];
-        const double m = (double)cover[(size_t)p * n_px + i];
-        if (d.x == 0) {
-            compose_step(C, m, paints + 4 * (size_t)p);
-        } else {
-            double col[4];
-            GradPaintPx e;
-            gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0,
-                             vw.col0, col, e);
-            gradpaint_step(C, m, col, paints + 4 * (size_t)p);
-        }
-    }
-    typename ComposePx<T>::type v;
-    v.x = (T)C[0]; v.y = (T)C[1]; v.z = (T)C[2]; v.w = (T)C[3];
-    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
-}
-
-// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
-template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_painted(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                       const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
-                                                                       int n_paths, int n_stops, size_t n_px, const T* __restrict__ grad_image,
-                                                                       double* through, T* grad_cover, double* __restrict__ part) {
-    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
-    double* mine = part + (size_t)blockIdx.x * (n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops);
-    for (int j = threadIdx.x; j < PAINTED_SLOTS; j += COMPOSE_BLOCK) {
-        SVGR_UNROLL
-        for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
-    }
-    __syncthreads();
-    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
-        const size_t i = base + threadIdx.x;
-        const bool live = i < n_px;
-        const unsigned row = live ? (unsigned)i / vw.cols : 0u, colj = live ? (unsigned)i - row * vw.cols : 0u;
-        double gi[4] = {0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            double above = 1.0;   // T_p: what the paths above p let through
-            for (int p = n_paths - 1; p >= 0; --p) {
-                const int4 d = desc[p];
-                const size_t at = (size_t)p * n_px + i;
-                const double m = (double)cover[at];
-                double u;
-                if (d.x == 0) {
-                    u = compose_through(m, paints[4 * (size_t)p + 3]);
-                } else {
-                    double col[4];
-                    GradPaintPx e;
-                    gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj,
-                                     vw.row0, vw.col0, col, e);
-                    u = gradpaint_through(m, col, paints + 4 * (size_t)p);
-                }
-                through[at] = above;
-                above = above * u;
-            }
-            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
-            gi[0] = (double)v.x; gi[1] = (double)v.y; gi[2] = (double)v.z; gi[3] = (double)v.w;
-        }
-        double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-        int p0 = 0;
-        while (p0 < n_paths) {
-            // the run of paths p0 .. p1 - 1 whose parameters fit the LDS rows: dense terms first, then the stops' (both contiguous)
-            const int s_first = desc[p0].z;
-            int p1 = p0, used = 0;
-            while (p1 < n_paths) {
-                const int4 d = desc[p1];
-                const int need = GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
-                if (used + need > PAINTED_SLOTS) break;
-                used += need;
-                ++p1;
-            }
-            const int nd = GRADPAINT_DENSE * (p1 - p0);
-            for (int p = p0; p < p1; ++p) {
-                const int4 d = desc[p];
-                const double* paint = paints + 4 * (size_t)p;
-                double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
-                int used_lo = -1, used_hi = -1;
-                if (live) {
-                    const size_t at = (size_t)p * n_px + i;
-                    m = (double)cover[at];
-                    if (d.x == 0) {
-                        const double dm = compose_vjp_step(C, through[at], gi, m, paint, dense);
-                        grad_cover[at] = (T)dm;
-                        compose_step(C, m, paint);
-                    } else {
-                        double col[4], P[4], t[4];
-                        GradPaintPx e;
-                        const double* g4 = geoms + 4 * (size_t)p;
-                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, g4, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0, vw.col0,
-                                         col, e);
-                        gradpaint_effective(col, paint, P);
-                        const double dm = compose_vjp_step(C, through[at], gi, m, P, t);
-                        grad_cover[at] = (T)dm;
-                        gradpaint_vjp(d.x, g4, pos + d.z, rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
-                        gradpaint_step(C, m, col, paint);
-                        used_lo = e.lo;
-                        used_hi = e.hi;
-                    }
-                }
-                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
-                double* rowd = &sums[wave][GRADPAINT_DENSE * (p - p0)];
-                if (d.x == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < 4; ++k)
-                        for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                    if (lane == 0) {
-                        SVGR_UNROLL
-                        for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
-                    }
-                    continue;
-                }
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k)
-                    for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                if (lane == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
-                }
-                const int ns = d.w - d.z;
-                for (int s = 0; s < ns; ++s) {
-                    const bool at_lo = used_lo == s, at_hi = used_hi == s;
-                    if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
-                    double v[GRADPAINT_STOP];
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_STOP; ++k) {
-                        v[k] = at_lo ? lo[k] : (at_hi ? hi[k] : 0.0);
-                        for (int q = 32; q > 0; q >>= 1) v[k] = v[k] + __shfl_down(v[k], q);
-                    }
-                    if (lane == 0) {
-                        double* rows = &sums[wave][nd + GRADPAINT_STOP * (d.z - s_first + s)];
-                        SVGR_UNROLL
-                        for (int k = 0; k < GRADPAINT_STOP; ++k) rows[k] = rows[k] + v[k];
-                    }
-                }
-            }
-            __syncthreads();
-            for (int j = threadIdx.x; j < used; j += COMPOSE_BLOCK) {
-                double s = sums[0][j];
-                SVGR_UNROLL
-                for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][j];
-                double* o = mine + (j < nd ? (size_t)GRADPAINT_DENSE * (size_t)p0 + (size_t)j
-                                           : n_dense + (size_t)GRADPAINT_STOP * (size_t)s_first + (size_t)(j - nd));
-                *o = *o + s;
-                SVGR_UNROLL
-                for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
-            }
-            __syncthreads();
-            p0 = p1;
-        }
-    }
-}
-
-// a lane per parameter: the partials in workgroup order, to the array the parameter belongs to
-__global__ __launch_bounds__(64) void k_compose_param_sum(const double* __restrict__ part, int n_groups, size_t n_dense, size_t n_params,
-                                                          double* __restrict__ g_paints, double* __restrict__ g_m6, double* __restrict__ g_geom,
-                                                          double* __restrict__ g_pos, double* __restrict__ g_rgba) {
-    const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (j >= n_params) return;
-    double s = 0.0;
-    for (int g = 0; g < n_groups; ++g) s = s + part[(size_t)g * n_params + j];
-    if (j < n_dense) {
-        const size_t p = j / GRADPAINT_DENSE;
-        const int k = (int)(j - p * GRADPAINT_DENSE);
-        if (k < 4) g_paints[4 * p + k] = s;
-        else if (k < 10) g_m6[6 * p + (k - 4)] = s;
-        else g_geom[4 * p + (k - 10)] = s;
-    } else {
-        const size_t q = (j - n_dense) / GRADPAINT_STOP;
-        const int k = (int)((j - n_dense) - q * GRADPAINT_STOP);
-        if (k == 0) g_pos[q] = s;
-        else g_rgba[4 * q + (k - 1)] = s;
-    }
-}
-
-struct PaintedShape {
-    ComposeShape c;
-    int n_stops;
+struct ComposeIn {
+    const T* cover;
+    const double* paints;
+    const int4* desc;          // {kind, spread, first stop, end stop} per path
+    const double *m6s, *geoms, *pos, *rgba;
+    const int4* items;         // {0, p, 0, 0}, {1 | 2, g, opacity slot or -1, clip or -1}, and svgr_mask.h's
+    const int *clip_off, *clip_planes;
+    const double* opacity;
     PaintedView vw;
+    size_t n_px;
 };
 
-static bool painted_has(const svgr_buf* b, size_t bytes) { return b && b->bytes >= bytes && (b->ptr || bytes == 0); }
+struct ComposeAt { size_t i; unsigned row, colj; };   // a lane's pixel
 
-// Everything of a painted description, its topology and its input buffers that can be wrong.
-static int painted_check(const char* entry, const svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints,
-                         const svgr_buf* m6, const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, PaintedShape& s) {
-    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
-    svgr_compose_desc cd;
-    cd.n_paths = d->n_paths; cd.rows = d->rows; cd.cols = d->cols; cd.plane = d->plane; cd.has_bg = d->has_bg;
-    for (int k = 0; k < 4; ++k) cd.bg[k] = d->bg[k];
-    if (int rc = compose_check(entry, ctx, &cd, cover, paints, s.c)) return rc;
-    const int64_t n = d->n_paths;
-    if (!d->kind || !d->spread || !d->path_stop_off) return fail(SVGR_E_INVALID, "%s: a topology table is NULL", entry);
-    if (d->n_stops < 0 || d->n_stops > n * GRADPAINT_MAX_STOPS) return fail(SVGR_E_INVALID, "%s: %lld stops for %lld paths", entry, (long long)d->n_stops, (long long)n);
-    if (d->path_stop_off[0] != 0 || (int64_t)d->path_stop_off[n] != d->n_stops)
-        return fail(SVGR_E_INVALID, "%s: path_stop_off goes from %d to %d, not from 0 to %lld", entry, (int)d->path_stop_off[0], (int)d->path_stop_off[n], (long long)d->n_stops);
-    for (int64_t p = 0; p < n; ++p) {
-        const int32_t kind = d->kind[p], spread = d->spread[p];
-        const int64_t ns = (int64_t)d->path_stop_off[p + 1] - (int64_t)d->path_stop_off[p];
-        if (kind < 0 || kind > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown kind %d (0 solid, 1 linear, 2 radial)", entry, (long long)p, (int)kind);
-        if (spread < 0 || spread > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown spread %d", entry, (long long)p, (int)spread);
-        if (ns < 0) return fail(SVGR_E_INVALID, "%s: path_stop_off decreases at path %lld", entry, (long long)p);
-        if (kind == 0 && ns != 0) return fail(SVGR_E_INVALID, "%s: the solid path %lld has %lld stops", entry, (long long)p, (long long)ns);
-        if (kind != 0 && (ns < 1 || ns > GRADPAINT_MAX_STOPS))
-            return fail(SVGR_E_INVALID, "%s: the gradient path %lld has %lld stops: 1 to %d", entry, (long long)p, (long long)ns, GRADPAINT_MAX_STOPS);
-    }
-    const size_t np = (size_t)n, nst = (size_t)d->n_stops;
-    if (!painted_has(m6, np * 48) || !painted_has(geom, np * 32) || !m6->ptr || !geom->ptr)
-        return fail(SVGR_E_INVALID, "%s: paint_m6 or paint_geom is missing or too small for the description", entry);
-    if (nst && (!painted_has(stop_pos, nst * 8) || !painted_has(stop_rgba, nst * 32)))
-        return fail(SVGR_E_INVALID, "%s: stop_pos or stop_rgba is missing or too small for the description", entry);
-    s.n_stops = (int)d->n_stops;
-    s.vw.row0 = (long long)d->row0;
-    s.vw.col0 = (long long)d->col0;
-    s.vw.cols = (unsigned)d->cols;
-    return 0;
+__device__ __forceinline__ ComposeAt compose_at(const PaintedView vw, size_t i, bool live) {   // (n_px < 2^31)
+    ComposeAt px;
+    px.i = i;
+    px.row = live ? (unsigned)i / vw.cols : 0u;
+    px.colj = live ? (unsigned)i - px.row * vw.cols : 0u;
+    return px;
 }
 
-// the topology tables into the device block, by kernel arguments
-static int painted_topology(const svgr_painted_desc* d, int n_paths, int4* desc, hipStream_t st) {
-    PaintedTopo t;
-    for (int first = 0; first < n_paths; first += PAINTED_TOPO) {
-        t.first = first;
-        t.n = std::min(PAINTED_TOPO, n_paths - first);
-        for (int q = 0; q < t.n; ++q) {
-            t.kind_spread[q] = (int)d->kind[first + q] | ((int)d->spread[first + q] << 8);
-            t.stop_off[q] = (int)d->path_stop_off[first + q];
-        }
-        t.stop_off[t.n] = (int)d->path_stop_off[first + t.n];
-        for (int q = t.n; q < PAINTED_TOPO; ++q) { t.kind_spread[q] = 0; t.stop_off[q + 1] = 0; }
-        SVGR_LAUNCH(k_painted_topology, grid1((size_t)t.n, 64), dim3(64), 0, st, t, desc);
-    }
-    return 0;
-}
-
-static const double* painted_ptr(const svgr_buf* b) { return b ? (const double*)b->ptr : nullptr; }
-
-static int painted_forward_impl(svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                                const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image) {
-    static const char* entry = "svgr_compose_painted_forward";
-    PaintedShape s;
-    if (int rc = painted_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, s)) return rc;
-    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (image->bytes < s.c.n_px * 4 * s.c.elem || !compose_aligned(image))
-        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    PoolBlock topo;   // (goes back at scope end by the pool's stream-order rule)
-    HIPCHK(topo.alloc((size_t)s.c.n_paths * sizeof(int4), ctx->device));
-    if (int rc = painted_topology(d, s.c.n_paths, topo.as<int4>(), st)) return rc;
-    const dim3 grid = grid1(s.c.n_px, COMPOSE_BLOCK);
-    if (d->plane == COVER_F32)
-        SVGR_LAUNCH(k_compose_over_painted<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.c.n_px, (float*)image->ptr);
-    else
-        SVGR_LAUNCH(k_compose_over_painted<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.c.n_px, (double*)image->ptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int painted_backward_impl(svgr_ctx* ctx, const svgr_painted_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                                 const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
-                                 svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
-                                 svgr_buf* grad_stop_rgba) {
-    static const char* entry = "svgr_compose_painted_backward";
-    PaintedShape s;
-    if (int rc = painted_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, s)) return rc;
-    if (!grad_image || !grad_cover || !grad_paints || !grad_m6 || !grad_geom) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (grad_image->bytes < s.c.n_px * 4 * s.c.elem || !compose_aligned(grad_image))
-        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
-    const size_t np = (size_t)s.c.n_paths, nst = (size_t)s.n_stops;
-    if (grad_cover->bytes < s.c.n_all * s.c.elem || grad_paints->bytes < np * 32 || grad_m6->bytes < np * 48 || grad_geom->bytes < np * 32)
-        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is too small for the description", entry);
-    if (nst && (!painted_has(grad_stop_pos, nst * 8) || !painted_has(grad_stop_rgba, nst * 32)))
-        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const size_t steps = (s.c.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
-    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
-    const size_t n_dense = np * GRADPAINT_DENSE, n_params = n_dense + nst * GRADPAINT_STOP;
-    // (the blocks go back at scope end by the pool's stream-order rule)
-    PoolBlock topo, part, through;   // the paths' descriptions; the workgroups' partial sums; float planes: the double T_p plane of walk 1
-    HIPCHK(topo.alloc(np * sizeof(int4), ctx->device));
-    HIPCHK(part.alloc((size_t)groups * n_params * 8, ctx->device));
-    if (d->plane == COVER_F32) HIPCHK(through.alloc(s.c.n_all * 8, ctx->device));
-    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n_params * 8, st));
-    if (int rc = painted_topology(d, s.c.n_paths, topo.as<int4>(), st)) return rc;
-    if (d->plane == COVER_F32) {
-        SVGR_LAUNCH(k_compose_vjp_painted<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.n_stops,
-                    s.c.n_px, (const float*)grad_image->ptr, through.as<double>(), (float*)grad_cover->ptr, part.as<double>());
-    } else {
-        SVGR_LAUNCH(k_compose_vjp_painted<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), s.c.bg, s.vw, s.c.n_paths, s.n_stops,
-                    s.c.n_px, (const double*)grad_image->ptr, (double*)grad_cover->ptr, (double*)grad_cover->ptr, part.as<double>());
-    }
-    SVGR_LAUNCH(k_compose_param_sum, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_params, (double*)grad_paints->ptr,
-                (double*)grad_m6->ptr, (double*)grad_geom->ptr, nst ? (double*)grad_stop_pos->ptr : nullptr, nst ? (double*)grad_stop_rgba->ptr : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" {
-int svgr_compose_painted_forward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
-                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image) {
-    return abi_guard("svgr_compose_painted_forward",
-                     [&]() { return painted_forward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, image); });
-}
-
-int svgr_compose_painted_backward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
-                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
-                                  svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
-                                  svgr_buf* grad_stop_rgba) {
-    return abi_guard("svgr_compose_painted_backward", [&]() {
-        return painted_backward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, grad_image, grad_cover, grad_paints, grad_m6,
-                                     grad_geom, grad_stop_pos, grad_stop_rgba);
-    });
-}
-}  // extern "C"
-
-// ======================================================================================
-// isolated groups in differentiable compositing: svgr_compose_grouped_forward / svgr_compose_grouped_backward
-// (csrc/svgr_group.h has the per-pixel arithmetic and the program's check, DESIGN.md 7z the derivation).  The painted compositor
-// above with a PROGRAM of FILL / BEGIN / END items instead of a flat list of paths: a group has an opacity, a clip mask of its own
-// coverage planes, both or neither.  New kernels beside the ones above, which are not involved.
-//   program   k_group_program         the checked program (items in the kernels' form, clip_off, clip_planes: one table of ints) goes
-//                                     up as kernel ARGUMENTS, GROUPED_INTS a launch: no copy from the caller's memory, no wait
-//   forward   k_compose_over_grouped  a lane per pixel.  The canvas of the open level is in registers; the canvases below it sit in
-//                                     LDS, a column per lane, indexed by the wave-uniform level: no private array, no scratch
-//   backward  k_compose_vjp_grouped   the two walks of svgr_group.h.  Walk 1 needs no stack (T_end is a plane per group in memory).
-//                                     Walk 2 keeps canvas and base adjoint of the open level in registers and those below in LDS.
-//                                     Parameter sums as in k_compose_vjp_painted: shuffle tree, per-wave LDS rows for a run of ITEMS
-//                                     whose parameters fit PAINTED_SLOTS, workgroup partials; an opacity is one more slot after the
-//                                     stops: n_params = 14 n_paths + 5 n_stops + n_opacities.  No atomics.
-//             k_compose_param_sum_grouped   k_compose_param_sum with the opacities
-// Program, paint descriptions and opacities are wave-uniform and read through uniform addresses of restrict pointers.
-// ======================================================================================
-#include "svgr_group.h"
-
-constexpr int GROUPED_INTS = 960;   // ints per k_group_program launch: within the 4 KiB of kernel arguments
-
-struct GroupSlice {
-    int first, n;
-    int v[GROUPED_INTS];
-};
-
-__global__ __launch_bounds__(64) void k_group_program(const GroupSlice t, int* __restrict__ table) {
-    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (q >= t.n) return;
-    table[t.first + q] = t.v[q];
-}
-
-struct GroupedProgram {
-    const int4* items;        // {0, p, 0, 0}, {1 | 2, g, opacity slot or -1, clip or -1}
-    const int* clip_off;
-    const int* clip_planes;
-    int n_items;
-};
-
+// the colour of gradient path p, d its description, at the pixel
 template <class T>
-__device__ __forceinline__ double grouped_mask(const T* __restrict__ cover, const int* __restrict__ clip_off, const int* __restrict__ clip_planes, int clip,
-                                               size_t n_px, size_t i) {
+__device__ __forceinline__ void compose_fill_colour(const ComposeIn<T>& in, int p, const int4 d, const ComposeAt px, double* col, GradPaintPx& e) {
+    gradpaint_colour(d.x, d.y, in.m6s + 6 * (size_t)p, in.geoms + 4 * (size_t)p, d.w - d.z, in.pos + d.z, in.rgba + 4 * (size_t)d.z, px.row, px.colj,
+                     in.vw.row0, in.vw.col0, col, e);
+}
+
+// forward: path p over the canvas X
+template <class T>
+__device__ __forceinline__ void compose_fill(const ComposeIn<T>& in, int p, const ComposeAt px, double* X) {
+    const int4 d = in.desc[p];
+    const double m = (double)in.cover[(size_t)p * in.n_px + px.i];
+    if (d.x == 0) {
+        compose_step(X, m, in.paints + 4 * (size_t)p);
+    } else {
+        double col[4];
+        GradPaintPx e;
+        compose_fill_colour(in, p, d, px, col, e);
+        gradpaint_step(X, m, col, in.paints + 4 * (size_t)p);
+    }
+}
+
+// walk 1: parks `above` (T_p) in the plane's slot and returns what path p lets through
+template <class T>
+__device__ __forceinline__ double compose_fill_through(const ComposeIn<T>& in, int p, const ComposeAt px, double above, double* through) {
+    const int4 d = in.desc[p];
+    const size_t at = (size_t)p * in.n_px + px.i;
+    const double m = (double)in.cover[at];
+    double u;
+    if (d.x == 0) {
+        u = compose_through(m, in.paints[4 * (size_t)p + 3]);
+    } else {
+        double col[4];
+        GradPaintPx e;
+        compose_fill_colour(in, p, d, px, col, e);
+        u = gradpaint_through(m, col, in.paints + 4 * (size_t)p);
+    }
+    through[at] = above;
+    return u;
+}
+
+// walk 2: d / d m_p over T_p, path p over the canvas X, and the path's terms summed over the wave into rowd (4 for a solid
+// path, GRADPAINT_DENSE for a gradient) and rows (GRADPAINT_STOP per stop, only the stops some lane of the wave used).  B is
+// the adjoint of X.  Nothing is added where no lane of the wave is covered.
+template <class T>
+__device__ __forceinline__ void compose_fill_vjp(const ComposeIn<T>& in, int p, const int4 d, bool live, const ComposeAt px, const double* through,
+                                                 T* grad_cover, double* X, const double* B, int lane, double* rowd, double* rows) {
+    const double* paint = in.paints + 4 * (size_t)p;
+    double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
+    SVGR_UNROLL
+    for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
+    SVGR_UNROLL
+    for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
+    int used_lo = -1, used_hi = -1;
+    if (live) {
+        const size_t at = (size_t)p * in.n_px + px.i;
+        m = (double)in.cover[at];
+        if (d.x == 0) {
+            const double dm = compose_vjp_step(X, through[at], B, m, paint, dense);
+            grad_cover[at] = (T)dm;
+            compose_step(X, m, paint);
+        } else {
+            double col[4], P[4], t[4];
+            GradPaintPx e;
+            compose_fill_colour(in, p, d, px, col, e);
+            gradpaint_effective(col, paint, P);
+            const double dm = compose_vjp_step(X, through[at], B, m, P, t);
+            grad_cover[at] = (T)dm;
+            gradpaint_vjp(d.x, in.geoms + 4 * (size_t)p, in.pos + d.z, in.rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
+            gradpaint_step(X, m, col, paint);
+            used_lo = e.lo;
+            used_hi = e.hi;
+        }
+    }
+    if (__ballot(m != 0.0) == 0ull) return;   // (the same in every lane of the wave; a lane past the end has m == 0)
+    if (d.x == 0) {
+        SVGR_UNROLL
+        for (int k = 0; k < 4; ++k) dense[k] = wave_sum(dense[k]);
+        if (lane == 0) {
+            SVGR_UNROLL
+            for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
+        }
+        return;
+    }
+    SVGR_UNROLL
+    for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = wave_sum(dense[k]);
+    if (lane == 0) {
+        SVGR_UNROLL
+        for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
+    }
+    const int ns = d.w - d.z;
+    for (int s = 0; s < ns; ++s) {
+        const bool at_lo = used_lo == s, at_hi = used_hi == s;
+        if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
+        double v[GRADPAINT_STOP];
+        SVGR_UNROLL
+        for (int k = 0; k < GRADPAINT_STOP; ++k) v[k] = wave_sum(at_lo ? lo[k] : (at_hi ? hi[k] : 0.0));
+        if (lane == 0) {
+            SVGR_UNROLL
+            for (int k = 0; k < GRADPAINT_STOP; ++k) rows[GRADPAINT_STOP * s + k] = rows[GRADPAINT_STOP * s + k] + v[k];
+        }
+    }
+}
+
+// the mask of clip `clip`: its planes composed OVER in one channel; 1 without a clip
+template <class T>
+__device__ __forceinline__ double compose_clip_mask(const ComposeIn<T>& in, int clip, size_t i) {
     if (clip < 0) return 1.0;
-    const int a0 = clip_off[clip], a1 = clip_off[clip + 1];
+    const int a0 = in.clip_off[clip], a1 = in.clip_off[clip + 1];
     double k = 0.0;
-    for (int a = a0; a < a1; ++a) k = group_mask_step(k, (double)cover[(size_t)clip_planes[a] * n_px + i], a == a0);
+    for (int a = a0; a < a1; ++a) k = group_mask_step(k, (double)in.cover[(size_t)in.clip_planes[a] * in.n_px + i], a == a0);
     return k;
 }
 
+// walk 2 at the closer of a clipped group: d / d m of every clip plane from dk = d / d k, the planes' suffix products parked in
+// their own slots as T_p is.  Returns the mask.
 template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_grouped(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                        const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                        const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                        const double* __restrict__ rgba, const int4* __restrict__ items,
-                                                                        const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
-                                                                        const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
-                                                                        int n_items, size_t n_px, T* __restrict__ image) {
-    __shared__ double below[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the canvases under the open level, a column per lane
-    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
-    if (i >= n_px) return;   // (no barrier below: a lane reads its own column only)
-    const unsigned row = (unsigned)i / vw.cols, colj = (unsigned)i - row * vw.cols;   // (n_px < 2^31)
-    double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-    int level = 0;
-    for (int q = 0; q < n_items; ++q) {
-        const int4 it = items[q];
-        if (it.x == GROUP_FILL) {
-            const int p = it.y;
-            const int4 d = desc[p];
-            const double m = (double)cover[(size_t)p * n_px + i];
-            if (d.x == 0) {
-                compose_step(X, m, paints + 4 * (size_t)p);
-            } else {
-                double col[4];
-                GradPaintPx e;
-                gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0,
-                                 vw.col0, col, e);
-                gradpaint_step(X, m, col, paints + 4 * (size_t)p);
-            }
-        } else if (it.x == GROUP_BEGIN) {
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                below[level][c][threadIdx.x] = X[c];
-                X[c] = 0.0;
-            }
-            ++level;
-        } else {
-            --level;
-            const double o = it.z < 0 ? 1.0 : opacity[it.z];
-            const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-            const double G[4] = {X[0], X[1], X[2], X[3]};
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) X[c] = below[level][c][threadIdx.x];
-            group_step(X, G, o, k);
-        }
+__device__ __forceinline__ double compose_clip_vjp(const ComposeIn<T>& in, int clip, size_t i, double dk, double* through, T* grad_cover) {
+    if (clip < 0) return 1.0;
+    const int a0 = in.clip_off[clip], a1 = in.clip_off[clip + 1];
+    double suffix = 1.0;
+    for (int a = a1 - 1; a >= a0; --a) {
+        const size_t at = (size_t)in.clip_planes[a] * in.n_px + i;
+        through[at] = suffix;
+        suffix = suffix * (1.0 - (double)in.cover[at]);
     }
-    typename ComposePx<T>::type v;
-    v.x = (T)X[0]; v.y = (T)X[1]; v.z = (T)X[2]; v.w = (T)X[3];
-    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
+    double k = 0.0;
+    for (int a = a0; a < a1; ++a) {
+        const size_t at = (size_t)in.clip_planes[a] * in.n_px + i;
+        const double dm = group_clip_vjp(dk, a == a0, k, through[at]);
+        grad_cover[at] = (T)dm;
+        k = group_mask_step(k, (double)in.cover[at], a == a0);
+    }
+    return k;
 }
 
-// the LDS slots an item's parameters take in a run: a FILL's 14 dense terms and 5 per stop, an END's opacity
-__device__ __forceinline__ int grouped_need(const int4 it, const int4* __restrict__ desc) {
-    if (it.x == GROUP_FILL) {
-        const int4 d = desc[it.y];
-        return GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
-    }
-    return it.x == GROUP_END && it.z >= 0 ? 1 : 0;
-}
-
-// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
-template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_grouped(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                       const double* __restrict__ rgba, const int4* __restrict__ items,
-                                                                       const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
-                                                                       const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
-                                                                       int n_items, int n_paths, int n_stops, int n_opacities, size_t n_px,
-                                                                       const T* __restrict__ grad_image, double* through, T* grad_cover,
-                                                                       double* __restrict__ t_end, double* __restrict__ part) {
-    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
-    __shared__ double below[GROUP_DEPTH][8][COMPOSE_BLOCK];   // canvas and base adjoint of the levels under the open one, a column per lane
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
-    const size_t n_stop_end = n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops;
-    double* mine = part + (size_t)blockIdx.x * (n_stop_end + (size_t)n_opacities);
+// the waves' LDS rows of parameter sums, PAINTED_SLOTS each
+__device__ __forceinline__ void compose_sums_clear(double (*sums)[PAINTED_SLOTS]) {
     for (int j = threadIdx.x; j < PAINTED_SLOTS; j += COMPOSE_BLOCK) {
         SVGR_UNROLL
         for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
     }
-    __syncthreads();
-    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
-        const size_t i = base + threadIdx.x;
-        const bool live = i < n_px;
-        const unsigned row = live ? (unsigned)i / vw.cols : 0u, colj = live ? (unsigned)i - row * vw.cols : 0u;
-        double B[4] = {0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            double above = 1.0;
-            for (int q = n_items - 1; q >= 0; --q) {
-                const int4 it = items[q];
-                if (it.x == GROUP_FILL) {
-                    const int p = it.y;
-                    const int4 d = desc[p];
-                    const size_t at = (size_t)p * n_px + i;
-                    const double m = (double)cover[at];
-                    double u;
-                    if (d.x == 0) {
-                        u = compose_through(m, paints[4 * (size_t)p + 3]);
-                    } else {
-                        double col[4];
-                        GradPaintPx e;
-                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj,
-                                         vw.row0, vw.col0, col, e);
-                        u = gradpaint_through(m, col, paints + 4 * (size_t)p);
-                    }
-                    through[at] = above;
-                    above = above * u;
-                } else if (it.x == GROUP_END) {
-                    t_end[(size_t)it.y * n_px + i] = above;
-                    above = 1.0;
-                } else {
-                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                    const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-                    const double u = group_through(above, o, k);
-                    above = t_end[(size_t)it.y * n_px + i] * u;
-                }
-            }
-            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
-            B[0] = (double)v.x; B[1] = (double)v.y; B[2] = (double)v.z; B[3] = (double)v.w;
-        }
-        double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-        int level = 0;
-        int q0 = 0;
-        while (q0 < n_items) {
-            // the run of items q0 .. q1 - 1 whose parameters fit the LDS rows, each item's slots after the one before
-            int q1 = q0, used = 0;
-            while (q1 < n_items) {
-                const int need = grouped_need(items[q1], desc);
-                if (used + need > PAINTED_SLOTS) break;
-                used += need;
-                ++q1;
-            }
-            int slot = 0;
-            for (int q = q0; q < q1; ++q) {
-                const int4 it = items[q];
-                double* rowd = &sums[wave][slot];
-                slot += grouped_need(it, desc);
-                if (it.x == GROUP_BEGIN) {
-                    if (live) {
-                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                        const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-                        double adj[4];
-                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            below[level][c][threadIdx.x] = X[c];
-                            below[level][4 + c][threadIdx.x] = B[c];
-                            X[c] = 0.0;
-                        }
-                        group_base(adj, o, k, B);
-                    }
-                    ++level;
-                    continue;
-                }
-                if (it.x == GROUP_END) {
-                    --level;
-                    double term = 0.0;
-                    if (live) {
-                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                        const double G[4] = {X[0], X[1], X[2], X[3]};
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            X[c] = below[level][c][threadIdx.x];
-                            B[c] = below[level][4 + c][threadIdx.x];
-                        }
-                        double adj[4];
-                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
-                        const double qd = compose_dot(adj, G);
-                        const double dk = qd * o;
-                        double k = 1.0;
-                        if (it.w >= 0) {
-                            const int a0 = clip_off[it.w], a1 = clip_off[it.w + 1];
-                            double suffix = 1.0;   // parked in the planes' own slots, as T_p is
-                            for (int a = a1 - 1; a >= a0; --a) {
-                                const size_t at = (size_t)clip_planes[a] * n_px + i;
-                                through[at] = suffix;
-                                suffix = suffix * (1.0 - (double)cover[at]);
-                            }
-                            k = 0.0;
-                            for (int a = a0; a < a1; ++a) {
-                                const size_t at = (size_t)clip_planes[a] * n_px + i;
-                                const double dm = group_clip_vjp(dk, a == a0, k, through[at]);
-                                grad_cover[at] = (T)dm;
-                                k = group_mask_step(k, (double)cover[at], a == a0);
-                            }
-                        }
-                        term = qd * k;
-                        group_step(X, G, o, k);
-                    }
-                    if (it.z >= 0) {
-                        for (int s = 32; s > 0; s >>= 1) term = term + __shfl_down(term, s);
-                        if (lane == 0) rowd[0] = rowd[0] + term;
-                    }
-                    continue;
-                }
-                const int p = it.y;
-                const int4 d = desc[p];
-                const double* paint = paints + 4 * (size_t)p;
-                double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
-                int used_lo = -1, used_hi = -1;
-                if (live) {
-                    const size_t at = (size_t)p * n_px + i;
-                    m = (double)cover[at];
-                    if (d.x == 0) {
-                        const double dm = compose_vjp_step(X, through[at], B, m, paint, dense);
-                        grad_cover[at] = (T)dm;
-                        compose_step(X, m, paint);
-                    } else {
-                        double col[4], P[4], t[4];
-                        GradPaintPx e;
-                        const double* g4 = geoms + 4 * (size_t)p;
-                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, g4, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0, vw.col0,
-                                         col, e);
-                        gradpaint_effective(col, paint, P);
-                        const double dm = compose_vjp_step(X, through[at], B, m, P, t);
-                        grad_cover[at] = (T)dm;
-                        gradpaint_vjp(d.x, g4, pos + d.z, rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
-                        gradpaint_step(X, m, col, paint);
-                        used_lo = e.lo;
-                        used_hi = e.hi;
-                    }
-                }
-                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
-                if (d.x == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < 4; ++k)
-                        for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                    if (lane == 0) {
-                        SVGR_UNROLL
-                        for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
-                    }
-                    continue;
-                }
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k)
-                    for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                if (lane == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
-                }
-                const int ns = d.w - d.z;
-                for (int s = 0; s < ns; ++s) {
-                    const bool at_lo = used_lo == s, at_hi = used_hi == s;
-                    if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
-                    double v[GRADPAINT_STOP];
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_STOP; ++k) {
-                        v[k] = at_lo ? lo[k] : (at_hi ? hi[k] : 0.0);
-                        for (int r = 32; r > 0; r >>= 1) v[k] = v[k] + __shfl_down(v[k], r);
-                    }
-                    if (lane == 0) {
-                        double* rows = rowd + GRADPAINT_DENSE + GRADPAINT_STOP * s;
-                        SVGR_UNROLL
-                        for (int k = 0; k < GRADPAINT_STOP; ++k) rows[k] = rows[k] + v[k];
-                    }
-                }
-            }
-            __syncthreads();
-            slot = 0;
-            for (int q = q0; q < q1; ++q) {
-                const int4 it = items[q];
-                const int need = grouped_need(it, desc);
-                if (need == 0) continue;
-                size_t dense_at, stop_at = 0;   // where the item's first GRADPAINT_DENSE slots and the ones after them go
-                if (it.x == GROUP_FILL) {
-                    dense_at = (size_t)GRADPAINT_DENSE * (size_t)it.y;
-                    stop_at = n_dense + (size_t)GRADPAINT_STOP * (size_t)desc[it.y].z;
-                } else {
-                    dense_at = n_stop_end + (size_t)it.z;
-                }
-                for (int j = threadIdx.x; j < need; j += COMPOSE_BLOCK) {
-                    double s = sums[0][slot + j];
-                    SVGR_UNROLL
-                    for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][slot + j];
-                    double* o = mine + (j < GRADPAINT_DENSE ? dense_at + (size_t)j : stop_at + (size_t)(j - GRADPAINT_DENSE));
-                    *o = *o + s;
-                    SVGR_UNROLL
-                    for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][slot + j] = 0.0;
-                }
-                slot += need;
-            }
-            __syncthreads();
-            q0 = q1;
-        }
+}
+
+// (between two barriers) slots slot .. slot + need - 1, added in wave order and cleared: the first `split` of them go to
+// mine[first_at ..], the others to mine[rest_at ..]
+__device__ __forceinline__ void compose_sums_flush(double (*sums)[PAINTED_SLOTS], int slot, int need, int split, double* mine, size_t first_at,
+                                                   size_t rest_at) {
+    for (int j = threadIdx.x; j < need; j += COMPOSE_BLOCK) {
+        double s = sums[0][slot + j];
+        SVGR_UNROLL
+        for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][slot + j];
+        double* o = mine + (j < split ? first_at + (size_t)j : rest_at + (size_t)(j - split));
+        *o = *o + s;
+        SVGR_UNROLL
+        for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][slot + j] = 0.0;
     }
 }
 
-// a lane per parameter: the partials in workgroup order, to the array the parameter belongs to
-__global__ __launch_bounds__(64) void k_compose_param_sum_grouped(const double* __restrict__ part, int n_groups, size_t n_dense, size_t n_stop_end,
-                                                                  size_t n_params, double* __restrict__ g_paints, double* __restrict__ g_m6,
-                                                                  double* __restrict__ g_geom, double* __restrict__ g_pos, double* __restrict__ g_rgba,
-                                                                  double* __restrict__ g_opacity) {
+// a lane per parameter: the workgroups' partials added in workgroup order, stored to the array the parameter belongs to.  The
+// parameters are 14 per path, then 5 per stop, then (from n_stop_end on; the painted tier has none) one per opacity.
+__global__ __launch_bounds__(64) void k_compose_param_sum(const double* __restrict__ part, int n_groups, size_t n_dense, size_t n_stop_end, size_t n_params,
+                                                          double* __restrict__ g_paints, double* __restrict__ g_m6, double* __restrict__ g_geom,
+                                                          double* __restrict__ g_pos, double* __restrict__ g_rgba, double* __restrict__ g_opacity) {
     const size_t j = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (j >= n_params) return;
     double s = 0.0;
@@ -11964,54 +11380,603 @@ __global__ __launch_bounds__(64) void k_compose_param_sum_grouped(const double* 
     }
 }
 
-struct GroupedShape {
-    PaintedShape p;
-    int n_items, n_groups, n_opacities, n_clips, n_clip_planes;
-    std::vector<int> table;   // items in the kernels' form, clip_off, clip_planes
+// ---- painted: a flat list of paths ----
+struct PaintedTopo {
+    int first, n;
+    int kind_spread[PAINTED_TOPO];     // kind | spread << 8
+    int stop_off[PAINTED_TOPO + 1];
 };
 
-// Everything of a grouped description that can be wrong, and the program's table.
-static int grouped_check(const char* entry, const svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints,
-                         const svgr_buf* m6, const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
-                         GroupedShape& s) {
+__global__ __launch_bounds__(64) void k_painted_topology(const PaintedTopo t, int4* __restrict__ desc) {
+    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (q >= t.n) return;
+    desc[t.first + q] = make_int4(t.kind_spread[q] & 255, t.kind_spread[q] >> 8, t.stop_off[q], t.stop_off[q + 1]);
+}
+
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_painted(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                        const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                        const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                        const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
+                                                                        int n_paths, size_t n_px, T* __restrict__ image) {
+    const ComposeIn<T> in = {cover, paints, desc, m6s, geoms, pos, rgba, nullptr, nullptr, nullptr, nullptr, vw, n_px};
+    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
+    if (i >= n_px) return;
+    const ComposeAt px = compose_at(vw, i, true);
+    double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+    for (int p = 0; p < n_paths; ++p) compose_fill(in, p, px, C);
+    compose_px_store(image, i, C);
+}
+
+// The two walks of k_compose_vjp.  The waves' sums sit in LDS for a run of paths whose parameters fit PAINTED_SLOTS: the paths'
+// dense rows first, then their stops' rows (both contiguous in the partials: n_params = 14 n_paths + 5 n_stops).
+// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
+template <class T>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_painted(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                       const double* __restrict__ rgba, const ComposeBg bg, const PaintedView vw,
+                                                                       int n_paths, int n_stops, size_t n_px, const T* __restrict__ grad_image,
+                                                                       double* through, T* grad_cover, double* __restrict__ part) {
+    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
+    const ComposeIn<T> in = {cover, paints, desc, m6s, geoms, pos, rgba, nullptr, nullptr, nullptr, nullptr, vw, n_px};
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
+    double* mine = part + (size_t)blockIdx.x * (n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops);
+    compose_sums_clear(sums);
+    __syncthreads();
+    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const bool live = i < n_px;
+        const ComposeAt px = compose_at(vw, i, live);
+        double gi[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            double above = 1.0;   // T_p: what the paths above p let through
+            for (int p = n_paths - 1; p >= 0; --p) above = above * compose_fill_through(in, p, px, above, through);
+            compose_px_load(grad_image, i, gi);
+        }
+        double C[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+        int p0 = 0;
+        while (p0 < n_paths) {
+            // the run of paths p0 .. p1 - 1 whose parameters fit the LDS rows
+            const int s_first = desc[p0].z;
+            int p1 = p0, used = 0;
+            while (p1 < n_paths) {
+                const int4 d = desc[p1];
+                const int need = GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
+                if (used + need > PAINTED_SLOTS) break;
+                used += need;
+                ++p1;
+            }
+            const int nd = GRADPAINT_DENSE * (p1 - p0);
+            for (int p = p0; p < p1; ++p) {
+                const int4 d = desc[p];
+                compose_fill_vjp(in, p, d, live, px, through, grad_cover, C, gi, lane, &sums[wave][GRADPAINT_DENSE * (p - p0)],
+                                 &sums[wave][nd + GRADPAINT_STOP * (d.z - s_first)]);
+            }
+            __syncthreads();
+            compose_sums_flush(sums, 0, used, nd, mine, (size_t)GRADPAINT_DENSE * (size_t)p0, n_dense + (size_t)GRADPAINT_STOP * (size_t)s_first);
+            __syncthreads();
+            p0 = p1;
+        }
+    }
+}
+
+// ---- grouped and masked: a program of items; MASKS is the tier ----
+// The canvas of the open level is in registers; the levels below it sit in LDS, a column per lane, indexed by the wave-uniform
+// level: no private array, no scratch.  The masked tier adds the held group H = (G o) k_clip of the pair open on a level, in LDS
+// too, and the mask canvas M of every pair parked in four planes of the call's scratch, as T_end is parked per group: walk 1
+// needs k_mask and walk 2 d k / d M before either arrives at the mask group.
+struct GroupSlice {
+    int first, n;
+    int v[GROUPED_INTS];
+};
+
+__global__ __launch_bounds__(64) void k_group_program(const GroupSlice t, int* __restrict__ table) {
+    const int q = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (q >= t.n) return;
+    table[t.first + q] = t.v[q];
+}
+
+struct GroupedProgram {
+    const int4* items;        // in the kernels' form (svgr_group.h, svgr_mask.h)
+    const int* clip_off;
+    const int* clip_planes;
+    int n_items;
+};
+
+template <bool MASKS>
+__device__ __forceinline__ int program_op(int x) {
+    if constexpr (MASKS) return mask_op(x);
+    else return x;
+}
+
+// the LDS slots an item's parameters take in a run: a FILL's 14 dense terms and 5 per stop, the opacity of an END or a HOLD
+template <bool MASKS>
+__device__ __forceinline__ int program_need(const int4 it, const int4* __restrict__ desc) {
+    const int op = program_op<MASKS>(it.x);
+    if (op == GROUP_FILL) {
+        const int4 d = desc[it.y];
+        return GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
+    }
+    return (op == GROUP_END || (MASKS && op == MASK_HOLD)) && it.z >= 0 ? 1 : 0;
+}
+
+// level `level` of a lane's column: the canvas X goes below and a transparent one opens / X comes back.  Walk 2 keeps the
+// canvas' adjoint B in the column's rows 4 .. 7.
+template <int BELOW>
+__device__ __forceinline__ void program_push(double (*below)[BELOW][COMPOSE_BLOCK], int level, double* X) {
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) {
+        below[level][c][threadIdx.x] = X[c];
+        X[c] = 0.0;
+    }
+}
+
+template <int BELOW>
+__device__ __forceinline__ void program_pop(double (*below)[BELOW][COMPOSE_BLOCK], int level, double* X) {
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) X[c] = below[level][c][threadIdx.x];
+}
+
+__device__ __forceinline__ void program_push_adjoint(double (*below)[8][COMPOSE_BLOCK], int level, double* X, const double* B) {
+    program_push(below, level, X);
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) below[level][4 + c][threadIdx.x] = B[c];
+}
+
+__device__ __forceinline__ void program_pop_adjoint(double (*below)[8][COMPOSE_BLOCK], int level, double* X, double* B) {
+    program_pop(below, level, X);
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) B[c] = below[level][4 + c][threadIdx.x];
+}
+
+// M of a pair from its four planes
+__device__ __forceinline__ void masked_parked(const double* park, int pair, size_t n_px, size_t i, double* M) {
+    const size_t at = (size_t)pair * 4 * n_px + i;
+    SVGR_UNROLL
+    for (int c = 0; c < 4; ++c) M[c] = park[at + (size_t)c * n_px];
+}
+
+// one pixel of the forward over items[0 .. n_run): X is the root canvas on entry and on return.  below has BELOW rows per level
+// (the canvas in the first four).  Masked tier only: held, and park, which if not null gets M of every pair (walk 0).
+template <class T, bool MASKS, int BELOW>
+__device__ __forceinline__ void program_forward_px(const ComposeIn<T>& in, int n_run, const ComposeAt px, double (*below)[BELOW][COMPOSE_BLOCK],
+                                                   double (*held)[4][COMPOSE_BLOCK], double* park, double* X) {
+    int level = 0;
+    for (int q = 0; q < n_run; ++q) {
+        const int4 it = in.items[q];
+        const int op = program_op<MASKS>(it.x);
+        // (how the op chains of this template read: a `MASKS && ...` arm is dead in the grouped instantiation; a `!MASKS || ...` arm
+        // is the grouped tier's catch-all, its last op; what follows it, under `if constexpr (MASKS)`, exists in the masked one only)
+        if (op == GROUP_FILL) {
+            compose_fill(in, it.y, px, X);
+        } else if (op == GROUP_BEGIN || (MASKS && (op == MASK_BEGIN_HELD || op == MASK_BEGIN_MASK))) {
+            program_push(below, level, X);
+            ++level;
+        } else if (!MASKS || op == GROUP_END) {   // (grouped: whatever is left is an END)
+            --level;
+            const double o = it.z < 0 ? 1.0 : in.opacity[it.z];
+            const double k = compose_clip_mask(in, it.w, px.i);
+            const double G[4] = {X[0], X[1], X[2], X[3]};
+            program_pop(below, level, X);
+            group_step(X, G, o, k);
+        } else if constexpr (MASKS) {
+            --level;
+            if (op == MASK_HOLD) {
+                const double o = it.z < 0 ? 1.0 : in.opacity[it.z];
+                const double k = compose_clip_mask(in, it.w, px.i);
+                double H[4];
+                mask_hold(X, o, k, H);
+                SVGR_UNROLL
+                for (int c = 0; c < 4; ++c) held[level][c][threadIdx.x] = H[c];
+                program_pop(below, level, X);
+            } else {   // MASK_END
+                const double M[4] = {X[0], X[1], X[2], X[3]};
+                if (park) {
+                    const size_t at = (size_t)mask_pair(it.x) * 4 * in.n_px + px.i;
+                    SVGR_UNROLL
+                    for (int c = 0; c < 4; ++c) park[at + (size_t)c * in.n_px] = M[c];
+                }
+                double H[4];
+                program_pop(below, level, X);
+                SVGR_UNROLL
+                for (int c = 0; c < 4; ++c) H[c] = held[level][c][threadIdx.x];
+                mask_step(X, H, mask_value(M));
+            }
+        }
+    }
+}
+
+template <class T, bool MASKS>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_program(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                        const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                        const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                        const double* __restrict__ rgba, const int4* __restrict__ items,
+                                                                        const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
+                                                                        const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
+                                                                        int n_items, size_t n_px, T* __restrict__ image) {
+    __shared__ double below[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the canvases under the open level, a column per lane
+    double (*held)[4][COMPOSE_BLOCK] = nullptr;
+    if constexpr (MASKS) {
+        __shared__ double held_lds[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the held group of the pair open on a level
+        held = held_lds;
+    }
+    const ComposeIn<T> in = {cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_px};
+    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
+    if (i >= n_px) return;   // (no barrier below: a lane reads its own column only)
+    double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+    program_forward_px<T, MASKS, 4>(in, n_items, compose_at(vw, i, true), below, held, nullptr, X);
+    compose_px_store(image, i, X);
+}
+
+// The two walks of svgr_group.h and svgr_mask.h.  Walk 1 needs no stack (T_end is a plane per group in memory).  Walk 2 keeps
+// canvas and base adjoint of the open level in registers and those below in LDS.  Parameter sums as in k_compose_vjp_painted, for a
+// run of ITEMS whose parameters fit PAINTED_SLOTS, each item's slots after the one before; an opacity is one more slot after
+// the stops: n_params = 14 n_paths + 5 n_stops + n_opacities.  Masked tier: walk 0 is the forward over the first n_walk0 items
+// (to the last END_MASK) and parks M of every pair; a program without pairs skips it and takes the grouped steps: the same bits.
+// The grouped tier passes n_walk0 = 0 and no park.
+// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
+template <class T, bool MASKS>
+__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_program(const T* __restrict__ cover, const double* __restrict__ paints,
+                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
+                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
+                                                                       const double* __restrict__ rgba, const int4* __restrict__ items,
+                                                                       const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
+                                                                       const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
+                                                                       int n_items, int n_walk0, int n_paths, int n_stops, int n_opacities, size_t n_px,
+                                                                       const T* __restrict__ grad_image, double* through, T* grad_cover,
+                                                                       double* __restrict__ t_end, double* park, double* __restrict__ part) {
+    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
+    __shared__ double below[GROUP_DEPTH][8][COMPOSE_BLOCK];   // canvas and base adjoint of the levels under the open one, a column per lane
+    double (*held)[4][COMPOSE_BLOCK] = nullptr;
+    if constexpr (MASKS) {
+        __shared__ double held_lds[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the held group of the pair open on a level
+        held = held_lds;
+    }
+    const ComposeIn<T> in = {cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_px};
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
+    const size_t n_stop_end = n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops;
+    double* mine = part + (size_t)blockIdx.x * (n_stop_end + (size_t)n_opacities);
+    compose_sums_clear(sums);
+    __syncthreads();
+    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
+        const size_t i = base + threadIdx.x;
+        const bool live = i < n_px;
+        const ComposeAt px = compose_at(vw, i, live);
+        double B[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            if constexpr (MASKS) {
+                if (n_walk0 > 0) {   // walk 0: the lane reads back below only what it parks here itself
+                    double X0[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+                    program_forward_px<T, true, 8>(in, n_walk0, px, below, held, park, X0);
+                }
+            }
+            double above = 1.0;
+            for (int q = n_items - 1; q >= 0; --q) {
+                const int4 it = items[q];
+                const int op = program_op<MASKS>(it.x);
+                if (op == GROUP_FILL) {
+                    above = above * compose_fill_through(in, it.y, px, above, through);
+                } else if (op == GROUP_END) {
+                    t_end[(size_t)it.y * n_px + i] = above;
+                    above = 1.0;
+                } else if (MASKS && op == MASK_END) {
+                    t_end[(size_t)it.z * n_px + i] = above;   // (of the pair's target)
+                    above = 1.0;
+                } else if (MASKS && op == MASK_HOLD) {
+                    above = 1.0;
+                } else if (!MASKS || op == GROUP_BEGIN) {   // (grouped: whatever is left is a BEGIN; the MASKS arms above are dead there)
+                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                    const double k = compose_clip_mask(in, it.w, i);
+                    const double u = group_through(above, o, k);
+                    above = t_end[(size_t)it.y * n_px + i] * u;
+                } else if constexpr (MASKS) {
+                    if (op == MASK_BEGIN_HELD) {
+                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                        const double k = compose_clip_mask(in, it.w, i);
+                        double M[4];
+                        masked_parked(park, mask_pair(it.x), n_px, i, M);
+                        const double u = mask_through(above, o, k, mask_value(M));
+                        above = t_end[(size_t)it.y * n_px + i] * u;
+                    }   // (the BEGIN of a mask group: nothing carries over)
+                }
+            }
+            compose_px_load(grad_image, i, B);
+        }
+        double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
+        [[maybe_unused]] double qok = 0.0;   // masked tier: from a HOLD to the BEGIN after it
+        int level = 0;
+        int q0 = 0;
+        while (q0 < n_items) {
+            // the run of items q0 .. q1 - 1 whose parameters fit the LDS rows
+            int q1 = q0, used = 0;
+            while (q1 < n_items) {
+                const int need = program_need<MASKS>(items[q1], desc);
+                if (used + need > PAINTED_SLOTS) break;
+                used += need;
+                ++q1;
+            }
+            int slot = 0;
+            for (int q = q0; q < q1; ++q) {
+                const int4 it = items[q];
+                const int op = program_op<MASKS>(it.x);
+                double* rowd = &sums[wave][slot];
+                slot += program_need<MASKS>(it, desc);
+                // (grouped: FILL, BEGIN and END, the first three arms with their `MASKS &&` parts dead; the last arm is masked only)
+                if (op == GROUP_FILL) {
+                    compose_fill_vjp(in, it.y, desc[it.y], live, px, through, grad_cover, X, B, lane, rowd, rowd + GRADPAINT_DENSE);
+                } else if (op == GROUP_BEGIN || (MASKS && op == MASK_BEGIN_HELD)) {
+                    if (live) {
+                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                        const double k = compose_clip_mask(in, it.w, i);
+                        double adj[4];
+                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
+                        program_push_adjoint(below, level, X, B);
+                        if (!MASKS || op == GROUP_BEGIN) {   // (grouped: always)
+                            group_base(adj, o, k, B);
+                        } else if constexpr (MASKS) {
+                            double M[4];
+                            masked_parked(park, mask_pair(it.x), n_px, i, M);
+                            mask_base(adj, o, k, mask_value(M), B);
+                        }
+                    }
+                    ++level;
+                } else if (op == GROUP_END || (MASKS && op == MASK_HOLD)) {
+                    --level;
+                    const bool hold = MASKS && op == MASK_HOLD;
+                    double term = 0.0;
+                    if (live) {
+                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
+                        const double G[4] = {X[0], X[1], X[2], X[3]};
+                        program_pop_adjoint(below, level, X, B);
+                        double adj[4];
+                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
+                        const double qd = compose_dot(adj, G);
+                        double km = 1.0;
+                        if constexpr (MASKS) {
+                            if (hold) {
+                                double M[4];
+                                masked_parked(park, mask_pair(it.x), n_px, i, M);
+                                km = mask_value(M);
+                            }
+                        }
+                        const double k = compose_clip_vjp(in, it.w, i, hold ? mask_clip_term(qd, o, km) : qd * o, through, grad_cover);
+                        if (!hold) {
+                            term = qd * k;
+                            group_step(X, G, o, k);
+                        } else if constexpr (MASKS) {
+                            term = mask_opacity_term(qd, k, km);
+                            qok = mask_held_dot(qd, o, k);
+                            double H[4];
+                            mask_hold(G, o, k, H);
+                            SVGR_UNROLL
+                            for (int c = 0; c < 4; ++c) held[level][c][threadIdx.x] = H[c];
+                        }
+                    }
+                    if (it.z >= 0) {
+                        term = wave_sum(term);
+                        if (lane == 0) rowd[0] = rowd[0] + term;
+                    }
+                } else if constexpr (MASKS) {
+                    if (op == MASK_BEGIN_MASK) {
+                        if (live) {
+                            double M[4];
+                            masked_parked(park, mask_pair(it.x), n_px, i, M);
+                            program_push_adjoint(below, level, X, B);
+                            mask_base_of_mask(qok, M, B);
+                        }
+                        ++level;
+                    } else {   // MASK_END
+                        --level;
+                        if (live) {
+                            double M[4], H[4];
+                            masked_parked(park, mask_pair(it.x), n_px, i, M);
+                            program_pop_adjoint(below, level, X, B);
+                            SVGR_UNROLL
+                            for (int c = 0; c < 4; ++c) H[c] = held[level][c][threadIdx.x];
+                            mask_step(X, H, mask_value(M));
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            slot = 0;
+            for (int q = q0; q < q1; ++q) {
+                const int4 it = items[q];
+                const int need = program_need<MASKS>(it, desc);
+                if (need == 0) continue;
+                // a FILL's dense terms and its stops' terms, or the opacity of an END or a HOLD
+                if (program_op<MASKS>(it.x) == GROUP_FILL)
+                    compose_sums_flush(sums, slot, need, GRADPAINT_DENSE, mine, (size_t)GRADPAINT_DENSE * (size_t)it.y,
+                                       n_dense + (size_t)GRADPAINT_STOP * (size_t)desc[it.y].z);
+                else
+                    compose_sums_flush(sums, slot, need, GRADPAINT_DENSE, mine, n_stop_end + (size_t)it.z, 0);
+                slot += need;
+            }
+            __syncthreads();
+            q0 = q1;
+        }
+    }
+}
+
+// ---- host: one checked description, one forward and one backward path ----
+enum ComposeTier { TIER_SOLID, TIER_PAINTED, TIER_GROUPED, TIER_MASKED };
+
+// The device buffers of a call: the inputs, the forward's output, the backward's.  A tier leaves what it does not take NULL, and
+// nothing looks at it.
+struct ComposeBufs {
+    const svgr_buf *cover, *paints, *m6, *geom, *stop_pos, *stop_rgba, *opacity;
+    svgr_buf* image;
+    const svgr_buf* grad_image;
+    svgr_buf *grad_cover, *grad_paints, *grad_m6, *grad_geom, *grad_stop_pos, *grad_stop_rgba, *grad_opacity;
+};
+
+// A checked description and the kernels' numbers from it: every tier fills what it has.
+struct ComposeShape {
+    int n_paths, plane;
+    size_t n_px, n_all, elem;   // pixels of one plane, of all planes, bytes of a plane element
+    ComposeBg bg;
+    int n_stops = 0;            // painted and above: the stops, the view, the caller's topology tables
+    PaintedView vw;
+    const int32_t *kind, *spread, *path_stop_off;
+    int n_items = 0, n_groups = 0, n_opacities = 0, n_clips = 0;   // grouped and above
+    std::vector<int> table;     // items in the kernels' form, clip_off, clip_planes
+    int n_pairs = 0, n_walk0 = 0;   // masked: the pairs; the items walk 0 runs: to the last END_MASK
+};
+
+static bool compose_aligned(const svgr_buf* b) { return ((uintptr_t)b->ptr & 15) == 0; }
+static bool painted_has(const svgr_buf* b, size_t bytes) { return b && b->bytes >= bytes && (b->ptr || bytes == 0); }
+static const double* painted_ptr(const svgr_buf* b) { return b ? (const double*)b->ptr : nullptr; }
+
+// Everything of a description, its host tables and its input buffers that can be wrong, in the order solid, painted, program.
+// The description's type says which of these it has; tier tells a masked program from a grouped one.
+template <class Desc>
+static int compose_check(ComposeTier tier, const char* entry, const svgr_ctx* ctx, const Desc* d, const ComposeBufs& b, ComposeShape& s) {
+    constexpr bool kPainted = !std::is_same_v<Desc, svgr_compose_desc>, kProgram = std::is_same_v<Desc, svgr_grouped_desc>;
+    if (kPainted && !d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);   // (the solid entries name a NULL ctx first)
+    if (!ctx) return fail(SVGR_E_INVALID, "%s: ctx is NULL", entry);
     if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
-    svgr_painted_desc pd;
-    pd.n_paths = d->n_paths; pd.rows = d->rows; pd.cols = d->cols; pd.plane = d->plane; pd.has_bg = d->has_bg;
-    for (int k = 0; k < 4; ++k) pd.bg[k] = d->bg[k];
-    pd.row0 = d->row0; pd.col0 = d->col0; pd.n_stops = d->n_stops;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_check(entry, ctx, &pd, cover, paints, m6, geom, stop_pos, stop_rgba, s.p)) return rc;
     constexpr int64_t kMax = (1ll << 31) - 1;
-    if (d->n_groups < 0 || d->n_groups > kMax || d->n_items < 0 || d->n_items > kMax || d->n_opacities < 0 || d->n_clip_planes < 0)
-        return fail(SVGR_E_INVALID, "%s: %lld items, %lld groups, %lld opacities, %lld clip planes", entry, (long long)d->n_items, (long long)d->n_groups,
-                    (long long)d->n_opacities, (long long)d->n_clip_planes);
-    if (d->n_groups > d->n_items) return fail(SVGR_E_INVALID, "%s: %lld groups in %lld items", entry, (long long)d->n_groups, (long long)d->n_items);
-    if (d->n_items > GROUP_MAX_ITEMS) return fail(SVGR_E_OVERFLOW, "%s: %lld items are beyond %d", entry, (long long)d->n_items, GROUP_MAX_ITEMS);
-    std::vector<int> seen((size_t)d->n_paths + (size_t)d->n_groups + (size_t)std::min(d->n_opacities, d->n_groups) + 1);
-    s.table.assign(4 * (size_t)d->n_items, 0);
-    long long at = -1;
-    int n_clips = 0;
-    if (const char* what = group_program_check(d->items, d->n_items, d->n_paths, d->n_groups, d->n_clip_planes, d->n_opacities, d->clip_off, d->clip_planes,
-                                               seen.data(), s.table.data(), &n_clips, &at))
-        return fail(SVGR_E_INVALID, "%s: the program is wrong: %s (at %lld)", entry, what, at);
-    if ((unsigned __int128)d->n_groups * (unsigned __int128)s.p.c.n_px > (unsigned __int128)kMax)
-        return fail(SVGR_E_OVERFLOW, "%s: %lld groups of %zu pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_groups, s.p.c.n_px);
-    if (d->n_opacities && (!painted_has(opacity, (size_t)d->n_opacities * 8) || !opacity->ptr))
-        return fail(SVGR_E_INVALID, "%s: opacity is missing or too small for the description", entry);
-    s.n_items = (int)d->n_items;
-    s.n_groups = (int)d->n_groups;
-    s.n_opacities = (int)d->n_opacities;
-    s.n_clips = n_clips;
-    s.n_clip_planes = (int)d->n_clip_planes;
-    if (n_clips) {
-        s.table.insert(s.table.end(), d->clip_off, d->clip_off + n_clips + 1);
-        s.table.insert(s.table.end(), d->clip_planes, d->clip_planes + d->n_clip_planes);
+    if (d->n_paths <= 0 || d->rows <= 0 || d->cols <= 0)
+        return fail(SVGR_E_INVALID, "%s: %lld planes of %lld x %lld pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
+    if (d->plane < 0 || d->plane >= COVER_PLANES) return fail(SVGR_E_INVALID, "%s: unknown plane type %d", entry, (int)d->plane);
+    if (d->has_bg != 0 && d->has_bg != 1) return fail(SVGR_E_INVALID, "%s: has_bg is 0 or 1, not %d", entry, (int)d->has_bg);
+    if (d->n_paths > kMax || d->rows > kMax || d->cols > kMax ||
+        (unsigned __int128)d->n_paths * (unsigned __int128)d->rows * (unsigned __int128)d->cols > (unsigned __int128)kMax)
+        return fail(SVGR_E_OVERFLOW, "%s: %lld planes of %lld x %lld pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_paths, (long long)d->rows, (long long)d->cols);
+    if (!b.cover || !b.paints) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    const int64_t n = d->n_paths;
+    s.n_paths = (int)n;
+    s.plane = (int)d->plane;
+    s.n_px = (size_t)d->rows * (size_t)d->cols;
+    s.n_all = s.n_px * (size_t)n;
+    s.elem = (size_t)cover_plane_bytes(d->plane);
+    if (b.cover->bytes < s.n_all * s.elem || b.paints->bytes < (size_t)n * 32)
+        return fail(SVGR_E_INVALID, "%s: cover or paints is too small for the description", entry);
+    for (int k = 0; k < 4; ++k) s.bg.c[k] = d->has_bg ? d->bg[k] : 0.0;
+    if constexpr (kPainted) {
+        if (!d->kind || !d->spread || !d->path_stop_off) return fail(SVGR_E_INVALID, "%s: a topology table is NULL", entry);
+        if (d->n_stops < 0 || d->n_stops > n * GRADPAINT_MAX_STOPS) return fail(SVGR_E_INVALID, "%s: %lld stops for %lld paths", entry, (long long)d->n_stops, (long long)n);
+        if (d->path_stop_off[0] != 0 || (int64_t)d->path_stop_off[n] != d->n_stops)
+            return fail(SVGR_E_INVALID, "%s: path_stop_off goes from %d to %d, not from 0 to %lld", entry, (int)d->path_stop_off[0], (int)d->path_stop_off[n], (long long)d->n_stops);
+        for (int64_t p = 0; p < n; ++p) {
+            const int32_t kind = d->kind[p], spread = d->spread[p];
+            const int64_t ns = (int64_t)d->path_stop_off[p + 1] - (int64_t)d->path_stop_off[p];
+            if (kind < 0 || kind > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown kind %d (0 solid, 1 linear, 2 radial)", entry, (long long)p, (int)kind);
+            if (spread < 0 || spread > 2) return fail(SVGR_E_INVALID, "%s: path %lld has the unknown spread %d", entry, (long long)p, (int)spread);
+            if (ns < 0) return fail(SVGR_E_INVALID, "%s: path_stop_off decreases at path %lld", entry, (long long)p);
+            if (kind == 0 && ns != 0) return fail(SVGR_E_INVALID, "%s: the solid path %lld has %lld stops", entry, (long long)p, (long long)ns);
+            if (kind != 0 && (ns < 1 || ns > GRADPAINT_MAX_STOPS))
+                return fail(SVGR_E_INVALID, "%s: the gradient path %lld has %lld stops: 1 to %d", entry, (long long)p, (long long)ns, GRADPAINT_MAX_STOPS);
+        }
+        const size_t np = (size_t)n, nst = (size_t)d->n_stops;
+        if (!painted_has(b.m6, np * 48) || !painted_has(b.geom, np * 32) || !b.m6->ptr || !b.geom->ptr)
+            return fail(SVGR_E_INVALID, "%s: paint_m6 or paint_geom is missing or too small for the description", entry);
+        if (nst && (!painted_has(b.stop_pos, nst * 8) || !painted_has(b.stop_rgba, nst * 32)))
+            return fail(SVGR_E_INVALID, "%s: stop_pos or stop_rgba is missing or too small for the description", entry);
+        s.n_stops = (int)d->n_stops;
+        s.vw.row0 = (long long)d->row0;
+        s.vw.col0 = (long long)d->col0;
+        s.vw.cols = (unsigned)d->cols;
+        s.kind = d->kind;
+        s.spread = d->spread;
+        s.path_stop_off = d->path_stop_off;
+    }
+    if constexpr (kProgram) {
+        if (d->n_groups < 0 || d->n_groups > kMax || d->n_items < 0 || d->n_items > kMax || d->n_opacities < 0 || d->n_clip_planes < 0)
+            return fail(SVGR_E_INVALID, "%s: %lld items, %lld groups, %lld opacities, %lld clip planes", entry, (long long)d->n_items, (long long)d->n_groups,
+                        (long long)d->n_opacities, (long long)d->n_clip_planes);
+        if (d->n_groups > d->n_items) return fail(SVGR_E_INVALID, "%s: %lld groups in %lld items", entry, (long long)d->n_groups, (long long)d->n_items);
+        if (d->n_items > GROUP_MAX_ITEMS) return fail(SVGR_E_OVERFLOW, "%s: %lld items are beyond %d", entry, (long long)d->n_items, GROUP_MAX_ITEMS);
+        std::vector<int> seen((size_t)d->n_paths + (size_t)d->n_groups + (size_t)std::min(d->n_opacities, d->n_groups) + 1);
+        s.table.assign(4 * (size_t)d->n_items, 0);
+        long long at = -1;
+        int last_mask = -1;
+        const char* what = tier == TIER_MASKED
+                               ? mask_program_check(d->items, d->n_items, d->n_paths, d->n_groups, d->n_clip_planes, d->n_opacities, d->clip_off, d->clip_planes,
+                                                    seen.data(), s.table.data(), &s.n_clips, &s.n_pairs, &last_mask, &at)
+                               : group_program_check(d->items, d->n_items, d->n_paths, d->n_groups, d->n_clip_planes, d->n_opacities, d->clip_off, d->clip_planes,
+                                                     seen.data(), s.table.data(), &s.n_clips, &at);
+        if (what) return fail(SVGR_E_INVALID, "%s: the program is wrong: %s (at %lld)", entry, what, at);
+        // (T_end is a plane per group; this bounds walk 0's planes too: a pair is two groups and parks four planes)
+        if ((unsigned __int128)d->n_groups * (unsigned __int128)s.n_px > (unsigned __int128)kMax)
+            return fail(SVGR_E_OVERFLOW, "%s: %lld groups of %zu pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_groups, s.n_px);
+        if (d->n_opacities && (!painted_has(b.opacity, (size_t)d->n_opacities * 8) || !b.opacity->ptr))
+            return fail(SVGR_E_INVALID, "%s: opacity is missing or too small for the description", entry);
+        s.n_items = (int)d->n_items;
+        s.n_groups = (int)d->n_groups;
+        s.n_opacities = (int)d->n_opacities;
+        s.n_walk0 = last_mask + 1;
+        if (s.n_clips) {
+            s.table.insert(s.table.end(), d->clip_off, d->clip_off + s.n_clips + 1);
+            s.table.insert(s.table.end(), d->clip_planes, d->clip_planes + d->n_clip_planes);
+        }
     }
     return 0;
 }
 
+// the forward's output
+static int compose_image_check(const char* entry, const ComposeShape& s, const svgr_buf* image) {
+    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (image->bytes < s.n_px * 4 * s.elem || !compose_aligned(image))
+        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
+    return 0;
+}
+
+// the backward's gradient image and outputs.  (The program tiers also refuse an output without memory, and say so.)
+static int compose_grads_check(ComposeTier tier, const char* entry, const ComposeShape& s, const ComposeBufs& b) {
+    const bool painted = tier != TIER_SOLID, program = tier == TIER_GROUPED || tier == TIER_MASKED;
+    if (!b.grad_image || !b.grad_cover || !b.grad_paints || (painted && (!b.grad_m6 || !b.grad_geom)))
+        return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
+    if (b.grad_image->bytes < s.n_px * 4 * s.elem || !compose_aligned(b.grad_image))
+        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
+    const size_t np = (size_t)s.n_paths, nst = (size_t)s.n_stops, nop = (size_t)s.n_opacities;
+    bool bad = b.grad_cover->bytes < s.n_all * s.elem || b.grad_paints->bytes < np * 32;
+    if (!painted) return bad ? fail(SVGR_E_INVALID, "%s: grad_cover or grad_paints is too small for the description", entry) : 0;
+    bad = bad || b.grad_m6->bytes < np * 48 || b.grad_geom->bytes < np * 32;
+    if (program) bad = bad || !b.grad_cover->ptr || !b.grad_paints->ptr || !b.grad_m6->ptr || !b.grad_geom->ptr;
+    if (bad)
+        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is %stoo small for the description", entry, program ? "missing or " : "");
+    if (nst && (!painted_has(b.grad_stop_pos, nst * 8) || !painted_has(b.grad_stop_rgba, nst * 32)))
+        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
+    if (nop && (!painted_has(b.grad_opacity, nop * 8) || !b.grad_opacity->ptr))
+        return fail(SVGR_E_INVALID, "%s: grad_opacity is missing or too small for the description", entry);
+    return 0;
+}
+
+// the workgroups of a backward kernel: they stride over the pixels
+static int compose_groups(const ComposeShape& s) {
+    const size_t steps = (s.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
+    return (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
+}
+
+// the plane type of a call as a type: f(T()) with T float or double
+template <class F>
+static void compose_by_plane(int plane, F&& f) {
+    if (plane == COVER_F32) f(float());
+    else f(double());
+}
+
+// the topology tables into the device block, by kernel arguments
+static void painted_topology(const ComposeShape& s, int4* desc, hipStream_t st) {
+    PaintedTopo t;
+    for (int first = 0; first < s.n_paths; first += PAINTED_TOPO) {
+        t.first = first;
+        t.n = std::min(PAINTED_TOPO, s.n_paths - first);
+        for (int q = 0; q < t.n; ++q) {
+            t.kind_spread[q] = (int)s.kind[first + q] | ((int)s.spread[first + q] << 8);
+            t.stop_off[q] = (int)s.path_stop_off[first + q];
+        }
+        t.stop_off[t.n] = (int)s.path_stop_off[first + t.n];
+        for (int q = t.n; q < PAINTED_TOPO; ++q) { t.kind_spread[q] = 0; t.stop_off[q + 1] = 0; }
+        SVGR_LAUNCH(k_painted_topology, grid1((size_t)t.n, 64), dim3(64), 0, st, t, desc);
+    }
+}
+
 // the program's table into the device block, by kernel arguments
-static GroupedProgram grouped_program(const GroupedShape& s, int* table, hipStream_t st) {
+static GroupedProgram grouped_program(const ComposeShape& s, int* table, hipStream_t st) {
     GroupSlice t;
     const int n = (int)s.table.size();
     for (int first = 0; first < n; first += GROUPED_INTS) {
@@ -12028,691 +11993,210 @@ static GroupedProgram grouped_program(const GroupedShape& s, int* table, hipStre
     return g;
 }
 
-static int grouped_forward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                                const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
-    static const char* entry = "svgr_compose_grouped_forward";
-    GroupedShape s;
-    if (int rc = grouped_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, s)) return rc;
-    const ComposeShape& c = s.p.c;
-    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (image->bytes < c.n_px * 4 * c.elem || !compose_aligned(image))
-        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
+static int compose_forward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const ComposeBufs& b) {
+    static const char* entry = "svgr_compose_forward";
+    ComposeShape s;
+    if (int rc = compose_check(TIER_SOLID, entry, ctx, d, b, s)) return rc;
+    if (int rc = compose_image_check(entry, s, b.image)) return rc;
     HIPCHK(enter_ctx(ctx));
     hipStream_t st = ctx->stream;
-    PoolBlock topo, table;   // (go back at scope end by the pool's stream-order rule)
-    HIPCHK(topo.alloc((size_t)c.n_paths * sizeof(int4), ctx->device));
-    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
-    svgr_painted_desc pd;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
-    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
-    const dim3 grid = grid1(c.n_px, COMPOSE_BLOCK);
-    if (d->plane == COVER_F32)
-        SVGR_LAUNCH(k_compose_over_grouped<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
-                    c.bg, s.p.vw, g.n_items, c.n_px, (float*)image->ptr);
-    else
-        SVGR_LAUNCH(k_compose_over_grouped<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
-                    c.bg, s.p.vw, g.n_items, c.n_px, (double*)image->ptr);
+    compose_by_plane(s.plane, [&](auto zero) {
+        using T = decltype(zero);
+        SVGR_LAUNCH(k_compose_over<T>, grid1(s.n_px, COMPOSE_BLOCK), dim3(COMPOSE_BLOCK), 0, st, (const T*)b.cover->ptr, (const double*)b.paints->ptr, s.bg,
+                    s.n_paths, s.n_px, (T*)b.image->ptr);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-static int grouped_backward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                                 const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
-                                 const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
-                                 svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
-    static const char* entry = "svgr_compose_grouped_backward";
-    GroupedShape s;
-    if (int rc = grouped_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, s)) return rc;
-    const ComposeShape& c = s.p.c;
-    if (!grad_image || !grad_cover || !grad_paints || !grad_m6 || !grad_geom) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (grad_image->bytes < c.n_px * 4 * c.elem || !compose_aligned(grad_image))
-        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
-    const size_t np = (size_t)c.n_paths, nst = (size_t)s.p.n_stops, nop = (size_t)s.n_opacities;
-    if (grad_cover->bytes < c.n_all * c.elem || grad_paints->bytes < np * 32 || grad_m6->bytes < np * 48 || grad_geom->bytes < np * 32 || !grad_cover->ptr ||
-        !grad_paints->ptr || !grad_m6->ptr || !grad_geom->ptr)
-        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is missing or too small for the description", entry);
-    if (nst && (!painted_has(grad_stop_pos, nst * 8) || !painted_has(grad_stop_rgba, nst * 32)))
-        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
-    if (nop && (!painted_has(grad_opacity, nop * 8) || !grad_opacity->ptr))
-        return fail(SVGR_E_INVALID, "%s: grad_opacity is missing or too small for the description", entry);
+static int compose_backward_impl(svgr_ctx* ctx, const svgr_compose_desc* d, const ComposeBufs& b) {
+    static const char* entry = "svgr_compose_backward";
+    ComposeShape s;
+    if (int rc = compose_check(TIER_SOLID, entry, ctx, d, b, s)) return rc;
+    if (int rc = compose_grads_check(TIER_SOLID, entry, s, b)) return rc;
     HIPCHK(enter_ctx(ctx));
     hipStream_t st = ctx->stream;
-    const size_t steps = (c.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
-    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
+    const int groups = compose_groups(s);
+    const size_t n4 = (size_t)s.n_paths * 4;
+    // (the blocks go back at scope end by the pool's stream-order rule)
+    PoolBlock part, through;   // the workgroups' partial paint sums; float planes: the double T_p plane of walk 1
+    HIPCHK(part.alloc((size_t)groups * n4 * 8, ctx->device));
+    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n4 * 8, st));
+    if (s.plane == COVER_F32) HIPCHK(through.alloc(s.n_all * 8, ctx->device));
+    compose_by_plane(s.plane, [&](auto zero) {
+        using T = decltype(zero);
+        SVGR_LAUNCH(k_compose_vjp<T>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const T*)b.cover->ptr, (const double*)b.paints->ptr, s.bg, s.n_paths,
+                    s.n_px, (const T*)b.grad_image->ptr, through.p ? through.as<double>() : (double*)b.grad_cover->ptr, (T*)b.grad_cover->ptr, part.as<double>());
+    });
+    SVGR_LAUNCH(k_compose_paint_sum, grid1(n4, 64), dim3(64), 0, st, (const double*)part.p, groups, n4, (double*)b.grad_paints->ptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the painted, grouped and masked forward: output check, blocks, table uploads, the tier's kernel
+template <class Desc>
+static int compose_tier_forward(ComposeTier tier, const char* entry, svgr_ctx* ctx, const Desc* d, const ComposeBufs& b) {
+    ComposeShape s;
+    if (int rc = compose_check(tier, entry, ctx, d, b, s)) return rc;
+    if (int rc = compose_image_check(entry, s, b.image)) return rc;
+    const bool program = tier != TIER_PAINTED;
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    PoolBlock topo, table;   // the paths' descriptions; the program (go back at scope end by the pool's stream-order rule)
+    HIPCHK(topo.alloc((size_t)s.n_paths * sizeof(int4), ctx->device));
+    if (program) HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
+    painted_topology(s, topo.as<int4>(), st);
+    const GroupedProgram g = program ? grouped_program(s, table.as<int>(), st) : GroupedProgram();
+    const dim3 grid = grid1(s.n_px, COMPOSE_BLOCK);
+    compose_by_plane(s.plane, [&](auto zero) {
+        using T = decltype(zero);
+        const T* cover = (const T*)b.cover->ptr;
+        const double* paints = (const double*)b.paints->ptr;
+        T* image = (T*)b.image->ptr;
+        if (!program) {
+            SVGR_LAUNCH(k_compose_over_painted<T>, grid, dim3(COMPOSE_BLOCK), 0, st, cover, paints, topo.as<int4>(), painted_ptr(b.m6), painted_ptr(b.geom),
+                        painted_ptr(b.stop_pos), painted_ptr(b.stop_rgba), s.bg, s.vw, s.n_paths, s.n_px, image);
+        } else {
+            const auto kernel = tier == TIER_MASKED ? k_compose_over_program<T, true> : k_compose_over_program<T, false>;
+            SVGR_LAUNCH(kernel, grid, dim3(COMPOSE_BLOCK), 0, st, cover, paints, topo.as<int4>(), painted_ptr(b.m6), painted_ptr(b.geom),
+                        painted_ptr(b.stop_pos), painted_ptr(b.stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(b.opacity), s.bg, s.vw, g.n_items,
+                        s.n_px, image);
+        }
+    });
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the painted, grouped and masked backward: output checks, blocks, memset, table uploads, the tier's kernel, the sum kernel
+template <class Desc>
+static int compose_tier_backward(ComposeTier tier, const char* entry, svgr_ctx* ctx, const Desc* d, const ComposeBufs& b) {
+    ComposeShape s;
+    if (int rc = compose_check(tier, entry, ctx, d, b, s)) return rc;
+    if (int rc = compose_grads_check(tier, entry, s, b)) return rc;
+    const bool program = tier != TIER_PAINTED;
+    HIPCHK(enter_ctx(ctx));
+    hipStream_t st = ctx->stream;
+    const int groups = compose_groups(s);
+    const size_t np = (size_t)s.n_paths, nst = (size_t)s.n_stops, nop = (size_t)s.n_opacities;
     const size_t n_dense = np * GRADPAINT_DENSE, n_stop_end = n_dense + nst * GRADPAINT_STOP, n_params = n_stop_end + nop;
     // (the blocks go back at scope end by the pool's stream-order rule)
-    PoolBlock topo, table, part, through, t_end;   // descriptions; the program; partial sums; float planes: the double plane of walk 1; T_end per group
+    // the paths' descriptions; the program; the workgroups' partial sums; float planes: the double T_p plane of walk 1; T_end per
+    // group; masked: M per pair, four planes
+    PoolBlock topo, table, part, through, t_end, park;
     HIPCHK(topo.alloc(np * sizeof(int4), ctx->device));
-    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
+    if (program) HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
     HIPCHK(part.alloc((size_t)groups * n_params * 8, ctx->device));
-    if (d->plane == COVER_F32) HIPCHK(through.alloc(c.n_all * 8, ctx->device));
-    HIPCHK(t_end.alloc(std::max<size_t>(1, (size_t)s.n_groups) * c.n_px * 8, ctx->device));
+    if (s.plane == COVER_F32) HIPCHK(through.alloc(s.n_all * 8, ctx->device));
+    if (program) HIPCHK(t_end.alloc(std::max<size_t>(1, (size_t)s.n_groups) * s.n_px * 8, ctx->device));
+    if (tier == TIER_MASKED) HIPCHK(park.alloc(std::max<size_t>(1, (size_t)s.n_pairs) * 4 * s.n_px * 8, ctx->device));
     HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n_params * 8, st));
-    svgr_painted_desc pd;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
-    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
-    if (d->plane == COVER_F32) {
-        SVGR_LAUNCH(k_compose_vjp_grouped<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
-                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const float*)grad_image->ptr,
-                    through.as<double>(), (float*)grad_cover->ptr, t_end.as<double>(), part.as<double>());
-    } else {
-        SVGR_LAUNCH(k_compose_vjp_grouped<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
-                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const double*)grad_image->ptr,
-                    (double*)grad_cover->ptr, (double*)grad_cover->ptr, t_end.as<double>(), part.as<double>());
-    }
-    SVGR_LAUNCH(k_compose_param_sum_grouped, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_stop_end, n_params,
-                (double*)grad_paints->ptr, (double*)grad_m6->ptr, (double*)grad_geom->ptr, nst ? (double*)grad_stop_pos->ptr : nullptr,
-                nst ? (double*)grad_stop_rgba->ptr : nullptr, nop ? (double*)grad_opacity->ptr : nullptr);
+    painted_topology(s, topo.as<int4>(), st);
+    const GroupedProgram g = program ? grouped_program(s, table.as<int>(), st) : GroupedProgram();
+    compose_by_plane(s.plane, [&](auto zero) {
+        using T = decltype(zero);
+        const T* cover = (const T*)b.cover->ptr;
+        const double* paints = (const double*)b.paints->ptr;
+        const T* grad_image = (const T*)b.grad_image->ptr;
+        T* grad_cover = (T*)b.grad_cover->ptr;
+        double* thr = through.p ? through.as<double>() : (double*)b.grad_cover->ptr;
+        if (!program) {
+            SVGR_LAUNCH(k_compose_vjp_painted<T>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, cover, paints, topo.as<int4>(), painted_ptr(b.m6),
+                        painted_ptr(b.geom), painted_ptr(b.stop_pos), painted_ptr(b.stop_rgba), s.bg, s.vw, s.n_paths, s.n_stops, s.n_px, grad_image, thr,
+                        grad_cover, part.as<double>());
+        } else {
+            const auto kernel = tier == TIER_MASKED ? k_compose_vjp_program<T, true> : k_compose_vjp_program<T, false>;
+            SVGR_LAUNCH(kernel, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, cover, paints, topo.as<int4>(), painted_ptr(b.m6), painted_ptr(b.geom),
+                        painted_ptr(b.stop_pos), painted_ptr(b.stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(b.opacity), s.bg, s.vw, g.n_items,
+                        s.n_walk0, s.n_paths, s.n_stops, s.n_opacities, s.n_px, grad_image, thr, grad_cover, t_end.as<double>(), park.as<double>(),
+                        part.as<double>());
+        }
+    });
+    SVGR_LAUNCH(k_compose_param_sum, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_stop_end, n_params,
+                (double*)b.grad_paints->ptr, (double*)b.grad_m6->ptr, (double*)b.grad_geom->ptr, nst ? (double*)b.grad_stop_pos->ptr : nullptr,
+                nst ? (double*)b.grad_stop_rgba->ptr : nullptr, nop ? (double*)b.grad_opacity->ptr : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 extern "C" {
+int svgr_compose_block(void) { return COMPOSE_BLOCK; }
+int svgr_compose_groups(void) { return COMPOSE_GROUPS; }
 int svgr_group_depth(void) { return GROUP_DEPTH; }
+
+int svgr_compose_forward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, svgr_buf* image) {
+    return abi_guard("svgr_compose_forward", [&]() {
+        ComposeBufs b = {};
+        b.cover = cover, b.paints = paints, b.image = image;
+        return compose_forward_impl(ctx, desc, b);
+    });
+}
+
+int svgr_compose_backward(svgr_ctx* ctx, const svgr_compose_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* grad_image,
+                          svgr_buf* grad_cover, svgr_buf* grad_paints) {
+    return abi_guard("svgr_compose_backward", [&]() {
+        ComposeBufs b = {};
+        b.cover = cover, b.paints = paints, b.grad_image = grad_image, b.grad_cover = grad_cover, b.grad_paints = grad_paints;
+        return compose_backward_impl(ctx, desc, b);
+    });
+}
+
+int svgr_compose_painted_forward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, svgr_buf* image) {
+    static const char* entry = "svgr_compose_painted_forward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_forward(TIER_PAINTED, entry, ctx, desc, ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, nullptr, image});
+    });
+}
+
+int svgr_compose_painted_backward(svgr_ctx* ctx, const svgr_painted_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
+                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* grad_image,
+                                  svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom, svgr_buf* grad_stop_pos,
+                                  svgr_buf* grad_stop_rgba) {
+    static const char* entry = "svgr_compose_painted_backward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_backward(TIER_PAINTED, entry, ctx, desc,
+                                     ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, nullptr, nullptr, grad_image, grad_cover, grad_paints,
+                                                 grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, nullptr});
+    });
+}
 
 int svgr_compose_grouped_forward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
-    return abi_guard("svgr_compose_grouped_forward",
-                     [&]() { return grouped_forward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, image); });
+    static const char* entry = "svgr_compose_grouped_forward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_forward(TIER_GROUPED, entry, ctx, desc, ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, image});
+    });
 }
 
 int svgr_compose_grouped_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
                                   const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
                                   const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
                                   svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
-    return abi_guard("svgr_compose_grouped_backward", [&]() {
-        return grouped_backward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, grad_image, grad_cover, grad_paints,
-                                     grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, grad_opacity);
+    static const char* entry = "svgr_compose_grouped_backward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_backward(TIER_GROUPED, entry, ctx, desc,
+                                     ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, nullptr, grad_image, grad_cover, grad_paints,
+                                                 grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, grad_opacity});
     });
 }
-}  // extern "C"
 
-// ======================================================================================
-// luminance-masked groups in differentiable compositing: svgr_compose_masked_forward / svgr_compose_masked_backward
-// (csrc/svgr_mask.h has the per-pixel arithmetic and the program's check, DESIGN.md 7za the derivation).  The grouped compositor
-// above with two more ops: HOLD closes a group but keeps it, END_MASK closes the mask group that follows it, reduces that canvas to
-// one scalar per pixel and composes the held group through it.  New kernels beside the ones above, which are not involved;
-// k_group_program and k_compose_param_sum_grouped are launched as they are.
-//   forward   k_compose_over_masked   k_compose_over_grouped, and the held group H = (G o) k_clip in LDS, a column per lane, indexed
-//                                     by the wave-uniform level of the pair: no private array, no scratch
-//   backward  k_compose_vjp_masked    walk 0 is that forward (to the last END_MASK) and parks the mask canvas M of every pair in four
-//                                     planes of the call's scratch, as T_end is parked per group: walk 1 needs k_mask and walk 2
-//                                     d k / d M before either arrives at the mask group.  Walks 1 and 2 are svgr_mask.h's; the
-//                                     parameter sums are k_compose_vjp_grouped's, a HOLD's opacity being a slot like an END's.
-// A program without pairs skips walk 0 and takes the grouped kernels' steps: the same bits.
-// ======================================================================================
-#include "svgr_mask.h"
-
-// one pixel of the forward over items[0 .. n_run): X is the root canvas on entry and on return.  below has BELOW rows per level
-// (the canvas in the first four); park, if not null, gets M of every pair.
-template <class T, int BELOW>
-__device__ __forceinline__ void masked_forward_px(const T* __restrict__ cover, const double* __restrict__ paints, const int4* __restrict__ desc,
-                                                  const double* __restrict__ m6s, const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                  const double* __restrict__ rgba, const int4* __restrict__ items, const int* __restrict__ clip_off,
-                                                  const int* __restrict__ clip_planes, const double* __restrict__ opacity, const PaintedView vw, int n_run,
-                                                  size_t n_px, size_t i, unsigned row, unsigned colj, double (*below)[BELOW][COMPOSE_BLOCK],
-                                                  double (*held)[4][COMPOSE_BLOCK], double* park, double* X) {
-    int level = 0;
-    for (int q = 0; q < n_run; ++q) {
-        const int4 it = items[q];
-        const int op = mask_op(it.x);
-        if (op == GROUP_FILL) {
-            const int p = it.y;
-            const int4 d = desc[p];
-            const double m = (double)cover[(size_t)p * n_px + i];
-            if (d.x == 0) {
-                compose_step(X, m, paints + 4 * (size_t)p);
-            } else {
-                double col[4];
-                GradPaintPx e;
-                gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0,
-                                 vw.col0, col, e);
-                gradpaint_step(X, m, col, paints + 4 * (size_t)p);
-            }
-        } else if (op == GROUP_BEGIN || op == MASK_BEGIN_HELD || op == MASK_BEGIN_MASK) {
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                below[level][c][threadIdx.x] = X[c];
-                X[c] = 0.0;
-            }
-            ++level;
-        } else if (op == GROUP_END) {
-            --level;
-            const double o = it.z < 0 ? 1.0 : opacity[it.z];
-            const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-            const double G[4] = {X[0], X[1], X[2], X[3]};
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) X[c] = below[level][c][threadIdx.x];
-            group_step(X, G, o, k);
-        } else if (op == MASK_HOLD) {
-            --level;
-            const double o = it.z < 0 ? 1.0 : opacity[it.z];
-            const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-            double H[4];
-            mask_hold(X, o, k, H);
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                held[level][c][threadIdx.x] = H[c];
-                X[c] = below[level][c][threadIdx.x];
-            }
-        } else {   // MASK_END
-            --level;
-            const double M[4] = {X[0], X[1], X[2], X[3]};
-            if (park) {
-                const size_t at = (size_t)mask_pair(it.x) * 4 * n_px + i;
-                SVGR_UNROLL
-                for (int c = 0; c < 4; ++c) park[at + (size_t)c * n_px] = M[c];
-            }
-            double H[4];
-            SVGR_UNROLL
-            for (int c = 0; c < 4; ++c) {
-                X[c] = below[level][c][threadIdx.x];
-                H[c] = held[level][c][threadIdx.x];
-            }
-            mask_step(X, H, mask_value(M));
-        }
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_over_masked(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                       const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                       const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                       const double* __restrict__ rgba, const int4* __restrict__ items,
-                                                                       const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
-                                                                       const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
-                                                                       int n_items, size_t n_px, T* __restrict__ image) {
-    __shared__ double below[GROUP_DEPTH][4][COMPOSE_BLOCK];   // the canvases under the open level, a column per lane
-    __shared__ double held[GROUP_DEPTH][4][COMPOSE_BLOCK];    // the held group of the pair open on a level
-    const size_t i = (size_t)blockIdx.x * COMPOSE_BLOCK + threadIdx.x;
-    if (i >= n_px) return;   // (no barrier below: a lane reads its own column only)
-    const unsigned row = (unsigned)i / vw.cols, colj = (unsigned)i - row * vw.cols;   // (n_px < 2^31)
-    double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-    masked_forward_px<T, 4>(cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_items, n_px, i, row, colj, below, held,
-                            nullptr, X);
-    typename ComposePx<T>::type v;
-    v.x = (T)X[0]; v.y = (T)X[1]; v.z = (T)X[2]; v.w = (T)X[3];
-    reinterpret_cast<typename ComposePx<T>::type*>(image)[i] = v;
-}
-
-// the LDS slots an item's parameters take in a run: a FILL's 14 dense terms and 5 per stop, the opacity of an END or a HOLD
-__device__ __forceinline__ int masked_need(const int4 it, const int4* __restrict__ desc) {
-    const int op = mask_op(it.x);
-    if (op == GROUP_FILL) {
-        const int4 d = desc[it.y];
-        return GRADPAINT_DENSE + GRADPAINT_STOP * (d.w - d.z);
-    }
-    return (op == GROUP_END || op == MASK_HOLD) && it.z >= 0 ? 1 : 0;
-}
-
-// M of a pair from its four planes
-__device__ __forceinline__ void masked_parked(const double* park, int pair, size_t n_px, size_t i, double* M) {
-    const size_t at = (size_t)pair * 4 * n_px + i;
-    SVGR_UNROLL
-    for (int c = 0; c < 4; ++c) M[c] = park[at + (size_t)c * n_px];
-}
-
-// (through and grad_cover are the same memory for double planes, as in k_compose_vjp)
-template <class T>
-__global__ __launch_bounds__(COMPOSE_BLOCK) void k_compose_vjp_masked(const T* __restrict__ cover, const double* __restrict__ paints,
-                                                                      const int4* __restrict__ desc, const double* __restrict__ m6s,
-                                                                      const double* __restrict__ geoms, const double* __restrict__ pos,
-                                                                      const double* __restrict__ rgba, const int4* __restrict__ items,
-                                                                      const int* __restrict__ clip_off, const int* __restrict__ clip_planes,
-                                                                      const double* __restrict__ opacity, const ComposeBg bg, const PaintedView vw,
-                                                                      int n_items, int n_walk0, int n_paths, int n_stops, int n_opacities, size_t n_px,
-                                                                      const T* __restrict__ grad_image, double* through, T* grad_cover,
-                                                                      double* __restrict__ t_end, double* park, double* __restrict__ part) {
-    __shared__ double sums[COMPOSE_WAVES][PAINTED_SLOTS];
-    __shared__ double below[GROUP_DEPTH][8][COMPOSE_BLOCK];   // canvas and base adjoint of the levels under the open one, a column per lane
-    __shared__ double held[GROUP_DEPTH][4][COMPOSE_BLOCK];    // the held group of the pair open on a level
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const size_t n_dense = (size_t)GRADPAINT_DENSE * (size_t)n_paths;
-    const size_t n_stop_end = n_dense + (size_t)GRADPAINT_STOP * (size_t)n_stops;
-    double* mine = part + (size_t)blockIdx.x * (n_stop_end + (size_t)n_opacities);
-    for (int j = threadIdx.x; j < PAINTED_SLOTS; j += COMPOSE_BLOCK) {
-        SVGR_UNROLL
-        for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][j] = 0.0;
-    }
-    __syncthreads();
-    for (size_t base = (size_t)blockIdx.x * COMPOSE_BLOCK; base < n_px; base += (size_t)gridDim.x * COMPOSE_BLOCK) {
-        const size_t i = base + threadIdx.x;
-        const bool live = i < n_px;
-        const unsigned row = live ? (unsigned)i / vw.cols : 0u, colj = live ? (unsigned)i - row * vw.cols : 0u;
-        double B[4] = {0.0, 0.0, 0.0, 0.0};
-        if (live) {
-            if (n_walk0 > 0) {   // walk 0: the lane reads back below only what it parks here itself
-                double X0[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-                masked_forward_px<T, 8>(cover, paints, desc, m6s, geoms, pos, rgba, items, clip_off, clip_planes, opacity, vw, n_walk0, n_px, i, row, colj,
-                                        below, held, park, X0);
-            }
-            double above = 1.0;
-            for (int q = n_items - 1; q >= 0; --q) {
-                const int4 it = items[q];
-                const int op = mask_op(it.x);
-                if (op == GROUP_FILL) {
-                    const int p = it.y;
-                    const int4 d = desc[p];
-                    const size_t at = (size_t)p * n_px + i;
-                    const double m = (double)cover[at];
-                    double u;
-                    if (d.x == 0) {
-                        u = compose_through(m, paints[4 * (size_t)p + 3]);
-                    } else {
-                        double col[4];
-                        GradPaintPx e;
-                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, geoms + 4 * (size_t)p, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj,
-                                         vw.row0, vw.col0, col, e);
-                        u = gradpaint_through(m, col, paints + 4 * (size_t)p);
-                    }
-                    through[at] = above;
-                    above = above * u;
-                } else if (op == GROUP_END) {
-                    t_end[(size_t)it.y * n_px + i] = above;
-                    above = 1.0;
-                } else if (op == MASK_END) {
-                    t_end[(size_t)it.z * n_px + i] = above;   // (of the pair's target)
-                    above = 1.0;
-                } else if (op == MASK_HOLD) {
-                    above = 1.0;
-                } else if (op == GROUP_BEGIN) {
-                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                    const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-                    const double u = group_through(above, o, k);
-                    above = t_end[(size_t)it.y * n_px + i] * u;
-                } else if (op == MASK_BEGIN_HELD) {
-                    const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                    const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-                    double M[4];
-                    masked_parked(park, mask_pair(it.x), n_px, i, M);
-                    const double u = mask_through(above, o, k, mask_value(M));
-                    above = t_end[(size_t)it.y * n_px + i] * u;
-                }   // (the BEGIN of a mask group: nothing carries over)
-            }
-            const typename ComposePx<T>::type v = reinterpret_cast<const typename ComposePx<T>::type*>(grad_image)[i];
-            B[0] = (double)v.x; B[1] = (double)v.y; B[2] = (double)v.z; B[3] = (double)v.w;
-        }
-        double X[4] = {bg.c[0], bg.c[1], bg.c[2], bg.c[3]};
-        double qok = 0.0;   // from a HOLD to the BEGIN after it
-        int level = 0;
-        int q0 = 0;
-        while (q0 < n_items) {
-            // the run of items q0 .. q1 - 1 whose parameters fit the LDS rows, each item's slots after the one before
-            int q1 = q0, used = 0;
-            while (q1 < n_items) {
-                const int need = masked_need(items[q1], desc);
-                if (used + need > PAINTED_SLOTS) break;
-                used += need;
-                ++q1;
-            }
-            int slot = 0;
-            for (int q = q0; q < q1; ++q) {
-                const int4 it = items[q];
-                const int op = mask_op(it.x);
-                double* rowd = &sums[wave][slot];
-                slot += masked_need(it, desc);
-                if (op == GROUP_BEGIN || op == MASK_BEGIN_HELD) {
-                    if (live) {
-                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                        const double k = grouped_mask(cover, clip_off, clip_planes, it.w, n_px, i);
-                        double adj[4];
-                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            below[level][c][threadIdx.x] = X[c];
-                            below[level][4 + c][threadIdx.x] = B[c];
-                            X[c] = 0.0;
-                        }
-                        if (op == GROUP_BEGIN) {
-                            group_base(adj, o, k, B);
-                        } else {
-                            double M[4];
-                            masked_parked(park, mask_pair(it.x), n_px, i, M);
-                            mask_base(adj, o, k, mask_value(M), B);
-                        }
-                    }
-                    ++level;
-                    continue;
-                }
-                if (op == MASK_BEGIN_MASK) {
-                    if (live) {
-                        double M[4];
-                        masked_parked(park, mask_pair(it.x), n_px, i, M);
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            below[level][c][threadIdx.x] = X[c];
-                            below[level][4 + c][threadIdx.x] = B[c];
-                            X[c] = 0.0;
-                        }
-                        mask_base_of_mask(qok, M, B);
-                    }
-                    ++level;
-                    continue;
-                }
-                if (op == MASK_END) {
-                    --level;
-                    if (live) {
-                        double M[4], H[4];
-                        masked_parked(park, mask_pair(it.x), n_px, i, M);
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            X[c] = below[level][c][threadIdx.x];
-                            B[c] = below[level][4 + c][threadIdx.x];
-                            H[c] = held[level][c][threadIdx.x];
-                        }
-                        mask_step(X, H, mask_value(M));
-                    }
-                    continue;
-                }
-                if (op == GROUP_END || op == MASK_HOLD) {
-                    --level;
-                    double term = 0.0;
-                    if (live) {
-                        const double o = it.z < 0 ? 1.0 : opacity[it.z];
-                        const double G[4] = {X[0], X[1], X[2], X[3]};
-                        SVGR_UNROLL
-                        for (int c = 0; c < 4; ++c) {
-                            X[c] = below[level][c][threadIdx.x];
-                            B[c] = below[level][4 + c][threadIdx.x];
-                        }
-                        double adj[4];
-                        group_adjoint(X, t_end[(size_t)it.y * n_px + i], B, adj);
-                        const double qd = compose_dot(adj, G);
-                        double km = 1.0;
-                        if (op == MASK_HOLD) {
-                            double M[4];
-                            masked_parked(park, mask_pair(it.x), n_px, i, M);
-                            km = mask_value(M);
-                        }
-                        const double dk = op == MASK_HOLD ? mask_clip_term(qd, o, km) : qd * o;
-                        double k = 1.0;
-                        if (it.w >= 0) {
-                            const int a0 = clip_off[it.w], a1 = clip_off[it.w + 1];
-                            double suffix = 1.0;   // parked in the planes' own slots, as T_p is
-                            for (int a = a1 - 1; a >= a0; --a) {
-                                const size_t at = (size_t)clip_planes[a] * n_px + i;
-                                through[at] = suffix;
-                                suffix = suffix * (1.0 - (double)cover[at]);
-                            }
-                            k = 0.0;
-                            for (int a = a0; a < a1; ++a) {
-                                const size_t at = (size_t)clip_planes[a] * n_px + i;
-                                const double dm = group_clip_vjp(dk, a == a0, k, through[at]);
-                                grad_cover[at] = (T)dm;
-                                k = group_mask_step(k, (double)cover[at], a == a0);
-                            }
-                        }
-                        if (op == MASK_HOLD) {
-                            term = mask_opacity_term(qd, k, km);
-                            qok = mask_held_dot(qd, o, k);
-                            double H[4];
-                            mask_hold(G, o, k, H);
-                            SVGR_UNROLL
-                            for (int c = 0; c < 4; ++c) held[level][c][threadIdx.x] = H[c];
-                        } else {
-                            term = qd * k;
-                            group_step(X, G, o, k);
-                        }
-                    }
-                    if (it.z >= 0) {
-                        for (int s = 32; s > 0; s >>= 1) term = term + __shfl_down(term, s);
-                        if (lane == 0) rowd[0] = rowd[0] + term;
-                    }
-                    continue;
-                }
-                const int p = it.y;
-                const int4 d = desc[p];
-                const double* paint = paints + 4 * (size_t)p;
-                double m = 0.0, dense[GRADPAINT_DENSE], lo[GRADPAINT_STOP], hi[GRADPAINT_STOP];
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k) dense[k] = 0.0;
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_STOP; ++k) lo[k] = hi[k] = 0.0;
-                int used_lo = -1, used_hi = -1;
-                if (live) {
-                    const size_t at = (size_t)p * n_px + i;
-                    m = (double)cover[at];
-                    if (d.x == 0) {
-                        const double dm = compose_vjp_step(X, through[at], B, m, paint, dense);
-                        grad_cover[at] = (T)dm;
-                        compose_step(X, m, paint);
-                    } else {
-                        double col[4], P[4], t[4];
-                        GradPaintPx e;
-                        const double* g4 = geoms + 4 * (size_t)p;
-                        gradpaint_colour(d.x, d.y, m6s + 6 * (size_t)p, g4, d.w - d.z, pos + d.z, rgba + 4 * (size_t)d.z, row, colj, vw.row0, vw.col0,
-                                         col, e);
-                        gradpaint_effective(col, paint, P);
-                        const double dm = compose_vjp_step(X, through[at], B, m, P, t);
-                        grad_cover[at] = (T)dm;
-                        gradpaint_vjp(d.x, g4, pos + d.z, rgba + 4 * (size_t)d.z, col, paint, e, t, dense, lo, hi);
-                        gradpaint_step(X, m, col, paint);
-                        used_lo = e.lo;
-                        used_hi = e.hi;
-                    }
-                }
-                if (__ballot(m != 0.0) == 0ull) continue;   // (the same in every lane of the wave; a lane past the end has m == 0)
-                if (d.x == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < 4; ++k)
-                        for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                    if (lane == 0) {
-                        SVGR_UNROLL
-                        for (int k = 0; k < 4; ++k) rowd[k] = rowd[k] + dense[k];
-                    }
-                    continue;
-                }
-                SVGR_UNROLL
-                for (int k = 0; k < GRADPAINT_DENSE; ++k)
-                    for (int s = 32; s > 0; s >>= 1) dense[k] = dense[k] + __shfl_down(dense[k], s);
-                if (lane == 0) {
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_DENSE; ++k) rowd[k] = rowd[k] + dense[k];
-                }
-                const int ns = d.w - d.z;
-                for (int s = 0; s < ns; ++s) {
-                    const bool at_lo = used_lo == s, at_hi = used_hi == s;
-                    if (__ballot(m != 0.0 && (at_lo || at_hi)) == 0ull) continue;
-                    double v[GRADPAINT_STOP];
-                    SVGR_UNROLL
-                    for (int k = 0; k < GRADPAINT_STOP; ++k) {
-                        v[k] = at_lo ? lo[k] : (at_hi ? hi[k] : 0.0);
-                        for (int r = 32; r > 0; r >>= 1) v[k] = v[k] + __shfl_down(v[k], r);
-                    }
-                    if (lane == 0) {
-                        double* rows = rowd + GRADPAINT_DENSE + GRADPAINT_STOP * s;
-                        SVGR_UNROLL
-                        for (int k = 0; k < GRADPAINT_STOP; ++k) rows[k] = rows[k] + v[k];
-                    }
-                }
-            }
-            __syncthreads();
-            slot = 0;
-            for (int q = q0; q < q1; ++q) {
-                const int4 it = items[q];
-                const int need = masked_need(it, desc);
-                if (need == 0) continue;
-                size_t dense_at, stop_at = 0;   // where the item's first GRADPAINT_DENSE slots and the ones after them go
-                if (mask_op(it.x) == GROUP_FILL) {
-                    dense_at = (size_t)GRADPAINT_DENSE * (size_t)it.y;
-                    stop_at = n_dense + (size_t)GRADPAINT_STOP * (size_t)desc[it.y].z;
-                } else {
-                    dense_at = n_stop_end + (size_t)it.z;
-                }
-                for (int j = threadIdx.x; j < need; j += COMPOSE_BLOCK) {
-                    double s = sums[0][slot + j];
-                    SVGR_UNROLL
-                    for (int w = 1; w < COMPOSE_WAVES; ++w) s = s + sums[w][slot + j];
-                    double* o = mine + (j < GRADPAINT_DENSE ? dense_at + (size_t)j : stop_at + (size_t)(j - GRADPAINT_DENSE));
-                    *o = *o + s;
-                    SVGR_UNROLL
-                    for (int w = 0; w < COMPOSE_WAVES; ++w) sums[w][slot + j] = 0.0;
-                }
-                slot += need;
-            }
-            __syncthreads();
-            q0 = q1;
-        }
-    }
-}
-
-struct MaskedShape {
-    GroupedShape g;
-    int n_pairs, n_walk0;   // masked pairs; the items walk 0 runs: to the last END_MASK
-};
-
-// Everything of a masked description that can be wrong, and the program's table: grouped_check with mask_program_check.
-static int masked_check(const char* entry, const svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints,
-                        const svgr_buf* m6, const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
-                        MaskedShape& m) {
-    GroupedShape& s = m.g;
-    if (!d) return fail(SVGR_E_INVALID, "%s: desc is NULL", entry);
-    svgr_painted_desc pd;
-    pd.n_paths = d->n_paths; pd.rows = d->rows; pd.cols = d->cols; pd.plane = d->plane; pd.has_bg = d->has_bg;
-    for (int k = 0; k < 4; ++k) pd.bg[k] = d->bg[k];
-    pd.row0 = d->row0; pd.col0 = d->col0; pd.n_stops = d->n_stops;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_check(entry, ctx, &pd, cover, paints, m6, geom, stop_pos, stop_rgba, s.p)) return rc;
-    constexpr int64_t kMax = (1ll << 31) - 1;
-    if (d->n_groups < 0 || d->n_groups > kMax || d->n_items < 0 || d->n_items > kMax || d->n_opacities < 0 || d->n_clip_planes < 0)
-        return fail(SVGR_E_INVALID, "%s: %lld items, %lld groups, %lld opacities, %lld clip planes", entry, (long long)d->n_items, (long long)d->n_groups,
-                    (long long)d->n_opacities, (long long)d->n_clip_planes);
-    if (d->n_groups > d->n_items) return fail(SVGR_E_INVALID, "%s: %lld groups in %lld items", entry, (long long)d->n_groups, (long long)d->n_items);
-    if (d->n_items > GROUP_MAX_ITEMS) return fail(SVGR_E_OVERFLOW, "%s: %lld items are beyond %d", entry, (long long)d->n_items, GROUP_MAX_ITEMS);
-    std::vector<int> seen((size_t)d->n_paths + (size_t)d->n_groups + (size_t)std::min(d->n_opacities, d->n_groups) + 1);
-    s.table.assign(4 * (size_t)d->n_items, 0);
-    long long at = -1;
-    int n_clips = 0, last_mask = -1;
-    m.n_pairs = 0;
-    if (const char* what = mask_program_check(d->items, d->n_items, d->n_paths, d->n_groups, d->n_clip_planes, d->n_opacities, d->clip_off, d->clip_planes,
-                                              seen.data(), s.table.data(), &n_clips, &m.n_pairs, &last_mask, &at))
-        return fail(SVGR_E_INVALID, "%s: the program is wrong: %s (at %lld)", entry, what, at);
-    // (this bounds walk 0's planes too: a pair is two groups and parks four planes)
-    if ((unsigned __int128)d->n_groups * (unsigned __int128)s.p.c.n_px > (unsigned __int128)kMax)
-        return fail(SVGR_E_OVERFLOW, "%s: %lld groups of %zu pixels are beyond 2^31 - 1 pixels", entry, (long long)d->n_groups, s.p.c.n_px);
-    if (d->n_opacities && (!painted_has(opacity, (size_t)d->n_opacities * 8) || !opacity->ptr))
-        return fail(SVGR_E_INVALID, "%s: opacity is missing or too small for the description", entry);
-    s.n_items = (int)d->n_items;
-    s.n_groups = (int)d->n_groups;
-    s.n_opacities = (int)d->n_opacities;
-    s.n_clips = n_clips;
-    s.n_clip_planes = (int)d->n_clip_planes;
-    m.n_walk0 = last_mask + 1;
-    if (n_clips) {
-        s.table.insert(s.table.end(), d->clip_off, d->clip_off + n_clips + 1);
-        s.table.insert(s.table.end(), d->clip_planes, d->clip_planes + d->n_clip_planes);
-    }
-    return 0;
-}
-
-static int masked_forward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                               const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
-    static const char* entry = "svgr_compose_masked_forward";
-    MaskedShape m;
-    if (int rc = masked_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, m)) return rc;
-    const GroupedShape& s = m.g;
-    const ComposeShape& c = s.p.c;
-    if (!image) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (image->bytes < c.n_px * 4 * c.elem || !compose_aligned(image))
-        return fail(SVGR_E_INVALID, "%s: image is too small for the description or not aligned to 16 bytes", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    PoolBlock topo, table;   // (go back at scope end by the pool's stream-order rule)
-    HIPCHK(topo.alloc((size_t)c.n_paths * sizeof(int4), ctx->device));
-    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
-    svgr_painted_desc pd;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
-    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
-    const dim3 grid = grid1(c.n_px, COMPOSE_BLOCK);
-    if (d->plane == COVER_F32)
-        SVGR_LAUNCH(k_compose_over_masked<float>, grid, dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
-                    c.bg, s.p.vw, g.n_items, c.n_px, (float*)image->ptr);
-    else
-        SVGR_LAUNCH(k_compose_over_masked<double>, grid, dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr, topo.as<int4>(),
-                    painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes, painted_ptr(opacity),
-                    c.bg, s.p.vw, g.n_items, c.n_px, (double*)image->ptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static int masked_backward_impl(svgr_ctx* ctx, const svgr_grouped_desc* d, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* m6,
-                                const svgr_buf* geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
-                                const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
-                                svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
-    static const char* entry = "svgr_compose_masked_backward";
-    MaskedShape m;
-    if (int rc = masked_check(entry, ctx, d, cover, paints, m6, geom, stop_pos, stop_rgba, opacity, m)) return rc;
-    const GroupedShape& s = m.g;
-    const ComposeShape& c = s.p.c;
-    if (!grad_image || !grad_cover || !grad_paints || !grad_m6 || !grad_geom) return fail(SVGR_E_INVALID, "%s: a buffer is NULL", entry);
-    if (grad_image->bytes < c.n_px * 4 * c.elem || !compose_aligned(grad_image))
-        return fail(SVGR_E_INVALID, "%s: grad_image is too small for the description or not aligned to 16 bytes", entry);
-    const size_t np = (size_t)c.n_paths, nst = (size_t)s.p.n_stops, nop = (size_t)s.n_opacities;
-    if (grad_cover->bytes < c.n_all * c.elem || grad_paints->bytes < np * 32 || grad_m6->bytes < np * 48 || grad_geom->bytes < np * 32 || !grad_cover->ptr ||
-        !grad_paints->ptr || !grad_m6->ptr || !grad_geom->ptr)
-        return fail(SVGR_E_INVALID, "%s: grad_cover, grad_paints, grad_m6 or grad_geom is missing or too small for the description", entry);
-    if (nst && (!painted_has(grad_stop_pos, nst * 8) || !painted_has(grad_stop_rgba, nst * 32)))
-        return fail(SVGR_E_INVALID, "%s: grad_stop_pos or grad_stop_rgba is missing or too small for the description", entry);
-    if (nop && (!painted_has(grad_opacity, nop * 8) || !grad_opacity->ptr))
-        return fail(SVGR_E_INVALID, "%s: grad_opacity is missing or too small for the description", entry);
-    HIPCHK(enter_ctx(ctx));
-    hipStream_t st = ctx->stream;
-    const size_t steps = (c.n_px + COMPOSE_BLOCK - 1) / COMPOSE_BLOCK;
-    const int groups = (int)(steps < (size_t)COMPOSE_GROUPS ? steps : (size_t)COMPOSE_GROUPS);
-    const size_t n_dense = np * GRADPAINT_DENSE, n_stop_end = n_dense + nst * GRADPAINT_STOP, n_params = n_stop_end + nop;
-    // (the blocks go back at scope end by the pool's stream-order rule)
-    PoolBlock topo, table, part, through, t_end, park;   // as in the grouped backward; M per pair, four planes
-    HIPCHK(topo.alloc(np * sizeof(int4), ctx->device));
-    HIPCHK(table.alloc(s.table.size() * sizeof(int), ctx->device));
-    HIPCHK(part.alloc((size_t)groups * n_params * 8, ctx->device));
-    if (d->plane == COVER_F32) HIPCHK(through.alloc(c.n_all * 8, ctx->device));
-    HIPCHK(t_end.alloc(std::max<size_t>(1, (size_t)s.n_groups) * c.n_px * 8, ctx->device));
-    HIPCHK(park.alloc(std::max<size_t>(1, (size_t)m.n_pairs) * 4 * c.n_px * 8, ctx->device));
-    HIPCHK(hipMemsetAsync(part.p, 0, (size_t)groups * n_params * 8, st));
-    svgr_painted_desc pd;
-    pd.kind = d->kind; pd.spread = d->spread; pd.path_stop_off = d->path_stop_off;
-    if (int rc = painted_topology(&pd, c.n_paths, topo.as<int4>(), st)) return rc;
-    const GroupedProgram g = grouped_program(s, table.as<int>(), st);
-    if (d->plane == COVER_F32) {
-        SVGR_LAUNCH(k_compose_vjp_masked<float>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const float*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
-                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, m.n_walk0, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const float*)grad_image->ptr,
-                    through.as<double>(), (float*)grad_cover->ptr, t_end.as<double>(), park.as<double>(), part.as<double>());
-    } else {
-        SVGR_LAUNCH(k_compose_vjp_masked<double>, dim3((unsigned)groups), dim3(COMPOSE_BLOCK), 0, st, (const double*)cover->ptr, (const double*)paints->ptr,
-                    topo.as<int4>(), painted_ptr(m6), painted_ptr(geom), painted_ptr(stop_pos), painted_ptr(stop_rgba), g.items, g.clip_off, g.clip_planes,
-                    painted_ptr(opacity), c.bg, s.p.vw, g.n_items, m.n_walk0, c.n_paths, s.p.n_stops, s.n_opacities, c.n_px, (const double*)grad_image->ptr,
-                    (double*)grad_cover->ptr, (double*)grad_cover->ptr, t_end.as<double>(), park.as<double>(), part.as<double>());
-    }
-    SVGR_LAUNCH(k_compose_param_sum_grouped, grid1(n_params, 64), dim3(64), 0, st, (const double*)part.p, groups, n_dense, n_stop_end, n_params,
-                (double*)grad_paints->ptr, (double*)grad_m6->ptr, (double*)grad_geom->ptr, nst ? (double*)grad_stop_pos->ptr : nullptr,
-                nst ? (double*)grad_stop_rgba->ptr : nullptr, nop ? (double*)grad_opacity->ptr : nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" {
 int svgr_compose_masked_forward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
                                 const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity, svgr_buf* image) {
-    return abi_guard("svgr_compose_masked_forward",
-                     [&]() { return masked_forward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, image); });
+    static const char* entry = "svgr_compose_masked_forward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_forward(TIER_MASKED, entry, ctx, desc, ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, image});
+    });
 }
 
 int svgr_compose_masked_backward(svgr_ctx* ctx, const svgr_grouped_desc* desc, const svgr_buf* cover, const svgr_buf* paints, const svgr_buf* paint_m6,
                                  const svgr_buf* paint_geom, const svgr_buf* stop_pos, const svgr_buf* stop_rgba, const svgr_buf* opacity,
                                  const svgr_buf* grad_image, svgr_buf* grad_cover, svgr_buf* grad_paints, svgr_buf* grad_m6, svgr_buf* grad_geom,
                                  svgr_buf* grad_stop_pos, svgr_buf* grad_stop_rgba, svgr_buf* grad_opacity) {
-    return abi_guard("svgr_compose_masked_backward", [&]() {
-        return masked_backward_impl(ctx, desc, cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, grad_image, grad_cover, grad_paints,
-                                    grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, grad_opacity);
+    static const char* entry = "svgr_compose_masked_backward";
+    return abi_guard(entry, [&]() {
+        return compose_tier_backward(TIER_MASKED, entry, ctx, desc,
+                                     ComposeBufs{cover, paints, paint_m6, paint_geom, stop_pos, stop_rgba, opacity, nullptr, grad_image, grad_cover, grad_paints,
+                                                 grad_m6, grad_geom, grad_stop_pos, grad_stop_rgba, grad_opacity});
     });
 }
 }  // extern "C"

@@ -1,7 +1,7 @@
 // svgr_mask.h -- per-pixel arithmetic of luminance-masked groups in differentiable compositing, on top of svgr_group.h: the value
 // of a mask and its derivative, a masked group as a source, and the check of a program that may hold masked pairs.
 //
-// Plain double arithmetic for the host (tests/mask_harness.cpp) and the device (k_compose_over_masked, k_compose_vjp_masked of
+// Plain double arithmetic for the host (tests/mask_harness.cpp) and the device (k_compose_over_program, k_compose_vjp_program of
 // svgr_hip.hip), both compiled with -ffp-contract=off.  The two fma calls of mask_value are explicit, as in k_layer_luminance;
 // nothing else is fused: every product and sum is rounded on its own, in the order written.  DESIGN.md 7za has the derivation,
 // tests/mask_ref.py restates all of it in numpy.

@@ -664,9 +664,9 @@ def _origin(origin):
     return o
 
 
-def _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops):
-    """(svgr_painted_desc, what it points at)."""
-    d = _abi.PaintedDesc()
+def _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, cls=_abi.PaintedDesc):
+    """(svgr_painted_desc, what it points at).  ``cls`` may be a description that begins with one."""
+    d = cls()
     d.n_paths, d.rows, d.cols, d.plane, d.has_bg = n_paths, rows, cols, plane, int(bg is not None)
     d.bg = (C.c_double * 4)(*(bg if bg is not None else (0.0,) * 4))
     d.row0, d.col0, d.n_stops = origin[0], origin[1], n_stops
@@ -724,15 +724,7 @@ def compose_painted(cover, paints, gp, bg=None, origin=(0, 0), dtype=None):
     component-wise (ones, or an opacity).  ``gp`` is a ``GradientPaints`` of numpy arrays (``gradient_paints`` builds one).  The
     arithmetic is the renderer's, in double; a float32 image is rounded once.  Wrong shapes and dtypes, non-finite values,
     ``p0 == p1``, ``r <= 0``, decreasing stop positions and every error of the topology are refused before any device work."""
-    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
-    n_paths, rows, cols = cover.shape
-    _n_pixels(n_paths, (0, 0, rows, cols))
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays]
-    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
-    desc, _keep = _painted_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]))
-    _abi._check(ctx.lib.svgr_compose_painted_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
-    return image.download((rows, cols, 4), cover.dtype)
+    return _tier_forward("painted", cover, paints, gp, None, bg, origin, dtype)
 
 
 def compose_painted_backward(cover, paints, gp, grad_image, bg=None, origin=(0, 0)):
@@ -742,68 +734,49 @@ def compose_painted_backward(cover, paints, gp, grad_image, bg=None, origin=(0, 
     derivatives with respect to ``m6``, ``geom``, ``stop_pos`` and ``stop_rgba`` (float64); the rows of solid paths and a radial
     gradient's unused slot are 0.  Where a derivative is not defined -- an offset exactly on a stop, a clamp, a wrap or a fold,
     the radial centre -- one side is taken and nothing is NaN.  No atomics: the same bits on every run."""
-    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin)
-    n_paths, rows, cols = cover.shape
-    grad_image = np.asarray(grad_image)
-    if grad_image.dtype != cover.dtype:
-        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
-    if grad_image.shape != (rows, cols, 4):
-        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
-    _n_pixels(n_paths, (0, 0, rows, cols))
-    n_stops = len(arrays[2])
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays]
-    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
-    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4))
-    g_cover = ctx.alloc(cover.nbytes)
-    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]   # (no stops at all: no stop buffers)
-    desc, _keep = _painted_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops)
-    _abi._check(ctx.lib.svgr_compose_painted_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
-    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
-    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:])
+    return _tier_backward("painted", cover, paints, gp, None, grad_image, bg, origin)
 
 
-@functools.lru_cache(maxsize=None)
-def _painted_function(torch):
-    class ComposePainted(torch.autograd.Function):
-        """image = ComposePainted.apply(planes, paints, m6, geom, stop_pos, stop_rgba, out, bg, origin, topo)."""
+def _tensor_args(torch, planes, paints_t, gp_t, program=None):
+    """The types, dtypes and shapes of a tensor call's arguments, checked: ``(named, n_stops)``, ``named`` the tensors as
+    ``(name, tensor, dtypes)``.  The program tiers pass ``program = (groups, opacity_t)``."""
+    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
+        raise TypeError("gp_t is a GradientPaints")
+    if program is not None and not isinstance(program[0], Groups):
+        raise TypeError("groups is a Groups")
+    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
+        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS)
+    if program is not None:
+        named += (("opacity_t", program[1], (torch.float64,)),)
+    for name, t, kinds in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
+        if t.dtype not in kinds or not t.is_cuda:
+            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
+    if planes.dim() != 3 or min(planes.shape) < 1:
+        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    n_paths = int(planes.shape[0])
+    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
+    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
+                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
+        if tuple(t.shape) != want or n_stops < 0:
+            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
+    if program is not None and program[1].dim() != 1:
+        raise ValueError(f"opacity_t is (n_opacities,), not {tuple(program[1].shape)}")
+    return named, n_stops
 
-        @staticmethod
-        def forward(fn, planes, paints, m6, geom, pos, rgba, out, bg, origin, topo):
-            ctx = _context(torch)
-            n_paths, rows, cols = (int(v) for v in planes.shape)
-            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
-            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba))
-            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
-            desc, _keep = _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]))
-            with _Ordered(ctx, torch):
-                b = _buffers(ctx, torch, *kept, image)
-                _abi._check(ctx.lib.svgr_compose_painted_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
-            fn.save_for_backward(*kept)
-            fn.painted_args = (plane, bg, origin, topo)
-            if out is not None:
-                fn.mark_dirty(out)
-            return image
 
-        @staticmethod
-        @torch.autograd.function.once_differentiable
-        def backward(fn, grad):
-            kept = fn.saved_tensors
-            plane, bg, origin, topo = fn.painted_args
-            n_paths, rows, cols = (int(v) for v in kept[0].shape)
-            ctx = _context(torch)
-            grad = grad.contiguous()
-            if grad.data_ptr() % 16:
-                grad = grad.clone(memory_format=torch.contiguous_format)
-            grads = tuple(torch.empty_like(t) for t in kept)
-            desc, _keep = _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]))
-            with _Ordered(ctx, torch):
-                b = _buffers(ctx, torch, *kept, grad, *grads)
-                _abi._check(ctx.lib.svgr_compose_painted_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
-            need = fn.needs_input_grad
-            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 4
-
-    return ComposePainted
+def _tensor_places(torch, named, planes, out):
+    """Every tensor of ``named`` on ``planes``' device, which is the library's context's; ``out``, if given, fit for the image."""
+    ctx = _context(torch)
+    for name, t, _k in named:
+        if t.device != planes.device or t.device.index != ctx.device:
+            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
+    if out is not None:
+        shape = (int(planes.shape[1]), int(planes.shape[2]), 4)
+        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != shape or not out.is_contiguous() \
+                or out.device != planes.device or out.data_ptr() % 16:
+            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {shape} on {planes.device}, aligned to 16 bytes")
 
 
 def compose_painted_tensor(planes, paints_t, gp_t, *, bg=None, origin=(0, 0), out=None):
@@ -818,35 +791,13 @@ def compose_painted_tensor(planes, paints_t, gp_t, *, bg=None, origin=(0, 0), ou
     VALUES are not looked at.  Degenerate ones -- ``p0 == p1``, ``r <= 0``, non-finite numbers, decreasing stop positions -- give
     NaN, infinities or a wrong stop, not an error."""
     torch = _torch()
-    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
-        raise TypeError("gp_t is a GradientPaints")
-    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
-        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS)
-    for name, t, kinds in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
-        if t.dtype not in kinds or not t.is_cuda:
-            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
-    if planes.dim() != 3 or min(planes.shape) < 1:
-        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    named, n_stops = _tensor_args(torch, planes, paints_t, gp_t)
     n_paths, rows, cols = (int(v) for v in planes.shape)
-    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
-    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
-                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
-        if tuple(t.shape) != want or n_stops < 0:
-            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
     _n_pixels(n_paths, (0, 0, rows, cols))
     topo = _painted_topology(gp_t, n_paths, n_stops)
     bg, origin = _compose_bg(bg), _origin(origin)
-    ctx = _context(torch)
-    for name, t, _k in named:
-        if t.device != planes.device or t.device.index != ctx.device:
-            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
-                or out.device != planes.device or out.data_ptr() % 16:
-            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
-    return _painted_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, out, bg, origin, topo)
+    _tensor_places(torch, named, planes, out)
+    return _tier_function(torch, "painted").apply(out, (bg, origin, topo), *(t for _n, t, _k in named))
 
 
 def render_painted_tensor(segs, m6, paints, gp, *, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
@@ -941,9 +892,8 @@ def group_program(tree):
                   np.array(opacity, dtype=np.float64))
 
 
-def _group_topology(groups, n_paths, n_opacities):
-    """items, clip_off and clip_planes on the host, checked as svgr_compose_grouped_forward checks them: (three int32 arrays,
-    n_groups)."""
+def _program_tables(groups):
+    """items, clip_off and clip_planes of a program as int64 arrays of the right dimensions."""
     if not isinstance(groups, Groups):
         raise TypeError("groups is a Groups")
     out = []
@@ -961,6 +911,36 @@ def _group_topology(groups, n_paths, n_opacities):
         raise ValueError(f"a program has at most {MAX_ITEMS} items")
     if clip_off.ndim != 1 or clip_planes.ndim != 1:
         raise ValueError("groups.clip_off and groups.clip_planes are lists of integers")
+    return items, clip_off, clip_planes
+
+
+def _program_uses(items, clip_off, clip_planes, planes, slots, clips):
+    """What is left to check once a program's items are walked: the opacity slots, the clips and the planes' uses, counted in
+    ``slots``, ``clips`` and ``planes``.  The three tables as the ABI takes them."""
+    n_paths = len(planes)
+    if (slots != 1).any():
+        raise ValueError("every opacity slot is used by exactly one group")
+    if sorted(clips) != list(range(len(clips))):
+        raise ValueError(f"the {len(clips)} clips are numbered from 0")
+    if clips or len(clip_planes):
+        count = np.diff(clip_off)
+        if len(clip_off) != len(clips) + 1 or clip_off[0] != 0 or clip_off[-1] != len(clip_planes) or (count < 1).any():
+            raise ValueError("groups.clip_off is n_clips + 1 strictly ascending integers from 0 to the number of clip planes")
+        if ((clip_planes < 0) | (clip_planes >= n_paths)).any():
+            raise ValueError(f"a clip plane is not one of {n_paths}")
+        np.add.at(planes, clip_planes, 1)
+    if (planes != 1).any():
+        p = int(np.nonzero(planes != 1)[0][0])
+        raise ValueError(f"plane {p} is used {int(planes[p])} times: every plane is used exactly once, by a FILL or as a clip plane")
+    if len(clip_off) == 0:
+        clip_off = np.zeros(1, dtype=np.int64)
+    return np.ascontiguousarray(items, dtype=np.int32), clip_off.astype(np.int32), clip_planes.astype(np.int32)
+
+
+def _group_topology(groups, n_paths, n_opacities):
+    """items, clip_off and clip_planes on the host, checked as svgr_compose_grouped_forward checks them: (three int32 arrays,
+    n_groups)."""
+    items, clip_off, clip_planes = _program_tables(groups)
     depth_max = group_depth()
     planes, slots, clips = np.zeros(n_paths, dtype=np.int64), np.zeros(n_opacities, dtype=np.int64), {}
     stack, n_groups = [], 0
@@ -992,44 +972,36 @@ def _group_topology(groups, n_paths, n_opacities):
             raise ValueError(f"item {i}: unknown op {op} (0 FILL, 1 BEGIN, 2 END)")
     if stack:
         raise ValueError(f"item {stack[-1]}: the group is not closed")
-    if (slots != 1).any():
-        raise ValueError("every opacity slot is used by exactly one group")
-    if sorted(clips) != list(range(len(clips))):
-        raise ValueError(f"the {len(clips)} clips are numbered from 0")
-    if clips or len(clip_planes):
-        count = np.diff(clip_off)
-        if len(clip_off) != len(clips) + 1 or clip_off[0] != 0 or clip_off[-1] != len(clip_planes) or (count < 1).any():
-            raise ValueError("groups.clip_off is n_clips + 1 strictly ascending integers from 0 to the number of clip planes")
-        if ((clip_planes < 0) | (clip_planes >= n_paths)).any():
-            raise ValueError(f"a clip plane is not one of {n_paths}")
-        np.add.at(planes, clip_planes, 1)
-    if (planes != 1).any():
-        p = int(np.nonzero(planes != 1)[0][0])
-        raise ValueError(f"plane {p} is used {int(planes[p])} times: every plane is used exactly once, by a FILL or as a clip plane")
-    if len(clip_off) == 0:
-        clip_off = np.zeros(1, dtype=np.int64)
-    return (np.ascontiguousarray(items, dtype=np.int32), clip_off.astype(np.int32), clip_planes.astype(np.int32)), n_groups
+    return _program_uses(items, clip_off, clip_planes, planes, slots, clips), n_groups
 
 
 def _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, gtopo, n_groups, n_opacities):
     """(svgr_grouped_desc, what it points at)."""
-    d = _abi.GroupedDesc()
-    d.n_paths, d.rows, d.cols, d.plane, d.has_bg = n_paths, rows, cols, plane, int(bg is not None)
-    d.bg = (C.c_double * 4)(*(bg if bg is not None else (0.0,) * 4))
-    d.row0, d.col0, d.n_stops = origin[0], origin[1], n_stops
-    d.kind, d.spread, d.path_stop_off = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in topo)
+    d, _topo = _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, _abi.GroupedDesc)
     d.n_items, d.n_groups, d.n_clip_planes, d.n_opacities = len(gtopo[0]), n_groups, len(gtopo[2]), n_opacities
     d.items, d.clip_off, d.clip_planes = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in gtopo)
     return d, (topo, gtopo)
 
 
-def _grouped_inputs(cover, paints, gp, groups, bg, origin, dtype=None):
+# The painted, grouped and masked entries are one binding in three tiers ("painted", "grouped", "masked": the word in the ABI's
+# entry names).  The painted tier has no program: its opacity and gtopo are None, its n_groups 0.
+def _tier_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, gtopo=None, n_groups=0, n_opacities=0):
+    """The tier's description: ``_painted_desc`` without a program, ``_grouped_desc`` with one."""
+    if gtopo is None:
+        return _painted_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops)
+    return _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, n_stops, gtopo, n_groups, n_opacities)
+
+
+def _tier_inputs(tier, cover, paints, gp, groups, bg, origin, dtype=None):
+    """``_painted_inputs`` and, for "grouped" and "masked", the tier's program, checked."""
     cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
+    if tier == "painted":
+        return cover, paints, bg, origin, topo, arrays, None, None, 0
     if not isinstance(groups, Groups):
         raise TypeError("groups is a Groups")
     opacity = groups.opacity
     if _is_tensor(opacity):
-        raise TypeError("groups.opacity is a numpy array here; compose_grouped_tensor takes a tensor")
+        raise TypeError(f"groups.opacity is a numpy array here; compose_{tier}_tensor takes a tensor")
     if isinstance(opacity, np.ndarray) and opacity.size and opacity.dtype != np.float64:
         raise TypeError(f"groups.opacity is float64, not {opacity.dtype}")
     try:
@@ -1040,8 +1012,48 @@ def _grouped_inputs(cover, paints, gp, groups, bg, origin, dtype=None):
         raise ValueError(f"groups.opacity is (n_opacities,), not {opacity.shape}")
     if not np.isfinite(opacity).all():
         raise ValueError("groups.opacity must be finite")
-    gtopo, n_groups = _group_topology(groups, len(cover), len(opacity))
+    gtopo, n_groups = _PROGRAM_TOPOLOGY[tier](groups, len(cover), len(opacity))
     return cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups
+
+
+def _tier_forward(tier, cover, paints, gp, groups, bg, origin, dtype):
+    """``compose_painted``, ``compose_grouped`` or ``compose_masked``: svgr_compose_<tier>_forward on numpy arrays."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _tier_inputs(tier, cover, paints, gp, groups, bg, origin, dtype)
+    n_paths, rows, cols = cover.shape
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    ctx = _abi.Context.get()
+    ins, n_op = (arrays, 0) if opacity is None else (arrays + [opacity], len(opacity))
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in ins]
+    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
+    desc, _keep = _tier_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]), gtopo, n_groups, n_op)
+    _abi._check(getattr(ctx.lib, f"svgr_compose_{tier}_forward")(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
+    return image.download((rows, cols, 4), cover.dtype)
+
+
+def _tier_backward(tier, cover, paints, gp, groups, grad_image, bg, origin):
+    """``compose_painted_backward``, ``compose_grouped_backward`` or ``compose_masked_backward``: svgr_compose_<tier>_backward on
+    numpy arrays.  ``grad_opacity`` ends the result of the tiers that have opacities."""
+    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _tier_inputs(tier, cover, paints, gp, groups, bg, origin)
+    n_paths, rows, cols = cover.shape
+    grad_image = np.asarray(grad_image)
+    if grad_image.dtype != cover.dtype:
+        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
+    if grad_image.shape != (rows, cols, 4):
+        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
+    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
+    n_stops = len(arrays[2])
+    ins, n_op = (arrays, 0) if opacity is None else (arrays + [opacity], len(opacity))
+    ctx = _abi.Context.get()
+    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in ins]
+    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
+    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4)) + (() if opacity is None else ((n_op,),))
+    g_cover = ctx.alloc(cover.nbytes)
+    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]   # (no stops, no opacities: no buffers for them)
+    desc, _keep = _tier_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops, gtopo, n_groups, n_op)
+    entry = getattr(ctx.lib, f"svgr_compose_{tier}_backward")
+    _abi._check(entry(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
+    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
+    return (g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:5]), *got[5:])
 
 
 def compose_grouped(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=None):
@@ -1053,15 +1065,7 @@ def compose_grouped(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=Non
     ``gp`` of a clip plane are ignored.  Groups nest at most ``group_depth()`` deep.  A program without groups gives
     ``compose_painted``'s bits.  Everything ``compose_painted`` refuses, non-finite opacities and every error of the program are
     refused before any device work."""
-    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _grouped_inputs(cover, paints, gp, groups, bg, origin, dtype)
-    n_paths, rows, cols = cover.shape
-    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
-    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
-    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]), gtopo, n_groups, len(opacity))
-    _abi._check(ctx.lib.svgr_compose_grouped_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
-    return image.download((rows, cols, 4), cover.dtype)
+    return _tier_forward("grouped", cover, paints, gp, groups, bg, origin, dtype)
 
 
 def compose_grouped_backward(cover, paints, gp, groups, grad_image, bg=None, origin=(0, 0)):
@@ -1072,45 +1076,32 @@ def compose_grouped_backward(cover, paints, gp, groups, grad_image, bg=None, ori
     ``grad_paints`` and ``grad_gp`` are ``compose_painted_backward``'s (the rows of clip planes are 0); ``grad_opacity`` is float64
     ``(n_opacities,)``.  Nothing is divided: an opacity or a mask of 0, an opaque and an empty group are ordinary values.  No
     atomics: the same bits on every run."""
-    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _grouped_inputs(cover, paints, gp, groups, bg, origin)
-    n_paths, rows, cols = cover.shape
-    grad_image = np.asarray(grad_image)
-    if grad_image.dtype != cover.dtype:
-        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
-    if grad_image.shape != (rows, cols, 4):
-        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
-    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
-    n_stops, n_op = len(arrays[2]), len(opacity)
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
-    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
-    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4), (n_op,))
-    g_cover = ctx.alloc(cover.nbytes)
-    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]
-    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops, gtopo, n_groups, n_op)
-    _abi._check(ctx.lib.svgr_compose_grouped_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
-    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
-    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:5]), got[5]
+    return _tier_backward("grouped", cover, paints, gp, groups, grad_image, bg, origin)
 
 
 @functools.lru_cache(maxsize=None)
-def _grouped_function(torch):
-    class ComposeGrouped(torch.autograd.Function):
-        """image = ComposeGrouped.apply(planes, paints, m6, geom, stop_pos, stop_rgba, opacity, out, bg, origin, topo, gtopo, n_groups)."""
+def _tier_function(torch, tier):
+    """The ``torch.autograd.Function`` of a tier, one class per tier: ComposePainted, ComposeGrouped, ComposeMasked."""
+    def description(kept, plane, static):   # static: (bg, origin, topo) and, with a program, (gtopo, n_groups)
+        n_paths, rows, cols = (int(v) for v in kept[0].shape)
+        return _tier_desc(n_paths, rows, cols, plane, *static[:3], int(kept[4].shape[0]), *static[3:], *(int(t.shape[0]) for t in kept[6:]))
+
+    class ComposeTier(torch.autograd.Function):
+        """image = ComposeTier.apply(out, static, planes, paints, m6, geom, stop_pos, stop_rgba[, opacity])."""
 
         @staticmethod
-        def forward(fn, planes, paints, m6, geom, pos, rgba, opacity, out, bg, origin, topo, gtopo, n_groups):
+        def forward(fn, out, static, *tensors):
             ctx = _context(torch)
-            n_paths, rows, cols = (int(v) for v in planes.shape)
+            planes = tensors[0]
             plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
-            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba, opacity))
-            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
-            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]), gtopo, n_groups, int(opacity.shape[0]))
+            kept = tuple(t.detach().contiguous() for t in tensors)
+            image = out if out is not None else torch.empty((*planes.shape[1:], 4), dtype=planes.dtype, device=planes.device)
+            desc, _keep = description(kept, plane, static)
             with _Ordered(ctx, torch):
                 b = _buffers(ctx, torch, *kept, image)
-                _abi._check(ctx.lib.svgr_compose_grouped_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+                _abi._check(getattr(ctx.lib, f"svgr_compose_{tier}_forward")(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
             fn.save_for_backward(*kept)
-            fn.grouped_args = (plane, bg, origin, topo, gtopo, n_groups)
+            fn.tier_args = (plane, static)
             if out is not None:
                 fn.mark_dirty(out)
             return image
@@ -1119,21 +1110,20 @@ def _grouped_function(torch):
         @torch.autograd.function.once_differentiable
         def backward(fn, grad):
             kept = fn.saved_tensors
-            plane, bg, origin, topo, gtopo, n_groups = fn.grouped_args
-            n_paths, rows, cols = (int(v) for v in kept[0].shape)
             ctx = _context(torch)
             grad = grad.contiguous()
             if grad.data_ptr() % 16:
                 grad = grad.clone(memory_format=torch.contiguous_format)
             grads = tuple(torch.empty_like(t) for t in kept)
-            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]), gtopo, n_groups, int(kept[6].shape[0]))
+            desc, _keep = description(kept, *fn.tier_args)
             with _Ordered(ctx, torch):
                 b = _buffers(ctx, torch, *kept, grad, *grads)
-                _abi._check(ctx.lib.svgr_compose_grouped_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
-            need = fn.needs_input_grad
-            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 6
+                _abi._check(getattr(ctx.lib, f"svgr_compose_{tier}_backward")(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
+            need = fn.needs_input_grad[2:]
+            return (None, None) + tuple(g if need[i] else None for i, g in enumerate(grads))
 
-    return ComposeGrouped
+    ComposeTier.__name__ = ComposeTier.__qualname__ = f"Compose{tier.capitalize()}"
+    return ComposeTier
 
 
 def compose_grouped_tensor(planes, paints_t, gp_t, groups, opacity_t, *, bg=None, origin=(0, 0), out=None):
@@ -1144,42 +1134,20 @@ def compose_grouped_tensor(planes, paints_t, gp_t, groups, opacity_t, *, bg=None
     a float64 ``(n_opacities,)`` CUDA tensor.  Any of the seven tensors may require grad.  ``bg``, ``origin``, ``out``, the stream
     ordering and the import-order rule (``tensor.IMPORT_ORDER``) are ``compose_painted_tensor``'s.  Only the program, shapes, dtypes
     and devices are checked: there is no host wait, so the VALUES are not looked at."""
+    return _program_tensor("grouped", planes, paints_t, gp_t, groups, opacity_t, bg, origin, out)
+
+
+def _program_tensor(tier, planes, paints_t, gp_t, groups, opacity_t, bg, origin, out):
+    """``compose_grouped_tensor`` or ``compose_masked_tensor``: the checks, then the tier's ``torch.autograd.Function``."""
     torch = _torch()
-    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
-        raise TypeError("gp_t is a GradientPaints")
-    if not isinstance(groups, Groups):
-        raise TypeError("groups is a Groups")
-    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
-        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS) + (("opacity_t", opacity_t, (torch.float64,)),)
-    for name, t, kinds in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
-        if t.dtype not in kinds or not t.is_cuda:
-            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
-    if planes.dim() != 3 or min(planes.shape) < 1:
-        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
+    named, n_stops = _tensor_args(torch, planes, paints_t, gp_t, (groups, opacity_t))
     n_paths, rows, cols = (int(v) for v in planes.shape)
-    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
-    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
-                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
-        if tuple(t.shape) != want or n_stops < 0:
-            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
-    if opacity_t.dim() != 1:
-        raise ValueError(f"opacity_t is (n_opacities,), not {tuple(opacity_t.shape)}")
     topo = _painted_topology(gp_t, n_paths, n_stops)
-    gtopo, n_groups = _group_topology(groups, n_paths, int(opacity_t.shape[0]))
+    gtopo, n_groups = _PROGRAM_TOPOLOGY[tier](groups, n_paths, int(opacity_t.shape[0]))
     _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
     bg, origin = _compose_bg(bg), _origin(origin)
-    ctx = _context(torch)
-    for name, t, _k in named:
-        if t.device != planes.device or t.device.index != ctx.device:
-            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
-                or out.device != planes.device or out.data_ptr() % 16:
-            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
-    return _grouped_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, opacity_t, out, bg, origin, topo, gtopo,
-                                          n_groups)
+    _tensor_places(torch, named, planes, out)
+    return _tier_function(torch, tier).apply(out, (bg, origin, topo, gtopo, n_groups), *(t for _n, t, _k in named))
 
 
 def render_grouped_tensor(segs, m6, paints, gp, opacity, *, groups, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
@@ -1244,23 +1212,7 @@ def mask_program(tree):
 
 def _mask_topology(groups, n_paths, n_opacities):
     """``_group_topology`` for a program that may hold masked pairs, checked as svgr_compose_masked_forward checks it."""
-    if not isinstance(groups, Groups):
-        raise TypeError("groups is a Groups")
-    out = []
-    for name, a in (("items", groups.items), ("clip_off", groups.clip_off), ("clip_planes", groups.clip_planes)):
-        if _is_tensor(a):
-            raise TypeError(f"groups.{name} stays on the host: a numpy array or a list")
-        a = np.asarray(a)
-        if a.size and a.dtype.kind not in "iu":
-            raise TypeError(f"groups.{name} holds integers, not {a.dtype}")
-        out.append(np.ascontiguousarray(a.astype(np.int64)))
-    items, clip_off, clip_planes = out
-    if items.ndim != 2 or items.shape[1] != 4 or len(items) < 1:
-        raise ValueError(f"groups.items is (n_items, 4) with at least one item, not {items.shape}")
-    if len(items) > MAX_ITEMS:
-        raise ValueError(f"a program has at most {MAX_ITEMS} items")
-    if clip_off.ndim != 1 or clip_planes.ndim != 1:
-        raise ValueError("groups.clip_off and groups.clip_planes are lists of integers")
+    items, clip_off, clip_planes = _program_tables(groups)
     depth_max = group_depth()
     planes, slots, clips = np.zeros(n_paths, dtype=np.int64), np.zeros(n_opacities, dtype=np.int64), {}
     stack, n_groups = [], 0   # the stack holds (index of the BEGIN, op of the closer it names)
@@ -1306,44 +1258,10 @@ def _mask_topology(groups, n_paths, n_opacities):
             raise ValueError(f"item {i}: unknown op {op} (0 FILL, 1 BEGIN, 2 END, 3 HOLD, 4 END_MASK)")
     if stack:
         raise ValueError(f"item {stack[-1][0]}: the group is not closed")
-    if (slots != 1).any():
-        raise ValueError("every opacity slot is used by exactly one group")
-    if sorted(clips) != list(range(len(clips))):
-        raise ValueError(f"the {len(clips)} clips are numbered from 0")
-    if clips or len(clip_planes):
-        count = np.diff(clip_off)
-        if len(clip_off) != len(clips) + 1 or clip_off[0] != 0 or clip_off[-1] != len(clip_planes) or (count < 1).any():
-            raise ValueError("groups.clip_off is n_clips + 1 strictly ascending integers from 0 to the number of clip planes")
-        if ((clip_planes < 0) | (clip_planes >= n_paths)).any():
-            raise ValueError(f"a clip plane is not one of {n_paths}")
-        np.add.at(planes, clip_planes, 1)
-    if (planes != 1).any():
-        p = int(np.nonzero(planes != 1)[0][0])
-        raise ValueError(f"plane {p} is used {int(planes[p])} times: every plane is used exactly once, by a FILL or as a clip plane")
-    if len(clip_off) == 0:
-        clip_off = np.zeros(1, dtype=np.int64)
-    return (np.ascontiguousarray(items, dtype=np.int32), clip_off.astype(np.int32), clip_planes.astype(np.int32)), n_groups
+    return _program_uses(items, clip_off, clip_planes, planes, slots, clips), n_groups
 
 
-def _masked_inputs(cover, paints, gp, groups, bg, origin, dtype=None):
-    cover, paints, bg, origin, topo, arrays = _painted_inputs(cover, paints, gp, bg, origin, dtype)
-    if not isinstance(groups, Groups):
-        raise TypeError("groups is a Groups")
-    opacity = groups.opacity
-    if _is_tensor(opacity):
-        raise TypeError("groups.opacity is a numpy array here; compose_masked_tensor takes a tensor")
-    if isinstance(opacity, np.ndarray) and opacity.size and opacity.dtype != np.float64:
-        raise TypeError(f"groups.opacity is float64, not {opacity.dtype}")
-    try:
-        opacity = np.ascontiguousarray(opacity, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError("groups.opacity is an array of doubles") from None
-    if opacity.ndim != 1:
-        raise ValueError(f"groups.opacity is (n_opacities,), not {opacity.shape}")
-    if not np.isfinite(opacity).all():
-        raise ValueError("groups.opacity must be finite")
-    gtopo, n_groups = _mask_topology(groups, len(cover), len(opacity))
-    return cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups
+_PROGRAM_TOPOLOGY = {"grouped": _group_topology, "masked": _mask_topology}   # the host check of a tier's program
 
 
 def compose_masked(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=None):
@@ -1354,15 +1272,7 @@ def compose_masked(cover, paints, gp, groups, bg=None, origin=(0, 0), dtype=None
     ``0.2125 r + 0.7154 g + 0.072 b``).  The mask's group counts as a group: towards ``group_depth()`` and in the limits.  A
     program without masks gives ``compose_grouped``'s bits.  Everything ``compose_grouped`` refuses and every wrong pairing of
     HOLD and END_MASK are refused before any device work."""
-    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _masked_inputs(cover, paints, gp, groups, bg, origin, dtype)
-    n_paths, rows, cols = cover.shape
-    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
-    image = ctx.alloc(rows * cols * 4 * cover.dtype.itemsize)
-    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, len(arrays[2]), gtopo, n_groups, len(opacity))
-    _abi._check(ctx.lib.svgr_compose_masked_forward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], image.handle))
-    return image.download((rows, cols, 4), cover.dtype)
+    return _tier_forward("masked", cover, paints, gp, groups, bg, origin, dtype)
 
 
 def compose_masked_backward(cover, paints, gp, groups, grad_image, bg=None, origin=(0, 0)):
@@ -1373,110 +1283,14 @@ def compose_masked_backward(cover, paints, gp, groups, grad_image, bg=None, orig
     takes the forward's branch, a clip to [0, 1] passes the gradient at 0 and at 1 (an opaque white mask still moves its paint).
     The only division is by an alpha above 1e-4: every finite input, a mask canvas of 0 included, gives finite gradients.  No
     atomics: the same bits on every run."""
-    cover, paints, bg, origin, topo, arrays, opacity, gtopo, n_groups = _masked_inputs(cover, paints, gp, groups, bg, origin)
-    n_paths, rows, cols = cover.shape
-    grad_image = np.asarray(grad_image)
-    if grad_image.dtype != cover.dtype:
-        raise TypeError(f"grad_image is {cover.dtype} like cover, not {grad_image.dtype}")
-    if grad_image.shape != (rows, cols, 4):
-        raise ValueError(f"grad_image is {(rows, cols, 4)}, not {grad_image.shape}")
-    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
-    n_stops, n_op = len(arrays[2]), len(opacity)
-    ctx = _abi.Context.get()
-    bufs = [ctx.from_host(cover), ctx.from_host(paints)] + [ctx.from_host(a) if a.size else None for a in arrays + [opacity]]
-    bufs.append(ctx.from_host(np.ascontiguousarray(grad_image)))
-    shapes = ((n_paths, 4), (n_paths, 6), (n_paths, 4), (n_stops,), (n_stops, 4), (n_op,))
-    g_cover = ctx.alloc(cover.nbytes)
-    outs = [ctx.alloc(int(np.prod(s)) * 8) if s[0] else None for s in shapes]
-    desc, _keep = _grouped_desc(n_paths, rows, cols, _PLANES[cover.dtype], bg, origin, topo, n_stops, gtopo, n_groups, n_op)
-    _abi._check(ctx.lib.svgr_compose_masked_backward(ctx.handle, C.byref(desc), *[_h(b) for b in bufs], g_cover.handle, *[_h(b) for b in outs]))
-    got = [b.download(s, np.float64) if b is not None else np.zeros(s) for b, s in zip(outs, shapes)]
-    return g_cover.download(cover.shape, cover.dtype), got[0], GradientPaints(topo[0], topo[1], topo[2], *got[1:5]), got[5]
-
-
-@functools.lru_cache(maxsize=None)
-def _masked_function(torch):
-    class ComposeMasked(torch.autograd.Function):
-        """image = ComposeMasked.apply(planes, paints, m6, geom, stop_pos, stop_rgba, opacity, out, bg, origin, topo, gtopo, n_groups)."""
-
-        @staticmethod
-        def forward(fn, planes, paints, m6, geom, pos, rgba, opacity, out, bg, origin, topo, gtopo, n_groups):
-            ctx = _context(torch)
-            n_paths, rows, cols = (int(v) for v in planes.shape)
-            plane = _abi.COVER_F64 if planes.dtype == torch.float64 else _abi.COVER_F32
-            kept = tuple(t.detach().contiguous() for t in (planes, paints, m6, geom, pos, rgba, opacity))
-            image = out if out is not None else torch.empty((rows, cols, 4), dtype=planes.dtype, device=planes.device)
-            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(pos.shape[0]), gtopo, n_groups, int(opacity.shape[0]))
-            with _Ordered(ctx, torch):
-                b = _buffers(ctx, torch, *kept, image)
-                _abi._check(ctx.lib.svgr_compose_masked_forward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
-            fn.save_for_backward(*kept)
-            fn.masked_args = (plane, bg, origin, topo, gtopo, n_groups)
-            if out is not None:
-                fn.mark_dirty(out)
-            return image
-
-        @staticmethod
-        @torch.autograd.function.once_differentiable
-        def backward(fn, grad):
-            kept = fn.saved_tensors
-            plane, bg, origin, topo, gtopo, n_groups = fn.masked_args
-            n_paths, rows, cols = (int(v) for v in kept[0].shape)
-            ctx = _context(torch)
-            grad = grad.contiguous()
-            if grad.data_ptr() % 16:
-                grad = grad.clone(memory_format=torch.contiguous_format)
-            grads = tuple(torch.empty_like(t) for t in kept)
-            desc, _keep = _grouped_desc(n_paths, rows, cols, plane, bg, origin, topo, int(kept[4].shape[0]), gtopo, n_groups, int(kept[6].shape[0]))
-            with _Ordered(ctx, torch):
-                b = _buffers(ctx, torch, *kept, grad, *grads)
-                _abi._check(ctx.lib.svgr_compose_masked_backward(ctx.handle, C.byref(desc), *[_h(x) for x in b]))
-            need = fn.needs_input_grad
-            return tuple(g if need[i] else None for i, g in enumerate(grads)) + (None,) * 6
-
-    return ComposeMasked
+    return _tier_backward("masked", cover, paints, gp, groups, grad_image, bg, origin)
 
 
 def compose_masked_tensor(planes, paints_t, gp_t, groups, opacity_t, *, bg=None, origin=(0, 0), out=None):
     """``compose_masked`` as a ``torch.autograd.Function``, whose backward is ``compose_masked_backward``: the arguments, the
     checks (the program, shapes, dtypes and devices, never the values), ``out``, the stream ordering and the import-order rule are
     ``compose_grouped_tensor``'s; ``groups`` is a ``mask_program``."""
-    torch = _torch()
-    if not isinstance(gp_t, tuple) or len(gp_t) != 7:
-        raise TypeError("gp_t is a GradientPaints")
-    if not isinstance(groups, Groups):
-        raise TypeError("groups is a Groups")
-    named = (("planes", planes, (torch.float32, torch.float64)), ("paints_t", paints_t, (torch.float64,))) \
-        + tuple((f"gp_t.{name}", getattr(gp_t, name), (torch.float64,)) for name, _w in _GP_ARRAYS) + (("opacity_t", opacity_t, (torch.float64,)),)
-    for name, t, kinds in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} is a torch.Tensor, not {type(t).__name__}")
-        if t.dtype not in kinds or not t.is_cuda:
-            raise TypeError(f"{name} is a {' or '.join(str(k) for k in kinds)} tensor on the device, not {t.dtype} on {t.device}")
-    if planes.dim() != 3 or min(planes.shape) < 1:
-        raise ValueError(f"planes is (n_paths, rows, cols) with every side positive, not {tuple(planes.shape)}")
-    n_paths, rows, cols = (int(v) for v in planes.shape)
-    n_stops = int(gp_t.stop_pos.shape[0]) if gp_t.stop_pos.dim() == 1 else -1
-    for name, t, want in (("paints_t", paints_t, (n_paths, 4)), ("gp_t.m6", gp_t.m6, (n_paths, 6)), ("gp_t.geom", gp_t.geom, (n_paths, 4)),
-                          ("gp_t.stop_pos", gp_t.stop_pos, (max(n_stops, 0),)), ("gp_t.stop_rgba", gp_t.stop_rgba, (max(n_stops, 0), 4))):
-        if tuple(t.shape) != want or n_stops < 0:
-            raise ValueError(f"{name} is {want}, not {tuple(t.shape)}")
-    if opacity_t.dim() != 1:
-        raise ValueError(f"opacity_t is (n_opacities,), not {tuple(opacity_t.shape)}")
-    topo = _painted_topology(gp_t, n_paths, n_stops)
-    gtopo, n_groups = _mask_topology(groups, n_paths, int(opacity_t.shape[0]))
-    _n_pixels(max(n_paths, n_groups), (0, 0, rows, cols))
-    bg, origin = _compose_bg(bg), _origin(origin)
-    ctx = _context(torch)
-    for name, t, _k in named:
-        if t.device != planes.device or t.device.index != ctx.device:
-            raise ValueError(f"{name} is on {t.device}, planes on {planes.device}, the library's context on device {ctx.device}")
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != planes.dtype or tuple(out.shape) != (rows, cols, 4) or not out.is_contiguous() \
-                or out.device != planes.device or out.data_ptr() % 16:
-            raise ValueError(f"out is a contiguous {planes.dtype} tensor of shape {(rows, cols, 4)} on {planes.device}, aligned to 16 bytes")
-    return _masked_function(torch).apply(planes, paints_t, gp_t.m6, gp_t.geom, gp_t.stop_pos, gp_t.stop_rgba, opacity_t, out, bg, origin, topo, gtopo,
-                                         n_groups)
+    return _program_tensor("masked", planes, paints_t, gp_t, groups, opacity_t, bg, origin, out)
 
 
 def render_masked_tensor(segs, m6, paints, gp, opacity, *, groups, kinds, path_seg_off, rules, viewport, bg=None, dtype=None, check: bool = False,
